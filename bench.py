@@ -131,6 +131,36 @@ def pmc_explain(kernel, scene, cfg, launch_ms):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def cycle_outputs(ctx, r, ranks=None):
+    """What a caller of the controller cycle receives: the result record (float64; the cost stays float32) and,
+    when a trajectory was found, the winner's path and velocity profile (kc_dwa_get_best).  With ranks, the
+    rank that owns the winner supplies the path (a collective: every rank calls this)."""
+    out = {k: np.asarray(getattr(r, k), np.float32 if k == "cost" else np.float64) for k, _ in r._fields_}
+    best = None
+    if r.found and (ranks is None or ctx.owns_sample(r.raw_index)):
+        px, py, (bvx, bvy, bom) = ctx.get_best()
+        best = {"best_path_x": px, "best_path_y": py, "best_vx": bvx, "best_vy": bvy, "best_omega": bom}
+    if ranks is not None:
+        best = next((b for b in ranks.gather(best) if b is not None), None)
+    out.update(best or {})
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64, at most DUMP_LIMIT_BYTES in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(d / f"{name}.npy", a)
+
+
 def algorithmic_bytes(N, P, map_side, S, O):
     """16 B per trajectory-step (8 B x,y written by the
     roll-out + 8 B read back by the cost pass) + 20 B per sample (12 B velocity
@@ -286,6 +316,10 @@ def controller_bench(args, rank, world, local_rank):
     elapsed = time.perf_counter() - t0
     if use_dist:
         elapsed = ranks.max(elapsed)[0]
+    if args.dump_outputs:  # the last timed cycle's outputs, before anything else runs on the context
+        dumped = cycle_outputs(ctx, last, ranks)
+        if rank == 0:
+            write_outputs(args.dump_outputs, dumped)
     # ---- same cycles again with HIP events around every kernel, recorded on the
     # stream the kernels are launched on (roofline leg; events cost a few us per
     # cycle, so they stay out of `value`)
@@ -558,7 +592,8 @@ def fresh_inputs_leg(kh, syn, ctx, cfg, inp, pose, args):
                                   max_sensor_range=inp["max_range"], segment=(seg, sacc, inp["ref_len"]))
 
     n = int(ctx.sample_window(base["ctr"], lim, cur(0), max_lin, max_ang, want_list=False))
-    steps, warm = min(args.steps, 1000), min(args.warmup, 100)
+    # as the top-level line (--fresh) the leg runs exactly --steps; beside the headline it is capped
+    steps, warm = (args.steps, args.warmup) if args.fresh else (min(args.steps, 1000), min(args.warmup, 100))
     for i in range(warm):
         step4(i)
     t4 = time.perf_counter()
@@ -574,6 +609,8 @@ def fresh_inputs_leg(kh, syn, ctx, cfg, inp, pose, args):
         r = step(i)
         lat.append(time.perf_counter() - ts)
     elapsed = time.perf_counter() - t0
+    if args.fresh and args.dump_outputs:
+        write_outputs(args.dump_outputs, cycle_outputs(ctx, r))
     ctx.timing_enable(True)
     kernel_ms = {}
     for i in range(min(steps, 300)):
@@ -722,6 +759,8 @@ def laserscan_leg(ctx, cfg, inp, vx, vy, om, P, S, pose, args, beams=1440):
         r = ctx.cycle(pose(i), P)
         lat.append(time.perf_counter() - ts)
     elapsed = time.perf_counter() - t0
+    if args.scan and args.dump_outputs:
+        write_outputs(args.dump_outputs, cycle_outputs(ctx, r))
     ctx.timing_enable(True)
     kernel_ms = {}
     for i in range(min(args.steps, 500)):
@@ -1177,7 +1216,7 @@ def ref_cost5k_bench(args):
     ctx.set_weights(kh.make_weights(*w["weights"]))
     ctx.set_tracked_segment(w["seg"], w["acc"][w["s0"]:w["s0"] + S], w["total"])
     ctx.cost_upload(w["px"], w["py"], w["vel"])
-    steps, warm = min(args.steps, 200), min(args.warmup, 20)
+    steps, warm = args.steps, args.warmup
     for _ in range(warm):
         ctx.cost_evaluate_resident(with_costs=False)
     lat = []
@@ -1438,7 +1477,13 @@ def main():
                     help="with --dry-launch: this rank dies behind the rendezvous, its peers wait for ever (launcher limit test)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed cycle returned in its last step as DIR/<name>.npy (controller lines only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.mapper or args.pointcloud or args.ref or args.dry_launch):
+        ap.error("--dump-outputs covers the controller lines (the default, --fresh, --scan)")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
