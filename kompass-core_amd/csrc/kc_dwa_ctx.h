@@ -17,6 +17,7 @@
 #include <atomic>
 #include <cfloat>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <unordered_map>
@@ -363,6 +364,15 @@ struct kc_dwa {
 // cell up to 4 k points, hundreds per cell here); beyond: the host path, finer grid.  (262144 until a raw depth image --
 // 307 200 points -- was priced: 6 ms of host build at 500 k points against 0.16 ms here, tools/big_cloud_sweep.py.)
 constexpr size_t kSensorDeviceMax = 1048576;
+// sensor_points_kernel packs id | rank << 12 into an int (tcell): 12 bits of bucket id (kHistRow cells), and the rank of
+// a point among its workgroup's points in one cell, below kSensorBlock * ppt, with ppt the host's
+// ceil(n / (kHistRowsMax * kSensorBlock)).  At kSensorDeviceMax that is 64 k ranks: 28 bits.
+static_assert(kHistRow == 1 << 12, "the bucket id field of tcell is 12 bits");
+constexpr size_t kSensorRankMax =
+    (kSensorDeviceMax + static_cast<size_t>(kHistRowsMax) * kSensorBlock - 1) / (static_cast<size_t>(kHistRowsMax) * kSensorBlock) *
+        kSensorBlock - 1;
+static_assert(((kSensorRankMax << 12) | (kHistRow - 1)) <= static_cast<size_t>(INT_MAX),
+              "id | rank << 12 of the largest device point list must fit an int");
 constexpr int kTiltCrop = 4000;                // half side of the kept window of a cropped tilted scan, in voxel columns
 constexpr size_t kSensorFusedMax = 32768;       // points up to which the one-launch sensor build CAN be used (spheres: it is their only device build)
 constexpr size_t kSensorFusedPays = 18432;      // ... and up to which it is ahead: every workgroup reads every point (tools/big_cloud_sweep.py,

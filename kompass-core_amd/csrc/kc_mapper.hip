@@ -33,14 +33,34 @@ struct MapGeom {
 // table (the reference calls ::cos(double) on the float sum orient + angle).
 // Both passes recompute it (a handful of operations) instead of a third kernel
 // and an array in between.
-__device__ __forceinline__ int2 beam_endpoint(const MapGeom &g, float range, double2 cs) {
+// A beam is skipped -- no stamp at all -- when the cell offset x / res or
+// y / res of its end point is not below 2^30 in magnitude: NaN and inf (a NaN
+// or inf range or angle) included.  The reference's int conversion is
+// undefined there, and 2^30 is the longest line of its int Bresenham
+// (ddx = 2 dx).  DESIGN.md §5.
+constexpr float kMaxCellOffset = 1073741824.0f;  // 2^30
+constexpr int kSkippedEnd = INT_MIN;              // end cell (x) of a skipped beam in `ends`
+
+__device__ __forceinline__ bool beam_endpoint(const MapGeom &g, float range, double2 cs, int2 &t) {
   const double r = static_cast<double>(range);
   const float x = static_cast<float>(static_cast<double>(g.pos0) + r * cs.x);
   const float y = static_cast<float>(static_cast<double>(g.pos1) + r * cs.y);
-  int2 t;
-  t.x = g.c0 + static_cast<int>(kc::div_rn(x, g.res));  // trunc toward zero
-  t.y = g.c1 + static_cast<int>(kc::div_rn(y, g.res));
-  return t;
+  const float qx = kc::div_rn(x, g.res), qy = kc::div_rn(y, g.res);
+  if (!(fabsf(qx) < kMaxCellOffset && fabsf(qy) < kMaxCellOffset)) return false;
+  t.x = g.c0 + static_cast<int>(qx);  // trunc toward zero
+  t.y = g.c1 + static_cast<int>(qy);
+  return true;
+}
+
+// Steps [*lo, *hi] of the steps 1..n of a line whose stamps can land on the
+// major axis [0, A): step i stamps at major coordinate a0 + astep i or one step
+// back, so only a_i in [-1, A] matter -- every other stamp falls outside the
+// grid.  This bounds the work of a beam by the grid, not by its length.
+__device__ __forceinline__ void step_window(int a0, int astep, int A, int n, int &lo, int &hi) {
+  const long long l = astep > 0 ? -1LL - a0 : static_cast<long long>(a0) - A;
+  const long long h = astep > 0 ? static_cast<long long>(A) - a0 : a0 + 1LL;
+  lo = static_cast<int>(max(l, 1LL));
+  hi = static_cast<int>(min(h, static_cast<long long>(n)));
 }
 
 __device__ __forceinline__ void stamp_empty(int *grid, const MapGeom &g, int i,
@@ -65,25 +85,29 @@ __global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_kernel(
   const int beam = block * kBeamsPerBlock + (threadIdx.x >> 6);
   if (beam >= n) return;
   const int lane = threadIdx.x & 63;
-  const int2 t = beam_endpoint(g, ranges[beam], trig[beam]);
+  int2 t;
+  if (!beam_endpoint(g, ranges[beam], trig[beam], t)) return;
   int dx = t.x - g.s0, dy = t.y - g.s1;
   const int xstep = dx >= 0 ? 1 : -1, ystep = dy >= 0 ? 1 : -1;
   dx = abs(dx);
   dy = abs(dy);
   if (lane == 0) stamp_empty(grid, g, g.s0, g.s1);  // first emitted point
-  const bool xmajor = 2 * dx >= 2 * dy;
-  // tiled scan: only the first step_limit steps (the tiles own the rest)
-  const int nsteps = min(xmajor ? dx : dy, step_limit);
-  if (nsteps == 0) return;
+  const bool xmajor = dx >= dy;
   const long long dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
   const long long ddmaj = 2 * dmaj, ddmin = 2 * dmin;
   const int astep = xmajor ? xstep : ystep, bstep = xmajor ? ystep : xstep;
   const int a0 = xmajor ? g.s0 : g.s1, b0 = xmajor ? g.s1 : g.s0;
+  int ifirst, ilast;
+  step_window(a0, astep, xmajor ? g.H : g.W, xmajor ? dx : dy, ifirst, ilast);
+  // tiled scan: only the first step_limit steps (the tiles own the rest)
+  ilast = min(ilast, step_limit);
+  if (ifirst > ilast) return;
   // The 64 lanes take 64 CONSECUTIVE steps per trip (closed-form state before step i, as above): the stores of
   // an x-major line then fall into a few 64-byte lines of the column-major grid instead of 64 -- the L2's write
   // transactions, not the arithmetic, bound this pass (a contiguous chunk of steps per lane: 18.6 us at
   // 4096 beams x ~500 steps)
-  for (int i = lane + 1; i <= nsteps; i += 64) {
+  for (int c = lane; c <= ilast - ifirst; c += 64) {
+    const int i = ifirst + c;
     const long long eprev = dmaj + (long long)(i - 1) * ddmin;
     const long long k = static_cast<long long>(
         floor(static_cast<double>(eprev - 1) / static_cast<double>(ddmaj)));
@@ -141,20 +165,26 @@ __global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_bayes_kernel(
   if (beam >= n) return;
   const unsigned int tag = static_cast<unsigned int>(beam) + 1u;
   const int lane = threadIdx.x & 63;
-  const int2 t = beam_endpoint(g, ranges[beam], trig[beam]);
+  int2 t;
+  if (!beam_endpoint(g, ranges[beam], trig[beam], t)) return;
   int dx = t.x - g.s0, dy = t.y - g.s1;
   const int xstep = dx >= 0 ? 1 : -1, ystep = dy >= 0 ? 1 : -1;
   dx = abs(dx);
   dy = abs(dy);
   if (lane == 0 && step_first <= 1) stamp_tag(grid, last, tag, hb, g, g.s0, g.s1);  // first emitted point
-  const bool xmajor = 2 * dx >= 2 * dy;
-  const int nsteps = xmajor ? dx : dy;
+  const bool xmajor = dx >= dy;
   const long long dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
   const long long ddmaj = 2 * dmaj, ddmin = 2 * dmin;
   const int astep = xmajor ? xstep : ystep, bstep = xmajor ? ystep : xstep;
   const int a0 = xmajor ? g.s0 : g.s1, b0 = xmajor ? g.s1 : g.s0;
-  const int nwalk = min(nsteps, step_limit);
-  for (int i = lane + step_first; i <= nwalk; i += 64) {
+  int ifirst, ilast;
+  step_window(a0, astep, xmajor ? g.H : g.W, xmajor ? dx : dy, ifirst, ilast);
+  ifirst = max(ifirst, step_first);
+  ilast = min(ilast, step_limit);
+  if (ifirst > ilast) return;
+  // (a counter from 0: i += 64 near INT_MAX would overflow; the window is at most A + 2 steps)
+  for (int c = lane; c <= ilast - ifirst; c += 64) {
+    const int i = ifirst + c;
     const long long eprev = dmaj + (long long)(i - 1) * ddmin;
     const long long k = static_cast<long long>(
         floor(static_cast<double>(eprev - 1) / static_cast<double>(ddmaj)));
@@ -206,15 +236,21 @@ __device__ __forceinline__ int sector_of_angle(float a) {
   return min(max(s, 0), 63);
 }
 
-// ends[b] = end cell of beam b; behind the n end cells, one byte per beam: its sector
+// ends[b] = end cell of beam b (x = kSkippedEnd: a skipped beam); behind the n end cells, one byte per beam:
+// its sector
 __global__ void beam_ends_kernel(MapGeom g, const float *__restrict__ ranges,
                                  const double2 *__restrict__ trig, int n, int2 *__restrict__ ends) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < n) {
-    const int2 t = beam_endpoint(g, ranges[b], trig[b]);
+    int2 t;
+    uint8_t sector = 0;
+    if (beam_endpoint(g, ranges[b], trig[b], t))
+      sector = static_cast<uint8_t>(
+          sector_of_angle(atan2f(static_cast<float>(t.y - g.s1), static_cast<float>(t.x - g.s0))));
+    else
+      t = make_int2(kSkippedEnd, kSkippedEnd);
     ends[b] = t;
-    reinterpret_cast<uint8_t *>(ends + n)[b] = static_cast<uint8_t>(
-        sector_of_angle(atan2f(static_cast<float>(t.y - g.s1), static_cast<float>(t.x - g.s0))));
+    reinterpret_cast<uint8_t *>(ends + n)[b] = sector;
   }
 }
 
@@ -315,6 +351,7 @@ __device__ void tile_accumulate(const MapGeom &g, const int2 *__restrict__ ends,
       if (b >= b_end) continue;
       if (!((smask >> sect[b]) & 1ull)) continue;
       const int2 t = ends[b];
+      if (t.x == kSkippedEnd) continue;
       const int dx = t.x - g.s0, dy = t.y - g.s1;
       const double cross = static_cast<double>(dx) * cj - static_cast<double>(dy) * ci;
       if (fabs(cross) <= fabs(static_cast<double>(dy)) * hi + fabs(static_cast<double>(dx)) * hj) {
@@ -440,9 +477,13 @@ __global__ __launch_bounds__(kTileThreads) void near_tiles_kernel(
   if (b_begin >= b_end) return;
   for (int t = threadIdx.x; t < kTileI * kTileJ; t += kTileThreads) L.cell[t] = 0u;
   tile_accumulate<true>(g, ends, n, b_begin, b_end, 1, kNearSteps, I0, I1, J0, J1, L);
-  // the first emitted point of every beam is the start cell
-  if (threadIdx.x == 0 && g.s0 >= I0 && g.s0 <= I1 && g.s1 >= J0 && g.s1 <= J1)
-    atomicMax(&L.cell[(g.s0 - I0) + (g.s1 - J0) * kTileI], static_cast<unsigned int>(b_end));
+  // the first emitted point of every beam that is not skipped is the start cell: the tag of the slice's last
+  // such beam (one load unless the slice ends in skipped beams)
+  if (threadIdx.x == 0 && g.s0 >= I0 && g.s0 <= I1 && g.s1 >= J0 && g.s1 <= J1) {
+    int b = b_end - 1;
+    while (b >= b_begin && ends[b].x == kSkippedEnd) --b;
+    if (b >= b_begin) atomicMax(&L.cell[(g.s0 - I0) + (g.s1 - J0) * kTileI], static_cast<unsigned int>(b) + 1u);
+  }
   __syncthreads();
   for (int t = threadIdx.x; t < kTileI * kTileJ; t += kTileThreads) {
     const unsigned int v = L.cell[t];
@@ -468,8 +509,8 @@ __global__ void endpoints_kernel(MapGeom g, const float *__restrict__ ranges,
                                  int4 *__restrict__ clear, size_t clear_vec, int beam_blocks) {
   if (static_cast<int>(blockIdx.x) < beam_blocks) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n) {
-      const int2 t = beam_endpoint(g, ranges[b], trig[b]);
+    int2 t;
+    if (b < n && beam_endpoint(g, ranges[b], trig[b], t)) {
       if (t.x >= 0 && t.x < g.H && t.y >= 0 && t.y < g.W)
         grid[(size_t)t.x + (size_t)t.y * (size_t)g.H] = KC_OCCUPIED;
     }

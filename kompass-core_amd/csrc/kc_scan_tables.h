@@ -28,20 +28,22 @@ struct Place {
   float r10, r11, z1, t1;
 };
 
-// xyz[3 i ..] = {float(r cos), float(r sin), hz}; hx / hy = the placed obstacle; returns false when a range is
-// not finite (the outputs are complete either way)
+// xyz[3 i ..] = {float(r cos), float(r sin), hz}; hx / hy = the placed obstacle; returns false when a placed
+// obstacle is not finite (the outputs are complete either way).  Decided on the floats, not the ranges: a finite
+// range can still give an inf or NaN obstacle (1e39 or DBL_MAX rounds to inf as a float; inf - inf inside the
+// placement), and box_of must never see one -- _mm256_min_ps drops the other operand against a NaN.
 inline bool points_scalar(const double *ranges, const double *cosv, const double *sinv, size_t i0, size_t n, float hz,
                           const Place &p, float *xyz, float *hx, float *hy) {
   bool finite = true;
   for (size_t i = i0; i < n; ++i) {
     const double r = ranges[i];
-    finite = finite && std::isfinite(r);
     const float x = static_cast<float>(r * cosv[i]), y = static_cast<float>(r * sinv[i]);
     xyz[3 * i] = x;
     xyz[3 * i + 1] = y;
     xyz[3 * i + 2] = hz;
     hx[i] = p.t0 + (p.r00 * x + (p.r01 * y + p.z0));
     hy[i] = p.t1 + (p.r10 * x + (p.r11 * y + p.z1));
+    finite = finite && std::isfinite(hx[i]) && std::isfinite(hy[i]);
   }
   return finite;
 }
@@ -50,12 +52,10 @@ __attribute__((target("avx2"))) inline bool points_avx2(const double *ranges, co
   const __m128 r00 = _mm_set1_ps(p.r00), r01 = _mm_set1_ps(p.r01), z0 = _mm_set1_ps(p.z0), t0 = _mm_set1_ps(p.t0);
   const __m128 r10 = _mm_set1_ps(p.r10), r11 = _mm_set1_ps(p.r11), z1 = _mm_set1_ps(p.z1), t1 = _mm_set1_ps(p.t1);
   const __m128 vz = _mm_set1_ps(hz);
-  __m256d bad = _mm256_setzero_pd();
+  __m128 bad = _mm_setzero_ps();
   size_t i = 0;
   for (; i + 4 <= n; i += 4) {
     const __m256d r = _mm256_loadu_pd(ranges + i);
-    const __m256d d = _mm256_sub_pd(r, r);  // 0 for a finite range, NaN otherwise
-    bad = _mm256_or_pd(bad, _mm256_cmp_pd(d, d, _CMP_UNORD_Q));
     const __m128 x = _mm256_cvtpd_ps(_mm256_mul_pd(r, _mm256_loadu_pd(cosv + i)));
     const __m128 y = _mm256_cvtpd_ps(_mm256_mul_pd(r, _mm256_loadu_pd(sinv + i)));
     // x0 y0 z x1 | y1 z x2 y2 | z x3 y3 z
@@ -68,10 +68,14 @@ __attribute__((target("avx2"))) inline bool points_avx2(const double *ranges, co
     _mm_storeu_ps(xyz + 3 * i, v0);
     _mm_storeu_ps(xyz + 3 * i + 4, v1);
     _mm_storeu_ps(xyz + 3 * i + 8, v2);
-    _mm_storeu_ps(hx + i, _mm_add_ps(t0, _mm_add_ps(_mm_mul_ps(r00, x), _mm_add_ps(_mm_mul_ps(r01, y), z0))));
-    _mm_storeu_ps(hy + i, _mm_add_ps(t1, _mm_add_ps(_mm_mul_ps(r10, x), _mm_add_ps(_mm_mul_ps(r11, y), z1))));
+    const __m128 ox = _mm_add_ps(t0, _mm_add_ps(_mm_mul_ps(r00, x), _mm_add_ps(_mm_mul_ps(r01, y), z0)));
+    const __m128 oy = _mm_add_ps(t1, _mm_add_ps(_mm_mul_ps(r10, x), _mm_add_ps(_mm_mul_ps(r11, y), z1)));
+    _mm_storeu_ps(hx + i, ox);
+    _mm_storeu_ps(hy + i, oy);
+    const __m128 dx = _mm_sub_ps(ox, ox), dy = _mm_sub_ps(oy, oy);  // 0 for a finite obstacle, NaN otherwise
+    bad = _mm_or_ps(bad, _mm_or_ps(_mm_cmpunord_ps(dx, dx), _mm_cmpunord_ps(dy, dy)));
   }
-  const bool f = _mm256_movemask_pd(bad) == 0;
+  const bool f = _mm_movemask_ps(bad) == 0;
   return points_scalar(ranges, cosv, sinv, i, n, hz, p, xyz, hx, hy) && f;
 }
 inline bool points(const double *ranges, const double *cosv, const double *sinv, size_t n, float hz, const Place &p,

@@ -73,12 +73,12 @@ constexpr int kHistRow = 64 * 64;  // ints per row of the histogram matrix
 constexpr int kHistRowsMax = 16;   // the host picks points per thread so that the rows fit
 struct SensorBigArgs {
   SensorArgs a;
-  int ppt;          // points per thread (1 .. 16): a workgroup takes 1024 * ppt consecutive points
+  int ppt;          // points per thread (1 .. 64): a workgroup takes 1024 * ppt consecutive points
   int rows;         // workgroups of the points kernel = rows of hist
   int *hist;        // [rows][kHistRow] points per bucket of each workgroup
   uint8_t *bytes;   // [gH][gwpr * 32] zero on entry, zero again when sensor_place_kernel is done
   float *tox, *toy; // [n] transformed coordinates (scratch)
-  int *tcell;       // [n] cell id | rank inside its workgroup (< 16 k) << 12, -1: not an obstacle
+  int *tcell;       // [n] cell id | rank inside its workgroup (< 64 k) << 12, -1: not an obstacle
   unsigned long long *dbg;  // KC_PHASE_STAMPS builds: [16 workgroups][16] s_memrealtime stamps, or null
 };
 #ifdef KC_PHASE_STAMPS
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kSensorBlock) void sensor_points_kernel(SensorBigAr
     int id;
     int rec = -1;
     if (sensor_obstacle(a, x, y, a.obs_z_zero ? 0.0f : z, ox, oy, id)) {
-      rec = id | (atomicAdd(&lhist[id], 1) << 12);  // id < 4096 cells, rank < 16 k
+      rec = id | (atomicAdd(&lhist[id], 1) << 12);  // id < 4096 cells, rank < kSensorBlock * ppt (kc_dwa_ctx.h)
       b.tox[i] = ox;
       b.toy[i] = oy;
     }

@@ -1745,58 +1745,62 @@ static inline void grid_emit(grid_sink *s, int i, int j) {
   }
 }
 
-/* line_drawing.h:55-124 */
-static void bresenham_enhanced(int x0, int y0, int x1, int y1, grid_sink *s) {
-  int x = x0, y = y0;
-  int dx = x1 - x0, dy = y1 - y0;
-  grid_emit(s, x, y);
-  int xstep = (dx >= 0) ? 1 : -1;
-  int ystep = (dy >= 0) ? 1 : -1;
-  dx = abs(dx);
-  dy = abs(dy);
-  int ddy = 2 * dy, ddx = 2 * dx;
-  if (ddx >= ddy) {
-    int errorprev = dx, error = dx;
-    for (int i = 0; i < dx; i++) {
-      x += xstep;
-      error += ddy;
-      if (error > ddx) {
-        y += ystep;
-        error -= ddx;
-        if (error + errorprev < ddx) {
-          grid_emit(s, x, y - ystep);
-        } else if (error + errorprev > ddx) {
-          grid_emit(s, x - xstep, y);
-        } else {
-          grid_emit(s, x - xstep, y);
-          grid_emit(s, x, y - ystep);
-        }
-      }
-      grid_emit(s, x, y);
-      errorprev = error;
-    }
-  } else {
-    int errorprev = dy, error = dy;
-    for (int i = 0; i < dy; i++) {
-      y += ystep;
-      error += ddx;
-      if (error > ddy) {
-        x += xstep;
-        error -= ddy;
-        if (error + errorprev < ddy) {
-          grid_emit(s, x - xstep, y);
-        } else if (error + errorprev > ddy) {
-          grid_emit(s, x, y - ystep);
-        } else {
-          grid_emit(s, x - xstep, y);
-          grid_emit(s, x, y - ystep);
-        }
-      }
-      grid_emit(s, x, y);
-      errorprev = error;
-    }
-  }
+/* The rule where the reference is undefined: a beam whose cell
+ * offset x / res or y / res is not below 2^30 in magnitude -- NaN and inf
+ * included -- stamps nothing.  The reference's (int) conversion is undefined
+ * there, and 2^30 is the longest line of its int Bresenham (ddx = 2 * dx).
+ * Returns 0 for a skipped beam, else the end cell. */
+static int beam_end(float x, float y, float res, int c0, int c1, int *t0, int *t1) {
+  const float qx = x / res, qy = y / res;
+  if (!(fabsf(qx) < 0x1p30f && fabsf(qy) < 0x1p30f)) return 0;
+  *t0 = c0 + (int)qx;
+  *t1 = c1 + (int)qy;
+  return 1;
 }
+
+typedef void (*cell_fn)(void *sink, int i, int j);
+
+/* bresenhamEnhanced (line_drawing.h:55-124) from (x0, y0) to (x1, y1) on an
+ * H x W grid, in major / minor form with 64-bit error terms.  Only the steps
+ * whose stamps can land in the grid are walked: step i stamps at major
+ * coordinate a0 + astep i or one step back, so steps with a_i outside [-1, A]
+ * are no-ops, and the state before the first walked step i has the closed form
+ * e = n + (i - 1) ddmin, k = floor((e - 1) / ddmaj) minor steps, error = e -
+ * k ddmaj (the reference's error stays in [1, ddmaj]).  The reference emits, in
+ * major / minor terms, (a, b - bstep) below the line, (a - astep, b) above it,
+ * both on it; every stamp is a maximum, so the order does not matter. */
+static void bresenham_walk(int x0, int y0, int x1, int y1, int H, int W, cell_fn emit, void *s) {
+  emit(s, x0, y0);
+  const long long dx = llabs((long long)x1 - x0), dy = llabs((long long)y1 - y0);
+  const int xstep = (x1 >= x0) ? 1 : -1, ystep = (y1 >= y0) ? 1 : -1;
+  const int xmajor = dx >= dy;
+  const long long n = xmajor ? dx : dy, ddmaj = 2 * n, ddmin = 2 * (xmajor ? dy : dx);
+  const int astep = xmajor ? xstep : ystep, bstep = xmajor ? ystep : xstep;
+  const long long a0 = xmajor ? x0 : y0, b0 = xmajor ? y0 : x0, A = xmajor ? H : W;
+  long long lo = astep > 0 ? -1 - a0 : a0 - A, hi = astep > 0 ? A - a0 : a0 + 1;
+  if (lo < 1) lo = 1;
+  if (hi > n) hi = n;
+  if (lo > hi) return;
+  const long long e = n + (lo - 1) * ddmin, k = (e - 1) / ddmaj;
+  long long a = a0 + astep * (lo - 1), b = b0 + bstep * k;
+  long long error = e - k * ddmaj;
+#define KO_EMIT(am, bm) (xmajor ? emit(s, (int)(am), (int)(bm)) : emit(s, (int)(bm), (int)(am)))
+  for (long long i = lo; i <= hi; ++i) {
+    const long long errorprev = error;
+    a += astep;
+    error += ddmin;
+    if (error > ddmaj) {
+      b += bstep;
+      error -= ddmaj;
+      if (error + errorprev <= ddmaj) KO_EMIT(a, b - bstep);
+      if (error + errorprev >= ddmaj) KO_EMIT(a - astep, b);
+    }
+    KO_EMIT(a, b);
+  }
+#undef KO_EMIT
+}
+
+static void grid_cell(void *s, int i, int j) { grid_emit((grid_sink *)s, i, j); }
 
 int ko_mapper_scan_to_grid(int H, int W, float res, const float pos[3],
                            float orient, const double *angles,
@@ -1816,9 +1820,8 @@ int ko_mapper_scan_to_grid(int H, int W, float res, const float pos[3],
         (float)((double)pos[0] + ((double)range * cos((double)(orient + angle))));
     const float y =
         (float)((double)pos[1] + ((double)range * sin((double)(orient + angle))));
-    s.to0 = c0 + (int)(x / res);
-    s.to1 = c1 + (int)(y / res);
-    bresenham_enhanced(s0, s1, s.to0, s.to1, &s);
+    if (!beam_end(x, y, res, c0, c1, &s.to0, &s.to1)) continue;
+    bresenham_walk(s0, s1, s.to0, s.to1, H, W, grid_cell, &s);
   }
   return 0;
 }
@@ -1919,41 +1922,7 @@ static inline void bayes_emit(bayes_sink *s, int i, int j) {
   }
 }
 
-/* bresenhamEnhanced (line_drawing.h:55-124) feeding bayes_emit */
-static void bresenham_bayes(int x0, int y0, int x1, int y1, bayes_sink *s) {
-  int x = x0, y = y0;
-  int dx = x1 - x0, dy = y1 - y0;
-  bayes_emit(s, x, y);
-  const int xstep = (dx >= 0) ? 1 : -1, ystep = (dy >= 0) ? 1 : -1;
-  dx = abs(dx);
-  dy = abs(dy);
-  const int ddy = 2 * dy, ddx = 2 * dx;
-  const int xmajor = ddx >= ddy;
-  const int n = xmajor ? dx : dy, ddmaj = xmajor ? ddx : ddy, ddmin = xmajor ? ddy : ddx;
-  int errorprev = n, error = n;
-  for (int i = 0; i < n; i++) {
-    if (xmajor) x += xstep; else y += ystep;
-    error += ddmin;
-    if (error > ddmaj) {
-      if (xmajor) y += ystep; else x += xstep;
-      error -= ddmaj;
-      /* x-major emits (x, y-ystep) below the line and (x-xstep, y) above; the
-       * y-major branch mirrors that */
-      const int lo = xmajor ? (error + errorprev < ddmaj) : (error + errorprev > ddmaj);
-      const int hi = xmajor ? (error + errorprev > ddmaj) : (error + errorprev < ddmaj);
-      if (lo) {
-        bayes_emit(s, x, y - ystep);
-      } else if (hi) {
-        bayes_emit(s, x - xstep, y);
-      } else {
-        bayes_emit(s, x - xstep, y);
-        bayes_emit(s, x, y - ystep);
-      }
-    }
-    bayes_emit(s, x, y);
-    errorprev = error;
-  }
-}
+static void bayes_cell_fn(void *s, int i, int j) { bayes_emit((bayes_sink *)s, i, j); }
 
 /* LocalMapper::scanToGridBaysian, local_mapper.cpp:222-241 (single thread:
  * the last beam that crosses a cell decides its probability) */
@@ -1969,10 +1938,9 @@ int ko_bmap_scan(ko_bmap *b, const double *angles, const double *ranges, size_t 
         (float)((double)b->pos0 + ((double)range * cos((double)(b->orient + angle))));
     const float y =
         (float)((double)b->pos1 + ((double)range * sin((double)(b->orient + angle))));
-    s.g.to0 = b->c0 + (int)(x / b->res);
-    s.g.to1 = b->c1 + (int)(y / b->res);
+    if (!beam_end(x, y, b->res, b->c0, b->c1, &s.g.to0, &s.g.to1)) continue;
     s.range = range;
-    bresenham_bayes(b->s0, b->s1, s.g.to0, s.g.to1, &s);
+    bresenham_walk(b->s0, b->s1, s.g.to0, s.g.to1, b->H, b->W, bayes_cell_fn, &s);
   }
   return 0;
 }
