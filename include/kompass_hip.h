@@ -346,6 +346,14 @@ int kc_dwa_rollout(kc_dwa *ctx, const kc_state *start, size_t num_points);
  * occupied voxel. */
 int kc_dwa_check_poses(kc_dwa *ctx, const double *x, const double *y,
                        const double *yaw, size_t n, uint8_t *hit_out);
+/* PurePursuit::checkCommandCollisions / findSafeCommand (pure_pursuit.cpp:150-212):
+ * candidate i is "clear" when none of the `horizon` poses reached by repeating
+ * Path::State::update(cmd_i, (float)dt) from *start touches an occupied voxel.
+ * *first_clear_out = smallest clear i, or -1. horizon == 0: every candidate is clear.
+ * Same tests and sensor data as kc_dwa_check_poses on those poses, in one launch. */
+int kc_dwa_first_clear_command(kc_dwa *ctx, const kc_state *start,
+                               const double *vx, const double *vy, const double *omega,
+                               size_t n, int horizon, double dt, int64_t *first_clear_out);
 
 /* A5-A10: CostEvaluator::getMinTrajectoryCost (cost_evaluator.cpp:49-109) on
  * the rolled-out samples; result stays on the device until fetched */

@@ -10,6 +10,7 @@
 #include <pybind11/stl.h>
 
 #include "controllers/dwa.h"
+#include "controllers/pure_pursuit.h"
 #include "mapping/local_mapper_gpu.h"
 #include "utils/logger.h"
 #include "utils/critical_zone_check.h"
@@ -345,6 +346,36 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def("disable_sharding", &DWA::disableSharding)
       .def("use_resident_path", &DWA::useResidentPath, py::arg("on"),
            "Tracked-segment tables from a device-resident copy of the path (saves host time, adds a kernel)");
+
+  // PurePursuit (bindings_control.cpp:159-207)
+  using PP = Control::PurePursuit;
+  py::class_<PP::PurePursuitConfig, Control::Follower::FollowerParameters>(c, "PurePursuitConfig").def(py::init<>());
+  py::class_<PP, Control::Follower>(c, "PurePursuit")
+      .def(py::init([](const Control::ControlType &type, const Control::ControlLimitsParams &lim,
+                       CollisionChecker::ShapeType shape, const std::vector<float> &dims, const py::object &spos,
+                       const py::object &srot, double res, const PP::PurePursuitConfig &cfg) {
+             return std::make_unique<PP>(type, lim, shape, dims, vec3(spos), vec4(srot), res, cfg);
+           }), "Init PurePursuit follower with collision avoidance configuration", py::arg("control_type"),
+           py::arg("control_limits"), py::arg("robot_shape_type"), py::arg("robot_dimensions"),
+           py::arg("sensor_position_robot"), py::arg("sensor_rotation_robot"), py::arg("octree_res") = 0.1,
+           py::arg("config") = PP::PurePursuitConfig())
+      .def("execute", static_cast<Control::Controller::Result (PP::*)(const Path::State, const double)>(&PP::execute),
+           "Execute Pure Pursuit control step with state update", py::arg("current_position"), py::arg("delta_time"))
+      .def("execute", static_cast<Control::Controller::Result (PP::*)(const double)>(&PP::execute),
+           "Execute Pure Pursuit control step (uses internal state)", py::arg("delta_time"))
+      .def("execute", [](PP &self, const double dt, const Control::LaserScan &scan) {
+             return self.execute<Control::LaserScan>(dt, scan);
+           }, "Execute Pure Pursuit with LaserScan obstacle avoidance", py::arg("delta_time"), py::arg("laser_scan"))
+      .def("execute", [](PP &self, const double dt, const py::object &cloud) {
+             // world-frame points: an (N, 3) float32 C-contiguous array is read where it lies, anything else
+             // (lists of 3-sequences, other dtypes) is converted first
+             const FArr a = py::cast<FArr>(cloud);
+             if (a.ndim() != 2 || a.shape(1) != 3) throw std::invalid_argument("expected an (N, 3) array of points");
+             return self.execute<Control::PointCloudView>(
+                 dt, Control::PointCloudView{a.data(), static_cast<size_t>(a.shape(0))});
+           }, "Execute Pure Pursuit with PointCloud obstacle avoidance", py::arg("delta_time"), py::arg("point_cloud"))
+      // (not in the reference: the candidate list the avoidance search walks, nominal command first)
+      .def("search_candidates", &PP::searchCandidates, py::arg("nominal"));
 
   // -------------------------------------------------------------- mapping
   auto mp = m.def_submodule("mapping", "Local Mapping module");

@@ -73,6 +73,9 @@ class Follower : public Controller {
     return on_.path->totalPathLength() > 0.0;
   }
   const Path::Path getCurrentPath() const;
+  // exp(-(k_curv * sum |curvature| + k_rot * |omega|)) over the lookahead from the nearest point, at least the
+  // minimum factor (follower.cpp:319-352)
+  double calculateExponentialSpeedFactor(double current_angular_vel) const;
 
  protected:
   // What setParams reads out of the parameter set, once per change

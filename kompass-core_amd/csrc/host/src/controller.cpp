@@ -190,5 +190,18 @@ void Follower::aimAtTarget() {
   on_.target->reverse = false;
 }
 
+double Follower::calculateExponentialSpeedFactor(double current_angular_vel) const {
+  if (!on_.path || !on_.ready) return 1.0;
+  double curvature_sum = 0.0, dist = 0.0;
+  // from the tracked point on, up to the lookahead distance
+  for (size_t i = on_.nearest->index; i < on_.path->getSize() - 1; ++i) {
+    curvature_sum += std::abs(on_.path->getCurvature(i));
+    dist += Path::Path::distance(on_.path->getIndex(i), on_.path->getIndex(i + 1));
+    if (dist >= knob_.lookahead) break;
+  }
+  const double exponent = (knob_.slow_in_curves * curvature_sum) + (knob_.slow_in_turns * std::abs(current_angular_vel));
+  return std::max(std::exp(-exponent), knob_.slowest);
+}
+
 }  // namespace Control
 }  // namespace Kompass

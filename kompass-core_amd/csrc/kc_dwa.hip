@@ -615,6 +615,7 @@ void kc_dwa_destroy(kc_dwa *c) {
   }
   (void)e;
   c->timing.release();
+  c->pp.release();
   c->d_vxt.release();
   c->d_vyt.release();
   c->d_vidx.release();

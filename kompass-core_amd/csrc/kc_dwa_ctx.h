@@ -358,6 +358,27 @@ struct kc_dwa {
   DevBuf<double> d_omega;              // [A] omega of every trig row
   DevBuf<double> d_sincostab;          // the 440 table values of kc_trig_exact.h beside the context's other tables
   bool freeze_valid = false;           // d_freeze describes the last roll-out
+
+  // kc_dwa_first_clear_command (kc_pp_search.hip): candidate velocities, the host trig table of the fallback, and
+  // three epoch-tagged result words (smallest clear index | trig failure | pose beyond a cropped scan) that the
+  // kernel raises with atomicMax -- a new epoch per call, so no launch resets them
+  struct PpSearch {
+    DevBuf<double> d_cand;                 // [3][n] vx | vy | omega
+    PinBuf<double> h_cand;
+    DevBuf<double2> d_trig;                // [n][horizon + 1] cos / sin(yaw_k) of the fallback
+    PinBuf<double2> h_trig;
+    DevBuf<unsigned long long> d_slots;    // [3]
+    PinBuf<unsigned long long> h_slots;
+    uint32_t epoch = 0;
+    void release() {
+      d_cand.release();
+      h_cand.release();
+      d_trig.release();
+      h_trig.release();
+      d_slots.release();
+      h_slots.release();
+    }
+  } pp;
 };
 
 // largest point list the device-side sensor update takes (bucket grid of at most 64 x 64 cells: about one obstacle per
@@ -470,6 +491,7 @@ int ensure_cycle_buffers(kc_dwa *c, size_t n, size_t P);
 int window_geometry(kc_dwa *c, double wx, double wy, double reach, CollDev &cd);
 int window_bits_host(kc_dwa *c, CollDev &cd);
 int build_window_at(kc_dwa *c, double wx, double wy, double reach, CollDev &cd);
+int tilt_params(kc_dwa *c, TiltDev &t);  // the tilted-octree tests' parameters of the last kc_dwa_set_scan
 int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bool trig_ready = false);
 int materialise_paths(kc_dwa *c);
 void cycle_kernel_limits(kc_dwa *c);   // dynamic-LDS limits of the roll-out / cost kernels -> lds_limit, cost_lds_ok, cost_batch_ok

@@ -124,6 +124,16 @@ class Robot:
     def radius(self) -> float:
         return RobotGeometry.get_radius(self.geometry_type, self.geometry_params)
 
+    @property
+    def wheelbase(self) -> float:
+        # (models.py get_wheelbase: the radius of a round body, else the lateral extent)
+        p = np.asarray(self.geometry_params, dtype=float)
+        if not RobotGeometry.is_valid_parameters(self.geometry_type, p):
+            raise ValueError("Invalid parameters for the robot geometry")
+        if self.geometry_type in (RobotGeometry.Type.CYLINDER, RobotGeometry.Type.SPHERE):
+            return float(p[0])
+        return float(p[1])
+
     def set_state(self, x: float, y: float, yaw: float, speed: float) -> None:
         self.state = RobotState(x=x, y=y, yaw=yaw, speed=speed)
 

@@ -127,6 +127,8 @@ SIGNATURES = {
     "kc_dwa_set_tracked_segment_xyz": (C.c_int, [_vp, _fp, _fp, _sz, C.c_float]),
     "kc_dwa_rollout": (C.c_int, [_vp, C.POINTER(State), _sz]),
     "kc_dwa_check_poses": (C.c_int, [_vp, _dp, _dp, _dp, _sz, C.POINTER(C.c_uint8)]),
+    "kc_dwa_first_clear_command": (C.c_int, [_vp, C.POINTER(State), _dp, _dp, _dp, _sz, C.c_int, C.c_double,
+                                             C.POINTER(C.c_int64)]),
     "kc_dwa_evaluate": (C.c_int, [_vp]),
     "kc_dwa_fetch_result": (C.c_int, [_vp, C.POINTER(Result)]),
     "kc_dwa_cycle": (C.c_int, [_vp, C.POINTER(State), _sz, C.POINTER(Result)]),
@@ -559,6 +561,18 @@ class DwaContext:
         _check(lib().kc_dwa_check_poses(self.h, _pd(x), _pd(y), _pd(yaw), len(x),
                                         hit.ctypes.data_as(C.POINTER(C.c_uint8))))
         return hit.astype(bool)
+
+    def first_clear_command(self, state, vx, vy, omega, horizon, dt) -> int:
+        """Index of the first (vx[i], vy[i], omega[i]) whose `horizon` poses rolled out
+        from `state` with step (float)dt touch no occupied voxel, or -1 (one launch)."""
+        vx, vy, omega = _f64(vx), _f64(vy), _f64(omega)
+        if not (len(vx) == len(vy) == len(omega)):
+            raise ValueError("vx, vy and omega must have the same length")
+        st = state if isinstance(state, State) else State(*state)
+        out = C.c_int64(-2)
+        _check(lib().kc_dwa_first_clear_command(self.h, C.byref(st), _pd(vx), _pd(vy), _pd(omega), len(vx),
+                                                int(horizon), float(dt), C.byref(out)))
+        return int(out.value)
 
     def evaluate(self):
         _check(lib().kc_dwa_evaluate(self.h))
