@@ -8,7 +8,7 @@
 // cell (plain stores, every writer stores the same value), pass 3 stamps
 // OCCUPIED on the end cells.  Stream order between the passes gives exactly
 // the max.  One wavefront per beam; the Bresenham error term has a closed form
-// per step, so the 64 lanes each rasterise a contiguous chunk of the line.
+// per step, so the 64 lanes each take one of 64 consecutive steps of the line.
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -52,86 +52,83 @@ __device__ __forceinline__ bool beam_endpoint(const MapGeom &g, float range, dou
   return true;
 }
 
-// Steps [*lo, *hi] of the steps 1..n of a line whose stamps can land on the
-// major axis [0, A): step i stamps at major coordinate a0 + astep i or one step
-// back, so only a_i in [-1, A] matter -- every other stamp falls outside the
-// grid.  This bounds the work of a beam by the grid, not by its length.
-__device__ __forceinline__ void step_window(int a0, int astep, int A, int n, int &lo, int &hi) {
-  const long long l = astep > 0 ? -1LL - a0 : static_cast<long long>(a0) - A;
-  const long long h = astep > 0 ? static_cast<long long>(A) - a0 : a0 + 1LL;
-  lo = static_cast<int>(max(l, 1LL));
-  hi = static_cast<int>(min(h, static_cast<long long>(n)));
+// line of one beam in major/minor form
+struct BeamLine {
+  int a0, b0, astep, bstep, nsteps;
+  long long dmaj, ddmaj, ddmin;
+  bool xmajor;
+};
+
+__device__ __forceinline__ BeamLine beam_line(const MapGeom &g, int2 t) {
+  BeamLine l;
+  const int dx = t.x - g.s0, dy = t.y - g.s1;
+  const int adx = abs(dx), ady = abs(dy);
+  l.xmajor = adx >= ady;  // 2 dx >= 2 dy
+  l.nsteps = l.xmajor ? adx : ady;
+  l.astep = l.xmajor ? (dx >= 0 ? 1 : -1) : (dy >= 0 ? 1 : -1);
+  l.bstep = l.xmajor ? (dy >= 0 ? 1 : -1) : (dx >= 0 ? 1 : -1);
+  l.a0 = l.xmajor ? g.s0 : g.s1;
+  l.b0 = l.xmajor ? g.s1 : g.s0;
+  l.dmaj = l.nsteps;
+  l.ddmaj = 2 * l.dmaj;
+  l.ddmin = 2 * static_cast<long long>(l.xmajor ? ady : adx);
+  return l;
 }
 
-__device__ __forceinline__ void stamp_empty(int *grid, const MapGeom &g, int i,
-                                            int j) {
-  if (i >= 0 && i < g.H && j >= 0 && j < g.W)
-    grid[(size_t)i + (size_t)j * (size_t)g.H] = KC_EMPTY;
+// bresenhamEnhanced (line_drawing.h:55-124) in closed form: after major-axis
+// step i (1..n), e_i = dmaj + i*ddmin, k_i = floor((e_i - 1)/ddmaj) minor
+// increments so far, error_i = e_i - k_i*ddmaj in [1, ddmaj].  This is k_i,
+// from a double quotient: exact while e_i < 2^53.
+__device__ __forceinline__ long long minor_after(const BeamLine &l, int i) {
+  return static_cast<long long>(floor(
+      static_cast<double>(l.dmaj + static_cast<long long>(i) * l.ddmin - 1) / static_cast<double>(l.ddmaj)));
 }
 
-// pass 2: bresenhamEnhanced (line_drawing.h:55-124), all cells as EMPTY.
-// Major-axis step i (1..n): e_i = d + i*dd_minor, k_i = floor((e_i - 1)/dd_major)
-// minor increments so far, error_i = e_i - k_i*dd_major in [1, dd_major].
-constexpr int kBeamsPerBlock = 4;
+// Steps [x, y] of [max(first, 1), min(last, nsteps)] whose stamps can land on
+// the major axis [A0, A1]: step i stamps at major coordinate a_i = a0 + astep i
+// or a_i - astep.  In 64 bits: a0 can lie far outside the grid.  With [A0, A1]
+// the grid, this bounds the work of a beam by the grid, not by its length.
+__device__ __forceinline__ int2 step_range(const BeamLine &l, int A0, int A1, int first, int last) {
+  const long long lo = l.astep > 0 ? static_cast<long long>(A0) - l.a0 : static_cast<long long>(l.a0) - A1;
+  const long long hi = l.astep > 0 ? static_cast<long long>(A1) + 1 - l.a0 : static_cast<long long>(l.a0) - A0 + 1;
+  return make_int2(static_cast<int>(max(lo, static_cast<long long>(max(first, 1)))),
+                   static_cast<int>(min(hi, static_cast<long long>(min(last, l.nsteps)))));
+}
 
-__global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_kernel(
-    MapGeom g, const float *__restrict__ ranges, const double2 *__restrict__ trig, int n,
-    int *__restrict__ grid, int step_limit) {
-  // Workgroups go to the eight XCDs round-robin, each with an L2 of its own: XCD x takes the x-th EIGHTH of the
-  // beams (a sector of an ordered scan), so the dirty partial lines of a grid region collect in one L2 instead of
-  // all eight
-  const int per_xcd = static_cast<int>(gridDim.x >> 3);  // (the host launches a multiple of eight workgroups)
-  const int block = static_cast<int>(blockIdx.x & 7u) * per_xcd + static_cast<int>(blockIdx.x >> 3);
-  const int beam = block * kBeamsPerBlock + (threadIdx.x >> 6);
-  if (beam >= n) return;
-  const int lane = threadIdx.x & 63;
-  int2 t;
-  if (!beam_endpoint(g, ranges[beam], trig[beam], t)) return;
-  int dx = t.x - g.s0, dy = t.y - g.s1;
-  const int xstep = dx >= 0 ? 1 : -1, ystep = dy >= 0 ? 1 : -1;
-  dx = abs(dx);
-  dy = abs(dy);
-  if (lane == 0) stamp_empty(grid, g, g.s0, g.s1);  // first emitted point
-  const bool xmajor = dx >= dy;
-  const long long dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
-  const long long ddmaj = 2 * dmaj, ddmin = 2 * dmin;
-  const int astep = xmajor ? xstep : ystep, bstep = xmajor ? ystep : xstep;
-  const int a0 = xmajor ? g.s0 : g.s1, b0 = xmajor ? g.s1 : g.s0;
-  int ifirst, ilast;
-  step_window(a0, astep, xmajor ? g.H : g.W, xmajor ? dx : dy, ifirst, ilast);
-  // tiled scan: only the first step_limit steps (the tiles own the rest)
-  ilast = min(ilast, step_limit);
-  if (ifirst > ilast) return;
-  // The 64 lanes take 64 CONSECUTIVE steps per trip (closed-form state before step i, as above): the stores of
-  // an x-major line then fall into a few 64-byte lines of the column-major grid instead of 64 -- the L2's write
-  // transactions, not the arithmetic, bound this pass (a contiguous chunk of steps per lane: 18.6 us at
-  // 4096 beams x ~500 steps)
-  for (int c = lane; c <= ilast - ifirst; c += 64) {
-    const int i = ifirst + c;
-    const long long eprev = dmaj + (long long)(i - 1) * ddmin;
-    const long long k = static_cast<long long>(
-        floor(static_cast<double>(eprev - 1) / static_cast<double>(ddmaj)));
-    const long long errorprev = eprev - k * ddmaj;
-    long long error = errorprev + ddmin;
-    const int a = a0 + astep * i;
-    int bq = b0 + bstep * (int)k;
+// The one line walk of the beam-parallel and the tiled kernels: steps
+// ifirst..ilast, from the closed-form state before step ifirst.  stamp(a, b)
+// takes major / minor coordinates; each step stamps (a, b - bstep) below the
+// line, (a - astep, b) above it, both on it, then (a, b).
+template <class Int, class Stamp>
+__device__ __forceinline__ void walk_steps(const BeamLine &l, int ifirst, int ilast, Stamp stamp) {
+  const long long k = minor_after(l, ifirst - 1);
+  const Int ddmaj = static_cast<Int>(l.ddmaj), ddmin = static_cast<Int>(l.ddmin);
+  Int error = static_cast<Int>(l.dmaj + static_cast<long long>(ifirst - 1) * l.ddmin - k * l.ddmaj);
+  int a = l.a0 + l.astep * (ifirst - 1);
+  int b = l.b0 + l.bstep * static_cast<int>(k);
+  for (int c = ilast - ifirst; c >= 0; --c) {
+    const Int errorprev = error;
+    a += l.astep;
+    error += ddmin;
     if (error > ddmaj) {
-      bq += bstep;
+      b += l.bstep;
       error -= ddmaj;
-      const bool lo = error + errorprev < ddmaj, hi = error + errorprev > ddmaj;
-      // x-major: lo -> (x, y - ystep), hi -> (x - xstep, y); y-major mirrored
-      if (!hi) {  // lo or both
-        if (xmajor) stamp_empty(grid, g, a, bq - bstep);
-        else stamp_empty(grid, g, bq - bstep, a);
-      }
-      if (!lo) {  // hi or both
-        if (xmajor) stamp_empty(grid, g, a - astep, bq);
-        else stamp_empty(grid, g, bq, a - astep);
-      }
+      const Int sum = error + errorprev;
+      if (sum <= ddmaj) stamp(a, b - l.bstep);
+      if (sum >= ddmaj) stamp(a - l.astep, b);
     }
-    if (xmajor) stamp_empty(grid, g, a, bq);
-    else stamp_empty(grid, g, bq, a);
+    stamp(a, b);
   }
+}
+
+// body(Int{}) with the error type of the line's walk: the error term stays in
+// [1, ddmaj] and the sums below 2 ddmaj, so 32 bits while nsteps < 2^28.  (The
+// beam-parallel kernel chooses once per beam, outside its lane loop: a branch
+// per step made the plain scan's rays_kernel 1.5 % slower.)
+template <class Body>
+__device__ __forceinline__ void with_error_type(const BeamLine &l, Body body) {
+  if (l.nsteps < (1 << 28)) body(int{});
+  else body(0LL);
 }
 
 // ---- M3: which beam decides a cell -------------------------------------------
@@ -147,68 +144,48 @@ __device__ __forceinline__ size_t tag_index(int i, int j, int hb) {
   return ((static_cast<size_t>(j >> 2) * hb + (i >> 2)) << 4) | ((j & 3) << 2) | (i & 3);
 }
 
-__device__ __forceinline__ void stamp_tag(int *grid, unsigned int *last, unsigned int tag, int hb,
-                                          const MapGeom &g, int i, int j) {
-  if (i >= 0 && i < g.H && j >= 0 && j < g.W) {
-    grid[(size_t)i + (size_t)j * (size_t)g.H] = KC_EMPTY;
-    atomicMax(&last[tag_index(i, j, hb)], tag);
-  }
-}
+// pass 2: the steps [step_first, step_limit] of every beam as EMPTY, with kBayes
+// also the tag of the beam (a tiled scan leaves the rest of a line to the tiles)
+constexpr int kBeamsPerBlock = 4;
 
-// same line as rays_kernel, one step per lane per pass: the state before step i
-// has the closed form used there for the first step of a chunk
-__global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_bayes_kernel(
+template <bool kBayes>
+__global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_kernel(
     MapGeom g, const float *__restrict__ ranges, const double2 *__restrict__ trig, int n,
-    int *__restrict__ grid, unsigned int *__restrict__ last, int hb, int step_first,
-    int step_limit) {
-  const int beam = blockIdx.x * kBeamsPerBlock + (threadIdx.x >> 6);
+    int *__restrict__ grid, unsigned int *__restrict__ last, int hb, int step_first, int step_limit) {
+  // Plain scans: workgroups go to the eight XCDs round-robin, each with an L2 of its own: XCD x takes the x-th
+  // EIGHTH of the beams (a sector of an ordered scan), so the dirty partial lines of a grid region collect in one
+  // L2 instead of all eight
+  int block = static_cast<int>(blockIdx.x);
+  if (!kBayes) {
+    const int per_xcd = static_cast<int>(gridDim.x >> 3);  // (the host launches a multiple of eight workgroups)
+    block = static_cast<int>(blockIdx.x & 7u) * per_xcd + static_cast<int>(blockIdx.x >> 3);
+  }
+  const int beam = block * kBeamsPerBlock + (threadIdx.x >> 6);
   if (beam >= n) return;
   const unsigned int tag = static_cast<unsigned int>(beam) + 1u;
   const int lane = threadIdx.x & 63;
   int2 t;
   if (!beam_endpoint(g, ranges[beam], trig[beam], t)) return;
-  int dx = t.x - g.s0, dy = t.y - g.s1;
-  const int xstep = dx >= 0 ? 1 : -1, ystep = dy >= 0 ? 1 : -1;
-  dx = abs(dx);
-  dy = abs(dy);
-  if (lane == 0 && step_first <= 1) stamp_tag(grid, last, tag, hb, g, g.s0, g.s1);  // first emitted point
-  const bool xmajor = dx >= dy;
-  const long long dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
-  const long long ddmaj = 2 * dmaj, ddmin = 2 * dmin;
-  const int astep = xmajor ? xstep : ystep, bstep = xmajor ? ystep : xstep;
-  const int a0 = xmajor ? g.s0 : g.s1, b0 = xmajor ? g.s1 : g.s0;
-  int ifirst, ilast;
-  step_window(a0, astep, xmajor ? g.H : g.W, xmajor ? dx : dy, ifirst, ilast);
-  ifirst = max(ifirst, step_first);
-  ilast = min(ilast, step_limit);
-  if (ifirst > ilast) return;
-  // (a counter from 0: i += 64 near INT_MAX would overflow; the window is at most A + 2 steps)
-  for (int c = lane; c <= ilast - ifirst; c += 64) {
-    const int i = ifirst + c;
-    const long long eprev = dmaj + (long long)(i - 1) * ddmin;
-    const long long k = static_cast<long long>(
-        floor(static_cast<double>(eprev - 1) / static_cast<double>(ddmaj)));
-    const long long errorprev = eprev - k * ddmaj;
-    long long error = errorprev + ddmin;
-    const int a = a0 + astep * i;
-    int bq = b0 + bstep * (int)k;
-    if (error > ddmaj) {
-      bq += bstep;
-      error -= ddmaj;
-      const bool lo = error + errorprev < ddmaj, hi = error + errorprev > ddmaj;
-      // x-major: lo -> (x, y - ystep), hi -> (x - xstep, y); y-major mirrored
-      if (!hi) {  // lo or both
-        if (xmajor) stamp_tag(grid, last, tag, hb, g, a, bq - bstep);
-        else stamp_tag(grid, last, tag, hb, g, bq - bstep, a);
-      }
-      if (!lo) {  // hi or both
-        if (xmajor) stamp_tag(grid, last, tag, hb, g, a - astep, bq);
-        else stamp_tag(grid, last, tag, hb, g, bq, a - astep);
-      }
+  auto stamp_cell = [&](int i, int j) {
+    if (i >= 0 && i < g.H && j >= 0 && j < g.W) {
+      grid[(size_t)i + (size_t)j * (size_t)g.H] = KC_EMPTY;
+      if (kBayes) atomicMax(&last[tag_index(i, j, hb)], tag);
     }
-    if (xmajor) stamp_tag(grid, last, tag, hb, g, a, bq);
-    else stamp_tag(grid, last, tag, hb, g, bq, a);
-  }
+  };
+  if (lane == 0 && step_first <= 1) stamp_cell(g.s0, g.s1);  // first emitted point
+  const BeamLine l = beam_line(g, t);
+  const int2 w = step_range(l, 0, (l.xmajor ? g.H : g.W) - 1, step_first, step_limit);
+  auto stamp = [&](int a, int b) {
+    if (l.xmajor) stamp_cell(a, b);
+    else stamp_cell(b, a);
+  };
+  // The 64 lanes take 64 CONSECUTIVE steps per trip, each a one-step walk from the closed form: the stores of an
+  // x-major line then fall into a few 64-byte lines of the column-major grid instead of 64 -- the L2's write
+  // transactions, not the arithmetic, bound this pass (a contiguous chunk of steps per lane: 18.6 us at 4096 beams
+  // x ~500 steps).  (A counter from 0: i += 64 near INT_MAX would overflow.)
+  with_error_type(l, [&](auto e) {
+    for (int c = lane; c <= w.y - w.x; c += 64) walk_steps<decltype(e)>(l, w.x + c, w.x + c, stamp);
+  });
 }
 
 // ---- tiled scan -----------------------------------------------------------------
@@ -219,8 +196,8 @@ __global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_bayes_kernel(
 // coalesced, UNEXPLORED included -- no clear pass, no global atomics, and steps
 // outside the grid are never walked.  Around the sensor every beam crosses the
 // same few tiles, so the first kNearSteps steps of each beam stay with the
-// beam-parallel kernels (rays_kernel / rays_bayes_kernel with a step limit),
-// which run behind this one and only ever raise a cell.
+// beam-parallel kernel (rays_kernel with a step limit), which runs behind this
+// one and only ever raises a cell.
 constexpr int kTileI = 64, kTileJ = 16, kNearSteps = 64;
 constexpr int kTileThreads = 256;
 constexpr int kChunkSteps = 16;  // steps one lane walks: the closed-form start costs a division
@@ -263,35 +240,6 @@ struct TileLds {
   TileTask task[kRoundBeams * kMaxChunks];
   int ntask;
 };
-
-// line of one beam in major/minor form
-struct BeamLine {
-  int a0, b0, astep, bstep, nsteps;
-  long long dmaj, ddmaj, ddmin;
-  bool xmajor;
-};
-
-__device__ __forceinline__ BeamLine beam_line(const MapGeom &g, int2 t) {
-  BeamLine l;
-  const int dx = t.x - g.s0, dy = t.y - g.s1;
-  const int adx = abs(dx), ady = abs(dy);
-  l.xmajor = adx >= ady;  // 2 dx >= 2 dy
-  l.nsteps = l.xmajor ? adx : ady;
-  l.astep = l.xmajor ? (dx >= 0 ? 1 : -1) : (dy >= 0 ? 1 : -1);
-  l.bstep = l.xmajor ? (dy >= 0 ? 1 : -1) : (dx >= 0 ? 1 : -1);
-  l.a0 = l.xmajor ? g.s0 : g.s1;
-  l.b0 = l.xmajor ? g.s1 : g.s0;
-  l.dmaj = l.nsteps;
-  l.ddmaj = 2 * l.dmaj;
-  l.ddmin = 2 * static_cast<long long>(l.xmajor ? ady : adx);
-  return l;
-}
-
-// minor increments made by the steps 1..i (k_i of rays_kernel)
-__device__ __forceinline__ long long minor_after(const BeamLine &l, int i) {
-  return static_cast<long long>(floor(
-      static_cast<double>(l.dmaj + static_cast<long long>(i) * l.ddmin - 1) / static_cast<double>(l.ddmaj)));
-}
 
 // Stamps of the beams [b_begin, b_end), steps [step_min, step_max], that fall
 // into the tile [I0..I1] x [J0..J1], into L.cell (tag = beam + 1, maximum; any
@@ -356,13 +304,9 @@ __device__ void tile_accumulate(const MapGeom &g, const int2 *__restrict__ ends,
       const double cross = static_cast<double>(dx) * cj - static_cast<double>(dy) * ci;
       if (fabs(cross) <= fabs(static_cast<double>(dy)) * hi + fabs(static_cast<double>(dx)) * hj) {
         const BeamLine l = beam_line(g, t);
-        const int A0 = l.xmajor ? I0 : J0, A1 = l.xmajor ? I1 : J1;
+        const int2 w = step_range(l, l.xmajor ? I0 : J0, l.xmajor ? I1 : J1, step_min, step_max);
+        const int ilo = w.x, ihi = w.y;
         const int B0 = l.xmajor ? J0 : I0, B1 = l.xmajor ? J1 : I1;
-        // a stamp of step i sits at major coordinate a_i or a_i - astep
-        int ilo = l.astep > 0 ? A0 - l.a0 : l.a0 - A1;
-        int ihi = l.astep > 0 ? A1 + 1 - l.a0 : l.a0 - A0 + 1;
-        ilo = max(ilo, max(step_min, 1));
-        ihi = min(ihi, min(step_max, l.nsteps));
         if (ilo <= ihi) {
           // the minor coordinate only moves one way: the stamps of steps
           // ilo..ihi lie between the minor cell before step ilo and the one
@@ -382,13 +326,15 @@ __device__ void tile_accumulate(const MapGeom &g, const int2 *__restrict__ ends,
     const int nt = L.ntask;
     for (int q = threadIdx.x; q < nt; q += kTileThreads) {
       const TileTask task = L.task[q];
-      const BeamLine l = beam_line(g, ends[task.beam]);
+      BeamLine l = beam_line(g, ends[task.beam]);
       const unsigned int tag = kBayes ? static_cast<unsigned int>(task.beam) + 1u : 1u;
-      // tile-local (major, minor) coordinates and LDS strides
+      // the walk in tile-local (major, minor) coordinates; the stamp maps them to LDS
       const int A0 = l.xmajor ? I0 : J0, B0 = l.xmajor ? J0 : I0;
       const unsigned int EA = static_cast<unsigned int>((l.xmajor ? I1 : J1) - A0 + 1);
       const unsigned int EB = static_cast<unsigned int>((l.xmajor ? J1 : I1) - B0 + 1);
       const int SA = l.xmajor ? 1 : kTileI, SB = l.xmajor ? kTileI : 1;
+      l.a0 -= A0;
+      l.b0 -= B0;
       auto stamp = [&](int am, int bm) {
         if (static_cast<unsigned int>(am) < EA && static_cast<unsigned int>(bm) < EB) {
           const int idx = am * SA + bm * SB;
@@ -396,43 +342,7 @@ __device__ void tile_accumulate(const MapGeom &g, const int2 *__restrict__ ends,
           else L.cell[idx] = 1u;
         }
       };
-      const long long k = minor_after(l, task.ifirst - 1);
-      const long long e0 = l.dmaj + static_cast<long long>(task.ifirst - 1) * l.ddmin - k * l.ddmaj;
-      int a = l.a0 + l.astep * (task.ifirst - 1) - A0;
-      int bq = l.b0 + l.bstep * static_cast<int>(k) - B0;
-      if (l.nsteps < (1 << 28)) {
-        // the error term stays in [1, ddmaj] and the sums below 2 ddmaj: 32 bits
-        const int ddmaj = static_cast<int>(l.ddmaj), ddmin = static_cast<int>(l.ddmin);
-        int error = static_cast<int>(e0);
-        for (int i = task.ifirst; i <= task.ilast; ++i) {
-          const int errorprev = error;
-          a += l.astep;
-          error += ddmin;
-          if (error > ddmaj) {
-            bq += l.bstep;
-            error -= ddmaj;
-            const int sum = error + errorprev;
-            if (sum <= ddmaj) stamp(a, bq - l.bstep);  // below the line, or both
-            if (sum >= ddmaj) stamp(a - l.astep, bq);  // above the line, or both
-          }
-          stamp(a, bq);
-        }
-      } else {
-        long long error = e0;
-        for (int i = task.ifirst; i <= task.ilast; ++i) {
-          const long long errorprev = error;
-          a += l.astep;
-          error += l.ddmin;
-          if (error > l.ddmaj) {
-            bq += l.bstep;
-            error -= l.ddmaj;
-            const long long sum = error + errorprev;
-            if (sum <= l.ddmaj) stamp(a, bq - l.bstep);
-            if (sum >= l.ddmaj) stamp(a - l.astep, bq);
-          }
-          stamp(a, bq);
-        }
-      }
+      with_error_type(l, [&](auto e) { walk_steps<decltype(e)>(l, task.ifirst, task.ilast, stamp); });
     }
     __syncthreads();
   }
@@ -754,55 +664,60 @@ int run_scan(kc_mapper *m, const double *angles, const double *ranges,
                           hipMemcpyHostToDevice, s));
   }
   const int ni = static_cast<int>(n);
-  const dim3 rgrid((ni + kBeamsPerBlock - 1) / kBeamsPerBlock), rblock(64 * kBeamsPerBlock);
   const int hb = (m->g.H + 3) / 4;
-  int step_limit = INT_MAX;
-  if (m->tiles) {
-    KC_TRY(m->d_ends.reserve(n + n / 8 + 2));  // end cells + one sector byte per beam
-    KC_TRY(m->timing.start("beam_ends_kernel", s));
+  const bool hybrid = bayes && m->tile_mode == 3;
+  auto timed = [&](const char *label, auto launch) {
+    KC_TRY(m->timing.start(label, s));
+    launch();
+    return m->timing.stop(s);
+  };
+  auto beam_ends = [&] {
     hipLaunchKernelGGL(beam_ends_kernel, dim3((ni + 255) / 256), dim3(256), 0, s, m->g,
                        m->d_ranges.p, m->d_trig.p, ni, m->d_ends.p);
-    KC_TRY(m->timing.stop(s));
+  };
+  // steps [first, limit] of every beam, one wavefront per beam
+  auto rays = [&](int first, int limit) {
+    const dim3 rgrid((ni + kBeamsPerBlock - 1) / kBeamsPerBlock), rblock(64 * kBeamsPerBlock);
+    if (bayes)
+      hipLaunchKernelGGL(rays_kernel<true>, rgrid, rblock, 0, s, m->g, m->d_ranges.p, m->d_trig.p, ni, m->d_grid.p,
+                         m->d_last.p, hb, first, limit);
+    else  // (a multiple of eight workgroups: the kernel deals the beams to the XCDs by eighths)
+      hipLaunchKernelGGL(rays_kernel<false>, dim3((rgrid.x + 7u) & ~7u), rblock, 0, s, m->g, m->d_ranges.p,
+                         m->d_trig.p, ni, m->d_grid.p, static_cast<unsigned int *>(nullptr), hb, first, limit);
+  };
+  // far field: one workgroup per tile, the steps beyond kNearSteps
+  auto far_tiles = [&] {
     const dim3 tgrid((m->g.H + kTileI - 1) / kTileI, (m->g.W + kTileJ - 1) / kTileJ);
-    KC_TRY(m->timing.start("scan_tiles_kernel", s));
     if (bayes)
       hipLaunchKernelGGL(scan_tiles_kernel<true>, tgrid, dim3(256), 0, s, m->g, m->d_ends.p, ni,
                          m->d_grid.p, m->d_last.p, hb);
     else
       hipLaunchKernelGGL(scan_tiles_kernel<false>, tgrid, dim3(256), 0, s, m->g, m->d_ends.p, ni,
                          m->d_grid.p, static_cast<unsigned int *>(nullptr), hb);
-    KC_TRY(m->timing.stop(s));
-    step_limit = kNearSteps;
-  }
-  const bool hybrid = bayes && m->tile_mode == 3;
-  if (hybrid) {
-    // far field: beam-parallel, a global atomic per stamp (few beams share a far cell)
-    KC_TRY(m->d_ends.reserve(n + n / 8 + 2));  // end cells + one sector byte per beam
-    hipLaunchKernelGGL(beam_ends_kernel, dim3((ni + 255) / 256), dim3(256), 0, s, m->g,
-                       m->d_ranges.p, m->d_trig.p, ni, m->d_ends.p);
-    KC_TRY(m->timing.start("rays_kernel", s));
-    hipLaunchKernelGGL(rays_bayes_kernel, rgrid, rblock, 0, s, m->g, m->d_ranges.p, m->d_trig.p,
-                       ni, m->d_grid.p, m->d_last.p, hb, kNearSteps + 1, INT_MAX);
-    KC_TRY(m->timing.stop(s));
-  }
-  KC_TRY(m->timing.start(bayes && (m->tiles || hybrid) ? "near_tiles_kernel" : "rays_kernel", s));
-  if (bayes && (m->tiles || hybrid)) {
-    // tiles that hold cells within kNearSteps + 1 (Chebyshev) of the start cell
+  };
+  // tiles that hold cells within kNearSteps + 1 (Chebyshev) of the start cell
+  auto near_tiles = [&] {
     const int ia = std::max(m->g.s0 - kNearSteps - 1, 0), ib = std::min(m->g.s0 + kNearSteps + 1, m->g.H - 1);
     const int ja = std::max(m->g.s1 - kNearSteps - 1, 0), jb = std::min(m->g.s1 + kNearSteps + 1, m->g.W - 1);
-    if (ia <= ib && ja <= jb) {
-      const int ti0 = ia / kTileI, tj0 = ja / kTileJ;
-      const dim3 ngrid(ib / kTileI - ti0 + 1, jb / kTileJ - tj0 + 1, std::min(kNearSlices, std::max(1, ni / 32)));
-      hipLaunchKernelGGL(near_tiles_kernel, ngrid, dim3(kTileThreads), 0, s, m->g, m->d_ends.p, ni,
-                         m->d_grid.p, m->d_last.p, hb, ti0, tj0);
-    }
-  } else if (bayes)
-    hipLaunchKernelGGL(rays_bayes_kernel, rgrid, rblock, 0, s, m->g, m->d_ranges.p, m->d_trig.p,
-                       ni, m->d_grid.p, m->d_last.p, hb, 1, step_limit);
-  else  // (a multiple of eight workgroups: the kernel deals the beams to the XCDs by eighths)
-    hipLaunchKernelGGL(rays_kernel, dim3((rgrid.x + 7u) & ~7u), rblock, 0, s, m->g, m->d_ranges.p, m->d_trig.p, ni,
-                       m->d_grid.p, step_limit);
-  KC_TRY(m->timing.stop(s));
+    if (ia > ib || ja > jb) return;
+    const int ti0 = ia / kTileI, tj0 = ja / kTileJ;
+    const dim3 ngrid(ib / kTileI - ti0 + 1, jb / kTileJ - tj0 + 1, std::min(kNearSlices, std::max(1, ni / 32)));
+    hipLaunchKernelGGL(near_tiles_kernel, ngrid, dim3(kTileThreads), 0, s, m->g, m->d_ends.p, ni,
+                       m->d_grid.p, m->d_last.p, hb, ti0, tj0);
+  };
+  if (m->tiles || hybrid) KC_TRY(m->d_ends.reserve(n + n / 8 + 2));  // end cells + one sector byte per beam
+  if (m->tiles) {  // far field in tiles, near field beam-parallel (plain) or in the near tiles (Bayesian)
+    KC_TRY(timed("beam_ends_kernel", beam_ends));
+    KC_TRY(timed("scan_tiles_kernel", far_tiles));
+    if (bayes) KC_TRY(timed("near_tiles_kernel", near_tiles));
+    else KC_TRY(timed("rays_kernel", [&] { rays(1, kNearSteps); }));
+  } else if (hybrid) {  // far field beam-parallel, a global atomic per stamp (few beams share a far cell)
+    beam_ends();
+    KC_TRY(timed("rays_kernel", [&] { rays(kNearSteps + 1, INT_MAX); }));
+    KC_TRY(timed("near_tiles_kernel", near_tiles));
+  } else {
+    KC_TRY(timed("rays_kernel", [&] { rays(1, INT_MAX); }));
+  }
   ++m->seq;
   KC_TRY(m->timing.start("endpoints_kernel", s));
   {

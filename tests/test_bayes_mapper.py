@@ -124,7 +124,7 @@ def _bits(a):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tiles", ["3", "1", "0"])  # hybrid (default) / all tiles / all beam-parallel
+@pytest.mark.parametrize("tiles", ["3", "1", "0"])  # hybrid / all tiles (default) / all beam-parallel
 @pytest.mark.parametrize("H,W,res,pos,orient,n,scale,params", _CASES)
 def test_bayes_scan_parity(H, W, res, pos, orient, n, scale, params, tiles, monkeypatch):
     import kompass_hip as kh
