@@ -669,6 +669,50 @@ int kc_zone_check_cloud_typed(kc_zone *ctx, const int8_t *data, size_t nbytes,
 int kc_zone_indices(kc_zone *ctx, int forward, int64_t *out, size_t cap,
                     size_t *count_out);
 
+/* ------------------------------------------------------------------------ */
+/* DepthDetector: 2-D detections -> 3-D boxes (vision/depth_detector.cpp)    */
+/* ------------------------------------------------------------------------ */
+typedef struct kc_depth kc_depth;
+
+/* DepthDetector ctor (depth_detector.cpp:10-42): depth_range = (min, max) in
+ * meters, camera_in_body from the translation and the (x, y, z, w) quaternion
+ * (not normalised, as in the reference), focal / principal = (fx, fy) /
+ * (cx, cy).  KC_ERR_INVALID unless factor is finite, > 0 and 65535 * factor is
+ * finite in float (every converted depth is then finite).  Needs no device: the
+ * first compute call opens the stream (KC_ERR_HIP there when none is usable). */
+int kc_depth_create(const float depth_range[2], const float cam_pos[3],
+                    const float cam_rot_xyzw[4], const float focal[2],
+                    const float principal[2], float factor, int device,
+                    kc_depth **out);
+void kc_depth_destroy(kc_depth *ctx);
+/* updateBoxes + get3dDetections (:44-81, :84-151).  img: a rows x cols uint16
+ * frame, element (r, c) at img[r * row_stride + c * col_stride] (any memory
+ * order); data_on_device != 0: img is a device address on ctx's device and is
+ * read in place, else the bounding rectangle of the clipped boxes is uploaded.
+ * boxes: n x (top.x, top.y, size.x, size.y); a box covers rows top.y ..
+ * top.y + size.y and columns top.x .. top.x + size.x, inclusive, computed in
+ * 64 bits; pixels outside the frame are skipped (the reference reads out of
+ * bounds).  state: (x, y, yaw) of the robot, or NULL to keep the previous
+ * body_in_world (the identity at first).  Per kept box (> 1 depth in range),
+ * in input order: out[6 m ..] = center[3], size[3] in the world frame and
+ * kept_index[m] = its input index; cap >= n. */
+int kc_depth_boxes(kc_depth *ctx, const uint16_t *img, int data_on_device,
+                   int64_t rows, int64_t cols, int64_t row_stride,
+                   int64_t col_stride, const int32_t *boxes, size_t n,
+                   const double *state, float *out, int32_t *kept_index,
+                   size_t cap, size_t *count_out);
+/* the raw per-box statistics of the same pass (tests): count_out[i] = depths
+ * kept, stats_out[4 i ..] = median, mad, min_d, max_d (zeros when count <= 1) */
+int kc_depth_box_stats(kc_depth *ctx, const uint16_t *img, int data_on_device,
+                       int64_t rows, int64_t cols, int64_t row_stride,
+                       int64_t col_stride, const int32_t *boxes, size_t n,
+                       int64_t *count_out, float *stats_out);
+/* bytes of frame the last call uploaded (0 for a frame on the device) */
+int kc_depth_last_upload(kc_depth *ctx, size_t *bytes_out);
+int kc_depth_timing_enable(kc_depth *ctx, int enable);
+int kc_depth_timing_get(kc_depth *ctx, const char **names, float *ms, size_t cap,
+                        size_t *count_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "utils/logger.h"
 #include "utils/critical_zone_check.h"
 #include "utils/pointcloud.h"
+#include "vision/depth_detector.h"
 
 namespace py = pybind11;
 using namespace Kompass;
@@ -58,6 +59,54 @@ FArr copy1(const Eigen::VectorXf &v) {
   return a;
 }
 Eigen::VectorXf toVec(const FArr &a) { return Eigen::VectorXf(a.data(), (Eigen::Index)a.size()); }
+
+// vision types: fixed vectors as numpy arrays (int32 / float32), read and written whole
+Eigen::Vector2i vec2i(const py::object &o) {
+  auto a = py::cast<std::vector<int>>(o);
+  if (a.size() != 2) throw std::invalid_argument("expected 2 values");
+  return Eigen::Vector2i(a[0], a[1]);
+}
+Eigen::Vector2f vec2f(const py::object &o) {
+  auto a = py::cast<std::vector<float>>(o);
+  if (a.size() != 2) throw std::invalid_argument("expected 2 values");
+  return Eigen::Vector2f(a[0], a[1]);
+}
+template <typename T, int N>
+py::array_t<T> arr(const Eigen::FixedVec<T, N> &v) {
+  py::array_t<T> a(N);
+  std::memcpy(a.mutable_data(), v.data(), sizeof(T) * N);
+  return a;
+}
+std::vector<Eigen::Vector2i> points2i(const py::object &o) {
+  std::vector<Eigen::Vector2i> out;
+  for (auto p : o) out.push_back(vec2i(py::reinterpret_borrow<py::object>(p)));
+  return out;
+}
+std::vector<Eigen::Vector3f> points3f(const py::object &o) {
+  std::vector<Eigen::Vector3f> out;
+  for (auto p : o) out.push_back(vec3(py::reinterpret_borrow<py::object>(p)));
+  return out;
+}
+template <typename T, int N>
+py::list arrs(const std::vector<Eigen::FixedVec<T, N>> &v) {
+  py::list l;
+  for (const auto &x : v) l.append(arr(x));
+  return l;
+}
+// a uint16 (H, W) numpy frame in any memory order, by pointer and strides (no copy)
+DepthImageView depthView(const py::array &a) {
+  if (!py::dtype::of<uint16_t>().is(a.dtype()) && a.dtype().num() != py::dtype::of<uint16_t>().num())
+    throw py::type_error("depth_img must be a uint16 array, got " + py::str(a.dtype()).cast<std::string>());
+  if (a.ndim() != 2) throw std::invalid_argument("depth_img must be 2-D (H, W)");
+  DepthImageView v;
+  v.data = static_cast<const uint16_t *>(a.data());
+  v.rows = a.shape(0);
+  v.cols = a.shape(1);
+  v.row_stride = a.strides(0) / static_cast<py::ssize_t>(sizeof(uint16_t));
+  v.col_stride = a.strides(1) / static_cast<py::ssize_t>(sizeof(uint16_t));
+  if (a.strides(0) % 2 || a.strides(1) % 2) throw std::invalid_argument("depth_img strides must be whole elements");
+  return v;
+}
 
 void fromDict(Parameters &p, const py::dict &d) {
   for (auto item : d) {
@@ -181,6 +230,64 @@ PYBIND11_MODULE(kompass_cpp, m) {
         if (key == "SPHERE") return CollisionChecker::ShapeType::SPHERE;
         throw std::runtime_error("Invalid key");
       });
+
+
+  // vision types (bindings_types.cpp:188-235)
+  py::class_<PointsOfInterest>(t, "PointsOfInterest")
+      .def(py::init<>())
+      .def(py::init<const PointsOfInterest &>())
+      .def(py::init([](const py::object &points, const py::object &img_size, float timestamp, const std::string &label) {
+             return PointsOfInterest(points2i(points), vec2i(img_size), timestamp, label);
+           }), py::arg("points"), py::arg("img_size") = std::vector<int>{640, 480}, py::arg("timestamp") = 0.0,
+           py::arg("label") = "")
+      .def_property("points_2d", [](const PointsOfInterest &p) { return arrs(p.Points2D); },
+                    [](PointsOfInterest &p, const py::object &o) { p.Points2D = points2i(o); })
+      .def_readwrite("timestamp", &PointsOfInterest::timestamp)
+      .def_readwrite("label", &PointsOfInterest::label)
+      .def_property("img_size", [](const PointsOfInterest &p) { return arr(p.img_size); },
+                    [](PointsOfInterest &p, const py::object &o) { p.img_size = vec2i(o); })
+      .def_property("vel", [](const PointsOfInterest &p) { return arr(p.vel); },
+                    [](PointsOfInterest &p, const py::object &o) { p.vel = vec2i(o); })
+      .def("set_vel", [](PointsOfInterest &p, const py::object &o) { p.setVel(vec2i(o)); })
+      .def("set_img_size", [](PointsOfInterest &p, const py::object &o) { p.setImgSize(vec2i(o)); });
+
+  py::class_<Bbox2D>(t, "Bbox2D")
+      .def(py::init<>())
+      .def(py::init<const Bbox2D &>())
+      .def(py::init([](const py::object &top, const py::object &size, float timestamp, const std::string &label) {
+             return Bbox2D(vec2i(top), vec2i(size), timestamp, label);
+           }), py::arg("top_left_corner"), py::arg("size"), py::arg("timestamp") = 0.0, py::arg("label") = "")
+      .def_property("top_left_corner", [](const Bbox2D &b) { return arr(b.top_corner); },
+                    [](Bbox2D &b, const py::object &o) { b.top_corner = vec2i(o); })
+      .def_property("size", [](const Bbox2D &b) { return arr(b.size); },
+                    [](Bbox2D &b, const py::object &o) { b.size = vec2i(o); })
+      .def_readwrite("timestamp", &Bbox2D::timestamp)
+      .def_readwrite("label", &Bbox2D::label)
+      .def_property("img_size", [](const Bbox2D &b) { return arr(b.img_size); },
+                    [](Bbox2D &b, const py::object &o) { b.img_size = vec2i(o); })
+      .def("set_vel", [](Bbox2D &b, const py::object &o) { b.setVel(vec3(o)); })
+      .def("set_img_size", [](Bbox2D &b, const py::object &o) { b.setImgSize(vec2i(o)); });
+
+  py::class_<Bbox3D>(t, "Bbox3D")
+      .def(py::init<>())
+      .def(py::init<const Bbox3D &>())
+      .def(py::init([](const py::object &center, const py::object &size, const py::object &cimg,
+                       const py::object &simg, float timestamp, const std::string &label, const py::object &pc) {
+             return Bbox3D(vec3(center), vec3(size), vec2i(cimg), vec2i(simg), timestamp, label, points3f(pc));
+           }), py::arg("center"), py::arg("size"), py::arg("center_img_frame"), py::arg("size_img_frame"),
+           py::arg("timestamp") = 0.0, py::arg("label") = "", py::arg("pc_points") = py::list())
+      .def_property("center", [](const Bbox3D &b) { return arr(b.center); },
+                    [](Bbox3D &b, const py::object &o) { b.center = vec3(o); })
+      .def_property("size", [](const Bbox3D &b) { return arr(b.size); },
+                    [](Bbox3D &b, const py::object &o) { b.size = vec3(o); })
+      .def_property("center_img_frame", [](const Bbox3D &b) { return arr(b.center_img_frame); },
+                    [](Bbox3D &b, const py::object &o) { b.center_img_frame = vec2i(o); })
+      .def_property("size_img_frame", [](const Bbox3D &b) { return arr(b.size_img_frame); },
+                    [](Bbox3D &b, const py::object &o) { b.size_img_frame = vec2i(o); })
+      .def_property("pc_points", [](const Bbox3D &b) { return arrs(b.pc_points); },
+                    [](Bbox3D &b, const py::object &o) { b.pc_points = points3f(o); })
+      .def_readwrite("timestamp", &Bbox3D::timestamp)
+      .def_readwrite("label", &Bbox3D::label);
 
   // ------------------------------------------------------------ configure
   auto cfg = m.def_submodule("configure", "Configuration classes");
@@ -565,6 +672,39 @@ PYBIND11_MODULE(kompass_cpp, m) {
          py::arg("x_offset"), py::arg("y_offset"), py::arg("z_offset"), py::arg("max_range"), py::arg("min_z"),
          py::arg("max_z"), py::arg("num_bins"),
          "Converts raw PointCloud2 to ranges only, using a fixed number of bins.");
+
+
+  // ---------------------------------------------------------------- vision
+  // (bindings_vision.cpp): the frame goes to kc_depth_boxes by pointer and strides
+  auto vi = m.def_submodule("vision", "Vision and Detection module");
+  auto compute = [](DepthDetector &self, const py::array &depth_img, const std::vector<Bbox2D> &boxes,
+                    float robot_x, float robot_y, float robot_yaw, float robot_speed) {
+    const DepthImageView v = depthView(depth_img);
+    {
+      py::gil_scoped_release nogil;
+      self.updateBoxes(v, boxes, std::optional<Path::State>(Path::State(robot_x, robot_y, robot_yaw, robot_speed)));
+    }
+    return self.get3dDetections().value_or(std::vector<Bbox3D>{});
+  };
+  py::class_<DepthDetector>(vi, "DepthDetector")
+      .def(py::init([](const py::object &depth_range, const py::object &t, const py::object &rot_xyzw,
+                       const py::object &focal, const py::object &principal, float factor) {
+             const Eigen::Vector4f q = vec4(rot_xyzw);
+             return std::make_unique<DepthDetector>(vec2f(depth_range), vec3(t), Eigen::Quaternionf(q(3), q(0), q(1), q(2)),
+                                                    vec2f(focal), vec2f(principal), factor);
+           }), py::arg("depth_range"), py::arg("camera_in_body_translation"), py::arg("camera_in_body_rotation"),
+           py::arg("focal_length"), py::arg("principal_point"), py::arg("depth_conversion_factor") = 1e-3,
+           "Initialize with camera translation and rotation (Vector4f as [x, y, z, w]).")
+      .def("compute_3d_detections", compute, py::arg("depth_img"), py::arg("input"), py::arg("robot_x"),
+           py::arg("robot_y"), py::arg("robot_yaw"), py::arg("robot_speed"))
+      .def("compute_3d_detections",
+           [compute](DepthDetector &self, const py::array &depth_img, const PointsOfInterest &poi, float robot_x,
+                     float robot_y, float robot_yaw, float robot_speed) {
+             return compute(self, depth_img, std::vector<Bbox2D>{Bbox2D(poi)}, robot_x, robot_y, robot_yaw,
+                            robot_speed);
+           },
+           py::arg("depth_img"), py::arg("input"), py::arg("robot_x"), py::arg("robot_y"), py::arg("robot_yaw"),
+           py::arg("robot_speed"));
 
   // ---------------------------------------------------------- module level
   py::enum_<LogLevel>(m, "LogLevel")

@@ -148,6 +148,8 @@ class DynMat {
 };
 using MatrixXi = DynMat<int, false>;   // column-major like Eigen's default
 using MatrixXf = DynMat<float, false>;
+template <typename T>
+using MatrixX = DynMat<T, false>;
 
 }  // namespace Eigen
 

@@ -196,6 +196,15 @@ SIGNATURES = {
     "kc_cloud_last_rebinned": (C.c_int, [_vp, C.POINTER(_sz)]),
     "kc_cloud_timing_enable": (C.c_int, [_vp, C.c_int]),
     "kc_cloud_timing_get": (C.c_int, [_vp, C.POINTER(C.c_char_p), _fp, _sz, C.POINTER(_sz)]),
+    "kc_depth_create": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, C.c_int, C.POINTER(_vp)]),
+    "kc_depth_destroy": (None, [_vp]),
+    "kc_depth_boxes": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _ip, _sz, _dp,
+                                 _fp, _ip, _sz, C.POINTER(_sz)]),
+    "kc_depth_box_stats": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _ip, _sz,
+                                     C.POINTER(C.c_int64), _fp]),
+    "kc_depth_last_upload": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "kc_depth_timing_enable": (C.c_int, [_vp, C.c_int]),
+    "kc_depth_timing_get": (C.c_int, [_vp, C.POINTER(C.c_char_p), _fp, _sz, C.POINTER(_sz)]),
 }
 
 _lib = None
@@ -965,3 +974,88 @@ class ZoneContext:
         n = _sz(0)
         _check(lib().kc_zone_indices(self.h, int(bool(forward)), out, self.n, C.byref(n)))
         return np.array(out[:n.value], dtype=np.int64)
+
+
+class DepthContext:
+    """Owner of one kc_depth context (DepthDetector: 2-D boxes -> 3-D boxes)."""
+
+    def __init__(self, depth_range, camera_in_body_translation, camera_in_body_rotation, focal_length,
+                 principal_point, depth_conversion_factor=1e-3, device=0):
+        dr, t, q = _f32(depth_range), _f32(camera_in_body_translation), _f32(camera_in_body_rotation)
+        f, p = _f32(focal_length), _f32(principal_point)
+        if dr.shape != (2,) or t.shape != (3,) or q.shape != (4,) or f.shape != (2,) or p.shape != (2,):
+            raise ValueError("depth_range (2), translation (3), rotation xyzw (4), focal (2), principal (2)")
+        self.h = _vp()
+        _check(lib().kc_depth_create(_pf(dr), _pf(t), _pf(q), _pf(f), _pf(p), float(np.float32(depth_conversion_factor)),
+                                     int(device), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().kc_depth_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _frame(img, device_ptr, shape, strides):
+        """(address, on_device, rows, cols, row_stride, col_stride) in elements; `img` is kept alive by the caller."""
+        if device_ptr is not None:
+            rows, cols = (int(v) for v in shape)
+            rs, cs = (int(v) for v in strides) if strides is not None else (cols, 1)
+            return int(device_ptr), 1, rows, cols, rs, cs
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint16:
+            raise TypeError("the depth frame must be a uint16 numpy array")
+        if img.ndim != 2:
+            raise ValueError(f"the depth frame must be 2-D (H, W), got shape {img.shape}")
+        rs, cs = (s // 2 for s in img.strides)
+        return img.__array_interface__["data"][0], 0, img.shape[0], img.shape[1], rs, cs
+
+    @staticmethod
+    def _boxes(boxes):
+        b = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+        return b, b.ctypes.data_as(_ip)
+
+    def boxes(self, img, boxes, state=None, device_ptr=None, shape=None, strides=None):
+        """(centres [m, 3], sizes [m, 3], kept input indices [m]) of the kept boxes.  boxes: [n, 4] of
+        (top.x, top.y, size.x, size.y); state: (x, y, yaw) or None to keep the previous one."""
+        addr, on_dev, rows, cols, rs, cs = self._frame(img, device_ptr, shape, strides)
+        b, pb = self._boxes(boxes)
+        n = len(b)
+        out = np.zeros((max(n, 1), 6), np.float32)
+        idx = np.zeros(max(n, 1), np.int32)
+        st = None if state is None else _f64(state)
+        m = _sz(0)
+        _check(lib().kc_depth_boxes(self.h, addr, on_dev, rows, cols, rs, cs, pb, n, _pd(st), _pf(out),
+                                    idx.ctypes.data_as(_ip), max(n, 1), C.byref(m)))
+        k = m.value
+        return out[:k, :3].copy(), out[:k, 3:].copy(), idx[:k].copy()
+
+    def box_stats(self, img, boxes, device_ptr=None, shape=None, strides=None):
+        """(count [n] int64, [n, 4] float32 of median, mad, min_d, max_d)."""
+        addr, on_dev, rows, cols, rs, cs = self._frame(img, device_ptr, shape, strides)
+        b, pb = self._boxes(boxes)
+        n = len(b)
+        cnt = np.zeros(max(n, 1), np.int64)
+        st = np.zeros((max(n, 1), 4), np.float32)
+        _check(lib().kc_depth_box_stats(self.h, addr, on_dev, rows, cols, rs, cs, pb, n,
+                                        cnt.ctypes.data_as(C.POINTER(C.c_int64)), _pf(st)))
+        return cnt[:n], st[:n]
+
+    def last_upload(self) -> int:
+        n = _sz(0)
+        _check(lib().kc_depth_last_upload(self.h, C.byref(n)))
+        return n.value
+
+    def timing_enable(self, on=True):
+        _check(lib().kc_depth_timing_enable(self.h, int(bool(on))))
+
+    def timings(self):
+        names = (C.c_char_p * 16)()
+        ms = (C.c_float * 16)()
+        n = _sz(0)
+        _check(lib().kc_depth_timing_get(self.h, names, ms, 16, C.byref(n)))
+        return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
