@@ -527,7 +527,9 @@ int kc_dwa_timing_get(kc_dwa *ctx, const char **names, float *ms, size_t cap,
 typedef struct kc_mapper kc_mapper;
 
 /* LocalMapper / LocalMapperGPU ctor (mapping/local_mapper.h:14-56,
- * local_mapper_gpu.h:15-66) -- the scan -> grid subset */
+ * local_mapper_gpu.h:15-66) -- the scan -> grid subset.  KC_ERR_RANGE for a
+ * sensor whose offset position / resolution is not below 2^30 cells
+ * (DESIGN.md §5). */
 int kc_mapper_create(int grid_height, int grid_width, float resolution,
                      const float laserscan_position[3],
                      float laserscan_orientation, size_t max_scan_size,

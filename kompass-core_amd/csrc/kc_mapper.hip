@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "kc_internal.h"
@@ -77,11 +78,24 @@ __device__ __forceinline__ BeamLine beam_line(const MapGeom &g, int2 t) {
 
 // bresenhamEnhanced (line_drawing.h:55-124) in closed form: after major-axis
 // step i (1..n), e_i = dmaj + i*ddmin, k_i = floor((e_i - 1)/ddmaj) minor
-// increments so far, error_i = e_i - k_i*ddmaj in [1, ddmaj].  This is k_i,
-// from a double quotient: exact while e_i < 2^53.
+// increments so far, error_i = e_i - k_i*ddmaj in [1, ddmaj].  This is k_i:
+// the double quotient is exact while e_i - 1 + ddmaj <= 2^53 (every line of
+// fewer than kExactQuotientSteps steps), and otherwise within one of k_i (its
+// relative error is ~2^-52 and k_i < 2^31): kCorrect adds the 64-bit remainder
+// test, so k_i is exact for every line of this build (sensor and end cell
+// within 2^30 cells: e_i < 2^63).
+constexpr int kExactQuotientSteps = (1 << 26) - 2;  // n + 2 n^2 + 2 n <= 2^53
+
+template <bool kCorrect = true>
 __device__ __forceinline__ long long minor_after(const BeamLine &l, int i) {
-  return static_cast<long long>(floor(
-      static_cast<double>(l.dmaj + static_cast<long long>(i) * l.ddmin - 1) / static_cast<double>(l.ddmaj)));
+  const long long num = l.dmaj + static_cast<long long>(i) * l.ddmin - 1;
+  long long k = static_cast<long long>(floor(static_cast<double>(num) / static_cast<double>(l.ddmaj)));
+  if (kCorrect) {
+    const long long r = num - k * l.ddmaj;
+    if (r < 0) --k;
+    else if (r >= l.ddmaj) ++k;
+  }
+  return k;
 }
 
 // Steps [x, y] of [max(first, 1), min(last, nsteps)] whose stamps can land on
@@ -99,9 +113,9 @@ __device__ __forceinline__ int2 step_range(const BeamLine &l, int A0, int A1, in
 // ifirst..ilast, from the closed-form state before step ifirst.  stamp(a, b)
 // takes major / minor coordinates; each step stamps (a, b - bstep) below the
 // line, (a - astep, b) above it, both on it, then (a, b).
-template <class Int, class Stamp>
+template <class Int, bool kCorrect, class Stamp>
 __device__ __forceinline__ void walk_steps(const BeamLine &l, int ifirst, int ilast, Stamp stamp) {
-  const long long k = minor_after(l, ifirst - 1);
+  const long long k = minor_after<kCorrect>(l, ifirst - 1);
   const Int ddmaj = static_cast<Int>(l.ddmaj), ddmin = static_cast<Int>(l.ddmin);
   Int error = static_cast<Int>(l.dmaj + static_cast<long long>(ifirst - 1) * l.ddmin - k * l.ddmaj);
   int a = l.a0 + l.astep * (ifirst - 1);
@@ -121,14 +135,18 @@ __device__ __forceinline__ void walk_steps(const BeamLine &l, int ifirst, int il
   }
 }
 
-// body(Int{}) with the error type of the line's walk: the error term stays in
-// [1, ddmaj] and the sums below 2 ddmaj, so 32 bits while nsteps < 2^28.  (The
-// beam-parallel kernel chooses once per beam, outside its lane loop: a branch
-// per step made the plain scan's rays_kernel 1.5 % slower.)
-template <class Body>
+// body(Int{}, kCorrect) with the error type of the line's walk -- the error
+// term stays in [1, ddmaj] and the sums below 2 ddmaj, so 32 bits while
+// nsteps < 2^28 -- and whether its closed-form quotient needs the remainder
+// test (minor_after).  (The beam-parallel kernel chooses once per beam, outside
+// its lane loop: a branch per step made the plain scan's rays_kernel 1.5 %
+// slower, and the remainder test in every step 3 %.  The tiled walks start from
+// the closed form once per chunk of steps and keep the test: kSkipExact false.)
+template <bool kSkipExact, class Body>
 __device__ __forceinline__ void with_error_type(const BeamLine &l, Body body) {
-  if (l.nsteps < (1 << 28)) body(int{});
-  else body(0LL);
+  if (kSkipExact && l.nsteps < kExactQuotientSteps) body(int{}, std::false_type{});
+  else if (l.nsteps < (1 << 28)) body(int{}, std::true_type{});
+  else body(0LL, std::true_type{});
 }
 
 // ---- M3: which beam decides a cell -------------------------------------------
@@ -183,8 +201,9 @@ __global__ __launch_bounds__(64 * kBeamsPerBlock) void rays_kernel(
   // x-major line then fall into a few 64-byte lines of the column-major grid instead of 64 -- the L2's write
   // transactions, not the arithmetic, bound this pass (a contiguous chunk of steps per lane: 18.6 us at 4096 beams
   // x ~500 steps).  (A counter from 0: i += 64 near INT_MAX would overflow.)
-  with_error_type(l, [&](auto e) {
-    for (int c = lane; c <= w.y - w.x; c += 64) walk_steps<decltype(e)>(l, w.x + c, w.x + c, stamp);
+  with_error_type<true>(l, [&](auto e, auto correct) {
+    for (int c = lane; c <= w.y - w.x; c += 64)
+      walk_steps<decltype(e), decltype(correct)::value>(l, w.x + c, w.x + c, stamp);
   });
 }
 
@@ -342,7 +361,9 @@ __device__ void tile_accumulate(const MapGeom &g, const int2 *__restrict__ ends,
           else L.cell[idx] = 1u;
         }
       };
-      with_error_type(l, [&](auto e) { walk_steps<decltype(e)>(l, task.ifirst, task.ilast, stamp); });
+      with_error_type<false>(l, [&](auto e, auto correct) {
+        walk_steps<decltype(e), decltype(correct)::value>(l, task.ifirst, task.ilast, stamp);
+      });
     }
     __syncthreads();
   }
@@ -478,6 +499,11 @@ __device__ __forceinline__ float bayes_cell(const BayesParams &bp, float res, fl
 // (gridDataProb.fill, :227).  The tag grid is cleared for the next scan on the
 // way.  A workgroup covers 64 x 4 cells: each wave reads four whole tag lines
 // and four 64-byte runs of the column-major probability grids.
+// The reference squares the offset in int, which overflows once the sensor is
+// more than 46 340 cells from the cell: kWide squares in 64 bits;
+// without it (every cell within 2^15 cells of the sensor on both axes, which
+// the host checks) the int square is exact and cheaper.
+template <bool kWide>
 __global__ __launch_bounds__(256) void bayes_cells_kernel(
     MapGeom g, BayesParams bp, const float *__restrict__ ranges, unsigned int *__restrict__ last,
     int hb, const float *__restrict__ prev, float *__restrict__ prob) {
@@ -490,9 +516,14 @@ __global__ __launch_bounds__(256) void bayes_cells_kernel(
   const unsigned int tag = last[tk];
   float v = bp.p_prior;
   if (tag != 0u) {
-    const int di = i - g.s0, dj = j - g.s1;
-    const float distance =
-        static_cast<float>(static_cast<int>(kc::dsqrt_rn(static_cast<double>(di * di + dj * dj))));
+    float distance;
+    if (kWide) {
+      const long long di = i - g.s0, dj = j - g.s1;
+      distance = static_cast<float>(static_cast<long long>(kc::dsqrt_rn(static_cast<double>(di * di + dj * dj))));
+    } else {
+      const int di = i - g.s0, dj = j - g.s1;
+      distance = static_cast<float>(static_cast<int>(kc::dsqrt_rn(static_cast<double>(di * di + dj * dj))));
+    }
     v = bayes_cell(bp, g.res, distance, ranges[tag - 1u], prev[k]);
     last[tk] = 0u;
   }
@@ -736,9 +767,15 @@ int run_scan(kc_mapper *m, const double *angles, const double *ranges,
   KC_TRY(m->timing.stop(s));
   if (bayes) {
     KC_TRY(m->timing.start("bayes_cells_kernel", s));
-    hipLaunchKernelGGL(bayes_cells_kernel, dim3((m->g.H + 63) / 64, (m->g.W + 3) / 4), dim3(256),
-                       0, s, m->g, m->bp, m->d_ranges.p, m->d_last.p, hb, m->d_prev.p,
-                       m->d_prob.p);
+    const auto far = [](int s0, int n) { return std::max(std::abs(static_cast<long long>(s0)),
+                                                          std::abs(static_cast<long long>(n) - 1 - s0)) >= (1 << 15); };
+    const dim3 cgrid((m->g.H + 63) / 64, (m->g.W + 3) / 4);
+    if (far(m->g.s0, m->g.H) || far(m->g.s1, m->g.W))
+      hipLaunchKernelGGL(bayes_cells_kernel<true>, cgrid, dim3(256), 0, s, m->g, m->bp, m->d_ranges.p, m->d_last.p,
+                         hb, m->d_prev.p, m->d_prob.p);
+    else
+      hipLaunchKernelGGL(bayes_cells_kernel<false>, cgrid, dim3(256), 0, s, m->g, m->bp, m->d_ranges.p, m->d_last.p,
+                         hb, m->d_prev.p, m->d_prob.p);
     KC_TRY(m->timing.stop(s));
     hipLaunchKernelGGL(scan_done_kernel, dim3(1), dim3(1), 0, s, m->h_seq.p, m->seq);
   }
@@ -766,6 +803,10 @@ int kc_mapper_create(int H, int W, float res, const float pos[3], float orient,
     KC_FAIL(KC_ERR_INVALID, "grid dimensions and resolution must be positive");
   if (static_cast<size_t>(H) * W > 0x3FFFFFFFul)
     KC_FAIL(KC_ERR_RANGE, "grid too large");
+  // localToGrid's int conversion of the sensor position (local_mapper.h:216-219): the same 2^30 rule as for the
+  // end cell of a beam, so every line of the walk has fewer than 2^31 steps
+  if (!(std::fabs(pos[0] / res) < kMaxCellOffset && std::fabs(pos[1] / res) < kMaxCellOffset))
+    KC_FAIL(KC_ERR_RANGE, "sensor position not below 2^30 cells from the grid centre");
   int ndev = 0;
   KC_HIP(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev)

@@ -528,8 +528,9 @@ def scan_to_grid(H, W, res, position, orientation, angles, ranges):
     p = _f32(position)
     a, r = _f64(angles), _f64(ranges)
     g = np.zeros(H * W, np.int32)
-    lib().ko_mapper_scan_to_grid(H, W, float(np.float32(res)), _pf(p), float(np.float32(orientation)),
-                                 _pd(a), _pd(r), len(a), _pi(g))
+    if lib().ko_mapper_scan_to_grid(H, W, float(np.float32(res)), _pf(p), float(np.float32(orientation)),
+                                    _pd(a), _pd(r), len(a), _pi(g)) != 0:
+        raise ValueError("sensor position not below 2^30 cells from the grid centre")
     return g.reshape(W, H).T.copy()  # column-major (i + j*H) -> [i, j]
 
 

@@ -1809,8 +1809,8 @@ int ko_mapper_scan_to_grid(int H, int W, float res, const float pos[3],
   const int c0 = (int)round((double)(H / 2)) - 1;
   const int c1 = (int)round((double)(W / 2)) - 1;
   /* localToGrid, local_mapper.h:210-222 */
-  const int s0 = c0 + (int)(pos[0] / res);
-  const int s1 = c1 + (int)(pos[1] / res);
+  int s0, s1;
+  if (!beam_end(pos[0], pos[1], res, c0, c1, &s0, &s1)) return -1; /* the sensor: same 2^30 rule */
   for (size_t k = 0; k < (size_t)H * (size_t)W; ++k) grid[k] = KO_UNEXPLORED;
   grid_sink s = {grid, H, W, 0, 0};
   for (size_t b = 0; b < n; ++b) {
@@ -1842,6 +1842,8 @@ ko_bmap *ko_bmap_create(int H, int W, float res, const float pos[3], float orien
                         float p_prior, float p_occupied, float p_empty,
                         float range_sure, float range_max, float wall_size) {
   if (H <= 0 || W <= 0 || !(res > 0.0f) || !pos) return NULL;
+  /* localToGrid of the sensor: the 2^30 rule of the end cells */
+  if (!(fabsf(pos[0] / res) < 0x1p30f && fabsf(pos[1] / res) < 0x1p30f)) return NULL;
   ko_bmap *b = (ko_bmap *)calloc(1, sizeof(*b));
   if (!b) return NULL;
   b->H = H;
@@ -1914,8 +1916,9 @@ static inline void bayes_emit(bayes_sink *s, int i, int j) {
   if (i >= 0 && i < b->H && j >= 0 && j < b->W) {
     /* (pt - m_startPoint).norm() on Vector2i: Eigen's integer norm, the double
      * sqrt truncated back to int */
-    const int di = i - b->s0, dj = j - b->s1;
-    const float distance = (float)(int)sqrt((double)(di * di + dj * dj));
+    const long long di = (long long)i - b->s0, dj = (long long)j - b->s1;
+    /* 64-bit squared norm: the reference's int overflows from 46 341 cells on */
+    const float distance = (float)(long long)sqrt((double)(di * di + dj * dj));
     const size_t k = (size_t)i + (size_t)j * (size_t)b->H;
     s->prob[k] = bayes_cell(b, distance, s->range, b->prev[k]);
     grid_emit(&s->g, i, j);

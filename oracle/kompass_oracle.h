@@ -248,7 +248,9 @@ size_t ko_dwa_closest_index(const ko_dwa *d);
 /* ---- M1/M2: LocalMapper (CPU semantics) ---------------------------------- */
 /* local_mapper.h:14-56,198-222; local_mapper.cpp:127-159,204-220;
  * line_drawing.h:55-124.  grid_out is column-major int32 [H x W]
- * (Eigen::MatrixXi), i.e. cell (i,j) at i + j*H. */
+ * (Eigen::MatrixXi), i.e. cell (i,j) at i + j*H.  Returns -1 (and writes
+ * nothing) for a sensor whose offset position / resolution is not below 2^30
+ * cells; ko_bmap_create returns NULL for one. */
 int ko_mapper_scan_to_grid(int grid_height, int grid_width, float resolution,
                            const float laserscan_position[3],
                            float laserscan_orientation, const double *angles,
