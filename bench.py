@@ -12,10 +12,16 @@ resident in HBM before the timed region starts.
 
 The headline line is BASELINE configs[1] on SURVEY 8(d)'s scene (Bernoulli 0.02
 clutter: only ~5 % of the samples survive the collision gate, so the cost stage
-has little to do -- `config.workload` says how many).  The same JSON line
-therefore carries the cycle on two more scenes of the same lattice, each with
-its own value / roofline / cpu_baseline: `mid_density` (about half admissible)
-and `open_space` (every sample admissible).
+has little to do -- `config.workload` says how many).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps,
+--dump-outputs, one JSON line.  `--full` adds everything else the line measures
+and checks: per-kernel HIP-event times and the roofline (a second pass over the
+steps), the CPU baseline with its winner check, and the legs beside the headline
+-- the cycle on two more scenes of the same lattice (`mid_density`: about half
+admissible, `open_space`: every sample admissible), LaserScan input, the input
+updates, fresh inputs every cycle, the cfg4 mapper; with several ranks the
+strong-scaling block.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`.  For N > 1 the ranks are one
 process per GPU: either the caller starts them (`python -m torch.distributed.run --nnodes=1
@@ -320,19 +326,20 @@ def controller_bench(args, rank, world, local_rank):
         dumped = cycle_outputs(ctx, last, ranks)
         if rank == 0:
             write_outputs(args.dump_outputs, dumped)
-    # ---- same cycles again with HIP events around every kernel, recorded on the
-    # stream the kernels are launched on (roofline leg; events cost a few us per
-    # cycle, so they stay out of `value`)
-    ctx.timing_enable(True)
     kernel_ms, host_ms = {}, {}
-    for i in range(args.steps):
-        one_cycle(i)
-        for name, ms in ctx.timings():
-            (host_ms if name.startswith("host:") else kernel_ms).setdefault(name, []).append(ms)
-    ctx.timing_enable(False)
-    last = one_cycle(args.steps - 1)
+    if args.full:
+        # ---- same cycles again with HIP events around every kernel, recorded on the
+        # stream the kernels are launched on (roofline leg; events cost a few us per
+        # cycle, so they stay out of `value`)
+        ctx.timing_enable(True)
+        for i in range(args.steps):
+            one_cycle(i)
+            for name, ms in ctx.timings():
+                (host_ms if name.startswith("host:") else kernel_ms).setdefault(name, []).append(ms)
+        ctx.timing_enable(False)
+        last = one_cycle(args.steps - 1)
 
-    # ---- result of the last cycle (for the parity check below) -------------
+    # ---- result of the last cycle, pose(args.steps - 1) (for the parity check below) ----
     found, cost, raw = bool(last.found), float(last.cost), int(last.raw_index)
     if use_dist:
         # what the transport itself reports: ncclCommCount / ncclCommUserRank / ncclCommCuDevice (kc_comm_query)
@@ -347,7 +354,7 @@ def controller_bench(args, rank, world, local_rank):
         steps_total = n_total * P  # trajectory-steps per cycle over all ranks
         value = steps_total * args.steps / elapsed
         # (the same pose as the cpu_baseline's winner and count: the last timed cycle)
-        n_adm = int(ctx.cycle(pose(args.steps - 1), P).n_admissible) if not use_dist else None
+        n_adm = int(last.n_admissible) if not use_dist else None
         n_adm_global = int(last.n_admissible) if use_dist else n_adm
         robot = 'omni' if base['ctr'] == 2 else 'diff-drive' if base['ctr'] == 1 else 'Ackermann'
         out = {
@@ -364,10 +371,6 @@ def controller_bench(args, rank, world, local_rank):
                             f"collision-checked, costs are computed for the admissible samples",
                 "scene": args.scene, "n_admissible": n_adm, "n_admissible_all_ranks": n_adm_global,
                 "samples_per_gpu": count, "global_samples": n_total, "points": P,
-                "launches_per_cycle": len(kernel_ms),
-                "cycle": "single launch (kc_dwa_cycle)" if "cycle_kernel" in kernel_ms else
-                         "three kernels" + (" (--split)" if args.split else " (kc_dwa_cycle keeps them beyond one resident "
-                                            "wave of workgroups and for small shards with many survivors)"),
                 "parallelism": f"sample-shard x{world}" if world > 1 else "single GPU",
                 "trig": ("device: the roll-out kernel evaluates glibc's sincos algorithm itself, bit-equal to the host libm "
                          "(csrc/kc_trig_exact.h); no host table, no host threads in the cycle"
@@ -375,12 +378,18 @@ def controller_bench(args, rank, world, local_rank):
             },
             "latency_p50_ms": float(np.percentile(np.array(lat) * 1e3, 50)),
             "latency_min_ms": float(np.min(lat) * 1e3), "latency_max_ms": float(np.max(lat) * 1e3),
-            "kernels_ms": {k: float(np.mean(v)) for k, v in kernel_ms.items()},
-            "host_phases_ms": {k: float(np.mean(v)) for k, v in host_ms.items()},
-            "roofline": roofline_of(kernel_ms, count, P, base["map_side"], S, O, args.scene, cfg),
             "winner": {"found": found, "cost": cost, "raw_index": raw},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            out["config"]["launches_per_cycle"] = len(kernel_ms)
+            out["config"]["cycle"] = (
+                "single launch (kc_dwa_cycle)" if "cycle_kernel" in kernel_ms else
+                "three kernels" + (" (--split)" if args.split else " (kc_dwa_cycle keeps them beyond one resident "
+                                   "wave of workgroups and for small shards with many survivors)"))
+            out["kernels_ms"] = {k: float(np.mean(v)) for k, v in kernel_ms.items()}
+            out["host_phases_ms"] = {k: float(np.mean(v)) for k, v in host_ms.items()}
+            out["roofline"] = roofline_of(kernel_ms, count, P, base["map_side"], S, O, args.scene, cfg)
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(inp, vx, vy, om, pose(args.steps - 1), found, cost, raw, args,
                                                args.cpu_seconds)
         if use_dist:
@@ -398,7 +407,7 @@ def controller_bench(args, rank, world, local_rank):
             out["ranks"] = seen
             out["ranks_agree"] = all(s_["winner"] == seen[0]["winner"] for s_ in seen)
             out["winner"]["index"] = int(last.index)
-        if world == 1 and not use_dist and not args.only_headline:
+        if world == 1 and not use_dist and args.full and not args.only_headline:
             # the same lattice on the two other scenes: each a bench line of its own
             for key, scene in (("mid_density", "mid"), ("open_space", "open")):
                 if scene == args.scene:
@@ -418,7 +427,7 @@ def controller_bench(args, rank, world, local_rank):
             margs = argparse.Namespace(**vars(args))
             margs.steps, margs.warmup = min(args.steps, 500), min(args.warmup, 50)
             out["mapper_cfg4"] = mapper_bench(margs)
-    if use_dist and not args.only_headline:
+    if use_dist and args.full and not args.only_headline:
         strong = {}
         for scfg in ("cfg3", "cfg5"):
             leg = strong_leg(kh, syn, sharding, scfg, rank, world, device, comm, args, ranks)
@@ -1463,8 +1472,11 @@ def main():
                     help="only the fresh_inputs leg (one reference cycle per step), as the top-level line (profiling passes)")
     ap.add_argument("--scan", action="store_true",
                     help="only the laserscan_room leg (LaserScan input, 1440 beams), as the top-level line (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel times and roofline, the CPU baseline and the other legs "
+                         "(scenes, LaserScan, input updates, fresh inputs, mapper; with several ranks the strong-scaling block)")
     ap.add_argument("--only-headline", action="store_true",
-                    help="no mid_density / open_space / extras legs (profiling passes: one scene per process)")
+                    help="with --full: no mid_density / open_space / extras legs (profiling passes: one scene per process)")
     ap.add_argument("--mapper", action="store_true", help="bench the LocalMapper (cfg4) instead")
     ap.add_argument("--bayes", action="store_true", help="with --mapper: the Bayesian mapping loop (8f rank 3)")
     ap.add_argument("--pointcloud", action="store_true", help="SURVEY 8f rank 1 instead of the controller")

@@ -2,7 +2,7 @@
 
     python3 tools/pmc_collect.py OUT_DIR NAME -- <bench.py arguments>
 
-e.g.  python3 tools/pmc_collect.py gpurun_out/r03_b cfg2_survey -- --only-headline --no-cpu --scene survey
+e.g.  python3 tools/pmc_collect.py out/r03_b cfg2_survey -- --full --only-headline --no-cpu --scene survey
 
 Seven runs of the same command: `--kernel-trace --stats` (kernel times), then SEPARATE counter passes --
 FETCH_SIZE, WRITE_SIZE and four SQ groups -- each with --kernel-trace only (never combined with another

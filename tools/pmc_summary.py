@@ -39,7 +39,7 @@ def main(fetch_csv, write_csv, out):
         kernels[k] = {"FETCH_SIZE_KB_mean": f, "launches_FETCH_SIZE": len(fe.get(k, [])),
                       "WRITE_SIZE_KB_mean": w, "launches_WRITE_SIZE": len(wr.get(k, [])),
                       "hbm_bytes_per_launch_corrected": int(round((2.0 * f + w) * 1024))}
-    doc = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 50 --warmup 5 "
+    doc = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 50 --warmup 5 "
                       "--no-cpu (two separate passes)",
            "unit_note": "rocprofv3 reports FETCH_SIZE / WRITE_SIZE in KB; corrected = (2 x FETCH + WRITE) x 1024 "
                         "(gfx950 FETCH_SIZE halves wide reads; upper bound for narrower ones)",

@@ -6,12 +6,12 @@ set -e
 TAG=${1:-r04_a}
 O=gpurun_out/$TAG
 mkdir -p $O
-for c in cfg1 cfg3 cfg5; do python bench.py --config $c > $O/${c}_bench.json 2>> $O/extra.err; done
+for c in cfg1 cfg3 cfg5; do python bench.py --full --config $c > $O/${c}_bench.json 2>> $O/extra.err; done
 for c in cfg3 cfg5; do for s in mid open; do
-  python bench.py --config $c --scene $s --only-headline --no-cpu --steps 300 --warmup 30 > $O/${c}_${s}_bench.json 2>> $O/extra.err
+  python bench.py --full --config $c --scene $s --only-headline --no-cpu --steps 300 --warmup 30 > $O/${c}_${s}_bench.json 2>> $O/extra.err
 done; done
-python bench.py --split --only-headline > $O/cfg2_split_bench.json 2>> $O/extra.err
-KC_BENCH_FORCE_DIST=1 python bench.py --only-headline --no-cpu > $O/cfg2_world1_rccl_bench.json 2>> $O/extra.err
+python bench.py --full --split --only-headline > $O/cfg2_split_bench.json 2>> $O/extra.err
+KC_BENCH_FORCE_DIST=1 python bench.py --full --only-headline --no-cpu > $O/cfg2_world1_rccl_bench.json 2>> $O/extra.err
 python bench.py --ref cost5k > $O/cost5k_bench.json 2>> $O/extra.err
 python bench.py --ref mapper400 > $O/mapper400_bench.json 2>> $O/extra.err
 python bench.py --mapper > $O/cfg4_mapper_bench.json 2>> $O/extra.err

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): tools/profile_round.sh TAG [quick]
-# The default bench line, then rocprofv3 evidence (tools/pmc_collect.py: kernel stats + separate counter
+# The full bench line (--full), then rocprofv3 evidence (tools/pmc_collect.py: kernel stats + separate counter
 # passes) for every workload the bench JSON prices: cfg2 on the three scenes, the fresh-input reference cycle
 # (sensor build pair + window + segment + cycle), cfg4 mapper, cfg3 / cfg5 mid (three-kernel cycle:
 # sample_cost_kernel), the reference's cost workload (velocity_sums_kernel); phase clocks of the cycle kernel.
@@ -8,9 +8,9 @@ set -e
 TAG=${1:-r04_a}
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/cfg2_bench.json 2> $O/cfg2_bench.err || { tail -5 $O/cfg2_bench.err; exit 1; }
+python bench.py --full > $O/cfg2_bench.json 2> $O/cfg2_bench.err || { tail -5 $O/cfg2_bench.err; exit 1; }
 tail -c 400 $O/cfg2_bench.json; echo
-C="--only-headline --no-cpu --steps 200 --warmup 20"
+C="--full --only-headline --no-cpu --steps 200 --warmup 20"
 for scene in survey mid open; do
   python3 tools/pmc_collect.py $O cfg2_$scene -- $C --scene $scene
 done
