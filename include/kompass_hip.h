@@ -672,6 +672,38 @@ int kc_zone_indices(kc_zone *ctx, int forward, int64_t *out, size_t cap,
                     size_t *count_out);
 
 /* ------------------------------------------------------------------------ */
+/* Deformable Virtual Zone (kompass_core/algorithms/dvz.py)                 */
+/* ------------------------------------------------------------------------ */
+typedef struct kc_dvz kc_dvz;
+
+/* The zone of DeformableVirtualZone as update_zone_size / _init_constant_zone_
+ * parameters (dvz.py:105-117, 151-172) leave it: zone_major_radius,
+ * zone_minor_radius, zone_center_shift_x / _y, zone_ori_shift.  The constant
+ * term C of _get_undeformed_radius (:232-236) is formed from them by the call. */
+typedef struct kc_dvz_zone {
+  double major_radius, minor_radius;
+  double center_shift_x, center_shift_y;
+  double ori_shift;
+} kc_dvz_zone;
+
+/* A context for scans of up to max_beams (1 .. 2^24) beams on `device`. */
+int kc_dvz_create(int device, size_t max_beams, kc_dvz **out);
+void kc_dvz_destroy(kc_dvz *ctx);
+/* get_total_deformation's loop (dvz.py:372-404) in one launch: per beam the
+ * undeformed radius (_get_undeformed_radius, :213-245, squares as products),
+ * the deformed radius (_get_deformation_radius, :247-266) and, for a deformed
+ * beam, (undeformed - deformed) / deformed and that times convert_to_0_2pi(angle).
+ * out = {sum of the first, sum of the second, number of deformed beams}, summed
+ * in double in a fixed order (the same bits on every call); the caller
+ * normalises (_regulate_deformation).  radii_or_null: n deformed radii
+ * (deformation_plot).  n == 0 launches nothing and gives zeros.  KC_ERR_INVALID
+ * for null pointers or a radius that is not > 0, KC_ERR_RANGE for n above the
+ * context's capacity, both before any device use. */
+int kc_dvz_deform(kc_dvz *ctx, const kc_dvz_zone *zone, const double *angles,
+                  const double *ranges, size_t n, double out[3],
+                  double *radii_or_null);
+
+/* ------------------------------------------------------------------------ */
 /* DepthDetector: 2-D detections -> 3-D boxes (vision/depth_detector.cpp)    */
 /* ------------------------------------------------------------------------ */
 typedef struct kc_depth kc_depth;

@@ -11,6 +11,7 @@
 
 #include "controllers/dwa.h"
 #include "controllers/pure_pursuit.h"
+#include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
 #include "utils/logger.h"
 #include "utils/critical_zone_check.h"
@@ -453,6 +454,16 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def("disable_sharding", &DWA::disableSharding)
       .def("use_resident_path", &DWA::useResidentPath, py::arg("on"),
            "Tracked-segment tables from a device-resident copy of the path (saves host time, adds a kernel)");
+
+  // Stanley (bindings_control.cpp:135-150)
+  py::class_<Control::Stanley::StanleyParameters, Control::Follower::FollowerParameters>(c, "StanleyParameters")
+      .def(py::init<>());
+  py::class_<Control::Stanley, Control::Follower>(c, "Stanley")
+      .def(py::init<>(), "Init Stanley follower with default parameters")
+      .def(py::init<Control::Stanley::StanleyParameters>(), "Init Stanley follower with custom config")
+      .def("compute_velocity_commands", &Control::Stanley::computeVelocityCommand)
+      .def("execute", &Control::Stanley::execute)
+      .def("set_robot_wheelbase", &Control::Stanley::setWheelBase);
 
   // PurePursuit (bindings_control.cpp:159-207)
   using PP = Control::PurePursuit;

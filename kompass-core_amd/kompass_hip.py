@@ -86,6 +86,12 @@ class Result(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DvzZone(C.Structure):
+    """kc_dvz_zone: the zone of DeformableVirtualZone (algorithms/dvz.py)."""
+    _fields_ = [("major_radius", C.c_double), ("minor_radius", C.c_double),
+                ("center_shift_x", C.c_double), ("center_shift_y", C.c_double), ("ori_shift", C.c_double)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -205,6 +211,9 @@ SIGNATURES = {
     "kc_depth_last_upload": (C.c_int, [_vp, C.POINTER(_sz)]),
     "kc_depth_timing_enable": (C.c_int, [_vp, C.c_int]),
     "kc_depth_timing_get": (C.c_int, [_vp, C.POINTER(C.c_char_p), _fp, _sz, C.POINTER(_sz)]),
+    "kc_dvz_create": (C.c_int, [C.c_int, _sz, C.POINTER(_vp)]),
+    "kc_dvz_destroy": (None, [_vp]),
+    "kc_dvz_deform": (C.c_int, [_vp, C.POINTER(DvzZone), _dp, _dp, _sz, _dp, _dp]),
 }
 
 _lib = None
@@ -1059,3 +1068,38 @@ class DepthContext:
         n = _sz(0)
         _check(lib().kc_depth_timing_get(self.h, names, ms, 16, C.byref(n)))
         return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+
+
+class DvzContext:
+    """Owner of one kc_dvz context (DeformableVirtualZone.get_total_deformation: one launch per call)."""
+
+    def __init__(self, max_beams=4096, device=0):
+        if int(max_beams) < 0:
+            raise ValueError(f"max_beams must be non-negative, got {max_beams}")
+        self.max_beams = int(max_beams)
+        self.h = _vp()
+        _check(lib().kc_dvz_create(int(device), self.max_beams, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().kc_dvz_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def deform(self, zone, angles, ranges, radii=False):
+        """(total, orientation_sum, n_deformed) over the beams, plus the per-beam deformed radii when `radii`.
+        zone: a DvzZone or (major_radius, minor_radius, center_shift_x, center_shift_y, ori_shift)."""
+        z = zone if isinstance(zone, DvzZone) else DvzZone(*(float(v) for v in zone))
+        a, r = _f64(angles).reshape(-1), _f64(ranges).reshape(-1)
+        if len(a) != len(r):
+            raise ValueError(f"{len(a)} angles and {len(r)} ranges")
+        out = (C.c_double * 3)()
+        rad = np.zeros(max(len(a), 1)) if radii else None
+        _check(lib().kc_dvz_deform(self.h, C.byref(z), _pd(a), _pd(r), len(a), out, _pd(rad)))
+        res = (float(out[0]), float(out[1]), int(out[2]))
+        return res + (rad[:len(a)],) if radii else res
