@@ -722,7 +722,9 @@ void kc_depth_destroy(kc_depth *ctx);
 /* updateBoxes + get3dDetections (:44-81, :84-151).  img: a rows x cols uint16
  * frame, element (r, c) at img[r * row_stride + c * col_stride] (any memory
  * order); data_on_device != 0: img is a device address on ctx's device and is
- * read in place, else the bounding rectangle of the clipped boxes is uploaded.
+ * read in place (KC_ERR_INVALID, before any read, unless hipPointerGetAttributes
+ * reports device memory of ctx's device and the whole frame lies inside that
+ * allocation), else the bounding rectangle of the clipped boxes is uploaded.
  * boxes: n x (top.x, top.y, size.x, size.y); a box covers rows top.y ..
  * top.y + size.y and columns top.x .. top.x + size.x, inclusive, computed in
  * 64 bits; pixels outside the frame are skipped (the reference reads out of
@@ -741,6 +743,11 @@ int kc_depth_box_stats(kc_depth *ctx, const uint16_t *img, int data_on_device,
                        int64_t rows, int64_t cols, int64_t row_stride,
                        int64_t col_stride, const int32_t *boxes, size_t n,
                        int64_t *count_out, float *stats_out);
+/* orders ctx's next reads after the work queued so far on a producer's stream
+ * (a hipStream_t; NULL = the legacy default stream), by an event the context
+ * stream waits for: no host wait.  For frames another library wrote on the
+ * device. */
+int kc_depth_after_stream(kc_depth *ctx, void *stream);
 /* bytes of frame the last call uploaded (0 for a frame on the device) */
 int kc_depth_last_upload(kc_depth *ctx, size_t *bytes_out);
 int kc_depth_timing_enable(kc_depth *ctx, int enable);

@@ -11,6 +11,8 @@
 
 #include "controllers/dwa.h"
 #include "controllers/pure_pursuit.h"
+#include "controllers/rgb_follower.h"
+#include "controllers/rgbd_follower.h"
 #include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
 #include "utils/logger.h"
@@ -107,6 +109,66 @@ DepthImageView depthView(const py::array &a) {
   v.col_stride = a.strides(1) / static_cast<py::ssize_t>(sizeof(uint16_t));
   if (a.strides(0) % 2 || a.strides(1) % 2) throw std::invalid_argument("depth_img strides must be whole elements");
   return v;
+}
+
+// A depth frame for the followers: a uint16 (H, W) numpy array (depthView), or an object that already lives on the
+// device and exposes __cuda_array_interface__ (a torch ROCm tensor, ...), read in place.  `stream` is what the read
+// must wait for: the interface's `stream` (1 = the legacy default stream, 2 = per-thread default, else a
+// hipStream_t); an interface without the key (version 2, as torch writes it) means the legacy default stream; an
+// explicit None means no wait.
+// A host frame that is not an ndarray (an __array_interface__ object, an __array__ that copies) is converted, and
+// the frame keeps that array alive for as long as the view is read.
+struct DepthFrame {
+  DepthImageView view;
+  bool wait = false;
+  void *stream = nullptr;
+  py::array host;  // owner of view.data for a host frame
+};
+DepthFrame depthFrame(const py::object &o) {
+  DepthFrame f;
+  if (!py::hasattr(o, "__cuda_array_interface__")) {
+    f.host = py::cast<py::array>(o);
+    f.view = depthView(f.host);
+    return f;
+  }
+  const py::dict d = o.attr("__cuda_array_interface__");
+  const std::string ts = py::cast<std::string>(d["typestr"]);
+  if (ts != "<u2" && ts != "|u2" && ts != "=u2")
+    throw py::type_error("depth_img must be a uint16 array, got typestr " + ts);
+  const auto shape = py::cast<std::vector<int64_t>>(d["shape"]);
+  if (shape.size() != 2) throw std::invalid_argument("depth_img must be 2-D (H, W)");
+  if (d.contains("mask") && !d["mask"].is_none()) throw std::invalid_argument("masked depth frames are not supported");
+  f.view.rows = shape[0];
+  f.view.cols = shape[1];
+  f.view.row_stride = shape[1];
+  f.view.col_stride = 1;
+  if (d.contains("strides") && !d["strides"].is_none()) {
+    const auto st = py::cast<std::vector<int64_t>>(d["strides"]);
+    if (st.size() != 2 || st[0] % 2 || st[1] % 2) throw std::invalid_argument("depth_img strides must be whole elements");
+    f.view.row_stride = st[0] / 2;
+    f.view.col_stride = st[1] / 2;
+  }
+  const py::tuple data = d["data"];
+  f.view.data = reinterpret_cast<const uint16_t *>(static_cast<uintptr_t>(py::cast<uint64_t>(data[0])));
+  f.view.on_device = true;
+  f.wait = true;
+  if (d.contains("stream")) {
+    const py::object s = d["stream"];
+    if (s.is_none()) {
+      f.wait = false;
+    } else {
+      const uint64_t h = py::cast<uint64_t>(s);
+      if (h == 0) throw std::invalid_argument("__cuda_array_interface__ stream 0 is not allowed");
+      f.stream = h == 1 ? nullptr : reinterpret_cast<void *>(static_cast<uintptr_t>(h));
+    }
+  }
+  return f;
+}
+py::object trackedState(const std::optional<Eigen::MatrixXf> &s) {
+  if (!s) return py::none();
+  FArr a(s->rows());
+  for (Eigen::Index i = 0; i < s->rows(); ++i) a.mutable_at(i) = (*s)(i, 0);
+  return a;
 }
 
 void fromDict(Parameters &p, const py::dict &d) {
@@ -494,6 +556,75 @@ PYBIND11_MODULE(kompass_cpp, m) {
            }, "Execute Pure Pursuit with PointCloud obstacle avoidance", py::arg("delta_time"), py::arg("point_cloud"))
       // (not in the reference: the candidate list the avoidance search walks, nominal command first)
       .def("search_candidates", &PP::searchCandidates, py::arg("nominal"));
+
+  // Vision followers (bindings_control.cpp:276-345)
+  using RGB = Control::RGBFollower;
+  py::class_<RGB::RGBFollowerConfig, Parameters>(c, "RGBFollowerParameters").def(py::init<>());
+  c.attr("RGBFollowerConfig") = c.attr("RGBFollowerParameters");
+  py::class_<RGB>(c, "RGBFollower")
+      .def(py::init<const Control::ControlType, const Control::ControlLimitsParams, const RGB::RGBFollowerConfig>(),
+           py::arg("control_type"), py::arg("control_limits"), py::arg("config") = RGB::RGBFollowerConfig())
+      .def("reset_target", &RGB::resetTarget)
+      .def("get_ctrl", &RGB::getCtrl)
+      .def("get_errors", [](const RGB &f) { return arr(f.getErrors()); })
+      .def("run", &RGB::run, py::arg("detection") = py::none())
+      // (not in the reference: the queued search commands, front first)
+      .def("pending_search_commands", &RGB::pendingSearchCommands);
+
+  using RGBD = Control::RGBDFollower;
+  py::class_<RGBD::RGBDFollowerConfig, RGB::RGBFollowerConfig>(c, "RGBDFollowerParameters").def(py::init<>());
+  auto frame_call = [](RGBD &self, const DepthFrame &f, auto &&fn) {
+    if (f.wait) self.depthAfterStream(f.stream);
+    py::gil_scoped_release nogil;
+    return fn();
+  };
+  py::class_<RGBD, Control::Follower>(c, "RGBDFollower")
+      .def(py::init([](const Control::ControlType &type, const Control::ControlLimitsParams &lim,
+                       const CollisionChecker::ShapeType &shape, const std::vector<float> &dims, const py::object &pos,
+                       const py::object &rot, const RGBD::RGBDFollowerConfig &cfg) {
+             return std::make_unique<RGBD>(type, lim, shape, dims, vec3(pos), vec4(rot), cfg);
+           }), py::arg("control_type"), py::arg("control_limits"), py::arg("robot_shape_type"),
+           py::arg("robot_dimensions"), py::arg("vision_sensor_position_wrt_body"),
+           py::arg("vision_sensor_rotation_wrt_body"), py::arg("config") = RGBD::RGBDFollowerConfig())
+      .def("set_camera_intrinsics", &RGBD::setCameraIntrinsics, py::arg("focal_length_x"), py::arg("focal_length_y"),
+           py::arg("principal_point_x"), py::arg("principal_point_y"))
+      .def("set_initial_tracking",
+           py::overload_cast<const int, const int, const std::vector<Bbox3D> &, const float>(&RGBD::setInitialTracking),
+           py::arg("pixel_x"), py::arg("pixel_y"), py::arg("detected_boxes_3d"), py::arg("robot_orientation") = 0.0)
+      .def("set_initial_tracking",
+           [frame_call](RGBD &self, int x, int y, const py::object &img, const std::vector<Bbox2D> &boxes, float yaw) {
+             const DepthFrame f = depthFrame(img);
+             return frame_call(self, f, [&] { return self.setInitialTracking(x, y, f.view, boxes, yaw); });
+           }, py::arg("pixel_x"), py::arg("pixel_y"), py::arg("aligned_depth_image"), py::arg("detected_boxes_2d"),
+           py::arg("robot_orientation") = 0.0)
+      .def("set_initial_tracking",
+           [frame_call](RGBD &self, const py::object &img, const Bbox2D &box, float yaw) {
+             const DepthFrame f = depthFrame(img);
+             return frame_call(self, f, [&] { return self.setInitialTracking(f.view, box, yaw); });
+           }, py::arg("aligned_depth_image"), py::arg("target_box_2d"), py::arg("robot_orientation") = 0.0)
+      .def("get_errors", [](const RGBD &f) { return arr(f.getErrors()); })
+      .def("get_tracking_ctrl",
+           py::overload_cast<const std::vector<Bbox3D> &, const Control::Velocity2D &>(&RGBD::getTrackingCtrl),
+           py::arg("detected_boxes_3d"), py::arg("robot_velocity"))
+      .def("get_tracking_ctrl",
+           [frame_call](RGBD &self, const py::object &img, const std::vector<Bbox2D> &boxes,
+                        const Control::Velocity2D &vel) {
+             const DepthFrame f = depthFrame(img);
+             return frame_call(self, f, [&] { return self.getTrackingCtrl(f.view, boxes, vel); });
+           }, py::arg("aligned_depth_image"), py::arg("detected_boxes_2d"), py::arg("robot_velocity"))
+      // (not in the reference: what the tests and tools read)
+      .def("get_tracked_state", [](const RGBD &f) { return trackedState(f.getTrackedState()); },
+           "The tracker's Kalman state (x, y, yaw, vx, vy, omega, ax, ay, a_yaw), or None")
+      .def("get_raw_tracking", [](const RGBD &f) -> py::object {
+             auto r = f.getRawTracking();
+             return r ? py::cast(r->box) : py::none();
+           }, "The last box the tracker accepted, or None")
+      .def("pending_search_commands", &RGBD::pendingSearchCommands)
+      .def("target_radius", &RGBD::targetRadius)
+      .def("robot_radius", &RGBD::robotRadius)
+      .def("goal_dist_tolerance", &RGBD::goalDistTolerance)
+      .def("depth_calls", &RGBD::depthCalls)
+      .def("depth_last_upload", &RGBD::depthLastUpload);
 
   // -------------------------------------------------------------- mapping
   auto mp = m.def_submodule("mapping", "Local Mapping module");

@@ -32,6 +32,71 @@ class Velocity2D {
   double v_[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
+// A tracked target's planar pose and velocity (reference: datatypes/control.h:14-188, Pose3D + TrackedPose2D).
+// As in the reference the yaw is kept as a float quaternion about z and read back as atan2(R10, R00) of its
+// rotation matrix; position in float, velocity in double.
+class TrackedPose2D {
+ public:
+  TrackedPose2D(const float pose_x, const float pose_y, const float pose_yaw, const Velocity2D &vel)
+      : vel_(vel) {
+    updatePose(pose_x, pose_y, pose_yaw);
+  }
+  TrackedPose2D(const float pose_x, const float pose_y, const float pose_yaw, const float vx, const float vy,
+                const float omega)
+      : vel_(vx, vy, omega) {
+    updatePose(pose_x, pose_y, pose_yaw);
+  }
+
+  float x() const { return position_[0]; }
+  float y() const { return position_[1]; }
+  float z() const { return position_[2]; }
+  float yaw() const {
+    // Eigen's toRotationMatrix of (w, 0, 0, qz): R00 = 1 - 2 qz qz, R10 = 2 qz w
+    const float tz = 2.0f * qz_;
+    return std::atan2(tz * qw_, 1.0f - tz * qz_);
+  }
+  float v() const {
+    const float vx = static_cast<float>(vel_.vx()), vy = static_cast<float>(vel_.vy());
+    return std::sqrt(vx * vx + vy * vy);
+  }
+  float omega() const { return static_cast<float>(vel_.omega()); }
+  const Velocity2D &velocity() const { return vel_; }
+
+  void updatePose(const float pose_x, const float pose_y, const float pose_yaw) {
+    position_[0] = pose_x;
+    position_[1] = pose_y;
+    position_[2] = 0.0f;
+    setYaw(pose_yaw);
+  }
+
+  // constant-velocity step in the target's own frame
+  void update(const float timeStep) {
+    const double c = std::cos(static_cast<double>(yaw())), s = std::sin(static_cast<double>(yaw()));
+    position_[0] += static_cast<float>((vel_.vx() * c - vel_.vy() * s) * timeStep);
+    position_[1] += static_cast<float>((vel_.vx() * s + vel_.vy() * c) * timeStep);
+    setYaw(static_cast<float>(yaw() + vel_.omega() * timeStep));
+  }
+  void update(const Velocity2D &vel, const float timeStep) {
+    vel_ = vel;
+    update(timeStep);
+  }
+
+  float distance(const float x, const float y, const float z = 0.0f) const {
+    const double dx = position_[0] - x, dy = position_[1] - y, dz = position_[2] - z;
+    return static_cast<float>(std::sqrt(dx * dx + dy * dy + dz * dz));
+  }
+
+ private:
+  void setYaw(const float yaw) {  // AngleAxisf(yaw, UnitZ) with zero pitch and roll
+    const float half = 0.5f * yaw;
+    qw_ = std::cos(half);
+    qz_ = std::sin(half);
+  }
+  float position_[3] = {0.0f, 0.0f, 0.0f};
+  float qw_ = 1.0f, qz_ = 0.0f;
+  Velocity2D vel_;
+};
+
 struct LinearVelocityControlParams {
   double maxVel, maxAcceleration, maxDeceleration;
   LinearVelocityControlParams(double maxVel = 1.0, double maxAcc = 10.0,

@@ -1,7 +1,7 @@
 // Vision datatypes of the kompass_cpp surface (reference: datatypes/tracking.h):
 // PointsOfInterest, Bbox2D and Bbox3D with the reference's constructors and
-// validation (std::invalid_argument).  The tracker types are outside this
-// build's scope.
+// validation (std::invalid_argument), and TrackedBbox3D, the box the
+// bounding-box tracker follows.
 #pragma once
 
 #include <algorithm>
@@ -10,7 +10,9 @@
 #include <string>
 #include <vector>
 
+#include "datatypes/control.h"
 #include "kc_linalg.h"
+#include "utils/logger.h"
 
 namespace Kompass {
 
@@ -121,6 +123,89 @@ struct Bbox3D {
   explicit Bbox3D(const Bbox2D &box2d)
       : center_img_frame(box2d.getCenter()), size_img_frame(box2d.size), timestamp(box2d.timestamp),
         label(box2d.label) {}
+
+  // image-frame limits (float, integer halves as in the reference)
+  Eigen::Vector2f getXLimitsImg() const {
+    return {static_cast<float>(center_img_frame.x() - size_img_frame.x() / 2),
+            static_cast<float>(center_img_frame.x() + size_img_frame.x() / 2)};
+  }
+  Eigen::Vector2f getYLimitsImg() const {
+    return {static_cast<float>(center_img_frame.y() - size_img_frame.y() / 2),
+            static_cast<float>(center_img_frame.y() + size_img_frame.y() / 2)};
+  }
+};
+
+// A box with the velocity and acceleration of its centre (reference: datatypes/tracking.h:207-283)
+struct TrackedBbox3D {
+  Bbox3D box;
+  Eigen::Vector3f vel = {0.0f, 0.0f, 0.0f};
+  Eigen::Vector3f acc = {0.0f, 0.0f, 0.0f};
+  int unique_id = 0;
+
+  TrackedBbox3D(const Bbox3D &box) : box(box) {}
+
+  void setSize(const Eigen::Vector3f &size) { box.size = size; }
+  void setfromBox(const Bbox3D &b) { box = b; }
+
+  // finite differences over the timestamps; a step <= 0 (the usual case: Bbox2D.timestamp defaults to 0) resets
+  // velocity and acceleration
+  void updateFromNewDetection(const Bbox3D &new_box) {
+    if (new_box.label != box.label) {
+      LOG_ERROR("Box label mismatch, cannot update tracking.");
+      return;
+    }
+    const float time_step = new_box.timestamp - box.timestamp;
+    if (time_step <= 0.0f) {
+      LOG_DEBUG("Box updated with invalid time step, Velocity wil be reset to zero.");
+      vel = {0.0f, 0.0f, 0.0f};
+      acc = {0.0f, 0.0f, 0.0f};
+    } else {
+      Eigen::Vector3f new_vel;
+      for (int i = 0; i < 3; ++i) new_vel(i) = (new_box.center(i) - box.center(i)) / time_step;
+      for (int i = 0; i < 3; ++i) acc(i) = (new_vel(i) - vel(i)) / time_step;
+      vel = new_vel;
+    }
+    setfromBox(new_box);
+  }
+
+  TrackedBbox3D predictConstantVel(const float dt) const {
+    TrackedBbox3D p(*this);
+    for (int i = 0; i < 3; ++i) p.box.center(i) += p.vel(i) * dt;
+    p.acc = {0.0f, 0.0f, 0.0f};
+    p.box.timestamp += dt;
+    return p;
+  }
+
+  TrackedBbox3D predictConstantAcc(const float dt) const {
+    TrackedBbox3D p(*this);
+    for (int i = 0; i < 3; ++i) p.vel(i) += acc(i) * dt;
+    for (int i = 0; i < 3; ++i) p.box.center(i) += p.vel(i) * dt;
+    p.box.timestamp += dt;
+    return p;
+  }
+
+  float v() const { return std::sqrt(vel.x() * vel.x() + vel.y() * vel.y()); }
+  float x() const { return box.center.x(); }
+  float y() const { return box.center.y(); }
+  float yaw() const { return std::atan2(vel(1), vel(0)); }
+  float omega() const { return 0.0f; }
+  float ang_acc() const { return 0.0f; }
+  float timestamp() const { return box.timestamp; }
+
+  void update(const float timeStep) {
+    box.center(0) += vel.x() * timeStep;
+    box.center(1) += vel.y() * timeStep;
+    box.timestamp += timeStep;
+  }
+
+  float distance(const float x, const float y, const float z = 0.0f) const {
+    const double dx = box.center.x() - x, dy = box.center.y() - y, dz = box.center.z() - z;
+    return static_cast<float>(std::sqrt(dx * dx + dy * dy + dz * dz));
+  }
+
+  Control::TrackedPose2D getTrackedPose() const {
+    return Control::TrackedPose2D(box.center.x(), box.center.y(), yaw(), vel.x(), vel.y(), 0.0f);
+  }
 };
 
 }  // namespace Kompass

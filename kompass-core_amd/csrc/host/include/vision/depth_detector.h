@@ -40,7 +40,14 @@ class DepthDetector {
 
   std::optional<std::vector<Bbox3D>> get3dDetections() const;
 
+  // (not in the reference's interface) kc_depth_boxes calls so far, and the frame bytes the last one uploaded
+  size_t calls() const { return calls_; }
+  size_t lastUpload() const;
+  // the next frame read waits for the work queued so far on `stream` (a hipStream_t; NULL: the legacy default)
+  void afterStream(void *stream);
+
  private:
+  size_t calls_ = 0;
   std::shared_ptr<kc_depth> ctx_;
   std::unique_ptr<std::vector<Bbox3D>> boxes_;
 };

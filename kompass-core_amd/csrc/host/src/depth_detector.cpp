@@ -23,6 +23,14 @@ std::optional<std::vector<Bbox3D>> DepthDetector::get3dDetections() const {
   return std::nullopt;
 }
 
+size_t DepthDetector::lastUpload() const {
+  size_t bytes = 0;
+  hip::check(kc_depth_last_upload(ctx_.get(), &bytes));
+  return bytes;
+}
+
+void DepthDetector::afterStream(void *stream) { hip::check(kc_depth_after_stream(ctx_.get(), stream)); }
+
 void DepthDetector::updateBoxes(const DepthImageView &img, const std::vector<Bbox2D> &detections,
                                 const std::optional<Path::State> &robot_state) {
   const size_t n = detections.size();
@@ -43,6 +51,7 @@ void DepthDetector::updateBoxes(const DepthImageView &img, const std::vector<Bbo
   std::vector<int32_t> kept(std::max<size_t>(n, 1));
   size_t m = 0;
   boxes_ = std::make_unique<std::vector<Bbox3D>>();
+  ++calls_;
   hip::check(kc_depth_boxes(ctx_.get(), img.data, img.on_device ? 1 : 0, img.rows, img.cols, img.row_stride,
                             img.col_stride, boxes.data(), n, robot_state ? state : nullptr, out.data(),
                             kept.data(), kept.size(), &m));

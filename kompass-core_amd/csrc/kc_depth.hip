@@ -330,6 +330,40 @@ int depth_ready(kc_depth *c) {
   return KC_OK;
 }
 
+// A frame passed as "on the device" is read by the kernel in place, so it must be device memory of the context's
+// device, and every element of the rows x cols frame must lie inside its allocation; anything else (a host
+// pointer, another GPU's memory, a shape larger than the buffer) is refused here, before any read.
+int check_device_frame(const kc_depth *c, const uint16_t *img, long long rows, long long cols, long long rs,
+                       long long cs) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, img) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "the device frame %p is not memory HIP knows", static_cast<const void *>(img));
+  }
+  if (at.type != hipMemoryTypeDevice)
+    KC_FAIL(KC_ERR_INVALID, "the device frame is not device memory (HIP memory type %d)", static_cast<int>(at.type));
+  if (at.device != c->device)
+    KC_FAIL(KC_ERR_INVALID, "the device frame lives on device %d, the detector reads device %d", at.device, c->device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<uint16_t *>(img)) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device frame");
+  }
+  // the lowest and highest element offsets of the frame
+  long long lo = 0, hi = 0, t = 0;
+  if (__builtin_mul_overflow(rows - 1, rs, &t)) KC_FAIL(KC_ERR_RANGE, "frame row stride out of range");
+  (t < 0 ? lo : hi) += t;
+  if (__builtin_mul_overflow(cols - 1, cs, &t)) KC_FAIL(KC_ERR_RANGE, "frame column stride out of range");
+  (t < 0 ? lo : hi) += t;
+  const long long first = reinterpret_cast<long long>(img) + 2 * lo, last = reinterpret_cast<long long>(img) + 2 * hi;
+  const long long b0 = reinterpret_cast<long long>(base), b1 = b0 + static_cast<long long>(size);
+  if (first < b0 || last + 2 > b1)
+    KC_FAIL(KC_ERR_INVALID, "the %lld x %lld device frame (strides %lld, %lld) runs outside its %zu-byte allocation",
+            rows, cols, rs, cs, size);
+  return KC_OK;
+}
+
 // The statistics of every box (count = 0 for a box with no pixel in the image).  Box pixels are the inclusive
 // limits top .. top + size (getXLimits / getYLimits) in 64-bit, clipped to the image.
 int depth_stats(kc_depth *c, const uint16_t *img, int on_device, long long rows, long long cols, long long rs,
@@ -343,6 +377,7 @@ int depth_stats(kc_depth *c, const uint16_t *img, int on_device, long long rows,
   KC_TRY(depth_ready(c));
   if (n == 0) return KC_OK;
   if (rows && cols && !img) KC_FAIL(KC_ERR_INVALID, "null frame");
+  if (on_device && rows && cols) KC_TRY(check_device_frame(c, img, rows, cols, rs, cs));
   // clip, and the bounding rectangle of the clipped boxes
   struct Clip {
     long long y0, x0, y1, x1;
@@ -569,6 +604,19 @@ int kc_depth_boxes(kc_depth *c, const uint16_t *img, int data_on_device, int64_t
     kept_index[m++] = static_cast<int32_t>(i);
   }
   *count_out = m;
+  return KC_OK;
+}
+
+int kc_depth_after_stream(kc_depth *c, void *stream) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_TRY(depth_ready(c));
+  KC_HIP(hipSetDevice(c->device));
+  hipEvent_t e = nullptr;
+  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(stream));
+  if (rc == hipSuccess) rc = hipStreamWaitEvent(c->stream, e, 0);
+  (void)hipEventDestroy(e);  // released once the wait is satisfied
+  KC_HIP(rc);
   return KC_OK;
 }
 

@@ -208,6 +208,7 @@ SIGNATURES = {
                                  _fp, _ip, _sz, C.POINTER(_sz)]),
     "kc_depth_box_stats": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _ip, _sz,
                                      C.POINTER(C.c_int64), _fp]),
+    "kc_depth_after_stream": (C.c_int, [_vp, C.c_void_p]),
     "kc_depth_last_upload": (C.c_int, [_vp, C.POINTER(_sz)]),
     "kc_depth_timing_enable": (C.c_int, [_vp, C.c_int]),
     "kc_depth_timing_get": (C.c_int, [_vp, C.POINTER(C.c_char_p), _fp, _sz, C.POINTER(_sz)]),
@@ -1053,6 +1054,11 @@ class DepthContext:
         _check(lib().kc_depth_box_stats(self.h, addr, on_dev, rows, cols, rs, cs, pb, n,
                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), _pf(st)))
         return cnt[:n], st[:n]
+
+    def after_stream(self, stream=None):
+        """Order the next frame read after the work queued so far on `stream` (a hipStream_t handle; None: the
+        legacy default stream)."""
+        _check(lib().kc_depth_after_stream(self.h, stream))
 
     def last_upload(self) -> int:
         n = _sz(0)
