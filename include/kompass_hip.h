@@ -628,6 +628,49 @@ int kc_cloud_to_laserscan_typed(kc_cloud *ctx, const int8_t *data, size_t nbytes
                                 double max_z, double angle_step, int num_bins,
                                 double *ranges_out, double *angles_out, size_t cap,
                                 size_t *bins_out);
+/* Points -> 2-D occupancy grid: the two loops of readPCDToOccupancyGrid
+ * (utils/pointcloud.h:468-540) over a cloud that crosses to the device once.
+ *
+ * kc_cloud_grid_extent is the bounding-box pass and the sizes (:486-503).
+ * data: n_points records of point_step bytes with float32 x, y, z at the given
+ * byte offsets (a packed (N, 3) float array is point_step 12, offsets 0 / 4 / 8);
+ * data_on_device as in kc_cloud_to_laserscan, and such a cloud is read in place
+ * (KC_ERR_INVALID, before any read, unless it is device memory of ctx's device
+ * and its nbytes lie inside one allocation); it must stay valid until the grid
+ * call that follows.  origin_out = {min_x, min_y, 0}; cells = (int)ceilf((max -
+ * min) / grid_resolution) per axis, in float.  A cloud with no extent on an axis
+ * has 0 cells on it.  Defined here, undefined in the reference: a point with a
+ * non-finite x or y takes part in neither pass; an empty cloud, or one in which
+ * no point has both x and y finite, gives 0 x 0 cells and origin {0, 0, 0}
+ * (:482-484).  The sign of
+ * a zero origin depends on point order there and is not defined here.
+ * KC_ERR_RANGE: grid_resolution not a positive finite float (before any launch),
+ * or more than KC_CLOUD_GRID_MAX_CELLS cells on an axis or in all (the
+ * reference overflows its int; nothing is allocated for the grid). */
+#define KC_CLOUD_GRID_MAX_CELLS (1u << 30)
+int kc_cloud_grid_extent(kc_cloud *ctx, const int8_t *data, size_t nbytes, int data_on_device,
+                         int point_step, size_t n_points, int x_offset, int y_offset, int z_offset,
+                         float grid_resolution, float origin_out[3], int *cells_x, int *cells_y);
+/* the classify-and-scatter pass (:506-536) over the cloud of the last extent
+ * call: cell = (int)((v - min) * (1.0f / grid_resolution)) per axis, a point
+ * outside [0, cells) on either axis is dropped (the points on the max edge of
+ * an extent that is a whole multiple of the resolution are); class 100 if
+ * z > z_ground_limit && z <= robot_height, else 0 if z <= z_ground_limit, else
+ * -1; a cell holds the maximum over its points, -1 where there is none.
+ * grid_out: int8, column-major [cells_x x cells_y], cell (i, j) at
+ * i + j * cells_x (Eigen's layout).  Bit-equal to the reference's loop whatever
+ * the order of the points.  KC_ERR_STATE without an extent call, KC_ERR_RANGE
+ * when the cells do not fit cap. */
+int kc_cloud_grid_fill(kc_cloud *ctx, float z_ground_limit, float robot_height,
+                       int8_t *grid_out, size_t cap);
+/* the same pass without the copy to the host: *dev_grid_int8 is the grid on
+ * ctx's device (NULL for an empty grid), valid until the next call on ctx */
+int kc_cloud_grid_device(kc_cloud *ctx, float z_ground_limit, float robot_height,
+                         void **dev_grid_int8);
+/* orders ctx's next reads after the work queued so far on a producer's stream
+ * (a hipStream_t; NULL = the legacy default stream): for clouds another
+ * library wrote on the device (kc_depth_after_stream is the same for frames) */
+int kc_cloud_after_stream(kc_cloud *ctx, void *stream);
 /* points the last call sent back to the host for exact binning */
 int kc_cloud_last_rebinned(kc_cloud *ctx, size_t *count_out);
 int kc_cloud_timing_enable(kc_cloud *ctx, int enable);

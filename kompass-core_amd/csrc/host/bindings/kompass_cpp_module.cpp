@@ -171,6 +171,76 @@ py::object trackedState(const std::optional<Eigen::MatrixXf> &s) {
   return a;
 }
 
+// (grid, origin) of the occupancy-grid calls: the int8 matrix moves to the heap and the (cells_x, cells_y)
+// column-major array views it (grid[i, j] is the cell (i, j)); no copy
+py::tuple gridResult(std::pair<OccupancyGridI8, std::array<float, 3>> &&r) {
+  auto *g = new OccupancyGridI8(std::move(r.first));
+  py::capsule owner(g, [](void *p) { delete static_cast<OccupancyGridI8 *>(p); });
+  py::array_t<int8_t> a({(py::ssize_t)g->rows(), (py::ssize_t)g->cols()},
+                        {(py::ssize_t)1, (py::ssize_t)std::max<Eigen::Index>(g->rows(), 1)}, g->data(), owner);
+  return py::make_tuple(a, py::make_tuple(r.second[0], r.second[1], r.second[2]));
+}
+void checkResolution(float grid_resolution) {
+  if (!(grid_resolution > 0.0f) || !std::isfinite(grid_resolution))
+    throw py::value_error("grid_resolution must be a positive finite float");
+}
+// points_to_occupancy_grid: an (N, 3) float32 cloud on the host (any array-like) or on the device (an object
+// with __cuda_array_interface__, read in place after the work queued on its stream: cf. depthFrame)
+py::tuple pointsToGrid(const py::object &o, float grid_resolution, float z_ground_limit, float robot_height) {
+  checkResolution(grid_resolution);
+  if (!py::hasattr(o, "__cuda_array_interface__")) {
+    const FArr a = py::cast<FArr>(o);
+    if (a.ndim() != 2 || a.shape(1) != 3) throw std::invalid_argument("expected an (N, 3) array of points");
+    const size_t n = static_cast<size_t>(a.shape(0));
+    const int8_t *data = reinterpret_cast<const int8_t *>(a.data());
+    std::pair<OccupancyGridI8, std::array<float, 3>> r;
+    {
+      py::gil_scoped_release nogil;
+      r = pointsToOccupancyGrid(data, n * 12, false, 12, n, 0, 4, 8, grid_resolution, z_ground_limit, robot_height);
+    }
+    return gridResult(std::move(r));
+  }
+  const py::dict d = o.attr("__cuda_array_interface__");
+  const std::string ts = py::cast<std::string>(d["typestr"]);
+  if (ts != "<f4" && ts != "=f4") throw py::type_error("points must be a float32 array, got typestr " + ts);
+  const auto shape = py::cast<std::vector<int64_t>>(d["shape"]);
+  if (shape.size() != 2 || shape[1] != 3) throw std::invalid_argument("expected an (N, 3) array of points");
+  if (d.contains("mask") && !d["mask"].is_none()) throw std::invalid_argument("masked clouds are not supported");
+  int64_t s0 = 12, s1 = 4;
+  if (d.contains("strides") && !d["strides"].is_none()) {
+    const auto st = py::cast<std::vector<int64_t>>(d["strides"]);
+    if (st.size() != 2) throw std::invalid_argument("points strides must match the shape");
+    s0 = st[0];
+    s1 = st[1];
+  }
+  const size_t n = static_cast<size_t>(shape[0]);
+  if (n == 0) s0 = 12, s1 = 4;  // nothing is read: whatever strides a producer reports for no rows
+  if (s1 < 4 || s0 < 2 * s1 + 4 || s0 > 0x7FFFFFFF)
+    throw std::invalid_argument("points must be records of x, y, z at increasing offsets (positive strides)");
+  const py::tuple data = d["data"];
+  const int8_t *ptr = reinterpret_cast<const int8_t *>(static_cast<uintptr_t>(py::cast<uint64_t>(data[0])));
+  bool wait = true;
+  void *stream = nullptr;
+  if (d.contains("stream")) {
+    const py::object s = d["stream"];
+    if (s.is_none()) {
+      wait = false;
+    } else {
+      const uint64_t h = py::cast<uint64_t>(s);
+      if (h == 0) throw std::invalid_argument("__cuda_array_interface__ stream 0 is not allowed");
+      stream = h == 1 ? nullptr : reinterpret_cast<void *>(static_cast<uintptr_t>(h));
+    }
+  }
+  std::pair<OccupancyGridI8, std::array<float, 3>> r;
+  {
+    py::gil_scoped_release nogil;
+    const size_t nbytes = n ? (n - 1) * static_cast<size_t>(s0) + static_cast<size_t>(2 * s1 + 4) : 0;
+    r = pointsToOccupancyGrid(ptr, nbytes, true, static_cast<int>(s0), n, 0, static_cast<int>(s1),
+                              static_cast<int>(2 * s1), grid_resolution, z_ground_limit, robot_height, wait, stream);
+  }
+  return gridResult(std::move(r));
+}
+
 void fromDict(Parameters &p, const py::dict &d) {
   for (auto item : d) {
     const std::string name = py::cast<std::string>(item.first);
@@ -742,8 +812,7 @@ PYBIND11_MODULE(kompass_cpp, m) {
            py::arg("max_height"), py::arg("min_height"), py::arg("range_max"), py::arg("max_points_per_line") = 32);
 
   // ----------------------------------------------------------------- utils
-  // (bindings_utils.cpp:47-118, bindings_gpu.cpp:40-68; the PCD reader of that
-  // submodule is outside this build's scope)
+  // (bindings_utils.cpp:47-129, bindings_gpu.cpp:40-68)
   auto ut = m.def_submodule("utils", "KOMPASS CPP utilities");
   {
     auto czInit = [](auto *tag, CriticalZoneChecker::InputType it, CollisionChecker::ShapeType shape,
@@ -814,6 +883,34 @@ PYBIND11_MODULE(kompass_cpp, m) {
          py::arg("x_offset"), py::arg("y_offset"), py::arg("z_offset"), py::arg("max_range"), py::arg("min_z"),
          py::arg("max_z"), py::arg("num_bins"),
          "Converts raw PointCloud2 to ranges only, using a fixed number of bins.");
+  // read_pcd / read_pcd_to_occupancy_grid (bindings_utils.cpp:122-129)
+  ut.def("read_pcd", [](const std::string &filename) {
+           std::optional<std::vector<std::array<float, 3>>> pts;
+           {
+             py::gil_scoped_release nogil;
+             pts = readPCD(filename);
+           }
+           if (!pts) throw std::runtime_error("Failed to read PCD file: " + filename);
+           auto *v = new std::vector<std::array<float, 3>>(std::move(*pts));
+           py::capsule owner(v, [](void *p) { delete static_cast<std::vector<std::array<float, 3>> *>(p); });
+           return py::array_t<float>({(py::ssize_t)v->size(), (py::ssize_t)3}, {(py::ssize_t)12, (py::ssize_t)4},
+                                     reinterpret_cast<const float *>(v->data()), owner);
+         }, py::arg("filename"), "Convert PCD file to a numpy array of points (zero-copy return).");
+  ut.def("read_pcd_to_occupancy_grid", [](const std::string &filename, float grid_resolution, float z_ground_limit,
+                                          float robot_height) {
+           checkResolution(grid_resolution);
+           std::pair<OccupancyGridI8, std::array<float, 3>> r;
+           {
+             py::gil_scoped_release nogil;
+             r = readPCDToOccupancyGrid(filename, grid_resolution, z_ground_limit, robot_height);
+           }
+           return gridResult(std::move(r));
+         }, py::arg("filename"), py::arg("grid_resolution"), py::arg("z_ground_limit"), py::arg("robot_height"),
+         "Convert PCD file to an occupancy grid (zero-copy return).");
+  // not in the reference: the same grid from a cloud that is already in memory, on the host or on the device
+  ut.def("points_to_occupancy_grid", &pointsToGrid, py::arg("points"), py::arg("grid_resolution"),
+         py::arg("z_ground_limit"), py::arg("robot_height"),
+         "Convert an (N, 3) float32 cloud (numpy array, or a device array read in place) to an occupancy grid.");
 
 
   // ---------------------------------------------------------------- vision

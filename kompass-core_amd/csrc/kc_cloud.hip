@@ -1,4 +1,5 @@
-// Raw point cloud -> laserscan on gfx950.
+// Raw point cloud -> laserscan on gfx950, and, in the second half of the file, points -> 2-D
+// occupancy grid (readPCDToOccupancyGrid, utils/pointcloud.h:468-540).
 //
 // Reference: pointCloudToLaserScanFromRaw, utils/pointcloud.h:116-177 (angle
 // step) and :205-259 (bin count); the SYCL kernel of the reference
@@ -17,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -246,6 +248,191 @@ __global__ void cloud_arm_kernel(unsigned long long *bins, int n, double max_ran
   if (i == 0) counts[0] = counts[1] = 0u;  // both edge-list counters
 }
 
+// ---- points -> occupancy grid (readPCDToOccupancyGrid, utils/pointcloud.h:468-540) ----------------------
+// Two streaming passes over the cloud.  Pass 1 (:486-497): bounding box of x / y, exact and order-free (min /
+// max).  Pass 2 (:511-536): the class of a point (occupied / ground / overhead) is a bit, the cell's byte of
+// a 32-bit word collects the bits with atomicOr, a decode pass turns the bits into the reference's -1 / 0 /
+// 100 -- the maximum over the cell's points whatever order they arrive in.  Points with a non-finite x or y
+// take part in neither pass.
+struct GridCloud {
+  const uint8_t *data;
+  long long n;         // points
+  int step, x_off, y_off, z_off;
+  int packed12;        // 12-byte x y z records on a 16-byte aligned base: four points = three 16-byte loads
+};
+
+struct GridPoint4 {
+  float x[4], y[4], z[4];
+};
+
+// points 4 g .. 4 g + 3 of a packed cloud
+__device__ __forceinline__ GridPoint4 grid_load4(const GridCloud &c, long long g) {
+  const float4 *q = reinterpret_cast<const float4 *>(c.data) + 3 * g;
+  const float4 a = q[0], b = q[1], d = q[2];
+  GridPoint4 p;
+  p.x[0] = a.x; p.y[0] = a.y; p.z[0] = a.z;
+  p.x[1] = a.w; p.y[1] = b.x; p.z[1] = b.y;
+  p.x[2] = b.z; p.y[2] = b.w; p.z[2] = d.x;
+  p.x[3] = d.y; p.y[3] = d.z; p.z[3] = d.w;
+  return p;
+}
+
+__device__ __forceinline__ void grid_load1(const GridCloud &c, long long i, float &x, float &y, float &z) {
+  const uint8_t *r = c.data + static_cast<size_t>(i) * static_cast<size_t>(c.step);
+  x = load_f32(r + c.x_off);
+  y = load_f32(r + c.y_off);
+  z = load_f32(r + c.z_off);
+}
+
+constexpr int kGridBlock = 256;
+constexpr int kGridMaxBlocks = 2048;  // 8 workgroups of 4 wavefronts for each of the 256 CUs
+
+struct Extent {
+  float min_x, min_y, max_x, max_y;
+};
+
+__device__ __forceinline__ void extent_add(Extent &e, float x, float y) {
+  if (!isfinite(x) || !isfinite(y)) return;
+  e.min_x = x < e.min_x ? x : e.min_x;
+  e.min_y = y < e.min_y ? y : e.min_y;
+  e.max_x = x > e.max_x ? x : e.max_x;
+  e.max_y = y > e.max_y ? y : e.max_y;
+}
+
+__device__ __forceinline__ void extent_merge(Extent &e, const Extent &o) {
+  e.min_x = o.min_x < e.min_x ? o.min_x : e.min_x;
+  e.min_y = o.min_y < e.min_y ? o.min_y : e.min_y;
+  e.max_x = o.max_x > e.max_x ? o.max_x : e.max_x;
+  e.max_y = o.max_y > e.max_y ? o.max_y : e.max_y;
+}
+
+// the workgroup's extent in lane 0 of wavefront 0 (blockDim.x <= 1024)
+__device__ __forceinline__ Extent extent_block_reduce(Extent e) {
+  __shared__ Extent part[16];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    Extent o;
+    o.min_x = __shfl_xor(e.min_x, d, 64);
+    o.min_y = __shfl_xor(e.min_y, d, 64);
+    o.max_x = __shfl_xor(e.max_x, d, 64);
+    o.max_y = __shfl_xor(e.max_y, d, 64);
+    extent_merge(e, o);
+  }
+  const int wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
+  if ((threadIdx.x & 63) == 0) part[wave] = e;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < waves; ++w) extent_merge(e, part[w]);
+  return e;
+}
+
+// pass 1: one partial row a workgroup
+__global__ __launch_bounds__(kGridBlock) void cloud_extent_kernel(GridCloud c, Extent *partial) {
+  Extent e{FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX};  // :487-490
+  const long long stride = static_cast<long long>(gridDim.x) * kGridBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kGridBlock + threadIdx.x;
+  long long done = 0;
+  if (c.packed12) {
+    const long long groups = c.n >> 2;
+    for (long long g = first; g < groups; g += stride) {
+      const GridPoint4 p = grid_load4(c, g);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) extent_add(e, p.x[u], p.y[u]);
+    }
+    done = groups << 2;
+  }
+  for (long long i = done + first; i < c.n; i += stride) {
+    float x, y, z;
+    grid_load1(c, i, x, y, z);
+    extent_add(e, x, y);
+  }
+  e = extent_block_reduce(e);
+  if (threadIdx.x == 0) partial[blockIdx.x] = e;
+}
+
+// ... reduced by one workgroup, straight into pinned host memory
+__global__ __launch_bounds__(kGridBlock) void cloud_extent_merge_kernel(const Extent *partial, int rows, Extent *host_out) {
+  Extent e{FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX};
+  for (int r = threadIdx.x; r < rows; r += kGridBlock) extent_merge(e, partial[r]);
+  e = extent_block_reduce(e);
+  if (threadIdx.x == 0) {
+    *host_out = e;
+    __threadfence_system();
+  }
+}
+
+struct GridFill {
+  float min_x, min_y, inv_res, z_ground, z_robot;
+  int cells_x, cells_y;
+  uint32_t *words;  // the grid's bytes, four cells a word: bit 0 = a ground point, bit 1 = an occupied point
+};
+
+__device__ __forceinline__ void grid_point(const GridFill &f, float x, float y, float z) {
+  if (!isfinite(x) || !isfinite(y)) return;
+  uint32_t bit;
+  if (z > f.z_ground && z <= f.z_robot) bit = 2u;  // :523 OCCUPIED
+  else if (z <= f.z_ground) bit = 1u;              // :526 EMPTY
+  else return;                                     // :529 UNEXPLORED (a NaN z too): the cell's initial value
+  const float dx = x - f.min_x, dy = y - f.min_y;
+  const float fx = dx * f.inv_res, fy = dy * f.inv_res;  // :517-518
+  // an int the float does not fit (or NaN from 0 * inf) is outside every grid
+  if (!(fx < 2147483648.0f) || !(fy < 2147483648.0f)) return;
+  const int cx = static_cast<int>(fx), cy = static_cast<int>(fy);
+  if (cx < 0 || cx >= f.cells_x || cy < 0 || cy >= f.cells_y) return;  // :520
+  const uint32_t cell = static_cast<uint32_t>(cx) + static_cast<uint32_t>(cy) * static_cast<uint32_t>(f.cells_x);
+  const uint32_t sh = (cell & 3u) * 8u;
+  uint32_t *w = f.words + (cell >> 2);
+  // a plain load first: when the cell already holds this class (or, for a ground point, the occupied one that
+  // outranks it) the atomic adds nothing.  Whatever the load returns, skipping is only done on bits that are
+  // set, and bits are never cleared during the pass.
+  // -DKC_GRID_NO_PRELOAD builds the variant without the load, for the A/B of tools/pcd_grid_time.py.
+#ifndef KC_GRID_NO_PRELOAD
+  const uint32_t cur = (*reinterpret_cast<volatile uint32_t *>(w) >> sh) & 3u;
+  if (cur >= bit) return;
+#endif
+  atomicOr(w, bit << sh);
+}
+
+// pass 2
+__global__ __launch_bounds__(kGridBlock) void cloud_grid_scatter_kernel(GridCloud c, GridFill f) {
+  const long long stride = static_cast<long long>(gridDim.x) * kGridBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kGridBlock + threadIdx.x;
+  long long done = 0;
+  if (c.packed12) {
+    const long long groups = c.n >> 2;
+    for (long long g = first; g < groups; g += stride) {
+      const GridPoint4 p = grid_load4(c, g);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) grid_point(f, p.x[u], p.y[u], p.z[u]);
+    }
+    done = groups << 2;
+  }
+  for (long long i = done + first; i < c.n; i += stride) {
+    float x, y, z;
+    grid_load1(c, i, x, y, z);
+    grid_point(f, x, y, z);
+  }
+}
+
+// class bits -> OccupancyType bytes, four cells a word: 0 -> -1, 1 -> 0, 2 | 3 -> 100
+__device__ __forceinline__ uint32_t grid_decode_word(uint32_t w) {
+  const uint32_t occ = (w >> 1) & 0x01010101u, gnd = w & 0x01010101u;
+  const uint32_t none = (occ | gnd) ^ 0x01010101u;
+  return occ * 100u | none * 0xFFu;
+}
+
+__global__ __launch_bounds__(kGridBlock) void cloud_grid_decode_kernel(uint4 *words16, long long n16) {
+  const long long stride = static_cast<long long>(gridDim.x) * kGridBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kGridBlock + threadIdx.x; i < n16; i += stride) {
+    uint4 v = words16[i];
+    v.x = grid_decode_word(v.x);
+    v.y = grid_decode_word(v.y);
+    v.z = grid_decode_word(v.z);
+    v.w = grid_decode_word(v.w);
+    words16[i] = v;
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -267,6 +454,15 @@ struct kc_cloud {
   PinBuf<float2> h_list;
   bool lds_ok = false;
   size_t last_rebinned = 0;
+  // points -> occupancy grid: the cloud of the last kc_cloud_grid_extent and its grid
+  GridCloud g_cloud{};
+  int g_state = 0;               // 0: no extent yet, 1: extent taken, 2: grid filled
+  float g_min_x = 0.f, g_min_y = 0.f, g_res = 0.f;
+  int g_cells_x = 0, g_cells_y = 0;
+  DevBuf<uint8_t> d_points;      // a host cloud, uploaded once for both passes
+  DevBuf<Extent> d_extent;       // [kGridMaxBlocks] partial rows
+  PinBuf<Extent> h_extent;
+  DevBuf<uint4> d_grid;          // the grid's bytes, padded to 16
 };
 
 extern "C" {
@@ -327,6 +523,10 @@ void kc_cloud_destroy(kc_cloud *c) {
   c->h_count.release();
   c->h_out.release();
   c->h_list.release();
+  c->d_points.release();
+  c->d_extent.release();
+  c->h_extent.release();
+  c->d_grid.release();
   delete c;
 }
 
@@ -505,6 +705,193 @@ int kc_cloud_timing_get(kc_cloud *c, const char **names, float *ms, size_t cap,
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   KC_HIP(hipSetDevice(c->device));
   return c->timing.get(names, ms, cap, count);
+}
+
+}  // extern "C"
+
+namespace {
+
+// a cloud passed as "on the device" is read in place: it must be device memory of the context's device and
+// all of its nbytes must lie inside one allocation; anything else is refused before any read
+int check_device_cloud(const kc_cloud *c, const void *data, size_t nbytes) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, data) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "the device cloud %p is not memory HIP knows", data);
+  }
+  if (at.type != hipMemoryTypeDevice)
+    KC_FAIL(KC_ERR_INVALID, "the device cloud is not device memory (HIP memory type %d)", static_cast<int>(at.type));
+  if (at.device != c->device)
+    KC_FAIL(KC_ERR_INVALID, "the device cloud lives on device %d, the context reads device %d", at.device, c->device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(data)) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device cloud");
+  }
+  const uintptr_t p = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(base);
+  if (p < b || nbytes > size || p - b > size - nbytes)
+    KC_FAIL(KC_ERR_INVALID, "the %zu-byte device cloud runs outside its %zu-byte allocation", nbytes, size);
+  return KC_OK;
+}
+
+unsigned grid_blocks(long long work) {
+  return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(kGridMaxBlocks, (work + kGridBlock - 1) / kGridBlock)));
+}
+
+}  // namespace
+
+extern "C" {
+
+int kc_cloud_grid_extent(kc_cloud *c, const int8_t *data, size_t nbytes, int data_on_device, int point_step,
+                         size_t n_points, int x_offset, int y_offset, int z_offset, float grid_resolution,
+                         float origin_out[3], int *cells_x, int *cells_y) {
+  if (!c || !origin_out || !cells_x || !cells_y || (n_points && !data)) KC_FAIL(KC_ERR_INVALID, "null argument");
+  c->g_state = 0;
+  origin_out[0] = origin_out[1] = origin_out[2] = 0.0f;
+  *cells_x = *cells_y = 0;
+  if (!(grid_resolution > 0.0f) || !std::isfinite(grid_resolution))
+    KC_FAIL(KC_ERR_RANGE, "grid_resolution must be a positive finite float, got %g", static_cast<double>(grid_resolution));
+  if (point_step <= 0 || x_offset < 0 || y_offset < 0 || z_offset < 0)
+    KC_FAIL(KC_ERR_INVALID, "point_step must be positive, offsets non-negative");
+  const int max_off = std::max(std::max(x_offset, y_offset), z_offset);
+  if (max_off > point_step - 4) KC_FAIL(KC_ERR_INVALID, "x / y / z do not fit a %d-byte record", point_step);
+  if (n_points > static_cast<size_t>(0x7FFFFFFF)) KC_FAIL(KC_ERR_RANGE, "more than 2^31 points");
+  // every field read lies inside the buffer: the last record may end after its z
+  if (n_points && (nbytes < static_cast<size_t>(max_off) + 4 ||
+                   (n_points - 1) > (nbytes - static_cast<size_t>(max_off) - 4) / static_cast<size_t>(point_step)))
+    KC_FAIL(KC_ERR_INVALID, "%zu records of %d bytes do not fit %zu bytes", n_points, point_step, nbytes);
+  GridCloud g{};
+  g.n = static_cast<long long>(n_points);
+  g.step = point_step;
+  g.x_off = x_offset;
+  g.y_off = y_offset;
+  g.z_off = z_offset;
+  c->g_res = grid_resolution;
+  c->g_cells_x = c->g_cells_y = 0;
+  c->g_min_x = c->g_min_y = 0.0f;
+  if (n_points == 0) {  // :482-484
+    c->g_cloud = g;
+    c->g_state = 1;
+    return KC_OK;
+  }
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  c->timing.begin_cycle();
+  const uint8_t *dev = reinterpret_cast<const uint8_t *>(data);
+  if (data_on_device) {
+    KC_TRY(check_device_cloud(c, data, nbytes));
+  } else {
+    KC_TRY(c->d_points.reserve(nbytes));
+    KC_HIP(hipMemcpyAsync(c->d_points.p, data, nbytes, hipMemcpyHostToDevice, s));
+    dev = c->d_points.p;
+    c->timing.mark("host:cloud_grid_upload");
+  }
+  g.data = dev;
+  g.packed12 = point_step == 12 && x_offset == 0 && y_offset == 4 && z_offset == 8 &&
+               (reinterpret_cast<uintptr_t>(dev) & 15u) == 0;
+  const unsigned blocks = grid_blocks(g.packed12 ? (g.n + 3) / 4 : g.n);
+  KC_TRY(c->d_extent.reserve(kGridMaxBlocks));
+  KC_TRY(c->h_extent.reserve(1));
+  KC_TRY(c->timing.start("cloud_extent_kernel", s));
+  hipLaunchKernelGGL(cloud_extent_kernel, dim3(blocks), dim3(kGridBlock), 0, s, g, c->d_extent.p);
+  hipLaunchKernelGGL(cloud_extent_merge_kernel, dim3(1), dim3(kGridBlock), 0, s, c->d_extent.p,
+                     static_cast<int>(blocks), c->h_extent.p);
+  KC_TRY(c->timing.stop(s));
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipStreamSynchronize(s));
+  const Extent e = c->h_extent.p[0];
+  c->g_cloud = g;
+  c->g_state = 1;
+  if (e.min_x > e.max_x) return KC_OK;  // no point with a finite x and y: as the empty cloud
+  // :500-503, float throughout; the cap is applied to the floats, before any cast or allocation
+  const float fx = std::ceil((e.max_x - e.min_x) / grid_resolution);
+  const float fy = std::ceil((e.max_y - e.min_y) / grid_resolution);
+  const float cap = static_cast<float>(KC_CLOUD_GRID_MAX_CELLS);
+  if (!(fx <= cap) || !(fy <= cap) ||
+      static_cast<double>(fx) * static_cast<double>(fy) > static_cast<double>(KC_CLOUD_GRID_MAX_CELLS)) {
+    c->g_state = 0;
+    KC_FAIL(KC_ERR_RANGE, "a %g x %g cell grid is above the cap of %zu cells", static_cast<double>(fx),
+            static_cast<double>(fy), static_cast<size_t>(KC_CLOUD_GRID_MAX_CELLS));
+  }
+  c->g_min_x = e.min_x;
+  c->g_min_y = e.min_y;
+  c->g_cells_x = static_cast<int>(fx);
+  c->g_cells_y = static_cast<int>(fy);
+  origin_out[0] = e.min_x;
+  origin_out[1] = e.min_y;
+  *cells_x = c->g_cells_x;
+  *cells_y = c->g_cells_y;
+  return KC_OK;
+}
+
+static int cloud_grid_run(kc_cloud *c, float z_ground_limit, float robot_height) {
+  if (c->g_state < 1) KC_FAIL(KC_ERR_STATE, "kc_cloud_grid_fill before kc_cloud_grid_extent");
+  const size_t cells = static_cast<size_t>(c->g_cells_x) * static_cast<size_t>(c->g_cells_y);
+  c->g_state = 2;
+  if (cells == 0) return KC_OK;
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t n16 = (cells + 15) / 16;
+  KC_TRY(c->d_grid.reserve(n16));
+  KC_TRY(c->timing.start("cloud_grid_clear", s));
+  KC_HIP(hipMemsetAsync(c->d_grid.p, 0, n16 * 16, s));
+  KC_TRY(c->timing.stop(s));
+  GridFill f{};
+  f.min_x = c->g_min_x;
+  f.min_y = c->g_min_y;
+  f.inv_res = 1.0f / c->g_res;  // :506
+  f.z_ground = z_ground_limit;
+  f.z_robot = robot_height;
+  f.cells_x = c->g_cells_x;
+  f.cells_y = c->g_cells_y;
+  f.words = reinterpret_cast<uint32_t *>(c->d_grid.p);
+  const GridCloud &g = c->g_cloud;
+  KC_TRY(c->timing.start("cloud_grid_scatter_kernel", s));
+  hipLaunchKernelGGL(cloud_grid_scatter_kernel, dim3(grid_blocks(g.packed12 ? (g.n + 3) / 4 : g.n)), dim3(kGridBlock), 0,
+                     s, g, f);
+  KC_TRY(c->timing.stop(s));
+  KC_TRY(c->timing.start("cloud_grid_decode_kernel", s));
+  hipLaunchKernelGGL(cloud_grid_decode_kernel, dim3(grid_blocks(static_cast<long long>(n16))), dim3(kGridBlock), 0, s,
+                     c->d_grid.p, static_cast<long long>(n16));
+  KC_TRY(c->timing.stop(s));
+  KC_HIP(hipGetLastError());
+  return KC_OK;
+}
+
+int kc_cloud_grid_fill(kc_cloud *c, float z_ground_limit, float robot_height, int8_t *grid_out, size_t cap) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (c->g_state < 1) KC_FAIL(KC_ERR_STATE, "kc_cloud_grid_fill before kc_cloud_grid_extent");
+  const size_t cells = static_cast<size_t>(c->g_cells_x) * static_cast<size_t>(c->g_cells_y);
+  if (cells > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", cells, cap);
+  if (cells && !grid_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  KC_TRY(cloud_grid_run(c, z_ground_limit, robot_height));
+  if (cells == 0) return KC_OK;
+  KC_HIP(hipMemcpyAsync(grid_out, c->d_grid.p, cells, hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_cloud_grid_device(kc_cloud *c, float z_ground_limit, float robot_height, void **dev_grid_int8) {
+  if (!c || !dev_grid_int8) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *dev_grid_int8 = nullptr;
+  KC_TRY(cloud_grid_run(c, z_ground_limit, robot_height));
+  if (static_cast<size_t>(c->g_cells_x) * static_cast<size_t>(c->g_cells_y) == 0) return KC_OK;
+  KC_HIP(hipStreamSynchronize(c->stream));
+  *dev_grid_int8 = c->d_grid.p;
+  return KC_OK;
+}
+
+int kc_cloud_after_stream(kc_cloud *c, void *stream) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_HIP(hipSetDevice(c->device));
+  hipEvent_t e = nullptr;
+  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(stream));
+  if (rc == hipSuccess) rc = hipStreamWaitEvent(c->stream, e, 0);
+  (void)hipEventDestroy(e);  // released once the wait is satisfied
+  KC_HIP(rc);
+  return KC_OK;
 }
 
 }  // extern "C"

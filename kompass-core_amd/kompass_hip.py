@@ -199,6 +199,11 @@ SIGNATURES = {
                                               C.c_int, _dp, _dp, _sz, C.POINTER(_sz)]),
     "kc_zone_check_cloud_typed": (C.c_int, [_vp, C.c_void_p, _sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_int, _fp]),
+    "kc_cloud_grid_extent": (C.c_int, [_vp, C.c_void_p, _sz, C.c_int, C.c_int, _sz, C.c_int, C.c_int, C.c_int,
+                                       C.c_float, _fp, _ip, _ip]),
+    "kc_cloud_grid_fill": (C.c_int, [_vp, C.c_float, C.c_float, C.c_void_p, _sz]),
+    "kc_cloud_grid_device": (C.c_int, [_vp, C.c_float, C.c_float, C.POINTER(_vp)]),
+    "kc_cloud_after_stream": (C.c_int, [_vp, C.c_void_p]),
     "kc_cloud_last_rebinned": (C.c_int, [_vp, C.POINTER(_sz)]),
     "kc_cloud_timing_enable": (C.c_int, [_vp, C.c_int]),
     "kc_cloud_timing_get": (C.c_int, [_vp, C.POINTER(C.c_char_p), _fp, _sz, C.POINTER(_sz)]),
@@ -921,6 +926,50 @@ class CloudContext:
                                                  float(angle_step) if by_step else 0.0, nb, _pd(ranges), _pd(angles),
                                                  cap, C.byref(n)))
         return (ranges[:n.value], angles[:n.value]) if by_step else ranges[:n.value]
+
+    def occupancy_grid(self, points, grid_resolution, z_ground_limit, robot_height, device_ptr=None, n_points=None,
+                       point_step=12, offsets=(0, 4, 8), nbytes=None, to_host=True):
+        """The two loops of readPCDToOccupancyGrid: (grid, origin), grid an int8 (cells_x, cells_y) array with
+        grid[i, j] the cell (i, j), origin [min_x, min_y, 0].  `points`: an (N, 3) float32 array on the host,
+        or raw records (bytes / int8 array with point_step, offsets and n_points); or pass device_ptr, n_points
+        (and nbytes) for a cloud that already lives on the device.  to_host=False runs the passes and returns
+        (device address of the grid, (cells_x, cells_y), origin) instead."""
+        with np.errstate(over="ignore"):
+            res = float(np.float32(grid_resolution))  # what the C ABI receives
+        if not (res > 0.0 and np.isfinite(res)):
+            raise ValueError("grid_resolution must be a positive finite float")
+        step = int(point_step)
+        if device_ptr is not None:
+            n = int(n_points)
+            ptr, on_dev = int(device_ptr), 1
+            size = int(nbytes) if nbytes is not None else n * step
+        else:
+            if isinstance(points, np.ndarray) and points.dtype != np.int8:
+                if points.ndim != 2 or points.shape[1] != 3:
+                    raise ValueError("expected an (N, 3) array of points")
+                buf = _f32(points)
+                n = buf.shape[0] if n_points is None else int(n_points)
+            else:
+                buf = np.ascontiguousarray(np.frombuffer(bytes(points), dtype=np.int8)
+                                           if not isinstance(points, np.ndarray) else points.reshape(-1))
+                n = buf.size // step if n_points is None else int(n_points)
+            ptr, size, on_dev = buf.ctypes.data, buf.nbytes, 0
+        origin = np.zeros(3, np.float32)
+        cx, cy = C.c_int(0), C.c_int(0)
+        _check(lib().kc_cloud_grid_extent(self.h, ptr, size, on_dev, step, n, int(offsets[0]), int(offsets[1]),
+                                          int(offsets[2]), res, _pf(origin), C.byref(cx), C.byref(cy)))
+        if not to_host:
+            dev = _vp()
+            _check(lib().kc_cloud_grid_device(self.h, float(z_ground_limit), float(robot_height), C.byref(dev)))
+            return dev.value or 0, (cx.value, cy.value), origin
+        grid = np.empty((cx.value, cy.value), np.int8, order="F")
+        _check(lib().kc_cloud_grid_fill(self.h, float(z_ground_limit), float(robot_height), grid.ctypes.data, grid.size))
+        return grid, origin
+
+    def after_stream(self, stream=None):
+        """Order the next reads after the work queued so far on `stream` (a hipStream_t address; None: the legacy
+        default stream)."""
+        _check(lib().kc_cloud_after_stream(self.h, stream))
 
     def last_rebinned(self) -> int:
         n = _sz(0)

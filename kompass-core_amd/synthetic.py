@@ -195,3 +195,23 @@ REF_COST5K = dict(path_points=[[0.0, 0.0, 0.0], [5.0, 0.0, 0.0], [10.0, 0.0, 0.0
                   acc_limits=(3.0, 3.0, 5.0),   # x_p(1,3,5), y_p(1,3,5), a_p(3.14,3,5,8): max accelerations
                   weights=(1.0, 1.0, 0.0, 1.0, 1.0))  # path, goal, (no obstacles set), smoothness, jerk
 REF_MAPPER400 = dict(height=400, width=400, res=0.05, beams=3600)
+
+
+def pcd_indoor_map(n_points: int, seed: int = 0, size=(100.0, 60.0)) -> np.ndarray:
+    """A SLAM-style map of a building floor as an (N, 3) float32 cloud: 60 % floor returns (z noise around 0),
+    25 % walls on a 5 m lattice (z up to 2.5 m, so ground, obstacle and overhead classes all occur) and 15 %
+    ceiling points over half of the floor (above any robot)."""
+    rng = np.random.default_rng(seed)
+    n = int(n_points)
+    nf, nw = int(0.6 * n), int(0.25 * n)
+    nc = n - nf - nw
+    sx, sy = size
+    floor = np.stack([rng.uniform(0, sx, nf), rng.uniform(0, sy, nf), rng.normal(0, 0.02, nf)], axis=1)
+    along_x = rng.random(nw) < 0.5
+    lat_x = 5.0 * rng.integers(0, int(sx / 5) + 1, nw) + rng.normal(0, 0.02, nw)
+    lat_y = 5.0 * rng.integers(0, int(sy / 5) + 1, nw) + rng.normal(0, 0.02, nw)
+    walls = np.stack([np.where(along_x, rng.uniform(0, sx, nw), lat_x), np.where(along_x, lat_y, rng.uniform(0, sy, nw)),
+                      rng.uniform(0, 2.5, nw)], axis=1)
+    ceil = np.stack([rng.uniform(0, sx / 2, nc), rng.uniform(0, sy, nc), 2.5 + rng.normal(0, 0.02, nc)], axis=1)
+    pts = np.concatenate([floor, walls, ceil]).astype(np.float32)
+    return pts[rng.permutation(n)]
