@@ -797,6 +797,70 @@ int kc_depth_timing_enable(kc_depth *ctx, int enable);
 int kc_depth_timing_get(kc_depth *ctx, const char **names, float *ms, size_t cap,
                         size_t *count_out);
 
+/* ------------------------------------------------------------------------ */
+/* Grid planner: occupancy grid -> collision-free path      */
+/* ------------------------------------------------------------------------ */
+typedef struct kc_planner kc_planner;
+
+/* Nothing in the reference to cite for the method: its planning submodule wraps
+ * OMPL (planning/ompl.h:18-89), which stays out of scope.  What is kept is the
+ * shape of that surface (setSpaceBoundsFromMap / setupProblem / solve / getPath /
+ * getCost, ompl.h:37-74), in the host class Planning::GridPlanner; this ABI is
+ * the integer core under it and works in cells.
+ *
+ * A grid is width x height cells, cell (i, j) at i + j * width: i runs along x
+ * and is the fast index.  That is the LocalMapper's layout (kc_mapper_grid_device:
+ * int32, width = grid_height, height = grid_width) and the PCD grid's
+ * (kc_cloud_grid_device: int8, width = cells_x, height = cells_y).  elem_bytes is
+ * 4 or 1 accordingly.  KC_OCCUPIED cells block, KC_UNEXPLORED cells block unless
+ * allow_unknown, every other value is free.  KC_ERR_RANGE above
+ * KC_PLANNER_MAX_CELLS cells (14 * cells must fit 32 bits). */
+#define KC_PLANNER_MAX_CELLS (1u << 28)
+#define KC_PLANNER_MAX_RADIUS_CELLS 254
+int kc_planner_create(int device, kc_planner **out);
+void kc_planner_destroy(kc_planner *ctx);
+/* the grid from host memory (one copy to the device) */
+int kc_planner_set_grid_host(kc_planner *ctx, const void *grid, int elem_bytes, int width, int height);
+/* the grid where it lies on ctx's device: read in place, no host round trip
+ * (KC_ERR_INVALID, before any read, unless it is device memory of ctx's device,
+ * inside one allocation and aligned to its cells).  The grid must be finished
+ * (kc_cloud_grid_device returns it so; kc_mapper_sync after a device scan); it is
+ * not read after the call returns. */
+int kc_planner_set_grid_device(kc_planner *ctx, const void *dev_grid, int elem_bytes, int width, int height);
+/* orders ctx's next read of a device grid after the work queued so far on a
+ * producer's stream (a hipStream_t; NULL = the legacy default stream), as
+ * kc_cloud_after_stream does: no host wait */
+int kc_planner_after_stream(kc_planner *ctx, void *stream);
+/* Validity, cost field and the start's status for one (start, goal) pair.
+ *  - a cell is invalid when a blocking cell (bi, bj) has (bi - i)^2 + (bj - j)^2
+ *    <= r2; cells outside the grid do not block.  KC_ERR_RANGE when r2 reaches
+ *    further than KC_PLANNER_MAX_RADIUS_CELLS cells.
+ *  - field[cell] = the exact length of the shortest 8-connected walk over valid
+ *    cells to the goal cell, a straight step 10 and a diagonal one 14, a diagonal
+ *    step only between two valid orthogonal neighbours; 0xFFFFFFFF where there
+ *    is none (and everywhere when the goal is outside the grid or invalid).
+ *  - *status_out: KC_PLAN_FOUND or why there is no path; that is not an error,
+ *    the call returns KC_OK.  *cost_out = field[start] (0xFFFFFFFF without a
+ *    path), *passes_out = relaxation passes the field needed, the one that found
+ *    nothing left to change included.
+ * KC_ERR_RANGE if the field still changes after cells + 1 passes (it cannot: every
+ * pass but the last settles a cell); KC_ERR_STATE without a grid. */
+enum { KC_PLAN_FOUND = 0, KC_PLAN_START_OUTSIDE = 1, KC_PLAN_GOAL_OUTSIDE = 2, KC_PLAN_START_INVALID = 3,
+       KC_PLAN_GOAL_INVALID = 4, KC_PLAN_UNREACHABLE = 5 };
+int kc_planner_solve(kc_planner *ctx, const int start_cell[2], const int goal_cell[2], uint32_t r2,
+                     int allow_unknown, int *status_out, uint32_t *cost_out, int *passes_out);
+/* the last solve's cost field and validity map (1 valid, 0 invalid), laid out as
+ * the grid (tests); either pointer may be NULL */
+int kc_planner_get_field(kc_planner *ctx, uint32_t *field_out, uint8_t *valid_out, size_t cap);
+/* the path of the last solve by steepest descent: from the start cell, the
+ * neighbour with the smallest field value among those a step may go to (valid,
+ * and for a diagonal between two valid orthogonal neighbours), the first of
+ * them in the order E, N, W, S, NE, NW, SW, SE ((+1, 0), (0, +1), (-1, 0),
+ * (0, -1), (+1, +1), (-1, +1), (-1, -1), (+1, -1)), until the goal cell.
+ * cells_ij_out: (i, j) pairs, start first; NULL asks for the count only.
+ * Zero points when the last solve found no path. */
+int kc_planner_get_path(kc_planner *ctx, int32_t *cells_ij_out, size_t cap_points, size_t *count_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "controllers/rgbd_follower.h"
 #include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
+#include "planning/grid_planner.h"
 #include "utils/logger.h"
 #include "utils/critical_zone_check.h"
 #include "utils/pointcloud.h"
@@ -239,6 +240,65 @@ py::tuple pointsToGrid(const py::object &o, float grid_resolution, float z_groun
                               static_cast<int>(2 * s1), grid_resolution, z_ground_limit, robot_height, wait, stream);
   }
   return gridResult(std::move(r));
+}
+
+// GridPlanner.set_grid: a (width, height) int32 or int8 grid, grid[i, j] the cell (i, j) -- a numpy array (any
+// memory order; one copy when it is not column-major already), or an object that lives on the device and exposes
+// __cuda_array_interface__ with that shape in column-major strides (the transpose of a C-contiguous (height,
+// width) torch tensor), read in place
+void plannerSetGrid(Planning::GridPlanner &p, const py::object &o) {
+  if (!py::hasattr(o, "__cuda_array_interface__")) {
+    const py::array a = py::cast<py::array>(o);
+    if (a.ndim() != 2) throw std::invalid_argument("the grid must be 2-D (width, height)");
+    if (a.dtype().num() == py::dtype::of<int8_t>().num()) {
+      const auto g = py::array_t<int8_t, py::array::f_style>::ensure(a);
+      p.setSpaceBoundsCheck(static_cast<int>(g.shape(0)), static_cast<int>(g.shape(1)));
+      const void *d = g.data();
+      py::gil_scoped_release nogil;
+      p.setGrid(d, 1);
+    } else if (a.dtype().num() == py::dtype::of<int32_t>().num()) {
+      const auto g = py::array_t<int32_t, py::array::f_style>::ensure(a);
+      p.setSpaceBoundsCheck(static_cast<int>(g.shape(0)), static_cast<int>(g.shape(1)));
+      const void *d = g.data();
+      py::gil_scoped_release nogil;
+      p.setGrid(d, 4);
+    } else {
+      throw py::type_error("the grid must be int32 or int8, got " + py::str(a.dtype()).cast<std::string>());
+    }
+    return;
+  }
+  const py::dict d = o.attr("__cuda_array_interface__");
+  const std::string ts = py::cast<std::string>(d["typestr"]);
+  int elem = 0;
+  if (ts == "<i4" || ts == "=i4") elem = 4;
+  else if (ts == "|i1" || ts == "<i1" || ts == "=i1") elem = 1;
+  else throw py::type_error("the grid must be int32 or int8, got typestr " + ts);
+  const auto shape = py::cast<std::vector<int64_t>>(d["shape"]);
+  if (shape.size() != 2) throw std::invalid_argument("the grid must be 2-D (width, height)");
+  if (d.contains("mask") && !d["mask"].is_none()) throw std::invalid_argument("masked grids are not supported");
+  if (!d.contains("strides") || d["strides"].is_none()) {
+    if (shape[0] != 1 && shape[1] != 1) throw std::invalid_argument("a device grid must be column-major: grid[i, j] at i + j * width");
+  } else {
+    const auto st = py::cast<std::vector<int64_t>>(d["strides"]);
+    if (st.size() != 2 || (shape[0] > 1 && st[0] != elem) || (shape[1] > 1 && st[1] != elem * shape[0]))
+      throw std::invalid_argument("a device grid must be column-major: grid[i, j] at i + j * width");
+  }
+  if (shape[0] > 0x7FFFFFFF || shape[1] > 0x7FFFFFFF) throw std::out_of_range("the grid is too large");
+  p.setSpaceBoundsCheck(static_cast<int>(shape[0]), static_cast<int>(shape[1]));
+  const py::tuple data = d["data"];
+  const void *ptr = reinterpret_cast<const void *>(static_cast<uintptr_t>(py::cast<uint64_t>(data[0])));
+  // the producer's stream must have finished the grid: wait for it as the interface asks
+  if (!d.contains("stream") || !d["stream"].is_none()) {
+    void *stream = nullptr;
+    if (d.contains("stream")) {
+      const uint64_t h = py::cast<uint64_t>(d["stream"]);
+      if (h == 0) throw std::invalid_argument("__cuda_array_interface__ stream 0 is not allowed");
+      stream = h == 1 ? nullptr : reinterpret_cast<void *>(static_cast<uintptr_t>(h));
+    }
+    p.waitForStream(stream);
+  }
+  py::gil_scoped_release nogil;
+  p.setGridOnDevice(ptr, elem);
 }
 
 void fromDict(Parameters &p, const py::dict &d) {
@@ -912,6 +972,59 @@ PYBIND11_MODULE(kompass_cpp, m) {
          py::arg("z_ground_limit"), py::arg("robot_height"),
          "Convert an (N, 3) float32 cloud (numpy array, or a device array read in place) to an occupancy grid.");
 
+
+  // -------------------------------------------------------------- planning
+  // not the reference's OMPL wrapper (planning/ompl.h; out of scope): a deterministic grid planner with that
+  // surface's method names where the meaning is the same
+  auto pl = m.def_submodule("planning", "Grid planning module");
+  py::class_<Planning::GridPlanner>(pl, "GridPlanner")
+      .def(py::init([](CollisionChecker::ShapeType shape, const std::vector<float> &dims, bool allow_unknown, float margin) {
+             return std::make_unique<Planning::GridPlanner>(shape, dims, allow_unknown, margin);
+           }), py::arg("robot_shape"), py::arg("robot_dimensions"), py::arg("allow_unknown") = true,
+           py::arg("margin") = 0.0f)
+      .def("set_space_bounds_from_map", &Planning::GridPlanner::setSpaceBoundsFromMap, py::arg("origin_x"),
+           py::arg("origin_y"), py::arg("width"), py::arg("height"), py::arg("resolution"))
+      .def("set_grid", &plannerSetGrid, py::arg("grid"),
+           "The (width, height) int32 / int8 grid of the map set before: a numpy array, or a device array read in place")
+      .def("set_grid_device", [](Planning::GridPlanner &p, uint64_t ptr, int elem_bytes) {
+             py::gil_scoped_release nogil;
+             p.setGridOnDevice(reinterpret_cast<const void *>(static_cast<uintptr_t>(ptr)), elem_bytes);
+           }, py::arg("device_ptr"), py::arg("elem_bytes") = 4, "A finished grid at a device address, read in place")
+      .def("set_grid_from_mapper", &Planning::GridPlanner::setGridFromMapper, py::arg("mapper"),
+           "The last grid of a LocalMapper where it lies on the device; takes the bounds from the mapper")
+      .def("setup_problem", &Planning::GridPlanner::setupProblem, py::arg("start_x"), py::arg("start_y"),
+           py::arg("start_yaw"), py::arg("goal_x"), py::arg("goal_y"), py::arg("goal_yaw"))
+      .def("solve", [](Planning::GridPlanner &p, double) {
+             py::gil_scoped_release nogil;
+             return p.solve();
+           }, py::arg("planning_timeout") = 0.0, "planning_timeout is accepted and unused: the solve is exact and bounded")
+      .def("get_solution", [](Planning::GridPlanner &p, bool simplify) -> py::object {
+             auto path = p.getPath(simplify);
+             if (!path) return py::none();
+             return py::cast(std::move(*path));
+           }, py::arg("simplify") = false)
+      .def("get_path_cells", [](Planning::GridPlanner &p, bool simplify) {
+             const std::vector<int32_t> ij = p.getPathCells(simplify);
+             py::array_t<int32_t> a({(py::ssize_t)(ij.size() / 2), (py::ssize_t)2});
+             if (!ij.empty()) std::memcpy(a.mutable_data(), ij.data(), ij.size() * sizeof(int32_t));
+             return a;
+           }, py::arg("simplify") = false)
+      .def("get_cost", &Planning::GridPlanner::getCost)
+      .def("get_field", [](Planning::GridPlanner &p) {
+             const py::ssize_t w = p.width(), h = p.height();
+             py::array_t<uint32_t, py::array::f_style> f({w, h});
+             py::array_t<uint8_t, py::array::f_style> v({w, h});
+             p.getField(f.mutable_data(), v.mutable_data(), static_cast<size_t>(w) * static_cast<size_t>(h));
+             return py::make_tuple(f, v);
+           }, "(cost field uint32, validity uint8) of the last solve, [i, j] as the grid")
+      .def("get_status", &Planning::GridPlanner::status)
+      .def("get_passes", &Planning::GridPlanner::passes)
+      .def("get_footprint_r2", &Planning::GridPlanner::footprintR2)
+      .def("get_cells", [](const Planning::GridPlanner &p) {
+             int s[2], g[2];
+             p.cells(s, g);
+             return py::make_tuple(py::make_tuple(s[0], s[1]), py::make_tuple(g[0], g[1]));
+           }, "(start cell, goal cell) of the last setup_problem");
 
   // ---------------------------------------------------------------- vision
   // (bindings_vision.cpp): the frame goes to kc_depth_boxes by pointer and strides

@@ -60,6 +60,12 @@ class LocalMapper {
   // refreshed by this call)
   void scanToGridOnDevice(const std::vector<double> &angles, const std::vector<double> &ranges);
   void setPreviousGridProb(const Eigen::MatrixXf *prob);
+  // geometry of the grid, for consumers of the device grid (Planning::GridPlanner): m_centralPoint is
+  // round(size / 2) - 1 per axis in integer division (local_mapper.h:26-27)
+  int gridHeight() const { return rows_; }
+  int gridWidth() const { return cols_; }
+  float resolution() const { return cell_; }
+  int centralCell(int axis) const { return (axis == 0 ? rows_ : cols_) / 2 - 1; }
 
  protected:
   const int rows_, cols_;

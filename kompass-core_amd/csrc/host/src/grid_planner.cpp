@@ -1,0 +1,191 @@
+// Planning::GridPlanner: frames, the footprint rule and the Path on the host; validity, cost field and the walk
+// on the device through kc_planner_* (DESIGN.md 4.10).
+#include "planning/grid_planner.h"
+
+#include <cmath>
+#include <limits>
+#include <stdexcept>
+#include <string>
+
+namespace Kompass {
+namespace Planning {
+
+namespace {
+// the circumscribed horizontal radius: cylinder (r, h) and sphere (r) -> r, box (x, y, z) -> half the diagonal
+double circumscribedRadius(const CollisionChecker::ShapeType &shape, const std::vector<float> &dims) {
+  switch (shape) {
+    case CollisionChecker::ShapeType::CYLINDER:
+      if (dims.size() < 2) throw std::invalid_argument("a cylinder needs (radius, height)");
+      return static_cast<double>(dims[0]);
+    case CollisionChecker::ShapeType::SPHERE:
+      if (dims.empty()) throw std::invalid_argument("a sphere needs (radius)");
+      return static_cast<double>(dims[0]);
+    case CollisionChecker::ShapeType::BOX: {
+      if (dims.size() < 3) throw std::invalid_argument("a box needs (x, y, z)");
+      const double x = dims[0], y = dims[1];
+      return 0.5 * std::sqrt(x * x + y * y);
+    }
+  }
+  throw std::invalid_argument("Invalid robot geometry type");
+}
+}  // namespace
+
+GridPlanner::GridPlanner(const CollisionChecker::ShapeType &shape, const std::vector<float> &dims, bool allow_unknown,
+                         float margin)
+    : allow_unknown_(allow_unknown) {
+  radius_ = circumscribedRadius(shape, dims) + static_cast<double>(margin);
+  if (!(radius_ >= 0.0) || !std::isfinite(radius_)) throw std::invalid_argument("the footprint radius must be finite and >= 0");
+  kc_planner *raw = nullptr;
+  hip::check(kc_planner_create(0, &raw));
+  ctx_.reset(raw);
+}
+
+void GridPlanner::setSpaceBoundsFromMap(float origin_x, float origin_y, int width, int height, float resolution) {
+  if (!(resolution > 0.0f) || !std::isfinite(resolution)) throw std::invalid_argument("resolution must be a positive finite float");
+  if (width <= 0 || height <= 0) throw std::invalid_argument("width and height must be positive");
+  if (!std::isfinite(origin_x) || !std::isfinite(origin_y)) throw std::invalid_argument("the origin must be finite");
+  if (have_grid_ && (width != width_ || height != height_)) have_grid_ = false;  // the grid of another map
+  forgetSolve();  // a path of the last frame is not one of this frame
+  ox_ = origin_x;
+  oy_ = origin_y;
+  width_ = width;
+  height_ = height;
+  res_ = resolution;
+  have_bounds_ = true;
+}
+
+void GridPlanner::needBounds() const {
+  if (!have_bounds_) throw std::runtime_error("GridPlanner: set_space_bounds_from_map first");
+}
+
+void GridPlanner::setSpaceBoundsCheck(int width, int height) const {
+  needBounds();
+  if (width != width_ || height != height_)
+    throw std::invalid_argument("the grid is " + std::to_string(width) + " x " + std::to_string(height) +
+                                " cells, the map's bounds say " + std::to_string(width_) + " x " + std::to_string(height_));
+}
+
+void GridPlanner::waitForStream(void *stream) { hip::check(kc_planner_after_stream(ctx_.get(), stream)); }
+
+// a new grid leaves nothing of the last solve: get_solution() is None and get_cost() infinite until the next one
+void GridPlanner::forgetSolve() {
+  status_ = -1;
+  passes_ = 0;
+  cost_ = 0xFFFFFFFFu;
+}
+
+void GridPlanner::setGrid(const void *host_grid, int elem_bytes) {
+  needBounds();
+  forgetSolve();
+  hip::check(kc_planner_set_grid_host(ctx_.get(), host_grid, elem_bytes, width_, height_));
+  have_grid_ = true;
+}
+
+void GridPlanner::setGridOnDevice(const void *dev_grid, int elem_bytes) {
+  needBounds();
+  forgetSolve();
+  hip::check(kc_planner_set_grid_device(ctx_.get(), dev_grid, elem_bytes, width_, height_));
+  have_grid_ = true;
+}
+
+void GridPlanner::setGridFromMapper(Mapping::LocalMapper &mapper) {
+  const float res = mapper.resolution();
+  // cell (i, j) of the mapper sits at ((i - c0) res, (j - c1) res): kc_dwa_set_grid_device's inverse of localToGrid
+  setSpaceBoundsFromMap(-static_cast<float>(mapper.centralCell(0)) * res, -static_cast<float>(mapper.centralCell(1)) * res,
+                        mapper.gridHeight(), mapper.gridWidth(), res);
+  void *dev = nullptr;
+  hip::check(kc_mapper_grid_device(mapper.hipContext(), &dev));
+  hip::check(kc_mapper_sync(mapper.hipContext()));
+  setGridOnDevice(dev, 4);
+}
+
+bool GridPlanner::worldToCell(float x, float origin, float resolution, int *cell) {
+  const float q = (x - origin) / resolution;
+  if (!std::isfinite(q) || std::fabs(q) >= 1073741824.0f) return false;
+  *cell = static_cast<int>(q);
+  return true;
+}
+
+uint32_t GridPlanner::radiusToR2(double radius, float resolution) {
+  const double r = radius / static_cast<double>(resolution);
+  const double r2 = std::floor(r * r * (1.0 + 1.0 / 1048576.0));
+  if (!(r2 < 4294967296.0)) throw std::out_of_range("the footprint radius is too many cells");
+  return static_cast<uint32_t>(r2);
+}
+
+uint32_t GridPlanner::footprintR2() const {
+  needBounds();
+  return radiusToR2(radius_, res_);
+}
+
+void GridPlanner::setupProblem(double start_x, double start_y, double, double goal_x, double goal_y, double) {
+  needBounds();
+  // a coordinate no cell holds is outside the grid
+  if (!worldToCell(static_cast<float>(start_x), ox_, res_, &start_[0])) start_[0] = -1;
+  if (!worldToCell(static_cast<float>(start_y), oy_, res_, &start_[1])) start_[1] = -1;
+  if (!worldToCell(static_cast<float>(goal_x), ox_, res_, &goal_[0])) goal_[0] = -1;
+  if (!worldToCell(static_cast<float>(goal_y), oy_, res_, &goal_[1])) goal_[1] = -1;
+  have_problem_ = true;
+  status_ = -1;
+}
+
+bool GridPlanner::solve() {
+  if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
+  if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
+  status_ = -1;
+  hip::check(kc_planner_solve(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
+  return status_ == KC_PLAN_FOUND;
+}
+
+void GridPlanner::cells(int start_out[2], int goal_out[2]) const {
+  start_out[0] = start_[0];
+  start_out[1] = start_[1];
+  goal_out[0] = goal_[0];
+  goal_out[1] = goal_[1];
+}
+
+std::vector<int32_t> GridPlanner::getPathCells(bool simplify) {
+  std::vector<int32_t> ij;
+  if (status_ != KC_PLAN_FOUND) return ij;
+  size_t n = 0;
+  hip::check(kc_planner_get_path(ctx_.get(), nullptr, 0, &n));
+  ij.resize(2 * n);
+  if (n) hip::check(kc_planner_get_path(ctx_.get(), ij.data(), n, &n));
+  if (!simplify || n < 3) return ij;
+  // a cell goes when the step into it equals the step out of it: exactly collinear runs, nothing geometric
+  std::vector<int32_t> out{ij[0], ij[1]};
+  for (size_t k = 1; k + 1 < n; ++k) {
+    const int32_t di0 = ij[2 * k] - ij[2 * k - 2], dj0 = ij[2 * k + 1] - ij[2 * k - 1];
+    const int32_t di1 = ij[2 * k + 2] - ij[2 * k], dj1 = ij[2 * k + 3] - ij[2 * k + 1];
+    if (di0 != di1 || dj0 != dj1) {
+      out.push_back(ij[2 * k]);
+      out.push_back(ij[2 * k + 1]);
+    }
+  }
+  out.push_back(ij[2 * n - 2]);
+  out.push_back(ij[2 * n - 1]);
+  return out;
+}
+
+std::optional<Path::Path> GridPlanner::getPath(bool simplify) {
+  if (status_ != KC_PLAN_FOUND) return std::nullopt;
+  const std::vector<int32_t> ij = getPathCells(simplify);
+  std::vector<Path::Point> pts;
+  pts.reserve(ij.size() / 2);
+  for (size_t k = 0; k + 1 < ij.size(); k += 2)
+    pts.emplace_back(cellToWorld(ij[k], ox_, res_), cellToWorld(ij[k + 1], oy_, res_), 0.0f);
+  return Path::Path(pts);
+}
+
+void GridPlanner::getField(uint32_t *field_out, uint8_t *valid_out, size_t cap) {
+  if (status_ < 0) throw std::runtime_error("GridPlanner: no solve since the last grid or problem");
+  hip::check(kc_planner_get_field(ctx_.get(), field_out, valid_out, cap));
+}
+
+float GridPlanner::getCost() const {
+  if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
+  return static_cast<float>(cost_) * res_ / 10.0f;
+}
+
+}  // namespace Planning
+}  // namespace Kompass

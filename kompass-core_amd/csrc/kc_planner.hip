@@ -1,0 +1,532 @@
+// Grid planner on gfx950: occupancy grid -> footprint validity -> exact 8-connected cost field from the goal ->
+// steepest-descent path.  Everything is integer work on cells; the world <-> cell conversions
+// and the radius -> R2 rule live in the host class (csrc/host/src/grid_planner.cpp).
+//
+// The reference has no counterpart: its planning submodule wraps OMPL (planning/ompl.h), which stays out of
+// scope.  The yardstick is the heap Dijkstra of tests/planner_ref.py, bit for bit.
+//
+//  (a) validity.  planner_classify_kernel turns the grid's cells (int32 as the mapper writes them, int8 as
+//      kc_cloud_grid_fill does) into a class byte; planner_rowdist_kernel takes, per cell, the distance in cells
+//      to the nearest blocking cell of its own row (255: none within R); planner_valid_kernel asks the 2 R + 1
+//      rows around a cell for rowdist^2 + dy^2 <= R2.  The nearest blocker of a row is the one that decides that
+//      row, so the two passes are the disc test exactly, at O(R) loads a cell instead of O(R^2).
+//  (b) cost field.  planner_relax_kernel: one workgroup per 64 x 64 tile, the tile and a one-cell halo in LDS,
+//      Jacobi iterations in LDS until the tile stops changing (or 256 iterations), the tile written to the OTHER
+//      of two field buffers.  A pass reads one buffer and writes the other: no workgroup reads what another one
+//      writes in the same launch, none waits for another, and the field after k passes is the same on every run.
+//      A workgroup that changed a cell stores the pass number into one device word; the host launches passes in
+//      batches of kPlanBatch and reads that word back once per batch; a word older than the batch's last pass means that
+//      pass changed nothing, i.e. both buffers hold the fixed point.
+//  (c) path.  planner_walk_kernel: one wavefront walks from the start, eight lanes load the eight neighbours of
+//      the current cell, a shuffle reduction takes the smallest (value, order) pair.
+//
+// Plain vector loads and stores only.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "kc_internal.h"
+#include "kompass_hip.h"
+
+namespace kc {
+
+constexpr uint32_t kPlanInf = 0xFFFFFFFFu;
+constexpr int kPlanTile = 64;                  // cells per side of a tile
+constexpr int kPlanHalo = kPlanTile + 2;       // ... with the one-cell ring around it
+constexpr int kPlanThreads = 1024;             // 16 wavefronts, four cells a lane
+constexpr int kPlanRows = kPlanTile * kPlanTile / kPlanThreads;
+constexpr int kPlanLocalIters = 4 * kPlanTile; // Jacobi iterations per tile and pass at the most
+constexpr int kPlanBatch = 8;                  // passes per read-back of the changed word
+constexpr int kPlanBlock = 256;
+constexpr int kPlanMaxBlocks = 2048;
+
+// the neighbour order of the walk (ties go to the first): E, N, W, S, NE, NW, SW, SE
+__constant__ const int kPlanDx[8] = {1, 0, -1, 0, 1, -1, -1, 1};
+__constant__ const int kPlanDy[8] = {0, 1, 0, -1, 1, 1, -1, -1};
+
+template <typename T>
+__global__ __launch_bounds__(kPlanBlock) void planner_classify_kernel(const T *grid, uint8_t *cls, long long n) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const int v = static_cast<int>(grid[i]);
+    cls[i] = v == KC_OCCUPIED ? 2 : (v == KC_UNEXPLORED ? 1 : 0);
+  }
+}
+
+__device__ __forceinline__ bool plan_blocks(uint8_t c, int block_unknown) { return c == 2 || (c == 1 && block_unknown); }
+
+__global__ __launch_bounds__(kPlanBlock) void planner_rowdist_kernel(const uint8_t *cls, uint8_t *rowd, int W, int H, int R,
+                                                                     int block_unknown) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const int x = static_cast<int>(i % W);
+    const uint8_t *row = cls + (i - x);
+    int found = 255;
+    for (int d = 0; d <= R; ++d) {
+      const bool l = x - d >= 0 && plan_blocks(row[x - d], block_unknown);   // cells outside the grid do not block
+      const bool r = x + d < W && plan_blocks(row[x + d], block_unknown);
+      if (l || r) {
+        found = d;
+        break;
+      }
+    }
+    rowd[i] = static_cast<uint8_t>(found);
+  }
+}
+
+__global__ __launch_bounds__(kPlanBlock) void planner_valid_kernel(const uint8_t *rowd, uint8_t *valid, int W, int H, int R,
+                                                                   uint32_t R2) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const int y = static_cast<int>(i / W);
+    const int lo = max(-R, -y), hi = min(R, H - 1 - y);
+    uint8_t ok = 1;
+    for (int dy = lo; dy <= hi; ++dy) {
+      const uint32_t d = rowd[i + static_cast<long long>(dy) * W];
+      if (d != 255u && d * d + static_cast<uint32_t>(dy * dy) <= R2) {
+        ok = 0;
+        break;
+      }
+    }
+    valid[i] = ok;
+  }
+}
+
+__global__ __launch_bounds__(kPlanBlock) void planner_init_kernel(uint32_t *a, uint32_t *b, const uint8_t *valid, long long n,
+                                                                  long long goal) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const uint32_t v = (i == goal && valid[i]) ? 0u : kPlanInf;
+    a[i] = v;
+    b[i] = v;
+  }
+}
+
+// one pass over one tile: `in` is only read, `out` only written (the tile's own cells)
+__global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                     const uint8_t *__restrict__ valid, int W, int H,
+                                                                     unsigned tiles_x, uint32_t *changed_word, uint32_t pass) {
+  __shared__ uint32_t f[kPlanHalo * kPlanHalo];
+  __shared__ uint8_t v[kPlanHalo * kPlanHalo];
+  // the tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more tile rows than gridDim.y holds
+  const int x0 = static_cast<int>(blockIdx.x % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(blockIdx.x / tiles_x) * kPlanTile - 1;
+  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
+    const int lx = k % kPlanHalo, ly = k / kPlanHalo;
+    const int gx = x0 + lx, gy = y0 + ly;
+    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
+    const size_t g = inside ? static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx) : 0;
+    const uint8_t ok = inside ? valid[g] : static_cast<uint8_t>(0);
+    v[k] = ok;
+    f[k] = ok ? in[g] : kPlanInf;  // invalid cells and cells outside the grid never carry a distance
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
+  const int off[8] = {1, kPlanHalo, -1, -kPlanHalo, kPlanHalo + 1, kPlanHalo - 1, -kPlanHalo - 1, -kPlanHalo + 1};
+  int idx[kPlanRows];
+  uint32_t cur[kPlanRows], orig[kPlanRows], mask[kPlanRows];
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int k = (1 + ty + r * (kPlanThreads / kPlanTile)) * kPlanHalo + 1 + tx;
+    idx[r] = k;
+    cur[r] = orig[r] = f[k];
+    uint32_t m = 0;
+    if (v[k]) {
+      const bool e = v[k + 1], n = v[k + kPlanHalo], w = v[k - 1], s = v[k - kPlanHalo];
+      // a diagonal step needs both orthogonal neighbours it passes between
+      m = (e ? 1u : 0u) | (n ? 2u : 0u) | (w ? 4u : 0u) | (s ? 8u : 0u) |
+          ((e && n && v[k + kPlanHalo + 1]) ? 16u : 0u) | ((w && n && v[k + kPlanHalo - 1]) ? 32u : 0u) |
+          ((w && s && v[k - kPlanHalo - 1]) ? 64u : 0u) | ((e && s && v[k - kPlanHalo + 1]) ? 128u : 0u);
+    }
+    mask[r] = m;
+  }
+  for (int it = 0; it < kPlanLocalIters; ++it) {
+    int ch = 0;
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) {
+      uint32_t best = cur[r];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if (mask[r] & (1u << q)) {
+          const uint32_t fn = f[idx[r] + off[q]];
+          const uint32_t c = fn + (q < 4 ? 10u : 14u);  // no wrap: 14 * cells < 2^32 (the cell cap)
+          if (fn != kPlanInf && c < best) best = c;
+        }
+      }
+      if (best < cur[r]) {
+        cur[r] = best;
+        ch = 1;
+      }
+    }
+    if (!__syncthreads_or(ch)) break;  // every lane has read this iteration's values
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) f[idx[r]] = cur[r];
+    __syncthreads();
+  }
+  int changed = 0;
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int gx = x0 + 1 + tx, gy = y0 + 1 + ty + r * (kPlanThreads / kPlanTile);
+    if (gx < W && gy < H) out[static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)] = cur[r];
+    changed |= cur[r] != orig[r];
+  }
+  if (__syncthreads_or(changed) && threadIdx.x == 0) *changed_word = pass;
+}
+
+// status words of the walk: out[0] = cells written, out[1] = 0 done / 1 capacity / 2 no descending neighbour
+__global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field, const uint8_t *valid, int W, int H, int sx,
+                                                          int sy, int32_t *cells, uint32_t cap, uint32_t *out) {
+  const int lane = threadIdx.x;
+  int cx = sx, cy = sy;
+  uint32_t n = 0, status = 0;
+  for (;;) {
+    const size_t c = static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(cx);
+    if (n >= cap) {
+      status = 1;
+      break;
+    }
+    if (lane == 0) cells[n] = static_cast<int32_t>(c);
+    ++n;
+    const uint32_t fc = field[c];
+    if (fc == 0u) break;
+    unsigned long long key = ~0ull;
+    if (lane < 8) {
+      const int dx = kPlanDx[lane], dy = kPlanDy[lane];
+      const int nx = cx + dx, ny = cy + dy;
+      if (nx >= 0 && nx < W && ny >= 0 && ny < H) {
+        const size_t g = static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(nx);
+        bool ok = valid[g] != 0;
+        if (ok && lane >= 4)
+          ok = valid[static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(nx)] != 0 &&
+               valid[static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(cx)] != 0;
+        if (ok) key = (static_cast<unsigned long long>(field[g]) << 3) | static_cast<unsigned long long>(lane);
+      }
+    }
+#pragma unroll
+    for (int d = 4; d >= 1; d >>= 1) {
+      const unsigned long long o = __shfl_xor(key, d, 64);
+      key = o < key ? o : key;
+    }
+    key = __shfl(key, 0, 64);
+    const uint32_t best = static_cast<uint32_t>(key >> 3);
+    if (key == ~0ull || best >= fc) {  // not on a converged field with a reachable start
+      status = 2;
+      break;
+    }
+    const int q = static_cast<int>(key & 7ull);
+    cx += kPlanDx[q];
+    cy += kPlanDy[q];
+  }
+  if (lane == 0) {
+    out[0] = n;
+    out[1] = status;
+  }
+}
+
+}  // namespace kc
+
+using namespace kc;
+
+struct kc_planner {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int W = 0, H = 0;
+  bool have_grid = false;
+  bool have_valid = false;   // d_valid holds the validity of (grid, valid_r2, valid_unknown)
+  uint32_t valid_r2 = 0;
+  int valid_unknown = 0;
+  bool solved = false;
+  int final_buf = 0;         // which of d_field holds the fixed point
+  int start[2] = {0, 0};
+  int status = -1;
+  uint32_t cost = kPlanInf;
+  bool have_path = false;
+  std::vector<int32_t> path; // linear cell indices, start first
+  DevBuf<uint8_t> d_stage;   // a host grid on its way to the classifier
+  DevBuf<uint8_t> d_cls, d_rowd, d_valid;
+  DevBuf<uint32_t> d_field[2];
+  DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status
+  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal]
+  DevBuf<int32_t> d_path;
+  PinBuf<int32_t> h_path;
+};
+
+namespace {
+
+unsigned plan_blocks_for(long long work) {
+  return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(kPlanMaxBlocks, (work + kPlanBlock - 1) / kPlanBlock)));
+}
+
+// a grid passed as "on the device" is read in place: device memory of the context's device, all of it inside
+// one allocation, aligned to its element; refused before any read otherwise (as kc_cloud_grid_extent does)
+int check_device_grid(const kc_planner *c, const void *data, size_t nbytes, int elem_bytes) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, data) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "the device grid %p is not memory HIP knows", data);
+  }
+  if (at.type != hipMemoryTypeDevice)
+    KC_FAIL(KC_ERR_INVALID, "the device grid is not device memory (HIP memory type %d)", static_cast<int>(at.type));
+  if (at.device != c->device)
+    KC_FAIL(KC_ERR_INVALID, "the device grid lives on device %d, the context reads device %d", at.device, c->device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(data)) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device grid");
+  }
+  const uintptr_t p = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(base);
+  if (p < b || nbytes > size || p - b > size - nbytes)
+    KC_FAIL(KC_ERR_INVALID, "the %zu-byte device grid runs outside its %zu-byte allocation", nbytes, size);
+  if (p % static_cast<uintptr_t>(elem_bytes)) KC_FAIL(KC_ERR_INVALID, "the device grid is not aligned to its %d-byte cells", elem_bytes);
+  return KC_OK;
+}
+
+int check_grid_shape(const void *grid, int elem_bytes, int width, int height) {
+  if (!grid) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (elem_bytes != 1 && elem_bytes != 4) KC_FAIL(KC_ERR_INVALID, "grid cells are int8 (1) or int32 (4) bytes, got %d", elem_bytes);
+  if (width <= 0 || height <= 0) KC_FAIL(KC_ERR_INVALID, "grid width and height must be positive, got %d x %d", width, height);
+  if (static_cast<unsigned long long>(width) * static_cast<unsigned long long>(height) > KC_PLANNER_MAX_CELLS)
+    KC_FAIL(KC_ERR_RANGE, "a %d x %d grid is above the cap of %u cells", width, height, static_cast<unsigned>(KC_PLANNER_MAX_CELLS));
+  return KC_OK;
+}
+
+// dev: the grid on the context's device, complete
+int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width, int height) {
+  const long long n = static_cast<long long>(width) * height;
+  c->have_grid = c->have_valid = c->solved = c->have_path = false;
+  KC_TRY(c->d_cls.reserve(static_cast<size_t>(n)));
+  if (elem_bytes == 4)
+    hipLaunchKernelGGL(planner_classify_kernel<int32_t>, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, c->stream,
+                       static_cast<const int32_t *>(dev), c->d_cls.p, n);
+  else
+    hipLaunchKernelGGL(planner_classify_kernel<int8_t>, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, c->stream,
+                       static_cast<const int8_t *>(dev), c->d_cls.p, n);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipStreamSynchronize(c->stream));  // the caller's grid is not read after the call returns
+  c->W = width;
+  c->H = height;
+  c->have_grid = true;
+  return KC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kc_planner_create(int device, kc_planner **out) {
+  if (!out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *out = nullptr;
+  int ndev = 0;
+  KC_HIP(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+  auto *c = new kc_planner();
+  c->device = device;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    set_error("HIP stream creation failed on device %d", device);
+    kc_planner_destroy(c);
+    return KC_ERR_HIP;
+  }
+  int rc;
+  if ((rc = c->d_word.reserve(4)) || (rc = c->h_word.reserve(8))) {
+    kc_planner_destroy(c);
+    return rc;
+  }
+  *out = c;
+  return KC_OK;
+}
+
+void kc_planner_destroy(kc_planner *c) {
+  if (!c) return;
+  hipError_t e = hipSetDevice(c->device);
+  if (c->stream) {
+    e = hipStreamSynchronize(c->stream);
+    e = hipStreamDestroy(c->stream);
+  }
+  (void)e;
+  c->d_stage.release();
+  c->d_cls.release();
+  c->d_rowd.release();
+  c->d_valid.release();
+  c->d_field[0].release();
+  c->d_field[1].release();
+  c->d_word.release();
+  c->h_word.release();
+  c->d_path.release();
+  c->h_path.release();
+  delete c;
+}
+
+int kc_planner_set_grid_host(kc_planner *c, const void *grid, int elem_bytes, int width, int height) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_TRY(check_grid_shape(grid, elem_bytes, width, height));
+  KC_HIP(hipSetDevice(c->device));
+  const size_t nbytes = static_cast<size_t>(width) * static_cast<size_t>(height) * static_cast<size_t>(elem_bytes);
+  KC_TRY(c->d_stage.reserve(nbytes));
+  KC_HIP(hipMemcpyAsync(c->d_stage.p, grid, nbytes, hipMemcpyHostToDevice, c->stream));
+  return planner_take_grid(c, c->d_stage.p, elem_bytes, width, height);
+}
+
+int kc_planner_set_grid_device(kc_planner *c, const void *dev_grid, int elem_bytes, int width, int height) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_TRY(check_grid_shape(dev_grid, elem_bytes, width, height));
+  KC_HIP(hipSetDevice(c->device));
+  const size_t nbytes = static_cast<size_t>(width) * static_cast<size_t>(height) * static_cast<size_t>(elem_bytes);
+  KC_TRY(check_device_grid(c, dev_grid, nbytes, elem_bytes));
+  return planner_take_grid(c, dev_grid, elem_bytes, width, height);
+}
+
+int kc_planner_after_stream(kc_planner *c, void *stream) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_HIP(hipSetDevice(c->device));
+  hipEvent_t e = nullptr;
+  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(stream));
+  if (rc == hipSuccess) rc = hipStreamWaitEvent(c->stream, e, 0);
+  (void)hipEventDestroy(e);  // released once the wait is satisfied
+  KC_HIP(rc);
+  return KC_OK;
+}
+
+int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell[2], uint32_t r2, int allow_unknown,
+                     int *status_out, uint32_t *cost_out, int *passes_out) {
+  if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve before a grid was set");
+  int R = 0;
+  while (static_cast<unsigned long long>(R + 1) * static_cast<unsigned long long>(R + 1) <= r2 && R <= KC_PLANNER_MAX_RADIUS_CELLS) ++R;
+  if (R > KC_PLANNER_MAX_RADIUS_CELLS)
+    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const long long n = static_cast<long long>(W) * H;
+  c->solved = c->have_path = false;
+  c->status = -1;
+  c->cost = kPlanInf;
+  if (cost_out) *cost_out = kPlanInf;
+  if (passes_out) *passes_out = 0;
+  const unsigned blocks = plan_blocks_for(n);
+  const int unknown_blocks = allow_unknown ? 0 : 1;
+  if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) {
+    c->have_valid = false;
+    KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
+    KC_TRY(c->d_valid.reserve(static_cast<size_t>(n)));
+    hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
+    hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_valid.p, W, H, R, r2);
+    KC_HIP(hipGetLastError());
+    c->have_valid = true;
+    c->valid_r2 = r2;
+    c->valid_unknown = unknown_blocks;
+  }
+  const bool start_in = start_cell[0] >= 0 && start_cell[0] < W && start_cell[1] >= 0 && start_cell[1] < H;
+  const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
+  const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
+  const long long start = start_in ? static_cast<long long>(start_cell[1]) * W + start_cell[0] : -1;
+  KC_TRY(c->d_field[0].reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_field[1].reserve(static_cast<size_t>(n)));
+  hipLaunchKernelGGL(planner_init_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, goal);
+  KC_HIP(hipMemsetAsync(c->d_word.p, 0, 4 * sizeof(uint32_t), s));
+  KC_HIP(hipGetLastError());
+  uint32_t pass = 0, last_changed = 0;
+  if (goal_in) {
+    // every pass that is not the last gives at least one more cell its final value: cells + 1 passes always do
+    const unsigned long long cap = static_cast<unsigned long long>(n) + 1ull;
+    // at most 2^28 / 64 tiles (a one-cell-wide grid), within gridDim.x
+    const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile), tiles_y = static_cast<unsigned>((H + kPlanTile - 1) / kPlanTile);
+    const dim3 tiles(tiles_x * tiles_y);
+    for (;;) {
+      for (int b = 0; b < kPlanBatch; ++b) {
+        ++pass;
+        hipLaunchKernelGGL(planner_relax_kernel, tiles, dim3(kPlanThreads), 0, s, c->d_field[(pass - 1) & 1].p,
+                           c->d_field[pass & 1].p, c->d_valid.p, W, H, tiles_x, c->d_word.p, pass);
+      }
+      KC_HIP(hipGetLastError());
+      KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      KC_HIP(hipStreamSynchronize(s));
+      last_changed = c->h_word.p[0];
+      if (last_changed < pass) break;
+      if (pass >= cap)
+        KC_FAIL(KC_ERR_RANGE, "the cost field of a %d x %d grid still changed after %u passes (cap %llu)", W, H, pass, cap);
+    }
+  }
+  c->final_buf = static_cast<int>(pass & 1u);
+  c->solved = true;
+  c->start[0] = start_cell[0];
+  c->start[1] = start_cell[1];
+  c->h_word.p[3] = kPlanInf;
+  c->h_word.p[4] = 0;
+  c->h_word.p[5] = 0;
+  if (start_in) {
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[3], c->d_field[c->final_buf].p + start, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[4], c->d_valid.p + start, 1, hipMemcpyDeviceToHost, s));
+  }
+  if (goal_in) KC_HIP(hipMemcpyAsync(&c->h_word.p[5], c->d_valid.p + goal, 1, hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  const bool start_ok = start_in && (c->h_word.p[4] & 0xFFu) != 0, goal_ok = goal_in && (c->h_word.p[5] & 0xFFu) != 0;
+  int st = KC_PLAN_FOUND;
+  if (!start_in) st = KC_PLAN_START_OUTSIDE;
+  else if (!goal_in) st = KC_PLAN_GOAL_OUTSIDE;
+  else if (!start_ok) st = KC_PLAN_START_INVALID;
+  else if (!goal_ok) st = KC_PLAN_GOAL_INVALID;
+  else if (c->h_word.p[3] == kPlanInf) st = KC_PLAN_UNREACHABLE;
+  c->status = st;
+  c->cost = st == KC_PLAN_FOUND ? c->h_word.p[3] : kPlanInf;
+  *status_out = st;
+  if (cost_out) *cost_out = c->cost;
+  // passes a batch of one would have run: the last that changed a cell and the one that found nothing to change
+  if (passes_out) *passes_out = goal_in ? static_cast<int>(last_changed + 1u) : 0;
+  return KC_OK;
+}
+
+int kc_planner_get_field(kc_planner *c, uint32_t *field_out, uint8_t *valid_out, size_t cap) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_field before kc_planner_solve");
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipSetDevice(c->device));
+  if (field_out)
+    KC_HIP(hipMemcpyAsync(field_out, c->d_field[c->final_buf].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (valid_out) KC_HIP(hipMemcpyAsync(valid_out, c->d_valid.p, n, hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_planner_get_path(kc_planner *c, int32_t *cells_ij_out, size_t cap_points, size_t *count_out) {
+  if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_path before kc_planner_solve");
+  if (c->status != KC_PLAN_FOUND) return KC_OK;  // no path: zero points
+  if (!c->have_path) {
+    KC_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    // every step lowers the field by 10 at least
+    const size_t cap = static_cast<size_t>(c->cost / 10u) + 2;
+    KC_TRY(c->d_path.reserve(cap));
+    KC_TRY(c->h_path.reserve(cap));
+    hipLaunchKernelGGL(planner_walk_kernel, dim3(1), dim3(64), 0, s, c->d_field[c->final_buf].p, c->d_valid.p, c->W, c->H,
+                       c->start[0], c->start[1], c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
+    KC_HIP(hipGetLastError());
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[1], c->d_word.p + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipStreamSynchronize(s));
+    const uint32_t count = c->h_word.p[1], wst = c->h_word.p[2];
+    if (wst != 0u || count == 0u || count > cap)
+      KC_FAIL(KC_ERR_STATE, "the path walk stopped after %u cells with status %u", count, wst);
+    KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipStreamSynchronize(s));
+    c->path.assign(c->h_path.p, c->h_path.p + count);
+    c->have_path = true;
+  }
+  *count_out = c->path.size();
+  if (!cells_ij_out) return KC_OK;  // the count alone
+  if (c->path.size() > cap_points) KC_FAIL(KC_ERR_RANGE, "%zu path cells do not fit the output capacity %zu", c->path.size(), cap_points);
+  for (size_t k = 0; k < c->path.size(); ++k) {
+    cells_ij_out[2 * k] = c->path[k] % c->W;
+    cells_ij_out[2 * k + 1] = c->path[k] / c->W;
+  }
+  return KC_OK;
+}
+
+}  // extern "C"

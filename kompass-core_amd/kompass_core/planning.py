@@ -1,0 +1,77 @@
+"""Grid planning front end: an occupancy grid on the host or on the device -> a collision-free
+`kompass_cpp.types.Path` for the followers (`kompass_cpp.planning.GridPlanner`).
+
+Not the reference's `OMPLGeometric` (`kompass_core/third_party/ompl/planner.py`, an OMPL wrapper and out of
+scope): a deterministic, exact 8-connected shortest path on the grid.  `setup_problem` is shaped like
+`OMPLGeometric.setup_problem` (:168-212), with the grid as one more argument.  The robot is a disc of its
+circumscribed horizontal radius (the cylinder's or sphere's radius, half the box's diagonal): yaw-free and
+conservative."""
+from typing import Dict, Optional
+
+import kompass_cpp
+
+from .models import Robot, RobotGeometry
+
+
+class GridPlanner:
+    def __init__(self, robot: Robot, allow_unknown: bool = True, margin: float = 0.0, simplify: bool = False):
+        """allow_unknown: UNEXPLORED cells can be crossed (default) or block like OCCUPIED ones.
+        margin: metres added to the robot's radius.  simplify: drop the interior points of straight runs."""
+        if not RobotGeometry.is_valid_parameters(robot.geometry_type, robot.geometry_params):
+            raise ValueError(f"invalid geometry parameters {robot.geometry_params} for {robot.geometry_type}")
+        self._planner = kompass_cpp.planning.GridPlanner(
+            robot_shape=RobotGeometry.Type.to_kompass_cpp_lib(robot.geometry_type),
+            robot_dimensions=[float(v) for v in robot.geometry_params], allow_unknown=bool(allow_unknown),
+            margin=float(margin))
+        self.simplify = bool(simplify)
+        self.solution = None
+
+    def setup_problem(self, map_meta_data: Dict, start_x: float, start_y: float, start_yaw: float, goal_x: float,
+                      goal_y: float, goal_yaw: float, grid=None):
+        """map_meta_data: origin_x, origin_y, width, height, resolution; cell (i, j) of the (width, height) grid
+        sits at (origin_x + i * resolution, origin_y + j * resolution).
+        grid: an int32 / int8 numpy array grid[i, j]; a device array with `__cuda_array_interface__` in
+        column-major strides (read in place); a `kompass_cpp.mapping.LocalMapper` or the front end's
+        `kompass_core.mapping.LocalMapper` (its last grid on the device; map_meta_data may then be None); or None
+        to keep the grid of the last call."""
+        mapper = grid
+        if hasattr(grid, "_mapper"):  # the front end's LocalMapper holds the class once it has mapped a scan
+            mapper = grid._mapper
+            if mapper is None:
+                raise ValueError("the LocalMapper has no grid yet: update it from a scan first")
+        if isinstance(mapper, kompass_cpp.mapping.LocalMapper):
+            self._planner.set_grid_from_mapper(mapper)
+        else:
+            if map_meta_data is None:
+                raise ValueError("map_meta_data is needed unless the grid is a LocalMapper")
+            missing = [k for k in ("origin_x", "origin_y", "width", "height", "resolution") if k not in map_meta_data]
+            if missing:
+                raise ValueError(f"map_meta_data lacks {missing}")
+            self._planner.set_space_bounds_from_map(
+                origin_x=map_meta_data["origin_x"], origin_y=map_meta_data["origin_y"], width=map_meta_data["width"],
+                height=map_meta_data["height"], resolution=map_meta_data["resolution"])
+            if grid is not None:
+                self._planner.set_grid(grid)
+        self._planner.setup_problem(start_x=start_x, start_y=start_y, start_yaw=start_yaw, goal_x=goal_x,
+                                    goal_y=goal_y, goal_yaw=goal_yaw)
+        self.solution = None
+
+    def solve(self) -> Optional["kompass_cpp.types.Path"]:
+        """The path, or None when the start or goal is outside the grid, invalid, or the goal out of reach."""
+        self.solution = self._planner.get_solution(self.simplify) if self._planner.solve() else None
+        return self.solution
+
+    def get_cost(self) -> float:
+        return self._planner.get_cost()
+
+    @property
+    def status(self) -> int:
+        return self._planner.get_status()
+
+    @property
+    def passes(self) -> int:
+        return self._planner.get_passes()
+
+    @property
+    def path_cells(self):
+        return self._planner.get_path_cells(self.simplify)

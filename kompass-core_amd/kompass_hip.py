@@ -220,6 +220,15 @@ SIGNATURES = {
     "kc_dvz_create": (C.c_int, [C.c_int, _sz, C.POINTER(_vp)]),
     "kc_dvz_destroy": (None, [_vp]),
     "kc_dvz_deform": (C.c_int, [_vp, C.POINTER(DvzZone), _dp, _dp, _sz, _dp, _dp]),
+    "kc_planner_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
+    "kc_planner_destroy": (None, [_vp]),
+    "kc_planner_set_grid_host": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "kc_planner_set_grid_device": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "kc_planner_after_stream": (C.c_int, [_vp, C.c_void_p]),
+    "kc_planner_solve": (C.c_int, [_vp, _ip, _ip, C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_int)]),
+    "kc_planner_get_field": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
+    "kc_planner_get_path": (C.c_int, [_vp, C.c_void_p, _sz, C.POINTER(_sz)]),
 }
 
 _lib = None
@@ -1158,3 +1167,73 @@ class DvzContext:
         _check(lib().kc_dvz_deform(self.h, C.byref(z), _pd(a), _pd(r), len(a), out, _pd(rad)))
         res = (float(out[0]), float(out[1]), int(out[2]))
         return res + (rad[:len(a)],) if radii else res
+
+
+PLAN_FOUND, PLAN_START_OUTSIDE, PLAN_GOAL_OUTSIDE, PLAN_START_INVALID, PLAN_GOAL_INVALID, PLAN_UNREACHABLE = range(6)
+PLAN_INF = 0xFFFFFFFF
+
+
+class PlannerContext:
+    """Owner of one kc_planner context (grid planner).  Works in cells: a grid is an array
+    g[i, j] of (width, height) cells, i along x; world coordinates are the business of kompass_cpp.planning."""
+
+    def __init__(self, device=0):
+        self.h = _vp()
+        self.shape = (0, 0)
+        _check(lib().kc_planner_create(int(device), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().kc_planner_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_grid(self, grid):
+        """grid[i, j]: an int32 or int8 (width, height) array on the host, any memory order."""
+        g = np.asarray(grid)
+        if g.ndim != 2 or g.dtype not in (np.int32, np.int8):
+            raise ValueError("expected a 2-D int32 or int8 grid")
+        g = np.asfortranarray(g)  # cell (i, j) at i + j * width
+        _check(lib().kc_planner_set_grid_host(self.h, g.ctypes.data, g.itemsize, g.shape[0], g.shape[1]))
+        self.shape = g.shape
+
+    def set_grid_device(self, device_ptr, width, height, elem_bytes=4):
+        """A finished grid on the context's device (MapperContext.grid_device_ptr after sync: int32, width =
+        grid_height, height = grid_width; CloudContext.occupancy_grid(to_host=False): int8)."""
+        _check(lib().kc_planner_set_grid_device(self.h, int(device_ptr), int(elem_bytes), int(width), int(height)))
+        self.shape = (int(width), int(height))
+
+    def after_stream(self, stream=None):
+        """Order the next device grid's read after the work queued so far on `stream` (None: the legacy default)."""
+        _check(lib().kc_planner_after_stream(self.h, stream))
+
+    def solve(self, start, goal, r2=0, allow_unknown=True):
+        """-> (status, cost, passes): PLAN_* status, field[start] in units of 10 per straight step."""
+        s = (C.c_int32 * 2)(int(start[0]), int(start[1]))
+        g = (C.c_int32 * 2)(int(goal[0]), int(goal[1]))
+        st, cost, passes = C.c_int(-1), C.c_uint32(0), C.c_int(0)
+        _check(lib().kc_planner_solve(self.h, s, g, int(r2), int(bool(allow_unknown)), C.byref(st), C.byref(cost),
+                                      C.byref(passes)))
+        return st.value, cost.value, passes.value
+
+    def field(self):
+        """(field uint32 [width, height], valid bool [width, height]) of the last solve."""
+        w, h = self.shape
+        f = np.empty((w, h), np.uint32, order="F")
+        v = np.empty((w, h), np.uint8, order="F")
+        _check(lib().kc_planner_get_field(self.h, f.ctypes.data, v.ctypes.data, f.size))
+        return f, v.astype(bool)
+
+    def path(self):
+        """(n, 2) int32 cells (i, j) from the start to the goal; n = 0 when the last solve found none."""
+        n = _sz(0)
+        _check(lib().kc_planner_get_path(self.h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 2), np.int32)
+        if n.value:
+            _check(lib().kc_planner_get_path(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out

@@ -215,3 +215,18 @@ def pcd_indoor_map(n_points: int, seed: int = 0, size=(100.0, 60.0)) -> np.ndarr
     ceil = np.stack([rng.uniform(0, sx / 2, nc), rng.uniform(0, sy, nc), 2.5 + rng.normal(0, 0.02, nc)], axis=1)
     pts = np.concatenate([floor, walls, ceil]).astype(np.float32)
     return pts[rng.permutation(n)]
+
+
+def pcd_indoor_map_doors(n_points: int, seed: int = 0, size=(100.0, 60.0), door=1.0) -> np.ndarray:
+    """pcd_indoor_map with a `door` metres wide opening in the middle of every 5 m wall segment: the wall points
+    (z above the floor noise) whose position along their wall is within door / 2 of a segment's middle are taken
+    out, the floor returns under them stay.  Every room then connects to its neighbours (tools/planner_time.py)."""
+    pts = pcd_indoor_map(n_points, seed, size)
+    x, y, z = pts[:, 0].astype(np.float64), pts[:, 1].astype(np.float64), pts[:, 2]
+    on_x_wall = np.abs(y / 5.0 - np.round(y / 5.0)) * 5.0 < 0.15   # a wall that runs along x
+    on_y_wall = np.abs(x / 5.0 - np.round(x / 5.0)) * 5.0 < 0.15
+    mid_x = np.abs(np.mod(x, 5.0) - 2.5) < door / 2
+    mid_y = np.abs(np.mod(y, 5.0) - 2.5) < door / 2
+    # 2.5 m from every crossing, so a doorway never touches the other family of walls
+    drop = (z > 0.1) & ((on_x_wall & mid_x & ~on_y_wall) | (on_y_wall & mid_y & ~on_x_wall))
+    return np.ascontiguousarray(pts[~drop])

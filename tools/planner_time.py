@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Grid planner timing: kc_planner_solve on the PCD benchmark's map (100 x 60 m at 0.05 m = 2004 x
+1204 cells, synthetic.pcd_indoor_map_doors, corner to corner) and on a 500 x 500 clutter grid, from a
+device-resident grid and from a host array; the path walk on its own; and the one-thread CPU baseline, the heap
+Dijkstra of tests/planner_ref.py.  Warm-up, then --reps repetitions: median and min .. max, the device named.
+
+  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--json out.json]
+  rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
+"""
+import argparse
+import ctypes as C
+import json
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
+    sys.path.insert(0, str(p))
+import kompass_hip as kh  # noqa: E402
+import planner_ref as ref  # noqa: E402
+import synthetic as syn  # noqa: E402
+
+
+def stats_ms(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), reps=reps)
+
+
+def device_name():
+    try:
+        out = subprocess.run(["rocminfo"], capture_output=True, text=True, timeout=30).stdout
+        names = [ln.split(":", 1)[1].strip() for ln in out.splitlines() if "Marketing Name" in ln]
+        names = [n for n in names if n]
+        gpus = [n for n in names if "Instinct" in n or "MI3" in n]
+        return gpus[0] if gpus else (names[-1] if names else "unknown")
+    except Exception:
+        return "unknown"
+
+
+def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
+    w, h = host_grid.shape
+    out = dict(scene=name, cells=[w, h], r2=r2)
+    # device-resident grid: classification + validity + field, then the same with the validity map kept
+    ctx.set_grid_device(dev_ptr, w, h, elem)
+    st, cost, passes = ctx.solve(start, goal, r2)
+    out.update(status=st, cost=cost, passes=passes, launched=-(-passes // 8) * 8)
+
+    def from_device():
+        ctx.set_grid_device(dev_ptr, w, h, elem)
+        ctx.solve(start, goal, r2)
+
+    def from_host():
+        ctx.set_grid(host_grid)
+        ctx.solve(start, goal, r2)
+
+    out["device_grid_ms"] = stats_ms(from_device, a.reps)
+    out["host_grid_ms"] = stats_ms(from_host, a.reps)
+    out["resolve_ms"] = stats_ms(lambda: ctx.solve(start, goal, r2), a.reps)   # grid and validity resident: field only
+
+    def walk():
+        ctx.solve(start, goal, r2)
+        ctx.path()
+
+    out["resolve_and_walk_ms"] = stats_ms(walk, a.reps)
+    out["path_cells"] = int(len(ctx.path()))
+    # what a host walk would have to pay first: the field's way back
+    out["field_readback_ms"] = stats_ms(lambda: ctx.field(), max(3, a.reps // 5))
+    if a.cpu_reps > 0:
+        valid = ref.validity(host_grid, r2)
+        out["cpu_validity_ms"] = stats_ms(lambda: ref.validity(host_grid, r2), a.cpu_reps, warm=0)
+        out["cpu_dijkstra_ms"] = stats_ms(lambda: ref.cost_field(valid, goal), a.cpu_reps, warm=0)
+        f, v = ctx.field()
+        assert (f == ref.cost_field(valid, goal)).all() and (v == valid).all()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--cpu-reps", type=int, default=1)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if kh.device_count() < 1:
+        raise SystemExit("needs a HIP device")
+    ctx, cloud = kh.PlannerContext(), kh.CloudContext()
+    res = []
+    # the PCD benchmark's map, the grid where kc_cloud_grid_device leaves it (int8)
+    pts = syn.pcd_indoor_map_doors(2_000_000)
+    host_grid, origin = cloud.occupancy_grid(pts, 0.05, 0.1, 1.0)
+    dev, (cx, cy), _ = cloud.occupancy_grid(pts, 0.05, 0.1, 1.0, to_host=False)
+    cell = lambda x, y: (ref.world_to_cell(x, origin[0], 0.05), ref.world_to_cell(y, origin[1], 0.05))  # noqa: E731
+    res.append(scene("pcd 2004 x 1204", ctx, host_grid, dev, 1, cell(2.5, 2.5), cell(97.5, 57.5),
+                     ref.radius_to_r2(0.2, 0.05), a))
+    # 500 x 500 clutter, int32 as the mapper writes it, in a device buffer of the tool's own
+    rng = np.random.default_rng(3)
+    g = np.asfortranarray(np.where(rng.random((500, 500)) < 0.1, 100, 0).astype(np.int32))
+    g[:8, :8] = g[-8:, -8:] = 0
+    hip = C.CDLL("libamdhip64.so")
+    buf = C.c_void_p()
+    assert hip.hipMalloc(C.byref(buf), C.c_size_t(g.nbytes)) == 0
+    assert hip.hipMemcpy(buf, C.c_void_p(g.ctypes.data), C.c_size_t(g.nbytes), 1) == 0
+    res.append(scene("clutter 500 x 500", ctx, g, buf.value, 4, (3, 3), (496, 496), 1, a))
+    hip.hipFree(buf)
+    out = dict(device=device_name(), date=time.strftime("%Y-%m-%d"), scenes=res)
+    for s in res:
+        print(f"{s['scene']}: status {s['status']}, cost {s['cost']}, {s['passes']} passes ({s['launched']} launched), "
+              f"{s['path_cells']} path cells")
+        for k in ("device_grid_ms", "host_grid_ms", "resolve_ms", "resolve_and_walk_ms", "field_readback_ms",
+                  "cpu_validity_ms", "cpu_dijkstra_ms"):
+            if k in s:
+                v = s[k]
+                print(f"  {k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+    print(json.dumps(out))
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(json.dumps(out, indent=1))
+    ctx.close()
+    cloud.close()
+
+
+if __name__ == "__main__":
+    main()
