@@ -572,8 +572,9 @@ int kc_cloud_to_laserscan_typed(kc_cloud *c, const int8_t *data, size_t nbytes,
   const long long per_row = (static_cast<long long>(row_step) + point_step - 1) / point_step;
   const long long n_rec = per_row * height;
   // nothing can be closer than a negative / NaN max_range: the reference leaves
-  // every bin at max_range
-  if (n_rec == 0 || nbytes == 0 || !(max_range >= 0.0)) return KC_OK;
+  // every bin at max_range.  -0.0 belongs here too (`distance < -0.0` never holds): its bit pattern is above every
+  // distance's, so bins armed with it on the global-atomic path would take any point
+  if (n_rec == 0 || nbytes == 0 || !(max_range >= 0.0) || std::signbit(max_range)) return KC_OK;
   if (n_rec > 0x7FFFFFFFll) KC_FAIL(KC_ERR_RANGE, "more than 2^31 point records");
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;

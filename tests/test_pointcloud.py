@@ -62,11 +62,11 @@ def test_oracle_num_bins_overload_and_minimum():
     np.testing.assert_array_equal(r, [f(1.0, 0.1), f(-0.1, 3.0), f(-1.5, -0.1), f(0.1, -2.5)])
 
 
-def _random_cloud(rng, n, edge_points=200, bins=360):
+def _random_cloud(rng, n, edge_points=200, bins=360, step=None):
     xyz = np.column_stack([rng.uniform(-8, 8, n), rng.uniform(-8, 8, n), rng.uniform(-0.5, 2.5, n)])
     # points exactly on / next to bin edges, on the axes, at the origin, out of range
     k = rng.integers(0, bins, edge_points)
-    th = k * (2.0 * np.pi / bins) + rng.choice([0.0, 1e-7, -1e-7, 3e-7], edge_points)
+    th = k * (step or 2.0 * np.pi / bins) + rng.choice([0.0, 1e-7, -1e-7, 3e-7], edge_points)  # step: bins of that width
     rad = rng.uniform(0.5, 6.0, edge_points)
     edge = np.column_stack([rad * np.cos(th), rad * np.sin(th), np.full(edge_points, 0.3)])
     special = np.array([[1.0, 0.0, 0.1], [1.0, -0.0, 0.1], [2.0, -1e-30, 0.1], [-3.0, 0.0, 0.1], [-3.0, -0.0, 0.1],
@@ -280,10 +280,13 @@ def _load_and_cast_bytes(buf, off, ftype):
         return np.float32(struct.unpack("<f" if ftype == 7 else "<d", raw)[0])
 
 
-def _scan_from_bytes(buf, nbytes, step, n, offs, ftype, max_range, min_z, max_z, num_bins):
+def _scan_from_bytes(buf, nbytes, step, n, offs, ftype, max_range, min_z, max_z, num_bins, angle_step=None):
     """pointCloudToLaserScanFromRaw (pointcloud.h:205-259) in plain Python over `_load_and_cast_bytes`; a record whose
-    furthest field would read past `nbytes` is skipped (:139-146, with the field's own size)."""
+    furthest field would read past `nbytes` is skipped (:139-146, with the field's own size).  With `angle_step` it is
+    the other overload (:116-177): ceil(2 pi / angle_step) bins, bin = int(angle / angle_step)."""
     size = np.dtype(FIELD_DTYPES[ftype]).itemsize
+    if angle_step is not None:
+        num_bins = int(np.ceil(2.0 * np.pi / angle_step))
     out = np.full(num_bins, float(max_range))
     for k in range(n):
         start = k * step
@@ -300,7 +303,8 @@ def _scan_from_bytes(buf, nbytes, step, n, offs, ftype, max_range, min_z, max_z,
         #                                            arctan2 is 1 ulp off at x == y, which moves points across bins)
         if ang < 0.0:
             ang += 2.0 * np.pi
-        b = min(int((ang / (2.0 * np.pi)) * num_bins), num_bins - 1)
+        b = int(ang / angle_step) if angle_step is not None else int((ang / (2.0 * np.pi)) * num_bins)
+        b = min(b, num_bins - 1)
         d = float(np.sqrt(r2))
         if d < out[b]:
             out[b] = d
@@ -382,3 +386,235 @@ def test_zone_checker_takes_typed_clouds():
             got = z.check_cloud(data, step, len(vals) * step, 1, len(vals), xo, yo, zo, fwd, field_type=ftype)
             want = o.check_cloud(data, step, len(vals) * step, 1, len(vals), xo, yo, zo, fwd)
             assert np.float32(got) == np.float32(want)
+
+
+# ---- more bins than the LDS holds: the global-atomic route of kc_cloud_to_laserscan ----------------------------
+# Up to 8192 bins a workgroup keeps its minima in LDS and a merge kernel hands them over; above, the bins are armed
+# with max_range in global memory, every point is a 64-bit atomic min there and the edge list is copied back.
+LDS_MAX_BINS = 8192
+BIG_BINS = (dict(num_bins=8192), dict(num_bins=8193), dict(num_bins=20000), dict(angle_step=5e-4))
+
+
+def _nbins(kw):
+    return int(np.ceil(2.0 * np.pi / kw["angle_step"])) if "angle_step" in kw else kw["num_bins"]
+
+
+def test_oracle_many_bins_match_the_byte_statement():
+    """The yardstick of the tests below, first: the C oracle at 8192 / 8193 / 20000 bins and at angle_step 5e-4
+    (12567 bins) against the plain-Python statement, on a cloud with points on and next to this grid's bin edges."""
+    for k, kw in enumerate(BIG_BINS):
+        nb = _nbins(kw)
+        assert nb == (8192, 8193, 20000, 12567)[k]
+        xyz = _random_cloud(np.random.default_rng(40 + k), 2500, edge_points=400, bins=nb, step=kw.get("angle_step"))
+        n, data = len(xyz), cloud_bytes(xyz)
+        got = ko.pointcloud_to_laserscan(data, STRIDE, n * STRIDE, 1, n, 0, 4, 8, 12.0, 0.0, 2.0, **kw)
+        want = _scan_from_bytes(data, data.size, STRIDE, n, (0, 4, 8), 7, 12.0, 0.0, 2.0, nb, kw.get("angle_step"))
+        if "angle_step" in kw:
+            np.testing.assert_array_equal(got[1], np.arange(nb) * kw["angle_step"])
+            got = got[0]
+        assert got.shape == (nb,)
+        np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))
+        assert 1000 < (want < 12.0).sum() < nb
+
+
+def _laid_out(xyz, layout):
+    """(data, point_step, row_step, height, width, x_off, y_off, z_off, field_type, records) of one cloud"""
+    n = len(xyz)
+    if layout == "packed16":
+        return cloud_bytes(xyz), 16, n * 16, 1, n, 0, 4, 8, 7, n
+    if layout == "unaligned":  # records of 13 bytes: every float is misaligned
+        return cloud_bytes(xyz, 13, 1), 13, n * 13, 1, n, 1, 5, 9, 7, n
+    if layout == "rows_with_padding":  # row_step not a multiple of point_step
+        w, h = 100, n // 100
+        body = cloud_bytes(xyz[:w * h]).view(np.uint8).reshape(h, w * 16)
+        padded = np.concatenate([body, np.zeros((h, 8), np.uint8)], axis=1)
+        return padded.reshape(-1).view(np.int8), 16, w * 16 + 8, h, w, 0, 4, 8, 7, w * h
+    ftype = {"float64": 8, "int16": 3}[layout]
+    if ftype == 3:  # centimetres: the integer fields keep the shape of the cloud
+        xyz = xyz[np.isfinite(xyz).all(axis=1)] * np.float32(100.0)
+    data, step, (xo, yo, zo), vals = typed_cloud(xyz, ftype)
+    return data, step, len(vals) * step, 1, len(vals), xo, yo, zo, ftype, len(vals)
+
+
+def _edge_listed(xyz, min_z, max_z, num_bins, angle_step=None):
+    """How many points of a float32 cloud the device hands to the host: those that pass the filters of
+    pointcloud.h:153-159 and whose angle (atan2 in double) lies within 1e-6 rad of an edge of its bin."""
+    x, y, z = (xyz[:, k].astype(np.float32) for k in range(3))
+    with np.errstate(over="ignore", invalid="ignore"):
+        r2 = (x * x + y * y).astype(np.float64)
+    zd = z.astype(np.float64)
+    keep = ~(r2 < 1e-6) & ~(zd < min_z) & ~((max_z >= 0.0) & (zd > max_z)) & np.isfinite(x) & np.isfinite(y)
+    ang = np.arctan2(y[keep].astype(np.float64), x[keep].astype(np.float64))
+    ang[ang < 0.0] += 2.0 * np.pi
+    width = angle_step if angle_step is not None else 2.0 * np.pi / num_bins
+    t = ang / angle_step if angle_step is not None else (ang / (2.0 * np.pi)) * num_bins
+    frac = t - np.floor(t)
+    edge = 1e-6 / width
+    return int(((frac < edge) | (frac > 1.0 - edge)).sum())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["packed16", "unaligned", "rows_with_padding", "float64", "int16"])
+def test_gpu_global_route_matches_oracle_bit_for_bit(layout):
+    import kompass_hip as kh
+
+    ctx = None
+    for k, kw in enumerate(BIG_BINS):
+        nb = _nbins(kw)
+        xyz = _random_cloud(np.random.default_rng(60 + k), 20000, edge_points=400, bins=nb, step=kw.get("angle_step"))
+        data, step, row, h, w, xo, yo, zo, ftype, n = _laid_out(xyz, layout)
+        max_range = 1200.0 if layout == "int16" else 12.0
+        if ctx is None:
+            ctx = kh.CloudContext(max_bytes=len(data), max_bins=720)  # (the bin buffers grow on demand)
+            ctx.timing_enable()
+        for min_z, max_z in ((0.0, 2.0), (-1.0, -1.0)):
+            if layout == "int16":
+                min_z, max_z = min_z * 100.0, max_z * 100.0 if max_z > 0 else max_z
+            want = ko.pointcloud_to_laserscan(data, step, row, h, w, xo, yo, zo, max_range, min_z, max_z,
+                                              field_type=ftype, **kw)
+            got = ctx.to_laserscan(data, step, row, h, w, xo, yo, zo, max_range, min_z, max_z, field_type=ftype, **kw)
+            if "angle_step" in kw:
+                np.testing.assert_array_equal(got[1].view(np.uint64), want[1].view(np.uint64))
+                got, want = got[0], want[0]
+            assert got.shape == (nb,)
+            np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))
+            assert (want < max_range).sum() > nb // 4
+            # which route ran: the LDS route ends in the merge kernel, the global one has none; on either, the edge
+            # points came back through the route's own list
+            names = [name for name, _ in ctx.timings()]
+            assert "cloud_bins_kernel" in names
+            assert ("cloud_merge_kernel" in names) == (nb <= LDS_MAX_BINS), (nb, names)
+            assert 0 < ctx.last_rebinned() < n // 4
+            if ftype == 7 and layout != "rows_with_padding":
+                assert ctx.last_rebinned() == _edge_listed(xyz, min_z, max_z, nb, kw.get("angle_step"))
+    ctx.close()
+
+
+_BIG_CLOUD = {}
+
+
+def _big_cloud():
+    if not _BIG_CLOUD:
+        rng = np.random.default_rng(9)
+        n = 1048577
+        xyz = np.column_stack([rng.uniform(-30, 30, n), rng.uniform(-30, 30, n), rng.uniform(0.0, 1.2, n)])
+        _BIG_CLOUD["xyz"] = xyz.astype(np.float32)
+    return _BIG_CLOUD["xyz"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 1025, 262145, 1048577])
+def test_gpu_point_counts_reach_the_stride_loops_on_both_routes(n):
+    """One point; two workgroups; one point past the 256 x 1024 lanes of the capped grid (the stride loop of the
+    general records, the second of the four loads a lane keeps in flight on packed records); one past four strides
+    (the packed loop's second round).  The last points of the cloud are the closest of their bins, so a loop that
+    stopped early shows."""
+    import kompass_hip as kh
+
+    xyz = _big_cloud()[:n].copy()
+    tail = min(n, 3)
+    xyz[n - tail:] = np.float32([[4e-3, 2e-4, 0.5], [-2e-4, 3e-3, 0.5], [-2e-3, -1e-4, 0.5]])[:tail]
+    layouts = ["packed16", "unaligned"] if n <= 262145 else ["packed16"]
+    ctx = kh.CloudContext(max_bytes=16 * n, max_bins=720)
+    ctx.timing_enable()
+    for layout in layouts:
+        data, step, row, h, w, xo, yo, zo, ftype, _ = _laid_out(xyz, layout)
+        assert len(data) <= (16 << 20) + 16
+        for nb in (720, 8193):
+            want = ko.pointcloud_to_laserscan(data, step, row, h, w, xo, yo, zo, 25.0, 0.0, 1.0, num_bins=nb)
+            got = ctx.to_laserscan(data, step, row, h, w, xo, yo, zo, 25.0, 0.0, 1.0, num_bins=nb)
+            np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))
+            assert ("cloud_merge_kernel" in [name for name, _ in ctx.timings()]) == (nb <= LDS_MAX_BINS)
+            assert ctx.last_rebinned() == _edge_listed(xyz, 0.0, 1.0, nb)
+            assert want.min() == float(np.sqrt(xyz[n - 1, 0] * xyz[n - 1, 0] + xyz[n - 1, 1] * xyz[n - 1, 1]))
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_one_context_across_both_routes():
+    """The two routes share the alternating pair of edge-list counters: the merge kernel clears the next call's, the
+    arm kernel clears both.  Six calls on one context, a different cloud each: a counter left standing shows as a
+    wrong count, a bin left standing as a range of the previous cloud."""
+    import kompass_hip as kh
+
+    ctx = kh.CloudContext(max_bytes=1 << 16, max_bins=720)
+    ctx.timing_enable()
+    counts = []
+    for call, nb in enumerate((720, 8193, 720, 8193, 8193, 720)):
+        rng = np.random.default_rng(200 + call)
+        xyz = np.vstack([_random_cloud(rng, 3000 + 500 * call, edge_points=150 + 40 * call, bins=720),
+                         _random_cloud(rng, 3000, edge_points=150 + 25 * call, bins=8193)])
+        n, data = len(xyz), cloud_bytes(xyz)
+        want = ko.pointcloud_to_laserscan(data, 16, n * 16, 1, n, 0, 4, 8, 12.0, 0.0, 2.0, num_bins=nb)
+        got = ctx.to_laserscan(data, 16, n * 16, 1, n, 0, 4, 8, 12.0, 0.0, 2.0, num_bins=nb)
+        np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64), err_msg=f"call {call}, {nb} bins")
+        assert ("cloud_merge_kernel" in [name for name, _ in ctx.timings()]) == (nb <= LDS_MAX_BINS)
+        listed = _edge_listed(xyz, 0.0, 2.0, nb)
+        assert ctx.last_rebinned() == listed, (call, nb)
+        counts.append(listed)
+    assert min(counts) > 100 and len(set(counts)) == len(counts)  # no two calls expect the same count
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_range", [0.0, -0.0, 1e-3, 1.5e-3, np.inf, -1.0])
+def test_gpu_global_route_max_range(max_range):
+    """On the global route the value the bins are armed with is the only `distance < ranges[bin]` there is.  Nothing is
+    closer than 0 (or than -0.0, or a negative range), and no point that passes the `range_sq < 1e-6` filter is closer
+    than 1e-3: every bin stays at max_range, sign included.  A few points are closer than 1.5e-3."""
+    import kompass_hip as kh
+
+    rng = np.random.default_rng(77)
+    near = np.float32([[1e-3, 0.0, 0.1], [7.1e-4, 7.1e-4, 0.1], [0.0, -1.0000001e-3, 0.1], [-1.1e-3, 1e-4, 0.1]])
+    n = 4218
+    ctx = kh.CloudContext(max_bytes=16 * n, max_bins=720)
+    for kw in (dict(num_bins=8193), dict(angle_step=5e-4)):
+        xyz = np.vstack([_random_cloud(rng, 4000, edge_points=200, bins=8193, step=kw.get("angle_step")), near])
+        assert len(xyz) == n
+        data = cloud_bytes(xyz)
+        want = ko.pointcloud_to_laserscan(data, 16, n * 16, 1, n, 0, 4, 8, max_range, 0.0, 2.0, **kw)
+        got = ctx.to_laserscan(data, 16, n * 16, 1, n, 0, 4, 8, max_range, 0.0, 2.0, **kw)
+        if "angle_step" in kw:
+            got, want = got[0], want[0]
+        np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))
+        if max_range <= 1e-3:
+            np.testing.assert_array_equal(want.view(np.uint64), np.full(len(want), max_range).view(np.uint64))
+        elif np.isfinite(max_range):
+            assert 0 < (want < max_range).sum() <= len(near)
+        else:
+            assert np.isinf(want).any() and (want < 12.0).sum() > 1000
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,dims", [(0, [0.3, 1.0]), (1, [0.6, 0.4, 1.0]), (2, [0.35])])
+def test_zone_checker_cloud_step_on_the_global_route(shape, dims):
+    """A checker preset with 9000 scan angles: its cloud step has 9000 bins (the global route) and its 160 degree
+    index sets span sixteen workgroups of the check kernel."""
+    import kompass_hip as kh
+
+    rng = np.random.default_rng(17 + shape)
+    angles = np.sort(rng.uniform(0, 2 * np.pi, 9000))
+    yaw = 0.4
+    args = (shape, dims, [0.1, -0.05, 0.3], [0.0, 0.0, np.sin(yaw / 2), np.cos(yaw / 2)], 160.0, 0.2, 0.9,
+            angles, 0.05, 1.5, 8.0)
+    z, o = kh.ZoneContext(*args), ko.CriticalZone(*args)
+    for fwd in (True, False):
+        assert len(o.indices(fwd)) > 256 and len(o.indices(fwd)) % 256 != 0
+        np.testing.assert_array_equal(z.indices(fwd), o.indices(fwd))
+    seen = set()
+    for trial in range(10):
+        m = 3000
+        d = [0.3, 0.8, 1.2, 3.0][trial % 4]
+        pts = np.column_stack([rng.uniform(-1, 1, m) * (d + 2), rng.uniform(-1, 1, m) * (d + 2), rng.uniform(-0.5, 2.0, m)])
+        pts = pts[np.hypot(pts[:, 0], pts[:, 1]) > d]
+        rec = np.zeros((len(pts), 4), np.float32)
+        rec[:, :3] = pts
+        c, k = rec.reshape(-1).view(np.int8), len(pts)
+        for fwd in (True, False):
+            want = o.check_cloud(c, 16, k * 16, 1, k, 0, 4, 8, fwd)
+            got = z.check_cloud(c, 16, k * 16, 1, k, 0, 4, 8, fwd)
+            assert np.float32(got).view(np.uint32) == np.float32(want).view(np.uint32)
+            seen.add("stop" if want == 0 else "clear" if want == 1 else "slow")
+    assert seen == {"stop", "clear", "slow"}
+    z.close()

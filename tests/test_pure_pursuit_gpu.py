@@ -124,6 +124,181 @@ def test_one_launch_refusals_match_the_pose_path():
     ctx.close()
 
 
+# ---------------------------------------------------------------- lane layouts of pp_search_kernel
+# A candidate owns G lanes, G the power of two >= H + 1 capped at 64; poses past 64 go through chunks of 64 with the
+# pose carried across by the segment's last lane.  The horizons: G = 4, 8, 16, 32, 64 with the segment exactly full
+# (H + 1 == G) and one short of / one past it; one full chunk (63), a second chunk of one lane (64) and of two (65);
+# two full chunks and a third of one and two lanes (127, 128, 129); four chunks (200).
+HORIZONS = (2, 3, 4, 7, 8, 15, 16, 31, 32, 63, 64, 65, 127, 128, 129, 200)
+START = (0.3, -0.2, 0.4)
+
+
+def _target_poses(H):
+    t = {1, H}
+    if H > 64:
+        t |= {64, 65}
+    if H > 128:
+        t |= {128, 129}
+    return sorted(t)
+
+
+def _which_pose_scene(H):
+    """(targets, candidates, cloud): one candidate per target pose index j, driving 0.8 m a step along its own arc
+    (its own heading in the body frame -- vy != 0 -- and its own omega != 0), and a small cluster of points exactly
+    where its pose j is: the steps are longer than robot plus cluster, so pose j is the candidate's only pose that
+    touches anything.  The candidate after them backs away slowly from all of it."""
+    targets = _target_poses(H)
+    cands, pts = [], []
+    for k, j in enumerate(targets):
+        phi = 1.9 if j == 1 else -1.0 + 2.0 * k / len(targets)
+        om = (0.08 + 0.02 * k) * (1 if k % 2 else -1)
+        c = (8.0 * math.cos(phi), 8.0 * math.sin(phi), om)
+        x, y, _ = ref.poses(START, [c], H, DT)
+        pts += [(x[j - 1] + dx, y[j - 1] + dy, 0.0) for dx, dy in ((0, 0), (0.03, 0), (-0.03, 0), (0, 0.03), (0, -0.03))]
+        cands.append(c)
+    cands.append((-0.5, -0.3, 0.1))
+    return targets, cands, np.asarray(pts, np.float32)
+
+
+def _hit_poses(coll, cand, H):
+    x, y, t = ref.poses(START, [cand], H, DT)
+    return [j + 1 for j in range(H) if coll.check_at(x[j], y[j], t[j])]
+
+
+@pytest.mark.parametrize("shape,dims", SHAPES)
+def test_first_clear_command_horizons_and_which_pose_hits(shape, dims):
+    ctx = kh.DwaContext(shape, dims, octree_res=0.1, max_samples=4, max_points=4)
+    coll = ko.Collision(shape, dims, res=0.1)
+    coll.update_state(*START)
+    for H in HORIZONS:
+        targets, cands, cloud = _which_pose_scene(H)
+        ctx.set_points(START + (0.0,), cloud)
+        coll.update_points(cloud, True)
+        # on the reference alone: candidate k is hit by its pose targets[k] and by no other, the last by none
+        hit = [_hit_poses(coll, c, H) for c in cands]
+        assert hit == [[j] for j in targets] + [[]], (H, hit)
+        first_hits = {h[0] for h in hit if h}
+        assert first_hits >= {1, H} | ({64, 65} if H > 64 else set()) | ({128, 129} if H > 128 else set())
+        vx, vy, om = (np.array(v) for v in zip(*cands))
+        assert _check(ctx, coll, START, vx, vy, om, H) == len(cands) - 1
+        # ... and without the clear candidate: none
+        assert _check(ctx, coll, START, vx[:-1], vy[:-1], om[:-1], H) == -1
+        # each of them alone (a hit that only a neighbour segment of the wavefront saw would pass above)
+        for k in range(len(cands) - 1):
+            assert ctx.first_clear_command(START, vx[k:k + 1], vy[k:k + 1], om[k:k + 1], H, DT) == -1, (H, targets[k])
+    ctx.close()
+
+
+@pytest.mark.parametrize("shape,dims", [SHAPES[0], SHAPES[1]])
+def test_first_clear_command_horizons_on_the_tilted_mount(shape, dims):
+    rng = np.random.default_rng(5)
+    ang = np.linspace(0, 2 * math.pi, 720, endpoint=False)
+    ranges = 1.0 + 0.6 * rng.random(720)
+    start = (0.1, 0.2, -0.3)
+    srot = (0.0, math.sin(0.2), 0.0, math.cos(0.2))
+    ctx = kh.DwaContext(shape, dims, (0.05, 0.0, 0.1), srot, 0.05, max_samples=4, max_points=4)
+    coll = ko.Collision(shape, dims, (0.05, 0.0, 0.1), srot, 0.05)
+    ctx.set_scan(start + (0.0,), ranges, ang, 10.0)
+    coll.update_state(*start)
+    coll.update_scan(ranges, ang)
+    # Pitched by 0.4 rad, the beams ahead of and behind the sensor leave the robot's height; the ones to its sides stay
+    # level.  So the candidates drive sideways, the fast ones first: they reach the ring 1 to 1.6 m away within the
+    # horizon -- the fastest some steps before its end, the next ones nearer to it -- and the slow ones do not.
+    n = 24
+    answers = set()
+    for H in HORIZONS:
+        speed = np.linspace(1.9, 0.4, n) * (1.3 / (DT * H))
+        vy = speed * np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+        vx = rng.uniform(-0.1, 0.1, n) * speed
+        om = rng.uniform(-0.5, 0.5, n) / (DT * H)
+        want = ref.first_clear(coll, start, list(zip(vx, vy, om)), H, DT)
+        assert want > 0, (H, want)  # on the reference: some candidates collide, one further down is clear
+        answers.add(want)
+        assert _check(ctx, coll, start, vx, vy, om, H) == want
+        assert _check(ctx, coll, start, vx[:want], vy[:want], om[:want], H) == -1
+    assert len(answers) > 1
+    ctx.close()
+
+
+def _wall_scene(rng, n, clear_at):
+    """n candidates that drive into a wall 0.55 m in front of the robot within their first three poses, but for the
+    one at `clear_at`, which backs away."""
+    th = START[2] + np.arange(-1.2, 1.2, 0.02)
+    wall = np.stack([START[0] + 0.55 * np.cos(th), START[1] + 0.55 * np.sin(th), np.zeros(len(th))], 1).astype(np.float32)
+    vx, vy, om = rng.uniform(1.5, 2.2, n), rng.uniform(-0.1, 0.1, n), rng.uniform(-0.3, 0.3, n)
+    if clear_at is not None:
+        vx[clear_at], vy[clear_at], om[clear_at] = -0.5, 0.02, 0.1
+    return wall, vx, vy, om
+
+
+# 4 wavefronts a workgroup, 64 / G candidates a wavefront, at most 4096 workgroups: 16384 candidates at G = 64 (H = 63)
+# and 32768 at G = 32 (H = 31) before the grid-stride loop runs a second round
+@pytest.mark.parametrize("H,n,clear_at", [(63, 3, 2), (63, 4, 3), (63, 5, 4), (63, 16401, 16400), (63, 16401, 7),
+                                          (31, 1, 0), (31, 2, 1), (31, 3, 2), (31, 32771, 32770), (31, 32771, None)])
+def test_first_clear_command_candidate_counts(H, n, clear_at):
+    shape, dims = SHAPES[1]
+    rng = np.random.default_rng(n + H)
+    wall, vx, vy, om = _wall_scene(rng, n, clear_at)
+    ctx = kh.DwaContext(shape, dims, octree_res=0.1, max_samples=4, max_points=4)
+    coll = ko.Collision(shape, dims, res=0.1)
+    ctx.set_points(START + (0.0,), wall)
+    coll.update_state(*START)
+    coll.update_points(wall, True)
+    # on the reference: everyone but the clear one is stopped within three poses, the clear one by nothing
+    for i in range(n):
+        if i == clear_at:
+            assert _hit_poses(coll, (vx[i], vy[i], om[i]), H) == []
+        else:
+            x, y, t = ref.poses(START, [(vx[i], vy[i], om[i])], 3, DT)
+            assert any(coll.check_at(x[j], y[j], t[j]) for j in range(3)), i
+    assert _check(ctx, coll, START, vx, vy, om, H) == (-1 if clear_at is None else clear_at)
+    ctx.close()
+
+
+def _gap_ring(rng, start):
+    """the ring of test_first_clear_command_kernel_level around a start with any yaw: the gap lies behind the robot"""
+    back = math.atan2(-math.sin(start[2]), -math.cos(start[2]))  # (the host libm's reduction of the yaw)
+    ang = rng.uniform(0, 2 * math.pi, 1500)
+    keep = np.abs(((ang - back) + math.pi) % (2 * math.pi) - math.pi) > 0.5
+    r = rng.uniform(1.1, 1.5, keep.sum())
+    return np.stack([start[0] + r * np.cos(ang[keep]), start[1] + r * np.sin(ang[keep]),
+                     rng.uniform(-0.1, 0.1, keep.sum())], 1).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape,dims", SHAPES)
+def test_first_clear_command_yaws_beyond_the_device_trig(shape, dims):
+    """|yaw| + omega_max * dt * H >= 1e8: the kernel reads cos / sin from a table the host's libm filled, one row a
+    candidate.  The reference's Path::State::update uses that libm too."""
+    rng = np.random.default_rng(23)
+    ctx = kh.DwaContext(shape, dims, octree_res=0.1, max_samples=4, max_points=4)
+    coll = ko.Collision(shape, dims, res=0.1)
+    vx, vy, om = _cands(rng, 41)
+    seen = []
+    for yaw in (1.5e8, -2.0e8):
+        start = (0.3, -0.2, yaw)
+        cloud = _gap_ring(rng, start)
+        ctx.set_points(start + (0.0,), cloud)
+        coll.update_state(*start)
+        coll.update_points(cloud, True)
+        for H in (10, 100):
+            k = 3.0 if H == 10 else 1.0  # (fast enough to reach the ring in ten steps)
+            seen.append(_check(ctx, coll, start, vx * k, vy * k, om, H))
+    # a small start yaw, one candidate whose omega alone takes the yaw past 1e8: first in the list, and last
+    start = (0.3, -0.2, 0.4)
+    cloud = _gap_ring(rng, start)
+    ctx.set_points(start + (0.0,), cloud)
+    coll.update_state(*start)
+    coll.update_points(cloud, True)
+    for H in (10, 100):
+        assert 1.2e8 * float(np.float32(DT)) * H >= 1e8 and abs(om).max() < 10.0
+        wild = (np.array([0.9]), np.array([0.0]), np.array([1.2e8]))
+        seen.append(_check(ctx, coll, start, *(np.concatenate([a, w]) for a, w in zip((vx, vy, om), wild)), H))
+        seen.append(_check(ctx, coll, start, *(np.concatenate([w, a]) for a, w in zip((vx, vy, om), wild)), H))
+        seen.append(_check(ctx, coll, start, vx, vy, om, H))  # (the same list on the device's own trig)
+    assert any(i > 0 for i in seen), seen  # some answers lie behind candidates that collide
+    ctx.close()
+
+
 # ---------------------------------------------------------------- class level
 TYPES = {"Ackermann": ref.ACKERMANN, "DiffDrive": ref.DIFFERENTIAL_DRIVE, "Omni": ref.OMNI}
 CPP_TYPES = {ref.ACKERMANN: kompass_cpp.control.ControlType.ACKERMANN,
