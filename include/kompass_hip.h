@@ -860,6 +860,26 @@ int kc_planner_get_field(kc_planner *ctx, uint32_t *field_out, uint8_t *valid_ou
  * cells_ij_out: (i, j) pairs, start first; NULL asks for the count only.
  * Zero points when the last solve found no path. */
 int kc_planner_get_path(kc_planner *ctx, int32_t *cells_ij_out, size_t cap_points, size_t *count_out);
+/* The clearance cost (rules 6 to 8), off by default.
+ *  - clear2[cell] = the smallest (bi - i)^2 + (bj - j)^2 over blocking cells when
+ *    that is <= c2, KC_PLANNER_CLEAR_FAR otherwise; pen[cell] =
+ *    pen_by_d2[clear2[cell]], 0 for CLEAR_FAR cells.
+ *  - a step pays for the cell it leaves: field[goal] = 0, field[a] = pen[a] + min
+ *    over the allowed steps a -> b of (step + field[b]).  kc_planner_solve answers
+ *    KC_ERR_RANGE when (14 + max(pen_by_d2)) * cells > 0xFFFFFFFE.
+ *  - the walk takes the neighbour with the smallest field + step (the same tie
+ *    order), so the steps and the penalties of the cells left sum to *cost_out.
+ * Validity, status and passes keep their meaning; with the cost off every output
+ * is what it is without these three calls. */
+#define KC_PLANNER_CLEAR_FAR 0xFFFFu
+/* n == c2 + 1 entries; c2 == 0 or a NULL table switches the clearance cost off.
+   KC_ERR_RANGE for c2 > 254^2, KC_ERR_INVALID for n != c2 + 1.  Forgets the last solve. */
+int kc_planner_set_clearance_cost(kc_planner *ctx, uint32_t c2, const uint32_t *pen_by_d2, size_t n);
+/* the last solve's clear2 and per-cell penalty, laid out as the grid; either may be NULL;
+   KC_ERR_STATE before a solve or with the clearance cost off */
+int kc_planner_get_clearance(kc_planner *ctx, uint16_t *clear2_out, uint32_t *penalty_out, size_t cap);
+/* smallest clear2 along the last path (KC_PLANNER_CLEAR_FAR: nothing within reach); KC_ERR_STATE without a path */
+int kc_planner_path_clearance(kc_planner *ctx, uint32_t *min_clear2_out);
 
 #ifdef __cplusplus
 }

@@ -1017,6 +1017,23 @@ PYBIND11_MODULE(kompass_cpp, m) {
              p.getField(f.mutable_data(), v.mutable_data(), static_cast<size_t>(w) * static_cast<size_t>(h));
              return py::make_tuple(f, v);
            }, "(cost field uint32, validity uint8) of the last solve, [i, j] as the grid")
+      .def("set_clearance_cost", &Planning::GridPlanner::setClearanceCost, py::arg("reach"), py::arg("weight"),
+           "Surcharge cells within `reach` metres beyond the footprint: `weight` straight-cell lengths at its edge, "
+           "falling to 0 at the reach; reach <= 0 or weight <= 0 switches it off")
+      .def_static("clearance_table", &Planning::GridPlanner::clearanceTable, py::arg("weight10"), py::arg("r2"), py::arg("c2"),
+                  "pen_by_d2[0 .. c2] of set_clearance_cost's rule, in integers")
+      .def("get_clearance", [](Planning::GridPlanner &p) {
+             const py::ssize_t w = p.width(), h = p.height();
+             py::array_t<uint16_t, py::array::f_style> c({w, h});
+             py::array_t<uint32_t, py::array::f_style> pen({w, h});
+             p.getClearance(c.mutable_data(), pen.mutable_data(), static_cast<size_t>(w) * static_cast<size_t>(h));
+             return py::make_tuple(c, pen);
+           }, "(clear2 uint16, penalty uint32) of the last solve, [i, j] as the grid; raises with the clearance cost off")
+      .def("get_path_min_clearance", &Planning::GridPlanner::getPathMinClearance,
+           "metres from the path's cells to the nearest blocking cell; inf when none is within reach")
+      .def("get_path_length", &Planning::GridPlanner::getPathLength, "the steps of the path alone, in metres")
+      .def("get_clearance_c2", &Planning::GridPlanner::clearanceC2)
+      .def("get_clearance_weight10", &Planning::GridPlanner::clearanceWeight10)
       .def("get_status", &Planning::GridPlanner::status)
       .def("get_passes", &Planning::GridPlanner::passes)
       .def("get_footprint_r2", &Planning::GridPlanner::footprintR2)

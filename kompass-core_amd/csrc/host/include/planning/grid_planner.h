@@ -4,7 +4,9 @@
 // The reference's planning submodule is an OMPL wrapper (planning/ompl.h:18-89) and stays out of scope; this
 // class keeps the method names of that surface where the meaning is the same (setSpaceBoundsFromMap,
 // setupProblem, solve, getPath, getCost) and is not a restatement of it: an exact 8-connected shortest path on
-// the grid, the robot a disc of its circumscribed horizontal radius (yaw-free, conservative).
+// the grid, the robot a disc of its circumscribed horizontal radius (yaw-free, conservative).  setClearanceCost
+// adds a surcharge per cell that falls with the distance to the nearest blocking cell (rules 6 to 8): the path
+// then trades length for clearance, as deterministically as before.
 #pragma once
 
 #include <cstdint>
@@ -49,7 +51,27 @@ class GridPlanner {
   std::optional<Path::Path> getPath(bool simplify = false);
   // the cells of that path, (i, j) pairs
   std::vector<int32_t> getPathCells(bool simplify = false);
+  // field[start] * resolution / 10: the steps, and with a clearance cost the penalties of the cells left
   float getCost() const;
+  // the steps of the path alone, summed from its cells: metres along the 8-connected path
+  float getPathLength();
+
+  // The clearance cost.  reach: metres beyond the footprint radius plus margin over which a cell is surcharged, C2
+  // = radiusToR2(radius + margin + reach, resolution), evaluated with the bounds and again when they change.
+  // weight: the surcharge at the footprint's edge in straight-cell lengths, Wt = lround(weight * 10); the table is
+  // clearanceTable(Wt, R2, C2).  reach <= 0 or weight <= 0 switches it off.  std::out_of_range where the reach is
+  // wider than 254 cells.
+  void setClearanceCost(float reach, float weight);
+  bool clearanceCostOn() const { return clear_on_; }
+  uint32_t clearanceC2() const;
+  uint32_t clearanceWeight10() const { return clear_on_ ? weight10_ : 0u; }
+  // pen_by_d2[0 .. c2]: 0 for d2 <= r2, else weight10 * (c2 - d2) / (c2 - r2) in integers (64-bit product); all
+  // zero when c2 <= r2
+  static std::vector<uint32_t> clearanceTable(uint32_t weight10, uint32_t r2, uint32_t c2);
+  // the last solve's clear2 and penalty per cell, width x height as the grid (cap: cells either output holds)
+  void getClearance(uint16_t *clear2_out, uint32_t *pen_out, size_t cap);
+  // sqrt(smallest clear2 along the path) * resolution; +inf when no blocking cell is within reach of it
+  float getPathMinClearance() const;
   // the last solve's cost field and validity map, width x height as the grid (cap: cells either output holds)
   void getField(uint32_t *field_out, uint8_t *valid_out, size_t cap);
   int width() const { return width_; }
@@ -81,6 +103,12 @@ class GridPlanner {
   int start_[2] = {-1, -1}, goal_[2] = {-1, -1};
   int status_ = -1, passes_ = 0;
   uint32_t cost_ = 0xFFFFFFFFu;
+  bool clear_on_ = false;
+  double reach_ = 0.0;
+  uint32_t weight10_ = 0;
+  bool clear_applied_ = false;  // the context holds the table of (applied_r2_, applied_c2_, applied_w10_)
+  uint32_t applied_r2_ = 0, applied_c2_ = 0, applied_w10_ = 0;
+  void applyClearanceCost();
   void needBounds() const;
   void forgetSolve();
 };

@@ -52,6 +52,73 @@ void GridPlanner::setSpaceBoundsFromMap(float origin_x, float origin_y, int widt
   height_ = height;
   res_ = resolution;
   have_bounds_ = true;
+  applyClearanceCost();  // R2 and C2 are cells of this resolution
+}
+
+void GridPlanner::setClearanceCost(float reach, float weight) {
+  const bool on = reach > 0.0f && weight > 0.0f;
+  if (on && (!std::isfinite(reach) || !std::isfinite(weight))) throw std::invalid_argument("reach and weight must be finite");
+  uint32_t w10 = 0;
+  if (on) {
+    const double w = static_cast<double>(weight) * 10.0;
+    if (!(w < 4294967295.0)) throw std::out_of_range("the clearance weight does not fit 32 bits");
+    w10 = static_cast<uint32_t>(std::lround(w));
+  }
+  const bool was_on = clear_on_;
+  const double old_reach = reach_;
+  const uint32_t old_w10 = weight10_;
+  clear_on_ = on && w10 > 0;
+  reach_ = clear_on_ ? static_cast<double>(reach) : 0.0;
+  weight10_ = clear_on_ ? w10 : 0u;
+  if (!have_bounds_) return;
+  try {
+    applyClearanceCost();
+  } catch (...) {  // a refused cost leaves the one before
+    clear_on_ = was_on;
+    reach_ = old_reach;
+    weight10_ = old_w10;
+    throw;
+  }
+}
+
+uint32_t GridPlanner::clearanceC2() const {
+  needBounds();
+  return clear_on_ ? radiusToR2(radius_ + reach_, res_) : 0u;
+}
+
+// hands the table to the context when it is not the one the context holds: a call forgets the last solve and the
+// validity map, so an unchanged table (the bounds of the same map again) is left alone
+void GridPlanner::applyClearanceCost() {
+  if (!clear_on_) {
+    if (clear_applied_) {
+      hip::check(kc_planner_set_clearance_cost(ctx_.get(), 0, nullptr, 0));
+      clear_applied_ = false;
+      forgetSolve();
+    }
+    return;
+  }
+  const uint32_t r2 = footprintR2(), c2 = clearanceC2();
+  if (c2 > static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+    throw std::out_of_range("the clearance reach is wider than " + std::to_string(KC_PLANNER_MAX_RADIUS_CELLS) + " cells");
+  if (clear_applied_ && applied_r2_ == r2 && applied_c2_ == c2 && applied_w10_ == weight10_) return;
+  const std::vector<uint32_t> table = clearanceTable(weight10_, r2, c2);
+  clear_applied_ = false;
+  hip::check(kc_planner_set_clearance_cost(ctx_.get(), c2, c2 ? table.data() : nullptr, c2 ? table.size() : 0));
+  clear_applied_ = c2 > 0;  // a reach of less than a cell at radius 0: no cell is surcharged, the cost stays off
+  applied_r2_ = r2;
+  applied_c2_ = c2;
+  applied_w10_ = weight10_;
+  forgetSolve();
+}
+
+std::vector<uint32_t> GridPlanner::clearanceTable(uint32_t weight10, uint32_t r2, uint32_t c2) {
+  if (c2 > static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+    throw std::out_of_range("a clearance reach of C2 = " + std::to_string(c2) + " is wider than " +
+                            std::to_string(KC_PLANNER_MAX_RADIUS_CELLS) + " cells");
+  std::vector<uint32_t> t(static_cast<size_t>(c2) + 1, 0u);
+  for (uint64_t d2 = static_cast<uint64_t>(r2) + 1; d2 <= c2; ++d2)
+    t[d2] = static_cast<uint32_t>(static_cast<uint64_t>(weight10) * (c2 - d2) / (c2 - r2));
+  return t;
 }
 
 void GridPlanner::needBounds() const {
@@ -185,6 +252,27 @@ void GridPlanner::getField(uint32_t *field_out, uint8_t *valid_out, size_t cap) 
 float GridPlanner::getCost() const {
   if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
   return static_cast<float>(cost_) * res_ / 10.0f;
+}
+
+float GridPlanner::getPathLength() {
+  if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
+  const std::vector<int32_t> ij = getPathCells(false);
+  uint64_t steps = 0;
+  for (size_t k = 2; k + 1 < ij.size(); k += 2) steps += (ij[k] != ij[k - 2] && ij[k + 1] != ij[k - 1]) ? 14u : 10u;
+  return static_cast<float>(steps) * res_ / 10.0f;
+}
+
+void GridPlanner::getClearance(uint16_t *clear2_out, uint32_t *pen_out, size_t cap) {
+  if (status_ < 0) throw std::runtime_error("GridPlanner: no solve since the last grid or problem");
+  hip::check(kc_planner_get_clearance(ctx_.get(), clear2_out, pen_out, cap));
+}
+
+float GridPlanner::getPathMinClearance() const {
+  if (status_ != KC_PLAN_FOUND) throw std::runtime_error("GridPlanner: no path");
+  uint32_t c2 = KC_PLANNER_CLEAR_FAR;
+  hip::check(kc_planner_path_clearance(ctx_.get(), &c2));
+  if (c2 == KC_PLANNER_CLEAR_FAR) return std::numeric_limits<float>::infinity();
+  return std::sqrt(static_cast<float>(c2)) * res_;
 }
 
 }  // namespace Planning

@@ -19,6 +19,11 @@
 //      pass changed nothing, i.e. both buffers hold the fixed point.
 //  (c) path.  planner_walk_kernel: one wavefront walks from the start, eight lanes load the eight neighbours of
 //      the current cell, a shuffle reduction takes the smallest (value, order) pair.
+//  (d) clearance cost (rules 6 to 8; off unless kc_planner_set_clearance_cost gave a table).  The row pass reaches
+//      max(R, Rc) cells; planner_clear_kernel takes min(rowdist^2 + dy^2) over the rows in reach and writes clear2,
+//      the table's penalty and the validity map in one go.  planner_relax_kernel<true> adds the penalty of the cell
+//      a step leaves, one register per owned cell; planner_walk_kernel<true> follows field + step and keeps the
+//      smallest clear2 it visits.  The <false> instantiations are the code of the planner without the cost.
 //
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
@@ -96,6 +101,28 @@ __global__ __launch_bounds__(kPlanBlock) void planner_valid_kernel(const uint8_t
   }
 }
 
+// rule 6 and the table of rule 7 in one column pass: rowd holds the row distances within Rm = max(R, Rc) cells
+__global__ __launch_bounds__(kPlanBlock) void planner_clear_kernel(const uint8_t *rowd, const uint32_t *pen_by_d2, uint16_t *clear2,
+                                                                   uint32_t *pen, uint8_t *valid, int W, int H, int Rm,
+                                                                   uint32_t R2, uint32_t C2) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const int y = static_cast<int>(i / W);
+    const int lo = max(-Rm, -y), hi = min(Rm, H - 1 - y);
+    uint32_t best = kPlanInf;  // the nearest blocking cell within Rm columns and Rm rows
+    for (int dy = lo; dy <= hi; ++dy) {
+      const uint32_t d = rowd[i + static_cast<long long>(dy) * W];
+      if (d != 255u) best = min(best, d * d + static_cast<uint32_t>(dy * dy));
+    }
+    // Rm covers both discs: a blocking cell within R2 or C2 is within Rm of the cell in both directions
+    const bool near = best <= C2;
+    clear2[i] = near ? static_cast<uint16_t>(best) : static_cast<uint16_t>(KC_PLANNER_CLEAR_FAR);
+    pen[i] = near ? pen_by_d2[best] : 0u;
+    valid[i] = best <= R2 ? 0 : 1;
+  }
+}
+
 __global__ __launch_bounds__(kPlanBlock) void planner_init_kernel(uint32_t *a, uint32_t *b, const uint8_t *valid, long long n,
                                                                   long long goal) {
   const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
@@ -106,10 +133,14 @@ __global__ __launch_bounds__(kPlanBlock) void planner_init_kernel(uint32_t *a, u
   }
 }
 
-// one pass over one tile: `in` is only read, `out` only written (the tile's own cells)
+// one pass over one tile: `in` is only read, `out` only written (the tile's own cells).  PEN: a step pays the
+// penalty of the cell it leaves (rule 7), which is the cell that is relaxed: one more register per owned cell, the
+// same LDS traffic.
+template <bool PEN>
 __global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                                     const uint8_t *__restrict__ valid, int W, int H,
-                                                                     unsigned tiles_x, uint32_t *changed_word, uint32_t pass) {
+                                                                     const uint8_t *__restrict__ valid, const uint32_t *__restrict__ pen,
+                                                                     int W, int H, unsigned tiles_x, uint32_t *changed_word,
+                                                                     uint32_t pass) {
   __shared__ uint32_t f[kPlanHalo * kPlanHalo];
   __shared__ uint8_t v[kPlanHalo * kPlanHalo];
   // the tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more tile rows than gridDim.y holds
@@ -128,10 +159,15 @@ __global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint3
   const int off[8] = {1, kPlanHalo, -1, -kPlanHalo, kPlanHalo + 1, kPlanHalo - 1, -kPlanHalo - 1, -kPlanHalo + 1};
   int idx[kPlanRows];
   uint32_t cur[kPlanRows], orig[kPlanRows], mask[kPlanRows];
+  uint32_t leave[PEN ? kPlanRows : 1];
 #pragma unroll
   for (int r = 0; r < kPlanRows; ++r) {
     const int k = (1 + ty + r * (kPlanThreads / kPlanTile)) * kPlanHalo + 1 + tx;
     idx[r] = k;
+    if constexpr (PEN) {
+      const int gx = x0 + 1 + tx, gy = y0 + 1 + ty + r * (kPlanThreads / kPlanTile);
+      leave[r] = (gx < W && gy < H) ? pen[static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)] : 0u;
+    }
     cur[r] = orig[r] = f[k];
     uint32_t m = 0;
     if (v[k]) {
@@ -152,7 +188,8 @@ __global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint3
       for (int q = 0; q < 8; ++q) {
         if (mask[r] & (1u << q)) {
           const uint32_t fn = f[idx[r] + off[q]];
-          const uint32_t c = fn + (q < 4 ? 10u : 14u);  // no wrap: 14 * cells < 2^32 (the cell cap)
+          uint32_t c = fn + (q < 4 ? 10u : 14u);  // no wrap: 14 * cells < 2^32 (the cell cap)
+          if constexpr (PEN) c += leave[r];       // nor here: (14 + max penalty) * cells < 2^32 (kc_planner_solve)
           if (fn != kPlanInf && c < best) best = c;
         }
       }
@@ -176,12 +213,16 @@ __global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint3
   if (__syncthreads_or(changed) && threadIdx.x == 0) *changed_word = pass;
 }
 
-// status words of the walk: out[0] = cells written, out[1] = 0 done / 1 capacity / 2 no descending neighbour
-__global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field, const uint8_t *valid, int W, int H, int sx,
-                                                          int sy, int32_t *cells, uint32_t cap, uint32_t *out) {
+// status words of the walk: out[0] = cells written, out[1] = 0 done / 1 capacity / 2 no descending neighbour.
+// PEN (rule 8): the key is field + step, its minimum must be field - penalty of the cell left, and out[2] = the
+// smallest clear2 among the cells visited.
+template <bool PEN>
+__global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field, const uint8_t *valid, const uint32_t *pen,
+                                                          const uint16_t *clear2, int W, int H, int sx, int sy, int32_t *cells,
+                                                          uint32_t cap, uint32_t *out) {
   const int lane = threadIdx.x;
   int cx = sx, cy = sy;
-  uint32_t n = 0, status = 0;
+  uint32_t n = 0, status = 0, min_clear = KC_PLANNER_CLEAR_FAR;
   for (;;) {
     const size_t c = static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(cx);
     if (n >= cap) {
@@ -191,6 +232,7 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
     if (lane == 0) cells[n] = static_cast<int32_t>(c);
     ++n;
     const uint32_t fc = field[c];
+    if constexpr (PEN) min_clear = min(min_clear, static_cast<uint32_t>(clear2[c]));
     if (fc == 0u) break;
     unsigned long long key = ~0ull;
     if (lane < 8) {
@@ -202,7 +244,9 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
         if (ok && lane >= 4)
           ok = valid[static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(nx)] != 0 &&
                valid[static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(cx)] != 0;
-        if (ok) key = (static_cast<unsigned long long>(field[g]) << 3) | static_cast<unsigned long long>(lane);
+        // 64 bits hold an unreached neighbour's 0xFFFFFFFF + 14 as well
+        const unsigned long long step = PEN ? (lane < 4 ? 10ull : 14ull) : 0ull;
+        if (ok) key = ((static_cast<unsigned long long>(field[g]) + step) << 3) | static_cast<unsigned long long>(lane);
       }
     }
 #pragma unroll
@@ -211,8 +255,12 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
       key = o < key ? o : key;
     }
     key = __shfl(key, 0, 64);
-    const uint32_t best = static_cast<uint32_t>(key >> 3);
-    if (key == ~0ull || best >= fc) {  // not on a converged field with a reachable start
+    bool off_field;  // not on a converged field with a reachable start
+    if constexpr (PEN)
+      off_field = key == ~0ull || (key >> 3) + static_cast<unsigned long long>(pen[c]) != static_cast<unsigned long long>(fc);
+    else
+      off_field = key == ~0ull || static_cast<uint32_t>(key >> 3) >= fc;
+    if (off_field) {
       status = 2;
       break;
     }
@@ -223,6 +271,7 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
   if (lane == 0) {
     out[0] = n;
     out[1] = status;
+    if constexpr (PEN) out[2] = min_clear;
   }
 }
 
@@ -235,7 +284,8 @@ struct kc_planner {
   hipStream_t stream = nullptr;
   int W = 0, H = 0;
   bool have_grid = false;
-  bool have_valid = false;   // d_valid holds the validity of (grid, valid_r2, valid_unknown)
+  bool have_valid = false;   // d_valid holds the validity of (grid, valid_r2, valid_unknown), and with the clearance
+                             // cost on d_clear2 / d_pen hold the clearance and penalty of (grid, clear_c2, table)
   uint32_t valid_r2 = 0;
   int valid_unknown = 0;
   bool solved = false;
@@ -248,8 +298,13 @@ struct kc_planner {
   DevBuf<uint8_t> d_stage;   // a host grid on its way to the classifier
   DevBuf<uint8_t> d_cls, d_rowd, d_valid;
   DevBuf<uint32_t> d_field[2];
-  DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status
-  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal]
+  uint32_t clear_c2 = 0;     // the clearance cost (rules 6 to 8): on while clear_c2 > 0
+  uint32_t clear_max_pen = 0;
+  uint32_t path_clear2 = KC_PLANNER_CLEAR_FAR;
+  DevBuf<uint32_t> d_pen_by_d2, d_pen;
+  DevBuf<uint16_t> d_clear2;
+  DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status, [3] its smallest clear2
+  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal], [6] d_word[3]
   DevBuf<int32_t> d_path;
   PinBuf<int32_t> h_path;
 };
@@ -313,6 +368,38 @@ int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width,
   return KC_OK;
 }
 
+// the walk of the last solve (status KC_PLAN_FOUND), once: c->path, and c->path_clear2 with the clearance cost on
+int planner_walk(kc_planner *c) {
+  if (c->have_path) return KC_OK;
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const bool pen_on = c->clear_c2 > 0;
+  // every step lowers the field by 10 at least
+  const size_t cap = static_cast<size_t>(c->cost / 10u) + 2;
+  KC_TRY(c->d_path.reserve(cap));
+  KC_TRY(c->h_path.reserve(cap));
+  if (pen_on)
+    hipLaunchKernelGGL(planner_walk_kernel<true>, dim3(1), dim3(64), 0, s, c->d_field[c->final_buf].p, c->d_valid.p, c->d_pen.p,
+                       c->d_clear2.p, c->W, c->H, c->start[0], c->start[1], c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
+  else
+    hipLaunchKernelGGL(planner_walk_kernel<false>, dim3(1), dim3(64), 0, s, c->d_field[c->final_buf].p, c->d_valid.p,
+                       static_cast<const uint32_t *>(nullptr), static_cast<const uint16_t *>(nullptr), c->W, c->H, c->start[0],
+                       c->start[1], c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipMemcpyAsync(&c->h_word.p[1], c->d_word.p + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (pen_on) KC_HIP(hipMemcpyAsync(&c->h_word.p[6], c->d_word.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  const uint32_t count = c->h_word.p[1], wst = c->h_word.p[2];
+  if (wst != 0u || count == 0u || count > cap)
+    KC_FAIL(KC_ERR_STATE, "the path walk stopped after %u cells with status %u", count, wst);
+  KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  c->path.assign(c->h_path.p, c->h_path.p + count);
+  c->path_clear2 = pen_on ? c->h_word.p[6] : static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
+  c->have_path = true;
+  return KC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -351,6 +438,9 @@ void kc_planner_destroy(kc_planner *c) {
   c->d_cls.release();
   c->d_rowd.release();
   c->d_valid.release();
+  c->d_pen_by_d2.release();
+  c->d_pen.release();
+  c->d_clear2.release();
   c->d_field[0].release();
   c->d_field[1].release();
   c->d_word.release();
@@ -399,10 +489,14 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   while (static_cast<unsigned long long>(R + 1) * static_cast<unsigned long long>(R + 1) <= r2 && R <= KC_PLANNER_MAX_RADIUS_CELLS) ++R;
   if (R > KC_PLANNER_MAX_RADIUS_CELLS)
     KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  const bool pen_on = c->clear_c2 > 0;
+  const long long n = static_cast<long long>(c->W) * c->H;
+  // field <= (14 + max penalty) * cells: the sums of the relaxation stay below the 0xFFFFFFFF of "no walk"
+  if (pen_on && (14ull + c->clear_max_pen) * static_cast<unsigned long long>(n) > 0xFFFFFFFEull)
+    KC_FAIL(KC_ERR_RANGE, "a clearance penalty of %u over %lld cells does not fit the 32-bit cost field", c->clear_max_pen, n);
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int W = c->W, H = c->H;
-  const long long n = static_cast<long long>(W) * H;
   c->solved = c->have_path = false;
   c->status = -1;
   c->cost = kPlanInf;
@@ -414,8 +508,18 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
     c->have_valid = false;
     KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
     KC_TRY(c->d_valid.reserve(static_cast<size_t>(n)));
-    hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
-    hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_valid.p, W, H, R, r2);
+    if (pen_on) {
+      int Rm = R;
+      while (static_cast<uint32_t>(Rm + 1) * static_cast<uint32_t>(Rm + 1) <= c->clear_c2) ++Rm;  // <= 254: kc_planner_set_clearance_cost
+      KC_TRY(c->d_clear2.reserve(static_cast<size_t>(n)));
+      KC_TRY(c->d_pen.reserve(static_cast<size_t>(n)));
+      hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, Rm, unknown_blocks);
+      hipLaunchKernelGGL(planner_clear_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_pen_by_d2.p, c->d_clear2.p,
+                         c->d_pen.p, c->d_valid.p, W, H, Rm, r2, c->clear_c2);
+    } else {
+      hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
+      hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_valid.p, W, H, R, r2);
+    }
     KC_HIP(hipGetLastError());
     c->have_valid = true;
     c->valid_r2 = r2;
@@ -440,8 +544,13 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
     for (;;) {
       for (int b = 0; b < kPlanBatch; ++b) {
         ++pass;
-        hipLaunchKernelGGL(planner_relax_kernel, tiles, dim3(kPlanThreads), 0, s, c->d_field[(pass - 1) & 1].p,
-                           c->d_field[pass & 1].p, c->d_valid.p, W, H, tiles_x, c->d_word.p, pass);
+        if (pen_on)
+          hipLaunchKernelGGL(planner_relax_kernel<true>, tiles, dim3(kPlanThreads), 0, s, c->d_field[(pass - 1) & 1].p,
+                             c->d_field[pass & 1].p, c->d_valid.p, c->d_pen.p, W, H, tiles_x, c->d_word.p, pass);
+        else
+          hipLaunchKernelGGL(planner_relax_kernel<false>, tiles, dim3(kPlanThreads), 0, s, c->d_field[(pass - 1) & 1].p,
+                             c->d_field[pass & 1].p, c->d_valid.p, static_cast<const uint32_t *>(nullptr), W, H, tiles_x,
+                             c->d_word.p, pass);
       }
       KC_HIP(hipGetLastError());
       KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -499,26 +608,7 @@ int kc_planner_get_path(kc_planner *c, int32_t *cells_ij_out, size_t cap_points,
   *count_out = 0;
   if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_path before kc_planner_solve");
   if (c->status != KC_PLAN_FOUND) return KC_OK;  // no path: zero points
-  if (!c->have_path) {
-    KC_HIP(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    // every step lowers the field by 10 at least
-    const size_t cap = static_cast<size_t>(c->cost / 10u) + 2;
-    KC_TRY(c->d_path.reserve(cap));
-    KC_TRY(c->h_path.reserve(cap));
-    hipLaunchKernelGGL(planner_walk_kernel, dim3(1), dim3(64), 0, s, c->d_field[c->final_buf].p, c->d_valid.p, c->W, c->H,
-                       c->start[0], c->start[1], c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
-    KC_HIP(hipGetLastError());
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[1], c->d_word.p + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    KC_HIP(hipStreamSynchronize(s));
-    const uint32_t count = c->h_word.p[1], wst = c->h_word.p[2];
-    if (wst != 0u || count == 0u || count > cap)
-      KC_FAIL(KC_ERR_STATE, "the path walk stopped after %u cells with status %u", count, wst);
-    KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    KC_HIP(hipStreamSynchronize(s));
-    c->path.assign(c->h_path.p, c->h_path.p + count);
-    c->have_path = true;
-  }
+  KC_TRY(planner_walk(c));
   *count_out = c->path.size();
   if (!cells_ij_out) return KC_OK;  // the count alone
   if (c->path.size() > cap_points) KC_FAIL(KC_ERR_RANGE, "%zu path cells do not fit the output capacity %zu", c->path.size(), cap_points);
@@ -526,6 +616,48 @@ int kc_planner_get_path(kc_planner *c, int32_t *cells_ij_out, size_t cap_points,
     cells_ij_out[2 * k] = c->path[k] % c->W;
     cells_ij_out[2 * k + 1] = c->path[k] / c->W;
   }
+  return KC_OK;
+}
+
+int kc_planner_set_clearance_cost(kc_planner *c, uint32_t c2, const uint32_t *pen_by_d2, size_t n) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  const bool on = c2 > 0 && pen_by_d2 != nullptr;
+  if (on) {
+    if (c2 > static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+      KC_FAIL(KC_ERR_RANGE, "a clearance reach of C2 = %u is wider than %d cells", c2, KC_PLANNER_MAX_RADIUS_CELLS);
+    if (n != static_cast<size_t>(c2) + 1) KC_FAIL(KC_ERR_INVALID, "the penalty table of C2 = %u has %u entries, not %zu", c2, c2 + 1u, n);
+    KC_HIP(hipSetDevice(c->device));
+    KC_TRY(c->d_pen_by_d2.reserve(n));
+    // pageable memory: the copy has left the caller's table when the call returns
+    KC_HIP(hipMemcpyAsync(c->d_pen_by_d2.p, pen_by_d2, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    KC_HIP(hipStreamSynchronize(c->stream));
+    c->clear_max_pen = *std::max_element(pen_by_d2, pen_by_d2 + n);
+  }
+  c->clear_c2 = on ? c2 : 0u;
+  c->have_valid = c->solved = c->have_path = false;  // clear2 and the penalty come with the validity pass
+  c->status = -1;
+  return KC_OK;
+}
+
+int kc_planner_get_clearance(kc_planner *c, uint16_t *clear2_out, uint32_t *penalty_out, size_t cap) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_clearance before kc_planner_solve");
+  if (c->clear_c2 == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_get_clearance with the clearance cost off");
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipSetDevice(c->device));
+  if (clear2_out) KC_HIP(hipMemcpyAsync(clear2_out, c->d_clear2.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  if (penalty_out) KC_HIP(hipMemcpyAsync(penalty_out, c->d_pen.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_planner_path_clearance(kc_planner *c, uint32_t *min_clear2_out) {
+  if (!c || !min_clear2_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->solved || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_path_clearance without a path");
+  if (c->clear_c2 == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_path_clearance with the clearance cost off");
+  KC_TRY(planner_walk(c));
+  *min_clear2_out = c->path_clear2;
   return KC_OK;
 }
 

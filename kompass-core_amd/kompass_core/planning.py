@@ -5,7 +5,9 @@ Not the reference's `OMPLGeometric` (`kompass_core/third_party/ompl/planner.py`,
 scope): a deterministic, exact 8-connected shortest path on the grid.  `setup_problem` is shaped like
 `OMPLGeometric.setup_problem` (:168-212), with the grid as one more argument.  The robot is a disc of its
 circumscribed horizontal radius (the cylinder's or sphere's radius, half the box's diagonal): yaw-free and
-conservative."""
+conservative.  A clearance cost (`clearance_reach`, `clearance_weight`) makes the path trade length for distance
+from obstacles: the counterpart, on the grid, of the `max_min_clearance` objective of the reference's OMPL front end
+(`third_party/ompl/config.py:120-123`) and of `PathGeometric::clearance`."""
 from typing import Dict, Optional
 
 import kompass_cpp
@@ -14,9 +16,11 @@ from .models import Robot, RobotGeometry
 
 
 class GridPlanner:
-    def __init__(self, robot: Robot, allow_unknown: bool = True, margin: float = 0.0, simplify: bool = False):
+    def __init__(self, robot: Robot, allow_unknown: bool = True, margin: float = 0.0, simplify: bool = False,
+                 clearance_reach: float = 0.0, clearance_weight: float = 0.0):
         """allow_unknown: UNEXPLORED cells can be crossed (default) or block like OCCUPIED ones.
-        margin: metres added to the robot's radius.  simplify: drop the interior points of straight runs."""
+        margin: metres added to the robot's radius.  simplify: drop the interior points of straight runs.
+        clearance_reach, clearance_weight: see set_clearance_cost; the defaults leave it off."""
         if not RobotGeometry.is_valid_parameters(robot.geometry_type, robot.geometry_params):
             raise ValueError(f"invalid geometry parameters {robot.geometry_params} for {robot.geometry_type}")
         self._planner = kompass_cpp.planning.GridPlanner(
@@ -24,6 +28,15 @@ class GridPlanner:
             robot_dimensions=[float(v) for v in robot.geometry_params], allow_unknown=bool(allow_unknown),
             margin=float(margin))
         self.simplify = bool(simplify)
+        self.solution = None
+        if clearance_reach > 0.0 and clearance_weight > 0.0:
+            self.set_clearance_cost(clearance_reach, clearance_weight)
+
+    def set_clearance_cost(self, reach: float, weight: float):
+        """Surcharge the cells within `reach` metres beyond the footprint (radius + margin): `weight` straight-cell
+        lengths at the footprint's edge, falling linearly in the squared distance to 0 at the reach.  The path
+        then minimises length plus surcharge.  reach <= 0 or weight <= 0 switches it off."""
+        self._planner.set_clearance_cost(float(reach), float(weight))
         self.solution = None
 
     def setup_problem(self, map_meta_data: Dict, start_x: float, start_y: float, start_yaw: float, goal_x: float,
@@ -62,7 +75,24 @@ class GridPlanner:
         return self.solution
 
     def get_cost(self) -> float:
+        """Metres of path, plus the surcharges of the cells it leaves while a clearance cost is set."""
         return self._planner.get_cost()
+
+    @property
+    def path_length(self) -> float:
+        """Metres along the path's steps alone."""
+        return self._planner.get_path_length()
+
+    @property
+    def min_clearance(self) -> float:
+        """Metres from the path's cells to the nearest blocking cell, inf when none is within the clearance reach
+        (needs a clearance cost)."""
+        return self._planner.get_path_min_clearance()
+
+    def clearance_field(self):
+        """(clear2 uint16, penalty uint32) [width, height] of the last solve: squared cells to the nearest blocking
+        cell (0xFFFF beyond the reach) and the surcharge per cell (needs a clearance cost)."""
+        return self._planner.get_clearance()
 
     @property
     def status(self) -> int:

@@ -229,6 +229,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_int)]),
     "kc_planner_get_field": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
     "kc_planner_get_path": (C.c_int, [_vp, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_set_clearance_cost": (C.c_int, [_vp, C.c_uint32, C.c_void_p, _sz]),
+    "kc_planner_get_clearance": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
+    "kc_planner_path_clearance": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None
@@ -1171,6 +1174,7 @@ class DvzContext:
 
 PLAN_FOUND, PLAN_START_OUTSIDE, PLAN_GOAL_OUTSIDE, PLAN_START_INVALID, PLAN_GOAL_INVALID, PLAN_UNREACHABLE = range(6)
 PLAN_INF = 0xFFFFFFFF
+PLAN_CLEAR_FAR = 0xFFFF
 
 
 class PlannerContext:
@@ -1237,3 +1241,30 @@ class PlannerContext:
         if n.value:
             _check(lib().kc_planner_get_path(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out
+
+    def set_clearance_cost(self, c2, table=None):
+        """The clearance cost of rules 6 to 8: table[d2] for d2 = 0 .. c2 is the surcharge of a cell whose nearest
+        blocking cell lies at squared distance d2.  c2 = 0 (or no table) switches it off.  Forgets the last solve."""
+        if table is None or int(c2) == 0:
+            _check(lib().kc_planner_set_clearance_cost(self.h, int(c2), None, 0))
+            return
+        t = np.ascontiguousarray(table)
+        if t.ndim != 1 or t.dtype.kind not in "iu" or (t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF)):
+            raise ValueError("expected a 1-D table of integers that fit uint32")
+        t = t.astype(np.uint32)
+        _check(lib().kc_planner_set_clearance_cost(self.h, int(c2), t.ctypes.data, t.size))
+
+    def clearance(self):
+        """(clear2 uint16 [width, height], penalty uint32 [width, height]) of the last solve; raises with the
+        clearance cost off."""
+        w, h = self.shape
+        c = np.empty((w, h), np.uint16, order="F")
+        p = np.empty((w, h), np.uint32, order="F")
+        _check(lib().kc_planner_get_clearance(self.h, c.ctypes.data, p.ctypes.data, c.size))
+        return c, p
+
+    def path_clearance(self):
+        """The smallest clear2 along the last path, both ends included (PLAN_CLEAR_FAR: nothing within reach)."""
+        v = C.c_uint32(0)
+        _check(lib().kc_planner_path_clearance(self.h, C.byref(v)))
+        return v.value

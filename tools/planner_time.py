@@ -3,8 +3,10 @@
 1204 cells, synthetic.pcd_indoor_map_doors, corner to corner) and on a 500 x 500 clutter grid, from a
 device-resident grid and from a host array; the path walk on its own; and the one-thread CPU baseline, the heap
 Dijkstra of tests/planner_ref.py.  Warm-up, then --reps repetitions: median and min .. max, the device named.
+--clearance REACH_CELLS,WEIGHT10 adds a leg with the clearance cost on (rules 6 to 8): C2 = (sqrt(R2) + REACH_CELLS)^2,
+the table of tests/planner_clearance_ref.py; the solve with the clearance pass, the field alone, the walk, the passes.
 
-  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--json out.json]
+  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--json out.json]
   rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
 """
 import argparse
@@ -21,6 +23,7 @@ ROOT = Path(__file__).resolve().parent.parent
 for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
     sys.path.insert(0, str(p))
 import kompass_hip as kh  # noqa: E402
+import planner_clearance_ref as cref  # noqa: E402
 import planner_ref as ref  # noqa: E402
 import synthetic as syn  # noqa: E402
 
@@ -81,6 +84,34 @@ def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
         out["cpu_dijkstra_ms"] = stats_ms(lambda: ref.cost_field(valid, goal), a.cpu_reps, warm=0)
         f, v = ctx.field()
         assert (f == ref.cost_field(valid, goal)).all() and (v == valid).all()
+    if a.clearance:
+        out["clearance"] = clearance_leg(ctx, start, goal, r2, a)
+    return out
+
+
+def clearance_leg(ctx, start, goal, r2, a):
+    """The same grid (resident) with the clearance cost on, then off again."""
+    reach, wt = (int(v) for v in a.clearance.split(","))
+    c2 = min(int((r2 ** 0.5 + reach) ** 2), cref.MAX_C2)
+    table = cref.clearance_table(wt, r2, c2)
+    ctx.set_clearance_cost(c2, table)
+    st, cost, passes = ctx.solve(start, goal, r2)
+    cells = ctx.path()
+    out = dict(c2=c2, weight10=wt, status=st, cost=cost, passes=passes, launched=-(-passes // 8) * 8,
+               path_cells=int(len(cells)), path_length=cref.path_length(cells), min_clear2=ctx.path_clearance())
+
+    def with_clearance_pass():
+        ctx.set_clearance_cost(c2, table)   # forgets clear2, the penalty and the validity map
+        ctx.solve(start, goal, r2)
+
+    def walk():
+        ctx.solve(start, goal, r2)
+        ctx.path()
+
+    out["table_clearance_field_ms"] = stats_ms(with_clearance_pass, a.reps)
+    out["resolve_ms"] = stats_ms(lambda: ctx.solve(start, goal, r2), a.reps)   # clear2 and penalty resident: field only
+    out["resolve_and_walk_ms"] = stats_ms(walk, a.reps)
+    ctx.set_clearance_cost(0)
     return out
 
 
@@ -88,6 +119,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--cpu-reps", type=int, default=1)
+    ap.add_argument("--clearance", default=None, metavar="REACH_CELLS,WEIGHT10")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if kh.device_count() < 1:
@@ -120,6 +152,14 @@ def main():
             if k in s:
                 v = s[k]
                 print(f"  {k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+        c = s.get("clearance")
+        if c:
+            print(f"  clearance cost C2 {c['c2']}, weight {c['weight10']}: status {c['status']}, cost {c['cost']}, length "
+                  f"{c['path_length']}, {c['passes']} passes ({c['launched']} launched), {c['path_cells']} path cells, "
+                  f"min clear2 {c['min_clear2']}")
+            for k in ("table_clearance_field_ms", "resolve_ms", "resolve_and_walk_ms"):
+                v = c[k]
+                print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
     print(json.dumps(out))
     if a.json:
         Path(a.json).parent.mkdir(parents=True, exist_ok=True)
