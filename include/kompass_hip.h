@@ -880,6 +880,26 @@ int kc_planner_set_clearance_cost(kc_planner *ctx, uint32_t c2, const uint32_t *
 int kc_planner_get_clearance(kc_planner *ctx, uint16_t *clear2_out, uint32_t *penalty_out, size_t cap);
 /* smallest clear2 along the last path (KC_PLANNER_CLEAR_FAR: nothing within reach); KC_ERR_STATE without a path */
 int kc_planner_path_clearance(kc_planner *ctx, uint32_t *min_clear2_out);
+/* The any-angle path (rules 9 to 12), on request only.
+ *  - the segment between cells a and b touches cell (i, j) when (i, j) lies in the
+ *    bounding box of a and b and 2 |dx (j - ay) - dy (i - ax)| <= |dx| + |dy|; it is
+ *    clear when every touched cell is valid and, while a clearance cost is set, holds
+ *    clear2 >= the walk's own smallest clear2 (kc_planner_path_clearance).
+ *  - from index s = 0 of the walk p[0 .. n-1] (kc_planner_get_path) the largest t in
+ *    (s, min(n - 1, s + max_span)] with p[s] -> p[t] clear is kept, s + 1 untested,
+ *    then s = t, until the last index.
+ * *count_out = kept indices, first and last of the walk among them; *min_clear2_out =
+ * the smallest clear2 over the kept cells and the touched cells of the kept segments
+ * that were tested (KC_PLANNER_CLEAR_FAR with the clearance cost off); either may be
+ * NULL.  Walks first if needed; one launch, kept per (solve, max_span).  KC_ERR_STATE
+ * unless the last solve found a path, KC_ERR_RANGE for max_span outside
+ * 1 .. KC_PLANNER_MAX_SPAN.  Cost, path and path clearance keep describing the walk. */
+#define KC_PLANNER_MAX_SPAN 1024
+int kc_planner_shortcut(kc_planner *ctx, int max_span, size_t *count_out, uint32_t *min_clear2_out);
+/* the last kc_planner_shortcut's kept cells ((i, j) pairs) and their indices into the
+ * walk, ascending; either may be NULL, both NULL asks for the count only;
+ * KC_ERR_STATE without one (a new solve forgets it) */
+int kc_planner_get_shortcut(kc_planner *ctx, int32_t *cells_ij_out, int32_t *index_out, size_t cap, size_t *count_out);
 
 #ifdef __cplusplus
 }

@@ -1032,6 +1032,27 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def("get_path_min_clearance", &Planning::GridPlanner::getPathMinClearance,
            "metres from the path's cells to the nearest blocking cell; inf when none is within reach")
       .def("get_path_length", &Planning::GridPlanner::getPathLength, "the steps of the path alone, in metres")
+      .def("get_any_angle_solution", [](Planning::GridPlanner &p, int max_span) -> py::object {
+             auto path = p.getAnyAnglePath(max_span);
+             if (!path) return py::none();
+             return py::cast(std::move(*path));
+           }, py::arg("max_span") = 128,
+           "The any-angle path: from each kept cell the farthest of the next max_span cells of the walk in line of sight")
+      .def("get_any_angle_cells", [](Planning::GridPlanner &p, int max_span, bool with_indices) -> py::object {
+             std::vector<int32_t> idx;
+             const std::vector<int32_t> ij = p.getAnyAngleCells(max_span, with_indices ? &idx : nullptr);
+             py::array_t<int32_t> a({(py::ssize_t)(ij.size() / 2), (py::ssize_t)2});
+             if (!ij.empty()) std::memcpy(a.mutable_data(), ij.data(), ij.size() * sizeof(int32_t));
+             if (!with_indices) return a;
+             py::array_t<int32_t> b((py::ssize_t)idx.size());
+             if (!idx.empty()) std::memcpy(b.mutable_data(), idx.data(), idx.size() * sizeof(int32_t));
+             return py::make_tuple(a, b);
+           }, py::arg("max_span") = 128, py::arg("with_indices") = false,
+           "(k, 2) cells of the any-angle path; with_indices: also their indices into get_path_cells()")
+      .def("get_any_angle_length", &Planning::GridPlanner::getAnyAngleLength, py::arg("max_span") = 128,
+           "metres along the any-angle path")
+      .def("get_any_angle_min_clearance", &Planning::GridPlanner::getAnyAngleMinClearance, py::arg("max_span") = 128,
+           "metres from the cells the any-angle path touches to the nearest blocking cell; inf without a clearance cost")
       .def("get_clearance_c2", &Planning::GridPlanner::clearanceC2)
       .def("get_clearance_weight10", &Planning::GridPlanner::clearanceWeight10)
       .def("get_status", &Planning::GridPlanner::status)

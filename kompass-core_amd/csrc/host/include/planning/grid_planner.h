@@ -6,7 +6,9 @@
 // setupProblem, solve, getPath, getCost) and is not a restatement of it: an exact 8-connected shortest path on
 // the grid, the robot a disc of its circumscribed horizontal radius (yaw-free, conservative).  setClearanceCost
 // adds a surcharge per cell that falls with the distance to the nearest blocking cell (rules 6 to 8): the path
-// then trades length for clearance, as deterministically as before.
+// then trades length for clearance, as deterministically as before.  getAnyAngle* hand out the any-angle path over
+// the same walk (rules 9 to 12): far fewer waypoints, straight where there is line of sight, and with a clearance
+// cost no closer to a blocking cell than the walk already came.
 #pragma once
 
 #include <cstdint>
@@ -55,6 +57,18 @@ class GridPlanner {
   float getCost() const;
   // the steps of the path alone, summed from its cells: metres along the 8-connected path
   float getPathLength();
+
+  // The any-angle path (rules 9 to 12): from each kept cell the farthest of the next max_span cells of the walk whose
+  // segment touches only valid cells (and, with a clearance cost, no cell closer to a blocking one than the walk's
+  // closest).  nullopt / empty / +inf without a path; std::out_of_range for max_span outside 1 ..
+  // KC_PLANNER_MAX_SPAN.  getCost, getPathLength and getPathMinClearance keep describing the walk.
+  std::optional<Path::Path> getAnyAnglePath(int max_span = 128);
+  // (i, j) pairs of its cells; indices_out (optional): their indices into getPathCells(false)
+  std::vector<int32_t> getAnyAngleCells(int max_span = 128, std::vector<int32_t> *indices_out = nullptr);
+  // resolution * sum of sqrt(dx^2 + dy^2) over consecutive kept cells, in double, in path order, cast to float
+  float getAnyAngleLength(int max_span = 128);
+  // sqrt(smallest clear2 the kept segments touch) * resolution; +inf with the clearance cost off or nothing in reach
+  float getAnyAngleMinClearance(int max_span = 128);
 
   // The clearance cost.  reach: metres beyond the footprint radius plus margin over which a cell is surcharged, C2
   // = radiusToR2(radius + margin + reach, resolution), evaluated with the bounds and again when they change.

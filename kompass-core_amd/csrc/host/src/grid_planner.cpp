@@ -262,6 +262,47 @@ float GridPlanner::getPathLength() {
   return static_cast<float>(steps) * res_ / 10.0f;
 }
 
+std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int32_t> *indices_out) {
+  std::vector<int32_t> ij;
+  if (indices_out) indices_out->clear();
+  if (status_ != KC_PLAN_FOUND) return ij;
+  size_t n = 0;
+  hip::check(kc_planner_shortcut(ctx_.get(), max_span, &n, nullptr));
+  ij.resize(2 * n);
+  if (indices_out) indices_out->resize(n);
+  hip::check(kc_planner_get_shortcut(ctx_.get(), ij.data(), indices_out ? indices_out->data() : nullptr, n, &n));
+  return ij;
+}
+
+std::optional<Path::Path> GridPlanner::getAnyAnglePath(int max_span) {
+  if (status_ != KC_PLAN_FOUND) return std::nullopt;
+  const std::vector<int32_t> ij = getAnyAngleCells(max_span);
+  std::vector<Path::Point> pts;
+  pts.reserve(ij.size() / 2);
+  for (size_t k = 0; k + 1 < ij.size(); k += 2)
+    pts.emplace_back(cellToWorld(ij[k], ox_, res_), cellToWorld(ij[k + 1], oy_, res_), 0.0f);
+  return Path::Path(pts);
+}
+
+float GridPlanner::getAnyAngleLength(int max_span) {
+  if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
+  const std::vector<int32_t> ij = getAnyAngleCells(max_span);
+  double sum = 0.0;
+  for (size_t k = 2; k + 1 < ij.size(); k += 2) {
+    const double dx = static_cast<double>(ij[k] - ij[k - 2]), dy = static_cast<double>(ij[k + 1] - ij[k - 1]);
+    sum += std::sqrt(dx * dx + dy * dy);
+  }
+  return static_cast<float>(static_cast<double>(res_) * sum);
+}
+
+float GridPlanner::getAnyAngleMinClearance(int max_span) {
+  if (status_ != KC_PLAN_FOUND) throw std::runtime_error("GridPlanner: no path");
+  uint32_t c2 = KC_PLANNER_CLEAR_FAR;
+  hip::check(kc_planner_shortcut(ctx_.get(), max_span, nullptr, &c2));
+  if (c2 == KC_PLANNER_CLEAR_FAR) return std::numeric_limits<float>::infinity();
+  return std::sqrt(static_cast<float>(c2)) * res_;
+}
+
 void GridPlanner::getClearance(uint16_t *clear2_out, uint32_t *pen_out, size_t cap) {
   if (status_ < 0) throw std::runtime_error("GridPlanner: no solve since the last grid or problem");
   hip::check(kc_planner_get_clearance(ctx_.get(), clear2_out, pen_out, cap));

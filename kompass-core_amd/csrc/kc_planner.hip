@@ -24,6 +24,11 @@
 //      the table's penalty and the validity map in one go.  planner_relax_kernel<true> adds the penalty of the cell
 //      a step leaves, one register per owned cell; planner_walk_kernel<true> follows field + step and keeps the
 //      smallest clear2 it visits.  The <false> instantiations are the code of the planner without the cost.
+//  (e) any-angle path (rules 9 to 12; on request, kc_planner_shortcut).  planner_shortcut_kernel: one workgroup behind
+//      the walk loops over the anchors; the window of the walk behind an anchor sits in LDS, its candidates go one
+//      to a wavefront from the far end in rounds of 16, the lanes of a wavefront stride over the columns of their
+//      segment and test the up to three touched cells of a column, and the largest clear index of the first round
+//      that has one is the next anchor.
 //
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
@@ -46,6 +51,8 @@ constexpr int kPlanLocalIters = 4 * kPlanTile; // Jacobi iterations per tile and
 constexpr int kPlanBatch = 8;                  // passes per read-back of the changed word
 constexpr int kPlanBlock = 256;
 constexpr int kPlanMaxBlocks = 2048;
+constexpr int kShortThreads = 1024;            // the shortcut's one workgroup: 16 wavefronts, a candidate each
+constexpr int kShortWaves = kShortThreads / 64;
 
 // the neighbour order of the walk (ties go to the first): E, N, W, S, NE, NW, SW, SE
 __constant__ const int kPlanDx[8] = {1, 0, -1, 0, 1, -1, -1, 1};
@@ -275,6 +282,99 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
   }
 }
 
+// status words of the shortcut: out[0] = kept indices written, out[1] = 0 done, out[2] = the smallest clear2 over the
+// kept cells and the touched cells of the kept segments that were tested (CLEAR_FAR without CLR).
+// Rule 11 over the walk path[0 .. n-1] (linear cells): from the anchor s the largest t <= min(n - 1, s + span) whose
+// segment is clear (rules 9 and 10), s + 1 untested.  CLR: a touched cell must also hold clear2 >= m.
+// Every touched cell lies in the bounding box of two cells of the walk, so no load leaves the grid.
+template <bool CLR>
+__global__ __launch_bounds__(kShortThreads) void planner_shortcut_kernel(const int32_t *__restrict__ path, uint32_t n, int span,
+                                                                         const uint8_t *__restrict__ valid,
+                                                                         const uint16_t *__restrict__ clear2, uint32_t m, int W,
+                                                                         int32_t *__restrict__ keep, uint32_t *out) {
+  __shared__ int32_t px[KC_PLANNER_MAX_SPAN + 1], py[KC_PLANNER_MAX_SPAN + 1];
+  __shared__ uint32_t best;  // of a round: (index - s) << 16 | 0xFFFF - smallest touched clear2, 0 for none clear
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t s = 0, kept = 1, min_touched = KC_PLANNER_CLEAR_FAR;  // kept and min_touched are lane 0's
+  if (tid == 0) {
+    keep[0] = 0;
+    if constexpr (CLR) min_touched = clear2[path[0]];
+  }
+  while (s + 1 < n) {
+    const int hi = static_cast<int>(min(static_cast<uint32_t>(span), n - 1 - s));
+    __syncthreads();  // the last anchor's window and its `best` have been read by everyone
+    for (int k = tid; k <= hi; k += kShortThreads) {
+      const int32_t c = path[s + k];
+      px[k] = c % W;
+      py[k] = c / W;
+    }
+    if (tid == 0) best = 0;
+    __syncthreads();
+    const int ax = px[0], ay = py[0];
+    uint32_t found = 0;
+    for (int top = hi; top >= 2 && !found; top -= kShortWaves) {
+      const int rel = top - wave;  // this wavefront's candidate
+      if (rel >= 2) {
+        const int dx = px[rel] - ax, dy = py[rel] - ay;
+        const int adx = abs(dx), ady = abs(dy);
+        const bool xmaj = adx >= ady;
+        const int M = xmaj ? adx : ady, mn = xmaj ? ady : adx;  // |dx|, |dy| <= rel <= 1024: the products fit
+        const int sM = xmaj ? (dx > 0) - (dx < 0) : (dy > 0) - (dy < 0);
+        const int sm = xmaj ? (dy > 0) - (dy < 0) : (dx > 0) - (dx < 0);
+        const int den = 2 * max(M, 1);
+        bool blocked = false;
+        uint32_t wmin = KC_PLANNER_CLEAR_FAR;
+        for (int k0 = 0; k0 <= M; k0 += 64) {
+          const int k = k0 + lane;  // a column of the major axis
+          if (k <= M) {
+            const int q = mn * k;
+            const int v1 = (2 * q + M) / den;  // the minor offset nearest to the segment: the touched ones are v1 - 1 .. v1 + 1
+#pragma unroll
+            for (int d = -1; d <= 1; ++d) {
+              const int v = v1 + d;
+              // rule 9: inside the bounding box and 2 |dx (j - ay) - dy (i - ax)| <= |dx| + |dy|
+              if (v >= 0 && v <= mn && 2 * abs(M * v - q) <= M + mn) {
+                const int cx = xmaj ? ax + sM * k : ax + sm * v, cy = xmaj ? ay + sm * v : ay + sM * k;
+                const size_t g = static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(cx);
+                blocked |= valid[g] == 0;
+                if constexpr (CLR) {
+                  const uint32_t c2 = clear2[g];
+                  blocked |= c2 < m;
+                  wmin = min(wmin, c2);
+                }
+              }
+            }
+          }
+          if (__any(blocked)) break;
+        }
+        if (!__any(blocked)) {
+          if constexpr (CLR) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) wmin = min(wmin, static_cast<uint32_t>(__shfl_xor(static_cast<int>(wmin), d, 64)));
+          }
+          if (lane == 0) atomicMax(&best, (static_cast<uint32_t>(rel) << 16) | (0xFFFFu - wmin));
+        }
+      }
+      __syncthreads();
+      found = best;
+      __syncthreads();  // nobody raises `best` in the next round before everyone has read this one's
+    }
+    s += found ? found >> 16 : 1u;
+    if (tid == 0) {
+      keep[kept++] = static_cast<int32_t>(s);
+      if constexpr (CLR) {
+        if (found) min_touched = min(min_touched, 0xFFFFu - (found & 0xFFFFu));
+        min_touched = min(min_touched, static_cast<uint32_t>(clear2[path[s]]));
+      }
+    }
+  }
+  if (tid == 0) {
+    out[0] = kept;
+    out[1] = 0;
+    out[2] = min_touched;
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -303,10 +403,17 @@ struct kc_planner {
   uint32_t path_clear2 = KC_PLANNER_CLEAR_FAR;
   DevBuf<uint32_t> d_pen_by_d2, d_pen;
   DevBuf<uint16_t> d_clear2;
-  DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status, [3] its smallest clear2
-  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal], [6] d_word[3]
+  DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status, [3] its smallest clear2,
+                             // [4..6] the shortcut's count, status and smallest touched clear2
+  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal], [6] d_word[3], [8..10] d_word[4..6]
   DevBuf<int32_t> d_path;
   PinBuf<int32_t> h_path;
+  bool have_short = false;   // short_idx holds rule 11's indices into `path` for short_span (forgotten with the walk)
+  int short_span = 0;
+  uint32_t short_clear2 = KC_PLANNER_CLEAR_FAR;
+  std::vector<int32_t> short_idx;
+  DevBuf<int32_t> d_keep;
+  PinBuf<int32_t> h_keep;
 };
 
 namespace {
@@ -397,6 +504,38 @@ int planner_walk(kc_planner *c) {
   c->path.assign(c->h_path.p, c->h_path.p + count);
   c->path_clear2 = pen_on ? c->h_word.p[6] : static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
   c->have_path = true;
+  c->have_short = false;  // a shortcut is one of this walk
+  return KC_OK;
+}
+
+// rules 9 to 12 over the walk of the last solve, once per (walk, max_span): c->short_idx, c->short_clear2
+int planner_shortcut(kc_planner *c, int max_span) {
+  KC_TRY(planner_walk(c));
+  if (c->have_short && c->short_span == max_span) return KC_OK;
+  c->have_short = false;
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const bool clr = c->clear_c2 > 0;
+  const size_t n = c->path.size();  // d_path still holds these cells: only the walk writes it
+  KC_TRY(c->d_keep.reserve(n));
+  KC_TRY(c->h_keep.reserve(n));
+  if (clr)
+    hipLaunchKernelGGL(planner_shortcut_kernel<true>, dim3(1), dim3(kShortThreads), 0, s, c->d_path.p, static_cast<uint32_t>(n),
+                       max_span, c->d_valid.p, c->d_clear2.p, c->path_clear2, c->W, c->d_keep.p, c->d_word.p + 4);
+  else
+    hipLaunchKernelGGL(planner_shortcut_kernel<false>, dim3(1), dim3(kShortThreads), 0, s, c->d_path.p, static_cast<uint32_t>(n),
+                       max_span, c->d_valid.p, static_cast<const uint16_t *>(nullptr), 0u, c->W, c->d_keep.p, c->d_word.p + 4);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipMemcpyAsync(&c->h_word.p[8], c->d_word.p + 4, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  const uint32_t count = c->h_word.p[8], sst = c->h_word.p[9];
+  if (sst != 0u || count == 0u || count > n) KC_FAIL(KC_ERR_STATE, "the shortcut stopped after %u indices with status %u", count, sst);
+  KC_HIP(hipMemcpyAsync(c->h_keep.p, c->d_keep.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  c->short_idx.assign(c->h_keep.p, c->h_keep.p + count);
+  c->short_clear2 = c->h_word.p[10];
+  c->short_span = max_span;
+  c->have_short = true;
   return KC_OK;
 }
 
@@ -418,7 +557,7 @@ int kc_planner_create(int device, kc_planner **out) {
     return KC_ERR_HIP;
   }
   int rc;
-  if ((rc = c->d_word.reserve(4)) || (rc = c->h_word.reserve(8))) {
+  if ((rc = c->d_word.reserve(8)) || (rc = c->h_word.reserve(12))) {
     kc_planner_destroy(c);
     return rc;
   }
@@ -447,6 +586,8 @@ void kc_planner_destroy(kc_planner *c) {
   c->h_word.release();
   c->d_path.release();
   c->h_path.release();
+  c->d_keep.release();
+  c->h_keep.release();
   delete c;
 }
 
@@ -658,6 +799,38 @@ int kc_planner_path_clearance(kc_planner *c, uint32_t *min_clear2_out) {
   if (c->clear_c2 == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_path_clearance with the clearance cost off");
   KC_TRY(planner_walk(c));
   *min_clear2_out = c->path_clear2;
+  return KC_OK;
+}
+
+int kc_planner_shortcut(kc_planner *c, int max_span, size_t *count_out, uint32_t *min_clear2_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (count_out) *count_out = 0;
+  if (!c->solved || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_shortcut without a path");
+  if (max_span < 1 || max_span > KC_PLANNER_MAX_SPAN)
+    KC_FAIL(KC_ERR_RANGE, "max_span %d is outside 1 .. %d", max_span, KC_PLANNER_MAX_SPAN);
+  KC_TRY(planner_shortcut(c, max_span));
+  if (count_out) *count_out = c->short_idx.size();
+  if (min_clear2_out) *min_clear2_out = c->short_clear2;
+  return KC_OK;
+}
+
+int kc_planner_get_shortcut(kc_planner *c, int32_t *cells_ij_out, int32_t *index_out, size_t cap, size_t *count_out) {
+  if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  if (!c->solved || c->status != KC_PLAN_FOUND || !c->have_path || !c->have_short)
+    KC_FAIL(KC_ERR_STATE, "kc_planner_get_shortcut before kc_planner_shortcut");
+  const size_t n = c->short_idx.size();
+  *count_out = n;
+  if (!cells_ij_out && !index_out) return KC_OK;  // the count alone
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu kept cells do not fit the output capacity %zu", n, cap);
+  for (size_t k = 0; k < n; ++k) {
+    const int32_t cell = c->path[static_cast<size_t>(c->short_idx[k])];
+    if (cells_ij_out) {
+      cells_ij_out[2 * k] = cell % c->W;
+      cells_ij_out[2 * k + 1] = cell / c->W;
+    }
+    if (index_out) index_out[k] = c->short_idx[k];
+  }
   return KC_OK;
 }
 

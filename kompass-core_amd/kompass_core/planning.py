@@ -7,7 +7,10 @@ scope): a deterministic, exact 8-connected shortest path on the grid.  `setup_pr
 circumscribed horizontal radius (the cylinder's or sphere's radius, half the box's diagonal): yaw-free and
 conservative.  A clearance cost (`clearance_reach`, `clearance_weight`) makes the path trade length for distance
 from obstacles: the counterpart, on the grid, of the `max_min_clearance` objective of the reference's OMPL front end
-(`third_party/ompl/config.py:120-123`) and of `PathGeometric::clearance`."""
+(`third_party/ompl/config.py:120-123`) and of `PathGeometric::clearance`.  `any_angle=True` hands out the any-angle
+path over the same solve (line-of-sight shortcuts between its cells): the counterpart of the `simplifySolution()` the
+reference's wrapper runs on every solve (`src/planning/ompl.cpp:61`).  An 8-connected path is at most 8 % longer than
+the any-angle optimum, so what the shortcut buys is few waypoints and steady headings, not length."""
 from typing import Dict, Optional
 
 import kompass_cpp
@@ -17,10 +20,14 @@ from .models import Robot, RobotGeometry
 
 class GridPlanner:
     def __init__(self, robot: Robot, allow_unknown: bool = True, margin: float = 0.0, simplify: bool = False,
-                 clearance_reach: float = 0.0, clearance_weight: float = 0.0):
+                 clearance_reach: float = 0.0, clearance_weight: float = 0.0, any_angle: bool = False,
+                 max_span: int = 128):
         """allow_unknown: UNEXPLORED cells can be crossed (default) or block like OCCUPIED ones.
         margin: metres added to the robot's radius.  simplify: drop the interior points of straight runs.
-        clearance_reach, clearance_weight: see set_clearance_cost; the defaults leave it off."""
+        clearance_reach, clearance_weight: see set_clearance_cost; the defaults leave it off.
+        any_angle: solve() returns the any-angle path: from each kept cell the farthest of the next `max_span` cells
+        (1 .. 1024) of the 8-connected path in line of sight, and with a clearance cost no closer to a blocking cell
+        than that path came.  `simplify` is then ignored: collinear runs within the span are subsumed."""
         if not RobotGeometry.is_valid_parameters(robot.geometry_type, robot.geometry_params):
             raise ValueError(f"invalid geometry parameters {robot.geometry_params} for {robot.geometry_type}")
         self._planner = kompass_cpp.planning.GridPlanner(
@@ -28,6 +35,10 @@ class GridPlanner:
             robot_dimensions=[float(v) for v in robot.geometry_params], allow_unknown=bool(allow_unknown),
             margin=float(margin))
         self.simplify = bool(simplify)
+        self.any_angle = bool(any_angle)
+        self.max_span = int(max_span)
+        if self.any_angle and not 1 <= self.max_span <= 1024:
+            raise ValueError(f"max_span must be in 1 .. 1024, got {max_span}")
         self.solution = None
         if clearance_reach > 0.0 and clearance_weight > 0.0:
             self.set_clearance_cost(clearance_reach, clearance_weight)
@@ -71,7 +82,12 @@ class GridPlanner:
 
     def solve(self) -> Optional["kompass_cpp.types.Path"]:
         """The path, or None when the start or goal is outside the grid, invalid, or the goal out of reach."""
-        self.solution = self._planner.get_solution(self.simplify) if self._planner.solve() else None
+        if not self._planner.solve():
+            self.solution = None
+        elif self.any_angle:
+            self.solution = self._planner.get_any_angle_solution(self.max_span)
+        else:
+            self.solution = self._planner.get_solution(self.simplify)
         return self.solution
 
     def get_cost(self) -> float:
@@ -104,4 +120,18 @@ class GridPlanner:
 
     @property
     def path_cells(self):
+        if self.any_angle:
+            return self._planner.get_any_angle_cells(self.max_span)
         return self._planner.get_path_cells(self.simplify)
+
+    @property
+    def any_angle_length(self) -> float:
+        """Metres along the any-angle path of `max_span` (path_length and get_cost keep describing the 8-connected
+        path under it)."""
+        return self._planner.get_any_angle_length(self.max_span)
+
+    @property
+    def any_angle_min_clearance(self) -> float:
+        """Metres from the cells the any-angle path touches to the nearest blocking cell: never below min_clearance;
+        inf without a clearance cost."""
+        return self._planner.get_any_angle_min_clearance(self.max_span)

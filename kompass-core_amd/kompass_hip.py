@@ -232,6 +232,8 @@ SIGNATURES = {
     "kc_planner_set_clearance_cost": (C.c_int, [_vp, C.c_uint32, C.c_void_p, _sz]),
     "kc_planner_get_clearance": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
     "kc_planner_path_clearance": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "kc_planner_shortcut": (C.c_int, [_vp, C.c_int, C.POINTER(_sz), C.POINTER(C.c_uint32)]),
+    "kc_planner_get_shortcut": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz)]),
 }
 
 _lib = None
@@ -1175,6 +1177,7 @@ class DvzContext:
 PLAN_FOUND, PLAN_START_OUTSIDE, PLAN_GOAL_OUTSIDE, PLAN_START_INVALID, PLAN_GOAL_INVALID, PLAN_UNREACHABLE = range(6)
 PLAN_INF = 0xFFFFFFFF
 PLAN_CLEAR_FAR = 0xFFFF
+PLAN_MAX_SPAN = 1024
 
 
 class PlannerContext:
@@ -1268,3 +1271,13 @@ class PlannerContext:
         v = C.c_uint32(0)
         _check(lib().kc_planner_path_clearance(self.h, C.byref(v)))
         return v.value
+
+    def shortcut(self, max_span=128):
+        """The any-angle path of rules 9 to 12 over the last path: (cells (k, 2) int32, indices (k,) int32 into
+        path(), min_clear2).  From each kept cell the farthest of the next max_span cells in line of sight is kept;
+        min_clear2 is the smallest clear2 the kept segments touch (PLAN_CLEAR_FAR with the clearance cost off)."""
+        n, v = _sz(0), C.c_uint32(0)
+        _check(lib().kc_planner_shortcut(self.h, int(max_span), C.byref(n), C.byref(v)))
+        cells, idx = np.empty((n.value, 2), np.int32), np.empty(n.value, np.int32)
+        _check(lib().kc_planner_get_shortcut(self.h, cells.ctypes.data, idx.ctypes.data, n.value, C.byref(n)))
+        return cells, idx, v.value

@@ -5,8 +5,11 @@ device-resident grid and from a host array; the path walk on its own; and the on
 Dijkstra of tests/planner_ref.py.  Warm-up, then --reps repetitions: median and min .. max, the device named.
 --clearance REACH_CELLS,WEIGHT10 adds a leg with the clearance cost on (rules 6 to 8): C2 = (sqrt(R2) + REACH_CELLS)^2,
 the table of tests/planner_clearance_ref.py; the solve with the clearance pass, the field alone, the walk, the passes.
+--shortcut W adds the any-angle path (rules 9 to 12) of span W: the walk call and the shortcut call behind it, each
+timed on its own after an untimed solve, the waypoints and the any-angle length against the walk's; with --clearance
+the same on the penalised path.
 
-  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--json out.json]
+  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--shortcut 128] [--json out.json]
   rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
 """
 import argparse
@@ -25,6 +28,7 @@ for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
 import kompass_hip as kh  # noqa: E402
 import planner_clearance_ref as cref  # noqa: E402
 import planner_ref as ref  # noqa: E402
+import planner_shortcut_ref as sref  # noqa: E402
 import synthetic as syn  # noqa: E402
 
 
@@ -37,6 +41,35 @@ def stats_ms(fn, reps, warm=3):
         fn()
         t.append((time.perf_counter() - t0) * 1e3)
     return dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), reps=reps)
+
+
+def shortcut_leg(ctx, start, goal, r2, a):
+    """The walk and the shortcut behind a solve of the resident grid, each call timed on its own."""
+    span = a.shortcut
+    walk_ms, short_ms = [], []
+    for k in range(3 + a.reps):
+        ctx.solve(start, goal, r2)
+        t0 = time.perf_counter()
+        walk = ctx.path()
+        t1 = time.perf_counter()
+        cells, idx, min_clear2 = ctx.shortcut(span)
+        t2 = time.perf_counter()
+        if k >= 3:
+            walk_ms.append((t1 - t0) * 1e3)
+            short_ms.append((t2 - t1) * 1e3)
+    st = lambda t: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), reps=len(t))  # noqa: E731
+    return dict(span=span, walk_ms=st(walk_ms), shortcut_ms=st(short_ms), path_cells=int(len(walk)), waypoints=int(len(idx)),
+                longest_span=int(np.diff(idx).max()) if len(idx) > 1 else 0, walk_length_cells=sref.length_cells(walk),
+                any_angle_length_cells=sref.length_cells(cells), min_clear2=int(min_clear2))
+
+
+def print_shortcut(c, indent):
+    print(f"{indent}shortcut span {c['span']}: {c['path_cells']} path cells -> {c['waypoints']} waypoints (longest span "
+          f"{c['longest_span']}), length {c['walk_length_cells']:.1f} -> {c['any_angle_length_cells']:.1f} cells, smallest touched "
+          f"clear2 {c['min_clear2']}")
+    for k in ("walk_ms", "shortcut_ms"):
+        v = c[k]
+        print(f"{indent}  {k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
 
 
 def device_name():
@@ -84,6 +117,8 @@ def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
         out["cpu_dijkstra_ms"] = stats_ms(lambda: ref.cost_field(valid, goal), a.cpu_reps, warm=0)
         f, v = ctx.field()
         assert (f == ref.cost_field(valid, goal)).all() and (v == valid).all()
+    if a.shortcut:
+        out["shortcut"] = shortcut_leg(ctx, start, goal, r2, a)
     if a.clearance:
         out["clearance"] = clearance_leg(ctx, start, goal, r2, a)
     return out
@@ -111,6 +146,8 @@ def clearance_leg(ctx, start, goal, r2, a):
     out["table_clearance_field_ms"] = stats_ms(with_clearance_pass, a.reps)
     out["resolve_ms"] = stats_ms(lambda: ctx.solve(start, goal, r2), a.reps)   # clear2 and penalty resident: field only
     out["resolve_and_walk_ms"] = stats_ms(walk, a.reps)
+    if a.shortcut:
+        out["shortcut"] = shortcut_leg(ctx, start, goal, r2, a)
     ctx.set_clearance_cost(0)
     return out
 
@@ -120,6 +157,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--cpu-reps", type=int, default=1)
     ap.add_argument("--clearance", default=None, metavar="REACH_CELLS,WEIGHT10")
+    ap.add_argument("--shortcut", type=int, default=0, metavar="W", help="time the any-angle path of span W")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if kh.device_count() < 1:
@@ -152,6 +190,8 @@ def main():
             if k in s:
                 v = s[k]
                 print(f"  {k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+        if "shortcut" in s:
+            print_shortcut(s["shortcut"], "  ")
         c = s.get("clearance")
         if c:
             print(f"  clearance cost C2 {c['c2']}, weight {c['weight10']}: status {c['status']}, cost {c['cost']}, length "
@@ -160,6 +200,8 @@ def main():
             for k in ("table_clearance_field_ms", "resolve_ms", "resolve_and_walk_ms"):
                 v = c[k]
                 print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+            if "shortcut" in c:
+                print_shortcut(c["shortcut"], "    ")
     print(json.dumps(out))
     if a.json:
         Path(a.json).parent.mkdir(parents=True, exist_ok=True)
