@@ -470,21 +470,15 @@ extern "C" {
 int kc_cloud_create(size_t max_bytes, size_t max_bins, int device, kc_cloud **out) {
   if (!out) KC_FAIL(KC_ERR_INVALID, "null argument");
   *out = nullptr;
-  int ndev = 0;
-  KC_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev)
-    KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(device, &stream));
   auto *c = new kc_cloud();
   c->device = device;
+  c->stream = stream;
   auto fail = [&](int rc) {
     kc_cloud_destroy(c);
     return rc;
   };
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    set_error("HIP stream creation failed on device %d", device);
-    return fail(KC_ERR_HIP);
-  }
   int rc;
   if ((rc = c->d_data.reserve(std::max<size_t>(max_bytes, 64))) ||
       (rc = c->d_bins.reserve(std::max<size_t>(max_bins, 16))) ||
@@ -507,26 +501,7 @@ int kc_cloud_create(size_t max_bytes, size_t max_bins, int device, kc_cloud **ou
 
 void kc_cloud_destroy(kc_cloud *c) {
   if (!c) return;
-  hipError_t e = hipSetDevice(c->device);
-  if (c->stream) {
-    e = hipStreamSynchronize(c->stream);
-    e = hipStreamDestroy(c->stream);
-  }
-  (void)e;
-  c->timing.release();
-  c->d_data.release();
-  c->d_bins.release();
-  c->d_list.release();
-  c->d_partial.release();
-  c->d_count.release();
-  c->h_bins.release();
-  c->h_count.release();
-  c->h_out.release();
-  c->h_list.release();
-  c->d_points.release();
-  c->d_extent.release();
-  c->h_extent.release();
-  c->d_grid.release();
+  close_device_stream(c->device, &c->stream);
   delete c;
 }
 
@@ -712,30 +687,6 @@ int kc_cloud_timing_get(kc_cloud *c, const char **names, float *ms, size_t cap,
 
 namespace {
 
-// a cloud passed as "on the device" is read in place: it must be device memory of the context's device and
-// all of its nbytes must lie inside one allocation; anything else is refused before any read
-int check_device_cloud(const kc_cloud *c, const void *data, size_t nbytes) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, data) != hipSuccess) {
-    (void)hipGetLastError();
-    KC_FAIL(KC_ERR_INVALID, "the device cloud %p is not memory HIP knows", data);
-  }
-  if (at.type != hipMemoryTypeDevice)
-    KC_FAIL(KC_ERR_INVALID, "the device cloud is not device memory (HIP memory type %d)", static_cast<int>(at.type));
-  if (at.device != c->device)
-    KC_FAIL(KC_ERR_INVALID, "the device cloud lives on device %d, the context reads device %d", at.device, c->device);
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(data)) != hipSuccess) {
-    (void)hipGetLastError();
-    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device cloud");
-  }
-  const uintptr_t p = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(base);
-  if (p < b || nbytes > size || p - b > size - nbytes)
-    KC_FAIL(KC_ERR_INVALID, "the %zu-byte device cloud runs outside its %zu-byte allocation", nbytes, size);
-  return KC_OK;
-}
-
 unsigned grid_blocks(long long work) {
   return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(kGridMaxBlocks, (work + kGridBlock - 1) / kGridBlock)));
 }
@@ -781,7 +732,8 @@ int kc_cloud_grid_extent(kc_cloud *c, const int8_t *data, size_t nbytes, int dat
   c->timing.begin_cycle();
   const uint8_t *dev = reinterpret_cast<const uint8_t *>(data);
   if (data_on_device) {
-    KC_TRY(check_device_cloud(c, data, nbytes));
+    // read in place: refused before any read unless all of it is this device's memory
+    KC_TRY(check_device_range(c->device, data, 0, static_cast<long long>(nbytes), 1, "cloud"));
   } else {
     KC_TRY(c->d_points.reserve(nbytes));
     KC_HIP(hipMemcpyAsync(c->d_points.p, data, nbytes, hipMemcpyHostToDevice, s));
@@ -885,14 +837,7 @@ int kc_cloud_grid_device(kc_cloud *c, float z_ground_limit, float robot_height, 
 
 int kc_cloud_after_stream(kc_cloud *c, void *stream) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
-  KC_HIP(hipSetDevice(c->device));
-  hipEvent_t e = nullptr;
-  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(stream));
-  if (rc == hipSuccess) rc = hipStreamWaitEvent(c->stream, e, 0);
-  (void)hipEventDestroy(e);  // released once the wait is satisfied
-  KC_HIP(rc);
-  return KC_OK;
+  return stream_wait_for(c->device, c->stream, stream);
 }
 
 }  // extern "C"

@@ -109,7 +109,7 @@ struct kc_comm {
   size_t shm_bytes = 0;
   long long shm_seq = 0;
   int shm_timeout_ms = 20000;
-  long long *h_stage = nullptr;  // pinned, 2 x kShmMaxWords
+  PinBuf<long long> h_stage;  // 2 x kShmMaxWords
 };
 
 #define KC_NCCL(expr)                                                              \
@@ -135,7 +135,7 @@ inline ShmRank *shm_rank(kc_comm *m, int r) {
 int shm_allreduce(kc_comm *m, const long long *send_dev, long long *recv_dev, size_t count, bool sum,
                   hipStream_t stream) {
   if (count > kShmMaxWords) KC_FAIL(KC_ERR_RANGE, "shm transport: %zu words exceed %zu", count, kShmMaxWords);
-  long long *mine = m->h_stage, *out = m->h_stage + kShmMaxWords;
+  long long *mine = m->h_stage.p, *out = m->h_stage.p + kShmMaxWords;
   KC_HIP(hipMemcpyAsync(mine, send_dev, count * sizeof(long long), hipMemcpyDeviceToHost, stream));
   KC_HIP(hipStreamSynchronize(stream));
   const long long seq = ++m->shm_seq;
@@ -323,13 +323,10 @@ int kc_comm_create_shm(int rank, int world, const char *name, int device, kc_com
     std::this_thread::sleep_for(std::chrono::milliseconds(1));
   }
   if (rank == 0) shm_unlink(m->shm_name.c_str());
-  hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&m->h_stage), 2 * kShmMaxWords * sizeof(long long),
-                               hipHostMallocDefault);
-  if (e != hipSuccess) {
-    set_error("hipHostMalloc failed: %s", hipGetErrorString(e));
+  if (const int rc = m->h_stage.reserve(2 * kShmMaxWords)) {
     munmap(m->shm_base, m->shm_bytes);
     delete m;
-    return KC_ERR_HIP;
+    return rc;
   }
   *out = m;
   return KC_OK;
@@ -342,10 +339,6 @@ void kc_comm_destroy(kc_comm *m) {
     hipError_t e = hipSetDevice(m->device);
     (void)e;
     (void)rccl().CommDestroy(m->comm);
-  }
-  if (m->h_stage) {
-    hipError_t e = hipHostFree(m->h_stage);
-    (void)e;
   }
   if (m->shm_base) munmap(m->shm_base, m->shm_bytes);
   delete m;

@@ -12,6 +12,74 @@ void set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
+int open_device_stream(int device, hipStream_t *stream) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess) {
+    (void)hipGetLastError();
+    ndev = 0;
+  }
+  if (device < 0 || device >= ndev) KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(stream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipGetLastError();
+    *stream = nullptr;
+    KC_FAIL(KC_ERR_HIP, "HIP stream creation failed on device %d", device);
+  }
+  return KC_OK;
+}
+
+// Every kc_*_destroy calls this (and ends its other streams and events) BEFORE it deletes the context: the
+// context's DevBuf / PinBuf / Timing members free themselves in its destructor, and nothing queued may still
+// read or write them then.
+void close_device_stream(int device, hipStream_t *stream) {
+  // (a context exists only once its stream is open, so the device is current for whatever its destroy ends next;
+  // kc_depth, which opens lazily, has nothing on the device while it has no stream)
+  if (!*stream) return;
+  hipError_t e = hipSetDevice(device);
+  e = hipStreamSynchronize(*stream);
+  e = hipStreamDestroy(*stream);
+  (void)e;
+  *stream = nullptr;
+}
+
+int stream_wait_for(int device, hipStream_t own, void *other) {
+  KC_HIP(hipSetDevice(device));
+  hipEvent_t e = nullptr;
+  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(other));
+  if (rc == hipSuccess) rc = hipStreamWaitEvent(own, e, 0);
+  (void)hipEventDestroy(e);  // released once the wait is satisfied
+  KC_HIP(rc);
+  return KC_OK;
+}
+
+int check_device_range(int device, const void *ptr, long long lo_bytes, long long hi_bytes, size_t align,
+                       const char *what) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "the device %s %p is not memory HIP knows", what, ptr);
+  }
+  if (at.type != hipMemoryTypeDevice)
+    KC_FAIL(KC_ERR_INVALID, "the device %s is not device memory (HIP memory type %d)", what, static_cast<int>(at.type));
+  if (at.device != device)
+    KC_FAIL(KC_ERR_INVALID, "the device %s lives on device %d, the context reads device %d", what, at.device, device);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) != hipSuccess) {
+    (void)hipGetLastError();
+    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device %s", what);
+  }
+  // offsets from the allocation's base, compared without forming an address: nothing here can wrap
+  const uintptr_t p = reinterpret_cast<uintptr_t>(ptr), b = reinterpret_cast<uintptr_t>(base);
+  const unsigned long long below = 0ull - static_cast<unsigned long long>(lo_bytes);  // |lo_bytes| where lo_bytes <= 0
+  if (lo_bytes > 0 || hi_bytes < 0 || p < b || p - b > size || below > p - b ||
+      static_cast<unsigned long long>(hi_bytes) > size - (p - b))
+    KC_FAIL(KC_ERR_INVALID, "the device %s (bytes %lld to %lld from its pointer) runs outside its %zu-byte allocation", what, lo_bytes,
+            hi_bytes, size);
+  if (align > 1 && p % align) KC_FAIL(KC_ERR_INVALID, "the device %s is not aligned to %zu bytes", what, align);
+  return KC_OK;
+}
+
 }  // namespace kc
 
 extern "C" {

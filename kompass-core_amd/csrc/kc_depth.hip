@@ -314,13 +314,7 @@ namespace {
 
 int depth_ready(kc_depth *c) {
   if (c->stream) return KC_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
-  (void)hipGetLastError();
-  if (c->device < 0 || c->device >= ndev)
-    KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", c->device, ndev);
-  KC_HIP(hipSetDevice(c->device));
-  KC_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  KC_TRY(open_device_stream(c->device, &c->stream));
   c->lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(depth_boxes_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kDepthMaxBins * 2) == hipSuccess;
   if (!c->lds_ok) {
@@ -330,38 +324,21 @@ int depth_ready(kc_depth *c) {
   return KC_OK;
 }
 
-// A frame passed as "on the device" is read by the kernel in place, so it must be device memory of the context's
-// device, and every element of the rows x cols frame must lie inside its allocation; anything else (a host
-// pointer, another GPU's memory, a shape larger than the buffer) is refused here, before any read.
+// A frame passed as "on the device" is read by the kernel in place: every element of the rows x cols frame must
+// lie in device memory of the context's device, inside one allocation; anything else (a host pointer, another
+// GPU's memory, a shape larger than the buffer) is refused here, before any read.
 int check_device_frame(const kc_depth *c, const uint16_t *img, long long rows, long long cols, long long rs,
                        long long cs) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, img) != hipSuccess) {
-    (void)hipGetLastError();
-    KC_FAIL(KC_ERR_INVALID, "the device frame %p is not memory HIP knows", static_cast<const void *>(img));
-  }
-  if (at.type != hipMemoryTypeDevice)
-    KC_FAIL(KC_ERR_INVALID, "the device frame is not device memory (HIP memory type %d)", static_cast<int>(at.type));
-  if (at.device != c->device)
-    KC_FAIL(KC_ERR_INVALID, "the device frame lives on device %d, the detector reads device %d", at.device, c->device);
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, const_cast<uint16_t *>(img)) != hipSuccess) {
-    (void)hipGetLastError();
-    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device frame");
-  }
-  // the lowest and highest element offsets of the frame
+  // the lowest and highest element offsets of the frame, then bytes [2 lo, 2 hi + 2)
   long long lo = 0, hi = 0, t = 0;
   if (__builtin_mul_overflow(rows - 1, rs, &t)) KC_FAIL(KC_ERR_RANGE, "frame row stride out of range");
-  (t < 0 ? lo : hi) += t;
+  (t < 0 ? lo : hi) = t;
   if (__builtin_mul_overflow(cols - 1, cs, &t)) KC_FAIL(KC_ERR_RANGE, "frame column stride out of range");
-  (t < 0 ? lo : hi) += t;
-  const long long first = reinterpret_cast<long long>(img) + 2 * lo, last = reinterpret_cast<long long>(img) + 2 * hi;
-  const long long b0 = reinterpret_cast<long long>(base), b1 = b0 + static_cast<long long>(size);
-  if (first < b0 || last + 2 > b1)
-    KC_FAIL(KC_ERR_INVALID, "the %lld x %lld device frame (strides %lld, %lld) runs outside its %zu-byte allocation",
-            rows, cols, rs, cs, size);
-  return KC_OK;
+  long long &end = t < 0 ? lo : hi;
+  if (__builtin_add_overflow(end, t, &end) || __builtin_mul_overflow(lo, 2ll, &lo) ||
+      __builtin_mul_overflow(hi, 2ll, &hi) || __builtin_add_overflow(hi, 2ll, &hi))
+    KC_FAIL(KC_ERR_RANGE, "frame strides out of range");
+  return check_device_range(c->device, img, lo, hi, 1, "frame");
 }
 
 // The statistics of every box (count = 0 for a box with no pixel in the image).  Box pixels are the inclusive
@@ -537,23 +514,7 @@ int kc_depth_create(const float depth_range[2], const float cam_pos[3], const fl
 
 void kc_depth_destroy(kc_depth *c) {
   if (!c) return;
-  if (c->stream) {
-    hipError_t e = hipSetDevice(c->device);
-    e = hipStreamSynchronize(c->stream);
-    e = hipStreamDestroy(c->stream);
-    (void)e;
-  }
-  c->timing.release();
-  c->d_img.release();
-  c->d_boxes.release();
-  c->d_work.release();
-  c->d_hist.release();
-  c->d_count.release();
-  c->d_out.release();
-  c->h_boxes.release();
-  c->h_work.release();
-  c->h_out.release();
-  c->h_img.release();
+  close_device_stream(c->device, &c->stream);
   delete c;
 }
 
@@ -610,14 +571,7 @@ int kc_depth_boxes(kc_depth *c, const uint16_t *img, int data_on_device, int64_t
 int kc_depth_after_stream(kc_depth *c, void *stream) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   KC_TRY(depth_ready(c));
-  KC_HIP(hipSetDevice(c->device));
-  hipEvent_t e = nullptr;
-  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(stream));
-  if (rc == hipSuccess) rc = hipStreamWaitEvent(c->stream, e, 0);
-  (void)hipEventDestroy(e);  // released once the wait is satisfied
-  KC_HIP(rc);
-  return KC_OK;
+  return stream_wait_for(c->device, c->stream, stream);
 }
 
 int kc_depth_last_upload(kc_depth *c, size_t *bytes_out) {

@@ -191,22 +191,16 @@ int kc_dvz_create(int device, size_t max_beams, kc_dvz **out) {
   *out = nullptr;
   if (max_beams == 0) KC_FAIL(KC_ERR_INVALID, "max_beams must be at least 1");
   if (max_beams > kDvzMaxBeams) KC_FAIL(KC_ERR_RANGE, "max_beams %zu above %zu", max_beams, kDvzMaxBeams);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess) ndev = 0;
-  if (device < 0 || device >= ndev)
-    KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(device, &stream));
   auto *z = new kc_dvz();
   z->device = device;
+  z->stream = stream;
   z->cap = max_beams;
   auto fail = [&](int rc) {
     kc_dvz_destroy(z);
     return rc;
   };
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking) != hipSuccess) {
-    set_error("HIP stream creation failed on device %d", device);
-    return fail(KC_ERR_HIP);
-  }
   const size_t blocks = (max_beams + kDvzBlock - 1) / kDvzBlock;
   int rc;
   if ((rc = z->d_angles.reserve(max_beams)) || (rc = z->d_ranges.reserve(max_beams)) ||
@@ -226,24 +220,7 @@ int kc_dvz_create(int device, size_t max_beams, kc_dvz **out) {
 
 void kc_dvz_destroy(kc_dvz *z) {
   if (!z) return;
-  hipError_t e = hipSetDevice(z->device);
-  if (z->stream) {
-    e = hipStreamSynchronize(z->stream);
-    e = hipStreamDestroy(z->stream);
-  }
-  (void)e;
-  z->d_angles.release();
-  z->d_ranges.release();
-  z->d_radii.release();
-  z->d_partial.release();
-  z->d_result.release();
-  z->d_tab.release();
-  z->d_trig.release();
-  z->d_ticket.release();
-  z->h_in.release();
-  z->h_radii.release();
-  z->h_result.release();
-  z->h_trig.release();
+  close_device_stream(z->device, &z->stream);
   delete z;
 }
 

@@ -421,12 +421,10 @@ int kc_dwa_create(const kc_dwa_params *p, kc_dwa **out) {
     KC_FAIL(KC_ERR_INVALID, "max_samples >= 1 and max_points >= 2 required");
   if (p->max_samples > 0x7FFFFFFFu / std::max<size_t>(p->max_points, 1))
     KC_FAIL(KC_ERR_RANGE, "max_samples * max_points exceeds 2^31");
-  int ndev = 0;
-  KC_HIP(hipGetDeviceCount(&ndev));
-  if (p->device < 0 || p->device >= ndev)
-    KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", p->device,
-            ndev);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(p->device, &stream));
   auto *c = new kc_dwa();
+  c->stream = c->own_stream = stream;
   c->prm = *p;
   for (int i = p->ndims; i < 3; ++i) c->prm.dims[i] = 0.0f;
   // collision_check.cpp:38-58
@@ -452,16 +450,6 @@ int kc_dwa_create(const kc_dwa_params *p, kc_dwa **out) {
     kc_dwa_destroy(c);
     return rc;
   };
-  if (hipSetDevice(p->device) != hipSuccess) {
-    set_error("hipSetDevice(%d) failed", p->device);
-    return fail(KC_ERR_HIP);
-  }
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) !=
-      hipSuccess) {
-    set_error("hipStreamCreate failed");
-    return fail(KC_ERR_HIP);
-  }
-  c->stream = c->own_stream;
   (void)WorkerPool::instance();  // start the host workers now, not inside the first cycle
   int rc;
   if ((rc = c->h_pub.reserve(8)) ||
@@ -509,8 +497,9 @@ int kc_dwa_create(const kc_dwa_params *p, kc_dwa **out) {
   return KC_OK;
 }
 
-void kc_dwa_destroy(kc_dwa *c) {
-  if (!c) return;
+// The diagnostics a context prints when it goes: the KC_DEBUG_HOST summary of the host side of its cycles and the
+// KC_DEBUG_STAMPS tables of the last cycle's kernels (nothing without those variables).
+static void dump_diagnostics(kc_dwa *c) {
   if (c->hprof.on && c->hprof.n) {
     const char *nm[8] = {"", "entry -> launch call", "launch call", "wait for the trig pool", "flag store", "back in kc_dwa_cycle", "wait for the slots", "fetch (slots + reduce + row)"};
     std::fprintf(stderr, "[kc host] %ld single-launch cycles, us per cycle:\n", c->hprof.n);
@@ -609,108 +598,24 @@ void kc_dwa_destroy(kc_dwa *c) {
       std::fprintf(stderr, "  %-14s %7.2f / %7.2f\n", nm[k], nb ? sm[k] / nb : 0.0, mx[k]);
     }
   }
-  if (c->own_stream) {
-    e = hipStreamSynchronize(c->own_stream);
-    e = hipStreamDestroy(c->own_stream);
-  }
   (void)e;
-  c->timing.release();
-  c->pp.release();
-  c->d_vxt.release();
-  c->d_vyt.release();
-  c->d_vidx.release();
-  c->d_pvi.release();
-  c->d_cpvi.release();
-  c->d_row.release();
-  c->h_trig.release();
-  c->d_trig.release();
-  c->h_bits.release();
-  c->d_bits.release();
-  c->h_ddz.release();
-  c->d_ddz.release();
-  c->d_px.release();
-  c->d_py.release();
-  c->d_costs.release();
-  c->d_flags.release();
-  c->d_dbg.release();
-  c->d_dbg2.release();
-  c->d_raw.release();
-  c->d_sensor_tmp.release();
-  c->d_sensor_bytes.release();
-  c->d_vsum.release();
-  c->d_gridcnt.release();
-  c->h_gridrec.release();
+}
+
+void kc_dwa_destroy(kc_dwa *c) {
+  if (!c) return;
+  dump_diagnostics(c);
+  close_device_stream(c->prm.device, &c->own_stream);
   if (c->aux_stream) {
-    hipError_t ae = hipStreamSynchronize(c->aux_stream);
-    ae = hipStreamDestroy(c->aux_stream);
-    ae = hipEventDestroy(c->aux_fork);
-    ae = hipEventDestroy(c->aux_join);
-    (void)ae;
+    hipError_t e = hipStreamSynchronize(c->aux_stream);
+    e = hipStreamDestroy(c->aux_stream);
+    e = hipEventDestroy(c->aux_fork);
+    e = hipEventDestroy(c->aux_join);
+    (void)e;
   }
   if (c->grid_ready) {
-    hipError_t ge = hipEventDestroy(c->grid_ready);
-    (void)ge;
+    hipError_t e = hipEventDestroy(c->grid_ready);
+    (void)e;
   }
-  c->d_perm.release();
-  c->d_prow.release();
-  c->d_vvx.release();
-  c->d_vvy.release();
-  c->d_vom.release();
-  c->h_seg.release();
-  c->d_seg.release();
-  c->d_near.release();
-  c->d_bbox.release();
-  c->d_path.release();
-  c->h_obs.release();
-  c->h_cells.release();
-  c->d_cells.release();
-  c->h_bobs.release();
-  c->d_bobs.release();
-  c->h_skip.release();
-  c->d_skip.release();
-  c->h_gbits.release();
-  c->h_gz.release();
-  c->d_gz.release();
-  c->h_zlut.release();
-  c->d_zlut.release();
-  c->d_block_keys.release();
-  c->d_gbits.release();
-  c->d_ginner.release();
-  c->d_gouter.release();
-  c->d_adm.release();
-  c->d_pos.release();
-  c->d_result.release();
-  c->h_result.release();
-  c->h_pub.release();
-  c->h_row.release();
-  c->d_adm_bits.release();
-  c->d_cperm.release();
-  c->d_cprow.release();
-  for (auto &t : c->patterns) {
-    t.vidx.release();
-    t.pvi.release();
-    t.cpvi.release();
-    t.row.release();
-    t.perm.release();
-    t.prow.release();
-    t.cperm.release();
-    t.cprow.release();
-  }
-  c->patterns.clear();
-  c->h_wrow.release();
-  c->h_slots.release();
-  c->d_oscan.release();
-  c->d_onear.release();
-  c->d_freeze.release();
-  c->d_first_hit.release();
-  c->d_frz.release();
-  c->d_omega.release();
-  c->d_sincostab.release();
-  c->d_gid.release();
-  c->d_xs.release();
-  c->d_xr.release();
-  c->h_xvec.release();
-  c->h_xrec.release();
   delete c;
 }
 

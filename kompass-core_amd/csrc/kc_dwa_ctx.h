@@ -177,6 +177,7 @@ struct kc_dwa {
     size_t perm_first = 0, perm_count = 0;
     int perm_cs = 0;
   };
+  static_assert(std::is_nothrow_move_constructible<PatternTables>::value, "`patterns` grows by moving its slots");
   std::vector<PatternTables> patterns;  // (inactive ones; the active pattern lives in the members above / below)
   uint64_t pattern_clock = 0;
   long pattern_hits = 0, pattern_builds = 0;
@@ -370,14 +371,6 @@ struct kc_dwa {
     DevBuf<unsigned long long> d_slots;    // [3]
     PinBuf<unsigned long long> h_slots;
     uint32_t epoch = 0;
-    void release() {
-      d_cand.release();
-      h_cand.release();
-      d_trig.release();
-      h_trig.release();
-      d_slots.release();
-      h_slots.release();
-    }
   } pp;
 };
 

@@ -9,6 +9,8 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "kompass_hip.h"
@@ -40,65 +42,73 @@ void set_error(const char *fmt, ...);
     if (_rc != KC_OK) return _rc; \
   } while (0)
 
-// ---- grow-only device buffer (reference grows its buffers the same way:
-// cost_evaluator_gpu.cpp:248-271, 314-333) ----------------------------------
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-  int reserve(size_t n) {
-    if (n <= cap) return KC_OK;
-    if (p) {
-      hipError_t e = hipFree(p);
-      (void)e;
-      p = nullptr;
-      cap = 0;
-    }
-    size_t want = n + n / 4 + 16;
-    KC_HIP(hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T)));
-    cap = want;
-    return KC_OK;
-  }
-  void release() {
-    if (p) {
-      hipError_t e = hipFree(p);
-      (void)e;
-    }
-    p = nullptr;
-    cap = 0;
-  }
+// ---- grow-only buffers that own their memory ---------------------------------
+// (the reference grows its buffers the same way: cost_evaluator_gpu.cpp:248-271, 314-333).  Move-only: the
+// destructor frees, a moved-from buffer is empty.  HIP errors of a free are ignored.
+struct DevAlloc {
+  static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+  static hipError_t free(void *p) { return hipFree(p); }
+};
+// pinned host memory (async H2D / D2H without a hidden sync)
+struct PinAlloc {
+  static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static hipError_t free(void *p) { return hipHostFree(p); }
 };
 
-// pinned host staging buffer (async H2D / D2H without a hidden sync)
-template <typename T>
-struct PinBuf {
+template <typename T, typename Alloc>
+struct OwnedBuf {
   T *p = nullptr;
   size_t cap = 0;
+  OwnedBuf() = default;
+  OwnedBuf(const OwnedBuf &) = delete;
+  OwnedBuf &operator=(const OwnedBuf &) = delete;
+  OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), cap(o.cap) {
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      cap = o.cap;
+      o.p = nullptr;
+      o.cap = 0;
+    }
+    return *this;
+  }
+  ~OwnedBuf() { release(); }
   int reserve(size_t n) {
     if (n <= cap) return KC_OK;
-    if (p) {
-      hipError_t e = hipHostFree(p);
-      (void)e;
-      p = nullptr;
-      cap = 0;
-    }
+    release();
     size_t want = n + n / 4 + 16;
-    KC_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), want * sizeof(T),
-                         hipHostMallocDefault));
+    KC_HIP(Alloc::alloc(reinterpret_cast<void **>(&p), want * sizeof(T)));
     cap = want;
     return KC_OK;
   }
   void release() {
     if (p) {
-      hipError_t e = hipHostFree(p);
+      hipError_t e = Alloc::free(p);
       (void)e;
     }
     p = nullptr;
     cap = 0;
   }
 };
+template <typename T>
+using DevBuf = OwnedBuf<T, DevAlloc>;
+template <typename T>
+using PinBuf = OwnedBuf<T, PinAlloc>;
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value && !std::is_copy_assignable<DevBuf<int>>::value &&
+                  std::is_nothrow_move_constructible<DevBuf<int>>::value &&
+                  std::is_nothrow_move_assignable<DevBuf<int>>::value,
+              "DevBuf owns device memory: move-only, and a std::vector of it grows by move");
+static_assert(!std::is_copy_constructible<PinBuf<int>>::value && !std::is_copy_assignable<PinBuf<int>>::value &&
+                  std::is_nothrow_move_constructible<PinBuf<int>>::value &&
+                  std::is_nothrow_move_assignable<PinBuf<int>>::value,
+              "PinBuf owns pinned memory: move-only, and a std::vector of it grows by move");
 
 // ---- per-kernel HIP-event timing on the launch stream ----------------------
+// (owns its events: move-only, the destructor destroys them)
 struct Timing {
   bool enabled = false;
   struct Rec {
@@ -114,6 +124,24 @@ struct Timing {
   };
   std::vector<HostRec> host;
   std::chrono::steady_clock::time_point t_mark;
+  Timing() = default;
+  Timing(const Timing &) = delete;
+  Timing &operator=(const Timing &) = delete;
+  Timing(Timing &&o) noexcept { *this = std::move(o); }
+  Timing &operator=(Timing &&o) noexcept {
+    if (this != &o) {
+      release();
+      enabled = o.enabled;
+      pool.swap(o.pool);  // (ours is empty after release)
+      used = o.used;
+      host.swap(o.host);
+      t_mark = o.t_mark;
+      o.used = 0;
+      o.host.clear();
+    }
+    return *this;
+  }
+  ~Timing() { release(); }
   void begin_cycle() {
     used = 0;
     host.clear();
@@ -172,6 +200,22 @@ struct Timing {
     used = 0;
   }
 };
+static_assert(!std::is_copy_constructible<Timing>::value && std::is_nothrow_move_constructible<Timing>::value,
+              "Timing owns its events: move-only");
+
+// ---- plumbing every device context shares (kc_common.hip) -------------------
+// Opens a context: `device` must be a visible HIP device (a failing device count is "0 visible": KC_ERR_HIP);
+// makes it current and creates the context's own non-blocking stream.
+int open_device_stream(int device, hipStream_t *stream);
+// Closes it (no-op for a stream never opened): device current, stream synchronised and destroyed.
+void close_device_stream(int device, hipStream_t *stream);
+// `own` waits for everything queued on `other` so far (a foreign stream of the same process)
+int stream_wait_for(int device, hipStream_t own, void *other);
+// Memory a caller passes as "on the device" is read by kernels in place: [ptr + lo_bytes, ptr + hi_bytes) must
+// lie inside one allocation of `device`'s memory and ptr % align == 0.  KC_ERR_INVALID otherwise, with `what`
+// (the noun: "cloud", "grid", "frame") in the message, and before any read.
+int check_device_range(int device, const void *ptr, long long lo_bytes, long long hi_bytes, size_t align,
+                       const char *what);
 
 // ---- correctly rounded f32 divide / sqrt on the device ----------------------
 // HIP's __fsqrt_rn lowers to the *native* (approximate) sqrt unless

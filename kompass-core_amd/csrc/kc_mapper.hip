@@ -807,13 +807,11 @@ int kc_mapper_create(int H, int W, float res, const float pos[3], float orient,
   // end cell of a beam, so every line of the walk has fewer than 2^31 steps
   if (!(std::fabs(pos[0] / res) < kMaxCellOffset && std::fabs(pos[1] / res) < kMaxCellOffset))
     KC_FAIL(KC_ERR_RANGE, "sensor position not below 2^30 cells from the grid centre");
-  int ndev = 0;
-  KC_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev)
-    KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device,
-            ndev);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(device, &stream));
   auto *m = new kc_mapper();
   m->device = device;
+  m->stream = m->own_stream = stream;
   m->orient = orient;
   m->g.H = H;
   m->g.W = W;
@@ -829,13 +827,6 @@ int kc_mapper_create(int H, int W, float res, const float pos[3], float orient,
     kc_mapper_destroy(m);
     return rc;
   };
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) !=
-          hipSuccess) {
-    set_error("HIP stream creation failed on device %d", device);
-    return fail(KC_ERR_HIP);
-  }
-  m->stream = m->own_stream;
   const size_t cells = static_cast<size_t>(H) * W;
   int rc;
   if ((rc = m->d_grid.reserve(cells)) || (rc = m->d_grid_alt.reserve(cells)) || (rc = m->h_grid.reserve(cells)) ||
@@ -863,28 +854,7 @@ int kc_mapper_create(int H, int W, float res, const float pos[3], float orient,
 
 void kc_mapper_destroy(kc_mapper *m) {
   if (!m) return;
-  hipError_t e = hipSetDevice(m->device);
-  if (m->own_stream) {
-    e = hipStreamSynchronize(m->own_stream);
-    e = hipStreamDestroy(m->own_stream);
-  }
-  (void)e;
-  m->timing.release();
-  m->d_grid.release();
-  m->d_grid_alt.release();
-  m->d_prob.release();
-  m->d_prev.release();
-  m->d_prev_tmp.release();
-  m->d_last.release();
-  m->h_prob.release();
-  m->d_ranges.release();
-  m->d_trig.release();
-  m->d_ticket.release();
-  m->d_ends.release();
-  m->h_seq.release();
-  m->h_ranges.release();
-  m->h_trig.release();
-  m->h_grid.release();
+  close_device_stream(m->device, &m->own_stream);
   delete m;
 }
 

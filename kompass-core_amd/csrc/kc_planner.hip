@@ -422,31 +422,6 @@ unsigned plan_blocks_for(long long work) {
   return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(kPlanMaxBlocks, (work + kPlanBlock - 1) / kPlanBlock)));
 }
 
-// a grid passed as "on the device" is read in place: device memory of the context's device, all of it inside
-// one allocation, aligned to its element; refused before any read otherwise (as kc_cloud_grid_extent does)
-int check_device_grid(const kc_planner *c, const void *data, size_t nbytes, int elem_bytes) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, data) != hipSuccess) {
-    (void)hipGetLastError();
-    KC_FAIL(KC_ERR_INVALID, "the device grid %p is not memory HIP knows", data);
-  }
-  if (at.type != hipMemoryTypeDevice)
-    KC_FAIL(KC_ERR_INVALID, "the device grid is not device memory (HIP memory type %d)", static_cast<int>(at.type));
-  if (at.device != c->device)
-    KC_FAIL(KC_ERR_INVALID, "the device grid lives on device %d, the context reads device %d", at.device, c->device);
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(data)) != hipSuccess) {
-    (void)hipGetLastError();
-    KC_FAIL(KC_ERR_INVALID, "no allocation holds the device grid");
-  }
-  const uintptr_t p = reinterpret_cast<uintptr_t>(data), b = reinterpret_cast<uintptr_t>(base);
-  if (p < b || nbytes > size || p - b > size - nbytes)
-    KC_FAIL(KC_ERR_INVALID, "the %zu-byte device grid runs outside its %zu-byte allocation", nbytes, size);
-  if (p % static_cast<uintptr_t>(elem_bytes)) KC_FAIL(KC_ERR_INVALID, "the device grid is not aligned to its %d-byte cells", elem_bytes);
-  return KC_OK;
-}
-
 int check_grid_shape(const void *grid, int elem_bytes, int width, int height) {
   if (!grid) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (elem_bytes != 1 && elem_bytes != 4) KC_FAIL(KC_ERR_INVALID, "grid cells are int8 (1) or int32 (4) bytes, got %d", elem_bytes);
@@ -546,16 +521,11 @@ extern "C" {
 int kc_planner_create(int device, kc_planner **out) {
   if (!out) KC_FAIL(KC_ERR_INVALID, "null argument");
   *out = nullptr;
-  int ndev = 0;
-  KC_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(device, &stream));
   auto *c = new kc_planner();
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    set_error("HIP stream creation failed on device %d", device);
-    kc_planner_destroy(c);
-    return KC_ERR_HIP;
-  }
+  c->stream = stream;
   int rc;
   if ((rc = c->d_word.reserve(8)) || (rc = c->h_word.reserve(12))) {
     kc_planner_destroy(c);
@@ -567,27 +537,7 @@ int kc_planner_create(int device, kc_planner **out) {
 
 void kc_planner_destroy(kc_planner *c) {
   if (!c) return;
-  hipError_t e = hipSetDevice(c->device);
-  if (c->stream) {
-    e = hipStreamSynchronize(c->stream);
-    e = hipStreamDestroy(c->stream);
-  }
-  (void)e;
-  c->d_stage.release();
-  c->d_cls.release();
-  c->d_rowd.release();
-  c->d_valid.release();
-  c->d_pen_by_d2.release();
-  c->d_pen.release();
-  c->d_clear2.release();
-  c->d_field[0].release();
-  c->d_field[1].release();
-  c->d_word.release();
-  c->h_word.release();
-  c->d_path.release();
-  c->h_path.release();
-  c->d_keep.release();
-  c->h_keep.release();
+  close_device_stream(c->device, &c->stream);
   delete c;
 }
 
@@ -606,20 +556,14 @@ int kc_planner_set_grid_device(kc_planner *c, const void *dev_grid, int elem_byt
   KC_TRY(check_grid_shape(dev_grid, elem_bytes, width, height));
   KC_HIP(hipSetDevice(c->device));
   const size_t nbytes = static_cast<size_t>(width) * static_cast<size_t>(height) * static_cast<size_t>(elem_bytes);
-  KC_TRY(check_device_grid(c, dev_grid, nbytes, elem_bytes));
+  // read in place: refused before any read unless all of it is this device's memory, aligned to its cells
+  KC_TRY(check_device_range(c->device, dev_grid, 0, static_cast<long long>(nbytes), static_cast<size_t>(elem_bytes), "grid"));
   return planner_take_grid(c, dev_grid, elem_bytes, width, height);
 }
 
 int kc_planner_after_stream(kc_planner *c, void *stream) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
-  KC_HIP(hipSetDevice(c->device));
-  hipEvent_t e = nullptr;
-  KC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipError_t rc = hipEventRecord(e, static_cast<hipStream_t>(stream));
-  if (rc == hipSuccess) rc = hipStreamWaitEvent(c->stream, e, 0);
-  (void)hipEventDestroy(e);  // released once the wait is satisfied
-  KC_HIP(rc);
-  return KC_OK;
+  return stream_wait_for(c->device, c->stream, stream);
 }
 
 int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell[2], uint32_t r2, int allow_unknown,

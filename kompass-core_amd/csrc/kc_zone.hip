@@ -104,12 +104,11 @@ int kc_zone_create(int shape, const float *dims, int ndims, const float sensor_p
   } else {
     KC_FAIL(KC_ERR_INVALID, "Invalid robot geometry type");
   }
-  int ndev = 0;
-  KC_HIP(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev)
-    KC_FAIL(KC_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(device, &stream));
   auto *z = new kc_zone();
   z->device = device;
+  z->stream = stream;
   z->n = n;
   z->robot_radius = radius;
   z->min_height = min_height;
@@ -141,11 +140,6 @@ int kc_zone_create(int shape, const float *dims, int ndims, const float sensor_p
     if (static_cast<double>(abs_theta) >= M_PI - static_cast<double>(crit))
       z->bwd.push_back(static_cast<int>(i));
   }
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking) != hipSuccess) {
-    set_error("HIP stream creation failed on device %d", device);
-    return fail(KC_ERR_HIP);
-  }
   const size_t m = std::max<size_t>(n, 1);
   int rc;
   if ((rc = z->d_cos.reserve(m)) || (rc = z->d_sin.reserve(m)) || (rc = z->d_fwd.reserve(m)) ||
@@ -169,21 +163,8 @@ int kc_zone_create(int shape, const float *dims, int ndims, const float sensor_p
 
 void kc_zone_destroy(kc_zone *z) {
   if (!z) return;
-  hipError_t e = hipSetDevice(z->device);
-  if (z->stream) {
-    e = hipStreamSynchronize(z->stream);
-    e = hipStreamDestroy(z->stream);
-  }
-  (void)e;
-  if (z->cloud) kc_cloud_destroy(z->cloud);
-  z->d_cos.release();
-  z->d_sin.release();
-  z->d_fwd.release();
-  z->d_bwd.release();
-  z->d_ranges.release();
-  z->d_factor.release();
-  z->h_ranges.release();
-  z->h_factor.release();
+  close_device_stream(z->device, &z->stream);
+  kc_cloud_destroy(z->cloud);
   delete z;
 }
 

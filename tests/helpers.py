@@ -2,6 +2,9 @@
 CPU oracle and through the HIP C ABI on identical inputs."""
 from __future__ import annotations
 
+import ctypes
+import re
+
 import numpy as np
 
 from oracle import ko
@@ -103,3 +106,48 @@ def assert_cycle_equal(o, h):
         bx, by, bv = h["best"]
         np.testing.assert_array_equal(bx, o["px"][o["index"]])
         np.testing.assert_array_equal(by, o["py"][o["index"]])
+
+
+def hip_runtime():
+    """The HIP runtime the library has loaded, for device memory of a test's own."""
+    import kompass_hip as kh
+
+    kh.lib()
+    with open("/proc/self/maps") as f:
+        m = re.search(r"(/\S*libamdhip64\.so[.\d]*)", f.read())
+    hip = ctypes.CDLL(m.group(1) if m else "libamdhip64.so")
+    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    hip.hipFree.argtypes = [ctypes.c_void_p]
+    return hip
+
+
+class DeviceArray:
+    """A device copy of a numpy array's bytes in its own memory order (C or Fortran; anything else is made C
+    first), made with the HIP runtime directly: memory this library did not produce.  `ptr`, `nbytes`, `free()`;
+    a context manager."""
+
+    def __init__(self, host):
+        self.hip = hip_runtime()
+        host = np.asarray(host)
+        if not (host.flags.c_contiguous or host.flags.f_contiguous):
+            host = np.ascontiguousarray(host)
+        self.nbytes = host.nbytes
+        self.p = ctypes.c_void_p()
+        assert self.hip.hipMalloc(ctypes.byref(self.p), max(self.nbytes, 1)) == 0
+        assert self.hip.hipMemcpy(self.p, host.ctypes.data_as(ctypes.c_void_p), self.nbytes, 1) == 0  # host to device
+
+    @property
+    def ptr(self):
+        return self.p.value
+
+    def free(self):
+        if self.p:
+            self.hip.hipFree(self.p)
+            self.p = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()

@@ -3,7 +3,6 @@ centre and size float, the kept-index list, and the five per-box statistics of k
 
 golden/bag_image_depth.npz (key "depth") is the reference's test frame tests/resources/control/bag_image_depth.tif,
 a real 1280x720 uint16 depth frame in mm, converted once to npz (data only)."""
-import ctypes
 import math
 from pathlib import Path
 
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 from depth_detector_ref import Detector, box_from_pois
+from helpers import DeviceArray
 
 pytestmark = pytest.mark.gpu
 
@@ -139,25 +139,11 @@ def test_memory_orders_and_views():
         check(ctx, det, img, bx, state=(1.0, 2.0, 0.5))
 
 
-class DeviceFrame:
-    """A device copy of a host frame in the given memory order, made with the HIP runtime directly (a buffer
-    this library did not produce)."""
-
-    def __init__(self, host, order="C"):
-        self.hip = ctypes.CDLL("libamdhip64.so")
-        self.hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-        self.hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        self.hip.hipFree.argtypes = [ctypes.c_void_p]
-        a = np.ascontiguousarray(host) if order == "C" else np.asfortranarray(host)
-        self.p = ctypes.c_void_p()
-        assert self.hip.hipMalloc(ctypes.byref(self.p), a.nbytes) == 0
-        assert self.hip.hipMemcpy(self.p, a.ctypes.data_as(ctypes.c_void_p), a.nbytes, 1) == 0
-        self.frame = dict(device_ptr=self.p.value, shape=a.shape, strides=[v // 2 for v in a.strides])
-
-    def free(self):
-        if self.p:
-            self.hip.hipFree(self.p)
-            self.p = ctypes.c_void_p()
+def device_frame(host, order="C"):
+    """A device copy of a host frame in the given memory order, and the keywords that describe it."""
+    a = np.ascontiguousarray(host) if order == "C" else np.asfortranarray(host)
+    dev = DeviceArray(a)
+    return dev, dict(device_ptr=dev.ptr, shape=a.shape, strides=[v // 2 for v in a.strides])
 
 
 def test_device_resident_frame():
@@ -165,12 +151,10 @@ def test_device_resident_frame():
     ctx, det = pair((0.1, 10.0), 1e-3)
     boxes = edge_boxes(*img.shape) + [(100, 50, 300, 200)]
     for order in ("C", "F"):
-        dev = DeviceFrame(img, order)
-        try:
-            check(ctx, det, None, boxes, state=(3.0, 4.0, -1.0), host=img, **dev.frame)
+        dev, frame = device_frame(img, order)
+        with dev:
+            check(ctx, det, None, boxes, state=(3.0, 4.0, -1.0), host=img, **frame)
             assert ctx.last_upload() == 0
-        finally:
-            dev.free()
 
 
 def test_states_mount_and_repeated_calls():

@@ -4,8 +4,6 @@ The OCCUPIED cells of a device-resident LocalMapper grid become the controller's
 sensor data without a host round trip.  Expected result: the oracle's point-list
 cycle on the list a host would have extracted from the same grid.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -15,35 +13,11 @@ import kompass_hip as kh  # noqa: E402
 import synthetic as syn  # noqa: E402
 from oracle import ko  # noqa: E402
 
-from helpers import assert_cycle_equal, hip_context, oracle_cycle  # noqa: E402
+from helpers import DeviceArray, assert_cycle_equal, hip_context, oracle_cycle  # noqa: E402
 
 
 def _central(H, W):
     return int(round(H // 2)) - 1, int(round(W // 2)) - 1   # local_mapper.h:26-27
-
-
-class _DeviceArray:
-    """A device copy of a host array, made with the HIP runtime directly (a grid
-    this library did not produce)."""
-
-    def __init__(self, host):
-        self.hip = C.CDLL("libamdhip64.so")
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        host = np.ascontiguousarray(host)
-        self.p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.p), host.nbytes) == 0
-        assert self.hip.hipMemcpy(self.p, host.ctypes.data_as(C.c_void_p), host.nbytes, 1) == 0
-
-    @property
-    def ptr(self):
-        return self.p.value
-
-    def free(self):
-        if self.p:
-            self.hip.hipFree(self.p)
-            self.p = C.c_void_p()
 
 
 def _points_from_grid(grid, res):
@@ -122,7 +96,7 @@ def test_foreign_grid_on_device(shape, dims, density):
     assert len(o["raw"]) > 0
     assert (len(inp["points"]) > 16384) == (density > 0.1)
     ctx = hip_context(kh, inp)
-    dev = _DeviceArray(grid.T.copy().reshape(-1))                                  # i + j*H
+    dev = DeviceArray(grid.T.copy().reshape(-1))                                  # i + j*H
     ctx.set_grid_device(inp["state"], dev.ptr, H, W, res, max_sensor_range=inp["max_range"])
     assert_cycle_equal(o, _cycle_from_ctx(ctx, inp))
     # pose batch on the same sensor state walks the host lists (fetched lazily from the device list)
@@ -137,7 +111,7 @@ def test_empty_grid_and_errors():
     inp = syn.make_controller_inputs("cfg1", seed=1, scale=1.0)
     H = W = 64
     ctx = hip_context(kh, inp)
-    dev = _DeviceArray(np.full(H * W, -1, np.int32))
+    dev = DeviceArray(np.full(H * W, -1, np.int32))
     ctx.set_grid_device(inp["state"], dev.ptr, H, W, 0.1, max_sensor_range=inp["max_range"])
     inp["points"] = np.zeros((0, 3), np.float32)
     o = oracle_cycle(inp)

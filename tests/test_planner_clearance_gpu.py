@@ -6,8 +6,6 @@ device-resident grids, and the class and the front end on the doorway scene.
 
 Every test runs under the time limit of test_planner_gpu.py, for its reason: a solve that went wrong would run to
 its pass cap, and only the thread method ends a native call."""
-import ctypes as C
-import re
 
 import numpy as np
 import pytest
@@ -20,6 +18,7 @@ import kompass_cpp  # noqa: E402
 import kompass_hip as kh  # noqa: E402
 import planner_clearance_ref as cref  # noqa: E402
 import planner_ref as ref  # noqa: E402
+from helpers import DeviceArray  # noqa: E402
 from test_planner_gpu import connected_pair, free_cells  # noqa: E402
 
 
@@ -206,14 +205,6 @@ def test_range(ctx):
     assert ctx.solve((0, 0), (63, 63))[:2] == (ref.FOUND, 63 * 14)   # a refused table leaves the one before
 
 
-def _hip_runtime():
-    """The HIP runtime the library has loaded, for a device buffer of the test's own."""
-    kh.lib()
-    with open("/proc/self/maps") as f:
-        m = re.search(r"(/\S*libamdhip64\.so[.\d]*)", f.read())
-    return C.CDLL(m.group(1) if m else "libamdhip64.so")
-
-
 def test_device_resident_grid(ctx):
     grid, start, goal = cref.doorway_scene()
     r2, c2, wt = 4, 100, 40
@@ -223,21 +214,12 @@ def test_device_resident_grid(ctx):
     assert compare(ctx, grid, [(start, goal)], r2, c2, table) == [ref.FOUND]
     host = outputs(ctx, start, goal, r2) + ctx.clearance() + (ctx.path_clearance(),)
     assert host[1] == 1524 and host[-1] == 81
-    hip = _hip_runtime()
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipFree.argtypes = [C.c_void_p]
     for dtype in (np.int32, np.int8):
         g = np.asfortranarray(grid.astype(dtype))
-        buf = C.c_void_p()
-        assert hip.hipMalloc(C.byref(buf), g.nbytes) == 0
-        try:
-            assert hip.hipMemcpy(buf, g.ctypes.data, g.nbytes, 1) == 0
+        with DeviceArray(g) as buf:
             ctx.set_grid(np.zeros_like(grid))
-            ctx.set_grid_device(buf.value, 96, 80, elem_bytes=g.itemsize)
+            ctx.set_grid_device(buf.ptr, 96, 80, elem_bytes=g.itemsize)
             dev = outputs(ctx, start, goal, r2) + ctx.clearance() + (ctx.path_clearance(),)
-        finally:
-            hip.hipFree(buf)
         assert dev[:3] == host[:3] and dev[-1] == host[-1]
         for a, b in zip(dev[3:-1], host[3:-1]):
             np.testing.assert_array_equal(a, b)

@@ -21,7 +21,7 @@ import kompass_hip as kh  # noqa: E402
 import planner_clearance_ref as cref  # noqa: E402
 import planner_ref as ref  # noqa: E402
 import planner_shortcut_ref as sref  # noqa: E402
-from test_planner_clearance_gpu import _hip_runtime  # noqa: E402
+from helpers import DeviceArray  # noqa: E402
 from test_planner_gpu import GOLD, ROBOT_RADIUS, _robot, connected_pair, free_cells  # noqa: E402
 
 SPANS = [1, 2, 17, 64, 1024]
@@ -237,23 +237,14 @@ def test_device_resident_grid(ctx):
     ctx.set_grid(grid)
     assert ctx.solve(start, goal, 4)[0] == ref.FOUND
     host = [ctx.shortcut(w) for w in (16, 128)]
-    hip = _hip_runtime()
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipFree.argtypes = [C.c_void_p]
     for dtype in (np.int32, np.int8):
         g = np.asfortranarray(grid.astype(dtype))
-        buf = C.c_void_p()
-        assert hip.hipMalloc(C.byref(buf), g.nbytes) == 0
-        try:
-            assert hip.hipMemcpy(buf, g.ctypes.data, g.nbytes, 1) == 0
+        with DeviceArray(g) as buf:
             ctx.set_grid(np.zeros_like(grid))
-            ctx.set_grid_device(buf.value, 96, 80, elem_bytes=g.itemsize)
+            ctx.set_grid_device(buf.ptr, 96, 80, elem_bytes=g.itemsize)
             assert ctx.solve(start, goal, 4)[0] == ref.FOUND
             assert compare(ctx, valid, [16, 128], clear2) == [11, 9]
             dev = [ctx.shortcut(w) for w in (16, 128)]
-        finally:
-            hip.hipFree(buf)
         for a, b in zip(dev, host):
             np.testing.assert_array_equal(a[0], b[0])
             np.testing.assert_array_equal(a[1], b[1])

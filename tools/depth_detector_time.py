@@ -21,7 +21,7 @@ for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
 
 import kompass_hip as kh  # noqa: E402
 from depth_detector_ref import Detector  # noqa: E402
-from test_depth_detector_gpu import DeviceFrame  # noqa: E402
+from test_depth_detector_gpu import device_frame  # noqa: E402
 from kompass_core.datatypes import Bbox2D  # noqa: E402
 from kompass_core.vision import DepthDetector  # noqa: E402
 
@@ -44,7 +44,7 @@ def main():
     a = ap.parse_args()
     img = np.load(ROOT / "tests" / "golden" / "bag_image_depth.npz")["depth"]
     h, w = img.shape
-    dev = DeviceFrame(img)
+    dev, dev_frame = device_frame(img)   # (dev keeps the device copy alive)
     args = (RANGE, [0, 0, 0], [0, 0, 0, 1], FOCAL, PRINCIPAL, FACTOR)
     ctx, ref, det = kh.DepthContext(*args), Detector(*args), DepthDetector(*args)
     ctx.timing_enable(True)
@@ -57,7 +57,7 @@ def main():
             for b, bb in zip(b2, boxes):
                 b.size = np.array([bb[2], bb[3]], np.int32)
             for where in ("host", "device"):
-                frame = dev.frame if where == "device" else {}
+                frame = dev_frame if where == "device" else {}
                 src = None if where == "device" else img
                 kern, up, call, e2e = [], [], [], []
                 for _ in range(a.runs):
