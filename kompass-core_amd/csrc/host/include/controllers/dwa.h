@@ -91,15 +91,11 @@ class DWA : public Follower {
   // picks the winner: every rank returns the same command, or every rank fails the cycle.
   // unique_id: KC_COMM_ID_BYTES from kc_comm_unique_id() of one rank.  Collective.
   void enableSharding(int rank, int world, const uint8_t *unique_id, int device = 0, int mode = KC_SHARD_ROWS) {
-    kc_comm *raw = nullptr;
-    hip::check(kc_comm_create(rank, world, unique_id, device, &raw));
-    adoptComm(raw, mode);
+    adoptComm(hip::make<hip::Comm>(kc_comm_create, rank, world, unique_id, device), mode);
   }
   // rehearsal transport for ranks that share a GPU (kc_comm_create_shm)
   void enableShardingShm(int rank, int world, const std::string &name, int device = 0, int mode = KC_SHARD_ROWS) {
-    kc_comm *raw = nullptr;
-    hip::check(kc_comm_create_shm(rank, world, name.c_str(), device, &raw));
-    adoptComm(raw, mode);
+    adoptComm(hip::make<hip::Comm>(kc_comm_create_shm, rank, world, name.c_str(), device), mode);
   }
   void disableSharding() {
     comm_.reset();
@@ -164,11 +160,12 @@ class DWA : public Follower {
  private:
   double max_forward_distance_ = 0.0;
   int host_threads_;
-  std::shared_ptr<kc_comm> comm_;
-  void adoptComm(kc_comm *raw, int mode) {
-    comm_ = std::shared_ptr<kc_comm>(raw, [](kc_comm *c) { kc_comm_destroy(c); });
+  hip::CommHandle comm_;
+  void adoptComm(hip::Comm comm, int mode) {
+    comm_ = std::move(comm);
     // the context keeps this rank's share of every lattice it is handed from now on
-    hip::check(kc_dwa_set_shard_rule(trajCostEvaluator->context().get(), kc_comm_rank(raw), kc_comm_world(raw), mode));
+    hip::check(kc_dwa_set_shard_rule(trajCostEvaluator->context().get(), kc_comm_rank(comm_.get()),
+                                     kc_comm_world(comm_.get()), mode));
   }
   std::unique_ptr<TrajectorySamples2D> debuggingSamples_ = nullptr;
   float maxLocalRange_ = 10.0;

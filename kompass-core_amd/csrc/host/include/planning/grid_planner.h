@@ -105,10 +105,7 @@ class GridPlanner {
   static uint32_t radiusToR2(double radius, float resolution);
 
  private:
-  struct Deleter {
-    void operator()(kc_planner *p) const { kc_planner_destroy(p); }
-  };
-  std::unique_ptr<kc_planner, Deleter> ctx_;
+  hip::PlannerHandle ctx_;
   double radius_ = 0.0;
   bool allow_unknown_ = true;
   float ox_ = 0.0f, oy_ = 0.0f, res_ = 0.0f;

@@ -31,12 +31,10 @@ class CriticalZoneChecker {
     const float pos[3] = {sensor_position_body(0), sensor_position_body(1), sensor_position_body(2)};
     const float rot[4] = {sensor_rotation_body(0), sensor_rotation_body(1), sensor_rotation_body(2),
                           sensor_rotation_body(3)};
-    kc_zone *raw = nullptr;
-    hip::check(kc_zone_create(static_cast<int>(robot_shape_type), robot_dimensions.data(),
-                              static_cast<int>(robot_dimensions.size()), pos, rot, critical_angle,
-                              critical_distance, slowdown_distance, angles.data(), angles.size(),
-                              min_height, max_height, range_max, 0, &raw));
-    ctx_.reset(raw, [](kc_zone *p) { kc_zone_destroy(p); });
+    ctx_ = hip::make<hip::ZoneHandle>(kc_zone_create, static_cast<int>(robot_shape_type), robot_dimensions.data(),
+                                      static_cast<int>(robot_dimensions.size()), pos, rot, critical_angle,
+                                      critical_distance, slowdown_distance, angles.data(), angles.size(),
+                                      min_height, max_height, range_max, 0);
   }
   virtual ~CriticalZoneChecker() = default;
 
@@ -57,7 +55,7 @@ class CriticalZoneChecker {
  protected:
   PointFieldType field_type_ = PointFieldType::FLOAT32;
   InputType input_type_;
-  std::shared_ptr<kc_zone> ctx_;
+  hip::ZoneHandle ctx_;
 };
 
 // critical_zone_check_gpu.h:36-53: same surface plus the datatype of the cloud's x / y / z fields, decoded as

@@ -7,6 +7,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 #include "kompass_hip.h"
 
@@ -23,29 +24,34 @@ inline void check(int rc) {
   }
 }
 
-struct DwaDeleter {
-  void operator()(kc_dwa *p) const { kc_dwa_destroy(p); }
+// The one owner of a context of the library: a unique_ptr whose deleter is the context's destroy function.
+template <class T, void (*Destroy)(T *)>
+struct FnDeleter {
+  void operator()(T *p) const { Destroy(p); }
 };
-struct MapperDeleter {
-  void operator()(kc_mapper *p) const { kc_mapper_destroy(p); }
-};
-struct CloudDeleter {
-  void operator()(kc_cloud *p) const { kc_cloud_destroy(p); }
-};
-using CloudHandle = std::unique_ptr<kc_cloud, CloudDeleter>;
+template <class T, void (*Destroy)(T *)>
+using Handle = std::unique_ptr<T, FnDeleter<T, Destroy>>;
+
+using Dwa = Handle<kc_dwa, kc_dwa_destroy>;
+using Comm = Handle<kc_comm, kc_comm_destroy>;
+using MapperHandle = Handle<kc_mapper, kc_mapper_destroy>;
+using CloudHandle = Handle<kc_cloud, kc_cloud_destroy>;
+using ZoneHandle = Handle<kc_zone, kc_zone_destroy>;
+using DepthHandle = Handle<kc_depth, kc_depth_destroy>;
+using PlannerHandle = Handle<kc_planner, kc_planner_destroy>;
+// The two shared contexts (sampler, evaluator and controller work on one kc_dwa): made from a Dwa / Comm, which
+// keeps the context while the control block is allocated.
 using DwaHandle = std::shared_ptr<kc_dwa>;
-using MapperHandle = std::unique_ptr<kc_mapper, MapperDeleter>;
+using CommHandle = std::shared_ptr<kc_comm>;
 
-inline DwaHandle makeDwa(const kc_dwa_params &p) {
-  kc_dwa *raw = nullptr;
-  check(kc_dwa_create(&p, &raw));
-  return DwaHandle(raw, DwaDeleter());
-}
-
-inline CloudHandle makeCloud(size_t max_bytes, size_t max_bins) {
-  kc_cloud *raw = nullptr;
-  check(kc_cloud_create(max_bytes, max_bins, 0, &raw));
-  return CloudHandle(raw);
+// create(args..., &raw), checked: the new context has its owner before anything can throw.
+template <class H, class Create, class... Args>
+H make(Create create, Args &&...args) {
+  typename H::pointer raw = nullptr;
+  const int rc = create(std::forward<Args>(args)..., &raw);
+  H owner(raw);
+  check(rc);
+  return owner;
 }
 
 }  // namespace hip

@@ -28,7 +28,7 @@ namespace Kompass {
 
 namespace detail {
 inline kc_cloud *sharedCloud() {
-  static hip::CloudHandle ctx = hip::makeCloud(1 << 20, 4096);
+  static hip::CloudHandle ctx = hip::make<hip::CloudHandle>(kc_cloud_create, 1 << 20, 4096, 0);
   return ctx.get();
 }
 // Calls on one kc_cloud context are serial (kompass_hip.h), and the grid is a protocol of several calls whose

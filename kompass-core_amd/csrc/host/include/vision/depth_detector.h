@@ -48,7 +48,7 @@ class DepthDetector {
 
  private:
   size_t calls_ = 0;
-  std::shared_ptr<kc_depth> ctx_;
+  hip::DepthHandle ctx_;
   std::unique_ptr<std::vector<Bbox3D>> boxes_;
 };
 

@@ -12,10 +12,8 @@ DepthDetector::DepthDetector(const Eigen::Vector2f &depth_range, const Eigen::Ve
                              const Eigen::Vector2f &principal_point, const float depth_conversion_factor) {
   const float rot[4] = {camera_in_body_rotation.x(), camera_in_body_rotation.y(), camera_in_body_rotation.z(),
                         camera_in_body_rotation.w()};
-  kc_depth *raw = nullptr;
-  hip::check(kc_depth_create(depth_range.data(), camera_in_body_translation.data(), rot, focal_length.data(),
-                             principal_point.data(), depth_conversion_factor, 0, &raw));
-  ctx_.reset(raw, [](kc_depth *p) { kc_depth_destroy(p); });
+  ctx_ = hip::make<hip::DepthHandle>(kc_depth_create, depth_range.data(), camera_in_body_translation.data(), rot,
+                                     focal_length.data(), principal_point.data(), depth_conversion_factor, 0);
 }
 
 std::optional<std::vector<Bbox3D>> DepthDetector::get3dDetections() const {

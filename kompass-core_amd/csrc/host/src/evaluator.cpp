@@ -47,7 +47,7 @@ hip::DwaHandle makeEvaluatorContext(const Eigen::Vector3f &spos, const Eigen::Qu
   p.acc_limits[1] = static_cast<float>(lim.velYParams.maxAcceleration);
   p.acc_limits[2] = static_cast<float>(lim.omegaParams.maxAcceleration);
   p.device = 0;
-  return hip::makeDwa(p);
+  return hip::make<hip::Dwa>(kc_dwa_create, &p);
 }
 }  // namespace
 

@@ -35,9 +35,7 @@ GridPlanner::GridPlanner(const CollisionChecker::ShapeType &shape, const std::ve
     : allow_unknown_(allow_unknown) {
   radius_ = circumscribedRadius(shape, dims) + static_cast<double>(margin);
   if (!(radius_ >= 0.0) || !std::isfinite(radius_)) throw std::invalid_argument("the footprint radius must be finite and >= 0");
-  kc_planner *raw = nullptr;
-  hip::check(kc_planner_create(0, &raw));
-  ctx_.reset(raw);
+  ctx_ = hip::make<hip::PlannerHandle>(kc_planner_create, 0);
 }
 
 void GridPlanner::setSpaceBoundsFromMap(float origin_x, float origin_y, int width, int height, float resolution) {

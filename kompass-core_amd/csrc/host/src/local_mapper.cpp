@@ -13,10 +13,9 @@ namespace Mapping {
 namespace {
 hip::MapperHandle makeMapper(int H, int W, float res, const Eigen::Vector3f &pos, float orient,
                              int scanSize) {
-  kc_mapper *raw = nullptr;
   const float p[3] = {pos(0), pos(1), pos(2)};
-  hip::check(kc_mapper_create(H, W, res, p, orient, static_cast<size_t>(std::max(scanSize, 1)), 0, &raw));
-  return hip::MapperHandle(raw);
+  return hip::make<hip::MapperHandle>(kc_mapper_create, H, W, res, p, orient,
+                                      static_cast<size_t>(std::max(scanSize, 1)), 0);
 }
 }  // namespace
 

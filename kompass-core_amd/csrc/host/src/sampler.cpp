@@ -61,7 +61,8 @@ CollisionChecker::CollisionChecker(const ShapeType shape, const std::vector<floa
                                    const Eigen::Quaternionf &srot, const double res)
     : voxel_(res) {
   shapeExtents(shape, dims, body_radius_, body_height_);
-  ctx_ = hip::makeDwa(baseParams(shape, dims, spos, srot, res));
+  const kc_dwa_params p = baseParams(shape, dims, spos, srot, res);
+  ctx_ = hip::make<hip::Dwa>(kc_dwa_create, &p);
 }
 CollisionChecker::CollisionChecker(hip::DwaHandle ctx, ShapeType shape,
                                    const std::vector<float> &dims, double res)
@@ -176,7 +177,7 @@ void TrajectorySampler::init(const CollisionChecker::ShapeType shape,
   p.acc_limits[0] = static_cast<float>(limits_.velXParams.maxAcceleration);
   p.acc_limits[1] = static_cast<float>(limits_.velYParams.maxAcceleration);
   p.acc_limits[2] = static_cast<float>(limits_.omegaParams.maxAcceleration);
-  ctx_ = hip::makeDwa(p);
+  ctx_ = hip::make<hip::Dwa>(kc_dwa_create, &p);
   checker_ = std::make_unique<CollisionChecker>(ctx_, shape, dims, octreeRes);
   if (drive_ != ControlType::OMNI)  // trajectory_sampler.cpp:51-54
     limits_.velYParams = LinearVelocityControlParams(0.0, 0.0, 0.0);

@@ -238,34 +238,6 @@ SIGNATURES = {
 
 _lib = None
 
-
-def lib():
-    """Load libkompass_hip.so (raises if it was not built -- no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise KompassHipError(
-            f"{LIB_PATH} is missing: build it with `make -C {_HERE}` "
-            "(or __graft_entry__.build()); there is no CPU fallback")
-    L = C.CDLL(str(LIB_PATH))
-    # KOMPASS_HIP_LIB_OLD=1 (with KOMPASS_HIP_LIB): an OLDER build of the library in a same-box A/B -- entries it does
-    # not export yet are skipped instead of failing the load (tools only; the tests never set it)
-    tolerant = os.environ.get("KOMPASS_HIP_LIB_OLD") == "1"
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            f = getattr(L, name)  # AttributeError if the symbol is not exported
-        except AttributeError:
-            if tolerant:
-                continue
-            raise
-        f.restype = res
-        f.argtypes = args
-    _lib = L
-    _bind_fast(L)
-    return L
-
-
 # The four calls of a controller cycle with fresh inputs (window, points, segment, cycle) sit on the critical
 # path in front of the cycle kernel's launch: a second prototype of each takes plain ADDRESSES (c_void_p from an
 # int: no ctypes pointer objects per call), the wrappers below reuse one State / Result per context and hand
@@ -273,9 +245,9 @@ def lib():
 _fast = {}
 
 
-def _bind_fast(L):
+def _fast_protos():
     vp, i, d, f, z = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_size_t
-    protos = {
+    return {
         "kc_dwa_set_points": (vp, vp, vp, z, f),
         "kc_dwa_set_tracked_segment": (vp, vp, vp, vp, vp, z, f),
         "kc_dwa_set_tracked_segment_xyz": (vp, vp, vp, z, f),
@@ -283,12 +255,54 @@ def _bind_fast(L):
         "kc_dwa_find_best_path": (vp, vp, vp, vp),
         "kc_dwa_sample_window": (vp, i, vp, d, d, d, i, i, vp, vp, vp, vp, z),
     }
-    for name, args in protos.items():
-        try:
-            _fast[name] = C.CFUNCTYPE(C.c_int, *args)((name, L))
-        except AttributeError:
-            if os.environ.get("KOMPASS_HIP_LIB_OLD") != "1":
-                raise
+
+
+def _missing(name, path):
+    def stub(*_args):
+        raise KompassHipError(f"{name} is not exported by {path} (loaded with tolerant=True)")
+    return stub
+
+
+def load(path=None, tolerant=False):
+    """Load the library at `path` (default: LIB_PATH), give every entry of SIGNATURES its prototype, bind `_fast`
+    and make it the library `lib()` returns.  A symbol the library does not export fails the load -- or, with
+    tolerant=True (an OLDER build in a same-box A/B, tools/ab_libs.sh), is bound to a stub, in the library object
+    and in `_fast`, that raises KompassHipError when it is called."""
+    global _lib
+    path = str(LIB_PATH if path is None else path)  # a file, or a name for the dynamic loader to find
+    try:
+        L = C.CDLL(path)
+    except OSError:
+        if os.path.exists(path):
+            raise
+        raise KompassHipError(
+            f"{path} is missing: build it with `make -C {_HERE}` "
+            "(or __graft_entry__.build()); there is no CPU fallback") from None
+    protos, fast = _fast_protos(), {}
+    for name, (res, args) in SIGNATURES.items():
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+            if name in protos:
+                fast[name] = C.CFUNCTYPE(C.c_int, *protos[name])((name, L))
+        elif tolerant:
+            setattr(L, name, _missing(name, path))
+            if name in protos:
+                fast[name] = getattr(L, name)
+        else:
+            raise KompassHipError(f"{path} does not export {name}: not a build of this version of the library")
+    _fast.update(fast)
+    _lib = L
+    return L
+
+
+def lib():
+    """The loaded libkompass_hip.so (raises if it was not built -- no fallback).  KOMPASS_HIP_LIB selects another
+    build (LIB_PATH), KOMPASS_HIP_LIB_OLD=1 loads it tolerantly: both are hooks of tools/ab_libs.sh."""
+    if _lib is not None:
+        return _lib
+    return load(tolerant=os.environ.get("KOMPASS_HIP_LIB_OLD") == "1")
 
 
 def _addr32(a):
@@ -319,9 +333,7 @@ def set_host_threads(n: int):
 def trig_selfcheck() -> int:
     """The restated sincos (csrc/kc_trig_exact.h) against the installed libm on the library's fixed argument
     set (host only); returns the number of arguments compared, raises when any differs."""
-    n = C.c_int64(0)
-    _check(lib().kc_trig_selfcheck(C.byref(n)))
-    return int(n.value)
+    return int(_out(C.c_int64, lib().kc_trig_selfcheck))
 
 
 def trig_table(yaw0: float, omega, n_steps: int, dt: float):
@@ -347,6 +359,79 @@ def _pf(a):
 
 def _pd(a):
     return a.ctypes.data_as(_dp) if a is not None else None
+
+
+def _out(ctype, fn, *args):
+    """fn(*args, &v) with v a zeroed `ctype`, checked -> v.value: the calls with one out-parameter, the last."""
+    v = ctype()
+    _check(fn(*args, C.byref(v)))
+    return v.value
+
+
+def _fill(fn, h, specs):
+    """The two calls of a list getter: fn(h, NULL ..., 0, &n) asks for the count, fn(h, arrays ..., n, &n) fills
+    one array per entry of `specs` -- (dtype, shape of one element), or None for an output that is not wanted.
+    -> the arrays cut to n rows (None where the spec is)."""
+    n = _sz(0)
+    _check(fn(h, *[None] * len(specs), 0, C.byref(n)))
+    k = n.value
+    out = [None if s is None else np.zeros((max(k, 1),) + s[1], s[0]) for s in specs]
+    if k:
+        ptrs = [a if a is None else a.ctypes.data_as(t) for a, t in zip(out, fn.argtypes[1:])]
+        _check(fn(h, *ptrs, k, C.byref(n)))
+    return [a if a is None else a[:k] for a in out]
+
+
+class _Owner:
+    """Owner of one context of the library: the handle `h`, and the one way it is released.  A subclass names its
+    C prefix (`_kc`: kc_dwa_destroy is its destroy function) and opens the handle with `_open`."""
+    _kc = None
+
+    def _open(self, create, *args):
+        """create(*args, &h), checked."""
+        self.h = _vp()
+        _check(create(*args, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            getattr(lib(), self._kc + "_destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _Timed:
+    """Per-kernel timing of a context (kc_*_timing_enable / kc_*_timing_get); `_timing_cap` is the most entries
+    `timings` asks for."""
+    _timing_cap = 16
+
+    def timing_enable(self, on=True):
+        _check(getattr(lib(), self._kc + "_timing_enable")(self.h, int(bool(on))))
+
+    def timings(self):
+        cap = self._timing_cap
+        names = (C.c_char_p * cap)()
+        ms = (C.c_float * cap)()
+        n = _sz(0)
+        _check(getattr(lib(), self._kc + "_timing_get")(self.h, names, ms, cap, C.byref(n)))
+        return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+
+
+class _StreamOrdered:
+    def after_stream(self, stream=None):
+        """Order the context's next read of a device buffer it is handed after the work queued so far on `stream`
+        (a hipStream_t address; None: the legacy default stream)."""
+        _check(getattr(lib(), self._kc + "_after_stream")(self.h, stream))
 
 
 def make_limits(vx=(1.0, 10.0, 10.0), vy=(1.0, 10.0, 10.0), omega=(np.pi, 1.0, 10.0, 10.0)) -> Limits:
@@ -390,18 +475,18 @@ def shard_merge(record, words_per_rank: int, world: int, mode: int, owner, n_tot
     return r
 
 
-class Comm:
+class Comm(_Owner):
     """Owner of one kc_comm: an RCCL communicator inside libkompass_hip.so, or -- shm_name given --
     the shared-memory rehearsal transport for ranks that share a GPU (kc_comm_create_shm)."""
+    _kc = "kc_comm"
 
     def __init__(self, rank: int, world: int, unique_id: bytes = None, device: int = 0, shm_name: str = None):
-        self.h = _vp()
         if shm_name is not None:
-            _check(lib().kc_comm_create_shm(int(rank), int(world), shm_name.encode(), int(device), C.byref(self.h)))
+            self._open(lib().kc_comm_create_shm, int(rank), int(world), shm_name.encode(), int(device))
         else:
             assert len(unique_id) == COMM_ID_BYTES
             buf = (C.c_uint8 * COMM_ID_BYTES).from_buffer_copy(unique_id)
-            _check(lib().kc_comm_create(int(rank), int(world), buf, int(device), C.byref(self.h)))
+            self._open(lib().kc_comm_create, int(rank), int(world), buf, int(device))
         self.rank, self.world = int(rank), int(world)
 
     @property
@@ -415,20 +500,10 @@ class Comm:
         _check(lib().kc_comm_query(self.h, C.byref(n), C.byref(r), C.byref(d)))
         return n.value, r.value, d.value
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_comm_destroy(self.h)
-            self.h = _vp()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DwaContext:
+class DwaContext(_Owner, _Timed):
     """Owner of one kc_dwa context (one HIP stream, persistent device buffers)."""
+    _kc, _timing_cap = "kc_dwa", 32
 
     def __init__(self, shape, dims, sensor_pos=(0, 0, 0), sensor_rot_xyzw=(0, 0, 0, 1), octree_res=0.1,
                  time_step=0.1, max_samples=1024, max_points=64, max_segment=512, max_obstacles=1024,
@@ -449,25 +524,13 @@ class DwaContext:
         p.max_segment, p.max_obstacles = int(max_segment), int(max_obstacles)
         p.device = int(device)
         self.params = p
-        self.h = _vp()
-        _check(lib().kc_dwa_create(C.byref(p), C.byref(self.h)))
+        self._open(lib().kc_dwa_create, C.byref(p))
         self._P = 0
         self._st = State()                      # reused by the per-cycle calls
         self._st_addr = C.addressof(self._st)
         self._n = _sz(0)
         self._n_addr = C.addressof(self._n)
         self._step = None
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_dwa_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- configuration ------------------------------------------------------
     def set_stream(self, stream_ptr):
@@ -480,9 +543,7 @@ class DwaContext:
         _check(lib().kc_dwa_set_option(self.h, name.encode(), float(value)))
 
     def get_option(self, name: str) -> float:
-        v = C.c_double(0.0)
-        _check(lib().kc_dwa_get_option(self.h, name.encode(), C.byref(v)))
-        return v.value
+        return _out(C.c_double, lib().kc_dwa_get_option, self.h, name.encode())
 
     def set_weights(self, w: Weights):
         _check(lib().kc_dwa_set_weights(self.h, C.byref(w)))
@@ -515,9 +576,7 @@ class DwaContext:
         _check(lib().kc_dwa_set_shard_rule(self.h, int(rank), int(world), int(mode)))
 
     def owns_sample(self, raw_index) -> bool:
-        v = C.c_int(0)
-        _check(lib().kc_dwa_owns_sample(self.h, int(raw_index), C.byref(v)))
-        return bool(v.value)
+        return bool(_out(C.c_int, lib().kc_dwa_owns_sample, self.h, int(raw_index)))
 
     def set_scan(self, state, ranges, angles, max_sensor_range=10.0):
         r, a = _f64(ranges), _f64(angles)
@@ -697,27 +756,13 @@ class DwaContext:
         return px, py, v
 
     def get_samples(self, with_costs=False, with_paths=True):
-        P = self._P
-        n = _sz(0)
-        _check(lib().kc_dwa_get_samples(self.h, None, None, None, None, 0, C.byref(n)))
-        k = n.value
-        if with_paths:
-            px, py = np.zeros((max(k, 1), P), np.float32), np.zeros((max(k, 1), P), np.float32)
-        else:
-            px = py = None
-        raw = np.zeros(max(k, 1), np.int32)
-        costs = np.zeros(max(k, 1), np.float32) if with_costs else None
-        _check(lib().kc_dwa_get_samples(self.h, _pf(px), _pf(py), raw.ctypes.data_as(_ip), _pf(costs), k,
-                                        C.byref(n)))
-        out = (px[:k], py[:k], raw[:k]) if with_paths else (None, None, raw[:k])
-        return out + (costs[:k],) if with_costs else out
+        path = (np.float32, (self._P,)) if with_paths else None
+        px, py, raw, costs = _fill(lib().kc_dwa_get_samples, self.h,
+                                   [path, path, (np.int32, ()), (np.float32, ()) if with_costs else None])
+        return (px, py, raw, costs) if with_costs else (px, py, raw)
 
     def get_freeze_steps(self):
-        n = _sz(0)
-        _check(lib().kc_dwa_get_freeze_steps(self.h, None, 0, C.byref(n)))
-        st = np.zeros(max(n.value, 1), np.int32)
-        _check(lib().kc_dwa_get_freeze_steps(self.h, st.ctypes.data_as(_ip), n.value, C.byref(n)))
-        return st[:n.value]
+        return _fill(lib().kc_dwa_get_freeze_steps, self.h, [(np.int32, ())])[0]
 
     def get_sample_velocity(self, raw_index):
         vx, vy, om = C.c_double(0), C.c_double(0), C.c_double(0)
@@ -768,9 +813,7 @@ class DwaContext:
         return r
 
     def global_index(self, comm: "Comm", raw_index) -> int:
-        v = C.c_int64(0)
-        _check(lib().kc_dwa_global_index(self.h, comm.h, int(raw_index), C.byref(v)))
-        return v.value
+        return _out(C.c_int64, lib().kc_dwa_global_index, self.h, comm.h, int(raw_index))
 
     def publish_result(self):
         """After an in-place reduction of the device record: hand it to the host
@@ -778,48 +821,22 @@ class DwaContext:
         _check(lib().kc_dwa_publish_result(self.h))
 
     def result_device_ptr(self) -> int:
-        p = _vp()
-        _check(lib().kc_dwa_result_device(self.h, C.byref(p)))
-        return p.value
+        return _out(_vp, lib().kc_dwa_result_device, self.h)
 
     def count_admissible_before(self, raw_index) -> int:
-        c = C.c_int64(0)
-        _check(lib().kc_dwa_count_admissible_before(self.h, int(raw_index), C.byref(c)))
-        return c.value
-
-    def timing_enable(self, on=True):
-        _check(lib().kc_dwa_timing_enable(self.h, int(bool(on))))
-
-    def timings(self):
-        names = (C.c_char_p * 32)()
-        ms = (C.c_float * 32)()
-        n = _sz(0)
-        _check(lib().kc_dwa_timing_get(self.h, names, ms, 32, C.byref(n)))
-        return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+        return _out(C.c_int64, lib().kc_dwa_count_admissible_before, self.h, int(raw_index))
 
 
-class MapperContext:
+class MapperContext(_Owner, _Timed):
     """Owner of one kc_mapper context (LocalMapper scan -> grid)."""
+    _kc = "kc_mapper"
 
     def __init__(self, grid_height, grid_width, resolution, laserscan_position=(0, 0, 0),
                  laserscan_orientation=0.0, max_scan_size=4096, device=0):
         pos = _f32(laserscan_position)
         self.H, self.W = int(grid_height), int(grid_width)
-        self.h = _vp()
-        _check(lib().kc_mapper_create(self.H, self.W, float(np.float32(resolution)), _pf(pos),
-                                      float(np.float32(laserscan_orientation)), int(max_scan_size),
-                                      int(device), C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_mapper_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(lib().kc_mapper_create, self.H, self.W, float(np.float32(resolution)), _pf(pos),
+                   float(np.float32(laserscan_orientation)), int(max_scan_size), int(device))
 
     def set_stream(self, stream_ptr):
         _check(lib().kc_mapper_set_stream(self.h, _vp(stream_ptr) if stream_ptr else None))
@@ -883,38 +900,15 @@ class MapperContext:
         _check(lib().kc_mapper_sync(self.h))
 
     def grid_device_ptr(self) -> int:
-        p = _vp()
-        _check(lib().kc_mapper_grid_device(self.h, C.byref(p)))
-        return p.value
-
-    def timing_enable(self, on=True):
-        _check(lib().kc_mapper_timing_enable(self.h, int(bool(on))))
-
-    def timings(self):
-        names = (C.c_char_p * 16)()
-        ms = (C.c_float * 16)()
-        n = _sz(0)
-        _check(lib().kc_mapper_timing_get(self.h, names, ms, 16, C.byref(n)))
-        return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+        return _out(_vp, lib().kc_mapper_grid_device, self.h)
 
 
-class CloudContext:
+class CloudContext(_Owner, _Timed, _StreamOrdered):
     """Owner of one kc_cloud context (raw point cloud -> laserscan)."""
+    _kc = "kc_cloud"
 
     def __init__(self, max_bytes=1 << 20, max_bins=4096, device=0):
-        self.h = _vp()
-        _check(lib().kc_cloud_create(int(max_bytes), int(max_bins), int(device), C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_cloud_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(lib().kc_cloud_create, int(max_bytes), int(max_bins), int(device))
 
     def to_laserscan(self, data, point_step, row_step, height, width, x_offset, y_offset, z_offset,
                      max_range, min_z, max_z, angle_step=None, num_bins=None, device_ptr=None, nbytes=None,
@@ -973,74 +967,40 @@ class CloudContext:
         _check(lib().kc_cloud_grid_extent(self.h, ptr, size, on_dev, step, n, int(offsets[0]), int(offsets[1]),
                                           int(offsets[2]), res, _pf(origin), C.byref(cx), C.byref(cy)))
         if not to_host:
-            dev = _vp()
-            _check(lib().kc_cloud_grid_device(self.h, float(z_ground_limit), float(robot_height), C.byref(dev)))
-            return dev.value or 0, (cx.value, cy.value), origin
+            dev = _out(_vp, lib().kc_cloud_grid_device, self.h, float(z_ground_limit), float(robot_height))
+            return dev or 0, (cx.value, cy.value), origin
         grid = np.empty((cx.value, cy.value), np.int8, order="F")
         _check(lib().kc_cloud_grid_fill(self.h, float(z_ground_limit), float(robot_height), grid.ctypes.data, grid.size))
         return grid, origin
 
-    def after_stream(self, stream=None):
-        """Order the next reads after the work queued so far on `stream` (a hipStream_t address; None: the legacy
-        default stream)."""
-        _check(lib().kc_cloud_after_stream(self.h, stream))
-
     def last_rebinned(self) -> int:
-        n = _sz(0)
-        _check(lib().kc_cloud_last_rebinned(self.h, C.byref(n)))
-        return n.value
-
-    def timing_enable(self, on=True):
-        _check(lib().kc_cloud_timing_enable(self.h, int(bool(on))))
-
-    def timings(self):
-        names = (C.c_char_p * 16)()
-        ms = (C.c_float * 16)()
-        n = _sz(0)
-        _check(lib().kc_cloud_timing_get(self.h, names, ms, 16, C.byref(n)))
-        return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+        return _out(_sz, lib().kc_cloud_last_rebinned, self.h)
 
 
-class ZoneContext:
+class ZoneContext(_Owner):
     """Owner of one kc_zone context (CriticalZoneChecker)."""
+    _kc = "kc_zone"
 
     def __init__(self, shape, dims, sensor_pos, sensor_rot_xyzw, critical_angle, critical_distance,
                  slowdown_distance, angles, min_height, max_height, range_max, device=0):
         d, sp, sr = _f32(dims), _f32(sensor_pos), _f32(sensor_rot_xyzw)
         a = _f64(angles)
         self.n = len(a)
-        self.h = _vp()
-        _check(lib().kc_zone_create(int(shape), _pf(d), len(d), _pf(sp), _pf(sr), float(np.float32(critical_angle)),
-                                    float(np.float32(critical_distance)), float(np.float32(slowdown_distance)),
-                                    _pd(a), len(a), float(np.float32(min_height)), float(np.float32(max_height)),
-                                    float(np.float32(range_max)), int(device), C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_zone_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(lib().kc_zone_create, int(shape), _pf(d), len(d), _pf(sp), _pf(sr), float(np.float32(critical_angle)),
+                   float(np.float32(critical_distance)), float(np.float32(slowdown_distance)), _pd(a), len(a),
+                   float(np.float32(min_height)), float(np.float32(max_height)), float(np.float32(range_max)), int(device))
 
     def check(self, ranges, forward) -> float:
         r = _f64(ranges)
-        f = C.c_float(0)
-        _check(lib().kc_zone_check(self.h, _pd(r), len(r), int(bool(forward)), C.byref(f)))
-        return float(f.value)
+        return float(_out(C.c_float, lib().kc_zone_check, self.h, _pd(r), len(r), int(bool(forward))))
 
     def check_cloud(self, data, point_step, row_step, height, width, x_offset, y_offset, z_offset, forward,
                     field_type=7) -> float:
         buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.int8) if not isinstance(data, np.ndarray)
                                    else data.view(np.int8).reshape(-1))
-        f = C.c_float(0)
-        _check(lib().kc_zone_check_cloud_typed(self.h, buf.ctypes.data, buf.size, int(point_step), int(row_step),
-                                               int(height), int(width), int(x_offset), int(y_offset), int(z_offset),
-                                               int(field_type), int(bool(forward)), C.byref(f)))
-        return float(f.value)
+        return float(_out(C.c_float, lib().kc_zone_check_cloud_typed, self.h, buf.ctypes.data, buf.size, int(point_step),
+                          int(row_step), int(height), int(width), int(x_offset), int(y_offset), int(z_offset),
+                          int(field_type), int(bool(forward))))
 
     def indices(self, forward):
         out = (C.c_int64 * max(self.n, 1))()
@@ -1049,8 +1009,9 @@ class ZoneContext:
         return np.array(out[:n.value], dtype=np.int64)
 
 
-class DepthContext:
+class DepthContext(_Owner, _Timed, _StreamOrdered):
     """Owner of one kc_depth context (DepthDetector: 2-D boxes -> 3-D boxes)."""
+    _kc = "kc_depth"
 
     def __init__(self, depth_range, camera_in_body_translation, camera_in_body_rotation, focal_length,
                  principal_point, depth_conversion_factor=1e-3, device=0):
@@ -1058,20 +1019,8 @@ class DepthContext:
         f, p = _f32(focal_length), _f32(principal_point)
         if dr.shape != (2,) or t.shape != (3,) or q.shape != (4,) or f.shape != (2,) or p.shape != (2,):
             raise ValueError("depth_range (2), translation (3), rotation xyzw (4), focal (2), principal (2)")
-        self.h = _vp()
-        _check(lib().kc_depth_create(_pf(dr), _pf(t), _pf(q), _pf(f), _pf(p), float(np.float32(depth_conversion_factor)),
-                                     int(device), C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_depth_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(lib().kc_depth_create, _pf(dr), _pf(t), _pf(q), _pf(f), _pf(p),
+                   float(np.float32(depth_conversion_factor)), int(device))
 
     @staticmethod
     def _frame(img, device_ptr, shape, strides):
@@ -1118,47 +1067,19 @@ class DepthContext:
                                         cnt.ctypes.data_as(C.POINTER(C.c_int64)), _pf(st)))
         return cnt[:n], st[:n]
 
-    def after_stream(self, stream=None):
-        """Order the next frame read after the work queued so far on `stream` (a hipStream_t handle; None: the
-        legacy default stream)."""
-        _check(lib().kc_depth_after_stream(self.h, stream))
-
     def last_upload(self) -> int:
-        n = _sz(0)
-        _check(lib().kc_depth_last_upload(self.h, C.byref(n)))
-        return n.value
-
-    def timing_enable(self, on=True):
-        _check(lib().kc_depth_timing_enable(self.h, int(bool(on))))
-
-    def timings(self):
-        names = (C.c_char_p * 16)()
-        ms = (C.c_float * 16)()
-        n = _sz(0)
-        _check(lib().kc_depth_timing_get(self.h, names, ms, 16, C.byref(n)))
-        return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+        return _out(_sz, lib().kc_depth_last_upload, self.h)
 
 
-class DvzContext:
+class DvzContext(_Owner):
     """Owner of one kc_dvz context (DeformableVirtualZone.get_total_deformation: one launch per call)."""
+    _kc = "kc_dvz"
 
     def __init__(self, max_beams=4096, device=0):
         if int(max_beams) < 0:
             raise ValueError(f"max_beams must be non-negative, got {max_beams}")
         self.max_beams = int(max_beams)
-        self.h = _vp()
-        _check(lib().kc_dvz_create(int(device), self.max_beams, C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_dvz_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(lib().kc_dvz_create, int(device), self.max_beams)
 
     def deform(self, zone, angles, ranges, radii=False):
         """(total, orientation_sum, n_deformed) over the beams, plus the per-beam deformed radii when `radii`.
@@ -1180,25 +1101,14 @@ PLAN_CLEAR_FAR = 0xFFFF
 PLAN_MAX_SPAN = 1024
 
 
-class PlannerContext:
+class PlannerContext(_Owner, _StreamOrdered):
     """Owner of one kc_planner context (grid planner).  Works in cells: a grid is an array
     g[i, j] of (width, height) cells, i along x; world coordinates are the business of kompass_cpp.planning."""
+    _kc = "kc_planner"
 
     def __init__(self, device=0):
-        self.h = _vp()
         self.shape = (0, 0)
-        _check(lib().kc_planner_create(int(device), C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().kc_planner_destroy(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(lib().kc_planner_create, int(device))
 
     def set_grid(self, grid):
         """grid[i, j]: an int32 or int8 (width, height) array on the host, any memory order."""
@@ -1214,10 +1124,6 @@ class PlannerContext:
         grid_height, height = grid_width; CloudContext.occupancy_grid(to_host=False): int8)."""
         _check(lib().kc_planner_set_grid_device(self.h, int(device_ptr), int(elem_bytes), int(width), int(height)))
         self.shape = (int(width), int(height))
-
-    def after_stream(self, stream=None):
-        """Order the next device grid's read after the work queued so far on `stream` (None: the legacy default)."""
-        _check(lib().kc_planner_after_stream(self.h, stream))
 
     def solve(self, start, goal, r2=0, allow_unknown=True):
         """-> (status, cost, passes): PLAN_* status, field[start] in units of 10 per straight step."""
@@ -1238,12 +1144,7 @@ class PlannerContext:
 
     def path(self):
         """(n, 2) int32 cells (i, j) from the start to the goal; n = 0 when the last solve found none."""
-        n = _sz(0)
-        _check(lib().kc_planner_get_path(self.h, None, 0, C.byref(n)))
-        out = np.empty((n.value, 2), np.int32)
-        if n.value:
-            _check(lib().kc_planner_get_path(self.h, out.ctypes.data, n.value, C.byref(n)))
-        return out
+        return _fill(lib().kc_planner_get_path, self.h, [(np.int32, (2,))])[0]
 
     def set_clearance_cost(self, c2, table=None):
         """The clearance cost of rules 6 to 8: table[d2] for d2 = 0 .. c2 is the surcharge of a cell whose nearest
@@ -1268,9 +1169,7 @@ class PlannerContext:
 
     def path_clearance(self):
         """The smallest clear2 along the last path, both ends included (PLAN_CLEAR_FAR: nothing within reach)."""
-        v = C.c_uint32(0)
-        _check(lib().kc_planner_path_clearance(self.h, C.byref(v)))
-        return v.value
+        return _out(C.c_uint32, lib().kc_planner_path_clearance, self.h)
 
     def shortcut(self, max_span=128):
         """The any-angle path of rules 9 to 12 over the last path: (cells (k, 2) int32, indices (k,) int32 into
