@@ -900,6 +900,50 @@ int kc_planner_shortcut(kc_planner *ctx, int max_span, size_t *count_out, uint32
  * walk, ascending; either may be NULL, both NULL asks for the count only;
  * KC_ERR_STATE without one (a new solve forgets it) */
 int kc_planner_get_shortcut(kc_planner *ctx, int32_t *cells_ij_out, int32_t *index_out, size_t cap, size_t *count_out);
+/* The oriented box footprint (rules 13 to 18), off by default.  The
+ * state is (cell, class); class k = 0 .. 3 is the box's length axis along (1, 0),
+ * (1, 1), (0, 1), (-1, 1).  a2 / b2: the squared half length / half width in cells
+ * (rule 2's R2 formula on x / 2 + margin and y / 2 + margin).
+ *  - (cell, k) is valid when no blocking cell lies at cell + (di, dj) for an offset of
+ *    mask k: k = 0: di^2 <= a2 and dj^2 <= b2; k = 2: dj^2 <= a2 and di^2 <= b2;
+ *    k = 1: (di + dj)^2 <= 2 a2 and (dj - di)^2 <= 2 b2; k = 3: (dj - di)^2 <= 2 a2 and
+ *    (di + dj)^2 <= 2 b2.  Cells outside the grid do not block.
+ *  - a cell is turn-valid when no blocking cell has di^2 + dj^2 <= a2 + b2 (the disc
+ *    test of kc_planner_solve with r2 = a2 + b2; it contains all four masks).
+ * turn10: the cost of a turn by one class (a straight step is 10), 1 .. 10000.
+ * a2 = 0 switches the mode off and forgets the last solve; every output of
+ * kc_planner_solve is then what it is without this call.  KC_ERR_RANGE for turn10
+ * outside 1 .. 10000 and for a2 + b2 > KC_PLANNER_MAX_RADIUS_CELLS^2; KC_ERR_STATE while a
+ * clearance cost is set (and kc_planner_set_clearance_cost answers the same while
+ * this mode is on).  While it is on, kc_planner_solve answers KC_ERR_STATE. */
+int kc_planner_set_oriented(kc_planner *ctx, uint32_t a2, uint32_t b2, uint32_t turn10);
+/* Validity, state field and the start's status for (start cell, start class) -> goal cell.
+ *  - field[k][cell] = 0 for every valid (goal, k); otherwise the minimum of cost +
+ *    field[next] over the moves (cell, k) -> (cell +- d_k, k), both states valid, 10 for
+ *    k = 0, 2 and 14 for k = 1, 3, and the turns (cell, k) -> (cell, k +- 1 mod 4) at
+ *    turn10 where the cell is turn-valid; 0xFFFFFFFF where nothing arrives.
+ *  - *status_out as kc_planner_solve: KC_PLAN_START_INVALID when (start, start_class)
+ *    is invalid, KC_PLAN_GOAL_INVALID when no class is valid at the goal, then
+ *    KC_PLAN_UNREACHABLE.  *cost_out = field[start_class][start], the turns included.
+ * KC_ERR_RANGE when max(14, turn10) * 4 * cells > 0xFFFFFFFE, or if the field still
+ * changes after 4 * cells + 1 passes (it cannot); KC_ERR_STATE without a grid or with
+ * the mode off; KC_ERR_INVALID for a class outside 0 .. 3. */
+int kc_planner_solve_oriented(kc_planner *ctx, const int start_cell[2], int start_class, const int goal_cell[2],
+                              int allow_unknown, int *status_out, uint32_t *cost_out, int *passes_out);
+/* the last oriented solve's field (four layers of width x height cells, class 0
+ * first), validity (a byte a cell, bit k = class k valid) and turn validity (1 / 0),
+ * laid out as the grid; any may be NULL; cap: cells (field4_out holds 4 * cap words);
+ * KC_ERR_STATE unless the last solve was kc_planner_solve_oriented */
+int kc_planner_get_oriented_field(kc_planner *ctx, uint32_t *field4_out, uint8_t *valid4_out, uint8_t *turn_valid_out, size_t cap);
+/* the state walk of the last oriented solve: from (start, start_class) the allowed
+ * transition with the smallest field[next] + cost, the first among equals in the
+ * order: the class's direction that comes first in E, N, W, S, NE, NW, SW, SE, its
+ * opposite, the turn to k + 1, the turn to k - 1; that minimum equals field[current].
+ * states_ijk_out: (i, j, k) triples, start first; NULL asks for the count only; zero
+ * states when the solve found no path.  kc_planner_get_path then gives the same
+ * walk's cells with the repeated cell of a turn collapsed; kc_planner_shortcut answers
+ * KC_ERR_STATE (a segment at an arbitrary angle has no class). */
+int kc_planner_get_oriented_path(kc_planner *ctx, int32_t *states_ijk_out, size_t cap, size_t *count_out);
 
 #ifdef __cplusplus
 }

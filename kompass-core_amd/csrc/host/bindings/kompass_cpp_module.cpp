@@ -1053,6 +1053,37 @@ PYBIND11_MODULE(kompass_cpp, m) {
            "metres along the any-angle path")
       .def("get_any_angle_min_clearance", &Planning::GridPlanner::getAnyAngleMinClearance, py::arg("max_span") = 128,
            "metres from the cells the any-angle path touches to the nearest blocking cell; inf without a clearance cost")
+      .def("set_oriented_footprint", &Planning::GridPlanner::setOrientedFootprint, py::arg("on"), py::arg("turn_cost") = 1.0f,
+           "Plan over (cell, heading class) with the box's own footprint (BOX robots): moves along the length axis where "
+           "the oriented box fits, turns of 45 degrees at `turn_cost` straight-cell lengths where the turning disc fits")
+      .def("oriented_on", &Planning::GridPlanner::orientedOn)
+      .def("get_oriented_turn10", &Planning::GridPlanner::orientedTurn10)
+      .def("get_oriented_a2_b2", [](const Planning::GridPlanner &p) {
+             uint32_t a2 = 0, b2 = 0;
+             p.orientedA2B2(&a2, &b2);
+             return py::make_tuple(a2, b2);
+           }, "(A2, B2) of the bounds set; (0, 0) with the mode off")
+      .def("get_path_states", [](Planning::GridPlanner &p) {
+             const std::vector<int32_t> ijk = p.getPathStates();
+             py::array_t<int32_t> a({(py::ssize_t)(ijk.size() / 3), (py::ssize_t)3});
+             if (!ijk.empty()) std::memcpy(a.mutable_data(), ijk.data(), ijk.size() * sizeof(int32_t));
+             return a;
+           }, "(n, 3) states (i, j, k) of the oriented walk; empty without a path or with the mode off")
+      .def("get_oriented_field", [](Planning::GridPlanner &p) {
+             const py::ssize_t w = p.width(), h = p.height();
+             py::array_t<uint32_t> f({(py::ssize_t)4, h, w});  // layer k, then cell (i, j) at i + j * width
+             py::array_t<uint8_t, py::array::f_style> v({w, h}), t({w, h});
+             p.getOrientedField(f.mutable_data(), v.mutable_data(), t.mutable_data(), static_cast<size_t>(w) * static_cast<size_t>(h));
+             return py::make_tuple(f.attr("transpose")(0, 2, 1), v, t);
+           }, "(field uint32 [4, i, j], validity bits uint8 [i, j] (bit k = class k), turn validity uint8 [i, j]) of the last oriented solve")
+      .def_static("orientation_class", &Planning::GridPlanner::orientationClass, py::arg("yaw"),
+                  "The heading class 0 .. 3 of a yaw: ((lround(yaw / (pi / 4)) mod 4) + 4) mod 4")
+      .def_static("oriented_mask", [](int k, uint32_t a2, uint32_t b2) {
+             const std::vector<int32_t> o = Planning::GridPlanner::orientedMask(k, a2, b2);
+             py::array_t<int32_t> a({(py::ssize_t)(o.size() / 2), (py::ssize_t)2});
+             if (!o.empty()) std::memcpy(a.mutable_data(), o.data(), o.size() * sizeof(int32_t));
+             return a;
+           }, py::arg("k"), py::arg("a2"), py::arg("b2"), "The (di, dj) offsets of class k's footprint mask, in integers")
       .def("get_clearance_c2", &Planning::GridPlanner::clearanceC2)
       .def("get_clearance_weight10", &Planning::GridPlanner::clearanceWeight10)
       .def("get_status", &Planning::GridPlanner::status)

@@ -8,7 +8,9 @@
 // adds a surcharge per cell that falls with the distance to the nearest blocking cell (rules 6 to 8): the path
 // then trades length for clearance, as deterministically as before.  getAnyAngle* hand out the any-angle path over
 // the same walk (rules 9 to 12): far fewer waypoints, straight where there is line of sight, and with a clearance
-// cost no closer to a blocking cell than the walk already came.
+// cost no closer to a blocking cell than the walk already came.  setOrientedFootprint (BOX robots, rules 13 to 18)
+// plans over (cell, heading class) with the box's own oriented footprint instead of the disc: the robot moves along
+// its length axis wherever the box fits and turns in place only where the turning disc fits.
 #pragma once
 
 #include <cstdint>
@@ -88,6 +90,29 @@ class GridPlanner {
   float getPathMinClearance() const;
   // the last solve's cost field and validity map, width x height as the grid (cap: cells either output holds)
   void getField(uint32_t *field_out, uint8_t *valid_out, size_t cap);
+
+  // The oriented footprint (rules 13 to 18), BOX robots only.  The state is (cell, class); class k = 0 .. 3 is the
+  // box's x axis along (1, 0), (1, 1), (0, 1), (-1, 1).  A2 = radiusToR2(x / 2 + margin, resolution) and B2 likewise
+  // from y, evaluated with the bounds and again when they change.  turn_cost: straight-cell lengths per 45 degrees,
+  // turn10 = lround(turn_cost * 10) in 1 .. 10000 (std::out_of_range beyond).  The start class comes from
+  // setupProblem's start_yaw; goal_yaw stays unused: every valid class at the goal cell is a goal state.
+  // std::invalid_argument for a shape that is no box, together with a clearance cost (here or in setClearanceCost,
+  // whichever comes second), and from the getAnyAngle* calls while it is on.  getCost includes the turns,
+  // getPathLength is the steps alone, getPath / getPathCells collapse the repeated cell of a turn.
+  void setOrientedFootprint(bool on, float turn_cost = 1.0f);
+  bool orientedOn() const { return oriented_on_; }
+  uint32_t orientedTurn10() const { return oriented_on_ ? turn10_ : 0u; }
+  // A2, B2 of the bounds set (0, 0 while the mode is off)
+  void orientedA2B2(uint32_t *a2_out, uint32_t *b2_out) const;
+  // the (i, j, k) triples of the last solve's state walk, start first; empty without a path or with the mode off
+  std::vector<int32_t> getPathStates();
+  // the last oriented solve's field (four layers, class 0 first), validity bits (bit k = class k) and turn validity
+  void getOrientedField(uint32_t *field4_out, uint8_t *valid4_out, uint8_t *turn_valid_out, size_t cap);
+  // k0 = ((lround(yaw / (pi / 4)) mod 4) + 4) mod 4, in double, halves away from zero; needs no device
+  static int orientationClass(double yaw);
+  // rule 14's offsets of class k as (di, dj) pairs, row by row (dj rising, then di); needs no device.
+  // std::invalid_argument for k outside 0 .. 3, std::out_of_range where A2 + B2 reaches beyond 254 cells.
+  static std::vector<int32_t> orientedMask(int k, uint32_t a2, uint32_t b2);
   int width() const { return width_; }
   int height() const { return height_; }
 
@@ -119,6 +144,14 @@ class GridPlanner {
   uint32_t weight10_ = 0;
   bool clear_applied_ = false;  // the context holds the table of (applied_r2_, applied_c2_, applied_w10_)
   uint32_t applied_r2_ = 0, applied_c2_ = 0, applied_w10_ = 0;
+  bool is_box_ = false;
+  double box_x_ = 0.0, box_y_ = 0.0, margin_ = 0.0;
+  bool oriented_on_ = false;
+  uint32_t turn10_ = 0;
+  int start_class_ = 0;
+  bool oriented_applied_ = false;  // the context holds (applied_a2_, applied_b2_, applied_turn10_)
+  uint32_t applied_a2_ = 0, applied_b2_ = 0, applied_turn10_ = 0;
+  void applyOriented();
   void applyClearanceCost();
   void needBounds() const;
   void forgetSolve();

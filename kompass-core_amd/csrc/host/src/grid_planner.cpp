@@ -35,6 +35,12 @@ GridPlanner::GridPlanner(const CollisionChecker::ShapeType &shape, const std::ve
     : allow_unknown_(allow_unknown) {
   radius_ = circumscribedRadius(shape, dims) + static_cast<double>(margin);
   if (!(radius_ >= 0.0) || !std::isfinite(radius_)) throw std::invalid_argument("the footprint radius must be finite and >= 0");
+  is_box_ = shape == CollisionChecker::ShapeType::BOX;
+  if (is_box_) {
+    box_x_ = static_cast<double>(dims[0]);
+    box_y_ = static_cast<double>(dims[1]);
+  }
+  margin_ = static_cast<double>(margin);
   ctx_ = hip::make<hip::PlannerHandle>(kc_planner_create, 0);
 }
 
@@ -51,10 +57,99 @@ void GridPlanner::setSpaceBoundsFromMap(float origin_x, float origin_y, int widt
   res_ = resolution;
   have_bounds_ = true;
   applyClearanceCost();  // R2 and C2 are cells of this resolution
+  applyOriented();       // and so are A2 and B2
+}
+
+void GridPlanner::setOrientedFootprint(bool on, float turn_cost) {
+  uint32_t t10 = 0;
+  if (on) {
+    if (!is_box_) throw std::invalid_argument("the oriented footprint needs a BOX robot");
+    if (clear_on_) throw std::invalid_argument("the oriented footprint cannot be combined with a clearance cost");
+    const double t = static_cast<double>(turn_cost) * 10.0;
+    if (!std::isfinite(t) || !(t >= 0.5) || !(t < 10000.5)) throw std::out_of_range("turn_cost must give a turn10 in 1 .. 10000");
+    t10 = static_cast<uint32_t>(std::lround(t));
+  }
+  const bool was_on = oriented_on_;
+  const uint32_t old_t10 = turn10_;
+  oriented_on_ = on;
+  turn10_ = t10;
+  if (!have_bounds_) return;
+  try {
+    applyOriented();
+  } catch (...) {  // a refused footprint leaves the one before
+    oriented_on_ = was_on;
+    turn10_ = old_t10;
+    throw;
+  }
+}
+
+void GridPlanner::orientedA2B2(uint32_t *a2_out, uint32_t *b2_out) const {
+  *a2_out = *b2_out = 0;
+  if (!oriented_on_) return;
+  needBounds();
+  *a2_out = radiusToR2(box_x_ / 2.0 + margin_, res_);
+  *b2_out = radiusToR2(box_y_ / 2.0 + margin_, res_);
+}
+
+// hands the box to the context when it is not the one the context holds, as applyClearanceCost does
+void GridPlanner::applyOriented() {
+  if (!oriented_on_) {
+    if (oriented_applied_) {
+      hip::check(kc_planner_set_oriented(ctx_.get(), 0, 0, 0));
+      oriented_applied_ = false;
+      forgetSolve();
+    }
+    return;
+  }
+  uint32_t a2 = 0, b2 = 0;
+  orientedA2B2(&a2, &b2);
+  if (a2 == 0) throw std::out_of_range("the box's half length is less than a cell: the oriented footprint has no length axis");
+  if (oriented_applied_ && applied_a2_ == a2 && applied_b2_ == b2 && applied_turn10_ == turn10_) return;
+  oriented_applied_ = false;
+  hip::check(kc_planner_set_oriented(ctx_.get(), a2, b2, turn10_));
+  oriented_applied_ = true;
+  applied_a2_ = a2;
+  applied_b2_ = b2;
+  applied_turn10_ = turn10_;
+  forgetSolve();
+}
+
+int GridPlanner::orientationClass(double yaw) {
+  const long q = std::lround(yaw / (M_PI / 4.0));
+  return static_cast<int>(((q % 4) + 4) % 4);
+}
+
+std::vector<int32_t> GridPlanner::orientedMask(int k, uint32_t a2, uint32_t b2) {
+  if (k < 0 || k > 3) throw std::invalid_argument("class " + std::to_string(k) + " is outside 0 .. 3");
+  const uint64_t t2 = static_cast<uint64_t>(a2) + b2;
+  if (t2 > static_cast<uint64_t>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+    throw std::out_of_range("a turning disc of T2 = " + std::to_string(t2) + " is wider than " +
+                            std::to_string(KC_PLANNER_MAX_RADIUS_CELLS) + " cells");
+  int64_t r = 0;
+  while (static_cast<uint64_t>((r + 1) * (r + 1)) <= t2) ++r;  // T2 contains every mask
+  const int64_t A = a2, B = b2;
+  std::vector<int32_t> out;
+  for (int64_t dj = -r; dj <= r; ++dj)
+    for (int64_t di = -r; di <= r; ++di) {
+      const int64_t s = (di + dj) * (di + dj), d = (dj - di) * (dj - di);
+      bool in = false;
+      switch (k) {
+        case 0: in = di * di <= A && dj * dj <= B; break;
+        case 2: in = dj * dj <= A && di * di <= B; break;
+        case 1: in = s <= 2 * A && d <= 2 * B; break;
+        default: in = d <= 2 * A && s <= 2 * B; break;
+      }
+      if (in) {
+        out.push_back(static_cast<int32_t>(di));
+        out.push_back(static_cast<int32_t>(dj));
+      }
+    }
+  return out;
 }
 
 void GridPlanner::setClearanceCost(float reach, float weight) {
   const bool on = reach > 0.0f && weight > 0.0f;
+  if (on && oriented_on_) throw std::invalid_argument("a clearance cost cannot be combined with the oriented footprint");
   if (on && (!std::isfinite(reach) || !std::isfinite(weight))) throw std::invalid_argument("reach and weight must be finite");
   uint32_t w10 = 0;
   if (on) {
@@ -183,8 +278,9 @@ uint32_t GridPlanner::footprintR2() const {
   return radiusToR2(radius_, res_);
 }
 
-void GridPlanner::setupProblem(double start_x, double start_y, double, double goal_x, double goal_y, double) {
+void GridPlanner::setupProblem(double start_x, double start_y, double start_yaw, double goal_x, double goal_y, double) {
   needBounds();
+  start_class_ = std::isfinite(start_yaw) ? orientationClass(start_yaw) : 0;  // the oriented footprint's k0; goal_yaw stays unused
   // a coordinate no cell holds is outside the grid
   if (!worldToCell(static_cast<float>(start_x), ox_, res_, &start_[0])) start_[0] = -1;
   if (!worldToCell(static_cast<float>(start_y), oy_, res_, &start_[1])) start_[1] = -1;
@@ -198,7 +294,10 @@ bool GridPlanner::solve() {
   if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
   if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
   status_ = -1;
-  hip::check(kc_planner_solve(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
+  if (oriented_on_)
+    hip::check(kc_planner_solve_oriented(ctx_.get(), start_, start_class_, goal_, allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
+  else
+    hip::check(kc_planner_solve(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
   return status_ == KC_PLAN_FOUND;
 }
 
@@ -260,7 +359,24 @@ float GridPlanner::getPathLength() {
   return static_cast<float>(steps) * res_ / 10.0f;
 }
 
+std::vector<int32_t> GridPlanner::getPathStates() {
+  std::vector<int32_t> ijk;
+  if (status_ != KC_PLAN_FOUND || !oriented_on_) return ijk;
+  size_t n = 0;
+  hip::check(kc_planner_get_oriented_path(ctx_.get(), nullptr, 0, &n));
+  ijk.resize(3 * n);
+  if (n) hip::check(kc_planner_get_oriented_path(ctx_.get(), ijk.data(), n, &n));
+  return ijk;
+}
+
+void GridPlanner::getOrientedField(uint32_t *field4_out, uint8_t *valid4_out, uint8_t *turn_valid_out, size_t cap) {
+  if (status_ < 0) throw std::runtime_error("GridPlanner: no solve since the last grid or problem");
+  hip::check(kc_planner_get_oriented_field(ctx_.get(), field4_out, valid4_out, turn_valid_out, cap));
+}
+
 std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int32_t> *indices_out) {
+  // a segment at an arbitrary angle has no heading class (rule 18)
+  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
   std::vector<int32_t> ij;
   if (indices_out) indices_out->clear();
   if (status_ != KC_PLAN_FOUND) return ij;
@@ -273,6 +389,7 @@ std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int
 }
 
 std::optional<Path::Path> GridPlanner::getAnyAnglePath(int max_span) {
+  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
   if (status_ != KC_PLAN_FOUND) return std::nullopt;
   const std::vector<int32_t> ij = getAnyAngleCells(max_span);
   std::vector<Path::Point> pts;
@@ -283,6 +400,7 @@ std::optional<Path::Path> GridPlanner::getAnyAnglePath(int max_span) {
 }
 
 float GridPlanner::getAnyAngleLength(int max_span) {
+  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
   if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
   const std::vector<int32_t> ij = getAnyAngleCells(max_span);
   double sum = 0.0;
@@ -294,6 +412,7 @@ float GridPlanner::getAnyAngleLength(int max_span) {
 }
 
 float GridPlanner::getAnyAngleMinClearance(int max_span) {
+  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
   if (status_ != KC_PLAN_FOUND) throw std::runtime_error("GridPlanner: no path");
   uint32_t c2 = KC_PLANNER_CLEAR_FAR;
   hip::check(kc_planner_shortcut(ctx_.get(), max_span, nullptr, &c2));

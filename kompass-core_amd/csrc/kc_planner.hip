@@ -29,6 +29,13 @@
 //      to a wavefront from the far end in rounds of 16, the lanes of a wavefront stride over the columns of their
 //      segment and test the up to three touched cells of a column, and the largest clear index of the first round
 //      that has one is the next anchor.
+//  (f) oriented box footprint (rules 13 to 18; off unless kc_planner_set_oriented gave a box).  The state is (cell,
+//      class), four classes.  The turning disc goes through the row and column passes of (a) with r2 = T2;
+//      planner_oriented_valid_kernel tests the four host-built offset lists, nearest offsets first, and skips the cells
+//      the disc already cleared (T2 contains every mask); a byte a cell holds the four class bits and the turn bit.
+//      planner_relax4_kernel is (b) over four layers: the same tile, halo, two buffers and changed word, 16 states a
+//      lane; layers 0 and 2 couple along rows and columns, 1 and 3 along the diagonals, all four at the same cell by
+//      a turn.  planner_walk4_kernel is (c) over states: four lanes, the two moves of the class and the two turns.
 //
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
@@ -375,6 +382,219 @@ __global__ __launch_bounds__(kShortThreads) void planner_shortcut_kernel(const i
   }
 }
 
+// ---- the oriented box footprint (rules 13 to 18) -----------------------------------------------------------------
+
+// the length axis of class k: E, NE, N, NW, the first of the class's two directions in the walk's order
+__constant__ const int kPlanClassDx[4] = {1, 1, 0, -1};
+__constant__ const int kPlanClassDy[4] = {0, 1, 1, 1};
+constexpr uint8_t kPlanTurnBit = 16;  // beside the four class bits of a cell's byte
+
+struct PlanMaskEnds {
+  uint32_t at[5];  // class k's offsets are offs[at[k] .. at[k + 1])
+};
+
+// rule 14: offs holds (di, dj) pairs, class after class, each class by rising di^2 + dj^2 so that a cell near a
+// blocking one leaves early.  turn: rule 15's disc; it contains every mask, so its cells are valid in all four.
+__global__ __launch_bounds__(kPlanBlock) void planner_oriented_valid_kernel(const uint8_t *__restrict__ cls,
+                                                                            const uint8_t *__restrict__ turn,
+                                                                            const int16_t *__restrict__ offs, PlanMaskEnds ends,
+                                                                            uint8_t *__restrict__ valid4, int W, int H,
+                                                                            int block_unknown) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    if (turn[i]) {
+      valid4[i] = static_cast<uint8_t>(15 | kPlanTurnBit);
+      continue;
+    }
+    const int x = static_cast<int>(i % W), y = static_cast<int>(i / W);
+    uint32_t bits = 0;
+    for (int k = 0; k < 4; ++k) {
+      bool ok = true;
+      for (uint32_t o = ends.at[k]; o < ends.at[k + 1]; ++o) {
+        const int nx = x + offs[2 * o], ny = y + offs[2 * o + 1];
+        // cells outside the grid do not block
+        if (nx >= 0 && nx < W && ny >= 0 && ny < H &&
+            plan_blocks(cls[static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(nx)], block_unknown)) {
+          ok = false;
+          break;
+        }
+      }
+      bits |= ok ? 1u << k : 0u;
+    }
+    valid4[i] = static_cast<uint8_t>(bits);
+  }
+}
+
+// layer k of a field buffer is its cells [k * n, (k + 1) * n)
+__global__ __launch_bounds__(kPlanBlock) void planner_init4_kernel(uint32_t *a, uint32_t *b, const uint8_t *valid4, long long n,
+                                                                   long long goal) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const uint32_t bits = i == goal ? valid4[i] : 0u;  // every valid class at the goal cell is a goal state
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t v = (bits >> k & 1u) ? 0u : kPlanInf;
+      a[static_cast<size_t>(k) * static_cast<size_t>(n) + static_cast<size_t>(i)] = v;
+      b[static_cast<size_t>(k) * static_cast<size_t>(n) + static_cast<size_t>(i)] = v;
+    }
+  }
+}
+
+// rule 16, one pass over one tile, as planner_relax_kernel: `in` is only read, `out` only written (the tile's own
+// cells, four layers).  A lane owns four cells and their sixteen states.  The moves read the neighbours' values of
+// the last iteration from LDS; the turns couple the four values of one cell, which one lane holds in registers.
+__global__ __launch_bounds__(kPlanThreads) void planner_relax4_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                      const uint8_t *__restrict__ valid4, int W, int H, size_t n,
+                                                                      unsigned tiles_x, uint32_t turn10, uint32_t *changed_word,
+                                                                      uint32_t pass) {
+  __shared__ uint32_t f[4][kPlanHalo * kPlanHalo];
+  __shared__ uint8_t v[kPlanHalo * kPlanHalo];
+  const int x0 = static_cast<int>(blockIdx.x % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(blockIdx.x / tiles_x) * kPlanTile - 1;
+  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
+    const int lx = k % kPlanHalo, ly = k / kPlanHalo;
+    const int gx = x0 + lx, gy = y0 + ly;
+    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
+    const size_t g = inside ? static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx) : 0;
+    const uint32_t bits = inside ? valid4[g] : 0u;
+    v[k] = static_cast<uint8_t>(bits);
+#pragma unroll
+    for (int l = 0; l < 4; ++l) f[l][k] = (bits >> l & 1u) ? in[static_cast<size_t>(l) * n + g] : kPlanInf;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
+  const int off[4] = {1, kPlanHalo + 1, kPlanHalo, kPlanHalo - 1};
+  int idx[kPlanRows];
+  uint32_t cur[kPlanRows][4], mask[kPlanRows];
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int k = (1 + ty + r * (kPlanThreads / kPlanTile)) * kPlanHalo + 1 + tx;
+    idx[r] = k;
+    const uint32_t here = v[k];
+    uint32_t m = (here & kPlanTurnBit) ? 256u : 0u;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      cur[r][l] = f[l][k];
+      // a move needs both states valid; no corner rule: the swept lattice points lie in the footprint of one end
+      if (here >> l & 1u) m |= ((v[k + off[l]] >> l & 1u) ? 1u << (2 * l) : 0u) | ((v[k - off[l]] >> l & 1u) ? 2u << (2 * l) : 0u);
+    }
+    mask[r] = m;
+  }
+  int changed = 0;
+  for (int it = 0; it < kPlanLocalIters; ++it) {
+    int ch = 0;
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) {
+      uint32_t b[4];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) {
+        uint32_t best = cur[r][l];
+        const uint32_t step = (l & 1) ? 14u : 10u;  // no wrap: max(14, turn10) * 4 * cells < 2^32 (kc_planner_solve_oriented)
+        if (mask[r] & (1u << (2 * l))) {
+          const uint32_t fn = f[l][idx[r] + off[l]];
+          if (fn != kPlanInf && fn + step < best) best = fn + step;
+        }
+        if (mask[r] & (2u << (2 * l))) {
+          const uint32_t fn = f[l][idx[r] - off[l]];
+          if (fn != kPlanInf && fn + step < best) best = fn + step;
+        }
+        b[l] = best;
+      }
+      if (mask[r] & 256u) {
+        uint32_t t[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) t[l] = min(b[(l + 1) & 3], b[(l + 3) & 3]);
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+          if (t[l] != kPlanInf && t[l] + turn10 < b[l]) b[l] = t[l] + turn10;
+      }
+#pragma unroll
+      for (int l = 0; l < 4; ++l)
+        if (b[l] < cur[r][l]) {
+          cur[r][l] = b[l];
+          ch = 1;
+        }
+    }
+    if (!__syncthreads_or(ch)) break;  // every lane has read this iteration's values
+    changed |= ch;
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r)
+#pragma unroll
+      for (int l = 0; l < 4; ++l) f[l][idx[r]] = cur[r][l];
+    __syncthreads();
+  }
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int gx = x0 + 1 + tx, gy = y0 + 1 + ty + r * (kPlanThreads / kPlanTile);
+    if (gx < W && gy < H) {
+      const size_t g = static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx);
+#pragma unroll
+      for (int l = 0; l < 4; ++l) out[static_cast<size_t>(l) * n + g] = cur[r][l];
+    }
+  }
+  if (__syncthreads_or(changed) && threadIdx.x == 0) *changed_word = pass;
+}
+
+// rule 17: one wavefront, four lanes: the class's first direction, its opposite, the turn to k + 1, the turn to k - 1.
+// states[] = 4 * cell + class; out[0] = states written, out[1] = 0 done / 1 capacity / 2 the minimum is not the field.
+__global__ __launch_bounds__(64) void planner_walk4_kernel(const uint32_t *field, const uint8_t *valid4, int W, int H, size_t n,
+                                                           int sx, int sy, int sk, uint32_t turn10, int32_t *states, uint32_t cap,
+                                                           uint32_t *out) {
+  const int lane = threadIdx.x;
+  int cx = sx, cy = sy, ck = sk;
+  uint32_t count = 0, status = 0;
+  for (;;) {
+    const size_t c = static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(cx);
+    if (count >= cap) {
+      status = 1;
+      break;
+    }
+    if (lane == 0) states[count] = static_cast<int32_t>(4 * c + static_cast<size_t>(ck));
+    ++count;
+    const uint32_t fc = field[static_cast<size_t>(ck) * n + c];
+    if (fc == 0u) break;
+    unsigned long long key = ~0ull;
+    if (lane < 2) {
+      const int sgn = lane == 0 ? 1 : -1;
+      const int nx = cx + sgn * kPlanClassDx[ck], ny = cy + sgn * kPlanClassDy[ck];
+      if (nx >= 0 && nx < W && ny >= 0 && ny < H) {
+        const size_t g = static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(nx);
+        // 64 bits hold an unreached state's 0xFFFFFFFF + cost as well; it never equals field[current]
+        if (valid4[g] >> ck & 1)
+          key = ((static_cast<unsigned long long>(field[static_cast<size_t>(ck) * n + g]) + ((ck & 1) ? 14ull : 10ull)) << 2) |
+                static_cast<unsigned long long>(lane);
+      }
+    } else if (lane < 4) {
+      if (valid4[c] & kPlanTurnBit) {
+        const int nk = lane == 2 ? (ck + 1) & 3 : (ck + 3) & 3;
+        key = ((static_cast<unsigned long long>(field[static_cast<size_t>(nk) * n + c]) + turn10) << 2) | static_cast<unsigned long long>(lane);
+      }
+    }
+#pragma unroll
+    for (int d = 2; d >= 1; d >>= 1) {
+      const unsigned long long o = __shfl_xor(key, d, 64);
+      key = o < key ? o : key;
+    }
+    key = __shfl(key, 0, 64);
+    if (key == ~0ull || (key >> 2) != static_cast<unsigned long long>(fc)) {  // not on a converged field with a reachable start
+      status = 2;
+      break;
+    }
+    const int q = static_cast<int>(key & 3ull);
+    if (q < 2) {
+      const int sgn = q == 0 ? 1 : -1;
+      cx += sgn * kPlanClassDx[ck];
+      cy += sgn * kPlanClassDy[ck];
+    } else {
+      ck = q == 2 ? (ck + 1) & 3 : (ck + 3) & 3;
+    }
+  }
+  if (lane == 0) {
+    out[0] = count;
+    out[1] = status;
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -414,6 +634,16 @@ struct kc_planner {
   std::vector<int32_t> short_idx;
   DevBuf<int32_t> d_keep;
   PinBuf<int32_t> h_keep;
+  uint32_t or_a2 = 0, or_b2 = 0, or_turn10 = 0;  // the oriented footprint (rules 13 to 18): on while or_a2 > 0
+  PlanMaskEnds or_ends = {};
+  bool or_have_valid = false;  // d_turn / d_valid4 hold the maps of (grid, or_a2, or_b2, or_valid_unknown)
+  int or_valid_unknown = 0;
+  bool or_solve = false;       // the last solve was kc_planner_solve_oriented: d_field4, start_class, states
+  int start_class = 0;
+  std::vector<int32_t> states; // the walk's states, 4 * cell + class; `path` then holds its cells, turns collapsed
+  DevBuf<int16_t> d_offs;
+  DevBuf<uint8_t> d_turn, d_valid4;
+  DevBuf<uint32_t> d_field4[2];
 };
 
 namespace {
@@ -434,7 +664,7 @@ int check_grid_shape(const void *grid, int elem_bytes, int width, int height) {
 // dev: the grid on the context's device, complete
 int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width, int height) {
   const long long n = static_cast<long long>(width) * height;
-  c->have_grid = c->have_valid = c->solved = c->have_path = false;
+  c->have_grid = c->have_valid = c->or_have_valid = c->solved = c->have_path = false;
   KC_TRY(c->d_cls.reserve(static_cast<size_t>(n)));
   if (elem_bytes == 4)
     hipLaunchKernelGGL(planner_classify_kernel<int32_t>, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, c->stream,
@@ -450,9 +680,63 @@ int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width,
   return KC_OK;
 }
 
+// rule 14's offsets of class k, by rising di^2 + dj^2 (then dj, then di); A2 + B2 within the radius cap
+std::vector<int16_t> oriented_offsets(int k, uint32_t a2, uint32_t b2) {
+  int r = 0;
+  while (static_cast<uint32_t>(r + 1) * static_cast<uint32_t>(r + 1) <= a2 + b2) ++r;  // T2 contains every mask
+  std::vector<std::pair<int, int>> o;
+  for (int dj = -r; dj <= r; ++dj)
+    for (int di = -r; di <= r; ++di) {
+      const uint32_t ii = static_cast<uint32_t>(di * di), jj = static_cast<uint32_t>(dj * dj);
+      const uint32_t ss = static_cast<uint32_t>((di + dj) * (di + dj)), dd = static_cast<uint32_t>((dj - di) * (dj - di));
+      const bool in = k == 0 ? ii <= a2 && jj <= b2 : k == 2 ? jj <= a2 && ii <= b2 : k == 1 ? ss <= 2 * a2 && dd <= 2 * b2 : dd <= 2 * a2 && ss <= 2 * b2;
+      if (in) o.emplace_back(di, dj);
+    }
+  std::stable_sort(o.begin(), o.end(), [](const std::pair<int, int> &p, const std::pair<int, int> &q) {
+    return p.first * p.first + p.second * p.second < q.first * q.first + q.second * q.second;
+  });
+  std::vector<int16_t> out;
+  out.reserve(2 * o.size());
+  for (const auto &p : o) {
+    out.push_back(static_cast<int16_t>(p.first));
+    out.push_back(static_cast<int16_t>(p.second));
+  }
+  return out;
+}
+
+// rule 17 over the last oriented solve (status KC_PLAN_FOUND), once: c->states, and c->path with the turns collapsed
+int planner_walk_oriented(kc_planner *c) {
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  // every transition lowers the field by min(10, turn10) at least, and no state comes twice
+  const size_t cap = std::min<size_t>(4 * n, static_cast<size_t>(c->cost / std::min<uint32_t>(10u, c->or_turn10))) + 2;
+  KC_TRY(c->d_path.reserve(cap));
+  KC_TRY(c->h_path.reserve(cap));
+  hipLaunchKernelGGL(planner_walk4_kernel, dim3(1), dim3(64), 0, s, c->d_field4[c->final_buf].p, c->d_valid4.p, c->W, c->H, n,
+                     c->start[0], c->start[1], c->start_class, c->or_turn10, c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipMemcpyAsync(&c->h_word.p[1], c->d_word.p + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  const uint32_t count = c->h_word.p[1], wst = c->h_word.p[2];
+  if (wst != 0u || count == 0u || count > cap)
+    KC_FAIL(KC_ERR_STATE, "the state walk stopped after %u states with status %u", count, wst);
+  KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  c->states.assign(c->h_path.p, c->h_path.p + count);
+  c->path.clear();
+  for (const int32_t st : c->states)
+    if (c->path.empty() || c->path.back() != st / 4) c->path.push_back(st / 4);  // a turn stays in its cell
+  c->path_clear2 = static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
+  c->have_path = true;
+  c->have_short = false;
+  return KC_OK;
+}
+
 // the walk of the last solve (status KC_PLAN_FOUND), once: c->path, and c->path_clear2 with the clearance cost on
 int planner_walk(kc_planner *c) {
   if (c->have_path) return KC_OK;
+  if (c->or_solve) return planner_walk_oriented(c);
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const bool pen_on = c->clear_c2 > 0;
@@ -570,6 +854,7 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
                      int *status_out, uint32_t *cost_out, int *passes_out) {
   if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve before a grid was set");
+  if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve with the oriented footprint on: kc_planner_solve_oriented");
   int R = 0;
   while (static_cast<unsigned long long>(R + 1) * static_cast<unsigned long long>(R + 1) <= r2 && R <= KC_PLANNER_MAX_RADIUS_CELLS) ++R;
   if (R > KC_PLANNER_MAX_RADIUS_CELLS)
@@ -582,7 +867,7 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int W = c->W, H = c->H;
-  c->solved = c->have_path = false;
+  c->solved = c->have_path = c->or_solve = false;
   c->status = -1;
   c->cost = kPlanInf;
   if (cost_out) *cost_out = kPlanInf;
@@ -678,6 +963,7 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
 int kc_planner_get_field(kc_planner *c, uint32_t *field_out, uint8_t *valid_out, size_t cap) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_field before kc_planner_solve");
+  if (c->or_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_field after an oriented solve: kc_planner_get_oriented_field");
   const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
   if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
   KC_HIP(hipSetDevice(c->device));
@@ -707,6 +993,7 @@ int kc_planner_get_path(kc_planner *c, int32_t *cells_ij_out, size_t cap_points,
 int kc_planner_set_clearance_cost(kc_planner *c, uint32_t c2, const uint32_t *pen_by_d2, size_t n) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   const bool on = c2 > 0 && pen_by_d2 != nullptr;
+  if (on && c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "a clearance cost cannot be set while the oriented footprint is on (rule 18)");
   if (on) {
     if (c2 > static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
       KC_FAIL(KC_ERR_RANGE, "a clearance reach of C2 = %u is wider than %d cells", c2, KC_PLANNER_MAX_RADIUS_CELLS);
@@ -750,6 +1037,7 @@ int kc_planner_shortcut(kc_planner *c, int max_span, size_t *count_out, uint32_t
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (count_out) *count_out = 0;
   if (!c->solved || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_shortcut without a path");
+  if (c->or_solve) KC_FAIL(KC_ERR_STATE, "no any-angle path in oriented mode: a segment at an arbitrary angle has no class (rule 18)");
   if (max_span < 1 || max_span > KC_PLANNER_MAX_SPAN)
     KC_FAIL(KC_ERR_RANGE, "max_span %d is outside 1 .. %d", max_span, KC_PLANNER_MAX_SPAN);
   KC_TRY(planner_shortcut(c, max_span));
@@ -774,6 +1062,175 @@ int kc_planner_get_shortcut(kc_planner *c, int32_t *cells_ij_out, int32_t *index
       cells_ij_out[2 * k + 1] = cell / c->W;
     }
     if (index_out) index_out[k] = c->short_idx[k];
+  }
+  return KC_OK;
+}
+
+int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t turn10) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (a2 == 0) {
+    c->or_a2 = c->or_b2 = c->or_turn10 = 0;
+    c->or_have_valid = c->solved = c->have_path = c->or_solve = false;
+    c->status = -1;
+    return KC_OK;
+  }
+  if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "the oriented footprint cannot be set while a clearance cost is on (rule 18)");
+  if (turn10 < 1u || turn10 > 10000u) KC_FAIL(KC_ERR_RANGE, "turn10 = %u is outside 1 .. 10000", turn10);
+  const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
+  if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+    KC_FAIL(KC_ERR_RANGE, "a turning disc of T2 = %llu is wider than %d cells", t2, KC_PLANNER_MAX_RADIUS_CELLS);
+  if (c->or_a2 != a2 || c->or_b2 != b2) {
+    std::vector<int16_t> all;
+    PlanMaskEnds ends = {};
+    for (int k = 0; k < 4; ++k) {
+      const std::vector<int16_t> o = oriented_offsets(k, a2, b2);
+      all.insert(all.end(), o.begin(), o.end());
+      ends.at[k + 1] = static_cast<uint32_t>(all.size() / 2);
+    }
+    KC_HIP(hipSetDevice(c->device));
+    KC_TRY(c->d_offs.reserve(all.size()));
+    // pageable memory: the copy has left the vector when the call returns
+    KC_HIP(hipMemcpyAsync(c->d_offs.p, all.data(), all.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    KC_HIP(hipStreamSynchronize(c->stream));
+    c->or_ends = ends;
+    c->or_have_valid = false;
+  }
+  c->or_a2 = a2;
+  c->or_b2 = b2;
+  c->or_turn10 = turn10;
+  c->solved = c->have_path = c->or_solve = false;
+  c->status = -1;
+  return KC_OK;
+}
+
+int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_class, const int goal_cell[2], int allow_unknown,
+                              int *status_out, uint32_t *cost_out, int *passes_out) {
+  if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_oriented before a grid was set");
+  if (c->or_a2 == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_oriented before kc_planner_set_oriented");
+  if (start_class < 0 || start_class > 3) KC_FAIL(KC_ERR_INVALID, "start class %d is outside 0 .. 3", start_class);
+  const long long n = static_cast<long long>(c->W) * c->H;
+  // field <= max(14, turn10) * (4 * cells - 1): the sums of the relaxation stay below the 0xFFFFFFFF of "nothing arrives"
+  if (static_cast<unsigned long long>(std::max<uint32_t>(14u, c->or_turn10)) * 4ull * static_cast<unsigned long long>(n) > 0xFFFFFFFEull)
+    KC_FAIL(KC_ERR_RANGE, "a turn cost of %u over 4 x %lld states does not fit the 32-bit field", c->or_turn10, n);
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  c->solved = c->have_path = false;
+  c->or_solve = true;
+  c->status = -1;
+  c->cost = kPlanInf;
+  if (cost_out) *cost_out = kPlanInf;
+  if (passes_out) *passes_out = 0;
+  const unsigned blocks = plan_blocks_for(n);
+  const int unknown_blocks = allow_unknown ? 0 : 1;
+  if (!c->or_have_valid || c->or_valid_unknown != unknown_blocks) {
+    c->or_have_valid = false;
+    const uint32_t t2 = c->or_a2 + c->or_b2;
+    int R = 0;
+    while (static_cast<uint32_t>(R + 1) * static_cast<uint32_t>(R + 1) <= t2) ++R;  // <= 254: kc_planner_set_oriented
+    KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
+    KC_TRY(c->d_turn.reserve(static_cast<size_t>(n)));
+    KC_TRY(c->d_valid4.reserve(static_cast<size_t>(n)));
+    // rule 15 is rule 2's disc with r2 = T2: the row distances are scratch, the disc solve's d_valid is not touched
+    hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
+    hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_turn.p, W, H, R, t2);
+    hipLaunchKernelGGL(planner_oriented_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_turn.p, c->d_offs.p,
+                       c->or_ends, c->d_valid4.p, W, H, unknown_blocks);
+    KC_HIP(hipGetLastError());
+    c->or_have_valid = true;
+    c->or_valid_unknown = unknown_blocks;
+  }
+  const bool start_in = start_cell[0] >= 0 && start_cell[0] < W && start_cell[1] >= 0 && start_cell[1] < H;
+  const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
+  const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
+  const long long start = start_in ? static_cast<long long>(start_cell[1]) * W + start_cell[0] : -1;
+  KC_TRY(c->d_field4[0].reserve(4 * static_cast<size_t>(n)));
+  KC_TRY(c->d_field4[1].reserve(4 * static_cast<size_t>(n)));
+  hipLaunchKernelGGL(planner_init4_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field4[0].p, c->d_field4[1].p, c->d_valid4.p, n, goal);
+  KC_HIP(hipMemsetAsync(c->d_word.p, 0, 4 * sizeof(uint32_t), s));
+  KC_HIP(hipGetLastError());
+  uint32_t pass = 0, last_changed = 0;
+  if (goal_in) {
+    // every pass that is not the last gives at least one more state its final value: 4 * cells + 1 passes always do
+    const unsigned long long cap = 4ull * static_cast<unsigned long long>(n) + 1ull;
+    const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile), tiles_y = static_cast<unsigned>((H + kPlanTile - 1) / kPlanTile);
+    const dim3 tiles(tiles_x * tiles_y);
+    for (;;) {
+      for (int b = 0; b < kPlanBatch; ++b) {
+        ++pass;
+        hipLaunchKernelGGL(planner_relax4_kernel, tiles, dim3(kPlanThreads), 0, s, c->d_field4[(pass - 1) & 1].p, c->d_field4[pass & 1].p,
+                           c->d_valid4.p, W, H, static_cast<size_t>(n), tiles_x, c->or_turn10, c->d_word.p, pass);
+      }
+      KC_HIP(hipGetLastError());
+      KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      KC_HIP(hipStreamSynchronize(s));
+      last_changed = c->h_word.p[0];
+      if (last_changed < pass) break;
+      if (pass >= cap)
+        KC_FAIL(KC_ERR_RANGE, "the state field of a %d x %d grid still changed after %u passes (cap %llu)", W, H, pass, cap);
+    }
+  }
+  c->final_buf = static_cast<int>(pass & 1u);
+  c->solved = true;
+  c->start[0] = start_cell[0];
+  c->start[1] = start_cell[1];
+  c->start_class = start_class;
+  c->h_word.p[3] = kPlanInf;
+  c->h_word.p[4] = 0;
+  c->h_word.p[5] = 0;
+  if (start_in) {
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[3], c->d_field4[c->final_buf].p + static_cast<size_t>(start_class) * static_cast<size_t>(n) + start,
+                          sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[4], c->d_valid4.p + start, 1, hipMemcpyDeviceToHost, s));
+  }
+  if (goal_in) KC_HIP(hipMemcpyAsync(&c->h_word.p[5], c->d_valid4.p + goal, 1, hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  const bool start_ok = start_in && ((c->h_word.p[4] >> start_class) & 1u) != 0, goal_ok = goal_in && (c->h_word.p[5] & 15u) != 0;
+  int st = KC_PLAN_FOUND;
+  if (!start_in) st = KC_PLAN_START_OUTSIDE;
+  else if (!goal_in) st = KC_PLAN_GOAL_OUTSIDE;
+  else if (!start_ok) st = KC_PLAN_START_INVALID;
+  else if (!goal_ok) st = KC_PLAN_GOAL_INVALID;
+  else if (c->h_word.p[3] == kPlanInf) st = KC_PLAN_UNREACHABLE;
+  c->status = st;
+  c->cost = st == KC_PLAN_FOUND ? c->h_word.p[3] : kPlanInf;
+  *status_out = st;
+  if (cost_out) *cost_out = c->cost;
+  if (passes_out) *passes_out = goal_in ? static_cast<int>(last_changed + 1u) : 0;
+  return KC_OK;
+}
+
+int kc_planner_get_oriented_field(kc_planner *c, uint32_t *field4_out, uint8_t *valid4_out, uint8_t *turn_valid_out, size_t cap) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->solved || !c->or_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_oriented_field before kc_planner_solve_oriented");
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipSetDevice(c->device));
+  if (field4_out)
+    KC_HIP(hipMemcpyAsync(field4_out, c->d_field4[c->final_buf].p, 4 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (valid4_out) KC_HIP(hipMemcpyAsync(valid4_out, c->d_valid4.p, n, hipMemcpyDeviceToHost, c->stream));
+  if (turn_valid_out) KC_HIP(hipMemcpyAsync(turn_valid_out, c->d_turn.p, n, hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  if (valid4_out)
+    for (size_t i = 0; i < n; ++i) valid4_out[i] &= 15u;  // the device byte carries the turn bit beside the four classes
+  return KC_OK;
+}
+
+int kc_planner_get_oriented_path(kc_planner *c, int32_t *states_ijk_out, size_t cap, size_t *count_out) {
+  if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  if (!c->solved || !c->or_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_oriented_path before kc_planner_solve_oriented");
+  if (c->status != KC_PLAN_FOUND) return KC_OK;  // no path: zero states
+  KC_TRY(planner_walk(c));
+  *count_out = c->states.size();
+  if (!states_ijk_out) return KC_OK;  // the count alone
+  if (c->states.size() > cap) KC_FAIL(KC_ERR_RANGE, "%zu states do not fit the output capacity %zu", c->states.size(), cap);
+  for (size_t k = 0; k < c->states.size(); ++k) {
+    const int32_t cell = c->states[k] / 4;
+    states_ijk_out[3 * k] = cell % c->W;
+    states_ijk_out[3 * k + 1] = cell / c->W;
+    states_ijk_out[3 * k + 2] = c->states[k] % 4;
   }
   return KC_OK;
 }

@@ -10,7 +10,14 @@ from obstacles: the counterpart, on the grid, of the `max_min_clearance` objecti
 (`third_party/ompl/config.py:120-123`) and of `PathGeometric::clearance`.  `any_angle=True` hands out the any-angle
 path over the same solve (line-of-sight shortcuts between its cells): the counterpart of the `simplifySolution()` the
 reference's wrapper runs on every solve (`src/planning/ompl.cpp:61`).  An 8-connected path is at most 8 % longer than
-the any-angle optimum, so what the shortcut buys is few waypoints and steady headings, not length."""
+the any-angle optimum, so what the shortcut buys is few waypoints and steady headings, not length.
+`footprint="oriented"` (BOX robots) replaces the disc by the box itself over four heading classes (multiples of 45
+degrees, the headings an 8-connected path can have): the robot moves along its own length axis wherever the oriented
+box fits and turns in place only where the whole turning disc fits, so a long box is handed a path through a corridor
+it can take lengthwise.  That is the restricted, deterministic counterpart of the reference's SE(2) planning against
+the real shape.  `goal_yaw` stays unused on purpose: every heading class the box fits in at the goal cell ends the
+path."""
+import math
 from typing import Dict, Optional
 
 import kompass_cpp
@@ -21,13 +28,29 @@ from .models import Robot, RobotGeometry
 class GridPlanner:
     def __init__(self, robot: Robot, allow_unknown: bool = True, margin: float = 0.0, simplify: bool = False,
                  clearance_reach: float = 0.0, clearance_weight: float = 0.0, any_angle: bool = False,
-                 max_span: int = 128):
+                 max_span: int = 128, footprint: str = "disc", turn_cost: float = 1.0):
         """allow_unknown: UNEXPLORED cells can be crossed (default) or block like OCCUPIED ones.
         margin: metres added to the robot's radius.  simplify: drop the interior points of straight runs.
         clearance_reach, clearance_weight: see set_clearance_cost; the defaults leave it off.
         any_angle: solve() returns the any-angle path: from each kept cell the farthest of the next `max_span` cells
         (1 .. 1024) of the 8-connected path in line of sight, and with a clearance cost no closer to a blocking cell
-        than that path came.  `simplify` is then ignored: collinear runs within the span are subsumed."""
+        than that path came.  `simplify` is then ignored: collinear runs within the span are subsumed.
+        footprint: "disc" (default) or "oriented": the box's own footprint over four heading classes, BOX robots only,
+        not together with a clearance cost or `any_angle`.  turn_cost: straight-cell lengths a turn of 45 degrees
+        costs (0.1 .. 1000); `get_cost()` includes the turns."""
+        if footprint not in ("disc", "oriented"):
+            raise ValueError(f"footprint must be 'disc' or 'oriented', got {footprint!r}")
+        self.footprint = footprint
+        if footprint == "oriented":
+            if robot.geometry_type != RobotGeometry.Type.BOX:
+                raise ValueError(f"the oriented footprint needs a BOX robot, got {robot.geometry_type}")
+            if clearance_reach > 0.0 and clearance_weight > 0.0:
+                raise ValueError("the oriented footprint cannot be combined with a clearance cost")
+            if any_angle:
+                raise ValueError("the oriented footprint has no any-angle path: a segment at an arbitrary angle has "
+                                 "no heading class")
+            if not (math.isfinite(turn_cost) and 1 <= math.floor(float(turn_cost) * 10.0 + 0.5) <= 10000):  # lround(turn_cost * 10)
+                raise ValueError(f"turn_cost must be in 0.1 .. 1000 straight-cell lengths, got {turn_cost}")
         if not RobotGeometry.is_valid_parameters(robot.geometry_type, robot.geometry_params):
             raise ValueError(f"invalid geometry parameters {robot.geometry_params} for {robot.geometry_type}")
         self._planner = kompass_cpp.planning.GridPlanner(
@@ -42,11 +65,14 @@ class GridPlanner:
         self.solution = None
         if clearance_reach > 0.0 and clearance_weight > 0.0:
             self.set_clearance_cost(clearance_reach, clearance_weight)
+        if footprint == "oriented":
+            self._planner.set_oriented_footprint(True, float(turn_cost))
 
     def set_clearance_cost(self, reach: float, weight: float):
         """Surcharge the cells within `reach` metres beyond the footprint (radius + margin): `weight` straight-cell
         lengths at the footprint's edge, falling linearly in the squared distance to 0 at the reach.  The path
-        then minimises length plus surcharge.  reach <= 0 or weight <= 0 switches it off."""
+        then minimises length plus surcharge.  reach <= 0 or weight <= 0 switches it off.  Raises with the oriented
+        footprint on."""
         self._planner.set_clearance_cost(float(reach), float(weight))
         self.solution = None
 
@@ -123,6 +149,12 @@ class GridPlanner:
         if self.any_angle:
             return self._planner.get_any_angle_cells(self.max_span)
         return self._planner.get_path_cells(self.simplify)
+
+    def get_path_states(self):
+        """(n, 3) int32 states (i, j, k) of the oriented path: cell and heading class, k = 0 .. 3 for the box's length
+        axis along (1, 0), (1, 1), (0, 1), (-1, 1); a turn repeats its cell.  Empty without a path or with
+        footprint="disc"."""
+        return self._planner.get_path_states()
 
     @property
     def any_angle_length(self) -> float:

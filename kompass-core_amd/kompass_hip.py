@@ -234,6 +234,11 @@ SIGNATURES = {
     "kc_planner_path_clearance": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "kc_planner_shortcut": (C.c_int, [_vp, C.c_int, C.POINTER(_sz), C.POINTER(C.c_uint32)]),
     "kc_planner_get_shortcut": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_set_oriented": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kc_planner_solve_oriented": (C.c_int, [_vp, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_int)]),
+    "kc_planner_get_oriented_field": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, _sz]),
+    "kc_planner_get_oriented_path": (C.c_int, [_vp, C.c_void_p, _sz, C.POINTER(_sz)]),
 }
 
 _lib = None
@@ -1180,3 +1185,35 @@ class PlannerContext(_Owner, _StreamOrdered):
         cells, idx = np.empty((n.value, 2), np.int32), np.empty(n.value, np.int32)
         _check(lib().kc_planner_get_shortcut(self.h, cells.ctypes.data, idx.ctypes.data, n.value, C.byref(n)))
         return cells, idx, v.value
+
+    def set_oriented(self, a2, b2=0, turn10=10):
+        """The oriented box footprint of rules 13 to 18: a2 / b2 the squared half length / half width in cells,
+        turn10 the cost of a turn by one class (a straight step is 10).  a2 = 0 switches it off.  Forgets the last
+        solve."""
+        _check(lib().kc_planner_set_oriented(self.h, int(a2), int(b2), int(turn10)))
+
+    def solve_oriented(self, start, start_class, goal, allow_unknown=True):
+        """-> (status, cost, passes) for the state (start cell, start class): cost = field[start_class][start], the
+        turns included."""
+        s = (C.c_int32 * 2)(int(start[0]), int(start[1]))
+        g = (C.c_int32 * 2)(int(goal[0]), int(goal[1]))
+        st, cost, passes = C.c_int(-1), C.c_uint32(0), C.c_int(0)
+        _check(lib().kc_planner_solve_oriented(self.h, s, int(start_class), g, int(bool(allow_unknown)), C.byref(st),
+                                               C.byref(cost), C.byref(passes)))
+        return st.value, cost.value, passes.value
+
+    def oriented_field(self):
+        """(field uint32 [4, width, height], valid bool [4, width, height], turn_valid bool [width, height]) of the
+        last oriented solve."""
+        w, h = self.shape
+        f = np.empty((4, h, w), np.uint32)   # layer k, then the grid's layout: cell (i, j) at i + j * width
+        v = np.empty((w, h), np.uint8, order="F")
+        t = np.empty((w, h), np.uint8, order="F")
+        _check(lib().kc_planner_get_oriented_field(self.h, f.ctypes.data, v.ctypes.data, t.ctypes.data, v.size))
+        valid = np.stack([(v >> k & 1).astype(bool) for k in range(4)])
+        return f.transpose(0, 2, 1), valid, t.astype(bool)
+
+    def oriented_path(self):
+        """(n, 3) int32 states (i, j, k) of the walk from (start, start class) to the goal; n = 0 when the last
+        oriented solve found none.  path() gives its cells with the repeated cell of a turn collapsed."""
+        return _fill(lib().kc_planner_get_oriented_path, self.h, [(np.int32, (3,))])[0]

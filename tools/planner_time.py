@@ -8,8 +8,13 @@ the table of tests/planner_clearance_ref.py; the solve with the clearance pass, 
 --shortcut W adds the any-angle path (rules 9 to 12) of span W: the walk call and the shortcut call behind it, each
 timed on its own after an untimed solve, the waypoints and the any-angle length against the walk's; with --clearance
 the same on the penalised path.
+--oriented X,Y[,TURN] adds a leg with the oriented box footprint (rules 13 to 18) of an X x Y m box at 0.05 m, start
+class 0, TURN straight-cell lengths a turn (default 1): classification + validity + field, the field alone, their
+difference as the validity's share, the state walk on its own after an untimed solve, the passes, and the CPU statement
+of tests/planner_oriented_ref.py (validity by masks, heap Dijkstra over the states), beside the disc figures of the run.
 
-  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--shortcut 128] [--json out.json]
+  python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--shortcut 128] [--oriented 1.5,0.2]
+                               [--json out.json]
   rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
 """
 import argparse
@@ -27,6 +32,7 @@ for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
     sys.path.insert(0, str(p))
 import kompass_hip as kh  # noqa: E402
 import planner_clearance_ref as cref  # noqa: E402
+import planner_oriented_ref as oref  # noqa: E402
 import planner_ref as ref  # noqa: E402
 import planner_shortcut_ref as sref  # noqa: E402
 import synthetic as syn  # noqa: E402
@@ -121,6 +127,53 @@ def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
         out["shortcut"] = shortcut_leg(ctx, start, goal, r2, a)
     if a.clearance:
         out["clearance"] = clearance_leg(ctx, start, goal, r2, a)
+    if a.oriented:
+        out["oriented"] = oriented_leg(ctx, host_grid, dev_ptr, elem, start, goal, a)
+    return out
+
+
+def oriented_leg(ctx, host_grid, dev_ptr, elem, start, goal, a):
+    """The same grid with the oriented footprint on, then off again."""
+    w, h = host_grid.shape
+    v = [float(x) for x in a.oriented.split(",")]
+    a2, b2 = oref.box_a2_b2((v[0], v[1]), 0.0, 0.05)
+    turn10 = int(round((v[2] if len(v) > 2 else 1.0) * 10))
+    ctx.set_oriented(a2, b2, turn10)
+    ctx.set_grid_device(dev_ptr, w, h, elem)
+    st, cost, passes = ctx.solve_oriented(start, 0, goal)
+    states = ctx.oriented_path()
+    f, valid, turn = ctx.oriented_field()
+    out = dict(a2=a2, b2=b2, turn10=turn10, mask_offsets=[len(oref.oriented_mask(k, a2, b2)) for k in range(4)], status=st,
+               cost=cost, passes=passes, launched=-(-passes // 8) * 8, states=int(len(states)), path_cells=int(len(ctx.path())),
+               turns=int((np.diff(states[:, 2]) != 0).sum()) if len(states) else 0,
+               valid_states=[int(x) for x in valid.sum(axis=(1, 2))], turn_valid_cells=int(turn.sum()))
+
+    def from_device():
+        ctx.set_grid_device(dev_ptr, w, h, elem)   # forgets the validity maps
+        ctx.solve_oriented(start, 0, goal)
+
+    out["device_grid_ms"] = stats_ms(from_device, a.reps)
+    out["resolve_ms"] = stats_ms(lambda: ctx.solve_oriented(start, 0, goal), a.reps)   # validity resident: field only
+    out["validity_ms_by_difference"] = out["device_grid_ms"]["median"] - out["resolve_ms"]["median"]
+    walk_ms = []
+    for k in range(3 + a.reps):
+        ctx.solve_oriented(start, 0, goal)
+        t0 = time.perf_counter()
+        ctx.oriented_path()
+        if k >= 3:
+            walk_ms.append((time.perf_counter() - t0) * 1e3)
+    out["walk_ms"] = dict(median=float(np.median(walk_ms)), min=float(min(walk_ms)), max=float(max(walk_ms)), reps=len(walk_ms))
+    if a.cpu_reps > 0:
+        t0 = time.perf_counter()
+        want_valid, want_turn = oref.oriented_validity(host_grid, a2, b2), oref.turn_validity(host_grid, a2, b2)
+        t1 = time.perf_counter()
+        want = oref.state_field(want_valid, want_turn, goal, turn10)
+        t2 = time.perf_counter()
+        out["cpu_validity_ms"] = dict(median=(t1 - t0) * 1e3, min=(t1 - t0) * 1e3, max=(t1 - t0) * 1e3, reps=1)
+        out["cpu_dijkstra_ms"] = dict(median=(t2 - t1) * 1e3, min=(t2 - t1) * 1e3, max=(t2 - t1) * 1e3, reps=1)
+        assert (valid == want_valid).all() and (turn == want_turn).all() and (f == want).all()
+    ctx.set_oriented(0)
+    ctx.set_grid_device(dev_ptr, w, h, elem)
     return out
 
 
@@ -158,6 +211,7 @@ def main():
     ap.add_argument("--cpu-reps", type=int, default=1)
     ap.add_argument("--clearance", default=None, metavar="REACH_CELLS,WEIGHT10")
     ap.add_argument("--shortcut", type=int, default=0, metavar="W", help="time the any-angle path of span W")
+    ap.add_argument("--oriented", default=None, metavar="X,Y[,TURN]", help="time the oriented footprint of an X x Y m box")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if kh.device_count() < 1:
@@ -202,6 +256,17 @@ def main():
                 print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
             if "shortcut" in c:
                 print_shortcut(c["shortcut"], "    ")
+        o = s.get("oriented")
+        if o:
+            print(f"  oriented footprint A2 {o['a2']}, B2 {o['b2']}, turn {o['turn10']}, offsets {o['mask_offsets']}: status "
+                  f"{o['status']}, cost {o['cost']}, {o['passes']} passes ({o['launched']} launched), {o['states']} states, "
+                  f"{o['path_cells']} path cells, {o['turns']} turns, valid states {o['valid_states']}, turn-valid cells "
+                  f"{o['turn_valid_cells']}")
+            for k in ("device_grid_ms", "resolve_ms", "walk_ms", "cpu_validity_ms", "cpu_dijkstra_ms"):
+                if k in o:
+                    v = o[k]
+                    print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+            print(f"    validity, by difference  {o['validity_ms_by_difference']:10.3f} ms")
     print(json.dumps(out))
     if a.json:
         Path(a.json).parent.mkdir(parents=True, exist_ok=True)
