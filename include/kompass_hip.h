@@ -944,6 +944,35 @@ int kc_planner_get_oriented_field(kc_planner *ctx, uint32_t *field4_out, uint8_t
  * walk's cells with the repeated cell of a turn collapsed; kc_planner_shortcut answers
  * KC_ERR_STATE (a segment at an arbitrary angle has no class). */
 int kc_planner_get_oriented_path(kc_planner *ctx, int32_t *states_ijk_out, size_t cap, size_t *count_out);
+/* Replan from the kept cost field (rules 19 and 20).  Arguments and
+ * outputs as kc_planner_solve, and the same field, validity, status, cost and path bit
+ * for bit; what differs is the work.  A context keeps the field of its last
+ * kc_planner_solve / kc_planner_replan whose goal was a valid cell, and through
+ * kc_planner_set_grid_host / _device of a grid of the same shape also the validity map
+ * and penalty it was made for.  When goal_cell, r2, allow_unknown, the clearance table
+ * and the shape are those of the kept field:
+ *  - no grid was set since (a new start alone): the field stays, no pass runs;
+ *  - else the new grid's maps are made and compared with the kept ones.  A cell is
+ *    touched when its validity differs, or with the clearance cost on when it is valid
+ *    in both and its penalty differs.  T = the minimum over touched cells of min(old
+ *    value, old values of the 8 neighbours inside the grid + 10), 0xFFFFFFFF terms left
+ *    out and 0xFFFFFFFF when there is none: every cell whose old value is below T keeps
+ *    it.  T == 0xFFFFFFFF: the field stays, no pass runs.  Otherwise the cells that are
+ *    valid now and were below T keep their value, the others start at 0xFFFFFFFF (the
+ *    goal at 0), and the passes of kc_planner_solve run over the 64 x 64 tiles whose
+ *    66 x 66 halo region holds a valid cell that was put back to 0xFFFFFFFF.
+ * *passes_out: passes by kc_planner_solve's rule, 0 when none ran; never more than
+ * kc_planner_solve needs on the same grid.  In every other case (no kept field, another
+ * goal, r2, allow_unknown, table or shape) the call is kc_planner_solve, its refusals
+ * included: KC_ERR_STATE with the oriented footprint on. */
+int kc_planner_replan(kc_planner *ctx, const int start_cell[2], const int goal_cell[2], uint32_t r2,
+                      int allow_unknown, int *status_out, uint32_t *cost_out, int *passes_out);
+/* what the last kc_planner_replan did: *replanned_out 1 when it kept a field, 0 when
+ * it was a full solve (or none was made); *threshold_out T, *touched_out the touched
+ * cells, *active_tiles_out the tiles a pass ran over (0xFFFFFFFF, 0, 0 unless a grid
+ * was compared).  Any pointer may be NULL. */
+int kc_planner_replan_info(kc_planner *ctx, int *replanned_out, uint32_t *threshold_out, uint32_t *touched_out,
+                           uint32_t *active_tiles_out);
 
 #ifdef __cplusplus
 }

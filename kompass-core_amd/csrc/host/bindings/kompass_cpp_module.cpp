@@ -998,6 +998,14 @@ PYBIND11_MODULE(kompass_cpp, m) {
              py::gil_scoped_release nogil;
              return p.solve();
            }, py::arg("planning_timeout") = 0.0, "planning_timeout is accepted and unused: the solve is exact and bounded")
+      .def("replan", [](Planning::GridPlanner &p) {
+             py::gil_scoped_release nogil;
+             return p.replan();
+           }, "solve() from the kept cost field after set_grid* and / or setup_problem with the same goal: the same "
+              "outputs, the passes only over what changed; a full solve when nothing can be kept")
+      .def("replanned", &Planning::GridPlanner::replanned, "the last replan() kept a field (false after a full solve)")
+      .def("get_replan_threshold", &Planning::GridPlanner::replanThreshold,
+           "the last replan()'s rollback threshold in field units; 0xFFFFFFFF when nothing was rolled back")
       .def("get_solution", [](Planning::GridPlanner &p, bool simplify) -> py::object {
              auto path = p.getPath(simplify);
              if (!path) return py::none();

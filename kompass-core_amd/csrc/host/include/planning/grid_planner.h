@@ -52,6 +52,15 @@ class GridPlanner {
   void setupProblem(double start_x, double start_y, double start_yaw, double goal_x, double goal_y, double goal_yaw);
   // false (and no path) when the start or the goal is outside the grid or invalid, or the goal out of reach
   bool solve();
+  // solve() from the field the context kept (rules 19 and 20): the same contract and the same outputs bit for bit.
+  // For a robot that follows its plan: after setGrid* with the map's next state and / or setupProblem with the
+  // same goal and a new start.  The passes run only over what the new grid changed, none when only the start
+  // moved.  A full solve, silently, when there is no kept field, the goal, the footprint or the clearance cost
+  // changed, or the oriented footprint is on (replanned() then says false).
+  bool replan();
+  // the last replan() kept a field / its rollback threshold in field units (0xFFFFFFFF: nothing was rolled back)
+  bool replanned() const { return replanned_; }
+  uint32_t replanThreshold() const { return replan_threshold_; }
   std::optional<Path::Path> getPath(bool simplify = false);
   // the cells of that path, (i, j) pairs
   std::vector<int32_t> getPathCells(bool simplify = false);
@@ -139,6 +148,8 @@ class GridPlanner {
   int start_[2] = {-1, -1}, goal_[2] = {-1, -1};
   int status_ = -1, passes_ = 0;
   uint32_t cost_ = 0xFFFFFFFFu;
+  bool replanned_ = false;
+  uint32_t replan_threshold_ = 0xFFFFFFFFu;
   bool clear_on_ = false;
   double reach_ = 0.0;
   uint32_t weight10_ = 0;

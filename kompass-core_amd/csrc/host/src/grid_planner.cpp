@@ -294,10 +294,26 @@ bool GridPlanner::solve() {
   if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
   if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
   status_ = -1;
+  replanned_ = false;
+  replan_threshold_ = 0xFFFFFFFFu;
   if (oriented_on_)
     hip::check(kc_planner_solve_oriented(ctx_.get(), start_, start_class_, goal_, allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
   else
     hip::check(kc_planner_solve(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
+  return status_ == KC_PLAN_FOUND;
+}
+
+bool GridPlanner::replan() {
+  if (oriented_on_) return solve();  // the state field is not kept (rule 20)
+  if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
+  if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
+  status_ = -1;
+  replanned_ = false;
+  replan_threshold_ = 0xFFFFFFFFu;
+  hip::check(kc_planner_replan(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
+  int kept = 0;
+  hip::check(kc_planner_replan_info(ctx_.get(), &kept, &replan_threshold_, nullptr, nullptr));
+  replanned_ = kept != 0;
   return status_ == KC_PLAN_FOUND;
 }
 

@@ -37,11 +37,17 @@
 //      lane; layers 0 and 2 couple along rows and columns, 1 and 3 along the diagonals, all four at the same cell by
 //      a turn.  planner_walk4_kernel is (c) over states: four lanes, the two moves of the class and the two turns.
 //
+//  (g) replan (rules 19 and 20; kc_planner_replan).  The context keeps the field of its last solve, and through a new
+//      grid its validity map and penalty.  planner_touched_kernel compares them with the new grid's and reduces the
+//      rollback threshold T; planner_rollback_kernel puts every value below T back into both buffers and marks the tiles
+//      that hold a cell that may still change; planner_relax_list_kernel is (b) over those tiles only.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "kc_internal.h"
@@ -150,15 +156,16 @@ __global__ __launch_bounds__(kPlanBlock) void planner_init_kernel(uint32_t *a, u
 // one pass over one tile: `in` is only read, `out` only written (the tile's own cells).  PEN: a step pays the
 // penalty of the cell it leaves (rule 7), which is the cell that is relaxed: one more register per owned cell, the
 // same LDS traffic.
+// `tile`: the tile's number, row by row; planner_relax_kernel takes it from blockIdx.x, planner_relax_list_kernel from
+// a list (rule 20).
 template <bool PEN>
-__global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                                     const uint8_t *__restrict__ valid, const uint32_t *__restrict__ pen,
-                                                                     int W, int H, unsigned tiles_x, uint32_t *changed_word,
-                                                                     uint32_t pass) {
+__device__ __forceinline__ void plan_relax_tile(unsigned tile, const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                const uint8_t *__restrict__ valid, const uint32_t *__restrict__ pen, int W, int H,
+                                                unsigned tiles_x, uint32_t *changed_word, uint32_t pass) {
   __shared__ uint32_t f[kPlanHalo * kPlanHalo];
   __shared__ uint8_t v[kPlanHalo * kPlanHalo];
   // the tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more tile rows than gridDim.y holds
-  const int x0 = static_cast<int>(blockIdx.x % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(blockIdx.x / tiles_x) * kPlanTile - 1;
+  const int x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
   for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
     const int lx = k % kPlanHalo, ly = k / kPlanHalo;
     const int gx = x0 + lx, gy = y0 + ly;
@@ -225,6 +232,117 @@ __global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint3
     changed |= cur[r] != orig[r];
   }
   if (__syncthreads_or(changed) && threadIdx.x == 0) *changed_word = pass;
+}
+
+template <bool PEN>
+__global__ __launch_bounds__(kPlanThreads) void planner_relax_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                     const uint8_t *__restrict__ valid, const uint32_t *__restrict__ pen,
+                                                                     int W, int H, unsigned tiles_x, uint32_t *changed_word,
+                                                                     uint32_t pass) {
+  plan_relax_tile<PEN>(blockIdx.x, in, out, valid, pen, W, H, tiles_x, changed_word, pass);
+}
+
+// rule 20: the same pass over the tiles of a list, one workgroup each; the tiles left out hold final values in both
+// buffers, so the halo a listed tile reads from them is what a pass over every tile would have read
+template <bool PEN>
+__global__ __launch_bounds__(kPlanThreads) void planner_relax_list_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                          const uint8_t *__restrict__ valid,
+                                                                          const uint32_t *__restrict__ pen, int W, int H,
+                                                                          unsigned tiles_x, const uint32_t *__restrict__ tiles,
+                                                                          uint32_t *changed_word, uint32_t pass) {
+  plan_relax_tile<PEN>(tiles[blockIdx.x], in, out, valid, pen, W, H, tiles_x, changed_word, pass);
+}
+
+// ---- the replan (rules 19 and 20) --------------------------------------------------------------------------------
+
+// rule 19 in one pass over the cells: a cell whose validity differs, or (PEN) whose penalty differs while it is valid
+// in both maps, is touched; its candidate is the smallest of its old value and its eight neighbours' old values + 10,
+// validity and the corner rule ignored.  out[0] takes the smallest candidate (the host sets it to INF first), out[1]
+// the number of touched cells: a wavefront reduction, then one atomic each per workgroup that saw a touched cell.
+// No wrap: a finite value is at most (14 + max penalty) * (cells - 1), and (14 + max penalty) * cells fits (kc_planner_solve).
+template <bool PEN>
+__global__ __launch_bounds__(kPlanBlock) void planner_touched_kernel(const uint32_t *__restrict__ old, const uint8_t *__restrict__ valid_old,
+                                                                     const uint8_t *__restrict__ valid_new,
+                                                                     const uint32_t *__restrict__ pen_old,
+                                                                     const uint32_t *__restrict__ pen_new, int W, int H, uint32_t *out) {
+  __shared__ uint32_t wave_min[kPlanBlock / 64], wave_cnt[kPlanBlock / 64];
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  uint32_t best = kPlanInf, cnt = 0;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const bool was = valid_old[i] != 0, is = valid_new[i] != 0;
+    bool touched = was != is;
+    if constexpr (PEN) touched = touched || (was && is && pen_old[i] != pen_new[i]);
+    if (!touched) continue;
+    ++cnt;
+    const int x = static_cast<int>(i % W), y = static_cast<int>(i / W);
+    best = min(best, old[i]);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int nx = x + kPlanDx[q], ny = y + kPlanDy[q];
+      if (nx >= 0 && nx < W && ny >= 0 && ny < H) {
+        const uint32_t u = old[static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(nx)];
+        if (u != kPlanInf) best = min(best, u + 10u);
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    best = min(best, static_cast<uint32_t>(__shfl_xor(static_cast<int>(best), d, 64)));
+    cnt += static_cast<uint32_t>(__shfl_xor(static_cast<int>(cnt), d, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wave_min[threadIdx.x >> 6] = best;
+    wave_cnt[threadIdx.x >> 6] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < kPlanBlock / 64; ++k) {
+      best = min(best, wave_min[k]);
+      cnt += wave_cnt[k];
+    }
+    if (cnt) {
+      atomicMin(&out[0], best);
+      atomicAdd(&out[1], cnt);
+    }
+  }
+}
+
+// rule 20's start state, into both field buffers as planner_init_kernel writes its own: the old value where the cell
+// is valid in the new map and below T, INF elsewhere, 0 at a valid goal.  `old` is one of a and b: a lane reads its
+// cell before it writes it, and no lane reads another's.  A valid cell that gets INF (the goal does not) may still
+// change: it marks every tile whose 66 x 66 halo region holds it, i.e. its own and, from a tile's edge, the ones
+// beside it (bytes, zero before the launch; every writer stores a 1).
+__global__ __launch_bounds__(kPlanBlock) void planner_rollback_kernel(const uint32_t *old, uint32_t *a, uint32_t *b,
+                                                                      const uint8_t *__restrict__ valid, int W, int H, long long goal,
+                                                                      uint32_t T, int tiles_x, int tiles_y, uint8_t *active) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const bool ok = valid[i] != 0;
+    const uint32_t o = old[i];
+    uint32_t v = (ok && o < T) ? o : kPlanInf;
+    if (i == goal && ok) v = 0u;
+    a[i] = v;
+    b[i] = v;
+    if (ok && v == kPlanInf) {
+      const int x = static_cast<int>(i % W), y = static_cast<int>(i / W);
+      const int tx = x / kPlanTile, ty = y / kPlanTile, lx = x % kPlanTile, ly = y % kPlanTile;
+      const int tx0 = (lx == 0 && tx > 0) ? tx - 1 : tx, tx1 = (lx == kPlanTile - 1 && tx + 1 < tiles_x) ? tx + 1 : tx;
+      const int ty0 = (ly == 0 && ty > 0) ? ty - 1 : ty, ty1 = (ly == kPlanTile - 1 && ty + 1 < tiles_y) ? ty + 1 : ty;
+      for (int u = ty0; u <= ty1; ++u)
+        for (int t = tx0; t <= tx1; ++t) active[static_cast<size_t>(u) * static_cast<size_t>(tiles_x) + static_cast<size_t>(t)] = 1;
+    }
+  }
+}
+
+// the marked tiles' numbers, in no particular order (a tile writes its own cells only, so the order decides nothing)
+__global__ __launch_bounds__(kPlanBlock) void planner_compact_kernel(const uint8_t *__restrict__ active, unsigned ntiles,
+                                                                     uint32_t *__restrict__ list, uint32_t *count) {
+  const unsigned stride = gridDim.x * kPlanBlock;
+  for (unsigned t = blockIdx.x * kPlanBlock + threadIdx.x; t < ntiles; t += stride)
+    if (active[t]) list[atomicAdd(count, 1u)] = t;
 }
 
 // status words of the walk: out[0] = cells written, out[1] = 0 done / 1 capacity / 2 no descending neighbour.
@@ -624,8 +742,10 @@ struct kc_planner {
   DevBuf<uint32_t> d_pen_by_d2, d_pen;
   DevBuf<uint16_t> d_clear2;
   DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status, [3] its smallest clear2,
-                             // [4..6] the shortcut's count, status and smallest touched clear2
-  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal], [6] d_word[3], [8..10] d_word[4..6]
+                             // [4..6] the shortcut's count, status and smallest touched clear2, [8..10] the replan's T,
+                             // touched cells and listed tiles
+  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal], [6] d_word[3], [8..10] d_word[4..6],
+                             // [12..14] d_word[8..10]
   DevBuf<int32_t> d_path;
   PinBuf<int32_t> h_path;
   bool have_short = false;   // short_idx holds rule 11's indices into `path` for short_span (forgotten with the walk)
@@ -644,6 +764,16 @@ struct kc_planner {
   DevBuf<int16_t> d_offs;
   DevBuf<uint8_t> d_turn, d_valid4;
   DevBuf<uint32_t> d_field4[2];
+  // the replan (rules 19 and 20)
+  bool fld_ok = false;         // d_field[final_buf] is the fixed point of (fld_goal, valid_r2, valid_unknown, the table) on a
+                               // W x H grid whose maps are d_valid (d_pen), the goal valid; a new grid of that shape leaves it
+  int fld_goal[2] = {0, 0};
+  DevBuf<uint8_t> d_valid_old; // the kept field's maps while the new grid's are made
+  DevBuf<uint32_t> d_pen_old;
+  DevBuf<uint8_t> d_tile_on;   // a byte a tile: its halo region holds a cell that may change
+  DevBuf<uint32_t> d_tile_list;
+  bool rp_kept = false;        // the last kc_planner_replan kept a field; T, touched cells, tiles relaxed
+  uint32_t rp_T = kPlanInf, rp_touched = 0, rp_tiles = 0;
 };
 
 namespace {
@@ -665,6 +795,7 @@ int check_grid_shape(const void *grid, int elem_bytes, int width, int height) {
 int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width, int height) {
   const long long n = static_cast<long long>(width) * height;
   c->have_grid = c->have_valid = c->or_have_valid = c->solved = c->have_path = false;
+  if (width != c->W || height != c->H) c->fld_ok = false;  // a kept field (rule 20) is one of this shape
   KC_TRY(c->d_cls.reserve(static_cast<size_t>(n)));
   if (elem_bytes == 4)
     hipLaunchKernelGGL(planner_classify_kernel<int32_t>, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, c->stream,
@@ -798,6 +929,118 @@ int planner_shortcut(kc_planner *c, int max_span) {
   return KC_OK;
 }
 
+// rules 2 and 6: the validity map of (grid, r2, unknown_blocks) into d_valid, and with the clearance cost on clear2 and the
+// penalty beside it; R = isqrt(r2)
+int planner_validity(kc_planner *c, int R, uint32_t r2, int unknown_blocks) {
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const long long n = static_cast<long long>(W) * H;
+  const unsigned blocks = plan_blocks_for(n);
+  c->have_valid = false;
+  KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_valid.reserve(static_cast<size_t>(n)));
+  if (c->clear_c2 > 0) {
+    int Rm = R;
+    while (static_cast<uint32_t>(Rm + 1) * static_cast<uint32_t>(Rm + 1) <= c->clear_c2) ++Rm;  // <= 254: kc_planner_set_clearance_cost
+    KC_TRY(c->d_clear2.reserve(static_cast<size_t>(n)));
+    KC_TRY(c->d_pen.reserve(static_cast<size_t>(n)));
+    hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, Rm, unknown_blocks);
+    hipLaunchKernelGGL(planner_clear_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_pen_by_d2.p, c->d_clear2.p,
+                       c->d_pen.p, c->d_valid.p, W, H, Rm, r2, c->clear_c2);
+  } else {
+    hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
+    hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_valid.p, W, H, R, r2);
+  }
+  KC_HIP(hipGetLastError());
+  c->have_valid = true;
+  c->valid_r2 = r2;
+  c->valid_unknown = unknown_blocks;
+  return KC_OK;
+}
+
+// rule 3's passes to the fixed point, in batches of kPlanBatch with one read-back of the changed word (zero before the
+// first): over every tile (list == nullptr, `blocks` of them) or over the `blocks` tiles of a list (rule 20).  Pass k
+// reads d_field[(k - 1) & 1] and writes d_field[k & 1]; *pass: passes launched, *last_changed: the last that changed a cell.
+int planner_relax(kc_planner *c, const uint32_t *list, unsigned blocks, uint32_t *pass_io, uint32_t *last_changed_out) {
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const bool pen_on = c->clear_c2 > 0;
+  const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile);
+  // every pass that is not the last gives at least one more cell its final value: cells + 1 passes always do
+  const unsigned long long cap = static_cast<unsigned long long>(W) * static_cast<unsigned long long>(H) + 1ull;
+  const uint32_t *pen = pen_on ? c->d_pen.p : nullptr;
+  uint32_t pass = *pass_io;
+  for (;;) {
+    for (int b = 0; b < kPlanBatch; ++b) {
+      ++pass;
+      const uint32_t *in = c->d_field[(pass - 1) & 1].p;
+      uint32_t *out = c->d_field[pass & 1].p;
+      if (list) {
+        if (pen_on)
+          hipLaunchKernelGGL(planner_relax_list_kernel<true>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
+                             tiles_x, list, c->d_word.p, pass);
+        else
+          hipLaunchKernelGGL(planner_relax_list_kernel<false>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
+                             tiles_x, list, c->d_word.p, pass);
+      } else {
+        if (pen_on)
+          hipLaunchKernelGGL(planner_relax_kernel<true>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
+                             tiles_x, c->d_word.p, pass);
+        else
+          hipLaunchKernelGGL(planner_relax_kernel<false>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
+                             tiles_x, c->d_word.p, pass);
+      }
+    }
+    KC_HIP(hipGetLastError());
+    KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipStreamSynchronize(s));
+    *pass_io = pass;
+    *last_changed_out = c->h_word.p[0];
+    if (*last_changed_out < pass) return KC_OK;
+    if (pass >= cap)
+      KC_FAIL(KC_ERR_RANGE, "the cost field of a %d x %d grid still changed after %u passes (cap %llu)", W, H, pass, cap);
+  }
+}
+
+// d_field[final_buf] holds the fixed point for goal_cell: the start's status and cost (rule 4), and what a replan
+// needs to know of this field
+int planner_finish(kc_planner *c, const int start_cell[2], const int goal_cell[2], int *status_out, uint32_t *cost_out) {
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const bool start_in = start_cell[0] >= 0 && start_cell[0] < W && start_cell[1] >= 0 && start_cell[1] < H;
+  const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
+  const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
+  const long long start = start_in ? static_cast<long long>(start_cell[1]) * W + start_cell[0] : -1;
+  c->solved = true;
+  c->start[0] = start_cell[0];
+  c->start[1] = start_cell[1];
+  c->h_word.p[3] = kPlanInf;
+  c->h_word.p[4] = 0;
+  c->h_word.p[5] = 0;
+  if (start_in) {
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[3], c->d_field[c->final_buf].p + start, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[4], c->d_valid.p + start, 1, hipMemcpyDeviceToHost, s));
+  }
+  if (goal_in) KC_HIP(hipMemcpyAsync(&c->h_word.p[5], c->d_valid.p + goal, 1, hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  const bool start_ok = start_in && (c->h_word.p[4] & 0xFFu) != 0, goal_ok = goal_in && (c->h_word.p[5] & 0xFFu) != 0;
+  int st = KC_PLAN_FOUND;
+  if (!start_in) st = KC_PLAN_START_OUTSIDE;
+  else if (!goal_in) st = KC_PLAN_GOAL_OUTSIDE;
+  else if (!start_ok) st = KC_PLAN_START_INVALID;
+  else if (!goal_ok) st = KC_PLAN_GOAL_INVALID;
+  else if (c->h_word.p[3] == kPlanInf) st = KC_PLAN_UNREACHABLE;
+  c->status = st;
+  c->cost = st == KC_PLAN_FOUND ? c->h_word.p[3] : kPlanInf;
+  *status_out = st;
+  if (cost_out) *cost_out = c->cost;
+  // rule 19's proof starts from old(goal) = 0: a field of all INF under an invalid goal is not kept
+  c->fld_ok = goal_ok;
+  c->fld_goal[0] = goal_cell[0];
+  c->fld_goal[1] = goal_cell[1];
+  return KC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -811,7 +1054,7 @@ int kc_planner_create(int device, kc_planner **out) {
   c->device = device;
   c->stream = stream;
   int rc;
-  if ((rc = c->d_word.reserve(8)) || (rc = c->h_word.reserve(12))) {
+  if ((rc = c->d_word.reserve(12)) || (rc = c->h_word.reserve(16))) {
     kc_planner_destroy(c);
     return rc;
   }
@@ -867,38 +1110,16 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int W = c->W, H = c->H;
-  c->solved = c->have_path = c->or_solve = false;
+  c->solved = c->have_path = c->or_solve = c->fld_ok = false;
   c->status = -1;
   c->cost = kPlanInf;
   if (cost_out) *cost_out = kPlanInf;
   if (passes_out) *passes_out = 0;
   const unsigned blocks = plan_blocks_for(n);
   const int unknown_blocks = allow_unknown ? 0 : 1;
-  if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) {
-    c->have_valid = false;
-    KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
-    KC_TRY(c->d_valid.reserve(static_cast<size_t>(n)));
-    if (pen_on) {
-      int Rm = R;
-      while (static_cast<uint32_t>(Rm + 1) * static_cast<uint32_t>(Rm + 1) <= c->clear_c2) ++Rm;  // <= 254: kc_planner_set_clearance_cost
-      KC_TRY(c->d_clear2.reserve(static_cast<size_t>(n)));
-      KC_TRY(c->d_pen.reserve(static_cast<size_t>(n)));
-      hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, Rm, unknown_blocks);
-      hipLaunchKernelGGL(planner_clear_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_pen_by_d2.p, c->d_clear2.p,
-                         c->d_pen.p, c->d_valid.p, W, H, Rm, r2, c->clear_c2);
-    } else {
-      hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
-      hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_valid.p, W, H, R, r2);
-    }
-    KC_HIP(hipGetLastError());
-    c->have_valid = true;
-    c->valid_r2 = r2;
-    c->valid_unknown = unknown_blocks;
-  }
-  const bool start_in = start_cell[0] >= 0 && start_cell[0] < W && start_cell[1] >= 0 && start_cell[1] < H;
+  if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) KC_TRY(planner_validity(c, R, r2, unknown_blocks));
   const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
   const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
-  const long long start = start_in ? static_cast<long long>(start_cell[1]) * W + start_cell[0] : -1;
   KC_TRY(c->d_field[0].reserve(static_cast<size_t>(n)));
   KC_TRY(c->d_field[1].reserve(static_cast<size_t>(n)));
   hipLaunchKernelGGL(planner_init_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, goal);
@@ -906,57 +1127,97 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   KC_HIP(hipGetLastError());
   uint32_t pass = 0, last_changed = 0;
   if (goal_in) {
-    // every pass that is not the last gives at least one more cell its final value: cells + 1 passes always do
-    const unsigned long long cap = static_cast<unsigned long long>(n) + 1ull;
     // at most 2^28 / 64 tiles (a one-cell-wide grid), within gridDim.x
     const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile), tiles_y = static_cast<unsigned>((H + kPlanTile - 1) / kPlanTile);
-    const dim3 tiles(tiles_x * tiles_y);
-    for (;;) {
-      for (int b = 0; b < kPlanBatch; ++b) {
-        ++pass;
-        if (pen_on)
-          hipLaunchKernelGGL(planner_relax_kernel<true>, tiles, dim3(kPlanThreads), 0, s, c->d_field[(pass - 1) & 1].p,
-                             c->d_field[pass & 1].p, c->d_valid.p, c->d_pen.p, W, H, tiles_x, c->d_word.p, pass);
-        else
-          hipLaunchKernelGGL(planner_relax_kernel<false>, tiles, dim3(kPlanThreads), 0, s, c->d_field[(pass - 1) & 1].p,
-                             c->d_field[pass & 1].p, c->d_valid.p, static_cast<const uint32_t *>(nullptr), W, H, tiles_x,
-                             c->d_word.p, pass);
-      }
-      KC_HIP(hipGetLastError());
-      KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      KC_HIP(hipStreamSynchronize(s));
-      last_changed = c->h_word.p[0];
-      if (last_changed < pass) break;
-      if (pass >= cap)
-        KC_FAIL(KC_ERR_RANGE, "the cost field of a %d x %d grid still changed after %u passes (cap %llu)", W, H, pass, cap);
-    }
+    KC_TRY(planner_relax(c, nullptr, tiles_x * tiles_y, &pass, &last_changed));
   }
   c->final_buf = static_cast<int>(pass & 1u);
-  c->solved = true;
-  c->start[0] = start_cell[0];
-  c->start[1] = start_cell[1];
-  c->h_word.p[3] = kPlanInf;
-  c->h_word.p[4] = 0;
-  c->h_word.p[5] = 0;
-  if (start_in) {
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[3], c->d_field[c->final_buf].p + start, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[4], c->d_valid.p + start, 1, hipMemcpyDeviceToHost, s));
-  }
-  if (goal_in) KC_HIP(hipMemcpyAsync(&c->h_word.p[5], c->d_valid.p + goal, 1, hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
-  const bool start_ok = start_in && (c->h_word.p[4] & 0xFFu) != 0, goal_ok = goal_in && (c->h_word.p[5] & 0xFFu) != 0;
-  int st = KC_PLAN_FOUND;
-  if (!start_in) st = KC_PLAN_START_OUTSIDE;
-  else if (!goal_in) st = KC_PLAN_GOAL_OUTSIDE;
-  else if (!start_ok) st = KC_PLAN_START_INVALID;
-  else if (!goal_ok) st = KC_PLAN_GOAL_INVALID;
-  else if (c->h_word.p[3] == kPlanInf) st = KC_PLAN_UNREACHABLE;
-  c->status = st;
-  c->cost = st == KC_PLAN_FOUND ? c->h_word.p[3] : kPlanInf;
-  *status_out = st;
-  if (cost_out) *cost_out = c->cost;
+  KC_TRY(planner_finish(c, start_cell, goal_cell, status_out, cost_out));
   // passes a batch of one would have run: the last that changed a cell and the one that found nothing to change
   if (passes_out) *passes_out = goal_in ? static_cast<int>(last_changed + 1u) : 0;
+  return KC_OK;
+}
+
+int kc_planner_replan(kc_planner *c, const int start_cell[2], const int goal_cell[2], uint32_t r2, int allow_unknown,
+                      int *status_out, uint32_t *cost_out, int *passes_out) {
+  if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  c->rp_kept = false;
+  c->rp_T = kPlanInf;
+  c->rp_touched = c->rp_tiles = 0;
+  const int unknown_blocks = allow_unknown ? 0 : 1;
+  // rule 20's fall-back: no kept field, or one of another problem; every refusal of kc_planner_solve is its own
+  if (!c->have_grid || c->or_a2 > 0 || !c->fld_ok || c->fld_goal[0] != goal_cell[0] || c->fld_goal[1] != goal_cell[1] ||
+      c->valid_r2 != r2 || c->valid_unknown != unknown_blocks)
+    return kc_planner_solve(c, start_cell, goal_cell, r2, allow_unknown, status_out, cost_out, passes_out);
+  // r2, the penalty table and the shape are the kept solve's: its range checks hold
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const long long n = static_cast<long long>(W) * H;
+  const bool pen_on = c->clear_c2 > 0;
+  c->solved = c->have_path = c->or_solve = c->fld_ok = false;
+  c->status = -1;
+  c->cost = kPlanInf;
+  if (cost_out) *cost_out = kPlanInf;
+  if (passes_out) *passes_out = 0;
+  uint32_t T = kPlanInf, touched = 0, listed = 0, pass = 0, last_changed = 0;
+  if (!c->have_valid) {  // a grid was set since: rule 19 against its maps; otherwise nothing is touched
+    const unsigned blocks = plan_blocks_for(n);
+    std::swap(c->d_valid, c->d_valid_old);
+    if (pen_on) std::swap(c->d_pen, c->d_pen_old);
+    int R = 0;
+    while (static_cast<uint32_t>(R + 1) * static_cast<uint32_t>(R + 1) <= r2) ++R;  // <= 254: the kept solve's
+    KC_TRY(planner_validity(c, R, r2, unknown_blocks));
+    uint32_t *old = c->d_field[c->final_buf].p;
+    KC_HIP(hipMemsetAsync(c->d_word.p + 8, 0xFF, sizeof(uint32_t), s));
+    KC_HIP(hipMemsetAsync(c->d_word.p + 9, 0, 2 * sizeof(uint32_t), s));
+    if (pen_on)
+      hipLaunchKernelGGL(planner_touched_kernel<true>, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_valid_old.p, c->d_valid.p,
+                         c->d_pen_old.p, c->d_pen.p, W, H, c->d_word.p + 8);
+    else
+      hipLaunchKernelGGL(planner_touched_kernel<false>, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_valid_old.p, c->d_valid.p,
+                         static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr), W, H, c->d_word.p + 8);
+    KC_HIP(hipGetLastError());
+    KC_HIP(hipMemcpyAsync(&c->h_word.p[12], c->d_word.p + 8, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipStreamSynchronize(s));
+    T = c->h_word.p[12];
+    touched = c->h_word.p[13];
+    if (T != kPlanInf) {
+      const int tiles_x = (W + kPlanTile - 1) / kPlanTile, tiles_y = (H + kPlanTile - 1) / kPlanTile;
+      const unsigned ntiles = static_cast<unsigned>(tiles_x) * static_cast<unsigned>(tiles_y);
+      KC_TRY(c->d_tile_on.reserve(ntiles));
+      KC_TRY(c->d_tile_list.reserve(ntiles));
+      KC_HIP(hipMemsetAsync(c->d_tile_on.p, 0, ntiles, s));
+      hipLaunchKernelGGL(planner_rollback_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_field[0].p, c->d_field[1].p,
+                         c->d_valid.p, W, H, static_cast<long long>(goal_cell[1]) * W + goal_cell[0], T, tiles_x, tiles_y, c->d_tile_on.p);
+      hipLaunchKernelGGL(planner_compact_kernel, dim3(plan_blocks_for(ntiles)), dim3(kPlanBlock), 0, s, c->d_tile_on.p, ntiles,
+                         c->d_tile_list.p, c->d_word.p + 10);
+      KC_HIP(hipMemsetAsync(c->d_word.p, 0, 4 * sizeof(uint32_t), s));
+      KC_HIP(hipGetLastError());
+      KC_HIP(hipMemcpyAsync(&c->h_word.p[14], c->d_word.p + 10, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      KC_HIP(hipStreamSynchronize(s));
+      listed = c->h_word.p[14];
+      if (listed > ntiles) KC_FAIL(KC_ERR_STATE, "%u tiles listed of %u", listed, ntiles);
+      // both buffers hold the rollback state, so pass 1 reads either
+      if (listed) KC_TRY(planner_relax(c, c->d_tile_list.p, listed, &pass, &last_changed));
+      c->final_buf = static_cast<int>(pass & 1u);
+    }
+  }
+  KC_TRY(planner_finish(c, start_cell, goal_cell, status_out, cost_out));
+  if (passes_out) *passes_out = listed ? static_cast<int>(last_changed + 1u) : 0;
+  c->rp_kept = true;
+  c->rp_T = T;
+  c->rp_touched = touched;
+  c->rp_tiles = listed;
+  return KC_OK;
+}
+
+int kc_planner_replan_info(kc_planner *c, int *replanned_out, uint32_t *threshold_out, uint32_t *touched_out, uint32_t *active_tiles_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (replanned_out) *replanned_out = c->rp_kept ? 1 : 0;
+  if (threshold_out) *threshold_out = c->rp_T;
+  if (touched_out) *touched_out = c->rp_touched;
+  if (active_tiles_out) *active_tiles_out = c->rp_tiles;
   return KC_OK;
 }
 
@@ -1006,7 +1267,7 @@ int kc_planner_set_clearance_cost(kc_planner *c, uint32_t c2, const uint32_t *pe
     c->clear_max_pen = *std::max_element(pen_by_d2, pen_by_d2 + n);
   }
   c->clear_c2 = on ? c2 : 0u;
-  c->have_valid = c->solved = c->have_path = false;  // clear2 and the penalty come with the validity pass
+  c->have_valid = c->solved = c->have_path = c->fld_ok = false;  // clear2 and the penalty come with the validity pass
   c->status = -1;
   return KC_OK;
 }
@@ -1070,7 +1331,7 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (a2 == 0) {
     c->or_a2 = c->or_b2 = c->or_turn10 = 0;
-    c->or_have_valid = c->solved = c->have_path = c->or_solve = false;
+    c->or_have_valid = c->solved = c->have_path = c->or_solve = c->fld_ok = false;
     c->status = -1;
     return KC_OK;
   }
@@ -1098,7 +1359,7 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
   c->or_a2 = a2;
   c->or_b2 = b2;
   c->or_turn10 = turn10;
-  c->solved = c->have_path = c->or_solve = false;
+  c->solved = c->have_path = c->or_solve = c->fld_ok = false;  // the oriented solve shares final_buf
   c->status = -1;
   return KC_OK;
 }

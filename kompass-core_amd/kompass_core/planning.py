@@ -63,6 +63,7 @@ class GridPlanner:
         if self.any_angle and not 1 <= self.max_span <= 1024:
             raise ValueError(f"max_span must be in 1 .. 1024, got {max_span}")
         self.solution = None
+        self._problem = None   # the last setup_problem's (start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw)
         if clearance_reach > 0.0 and clearance_weight > 0.0:
             self.set_clearance_cost(clearance_reach, clearance_weight)
         if footprint == "oriented":
@@ -104,11 +105,42 @@ class GridPlanner:
                 self._planner.set_grid(grid)
         self._planner.setup_problem(start_x=start_x, start_y=start_y, start_yaw=start_yaw, goal_x=goal_x,
                                     goal_y=goal_y, goal_yaw=goal_yaw)
+        self._problem = (start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw)
         self.solution = None
 
     def solve(self) -> Optional["kompass_cpp.types.Path"]:
         """The path, or None when the start or goal is outside the grid, invalid, or the goal out of reach."""
-        if not self._planner.solve():
+        return self._solution(self._planner.solve())
+
+    def replan(self, map=None, start=None) -> Optional["kompass_cpp.types.Path"]:
+        """solve() for the goal of the last setup_problem from the cost field the planner kept: the same path, at the
+        cost of what changed.  map: the map's next state, a grid as setup_problem takes it (same shape and
+        metadata), or None for the grid as it is.  start: the robot's new (x, y) or (x, y, yaw), or None.  With only a
+        new start no pass runs; with a new map the passes run over the part of the field a changed cell can reach.
+        Falls back to a full solve by itself where nothing can be kept (`replanned` says which it was)."""
+        if self._problem is None:
+            raise RuntimeError("replan needs a setup_problem first: it keeps that goal")
+        if map is not None:
+            mapper = map._mapper if hasattr(map, "_mapper") else map
+            if mapper is None:
+                raise ValueError("the LocalMapper has no grid yet: update it from a scan first")
+            if isinstance(mapper, kompass_cpp.mapping.LocalMapper):
+                self._planner.set_grid_from_mapper(mapper)
+            else:
+                self._planner.set_grid(mapper)
+        if start is not None:
+            yaw = float(start[2]) if len(start) > 2 else self._problem[2]
+            p = self._problem = (float(start[0]), float(start[1]), yaw) + self._problem[3:]
+            self._planner.setup_problem(start_x=p[0], start_y=p[1], start_yaw=p[2], goal_x=p[3], goal_y=p[4], goal_yaw=p[5])
+        return self._solution(self._planner.replan())
+
+    @property
+    def replanned(self) -> bool:
+        """The last replan() kept a field; False after a solve() and after a replan() that had to solve in full."""
+        return self._planner.replanned()
+
+    def _solution(self, found):
+        if not found:
             self.solution = None
         elif self.any_angle:
             self.solution = self._planner.get_any_angle_solution(self.max_span)

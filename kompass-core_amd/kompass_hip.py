@@ -239,6 +239,10 @@ SIGNATURES = {
                                             C.POINTER(C.c_int)]),
     "kc_planner_get_oriented_field": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, _sz]),
     "kc_planner_get_oriented_path": (C.c_int, [_vp, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_replan": (C.c_int, [_vp, _ip, _ip, C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_int)]),
+    "kc_planner_replan_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
 }
 
 _lib = None
@@ -1217,3 +1221,22 @@ class PlannerContext(_Owner, _StreamOrdered):
         """(n, 3) int32 states (i, j, k) of the walk from (start, start class) to the goal; n = 0 when the last
         oriented solve found none.  path() gives its cells with the repeated cell of a turn collapsed."""
         return _fill(lib().kc_planner_get_oriented_path, self.h, [(np.int32, (3,))])[0]
+
+    def replan(self, start, goal, r2=0, allow_unknown=True):
+        """solve() from the field the context kept (rules 19 and 20): the same outputs bit for bit, the passes only
+        over what a grid set since the last solve changed, none when only the start moved.  A full solve when
+        there is no kept field or goal, r2, allow_unknown, the clearance table or the shape differ.
+        -> (status, cost, passes)."""
+        s = (C.c_int32 * 2)(int(start[0]), int(start[1]))
+        g = (C.c_int32 * 2)(int(goal[0]), int(goal[1]))
+        st, cost, passes = C.c_int(-1), C.c_uint32(0), C.c_int(0)
+        _check(lib().kc_planner_replan(self.h, s, g, int(r2), int(bool(allow_unknown)), C.byref(st), C.byref(cost),
+                                       C.byref(passes)))
+        return st.value, cost.value, passes.value
+
+    def replan_info(self):
+        """(replanned, threshold, touched, active_tiles) of the last replan(): whether it kept a field, rule 19's T
+        (PLAN_INF: nothing to roll back), the touched cells and the tiles a pass ran over."""
+        kept, t, touched, tiles = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(lib().kc_planner_replan_info(self.h, C.byref(kept), C.byref(t), C.byref(touched), C.byref(tiles)))
+        return bool(kept.value), t.value, touched.value, tiles.value

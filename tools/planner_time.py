@@ -12,9 +12,14 @@ the same on the penalised path.
 class 0, TURN straight-cell lengths a turn (default 1): classification + validity + field, the field alone, their
 difference as the validity's share, the state walk on its own after an untimed solve, the passes, and the CPU statement
 of tests/planner_oriented_ref.py (validity by masks, heap Dijkstra over the states), beside the disc figures of the run.
+--replan adds the replan (rules 19 and 20) on both scenes, from host arrays, alternating in one process: (a) a full
+solve of the changed grid, (b) kc_planner_replan of the same grid behind an untimed solve of the unchanged one, the
+change a 5 x 5 blocked patch on the path 10 %, 50 % and 90 % of the way from the start, and (c) the replan with only
+the start moved (no grid set); milliseconds, passes, the threshold, the touched cells and the tiles relaxed; with
+--clearance the same with the cost on.
 
   python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--shortcut 128] [--oriented 1.5,0.2]
-                               [--json out.json]
+                               [--replan] [--json out.json]
   rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
 """
 import argparse
@@ -78,6 +83,71 @@ def print_shortcut(c, indent):
         print(f"{indent}  {k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
 
 
+def replan_leg(ctx, host_grid, start, goal, r2, a):
+    """(a), (b) and (c) of the module's text on the grid and cost the context holds."""
+    ctx.set_grid(host_grid)
+    ctx.solve(start, goal, r2)
+    path = ctx.path()
+    out = dict(legs=[])
+    st = lambda t: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), reps=len(t))  # noqa: E731
+    for pct in (10, 50, 90):
+        ci, cj = (int(v) for v in path[len(path) * pct // 100])
+        changed = host_grid.copy()
+        changed[max(ci - 2, 0):ci + 3, max(cj - 2, 0):cj + 3] = 100
+        full_ms, replan_ms = [], []
+        for k in range(3 + a.reps):
+            t0 = time.perf_counter()
+            ctx.set_grid(changed)
+            full = ctx.solve(start, goal, r2)
+            t1 = time.perf_counter()
+            ctx.set_grid(host_grid)
+            ctx.solve(start, goal, r2)
+            t2 = time.perf_counter()
+            ctx.set_grid(changed)
+            got = ctx.replan(start, goal, r2)
+            t3 = time.perf_counter()
+            if k >= 3:
+                full_ms.append((t1 - t0) * 1e3)
+                replan_ms.append((t3 - t2) * 1e3)
+        kept, T, touched, tiles = ctx.replan_info()
+        assert kept and got[:2] == full[:2]
+        w, h = host_grid.shape
+        out["legs"].append(dict(percent=pct, patch=[ci, cj], status=got[0], cost=got[1], full_solve_ms=st(full_ms), full_passes=full[2],
+                                replan_ms=st(replan_ms), replan_passes=got[2], threshold=T, touched=touched, active_tiles=tiles,
+                                tiles=-(-w // 64) * -(-h // 64)))
+    ctx.set_grid(host_grid)
+    ctx.solve(start, goal, r2)
+    moved = tuple(int(v) for v in path[len(path) // 10])
+    t = []
+    for k in range(3 + a.reps):
+        t0 = time.perf_counter()
+        got = ctx.replan(moved if k % 2 else start, goal, r2)
+        if k >= 3:
+            t.append((time.perf_counter() - t0) * 1e3)
+    assert ctx.replan_info() == (True, 0xFFFFFFFF, 0, 0) and got[2] == 0
+    out["start_moved_ms"] = st(t)
+    t = []
+    for k in range(3 + a.reps):
+        ctx.replan(moved if k % 2 else start, goal, r2)
+        t0 = time.perf_counter()
+        ctx.path()
+        if k >= 3:
+            t.append((time.perf_counter() - t0) * 1e3)
+    out["walk_behind_it_ms"] = st(t)
+    return out
+
+
+def print_replan(r, indent):
+    for leg in r["legs"]:
+        f, p = leg["full_solve_ms"], leg["replan_ms"]
+        print(f"{indent}patch at {leg['percent']} % of the path {leg['patch']}: full solve {f['median']:.3f} ms [{f['min']:.3f}, {f['max']:.3f}] "
+              f"{leg['full_passes']} passes; replan {p['median']:.3f} ms [{p['min']:.3f}, {p['max']:.3f}] {leg['replan_passes']} passes, "
+              f"{leg['active_tiles']} of {leg['tiles']} tiles, T {leg['threshold']}, {leg['touched']} touched, cost {leg['cost']}")
+    for k in ("start_moved_ms", "walk_behind_it_ms"):
+        v = r[k]
+        print(f"{indent}{k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+
+
 def device_name():
     try:
         out = subprocess.run(["rocminfo"], capture_output=True, text=True, timeout=30).stdout
@@ -125,8 +195,10 @@ def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
         assert (f == ref.cost_field(valid, goal)).all() and (v == valid).all()
     if a.shortcut:
         out["shortcut"] = shortcut_leg(ctx, start, goal, r2, a)
+    if a.replan:
+        out["replan"] = replan_leg(ctx, np.asarray(host_grid), start, goal, r2, a)
     if a.clearance:
-        out["clearance"] = clearance_leg(ctx, start, goal, r2, a)
+        out["clearance"] = clearance_leg(ctx, np.asarray(host_grid), start, goal, r2, a)
     if a.oriented:
         out["oriented"] = oriented_leg(ctx, host_grid, dev_ptr, elem, start, goal, a)
     return out
@@ -177,7 +249,7 @@ def oriented_leg(ctx, host_grid, dev_ptr, elem, start, goal, a):
     return out
 
 
-def clearance_leg(ctx, start, goal, r2, a):
+def clearance_leg(ctx, host_grid, start, goal, r2, a):
     """The same grid (resident) with the clearance cost on, then off again."""
     reach, wt = (int(v) for v in a.clearance.split(","))
     c2 = min(int((r2 ** 0.5 + reach) ** 2), cref.MAX_C2)
@@ -201,6 +273,8 @@ def clearance_leg(ctx, start, goal, r2, a):
     out["resolve_and_walk_ms"] = stats_ms(walk, a.reps)
     if a.shortcut:
         out["shortcut"] = shortcut_leg(ctx, start, goal, r2, a)
+    if a.replan:
+        out["replan"] = replan_leg(ctx, host_grid, start, goal, r2, a)
     ctx.set_clearance_cost(0)
     return out
 
@@ -212,6 +286,7 @@ def main():
     ap.add_argument("--clearance", default=None, metavar="REACH_CELLS,WEIGHT10")
     ap.add_argument("--shortcut", type=int, default=0, metavar="W", help="time the any-angle path of span W")
     ap.add_argument("--oriented", default=None, metavar="X,Y[,TURN]", help="time the oriented footprint of an X x Y m box")
+    ap.add_argument("--replan", action="store_true", help="time the replan against a full solve of the changed grid")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if kh.device_count() < 1:
@@ -246,6 +321,8 @@ def main():
                 print(f"  {k:22s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
         if "shortcut" in s:
             print_shortcut(s["shortcut"], "  ")
+        if "replan" in s:
+            print_replan(s["replan"], "  ")
         c = s.get("clearance")
         if c:
             print(f"  clearance cost C2 {c['c2']}, weight {c['weight10']}: status {c['status']}, cost {c['cost']}, length "
@@ -256,6 +333,8 @@ def main():
                 print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
             if "shortcut" in c:
                 print_shortcut(c["shortcut"], "    ")
+            if "replan" in c:
+                print_replan(c["replan"], "    ")
         o = s.get("oriented")
         if o:
             print(f"  oriented footprint A2 {o['a2']}, B2 {o['b2']}, turn {o['turn10']}, offsets {o['mask_offsets']}: status "
