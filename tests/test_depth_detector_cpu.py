@@ -1,13 +1,15 @@
 """DepthDetector surface without a GPU: the vision types with the reference's constructors, fields and validation
 (datatypes/tracking.h, bindings_types.cpp:188-235), Bbox2D(PointsOfInterest) against the restatement, the
 restatement against closed-form answers of the reference test's scenarios (tests/test_depth_detector.py), the
-conversion-factor and frame checks, and no CPU fallback."""
+conversion-factor and frame checks, no CPU fallback, and the claims, raw intervals and chunk sizes of the edge scenes
+(depth_scenes.py) that test_depth_detector_edges_gpu.py runs on the device."""
 import math
 
 import numpy as np
 import pytest
 
 import kompass_cpp
+import depth_scenes
 import kompass_hip as kh
 from depth_detector_ref import Detector, box_from_pois
 from kompass_core.datatypes import Bbox2D, Bbox3D, PointsOfInterest
@@ -127,6 +129,44 @@ def test_restatement_median_and_band():
     assert (n, float(med), float(mad), float(mn), float(mx)) == (5, 3.0, 1.0, 2.0, 4.0)
     (n, med, mad, _, _), = det.stats(img, [(0, 0, 3, 0)])  # 1, 2, 3, 4: even
     assert (n, float(med), float(mad)) == (4, 2.5, 1.0)
+
+
+def scene_on_restatement(name):
+    """(stats, kept) of every box of a scene, from the restatement alone."""
+    frame, boxes, depth_range, factor, claim = depth_scenes.SCENES[name].build()
+    det = Detector(np.array(depth_range, np.float32), [0, 0, 0], [0, 0, 0, 1], [1, 1], [0, 0], factor)
+    kept = [depth_scenes.kept_values(frame, b, depth_range, factor) for b in boxes]
+    return det.stats(frame, boxes), kept, claim
+
+
+@pytest.mark.parametrize("name", list(depth_scenes.SCENES))
+def test_scene_claims_hold_on_the_restatement(name):
+    """Every edge scene of test_depth_detector_edges_gpu.py is what it says it is: its claim holds on the
+    restatement's statistics and on the kept values, and the restatement counted exactly the kept values."""
+    assert depth_scenes.SCENES[name].build()[3] in (1.0, 0.5)
+    stats, kept, claim = scene_on_restatement(name)
+    assert [s[0] for s in stats] == [len(k) for k in kept]
+    assert claim(stats, kept)
+
+
+@pytest.mark.parametrize("name", list(depth_scenes.SCENES))
+def test_scene_raw_interval_and_chunk(name):
+    """The raw interval [d_lo, d_lo + nbins) by the rule of kc_depth_create (convert all 65536 values, keep
+    min <= v <= max), recomputed value by value, and the chunk size it selects."""
+    scene = depth_scenes.SCENES[name]
+    _, _, depth_range, factor, _ = scene.build()
+    lo, hi = -1, -2
+    for d in range(65536):
+        v = np.float32(d) * np.float32(factor)
+        if v <= np.float32(depth_range[1]) and v >= np.float32(depth_range[0]):
+            lo, hi = (d if lo < 0 else lo), d
+        elif lo >= 0:
+            break  # float(d) * factor is non-decreasing: nothing is kept after the first value above max
+    assert (lo, hi - lo + 1) == depth_scenes.raw_interval(depth_range, factor)
+    assert hi - lo + 1 == scene.nbins
+    assert scene.chunk == (8192 if scene.nbins <= 16384 else 32768)
+    if name.startswith(("counter_", "chunk_")):  # named after the chunk size they are built for
+        assert scene.chunk == next(int(t) for t in name.split("_") if t in ("8192", "32768"))
 
 
 def test_conversion_factor_and_frame_checks():
