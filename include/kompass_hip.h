@@ -974,6 +974,98 @@ int kc_planner_replan(kc_planner *ctx, const int start_cell[2], const int goal_c
 int kc_planner_replan_info(kc_planner *ctx, int *replanned_out, uint32_t *threshold_out, uint32_t *touched_out,
                            uint32_t *active_tiles_out);
 
+/* ------------------------------------------------------------------------ */
+/* World map: the mapper's egocentric grids fused on the device */
+/* ------------------------------------------------------------------------ */
+typedef struct kc_worldmap kc_worldmap;
+
+/* Nothing in the reference to cite for the method: it leaves the world-frame map to
+ * its ROS side.  This is the layer between kc_mapper (an egocentric grid that turns
+ * with the robot) and kc_planner_replan (which wants a world-frame map that changes):
+ * the map lives on the device, is updated from each local grid where that grid lies
+ * and is read in place by kc_planner_set_grid_device(ctx, cls, 1, width, height).
+ *
+ * The map is width x height cells, cell (I, J) at I + J * width (the planner's
+ * layout), (origin_x, origin_y) the world position of cell (0, 0)'s centre.  Two int8
+ * planes: evidence (-128 never observed, else e_min .. e_max) and cls (KC_UNEXPLORED
+ * while never observed, KC_OCCUPIED when evidence >= occ_thr, KC_EMPTY otherwise).
+ * Integers only, and independent of thread order: DESIGN.md 4.11 has the rules, the
+ * tests hold every plane to them bit for bit.  KC_ERR_RANGE above 32768 cells a side
+ * or KC_PLANNER_MAX_CELLS cells. */
+typedef struct kc_worldmap_pose { /* the local grid's frame in the map, 16 fraction bits */
+  int32_t cq, sq;                 /* lrint(cos(yaw) * 65536), lrint(sin(yaw) * 65536) */
+  int64_t tx, ty;                 /* llrint((p - origin) / resolution * 65536) per axis */
+} kc_worldmap_pose;
+typedef struct kc_worldmap_result { /* what an update did to the cls plane */
+  uint32_t changed;                 /* cells whose cls byte changed */
+  int32_t i_min, j_min, i_max, j_max; /* their bounding box in cells; all -1 when changed == 0 */
+} kc_worldmap_result;
+
+/* a map of never-observed cells with the default model (hit 3, miss 1, e_min -8, e_max
+ * 14, occ_thr 1).  The shape is checked before the device is looked for. */
+int kc_worldmap_create(int device, int width, int height, float resolution, double origin_x, double origin_y,
+                       kc_worldmap **out);
+void kc_worldmap_destroy(kc_worldmap *ctx);
+/* the geometry given to kc_worldmap_create; any pointer may be NULL */
+int kc_worldmap_info(kc_worldmap *ctx, int *width_out, int *height_out, float *resolution_out, double *origin_x_out,
+                     double *origin_y_out);
+/* The update model: an observation of KC_OCCUPIED adds hit (up to e_max), one of
+ * KC_EMPTY takes miss away (down to e_min), a never-observed cell counts from 0.
+ * hit, miss in 1 .. 127, e_min in -127 .. 0, e_max in 0 .. 127, e_min < occ_thr <=
+ * e_max, KC_ERR_INVALID otherwise (kc_worldmap_check_model is that test alone: host
+ * only).  hit = miss = 127, e_min = -127, e_max = 127: the latest observation wins.
+ * Evidence counted by one model means nothing under another: set_model clears the map. */
+int kc_worldmap_check_model(int hit, int miss, int e_min, int e_max, int occ_thr);
+int kc_worldmap_set_model(kc_worldmap *ctx, int hit, int miss, int e_min, int e_max, int occ_thr);
+/* The pose (px, py, yaw) of a local grid's frame in a map of this resolution and
+ * origin, quantised as kc_worldmap_pose says; all of it in double, cos / sin from
+ * libm, lrint / llrint to nearest even.  Host only: it takes the map's geometry
+ * rather than a context, so that it works without a device.  KC_ERR_RANGE when the pose
+ * lies more than 2^20 cells from the origin, KC_ERR_INVALID for anything non-finite. */
+int kc_worldmap_quantise_pose(float resolution, double origin_x, double origin_y, double px, double py, double yaw,
+                              kc_worldmap_pose *out);
+/* what every update checks of its local grid before the device is used (host only):
+ * positive sides, central cell within 2^30, and `resolution` the very float
+ * `world_resolution` is (KC_ERR_INVALID: resampling is out of scope) */
+int kc_worldmap_check_grid(float world_resolution, int grid_height, int grid_width, int central_i, int central_j,
+                           float resolution);
+/* One update from a local grid: int32, column-major [grid_height x grid_width] (the
+ * LocalMapper layout, kc_mapper_grid_device), local cell (i, j) the point ((i -
+ * central_i) res, (j - central_j) res) of the frame `pose` places in the map -- the
+ * frame of kc_dwa_set_grid_device.  Every map cell looks up the one local cell it
+ * falls into (a gather: no holes under rotation, no write conflicts); KC_OCCUPIED and
+ * KC_EMPTY observations count, every other value and every cell outside the local
+ * grid leaves the map cell as it is.  One kernel launch and the read-back of *out; the
+ * call returns with the map finished, so a planner may read it at once.
+ * _device: the grid where it lies on ctx's device, finished (KC_ERR_INVALID, before
+ * any read, unless it is device memory of ctx's device inside one allocation);
+ * _host: one copy up. */
+int kc_worldmap_update_device(kc_worldmap *ctx, const int32_t *dev_grid, int grid_height, int grid_width, int central_i,
+                              int central_j, float resolution, const kc_worldmap_pose *pose, kc_worldmap_result *out);
+int kc_worldmap_update_host(kc_worldmap *ctx, const int32_t *grid, int grid_height, int grid_width, int central_i,
+                            int central_j, float resolution, const kc_worldmap_pose *pose, kc_worldmap_result *out);
+/* same, from a mapper context of this library: geometry and stream ordering (event
+ * wait, no host synchronisation of the mapper) are taken from it, as
+ * kc_dwa_set_grid_from_mapper does */
+int kc_worldmap_update_from_mapper(kc_worldmap *ctx, struct kc_mapper *mapper, const kc_worldmap_pose *pose,
+                                   kc_worldmap_result *out);
+/* A prior replaces the whole state: a grid of the map's shape and layout, int8 or int32
+ * (elem_bytes 1 or 4; kc_cloud_grid_device gives the former): KC_OCCUPIED -> e_max,
+ * KC_EMPTY -> e_min, anything else never observed.  KC_ERR_INVALID for another shape.
+ * _device reads a finished grid in place, checked as above; kc_worldmap_after_stream
+ * orders that read (and kc_worldmap_update_device's) after the work queued so far on a
+ * producer's stream, as kc_planner_after_stream does. */
+int kc_worldmap_set_prior_host(kc_worldmap *ctx, const void *grid, int elem_bytes, int width, int height);
+int kc_worldmap_set_prior_device(kc_worldmap *ctx, const void *dev_grid, int elem_bytes, int width, int height);
+int kc_worldmap_after_stream(kc_worldmap *ctx, void *stream);
+/* every cell never observed again */
+int kc_worldmap_clear(kc_worldmap *ctx);
+/* the cls plane on the device (int8, width x height): valid until destroy, finished
+ * whenever no call on ctx is running */
+int kc_worldmap_grid_device(kc_worldmap *ctx, void **dev_cls_int8);
+/* copies of the planes, cap the cells either output holds; either pointer may be NULL */
+int kc_worldmap_get(kc_worldmap *ctx, int8_t *cls_out, int8_t *evidence_out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "controllers/rgbd_follower.h"
 #include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
+#include "mapping/world_map.h"
 #include "planning/grid_planner.h"
 #include "utils/logger.h"
 #include "utils/critical_zone_check.h"
@@ -299,6 +300,79 @@ void plannerSetGrid(Planning::GridPlanner &p, const py::object &o) {
   }
   py::gil_scoped_release nogil;
   p.setGridOnDevice(ptr, elem);
+}
+
+// WorldMap.device_grid: the cls plane where it lies, as an object with __cuda_array_interface__ -- (width, height)
+// int8 in column-major strides, the form GridPlanner.set_grid reads in place.  `stream` is None: the map is
+// finished whenever no call on it is running.  Keeps the map alive.
+struct WorldMapDeviceGrid {
+  py::object map;
+  uint64_t ptr;
+  int width, height;
+};
+py::dict worldMapInterface(const WorldMapDeviceGrid &g) {
+  py::dict d;
+  d["shape"] = py::make_tuple(g.width, g.height);
+  d["typestr"] = "|i1";
+  d["data"] = py::make_tuple(g.ptr, false);
+  d["strides"] = py::make_tuple(1, g.width);
+  d["version"] = 3;
+  d["stream"] = py::none();
+  return d;
+}
+
+// WorldMap.set_prior: a (width, height) int32 or int8 grid, grid[I, J] the cell (I, J) -- a numpy array (any memory
+// order), or a device array with __cuda_array_interface__ in column-major strides, read in place (cf. plannerSetGrid)
+void worldMapSetPrior(Mapping::WorldMap &m, const py::object &o) {
+  if (!py::hasattr(o, "__cuda_array_interface__")) {
+    const py::array a = py::cast<py::array>(o);
+    if (a.ndim() != 2) throw std::invalid_argument("the prior must be 2-D (width, height)");
+    const int w = static_cast<int>(a.shape(0)), h = static_cast<int>(a.shape(1));
+    if (a.dtype().num() == py::dtype::of<int8_t>().num()) {
+      const auto g = py::array_t<int8_t, py::array::f_style>::ensure(a);
+      const void *d = g.data();
+      py::gil_scoped_release nogil;
+      m.setPrior(d, 1, w, h);
+    } else if (a.dtype().num() == py::dtype::of<int32_t>().num()) {
+      const auto g = py::array_t<int32_t, py::array::f_style>::ensure(a);
+      const void *d = g.data();
+      py::gil_scoped_release nogil;
+      m.setPrior(d, 4, w, h);
+    } else {
+      throw py::type_error("the prior must be int32 or int8, got " + py::str(a.dtype()).cast<std::string>());
+    }
+    return;
+  }
+  const py::dict d = o.attr("__cuda_array_interface__");
+  const std::string ts = py::cast<std::string>(d["typestr"]);
+  int elem = 0;
+  if (ts == "<i4" || ts == "=i4") elem = 4;
+  else if (ts == "|i1" || ts == "<i1" || ts == "=i1") elem = 1;
+  else throw py::type_error("the prior must be int32 or int8, got typestr " + ts);
+  const auto shape = py::cast<std::vector<int64_t>>(d["shape"]);
+  if (shape.size() != 2) throw std::invalid_argument("the prior must be 2-D (width, height)");
+  if (d.contains("mask") && !d["mask"].is_none()) throw std::invalid_argument("masked grids are not supported");
+  if (!d.contains("strides") || d["strides"].is_none()) {
+    if (shape[0] != 1 && shape[1] != 1) throw std::invalid_argument("a device prior must be column-major: grid[I, J] at I + J * width");
+  } else {
+    const auto st = py::cast<std::vector<int64_t>>(d["strides"]);
+    if (st.size() != 2 || (shape[0] > 1 && st[0] != elem) || (shape[1] > 1 && st[1] != elem * shape[0]))
+      throw std::invalid_argument("a device prior must be column-major: grid[I, J] at I + J * width");
+  }
+  if (shape[0] > 0x7FFFFFFF || shape[1] > 0x7FFFFFFF) throw std::out_of_range("the prior is too large");
+  const py::tuple data = d["data"];
+  const void *ptr = reinterpret_cast<const void *>(static_cast<uintptr_t>(py::cast<uint64_t>(data[0])));
+  if (!d.contains("stream") || !d["stream"].is_none()) {
+    void *stream = nullptr;
+    if (d.contains("stream")) {
+      const uint64_t h = py::cast<uint64_t>(d["stream"]);
+      if (h == 0) throw std::invalid_argument("__cuda_array_interface__ stream 0 is not allowed");
+      stream = h == 1 ? nullptr : reinterpret_cast<void *>(static_cast<uintptr_t>(h));
+    }
+    m.waitForStream(stream);
+  }
+  py::gil_scoped_release nogil;
+  m.setPriorOnDevice(ptr, elem, static_cast<int>(shape[0]), static_cast<int>(shape[1]));
 }
 
 void fromDict(Parameters &p, const py::dict &d) {
@@ -870,6 +944,63 @@ PYBIND11_MODULE(kompass_cpp, m) {
            }), py::arg("grid_height"), py::arg("grid_width"), py::arg("resolution"), py::arg("laserscan_position"),
            py::arg("laserscan_orientation"), py::arg("is_pointcloud"), py::arg("scan_size"), py::arg("angle_step"),
            py::arg("max_height"), py::arg("min_height"), py::arg("range_max"), py::arg("max_points_per_line") = 32);
+
+  // not in the reference, which leaves the world-frame map to its ROS side
+  py::class_<WorldMapDeviceGrid>(mp, "WorldMapDeviceGrid")
+      .def_property_readonly("__cuda_array_interface__", &worldMapInterface)
+      .def_property_readonly("shape", [](const WorldMapDeviceGrid &g) { return py::make_tuple(g.width, g.height); });
+  auto plane = [](const std::vector<int8_t> &v, int w, int h) {
+    py::array_t<int8_t, py::array::f_style> a({(py::ssize_t)w, (py::ssize_t)h});
+    if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size());
+    return a;
+  };
+  py::class_<Mapping::WorldMap>(mp, "WorldMap")
+      .def(py::init([](int width, int height, float resolution, double origin_x, double origin_y) {
+             return std::make_unique<Mapping::WorldMap>(width, height, resolution, origin_x, origin_y);
+           }), py::arg("width"), py::arg("height"), py::arg("resolution"), py::arg("origin_x") = 0.0, py::arg("origin_y") = 0.0)
+      .def("set_model", &Mapping::WorldMap::setModel, py::arg("hit") = 3, py::arg("miss") = 1, py::arg("e_min") = -8,
+           py::arg("e_max") = 14, py::arg("occ_thr") = 1,
+           "Evidence an OCCUPIED / EMPTY observation adds / takes away within e_min .. e_max, OCCUPIED from occ_thr up; clears the map")
+      .def("set_prior", &worldMapSetPrior, py::arg("grid"),
+           "A (width, height) int32 / int8 grid replaces the state: a numpy array, or a device array read in place")
+      .def("update", [](Mapping::WorldMap &m, const Mapping::LocalMapper &mapper, double x, double y, double yaw) {
+             py::gil_scoped_release nogil;
+             return m.update(mapper, x, y, yaw);
+           }, py::arg("mapper"), py::arg("x"), py::arg("y"), py::arg("yaw"),
+           "Fuse the mapper's last grid where it lies on the device; (x, y, yaw): the robot's pose in the world.  -> changed cells")
+      .def("update", [](Mapping::WorldMap &m, const py::array &grid, double x, double y, double yaw) {
+             if (grid.ndim() != 2 || grid.dtype().num() != py::dtype::of<int32_t>().num())
+               throw std::invalid_argument("the local grid must be a 2-D int32 array (grid_height, grid_width)");
+             const auto g = py::array_t<int32_t, py::array::f_style>::ensure(grid);
+             const int32_t *d = g.data();
+             const int gh = static_cast<int>(g.shape(0)), gw = static_cast<int>(g.shape(1));
+             py::gil_scoped_release nogil;
+             return m.update(d, gh, gw, x, y, yaw);
+           }, py::arg("grid"), py::arg("x"), py::arg("y"), py::arg("yaw"),
+           "Fuse a (grid_height, grid_width) int32 grid from the host, the mapper's central cell.  -> changed cells")
+      .def("clear", &Mapping::WorldMap::clear)
+      .def("get_cls", [plane](const Mapping::WorldMap &m) { return plane(m.cls(), m.width(), m.height()); },
+           "the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied")
+      .def("get_evidence", [plane](const Mapping::WorldMap &m) { return plane(m.evidence(), m.width(), m.height()); },
+           "the evidence plane, int8 [width, height]: -128 never observed")
+      .def("get_changed", &Mapping::WorldMap::changed, "cells whose class the last update changed")
+      .def("get_changed_box", [](const Mapping::WorldMap &m) {
+             const auto b = m.changedBox();
+             return py::make_tuple(b[0], b[1], b[2], b[3]);
+           }, "(i_min, j_min, i_max, j_max) of those cells; all -1 when there are none")
+      .def("device_grid", [](py::object self) {
+             const auto &m = self.cast<const Mapping::WorldMap &>();
+             return WorldMapDeviceGrid{self, static_cast<uint64_t>(reinterpret_cast<uintptr_t>(m.deviceGrid())), m.width(), m.height()};
+           }, "The class plane on the device: an object with __cuda_array_interface__ that GridPlanner.set_grid reads in place")
+      .def_static("quantise_pose", [](float resolution, double origin_x, double origin_y, double x, double y, double yaw) {
+             const kc_worldmap_pose p = Mapping::WorldMap::quantisePose(resolution, origin_x, origin_y, x, y, yaw);
+             return py::make_tuple(p.cq, p.sq, p.tx, p.ty);
+           }, py::arg("resolution"), py::arg("origin_x"), py::arg("origin_y"), py::arg("x"), py::arg("y"), py::arg("yaw"),
+           "(cq, sq, tx, ty): the pose as the update takes it, 16 fraction bits; needs no device")
+      .def_property_readonly("width", &Mapping::WorldMap::width)
+      .def_property_readonly("height", &Mapping::WorldMap::height)
+      .def_property_readonly("resolution", &Mapping::WorldMap::resolution)
+      .def_property_readonly("origin", [](const Mapping::WorldMap &m) { return py::make_tuple(m.originX(), m.originY()); });
 
   // ----------------------------------------------------------------- utils
   // (bindings_utils.cpp:47-129, bindings_gpu.cpp:40-68)

@@ -1,0 +1,72 @@
+// World-frame occupancy map that stays on the device, fused from the LocalMapper's egocentric grids
+// (kc_worldmap_*, csrc/kc_worldmap.hip).
+//
+// Nothing in the reference to restate: it leaves the world-frame map to its ROS side.  This is the map between
+// Mapping::LocalMapper, whose grid turns with the robot and forgets what leaves its window, and
+// Planning::GridPlanner::replan, which wants a world-frame map that changes: seeded from a prior (the PCD grid),
+// updated from each local grid where that grid lies, read in place by the planner.
+#pragma once
+
+#include <array>
+#include <cstdint>
+#include <vector>
+
+#include "mapping/local_mapper.h"
+#include "utils/hip_backend.h"
+
+namespace Kompass {
+namespace Mapping {
+
+class WorldMap {
+ public:
+  // width x height cells, cell (I, J) at I + J * width; (origin_x, origin_y): the world position of cell (0, 0)'s
+  // centre.  std::invalid_argument / std::out_of_range for a bad shape, before a device is looked for.
+  WorldMap(int width, int height, float resolution, double origin_x = 0.0, double origin_y = 0.0);
+
+  // hit / miss: evidence an OCCUPIED / EMPTY observation adds / takes away, within e_min .. e_max; a cell is
+  // OCCUPIED from occ_thr up.  Clears the map.
+  void setModel(int hit, int miss, int e_min, int e_max, int occ_thr);
+  // A grid of the map's shape and layout, int8 or int32 (elem_bytes 1 or 4): OCCUPIED -> e_max, EMPTY -> e_min,
+  // anything else never observed.  Replaces the whole state.  The device overload reads a finished grid in place.
+  void setPrior(const void *host_grid, int elem_bytes, int width, int height);
+  void setPriorOnDevice(const void *dev_grid, int elem_bytes, int width, int height);
+  // orders the next device grid's read after the work queued so far on a producer's stream (no host wait)
+  void waitForStream(void *stream);
+
+  // One update from the mapper's last grid where it lies on the device, ordered after its scan without a host
+  // wait; (x, y, yaw): the robot's pose in the world, i.e. the pose of the grid's frame.  Returns changed().
+  uint32_t update(const LocalMapper &mapper, double x, double y, double yaw);
+  // ... from a grid on the host: int32, column-major grid_height x grid_width, the mapper's central cell
+  uint32_t update(const int32_t *grid, int grid_height, int grid_width, double x, double y, double yaw);
+  // ... from a finished grid on the device, read in place
+  uint32_t updateOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw);
+  void clear();
+
+  // copies of the planes, width x height as the map
+  std::vector<int8_t> cls() const;
+  std::vector<int8_t> evidence() const;
+  // the last update: cells whose class changed and their box (i_min, j_min, i_max, j_max), all -1 when none did
+  uint32_t changed() const { return last_.changed; }
+  std::array<int, 4> changedBox() const { return {last_.i_min, last_.j_min, last_.i_max, last_.j_max}; }
+  // the cls plane on the device: int8, width x height, what GridPlanner::setGridOnDevice(ptr, 1) reads in place
+  const void *deviceGrid() const;
+
+  int width() const { return width_; }
+  int height() const { return height_; }
+  float resolution() const { return res_; }
+  double originX() const { return ox_; }
+  double originY() const { return oy_; }
+  kc_worldmap *hipContext() const { return ctx_.get(); }
+  // the pose as the kernel takes it; needs no device
+  static kc_worldmap_pose quantisePose(float resolution, double origin_x, double origin_y, double x, double y, double yaw);
+
+ private:
+  int width_, height_;
+  float res_;
+  double ox_, oy_;
+  hip::WorldMapHandle ctx_;
+  kc_worldmap_result last_ = {0, -1, -1, -1, -1};
+};
+
+}  // namespace Mapping
+}  // namespace Kompass

@@ -39,6 +39,7 @@ using CloudHandle = Handle<kc_cloud, kc_cloud_destroy>;
 using ZoneHandle = Handle<kc_zone, kc_zone_destroy>;
 using DepthHandle = Handle<kc_depth, kc_depth_destroy>;
 using PlannerHandle = Handle<kc_planner, kc_planner_destroy>;
+using WorldMapHandle = Handle<kc_worldmap, kc_worldmap_destroy>;
 // The two shared contexts (sampler, evaluator and controller work on one kc_dwa): made from a Dwa / Comm, which
 // keeps the context while the control block is allocated.
 using DwaHandle = std::shared_ptr<kc_dwa>;

@@ -1,0 +1,78 @@
+// WorldMap host side: argument plumbing over kc_worldmap_* (no reference counterpart, see the header).
+#include "mapping/world_map.h"
+
+namespace Kompass {
+namespace Mapping {
+
+WorldMap::WorldMap(int width, int height, float resolution, double origin_x, double origin_y)
+    : width_(width), height_(height), res_(resolution), ox_(origin_x), oy_(origin_y),
+      ctx_(hip::make<hip::WorldMapHandle>(kc_worldmap_create, 0, width, height, resolution, origin_x, origin_y)) {}
+
+void WorldMap::setModel(int hit, int miss, int e_min, int e_max, int occ_thr) {
+  hip::check(kc_worldmap_set_model(ctx_.get(), hit, miss, e_min, e_max, occ_thr));
+  last_ = {0, -1, -1, -1, -1};
+}
+
+void WorldMap::setPrior(const void *host_grid, int elem_bytes, int width, int height) {
+  hip::check(kc_worldmap_set_prior_host(ctx_.get(), host_grid, elem_bytes, width, height));
+  last_ = {0, -1, -1, -1, -1};
+}
+
+void WorldMap::setPriorOnDevice(const void *dev_grid, int elem_bytes, int width, int height) {
+  hip::check(kc_worldmap_set_prior_device(ctx_.get(), dev_grid, elem_bytes, width, height));
+  last_ = {0, -1, -1, -1, -1};
+}
+
+void WorldMap::waitForStream(void *stream) { hip::check(kc_worldmap_after_stream(ctx_.get(), stream)); }
+
+kc_worldmap_pose WorldMap::quantisePose(float resolution, double origin_x, double origin_y, double x, double y, double yaw) {
+  kc_worldmap_pose p{};
+  hip::check(kc_worldmap_quantise_pose(resolution, origin_x, origin_y, x, y, yaw, &p));
+  return p;
+}
+
+uint32_t WorldMap::update(const LocalMapper &mapper, double x, double y, double yaw) {
+  const kc_worldmap_pose p = quantisePose(res_, ox_, oy_, x, y, yaw);
+  hip::check(kc_worldmap_update_from_mapper(ctx_.get(), mapper.hipContext(), &p, &last_));
+  return last_.changed;
+}
+
+uint32_t WorldMap::update(const int32_t *grid, int grid_height, int grid_width, double x, double y, double yaw) {
+  const kc_worldmap_pose p = quantisePose(res_, ox_, oy_, x, y, yaw);
+  hip::check(kc_worldmap_update_host(ctx_.get(), grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_, &p,
+                                     &last_));
+  return last_.changed;
+}
+
+uint32_t WorldMap::updateOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw) {
+  const kc_worldmap_pose p = quantisePose(res_, ox_, oy_, x, y, yaw);
+  hip::check(kc_worldmap_update_device(ctx_.get(), dev_grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_,
+                                       &p, &last_));
+  return last_.changed;
+}
+
+void WorldMap::clear() {
+  hip::check(kc_worldmap_clear(ctx_.get()));
+  last_ = {0, -1, -1, -1, -1};
+}
+
+std::vector<int8_t> WorldMap::cls() const {
+  std::vector<int8_t> out(static_cast<size_t>(width_) * static_cast<size_t>(height_));
+  hip::check(kc_worldmap_get(ctx_.get(), out.data(), nullptr, out.size()));
+  return out;
+}
+
+std::vector<int8_t> WorldMap::evidence() const {
+  std::vector<int8_t> out(static_cast<size_t>(width_) * static_cast<size_t>(height_));
+  hip::check(kc_worldmap_get(ctx_.get(), nullptr, out.data(), out.size()));
+  return out;
+}
+
+const void *WorldMap::deviceGrid() const {
+  void *p = nullptr;
+  hip::check(kc_worldmap_grid_device(ctx_.get(), &p));
+  return p;
+}
+
+}  // namespace Mapping
+}  // namespace Kompass

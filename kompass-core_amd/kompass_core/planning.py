@@ -22,6 +22,7 @@ from typing import Dict, Optional
 
 import kompass_cpp
 
+from .mapping.world_map import WorldMap
 from .models import Robot, RobotGeometry
 
 
@@ -83,8 +84,11 @@ class GridPlanner:
         sits at (origin_x + i * resolution, origin_y + j * resolution).
         grid: an int32 / int8 numpy array grid[i, j]; a device array with `__cuda_array_interface__` in
         column-major strides (read in place); a `kompass_cpp.mapping.LocalMapper` or the front end's
-        `kompass_core.mapping.LocalMapper` (its last grid on the device; map_meta_data may then be None); or None
-        to keep the grid of the last call."""
+        `kompass_core.mapping.LocalMapper` (its last grid on the device; map_meta_data may then be None); a
+        `kompass_core.mapping.WorldMap` (its class plane on the device and its metadata; map_meta_data may be None);
+        or None to keep the grid of the last call."""
+        if isinstance(grid, WorldMap):
+            map_meta_data, grid = grid.map_meta_data, grid.device_grid
         mapper = grid
         if hasattr(grid, "_mapper"):  # the front end's LocalMapper holds the class once it has mapped a scan
             mapper = grid._mapper
@@ -121,6 +125,8 @@ class GridPlanner:
         if self._problem is None:
             raise RuntimeError("replan needs a setup_problem first: it keeps that goal")
         if map is not None:
+            if isinstance(map, WorldMap):
+                map = map.device_grid
             mapper = map._mapper if hasattr(map, "_mapper") else map
             if mapper is None:
                 raise ValueError("the LocalMapper has no grid yet: update it from a scan first")

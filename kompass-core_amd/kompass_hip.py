@@ -92,6 +92,21 @@ class DvzZone(C.Structure):
                 ("center_shift_x", C.c_double), ("center_shift_y", C.c_double), ("ori_shift", C.c_double)]
 
 
+class WorldMapPose(C.Structure):
+    """kc_worldmap_pose: the local grid's frame in the map, 16 fraction bits."""
+    _fields_ = [("cq", C.c_int32), ("sq", C.c_int32), ("tx", C.c_int64), ("ty", C.c_int64)]
+
+
+class WorldMapResult(C.Structure):
+    """kc_worldmap_result: what an update did to the cls plane."""
+    _fields_ = [("changed", C.c_uint32), ("i_min", C.c_int32), ("j_min", C.c_int32), ("i_max", C.c_int32),
+                ("j_max", C.c_int32)]
+
+    def as_tuple(self):
+        """(changed, (i_min, j_min, i_max, j_max)); the box is all -1 when nothing changed."""
+        return int(self.changed), (int(self.i_min), int(self.j_min), int(self.i_max), int(self.j_max))
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -243,6 +258,25 @@ SIGNATURES = {
                                     C.POINTER(C.c_int)]),
     "kc_planner_replan_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32)]),
+    "kc_worldmap_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_double, C.POINTER(_vp)]),
+    "kc_worldmap_destroy": (None, [_vp]),
+    "kc_worldmap_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _dp, _dp]),
+    "kc_worldmap_check_model": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kc_worldmap_set_model": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kc_worldmap_quantise_pose": (C.c_int, [C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.POINTER(WorldMapPose)]),
+    "kc_worldmap_check_grid": (C.c_int, [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "kc_worldmap_update_device": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                            C.POINTER(WorldMapPose), C.POINTER(WorldMapResult)]),
+    "kc_worldmap_update_host": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.POINTER(WorldMapPose), C.POINTER(WorldMapResult)]),
+    "kc_worldmap_update_from_mapper": (C.c_int, [_vp, _vp, C.POINTER(WorldMapPose), C.POINTER(WorldMapResult)]),
+    "kc_worldmap_set_prior_host": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "kc_worldmap_set_prior_device": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "kc_worldmap_after_stream": (C.c_int, [_vp, C.c_void_p]),
+    "kc_worldmap_clear": (C.c_int, [_vp]),
+    "kc_worldmap_grid_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "kc_worldmap_get": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
 }
 
 _lib = None
@@ -1240,3 +1274,109 @@ class PlannerContext(_Owner, _StreamOrdered):
         kept, t, touched, tiles = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         _check(lib().kc_planner_replan_info(self.h, C.byref(kept), C.byref(t), C.byref(touched), C.byref(tiles)))
         return bool(kept.value), t.value, touched.value, tiles.value
+
+
+def worldmap_check_model(hit=3, miss=1, e_min=-8, e_max=14, occ_thr=1):
+    """The test kc_worldmap_set_model makes of its parameters (host only); raises ValueError."""
+    _check(lib().kc_worldmap_check_model(int(hit), int(miss), int(e_min), int(e_max), int(occ_thr)))
+
+
+def worldmap_check_grid(world_resolution, grid_height, grid_width, central, resolution):
+    """The test every world map update makes of its local grid before the device is used (host only)."""
+    _check(lib().kc_worldmap_check_grid(float(np.float32(world_resolution)), int(grid_height), int(grid_width),
+                                        int(central[0]), int(central[1]), float(np.float32(resolution))))
+
+
+def worldmap_quantise_pose(resolution, origin, x, y, yaw) -> WorldMapPose:
+    """(x, y, yaw) of a local grid's frame in a map of this resolution and origin -> WorldMapPose (host only)."""
+    p = WorldMapPose()
+    _check(lib().kc_worldmap_quantise_pose(float(np.float32(resolution)), float(origin[0]), float(origin[1]), float(x),
+                                           float(y), float(yaw), C.byref(p)))
+    return p
+
+
+class WorldMapContext(_Owner, _StreamOrdered):
+    """Owner of one kc_worldmap context: a world-frame map on the device, fused from local grids.
+    Works in cells: a plane is an array m[I, J] of (width, height) cells, I along x, as PlannerContext's grids."""
+    _kc = "kc_worldmap"
+
+    def __init__(self, width, height, resolution, origin=(0.0, 0.0), device=0):
+        self.shape = (int(width), int(height))
+        self.resolution = float(np.float32(resolution))
+        self.origin = (float(origin[0]), float(origin[1]))
+        self._open(lib().kc_worldmap_create, int(device), self.shape[0], self.shape[1], self.resolution, self.origin[0],
+                   self.origin[1])
+
+    def set_model(self, hit=3, miss=1, e_min=-8, e_max=14, occ_thr=1):
+        """The update model; clears the map."""
+        _check(lib().kc_worldmap_set_model(self.h, int(hit), int(miss), int(e_min), int(e_max), int(occ_thr)))
+
+    def quantise_pose(self, x, y, yaw) -> WorldMapPose:
+        return worldmap_quantise_pose(self.resolution, self.origin, x, y, yaw)
+
+    def _pose(self, pose):
+        return pose if isinstance(pose, WorldMapPose) else self.quantise_pose(*pose)
+
+    @staticmethod
+    def _central(grid_height, grid_width, central):
+        # the mapper's central cell (local_mapper.h:26-27)
+        return (grid_height // 2 - 1, grid_width // 2 - 1) if central is None else central
+
+    def update(self, grid, pose, central=None, resolution=None):
+        """grid: int32 [grid_height, grid_width] on the host (MapperContext.scan_to_grid's form), any memory order;
+        pose: (x, y, yaw) of its frame in the world, or a WorldMapPose.  -> (changed, (i_min, j_min, i_max, j_max))."""
+        g = np.asarray(grid)
+        if g.ndim != 2 or g.dtype != np.int32:
+            raise ValueError("expected a 2-D int32 grid")
+        g = np.asfortranarray(g)  # local cell (i, j) at i + j * grid_height
+        c = self._central(g.shape[0], g.shape[1], central)
+        p, r = self._pose(pose), WorldMapResult()
+        _check(lib().kc_worldmap_update_host(self.h, g.ctypes.data, g.shape[0], g.shape[1], int(c[0]), int(c[1]),
+                                             self.resolution if resolution is None else float(np.float32(resolution)),
+                                             C.byref(p), C.byref(r)))
+        return r.as_tuple()
+
+    def update_device(self, device_ptr, grid_height, grid_width, pose, central=None, resolution=None):
+        """A finished int32 grid on the context's device, column-major [grid_height x grid_width], read in place."""
+        c = self._central(int(grid_height), int(grid_width), central)
+        p, r = self._pose(pose), WorldMapResult()
+        _check(lib().kc_worldmap_update_device(self.h, int(device_ptr), int(grid_height), int(grid_width), int(c[0]),
+                                               int(c[1]),
+                                               self.resolution if resolution is None else float(np.float32(resolution)),
+                                               C.byref(p), C.byref(r)))
+        return r.as_tuple()
+
+    def update_from_mapper(self, mapper: "MapperContext", pose):
+        """The last grid of a MapperContext where it lies, ordered after its scan without a host wait."""
+        p, r = self._pose(pose), WorldMapResult()
+        _check(lib().kc_worldmap_update_from_mapper(self.h, mapper.h, C.byref(p), C.byref(r)))
+        return r.as_tuple()
+
+    def set_prior(self, grid):
+        """grid[I, J]: an int32 or int8 (width, height) array on the host; replaces the whole state."""
+        g = np.asarray(grid)
+        if g.ndim != 2 or g.dtype not in (np.int32, np.int8):
+            raise ValueError("expected a 2-D int32 or int8 grid")
+        g = np.asfortranarray(g)
+        _check(lib().kc_worldmap_set_prior_host(self.h, g.ctypes.data, g.itemsize, g.shape[0], g.shape[1]))
+
+    def set_prior_device(self, device_ptr, width, height, elem_bytes=1):
+        """A finished grid of the map's shape on the context's device (CloudContext.occupancy_grid(to_host=False):
+        int8), read in place."""
+        _check(lib().kc_worldmap_set_prior_device(self.h, int(device_ptr), int(elem_bytes), int(width), int(height)))
+
+    def clear(self):
+        _check(lib().kc_worldmap_clear(self.h))
+
+    def grid_device_ptr(self) -> int:
+        """The cls plane on the device: int8, (width, height), what PlannerContext.set_grid_device(ptr, width, height,
+        elem_bytes=1) reads in place."""
+        return _out(_vp, lib().kc_worldmap_grid_device, self.h)
+
+    def planes(self):
+        """(cls int8 [width, height], evidence int8 [width, height]) copied to the host."""
+        w, h = self.shape
+        c = np.empty((w, h), np.int8, order="F")
+        e = np.empty((w, h), np.int8, order="F")
+        _check(lib().kc_worldmap_get(self.h, c.ctypes.data, e.ctypes.data, c.size))
+        return c, e
