@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <memory>
 #include <optional>
+#include <stdexcept>
 #include <vector>
 
 #include "datatypes/path.h"
@@ -165,7 +166,12 @@ class GridPlanner {
   void applyOriented();
   void applyClearanceCost();
   void needBounds() const;
+  void needDiscMode() const {  // the any-angle calls: a segment at an arbitrary angle has no heading class (rule 18)
+    if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
+  }
   void forgetSolve();
+  void beginSolve();
+  Path::Path cellsToPath(const std::vector<int32_t> &ij) const;  // (i, j) pairs -> the cells' world points
 };
 
 }  // namespace Planning

@@ -290,12 +290,17 @@ void GridPlanner::setupProblem(double start_x, double start_y, double start_yaw,
   status_ = -1;
 }
 
-bool GridPlanner::solve() {
+// what solve() and replan() start with
+void GridPlanner::beginSolve() {
   if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
   if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
   status_ = -1;
   replanned_ = false;
   replan_threshold_ = 0xFFFFFFFFu;
+}
+
+bool GridPlanner::solve() {
+  beginSolve();
   if (oriented_on_)
     hip::check(kc_planner_solve_oriented(ctx_.get(), start_, start_class_, goal_, allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
   else
@@ -305,11 +310,7 @@ bool GridPlanner::solve() {
 
 bool GridPlanner::replan() {
   if (oriented_on_) return solve();  // the state field is not kept (rule 20)
-  if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
-  if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
-  status_ = -1;
-  replanned_ = false;
-  replan_threshold_ = 0xFFFFFFFFu;
+  beginSolve();
   hip::check(kc_planner_replan(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
   int kept = 0;
   hip::check(kc_planner_replan_info(ctx_.get(), &kept, &replan_threshold_, nullptr, nullptr));
@@ -347,14 +348,17 @@ std::vector<int32_t> GridPlanner::getPathCells(bool simplify) {
   return out;
 }
 
-std::optional<Path::Path> GridPlanner::getPath(bool simplify) {
-  if (status_ != KC_PLAN_FOUND) return std::nullopt;
-  const std::vector<int32_t> ij = getPathCells(simplify);
+Path::Path GridPlanner::cellsToPath(const std::vector<int32_t> &ij) const {
   std::vector<Path::Point> pts;
   pts.reserve(ij.size() / 2);
   for (size_t k = 0; k + 1 < ij.size(); k += 2)
     pts.emplace_back(cellToWorld(ij[k], ox_, res_), cellToWorld(ij[k + 1], oy_, res_), 0.0f);
   return Path::Path(pts);
+}
+
+std::optional<Path::Path> GridPlanner::getPath(bool simplify) {
+  if (status_ != KC_PLAN_FOUND) return std::nullopt;
+  return cellsToPath(getPathCells(simplify));
 }
 
 void GridPlanner::getField(uint32_t *field_out, uint8_t *valid_out, size_t cap) {
@@ -391,8 +395,7 @@ void GridPlanner::getOrientedField(uint32_t *field4_out, uint8_t *valid4_out, ui
 }
 
 std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int32_t> *indices_out) {
-  // a segment at an arbitrary angle has no heading class (rule 18)
-  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
+  needDiscMode();
   std::vector<int32_t> ij;
   if (indices_out) indices_out->clear();
   if (status_ != KC_PLAN_FOUND) return ij;
@@ -405,18 +408,13 @@ std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int
 }
 
 std::optional<Path::Path> GridPlanner::getAnyAnglePath(int max_span) {
-  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
+  needDiscMode();
   if (status_ != KC_PLAN_FOUND) return std::nullopt;
-  const std::vector<int32_t> ij = getAnyAngleCells(max_span);
-  std::vector<Path::Point> pts;
-  pts.reserve(ij.size() / 2);
-  for (size_t k = 0; k + 1 < ij.size(); k += 2)
-    pts.emplace_back(cellToWorld(ij[k], ox_, res_), cellToWorld(ij[k + 1], oy_, res_), 0.0f);
-  return Path::Path(pts);
+  return cellsToPath(getAnyAngleCells(max_span));
 }
 
 float GridPlanner::getAnyAngleLength(int max_span) {
-  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
+  needDiscMode();
   if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
   const std::vector<int32_t> ij = getAnyAngleCells(max_span);
   double sum = 0.0;
@@ -428,7 +426,7 @@ float GridPlanner::getAnyAngleLength(int max_span) {
 }
 
 float GridPlanner::getAnyAngleMinClearance(int max_span) {
-  if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
+  needDiscMode();
   if (status_ != KC_PLAN_FOUND) throw std::runtime_error("GridPlanner: no path");
   uint32_t c2 = KC_PLANNER_CLEAR_FAR;
   hip::check(kc_planner_shortcut(ctx_.get(), max_span, nullptr, &c2));

@@ -46,7 +46,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -713,6 +715,25 @@ __global__ __launch_bounds__(64) void planner_walk4_kernel(const uint32_t *field
   }
 }
 
+// The kernels' status words, one struct on the device and in pinned memory: a read-back copies a member onto itself.
+struct PlanWords {
+  uint32_t changed;                                 // the last pass that changed a cell
+  uint32_t walk_count, walk_status, walk_clear2;    // either walk's out[0..1]; out[2] of planner_walk_kernel<true>
+  uint32_t short_count, short_status, short_clear2; // planner_shortcut_kernel's out[0..2]
+  uint32_t rp_T, rp_touched, rp_listed;             // planner_touched_kernel's out[0..1], planner_compact_kernel's count
+};
+constexpr size_t kPlanSolveWords = 4;  // zeroed by one memset before the passes of a solve: changed and the walk's three
+// what the memsets, the multi-word copies and the kernels' out[] rely on
+static_assert(sizeof(PlanWords) == 40 && offsetof(PlanWords, changed) == 0 && offsetof(PlanWords, walk_count) == 4 &&
+                  offsetof(PlanWords, walk_status) == 8 && offsetof(PlanWords, walk_clear2) == 12 && offsetof(PlanWords, short_count) == 16 &&
+                  offsetof(PlanWords, short_status) == 20 && offsetof(PlanWords, short_clear2) == 24 && offsetof(PlanWords, rp_T) == 28 &&
+                  offsetof(PlanWords, rp_touched) == 32 && offsetof(PlanWords, rp_listed) == 36,
+              "changed .. walk_clear2 are words 0 .. 3; each kernel's out[0..2] are neighbours in its order");
+struct PlanPinned {
+  PlanWords w;
+  uint32_t start_field, start_valid, goal_valid;  // planner_finish's read-backs: field[start], a validity byte each
+};
+
 }  // namespace kc
 
 using namespace kc;
@@ -721,6 +742,7 @@ struct kc_planner {
   int device = 0;
   hipStream_t stream = nullptr;
   int W = 0, H = 0;
+  unsigned tiles_x = 0, tiles_y = 0;  // of kPlanTile cells; at most 2^28 / 64 tiles (a one-cell-wide grid), within gridDim.x
   bool have_grid = false;
   bool have_valid = false;   // d_valid holds the validity of (grid, valid_r2, valid_unknown), and with the clearance
                              // cost on d_clear2 / d_pen hold the clearance and penalty of (grid, clear_c2, table)
@@ -741,14 +763,11 @@ struct kc_planner {
   uint32_t path_clear2 = KC_PLANNER_CLEAR_FAR;
   DevBuf<uint32_t> d_pen_by_d2, d_pen;
   DevBuf<uint16_t> d_clear2;
-  DevBuf<uint32_t> d_word;   // [0] last pass that changed a cell, [1..2] the walk's count and status, [3] its smallest clear2,
-                             // [4..6] the shortcut's count, status and smallest touched clear2, [8..10] the replan's T,
-                             // touched cells and listed tiles
-  PinBuf<uint32_t> h_word;   // [0..2] as d_word, [3] field[start], [4] valid[start], [5] valid[goal], [6] d_word[3], [8..10] d_word[4..6],
-                             // [12..14] d_word[8..10]
+  DevBuf<PlanWords> d_word;  // one element each
+  PinBuf<PlanPinned> h_word;
   DevBuf<int32_t> d_path;
   PinBuf<int32_t> h_path;
-  bool have_short = false;   // short_idx holds rule 11's indices into `path` for short_span (forgotten with the walk)
+  bool have_short = false;   // short_idx holds rule 11's indices into `path` for short_span; only with have_path
   int short_span = 0;
   uint32_t short_clear2 = KC_PLANNER_CLEAR_FAR;
   std::vector<int32_t> short_idx;
@@ -778,6 +797,50 @@ struct kc_planner {
 
 namespace {
 
+// What a context holds is a ladder: grid -> maps (the disc's, the oriented masks') -> field (with the kept field's
+// fld_ok) -> walk -> shortcut.  Whatever changes a level calls the forget_* of the level below it, which drops that
+// level and every one after it.
+void forget_walk(kc_planner *c) { c->have_path = c->have_short = false; }
+
+// also what a solve starts with: its outputs say "nothing" until it ends
+void forget_solve(kc_planner *c, uint32_t *cost_out = nullptr, int *passes_out = nullptr) {
+  c->solved = c->or_solve = c->fld_ok = false;
+  c->status = -1;
+  c->cost = kPlanInf;
+  if (cost_out) *cost_out = kPlanInf;
+  if (passes_out) *passes_out = 0;
+  forget_walk(c);
+}
+
+void forget_maps(kc_planner *c, bool disc, bool oriented) {
+  if (disc) c->have_valid = false;
+  if (oriented) c->or_have_valid = false;
+  forget_solve(c);
+}
+
+// f(std::true_type) or f(std::false_type): one launch statement for both instantiations of a <bool> kernel
+template <typename F>
+void with_bool(bool on, F &&f) { on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// floor(sqrt(v)) for v < (KC_PLANNER_MAX_RADIUS_CELLS + 1)^2, which kc_planner_solve and the two setters see to: at most
+// KC_PLANNER_MAX_RADIUS_CELLS = 254, the largest distance a rowd byte holds beside its 255 of "none"
+int plan_isqrt(uint32_t v) {
+  int r = 0;
+  while (static_cast<uint32_t>(r + 1) * static_cast<uint32_t>(r + 1) <= v) ++r;
+  return r;
+}
+
+// the linear index of a cell, -1 outside the grid
+long long plan_cell_index(const kc_planner *c, const int cell[2]) {
+  const bool in = cell[0] >= 0 && cell[0] < c->W && cell[1] >= 0 && cell[1] < c->H;
+  return in ? static_cast<long long>(cell[1]) * c->W + cell[0] : -1;
+}
+
+// `count` status words from `first` on, device to pinned, on the stream
+hipError_t plan_fetch_words(kc_planner *c, uint32_t PlanWords::*first, size_t count) {
+  return hipMemcpyAsync(&(c->h_word.p->w.*first), &(c->d_word.p->*first), count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+}
+
 unsigned plan_blocks_for(long long work) {
   return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(kPlanMaxBlocks, (work + kPlanBlock - 1) / kPlanBlock)));
 }
@@ -794,8 +857,10 @@ int check_grid_shape(const void *grid, int elem_bytes, int width, int height) {
 // dev: the grid on the context's device, complete
 int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width, int height) {
   const long long n = static_cast<long long>(width) * height;
-  c->have_grid = c->have_valid = c->or_have_valid = c->solved = c->have_path = false;
-  if (width != c->W || height != c->H) c->fld_ok = false;  // a kept field (rule 20) is one of this shape
+  const bool keep_field = c->fld_ok && width == c->W && height == c->H;  // a kept field (rule 20) is one of this shape
+  c->have_grid = false;
+  forget_maps(c, true, true);
+  c->fld_ok = keep_field;
   KC_TRY(c->d_cls.reserve(static_cast<size_t>(n)));
   if (elem_bytes == 4)
     hipLaunchKernelGGL(planner_classify_kernel<int32_t>, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, c->stream,
@@ -807,14 +872,15 @@ int planner_take_grid(kc_planner *c, const void *dev, int elem_bytes, int width,
   KC_HIP(hipStreamSynchronize(c->stream));  // the caller's grid is not read after the call returns
   c->W = width;
   c->H = height;
+  c->tiles_x = static_cast<unsigned>((width + kPlanTile - 1) / kPlanTile);
+  c->tiles_y = static_cast<unsigned>((height + kPlanTile - 1) / kPlanTile);
   c->have_grid = true;
   return KC_OK;
 }
 
 // rule 14's offsets of class k, by rising di^2 + dj^2 (then dj, then di); A2 + B2 within the radius cap
 std::vector<int16_t> oriented_offsets(int k, uint32_t a2, uint32_t b2) {
-  int r = 0;
-  while (static_cast<uint32_t>(r + 1) * static_cast<uint32_t>(r + 1) <= a2 + b2) ++r;  // T2 contains every mask
+  const int r = plan_isqrt(a2 + b2);  // T2 contains every mask
   std::vector<std::pair<int, int>> o;
   for (int dj = -r; dj <= r; ++dj)
     for (int di = -r; di <= r; ++di) {
@@ -835,32 +901,41 @@ std::vector<int16_t> oriented_offsets(int k, uint32_t a2, uint32_t b2) {
   return out;
 }
 
+// behind either walk kernel's launch: its count and status (and walk_clear2, a copy of its own) come back, then the
+// `count` int32 it wrote to d_path arrive in h_path; "the <noun> walk stopped after .. <unit>"
+int planner_walk_fetch(kc_planner *c, size_t cap, bool clear2_too, const char *noun, const char *unit, uint32_t *count_out) {
+  hipStream_t s = c->stream;
+  KC_HIP(hipGetLastError());
+  KC_HIP(plan_fetch_words(c, &PlanWords::walk_count, 2));
+  if (clear2_too) KC_HIP(plan_fetch_words(c, &PlanWords::walk_clear2, 1));
+  KC_HIP(hipStreamSynchronize(s));
+  const uint32_t count = c->h_word.p->w.walk_count, wst = c->h_word.p->w.walk_status;
+  if (wst != 0u || count == 0u || count > cap)
+    KC_FAIL(KC_ERR_STATE, "the %s walk stopped after %u %s with status %u", noun, count, unit, wst);
+  KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  *count_out = count;
+  return KC_OK;
+}
+
 // rule 17 over the last oriented solve (status KC_PLAN_FOUND), once: c->states, and c->path with the turns collapsed
 int planner_walk_oriented(kc_planner *c) {
   KC_HIP(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
   const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
   // every transition lowers the field by min(10, turn10) at least, and no state comes twice
   const size_t cap = std::min<size_t>(4 * n, static_cast<size_t>(c->cost / std::min<uint32_t>(10u, c->or_turn10))) + 2;
   KC_TRY(c->d_path.reserve(cap));
   KC_TRY(c->h_path.reserve(cap));
-  hipLaunchKernelGGL(planner_walk4_kernel, dim3(1), dim3(64), 0, s, c->d_field4[c->final_buf].p, c->d_valid4.p, c->W, c->H, n,
-                     c->start[0], c->start[1], c->start_class, c->or_turn10, c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
-  KC_HIP(hipGetLastError());
-  KC_HIP(hipMemcpyAsync(&c->h_word.p[1], c->d_word.p + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
-  const uint32_t count = c->h_word.p[1], wst = c->h_word.p[2];
-  if (wst != 0u || count == 0u || count > cap)
-    KC_FAIL(KC_ERR_STATE, "the state walk stopped after %u states with status %u", count, wst);
-  KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
+  hipLaunchKernelGGL(planner_walk4_kernel, dim3(1), dim3(64), 0, c->stream, c->d_field4[c->final_buf].p, c->d_valid4.p, c->W, c->H, n, c->start[0],
+                     c->start[1], c->start_class, c->or_turn10, c->d_path.p, static_cast<uint32_t>(cap), &c->d_word.p->walk_count);
+  uint32_t count = 0;
+  KC_TRY(planner_walk_fetch(c, cap, false, "state", "states", &count));
   c->states.assign(c->h_path.p, c->h_path.p + count);
   c->path.clear();
   for (const int32_t st : c->states)
     if (c->path.empty() || c->path.back() != st / 4) c->path.push_back(st / 4);  // a turn stays in its cell
   c->path_clear2 = static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
   c->have_path = true;
-  c->have_short = false;
   return KC_OK;
 }
 
@@ -869,32 +944,22 @@ int planner_walk(kc_planner *c) {
   if (c->have_path) return KC_OK;
   if (c->or_solve) return planner_walk_oriented(c);
   KC_HIP(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
   const bool pen_on = c->clear_c2 > 0;
+  const uint32_t *pen = pen_on ? c->d_pen.p : nullptr;
+  const uint16_t *clear2 = pen_on ? c->d_clear2.p : nullptr;
   // every step lowers the field by 10 at least
   const size_t cap = static_cast<size_t>(c->cost / 10u) + 2;
   KC_TRY(c->d_path.reserve(cap));
   KC_TRY(c->h_path.reserve(cap));
-  if (pen_on)
-    hipLaunchKernelGGL(planner_walk_kernel<true>, dim3(1), dim3(64), 0, s, c->d_field[c->final_buf].p, c->d_valid.p, c->d_pen.p,
-                       c->d_clear2.p, c->W, c->H, c->start[0], c->start[1], c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
-  else
-    hipLaunchKernelGGL(planner_walk_kernel<false>, dim3(1), dim3(64), 0, s, c->d_field[c->final_buf].p, c->d_valid.p,
-                       static_cast<const uint32_t *>(nullptr), static_cast<const uint16_t *>(nullptr), c->W, c->H, c->start[0],
-                       c->start[1], c->d_path.p, static_cast<uint32_t>(cap), c->d_word.p + 1);
-  KC_HIP(hipGetLastError());
-  KC_HIP(hipMemcpyAsync(&c->h_word.p[1], c->d_word.p + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  if (pen_on) KC_HIP(hipMemcpyAsync(&c->h_word.p[6], c->d_word.p + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
-  const uint32_t count = c->h_word.p[1], wst = c->h_word.p[2];
-  if (wst != 0u || count == 0u || count > cap)
-    KC_FAIL(KC_ERR_STATE, "the path walk stopped after %u cells with status %u", count, wst);
-  KC_HIP(hipMemcpyAsync(c->h_path.p, c->d_path.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
+  with_bool(pen_on, [&](auto on) {
+    hipLaunchKernelGGL(planner_walk_kernel<decltype(on)::value>, dim3(1), dim3(64), 0, c->stream, c->d_field[c->final_buf].p, c->d_valid.p, pen,
+                       clear2, c->W, c->H, c->start[0], c->start[1], c->d_path.p, static_cast<uint32_t>(cap), &c->d_word.p->walk_count);
+  });
+  uint32_t count = 0;
+  KC_TRY(planner_walk_fetch(c, cap, pen_on, "path", "cells", &count));
   c->path.assign(c->h_path.p, c->h_path.p + count);
-  c->path_clear2 = pen_on ? c->h_word.p[6] : static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
+  c->path_clear2 = pen_on ? c->h_word.p->w.walk_clear2 : static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
   c->have_path = true;
-  c->have_short = false;  // a shortcut is one of this walk
   return KC_OK;
 }
 
@@ -909,39 +974,37 @@ int planner_shortcut(kc_planner *c, int max_span) {
   const size_t n = c->path.size();  // d_path still holds these cells: only the walk writes it
   KC_TRY(c->d_keep.reserve(n));
   KC_TRY(c->h_keep.reserve(n));
-  if (clr)
-    hipLaunchKernelGGL(planner_shortcut_kernel<true>, dim3(1), dim3(kShortThreads), 0, s, c->d_path.p, static_cast<uint32_t>(n),
-                       max_span, c->d_valid.p, c->d_clear2.p, c->path_clear2, c->W, c->d_keep.p, c->d_word.p + 4);
-  else
-    hipLaunchKernelGGL(planner_shortcut_kernel<false>, dim3(1), dim3(kShortThreads), 0, s, c->d_path.p, static_cast<uint32_t>(n),
-                       max_span, c->d_valid.p, static_cast<const uint16_t *>(nullptr), 0u, c->W, c->d_keep.p, c->d_word.p + 4);
+  const uint16_t *clear2 = clr ? c->d_clear2.p : nullptr;
+  with_bool(clr, [&](auto on) {
+    hipLaunchKernelGGL(planner_shortcut_kernel<decltype(on)::value>, dim3(1), dim3(kShortThreads), 0, s, c->d_path.p, static_cast<uint32_t>(n),
+                       max_span, c->d_valid.p, clear2, clr ? c->path_clear2 : 0u, c->W, c->d_keep.p, &c->d_word.p->short_count);
+  });
   KC_HIP(hipGetLastError());
-  KC_HIP(hipMemcpyAsync(&c->h_word.p[8], c->d_word.p + 4, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  KC_HIP(plan_fetch_words(c, &PlanWords::short_count, 3));
   KC_HIP(hipStreamSynchronize(s));
-  const uint32_t count = c->h_word.p[8], sst = c->h_word.p[9];
+  const uint32_t count = c->h_word.p->w.short_count, sst = c->h_word.p->w.short_status;
   if (sst != 0u || count == 0u || count > n) KC_FAIL(KC_ERR_STATE, "the shortcut stopped after %u indices with status %u", count, sst);
   KC_HIP(hipMemcpyAsync(c->h_keep.p, c->d_keep.p, count * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   KC_HIP(hipStreamSynchronize(s));
   c->short_idx.assign(c->h_keep.p, c->h_keep.p + count);
-  c->short_clear2 = c->h_word.p[10];
+  c->short_clear2 = c->h_word.p->w.short_clear2;
   c->short_span = max_span;
   c->have_short = true;
   return KC_OK;
 }
 
 // rules 2 and 6: the validity map of (grid, r2, unknown_blocks) into d_valid, and with the clearance cost on clear2 and the
-// penalty beside it; R = isqrt(r2)
-int planner_validity(kc_planner *c, int R, uint32_t r2, int unknown_blocks) {
+// penalty beside it
+int planner_validity(kc_planner *c, uint32_t r2, int unknown_blocks) {
   hipStream_t s = c->stream;
-  const int W = c->W, H = c->H;
+  const int W = c->W, H = c->H, R = plan_isqrt(r2);
   const long long n = static_cast<long long>(W) * H;
   const unsigned blocks = plan_blocks_for(n);
   c->have_valid = false;
   KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
   KC_TRY(c->d_valid.reserve(static_cast<size_t>(n)));
   if (c->clear_c2 > 0) {
-    int Rm = R;
-    while (static_cast<uint32_t>(Rm + 1) * static_cast<uint32_t>(Rm + 1) <= c->clear_c2) ++Rm;  // <= 254: kc_planner_set_clearance_cost
+    const int Rm = std::max(R, plan_isqrt(c->clear_c2));
     KC_TRY(c->d_clear2.reserve(static_cast<size_t>(n)));
     KC_TRY(c->d_pen.reserve(static_cast<size_t>(n)));
     hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, Rm, unknown_blocks);
@@ -959,83 +1022,82 @@ int planner_validity(kc_planner *c, int R, uint32_t r2, int unknown_blocks) {
 }
 
 // rule 3's passes to the fixed point, in batches of kPlanBatch with one read-back of the changed word (zero before the
-// first): over every tile (list == nullptr, `blocks` of them) or over the `blocks` tiles of a list (rule 20).  Pass k
-// reads d_field[(k - 1) & 1] and writes d_field[k & 1]; *pass: passes launched, *last_changed: the last that changed a cell.
-int planner_relax(kc_planner *c, const uint32_t *list, unsigned blocks, uint32_t *pass_io, uint32_t *last_changed_out) {
-  hipStream_t s = c->stream;
-  const int W = c->W, H = c->H;
-  const bool pen_on = c->clear_c2 > 0;
-  const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile);
-  // every pass that is not the last gives at least one more cell its final value: cells + 1 passes always do
-  const unsigned long long cap = static_cast<unsigned long long>(W) * static_cast<unsigned long long>(H) + 1ull;
-  const uint32_t *pen = pen_on ? c->d_pen.p : nullptr;
-  uint32_t pass = *pass_io;
-  for (;;) {
+// first) a batch.  launch(k, b) queues pass k, which reads buffer b = (k - 1) & 1 of a field pair and writes the other.
+// A pass that is not the last gives at least one more of the `states` cells or states its final value: states + 1
+// passes always do.  c->final_buf: the buffer the last pass wrote; *passes_out: the passes a batch of one would have
+// run, the last that changed a cell and the one that found nothing to change.
+template <typename Launch>
+int planner_relax(kc_planner *c, Launch &&launch, unsigned long long states, const char *noun, uint32_t *passes_out) {
+  const unsigned long long cap = states + 1ull;
+  for (uint32_t pass = 0;;) {
     for (int b = 0; b < kPlanBatch; ++b) {
       ++pass;
-      const uint32_t *in = c->d_field[(pass - 1) & 1].p;
-      uint32_t *out = c->d_field[pass & 1].p;
-      if (list) {
-        if (pen_on)
-          hipLaunchKernelGGL(planner_relax_list_kernel<true>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
-                             tiles_x, list, c->d_word.p, pass);
-        else
-          hipLaunchKernelGGL(planner_relax_list_kernel<false>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
-                             tiles_x, list, c->d_word.p, pass);
-      } else {
-        if (pen_on)
-          hipLaunchKernelGGL(planner_relax_kernel<true>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
-                             tiles_x, c->d_word.p, pass);
-        else
-          hipLaunchKernelGGL(planner_relax_kernel<false>, dim3(blocks), dim3(kPlanThreads), 0, s, in, out, c->d_valid.p, pen, W, H,
-                             tiles_x, c->d_word.p, pass);
-      }
+      launch(pass, static_cast<int>((pass - 1) & 1u));
     }
     KC_HIP(hipGetLastError());
-    KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    KC_HIP(hipStreamSynchronize(s));
-    *pass_io = pass;
-    *last_changed_out = c->h_word.p[0];
-    if (*last_changed_out < pass) return KC_OK;
+    KC_HIP(plan_fetch_words(c, &PlanWords::changed, 1));
+    KC_HIP(hipStreamSynchronize(c->stream));
+    const uint32_t last_changed = c->h_word.p->w.changed;
+    if (last_changed < pass) {
+      c->final_buf = static_cast<int>(pass & 1u);
+      *passes_out = last_changed + 1u;
+      return KC_OK;
+    }
     if (pass >= cap)
-      KC_FAIL(KC_ERR_RANGE, "the cost field of a %d x %d grid still changed after %u passes (cap %llu)", W, H, pass, cap);
+      KC_FAIL(KC_ERR_RANGE, "the %s field of a %d x %d grid still changed after %u passes (cap %llu)", noun, c->W, c->H, pass, cap);
   }
 }
 
-// d_field[final_buf] holds the fixed point for goal_cell: the start's status and cost (rule 4), and what a replan
-// needs to know of this field
-int planner_finish(kc_planner *c, const int start_cell[2], const int goal_cell[2], int *status_out, uint32_t *cost_out) {
+// the disc's pass over `blocks` tiles: all of them (list == nullptr) or those of a list
+auto disc_pass(kc_planner *c, const uint32_t *list, unsigned blocks) {
+  return [=](uint32_t pass, int b) {
+    const bool pen_on = c->clear_c2 > 0;
+    const uint32_t *in = c->d_field[b].p, *pen = pen_on ? c->d_pen.p : nullptr;
+    uint32_t *out = c->d_field[b ^ 1].p, *changed = &c->d_word.p->changed;
+    with_bool(pen_on, [&](auto on) {
+      if (list)
+        hipLaunchKernelGGL(planner_relax_list_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanThreads), 0, c->stream, in, out,
+                           c->d_valid.p, pen, c->W, c->H, c->tiles_x, list, changed, pass);
+      else
+        hipLaunchKernelGGL(planner_relax_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanThreads), 0, c->stream, in, out,
+                           c->d_valid.p, pen, c->W, c->H, c->tiles_x, changed, pass);
+    });
+  };
+}
+
+// `field` (a layer of the pair's buffer c->final_buf) holds the fixed point for goal_cell over the validity bytes
+// `valid`: the start's status and cost (rule 4).  A cell is valid where its byte has a bit of its mask.  keep_field:
+// the field may serve a replan, which needs to know its goal.
+int planner_finish(kc_planner *c, const int start_cell[2], const int goal_cell[2], const uint32_t *field, const uint8_t *valid,
+                   uint32_t start_mask, uint32_t goal_mask, bool keep_field, int *status_out, uint32_t *cost_out) {
   hipStream_t s = c->stream;
-  const int W = c->W, H = c->H;
-  const bool start_in = start_cell[0] >= 0 && start_cell[0] < W && start_cell[1] >= 0 && start_cell[1] < H;
-  const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
-  const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
-  const long long start = start_in ? static_cast<long long>(start_cell[1]) * W + start_cell[0] : -1;
+  const long long start = plan_cell_index(c, start_cell), goal = plan_cell_index(c, goal_cell);
+  PlanPinned *h = c->h_word.p;
   c->solved = true;
   c->start[0] = start_cell[0];
   c->start[1] = start_cell[1];
-  c->h_word.p[3] = kPlanInf;
-  c->h_word.p[4] = 0;
-  c->h_word.p[5] = 0;
-  if (start_in) {
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[3], c->d_field[c->final_buf].p + start, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[4], c->d_valid.p + start, 1, hipMemcpyDeviceToHost, s));
+  h->start_field = kPlanInf;
+  h->start_valid = 0;
+  h->goal_valid = 0;
+  if (start >= 0) {
+    KC_HIP(hipMemcpyAsync(&h->start_field, field + start, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipMemcpyAsync(&h->start_valid, valid + start, 1, hipMemcpyDeviceToHost, s));
   }
-  if (goal_in) KC_HIP(hipMemcpyAsync(&c->h_word.p[5], c->d_valid.p + goal, 1, hipMemcpyDeviceToHost, s));
+  if (goal >= 0) KC_HIP(hipMemcpyAsync(&h->goal_valid, valid + goal, 1, hipMemcpyDeviceToHost, s));
   KC_HIP(hipStreamSynchronize(s));
-  const bool start_ok = start_in && (c->h_word.p[4] & 0xFFu) != 0, goal_ok = goal_in && (c->h_word.p[5] & 0xFFu) != 0;
+  const bool start_ok = (h->start_valid & start_mask) != 0, goal_ok = (h->goal_valid & goal_mask) != 0;
   int st = KC_PLAN_FOUND;
-  if (!start_in) st = KC_PLAN_START_OUTSIDE;
-  else if (!goal_in) st = KC_PLAN_GOAL_OUTSIDE;
+  if (start < 0) st = KC_PLAN_START_OUTSIDE;
+  else if (goal < 0) st = KC_PLAN_GOAL_OUTSIDE;
   else if (!start_ok) st = KC_PLAN_START_INVALID;
   else if (!goal_ok) st = KC_PLAN_GOAL_INVALID;
-  else if (c->h_word.p[3] == kPlanInf) st = KC_PLAN_UNREACHABLE;
+  else if (h->start_field == kPlanInf) st = KC_PLAN_UNREACHABLE;
   c->status = st;
-  c->cost = st == KC_PLAN_FOUND ? c->h_word.p[3] : kPlanInf;
+  c->cost = st == KC_PLAN_FOUND ? h->start_field : kPlanInf;
   *status_out = st;
   if (cost_out) *cost_out = c->cost;
   // rule 19's proof starts from old(goal) = 0: a field of all INF under an invalid goal is not kept
-  c->fld_ok = goal_ok;
+  c->fld_ok = keep_field && goal_ok;
   c->fld_goal[0] = goal_cell[0];
   c->fld_goal[1] = goal_cell[1];
   return KC_OK;
@@ -1054,7 +1116,7 @@ int kc_planner_create(int device, kc_planner **out) {
   c->device = device;
   c->stream = stream;
   int rc;
-  if ((rc = c->d_word.reserve(12)) || (rc = c->h_word.reserve(16))) {
+  if ((rc = c->d_word.reserve(1)) || (rc = c->h_word.reserve(1))) {
     kc_planner_destroy(c);
     return rc;
   }
@@ -1098,43 +1160,28 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve before a grid was set");
   if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve with the oriented footprint on: kc_planner_solve_oriented");
-  int R = 0;
-  while (static_cast<unsigned long long>(R + 1) * static_cast<unsigned long long>(R + 1) <= r2 && R <= KC_PLANNER_MAX_RADIUS_CELLS) ++R;
-  if (R > KC_PLANNER_MAX_RADIUS_CELLS)
+  if (r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
     KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
-  const bool pen_on = c->clear_c2 > 0;
   const long long n = static_cast<long long>(c->W) * c->H;
   // field <= (14 + max penalty) * cells: the sums of the relaxation stay below the 0xFFFFFFFF of "no walk"
-  if (pen_on && (14ull + c->clear_max_pen) * static_cast<unsigned long long>(n) > 0xFFFFFFFEull)
+  if (c->clear_c2 > 0 && (14ull + c->clear_max_pen) * static_cast<unsigned long long>(n) > 0xFFFFFFFEull)
     KC_FAIL(KC_ERR_RANGE, "a clearance penalty of %u over %lld cells does not fit the 32-bit cost field", c->clear_max_pen, n);
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  const int W = c->W, H = c->H;
-  c->solved = c->have_path = c->or_solve = c->fld_ok = false;
-  c->status = -1;
-  c->cost = kPlanInf;
-  if (cost_out) *cost_out = kPlanInf;
-  if (passes_out) *passes_out = 0;
-  const unsigned blocks = plan_blocks_for(n);
+  forget_solve(c, cost_out, passes_out);
   const int unknown_blocks = allow_unknown ? 0 : 1;
-  if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) KC_TRY(planner_validity(c, R, r2, unknown_blocks));
-  const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
-  const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
+  if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) KC_TRY(planner_validity(c, r2, unknown_blocks));
+  const long long goal = plan_cell_index(c, goal_cell);
   KC_TRY(c->d_field[0].reserve(static_cast<size_t>(n)));
   KC_TRY(c->d_field[1].reserve(static_cast<size_t>(n)));
-  hipLaunchKernelGGL(planner_init_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, goal);
-  KC_HIP(hipMemsetAsync(c->d_word.p, 0, 4 * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(planner_init_kernel, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, goal);
+  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), s));
   KC_HIP(hipGetLastError());
-  uint32_t pass = 0, last_changed = 0;
-  if (goal_in) {
-    // at most 2^28 / 64 tiles (a one-cell-wide grid), within gridDim.x
-    const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile), tiles_y = static_cast<unsigned>((H + kPlanTile - 1) / kPlanTile);
-    KC_TRY(planner_relax(c, nullptr, tiles_x * tiles_y, &pass, &last_changed));
-  }
-  c->final_buf = static_cast<int>(pass & 1u);
-  KC_TRY(planner_finish(c, start_cell, goal_cell, status_out, cost_out));
-  // passes a batch of one would have run: the last that changed a cell and the one that found nothing to change
-  if (passes_out) *passes_out = goal_in ? static_cast<int>(last_changed + 1u) : 0;
+  c->final_buf = 0;  // both buffers hold the initial state
+  uint32_t passes = 0;
+  if (goal >= 0) KC_TRY(planner_relax(c, disc_pass(c, nullptr, c->tiles_x * c->tiles_y), n, "cost", &passes));
+  KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field[c->final_buf].p, c->d_valid.p, 0xFFu, 0xFFu, true, status_out, cost_out));
+  if (passes_out) *passes_out = static_cast<int>(passes);
   return KC_OK;
 }
 
@@ -1155,56 +1202,47 @@ int kc_planner_replan(kc_planner *c, const int start_cell[2], const int goal_cel
   const int W = c->W, H = c->H;
   const long long n = static_cast<long long>(W) * H;
   const bool pen_on = c->clear_c2 > 0;
-  c->solved = c->have_path = c->or_solve = c->fld_ok = false;
-  c->status = -1;
-  c->cost = kPlanInf;
-  if (cost_out) *cost_out = kPlanInf;
-  if (passes_out) *passes_out = 0;
-  uint32_t T = kPlanInf, touched = 0, listed = 0, pass = 0, last_changed = 0;
+  PlanWords *d = c->d_word.p;
+  forget_solve(c, cost_out, passes_out);
+  uint32_t T = kPlanInf, touched = 0, listed = 0, passes = 0;
   if (!c->have_valid) {  // a grid was set since: rule 19 against its maps; otherwise nothing is touched
     const unsigned blocks = plan_blocks_for(n);
     std::swap(c->d_valid, c->d_valid_old);
     if (pen_on) std::swap(c->d_pen, c->d_pen_old);
-    int R = 0;
-    while (static_cast<uint32_t>(R + 1) * static_cast<uint32_t>(R + 1) <= r2) ++R;  // <= 254: the kept solve's
-    KC_TRY(planner_validity(c, R, r2, unknown_blocks));
-    uint32_t *old = c->d_field[c->final_buf].p;
-    KC_HIP(hipMemsetAsync(c->d_word.p + 8, 0xFF, sizeof(uint32_t), s));
-    KC_HIP(hipMemsetAsync(c->d_word.p + 9, 0, 2 * sizeof(uint32_t), s));
-    if (pen_on)
-      hipLaunchKernelGGL(planner_touched_kernel<true>, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_valid_old.p, c->d_valid.p,
-                         c->d_pen_old.p, c->d_pen.p, W, H, c->d_word.p + 8);
-    else
-      hipLaunchKernelGGL(planner_touched_kernel<false>, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_valid_old.p, c->d_valid.p,
-                         static_cast<const uint32_t *>(nullptr), static_cast<const uint32_t *>(nullptr), W, H, c->d_word.p + 8);
+    KC_TRY(planner_validity(c, r2, unknown_blocks));
+    const uint32_t *old = c->d_field[c->final_buf].p, *pen_old = pen_on ? c->d_pen_old.p : nullptr, *pen_new = pen_on ? c->d_pen.p : nullptr;
+    KC_HIP(hipMemsetAsync(&d->rp_T, 0xFF, sizeof(uint32_t), s));
+    KC_HIP(hipMemsetAsync(&d->rp_touched, 0, 2 * sizeof(uint32_t), s));
+    with_bool(pen_on, [&](auto on) {
+      hipLaunchKernelGGL(planner_touched_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_valid_old.p, c->d_valid.p,
+                         pen_old, pen_new, W, H, &d->rp_T);
+    });
     KC_HIP(hipGetLastError());
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[12], c->d_word.p + 8, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    KC_HIP(plan_fetch_words(c, &PlanWords::rp_T, 2));
     KC_HIP(hipStreamSynchronize(s));
-    T = c->h_word.p[12];
-    touched = c->h_word.p[13];
+    T = c->h_word.p->w.rp_T;
+    touched = c->h_word.p->w.rp_touched;
     if (T != kPlanInf) {
-      const int tiles_x = (W + kPlanTile - 1) / kPlanTile, tiles_y = (H + kPlanTile - 1) / kPlanTile;
-      const unsigned ntiles = static_cast<unsigned>(tiles_x) * static_cast<unsigned>(tiles_y);
+      const unsigned ntiles = c->tiles_x * c->tiles_y;
       KC_TRY(c->d_tile_on.reserve(ntiles));
       KC_TRY(c->d_tile_list.reserve(ntiles));
       KC_HIP(hipMemsetAsync(c->d_tile_on.p, 0, ntiles, s));
-      hipLaunchKernelGGL(planner_rollback_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_field[0].p, c->d_field[1].p,
-                         c->d_valid.p, W, H, static_cast<long long>(goal_cell[1]) * W + goal_cell[0], T, tiles_x, tiles_y, c->d_tile_on.p);
+      hipLaunchKernelGGL(planner_rollback_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, old, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, W,
+                         H, plan_cell_index(c, goal_cell), T, static_cast<int>(c->tiles_x), static_cast<int>(c->tiles_y), c->d_tile_on.p);
       hipLaunchKernelGGL(planner_compact_kernel, dim3(plan_blocks_for(ntiles)), dim3(kPlanBlock), 0, s, c->d_tile_on.p, ntiles,
-                         c->d_tile_list.p, c->d_word.p + 10);
-      KC_HIP(hipMemsetAsync(c->d_word.p, 0, 4 * sizeof(uint32_t), s));
+                         c->d_tile_list.p, &d->rp_listed);
+      KC_HIP(hipMemsetAsync(d, 0, kPlanSolveWords * sizeof(uint32_t), s));
       KC_HIP(hipGetLastError());
-      KC_HIP(hipMemcpyAsync(&c->h_word.p[14], c->d_word.p + 10, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      KC_HIP(plan_fetch_words(c, &PlanWords::rp_listed, 1));
       KC_HIP(hipStreamSynchronize(s));
-      listed = c->h_word.p[14];
+      listed = c->h_word.p->w.rp_listed;
       if (listed > ntiles) KC_FAIL(KC_ERR_STATE, "%u tiles listed of %u", listed, ntiles);
-      // both buffers hold the rollback state, so pass 1 reads either
-      if (listed) KC_TRY(planner_relax(c, c->d_tile_list.p, listed, &pass, &last_changed));
-      c->final_buf = static_cast<int>(pass & 1u);
+      c->final_buf = 0;  // both buffers hold the rollback state, so pass 1 reads either
+      if (listed) KC_TRY(planner_relax(c, disc_pass(c, c->d_tile_list.p, listed), n, "cost", &passes));
     }
   }
-  KC_TRY(planner_finish(c, start_cell, goal_cell, status_out, cost_out));
-  if (passes_out) *passes_out = listed ? static_cast<int>(last_changed + 1u) : 0;
+  KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field[c->final_buf].p, c->d_valid.p, 0xFFu, 0xFFu, true, status_out, cost_out));
+  if (passes_out) *passes_out = static_cast<int>(passes);
   c->rp_kept = true;
   c->rp_T = T;
   c->rp_touched = touched;
@@ -1267,8 +1305,7 @@ int kc_planner_set_clearance_cost(kc_planner *c, uint32_t c2, const uint32_t *pe
     c->clear_max_pen = *std::max_element(pen_by_d2, pen_by_d2 + n);
   }
   c->clear_c2 = on ? c2 : 0u;
-  c->have_valid = c->solved = c->have_path = c->fld_ok = false;  // clear2 and the penalty come with the validity pass
-  c->status = -1;
+  forget_maps(c, true, false);  // clear2 and the penalty come with the validity pass
   return KC_OK;
 }
 
@@ -1331,8 +1368,7 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (a2 == 0) {
     c->or_a2 = c->or_b2 = c->or_turn10 = 0;
-    c->or_have_valid = c->solved = c->have_path = c->or_solve = c->fld_ok = false;
-    c->status = -1;
+    forget_maps(c, false, true);
     return KC_OK;
   }
   if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "the oriented footprint cannot be set while a clearance cost is on (rule 18)");
@@ -1340,7 +1376,8 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
   const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
   if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
     KC_FAIL(KC_ERR_RANGE, "a turning disc of T2 = %llu is wider than %d cells", t2, KC_PLANNER_MAX_RADIUS_CELLS);
-  if (c->or_a2 != a2 || c->or_b2 != b2) {
+  const bool new_box = c->or_a2 != a2 || c->or_b2 != b2;
+  if (new_box) {
     std::vector<int16_t> all;
     PlanMaskEnds ends = {};
     for (int k = 0; k < 4; ++k) {
@@ -1354,13 +1391,11 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
     KC_HIP(hipMemcpyAsync(c->d_offs.p, all.data(), all.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     KC_HIP(hipStreamSynchronize(c->stream));
     c->or_ends = ends;
-    c->or_have_valid = false;
   }
   c->or_a2 = a2;
   c->or_b2 = b2;
   c->or_turn10 = turn10;
-  c->solved = c->have_path = c->or_solve = c->fld_ok = false;  // the oriented solve shares final_buf
-  c->status = -1;
+  forget_maps(c, false, new_box);  // an unchanged box keeps its masks; the oriented solve shares final_buf with the kept field
   return KC_OK;
 }
 
@@ -1377,19 +1412,14 @@ int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int W = c->W, H = c->H;
-  c->solved = c->have_path = false;
+  forget_solve(c, cost_out, passes_out);  // no kept field to lose: kc_planner_set_oriented dropped it
   c->or_solve = true;
-  c->status = -1;
-  c->cost = kPlanInf;
-  if (cost_out) *cost_out = kPlanInf;
-  if (passes_out) *passes_out = 0;
   const unsigned blocks = plan_blocks_for(n);
   const int unknown_blocks = allow_unknown ? 0 : 1;
   if (!c->or_have_valid || c->or_valid_unknown != unknown_blocks) {
     c->or_have_valid = false;
     const uint32_t t2 = c->or_a2 + c->or_b2;
-    int R = 0;
-    while (static_cast<uint32_t>(R + 1) * static_cast<uint32_t>(R + 1) <= t2) ++R;  // <= 254: kc_planner_set_oriented
+    const int R = plan_isqrt(t2);
     KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
     KC_TRY(c->d_turn.reserve(static_cast<size_t>(n)));
     KC_TRY(c->d_valid4.reserve(static_cast<size_t>(n)));
@@ -1402,63 +1432,26 @@ int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_
     c->or_have_valid = true;
     c->or_valid_unknown = unknown_blocks;
   }
-  const bool start_in = start_cell[0] >= 0 && start_cell[0] < W && start_cell[1] >= 0 && start_cell[1] < H;
-  const bool goal_in = goal_cell[0] >= 0 && goal_cell[0] < W && goal_cell[1] >= 0 && goal_cell[1] < H;
-  const long long goal = goal_in ? static_cast<long long>(goal_cell[1]) * W + goal_cell[0] : -1;
-  const long long start = start_in ? static_cast<long long>(start_cell[1]) * W + start_cell[0] : -1;
+  const long long goal = plan_cell_index(c, goal_cell);
   KC_TRY(c->d_field4[0].reserve(4 * static_cast<size_t>(n)));
   KC_TRY(c->d_field4[1].reserve(4 * static_cast<size_t>(n)));
   hipLaunchKernelGGL(planner_init4_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field4[0].p, c->d_field4[1].p, c->d_valid4.p, n, goal);
-  KC_HIP(hipMemsetAsync(c->d_word.p, 0, 4 * sizeof(uint32_t), s));
+  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), s));
   KC_HIP(hipGetLastError());
-  uint32_t pass = 0, last_changed = 0;
-  if (goal_in) {
-    // every pass that is not the last gives at least one more state its final value: 4 * cells + 1 passes always do
-    const unsigned long long cap = 4ull * static_cast<unsigned long long>(n) + 1ull;
-    const unsigned tiles_x = static_cast<unsigned>((W + kPlanTile - 1) / kPlanTile), tiles_y = static_cast<unsigned>((H + kPlanTile - 1) / kPlanTile);
-    const dim3 tiles(tiles_x * tiles_y);
-    for (;;) {
-      for (int b = 0; b < kPlanBatch; ++b) {
-        ++pass;
-        hipLaunchKernelGGL(planner_relax4_kernel, tiles, dim3(kPlanThreads), 0, s, c->d_field4[(pass - 1) & 1].p, c->d_field4[pass & 1].p,
-                           c->d_valid4.p, W, H, static_cast<size_t>(n), tiles_x, c->or_turn10, c->d_word.p, pass);
-      }
-      KC_HIP(hipGetLastError());
-      KC_HIP(hipMemcpyAsync(c->h_word.p, c->d_word.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      KC_HIP(hipStreamSynchronize(s));
-      last_changed = c->h_word.p[0];
-      if (last_changed < pass) break;
-      if (pass >= cap)
-        KC_FAIL(KC_ERR_RANGE, "the state field of a %d x %d grid still changed after %u passes (cap %llu)", W, H, pass, cap);
-    }
+  c->final_buf = 0;  // both buffers hold the initial state
+  uint32_t passes = 0;
+  if (goal >= 0) {
+    const auto pass4 = [&](uint32_t pass, int b) {
+      hipLaunchKernelGGL(planner_relax4_kernel, dim3(c->tiles_x * c->tiles_y), dim3(kPlanThreads), 0, s, c->d_field4[b].p, c->d_field4[b ^ 1].p,
+                         c->d_valid4.p, W, H, static_cast<size_t>(n), c->tiles_x, c->or_turn10, &c->d_word.p->changed, pass);
+    };
+    KC_TRY(planner_relax(c, pass4, 4ull * n, "state", &passes));
   }
-  c->final_buf = static_cast<int>(pass & 1u);
-  c->solved = true;
-  c->start[0] = start_cell[0];
-  c->start[1] = start_cell[1];
   c->start_class = start_class;
-  c->h_word.p[3] = kPlanInf;
-  c->h_word.p[4] = 0;
-  c->h_word.p[5] = 0;
-  if (start_in) {
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[3], c->d_field4[c->final_buf].p + static_cast<size_t>(start_class) * static_cast<size_t>(n) + start,
-                          sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    KC_HIP(hipMemcpyAsync(&c->h_word.p[4], c->d_valid4.p + start, 1, hipMemcpyDeviceToHost, s));
-  }
-  if (goal_in) KC_HIP(hipMemcpyAsync(&c->h_word.p[5], c->d_valid4.p + goal, 1, hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
-  const bool start_ok = start_in && ((c->h_word.p[4] >> start_class) & 1u) != 0, goal_ok = goal_in && (c->h_word.p[5] & 15u) != 0;
-  int st = KC_PLAN_FOUND;
-  if (!start_in) st = KC_PLAN_START_OUTSIDE;
-  else if (!goal_in) st = KC_PLAN_GOAL_OUTSIDE;
-  else if (!start_ok) st = KC_PLAN_START_INVALID;
-  else if (!goal_ok) st = KC_PLAN_GOAL_INVALID;
-  else if (c->h_word.p[3] == kPlanInf) st = KC_PLAN_UNREACHABLE;
-  c->status = st;
-  c->cost = st == KC_PLAN_FOUND ? c->h_word.p[3] : kPlanInf;
-  *status_out = st;
-  if (cost_out) *cost_out = c->cost;
-  if (passes_out) *passes_out = goal_in ? static_cast<int>(last_changed + 1u) : 0;
+  // the start needs its own class, the goal any (rule 16); the state field is not kept (rule 20)
+  KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field4[c->final_buf].p + static_cast<size_t>(start_class) * static_cast<size_t>(n),
+                        c->d_valid4.p, 1u << start_class, 15u, false, status_out, cost_out));
+  if (passes_out) *passes_out = static_cast<int>(passes);
   return KC_OK;
 }
 
