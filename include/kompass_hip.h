@@ -846,7 +846,8 @@ int kc_planner_after_stream(kc_planner *ctx, void *stream);
  * KC_ERR_RANGE if the field still changes after cells + 1 passes (it cannot: every
  * pass but the last settles a cell); KC_ERR_STATE without a grid. */
 enum { KC_PLAN_FOUND = 0, KC_PLAN_START_OUTSIDE = 1, KC_PLAN_GOAL_OUTSIDE = 2, KC_PLAN_START_INVALID = 3,
-       KC_PLAN_GOAL_INVALID = 4, KC_PLAN_UNREACHABLE = 5 };
+       KC_PLAN_GOAL_INVALID = 4, KC_PLAN_UNREACHABLE = 5,
+       KC_PLAN_NO_FRONTIER = 6 /* kc_planner_explore alone: no frontier is kept */ };
 int kc_planner_solve(kc_planner *ctx, const int start_cell[2], const int goal_cell[2], uint32_t r2,
                      int allow_unknown, int *status_out, uint32_t *cost_out, int *passes_out);
 /* the last solve's cost field and validity map (1 valid, 0 invalid), laid out as
@@ -973,6 +974,62 @@ int kc_planner_replan(kc_planner *ctx, const int start_cell[2], const int goal_c
  * was compared).  Any pointer may be NULL. */
 int kc_planner_replan_info(kc_planner *ctx, int *replanned_out, uint32_t *threshold_out, uint32_t *touched_out,
                            uint32_t *active_tiles_out);
+/* Exploration (rules 21 to 26): the frontiers of the known map that the
+ * robot can reach, nearest first, and the way to each.  A solve-type call like
+ * kc_planner_solve: it replaces the last solve's outputs.
+ *  - rule 21: a cell is explore-valid when no KC_OCCUPIED cell lies within r2 of it (the
+ *    test of kc_planner_solve with allow_unknown = 1) and it is not KC_UNEXPLORED itself.
+ *    No allow_unknown argument: unknown cells neither inflate nor can be crossed.
+ *  - rule 22: field = kc_planner_solve's field over explore-valid cells with robot_cell
+ *    as its root.  *status_out = KC_PLAN_START_OUTSIDE for a robot cell outside the grid,
+ *    KC_PLAN_START_INVALID for one that is not explore-valid; both with zero frontiers.
+ *  - rule 23: a frontier cell is explore-valid, has min_cost <= field < 0xFFFFFFFF and a
+ *    KC_UNEXPLORED cell among its four orthogonal neighbours inside the grid.
+ *  - rule 24: a frontier is an 8-connected component of frontier cells, its label the
+ *    smallest flat index i + j * width among them; *components_out counts them; one is
+ *    kept when it has at least min_size cells.
+ *  - rule 25: *count_out kept frontiers, sorted by (cost, entry flat index); *status_out =
+ *    KC_PLAN_FOUND with at least one, KC_PLAN_NO_FRONTIER with none.
+ * *passes_out: the field's passes by kc_planner_solve's rule; *label_passes_out: the
+ * labelling's by the same rule (0 when there is no frontier cell).  Any of the last four
+ * pointers may be NULL.  Before any device use: KC_ERR_RANGE for r2 beyond
+ * KC_PLANNER_MAX_RADIUS_CELLS cells and for min_size == 0; KC_ERR_STATE without a grid,
+ * with a clearance cost set or with the oriented footprint on.  Afterwards
+ * kc_planner_get_field gives the explore field and rule 21's map; kc_planner_get_path,
+ * kc_planner_shortcut and kc_planner_path_clearance answer KC_ERR_STATE until the next
+ * solve; kc_planner_solve gives what a fresh context gives and kc_planner_replan is a
+ * full solve: neither rule 21's map nor the robot's field is kept for them. */
+typedef struct kc_planner_frontier {
+  uint64_t sum_i, sum_j;     /* exact sums of the cells' indices: the centroid is (sum_i, sum_j) / size */
+  uint32_t size;             /* cells */
+  uint32_t root;             /* the label */
+  uint32_t cost;             /* field[entry cell] */
+  int32_t entry_i, entry_j;  /* the cell with the smallest (field, flat index) */
+  uint32_t reserved_;
+} kc_planner_frontier;
+int kc_planner_explore(kc_planner *ctx, const int robot_cell[2], uint32_t r2, uint32_t min_cost, uint32_t min_size,
+                       int *status_out, uint32_t *components_out, size_t *count_out, int *passes_out,
+                       int *label_passes_out);
+/* rule 25: the kept frontiers of the last kc_planner_explore in their order; NULL asks
+ * for the count only; KC_ERR_RANGE when they do not fit cap; KC_ERR_STATE unless the last
+ * solve-type call was kc_planner_explore */
+int kc_planner_get_frontiers(kc_planner *ctx, kc_planner_frontier *out, size_t cap, size_t *count_out);
+/* rule 26: the path to kept frontier k: the walk from its entry cell down the field,
+ * at each cell the allowed neighbour with the smallest field + step (10 / 14), the first
+ * in kc_planner_get_path's order among equals (that minimum equals the cell's field:
+ * the steps sum to the frontier's cost exactly), handed out reversed: (i, j) pairs, the
+ * robot's cell first, the entry cell last.  NULL asks for the count only.  KC_ERR_RANGE for
+ * k outside the kept list; KC_ERR_STATE unless the last solve-type call was
+ * kc_planner_explore */
+int kc_planner_get_frontier_path(kc_planner *ctx, size_t k, int32_t *cells_ij_out, size_t cap, size_t *count_out);
+/* rule 24's labels of every frontier cell, kept or not, laid out as the grid, 0xFFFFFFFF
+ * where the cell is no frontier cell (tests); KC_ERR_STATE as above */
+int kc_planner_get_frontier_labels(kc_planner *ctx, uint32_t *labels_out, size_t cap);
+/* what the last kc_planner_explore did (tools): the 64 x 64 tiles that hold a frontier
+ * cell and so were labelled (rule 24 runs over those alone), all tiles, and the host's
+ * clock in milliseconds around its three phases, each ended by a read-back: validity +
+ * field, mark + label, sizes + records.  Any pointer may be NULL; KC_ERR_STATE as above */
+int kc_planner_explore_info(kc_planner *ctx, uint32_t *listed_tiles_out, uint32_t *tiles_out, float phase_ms_out[3]);
 
 /* ------------------------------------------------------------------------ */
 /* World map: the mapper's egocentric grids fused on the device */

@@ -1223,6 +1223,42 @@ PYBIND11_MODULE(kompass_cpp, m) {
              if (!o.empty()) std::memcpy(a.mutable_data(), o.data(), o.size() * sizeof(int32_t));
              return a;
            }, py::arg("k"), py::arg("a2"), py::arg("b2"), "The (di, dj) offsets of class k's footprint mask, in integers")
+      .def("explore", [](Planning::GridPlanner &p, double robot_x, double robot_y, double min_distance, uint32_t min_size) {
+             py::gil_scoped_release nogil;
+             return p.explore(robot_x, robot_y, min_distance, min_size);
+           }, py::arg("robot_x"), py::arg("robot_y"), py::arg("min_distance") = 0.0, py::arg("min_size") = 8,
+           "The frontiers of the known map the robot can reach (rules 21 to 26): true when at least one of min_size cells "
+           "or more lies min_distance metres or more along the field; raises with a clearance cost or the oriented footprint on")
+      .def("get_frontiers", [](Planning::GridPlanner &p) {
+             py::list out;
+             for (const auto &f : p.frontiers())
+               out.append(py::dict(py::arg("entry") = py::make_tuple(f.entry_x, f.entry_y), py::arg("entry_cell") = py::make_tuple(f.entry_i, f.entry_j),
+                                   py::arg("centroid") = py::make_tuple(f.centroid_x, f.centroid_y), py::arg("cost") = f.cost,
+                                   py::arg("size") = f.size, py::arg("root") = f.root));
+             return out;
+           }, "The kept frontiers of the last explore(), nearest first: dicts of entry (x, y), entry_cell (i, j), centroid (x, y), "
+              "cost in metres, size in cells and root (the label)")
+      .def("get_frontier_solution", [](Planning::GridPlanner &p, size_t k) -> py::object {
+             auto path = p.frontierPath(k);
+             if (!path) return py::none();
+             return py::cast(std::move(*path));
+           }, py::arg("k"), "The Path from the robot to the entry cell of kept frontier k")
+      .def("get_frontier_path_cells", [](Planning::GridPlanner &p, size_t k) {
+             const std::vector<int32_t> ij = p.frontierPathCells(k);
+             py::array_t<int32_t> a({(py::ssize_t)(ij.size() / 2), (py::ssize_t)2});
+             if (!ij.empty()) std::memcpy(a.mutable_data(), ij.data(), ij.size() * sizeof(int32_t));
+             return a;
+           }, py::arg("k"))
+      .def("get_frontier_labels", [](Planning::GridPlanner &p) {
+             const py::ssize_t w = p.width(), h = p.height();
+             py::array_t<uint32_t, py::array::f_style> l({w, h});
+             p.frontierLabels(l.mutable_data(), static_cast<size_t>(w) * static_cast<size_t>(h));
+             return l;
+           }, "uint32 [i, j]: the label of every frontier cell of the last explore(), 0xFFFFFFFF elsewhere")
+      .def("get_components", &Planning::GridPlanner::components, "the frontiers of the last explore(), kept or not")
+      .def("get_label_passes", &Planning::GridPlanner::labelPasses)
+      .def_static("min_distance_to_cost", &Planning::GridPlanner::minDistanceToCost, py::arg("min_distance"), py::arg("resolution"),
+                  "min_cost of explore(): lround(min_distance / resolution * 10), needs no device")
       .def("get_clearance_c2", &Planning::GridPlanner::clearanceC2)
       .def("get_clearance_weight10", &Planning::GridPlanner::clearanceWeight10)
       .def("get_status", &Planning::GridPlanner::status)

@@ -10,7 +10,9 @@
 // the same walk (rules 9 to 12): far fewer waypoints, straight where there is line of sight, and with a clearance
 // cost no closer to a blocking cell than the walk already came.  setOrientedFootprint (BOX robots, rules 13 to 18)
 // plans over (cell, heading class) with the box's own oriented footprint instead of the disc: the robot moves along
-// its length axis wherever the box fits and turns in place only where the turning disc fits.
+// its length axis wherever the box fits and turns in place only where the turning disc fits.  explore (rules 21 to 26)
+// asks the map instead of the caller for a goal: the frontiers of the known map that the robot can reach, nearest
+// first, and the path to each.
 #pragma once
 
 #include <cstdint>
@@ -123,6 +125,33 @@ class GridPlanner {
   // rule 14's offsets of class k as (di, dj) pairs, row by row (dj rising, then di); needs no device.
   // std::invalid_argument for k outside 0 .. 3, std::out_of_range where A2 + B2 reaches beyond 254 cells.
   static std::vector<int32_t> orientedMask(int k, uint32_t a2, uint32_t b2);
+  // Exploration (rules 21 to 26): the reachable frontiers of the grid from the cell of (robot_x, robot_y), the
+  // footprint the disc (only occupied cells inflate, unknown cells are never crossed: allow_unknown plays no part).
+  // min_distance_m: a frontier cell lies at least that far along the field, min_cost = lround(min_distance_m /
+  // resolution * 10) in double; min_size: the cells a frontier has at least (std::out_of_range for 0).  true when at
+  // least one is kept.  A solve-type call: getPath / getCost describe nothing until the next solve(), getField gives
+  // the explore field.  The problem of the last setupProblem is not touched: the robot's position is this call's
+  // own argument, and the next solve() or replan() (a full solve then) plans from the start that was set up.
+  // std::invalid_argument with a clearance cost or the oriented footprint on: a frontier is ranked by plain travel
+  // cost to a cell, which neither defines (rule 22).
+  struct Frontier {
+    float entry_x, entry_y;        // the nearest cell of the frontier, in the map's frame
+    int entry_i, entry_j;
+    float centroid_x, centroid_y;  // origin + (sum of the indices / size) * resolution, in double, cast to float
+    float cost;                    // field[entry] * resolution / 10, as getCost
+    uint32_t size, root;
+  };
+  bool explore(double robot_x, double robot_y, double min_distance_m = 0.0, uint32_t min_size = 8);
+  // the kept frontiers of the last explore(), sorted by (cost, entry flat index); empty after anything else
+  std::vector<Frontier> frontiers();
+  uint32_t components() const { return components_; }
+  int labelPasses() const { return label_passes_; }
+  // the path to kept frontier k, robot first; std::out_of_range for k outside the list
+  std::optional<Path::Path> frontierPath(size_t k);
+  std::vector<int32_t> frontierPathCells(size_t k);
+  // rule 24's labels, width x height as the grid, 0xFFFFFFFF where the cell is no frontier cell
+  void frontierLabels(uint32_t *labels_out, size_t cap);
+  static uint32_t minDistanceToCost(double min_distance_m, float resolution);
   int width() const { return width_; }
   int height() const { return height_; }
 
@@ -151,6 +180,9 @@ class GridPlanner {
   uint32_t cost_ = 0xFFFFFFFFu;
   bool replanned_ = false;
   uint32_t replan_threshold_ = 0xFFFFFFFFu;
+  bool explored_ = false;  // the last solve-type call was explore(): status_ is its status, cost_ stays at "none"
+  uint32_t components_ = 0;
+  int label_passes_ = 0;
   bool clear_on_ = false;
   double reach_ = 0.0;
   uint32_t weight10_ = 0;
@@ -169,6 +201,7 @@ class GridPlanner {
   void needDiscMode() const {  // the any-angle calls: a segment at an arbitrary angle has no heading class (rule 18)
     if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
   }
+  bool havePath() const { return status_ == KC_PLAN_FOUND && !explored_; }  // of a solve: explore() hands out frontier paths
   void forgetSolve();
   void beginSolve();
   Path::Path cellsToPath(const std::vector<int32_t> &ij) const;  // (i, j) pairs -> the cells' world points

@@ -232,6 +232,9 @@ void GridPlanner::forgetSolve() {
   status_ = -1;
   passes_ = 0;
   cost_ = 0xFFFFFFFFu;
+  explored_ = false;
+  components_ = 0;
+  label_passes_ = 0;
 }
 
 void GridPlanner::setGrid(const void *host_grid, int elem_bytes) {
@@ -294,9 +297,79 @@ void GridPlanner::setupProblem(double start_x, double start_y, double start_yaw,
 void GridPlanner::beginSolve() {
   if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
   if (!have_problem_) throw std::runtime_error("GridPlanner: setup_problem first");
-  status_ = -1;
+  forgetSolve();
   replanned_ = false;
   replan_threshold_ = 0xFFFFFFFFu;
+}
+
+uint32_t GridPlanner::minDistanceToCost(double min_distance_m, float resolution) {
+  if (!(min_distance_m >= 0.0) || !std::isfinite(min_distance_m)) throw std::invalid_argument("min_distance must be finite and >= 0");
+  const double c = min_distance_m / static_cast<double>(resolution) * 10.0;
+  if (!(c < 4294967294.5)) throw std::out_of_range("min_distance is too many cells");
+  return static_cast<uint32_t>(std::llround(c));
+}
+
+bool GridPlanner::explore(double robot_x, double robot_y, double min_distance_m, uint32_t min_size) {
+  if (oriented_on_) throw std::invalid_argument("GridPlanner: no exploration with the oriented footprint on: a frontier is ranked by the disc's travel cost to a cell");
+  if (clear_on_) throw std::invalid_argument("GridPlanner: no exploration with a clearance cost set: a frontier is ranked by plain travel cost");
+  needBounds();
+  if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
+  const uint32_t min_cost = minDistanceToCost(min_distance_m, res_);
+  forgetSolve();
+  replanned_ = false;
+  replan_threshold_ = 0xFFFFFFFFu;
+  // a coordinate no cell holds is outside the grid.  The robot's cell is this call's own: the start and the goal of
+  // the last setupProblem stay what they are for the next solve() or replan()
+  int robot[2] = {-1, -1};
+  if (!worldToCell(static_cast<float>(robot_x), ox_, res_, &robot[0])) robot[0] = -1;
+  if (!worldToCell(static_cast<float>(robot_y), oy_, res_, &robot[1])) robot[1] = -1;
+  size_t kept = 0;
+  hip::check(kc_planner_explore(ctx_.get(), robot, footprintR2(), min_cost, min_size, &status_, &components_, &kept, &passes_, &label_passes_));
+  explored_ = true;
+  return status_ == KC_PLAN_FOUND;
+}
+
+std::vector<GridPlanner::Frontier> GridPlanner::frontiers() {
+  std::vector<Frontier> out;
+  if (!explored_) return out;
+  size_t n = 0;
+  hip::check(kc_planner_get_frontiers(ctx_.get(), nullptr, 0, &n));
+  std::vector<kc_planner_frontier> rec(n);
+  if (n) hip::check(kc_planner_get_frontiers(ctx_.get(), rec.data(), n, &n));
+  out.reserve(n);
+  for (const kc_planner_frontier &r : rec) {
+    Frontier f;
+    f.entry_i = r.entry_i;
+    f.entry_j = r.entry_j;
+    f.entry_x = cellToWorld(r.entry_i, ox_, res_);
+    f.entry_y = cellToWorld(r.entry_j, oy_, res_);
+    const double size = static_cast<double>(r.size);
+    f.centroid_x = static_cast<float>(static_cast<double>(ox_) + static_cast<double>(r.sum_i) / size * static_cast<double>(res_));
+    f.centroid_y = static_cast<float>(static_cast<double>(oy_) + static_cast<double>(r.sum_j) / size * static_cast<double>(res_));
+    f.cost = static_cast<float>(r.cost) * res_ / 10.0f;
+    f.size = r.size;
+    f.root = r.root;
+    out.push_back(f);
+  }
+  return out;
+}
+
+std::vector<int32_t> GridPlanner::frontierPathCells(size_t k) {
+  if (!explored_) throw std::runtime_error("GridPlanner: frontier paths come after explore()");
+  size_t n = 0;
+  hip::check(kc_planner_get_frontier_path(ctx_.get(), k, nullptr, 0, &n));
+  std::vector<int32_t> ij(2 * n);
+  if (n) hip::check(kc_planner_get_frontier_path(ctx_.get(), k, ij.data(), n, &n));
+  return ij;
+}
+
+std::optional<Path::Path> GridPlanner::frontierPath(size_t k) {
+  return cellsToPath(frontierPathCells(k));
+}
+
+void GridPlanner::frontierLabels(uint32_t *labels_out, size_t cap) {
+  if (!explored_) throw std::runtime_error("GridPlanner: frontier labels come after explore()");
+  hip::check(kc_planner_get_frontier_labels(ctx_.get(), labels_out, cap));
 }
 
 bool GridPlanner::solve() {
@@ -327,7 +400,7 @@ void GridPlanner::cells(int start_out[2], int goal_out[2]) const {
 
 std::vector<int32_t> GridPlanner::getPathCells(bool simplify) {
   std::vector<int32_t> ij;
-  if (status_ != KC_PLAN_FOUND) return ij;
+  if (!havePath()) return ij;
   size_t n = 0;
   hip::check(kc_planner_get_path(ctx_.get(), nullptr, 0, &n));
   ij.resize(2 * n);
@@ -357,7 +430,7 @@ Path::Path GridPlanner::cellsToPath(const std::vector<int32_t> &ij) const {
 }
 
 std::optional<Path::Path> GridPlanner::getPath(bool simplify) {
-  if (status_ != KC_PLAN_FOUND) return std::nullopt;
+  if (!havePath()) return std::nullopt;
   return cellsToPath(getPathCells(simplify));
 }
 
@@ -367,12 +440,12 @@ void GridPlanner::getField(uint32_t *field_out, uint8_t *valid_out, size_t cap) 
 }
 
 float GridPlanner::getCost() const {
-  if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
+  if (!havePath()) return std::numeric_limits<float>::infinity();
   return static_cast<float>(cost_) * res_ / 10.0f;
 }
 
 float GridPlanner::getPathLength() {
-  if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
+  if (!havePath()) return std::numeric_limits<float>::infinity();
   const std::vector<int32_t> ij = getPathCells(false);
   uint64_t steps = 0;
   for (size_t k = 2; k + 1 < ij.size(); k += 2) steps += (ij[k] != ij[k - 2] && ij[k + 1] != ij[k - 1]) ? 14u : 10u;
@@ -381,7 +454,7 @@ float GridPlanner::getPathLength() {
 
 std::vector<int32_t> GridPlanner::getPathStates() {
   std::vector<int32_t> ijk;
-  if (status_ != KC_PLAN_FOUND || !oriented_on_) return ijk;
+  if (!havePath() || !oriented_on_) return ijk;
   size_t n = 0;
   hip::check(kc_planner_get_oriented_path(ctx_.get(), nullptr, 0, &n));
   ijk.resize(3 * n);
@@ -398,7 +471,7 @@ std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int
   needDiscMode();
   std::vector<int32_t> ij;
   if (indices_out) indices_out->clear();
-  if (status_ != KC_PLAN_FOUND) return ij;
+  if (!havePath()) return ij;
   size_t n = 0;
   hip::check(kc_planner_shortcut(ctx_.get(), max_span, &n, nullptr));
   ij.resize(2 * n);
@@ -409,13 +482,13 @@ std::vector<int32_t> GridPlanner::getAnyAngleCells(int max_span, std::vector<int
 
 std::optional<Path::Path> GridPlanner::getAnyAnglePath(int max_span) {
   needDiscMode();
-  if (status_ != KC_PLAN_FOUND) return std::nullopt;
+  if (!havePath()) return std::nullopt;
   return cellsToPath(getAnyAngleCells(max_span));
 }
 
 float GridPlanner::getAnyAngleLength(int max_span) {
   needDiscMode();
-  if (status_ != KC_PLAN_FOUND) return std::numeric_limits<float>::infinity();
+  if (!havePath()) return std::numeric_limits<float>::infinity();
   const std::vector<int32_t> ij = getAnyAngleCells(max_span);
   double sum = 0.0;
   for (size_t k = 2; k + 1 < ij.size(); k += 2) {
@@ -427,7 +500,7 @@ float GridPlanner::getAnyAngleLength(int max_span) {
 
 float GridPlanner::getAnyAngleMinClearance(int max_span) {
   needDiscMode();
-  if (status_ != KC_PLAN_FOUND) throw std::runtime_error("GridPlanner: no path");
+  if (!havePath()) throw std::runtime_error("GridPlanner: no path");
   uint32_t c2 = KC_PLANNER_CLEAR_FAR;
   hip::check(kc_planner_shortcut(ctx_.get(), max_span, nullptr, &c2));
   if (c2 == KC_PLANNER_CLEAR_FAR) return std::numeric_limits<float>::infinity();
@@ -440,7 +513,7 @@ void GridPlanner::getClearance(uint16_t *clear2_out, uint32_t *pen_out, size_t c
 }
 
 float GridPlanner::getPathMinClearance() const {
-  if (status_ != KC_PLAN_FOUND) throw std::runtime_error("GridPlanner: no path");
+  if (!havePath()) throw std::runtime_error("GridPlanner: no path");
   uint32_t c2 = KC_PLANNER_CLEAR_FAR;
   hip::check(kc_planner_path_clearance(ctx_.get(), &c2));
   if (c2 == KC_PLANNER_CLEAR_FAR) return std::numeric_limits<float>::infinity();

@@ -42,10 +42,19 @@
 //      rollback threshold T; planner_rollback_kernel puts every value below T back into both buffers and marks the tiles
 //      that hold a cell that may still change; planner_relax_list_kernel is (b) over those tiles only.
 //
+//  (h) exploration (rules 21 to 26; kc_planner_explore).  The validity of (a) with unknown not blocking, then
+//      planner_known_kernel takes the unknown cells out; the field of (b) rooted at the robot's cell;
+//      planner_frontier_mark_kernel writes the frontier bytes, both label planes and the tiles that hold a frontier cell;
+//      planner_label_kernel is (b)'s tile, halo, two buffers and changed word with "the smallest label among my eight
+//      frontier neighbours and me" as its update, over the listed tiles; sizes, kept roots and the records go by vector
+//      atomics from plain HIP (32-bit add at the root, 64-bit add and min at the record); planner_walk_kernel<false, true>
+//      walks from an entry cell down to the robot by field + step, so that the path costs what the record says.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstddef>
 #include <cstring>
 #include <type_traits>
@@ -155,6 +164,27 @@ __global__ __launch_bounds__(kPlanBlock) void planner_init_kernel(uint32_t *a, u
   }
 }
 
+// the 66 x 66 halo region of tile `tile` into LDS: v the byte of `map` (valid cells for the relaxation, frontier cells
+// for the labelling), f the value of `in` where that byte is set and INF elsewhere and outside the grid; *x0, *y0 the
+// grid cell of the region's corner.  Ends with the barrier behind the stores.
+__device__ __forceinline__ void plan_load_tile(unsigned tile, const uint32_t *__restrict__ in, const uint8_t *__restrict__ map, int W,
+                                               int H, unsigned tiles_x, uint32_t *f, uint8_t *v, int *x0_out, int *y0_out) {
+  // the tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more tile rows than gridDim.y holds
+  const int x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
+  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
+    const int lx = k % kPlanHalo, ly = k / kPlanHalo;
+    const int gx = x0 + lx, gy = y0 + ly;
+    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
+    const size_t g = inside ? static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx) : 0;
+    const uint8_t ok = inside ? map[g] : static_cast<uint8_t>(0);
+    v[k] = ok;
+    f[k] = ok ? in[g] : kPlanInf;  // invalid cells and cells outside the grid never carry a distance
+  }
+  __syncthreads();
+  *x0_out = x0;
+  *y0_out = y0;
+}
+
 // one pass over one tile: `in` is only read, `out` only written (the tile's own cells).  PEN: a step pays the
 // penalty of the cell it leaves (rule 7), which is the cell that is relaxed: one more register per owned cell, the
 // same LDS traffic.
@@ -166,18 +196,8 @@ __device__ __forceinline__ void plan_relax_tile(unsigned tile, const uint32_t *_
                                                 unsigned tiles_x, uint32_t *changed_word, uint32_t pass) {
   __shared__ uint32_t f[kPlanHalo * kPlanHalo];
   __shared__ uint8_t v[kPlanHalo * kPlanHalo];
-  // the tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more tile rows than gridDim.y holds
-  const int x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
-  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
-    const int lx = k % kPlanHalo, ly = k / kPlanHalo;
-    const int gx = x0 + lx, gy = y0 + ly;
-    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
-    const size_t g = inside ? static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx) : 0;
-    const uint8_t ok = inside ? valid[g] : static_cast<uint8_t>(0);
-    v[k] = ok;
-    f[k] = ok ? in[g] : kPlanInf;  // invalid cells and cells outside the grid never carry a distance
-  }
-  __syncthreads();
+  int x0, y0;
+  plan_load_tile(tile, in, valid, W, H, tiles_x, f, v, &x0, &y0);
   const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
   const int off[8] = {1, kPlanHalo, -1, -kPlanHalo, kPlanHalo + 1, kPlanHalo - 1, -kPlanHalo - 1, -kPlanHalo + 1};
   int idx[kPlanRows];
@@ -347,10 +367,166 @@ __global__ __launch_bounds__(kPlanBlock) void planner_compact_kernel(const uint8
     if (active[t]) list[atomicAdd(count, 1u)] = t;
 }
 
+// ---- exploration (rules 21 to 26) --------------------------------------------------------------------------------
+
+// rule 21's second half: an unknown cell is not explore-valid (the row and column passes ran with unknown not blocking)
+__global__ __launch_bounds__(kPlanBlock) void planner_known_kernel(const uint8_t *__restrict__ cls, uint8_t *valid, long long n) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride)
+    if (cls[i] == 1) valid[i] = 0;
+}
+
+// rule 23, one lane a cell: the frontier byte, the start of both label planes (the cell's own flat index, INF for the
+// rest) and a 1 into the byte of the tile that holds a frontier cell (bytes, zero before the launch).  A tile without
+// one holds INF in both planes and never changes, so only a cell's own tile is marked.
+__global__ __launch_bounds__(kPlanBlock) void planner_frontier_mark_kernel(const uint8_t *__restrict__ cls, const uint8_t *__restrict__ valid,
+                                                                           const uint32_t *__restrict__ field, uint32_t min_cost, int W,
+                                                                           int H, int tiles_x, uint8_t *__restrict__ front,
+                                                                           uint32_t *__restrict__ la, uint32_t *__restrict__ lb,
+                                                                           uint8_t *tile_on) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const uint32_t f = field[i];
+    bool fr = valid[i] != 0 && f != kPlanInf && f >= min_cost;
+    const int x = static_cast<int>(i % W), y = static_cast<int>(i / W);
+    if (fr)  // the four neighbours inside the grid, in the walk's order
+      fr = (x + 1 < W && cls[i + 1] == 1) || (y + 1 < H && cls[i + W] == 1) || (x > 0 && cls[i - 1] == 1) || (y > 0 && cls[i - W] == 1);
+    front[i] = fr ? 1 : 0;
+    const uint32_t l = fr ? static_cast<uint32_t>(i) : kPlanInf;  // the cell cap keeps a flat index below INF
+    la[i] = l;
+    lb[i] = l;
+    if (fr) tile_on[static_cast<size_t>(y / kPlanTile) * static_cast<size_t>(tiles_x) + static_cast<size_t>(x / kPlanTile)] = 1;
+  }
+}
+
+// rule 24, one pass over one listed tile, as plan_relax_tile: `in` is only read, `out` only written (the tile's own
+// cells).  A frontier cell takes the smallest label among itself and its eight neighbours; the cells that are no
+// frontier cells, and the ring outside the grid, hold INF and so never win.
+__global__ __launch_bounds__(kPlanThreads) void planner_label_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                     const uint8_t *__restrict__ front, int W, int H, unsigned tiles_x,
+                                                                     const uint32_t *__restrict__ tiles, uint32_t *changed_word,
+                                                                     uint32_t pass) {
+  __shared__ uint32_t f[kPlanHalo * kPlanHalo];
+  // The shared load's byte plane is not read here, and the compiler drops it (17 680 bytes of LDS, f alone).  Nor does
+  // the frontier byte decide a value: the mark kernel put INF into both label planes wherever the byte is 0, so what
+  // the load selects is in[g] inside the grid and INF outside it.  The bytes are passed because the helper is the
+  // relaxation's, unchanged.
+  __shared__ uint8_t v[kPlanHalo * kPlanHalo];
+  int x0, y0;
+  plan_load_tile(tiles[blockIdx.x], in, front, W, H, tiles_x, f, v, &x0, &y0);
+  const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
+  const int off[8] = {1, kPlanHalo, -1, -kPlanHalo, kPlanHalo + 1, kPlanHalo - 1, -kPlanHalo - 1, -kPlanHalo + 1};
+  int idx[kPlanRows];
+  uint32_t cur[kPlanRows], orig[kPlanRows];
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    idx[r] = (1 + ty + r * (kPlanThreads / kPlanTile)) * kPlanHalo + 1 + tx;
+    cur[r] = orig[r] = f[idx[r]];
+  }
+  for (int it = 0; it < kPlanLocalIters; ++it) {
+    int ch = 0;
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) {
+      if (cur[r] == kPlanInf) continue;  // no frontier cell
+      uint32_t best = cur[r];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) best = min(best, f[idx[r] + off[q]]);
+      if (best < cur[r]) {
+        cur[r] = best;
+        ch = 1;
+      }
+    }
+    if (!__syncthreads_or(ch)) break;  // every lane has read this iteration's values
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) f[idx[r]] = cur[r];
+    __syncthreads();
+  }
+  int changed = 0;
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int gx = x0 + 1 + tx, gy = y0 + 1 + ty + r * (kPlanThreads / kPlanTile);
+    if (gx < W && gy < H) out[static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)] = cur[r];
+    changed |= cur[r] != orig[r];
+  }
+  if (__syncthreads_or(changed) && threadIdx.x == 0) *changed_word = pass;
+}
+
+// rule 24's cell counts: `size` is a plane of zeros; a frontier cell adds one at its root (the label is a flat index)
+__global__ __launch_bounds__(kPlanBlock) void planner_frontier_size_kernel(const uint32_t *__restrict__ label, uint32_t *size, long long n) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const uint32_t l = label[i];
+    if (l != kPlanInf) atomicAdd(&size[l], 1u);
+  }
+}
+
+// a root is the cell that holds its own index.  out[0] += roots, out[1] += roots of at least min_size cells: a
+// wavefront reduction, then one atomic each per wavefront that saw a root.
+__global__ __launch_bounds__(kPlanBlock) void planner_frontier_count_kernel(const uint32_t *__restrict__ label, const uint32_t *__restrict__ size,
+                                                                            long long n, uint32_t min_size, uint32_t *out) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  uint32_t roots = 0, kept = 0;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride)
+    if (label[i] == static_cast<uint32_t>(i)) {
+      ++roots;
+      kept += size[i] >= min_size ? 1u : 0u;
+    }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    roots += static_cast<uint32_t>(__shfl_xor(static_cast<int>(roots), d, 64));
+    kept += static_cast<uint32_t>(__shfl_xor(static_cast<int>(kept), d, 64));
+  }
+  if ((threadIdx.x & 63) == 0 && roots) {
+    atomicAdd(&out[0], roots);
+    atomicAdd(&out[1], kept);
+  }
+}
+
+// rule 25's record as the device fills it; key = field << 32 | flat index of the entry cell
+struct PlanFrontierRec {
+  unsigned long long sum_i, sum_j, key;
+  uint32_t root, size;
+};
+
+// a kept root takes the next slot (any order: the host sorts) and starts its record; afterwards size[root] is the
+// slot of a kept root and INF for a dropped one.  rec holds as many records as planner_frontier_count_kernel counted.
+__global__ __launch_bounds__(kPlanBlock) void planner_frontier_slot_kernel(const uint32_t *__restrict__ label, uint32_t *size, long long n,
+                                                                           uint32_t min_size, PlanFrontierRec *rec, uint32_t *counter) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    if (label[i] != static_cast<uint32_t>(i)) continue;
+    const uint32_t cells = size[i];
+    uint32_t slot = kPlanInf;
+    if (cells >= min_size) {
+      slot = atomicAdd(counter, 1u);
+      rec[slot] = PlanFrontierRec{0ull, 0ull, ~0ull, static_cast<uint32_t>(i), cells};
+    }
+    size[i] = slot;
+  }
+}
+
+// rule 25: the cells of kept frontiers add their indices to their record and offer their (field, flat index)
+__global__ __launch_bounds__(kPlanBlock) void planner_frontier_record_kernel(const uint32_t *__restrict__ label, const uint32_t *__restrict__ slot,
+                                                                             const uint32_t *__restrict__ field, int W, long long n,
+                                                                             PlanFrontierRec *rec) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const uint32_t l = label[i];
+    if (l == kPlanInf) continue;
+    const uint32_t s = slot[l];
+    if (s == kPlanInf) continue;
+    atomicAdd(&rec[s].sum_i, static_cast<unsigned long long>(i % W));
+    atomicAdd(&rec[s].sum_j, static_cast<unsigned long long>(i / W));
+    atomicMin(&rec[s].key, (static_cast<unsigned long long>(field[i]) << 32) | static_cast<unsigned long long>(i));
+  }
+}
+
 // status words of the walk: out[0] = cells written, out[1] = 0 done / 1 capacity / 2 no descending neighbour.
 // PEN (rule 8): the key is field + step, its minimum must be field - penalty of the cell left, and out[2] = the
-// smallest clear2 among the cells visited.
-template <bool PEN>
+// smallest clear2 among the cells visited.  STEP without PEN (rule 26): rule 8's key and test with no penalty plane,
+// the walk that realises the field; <false> and <true> are <false, false> and <true, true>.
+template <bool PEN, bool STEP = PEN>
 __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field, const uint8_t *valid, const uint32_t *pen,
                                                           const uint16_t *clear2, int W, int H, int sx, int sy, int32_t *cells,
                                                           uint32_t cap, uint32_t *out) {
@@ -379,7 +555,7 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
           ok = valid[static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(nx)] != 0 &&
                valid[static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(cx)] != 0;
         // 64 bits hold an unreached neighbour's 0xFFFFFFFF + 14 as well
-        const unsigned long long step = PEN ? (lane < 4 ? 10ull : 14ull) : 0ull;
+        const unsigned long long step = STEP ? (lane < 4 ? 10ull : 14ull) : 0ull;
         if (ok) key = ((static_cast<unsigned long long>(field[g]) + step) << 3) | static_cast<unsigned long long>(lane);
       }
     }
@@ -392,6 +568,8 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
     bool off_field;  // not on a converged field with a reachable start
     if constexpr (PEN)
       off_field = key == ~0ull || (key >> 3) + static_cast<unsigned long long>(pen[c]) != static_cast<unsigned long long>(fc);
+    else if constexpr (STEP)
+      off_field = key == ~0ull || (key >> 3) != static_cast<unsigned long long>(fc);
     else
       off_field = key == ~0ull || static_cast<uint32_t>(key >> 3) >= fc;
     if (off_field) {
@@ -721,13 +899,16 @@ struct PlanWords {
   uint32_t walk_count, walk_status, walk_clear2;    // either walk's out[0..1]; out[2] of planner_walk_kernel<true>
   uint32_t short_count, short_status, short_clear2; // planner_shortcut_kernel's out[0..2]
   uint32_t rp_T, rp_touched, rp_listed;             // planner_touched_kernel's out[0..1], planner_compact_kernel's count
+  uint32_t ex_listed;                               // planner_compact_kernel's count of the tiles that hold a frontier cell
+  uint32_t ex_components, ex_kept, ex_slots;        // planner_frontier_count_kernel's out[0..1], planner_frontier_slot_kernel's counter
 };
 constexpr size_t kPlanSolveWords = 4;  // zeroed by one memset before the passes of a solve: changed and the walk's three
 // what the memsets, the multi-word copies and the kernels' out[] rely on
-static_assert(sizeof(PlanWords) == 40 && offsetof(PlanWords, changed) == 0 && offsetof(PlanWords, walk_count) == 4 &&
+static_assert(sizeof(PlanWords) == 56 && offsetof(PlanWords, changed) == 0 && offsetof(PlanWords, walk_count) == 4 &&
                   offsetof(PlanWords, walk_status) == 8 && offsetof(PlanWords, walk_clear2) == 12 && offsetof(PlanWords, short_count) == 16 &&
                   offsetof(PlanWords, short_status) == 20 && offsetof(PlanWords, short_clear2) == 24 && offsetof(PlanWords, rp_T) == 28 &&
-                  offsetof(PlanWords, rp_touched) == 32 && offsetof(PlanWords, rp_listed) == 36,
+                  offsetof(PlanWords, rp_touched) == 32 && offsetof(PlanWords, rp_listed) == 36 && offsetof(PlanWords, ex_listed) == 40 &&
+                  offsetof(PlanWords, ex_components) == 44 && offsetof(PlanWords, ex_kept) == 48 && offsetof(PlanWords, ex_slots) == 52,
               "changed .. walk_clear2 are words 0 .. 3; each kernel's out[0..2] are neighbours in its order");
 struct PlanPinned {
   PlanWords w;
@@ -793,6 +974,17 @@ struct kc_planner {
   DevBuf<uint32_t> d_tile_list;
   bool rp_kept = false;        // the last kc_planner_replan kept a field; T, touched cells, tiles relaxed
   uint32_t rp_T = kPlanInf, rp_touched = 0, rp_tiles = 0;
+  // exploration (rules 21 to 26)
+  bool explored = false;       // the last solve-type call was kc_planner_explore: d_field[final_buf] is rooted at the robot's
+                               // cell `start`, d_valid is rule 21's map (have_valid stays false: no solve may take it for its own)
+  int label_buf = 0;           // which of d_label holds rule 24's labels; the other one is the size / slot plane
+  uint32_t ex_components = 0, ex_tiles = 0;
+  float ex_ms[3] = {0.0f, 0.0f, 0.0f};  // host clock around the field, mark + label and records phases, each ended by its read-back
+  std::vector<kc_planner_frontier> frontiers;  // the kept records, sorted by (cost, entry flat index)
+  DevBuf<uint8_t> d_front;
+  DevBuf<uint32_t> d_label[2];
+  DevBuf<PlanFrontierRec> d_rec;
+  PinBuf<PlanFrontierRec> h_rec;
 };
 
 namespace {
@@ -804,7 +996,8 @@ void forget_walk(kc_planner *c) { c->have_path = c->have_short = false; }
 
 // also what a solve starts with: its outputs say "nothing" until it ends
 void forget_solve(kc_planner *c, uint32_t *cost_out = nullptr, int *passes_out = nullptr) {
-  c->solved = c->or_solve = c->fld_ok = false;
+  c->solved = c->or_solve = c->fld_ok = c->explored = false;
+  c->frontiers.clear();
   c->status = -1;
   c->cost = kPlanInf;
   if (cost_out) *cost_out = kPlanInf;
@@ -1024,10 +1217,11 @@ int planner_validity(kc_planner *c, uint32_t r2, int unknown_blocks) {
 // rule 3's passes to the fixed point, in batches of kPlanBatch with one read-back of the changed word (zero before the
 // first) a batch.  launch(k, b) queues pass k, which reads buffer b = (k - 1) & 1 of a field pair and writes the other.
 // A pass that is not the last gives at least one more of the `states` cells or states its final value: states + 1
-// passes always do.  c->final_buf: the buffer the last pass wrote; *passes_out: the passes a batch of one would have
-// run, the last that changed a cell and the one that found nothing to change.
+// passes always do.  *final_out: the buffer the last pass wrote; *passes_out: the passes a batch of one would have
+// run, the last that changed a cell and the one that found nothing to change.  The labelling (rule 24) is the same
+// loop: a pass that is not the last gives one more frontier cell its final label at least.
 template <typename Launch>
-int planner_relax(kc_planner *c, Launch &&launch, unsigned long long states, const char *noun, uint32_t *passes_out) {
+int planner_relax(kc_planner *c, Launch &&launch, unsigned long long states, const char *noun, int *final_out, uint32_t *passes_out) {
   const unsigned long long cap = states + 1ull;
   for (uint32_t pass = 0;;) {
     for (int b = 0; b < kPlanBatch; ++b) {
@@ -1039,7 +1233,7 @@ int planner_relax(kc_planner *c, Launch &&launch, unsigned long long states, con
     KC_HIP(hipStreamSynchronize(c->stream));
     const uint32_t last_changed = c->h_word.p->w.changed;
     if (last_changed < pass) {
-      c->final_buf = static_cast<int>(pass & 1u);
+      *final_out = static_cast<int>(pass & 1u);
       *passes_out = last_changed + 1u;
       return KC_OK;
     }
@@ -1179,7 +1373,7 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   KC_HIP(hipGetLastError());
   c->final_buf = 0;  // both buffers hold the initial state
   uint32_t passes = 0;
-  if (goal >= 0) KC_TRY(planner_relax(c, disc_pass(c, nullptr, c->tiles_x * c->tiles_y), n, "cost", &passes));
+  if (goal >= 0) KC_TRY(planner_relax(c, disc_pass(c, nullptr, c->tiles_x * c->tiles_y), n, "cost", &c->final_buf, &passes));
   KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field[c->final_buf].p, c->d_valid.p, 0xFFu, 0xFFu, true, status_out, cost_out));
   if (passes_out) *passes_out = static_cast<int>(passes);
   return KC_OK;
@@ -1238,7 +1432,7 @@ int kc_planner_replan(kc_planner *c, const int start_cell[2], const int goal_cel
       listed = c->h_word.p->w.rp_listed;
       if (listed > ntiles) KC_FAIL(KC_ERR_STATE, "%u tiles listed of %u", listed, ntiles);
       c->final_buf = 0;  // both buffers hold the rollback state, so pass 1 reads either
-      if (listed) KC_TRY(planner_relax(c, disc_pass(c, c->d_tile_list.p, listed), n, "cost", &passes));
+      if (listed) KC_TRY(planner_relax(c, disc_pass(c, c->d_tile_list.p, listed), n, "cost", &c->final_buf, &passes));
     }
   }
   KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field[c->final_buf].p, c->d_valid.p, 0xFFu, 0xFFu, true, status_out, cost_out));
@@ -1277,6 +1471,7 @@ int kc_planner_get_path(kc_planner *c, int32_t *cells_ij_out, size_t cap_points,
   if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   *count_out = 0;
   if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_path before kc_planner_solve");
+  if (c->explored) KC_FAIL(KC_ERR_STATE, "kc_planner_get_path after kc_planner_explore: kc_planner_get_frontier_path");
   if (c->status != KC_PLAN_FOUND) return KC_OK;  // no path: zero points
   KC_TRY(planner_walk(c));
   *count_out = c->path.size();
@@ -1324,7 +1519,7 @@ int kc_planner_get_clearance(kc_planner *c, uint16_t *clear2_out, uint32_t *pena
 
 int kc_planner_path_clearance(kc_planner *c, uint32_t *min_clear2_out) {
   if (!c || !min_clear2_out) KC_FAIL(KC_ERR_INVALID, "null argument");
-  if (!c->solved || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_path_clearance without a path");
+  if (!c->solved || c->explored || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_path_clearance without a path");
   if (c->clear_c2 == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_path_clearance with the clearance cost off");
   KC_TRY(planner_walk(c));
   *min_clear2_out = c->path_clear2;
@@ -1334,7 +1529,7 @@ int kc_planner_path_clearance(kc_planner *c, uint32_t *min_clear2_out) {
 int kc_planner_shortcut(kc_planner *c, int max_span, size_t *count_out, uint32_t *min_clear2_out) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (count_out) *count_out = 0;
-  if (!c->solved || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_shortcut without a path");
+  if (!c->solved || c->explored || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_shortcut without a path");
   if (c->or_solve) KC_FAIL(KC_ERR_STATE, "no any-angle path in oriented mode: a segment at an arbitrary angle has no class (rule 18)");
   if (max_span < 1 || max_span > KC_PLANNER_MAX_SPAN)
     KC_FAIL(KC_ERR_RANGE, "max_span %d is outside 1 .. %d", max_span, KC_PLANNER_MAX_SPAN);
@@ -1347,7 +1542,7 @@ int kc_planner_shortcut(kc_planner *c, int max_span, size_t *count_out, uint32_t
 int kc_planner_get_shortcut(kc_planner *c, int32_t *cells_ij_out, int32_t *index_out, size_t cap, size_t *count_out) {
   if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   *count_out = 0;
-  if (!c->solved || c->status != KC_PLAN_FOUND || !c->have_path || !c->have_short)
+  if (!c->solved || c->explored || c->status != KC_PLAN_FOUND || !c->have_path || !c->have_short)
     KC_FAIL(KC_ERR_STATE, "kc_planner_get_shortcut before kc_planner_shortcut");
   const size_t n = c->short_idx.size();
   *count_out = n;
@@ -1445,7 +1640,7 @@ int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_
       hipLaunchKernelGGL(planner_relax4_kernel, dim3(c->tiles_x * c->tiles_y), dim3(kPlanThreads), 0, s, c->d_field4[b].p, c->d_field4[b ^ 1].p,
                          c->d_valid4.p, W, H, static_cast<size_t>(n), c->tiles_x, c->or_turn10, &c->d_word.p->changed, pass);
     };
-    KC_TRY(planner_relax(c, pass4, 4ull * n, "state", &passes));
+    KC_TRY(planner_relax(c, pass4, 4ull * n, "state", &c->final_buf, &passes));
   }
   c->start_class = start_class;
   // the start needs its own class, the goal any (rule 16); the state field is not kept (rule 20)
@@ -1486,6 +1681,195 @@ int kc_planner_get_oriented_path(kc_planner *c, int32_t *states_ijk_out, size_t 
     states_ijk_out[3 * k + 1] = cell / c->W;
     states_ijk_out[3 * k + 2] = c->states[k] % 4;
   }
+  return KC_OK;
+}
+
+int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint32_t min_cost, uint32_t min_size, int *status_out,
+                       uint32_t *components_out, size_t *count_out, int *passes_out, int *label_passes_out) {
+  if (!c || !robot_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (components_out) *components_out = 0;
+  if (count_out) *count_out = 0;
+  if (label_passes_out) *label_passes_out = 0;
+  if (r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
+    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  if (min_size == 0) KC_FAIL(KC_ERR_RANGE, "min_size must be at least 1");
+  if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_explore before a grid was set");
+  if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_explore with the oriented footprint on (rule 22)");
+  if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_explore with a clearance cost set (rule 22)");
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const long long n = static_cast<long long>(W) * H;
+  const unsigned blocks = plan_blocks_for(n), ntiles = c->tiles_x * c->tiles_y;
+  PlanWords *d = c->d_word.p;
+  forget_solve(c, nullptr, passes_out);
+  c->ex_components = c->ex_tiles = 0;
+  const auto now = [] { return std::chrono::steady_clock::now(); };
+  const auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<float, std::milli>(now() - t).count(); };
+  auto t0 = now();
+  // rule 21.  d_valid then describes no (r2, unknown) of a solve: the cache says so, and forget_solve dropped the kept field
+  KC_TRY(planner_validity(c, r2, 0));
+  c->have_valid = false;
+  hipLaunchKernelGGL(planner_known_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_valid.p, n);
+  // rule 22: rule 3's field with the robot's cell as its root
+  const long long robot = plan_cell_index(c, robot_cell);
+  KC_TRY(c->d_field[0].reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_field[1].reserve(static_cast<size_t>(n)));
+  hipLaunchKernelGGL(planner_init_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, robot);
+  KC_HIP(hipMemsetAsync(d, 0, kPlanSolveWords * sizeof(uint32_t), s));
+  KC_HIP(hipGetLastError());
+  c->final_buf = 0;  // both buffers hold the initial state
+  uint32_t passes = 0, label_passes = 0;
+  if (robot >= 0) KC_TRY(planner_relax(c, disc_pass(c, nullptr, ntiles), n, "cost", &c->final_buf, &passes));
+  PlanPinned *h = c->h_word.p;
+  h->start_valid = 0;
+  if (robot >= 0) KC_HIP(hipMemcpyAsync(&h->start_valid, c->d_valid.p + robot, 1, hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  c->ex_ms[0] = ms_since(t0);
+  t0 = now();
+  // rule 23, and the tiles that hold a frontier cell.  With the robot outside the grid or on a cell that is not
+  // explore-valid the field is INF everywhere and nothing is marked.
+  const uint32_t *field = c->d_field[c->final_buf].p;
+  KC_TRY(c->d_front.reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_label[0].reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_label[1].reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_tile_on.reserve(ntiles));
+  KC_TRY(c->d_tile_list.reserve(ntiles));
+  KC_HIP(hipMemsetAsync(c->d_tile_on.p, 0, ntiles, s));
+  KC_HIP(hipMemsetAsync(&d->ex_listed, 0, 4 * sizeof(uint32_t), s));  // ex_listed .. ex_slots
+  hipLaunchKernelGGL(planner_frontier_mark_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_valid.p, field, min_cost, W, H,
+                     static_cast<int>(c->tiles_x), c->d_front.p, c->d_label[0].p, c->d_label[1].p, c->d_tile_on.p);
+  hipLaunchKernelGGL(planner_compact_kernel, dim3(plan_blocks_for(ntiles)), dim3(kPlanBlock), 0, s, c->d_tile_on.p, ntiles, c->d_tile_list.p,
+                     &d->ex_listed);
+  KC_HIP(hipMemsetAsync(&d->changed, 0, sizeof(uint32_t), s));
+  KC_HIP(hipGetLastError());
+  KC_HIP(plan_fetch_words(c, &PlanWords::ex_listed, 1));
+  KC_HIP(hipStreamSynchronize(s));  // whatever is listed: the mark kernel has ended here, inside the second phase's clock
+  const uint32_t listed = h->w.ex_listed;
+  if (listed > ntiles) KC_FAIL(KC_ERR_STATE, "%u tiles listed of %u", listed, ntiles);
+  c->label_buf = 0;  // both planes hold the initial labels
+  if (listed) {
+    // rule 24 over the listed tiles, to the fixed point
+    const auto label_pass = [&](uint32_t pass, int b) {
+      hipLaunchKernelGGL(planner_label_kernel, dim3(listed), dim3(kPlanThreads), 0, s, c->d_label[b].p, c->d_label[b ^ 1].p, c->d_front.p, W, H,
+                         c->tiles_x, c->d_tile_list.p, &d->changed, pass);
+    };
+    KC_TRY(planner_relax(c, label_pass, n, "label", &c->label_buf, &label_passes));
+  }
+  c->ex_ms[1] = ms_since(t0);
+  t0 = now();
+  uint32_t components = 0, kept = 0;
+  if (listed) {
+    // rule 24's sizes at the roots, in the plane the labels no longer need (both hold the fixed point), then the two counts
+    const uint32_t *label = c->d_label[c->label_buf].p;
+    uint32_t *size = c->d_label[c->label_buf ^ 1].p;
+    KC_HIP(hipMemsetAsync(size, 0, static_cast<size_t>(n) * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(planner_frontier_size_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, label, size, n);
+    hipLaunchKernelGGL(planner_frontier_count_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, label, size, n, min_size, &d->ex_components);
+    KC_HIP(hipGetLastError());
+    KC_HIP(plan_fetch_words(c, &PlanWords::ex_components, 2));
+    KC_HIP(hipStreamSynchronize(s));
+    components = h->w.ex_components;
+    kept = h->w.ex_kept;
+    if (kept > components || components > static_cast<unsigned long long>(n)) KC_FAIL(KC_ERR_STATE, "%u of %u components kept on %lld cells", kept, components, n);
+    if (kept) {
+      // rule 25: as many records as are kept, not one a cell
+      KC_TRY(c->d_rec.reserve(kept));
+      KC_TRY(c->h_rec.reserve(kept));
+      hipLaunchKernelGGL(planner_frontier_slot_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, label, size, n, min_size, c->d_rec.p, &d->ex_slots);
+      hipLaunchKernelGGL(planner_frontier_record_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, label, size, field, W, n, c->d_rec.p);
+      KC_HIP(hipGetLastError());
+      KC_HIP(hipMemcpyAsync(c->h_rec.p, c->d_rec.p, kept * sizeof(PlanFrontierRec), hipMemcpyDeviceToHost, s));
+      KC_HIP(hipStreamSynchronize(s));
+      std::sort(c->h_rec.p, c->h_rec.p + kept, [](const PlanFrontierRec &a, const PlanFrontierRec &b) { return a.key < b.key; });
+      c->frontiers.reserve(kept);
+      for (uint32_t k = 0; k < kept; ++k) {
+        const PlanFrontierRec &r = c->h_rec.p[k];
+        const uint32_t entry = static_cast<uint32_t>(r.key & 0xFFFFFFFFull);
+        kc_planner_frontier f = {};
+        f.sum_i = r.sum_i;
+        f.sum_j = r.sum_j;
+        f.size = r.size;
+        f.root = r.root;
+        f.cost = static_cast<uint32_t>(r.key >> 32);
+        f.entry_i = static_cast<int32_t>(entry % static_cast<uint32_t>(W));
+        f.entry_j = static_cast<int32_t>(entry / static_cast<uint32_t>(W));
+        c->frontiers.push_back(f);
+      }
+    }
+  }
+  c->ex_ms[2] = ms_since(t0);
+  int st = kept ? KC_PLAN_FOUND : KC_PLAN_NO_FRONTIER;
+  if (robot < 0) st = KC_PLAN_START_OUTSIDE;
+  else if (!h->start_valid) st = KC_PLAN_START_INVALID;
+  c->solved = c->explored = true;
+  c->start[0] = robot_cell[0];
+  c->start[1] = robot_cell[1];
+  c->status = st;
+  c->ex_components = components;
+  c->ex_tiles = listed;
+  *status_out = st;
+  if (components_out) *components_out = components;
+  if (count_out) *count_out = kept;
+  if (passes_out) *passes_out = static_cast<int>(passes);
+  if (label_passes_out) *label_passes_out = static_cast<int>(label_passes);
+  return KC_OK;
+}
+
+int kc_planner_explore_info(kc_planner *c, uint32_t *listed_tiles_out, uint32_t *tiles_out, float phase_ms_out[3]) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->explored) KC_FAIL(KC_ERR_STATE, "kc_planner_explore_info unless the last solve-type call was kc_planner_explore");
+  if (listed_tiles_out) *listed_tiles_out = c->ex_tiles;
+  if (tiles_out) *tiles_out = c->tiles_x * c->tiles_y;
+  if (phase_ms_out) std::copy(c->ex_ms, c->ex_ms + 3, phase_ms_out);
+  return KC_OK;
+}
+
+int kc_planner_get_frontiers(kc_planner *c, kc_planner_frontier *out, size_t cap, size_t *count_out) {
+  if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  if (!c->explored) KC_FAIL(KC_ERR_STATE, "kc_planner_get_frontiers unless the last solve-type call was kc_planner_explore");
+  *count_out = c->frontiers.size();
+  if (!out) return KC_OK;  // the count alone
+  if (c->frontiers.size() > cap) KC_FAIL(KC_ERR_RANGE, "%zu frontiers do not fit the output capacity %zu", c->frontiers.size(), cap);
+  std::copy(c->frontiers.begin(), c->frontiers.end(), out);
+  return KC_OK;
+}
+
+int kc_planner_get_frontier_path(kc_planner *c, size_t k, int32_t *cells_ij_out, size_t cap, size_t *count_out) {
+  if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  if (!c->explored) KC_FAIL(KC_ERR_STATE, "kc_planner_get_frontier_path unless the last solve-type call was kc_planner_explore");
+  if (k >= c->frontiers.size()) KC_FAIL(KC_ERR_RANGE, "frontier %zu of %zu", k, c->frontiers.size());
+  const kc_planner_frontier &f = c->frontiers[k];
+  // rule 26: every step of the walk lowers the field by its own 10 or 14
+  const size_t cells = static_cast<size_t>(f.cost / 10u) + 2;
+  KC_HIP(hipSetDevice(c->device));
+  KC_TRY(c->d_path.reserve(cells));
+  KC_TRY(c->h_path.reserve(cells));
+  hipLaunchKernelGGL((planner_walk_kernel<false, true>), dim3(1), dim3(64), 0, c->stream, c->d_field[c->final_buf].p, c->d_valid.p, nullptr, nullptr,
+                     c->W, c->H, f.entry_i, f.entry_j, c->d_path.p, static_cast<uint32_t>(cells), &c->d_word.p->walk_count);
+  uint32_t count = 0;
+  KC_TRY(planner_walk_fetch(c, cells, false, "frontier", "cells", &count));
+  *count_out = count;
+  if (!cells_ij_out) return KC_OK;  // the count alone
+  if (count > cap) KC_FAIL(KC_ERR_RANGE, "%u path cells do not fit the output capacity %zu", count, cap);
+  for (uint32_t q = 0; q < count; ++q) {  // the walk ends at the robot's cell: handed out reversed
+    const int32_t cell = c->h_path.p[count - 1 - q];
+    cells_ij_out[2 * q] = cell % c->W;
+    cells_ij_out[2 * q + 1] = cell / c->W;
+  }
+  return KC_OK;
+}
+
+int kc_planner_get_frontier_labels(kc_planner *c, uint32_t *labels_out, size_t cap) {
+  if (!c || !labels_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->explored) KC_FAIL(KC_ERR_STATE, "kc_planner_get_frontier_labels unless the last solve-type call was kc_planner_explore");
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipSetDevice(c->device));
+  KC_HIP(hipMemcpyAsync(labels_out, c->d_label[c->label_buf].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
   return KC_OK;
 }
 

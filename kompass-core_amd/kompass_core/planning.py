@@ -16,14 +16,29 @@ degrees, the headings an 8-connected path can have): the robot moves along its o
 box fits and turns in place only where the whole turning disc fits, so a long box is handed a path through a corridor
 it can take lengthwise.  That is the restricted, deterministic counterpart of the reference's SE(2) planning against
 the real shape.  `goal_yaw` stays unused on purpose: every heading class the box fits in at the goal cell ends the
-path."""
+path.
+`find_frontiers` / `explore` ask the map for the goal instead of the caller: the frontiers of the known map (free cells
+beside unexplored ones) that the robot's disc can reach without crossing an unexplored cell, as 8-connected components,
+nearest first by travel cost, each with its nearest cell, its centroid and the path to it.  The reference leaves
+frontier detection to its ROS side, as it does the world map; here it runs on the map where it lies on the device.
+Not combined with a clearance cost or the oriented footprint: a frontier is ranked by plain travel cost to a cell."""
 import math
-from typing import Dict, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import kompass_cpp
 
 from .mapping.world_map import WorldMap
 from .models import Robot, RobotGeometry
+
+
+class Frontier(NamedTuple):
+    """One reachable frontier of `GridPlanner.find_frontiers`."""
+    entry: Tuple[float, float]        # its nearest cell by travel cost, (x, y) in the map's frame
+    entry_cell: Tuple[int, int]       # that cell's (i, j)
+    centroid: Tuple[float, float]     # the mean of its cells, (x, y)
+    cost: float                       # metres of path from the robot to the entry cell
+    size: int                         # cells
+    root: int                         # its label: the smallest flat index i + j * width among its cells
 
 
 class GridPlanner:
@@ -64,6 +79,7 @@ class GridPlanner:
         if self.any_angle and not 1 <= self.max_span <= 1024:
             raise ValueError(f"max_span must be in 1 .. 1024, got {max_span}")
         self.solution = None
+        self.frontiers: List[Frontier] = []   # of the last find_frontiers()
         self._problem = None   # the last setup_problem's (start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw)
         if clearance_reach > 0.0 and clearance_weight > 0.0:
             self.set_clearance_cost(clearance_reach, clearance_weight)
@@ -87,6 +103,14 @@ class GridPlanner:
         `kompass_core.mapping.LocalMapper` (its last grid on the device; map_meta_data may then be None); a
         `kompass_core.mapping.WorldMap` (its class plane on the device and its metadata; map_meta_data may be None);
         or None to keep the grid of the last call."""
+        self._set_map(map_meta_data, grid)
+        self._planner.setup_problem(start_x=start_x, start_y=start_y, start_yaw=start_yaw, goal_x=goal_x,
+                                    goal_y=goal_y, goal_yaw=goal_yaw)
+        self._problem = (start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw)
+        self.solution = None
+
+    def _set_map(self, map_meta_data, grid):
+        """The bounds and the grid as setup_problem takes them."""
         if isinstance(grid, WorldMap):
             map_meta_data, grid = grid.map_meta_data, grid.device_grid
         mapper = grid
@@ -107,10 +131,6 @@ class GridPlanner:
                 height=map_meta_data["height"], resolution=map_meta_data["resolution"])
             if grid is not None:
                 self._planner.set_grid(grid)
-        self._planner.setup_problem(start_x=start_x, start_y=start_y, start_yaw=start_yaw, goal_x=goal_x,
-                                    goal_y=goal_y, goal_yaw=goal_yaw)
-        self._problem = (start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw)
-        self.solution = None
 
     def solve(self) -> Optional["kompass_cpp.types.Path"]:
         """The path, or None when the start or goal is outside the grid, invalid, or the goal out of reach."""
@@ -139,6 +159,66 @@ class GridPlanner:
             p = self._problem = (float(start[0]), float(start[1]), yaw) + self._problem[3:]
             self._planner.setup_problem(start_x=p[0], start_y=p[1], start_yaw=p[2], goal_x=p[3], goal_y=p[4], goal_yaw=p[5])
         return self._solution(self._planner.replan())
+
+    def find_frontiers(self, robot_x: float, robot_y: float, map=None, map_meta_data: Optional[Dict] = None,
+                       min_size: int = 8, min_distance: float = 0.0) -> List[Frontier]:
+        """The frontiers of the known map the robot can reach from (robot_x, robot_y), nearest first.  A frontier
+        cell is a cell the robot's disc fits on (only occupied cells inflate; unexplored cells are never crossed,
+        whatever `allow_unknown` says), at `min_distance` metres of path or more, beside an unexplored cell; a
+        frontier is an 8-connected group of at least `min_size` of them.  map: anything setup_problem(grid=...) takes,
+        a WorldMap or a LocalMapper read in place, or None for the grid and bounds as they are.  An empty list when
+        there is none, or the robot's cell is outside the map or not free for the disc (`status` says which).
+        A solve-type call: `solution`, get_cost and path_cells describe nothing until the next solve().  The problem
+        of the last setup_problem stays: the next solve() or replan() plans from its start to its goal, not from
+        (robot_x, robot_y).  A map or metadata given here replaces the grid and the bounds as setup_problem's would, and
+        that problem's start and goal are then taken into the new bounds' cells again."""
+        if self.footprint == "oriented":
+            raise ValueError("exploration is not combined with the oriented footprint: a frontier is ranked by the "
+                             "disc's travel cost to a cell, and the oriented field is one of (cell, heading) states")
+        if self._planner.get_clearance_weight10() > 0:
+            raise ValueError("exploration is not combined with a clearance cost: a frontier is ranked by plain travel "
+                             "cost, and min_distance is a length")
+        if int(min_size) < 1:
+            raise ValueError(f"min_size must be at least 1, got {min_size}")
+        if not (math.isfinite(min_distance) and min_distance >= 0.0):
+            raise ValueError(f"min_distance must be finite and >= 0, got {min_distance}")
+        if map is not None or map_meta_data is not None:
+            self._set_map(map_meta_data, map)
+            if self._problem is not None:   # its cells were those of the bounds before
+                p = self._problem
+                self._planner.setup_problem(start_x=p[0], start_y=p[1], start_yaw=p[2], goal_x=p[3], goal_y=p[4], goal_yaw=p[5])
+        self.solution = None
+        self._planner.explore(robot_x=float(robot_x), robot_y=float(robot_y), min_distance=float(min_distance),
+                              min_size=int(min_size))
+        self.frontiers = [Frontier(**f) for f in self._planner.get_frontiers()]
+        return self.frontiers
+
+    def explore(self, robot_x: float, robot_y: float, map=None, map_meta_data: Optional[Dict] = None, min_size: int = 8,
+                min_distance: float = 0.0) -> Optional["kompass_cpp.types.Path"]:
+        """find_frontiers, then the path to the nearest one (robot first, its entry cell last), or None without one."""
+        found = self.find_frontiers(robot_x, robot_y, map=map, map_meta_data=map_meta_data, min_size=min_size,
+                                    min_distance=min_distance)
+        return self.frontier_path(0) if found else None
+
+    def frontier_path(self, k: int) -> "kompass_cpp.types.Path":
+        """The path to frontier k of the last find_frontiers() list; IndexError outside it."""
+        if not 0 <= int(k) < len(self.frontiers):
+            raise IndexError(f"frontier {k} of {len(self.frontiers)}")
+        return self._planner.get_frontier_solution(int(k))
+
+    def frontier_path_cells(self, k: int):
+        if not 0 <= int(k) < len(self.frontiers):
+            raise IndexError(f"frontier {k} of {len(self.frontiers)}")
+        return self._planner.get_frontier_path_cells(int(k))
+
+    @property
+    def components(self) -> int:
+        """The frontiers of the last find_frontiers(), kept or not."""
+        return self._planner.get_components()
+
+    def frontier_labels(self):
+        """uint32 [width, height]: the label of every frontier cell of the last find_frontiers(), 0xFFFFFFFF elsewhere."""
+        return self._planner.get_frontier_labels()
 
     @property
     def replanned(self) -> bool:

@@ -258,6 +258,12 @@ SIGNATURES = {
                                     C.POINTER(C.c_int)]),
     "kc_planner_replan_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint32)]),
+    "kc_planner_explore": (C.c_int, [_vp, _ip, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                     C.POINTER(_sz), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kc_planner_get_frontiers": (C.c_int, [_vp, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_get_frontier_path": (C.c_int, [_vp, _sz, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_get_frontier_labels": (C.c_int, [_vp, C.c_void_p, _sz]),
+    "kc_planner_explore_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "kc_worldmap_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_double, C.c_double, C.POINTER(_vp)]),
     "kc_worldmap_destroy": (None, [_vp]),
     "kc_worldmap_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, _dp, _dp]),
@@ -1139,6 +1145,10 @@ class DvzContext(_Owner):
 
 
 PLAN_FOUND, PLAN_START_OUTSIDE, PLAN_GOAL_OUTSIDE, PLAN_START_INVALID, PLAN_GOAL_INVALID, PLAN_UNREACHABLE = range(6)
+PLAN_NO_FRONTIER = 6
+# kc_planner_frontier, field for field
+PLAN_FRONTIER_DTYPE = np.dtype([("sum_i", np.uint64), ("sum_j", np.uint64), ("size", np.uint32), ("root", np.uint32),
+                                ("cost", np.uint32), ("entry_i", np.int32), ("entry_j", np.int32), ("reserved_", np.uint32)])
 PLAN_INF = 0xFFFFFFFF
 PLAN_CLEAR_FAR = 0xFFFF
 PLAN_MAX_SPAN = 1024
@@ -1274,6 +1284,49 @@ class PlannerContext(_Owner, _StreamOrdered):
         kept, t, touched, tiles = C.c_int(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         _check(lib().kc_planner_replan_info(self.h, C.byref(kept), C.byref(t), C.byref(touched), C.byref(tiles)))
         return bool(kept.value), t.value, touched.value, tiles.value
+
+    def explore(self, robot, r2=0, min_cost=0, min_size=1):
+        """The reachable frontiers of the known map, nearest first (rules 21 to 26): frontier cells are explore-valid
+        cells (no occupied cell within r2, not unknown) with min_cost <= field < INF from the robot's cell and an
+        unknown orthogonal neighbour; a frontier is an 8-connected component of them, kept from min_size cells on.
+        -> (status, components, kept, field passes, label passes); status PLAN_FOUND, PLAN_NO_FRONTIER,
+        PLAN_START_OUTSIDE or PLAN_START_INVALID.  field() then gives the explore field and validity."""
+        cell = (C.c_int32 * 2)(int(robot[0]), int(robot[1]))
+        st, comps, kept, passes, lpasses = C.c_int(-1), C.c_uint32(0), _sz(0), C.c_int(0), C.c_int(0)
+        _check(lib().kc_planner_explore(self.h, cell, int(r2), int(min_cost), int(min_size), C.byref(st), C.byref(comps),
+                                        C.byref(kept), C.byref(passes), C.byref(lpasses)))
+        return st.value, comps.value, kept.value, passes.value, lpasses.value
+
+    def frontiers(self):
+        """The kept frontiers of the last explore(), sorted by (cost, entry flat index): a structured array of
+        PLAN_FRONTIER_DTYPE (sum_i, sum_j, size, root, cost, entry_i, entry_j)."""
+        n = _sz(0)
+        _check(lib().kc_planner_get_frontiers(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, PLAN_FRONTIER_DTYPE)
+        if n.value:
+            _check(lib().kc_planner_get_frontiers(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def frontier_path(self, k):
+        """(n, 2) int32 cells (i, j) from the robot's cell to the entry cell of kept frontier k."""
+        n = _sz(0)
+        _check(lib().kc_planner_get_frontier_path(self.h, int(k), None, 0, C.byref(n)))
+        cells = np.empty((n.value, 2), np.int32)
+        _check(lib().kc_planner_get_frontier_path(self.h, int(k), cells.ctypes.data, n.value, C.byref(n)))
+        return cells[:n.value]
+
+    def frontier_labels(self):
+        """uint32 [width, height]: the label of every frontier cell of the last explore(), PLAN_INF elsewhere."""
+        w, h = self.shape
+        lab = np.empty((w, h), np.uint32, order="F")
+        _check(lib().kc_planner_get_frontier_labels(self.h, lab.ctypes.data, lab.size))
+        return lab
+
+    def explore_info(self):
+        """(tiles labelled, all tiles, (field ms, mark + label ms, records ms)) of the last explore()."""
+        listed, tiles, ms = C.c_uint32(0), C.c_uint32(0), (C.c_float * 3)()
+        _check(lib().kc_planner_explore_info(self.h, C.byref(listed), C.byref(tiles), ms))
+        return listed.value, tiles.value, tuple(float(v) for v in ms)
 
 
 def worldmap_check_model(hit=3, miss=1, e_min=-8, e_max=14, occ_thr=1):

@@ -17,9 +17,15 @@ solve of the changed grid, (b) kc_planner_replan of the same grid behind an unti
 change a 5 x 5 blocked patch on the path 10 %, 50 % and 90 % of the way from the start, and (c) the replan with only
 the start moved (no grid set); milliseconds, passes, the threshold, the touched cells and the tiles relaxed; with
 --clearance the same with the cost on.
+--frontiers adds the exploration (rules 21 to 26) on both scenes: the part of the map farther than --frontier-radius
+cells from the robot (the scene's start) is turned to unknown; kc_planner_explore (r2 of the scene, min_cost 0, min_size
+8) on the resident grid, the whole call and its three phases by the library's own host clock (validity + field, mark +
+label, sizes + records), the field and label passes, the tiles labelled of all tiles, the frontiers kept of the
+components, the path to the first; and the Python statement of tests/planner_frontier_ref.py on one CPU thread (numpy,
+a heap Dijkstra and a flood fill in the interpreter: not a compiled CPU implementation).
 
   python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--shortcut 128] [--oriented 1.5,0.2]
-                               [--replan] [--json out.json]
+                               [--replan] [--frontiers] [--json out.json]
   rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
 """
 import argparse
@@ -37,6 +43,7 @@ for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
     sys.path.insert(0, str(p))
 import kompass_hip as kh  # noqa: E402
 import planner_clearance_ref as cref  # noqa: E402
+import planner_frontier_ref as fref  # noqa: E402
 import planner_oriented_ref as oref  # noqa: E402
 import planner_ref as ref  # noqa: E402
 import planner_shortcut_ref as sref  # noqa: E402
@@ -137,6 +144,53 @@ def replan_leg(ctx, host_grid, start, goal, r2, a):
     return out
 
 
+def frontier_leg(ctx, host_grid, start, r2, a):
+    """The scene's grid with everything beyond a radius of the robot unknown, then the scene's own grid again."""
+    w, h = host_grid.shape
+    ii, jj = np.meshgrid(np.arange(w), np.arange(h), indexing="ij")
+    radius = min(a.frontier_radius, max(w, h))
+    g = np.asarray(host_grid).copy()
+    g[(ii - start[0]) ** 2 + (jj - start[1]) ** 2 > radius * radius] = ref.UNEXPLORED
+    ctx.set_grid(g)
+    st, comps, kept, passes, lpasses = ctx.explore(start, r2, 0, 8)
+    listed, tiles, _ = ctx.explore_info()
+    out = dict(radius_cells=radius, status=st, components=comps, kept=kept, passes=passes, label_passes=lpasses, listed_tiles=listed,
+               tiles=tiles, first_path_cells=int(len(ctx.frontier_path(0))) if kept else 0)
+    whole, phases = [], []
+    for k in range(3 + a.reps):
+        t0 = time.perf_counter()
+        ctx.explore(start, r2, 0, 8)
+        t1 = time.perf_counter()
+        if k >= 3:
+            whole.append((t1 - t0) * 1e3)
+            phases.append(ctx.explore_info()[2])
+    st_ = lambda t: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), reps=len(t))  # noqa: E731
+    out["explore_ms"] = st_(whole)
+    for k, name in enumerate(("field_ms", "mark_label_ms", "records_ms")):
+        out[name] = st_([p[k] for p in phases])
+    if kept:
+        out["first_path_ms"] = stats_ms(lambda: ctx.frontier_path(0), a.reps)
+    if a.cpu_reps > 0:
+        t0 = time.perf_counter()
+        want = fref.explore(g, start, r2, 0, 8, paths=False)
+        dt = (time.perf_counter() - t0) * 1e3
+        out["python_statement_one_thread_ms"] = dict(median=dt, min=dt, max=dt, reps=1)
+        assert (want["status"], want["components"], len(want["frontiers"])) == (st, comps, kept)
+        assert (ctx.frontier_labels() == want["labels"]).all()
+    ctx.set_grid(host_grid)
+    return out
+
+
+def print_frontiers(f, indent):
+    print(f"{indent}frontiers within {f['radius_cells']} cells: status {f['status']}, {f['kept']} kept of {f['components']} components, "
+          f"{f['passes']} field passes, {f['label_passes']} label passes, {f['listed_tiles']} of {f['tiles']} tiles labelled, "
+          f"{f['first_path_cells']} cells to the first")
+    for k in ("explore_ms", "field_ms", "mark_label_ms", "records_ms", "first_path_ms", "python_statement_one_thread_ms"):
+        if k in f:
+            v = f[k]
+            print(f"{indent}  {k:30s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+
+
 def print_replan(r, indent):
     for leg in r["legs"]:
         f, p = leg["full_solve_ms"], leg["replan_ms"]
@@ -197,6 +251,8 @@ def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
         out["shortcut"] = shortcut_leg(ctx, start, goal, r2, a)
     if a.replan:
         out["replan"] = replan_leg(ctx, np.asarray(host_grid), start, goal, r2, a)
+    if a.frontiers:
+        out["frontiers"] = frontier_leg(ctx, host_grid, start, r2, a)
     if a.clearance:
         out["clearance"] = clearance_leg(ctx, np.asarray(host_grid), start, goal, r2, a)
     if a.oriented:
@@ -287,6 +343,8 @@ def main():
     ap.add_argument("--shortcut", type=int, default=0, metavar="W", help="time the any-angle path of span W")
     ap.add_argument("--oriented", default=None, metavar="X,Y[,TURN]", help="time the oriented footprint of an X x Y m box")
     ap.add_argument("--replan", action="store_true", help="time the replan against a full solve of the changed grid")
+    ap.add_argument("--frontiers", action="store_true", help="time kc_planner_explore with the far part of the map unknown")
+    ap.add_argument("--frontier-radius", type=int, default=300, metavar="CELLS", help="what the robot knows, in cells around it")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if kh.device_count() < 1:
@@ -323,6 +381,8 @@ def main():
             print_shortcut(s["shortcut"], "  ")
         if "replan" in s:
             print_replan(s["replan"], "  ")
+        if "frontiers" in s:
+            print_frontiers(s["frontiers"], "  ")
         c = s.get("clearance")
         if c:
             print(f"  clearance cost C2 {c['c2']}, weight {c['weight10']}: status {c['status']}, cost {c['cost']}, length "
