@@ -1123,6 +1123,69 @@ int kc_worldmap_grid_device(kc_worldmap *ctx, void **dev_cls_int8);
 /* copies of the planes, cap the cells either output holds; either pointer may be NULL */
 int kc_worldmap_get(kc_worldmap *ctx, int8_t *cls_out, int8_t *evidence_out, size_t cap);
 
+/* Correlative match of a local grid against the map (DESIGN.md 4.11 rules 9 to 15): which
+ * pose near a guess puts the grid's occupied cells onto the map's?  Integers only, sums
+ * of integers, so no result depends on thread order; the map is not modified.
+ * Rule 9: every local cell (i, j) that holds KC_OCCUPIED is a point (a, b) = (i -
+ * central_i, j - central_j); no other value counts.  Rule 10: the window is n_yaw = K
+ * rotations each side of the guess's yaw, yaw_step apart, and reach = S whole cells each
+ * side along both axes.  Rule 11: under rotation k a point lands at I0 = (TX + Cq_k a -
+ * Sq_k b + 2^15) >> 16, J0 = (TY + Sq_k a + Cq_k b + 2^15) >> 16 (int64, arithmetic
+ * shifts; the guess's fraction is kept), under translation (u, v) in world cell (I0 + u,
+ * J0 + v).  Rule 12: a world cell weighs 3 if its cls byte is KC_OCCUPIED, else 2 if one
+ * of its four orthogonal neighbours inside the map is, else 1 if a diagonal one is, else
+ * 0; a cell outside the map weighs 0 and is nobody's neighbour.  Rule 13: score(k, u,
+ * v) is the sum of the landing cells' weights over all points, uint32, stored at (k + K)
+ * (2S+1)^2 + (v + S) (2S+1) + (u + S).  Rule 14: the largest score wins, among equals
+ * the smallest (u u + v v, |k|, k, v, u): a flat score returns the guess. */
+#define KC_WORLDMAP_MATCH_MAX_YAW 31    /* K */
+#define KC_WORLDMAP_MATCH_MAX_REACH 31  /* S */
+#define KC_WORLDMAP_MATCH_MAX_SIDE 8192 /* cells a side of the local grid */
+typedef struct kc_worldmap_rotation { /* rule 10: rotation k of the window */
+  int32_t cq, sq;                     /* lrint(cos(yaw_k) * 65536), lrint(sin(yaw_k) * 65536) */
+} kc_worldmap_rotation;
+typedef struct kc_worldmap_match_result { /* rule 15 */
+  int32_t k, u, v;                        /* the winner: rotation step, translation in cells */
+  uint32_t score, score_guess;            /* the winner's, and score(0, 0, 0) */
+  uint32_t n_points;                      /* rule 9's count; 0: every score is 0, the guess wins */
+  kc_worldmap_pose pose;                  /* (Cq_k, Sq_k, TX + (u << 16), TY + (v << 16)): ready for an update */
+} kc_worldmap_match_result;
+/* rule 10's ranges (host only): n_yaw and reach in 0 .. 31, yaw_step a finite double >=
+ * 0, KC_ERR_INVALID otherwise */
+int kc_worldmap_match_check_window(int n_yaw, double yaw_step, int reach);
+/* rule 9's test of the local grid (host only): kc_worldmap_check_grid, then KC_ERR_RANGE
+ * for a side above 8192 or a cell more than 8192 cells from the central cell along an
+ * axis (which bounds the scratch plane) */
+int kc_worldmap_match_check_grid(float world_resolution, int grid_height, int grid_width, int central_i, int central_j,
+                                 float resolution);
+/* rule 10's table (host only, compare kc_worldmap_quantise_pose): out[k + n_yaw] for k =
+ * -n_yaw .. n_yaw from yaw_k = yaw + (double)k * yaw_step, in double with libm's cos /
+ * sin and lrint.  KC_ERR_RANGE when cap < 2 n_yaw + 1. */
+int kc_worldmap_match_rotations(double yaw, int n_yaw, double yaw_step, kc_worldmap_rotation *out, size_t cap);
+/* One match.  The grid arguments, pointer checks and stream ordering are those of the
+ * three kc_worldmap_update_* entries; guess: the quantised pose guess (its tx, ty are
+ * rule 11's TX, TY), rotations: 2 n_yaw + 1 pairs as kc_worldmap_match_rotations gives
+ * them (KC_ERR_INVALID for a pair that is no unit vector in 16 fraction bits).  Every
+ * argument is checked before the device is used.  Four launches (weights over a scratch
+ * plane, points, scores, pick) and the read-back of the record; returns with it final. */
+int kc_worldmap_match_device(kc_worldmap *ctx, const int32_t *dev_grid, int grid_height, int grid_width, int central_i,
+                             int central_j, float resolution, const kc_worldmap_pose *guess,
+                             const kc_worldmap_rotation *rotations, int n_yaw, int reach, kc_worldmap_match_result *out);
+int kc_worldmap_match_host(kc_worldmap *ctx, const int32_t *grid, int grid_height, int grid_width, int central_i,
+                           int central_j, float resolution, const kc_worldmap_pose *guess,
+                           const kc_worldmap_rotation *rotations, int n_yaw, int reach, kc_worldmap_match_result *out);
+int kc_worldmap_match_from_mapper(kc_worldmap *ctx, struct kc_mapper *mapper, const kc_worldmap_pose *guess,
+                                  const kc_worldmap_rotation *rotations, int n_yaw, int reach,
+                                  kc_worldmap_match_result *out);
+/* rule 13's table of the last match, (2K+1) (2S+1)^2 words; KC_ERR_RANGE when they do not
+ * fit cap, KC_ERR_STATE before the first match */
+int kc_worldmap_match_scores(kc_worldmap *ctx, uint32_t *out, size_t cap);
+/* HIP-event times of the last match's four launches in milliseconds (weight, points,
+ * score, pick), for tools; recorded only while enabled.  KC_ERR_STATE when the last
+ * match was not timed. */
+int kc_worldmap_match_set_timing(kc_worldmap *ctx, int enable);
+int kc_worldmap_match_times(kc_worldmap *ctx, float ms_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -321,6 +321,35 @@ py::dict worldMapInterface(const WorldMapDeviceGrid &g) {
   return d;
 }
 
+// WorldMap.match: the record of one match and, through the map it keeps alive, its score table
+struct WorldMapMatch {
+  Mapping::WorldMap::Match m;
+  py::object map;
+  uint64_t number;
+};
+py::array worldMapMatchScores(const WorldMapMatch &r) {
+  const auto &m = r.map.cast<const Mapping::WorldMap &>();
+  if (m.matchCount() != r.number) throw std::runtime_error("the map has made another match since: its table has replaced this one");
+  const py::ssize_t nr = 2 * r.m.n_yaw + 1, side = 2 * r.m.reach + 1;
+  std::vector<uint32_t> v;
+  {
+    py::gil_scoped_release nogil;
+    v = m.matchScores();
+  }
+  py::array_t<uint32_t> a({nr, side, side});
+  if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(uint32_t));
+  return a;
+}
+kc_worldmap_pose worldMapPose(const py::tuple &t) {
+  if (t.size() != 4) throw std::invalid_argument("a quantised pose is (cq, sq, tx, ty)");
+  return kc_worldmap_pose{py::cast<int32_t>(t[0]), py::cast<int32_t>(t[1]), py::cast<int64_t>(t[2]), py::cast<int64_t>(t[3])};
+}
+const py::array_t<int32_t, py::array::f_style> worldMapLocalGrid(const py::array &grid) {
+  if (grid.ndim() != 2 || grid.dtype().num() != py::dtype::of<int32_t>().num())
+    throw std::invalid_argument("the local grid must be a 2-D int32 array (grid_height, grid_width)");
+  return py::array_t<int32_t, py::array::f_style>::ensure(grid);
+}
+
 // WorldMap.set_prior: a (width, height) int32 or int8 grid, grid[I, J] the cell (I, J) -- a numpy array (any memory
 // order), or a device array with __cuda_array_interface__ in column-major strides, read in place (cf. plannerSetGrid)
 void worldMapSetPrior(Mapping::WorldMap &m, const py::object &o) {
@@ -954,6 +983,22 @@ PYBIND11_MODULE(kompass_cpp, m) {
     if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size());
     return a;
   };
+  py::class_<WorldMapMatch>(mp, "WorldMapMatch")
+      .def_property_readonly("k", [](const WorldMapMatch &r) { return r.m.k; })
+      .def_property_readonly("u", [](const WorldMapMatch &r) { return r.m.u; })
+      .def_property_readonly("v", [](const WorldMapMatch &r) { return r.m.v; })
+      .def_property_readonly("score", [](const WorldMapMatch &r) { return r.m.score; })
+      .def_property_readonly("score_guess", [](const WorldMapMatch &r) { return r.m.score_guess; })
+      .def_property_readonly("points", [](const WorldMapMatch &r) { return r.m.points; })
+      .def_property_readonly("x", [](const WorldMapMatch &r) { return r.m.x; })
+      .def_property_readonly("y", [](const WorldMapMatch &r) { return r.m.y; })
+      .def_property_readonly("yaw", [](const WorldMapMatch &r) { return r.m.yaw; })
+      .def_property_readonly("pose", [](const WorldMapMatch &r) {
+             return py::make_tuple(r.m.pose.cq, r.m.pose.sq, r.m.pose.tx, r.m.pose.ty);
+           }, "the corrected pose as the update takes it: (cq, sq, tx, ty), 16 fraction bits")
+      .def("scores", &worldMapMatchScores,
+           "the score table, uint32 [2 n_yaw + 1, 2 reach + 1, 2 reach + 1] indexed [k + n_yaw, v + reach, u + reach]; "
+           "RuntimeError once the map has made another match");
   py::class_<Mapping::WorldMap>(mp, "WorldMap")
       .def(py::init([](int width, int height, float resolution, double origin_x, double origin_y) {
              return std::make_unique<Mapping::WorldMap>(width, height, resolution, origin_x, origin_y);
@@ -978,6 +1023,44 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return m.update(d, gh, gw, x, y, yaw);
            }, py::arg("grid"), py::arg("x"), py::arg("y"), py::arg("yaw"),
            "Fuse a (grid_height, grid_width) int32 grid from the host, the mapper's central cell.  -> changed cells")
+      .def("match", [](py::object self, const Mapping::LocalMapper &mapper, double x, double y, double yaw, int n_yaw,
+                       double yaw_step, int reach) {
+             auto &m = self.cast<Mapping::WorldMap &>();
+             Mapping::WorldMap::Match r;
+             {
+               py::gil_scoped_release nogil;
+               r = m.match(mapper, x, y, yaw, n_yaw, yaw_step, reach);
+             }
+             return WorldMapMatch{r, self, m.matchCount()};
+           }, py::arg("local"), py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("n_yaw"), py::arg("yaw_step"), py::arg("reach"),
+           "Match the mapper's last grid where it lies against the map around the guess (x, y, yaw); the map is not modified")
+      .def("match", [](py::object self, const py::array &grid, double x, double y, double yaw, int n_yaw, double yaw_step,
+                       int reach) {
+             auto &m = self.cast<Mapping::WorldMap &>();
+             const auto g = worldMapLocalGrid(grid);
+             const int32_t *d = g.data();
+             const int gh = static_cast<int>(g.shape(0)), gw = static_cast<int>(g.shape(1));
+             Mapping::WorldMap::Match r;
+             {
+               py::gil_scoped_release nogil;
+               r = m.match(d, gh, gw, x, y, yaw, n_yaw, yaw_step, reach);
+             }
+             return WorldMapMatch{r, self, m.matchCount()};
+           }, py::arg("local"), py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("n_yaw"), py::arg("yaw_step"), py::arg("reach"),
+           "Match a (grid_height, grid_width) int32 grid from the host, the mapper's central cell")
+      .def("update_at", [](Mapping::WorldMap &m, const Mapping::LocalMapper &mapper, const py::tuple &pose) {
+             const kc_worldmap_pose p = worldMapPose(pose);
+             py::gil_scoped_release nogil;
+             return m.updateAt(mapper, p);
+           }, py::arg("mapper"), py::arg("pose"), "update at a quantised pose (cq, sq, tx, ty), a match's `pose`")
+      .def("update_at", [](Mapping::WorldMap &m, const py::array &grid, const py::tuple &pose) {
+             const kc_worldmap_pose p = worldMapPose(pose);
+             const auto g = worldMapLocalGrid(grid);
+             const int32_t *d = g.data();
+             const int gh = static_cast<int>(g.shape(0)), gw = static_cast<int>(g.shape(1));
+             py::gil_scoped_release nogil;
+             return m.updateAt(d, gh, gw, p);
+           }, py::arg("grid"), py::arg("pose"), "update at a quantised pose (cq, sq, tx, ty), a match's `pose`")
       .def("clear", &Mapping::WorldMap::clear)
       .def("get_cls", [plane](const Mapping::WorldMap &m) { return plane(m.cls(), m.width(), m.height()); },
            "the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied")

@@ -42,6 +42,29 @@ class WorldMap {
   uint32_t updateOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw);
   void clear();
 
+  // Correlative match (DESIGN.md 4.11 rules 9 to 15): the pose within n_yaw steps of yaw_step each side of the guess's
+  // yaw and `reach` cells each side of its position that puts the grid's occupied cells onto the map best.  The map is
+  // not modified.  Same three sources as update.
+  struct Match {
+    int k = 0, u = 0, v = 0;                         // the winner: yaw step, cells along x and y
+    uint32_t score = 0, score_guess = 0, points = 0;  // the winner's score, the guess's, the occupied local cells
+    double x = 0.0, y = 0.0, yaw = 0.0;              // the corrected pose: yaw + k * yaw_step, x + u * resolution, y + v * resolution
+    kc_worldmap_pose pose = {0, 0, 0, 0};            // ... as the update kernel takes it
+    int n_yaw = 0, reach = 0;                        // the window
+  };
+  Match match(const LocalMapper &mapper, double x, double y, double yaw, int n_yaw, double yaw_step, int reach);
+  Match match(const int32_t *grid, int grid_height, int grid_width, double x, double y, double yaw, int n_yaw, double yaw_step,
+              int reach);
+  Match matchOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw, int n_yaw,
+                      double yaw_step, int reach);
+  // rule 13's table of the last match: (2 n_yaw + 1) x (2 reach + 1) x (2 reach + 1), [k][v][u]
+  std::vector<uint32_t> matchScores() const;
+  // matches made so far: a Match whose number this is owns the table
+  uint64_t matchCount() const { return match_count_; }
+  // One update at a quantised pose (a Match's), from the same three sources
+  uint32_t updateAt(const LocalMapper &mapper, const kc_worldmap_pose &pose);
+  uint32_t updateAt(const int32_t *grid, int grid_height, int grid_width, const kc_worldmap_pose &pose);
+
   // copies of the planes, width x height as the map
   std::vector<int8_t> cls() const;
   std::vector<int8_t> evidence() const;
@@ -66,6 +89,15 @@ class WorldMap {
   double ox_, oy_;
   hip::WorldMapHandle ctx_;
   kc_worldmap_result last_ = {0, -1, -1, -1, -1};
+  uint64_t match_count_ = 0;
+  int match_rot_ = 0, match_side_ = 0;  // the last match's table: rotations, candidates a side
+
+  struct Window {
+    kc_worldmap_pose guess;
+    std::vector<kc_worldmap_rotation> rot;
+  };
+  Window window(double x, double y, double yaw, int n_yaw, double yaw_step, int reach) const;
+  Match finish(const kc_worldmap_match_result &r, double x, double y, double yaw, int n_yaw, double yaw_step, int reach);
 };
 
 }  // namespace Mapping

@@ -51,6 +51,79 @@ uint32_t WorldMap::updateOnDevice(const int32_t *dev_grid, int grid_height, int 
   return last_.changed;
 }
 
+WorldMap::Window WorldMap::window(double x, double y, double yaw, int n_yaw, double yaw_step, int reach) const {
+  hip::check(kc_worldmap_match_check_window(n_yaw, yaw_step, reach));
+  Window w;
+  w.guess = quantisePose(res_, ox_, oy_, x, y, yaw);
+  w.rot.resize(static_cast<size_t>(2 * n_yaw + 1));
+  hip::check(kc_worldmap_match_rotations(yaw, n_yaw, yaw_step, w.rot.data(), w.rot.size()));
+  return w;
+}
+
+WorldMap::Match WorldMap::finish(const kc_worldmap_match_result &r, double x, double y, double yaw, int n_yaw, double yaw_step,
+                                 int reach) {
+  ++match_count_;
+  match_rot_ = 2 * n_yaw + 1;
+  match_side_ = 2 * reach + 1;
+  Match m;
+  m.k = r.k;
+  m.u = r.u;
+  m.v = r.v;
+  m.score = r.score;
+  m.score_guess = r.score_guess;
+  m.points = r.n_points;
+  const double R = static_cast<double>(res_);
+  m.yaw = yaw + static_cast<double>(r.k) * yaw_step;
+  m.x = x + r.u * R;
+  m.y = y + r.v * R;
+  m.pose = r.pose;
+  m.n_yaw = n_yaw;
+  m.reach = reach;
+  return m;
+}
+
+WorldMap::Match WorldMap::match(const LocalMapper &mapper, double x, double y, double yaw, int n_yaw, double yaw_step, int reach) {
+  const Window w = window(x, y, yaw, n_yaw, yaw_step, reach);
+  kc_worldmap_match_result r{};
+  hip::check(kc_worldmap_match_from_mapper(ctx_.get(), mapper.hipContext(), &w.guess, w.rot.data(), n_yaw, reach, &r));
+  return finish(r, x, y, yaw, n_yaw, yaw_step, reach);
+}
+
+WorldMap::Match WorldMap::match(const int32_t *grid, int grid_height, int grid_width, double x, double y, double yaw, int n_yaw,
+                                double yaw_step, int reach) {
+  const Window w = window(x, y, yaw, n_yaw, yaw_step, reach);
+  kc_worldmap_match_result r{};
+  hip::check(kc_worldmap_match_host(ctx_.get(), grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_,
+                                    &w.guess, w.rot.data(), n_yaw, reach, &r));
+  return finish(r, x, y, yaw, n_yaw, yaw_step, reach);
+}
+
+WorldMap::Match WorldMap::matchOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw,
+                                        int n_yaw, double yaw_step, int reach) {
+  const Window w = window(x, y, yaw, n_yaw, yaw_step, reach);
+  kc_worldmap_match_result r{};
+  hip::check(kc_worldmap_match_device(ctx_.get(), dev_grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_,
+                                      &w.guess, w.rot.data(), n_yaw, reach, &r));
+  return finish(r, x, y, yaw, n_yaw, yaw_step, reach);
+}
+
+std::vector<uint32_t> WorldMap::matchScores() const {
+  std::vector<uint32_t> out(static_cast<size_t>(match_rot_) * static_cast<size_t>(match_side_) * static_cast<size_t>(match_side_));
+  hip::check(kc_worldmap_match_scores(ctx_.get(), out.data(), out.size()));
+  return out;
+}
+
+uint32_t WorldMap::updateAt(const LocalMapper &mapper, const kc_worldmap_pose &pose) {
+  hip::check(kc_worldmap_update_from_mapper(ctx_.get(), mapper.hipContext(), &pose, &last_));
+  return last_.changed;
+}
+
+uint32_t WorldMap::updateAt(const int32_t *grid, int grid_height, int grid_width, const kc_worldmap_pose &pose) {
+  hip::check(kc_worldmap_update_host(ctx_.get(), grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_, &pose,
+                                     &last_));
+  return last_.changed;
+}
+
 void WorldMap::clear() {
   hip::check(kc_worldmap_clear(ctx_.get()));
   last_ = {0, -1, -1, -1, -1};

@@ -22,6 +22,17 @@
 //  (d) prior / clear.  worldmap_prior_kernel owns dwords by flat index (the planes start at an allocation, so cells
 //      4 t .. 4 t + 3 are one aligned dword, whatever W is); the cells behind the last whole dword go as bytes.
 //
+//  (e) match (rules 9 to 15).  Four launches on the context's stream and one read-back, the map untouched:
+//      worldmap_weight_kernel turns the nine cls bytes around every cell of a square scratch plane into one weight
+//      byte (rule 12), zeroes the score table and the point counter; worldmap_points_kernel compacts the occupied
+//      local cells into packed (a, b) pairs; worldmap_score_kernel is one workgroup per (rotation, share of the point
+//      chunks) that keeps its candidates' sums in registers and adds them into the table with one uint32 atomic per
+//      candidate; worldmap_pick_kernel folds the table under rule 14 into the record.
+//      The plane is centred on (TX >> 16, TY >> 16) and is NOT clipped to the map: cells outside hold 0, so the
+//      score loop has no bounds test.  Its half side only has to be large enough (wm_match_half has the argument);
+//      every weight is computed from the cls plane with the map's own bounds, so the box never decides one.
+//      uint32 adds commute: the table does not depend on the order the workgroups arrive in.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -149,6 +160,160 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_prior_kernel(const T *grid,
   }
 }
 
+// ---- match (rules 9 to 15) ---------------------------------------------------------------------------------------
+constexpr int kWmMatchMaxYaw = KC_WORLDMAP_MATCH_MAX_YAW, kWmMatchMaxReach = KC_WORLDMAP_MATCH_MAX_REACH;
+constexpr int kWmMatchMaxSide = KC_WORLDMAP_MATCH_MAX_SIDE;
+constexpr int kWmMatchRot = 2 * kWmMatchMaxYaw + 1;
+constexpr int kWmChunk = 256;        // points formed into LDS at a time: one a lane
+constexpr int kWmCandPerLane = 16;   // ceil(63 * 63 / 256)
+constexpr int kWmChunkBlocks = 32;   // workgroups that share one rotation's chunks
+constexpr int kWmPickBlock = 1024;
+constexpr int kWmMatchRecWords = 6;  // k, u, v, score, score_guess, n_points
+
+struct WmWeightArgs {
+  const int8_t *cls;
+  uint8_t *plane;
+  uint32_t *table;
+  uint32_t *n_points;
+  long long plane_cells, table_cells;
+  int W, H;
+  int i0, j0;  // the world cell of plane cell (0, 0)
+  int P;       // the plane's side
+};
+
+__device__ __forceinline__ bool wm_occ(const int8_t *cls, int W, int H, int I, int J) {
+  return I >= 0 && I < W && J >= 0 && J < H && cls[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(W)] == KC_OCCUPIED;
+}
+
+// rule 12, one lane a plane cell; the same lanes zero the table of the match that follows
+__global__ __launch_bounds__(kWmBlock) void worldmap_weight_kernel(WmWeightArgs a) {
+  const long long stride = static_cast<long long>(gridDim.x) * kWmBlock;
+  const long long t0 = static_cast<long long>(blockIdx.x) * kWmBlock + threadIdx.x;
+  if (t0 == 0) *a.n_points = 0;
+  for (long long t = t0; t < a.table_cells; t += stride) a.table[t] = 0;
+  for (long long t = t0; t < a.plane_cells; t += stride) {
+    const int I = a.i0 + static_cast<int>(t % a.P), J = a.j0 + static_cast<int>(t / a.P);
+    int w = 0;
+    if (I >= 0 && I < a.W && J >= 0 && J < a.H) {  // a cell outside the map has weight 0
+      if (wm_occ(a.cls, a.W, a.H, I, J)) w = 3;
+      else if (wm_occ(a.cls, a.W, a.H, I - 1, J) || wm_occ(a.cls, a.W, a.H, I + 1, J) || wm_occ(a.cls, a.W, a.H, I, J - 1) ||
+               wm_occ(a.cls, a.W, a.H, I, J + 1))
+        w = 2;
+      else if (wm_occ(a.cls, a.W, a.H, I - 1, J - 1) || wm_occ(a.cls, a.W, a.H, I + 1, J - 1) ||
+               wm_occ(a.cls, a.W, a.H, I - 1, J + 1) || wm_occ(a.cls, a.W, a.H, I + 1, J + 1))
+        w = 1;
+    }
+    a.plane[t] = static_cast<uint8_t>(w);
+  }
+}
+
+// rule 9: the occupied local cells as (a & 0xFFFF) | (b << 16), in any order.  A wavefront reserves its slots with one
+// atomic; points[] holds gh * gw words, so no count can overrun it.
+__global__ __launch_bounds__(kWmBlock) void worldmap_points_kernel(const int32_t *local, long long cells, int gh, int c0, int c1,
+                                                                   uint32_t *points, uint32_t *n_points) {
+  const long long stride = static_cast<long long>(gridDim.x) * kWmBlock;
+  const long long rounds = (cells + stride - 1) / stride;  // every lane of a wavefront makes every round: the ballot is whole
+  long long t = static_cast<long long>(blockIdx.x) * kWmBlock + threadIdx.x;
+  const int lane = static_cast<int>(threadIdx.x) & 63;
+  for (long long r = 0; r < rounds; ++r, t += stride) {
+    const bool occ = t < cells && local[t] == KC_OCCUPIED;
+    const unsigned long long mask = __ballot(occ);
+    if (mask == 0) continue;
+    const int leader = __ffsll(mask) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(n_points, static_cast<uint32_t>(__popcll(mask)));
+    base = __shfl(base, leader);
+    if (occ) {
+      const int pa = static_cast<int>(t % gh) - c0, pb = static_cast<int>(t / gh) - c1;
+      points[base + __popcll(mask & ((1ull << lane) - 1ull))] =
+          (static_cast<uint32_t>(pa) & 0xFFFFu) | (static_cast<uint32_t>(pb) << 16);
+    }
+  }
+}
+
+struct WmScoreArgs {
+  const uint8_t *plane;
+  const uint32_t *points, *n_points;
+  uint32_t *table;
+  long long tx, ty;
+  int i0, j0, P;  // the plane: world cell of its cell (0, 0), side
+  int S, T, ncand;
+  kc_worldmap_rotation rot[kWmMatchRot];
+};
+
+// rules 11 and 13.  blockIdx.y: the rotation; blockIdx.x: which of the chunks of kWmChunk points.  Candidate q = (v + S)
+// T + (u + S) belongs to lane q % 256, so consecutive lanes read consecutive bytes of a patch row.  M: candidates a lane.
+template <int M>
+__global__ __launch_bounds__(kWmBlock) void worldmap_score_kernel(WmScoreArgs a) {
+  __shared__ int s_base[kWmChunk];
+  const int lane = static_cast<int>(threadIdx.x);
+  const long long n = *a.n_points;
+  const long long cq = a.rot[blockIdx.y].cq, sq = a.rot[blockIdx.y].sq;
+  int off[M];
+  uint32_t acc[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int q = lane + m * kWmBlock;
+    off[m] = q < a.ncand ? (q % a.T) + (q / a.T) * a.P : 0;  // a lane's spare slots read the patch's corner and are dropped
+    acc[m] = 0;
+  }
+  for (long long first = static_cast<long long>(blockIdx.x) * kWmChunk; first < n; first += static_cast<long long>(gridDim.x) * kWmChunk) {
+    const int count = static_cast<int>(min(static_cast<long long>(kWmChunk), n - first));
+    if (lane < count) {
+      const uint32_t w = a.points[first + lane];
+      const long long pa = static_cast<int16_t>(w & 0xFFFFu), pb = static_cast<int16_t>(w >> 16);
+      const long long X = a.tx + cq * pa - sq * pb, Y = a.ty + sq * pa + cq * pb;
+      const int I0 = static_cast<int>((X + (1ll << 15)) >> 16), J0 = static_cast<int>((Y + (1ll << 15)) >> 16);
+      s_base[lane] = (I0 - a.S - a.i0) + (J0 - a.S - a.j0) * a.P;  // the patch's corner (u, v) = (-S, -S) in the plane
+    }
+    __syncthreads();
+    for (int p = 0; p < count; ++p) {
+      const uint8_t *row = a.plane + s_base[p];
+#pragma unroll
+      for (int m = 0; m < M; ++m) acc[m] += row[off[m]];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int q = lane + m * kWmBlock;
+    if (q < a.ncand && acc[m] != 0) atomicAdd(&a.table[static_cast<size_t>(blockIdx.y) * a.ncand + q], acc[m]);
+  }
+}
+
+// rule 14 as one 64-bit max: score above 29 bits of (2^29 - 1 - tie), tie = (u u + v v, rank of k, v + S, u + S) in
+// 11 + 6 + 6 + 6 bits, rank 0, 1, 2, 3, 4 .. for k = 0, -1, 1, -2, 2 .. (that is the order (|k|, k)).
+__global__ __launch_bounds__(kWmPickBlock) void worldmap_pick_kernel(const uint32_t *table, const uint32_t *n_points, int K, int S,
+                                                                      int *rec) {
+  __shared__ unsigned long long s_key[kWmPickBlock];
+  const int T = 2 * S + 1, ncand = T * T, total = (2 * K + 1) * ncand;
+  unsigned long long best = 0;
+  for (int e = static_cast<int>(threadIdx.x); e < total; e += kWmPickBlock) {
+    const int k = e / ncand - K, q = e % ncand, v = q / T - S, u = q % T - S;
+    const unsigned rank = k < 0 ? static_cast<unsigned>(-2 * k - 1) : static_cast<unsigned>(2 * k);
+    const unsigned tie = (((static_cast<unsigned>(u * u + v * v) << 6 | rank) << 6 | static_cast<unsigned>(v + S)) << 6) |
+                         static_cast<unsigned>(u + S);
+    const unsigned long long key = (static_cast<unsigned long long>(table[e]) << 29) | (0x1FFFFFFFu - tie);
+    best = key > best ? key : best;
+  }
+  s_key[threadIdx.x] = best;
+  __syncthreads();
+  for (int h = kWmPickBlock / 2; h > 0; h >>= 1) {
+    if (static_cast<int>(threadIdx.x) < h && s_key[threadIdx.x + h] > s_key[threadIdx.x]) s_key[threadIdx.x] = s_key[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const unsigned tie = 0x1FFFFFFFu - static_cast<unsigned>(s_key[0] & 0x1FFFFFFFull);
+    const unsigned rank = (tie >> 12) & 63u;
+    rec[0] = rank & 1u ? -static_cast<int>((rank + 1) / 2) : static_cast<int>(rank / 2);
+    rec[1] = static_cast<int>(tie & 63u) - S;
+    rec[2] = static_cast<int>((tie >> 6) & 63u) - S;
+    rec[3] = static_cast<int>(static_cast<uint32_t>(s_key[0] >> 29));
+    rec[4] = static_cast<int>(table[static_cast<size_t>(K) * ncand + S * T + S]);
+    rec[5] = static_cast<int>(*n_points);
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -167,6 +332,14 @@ struct kc_worldmap {
   PinBuf<int> h_rec;
   unsigned long long seq = 0;  // updates launched: record seq & 1 is the next one's
   bool rec_ready = false;      // both records hold their start values
+  // match: scratch grown on demand and kept
+  DevBuf<uint8_t> d_weight;    // rule 12 over the scratch plane
+  DevBuf<uint32_t> d_points;   // packed (a, b), at most one a local cell
+  DevBuf<uint32_t> d_scores;   // the table, behind it the point counter
+  DevBuf<int> d_mrec;
+  PinBuf<int> h_mrec;
+  int match_K = -1, match_S = -1;  // the window of the table d_scores holds; -1: none
+  Timing match_time;               // weight, points, score, pick
 };
 
 namespace {
@@ -324,6 +497,148 @@ int wm_update(kc_worldmap *c, const int32_t *dev, int gh, int gw, int c0, int c1
     out->j_max = r[4];
   }
   return KC_OK;
+}
+
+int wm_check_window(int n_yaw, double yaw_step, int reach) {
+  if (n_yaw < 0 || n_yaw > kWmMatchMaxYaw) KC_FAIL(KC_ERR_INVALID, "n_yaw must be in 0 .. %d, got %d", kWmMatchMaxYaw, n_yaw);
+  if (reach < 0 || reach > kWmMatchMaxReach) KC_FAIL(KC_ERR_INVALID, "reach must be in 0 .. %d, got %d", kWmMatchMaxReach, reach);
+  if (!std::isfinite(yaw_step) || !(yaw_step >= 0.0)) KC_FAIL(KC_ERR_INVALID, "yaw_step must be finite and >= 0, got %g", yaw_step);
+  return KC_OK;
+}
+
+// rule 9's checks: an update's, the cap on the sides, and every cell within that cap of the central cell (a point's
+// (a, b) then fits 16 bits each, and the scratch plane is bounded)
+int wm_check_match_grid(float world_res, int gh, int gw, int c0, int c1, float res) {
+  KC_TRY(wm_check_grid(world_res, gh, gw, c0, c1, res));
+  if (gh > kWmMatchMaxSide || gw > kWmMatchMaxSide)
+    KC_FAIL(KC_ERR_RANGE, "a %d x %d local grid is above the match's cap of %d cells a side", gh, gw, kWmMatchMaxSide);
+  if (c0 < -kWmMatchMaxSide || c0 - (gh - 1) > kWmMatchMaxSide || c1 < -kWmMatchMaxSide || c1 - (gw - 1) > kWmMatchMaxSide ||
+      c0 > kWmMatchMaxSide || (gh - 1) - c0 > kWmMatchMaxSide || c1 > kWmMatchMaxSide || (gw - 1) - c1 > kWmMatchMaxSide)
+    KC_FAIL(KC_ERR_RANGE, "central cell (%d, %d) is more than %d cells from a cell of the %d x %d local grid", c0, c1,
+            kWmMatchMaxSide, gh, gw);
+  return KC_OK;
+}
+
+int wm_check_match_args(const kc_worldmap_pose *guess, const kc_worldmap_rotation *rot, int K, int S) {
+  KC_TRY(wm_check_window(K, 0.0, S));
+  KC_TRY(wm_check_pose(guess));
+  if (!rot) KC_FAIL(KC_ERR_INVALID, "null rotation table");
+  // (the scratch plane's size rests on this: wm_match_half)
+  for (int r = 0; r <= 2 * K; ++r) {
+    const long long cq = rot[r].cq, sq = rot[r].sq;
+    if (cq < -65536 || cq > 65536 || sq < -65536 || sq > 65536 || cq * cq + sq * sq > 65537ll * 65537ll)
+      KC_FAIL(KC_ERR_INVALID, "rotation %d (cq, sq) = (%d, %d) is no unit vector in 16 fraction bits", r - K, rot[r].cq, rot[r].sq);
+  }
+  return KC_OK;
+}
+
+// The plane's half side.  A point (a, b) lands, before translation, at I0 = floor((TX + d + 2^15) / 2^16) with
+// |d| = |Cq a - Sq b| <= sqrt(Cq^2 + Sq^2) hypot(a, b) <= 2^16 (1 + 2^-15) r (wm_check_match_args holds the table to that), r the hypot of the farthest cell; with
+// TX = 2^16 cx + f, 0 <= f < 2^16, that is cx + floor((f + d) / 2^16 + 1/2), within ceil(r (1 + 2^-15)) + 1 of cx.
+// r <= 8192 sqrt 2 makes r 2^-15 < 1, the translation adds S: ceil(r) + S + 3 holds every landing cell, J alike.
+int wm_match_half(int gh, int gw, int c0, int c1, int S) {
+  const double a = std::max(std::abs(c0), std::abs(gh - 1 - c0)), b = std::max(std::abs(c1), std::abs(gw - 1 - c1));
+  return static_cast<int>(std::ceil(std::hypot(a, b))) + S + 3;
+}
+
+template <int M>
+void wm_launch_score(kc_worldmap *c, const WmScoreArgs &a, dim3 grid) {
+  hipLaunchKernelGGL(worldmap_score_kernel<M>, grid, dim3(kWmBlock), 0, c->stream, a);
+}
+
+// dev: the local grid on the context's device, complete in the order of the context's stream
+int wm_match(kc_worldmap *c, const int32_t *dev, int gh, int gw, int c0, int c1, const kc_worldmap_pose *g,
+             const kc_worldmap_rotation *rot, int K, int S, kc_worldmap_match_result *out) {
+  const int T = 2 * S + 1, ncand = T * T, nrot = 2 * K + 1;
+  const size_t table_cells = static_cast<size_t>(nrot) * ncand, cells = static_cast<size_t>(gh) * static_cast<size_t>(gw);
+  const int half = wm_match_half(gh, gw, c0, c1, S), P = 2 * half + 1;
+  const size_t plane_cells = static_cast<size_t>(P) * static_cast<size_t>(P);
+  c->match_K = c->match_S = -1;
+  KC_TRY(c->d_weight.reserve(plane_cells));
+  KC_TRY(c->d_points.reserve(cells));
+  KC_TRY(c->d_scores.reserve(static_cast<size_t>(kWmMatchRot) * kWmMatchRot * kWmMatchRot + 1));
+  KC_TRY(c->d_mrec.reserve(kWmMatchRecWords));
+  KC_TRY(c->h_mrec.reserve(kWmMatchRecWords));
+  uint32_t *n_points = c->d_scores.p + table_cells;
+
+  WmWeightArgs w{};
+  w.cls = c->d_cls.p;
+  w.plane = c->d_weight.p;
+  w.table = c->d_scores.p;
+  w.n_points = n_points;
+  w.plane_cells = static_cast<long long>(plane_cells);
+  w.table_cells = static_cast<long long>(table_cells);
+  w.W = c->W;
+  w.H = c->H;
+  w.i0 = static_cast<int>(g->tx >> 16) - half;
+  w.j0 = static_cast<int>(g->ty >> 16) - half;
+  w.P = P;
+  c->match_time.begin_cycle();
+  KC_TRY(c->match_time.start("weight", c->stream));
+  hipLaunchKernelGGL(worldmap_weight_kernel, dim3(wm_blocks_for(static_cast<long long>(std::max(plane_cells, table_cells)))),
+                     dim3(kWmBlock), 0, c->stream, w);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->match_time.stop(c->stream));
+
+  KC_TRY(c->match_time.start("points", c->stream));
+  hipLaunchKernelGGL(worldmap_points_kernel, dim3(wm_blocks_for(static_cast<long long>(cells))), dim3(kWmBlock), 0, c->stream, dev,
+                     static_cast<long long>(cells), gh, c0, c1, c->d_points.p, n_points);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->match_time.stop(c->stream));
+
+  WmScoreArgs s{};
+  s.plane = c->d_weight.p;
+  s.points = c->d_points.p;
+  s.n_points = n_points;
+  s.table = c->d_scores.p;
+  s.tx = g->tx;
+  s.ty = g->ty;
+  s.i0 = w.i0;
+  s.j0 = w.j0;
+  s.P = P;
+  s.S = S;
+  s.T = T;
+  s.ncand = ncand;
+  std::memcpy(s.rot, rot, sizeof(kc_worldmap_rotation) * static_cast<size_t>(nrot));
+  const unsigned chunks = static_cast<unsigned>(std::min<size_t>((cells + kWmChunk - 1) / kWmChunk, kWmChunkBlocks));
+  const dim3 sgrid(chunks, static_cast<unsigned>(nrot));
+  const int per_lane = (ncand + kWmBlock - 1) / kWmBlock;
+  KC_TRY(c->match_time.start("score", c->stream));
+  if (per_lane <= 1) wm_launch_score<1>(c, s, sgrid);
+  else if (per_lane <= 2) wm_launch_score<2>(c, s, sgrid);
+  else if (per_lane <= 4) wm_launch_score<4>(c, s, sgrid);
+  else if (per_lane <= 8) wm_launch_score<8>(c, s, sgrid);
+  else wm_launch_score<kWmCandPerLane>(c, s, sgrid);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->match_time.stop(c->stream));
+
+  KC_TRY(c->match_time.start("pick", c->stream));
+  hipLaunchKernelGGL(worldmap_pick_kernel, dim3(1), dim3(kWmPickBlock), 0, c->stream, c->d_scores.p, n_points, K, S, c->d_mrec.p);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->match_time.stop(c->stream));
+  KC_HIP(hipMemcpyAsync(c->h_mrec.p, c->d_mrec.p, kWmMatchRecWords * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->match_K = K;
+  c->match_S = S;
+  const int *r = c->h_mrec.p;
+  out->k = r[0];
+  out->u = r[1];
+  out->v = r[2];
+  out->score = static_cast<uint32_t>(r[3]);
+  out->score_guess = static_cast<uint32_t>(r[4]);
+  out->n_points = static_cast<uint32_t>(r[5]);
+  if (out->k < -K || out->k > K || out->u < -S || out->u > S || out->v < -S || out->v > S)
+    KC_FAIL(KC_ERR_HIP, "the match's record (%d, %d, %d) lies outside its window", out->k, out->u, out->v);
+  out->pose.cq = rot[out->k + K].cq;
+  out->pose.sq = rot[out->k + K].sq;
+  out->pose.tx = g->tx + static_cast<int64_t>(out->u) * 65536;
+  out->pose.ty = g->ty + static_cast<int64_t>(out->v) * 65536;
+  return KC_OK;
+}
+
+void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *out) {
+  *out = kc_worldmap_match_result{};
+  if (g) out->pose = *g;
 }
 
 }  // namespace
@@ -498,6 +813,97 @@ int kc_worldmap_get(kc_worldmap *c, int8_t *cls_out, int8_t *evidence_out, size_
   if (evidence_out) KC_HIP(hipMemcpyAsync(evidence_out, c->d_evidence.p, n, hipMemcpyDeviceToHost, c->stream));
   KC_HIP(hipStreamSynchronize(c->stream));
   return KC_OK;
+}
+
+int kc_worldmap_match_check_window(int n_yaw, double yaw_step, int reach) { return wm_check_window(n_yaw, yaw_step, reach); }
+
+int kc_worldmap_match_check_grid(float world_resolution, int grid_height, int grid_width, int central_i, int central_j,
+                                 float resolution) {
+  return wm_check_match_grid(world_resolution, grid_height, grid_width, central_i, central_j, resolution);
+}
+
+int kc_worldmap_match_rotations(double yaw, int n_yaw, double yaw_step, kc_worldmap_rotation *out, size_t cap) {
+  KC_TRY(wm_check_window(n_yaw, yaw_step, 0));
+  if (!out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!std::isfinite(yaw)) KC_FAIL(KC_ERR_INVALID, "the yaw must be finite");
+  if (cap < static_cast<size_t>(2 * n_yaw + 1)) KC_FAIL(KC_ERR_RANGE, "%d rotations do not fit the output capacity %zu", 2 * n_yaw + 1, cap);
+  for (int k = -n_yaw; k <= n_yaw; ++k) {
+    const double yk = yaw + static_cast<double>(k) * yaw_step;
+    out[k + n_yaw].cq = static_cast<int32_t>(std::lrint(std::cos(yk) * 65536.0));
+    out[k + n_yaw].sq = static_cast<int32_t>(std::lrint(std::sin(yk) * 65536.0));
+  }
+  return KC_OK;
+}
+
+int kc_worldmap_match_device(kc_worldmap *c, const int32_t *dev_grid, int grid_height, int grid_width, int central_i,
+                             int central_j, float resolution, const kc_worldmap_pose *guess, const kc_worldmap_rotation *rotations,
+                             int n_yaw, int reach, kc_worldmap_match_result *out) {
+  if (!c || !dev_grid || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  wm_clear_match_result(guess, out);
+  KC_TRY(wm_check_match_args(guess, rotations, n_yaw, reach));
+  KC_TRY(wm_check_match_grid(c->res, grid_height, grid_width, central_i, central_j, resolution));
+  KC_HIP(hipSetDevice(c->device));
+  const long long nbytes = static_cast<long long>(grid_height) * grid_width * static_cast<long long>(sizeof(int32_t));
+  KC_TRY(check_device_range(c->device, dev_grid, 0, nbytes, sizeof(int32_t), "grid"));
+  return wm_match(c, dev_grid, grid_height, grid_width, central_i, central_j, guess, rotations, n_yaw, reach, out);
+}
+
+int kc_worldmap_match_host(kc_worldmap *c, const int32_t *grid, int grid_height, int grid_width, int central_i, int central_j,
+                           float resolution, const kc_worldmap_pose *guess, const kc_worldmap_rotation *rotations, int n_yaw,
+                           int reach, kc_worldmap_match_result *out) {
+  if (!c || !grid || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  wm_clear_match_result(guess, out);
+  KC_TRY(wm_check_match_args(guess, rotations, n_yaw, reach));
+  KC_TRY(wm_check_match_grid(c->res, grid_height, grid_width, central_i, central_j, resolution));
+  KC_HIP(hipSetDevice(c->device));
+  const size_t cells = static_cast<size_t>(grid_height) * static_cast<size_t>(grid_width);
+  KC_TRY(c->d_stage.reserve(cells));
+  KC_HIP(hipMemcpyAsync(c->d_stage.p, grid, cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  return wm_match(c, c->d_stage.p, grid_height, grid_width, central_i, central_j, guess, rotations, n_yaw, reach, out);
+}
+
+int kc_worldmap_match_from_mapper(kc_worldmap *c, kc_mapper *mapper, const kc_worldmap_pose *guess,
+                                  const kc_worldmap_rotation *rotations, int n_yaw, int reach, kc_worldmap_match_result *out) {
+  if (!c || !mapper || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  wm_clear_match_result(guess, out);
+  KC_TRY(wm_check_match_args(guess, rotations, n_yaw, reach));
+  MapperView v{};
+  KC_TRY(mapper_view(mapper, &v));
+  if (v.device != c->device) KC_FAIL(KC_ERR_INVALID, "mapper on device %d, world map on device %d", v.device, c->device);
+  KC_TRY(wm_check_match_grid(c->res, v.H, v.W, v.c0, v.c1, v.res));
+  KC_HIP(hipSetDevice(c->device));
+  // the map's stream waits for the scan; the host does not
+  if (!c->grid_ready) KC_HIP(hipEventCreateWithFlags(&c->grid_ready, hipEventDisableTiming));
+  KC_HIP(hipEventRecord(c->grid_ready, v.stream));
+  KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
+  return wm_match(c, v.grid, v.H, v.W, v.c0, v.c1, guess, rotations, n_yaw, reach, out);
+}
+
+int kc_worldmap_match_scores(kc_worldmap *c, uint32_t *out, size_t cap) {
+  if (!c || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (c->match_K < 0) KC_FAIL(KC_ERR_STATE, "no match has been made on this map");
+  const int T = 2 * c->match_S + 1;
+  const size_t n = static_cast<size_t>(2 * c->match_K + 1) * T * T;
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu scores do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipSetDevice(c->device));
+  KC_HIP(hipMemcpyAsync(out, c->d_scores.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_worldmap_match_set_timing(kc_worldmap *c, int enable) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  c->match_time.enabled = enable != 0;
+  c->match_time.begin_cycle();
+  return KC_OK;
+}
+
+int kc_worldmap_match_times(kc_worldmap *c, float ms_out[4]) {
+  if (!c || !ms_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->match_time.enabled || c->match_time.used != 4) KC_FAIL(KC_ERR_STATE, "no match has been timed on this map");
+  KC_HIP(hipSetDevice(c->device));
+  size_t n = 0;
+  return c->match_time.get(nullptr, ms_out, 4, &n);
 }
 
 }  // extern "C"

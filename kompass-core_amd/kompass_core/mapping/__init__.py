@@ -1,2 +1,2 @@
 from .local_mapper import LocalMapper, MapConfig, ScanModelConfig  # noqa: F401
-from .world_map import WorldMap  # noqa: F401
+from .world_map import WorldMap, WorldMapMatch  # noqa: F401

@@ -7,11 +7,42 @@ map between the two: seeded from a prior (the PCD grid), updated from each local
 handed to the planner in place (`setup_problem(None, ..., grid=world_map)`, `replan(map=world_map)`)."""
 from __future__ import annotations
 
-from typing import Dict, Tuple
+import math
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
 import kompass_cpp
+
+
+class WorldMapMatch:
+    """What `WorldMap.match` found (DESIGN.md 4.11 rules 9 to 15): the winner (k, u, v) of the window in yaw steps and
+    cells, its `score`, the guess's `score_guess`, the `points` (occupied local cells) that were matched, the
+    corrected pose `x, y, yaw`, and `ratio = score / (3 * points)`: 1.0 when every point sits on an occupied cell
+    of the map, 0.0 without points.  `scores()` is the whole table, uint32 [2 n_yaw + 1, 2 reach + 1, 2 reach + 1]
+    indexed [k + n_yaw, v + reach, u + reach], for whoever wants a covariance; it is the map's last table, so it
+    raises once the map has made another match.  `applied`: set by `update(match=True)`, whether the update fused
+    at the corrected pose."""
+
+    def __init__(self, record):
+        self._record = record
+        self.applied: Optional[bool] = None
+
+    def __getattr__(self, name):
+        if name in ("k", "u", "v", "score", "score_guess", "points", "x", "y", "yaw", "pose"):
+            return getattr(self._record, name)
+        raise AttributeError(name)
+
+    @property
+    def ratio(self) -> float:
+        return self.score / (3.0 * self.points) if self.points else 0.0
+
+    def scores(self) -> np.ndarray:
+        return self._record.scores()
+
+    def __repr__(self):
+        return (f"WorldMapMatch(k={self.k}, u={self.u}, v={self.v}, score={self.score}, score_guess={self.score_guess}, "
+                f"points={self.points}, ratio={self.ratio:.3f}, applied={self.applied})")
 
 
 class WorldMap:
@@ -25,6 +56,7 @@ class WorldMap:
                                                  origin_x=float(origin[0]), origin_y=float(origin[1]))
         if (hit, miss, e_min, e_max, occ_thr) != (3, 1, -8, 14, 1):
             self._map.set_model(hit=int(hit), miss=int(miss), e_min=int(e_min), e_max=int(e_max), occ_thr=int(occ_thr))
+        self.last_match: Optional[WorldMapMatch] = None  # of the last update(match=True)
 
     def set_model(self, hit: int = 3, miss: int = 1, e_min: int = -8, e_max: int = 14, occ_thr: int = 1) -> None:
         """Another update model; clears the map (evidence counted by one model means nothing under another)."""
@@ -36,11 +68,8 @@ class WorldMap:
         anything else never observed.  Replaces the whole state."""
         self._map.set_prior(grid)
 
-    def update(self, robot_state, local_map) -> int:
-        """Fuse one local grid; robot_state (x, y, yaw): the robot's pose in the world.  local_map: the front end's
-        `LocalMapper` or a `kompass_cpp.mapping.LocalMapper` (its last grid where it lies on the device, no host
-        round trip), or an int32 (grid_height, grid_width) array as `LocalMapper.occupancy`.  -> cells whose class
-        changed."""
+    @staticmethod
+    def _local(local_map):
         mapper = local_map
         if hasattr(local_map, "_mapper"):  # the front end's LocalMapper holds the class once it has mapped a scan
             mapper = local_map._mapper
@@ -48,6 +77,36 @@ class WorldMap:
                 raise ValueError("the LocalMapper has no grid yet: update it from a scan first")
         if not isinstance(mapper, kompass_cpp.mapping.LocalMapper):
             mapper = np.asarray(mapper)
+        return mapper
+
+    def match(self, robot_state, local_map, n_yaw: int = 10, yaw_step: float = math.radians(0.5), reach: int = 10) -> WorldMapMatch:
+        """Check a pose against the map: of the poses within `n_yaw` steps of `yaw_step` radians each side of
+        robot_state's yaw and `reach` cells each side of its position, the one that puts the occupied cells of
+        local_map (anything `update` accepts) onto the occupied cells of the map best.  Whole cells and whole yaw
+        steps only; n_yaw and reach are at most 31.  The map is not modified.  -> WorldMapMatch."""
+        return WorldMapMatch(self._map.match(self._local(local_map), float(robot_state.x), float(robot_state.y),
+                                             float(robot_state.yaw), int(n_yaw), float(yaw_step), int(reach)))
+
+    def update(self, robot_state, local_map, match: bool = False, min_ratio: float = 0.6, min_points: int = 30, **window) -> int:
+        """Fuse one local grid; robot_state (x, y, yaw): the robot's pose in the world.  local_map: the front end's
+        `LocalMapper` or a `kompass_cpp.mapping.LocalMapper` (its last grid where it lies on the device, no host
+        round trip), or an int32 (grid_height, grid_width) array as `LocalMapper.occupancy`.  -> cells whose class
+        changed.
+
+        match=True: `match(robot_state, local_map, **window)` first, and fuse at the corrected pose when the match
+        is trusted: ratio >= min_ratio, points >= min_points and score > score_guess; at the given pose otherwise.
+        `last_match` holds the WorldMapMatch, its `applied` the decision.  The defaults of min_ratio and min_points
+        are judgement, not measurement: nobody has tuned them on a robot."""
+        mapper = self._local(local_map)
+        if not match:
+            if window:
+                raise TypeError(f"unexpected arguments without match=True: {sorted(window)}")
+            return self._map.update(mapper, float(robot_state.x), float(robot_state.y), float(robot_state.yaw))
+        m = self.match(robot_state, mapper, **window)
+        m.applied = bool(m.ratio >= min_ratio and m.points >= min_points and m.score > m.score_guess)
+        self.last_match = m
+        if m.applied:
+            return self._map.update_at(mapper, m.pose)
         return self._map.update(mapper, float(robot_state.x), float(robot_state.y), float(robot_state.yaw))
 
     def clear(self) -> None:

@@ -107,6 +107,23 @@ class WorldMapResult(C.Structure):
         return int(self.changed), (int(self.i_min), int(self.j_min), int(self.i_max), int(self.j_max))
 
 
+class WorldMapRotation(C.Structure):
+    """kc_worldmap_rotation: one rotation of a match's window, 16 fraction bits."""
+    _fields_ = [("cq", C.c_int32), ("sq", C.c_int32)]
+
+
+class WorldMapMatchResult(C.Structure):
+    """kc_worldmap_match_result: the winner of a match (DESIGN.md 4.11 rule 15)."""
+    _fields_ = [("k", C.c_int32), ("u", C.c_int32), ("v", C.c_int32), ("score", C.c_uint32), ("score_guess", C.c_uint32),
+                ("n_points", C.c_uint32), ("pose", WorldMapPose)]
+
+    def as_dict(self):
+        """k, u, v, score, score_guess, points, and pose: the corrected (cq, sq, tx, ty)."""
+        p = self.pose
+        return dict(k=int(self.k), u=int(self.u), v=int(self.v), score=int(self.score), score_guess=int(self.score_guess),
+                    points=int(self.n_points), pose=(int(p.cq), int(p.sq), int(p.tx), int(p.ty)))
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -283,6 +300,20 @@ SIGNATURES = {
     "kc_worldmap_clear": (C.c_int, [_vp]),
     "kc_worldmap_grid_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "kc_worldmap_get": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
+    "kc_worldmap_match_check_window": (C.c_int, [C.c_int, C.c_double, C.c_int]),
+    "kc_worldmap_match_check_grid": (C.c_int, [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "kc_worldmap_match_rotations": (C.c_int, [C.c_double, C.c_int, C.c_double, C.POINTER(WorldMapRotation), _sz]),
+    "kc_worldmap_match_device": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                           C.POINTER(WorldMapPose), C.POINTER(WorldMapRotation), C.c_int, C.c_int,
+                                           C.POINTER(WorldMapMatchResult)]),
+    "kc_worldmap_match_host": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         C.POINTER(WorldMapPose), C.POINTER(WorldMapRotation), C.c_int, C.c_int,
+                                         C.POINTER(WorldMapMatchResult)]),
+    "kc_worldmap_match_from_mapper": (C.c_int, [_vp, _vp, C.POINTER(WorldMapPose), C.POINTER(WorldMapRotation), C.c_int,
+                                                C.c_int, C.POINTER(WorldMapMatchResult)]),
+    "kc_worldmap_match_scores": (C.c_int, [_vp, C.c_void_p, _sz]),
+    "kc_worldmap_match_set_timing": (C.c_int, [_vp, C.c_int]),
+    "kc_worldmap_match_times": (C.c_int, [_vp, _fp]),
 }
 
 _lib = None
@@ -1348,6 +1379,26 @@ def worldmap_quantise_pose(resolution, origin, x, y, yaw) -> WorldMapPose:
     return p
 
 
+def worldmap_match_check_window(n_yaw, yaw_step, reach):
+    """Rule 10's ranges of a match's window (host only); raises ValueError."""
+    _check(lib().kc_worldmap_match_check_window(int(n_yaw), float(yaw_step), int(reach)))
+
+
+def worldmap_match_check_grid(world_resolution, grid_height, grid_width, central, resolution):
+    """The test every match makes of its local grid before the device is used (host only)."""
+    _check(lib().kc_worldmap_match_check_grid(float(np.float32(world_resolution)), int(grid_height), int(grid_width),
+                                              int(central[0]), int(central[1]), float(np.float32(resolution))))
+
+
+def worldmap_match_rotations(yaw, n_yaw, yaw_step):
+    """Rule 10's table (host only): [(Cq_k, Sq_k) for k = -n_yaw .. n_yaw]."""
+    worldmap_match_check_window(n_yaw, yaw_step, 0)
+    n = 2 * int(n_yaw) + 1
+    rot = (WorldMapRotation * n)()
+    _check(lib().kc_worldmap_match_rotations(float(yaw), int(n_yaw), float(yaw_step), rot, n))
+    return [(int(r.cq), int(r.sq)) for r in rot]
+
+
 class WorldMapContext(_Owner, _StreamOrdered):
     """Owner of one kc_worldmap context: a world-frame map on the device, fused from local grids.
     Works in cells: a plane is an array m[I, J] of (width, height) cells, I along x, as PlannerContext's grids."""
@@ -1404,6 +1455,69 @@ class WorldMapContext(_Owner, _StreamOrdered):
         p, r = self._pose(pose), WorldMapResult()
         _check(lib().kc_worldmap_update_from_mapper(self.h, mapper.h, C.byref(p), C.byref(r)))
         return r.as_tuple()
+
+    def _window(self, pose, n_yaw, yaw_step, reach, rotations):
+        """-> (guess, rotation table, K, S) of a match.  pose: (x, y, yaw) with n_yaw / yaw_step, or a WorldMapPose
+        with `rotations`, the 2K + 1 (cq, sq) pairs."""
+        if rotations is None:
+            if isinstance(pose, WorldMapPose):
+                raise ValueError("a quantised guess needs its rotation table")
+            rotations = worldmap_match_rotations(pose[2], n_yaw, yaw_step)
+        if len(rotations) % 2 != 1:
+            raise ValueError("a rotation table holds 2 K + 1 pairs")
+        rot = (WorldMapRotation * len(rotations))(*[WorldMapRotation(int(c), int(s)) for c, s in rotations])
+        return self._pose(pose), rot, len(rotations) // 2, int(reach)
+
+    def match(self, grid, pose, n_yaw=0, yaw_step=0.0, reach=0, central=None, resolution=None, rotations=None):
+        """Rules 9 to 15: the pose of the window around the guess `pose` that puts the occupied cells of `grid` (as
+        update takes it) onto the map best.  -> dict(k, u, v, score, score_guess, points, pose)."""
+        g = np.asarray(grid)
+        if g.ndim != 2 or g.dtype != np.int32:
+            raise ValueError("expected a 2-D int32 grid")
+        g = np.asfortranarray(g)
+        c = self._central(g.shape[0], g.shape[1], central)
+        p, rot, K, S = self._window(pose, n_yaw, yaw_step, reach, rotations)
+        r = WorldMapMatchResult()
+        _check(lib().kc_worldmap_match_host(self.h, g.ctypes.data, g.shape[0], g.shape[1], int(c[0]), int(c[1]),
+                                            self.resolution if resolution is None else float(np.float32(resolution)),
+                                            C.byref(p), rot, K, S, C.byref(r)))
+        return r.as_dict()
+
+    def match_device(self, device_ptr, grid_height, grid_width, pose, n_yaw=0, yaw_step=0.0, reach=0, central=None,
+                     resolution=None, rotations=None):
+        """The same from a finished int32 grid on the context's device, read in place."""
+        c = self._central(int(grid_height), int(grid_width), central)
+        p, rot, K, S = self._window(pose, n_yaw, yaw_step, reach, rotations)
+        r = WorldMapMatchResult()
+        _check(lib().kc_worldmap_match_device(self.h, int(device_ptr), int(grid_height), int(grid_width), int(c[0]),
+                                              int(c[1]),
+                                              self.resolution if resolution is None else float(np.float32(resolution)),
+                                              C.byref(p), rot, K, S, C.byref(r)))
+        return r.as_dict()
+
+    def match_from_mapper(self, mapper: "MapperContext", pose, n_yaw=0, yaw_step=0.0, reach=0, rotations=None):
+        """The same from the last grid of a MapperContext where it lies, ordered after its scan without a host wait."""
+        p, rot, K, S = self._window(pose, n_yaw, yaw_step, reach, rotations)
+        r = WorldMapMatchResult()
+        _check(lib().kc_worldmap_match_from_mapper(self.h, mapper.h, C.byref(p), rot, K, S, C.byref(r)))
+        return r.as_dict()
+
+    def match_scores(self, n_yaw, reach):
+        """Rule 13's table of the last match, uint32 [2K+1, 2S+1, 2S+1] indexed [k + K, v + S, u + S]; the window
+        must be the one that match was given (the library checks the size)."""
+        t = 2 * int(reach) + 1
+        out = np.empty((2 * int(n_yaw) + 1, t, t), np.uint32)
+        _check(lib().kc_worldmap_match_scores(self.h, out.ctypes.data, out.size))
+        return out
+
+    def match_set_timing(self, enable=True):
+        _check(lib().kc_worldmap_match_set_timing(self.h, int(bool(enable))))
+
+    def match_times(self):
+        """(weight, points, score, pick) launches of the last match in milliseconds, by HIP events."""
+        ms = (C.c_float * 4)()
+        _check(lib().kc_worldmap_match_times(self.h, ms))
+        return tuple(float(v) for v in ms)
 
     def set_prior(self, grid):
         """grid[I, J]: an int32 or int8 (width, height) array on the host; replaces the whole state."""

@@ -9,7 +9,15 @@ Per yaw one JSON line with median [min, max] milliseconds over --reps repetition
 planes of both sides compared once (the tool stops when they differ).  The numpy statement is the yardstick's cost,
 no claim about a compiled CPU paste.  To be run by hand; nothing is gated on these numbers.
 
-  python tools/worldmap_time.py [--reps 30] [--warmup 3] [--yaws 0,0.3,0.785398,1.570796,-2.5]"""
+  python tools/worldmap_time.py [--reps 30] [--warmup 3] [--yaws 0,0.3,0.785398,1.570796,-2.5]
+
+--match times the correlative match instead (rules 9 to 15): the same 400 x 400 local grid against a world that holds
+what it saw, the guess a few cells and a degree off, windows K = S = 10 and K = S = 20.  Per window one JSON line: the
+whole call (four launches and the read-back, host clock), the four launches by HIP events (a second series of calls,
+with the events on), and the numpy statement of the rules (tests/worldmap_match_ref.py, one CPU thread: the yardstick's
+cost, not a compiled CPU implementation), whose table and record the device's are compared with once.
+
+  python tools/worldmap_time.py --match [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -25,6 +33,7 @@ sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
 
 import kompass_hip as kh  # noqa: E402
 import synthetic as syn  # noqa: E402
+import worldmap_match_ref as mref  # noqa: E402
 import worldmap_ref as ref  # noqa: E402
 from helpers import DeviceArray, hip_runtime  # noqa: E402
 
@@ -43,14 +52,62 @@ def timed(fn, reps, warmup):
     return [round(statistics.median(out), 4), round(min(out), 4), round(max(out), 4)]
 
 
+def spread(v):
+    return [round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)]
+
+
+def match_leg(args):
+    hip = hip_runtime()
+    ang, rng = syn.dense_scan(2048, 1.2)
+    true = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021, 0.3)
+    r = float(np.float32(RES))
+    guess = (true[0] - 3 * r, true[1] + 2 * r, true[2] + 0.0175)
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as ctx:
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        local = np.empty(GH * GW, np.int32)
+        assert hip.hipMemcpy(local.ctypes.data_as(C.c_void_p), C.c_void_p(mapper.grid_device_ptr()), local.nbytes, 2) == 0
+        g = local.reshape(GW, GH).T
+        want = ref.WorldMapRef(W, H, RES, ORIGIN)
+        assert ctx.update_from_mapper(mapper, true) == want.update(g, true)
+        for K in (10, 20):
+            S, step = K, 0.00873 * 10 / K   # the same +- 5 degrees either way
+            window = dict(n_yaw=K, yaw_step=step, reach=S)
+            t0 = time.perf_counter()
+            exp, table, _ = mref.match_pose(want, g, guess, K, step, S)
+            numpy_ms = (time.perf_counter() - t0) * 1e3
+            got = ctx.match_from_mapper(mapper, guess, **window)
+            assert got == exp._asdict(), (got, exp, "device and statement disagree")
+            assert np.array_equal(ctx.match_scores(K, S), table), "score tables differ"
+            whole = timed(lambda: ctx.match_from_mapper(mapper, guess, **window), args.reps, args.warmup)
+            ctx.match_set_timing(True)
+            parts = []
+            for k in range(args.warmup + args.reps):
+                ctx.match_from_mapper(mapper, guess, **window)
+                if k >= args.warmup:
+                    parts.append(ctx.match_times())
+            ctx.match_set_timing(False)
+            names = ["weight", "points", "score", "pick"]
+            line = {"world": [W, H], "local": [GH, GW], "n_yaw": K, "reach": S, "yaw_step": step, "points": exp.points,
+                    "candidates": int(table.size), "winner": [exp.k, exp.u, exp.v], "score": exp.score,
+                    "score_guess": exp.score_guess, "reps": args.reps, "warmup": args.warmup, "device_match_ms": whole,
+                    "numpy_statement_one_thread_ms_once": round(numpy_ms, 1)}
+            for i, n in enumerate(names):
+                line[f"launch_{n}_ms"] = spread([p[i] for p in parts])
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--yaws", default="0,0.3,0.785398,1.570796,-2.5")
+    ap.add_argument("--match", action="store_true", help="time the correlative match instead of the update")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
+    if args.match:
+        return match_leg(args)
     hip = hip_runtime()
     ang, rng = syn.dense_scan(2048, 1.2)                      # ranges 3.6 .. 8.4 m in a 20 m window
     pose_xy = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021)
