@@ -309,6 +309,18 @@ int kc_dwa_set_grid_device(kc_dwa *ctx, const kc_state *state, const int32_t *de
 struct kc_mapper;
 int kc_dwa_set_grid_from_mapper(kc_dwa *ctx, const kc_state *state, struct kc_mapper *mapper,
                                 float max_sensor_range);
+/* The obstacles of a world map (kc_worldmap, below) within sensor range of the robot,
+ * without leaving the device.  Nothing in the reference to cite: it leaves the world map
+ * to its ROS side, and its controllers see the current scan only.  The centre is
+ * (state->x, state->y); the list is that of kc_worldmap_points (DESIGN.md 4.11 rules 16
+ * to 19).  State afterwards == kc_dwa_set_points(ctx, state, list, n, max_sensor_range):
+ * global frame.  Every argument is checked before the device is used: KC_ERR_INVALID for
+ * a null pointer, a map on another device or a max_sensor_range that is not a finite
+ * float > 0, KC_ERR_RANGE as kc_worldmap_window says.  The controller's stream waits for
+ * the map's (event wait, no host synchronisation of the map) and runs the extraction;
+ * the call returns with the list extracted, so the map may be updated again at once. */
+struct kc_worldmap;
+int kc_dwa_set_worldmap(kc_dwa *ctx, const kc_state *state, struct kc_worldmap *map, float max_sensor_range);
 
 /* the (reference_path, tracked_segment) arguments of getMinTrajectoryCost
  * (cost_evaluator.h:139-142): segment points (Path::View X/Y/Z, path.h:39-76),
@@ -1122,6 +1134,33 @@ int kc_worldmap_clear(kc_worldmap *ctx);
 int kc_worldmap_grid_device(kc_worldmap *ctx, void **dev_cls_int8);
 /* copies of the planes, cap the cells either output holds; either pointer may be NULL */
 int kc_worldmap_get(kc_worldmap *ctx, int8_t *cls_out, int8_t *evidence_out, size_t cap);
+
+/* The map's obstacles near the robot as a world-frame point list (DESIGN.md 4.11 rules 16
+ * to 19).  Nothing in the reference to cite, as above: it leaves the world map to its
+ * ROS side.
+ * Rule 16: the robot's position is quantised as kc_worldmap_quantise_pose does with yaw 0;
+ * the centre cell is Ic = (tx + 2^15) >> 16, Jc = (ty + 2^15) >> 16 (arithmetic shifts),
+ * the radius Rc = (int)ceil((double)max_sensor_range / (double)resolution).  Rule 17: cell
+ * (I, J) counts iff it lies inside the map, its cls byte is KC_OCCUPIED and (I - Ic)^2 +
+ * (J - Jc)^2 <= Rc^2 in int64.  Rule 18: its point is x = (float)(origin_x + (double)I *
+ * (double)resolution), y alike with J and origin_y, z = 0: the cell's centre, product and
+ * sum rounded once each in double.  Rule 19: the list is the set of those points in no
+ * particular order, with its count and the index bounds of the counted cells.
+ * kc_worldmap_window is rule 16 alone (host only, needs no device): KC_ERR_INVALID unless
+ * max_sensor_range is a finite float > 0 and everything else finite, KC_ERR_RANGE for Rc >
+ * 2048 (which bounds the scratch list) or a position more than 2^20 cells from the
+ * origin. */
+int kc_worldmap_window(float resolution, double origin_x, double origin_y, double x, double y, float max_sensor_range,
+                       int32_t *ic_out, int32_t *jc_out, int32_t *rc_out);
+/* The list into host memory: one launch over the window's box clipped to the map, and the
+ * read-back; returns with the list final.  xyz_out: cap points of three floats, or NULL
+ * for the count and the bounds only.  bounds_out: i_min, i_max, j_min, j_max of the
+ * counted cells, every one -1 when *count_out is 0.  cap < count: KC_ERR_RANGE with
+ * *count_out set and nothing written to xyz_out.  A robot outside the map is no error:
+ * the window is clipped, perhaps to nothing.  Every argument is checked before the
+ * device is used. */
+int kc_worldmap_points(kc_worldmap *ctx, double x, double y, float max_sensor_range, float *xyz_out, size_t cap,
+                       size_t *count_out, int32_t bounds_out[4]);
 
 /* Correlative match of a local grid against the map (DESIGN.md 4.11 rules 9 to 15): which
  * pose near a guess puts the grid's occupied cells onto the map's?  Integers only, sums

@@ -710,6 +710,10 @@ PYBIND11_MODULE(kompass_cpp, m) {
       // the device (not in the reference: SURVEY 8f rank 4)
       .def("compute_velocity_commands", [](DWA &d, const Control::Velocity2D &v, const Mapping::LocalMapper &m) {
              return d.computeVelocityCommandsSet<Mapping::LocalMapper>(v, m); })
+      // sensor data = the occupied cells of a WorldMap within sensor range of the robot, extracted on the
+      // device (not in the reference: DESIGN.md 4.11 rules 16 to 19)
+      .def("compute_velocity_commands", [](DWA &d, const Control::Velocity2D &v, const Mapping::WorldMap &m) {
+             return d.computeVelocityCommandsSet<Mapping::WorldMap>(v, m); })
       .def("compute_velocity_commands", [](DWA &d, const Control::Velocity2D &v, const py::object &cloud) {
              // an (N, 3) float32 C-contiguous array is consumed where it lies; anything else (lists of
              // tuples, other dtypes) is converted first
@@ -779,6 +783,10 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def("execute", [](PP &self, const double dt, const Control::LaserScan &scan) {
              return self.execute<Control::LaserScan>(dt, scan);
            }, "Execute Pure Pursuit with LaserScan obstacle avoidance", py::arg("delta_time"), py::arg("laser_scan"))
+      // (not in the reference: the obstacles of a WorldMap within sensor range, extracted on the device)
+      .def("execute", [](PP &self, const double dt, const Mapping::WorldMap &map) {
+             return self.execute<Mapping::WorldMap>(dt, map);
+           }, "Execute Pure Pursuit with the obstacles of a world map", py::arg("delta_time"), py::arg("world_map"))
       .def("execute", [](PP &self, const double dt, const py::object &cloud) {
              // world-frame points: an (N, 3) float32 C-contiguous array is read where it lies, anything else
              // (lists of 3-sequences, other dtypes) is converted first
@@ -1062,6 +1070,17 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return m.updateAt(d, gh, gw, p);
            }, py::arg("grid"), py::arg("pose"), "update at a quantised pose (cq, sq, tx, ty), a match's `pose`")
       .def("clear", &Mapping::WorldMap::clear)
+      .def("points", [](const Mapping::WorldMap &m, double x, double y, float max_sensor_range) {
+             std::vector<Path::Point> pts;
+             {
+               py::gil_scoped_release nogil;
+               pts = m.points(x, y, max_sensor_range);
+             }
+             FArr a({(py::ssize_t)pts.size(), (py::ssize_t)3});
+             if (!pts.empty()) std::memcpy(a.mutable_data(), pts.data()->data(), sizeof(float) * 3 * pts.size());
+             return a;
+           }, py::arg("x"), py::arg("y"), py::arg("max_sensor_range"),
+           "The occupied cells within max_sensor_range of (x, y) as world-frame points, float32 [n, 3], in no particular order")
       .def("get_cls", [plane](const Mapping::WorldMap &m) { return plane(m.cls(), m.width(), m.height()); },
            "the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied")
       .def("get_evidence", [plane](const Mapping::WorldMap &m) { return plane(m.evidence(), m.width(), m.height()); },

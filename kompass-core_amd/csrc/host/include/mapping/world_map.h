@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "datatypes/path.h"
 #include "mapping/local_mapper.h"
 #include "utils/hip_backend.h"
 
@@ -64,6 +65,12 @@ class WorldMap {
   // One update at a quantised pose (a Match's), from the same three sources
   uint32_t updateAt(const LocalMapper &mapper, const kc_worldmap_pose &pose);
   uint32_t updateAt(const int32_t *grid, int grid_height, int grid_width, const kc_worldmap_pose &pose);
+
+  // The occupied cells within max_sensor_range of (x, y) as world-frame points, z = 0, in no particular order (DESIGN.md
+  // 4.11 rules 16 to 19): a cloud to show, or to hand to a consumer of point lists.  The controllers take the map itself
+  // (CollisionChecker::updateSensorData) and never see this list.  std::invalid_argument unless max_sensor_range is a
+  // finite float > 0, std::out_of_range above 2048 cells of radius.
+  std::vector<Path::Point> points(double x, double y, float max_sensor_range) const;
 
   // copies of the planes, width x height as the map
   std::vector<int8_t> cls() const;

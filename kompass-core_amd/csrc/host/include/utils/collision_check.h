@@ -5,6 +5,7 @@
 #pragma once
 
 #include "mapping/local_mapper.h"
+#include "mapping/world_map.h"
 
 #include <memory>
 #include <vector>
@@ -37,6 +38,9 @@ class CollisionChecker {
   void updateSensorData(const Control::PointCloudView &cloud, const bool global_frame = true);
   // the OCCUPIED cells of the mapper's device-resident grid as the point list (no host round trip)
   void updateSensorData(const Mapping::LocalMapper &mapper, const bool global_frame = true);
+  // the occupied cells of a world map within maxSensorRange of the robot, extracted on the device (not in the
+  // reference: kc_dwa_set_worldmap, DESIGN.md 4.11 rules 16 to 19); world-frame by construction
+  void updateSensorData(const Mapping::WorldMap &map, const bool global_frame = true);
 
   bool checkCollisions();
   bool checkCollisions(const Path::State pose);

@@ -78,6 +78,9 @@ class TrajectorySampler {
   std::unique_ptr<TrajectorySamples2D>
   generateTrajectories(const Velocity2D &current_vel, const Path::State &current_pose,
                        const Mapping::LocalMapper &mapper);
+  std::unique_ptr<TrajectorySamples2D>
+  generateTrajectories(const Velocity2D &current_vel, const Path::State &current_pose,
+                       const Mapping::WorldMap &map);
 
   void resetOctreeResolution(const double resolution);
   float getRobotRadius() const;
@@ -106,6 +109,8 @@ class TrajectorySampler {
                          float max_sensor_range);
   size_t rolloutOnDevice(const Velocity2D &current_vel, const Path::State &pose,
                          const Mapping::LocalMapper &mapper, float max_sensor_range);
+  size_t rolloutOnDevice(const Velocity2D &current_vel, const Path::State &pose,
+                         const Mapping::WorldMap &map, float max_sensor_range);
   // the same without the roll-out launch: sensor data + lattice of this cycle are
   // resident afterwards, CostEvaluator::cycleOnDevice runs the whole cycle (one launch)
   template <typename T>

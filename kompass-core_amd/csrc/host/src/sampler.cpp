@@ -102,6 +102,10 @@ void CollisionChecker::updateSensorData(const Mapping::LocalMapper &mapper, cons
   const kc_state st = toKc(pose_);
   hip::check(kc_dwa_set_grid_from_mapper(ctx_.get(), &st, mapper.hipContext(), maxSensorRange));
 }
+void CollisionChecker::updateSensorData(const Mapping::WorldMap &map, const bool) {
+  const kc_state st = toKc(pose_);
+  hip::check(kc_dwa_set_worldmap(ctx_.get(), &st, map.hipContext(), maxSensorRange));
+}
 std::vector<bool> CollisionChecker::checkCollisions(const std::vector<Path::State> &states) {
   const size_t n = states.size();
   std::vector<double> x(n), y(n), yaw(n);
@@ -260,6 +264,13 @@ size_t TrajectorySampler::rolloutOnDevice(const Velocity2D &vel, const Path::Sta
   checker_->updateSensorData(mapper);
   return launch(vel, pose);
 }
+size_t TrajectorySampler::rolloutOnDevice(const Velocity2D &vel, const Path::State &pose,
+                                          const Mapping::WorldMap &map, float max_range) {
+  checker_->maxSensorRange = max_range;
+  checker_->updateState(pose);
+  checker_->updateSensorData(map);
+  return launch(vel, pose);
+}
 
 std::unique_ptr<TrajectorySamples2D> TrajectorySampler::collect() {
   const size_t P = numPointsPerTrajectory;
@@ -307,6 +318,12 @@ std::unique_ptr<TrajectorySamples2D>
 TrajectorySampler::generateTrajectories(const Velocity2D &vel, const Path::State &pose,
                                         const Mapping::LocalMapper &mapper) {
   rolloutOnDevice(vel, pose, mapper, checker_->maxSensorRange);
+  return collect();
+}
+std::unique_ptr<TrajectorySamples2D>
+TrajectorySampler::generateTrajectories(const Velocity2D &vel, const Path::State &pose,
+                                        const Mapping::WorldMap &map) {
+  rolloutOnDevice(vel, pose, map, checker_->maxSensorRange);
   return collect();
 }
 

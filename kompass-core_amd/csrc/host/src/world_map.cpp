@@ -129,6 +129,17 @@ void WorldMap::clear() {
   last_ = {0, -1, -1, -1, -1};
 }
 
+std::vector<Path::Point> WorldMap::points(double x, double y, float max_sensor_range) const {
+  static_assert(sizeof(Path::Point) == 3 * sizeof(float), "Path::Point must be packed (x, y, z)");
+  size_t n = 0;
+  int32_t bounds[4];
+  hip::check(kc_worldmap_points(ctx_.get(), x, y, max_sensor_range, nullptr, 0, &n, bounds));
+  std::vector<Path::Point> out(n);
+  if (n) hip::check(kc_worldmap_points(ctx_.get(), x, y, max_sensor_range, out.data()->data(), n, &n, bounds));
+  out.resize(n);
+  return out;
+}
+
 std::vector<int8_t> WorldMap::cls() const {
   std::vector<int8_t> out(static_cast<size_t>(width_) * static_cast<size_t>(height_));
   hip::check(kc_worldmap_get(ctx_.get(), out.data(), nullptr, out.size()));

@@ -1306,54 +1306,29 @@ int kc_dwa_set_points_sensor_frame(kc_dwa *c, const kc_state *st, const float *x
   return set_points_impl(c, st, xyz, n, max_range, false);
 }
 
-// SURVEY 8f rank 4: the mapper's grid feeds the controller without leaving the
-// device.  Same state as kc_dwa_set_points with the list of the OCCUPIED cells.
-int kc_dwa_set_grid_device(kc_dwa *c, const kc_state *st, const int32_t *dev_grid, int H, int W,
-                           float res, int c0, int c1, float max_range) {
-  if (!c || !st || !dev_grid) KC_FAIL(KC_ERR_INVALID, "null argument");
-  if (H <= 0 || W <= 0 || !(res > 0.0f) || static_cast<size_t>(H) * W > 0x3FFFFFFFul)
-    KC_FAIL(KC_ERR_INVALID, "grid dimensions and resolution must be positive");
-  KC_TRY(use_device(c));
-  KC_TRY(quiesce_for_update(c));
-  c->frame = hm::Rigid3f::identity();
-  c->tilted = false;
-  ++c->sensor_version;
-  c->oscan_valid = false;
-  c->onear_ok = false;
-  const hm::Rigid3f body = hm::Rigid3f::from_pose2d(st->x, st->y, st->yaw);
-  c->obs_tf = c->sensor_tf_body * body;
-  c->raw_is_scan = false;
-  c->raw_on_device = false;
-  c->have_sensor = true;
-  c->max_obs_dist = max_range / 3.0f;
-  c->host_lists_valid = true;
-  const size_t cells = static_cast<size_t>(H) * W;
-  KC_TRY(c->d_raw.reserve(3 * cells + 16));
+// The two hand-offs that form their point list on the device (a mapper's grid, the world map's window) share what
+// follows the extraction.  The counter block both kernels add into: count, i_min, i_max, j_min, j_max, a line each.
+int arm_list_counters(kc_dwa *c) {
   KC_TRY(c->h_gridrec.reserve(8));
-  if (!c->d_gridcnt.p) {
-    KC_TRY(c->d_gridcnt.reserve(5 * kGridCntStride));
-    int init[5 * kGridCntStride] = {0};
-    init[1 * kGridCntStride] = INT_MAX;
-    init[2 * kGridCntStride] = INT_MIN;
-    init[3 * kGridCntStride] = INT_MAX;
-    init[4 * kGridCntStride] = INT_MIN;
-    KC_HIP(hipMemcpyAsync(c->d_gridcnt.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-    KC_HIP(hipStreamSynchronize(c->stream));
-    c->h_gridrec.p[0] = 0;
-  }
-  GridPtsArgs ga{};
-  ga.grid = dev_grid;
-  ga.H = H;
-  ga.W = W;
-  ga.c0 = c0;
-  ga.c1 = c1;
-  ga.res = res;
-  ga.xyz = c->d_raw.p;
-  ga.cnt = c->d_gridcnt.p;
+  if (c->d_gridcnt.p) return KC_OK;
+  KC_TRY(c->d_gridcnt.reserve(5 * kGridCntStride));
+  int init[5 * kGridCntStride] = {0};
+  init[1 * kGridCntStride] = INT_MAX;
+  init[2 * kGridCntStride] = INT_MIN;
+  init[3 * kGridCntStride] = INT_MAX;
+  init[4 * kGridCntStride] = INT_MIN;
+  KC_HIP(hipMemcpyAsync(c->d_gridcnt.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->h_gridrec.p[0] = 0;
+  return KC_OK;
+}
+
+// Behind an extraction queued on the controller's stream into d_raw and d_gridcnt: publish the count and the index
+// bounds, wait for them, then the sensor update of that list.  bounds_of(rec, lo, hi): the list's float bounds from the
+// record's index bounds rec[2 .. 5] (the hand-off knows its cell -> point rule; the host never sees a point).
+template <typename BoundsOf>
+int finish_list_handoff(kc_dwa *c, BoundsOf bounds_of) {
   const long long seq = ++c->grid_seq;
-  KC_TRY(c->timing.start("grid_points_kernel", c->stream));
-  hipLaunchKernelGGL(grid_points_kernel, dim3(blocks_for(cells, 256)), dim3(256), 0, c->stream, ga);
-  KC_TRY(c->timing.stop(c->stream));
   hipLaunchKernelGGL(grid_points_publish_kernel, dim3(1), dim3(1), 0, c->stream, c->d_gridcnt.p,
                      c->h_gridrec.p, seq);
   KC_HIP(hipGetLastError());
@@ -1376,10 +1351,8 @@ int kc_dwa_set_grid_device(kc_dwa *c, const kc_state *st, const int32_t *dev_gri
     KC_TRY(upload_voxels(c));
     return upload_obstacles(c, 0);
   }
-  const float lo[3] = {static_cast<float>(static_cast<int>(c->h_gridrec.p[2]) - c0) * res,
-                       static_cast<float>(static_cast<int>(c->h_gridrec.p[4]) - c1) * res, 0.0f};
-  const float hi[3] = {static_cast<float>(static_cast<int>(c->h_gridrec.p[3]) - c0) * res,
-                       static_cast<float>(static_cast<int>(c->h_gridrec.p[5]) - c1) * res, 0.0f};
+  float lo[3], hi[3];
+  bounds_of(c->h_gridrec.p, lo, hi);
   bool done = false;
   KC_TRY(sensor_update_device_bounded(c, nullptr, n, lo, hi, &done));
   if (done) return KC_OK;
@@ -1393,6 +1366,57 @@ int kc_dwa_set_grid_device(kc_dwa *c, const kc_state *st, const int32_t *dev_gri
   build_host_lists(c, c->raw_xyz.data(), n);
   KC_TRY(upload_voxels(c));
   return upload_obstacles(c, n);
+}
+
+// What kc_dwa_set_points sets before its sensor update, for a global-frame list that is formed on the device
+int begin_device_list(kc_dwa *c, const kc_state *st, float max_range) {
+  KC_TRY(quiesce_for_update(c));
+  c->frame = hm::Rigid3f::identity();
+  c->tilted = false;
+  ++c->sensor_version;
+  c->oscan_valid = false;
+  c->onear_ok = false;
+  const hm::Rigid3f body = hm::Rigid3f::from_pose2d(st->x, st->y, st->yaw);
+  c->obs_tf = c->sensor_tf_body * body;
+  c->raw_is_scan = false;
+  c->raw_on_device = false;
+  c->have_sensor = true;
+  c->max_obs_dist = max_range / 3.0f;
+  c->host_lists_valid = true;
+  return KC_OK;
+}
+
+// SURVEY 8f rank 4: the mapper's grid feeds the controller without leaving the
+// device.  Same state as kc_dwa_set_points with the list of the OCCUPIED cells.
+int kc_dwa_set_grid_device(kc_dwa *c, const kc_state *st, const int32_t *dev_grid, int H, int W,
+                           float res, int c0, int c1, float max_range) {
+  if (!c || !st || !dev_grid) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (H <= 0 || W <= 0 || !(res > 0.0f) || static_cast<size_t>(H) * W > 0x3FFFFFFFul)
+    KC_FAIL(KC_ERR_INVALID, "grid dimensions and resolution must be positive");
+  KC_TRY(use_device(c));
+  KC_TRY(begin_device_list(c, st, max_range));
+  const size_t cells = static_cast<size_t>(H) * W;
+  KC_TRY(c->d_raw.reserve(3 * cells + 16));
+  KC_TRY(arm_list_counters(c));
+  GridPtsArgs ga{};
+  ga.grid = dev_grid;
+  ga.H = H;
+  ga.W = W;
+  ga.c0 = c0;
+  ga.c1 = c1;
+  ga.res = res;
+  ga.xyz = c->d_raw.p;
+  ga.cnt = c->d_gridcnt.p;
+  KC_TRY(c->timing.start("grid_points_kernel", c->stream));
+  hipLaunchKernelGGL(grid_points_kernel, dim3(blocks_for(cells, 256)), dim3(256), 0, c->stream, ga);
+  KC_TRY(c->timing.stop(c->stream));
+  return finish_list_handoff(c, [&](const long long *rec, float lo[3], float hi[3]) {
+    lo[0] = static_cast<float>(static_cast<int>(rec[2]) - c0) * res;
+    lo[1] = static_cast<float>(static_cast<int>(rec[4]) - c1) * res;
+    hi[0] = static_cast<float>(static_cast<int>(rec[3]) - c0) * res;
+    hi[1] = static_cast<float>(static_cast<int>(rec[5]) - c1) * res;
+    lo[2] = hi[2] = 0.0f;
+  });
 }
 
 int kc_dwa_set_grid_from_mapper(kc_dwa *c, const kc_state *st, kc_mapper *m, float max_range) {
@@ -1409,6 +1433,44 @@ int kc_dwa_set_grid_from_mapper(kc_dwa *c, const kc_state *st, kc_mapper *m, flo
     KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
   }
   return kc_dwa_set_grid_device(c, st, v.grid, v.H, v.W, v.res, v.c0, v.c1, max_range);
+}
+
+// The world map's obstacles within sensor range of the robot (DESIGN.md 4.11 rules 16 to 19): the same hand-off with the
+// list extracted from the map's cls plane by kc_worldmap.hip's kernel, on this context's stream.
+int kc_dwa_set_worldmap(kc_dwa *c, const kc_state *st, kc_worldmap *map, float max_range) {
+  if (!c || !st || !map) KC_FAIL(KC_ERR_INVALID, "null argument");
+  kc::WorldMapView v{};
+  KC_TRY(kc::worldmap_view(map, &v));
+  if (v.device != c->prm.device)
+    KC_FAIL(KC_ERR_INVALID, "world map on device %d, controller on device %d", v.device, c->prm.device);
+  kc::WorldMapWindow w{};
+  KC_TRY(kc::worldmap_window(v, st->x, st->y, max_range, &w));
+  KC_TRY(use_device(c));
+  KC_TRY(begin_device_list(c, st, max_range));
+  if (w.max_points == 0) {  // the window misses the map: the empty list, no launch
+    build_host_lists(c, nullptr, 0);
+    KC_TRY(upload_voxels(c));
+    return upload_obstacles(c, 0);
+  }
+  KC_TRY(c->d_raw.reserve(3 * w.max_points + 16));
+  KC_TRY(arm_list_counters(c));
+  if (v.stream != c->stream) {
+    // the controller's stream waits for the map's writes; the host does not
+    if (!c->grid_ready) KC_HIP(hipEventCreateWithFlags(&c->grid_ready, hipEventDisableTiming));
+    KC_HIP(hipEventRecord(c->grid_ready, v.stream));
+    KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
+  }
+  KC_TRY(c->timing.start("worldmap_window_points_kernel", c->stream));
+  KC_TRY(kc::worldmap_queue_points(v, w, c->d_raw.p, c->d_gridcnt.p, nullptr, c->stream));
+  KC_TRY(c->timing.stop(c->stream));
+  const double res = static_cast<double>(v.res);
+  return finish_list_handoff(c, [&](const long long *rec, float lo[3], float hi[3]) {
+    lo[0] = kc::worldmap_cell_coord(v.ox, static_cast<int>(rec[2]), res);
+    hi[0] = kc::worldmap_cell_coord(v.ox, static_cast<int>(rec[3]), res);
+    lo[1] = kc::worldmap_cell_coord(v.oy, static_cast<int>(rec[4]), res);
+    hi[1] = kc::worldmap_cell_coord(v.oy, static_cast<int>(rec[5]), res);
+    lo[2] = hi[2] = 0.0f;
+  });
 }
 
 // x / y / z rows, or xyz = [S][3] interleaved points (Path::Point order) de-interleaved on the way into the rows

@@ -290,6 +290,34 @@ struct MapperView {
 };
 int mapper_view(kc_mapper *m, MapperView *out);
 
+// internal view of a world map for the obstacle hand-off (kc_worldmap.hip owns the planes and the kernel; DESIGN.md
+// 4.11 rules 16 to 19)
+struct WorldMapView {
+  const int8_t *cls;  // [W x H], cell (I, J) at I + J * W
+  int W, H;
+  float res;
+  double ox, oy;
+  hipStream_t stream;
+  int device;
+};
+int worldmap_view(kc_worldmap *m, WorldMapView *out);
+// rule 16's window, and the number of map cells inside rule 17's disc: the most points a list of it can hold
+struct WorldMapWindow {
+  int ic, jc, rc;
+  size_t max_points;  // 0: the window misses the map, nothing to launch
+};
+int worldmap_window(const WorldMapView &v, double x, double y, float max_range, WorldMapWindow *out);
+// Queues the extraction on `stream` (the caller's: it orders the launch after the map's writes itself): the points into
+// xyz ([max_points][3] floats; nullptr counts only), the count and the index bounds i_min, i_max, j_min, j_max into cnt,
+// five words 16 words apart that hold 0, INT_MAX, INT_MIN, INT_MAX, INT_MIN (grid_points_kernel's block, so
+// grid_points_publish_kernel serves both).  rearm: another such block the launch puts back to those values, or nullptr.
+int worldmap_queue_points(const WorldMapView &v, const WorldMapWindow &w, float *xyz, unsigned int *cnt, unsigned int *rearm,
+                          hipStream_t stream);
+// rule 18: the coordinate of cell index k along one axis
+__host__ __device__ inline float worldmap_cell_coord(double origin, int k, double res) {
+  return static_cast<float>(origin + static_cast<double>(k) * res);
+}
+
 // kc_comm.hip: all-reduce (min, or sum) of int64 words on a stream; send == recv is allowed
 int comm_allreduce_i64(kc_comm *m, const long long *send, long long *recv, size_t count, bool sum,
                        hipStream_t stream);

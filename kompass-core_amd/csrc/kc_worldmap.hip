@@ -33,6 +33,15 @@
 //      every weight is computed from the cls plane with the map's own bounds, so the box never decides one.
 //      uint32 adds commute: the table does not depend on the order the workgroups arrive in.
 //
+//  (f) obstacle list (rules 16 to 19).  worldmap_window_points_kernel (the match's worldmap_points_kernel has the
+//      shorter name already) runs over the bounding box of the disc clipped to the map, in the update kernel's
+//      layout: 64 lanes along I, so a wavefront loads consecutive bytes of one cls row, four rows a workgroup.
+//      Compaction as grid_points_kernel does it (kc_sensor_kernels.h): ballot + popcount in the wavefront, hits and
+//      the four index bounds gathered in LDS, one slot range and four bound atomics per workgroup that holds a hit,
+//      the five counters a 64-byte line each.  Counts and min / max commute: only the list's order depends on the
+//      order of arrival, and rule 19 leaves that open.  The launcher (kc_internal.h) queues it on a caller's stream
+//      into a caller's buffers, which is how the controller's translation unit reaches it.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -314,6 +323,86 @@ __global__ __launch_bounds__(kWmPickBlock) void worldmap_pick_kernel(const uint3
   }
 }
 
+// ---- obstacle list (rules 16 to 19) ------------------------------------------------------------------------------
+constexpr int kWmPtsStride = 16;           // words between two counters: one 64-byte line each (kGridCntStride)
+constexpr int kWmPtsMaxRadius = 2048;      // rule 16's cap on Rc
+
+struct WmWindowArgs {
+  const int8_t *cls;
+  float *xyz;            // [n][3]; nullptr: count and bounds only
+  unsigned int *cnt;     // count, then (as int) i_min, i_max, j_min, j_max at kWmPtsStride words each
+  unsigned int *rearm;   // a second counter block to put back to its start values, or nullptr
+  int W;
+  int i_lo, j_lo, i_hi, j_hi;  // the launch box, inclusive, inside the map
+  int ic, jc;
+  long long r2;
+  double res, ox, oy;
+};
+
+__global__ __launch_bounds__(kWmBlock) void worldmap_window_points_kernel(WmWindowArgs a) {
+  __shared__ unsigned int s_hits, s_base;
+  __shared__ int s_lo_i, s_hi_i, s_lo_j, s_hi_j;
+  const bool first_thread = threadIdx.x == 0 && threadIdx.y == 0;
+  if (first_thread) {
+    s_hits = 0u;
+    s_lo_i = INT_MAX;
+    s_hi_i = INT_MIN;
+    s_lo_j = INT_MAX;
+    s_hi_j = INT_MIN;
+    if (a.rearm && blockIdx.x == 0 && blockIdx.y == 0) {  // no lane of this launch reads it
+      int *r = reinterpret_cast<int *>(a.rearm);
+      a.rearm[0] = 0u;
+      r[1 * kWmPtsStride] = INT_MAX;
+      r[2 * kWmPtsStride] = INT_MIN;
+      r[3 * kWmPtsStride] = INT_MAX;
+      r[4 * kWmPtsStride] = INT_MIN;
+    }
+  }
+  __syncthreads();
+  const int I = a.i_lo + static_cast<int>(blockIdx.x) * kWmLanes + static_cast<int>(threadIdx.x);
+  const int J = a.j_lo + static_cast<int>(blockIdx.y) * kWmRows + static_cast<int>(threadIdx.y);
+  bool hit = false;
+  if (I <= a.i_hi && J <= a.j_hi) {  // the box is a launch bound inside the map; rule 17's disc is tested in full
+    const long long di = static_cast<long long>(I) - a.ic, dj = static_cast<long long>(J) - a.jc;
+    if (di * di + dj * dj <= a.r2)
+      hit = a.cls[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)] == KC_OCCUPIED;
+  }
+  // one wavefront is one row segment (blockDim.x == 64): J is uniform in it, I ascends with the lane
+  const unsigned long long mask = __ballot(hit);
+  const int lane = static_cast<int>(threadIdx.x);
+  unsigned int rank = 0;
+  if (mask != 0ull) {
+    const int first = __ffsll(mask) - 1, last = 63 - __clzll(mask);
+    unsigned int wbase = 0;
+    if (lane == first) {
+      wbase = atomicAdd(&s_hits, static_cast<unsigned int>(__popcll(mask)));
+      atomicMin(&s_lo_i, I);
+      atomicMin(&s_lo_j, J);
+      atomicMax(&s_hi_j, J);
+    }
+    if (lane == last) atomicMax(&s_hi_i, I);
+    wbase = __shfl(wbase, first, 64);
+    rank = wbase + static_cast<unsigned int>(__popcll(mask & ((1ull << lane) - 1ull)));
+  }
+  __syncthreads();
+  if (s_hits == 0u) return;
+  if (first_thread) {
+    s_base = atomicAdd(&a.cnt[0], s_hits);
+    int *b = reinterpret_cast<int *>(a.cnt);
+    atomicMin(&b[1 * kWmPtsStride], s_lo_i);
+    atomicMax(&b[2 * kWmPtsStride], s_hi_i);
+    atomicMin(&b[3 * kWmPtsStride], s_lo_j);
+    atomicMax(&b[4 * kWmPtsStride], s_hi_j);
+  }
+  __syncthreads();
+  if (hit && a.xyz) {
+    const size_t slot = static_cast<size_t>(s_base) + rank;
+    a.xyz[3 * slot] = worldmap_cell_coord(a.ox, I, a.res);
+    a.xyz[3 * slot + 1] = worldmap_cell_coord(a.oy, J, a.res);
+    a.xyz[3 * slot + 2] = 0.0f;
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -340,6 +429,12 @@ struct kc_worldmap {
   PinBuf<int> h_mrec;
   int match_K = -1, match_S = -1;  // the window of the table d_scores holds; -1: none
   Timing match_time;               // weight, points, score, pick
+  // obstacle list (rules 16 to 19): scratch grown on demand and kept
+  DevBuf<float> d_pts;             // the list of the last kc_worldmap_points
+  DevBuf<unsigned int> d_ptcnt;    // two counter blocks of 5 lines: call n counts in block n & 1 and re-arms the other
+  PinBuf<int> h_ptrec;
+  unsigned long long pt_seq = 0;
+  bool ptcnt_ready = false;        // both blocks hold their start values
 };
 
 namespace {
@@ -636,6 +731,47 @@ int wm_match(kc_worldmap *c, const int32_t *dev, int gh, int gw, int c0, int c1,
   return KC_OK;
 }
 
+// rule 16: the window's centre cell and radius in cells
+int wm_window(float res, double ox, double oy, double x, double y, float max_range, int *ic, int *jc, int *rc) {
+  if (!std::isfinite(max_range) || !(max_range > 0.0f))
+    KC_FAIL(KC_ERR_INVALID, "max_sensor_range must be a finite float > 0, got %g", static_cast<double>(max_range));
+  kc_worldmap_pose p;
+  KC_TRY(kc_worldmap_quantise_pose(res, ox, oy, x, y, 0.0, &p));
+  const double cells = std::ceil(static_cast<double>(max_range) / static_cast<double>(res));
+  if (!(cells <= static_cast<double>(kWmPtsMaxRadius)))
+    KC_FAIL(KC_ERR_RANGE, "a sensor range of %g m is %g cells at %g m, above the cap of %d", static_cast<double>(max_range), cells,
+            static_cast<double>(res), kWmPtsMaxRadius);
+  *ic = static_cast<int>((p.tx + (1ll << 15)) >> 16);
+  *jc = static_cast<int>((p.ty + (1ll << 15)) >> 16);
+  *rc = static_cast<int>(cells);
+  return KC_OK;
+}
+
+// The disc's bounding box clipped to the map, inclusive; false when empty.  |ic|, |jc| <= 2^20 + 1 and rc <= 2048: no sum
+// here leaves int.
+bool wm_window_box(int W, int H, int ic, int jc, int rc, int box[4]) {
+  box[0] = std::max(ic - rc, 0);
+  box[1] = std::max(jc - rc, 0);
+  box[2] = std::min(ic + rc, W - 1);
+  box[3] = std::min(jc + rc, H - 1);
+  return box[0] <= box[2] && box[1] <= box[3];
+}
+
+// both counter blocks to their start values
+int wm_reset_point_counters(kc_worldmap *c) {
+  int init[2 * 5 * kWmPtsStride] = {0};
+  for (int b = 0; b < 2; ++b) {
+    int *blk = init + b * 5 * kWmPtsStride;
+    blk[1 * kWmPtsStride] = blk[3 * kWmPtsStride] = INT_MAX;
+    blk[2 * kWmPtsStride] = blk[4 * kWmPtsStride] = INT_MIN;
+  }
+  c->ptcnt_ready = false;
+  KC_HIP(hipMemcpyAsync(c->d_ptcnt.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));  // `init` is on this frame
+  c->ptcnt_ready = true;
+  return KC_OK;
+}
+
 void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *out) {
   *out = kc_worldmap_match_result{};
   if (g) out->pose = *g;
@@ -643,7 +779,114 @@ void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *
 
 }  // namespace
 
+namespace kc {
+
+int worldmap_view(kc_worldmap *m, WorldMapView *out) {
+  if (!m || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *out = WorldMapView{m->d_cls.p, m->W, m->H, m->res, m->ox, m->oy, m->stream, m->device};
+  return KC_OK;
+}
+
+int worldmap_window(const WorldMapView &v, double x, double y, float max_range, WorldMapWindow *out) {
+  *out = WorldMapWindow{};
+  KC_TRY(wm_window(v.res, v.ox, v.oy, x, y, max_range, &out->ic, &out->jc, &out->rc));
+  int box[4];
+  if (!wm_window_box(v.W, v.H, out->ic, out->jc, out->rc, box)) return KC_OK;
+  // rule 17's cells inside the map, row by row: what the list can hold at most
+  const long long r2 = static_cast<long long>(out->rc) * out->rc;
+  size_t cells = 0;
+  for (int J = box[1]; J <= box[3]; ++J) {
+    const long long dj = static_cast<long long>(J) - out->jc, rest = r2 - dj * dj;
+    long long h = static_cast<long long>(std::sqrt(static_cast<double>(rest)));
+    while (h * h > rest) --h;
+    while ((h + 1) * (h + 1) <= rest) ++h;
+    const long long lo = std::max<long long>(out->ic - h, 0), hi = std::min<long long>(out->ic + h, v.W - 1);
+    if (lo <= hi) cells += static_cast<size_t>(hi - lo + 1);
+  }
+  out->max_points = cells;
+  return KC_OK;
+}
+
+int worldmap_queue_points(const WorldMapView &v, const WorldMapWindow &w, float *xyz, unsigned int *cnt, unsigned int *rearm,
+                          hipStream_t stream) {
+  int box[4];
+  if (!wm_window_box(v.W, v.H, w.ic, w.jc, w.rc, box)) KC_FAIL(KC_ERR_STATE, "an empty window has no launch");
+  WmWindowArgs a{};
+  a.cls = v.cls;
+  a.xyz = xyz;
+  a.cnt = cnt;
+  a.rearm = rearm;
+  a.W = v.W;
+  a.i_lo = box[0];
+  a.j_lo = box[1];
+  a.i_hi = box[2];
+  a.j_hi = box[3];
+  a.ic = w.ic;
+  a.jc = w.jc;
+  a.r2 = static_cast<long long>(w.rc) * w.rc;
+  a.res = static_cast<double>(v.res);
+  a.ox = v.ox;
+  a.oy = v.oy;
+  const dim3 grid((box[2] - box[0]) / kWmLanes + 1, (box[3] - box[1]) / kWmRows + 1), block(kWmLanes, kWmRows);
+  hipLaunchKernelGGL(worldmap_window_points_kernel, grid, block, 0, stream, a);
+  KC_HIP(hipGetLastError());
+  return KC_OK;
+}
+
+}  // namespace kc
+
 extern "C" {
+
+int kc_worldmap_window(float resolution, double origin_x, double origin_y, double x, double y, float max_sensor_range,
+                       int32_t *ic_out, int32_t *jc_out, int32_t *rc_out) {
+  if (!ic_out || !jc_out || !rc_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *ic_out = *jc_out = *rc_out = 0;
+  int ic, jc, rc;
+  KC_TRY(wm_window(resolution, origin_x, origin_y, x, y, max_sensor_range, &ic, &jc, &rc));
+  *ic_out = ic;
+  *jc_out = jc;
+  *rc_out = rc;
+  return KC_OK;
+}
+
+int kc_worldmap_points(kc_worldmap *c, double x, double y, float max_sensor_range, float *xyz_out, size_t cap, size_t *count_out,
+                       int32_t bounds_out[4]) {
+  if (!c || !count_out || !bounds_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  bounds_out[0] = bounds_out[1] = bounds_out[2] = bounds_out[3] = -1;
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c, &v));
+  WorldMapWindow w{};
+  KC_TRY(worldmap_window(v, x, y, max_sensor_range, &w));
+  if (w.max_points == 0) return KC_OK;  // the window misses the map: rule 17
+  KC_HIP(hipSetDevice(c->device));
+  if (xyz_out) KC_TRY(c->d_pts.reserve(3 * w.max_points));
+  KC_TRY(c->d_ptcnt.reserve(2 * 5 * kWmPtsStride));
+  KC_TRY(c->h_ptrec.reserve(5 * kWmPtsStride));
+  if (!c->ptcnt_ready) KC_TRY(wm_reset_point_counters(c));
+  unsigned int *cnt = c->d_ptcnt.p + (c->pt_seq & 1) * 5 * kWmPtsStride;
+  unsigned int *next = c->d_ptcnt.p + ((c->pt_seq + 1) & 1) * 5 * kWmPtsStride;
+  c->ptcnt_ready = false;  // until the read-back below says this launch ran: a failure leaves the counters unknown
+  KC_TRY(worldmap_queue_points(v, w, xyz_out ? c->d_pts.p : nullptr, cnt, next, c->stream));
+  KC_HIP(hipMemcpyAsync(c->h_ptrec.p, cnt, 5 * kWmPtsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  ++c->pt_seq;
+  c->ptcnt_ready = true;
+  const int *r = c->h_ptrec.p;
+  const size_t n = static_cast<size_t>(static_cast<unsigned int>(r[0]));
+  if (n > w.max_points) KC_FAIL(KC_ERR_HIP, "the window's count %zu is above its %zu cells", n, w.max_points);
+  *count_out = n;
+  if (n == 0) return KC_OK;
+  bounds_out[0] = r[1 * kWmPtsStride];
+  bounds_out[1] = r[2 * kWmPtsStride];
+  bounds_out[2] = r[3 * kWmPtsStride];
+  bounds_out[3] = r[4 * kWmPtsStride];
+  if (!xyz_out) return KC_OK;
+  if (cap < n) KC_FAIL(KC_ERR_RANGE, "%zu points do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipMemcpyAsync(xyz_out, c->d_pts.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
 
 int kc_worldmap_check_model(int hit, int miss, int e_min, int e_max, int occ_thr) {
   return wm_check_model(hit, miss, e_min, e_max, occ_thr);

@@ -11,6 +11,7 @@ from attrs import Factory, define, field, validators
 
 import kompass_cpp
 from ..datatypes.laserscan import LaserScanData
+from ..mapping.world_map import cpp_world_map
 from ..models import Robot, RobotCtrlLimits, RobotGeometry, RobotState, RobotType
 from ._base_ import FollowerConfig, FollowerTemplate
 from ._trajectory_ import TrajectoryCostsWeights
@@ -89,7 +90,12 @@ class DWA(FollowerTemplate):
             self._result.is_found = False
             return False
         vel = kompass_cpp.types.Velocity2D(vx=current_state.vx, vy=current_state.vy, omega=current_state.omega)
-        if isinstance(local_map, kompass_cpp.mapping.LocalMapper):
+        world_map = cpp_world_map(local_map)
+        if world_map is not None:
+            # not in the reference: the world map's occupied cells within sensor range of the robot, extracted
+            # where the map lies on the device (DESIGN.md 4.11 rules 16 to 19)
+            sensor = world_map
+        elif isinstance(local_map, kompass_cpp.mapping.LocalMapper):
             # not in the reference: the mapper's last grid is consumed where it
             # lies on the device (OCCUPIED cells -> point list)
             sensor = local_map
@@ -108,7 +114,7 @@ class DWA(FollowerTemplate):
             logging.error("Cannot compute control without sensor data. Provide 'laser_scan' or 'point_cloud' input")
             return False
         try:
-            if debug and not isinstance(sensor, kompass_cpp.mapping.LocalMapper):
+            if debug and not isinstance(sensor, (kompass_cpp.mapping.LocalMapper, kompass_cpp.mapping.WorldMap)):
                 self._planner.debug_velocity_search(vel, sensor, self._config.drop_samples)
             self._result = self._planner.compute_velocity_commands(vel, sensor)
         except Exception as e:  # reference: log and report "no control"

@@ -11,6 +11,7 @@ import numpy as np
 from attrs import asdict, define, field, validators
 
 import kompass_cpp
+from ..mapping.world_map import cpp_world_map
 from ..models import Robot, RobotCtrlLimits, RobotGeometry, RobotState, RobotType
 from ._base_ import FollowerConfig, FollowerTemplate
 
@@ -84,7 +85,11 @@ class PurePursuit(FollowerTemplate):
         self._planner.set_current_velocity(
             kompass_cpp.types.Velocity2D(vx=current_state.vx, vy=current_state.vy, omega=current_state.omega))
         dt = self._control_time_step
-        if kwargs.get("local_map") is not None:
+        world_map = cpp_world_map(kwargs.get("local_map"))
+        if world_map is not None:
+            # not in the reference: the world map's occupied cells within sensor range, extracted on the device
+            self._result = self._planner.execute(dt, world_map)
+        elif kwargs.get("local_map") is not None:
             self._result = self._planner.execute(dt, np.asarray(kwargs["local_map"], dtype=np.float32))
         elif kwargs.get("laser_scan") is not None:
             scan = kwargs["laser_scan"]

@@ -45,6 +45,13 @@ class WorldMapMatch:
                 f"points={self.points}, ratio={self.ratio:.3f}, applied={self.applied})")
 
 
+def cpp_world_map(obj):
+    """The `kompass_cpp.mapping.WorldMap` behind `obj` (this module's `WorldMap`, or the class itself), else None: what
+    the controllers' `loop_step(local_map=...)` looks for."""
+    inner = getattr(obj, "_map", obj)
+    return inner if isinstance(inner, kompass_cpp.mapping.WorldMap) else None
+
+
 class WorldMap:
     def __init__(self, width: int, height: int, resolution: float, origin: Tuple[float, float] = (0.0, 0.0), hit: int = 3,
                  miss: int = 1, e_min: int = -8, e_max: int = 14, occ_thr: int = 1):
@@ -111,6 +118,13 @@ class WorldMap:
 
     def clear(self) -> None:
         self._map.clear()
+
+    def points(self, robot_state, max_range: float) -> np.ndarray:
+        """The occupied cells within max_range metres of robot_state's position as world-frame points, float32 [n, 3]
+        with z = 0, in no particular order (DESIGN.md 4.11 rules 16 to 19): a cloud to show or to hand to a consumer of
+        point clouds.  `DWA.loop_step(local_map=world_map)` and `PurePursuit.loop_step(local_map=world_map)` take the
+        map itself and extract the same list on the device."""
+        return self._map.points(float(robot_state.x), float(robot_state.y), float(max_range))
 
     @property
     def occupancy(self) -> np.ndarray:

@@ -161,6 +161,7 @@ SIGNATURES = {
     "kc_dwa_set_grid_device": (C.c_int, [_vp, C.POINTER(State), _vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                          C.c_float]),
     "kc_dwa_set_grid_from_mapper": (C.c_int, [_vp, C.POINTER(State), _vp, C.c_float]),
+    "kc_dwa_set_worldmap": (C.c_int, [_vp, C.POINTER(State), _vp, C.c_float]),
     "kc_dwa_set_tracked_segment": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _sz, C.c_float]),
     "kc_dwa_set_tracked_segment_xyz": (C.c_int, [_vp, _fp, _fp, _sz, C.c_float]),
     "kc_dwa_rollout": (C.c_int, [_vp, C.POINTER(State), _sz]),
@@ -300,6 +301,10 @@ SIGNATURES = {
     "kc_worldmap_clear": (C.c_int, [_vp]),
     "kc_worldmap_grid_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "kc_worldmap_get": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
+    "kc_worldmap_window": (C.c_int, [C.c_float, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "kc_worldmap_points": (C.c_int, [_vp, C.c_double, C.c_double, C.c_float, C.c_void_p, _sz, C.POINTER(_sz),
+                                     C.POINTER(C.c_int32)]),
     "kc_worldmap_match_check_window": (C.c_int, [C.c_int, C.c_double, C.c_int]),
     "kc_worldmap_match_check_grid": (C.c_int, [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "kc_worldmap_match_rotations": (C.c_int, [C.c_double, C.c_int, C.c_double, C.POINTER(WorldMapRotation), _sz]),
@@ -693,6 +698,13 @@ class DwaContext(_Owner, _Timed):
         """Same, from a MapperContext: the scan may still be in flight (stream-ordered)."""
         st = State(*state)
         _check(lib().kc_dwa_set_grid_from_mapper(self.h, C.byref(st), mapper.h, float(max_sensor_range)))
+
+    def set_worldmap(self, state, worldmap, max_sensor_range=10.0):
+        """The occupied cells of a WorldMapContext within max_sensor_range of (state.x, state.y) -> sensor data, on the
+        device (DESIGN.md 4.11 rules 16 to 19).  Same state as set_points with WorldMapContext.points' list."""
+        st = State(*state)
+        _check(lib().kc_dwa_set_worldmap(self.h, C.byref(st), None if worldmap is None else worldmap.h,
+                                         float(np.float32(max_sensor_range))))
 
     def set_path(self, path_xyz, acc_at_point, total_length):
         """The whole interpolated reference path, resident on the device (once per path)."""
@@ -1379,6 +1391,14 @@ def worldmap_quantise_pose(resolution, origin, x, y, yaw) -> WorldMapPose:
     return p
 
 
+def worldmap_window(resolution, origin, x, y, max_sensor_range):
+    """Rule 16 (host only): the centre cell and the radius in cells of the obstacle window -> (Ic, Jc, Rc)."""
+    ic, jc, rc = C.c_int32(), C.c_int32(), C.c_int32()
+    _check(lib().kc_worldmap_window(float(np.float32(resolution)), float(origin[0]), float(origin[1]), float(x), float(y),
+                                    float(np.float32(max_sensor_range)), C.byref(ic), C.byref(jc), C.byref(rc)))
+    return ic.value, jc.value, rc.value
+
+
 def worldmap_match_check_window(n_yaw, yaw_step, reach):
     """Rule 10's ranges of a match's window (host only); raises ValueError."""
     _check(lib().kc_worldmap_match_check_window(int(n_yaw), float(yaw_step), int(reach)))
@@ -1534,6 +1554,22 @@ class WorldMapContext(_Owner, _StreamOrdered):
 
     def clear(self):
         _check(lib().kc_worldmap_clear(self.h))
+
+    def points(self, x, y, max_sensor_range, cap=None, count_only=False):
+        """Rules 16 to 19: the occupied cells within max_sensor_range of (x, y) as world-frame points, in no particular
+        order -> (xyz float32 [n, 3], (i_min, i_max, j_min, j_max)), the bounds all -1 when n == 0.  count_only: ->
+        (n, bounds) without the list.  cap: the points the output holds (default: as many as there are); IndexError
+        when there are more."""
+        n, b = _sz(0), (C.c_int32 * 4)()
+        args = (self.h, float(x), float(y), float(np.float32(max_sensor_range)))
+        if count_only or cap is None:
+            _check(lib().kc_worldmap_points(*args, None, 0, C.byref(n), b))
+            if count_only:
+                return int(n.value), tuple(int(v) for v in b)
+            cap = int(n.value)
+        out = np.empty((int(cap), 3), np.float32)
+        _check(lib().kc_worldmap_points(*args, out.ctypes.data if out.size else None, int(cap), C.byref(n), b))
+        return out[:int(n.value)], tuple(int(v) for v in b)
 
     def grid_device_ptr(self) -> int:
         """The cls plane on the device: int8, (width, height), what PlannerContext.set_grid_device(ptr, width, height,

@@ -17,7 +17,19 @@ whole call (four launches and the read-back, host clock), the four launches by H
 with the events on), and the numpy statement of the rules (tests/worldmap_match_ref.py, one CPU thread: the yardstick's
 cost, not a compiled CPU implementation), whose table and record the device's are compared with once.
 
-  python tools/worldmap_time.py --match [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --match [--reps 30] [--warmup 3]
+
+--points times the obstacle hand-off instead (rules 16 to 19): the same world holding what the 400 x 400 local grid saw,
+the robot in the middle, max_sensor_range 10 m (Rc = 200).  One JSON line with
+  (a) kc_dwa_set_worldmap: the extraction on the controller's stream and the sensor build behind it;
+  (b) kc_worldmap_points: the list into host memory;
+  (c) the route without it: kc_worldmap_get of the class plane, numpy.nonzero + rule 18 in numpy over the window,
+      kc_dwa_set_points, each timed on its own;
+  (d) kc_dwa_set_grid_from_mapper on the local grid, the yardstick for a hand-off on the device.
+Every repetition ends with a device synchronisation inside the timed span, so the controller's entries are timed with
+the sensor build they queue.  The lists of (a) to (c) are compared with the statement once.
+
+  python tools/worldmap_time.py --points [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -34,8 +46,9 @@ sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
 import kompass_hip as kh  # noqa: E402
 import synthetic as syn  # noqa: E402
 import worldmap_match_ref as mref  # noqa: E402
+import worldmap_points_ref as pref  # noqa: E402
 import worldmap_ref as ref  # noqa: E402
-from helpers import DeviceArray, hip_runtime  # noqa: E402
+from helpers import DeviceArray, hip_context, hip_runtime  # noqa: E402
 
 W, H, RES, ORIGIN = 2004, 1204, 0.05, (-50.0, -30.0)
 GH = GW = 400
@@ -97,17 +110,89 @@ def match_leg(args):
             print(json.dumps(line), flush=True)
 
 
+def points_leg(args):
+    hip = hip_runtime()
+    ang, rng = syn.dense_scan(2048, 1.2)
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r, ORIGIN[1] + (H // 2) * r)   # on a cell centre: the world holds the local grid's cells
+    max_range = 10.0
+    inp = syn.make_controller_inputs("cfg2", seed=0, scale=0.25)
+    st = centre + (0.0, 0.0)
+
+    def synced(fn):
+        def run():
+            fn()
+            assert hip.hipDeviceSynchronize() == 0
+        return run
+
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as wm:
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        wm.update_from_mapper(mapper, centre + (0.0,))
+        cls = wm.planes()[0]
+        want, n, bounds = pref.worldmap_points_ref(cls, RES, ORIGIN, centre[0], centre[1], max_range)
+        got, got_bounds = wm.points(centre[0], centre[1], max_range)
+        assert got_bounds == bounds and pref.sort_points(got, RES, ORIGIN).tobytes() == want.tobytes(), "device and statement disagree"
+        ic, jc, rc = kh.worldmap_window(RES, ORIGIN, centre[0], centre[1], max_range)
+        inp["points"] = want
+        ctx = hip_context(kh, inp)
+        host_cls = np.empty((W, H), np.int8, order="F")
+        lists = {}
+
+        def get():
+            kh._check(kh.lib().kc_worldmap_get(wm.h, host_cls.ctypes.data, None, host_cls.size))
+
+        def numpy_list():
+            i0, i1, j0, j1 = max(ic - rc, 0), min(ic + rc, W - 1), max(jc - rc, 0), min(jc + rc, H - 1)
+            box = host_cls[i0:i1 + 1, j0:j1 + 1]
+            di = np.arange(i0, i1 + 1, dtype=np.int64)[:, None] - ic
+            dj = np.arange(j0, j1 + 1, dtype=np.int64)[None, :] - jc
+            ii, jj = np.nonzero((box == ref.OCCUPIED) & (di * di + dj * dj <= rc * rc))
+            lists["host"] = pref.cell_points(RES, ORIGIN, ii + i0, jj + j0)
+
+        get()
+        numpy_list()
+        assert pref.sort_points(lists["host"], RES, ORIGIN).tobytes() == want.tobytes(), "host route and statement disagree"
+        mapper_points = int((np.asarray(mapper.scan_to_grid(ang, rng)) == ref.OCCUPIED).sum())
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        line = {"world": [W, H], "local": [GH, GW], "max_sensor_range": max_range, "radius_cells": rc, "points": n,
+                "mapper_points": mapper_points, "reps": args.reps, "warmup": args.warmup}
+        legs = [("a_dwa_set_worldmap_ms", lambda: ctx.set_worldmap(st, wm, max_range)),
+                ("b_worldmap_points_to_host_ms", lambda: wm.points(centre[0], centre[1], max_range, cap=n)),
+                ("c1_worldmap_get_cls_ms", get),
+                ("c2_numpy_nonzero_rule18_ms", numpy_list),
+                ("c3_dwa_set_points_ms", lambda: ctx.set_points(st, lists["host"], max_range)),
+                ("d_dwa_set_grid_from_mapper_ms", lambda: ctx.set_grid_from_mapper(st, mapper, max_range))]
+        for name, fn in legs:
+            line[name] = timed(synced(fn), args.reps, args.warmup)
+        line["c_total_ms"] = round(sum(line[k][0] for k in ("c1_worldmap_get_cls_ms", "c2_numpy_nonzero_rule18_ms", "c3_dwa_set_points_ms")), 4)
+        # a second pass over (a) and (d) in alternation: their difference is judged against (d)'s own spread in this run
+        alt = {"a": [], "d": []}
+        for k in range(args.warmup + args.reps):
+            for key, fn in (("a", legs[0][1]), ("d", legs[5][1])):
+                t0 = time.perf_counter()
+                synced(fn)()
+                if k >= args.warmup:
+                    alt[key].append((time.perf_counter() - t0) * 1e3)
+        line["a_alternating_ms"], line["d_alternating_ms"] = spread(alt["a"]), spread(alt["d"])
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--yaws", default="0,0.3,0.785398,1.570796,-2.5")
     ap.add_argument("--match", action="store_true", help="time the correlative match instead of the update")
+    ap.add_argument("--points", action="store_true", help="time the obstacle hand-off to the controller instead")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
     if args.match:
         return match_leg(args)
+    if args.points:
+        return points_leg(args)
     hip = hip_runtime()
     ang, rng = syn.dense_scan(2048, 1.2)                      # ranges 3.6 .. 8.4 m in a 20 m window
     pose_xy = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021)
