@@ -1022,9 +1022,7 @@ PYBIND11_MODULE(kompass_cpp, m) {
            }, py::arg("mapper"), py::arg("x"), py::arg("y"), py::arg("yaw"),
            "Fuse the mapper's last grid where it lies on the device; (x, y, yaw): the robot's pose in the world.  -> changed cells")
       .def("update", [](Mapping::WorldMap &m, const py::array &grid, double x, double y, double yaw) {
-             if (grid.ndim() != 2 || grid.dtype().num() != py::dtype::of<int32_t>().num())
-               throw std::invalid_argument("the local grid must be a 2-D int32 array (grid_height, grid_width)");
-             const auto g = py::array_t<int32_t, py::array::f_style>::ensure(grid);
+             const auto g = worldMapLocalGrid(grid);
              const int32_t *d = g.data();
              const int gh = static_cast<int>(g.shape(0)), gw = static_cast<int>(g.shape(1));
              py::gil_scoped_release nogil;

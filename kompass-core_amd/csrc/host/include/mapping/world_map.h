@@ -99,12 +99,18 @@ class WorldMap {
   uint64_t match_count_ = 0;
   int match_rot_ = 0, match_side_ = 0;  // the last match's table: rotations, candidates a side
 
-  struct Window {
-    kc_worldmap_pose guess;
-    std::vector<kc_worldmap_rotation> rot;
+  // Where a local grid comes from: the mapper's last grid where it lies, or a grid on the host or on the device with its
+  // shape and the mapper's central cell.  Every public update / match names one and goes through updateFrom / matchFrom.
+  struct GridSource {
+    enum Kind { Mapper, Host, Device } kind;
+    const LocalMapper *mapper;
+    const int32_t *grid;
+    int height, width, central_i, central_j;
+    GridSource(const LocalMapper &m) : kind(Mapper), mapper(&m), grid(nullptr), height(0), width(0), central_i(0), central_j(0) {}
+    GridSource(Kind k, const int32_t *grid, int grid_height, int grid_width);
   };
-  Window window(double x, double y, double yaw, int n_yaw, double yaw_step, int reach) const;
-  Match finish(const kc_worldmap_match_result &r, double x, double y, double yaw, int n_yaw, double yaw_step, int reach);
+  uint32_t updateFrom(const GridSource &s, const kc_worldmap_pose &pose);
+  Match matchFrom(const GridSource &s, double x, double y, double yaw, int n_yaw, double yaw_step, int reach);
 };
 
 }  // namespace Mapping

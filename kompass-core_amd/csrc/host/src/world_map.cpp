@@ -31,37 +31,51 @@ kc_worldmap_pose WorldMap::quantisePose(float resolution, double origin_x, doubl
   return p;
 }
 
-uint32_t WorldMap::update(const LocalMapper &mapper, double x, double y, double yaw) {
-  const kc_worldmap_pose p = quantisePose(res_, ox_, oy_, x, y, yaw);
-  hip::check(kc_worldmap_update_from_mapper(ctx_.get(), mapper.hipContext(), &p, &last_));
+// the mapper's central cell (local_mapper.h)
+WorldMap::GridSource::GridSource(Kind k, const int32_t *g, int grid_height, int grid_width)
+    : kind(k), mapper(nullptr), grid(g), height(grid_height), width(grid_width), central_i(grid_height / 2 - 1),
+      central_j(grid_width / 2 - 1) {}
+
+uint32_t WorldMap::updateFrom(const GridSource &s, const kc_worldmap_pose &p) {
+  if (s.kind == GridSource::Mapper) {
+    hip::check(kc_worldmap_update_from_mapper(ctx_.get(), s.mapper->hipContext(), &p, &last_));
+  } else {
+    const auto entry = s.kind == GridSource::Host ? kc_worldmap_update_host : kc_worldmap_update_device;
+    hip::check(entry(ctx_.get(), s.grid, s.height, s.width, s.central_i, s.central_j, res_, &p, &last_));
+  }
   return last_.changed;
+}
+
+uint32_t WorldMap::update(const LocalMapper &mapper, double x, double y, double yaw) {
+  return updateFrom(mapper, quantisePose(res_, ox_, oy_, x, y, yaw));
 }
 
 uint32_t WorldMap::update(const int32_t *grid, int grid_height, int grid_width, double x, double y, double yaw) {
-  const kc_worldmap_pose p = quantisePose(res_, ox_, oy_, x, y, yaw);
-  hip::check(kc_worldmap_update_host(ctx_.get(), grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_, &p,
-                                     &last_));
-  return last_.changed;
+  return updateFrom({GridSource::Host, grid, grid_height, grid_width}, quantisePose(res_, ox_, oy_, x, y, yaw));
 }
 
 uint32_t WorldMap::updateOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw) {
-  const kc_worldmap_pose p = quantisePose(res_, ox_, oy_, x, y, yaw);
-  hip::check(kc_worldmap_update_device(ctx_.get(), dev_grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_,
-                                       &p, &last_));
-  return last_.changed;
+  return updateFrom({GridSource::Device, dev_grid, grid_height, grid_width}, quantisePose(res_, ox_, oy_, x, y, yaw));
 }
 
-WorldMap::Window WorldMap::window(double x, double y, double yaw, int n_yaw, double yaw_step, int reach) const {
+uint32_t WorldMap::updateAt(const LocalMapper &mapper, const kc_worldmap_pose &pose) { return updateFrom(mapper, pose); }
+
+uint32_t WorldMap::updateAt(const int32_t *grid, int grid_height, int grid_width, const kc_worldmap_pose &pose) {
+  return updateFrom({GridSource::Host, grid, grid_height, grid_width}, pose);
+}
+
+WorldMap::Match WorldMap::matchFrom(const GridSource &s, double x, double y, double yaw, int n_yaw, double yaw_step, int reach) {
   hip::check(kc_worldmap_match_check_window(n_yaw, yaw_step, reach));
-  Window w;
-  w.guess = quantisePose(res_, ox_, oy_, x, y, yaw);
-  w.rot.resize(static_cast<size_t>(2 * n_yaw + 1));
-  hip::check(kc_worldmap_match_rotations(yaw, n_yaw, yaw_step, w.rot.data(), w.rot.size()));
-  return w;
-}
-
-WorldMap::Match WorldMap::finish(const kc_worldmap_match_result &r, double x, double y, double yaw, int n_yaw, double yaw_step,
-                                 int reach) {
+  const kc_worldmap_pose guess = quantisePose(res_, ox_, oy_, x, y, yaw);
+  std::vector<kc_worldmap_rotation> rot(static_cast<size_t>(2 * n_yaw + 1));
+  hip::check(kc_worldmap_match_rotations(yaw, n_yaw, yaw_step, rot.data(), rot.size()));
+  kc_worldmap_match_result r{};
+  if (s.kind == GridSource::Mapper) {
+    hip::check(kc_worldmap_match_from_mapper(ctx_.get(), s.mapper->hipContext(), &guess, rot.data(), n_yaw, reach, &r));
+  } else {
+    const auto entry = s.kind == GridSource::Host ? kc_worldmap_match_host : kc_worldmap_match_device;
+    hip::check(entry(ctx_.get(), s.grid, s.height, s.width, s.central_i, s.central_j, res_, &guess, rot.data(), n_yaw, reach, &r));
+  }
   ++match_count_;
   match_rot_ = 2 * n_yaw + 1;
   match_side_ = 2 * reach + 1;
@@ -83,45 +97,23 @@ WorldMap::Match WorldMap::finish(const kc_worldmap_match_result &r, double x, do
 }
 
 WorldMap::Match WorldMap::match(const LocalMapper &mapper, double x, double y, double yaw, int n_yaw, double yaw_step, int reach) {
-  const Window w = window(x, y, yaw, n_yaw, yaw_step, reach);
-  kc_worldmap_match_result r{};
-  hip::check(kc_worldmap_match_from_mapper(ctx_.get(), mapper.hipContext(), &w.guess, w.rot.data(), n_yaw, reach, &r));
-  return finish(r, x, y, yaw, n_yaw, yaw_step, reach);
+  return matchFrom(mapper, x, y, yaw, n_yaw, yaw_step, reach);
 }
 
 WorldMap::Match WorldMap::match(const int32_t *grid, int grid_height, int grid_width, double x, double y, double yaw, int n_yaw,
                                 double yaw_step, int reach) {
-  const Window w = window(x, y, yaw, n_yaw, yaw_step, reach);
-  kc_worldmap_match_result r{};
-  hip::check(kc_worldmap_match_host(ctx_.get(), grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_,
-                                    &w.guess, w.rot.data(), n_yaw, reach, &r));
-  return finish(r, x, y, yaw, n_yaw, yaw_step, reach);
+  return matchFrom({GridSource::Host, grid, grid_height, grid_width}, x, y, yaw, n_yaw, yaw_step, reach);
 }
 
 WorldMap::Match WorldMap::matchOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw,
                                         int n_yaw, double yaw_step, int reach) {
-  const Window w = window(x, y, yaw, n_yaw, yaw_step, reach);
-  kc_worldmap_match_result r{};
-  hip::check(kc_worldmap_match_device(ctx_.get(), dev_grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_,
-                                      &w.guess, w.rot.data(), n_yaw, reach, &r));
-  return finish(r, x, y, yaw, n_yaw, yaw_step, reach);
+  return matchFrom({GridSource::Device, dev_grid, grid_height, grid_width}, x, y, yaw, n_yaw, yaw_step, reach);
 }
 
 std::vector<uint32_t> WorldMap::matchScores() const {
   std::vector<uint32_t> out(static_cast<size_t>(match_rot_) * static_cast<size_t>(match_side_) * static_cast<size_t>(match_side_));
   hip::check(kc_worldmap_match_scores(ctx_.get(), out.data(), out.size()));
   return out;
-}
-
-uint32_t WorldMap::updateAt(const LocalMapper &mapper, const kc_worldmap_pose &pose) {
-  hip::check(kc_worldmap_update_from_mapper(ctx_.get(), mapper.hipContext(), &pose, &last_));
-  return last_.changed;
-}
-
-uint32_t WorldMap::updateAt(const int32_t *grid, int grid_height, int grid_width, const kc_worldmap_pose &pose) {
-  hip::check(kc_worldmap_update_host(ctx_.get(), grid, grid_height, grid_width, grid_height / 2 - 1, grid_width / 2 - 1, res_, &pose,
-                                     &last_));
-  return last_.changed;
 }
 
 void WorldMap::clear() {

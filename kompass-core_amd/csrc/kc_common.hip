@@ -27,9 +27,9 @@ int open_device_stream(int device, hipStream_t *stream) {
   return KC_OK;
 }
 
-// Every kc_*_destroy calls this (and ends its other streams and events) BEFORE it deletes the context: the
-// context's DevBuf / PinBuf / Timing members free themselves in its destructor, and nothing queued may still
-// read or write them then.
+// Every kc_*_destroy calls this (and ends its other streams) BEFORE it deletes the context: the context's
+// DevBuf / PinBuf / OrderEvent / Timing members free themselves in its destructor, with this device current, and
+// nothing queued may still read or write them then.
 void close_device_stream(int device, hipStream_t *stream) {
   // (a context exists only once its stream is open, so the device is current for whatever its destroy ends next;
   // kc_depth, which opens lazily, has nothing on the device while it has no stream)
@@ -49,6 +49,14 @@ int stream_wait_for(int device, hipStream_t own, void *other) {
   if (rc == hipSuccess) rc = hipStreamWaitEvent(own, e, 0);
   (void)hipEventDestroy(e);  // released once the wait is satisfied
   KC_HIP(rc);
+  return KC_OK;
+}
+
+int stream_wait_through(OrderEvent &ev, hipStream_t own, hipStream_t producer) {
+  if (own == producer) return KC_OK;
+  if (!ev.e) KC_HIP(hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+  KC_HIP(hipEventRecord(ev.e, producer));
+  KC_HIP(hipStreamWaitEvent(own, ev.e, 0));
   return KC_OK;
 }
 

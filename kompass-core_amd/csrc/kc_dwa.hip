@@ -612,10 +612,6 @@ void kc_dwa_destroy(kc_dwa *c) {
     e = hipEventDestroy(c->aux_join);
     (void)e;
   }
-  if (c->grid_ready) {
-    hipError_t e = hipEventDestroy(c->grid_ready);
-    (void)e;
-  }
   delete c;
 }
 

@@ -79,7 +79,7 @@ struct kc_dwa {
   DevBuf<unsigned int> d_gridcnt;
   PinBuf<long long> h_gridrec;  // {seq, count, imin, imax, jmin, jmax}
   long long grid_seq = 0;
-  hipEvent_t grid_ready = nullptr;  // mapper stream -> this stream
+  OrderEvent grid_ready;  // a mapper's or a world map's stream -> this stream
   bool device_sensor = true;            // KC_SENSOR_HOST=1 turns the device-side update off
   long sensor_stamp_calls = 0;
   bool sensor_fused_ok = false;         // sensor_fused_kernel may take kSensorFusedLds

@@ -1323,6 +1323,13 @@ int arm_list_counters(kc_dwa *c) {
   return KC_OK;
 }
 
+// The sensor state of a list without a point: no voxel, no obstacle
+static int set_empty_list(kc_dwa *c) {
+  build_host_lists(c, nullptr, 0);
+  KC_TRY(upload_voxels(c));
+  return upload_obstacles(c, 0);
+}
+
 // Behind an extraction queued on the controller's stream into d_raw and d_gridcnt: publish the count and the index
 // bounds, wait for them, then the sensor update of that list.  bounds_of(rec, lo, hi): the list's float bounds from the
 // record's index bounds rec[2 .. 5] (the hand-off knows its cell -> point rule; the host never sees a point).
@@ -1346,11 +1353,7 @@ int finish_list_handoff(kc_dwa *c, BoundsOf bounds_of) {
     if (*p != seq) KC_FAIL(KC_ERR_HIP, "the grid hand-off kernels did not report");
   }
   const size_t n = static_cast<size_t>(c->h_gridrec.p[1]);
-  if (n == 0) {
-    build_host_lists(c, nullptr, 0);
-    KC_TRY(upload_voxels(c));
-    return upload_obstacles(c, 0);
-  }
+  if (n == 0) return set_empty_list(c);
   float lo[3], hi[3];
   bounds_of(c->h_gridrec.p, lo, hi);
   bool done = false;
@@ -1426,12 +1429,7 @@ int kc_dwa_set_grid_from_mapper(kc_dwa *c, const kc_state *st, kc_mapper *m, flo
   if (v.device != c->prm.device)
     KC_FAIL(KC_ERR_INVALID, "mapper on device %d, controller on device %d", v.device, c->prm.device);
   KC_TRY(use_device(c));
-  if (v.stream != c->stream) {
-    // the controller's stream waits for the scan; the host does not
-    if (!c->grid_ready) KC_HIP(hipEventCreateWithFlags(&c->grid_ready, hipEventDisableTiming));
-    KC_HIP(hipEventRecord(c->grid_ready, v.stream));
-    KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
-  }
+  KC_TRY(kc::stream_wait_through(c->grid_ready, c->stream, v.stream));  // for the scan; the host does not wait
   return kc_dwa_set_grid_device(c, st, v.grid, v.H, v.W, v.res, v.c0, v.c1, max_range);
 }
 
@@ -1447,19 +1445,10 @@ int kc_dwa_set_worldmap(kc_dwa *c, const kc_state *st, kc_worldmap *map, float m
   KC_TRY(kc::worldmap_window(v, st->x, st->y, max_range, &w));
   KC_TRY(use_device(c));
   KC_TRY(begin_device_list(c, st, max_range));
-  if (w.max_points == 0) {  // the window misses the map: the empty list, no launch
-    build_host_lists(c, nullptr, 0);
-    KC_TRY(upload_voxels(c));
-    return upload_obstacles(c, 0);
-  }
+  if (w.max_points == 0) return set_empty_list(c);  // the window misses the map: no launch
   KC_TRY(c->d_raw.reserve(3 * w.max_points + 16));
   KC_TRY(arm_list_counters(c));
-  if (v.stream != c->stream) {
-    // the controller's stream waits for the map's writes; the host does not
-    if (!c->grid_ready) KC_HIP(hipEventCreateWithFlags(&c->grid_ready, hipEventDisableTiming));
-    KC_HIP(hipEventRecord(c->grid_ready, v.stream));
-    KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
-  }
+  KC_TRY(kc::stream_wait_through(c->grid_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
   KC_TRY(c->timing.start("worldmap_window_points_kernel", c->stream));
   KC_TRY(kc::worldmap_queue_points(v, w, c->d_raw.p, c->d_gridcnt.p, nullptr, c->stream));
   KC_TRY(c->timing.stop(c->stream));

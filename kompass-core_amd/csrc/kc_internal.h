@@ -107,6 +107,57 @@ static_assert(!std::is_copy_constructible<PinBuf<int>>::value && !std::is_copy_a
                   std::is_nothrow_move_assignable<PinBuf<int>>::value,
               "PinBuf owns pinned memory: move-only, and a std::vector of it grows by move");
 
+// ---- an event that orders one stream behind another ---------------------------
+// Created by its first stream_wait_through, without timing, and kept.  Move-only; destroyed with the context it is a
+// member of, whose kc_*_destroy has made the device current by then (as for the buffers).
+struct OrderEvent {
+  hipEvent_t e = nullptr;
+  OrderEvent() = default;
+  OrderEvent(OrderEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+  ~OrderEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// ---- a flip-flop record: a launch's few result words without a launch to reset them (kc_worldmap.hip (c), (f)) ----
+// Two device blocks of start.size() words: call n works in block n & 1, its launch puts the other back to the start values,
+// commit() reads the block back.  ready (both blocks hold their start values) is dropped by begin() and raised by
+// commit(): a call that fails in between makes the next begin() arm the blocks again.
+struct FlipRecord {
+  std::vector<int> start;      // one block's start values
+  DevBuf<int> d;
+  PinBuf<int> h;               // the block of the last commit()
+  unsigned long long seq = 0;  // calls committed
+  bool ready = false;
+  int *cur = nullptr;          // the block of the call between begin() and commit()
+
+  int arm(hipStream_t s) {
+    ready = false;
+    KC_TRY(d.reserve(2 * start.size()));
+    KC_TRY(h.reserve(start.size()));
+    for (size_t b = 0; b < 2; ++b)
+      KC_HIP(hipMemcpyAsync(d.p + b * start.size(), start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    KC_HIP(hipStreamSynchronize(s));
+    ready = true;
+    return KC_OK;
+  }
+  // -> cur, this call's block, and *rearm, the one its launch puts back
+  int begin(hipStream_t s, int **rearm) {
+    if (!ready) KC_TRY(arm(s));
+    cur = d.p + (seq & 1) * start.size();
+    *rearm = d.p + (~seq & 1) * start.size();
+    ready = false;
+    return KC_OK;
+  }
+  int commit(hipStream_t s) {
+    KC_HIP(hipMemcpyAsync(h.p, cur, start.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    KC_HIP(hipStreamSynchronize(s));
+    ++seq;
+    ready = true;
+    return KC_OK;
+  }
+};
+
 // ---- per-kernel HIP-event timing on the launch stream ----------------------
 // (owns its events: move-only, the destructor destroys them)
 struct Timing {
@@ -211,6 +262,9 @@ int open_device_stream(int device, hipStream_t *stream);
 void close_device_stream(int device, hipStream_t *stream);
 // `own` waits for everything queued on `other` so far (a foreign stream of the same process)
 int stream_wait_for(int device, hipStream_t own, void *other);
+// The same between two contexts' streams through the waiting context's cached event, its device current; the host does
+// not wait.  Nothing to do when both are one stream.
+int stream_wait_through(OrderEvent &ev, hipStream_t own, hipStream_t producer);
 // Memory a caller passes as "on the device" is read by kernels in place: [ptr + lo_bytes, ptr + hi_bytes) must
 // lie inside one allocation of `device`'s memory and ptr % align == 0.  KC_ERR_INVALID otherwise, with `what`
 // (the noun: "cloud", "grid", "frame") in the message, and before any read.

@@ -16,7 +16,7 @@
 //      The box is a launch bound, not part of the rule: every lane runs the full test of rule 4.
 //  (c) result record.  A wavefront counts its class changes by ballot + popcount and adds them with one atomic;
 //      lanes that changed their class fold their cell into the box by atomic min / max (the wavefront's extremes,
-//      one lane each).  Two records alternate: update n accumulates into record n & 1 and puts record (n + 1) & 1
+//      one lane each).  Two records alternate (FlipRecord, kc_internal.h): update n accumulates into record n & 1 and puts record (n + 1) & 1
 //      back to its start values, which no lane of this launch reads, so an update is one launch plus the read-back
 //      of five words.
 //  (d) prior / clear.  worldmap_prior_kernel owns dwords by flat index (the planes start at an allocation, so cells
@@ -410,17 +410,14 @@ using namespace kc;
 struct kc_worldmap {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t grid_ready = nullptr;  // the mapper's scan, for update_from_mapper
+  OrderEvent grid_ready;  // a mapper's scan, for the grids read where the mapper left them
   int W = 0, H = 0;
   float res = 0.0f;
   double ox = 0.0, oy = 0.0;
   WmModel m = {3, 1, -8, 14, 1};
   DevBuf<int8_t> d_evidence, d_cls;
   DevBuf<int32_t> d_stage;   // a host grid (local, or an int32 prior) on its way to a kernel
-  DevBuf<int> d_rec;         // two records of kWmRecWords
-  PinBuf<int> h_rec;
-  unsigned long long seq = 0;  // updates launched: record seq & 1 is the next one's
-  bool rec_ready = false;      // both records hold their start values
+  FlipRecord rec;            // the update's: kWmRecWords a block
   // match: scratch grown on demand and kept
   DevBuf<uint8_t> d_weight;    // rule 12 over the scratch plane
   DevBuf<uint32_t> d_points;   // packed (a, b), at most one a local cell
@@ -431,13 +428,24 @@ struct kc_worldmap {
   Timing match_time;               // weight, points, score, pick
   // obstacle list (rules 16 to 19): scratch grown on demand and kept
   DevBuf<float> d_pts;             // the list of the last kc_worldmap_points
-  DevBuf<unsigned int> d_ptcnt;    // two counter blocks of 5 lines: call n counts in block n & 1 and re-arms the other
-  PinBuf<int> h_ptrec;
-  unsigned long long pt_seq = 0;
-  bool ptcnt_ready = false;        // both blocks hold their start values
+  FlipRecord pts_rec;              // the list's counters: 5 lines of kWmPtsStride words a block
 };
 
 namespace {
+
+// A local grid, [gh x gw] column-major; from wm_resolve, p is on the device and complete in the stream's order
+struct LocalGrid {
+  const int32_t *p;
+  int gh, gw, c0, c1;
+  float res;
+};
+
+// Where a call's local grid comes from: the caller's description with p on the host or the device, or a mapper's view
+struct GridSource {
+  enum Kind { Host, Device, Mapper } kind;
+  LocalGrid grid;
+  kc_mapper *mapper;
+};
 
 int wm_check_model(int hit, int miss, int e_min, int e_max, int occ_thr) {
   if (hit < 1 || hit > 127 || miss < 1 || miss > 127)
@@ -484,12 +492,13 @@ unsigned wm_blocks_for(long long work) {
   return static_cast<unsigned>(std::max<long long>(1, std::min<long long>(kWmMaxBlocks, (work + kWmBlock - 1) / kWmBlock)));
 }
 
-int wm_reset_records(kc_worldmap *c) {
-  const int init[2 * kWmRecWords] = {0, INT_MAX, INT_MAX, -1, -1, 0, INT_MAX, INT_MAX, -1, -1};
-  c->rec_ready = false;
-  KC_HIP(hipMemcpyAsync(c->d_rec.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));  // `init` is on this frame
-  c->rec_ready = true;
+// The launch of one lane a cell over an inclusive box of cells: kWmLanes cells along I and kWmRows rows a workgroup
+dim3 wm_box_grid(const int box[4]) { return dim3((box[2] - box[0]) / kWmLanes + 1, (box[3] - box[1]) / kWmRows + 1); }
+
+// `host` (nbytes of a local grid or a prior) into d_stage, in the order of the context's stream
+int wm_stage(kc_worldmap *c, const void *host, size_t nbytes) {
+  KC_TRY(c->d_stage.reserve((nbytes + 3) / 4));
+  KC_HIP(hipMemcpyAsync(c->d_stage.p, host, nbytes, hipMemcpyHostToDevice, c->stream));
   return KC_OK;
 }
 
@@ -545,45 +554,66 @@ bool wm_box(const kc_worldmap *c, const kc_worldmap_pose *p, int gh, int gw, int
   return true;
 }
 
-// dev: the local grid on the context's device, complete in the order of the context's stream
-int wm_update(kc_worldmap *c, const int32_t *dev, int gh, int gw, int c0, int c1, const kc_worldmap_pose *p,
-              kc_worldmap_result *out) {
+// The one way a local grid reaches a kernel.  Host work first: a mapper's view (and that it lives on this device), then
+// check(grid), the operation's own refusals; only then the device: a host grid is staged, a device grid must lie inside
+// one allocation, a mapper's grid is read where it lies once the context's stream has waited for the scan.
+template <typename Check>
+int wm_resolve(kc_worldmap *c, const GridSource &s, Check check, LocalGrid *g) {
+  MapperView v{};
+  *g = s.grid;
+  if (s.kind == GridSource::Mapper) {
+    KC_TRY(mapper_view(s.mapper, &v));
+    if (v.device != c->device) KC_FAIL(KC_ERR_INVALID, "mapper on device %d, world map on device %d", v.device, c->device);
+    *g = LocalGrid{v.grid, v.H, v.W, v.c0, v.c1, v.res};
+  }
+  KC_TRY(check(*g));
+  KC_HIP(hipSetDevice(c->device));
+  const size_t nbytes = static_cast<size_t>(g->gh) * static_cast<size_t>(g->gw) * sizeof(int32_t);
+  if (s.kind == GridSource::Mapper) return stream_wait_through(c->grid_ready, c->stream, v.stream);  // the host does not wait
+  if (s.kind == GridSource::Device)
+    return check_device_range(c->device, g->p, 0, static_cast<long long>(nbytes), sizeof(int32_t), "grid");
+  KC_TRY(wm_stage(c, g->p, nbytes));
+  g->p = c->d_stage.p;
+  return KC_OK;
+}
+
+// Check order: the grid, the pose, then the device
+int wm_update(kc_worldmap *c, const GridSource &s, const kc_worldmap_pose *p, kc_worldmap_result *out) {
+  LocalGrid g{};
+  KC_TRY(wm_resolve(c, s, [&](const LocalGrid &l) {
+    KC_TRY(wm_check_grid(c->res, l.gh, l.gw, l.c0, l.c1, l.res));
+    return wm_check_pose(p);
+  }, &g));
   *out = kc_worldmap_result{0, -1, -1, -1, -1};
   int box[4];
-  if (!wm_box(c, p, gh, gw, c0, c1, box)) {
+  if (!wm_box(c, p, g.gh, g.gw, g.c0, g.c1, box)) {
     KC_HIP(hipStreamSynchronize(c->stream));  // nothing to do, but the grid is not read after the call returns
     return KC_OK;
   }
-  if (!c->rec_ready) KC_TRY(wm_reset_records(c));
   WmUpdateArgs a{};
-  a.local = dev;
+  KC_TRY(c->rec.begin(c->stream, &a.rec_next));
+  a.rec = c->rec.cur;
+  a.local = g.p;
   a.evidence = c->d_evidence.p;
   a.cls = c->d_cls.p;
-  a.rec = c->d_rec.p + (c->seq & 1) * kWmRecWords;
-  a.rec_next = c->d_rec.p + ((c->seq + 1) & 1) * kWmRecWords;
   a.tx = p->tx;
   a.ty = p->ty;
   a.cq = p->cq;
   a.sq = p->sq;
   a.W = c->W;
-  a.gh = gh;
-  a.gw = gw;
-  a.c0 = c0;
-  a.c1 = c1;
+  a.gh = g.gh;
+  a.gw = g.gw;
+  a.c0 = g.c0;
+  a.c1 = g.c1;
   a.i_lo = box[0];
   a.j_lo = box[1];
   a.i_hi = box[2];
   a.j_hi = box[3];
   a.m = c->m;
-  const dim3 grid((box[2] - box[0]) / kWmLanes + 1, (box[3] - box[1]) / kWmRows + 1), block(kWmLanes, kWmRows);
-  c->rec_ready = false;  // until the read-back below says this launch ran: a failure leaves the records unknown
-  hipLaunchKernelGGL(worldmap_update_kernel, grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(worldmap_update_kernel, wm_box_grid(box), dim3(kWmLanes, kWmRows), 0, c->stream, a);
   KC_HIP(hipGetLastError());
-  KC_HIP(hipMemcpyAsync(c->h_rec.p, a.rec, kWmRecWords * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));
-  ++c->seq;
-  c->rec_ready = true;
-  const int *r = c->h_rec.p;
+  KC_TRY(c->rec.commit(c->stream));
+  const int *r = c->rec.h.p;
   out->changed = static_cast<uint32_t>(r[0]);
   if (r[0] != 0) {
     out->i_min = r[1];
@@ -641,9 +671,14 @@ void wm_launch_score(kc_worldmap *c, const WmScoreArgs &a, dim3 grid) {
   hipLaunchKernelGGL(worldmap_score_kernel<M>, grid, dim3(kWmBlock), 0, c->stream, a);
 }
 
-// dev: the local grid on the context's device, complete in the order of the context's stream
-int wm_match(kc_worldmap *c, const int32_t *dev, int gh, int gw, int c0, int c1, const kc_worldmap_pose *g,
-             const kc_worldmap_rotation *rot, int K, int S, kc_worldmap_match_result *out) {
+// Check order: the window, the guess and the rotation table, the grid, then the device
+int wm_match(kc_worldmap *c, const GridSource &src, const kc_worldmap_pose *g, const kc_worldmap_rotation *rot, int K, int S,
+             kc_worldmap_match_result *out) {
+  KC_TRY(wm_check_match_args(g, rot, K, S));
+  LocalGrid l{};
+  KC_TRY(wm_resolve(c, src, [&](const LocalGrid &m) { return wm_check_match_grid(c->res, m.gh, m.gw, m.c0, m.c1, m.res); }, &l));
+  const int32_t *dev = l.p;
+  const int gh = l.gh, gw = l.gw, c0 = l.c0, c1 = l.c1;
   const int T = 2 * S + 1, ncand = T * T, nrot = 2 * K + 1;
   const size_t table_cells = static_cast<size_t>(nrot) * ncand, cells = static_cast<size_t>(gh) * static_cast<size_t>(gw);
   const int half = wm_match_half(gh, gw, c0, c1, S), P = 2 * half + 1;
@@ -757,21 +792,6 @@ bool wm_window_box(int W, int H, int ic, int jc, int rc, int box[4]) {
   return box[0] <= box[2] && box[1] <= box[3];
 }
 
-// both counter blocks to their start values
-int wm_reset_point_counters(kc_worldmap *c) {
-  int init[2 * 5 * kWmPtsStride] = {0};
-  for (int b = 0; b < 2; ++b) {
-    int *blk = init + b * 5 * kWmPtsStride;
-    blk[1 * kWmPtsStride] = blk[3 * kWmPtsStride] = INT_MAX;
-    blk[2 * kWmPtsStride] = blk[4 * kWmPtsStride] = INT_MIN;
-  }
-  c->ptcnt_ready = false;
-  KC_HIP(hipMemcpyAsync(c->d_ptcnt.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));  // `init` is on this frame
-  c->ptcnt_ready = true;
-  return KC_OK;
-}
-
 void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *out) {
   *out = kc_worldmap_match_result{};
   if (g) out->pose = *g;
@@ -827,8 +847,7 @@ int worldmap_queue_points(const WorldMapView &v, const WorldMapWindow &w, float 
   a.res = static_cast<double>(v.res);
   a.ox = v.ox;
   a.oy = v.oy;
-  const dim3 grid((box[2] - box[0]) / kWmLanes + 1, (box[3] - box[1]) / kWmRows + 1), block(kWmLanes, kWmRows);
-  hipLaunchKernelGGL(worldmap_window_points_kernel, grid, block, 0, stream, a);
+  hipLaunchKernelGGL(worldmap_window_points_kernel, wm_box_grid(box), dim3(kWmLanes, kWmRows), 0, stream, a);
   KC_HIP(hipGetLastError());
   return KC_OK;
 }
@@ -841,12 +860,7 @@ int kc_worldmap_window(float resolution, double origin_x, double origin_y, doubl
                        int32_t *ic_out, int32_t *jc_out, int32_t *rc_out) {
   if (!ic_out || !jc_out || !rc_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   *ic_out = *jc_out = *rc_out = 0;
-  int ic, jc, rc;
-  KC_TRY(wm_window(resolution, origin_x, origin_y, x, y, max_sensor_range, &ic, &jc, &rc));
-  *ic_out = ic;
-  *jc_out = jc;
-  *rc_out = rc;
-  return KC_OK;
+  return wm_window(resolution, origin_x, origin_y, x, y, max_sensor_range, ic_out, jc_out, rc_out);  // (writes on success only)
 }
 
 int kc_worldmap_points(kc_worldmap *c, double x, double y, float max_sensor_range, float *xyz_out, size_t cap, size_t *count_out,
@@ -861,18 +875,12 @@ int kc_worldmap_points(kc_worldmap *c, double x, double y, float max_sensor_rang
   if (w.max_points == 0) return KC_OK;  // the window misses the map: rule 17
   KC_HIP(hipSetDevice(c->device));
   if (xyz_out) KC_TRY(c->d_pts.reserve(3 * w.max_points));
-  KC_TRY(c->d_ptcnt.reserve(2 * 5 * kWmPtsStride));
-  KC_TRY(c->h_ptrec.reserve(5 * kWmPtsStride));
-  if (!c->ptcnt_ready) KC_TRY(wm_reset_point_counters(c));
-  unsigned int *cnt = c->d_ptcnt.p + (c->pt_seq & 1) * 5 * kWmPtsStride;
-  unsigned int *next = c->d_ptcnt.p + ((c->pt_seq + 1) & 1) * 5 * kWmPtsStride;
-  c->ptcnt_ready = false;  // until the read-back below says this launch ran: a failure leaves the counters unknown
-  KC_TRY(worldmap_queue_points(v, w, xyz_out ? c->d_pts.p : nullptr, cnt, next, c->stream));
-  KC_HIP(hipMemcpyAsync(c->h_ptrec.p, cnt, 5 * kWmPtsStride * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));
-  ++c->pt_seq;
-  c->ptcnt_ready = true;
-  const int *r = c->h_ptrec.p;
+  int *rearm = nullptr;
+  KC_TRY(c->pts_rec.begin(c->stream, &rearm));
+  KC_TRY(worldmap_queue_points(v, w, xyz_out ? c->d_pts.p : nullptr, reinterpret_cast<unsigned int *>(c->pts_rec.cur),
+                               reinterpret_cast<unsigned int *>(rearm), c->stream));
+  KC_TRY(c->pts_rec.commit(c->stream));
+  const int *r = c->pts_rec.h.p;
   const size_t n = static_cast<size_t>(static_cast<unsigned int>(r[0]));
   if (n > w.max_points) KC_FAIL(KC_ERR_HIP, "the window's count %zu is above its %zu cells", n, w.max_points);
   *count_out = n;
@@ -935,10 +943,16 @@ int kc_worldmap_create(int device, int width, int height, float resolution, doub
   c->res = resolution;
   c->ox = origin_x;
   c->oy = origin_y;
+  const int rec_start[kWmRecWords] = {0, INT_MAX, INT_MAX, -1, -1};  // what worldmap_update_kernel puts back
+  c->rec.start.assign(rec_start, rec_start + kWmRecWords);
+  std::vector<int> &pts_start = c->pts_rec.start;  // ... and worldmap_window_points_kernel
+  pts_start.assign(5 * kWmPtsStride, 0);
+  pts_start[1 * kWmPtsStride] = pts_start[3 * kWmPtsStride] = INT_MAX;
+  pts_start[2 * kWmPtsStride] = pts_start[4 * kWmPtsStride] = INT_MIN;
   const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
   int rc;
-  if ((rc = c->d_evidence.reserve(n)) || (rc = c->d_cls.reserve(n)) || (rc = c->d_rec.reserve(2 * kWmRecWords)) ||
-      (rc = c->h_rec.reserve(kWmRecWords)) || (rc = wm_reset_records(c)) || (rc = wm_take_prior(c, nullptr, 1))) {
+  if ((rc = c->d_evidence.reserve(n)) || (rc = c->d_cls.reserve(n)) || (rc = c->rec.arm(c->stream)) ||
+      (rc = wm_take_prior(c, nullptr, 1))) {
     kc_worldmap_destroy(c);
     return rc;
   }
@@ -949,11 +963,7 @@ int kc_worldmap_create(int device, int width, int height, float resolution, doub
 void kc_worldmap_destroy(kc_worldmap *c) {
   if (!c) return;
   close_device_stream(c->device, &c->stream);
-  if (c->grid_ready) {
-    hipError_t e = hipEventDestroy(c->grid_ready);
-    (void)e;
-  }
-  delete c;
+  delete c;  // (the device is current: the buffers and the event go with the context)
 }
 
 int kc_worldmap_info(kc_worldmap *c, int *width_out, int *height_out, float *resolution_out, double *origin_x_out,
@@ -985,8 +995,7 @@ int kc_worldmap_set_prior_host(kc_worldmap *c, const void *grid, int elem_bytes,
   KC_TRY(wm_check_prior(c, grid, elem_bytes, width, height));
   KC_HIP(hipSetDevice(c->device));
   const size_t nbytes = static_cast<size_t>(width) * static_cast<size_t>(height) * static_cast<size_t>(elem_bytes);
-  KC_TRY(c->d_stage.reserve((nbytes + 3) / 4));
-  KC_HIP(hipMemcpyAsync(c->d_stage.p, grid, nbytes, hipMemcpyHostToDevice, c->stream));
+  KC_TRY(wm_stage(c, grid, nbytes));
   return wm_take_prior(c, c->d_stage.p, elem_bytes);
 }
 
@@ -1006,39 +1015,20 @@ int kc_worldmap_after_stream(kc_worldmap *c, void *stream) {
 int kc_worldmap_update_device(kc_worldmap *c, const int32_t *dev_grid, int grid_height, int grid_width, int central_i,
                               int central_j, float resolution, const kc_worldmap_pose *pose, kc_worldmap_result *out) {
   if (!c || !dev_grid || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
-  KC_TRY(wm_check_grid(c->res, grid_height, grid_width, central_i, central_j, resolution));
-  KC_TRY(wm_check_pose(pose));
-  KC_HIP(hipSetDevice(c->device));
-  const long long nbytes = static_cast<long long>(grid_height) * grid_width * static_cast<long long>(sizeof(int32_t));
-  KC_TRY(check_device_range(c->device, dev_grid, 0, nbytes, sizeof(int32_t), "grid"));
-  return wm_update(c, dev_grid, grid_height, grid_width, central_i, central_j, pose, out);
+  const GridSource src{GridSource::Device, {dev_grid, grid_height, grid_width, central_i, central_j, resolution}, nullptr};
+  return wm_update(c, src, pose, out);
 }
 
 int kc_worldmap_update_host(kc_worldmap *c, const int32_t *grid, int grid_height, int grid_width, int central_i,
                             int central_j, float resolution, const kc_worldmap_pose *pose, kc_worldmap_result *out) {
   if (!c || !grid || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
-  KC_TRY(wm_check_grid(c->res, grid_height, grid_width, central_i, central_j, resolution));
-  KC_TRY(wm_check_pose(pose));
-  KC_HIP(hipSetDevice(c->device));
-  const size_t cells = static_cast<size_t>(grid_height) * static_cast<size_t>(grid_width);
-  KC_TRY(c->d_stage.reserve(cells));
-  KC_HIP(hipMemcpyAsync(c->d_stage.p, grid, cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  return wm_update(c, c->d_stage.p, grid_height, grid_width, central_i, central_j, pose, out);
+  const GridSource src{GridSource::Host, {grid, grid_height, grid_width, central_i, central_j, resolution}, nullptr};
+  return wm_update(c, src, pose, out);
 }
 
 int kc_worldmap_update_from_mapper(kc_worldmap *c, kc_mapper *mapper, const kc_worldmap_pose *pose, kc_worldmap_result *out) {
   if (!c || !mapper || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
-  MapperView v{};
-  KC_TRY(mapper_view(mapper, &v));
-  if (v.device != c->device) KC_FAIL(KC_ERR_INVALID, "mapper on device %d, world map on device %d", v.device, c->device);
-  KC_TRY(wm_check_grid(c->res, v.H, v.W, v.c0, v.c1, v.res));
-  KC_TRY(wm_check_pose(pose));
-  KC_HIP(hipSetDevice(c->device));
-  // the map's stream waits for the scan; the host does not
-  if (!c->grid_ready) KC_HIP(hipEventCreateWithFlags(&c->grid_ready, hipEventDisableTiming));
-  KC_HIP(hipEventRecord(c->grid_ready, v.stream));
-  KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
-  return wm_update(c, v.grid, v.H, v.W, v.c0, v.c1, pose, out);
+  return wm_update(c, GridSource{GridSource::Mapper, {}, mapper}, pose, out);
 }
 
 int kc_worldmap_grid_device(kc_worldmap *c, void **dev_cls_int8) {
@@ -1083,12 +1073,8 @@ int kc_worldmap_match_device(kc_worldmap *c, const int32_t *dev_grid, int grid_h
                              int n_yaw, int reach, kc_worldmap_match_result *out) {
   if (!c || !dev_grid || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
   wm_clear_match_result(guess, out);
-  KC_TRY(wm_check_match_args(guess, rotations, n_yaw, reach));
-  KC_TRY(wm_check_match_grid(c->res, grid_height, grid_width, central_i, central_j, resolution));
-  KC_HIP(hipSetDevice(c->device));
-  const long long nbytes = static_cast<long long>(grid_height) * grid_width * static_cast<long long>(sizeof(int32_t));
-  KC_TRY(check_device_range(c->device, dev_grid, 0, nbytes, sizeof(int32_t), "grid"));
-  return wm_match(c, dev_grid, grid_height, grid_width, central_i, central_j, guess, rotations, n_yaw, reach, out);
+  const GridSource src{GridSource::Device, {dev_grid, grid_height, grid_width, central_i, central_j, resolution}, nullptr};
+  return wm_match(c, src, guess, rotations, n_yaw, reach, out);
 }
 
 int kc_worldmap_match_host(kc_worldmap *c, const int32_t *grid, int grid_height, int grid_width, int central_i, int central_j,
@@ -1096,30 +1082,15 @@ int kc_worldmap_match_host(kc_worldmap *c, const int32_t *grid, int grid_height,
                            int reach, kc_worldmap_match_result *out) {
   if (!c || !grid || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
   wm_clear_match_result(guess, out);
-  KC_TRY(wm_check_match_args(guess, rotations, n_yaw, reach));
-  KC_TRY(wm_check_match_grid(c->res, grid_height, grid_width, central_i, central_j, resolution));
-  KC_HIP(hipSetDevice(c->device));
-  const size_t cells = static_cast<size_t>(grid_height) * static_cast<size_t>(grid_width);
-  KC_TRY(c->d_stage.reserve(cells));
-  KC_HIP(hipMemcpyAsync(c->d_stage.p, grid, cells * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  return wm_match(c, c->d_stage.p, grid_height, grid_width, central_i, central_j, guess, rotations, n_yaw, reach, out);
+  const GridSource src{GridSource::Host, {grid, grid_height, grid_width, central_i, central_j, resolution}, nullptr};
+  return wm_match(c, src, guess, rotations, n_yaw, reach, out);
 }
 
 int kc_worldmap_match_from_mapper(kc_worldmap *c, kc_mapper *mapper, const kc_worldmap_pose *guess,
                                   const kc_worldmap_rotation *rotations, int n_yaw, int reach, kc_worldmap_match_result *out) {
   if (!c || !mapper || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
   wm_clear_match_result(guess, out);
-  KC_TRY(wm_check_match_args(guess, rotations, n_yaw, reach));
-  MapperView v{};
-  KC_TRY(mapper_view(mapper, &v));
-  if (v.device != c->device) KC_FAIL(KC_ERR_INVALID, "mapper on device %d, world map on device %d", v.device, c->device);
-  KC_TRY(wm_check_match_grid(c->res, v.H, v.W, v.c0, v.c1, v.res));
-  KC_HIP(hipSetDevice(c->device));
-  // the map's stream waits for the scan; the host does not
-  if (!c->grid_ready) KC_HIP(hipEventCreateWithFlags(&c->grid_ready, hipEventDisableTiming));
-  KC_HIP(hipEventRecord(c->grid_ready, v.stream));
-  KC_HIP(hipStreamWaitEvent(c->stream, c->grid_ready, 0));
-  return wm_match(c, v.grid, v.H, v.W, v.c0, v.c1, guess, rotations, n_yaw, reach, out);
+  return wm_match(c, GridSource{GridSource::Mapper, {}, mapper}, guess, rotations, n_yaw, reach, out);
 }
 
 int kc_worldmap_match_scores(kc_worldmap *c, uint32_t *out, size_t cap) {

@@ -1441,44 +1441,43 @@ class WorldMapContext(_Owner, _StreamOrdered):
     def _pose(self, pose):
         return pose if isinstance(pose, WorldMapPose) else self.quantise_pose(*pose)
 
-    @staticmethod
-    def _central(grid_height, grid_width, central):
-        # the mapper's central cell (local_mapper.h:26-27)
-        return (grid_height // 2 - 1, grid_width // 2 - 1) if central is None else central
+    def _grid_args(self, grid, device_ptr, shape, central, resolution):
+        """-> ((pointer, grid_height, grid_width, central_i, central_j, resolution) as the C entries take a local grid, the
+        array that keeps a host pointer alive).  grid: 2-D int32 on the host, any memory order; or device_ptr with shape."""
+        g = None
+        if device_ptr is None:
+            g = np.asarray(grid)
+            if g.ndim != 2 or g.dtype != np.int32:
+                raise ValueError("expected a 2-D int32 grid")
+            g = np.asfortranarray(g)  # local cell (i, j) at i + j * grid_height
+            device_ptr, shape = g.ctypes.data, g.shape
+        gh, gw = int(shape[0]), int(shape[1])
+        c = (gh // 2 - 1, gw // 2 - 1) if central is None else central  # the mapper's central cell (local_mapper.h:26-27)
+        res = self.resolution if resolution is None else float(np.float32(resolution))
+        return (int(device_ptr), gh, gw, int(c[0]), int(c[1]), res), g
+
+    def _update(self, entry, source, pose):
+        p, r = self._pose(pose), WorldMapResult()
+        _check(entry(self.h, *source, C.byref(p), C.byref(r)))
+        return r.as_tuple()
 
     def update(self, grid, pose, central=None, resolution=None):
         """grid: int32 [grid_height, grid_width] on the host (MapperContext.scan_to_grid's form), any memory order;
         pose: (x, y, yaw) of its frame in the world, or a WorldMapPose.  -> (changed, (i_min, j_min, i_max, j_max))."""
-        g = np.asarray(grid)
-        if g.ndim != 2 or g.dtype != np.int32:
-            raise ValueError("expected a 2-D int32 grid")
-        g = np.asfortranarray(g)  # local cell (i, j) at i + j * grid_height
-        c = self._central(g.shape[0], g.shape[1], central)
-        p, r = self._pose(pose), WorldMapResult()
-        _check(lib().kc_worldmap_update_host(self.h, g.ctypes.data, g.shape[0], g.shape[1], int(c[0]), int(c[1]),
-                                             self.resolution if resolution is None else float(np.float32(resolution)),
-                                             C.byref(p), C.byref(r)))
-        return r.as_tuple()
+        args, _keep = self._grid_args(grid, None, None, central, resolution)
+        return self._update(lib().kc_worldmap_update_host, args, pose)
 
     def update_device(self, device_ptr, grid_height, grid_width, pose, central=None, resolution=None):
         """A finished int32 grid on the context's device, column-major [grid_height x grid_width], read in place."""
-        c = self._central(int(grid_height), int(grid_width), central)
-        p, r = self._pose(pose), WorldMapResult()
-        _check(lib().kc_worldmap_update_device(self.h, int(device_ptr), int(grid_height), int(grid_width), int(c[0]),
-                                               int(c[1]),
-                                               self.resolution if resolution is None else float(np.float32(resolution)),
-                                               C.byref(p), C.byref(r)))
-        return r.as_tuple()
+        args, _ = self._grid_args(None, device_ptr, (grid_height, grid_width), central, resolution)
+        return self._update(lib().kc_worldmap_update_device, args, pose)
 
     def update_from_mapper(self, mapper: "MapperContext", pose):
         """The last grid of a MapperContext where it lies, ordered after its scan without a host wait."""
-        p, r = self._pose(pose), WorldMapResult()
-        _check(lib().kc_worldmap_update_from_mapper(self.h, mapper.h, C.byref(p), C.byref(r)))
-        return r.as_tuple()
+        return self._update(lib().kc_worldmap_update_from_mapper, (mapper.h,), pose)
 
-    def _window(self, pose, n_yaw, yaw_step, reach, rotations):
-        """-> (guess, rotation table, K, S) of a match.  pose: (x, y, yaw) with n_yaw / yaw_step, or a WorldMapPose
-        with `rotations`, the 2K + 1 (cq, sq) pairs."""
+    def _match(self, entry, source, pose, n_yaw, yaw_step, reach, rotations):
+        """pose: (x, y, yaw) with n_yaw / yaw_step, or a WorldMapPose with `rotations`, the 2K + 1 (cq, sq) pairs."""
         if rotations is None:
             if isinstance(pose, WorldMapPose):
                 raise ValueError("a quantised guess needs its rotation table")
@@ -1486,41 +1485,25 @@ class WorldMapContext(_Owner, _StreamOrdered):
         if len(rotations) % 2 != 1:
             raise ValueError("a rotation table holds 2 K + 1 pairs")
         rot = (WorldMapRotation * len(rotations))(*[WorldMapRotation(int(c), int(s)) for c, s in rotations])
-        return self._pose(pose), rot, len(rotations) // 2, int(reach)
+        p, r = self._pose(pose), WorldMapMatchResult()
+        _check(entry(self.h, *source, C.byref(p), rot, len(rotations) // 2, int(reach), C.byref(r)))
+        return r.as_dict()
 
     def match(self, grid, pose, n_yaw=0, yaw_step=0.0, reach=0, central=None, resolution=None, rotations=None):
         """Rules 9 to 15: the pose of the window around the guess `pose` that puts the occupied cells of `grid` (as
         update takes it) onto the map best.  -> dict(k, u, v, score, score_guess, points, pose)."""
-        g = np.asarray(grid)
-        if g.ndim != 2 or g.dtype != np.int32:
-            raise ValueError("expected a 2-D int32 grid")
-        g = np.asfortranarray(g)
-        c = self._central(g.shape[0], g.shape[1], central)
-        p, rot, K, S = self._window(pose, n_yaw, yaw_step, reach, rotations)
-        r = WorldMapMatchResult()
-        _check(lib().kc_worldmap_match_host(self.h, g.ctypes.data, g.shape[0], g.shape[1], int(c[0]), int(c[1]),
-                                            self.resolution if resolution is None else float(np.float32(resolution)),
-                                            C.byref(p), rot, K, S, C.byref(r)))
-        return r.as_dict()
+        args, _keep = self._grid_args(grid, None, None, central, resolution)
+        return self._match(lib().kc_worldmap_match_host, args, pose, n_yaw, yaw_step, reach, rotations)
 
     def match_device(self, device_ptr, grid_height, grid_width, pose, n_yaw=0, yaw_step=0.0, reach=0, central=None,
                      resolution=None, rotations=None):
         """The same from a finished int32 grid on the context's device, read in place."""
-        c = self._central(int(grid_height), int(grid_width), central)
-        p, rot, K, S = self._window(pose, n_yaw, yaw_step, reach, rotations)
-        r = WorldMapMatchResult()
-        _check(lib().kc_worldmap_match_device(self.h, int(device_ptr), int(grid_height), int(grid_width), int(c[0]),
-                                              int(c[1]),
-                                              self.resolution if resolution is None else float(np.float32(resolution)),
-                                              C.byref(p), rot, K, S, C.byref(r)))
-        return r.as_dict()
+        args, _ = self._grid_args(None, device_ptr, (grid_height, grid_width), central, resolution)
+        return self._match(lib().kc_worldmap_match_device, args, pose, n_yaw, yaw_step, reach, rotations)
 
     def match_from_mapper(self, mapper: "MapperContext", pose, n_yaw=0, yaw_step=0.0, reach=0, rotations=None):
         """The same from the last grid of a MapperContext where it lies, ordered after its scan without a host wait."""
-        p, rot, K, S = self._window(pose, n_yaw, yaw_step, reach, rotations)
-        r = WorldMapMatchResult()
-        _check(lib().kc_worldmap_match_from_mapper(self.h, mapper.h, C.byref(p), rot, K, S, C.byref(r)))
-        return r.as_dict()
+        return self._match(lib().kc_worldmap_match_from_mapper, (mapper.h,), pose, n_yaw, yaw_step, reach, rotations)
 
     def match_scores(self, n_yaw, reach):
         """Rule 13's table of the last match, uint32 [2K+1, 2S+1, 2S+1] indexed [k + K, v + S, u + S]; the window
