@@ -1162,6 +1162,67 @@ int kc_worldmap_window(float resolution, double origin_x, double origin_y, doubl
 int kc_worldmap_points(kc_worldmap *ctx, double x, double y, float max_sensor_range, float *xyz_out, size_t cap,
                        size_t *count_out, int32_t bounds_out[4]);
 
+/* A virtual laser scan ray-cast from the map (DESIGN.md 4.11 rules 20 to 27): what a lidar
+ * at a pose would range, by the map's memory.  Nothing in the reference to cite, as above.
+ * Integers throughout (int64, arithmetic shifts) except where a range becomes a double, so
+ * every range is independent of thread order; the map is not modified.
+ * Rule 20: the scan frame's pose (Cq, Sq, TX, TY) as kc_worldmap_quantise_pose gives it;
+ * X0 = TX + 2^15, Y0 = TY + 2^15, start cell I0 = X0 >> 16, J0 = Y0 >> 16, fractions fx =
+ * X0 & 0xFFFF, fy = Y0 & 0xFFFF; Rc = (int)ceil((double)range_max / (double)resolution).
+ * Rule 21: beam k of angle a_k (scan frame) has ac_k = lrint(cos(a_k) * 2^30), as_k =
+ * lrint(sin(a_k) * 2^30), int32, cos / sin the host libm's in double.  Rule 22: dx = (Cq
+ * ac_k - Sq as_k + 2^15) >> 16, dy = (Sq ac_k + Cq as_k + 2^15) >> 16.  Rule 23, the walk:
+ * sx = dx > 0 ? 1 : -1, ex = dx > 0 ? 65536 - fx : fx, y alike; a start cell that blocks
+ * ends the beam with e = 0; otherwise step along x if dy == 0, along y if dx == 0, else
+ * along x iff ex |dy| <= ey |dx| (a tie: x first, the y step follows at the same distance,
+ * so a ray through a corner visits the cell beside it); a step along x sets e = ex, a =
+ * |dx|, I += sx, ex += 65536, one along y alike; after it the beam ends without a hit if
+ * |I - I0| > Rc + 1 or |J - J0| > Rc + 1, and with the candidate (I, J, e, a) if the cell
+ * blocks.  Cells outside the map never block; a scan may start outside and look in.  Rule
+ * 24: r = ((double)e * 16384.0 / (double)a) * (double)resolution, one division and one
+ * product, each rounded once; the first blocking cell decides, and counts iff r <=
+ * (double)range_max.  Rule 25: a cell blocks if its cls byte is KC_OCCUPIED, with
+ * KC_SCAN_UNKNOWN_BLOCKS also if it is KC_UNEXPLORED.  Rule 26: ranges[p * B + k] is r on a
+ * hit and (double)range_max otherwise, cells[p * B + k] is I + J * width on a hit and -1
+ * otherwise.  Rule 27: with a present scan real[k] the stored range is real[k] < v ? real[k]
+ * : v, a NaN or an infinite real[k] leaves v. */
+#define KC_SCAN_UNKNOWN_BLOCKS 1u
+/* rule 21's table (host only, needs no device): ac_as_out[2 k], ac_as_out[2 k + 1] = ac_k,
+ * as_k.  KC_ERR_INVALID for a non-finite angle, and then nothing is written. */
+int kc_worldmap_scan_table(const double *angles, size_t n, int32_t *ac_as_out);
+/* the refusals of rules 20, 21 and 25 (host only), in this order: KC_ERR_INVALID for no
+ * pose or no beam, KC_ERR_RANGE above 65536 beams or n_poses * n_beams > 2^22,
+ * KC_ERR_INVALID unless range_max is a finite float > 0, KC_ERR_RANGE for Rc > 2048,
+ * KC_ERR_INVALID for unknown flag bits.  rc_out (may be NULL): Rc, 0 on a refusal. */
+int kc_worldmap_scan_check(float resolution, size_t n_poses, size_t n_beams, float range_max, unsigned int flags,
+                           int32_t *rc_out);
+/* The scan of n_poses poses x n_beams angles into host memory: one launch (a lane a beam,
+ * a single pose in the kernel arguments, a batch from a device buffer) and one read-back;
+ * returns with the outputs final.  ranges_out and cells_or_null hold n_poses * n_beams
+ * values.  The context keeps the table of the last angle array and forms it again only
+ * when the bytes differ.  Checks: null arguments, then kc_worldmap_scan_check, the angles
+ * (finite) and the poses (as an update's), then the device; a refused call queues nothing. */
+int kc_worldmap_scan(kc_worldmap *ctx, const kc_worldmap_pose *poses, size_t n_poses, const double *angles,
+                     size_t n_beams, float range_max, unsigned int flags, double *ranges_out, int32_t *cells_or_null);
+/* kc_dvz_deform on the map's scan at `pose` (rules 26 and 27), without the ranges leaving
+ * the device: the scan is queued on the DVZ context's stream, behind an event on the
+ * map's stream (no host wait on the map), straight into the buffer the deformation kernel
+ * reads; that kernel follows unchanged, so out[3] and radii_or_null are kc_dvz_deform's on
+ * those ranges, bit for bit.  real_or_null: n present ranges to merge by rule 27.
+ * ranges_or_null: the n ranges the zone was deformed by.  Checks: null arguments; n (1 ..
+ * the context's max_beams), the zone, the angles, range_max and flags, the pose; the
+ * map's device against the context's (KC_ERR_INVALID); then the device. */
+int kc_dvz_deform_worldmap(kc_dvz *ctx, const kc_dvz_zone *zone, kc_worldmap *map, const kc_worldmap_pose *pose,
+                           const double *angles, size_t n, float range_max, unsigned int flags,
+                           const double *real_or_null, double out[3], double *radii_or_null, double *ranges_or_null);
+/* kc_zone_check on the map's scan at `pose`, the scan frame (the sensor's pose in the
+ * world): the checker's own preset angles, whose table kc_zone_create formed, and its
+ * range_max; the scan is queued on the checker's stream into the buffer zone_check_kernel
+ * reads, ordered as above.  real_or_null: the preset's count of present ranges (rule 27).
+ * A checker without angles gives 1.  Checks as above. */
+int kc_zone_check_worldmap(kc_zone *ctx, kc_worldmap *map, const kc_worldmap_pose *pose, unsigned int flags,
+                           const double *real_or_null, int forward, float *factor_out);
+
 /* Correlative match of a local grid against the map (DESIGN.md 4.11 rules 9 to 15): which
  * pose near a guess puts the grid's occupied cells onto the map's?  Integers only, sums
  * of integers, so no result depends on thread order; the map is not modified.

@@ -1079,6 +1079,34 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return a;
            }, py::arg("x"), py::arg("y"), py::arg("max_sensor_range"),
            "The occupied cells within max_sensor_range of (x, y) as world-frame points, float32 [n, 3], in no particular order")
+      .def("scan", [](const Mapping::WorldMap &m, double x, double y, double yaw, const std::vector<double> &angles,
+                      float range_max, bool unknown_blocks, bool return_cells) -> py::object {
+             std::vector<double> r;
+             std::vector<int32_t> c;
+             {
+               py::gil_scoped_release nogil;
+               r = return_cells ? m.scanCells(x, y, yaw, angles, range_max, unknown_blocks, c)
+                                : m.scan(x, y, yaw, angles, range_max, unknown_blocks);
+             }
+             py::array_t<double> ra(static_cast<py::ssize_t>(r.size()), r.data());
+             if (!return_cells) return std::move(ra);
+             return py::make_tuple(ra, py::array_t<int32_t>(static_cast<py::ssize_t>(c.size()), c.data()));
+           }, py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("angles"), py::arg("range_max"),
+           py::arg("unknown_blocks") = false, py::arg("return_cells") = false,
+           "The map's virtual laser scan from the frame (x, y, yaw): float64 [B], the distance to the first occupied cell "
+           "along every beam angle within range_max, else range_max; with return_cells also the hit cells I + J * width")
+      .def("scans", [](const Mapping::WorldMap &m, const std::vector<std::array<double, 3>> &poses,
+                       const std::vector<double> &angles, float range_max, bool unknown_blocks) {
+             std::vector<double> r;
+             {
+               py::gil_scoped_release nogil;
+               r = m.scans(poses, angles, range_max, unknown_blocks);
+             }
+             py::array_t<double> a({static_cast<py::ssize_t>(poses.size()), static_cast<py::ssize_t>(angles.size())});
+             if (!r.empty()) std::memcpy(a.mutable_data(), r.data(), sizeof(double) * r.size());
+             return a;
+           }, py::arg("poses"), py::arg("angles"), py::arg("range_max"), py::arg("unknown_blocks") = false,
+           "The same for a batch of poses (x, y, yaw) in one launch: float64 [M, B]")
       .def("get_cls", [plane](const Mapping::WorldMap &m) { return plane(m.cls(), m.width(), m.height()); },
            "the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied")
       .def("get_evidence", [plane](const Mapping::WorldMap &m) { return plane(m.evidence(), m.width(), m.height()); },
@@ -1112,6 +1140,11 @@ PYBIND11_MODULE(kompass_cpp, m) {
       using T = std::remove_pointer_t<decltype(tag)>;
       return std::make_unique<T>(it, shape, dims, vec3(spos), vec4(srot), ca, cd, sd, angles, minh, maxh, rmax);
     };
+    auto worldMapOf = [](const py::object &o) -> const Mapping::WorldMap & {
+      const py::object inner = py::hasattr(o, "_map") ? py::object(o.attr("_map")) : o;
+      if (!py::isinstance<Mapping::WorldMap>(inner)) throw py::type_error("expected a WorldMap");
+      return inner.cast<const Mapping::WorldMap &>();
+    };
     py::class_<CriticalZoneChecker> cz(ut, "CriticalZoneChecker");
     py::enum_<CriticalZoneChecker::InputType>(cz, "InputType")
         .value("LASERSCAN", CriticalZoneChecker::InputType::LASERSCAN)
@@ -1136,7 +1169,20 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def("check", py::overload_cast<const std::vector<int8_t> &, int, int, int, int, int, int, int, bool>(
                           &CriticalZoneChecker::check),
              py::arg("data"), py::arg("point_step"), py::arg("row_step"), py::arg("height"), py::arg("width"),
-             py::arg("x_offset"), py::arg("y_offset"), py::arg("z_offset"), py::arg("forward"));
+             py::arg("x_offset"), py::arg("y_offset"), py::arg("z_offset"), py::arg("forward"))
+        // (not in the reference: the check on a WorldMap's virtual scan at the robot's pose, the ranges on the device)
+        // world_map: the class, or the front end's WorldMap that holds one as `_map`
+        .def("check", [worldMapOf](CriticalZoneChecker &c, const py::object &world_map, double x, double y, double yaw, bool forward) {
+               const Mapping::WorldMap &map = worldMapOf(world_map);
+               py::gil_scoped_release nogil;
+               return c.check(map, x, y, yaw, forward);
+             }, py::arg("world_map"), py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("forward"))
+        .def("check", [worldMapOf](CriticalZoneChecker &c, const py::object &world_map, double x, double y, double yaw, bool forward,
+                                   const std::vector<double> &ranges) {
+               const Mapping::WorldMap &map = worldMapOf(world_map);
+               py::gil_scoped_release nogil;
+               return c.check(map, x, y, yaw, forward, ranges);
+             }, py::arg("world_map"), py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("forward"), py::arg("ranges"));
     py::class_<CriticalZoneCheckerGPU, CriticalZoneChecker>(ut, "CriticalZoneCheckerGPU")
         .def(py::init([](CriticalZoneChecker::InputType it, CollisionChecker::ShapeType shape,
                          const std::vector<float> &dims, const py::object &spos, const py::object &srot, float ca,

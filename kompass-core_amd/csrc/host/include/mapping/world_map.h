@@ -72,6 +72,19 @@ class WorldMap {
   // finite float > 0, std::out_of_range above 2048 cells of radius.
   std::vector<Path::Point> points(double x, double y, float max_sensor_range) const;
 
+  // The map's virtual laser scan (DESIGN.md 4.11 rules 20 to 27): what a lidar whose frame is at (x, y, yaw) in the world
+  // would range over the beam `angles` (scan frame), by the map's memory: the distance to the first OCCUPIED cell (with
+  // unknown_blocks also a never-observed one) within range_max, else range_max.  One launch on the device.  scans: a batch
+  // of poses {x, y, yaw} in one launch, ranges[p * angles.size() + k].  scanCells: also the hit cells I + J * width, -1
+  // where a beam has no hit.  Exceptions as points(): std::invalid_argument (range_max, a non-finite angle or pose, no
+  // beam), std::out_of_range (above 2048 cells of range, 65536 beams or 2^22 rays).
+  std::vector<double> scan(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
+                           bool unknown_blocks = false) const;
+  std::vector<double> scans(const std::vector<std::array<double, 3>> &poses, const std::vector<double> &angles, float range_max,
+                            bool unknown_blocks = false) const;
+  std::vector<double> scanCells(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
+                                bool unknown_blocks, std::vector<int32_t> &cells_out) const;
+
   // copies of the planes, width x height as the map
   std::vector<int8_t> cls() const;
   std::vector<int8_t> evidence() const;
@@ -111,6 +124,8 @@ class WorldMap {
   };
   uint32_t updateFrom(const GridSource &s, const kc_worldmap_pose &pose);
   Match matchFrom(const GridSource &s, double x, double y, double yaw, int n_yaw, double yaw_step, int reach);
+  std::vector<double> scanPoses(const std::vector<std::array<double, 3>> &poses, const std::vector<double> &angles, float range_max,
+                                bool unknown_blocks, std::vector<int32_t> *cells_out) const;
 };
 
 }  // namespace Mapping

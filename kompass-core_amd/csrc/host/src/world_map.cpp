@@ -132,6 +132,35 @@ std::vector<Path::Point> WorldMap::points(double x, double y, float max_sensor_r
   return out;
 }
 
+std::vector<double> WorldMap::scanPoses(const std::vector<std::array<double, 3>> &poses, const std::vector<double> &angles,
+                                        float range_max, bool unknown_blocks, std::vector<int32_t> *cells_out) const {
+  const unsigned flags = unknown_blocks ? KC_SCAN_UNKNOWN_BLOCKS : 0u;
+  hip::check(kc_worldmap_scan_check(res_, poses.size(), angles.size(), range_max, flags, nullptr));
+  std::vector<kc_worldmap_pose> q;
+  q.reserve(poses.size());
+  for (const auto &p : poses) q.push_back(quantisePose(res_, ox_, oy_, p[0], p[1], p[2]));
+  std::vector<double> out(poses.size() * angles.size());
+  if (cells_out) cells_out->assign(out.size(), -1);
+  hip::check(kc_worldmap_scan(ctx_.get(), q.data(), q.size(), angles.data(), angles.size(), range_max, flags, out.data(),
+                              cells_out ? cells_out->data() : nullptr));
+  return out;
+}
+
+std::vector<double> WorldMap::scan(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
+                                   bool unknown_blocks) const {
+  return scanPoses({{x, y, yaw}}, angles, range_max, unknown_blocks, nullptr);
+}
+
+std::vector<double> WorldMap::scans(const std::vector<std::array<double, 3>> &poses, const std::vector<double> &angles, float range_max,
+                                    bool unknown_blocks) const {
+  return scanPoses(poses, angles, range_max, unknown_blocks, nullptr);
+}
+
+std::vector<double> WorldMap::scanCells(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
+                                        bool unknown_blocks, std::vector<int32_t> &cells_out) const {
+  return scanPoses({{x, y, yaw}}, angles, range_max, unknown_blocks, &cells_out);
+}
+
 std::vector<int8_t> WorldMap::cls() const {
   std::vector<int8_t> out(static_cast<size_t>(width_) * static_cast<size_t>(height_));
   hip::check(kc_worldmap_get(ctx_.get(), out.data(), nullptr, out.size()));

@@ -182,7 +182,75 @@ struct kc_dvz {
   PinBuf<double> h_result;  // the record {total, orientation_sum, n_deformed}
   PinBuf<double> h_radii;   // deformation_plot, on request
   PinBuf<double2> h_trig;   // the host libm's (cos, sin) when the device trig does not apply
+  // kc_dvz_deform_worldmap: the map's virtual scan (DESIGN.md 4.11 rules 20 to 27) lands in d_ranges
+  OrderEvent map_ready;     // the map's stream, for its writes
+  ScanTable scan_table;
+  DevBuf<double> d_real;    // rule 27's present scan
+  PinBuf<double> h_ranges;  // the ranges the zone was deformed by, on request
 };
+
+namespace {
+
+// One deformation but for where the ranges come from: fill() queues them into z->d_ranges on the context's stream, after
+// the angles' upload.  ranges_out: a copy of them for the caller, or nullptr.
+template <typename Fill>
+int dvz_run(kc_dvz *z, const kc_dvz_zone *zone, const double *angles, size_t n, double out[3], double *radii_or_null,
+            double *ranges_out, Fill fill) {
+  hipStream_t s = z->stream;
+  DvzArgs a{};
+  a.minor = zone->minor_radius;
+  a.major = zone->major_radius;
+  a.shift_x = zone->center_shift_x;
+  a.shift_y = zone->center_shift_y;
+  a.ori = zone->ori_shift;
+  // dvz.py:232-236, with the reference's operand order; x ** 2 as x * x
+  a.minor2 = a.minor * a.minor;
+  a.major2 = a.major * a.major;
+  const double cx = a.shift_x * a.minor, cy = a.shift_y * a.major, mm = a.minor * a.major;
+  a.C = cx * cx + cy * cy - mm * mm;
+  a.n = static_cast<int>(n);
+  std::memcpy(z->h_in.p, angles, n * sizeof(double));
+  bool dev_trig = dvz_trig_ok();
+  for (size_t i = 0; dev_trig && i < n; ++i) dev_trig = device_trig_covers(angles[i] - a.ori);
+  KC_HIP(hipMemcpyAsync(z->d_angles.p, z->h_in.p, n * sizeof(double), hipMemcpyHostToDevice, s));
+  KC_TRY(fill());
+  if (!dev_trig) {  // np.cos / np.sin of the reference: the host libm's cos / sin
+    KC_TRY(z->h_trig.reserve(n));
+    KC_TRY(z->d_trig.reserve(n));
+    for (size_t i = 0; i < n; ++i) {
+      const double x = angles[i] - a.ori;
+      z->h_trig.p[i] = make_double2(host_cos(x), host_sin(x));
+    }
+    KC_HIP(hipMemcpyAsync(z->d_trig.p, z->h_trig.p, n * sizeof(double2), hipMemcpyHostToDevice, s));
+    a.trig = z->d_trig.p;
+  }
+  a.angles = z->d_angles.p;
+  a.ranges = z->d_ranges.p;
+  a.tab = z->d_tab.p;
+  a.radii = radii_or_null ? z->d_radii.p : nullptr;
+  a.partial = z->d_partial.p;
+  a.ticket = z->d_ticket.p;
+  a.result = z->d_result.p;
+  const unsigned blocks = static_cast<unsigned>((n + kDvzBlock - 1) / kDvzBlock);
+  hipLaunchKernelGGL(dvz_deform_kernel, dim3(blocks), dim3(kDvzBlock), 0, s, a);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipMemcpyAsync(z->h_result.p, z->d_result.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (radii_or_null) {
+    KC_TRY(z->h_radii.reserve(n));
+    KC_HIP(hipMemcpyAsync(z->h_radii.p, z->d_radii.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (ranges_out) {
+    KC_TRY(z->h_ranges.reserve(n));
+    KC_HIP(hipMemcpyAsync(z->h_ranges.p, z->d_ranges.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  KC_HIP(hipStreamSynchronize(s));
+  std::memcpy(out, z->h_result.p, 3 * sizeof(double));
+  if (radii_or_null) std::memcpy(radii_or_null, z->h_radii.p, n * sizeof(double));
+  if (ranges_out) std::memcpy(ranges_out, z->h_ranges.p, n * sizeof(double));
+  return KC_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -234,54 +302,52 @@ int kc_dvz_deform(kc_dvz *z, const kc_dvz_zone *zone, const double *angles, cons
   out[0] = out[1] = out[2] = 0.0;
   if (n == 0) return KC_OK;
   KC_HIP(hipSetDevice(z->device));
-  hipStream_t s = z->stream;
-  DvzArgs a{};
-  a.minor = zone->minor_radius;
-  a.major = zone->major_radius;
-  a.shift_x = zone->center_shift_x;
-  a.shift_y = zone->center_shift_y;
-  a.ori = zone->ori_shift;
-  // dvz.py:232-236, with the reference's operand order; x ** 2 as x * x
-  a.minor2 = a.minor * a.minor;
-  a.major2 = a.major * a.major;
-  const double cx = a.shift_x * a.minor, cy = a.shift_y * a.major, mm = a.minor * a.major;
-  a.C = cx * cx + cy * cy - mm * mm;
-  a.n = static_cast<int>(n);
-  std::memcpy(z->h_in.p, angles, n * sizeof(double));
-  std::memcpy(z->h_in.p + n, ranges, n * sizeof(double));
-  bool dev_trig = dvz_trig_ok();
-  for (size_t i = 0; dev_trig && i < n; ++i) dev_trig = device_trig_covers(angles[i] - a.ori);
-  KC_HIP(hipMemcpyAsync(z->d_angles.p, z->h_in.p, n * sizeof(double), hipMemcpyHostToDevice, s));
-  KC_HIP(hipMemcpyAsync(z->d_ranges.p, z->h_in.p + n, n * sizeof(double), hipMemcpyHostToDevice, s));
-  if (!dev_trig) {  // np.cos / np.sin of the reference: the host libm's cos / sin
-    KC_TRY(z->h_trig.reserve(n));
-    KC_TRY(z->d_trig.reserve(n));
-    for (size_t i = 0; i < n; ++i) {
-      const double x = angles[i] - a.ori;
-      z->h_trig.p[i] = make_double2(host_cos(x), host_sin(x));
+  return dvz_run(z, zone, angles, n, out, radii_or_null, nullptr, [&]() -> int {
+    std::memcpy(z->h_in.p + n, ranges, n * sizeof(double));
+    KC_HIP(hipMemcpyAsync(z->d_ranges.p, z->h_in.p + n, n * sizeof(double), hipMemcpyHostToDevice, z->stream));
+    return KC_OK;
+  });
+}
+
+// Check order: null arguments; the count, the zone, the scan's own refusals, the angles, the pose; the map's device; then
+// the device
+int kc_dvz_deform_worldmap(kc_dvz *z, const kc_dvz_zone *zone, kc_worldmap *map, const kc_worldmap_pose *pose,
+                           const double *angles, size_t n, float range_max, unsigned int flags, const double *real_or_null,
+                           double out[3], double *radii_or_null, double *ranges_or_null) {
+  if (!z || !zone || !map || !pose || !angles || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (n > z->cap) KC_FAIL(KC_ERR_RANGE, "%zu beams for a context of %zu", n, z->cap);
+  if (!(zone->minor_radius > 0.0) || !(zone->major_radius > 0.0))
+    KC_FAIL(KC_ERR_INVALID, "zone radii must be positive (minor %g, major %g)", zone->minor_radius,
+            zone->major_radius);
+  WorldMapView v{};
+  KC_TRY(worldmap_view(map, &v));
+  WorldMapScan sc{};
+  KC_TRY(worldmap_scan_check(v.res, 1, n, range_max, flags, &sc.rc));
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
+  KC_TRY(worldmap_check_pose(pose));
+  if (v.device != z->device) KC_FAIL(KC_ERR_INVALID, "world map on device %d, DVZ context on device %d", v.device, z->device);
+  out[0] = out[1] = out[2] = 0.0;
+  KC_HIP(hipSetDevice(z->device));
+  if (real_or_null) KC_TRY(z->d_real.reserve(n));
+  return dvz_run(z, zone, angles, n, out, radii_or_null, ranges_or_null, [&]() -> int {
+    hipStream_t s = z->stream;
+    KC_TRY(z->scan_table.ensure(angles, n, s));
+    if (real_or_null) {
+      std::memcpy(z->h_in.p + n, real_or_null, n * sizeof(double));
+      KC_HIP(hipMemcpyAsync(z->d_real.p, z->h_in.p + n, n * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    KC_HIP(hipMemcpyAsync(z->d_trig.p, z->h_trig.p, n * sizeof(double2), hipMemcpyHostToDevice, s));
-    a.trig = z->d_trig.p;
-  }
-  a.angles = z->d_angles.p;
-  a.ranges = z->d_ranges.p;
-  a.tab = z->d_tab.p;
-  a.radii = radii_or_null ? z->d_radii.p : nullptr;
-  a.partial = z->d_partial.p;
-  a.ticket = z->d_ticket.p;
-  a.result = z->d_result.p;
-  const unsigned blocks = static_cast<unsigned>((n + kDvzBlock - 1) / kDvzBlock);
-  hipLaunchKernelGGL(dvz_deform_kernel, dim3(blocks), dim3(kDvzBlock), 0, s, a);
-  KC_HIP(hipGetLastError());
-  KC_HIP(hipMemcpyAsync(z->h_result.p, z->d_result.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (radii_or_null) {
-    KC_TRY(z->h_radii.reserve(n));
-    KC_HIP(hipMemcpyAsync(z->h_radii.p, z->d_radii.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  KC_HIP(hipStreamSynchronize(s));
-  std::memcpy(out, z->h_result.p, 3 * sizeof(double));
-  if (radii_or_null) std::memcpy(radii_or_null, z->h_radii.p, n * sizeof(double));
-  return KC_OK;
+    KC_TRY(stream_wait_through(z->map_ready, s, v.stream));  // for the map's writes; the host does not wait
+    sc.table = z->scan_table.d.p;
+    sc.pose = *pose;
+    sc.n_poses = 1;
+    sc.n_beams = n;
+    sc.range_max = range_max;
+    sc.flags = flags;
+    sc.real = real_or_null ? z->d_real.p : nullptr;
+    sc.ranges = z->d_ranges.p;
+    return worldmap_queue_scan(v, sc, s);
+  });
 }
 
 }  // extern "C"

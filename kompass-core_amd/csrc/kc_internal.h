@@ -367,6 +367,39 @@ int worldmap_window(const WorldMapView &v, double x, double y, float max_range, 
 // grid_points_publish_kernel serves both).  rearm: another such block the launch puts back to those values, or nullptr.
 int worldmap_queue_points(const WorldMapView &v, const WorldMapWindow &w, float *xyz, unsigned int *cnt, unsigned int *rearm,
                           hipStream_t stream);
+// ---- the map's virtual laser scan (kc_worldmap.hip (g); DESIGN.md 4.11 rules 20 to 27) ----
+// rule 21's table of one angle array, kept by whoever scans with it: ensure() forms and uploads it again only when the
+// bytes of `angles` differ from those it was formed from.  The upload is queued on `s`; the pinned copy is rewritten by
+// the host, so the owner's entries return with their stream drained (all of them do).
+struct ScanTable {
+  std::vector<double> angles;  // what the table was formed from
+  PinBuf<int32_t> h;           // (ac_k, as_k) pairs
+  DevBuf<int32_t> d;
+  bool valid = false;
+  int ensure(const double *a, size_t n, hipStream_t s);
+};
+// rule 21 on the host: KC_ERR_INVALID for a non-finite angle, and then nothing is written
+int worldmap_scan_table(const double *angles, size_t n, int32_t *ac_as_out);
+// the refusals of rules 20, 21 and 25, in that order: counts, range_max, flags
+int worldmap_scan_check(float res, size_t n_poses, size_t n_beams, float range_max, unsigned flags, int *rc_out);
+// wm_check_pose: what every pose handed to the map must satisfy
+int worldmap_check_pose(const kc_worldmap_pose *p);
+struct WorldMapScan {
+  const int32_t *table;               // the device copy of a ScanTable of n_beams pairs
+  const kc_worldmap_pose *dev_poses;  // n_poses poses on the device; nullptr: the one pose below, in the kernel arguments
+  kc_worldmap_pose pose;
+  size_t n_poses, n_beams;
+  int rc;                             // rule 20's Rc, from worldmap_scan_check
+  float range_max;
+  unsigned flags;
+  const double *real;                 // rule 27: n_beams present ranges on the device (one pose only), or nullptr
+  double *ranges;                     // [n_poses * n_beams]
+  int32_t *cells;                     // the same count, or nullptr
+};
+// Queues the one launch on `stream` (the caller's: it orders the launch after the map's writes itself).  Every argument
+// has been checked by then.
+int worldmap_queue_scan(const WorldMapView &v, const WorldMapScan &s, hipStream_t stream);
+
 // rule 18: the coordinate of cell index k along one axis
 __host__ __device__ inline float worldmap_cell_coord(double origin, int k, double res) {
   return static_cast<float>(origin + static_cast<double>(k) * res);

@@ -403,6 +403,120 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_window_points_kernel(WmWind
   }
 }
 
+// ---- virtual laser scan (rules 20 to 27) -------------------------------------------------------------------------
+constexpr int kWmScanBlock = 256;          // beams a workgroup
+constexpr int kWmScanS = 8;                // steps of the walk a round: their byte loads are in flight together
+constexpr int kWmScanEnd = 1;              // a step outside rule 23's box; no cls byte has this value
+constexpr size_t kWmScanMaxBeams = 65536;
+constexpr size_t kWmScanMaxRays = size_t{1} << 22;
+
+struct WmScanArgs {
+  const int8_t *cls;
+  const int2 *table;              // rule 21: (ac, as) a beam
+  const kc_worldmap_pose *poses;  // a batch on the device; nullptr: pose
+  kc_worldmap_pose pose;
+  const double *real;             // rule 27, or nullptr
+  double *ranges;
+  int32_t *cells;                 // or nullptr
+  int W, H, B, rc, unknown_blocks;
+  double res, range_max;
+};
+
+// rule 24: e * 16384 is exact (e < 2^28), then one division and one product
+__device__ __forceinline__ double wm_scan_range(int e, int a, double res) {
+  return (static_cast<double>(e) * 16384.0 / static_cast<double>(a)) * res;
+}
+
+__device__ __forceinline__ bool wm_scan_blocks(int v, int unknown_blocks) {
+  return v == KC_OCCUPIED || (unknown_blocks && v == KC_UNEXPLORED);
+}
+
+// blockIdx.x: the pose; blockIdx.y * 256 + threadIdx.x: the beam.  The walk's addresses do not depend on the bytes it
+// loads, so a round forms kWmScanS steps ahead, loads their bytes together (a step outside the map loads cell 0 and drops
+// it: no branch around a load), and only then looks for the first one that ends the beam.  D = ex |dy| - ey |dx| is kept
+// by addition.  Between rounds the walk also ends once the last step's own r is above range_max: r never decreases along
+// a walk (rule 24), so no later cell could count, and the output is that of the full box.
+__global__ __launch_bounds__(kWmScanBlock) void worldmap_scan_kernel(WmScanArgs a) {
+  const int k = static_cast<int>(blockIdx.y) * kWmScanBlock + static_cast<int>(threadIdx.x);
+  if (k >= a.B) return;
+  const kc_worldmap_pose p = a.poses ? a.poses[blockIdx.x] : a.pose;
+  const int2 t = a.table[k];
+  const long long cq = p.cq, sq = p.sq;
+  const int dx = static_cast<int>((cq * t.x - sq * t.y + (1ll << 15)) >> 16);
+  const int dy = static_cast<int>((sq * t.x + cq * t.y + (1ll << 15)) >> 16);
+  const long long X0 = p.tx + (1ll << 15), Y0 = p.ty + (1ll << 15);
+  const int I0 = static_cast<int>(X0 >> 16), J0 = static_cast<int>(Y0 >> 16);
+  const int fx = static_cast<int>(X0 & 0xFFFF), fy = static_cast<int>(Y0 & 0xFFFF);
+  const int sx = dx > 0 ? 1 : -1, sy = dy > 0 ? 1 : -1;
+  const int adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
+  int ex = dx > 0 ? 65536 - fx : fx, ey = dy > 0 ? 65536 - fy : fy;
+  long long D = static_cast<long long>(ex) * ady - static_cast<long long>(ey) * adx;
+  const long long step_x = 65536ll * ady, step_y = 65536ll * adx;
+  const bool only_x = dy == 0, only_y = dx == 0;
+  const int box = a.rc + 1;
+  int I = I0, J = J0;
+  bool hit = false, done = false;
+  double r = 0.0;
+  int hit_i = I0, hit_j = J0;
+  if (I0 >= 0 && I0 < a.W && J0 >= 0 && J0 < a.H &&
+      wm_scan_blocks(a.cls[static_cast<size_t>(I0) + static_cast<size_t>(J0) * static_cast<size_t>(a.W)], a.unknown_blocks))
+    hit = done = true;  // rule 23: e = 0
+  // every step leaves a cell, so 2 (Rc + 2) steps leave the box along one axis: the count only bounds the loop
+  const int max_rounds = (2 * (a.rc + 2)) / kWmScanS + 2;
+  for (int round = 0; round < max_rounds && !done; ++round) {
+    const int Is = I, Js = J;
+    int es[kWmScanS], v[kWmScanS];
+    unsigned xmask = 0u;
+#pragma unroll
+    for (int s = 0; s < kWmScanS; ++s) {
+      if (only_x || (!only_y && D <= 0)) {
+        es[s] = ex;
+        I += sx;
+        ex += 65536;
+        D += step_x;
+        xmask |= 1u << s;
+      } else {
+        es[s] = ey;
+        J += sy;
+        ey += 65536;
+        D -= step_y;
+      }
+      const int di = I - I0, dj = J - J0;
+      const bool out = di > box || di < -box || dj > box || dj < -box;
+      const bool in = !out && I >= 0 && I < a.W && J >= 0 && J < a.H;
+      const size_t cell = in ? static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W) : size_t{0};
+      const int byte = a.cls[cell];
+      v[s] = out ? kWmScanEnd : (in ? byte : static_cast<int>(KC_EMPTY));
+    }
+#pragma unroll
+    for (int s = 0; s < kWmScanS; ++s) {
+      if (done) continue;
+      if (v[s] == kWmScanEnd) {
+        done = true;
+      } else if (wm_scan_blocks(v[s], a.unknown_blocks)) {
+        done = true;
+        const int nx = __popc(xmask & ((2u << s) - 1u));
+        const double rr = wm_scan_range(es[s], (xmask >> s) & 1u ? adx : ady, a.res);
+        if (rr <= a.range_max) {
+          hit = true;
+          r = rr;
+          hit_i = Is + sx * nx;
+          hit_j = Js + sy * (s + 1 - nx);
+        }
+      }
+    }
+    if (!done && wm_scan_range(es[kWmScanS - 1], (xmask >> (kWmScanS - 1)) & 1u ? adx : ady, a.res) > a.range_max) done = true;
+  }
+  double out = hit ? r : a.range_max;
+  if (a.real) {  // rule 27: a NaN compares false, an infinity is left out by name
+    const double q = a.real[k];
+    if (isfinite(q) && q < out) out = q;
+  }
+  const size_t slot = static_cast<size_t>(blockIdx.x) * static_cast<size_t>(a.B) + static_cast<size_t>(k);
+  a.ranges[slot] = out;
+  if (a.cells) a.cells[slot] = hit ? hit_i + hit_j * a.W : -1;
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -429,6 +543,12 @@ struct kc_worldmap {
   // obstacle list (rules 16 to 19): scratch grown on demand and kept
   DevBuf<float> d_pts;             // the list of the last kc_worldmap_points
   FlipRecord pts_rec;              // the list's counters: 5 lines of kWmPtsStride words a block
+  // virtual scan (rules 20 to 27): the table of the last angle array, scratch grown on demand and kept
+  ScanTable scan_table;
+  DevBuf<kc_worldmap_pose> d_poses;
+  PinBuf<kc_worldmap_pose> h_poses;
+  DevBuf<double> d_scan;           // the ranges, behind them the cells as int32: one read-back
+  PinBuf<double> h_scan;
 };
 
 namespace {
@@ -852,6 +972,78 @@ int worldmap_queue_points(const WorldMapView &v, const WorldMapWindow &w, float 
   return KC_OK;
 }
 
+// ---- virtual scan (rules 20 to 27) ----
+namespace {
+// libm's separate cos and sin through pointers, so that the compiler cannot fold the pair into one sincos call (whose
+// bits differ from theirs in about 0.1 % of arguments where glibc picks its FMA builds: kc_dvz.hip has the story)
+double (*volatile scan_cos)(double) = static_cast<double (*)(double)>(std::cos);
+double (*volatile scan_sin)(double) = static_cast<double (*)(double)>(std::sin);
+}  // namespace
+
+int worldmap_scan_table(const double *angles, size_t n, int32_t *out) {
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
+  for (size_t k = 0; k < n; ++k) {
+    out[2 * k] = static_cast<int32_t>(std::lrint(scan_cos(angles[k]) * 1073741824.0));
+    out[2 * k + 1] = static_cast<int32_t>(std::lrint(scan_sin(angles[k]) * 1073741824.0));
+  }
+  return KC_OK;
+}
+
+int worldmap_scan_check(float res, size_t n_poses, size_t n_beams, float range_max, unsigned flags, int *rc_out) {
+  if (!(res > 0.0f) || !std::isfinite(res)) KC_FAIL(KC_ERR_INVALID, "the resolution must be positive");
+  if (n_poses == 0 || n_beams == 0) KC_FAIL(KC_ERR_INVALID, "a scan needs at least one pose and one beam, got %zu x %zu", n_poses, n_beams);
+  if (n_beams > kWmScanMaxBeams) KC_FAIL(KC_ERR_RANGE, "%zu beams are above the cap of %zu", n_beams, kWmScanMaxBeams);
+  if (n_poses > kWmScanMaxRays || n_poses * n_beams > kWmScanMaxRays)
+    KC_FAIL(KC_ERR_RANGE, "%zu poses x %zu beams are above the cap of %zu rays", n_poses, n_beams, kWmScanMaxRays);
+  if (!std::isfinite(range_max) || !(range_max > 0.0f))
+    KC_FAIL(KC_ERR_INVALID, "range_max must be a finite float > 0, got %g", static_cast<double>(range_max));
+  const double cells = std::ceil(static_cast<double>(range_max) / static_cast<double>(res));
+  if (!(cells <= static_cast<double>(kWmPtsMaxRadius)))
+    KC_FAIL(KC_ERR_RANGE, "a range of %g m is %g cells at %g m, above the cap of %d", static_cast<double>(range_max), cells,
+            static_cast<double>(res), kWmPtsMaxRadius);
+  if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS)) KC_FAIL(KC_ERR_INVALID, "unknown scan flag bits 0x%x", flags);
+  if (rc_out) *rc_out = static_cast<int>(cells);
+  return KC_OK;
+}
+
+int worldmap_check_pose(const kc_worldmap_pose *p) { return wm_check_pose(p); }
+
+int ScanTable::ensure(const double *a, size_t n, hipStream_t s) {
+  if (valid && angles.size() == n && std::memcmp(angles.data(), a, n * sizeof(double)) == 0) return KC_OK;
+  valid = false;
+  KC_HIP(hipStreamSynchronize(s));  // an upload of the pinned copy that a failed call left queued
+  KC_TRY(h.reserve(2 * n));
+  KC_TRY(d.reserve(2 * n));
+  KC_TRY(worldmap_scan_table(a, n, h.p));
+  KC_HIP(hipMemcpyAsync(d.p, h.p, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  angles.assign(a, a + n);
+  valid = true;
+  return KC_OK;
+}
+
+int worldmap_queue_scan(const WorldMapView &v, const WorldMapScan &s, hipStream_t stream) {
+  WmScanArgs a{};
+  a.cls = v.cls;
+  a.table = reinterpret_cast<const int2 *>(s.table);
+  a.poses = s.dev_poses;
+  a.pose = s.pose;
+  a.real = s.real;
+  a.ranges = s.ranges;
+  a.cells = s.cells;
+  a.W = v.W;
+  a.H = v.H;
+  a.B = static_cast<int>(s.n_beams);
+  a.rc = s.rc;
+  a.unknown_blocks = (s.flags & KC_SCAN_UNKNOWN_BLOCKS) ? 1 : 0;
+  a.res = static_cast<double>(v.res);
+  a.range_max = static_cast<double>(s.range_max);
+  const dim3 grid(static_cast<unsigned>(s.n_poses), static_cast<unsigned>((s.n_beams + kWmScanBlock - 1) / kWmScanBlock));
+  hipLaunchKernelGGL(worldmap_scan_kernel, grid, dim3(kWmScanBlock), 0, stream, a);
+  KC_HIP(hipGetLastError());
+  return KC_OK;
+}
+
 }  // namespace kc
 
 extern "C" {
@@ -893,6 +1085,58 @@ int kc_worldmap_points(kc_worldmap *c, double x, double y, float max_sensor_rang
   if (cap < n) KC_FAIL(KC_ERR_RANGE, "%zu points do not fit the output capacity %zu", n, cap);
   KC_HIP(hipMemcpyAsync(xyz_out, c->d_pts.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_worldmap_scan_table(const double *angles, size_t n, int32_t *ac_as_out) {
+  if (!angles || !ac_as_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  return worldmap_scan_table(angles, n, ac_as_out);
+}
+
+int kc_worldmap_scan_check(float resolution, size_t n_poses, size_t n_beams, float range_max, unsigned int flags, int32_t *rc_out) {
+  if (rc_out) *rc_out = 0;
+  int rc = 0;
+  KC_TRY(worldmap_scan_check(resolution, n_poses, n_beams, range_max, flags, &rc));
+  if (rc_out) *rc_out = rc;
+  return KC_OK;
+}
+
+// Check order: null arguments; counts, angles, range_max and flags, the poses; then the device
+int kc_worldmap_scan(kc_worldmap *c, const kc_worldmap_pose *poses, size_t n_poses, const double *angles, size_t n_beams,
+                     float range_max, unsigned int flags, double *ranges_out, int32_t *cells_or_null) {
+  if (!c || !poses || !angles || !ranges_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  WorldMapScan s{};
+  KC_TRY(worldmap_scan_check(c->res, n_poses, n_beams, range_max, flags, &s.rc));
+  for (size_t k = 0; k < n_beams; ++k)
+    if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
+  for (size_t p = 0; p < n_poses; ++p) KC_TRY(wm_check_pose(&poses[p]));
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c, &v));
+  KC_HIP(hipSetDevice(c->device));
+  const size_t rays = n_poses * n_beams, words = rays + (cells_or_null ? (rays + 1) / 2 : 0);
+  KC_TRY(c->d_scan.reserve(words));
+  KC_TRY(c->h_scan.reserve(words));
+  KC_TRY(c->scan_table.ensure(angles, n_beams, c->stream));
+  if (n_poses > 1) {
+    KC_TRY(c->d_poses.reserve(n_poses));
+    KC_TRY(c->h_poses.reserve(n_poses));
+    std::memcpy(c->h_poses.p, poses, n_poses * sizeof(kc_worldmap_pose));
+    KC_HIP(hipMemcpyAsync(c->d_poses.p, c->h_poses.p, n_poses * sizeof(kc_worldmap_pose), hipMemcpyHostToDevice, c->stream));
+    s.dev_poses = c->d_poses.p;
+  }
+  s.table = c->scan_table.d.p;
+  s.pose = poses[0];
+  s.n_poses = n_poses;
+  s.n_beams = n_beams;
+  s.range_max = range_max;
+  s.flags = flags;
+  s.ranges = c->d_scan.p;
+  s.cells = cells_or_null ? reinterpret_cast<int32_t *>(c->d_scan.p + rays) : nullptr;
+  KC_TRY(worldmap_queue_scan(v, s, c->stream));
+  KC_HIP(hipMemcpyAsync(c->h_scan.p, c->d_scan.p, words * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  std::memcpy(ranges_out, c->h_scan.p, rays * sizeof(double));
+  if (cells_or_null) std::memcpy(cells_or_null, c->h_scan.p + rays, rays * sizeof(int32_t));
   return KC_OK;
 }
 

@@ -79,7 +79,47 @@ struct kc_zone {
   PinBuf<unsigned int> h_factor;
   kc_cloud *cloud = nullptr;
   std::vector<double> cloud_ranges;
+  // kc_zone_check_worldmap: the map's virtual scan (DESIGN.md 4.11 rules 20 to 27) lands in d_ranges
+  OrderEvent map_ready;   // the map's stream, for its writes
+  ScanTable scan_table;   // of the preset angles, formed at kc_zone_create
+  DevBuf<double> d_real;  // rule 27's present scan
 };
+
+namespace {
+
+// One check but for where the ranges come from: fill() queues the preset's count of them into z->d_ranges on the
+// context's stream.
+template <typename Fill>
+int zone_run(kc_zone *z, int forward, float *factor_out, Fill fill) {
+  const std::vector<int> &idx = forward ? z->fwd : z->bwd;
+  hipStream_t s = z->stream;
+  KC_TRY(fill());
+  const float one = 1.0f;
+  std::memcpy(z->h_factor.p, &one, sizeof(float));
+  KC_HIP(hipMemcpyAsync(z->d_factor.p, z->h_factor.p, sizeof(unsigned int), hipMemcpyHostToDevice, s));
+  ZoneArgs a{};
+  a.ranges = z->d_ranges.p;
+  a.cos_a = z->d_cos.p;
+  a.sin_a = z->d_sin.p;
+  a.idx = forward ? z->d_fwd.p : z->d_bwd.p;
+  a.n_idx = static_cast<int>(idx.size());
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.R[r][c] = z->tf.R[r][c];
+    a.t[r] = z->tf.t[r];
+  }
+  a.robot_radius = z->robot_radius;
+  a.critical_distance = z->critical_distance;
+  a.slowdown_distance = z->slowdown_distance;
+  a.factor_bits = z->d_factor.p;
+  hipLaunchKernelGGL(zone_check_kernel, dim3((a.n_idx + 255) / 256), dim3(256), 0, s, a);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipMemcpyAsync(z->h_factor.p, z->d_factor.p, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  KC_HIP(hipStreamSynchronize(s));
+  std::memcpy(factor_out, z->h_factor.p, sizeof(float));
+  return KC_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -156,6 +196,17 @@ int kc_zone_create(int shape, const float *dims, int ndims, const float sensor_p
       set_error("preset upload failed");
       return fail(KC_ERR_HIP);
     }
+    // rule 21's table of the preset, for kc_zone_check_worldmap; a preset with a non-finite angle has none, and that
+    // entry then refuses
+    bool finite = true;
+    for (size_t i = 0; i < n; ++i) finite = finite && std::isfinite(angles[i]);
+    if (finite) {
+      if ((rc = z->scan_table.ensure(angles, n, stream))) return fail(rc);
+      if (hipStreamSynchronize(stream) != hipSuccess) {
+        set_error("preset upload failed");
+        return fail(KC_ERR_HIP);
+      }
+    }
   }
   *out = z;
   return KC_OK;
@@ -176,32 +227,47 @@ int kc_zone_check(kc_zone *z, const double *ranges, size_t n, int forward, float
   *factor_out = 1.0f;
   if (idx.empty()) return KC_OK;
   KC_HIP(hipSetDevice(z->device));
-  hipStream_t s = z->stream;
-  std::memcpy(z->h_ranges.p, ranges, z->n * sizeof(double));
-  const float one = 1.0f;
-  std::memcpy(z->h_factor.p, &one, sizeof(float));
-  KC_HIP(hipMemcpyAsync(z->d_ranges.p, z->h_ranges.p, z->n * sizeof(double), hipMemcpyHostToDevice, s));
-  KC_HIP(hipMemcpyAsync(z->d_factor.p, z->h_factor.p, sizeof(unsigned int), hipMemcpyHostToDevice, s));
-  ZoneArgs a{};
-  a.ranges = z->d_ranges.p;
-  a.cos_a = z->d_cos.p;
-  a.sin_a = z->d_sin.p;
-  a.idx = forward ? z->d_fwd.p : z->d_bwd.p;
-  a.n_idx = static_cast<int>(idx.size());
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) a.R[r][c] = z->tf.R[r][c];
-    a.t[r] = z->tf.t[r];
-  }
-  a.robot_radius = z->robot_radius;
-  a.critical_distance = z->critical_distance;
-  a.slowdown_distance = z->slowdown_distance;
-  a.factor_bits = z->d_factor.p;
-  hipLaunchKernelGGL(zone_check_kernel, dim3((a.n_idx + 255) / 256), dim3(256), 0, s, a);
-  KC_HIP(hipGetLastError());
-  KC_HIP(hipMemcpyAsync(z->h_factor.p, z->d_factor.p, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-  KC_HIP(hipStreamSynchronize(s));
-  std::memcpy(factor_out, z->h_factor.p, sizeof(float));
-  return KC_OK;
+  return zone_run(z, forward, factor_out, [&]() -> int {
+    std::memcpy(z->h_ranges.p, ranges, z->n * sizeof(double));
+    KC_HIP(hipMemcpyAsync(z->d_ranges.p, z->h_ranges.p, z->n * sizeof(double), hipMemcpyHostToDevice, z->stream));
+    return KC_OK;
+  });
+}
+
+// Check order: null arguments; the scan's own refusals and the pose; the map's device; then the device
+int kc_zone_check_worldmap(kc_zone *z, kc_worldmap *map, const kc_worldmap_pose *pose, unsigned int flags,
+                           const double *real_or_null, int forward, float *factor_out) {
+  if (!z || !map || !pose || !factor_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *factor_out = 1.0f;
+  WorldMapView v{};
+  KC_TRY(worldmap_view(map, &v));
+  WorldMapScan sc{};
+  if (z->n) KC_TRY(worldmap_scan_check(v.res, 1, z->n, z->range_max, flags, &sc.rc));
+  else if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS)) KC_FAIL(KC_ERR_INVALID, "unknown scan flag bits 0x%x", flags);
+  if (z->n && !z->scan_table.valid) KC_FAIL(KC_ERR_INVALID, "the checker's preset holds a non-finite angle");
+  KC_TRY(worldmap_check_pose(pose));
+  if (v.device != z->device) KC_FAIL(KC_ERR_INVALID, "world map on device %d, zone checker on device %d", v.device, z->device);
+  const std::vector<int> &idx = forward ? z->fwd : z->bwd;
+  if (idx.empty()) return KC_OK;
+  KC_HIP(hipSetDevice(z->device));
+  if (real_or_null) KC_TRY(z->d_real.reserve(z->n));
+  return zone_run(z, forward, factor_out, [&]() -> int {
+    hipStream_t s = z->stream;
+    if (real_or_null) {
+      std::memcpy(z->h_ranges.p, real_or_null, z->n * sizeof(double));
+      KC_HIP(hipMemcpyAsync(z->d_real.p, z->h_ranges.p, z->n * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    KC_TRY(stream_wait_through(z->map_ready, s, v.stream));  // for the map's writes; the host does not wait
+    sc.table = z->scan_table.d.p;
+    sc.pose = *pose;
+    sc.n_poses = 1;
+    sc.n_beams = z->n;
+    sc.range_max = z->range_max;
+    sc.flags = flags;
+    sc.real = real_or_null ? z->d_real.p : nullptr;
+    sc.ranges = z->d_ranges.p;
+    return worldmap_queue_scan(v, sc, s);
+  });
 }
 
 int kc_zone_check_cloud(kc_zone *z, const int8_t *data, size_t nbytes, int point_step,

@@ -13,6 +13,7 @@ import kompass_cpp
 from ..algorithms import DeformableVirtualZone, DeformableVirtualZoneParams
 from ..algorithms.dvz import _to_0_2pi
 from ..datatypes.laserscan import LaserScanData
+from ..mapping.world_map import WorldMap, cpp_world_map
 from ..models import Robot, RobotCtrlLimits, RobotState
 from ._base_ import FollowerTemplate
 from .stanley import Stanley, StanleyConfig
@@ -71,8 +72,17 @@ class DVZ(FollowerTemplate):
     def set_path(self, global_path, **_) -> None:
         self.__reference_cmd_generator.set_path(global_path=global_path)
 
-    def loop_step(self, *, laser_scan: LaserScanData, current_state: RobotState,
+    def loop_step(self, *, laser_scan: Optional[LaserScanData] = None, current_state: RobotState, local_map=None,
                   initial_control_seq: Optional[np.ndarray] = None, debug: bool = False, **_) -> bool:
+        """local_map (not in the reference): a `WorldMap`; the zone is then deformed by the map's virtual scan at
+        current_state (DESIGN.md 4.11 rules 20 to 27) over laser_scan's angles, or 360 beams over [0, 2 pi) without
+        one, merged with laser_scan's ranges by a per-beam minimum when it has them.  Without local_map the step is
+        the reference's and laser_scan is required."""
+        world_map = cpp_world_map(local_map)
+        if world_map is not None:
+            laser_scan = self._scan_from_map(local_map, laser_scan, current_state)
+        elif laser_scan is None:
+            raise TypeError("DVZ.loop_step() missing 1 required keyword-only argument: 'laser_scan'")
         if initial_control_seq is not None:
             seq = np.asarray(initial_control_seq)
             ref_linear_x = seq[0, 0]
@@ -88,6 +98,28 @@ class DVZ(FollowerTemplate):
                                                                         self._control_time_step)
         self._dvz_angular = self._path_controller.compute_angular_control(ref_angular)
         return True
+
+    @staticmethod
+    def _scan_from_map(local_map, laser_scan: Optional[LaserScanData], current_state: RobotState) -> LaserScanData:
+        """The scan the zone sees with a world map: the map's ranges at current_state, under the present ones where
+        those are nearer.  The ranges come to the host (`WorldMap.scan`) and go the usual way from there; the route
+        that keeps them on the device is `kompass_hip.DvzContext.deform_worldmap`."""
+        front = local_map if isinstance(local_map, WorldMap) else None
+        if laser_scan is None:
+            angles = np.arange(360) * (2 * np.pi / 360)
+            range_max = LaserScanData().range_max
+        else:
+            if laser_scan.angles.any():
+                angles = laser_scan.angles
+            else:
+                angles = _to_0_2pi(np.arange(laser_scan.angle_min, laser_scan.angle_max, laser_scan.angle_increment))
+            range_max = laser_scan.range_max
+        pose = (float(current_state.x), float(current_state.y), float(current_state.yaw))
+        a = np.ascontiguousarray(angles, dtype=np.float64)
+        ranges = front.scan(pose, a, range_max) if front is not None else cpp_world_map(local_map).scan(*pose, a, float(range_max))
+        if laser_scan is not None and laser_scan.ranges.size == a.size:
+            ranges = WorldMap.merge_scan(laser_scan.ranges, ranges)
+        return LaserScanData(range_max=range_max, ranges=ranges, angles=a)
 
     def _get_dvz_deformation(self, laser_scan_data: LaserScanData, debug: bool = False) -> None:
         if laser_scan_data.angles.any():

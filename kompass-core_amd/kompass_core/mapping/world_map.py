@@ -126,6 +126,43 @@ class WorldMap:
         map itself and extract the same list on the device."""
         return self._map.points(float(robot_state.x), float(robot_state.y), float(max_range))
 
+    @staticmethod
+    def _pose(robot_state) -> Tuple[float, float, float]:
+        if hasattr(robot_state, "yaw"):
+            return float(robot_state.x), float(robot_state.y), float(robot_state.yaw)
+        x, y, yaw = robot_state
+        return float(x), float(y), float(yaw)
+
+    def scan(self, robot_state, angles, range_max: float, unknown_blocks: bool = False, return_cells: bool = False):
+        """The map's virtual laser scan (DESIGN.md 4.11 rules 20 to 27): what a lidar whose frame is at robot_state
+        (x, y, yaw) would range along the beam `angles` (radians, in that frame), by the map's memory -> float64 [B]: the
+        distance to the first occupied cell within range_max, else range_max.  unknown_blocks: a never-observed cell
+        ends a beam as well.  return_cells: -> (ranges, int32 [B] of the hit cells I + J * width, -1 without a hit).
+        One launch on the device."""
+        a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        return self._map.scan(*self._pose(robot_state), a, float(range_max), bool(unknown_blocks), bool(return_cells))
+
+    def scans(self, poses, angles, range_max: float, unknown_blocks: bool = False) -> np.ndarray:
+        """The same for M poses (robot states or (x, y, yaw)) in one launch -> float64 [M, B]."""
+        a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        return self._map.scans([self._pose(p) for p in poses], a, float(range_max), bool(unknown_blocks))
+
+    def laser_scan(self, robot_state, angles=None, range_max: float = 20.0, unknown_blocks: bool = False):
+        """`scan` as a `LaserScanData`; angles: default 360 beams over [0, 2 pi)."""
+        from ..datatypes.laserscan import LaserScanData
+
+        a = np.arange(360) * (2 * math.pi / 360) if angles is None else np.asarray(angles, dtype=float).reshape(-1)
+        inc = float(a[1] - a[0]) if a.size > 1 else 0.0
+        return LaserScanData(angle_min=float(a[0]), angle_max=float(a[-1]), angle_increment=inc, range_max=float(range_max),
+                             ranges=self.scan(robot_state, a, range_max, unknown_blocks), angles=a)
+
+    @staticmethod
+    def merge_scan(present, from_map) -> np.ndarray:
+        """Rule 27: per beam the present range where it is finite and below the map's, else the map's."""
+        q, v = np.asarray(present, dtype=np.float64), np.asarray(from_map, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            return np.where(np.isfinite(q) & (q < v), q, v)
+
     @property
     def occupancy(self) -> np.ndarray:
         """A host copy of the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied."""

@@ -305,6 +305,13 @@ SIGNATURES = {
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "kc_worldmap_points": (C.c_int, [_vp, C.c_double, C.c_double, C.c_float, C.c_void_p, _sz, C.POINTER(_sz),
                                      C.POINTER(C.c_int32)]),
+    "kc_worldmap_scan_table": (C.c_int, [_dp, _sz, _ip]),
+    "kc_worldmap_scan_check": (C.c_int, [C.c_float, _sz, _sz, C.c_float, C.c_uint, _ip]),
+    "kc_worldmap_scan": (C.c_int, [_vp, C.POINTER(WorldMapPose), _sz, _dp, _sz, C.c_float, C.c_uint, _dp, _ip]),
+    "kc_dvz_deform_worldmap": (C.c_int, [_vp, C.POINTER(DvzZone), _vp, C.POINTER(WorldMapPose), _dp, _sz, C.c_float,
+                                         C.c_uint, _dp, _dp, _dp, _dp]),
+    "kc_zone_check_worldmap": (C.c_int, [_vp, _vp, C.POINTER(WorldMapPose), C.c_uint, _dp, C.c_int,
+                                         C.POINTER(C.c_float)]),
     "kc_worldmap_match_check_window": (C.c_int, [C.c_int, C.c_double, C.c_int]),
     "kc_worldmap_match_check_grid": (C.c_int, [C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "kc_worldmap_match_rotations": (C.c_int, [C.c_double, C.c_int, C.c_double, C.POINTER(WorldMapRotation), _sz]),
@@ -1086,6 +1093,18 @@ class ZoneContext(_Owner):
         r = _f64(ranges)
         return float(_out(C.c_float, lib().kc_zone_check, self.h, _pd(r), len(r), int(bool(forward))))
 
+    def check_worldmap(self, worldmap: "WorldMapContext", pose, forward, unknown_blocks=False, real=None,
+                       flags=None) -> float:
+        """check() on the virtual scan of `worldmap` at the scan frame's `pose` ((x, y, yaw) or a WorldMapPose) over the
+        preset angles and range_max (DESIGN.md 4.11 rules 20 to 27).  real: the preset's count of present ranges to
+        merge by rule 27."""
+        q = None if real is None else _f64(real).reshape(-1)
+        if q is not None and len(q) != self.n:
+            raise ValueError(f"{len(q)} present ranges for a preset of {self.n} angles")
+        p = worldmap._pose(pose)
+        return float(_out(C.c_float, lib().kc_zone_check_worldmap, self.h, worldmap.h, C.byref(p),
+                          _scan_flags(unknown_blocks, flags), _pd(q), int(bool(forward))))
+
     def check_cloud(self, data, point_step, row_step, height, width, x_offset, y_offset, z_offset, forward,
                     field_type=7) -> float:
         buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.int8) if not isinstance(data, np.ndarray)
@@ -1184,6 +1203,26 @@ class DvzContext(_Owner):
         rad = np.zeros(max(len(a), 1)) if radii else None
         _check(lib().kc_dvz_deform(self.h, C.byref(z), _pd(a), _pd(r), len(a), out, _pd(rad)))
         res = (float(out[0]), float(out[1]), int(out[2]))
+        return res + (rad[:len(a)],) if radii else res
+
+    def deform_worldmap(self, zone, worldmap: "WorldMapContext", pose, angles, range_max, unknown_blocks=False, real=None,
+                        radii=False, flags=None):
+        """deform() on the virtual scan of `worldmap` at `pose` ((x, y, yaw) or a WorldMapPose; DESIGN.md 4.11 rules 20 to
+        27), queued on this context's stream without the ranges leaving the device.  real: present ranges to merge by
+        rule 27.  -> (total, orientation_sum, n_deformed, ranges[, radii])."""
+        z = zone if isinstance(zone, DvzZone) else DvzZone(*(float(v) for v in zone))
+        a = _f64(angles).reshape(-1)
+        q = None if real is None else _f64(real).reshape(-1)
+        if q is not None and len(q) != len(a):
+            raise ValueError(f"{len(a)} angles and {len(q)} present ranges")
+        p = worldmap._pose(pose)
+        out = (C.c_double * 3)()
+        rad = np.zeros(max(len(a), 1)) if radii else None
+        rng = np.zeros(max(len(a), 1))
+        _check(lib().kc_dvz_deform_worldmap(self.h, C.byref(z), worldmap.h, C.byref(p), _pd(a), len(a),
+                                            float(np.float32(range_max)), _scan_flags(unknown_blocks, flags), _pd(q), out,
+                                            _pd(rad), _pd(rng)))
+        res = (float(out[0]), float(out[1]), int(out[2]), rng[:len(a)])
         return res + (rad[:len(a)],) if radii else res
 
 
@@ -1399,6 +1438,28 @@ def worldmap_window(resolution, origin, x, y, max_sensor_range):
     return ic.value, jc.value, rc.value
 
 
+SCAN_UNKNOWN_BLOCKS = 1  # KC_SCAN_UNKNOWN_BLOCKS
+
+
+def worldmap_scan_table(angles):
+    """Rule 21 (host only): int32 [n, 2] of (ac_k, as_k) = lrint(cos(a_k) 2^30), lrint(sin(a_k) 2^30)."""
+    a = _f64(angles).reshape(-1)
+    out = np.zeros((len(a), 2), np.int32)
+    if len(a):
+        _check(lib().kc_worldmap_scan_table(_pd(a), len(a), out.ctypes.data_as(_ip)))
+    return out
+
+
+def worldmap_scan_check(resolution, n_poses, n_beams, range_max, flags=0):
+    """The refusals of rules 20, 21 and 25 (host only) -> Rc; raises ValueError / IndexError."""
+    return int(_out(C.c_int32, lib().kc_worldmap_scan_check, float(np.float32(resolution)), int(n_poses), int(n_beams),
+                    float(np.float32(range_max)), int(flags)))
+
+
+def _scan_flags(unknown_blocks, flags):
+    return int(flags) if flags is not None else (SCAN_UNKNOWN_BLOCKS if unknown_blocks else 0)
+
+
 def worldmap_match_check_window(n_yaw, yaw_step, reach):
     """Rule 10's ranges of a match's window (host only); raises ValueError."""
     _check(lib().kc_worldmap_match_check_window(int(n_yaw), float(yaw_step), int(reach)))
@@ -1553,6 +1614,23 @@ class WorldMapContext(_Owner, _StreamOrdered):
         out = np.empty((int(cap), 3), np.float32)
         _check(lib().kc_worldmap_points(*args, out.ctypes.data if out.size else None, int(cap), C.byref(n), b))
         return out[:int(n.value)], tuple(int(v) for v in b)
+
+    def scan(self, poses, angles, range_max, unknown_blocks=False, return_cells=False, flags=None):
+        """Rules 20 to 27: the map's virtual laser scan.  poses: one (x, y, yaw) or WorldMapPose -> float64 [B]; a
+        sequence of them -> [M, B].  return_cells: also the hit cells I + J * width, int32, -1 for no hit.  flags: the
+        raw flag word instead of unknown_blocks."""
+        single = isinstance(poses, WorldMapPose) or (len(poses) == 3 and np.ndim(poses[0]) == 0)
+        plist = [self._pose(p) for p in ([poses] if single else poses)]
+        arr = (WorldMapPose * max(len(plist), 1))(*plist)
+        a = _f64(angles).reshape(-1)
+        shape = (len(a),) if single else (len(plist), len(a))
+        r = np.zeros(max(len(plist) * len(a), 1))
+        c = np.zeros(r.size, np.int32) if return_cells else None
+        _check(lib().kc_worldmap_scan(self.h, arr, len(plist), _pd(a), len(a), float(np.float32(range_max)),
+                                      _scan_flags(unknown_blocks, flags), _pd(r),
+                                      c.ctypes.data_as(_ip) if return_cells else None))
+        n = len(plist) * len(a)
+        return (r[:n].reshape(shape), c[:n].reshape(shape)) if return_cells else r[:n].reshape(shape)
 
     def grid_device_ptr(self) -> int:
         """The cls plane on the device: int8, (width, height), what PlannerContext.set_grid_device(ptr, width, height,

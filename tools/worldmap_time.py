@@ -29,7 +29,20 @@ the robot in the middle, max_sensor_range 10 m (Rc = 200).  One JSON line with
 Every repetition ends with a device synchronisation inside the timed span, so the controller's entries are timed with
 the sensor build they queue.  The lists of (a) to (c) are compared with the statement once.
 
-  python tools/worldmap_time.py --points [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --points [--reps 30] [--warmup 3]
+
+--scan times the virtual laser scan instead (rules 20 to 27): the same world holding what the 400 x 400 local grid saw,
+the scan frame in the middle, range_max 10 m (Rc = 200).  One JSON line with
+  (a) kc_worldmap_scan to the host at 360, 1440 and 4096 beams;
+  (b) a batch of 1024 poses x 360 beams in one launch;
+  (c) kc_dvz_deform_worldmap against kc_worldmap_scan followed by kc_dvz_deform, and kc_zone_check_worldmap against
+      kc_worldmap_scan followed by kc_zone_check, at 360 beams;
+  (d) the route without it: kc_worldmap_get of the class plane alone, and the Python statement of the rules
+      (tests/worldmap_scan_ref.py, one loop a beam on one CPU thread: a Python statement's cost, not a compiled CPU
+      implementation) timed once.
+The ranges of (a) at 360 beams are compared with the statement once.
+
+  python tools/worldmap_time.py --scan [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -48,6 +61,7 @@ import synthetic as syn  # noqa: E402
 import worldmap_match_ref as mref  # noqa: E402
 import worldmap_points_ref as pref  # noqa: E402
 import worldmap_ref as ref  # noqa: E402
+import worldmap_scan_ref as sref  # noqa: E402
 from helpers import DeviceArray, hip_context, hip_runtime  # noqa: E402
 
 W, H, RES, ORIGIN = 2004, 1204, 0.05, (-50.0, -30.0)
@@ -179,6 +193,60 @@ def points_leg(args):
         print(json.dumps(line), flush=True)
 
 
+def scan_leg(args):
+    ang, rng = syn.dense_scan(2048, 1.2)
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r, ORIGIN[1] + (H // 2) * r)
+    pose = centre + (0.3,)
+    range_max = 10.0
+    zone = (1.2, 0.8, 0.1, -0.05, 0.3)
+
+    def beams(n):
+        return np.arange(n) * (2 * np.pi / n)
+
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as wm, \
+            kh.DvzContext(max_beams=4096) as dvz, \
+            kh.ZoneContext(kh.CYLINDER, [0.2, 0.4], [0, 0, 0], [0, 0, 0, 1], 160.0, 0.3, 1.0, beams(360), 0.0, 2.0, range_max) as zc:
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        wm.update_from_mapper(mapper, centre + (0.0,))
+        cls = wm.planes()[0]
+        a360 = beams(360)
+        t0 = time.perf_counter()
+        want_r, want_c = sref.scan(cls, RES, ORIGIN, [pose], a360, range_max)
+        statement_ms = (time.perf_counter() - t0) * 1e3
+        got_r, got_c = wm.scan(pose, a360, range_max, return_cells=True)
+        assert got_r.tobytes() == want_r[0].tobytes() and got_c.tobytes() == want_c[0].tobytes(), "device and statement disagree"
+        assert dvz.deform_worldmap(zone, wm, pose, a360, range_max)[:3] == dvz.deform(zone, a360, want_r[0])
+        assert zc.check_worldmap(wm, pose, True) == zc.check(want_r[0], True)
+        host_cls = np.empty((W, H), np.int8, order="F")
+        line = {"world": [W, H], "local": [GH, GW], "range_max": range_max, "radius_cells": kh.worldmap_scan_check(RES, 1, 360, range_max),
+                "hits_of_360": int((want_c >= 0).sum()), "reps": args.reps, "warmup": args.warmup}
+        for n in (360, 1440, 4096):
+            a = beams(n)
+            line[f"a_scan_{n}_beams_to_host_ms"] = timed(lambda: wm.scan(pose, a, range_max), args.reps, args.warmup)
+        rs = np.random.default_rng(3)
+        poses = [(centre[0] + dx, centre[1] + dy, yaw) for dx, dy, yaw in
+                 zip(rs.uniform(-2, 2, 1024), rs.uniform(-2, 2, 1024), rs.uniform(-np.pi, np.pi, 1024))]
+        qposes = [wm.quantise_pose(*p) for p in poses]
+        line["b_scan_1024_poses_x_360_beams_ms"] = timed(lambda: wm.scan(qposes, a360, range_max), args.reps, args.warmup)
+
+        def scan_then_deform():
+            dvz.deform(zone, a360, wm.scan(pose, a360, range_max))
+
+        def scan_then_check():
+            zc.check(wm.scan(pose, a360, range_max), True)
+
+        line["c_dvz_deform_worldmap_ms"] = timed(lambda: dvz.deform_worldmap(zone, wm, pose, a360, range_max), args.reps, args.warmup)
+        line["c_scan_then_dvz_deform_ms"] = timed(scan_then_deform, args.reps, args.warmup)
+        line["c_zone_check_worldmap_ms"] = timed(lambda: zc.check_worldmap(wm, pose, True), args.reps, args.warmup)
+        line["c_scan_then_zone_check_ms"] = timed(scan_then_check, args.reps, args.warmup)
+        line["d_worldmap_get_cls_alone_ms"] = timed(
+            lambda: kh._check(kh.lib().kc_worldmap_get(wm.h, host_cls.ctypes.data, None, host_cls.size)), args.reps, args.warmup)
+        line["d_python_statement_360_beams_one_thread_ms_once"] = round(statement_ms, 1)
+        print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -186,6 +254,7 @@ def main():
     ap.add_argument("--yaws", default="0,0.3,0.785398,1.570796,-2.5")
     ap.add_argument("--match", action="store_true", help="time the correlative match instead of the update")
     ap.add_argument("--points", action="store_true", help="time the obstacle hand-off to the controller instead")
+    ap.add_argument("--scan", action="store_true", help="time the virtual laser scan instead")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
@@ -193,6 +262,8 @@ def main():
         return match_leg(args)
     if args.points:
         return points_leg(args)
+    if args.scan:
+        return scan_leg(args)
     hip = hip_runtime()
     ang, rng = syn.dense_scan(2048, 1.2)                      # ranges 3.6 .. 8.4 m in a 20 m window
     pose_xy = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021)
