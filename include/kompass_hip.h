@@ -1286,6 +1286,134 @@ int kc_worldmap_match_scores(kc_worldmap *ctx, uint32_t *out, size_t cap);
 int kc_worldmap_match_set_timing(kc_worldmap *ctx, int enable);
 int kc_worldmap_match_times(kc_worldmap *ctx, float ms_out[4]);
 
+/* ------------------------------------------------------------------------ */
+/* Monte-Carlo localisation over the world map (DESIGN.md 4.11 rules 28 to 41) */
+/* ------------------------------------------------------------------------ */
+/* Nothing in the reference to cite: it leaves localisation, like the world map, to its ROS
+ * side.  N particles on the device, advanced by odometry with seeded integer noise, scored
+ * against a laser scan by ray-casting the map in place with the scan's own walk, reduced to
+ * one record the host turns into an estimate.  Integers throughout (int64, arithmetic
+ * shifts, exact sums): no result depends on thread order, tests/worldmap_mcl_ref.py states
+ * every rule in Python ints and the device equals it bit for bit.  No kernel modifies the map.
+ * Rule 28, particle: (TX, TY, h, acc).  TX, TY: int64 with 16 fraction bits of a cell, as
+ * kc_worldmap_pose's, clamped to +-2^36; h: heading in 2^-16 turn, 0 .. 65535, it wraps;
+ * acc: uint32 accumulated penalty.  The particle is the scan frame's pose: a sensor's yaw
+ * offset is folded into the beam angles by the caller, a translated mount is out of scope.
+ * Rule 29, heading table: Cq(h) = lrint(cos(2 pi h / 65536) * 65536), Sq(h) alike, the
+ * host libm's in double; 65536 pairs built once on the host, kept on the device.
+ * Rule 30, random numbers, counter-based, all mod 2^64: mix64(x): z = x +
+ * 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ * 0x94D049BB133111EB; z ^ (z >> 31) (mix64(0) = 0xE220A8397B1DCDAF).  draw(seed, step, p, c)
+ * = mix64(mix64(seed ^ (step << 32)) ^ ((p << 8) | c)), c < 256.  noise(v, s): with the four
+ * 16-bit fields a0 .. a3 of v, g = a0 + a1 + a2 + a3 - 131070, noise = (g s + 2^15) >> 16,
+ * s >= 0 an int32.  g's standard deviation is sqrt((65536^2 - 1) / 3); a front end forms s =
+ * lrint(sigma * 65536 / that) for a sigma in the quantity's units; this ABI takes s as given.
+ * Rule 31, predict: increments d_f, d_l (forward, lateral; 2^-16 cells, |d| <= 2^36) and d_h
+ * (heading units), scales s_f, s_l, s_h.  With (C, S) = (Cq(h), Sq(h)) of the heading BEFORE
+ * the step: F = d_f + noise(draw(.., p, 0), s_f), L = d_l + noise(draw(.., p, 1), s_l), TX +=
+ * (C F - S L + 2^15) >> 16, TY += (S F + C L + 2^15) >> 16, both clamped, h = (h + d_h +
+ * noise(draw(.., p, 2), s_h)) & 0xFFFF.
+ * Rule 32, expected range: beam k of the new particle walks as rules 21 to 23 and 25 say from
+ * the pose (Cq(h), Sq(h), TX, TY), box Rc + 1, KC_SCAN_UNKNOWN_BLOCKS honoured.  ZMAX =
+ * llrint((double)range_max / (double)resolution * 65536).  The first blocking cell gives q =
+ * floor(e 2^30 / a) (e < 2^28); a start cell that blocks q = 0; no hit or q > ZMAX: q = ZMAX.
+ * Rule 33, measured range, quantised by the caller: zq_k = llrint(z_k / resolution * 65536)
+ * for a finite 0 <= z_k < range_max, else ZMAX (a beam without a return), or -1 with
+ * KC_MCL_SKIP_NO_RETURN: such a beam contributes nothing.  A step refuses a zq outside 0 ..
+ * ZMAX, and a -1 without the flag.
+ * Rule 34, penalty: bin = min(|q - zq_k| >> err_shift, E - 1), cost_p = sum_k pen[bin],
+ * uint32; pen: E <= 4096 uint16 entries, err_shift in 0 .. 30.
+ * Rule 35, accumulate: acc_p = min(acc_p - min_prev + cost_p, 2^30), min_prev the smallest
+ * acc after the previous step, 0 after an init or a resample; amin = min_p acc_p, best the
+ * lowest index with acc_p == amin.
+ * Rule 36, weight: w_p = wtab[min((acc_p - amin) >> w_shift, EW - 1)]; wtab: EW <= 4096
+ * uint32 entries that do not increase, 1 <= wtab[0] <= 2^20, w_shift in 0 .. 30.
+ * Rule 37, record: exact sums over all particles, kc_mcl_record.
+ * Rule 38, limits: 1 <= N <= 65536, 1 <= B <= 1024, N B <= 2^22; kc_mcl_check's order.
+ * Rule 39, estimate (the host's, from the record): TXe = TX_best + floor(SX / W1), TYe alike;
+ * yaw = atan2((double)SS, (double)SC); x = origin_x + (double)TXe / 65536 * resolution;
+ * n_eff = (double)W1 * (double)W1 / (double)W2.
+ * Rule 40, resample: the host decides (W1 W1 r_den < r_num N W2 in exact integers, 1 / 2 by
+ * default); systematic: cum_i the inclusive prefix sum of w in index order, u0 = draw(seed,
+ * step, N, 15) mod W1, slot j takes the state of the smallest i with N cum_i > u0 + j W1 and
+ * acc 0; double-buffered, no slot reads what another writes.
+ * Rule 41, init; either sets the step counter to 0, a step increments it before it draws.
+ * Gaussian: TX = TX0 + noise(draw(seed, 0, p, 0), s_xy), TY with channel 1, h = (h0 +
+ * noise(draw(seed, 0, p, 2), s_h)) & 0xFFFF, TX and TY clamped, acc 0.  Global: the free
+ * cells are those whose cls byte is KC_EMPTY, in the order of I + J * width, n_free of them;
+ * particle p takes number draw(seed, 0, p, 0) mod n_free; with v = draw(seed, 0, p, 1): TX = (I
+ * << 16) + (v & 0xFFFF) - 2^15, TY = (J << 16) + ((v >> 16) & 0xFFFF) - 2^15, h = (v >> 32) &
+ * 0xFFFF. */
+typedef struct kc_mcl kc_mcl;
+#define KC_MCL_SKIP_NO_RETURN 2u /* beside KC_SCAN_UNKNOWN_BLOCKS in a step's flags */
+#define KC_MCL_MAX_PARTICLES 65536
+#define KC_MCL_MAX_BEAMS 1024
+#define KC_MCL_MAX_TABLE 4096
+typedef struct kc_mcl_record { /* rule 37 */
+  uint64_t w1, w2;             /* sum w, sum w^2 */
+  uint64_t sx_lo;              /* SX = sum w (TX_p - TX_best) as a 128-bit two's complement (lo, hi) */
+  int64_t sx_hi;
+  uint64_t sy_lo;              /* SY alike */
+  int64_t sy_hi;
+  int64_t sc, ss;              /* sum w Cq(h_p), sum w Sq(h_p) */
+  int64_t best_tx, best_ty;    /* the best particle's state */
+  uint32_t best_h;
+  uint32_t amin, best;         /* rule 35 */
+  uint32_t step;               /* the step counter of the step that formed the record */
+} kc_mcl_record;
+/* Rule 38's refusals (host only), in this order: KC_ERR_INVALID unless the resolution is a
+ * finite float > 0; KC_ERR_INVALID for no particle or no beam; KC_ERR_RANGE above 65536
+ * particles, then above 1024 beams, then above 2^22 rays; KC_ERR_INVALID unless range_max is a
+ * finite float > 0; KC_ERR_RANGE for Rc > 2048; pen (skipped when NULL): KC_ERR_INVALID for no
+ * entry, KC_ERR_RANGE above 4096, KC_ERR_INVALID for err_shift outside 0 .. 30; wtab (skipped
+ * when NULL): the same three, then KC_ERR_INVALID for wtab[0] outside 1 .. 2^20 and for an
+ * entry above the one before it; KC_ERR_INVALID for unknown flag bits.  rc_out, zmax_out (may
+ * be NULL): Rc and ZMAX, 0 on a refusal. */
+int kc_mcl_check(float resolution, size_t n_particles, size_t n_beams, float range_max, const uint16_t *pen_or_null, size_t n_pen,
+                 int err_shift, const uint32_t *wtab_or_null, size_t n_wtab, int w_shift, unsigned int flags, int32_t *rc_out,
+                 int64_t *zmax_out);
+/* rule 29 for one heading (host only); KC_ERR_RANGE above 65535 */
+int kc_mcl_heading(uint32_t h, int32_t *cq_out, int32_t *sq_out);
+/* A localiser of n_particles over `map`, on its device, with its own stream; the map must
+ * outlive it.  angles: the n_beams beam angles in the scan frame (rule 21's table is formed
+ * here).  Checks: null arguments, kc_mcl_check without tables, the angles (finite), then the
+ * device. */
+int kc_mcl_create(kc_worldmap *map, size_t n_particles, const double *angles, size_t n_beams, float range_max, uint64_t seed,
+                  kc_mcl **out);
+void kc_mcl_destroy(kc_mcl *ctx);
+/* what the context was made with, Rc, ZMAX and the step counter; any pointer may be NULL */
+int kc_mcl_info(kc_mcl *ctx, size_t *n_particles_out, size_t *n_beams_out, int32_t *rc_out, int64_t *zmax_out, uint32_t *step_out);
+/* rules 34 and 36's tables and shifts, checked as kc_mcl_check does; the particles stay, the
+ * weights of the last step do not (a resample needs a new step) */
+int kc_mcl_set_model(kc_mcl *ctx, const uint16_t *pen, size_t n_pen, int err_shift, const uint32_t *wtab, size_t n_wtab, int w_shift);
+/* rule 41.  init_pose: KC_ERR_RANGE for |TX0|, |TY0| > 2^36 or h0 > 65535, KC_ERR_INVALID for
+ * a negative scale.  init_global: two launches around a read-back of the row counts, ordered
+ * behind the map's stream; *n_free_out (may be NULL) the free cells; KC_ERR_STATE with none. */
+int kc_mcl_init_pose(kc_mcl *ctx, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s_xy, int32_t s_h);
+int kc_mcl_init_global(kc_mcl *ctx, size_t *n_free_out);
+/* One step (rules 31 to 37): two launches (predict + walk + penalty; weight + record) behind
+ * an event on the map's stream, and the read-back of *out; returns with it final.  zq: n_beams
+ * quantised ranges (rule 33).  Checks, in this order: null arguments; KC_ERR_STATE without a
+ * model, then without an init; KC_ERR_RANGE for |d_f|, |d_l| > 2^36; KC_ERR_INVALID for a
+ * negative scale, unknown flag bits, a zq outside rule 33; then the device.  A refused call
+ * queues nothing. */
+int kc_mcl_step(kc_mcl *ctx, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, int32_t s_l, int32_t s_h, const int32_t *zq,
+                unsigned int flags, kc_mcl_record *out);
+/* rule 40's copy by the last step's weights: two launches (prefix sum, select), no read-back.
+ * KC_ERR_STATE unless a step has run since the last init, resample or set_model. */
+int kc_mcl_resample(kc_mcl *ctx);
+/* the states and acc into host memory, for tests and tools; any output may be NULL; cap: the
+ * particles each holds (KC_ERR_RANGE below N); KC_ERR_STATE before an init */
+int kc_mcl_particles(kc_mcl *ctx, int64_t *tx_out, int64_t *ty_out, uint32_t *h_out, uint32_t *acc_out, size_t cap);
+/* where they lie on the device (int64, int64, uint32, uint32; N each): valid until the next
+ * step, resample or init, which change buffers */
+int kc_mcl_particles_device(kc_mcl *ctx, void **tx_out, void **ty_out, void **h_out, void **acc_out);
+/* HIP-event times in milliseconds of the last step's two launches (walk, weigh) and the last
+ * resample's (prefix, select; 0 when none ran), for tools; recorded only while enabled.
+ * KC_ERR_STATE when no step was timed. */
+int kc_mcl_set_timing(kc_mcl *ctx, int enable);
+int kc_mcl_times(kc_mcl *ctx, float ms_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "controllers/rgbd_follower.h"
 #include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
+#include "mapping/mcl.h"
 #include "mapping/world_map.h"
 #include "planning/grid_planner.h"
 #include "utils/logger.h"
@@ -1129,6 +1130,120 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def_property_readonly("height", &Mapping::WorldMap::height)
       .def_property_readonly("resolution", &Mapping::WorldMap::resolution)
       .def_property_readonly("origin", [](const Mapping::WorldMap &m) { return py::make_tuple(m.originX(), m.originY()); });
+
+  // (not in the reference: Monte-Carlo localisation over a WorldMap, the particles on the device; DESIGN.md 4.11 rules
+  // 28 to 41)
+  {
+    using MCL = Mapping::MCL;
+    // SX, SY as Python ints: (hi << 64) + lo
+    auto wideInt = [](uint64_t lo, int64_t hi) { return (py::int_(hi) << py::int_(64)) + py::int_(lo); };
+    py::class_<MCL::Estimate>(mp, "MCLEstimate")
+        .def_readonly("x", &MCL::Estimate::x)
+        .def_readonly("y", &MCL::Estimate::y)
+        .def_readonly("yaw", &MCL::Estimate::yaw)
+        .def_readonly("n_eff", &MCL::Estimate::n_eff)
+        .def_readonly("spread", &MCL::Estimate::spread)
+        .def_readonly("resampled", &MCL::Estimate::resampled)
+        .def_readonly("best_cost", &MCL::Estimate::best_cost)
+        .def_readonly("txe", &MCL::Estimate::txe)
+        .def_readonly("tye", &MCL::Estimate::tye)
+        .def_property_readonly("record", [wideInt](const MCL::Estimate &e) {
+               const kc_mcl_record &r = e.record;
+               return py::make_tuple(r.w1, r.w2, wideInt(r.sx_lo, r.sx_hi), wideInt(r.sy_lo, r.sy_hi), r.sc, r.ss, r.amin, r.best,
+                                     r.best_tx, r.best_ty, r.best_h, r.step);
+             }, "(w1, w2, sx, sy, sc, ss, amin, best, best_tx, best_ty, best_h, step): rule 37's exact sums");
+    py::class_<MCL>(mp, "MCL")
+        .def(py::init([](const Mapping::WorldMap &map, size_t n_particles, const std::vector<double> &angles, float range_max,
+                         uint64_t seed) { return std::make_unique<MCL>(map, n_particles, angles, range_max, seed); }),
+             py::arg("world_map"), py::arg("n_particles"), py::arg("angles"), py::arg("range_max"), py::arg("seed") = 0,
+             py::keep_alive<1, 2>())
+        .def("set_model", [](MCL &m, double sigma_hit, int err_shift, int n_pen, double floor, double pen_scale, int w_shift, int n_w,
+                             uint32_t wtab0, double temperature) {
+               MCL::Model d;
+               d.sigma_hit = sigma_hit;
+               d.err_shift = err_shift;
+               d.n_pen = n_pen;
+               d.floor = floor;
+               d.pen_scale = pen_scale;
+               d.w_shift = w_shift;
+               d.n_w = n_w;
+               d.wtab0 = wtab0;
+               d.temperature = temperature;
+               m.setModel(d);
+             }, py::arg("sigma_hit") = 0.1, py::arg("err_shift") = 12, py::arg("n_pen") = 256, py::arg("floor") = 0.05,
+             py::arg("pen_scale") = 64.0, py::arg("w_shift") = 4, py::arg("n_w") = 1024, py::arg("wtab0") = 1u << 16,
+             py::arg("temperature") = 256.0, "The sensor model the penalty and weight tables are built from (judgement)")
+        .def("set_tables", [](MCL &m, const std::vector<uint16_t> &pen, int err_shift, const std::vector<uint32_t> &wtab, int w_shift) {
+               MCL::Tables t;
+               t.pen = pen;
+               t.err_shift = err_shift;
+               t.wtab = wtab;
+               t.w_shift = w_shift;
+               m.setTables(t);
+             }, py::arg("pen"), py::arg("err_shift"), py::arg("wtab"), py::arg("w_shift"))
+        .def("set_motion_noise", &MCL::setMotionNoise, py::arg("sigma_forward"), py::arg("sigma_lateral"), py::arg("sigma_yaw"))
+        .def("set_resample_ratio", &MCL::setResampleRatio, py::arg("num"), py::arg("den"))
+        .def("set_flags", &MCL::setFlags, py::arg("unknown_blocks") = false, py::arg("skip_no_return") = false)
+        .def("set_spread", &MCL::setSpread, py::arg("on"))
+        .def("init", &MCL::init, py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("sigma_xy"), py::arg("sigma_yaw"))
+        .def("init_global", &MCL::initGlobal, "Seed the particles uniformly over the map's empty cells -> their count")
+        .def("step", [](MCL &m, const std::array<double, 3> &from, const std::array<double, 3> &to, const std::vector<double> &ranges) {
+               py::gil_scoped_release nogil;
+               return m.step(from, to, ranges);
+             }, py::arg("odom_from"), py::arg("odom_to"), py::arg("ranges"))
+        .def("step_quantised", [](MCL &m, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, int32_t s_l, int32_t s_h,
+                                  const std::vector<int32_t> &zq, unsigned flags, bool resample) {
+               py::gil_scoped_release nogil;
+               return m.stepQuantised(d_f, d_l, d_h, s_f, s_l, s_h, zq, flags, resample);
+             }, py::arg("d_f"), py::arg("d_l"), py::arg("d_h"), py::arg("s_f"), py::arg("s_l"), py::arg("s_h"), py::arg("zq"),
+             py::arg("flags") = 0u, py::arg("resample") = true)
+        .def("resample", &MCL::resample)
+        .def("particles", [](const MCL &m) {
+               const MCL::Particles p = m.particles();
+               const py::ssize_t n = static_cast<py::ssize_t>(p.tx.size());
+               return py::make_tuple(py::array_t<int64_t>(n, p.tx.data()), py::array_t<int64_t>(n, p.ty.data()),
+                                     py::array_t<uint32_t>(n, p.h.data()), py::array_t<uint32_t>(n, p.acc.data()));
+             }, "(tx int64, ty int64, h uint32, acc uint32), N each: the states in 2^-16 cells and 2^-16 turns")
+        .def_property_readonly("size", &MCL::size)
+        .def_property_readonly("beams", &MCL::beams)
+        .def_property_readonly("zmax", &MCL::zmax)
+        .def_static("noise_scale", &MCL::noiseScale, py::arg("sigma_units"))
+        .def_static("quantise_heading", &MCL::quantiseHeading, py::arg("yaw"))
+        .def_static("quantise_ranges", &MCL::quantiseRanges, py::arg("ranges"), py::arg("resolution"), py::arg("range_max"),
+                    py::arg("flags") = 0u)
+        .def_static("odometry_increment", [](float resolution, const std::array<double, 3> &from, const std::array<double, 3> &to) {
+               const auto d = MCL::odometryIncrement(resolution, from, to);
+               return py::make_tuple(d[0], d[1], d[2]);
+             }, py::arg("resolution"), py::arg("odom_from"), py::arg("odom_to"))
+        .def_static("estimate_of", [](uint64_t w1, uint64_t w2, uint64_t sx_lo, int64_t sx_hi, uint64_t sy_lo, int64_t sy_hi, int64_t sc,
+                                      int64_t ss, int64_t best_tx, int64_t best_ty, float resolution, double origin_x, double origin_y) {
+               kc_mcl_record r{};
+               r.w1 = w1;
+               r.w2 = w2;
+               r.sx_lo = sx_lo;
+               r.sx_hi = sx_hi;
+               r.sy_lo = sy_lo;
+               r.sy_hi = sy_hi;
+               r.sc = sc;
+               r.ss = ss;
+               r.best_tx = best_tx;
+               r.best_ty = best_ty;
+               return MCL::estimateOf(r, resolution, origin_x, origin_y);
+             }, "Rule 39 from a record's sums, SX and SY as (lo uint64, hi int64); needs no device")
+        .def_static("should_resample", [](uint64_t w1, uint64_t w2, size_t n, uint32_t num, uint32_t den) {
+               kc_mcl_record r{};
+               r.w1 = w1;
+               r.w2 = w2;
+               return MCL::shouldResample(r, n, num, den);
+             }, py::arg("w1"), py::arg("w2"), py::arg("n"), py::arg("num") = 1u, py::arg("den") = 2u,
+             "Rule 40's decision in exact integers; needs no device")
+        .def_static("sensor_tables", [](float resolution, double sigma_hit) {
+               MCL::Model d;
+               d.sigma_hit = sigma_hit;
+               const MCL::Tables t = MCL::sensorTables(resolution, d);
+               return py::make_tuple(t.pen, t.err_shift, t.wtab, t.w_shift);
+             }, py::arg("resolution"), py::arg("sigma_hit") = 0.1, "(pen, err_shift, wtab, w_shift) of the default model");
+  }
 
   // ----------------------------------------------------------------- utils
   // (bindings_utils.cpp:47-129, bindings_gpu.cpp:40-68)

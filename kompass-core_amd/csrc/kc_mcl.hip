@@ -1,0 +1,773 @@
+// Monte-Carlo localisation over the world map (kc_mcl_*; DESIGN.md 4.11 rules 28 to 41).
+//
+// Nothing in the reference to restate: it leaves localisation, like the world map, to its ROS side.  N particles
+// (TX, TY, h, acc) live on the device; a step advances them by an odometry increment with counter-based integer noise,
+// ray-casts the map in place for every particle x beam with the scan's own walk (kc_worldmap_walk.h), sums a table
+// penalty per particle, and reduces the weights to one record the host turns into an estimate.  Integers only, exact
+// sums: no result depends on thread order, and tests/worldmap_mcl_ref.py states every rule in Python ints.
+//
+// Launches: a step is mcl_walk_kernel + mcl_weigh_kernel and the read-back of the record; a resample is
+// mcl_prefix_kernel + mcl_select_kernel without a read-back.
+//  (a) mcl_walk_kernel: ray r = particle r / B, beam r % B, so consecutive beams of consecutive particles sit on
+//      consecutive lanes and every lane but the last workgroup's tail has a ray, whatever B is.  Each ray recomputes its
+//      particle's predict step (six mix64, a few products: nothing next to a walk) from the OLD state buffer; beam 0
+//      stores it into the NEW one, so no ray reads what another writes.  pen lies in LDS.  A wavefront reduces the
+//      penalties of equal particles by a segmented shuffle-down (the segments are contiguous), each segment's first lane
+//      adds its sum to cost[p] with one uint32 atomic: integer adds only, exact in any order.
+//  (b) mcl_weigh_kernel: one workgroup of 1024.  Pass 1 forms acc and the packed minimum (acc << 32 | p: the lowest
+//      index among equals), pass 2 the weights and the record's sums.  w (x - x_best) can reach 2^57 and 65536 of them
+//      2^73: each product is split into its low 32 bits and the rest, both summed in 64 bits and joined once at the end.
+//      It leaves cost at 0 for the next step and amin in the state word rule 35 calls min_prev.
+//  (c) mcl_prefix_kernel: one workgroup; a lane sums a contiguous chunk, the 1024 partials are scanned in LDS.
+//  (d) mcl_select_kernel: a lane a slot, a binary search over the prefix; reads the current state buffer and writes the
+//      other one.
+//  (e) global init: row counts of KC_EMPTY (a workgroup a row), the prefix over rows on the host, then a wavefront a
+//      particle: a binary search for the row and a ballot walk along it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "kc_internal.h"
+#include "kc_worldmap_walk.h"
+#include "kompass_hip.h"
+
+namespace kc {
+
+constexpr int kMclBlock = 256;
+constexpr int kMclOne = 1024;  // the single-workgroup kernels
+constexpr long long kMclMaxOffset = 1ll << 36;
+constexpr unsigned kMclAccCap = 1u << 30;
+
+__host__ __device__ inline unsigned long long mcl_mix64(unsigned long long x) {
+  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// key = mix64(seed ^ (step << 32)), formed once on the host
+__host__ __device__ inline unsigned long long mcl_draw(unsigned long long key, unsigned long long p, unsigned c) {
+  return mcl_mix64(key ^ ((p << 8) | c));
+}
+__host__ __device__ inline long long mcl_noise(unsigned long long v, int s) {
+  const long long g =
+      static_cast<long long>((v & 0xFFFF) + ((v >> 16) & 0xFFFF) + ((v >> 32) & 0xFFFF) + (v >> 48)) - 131070ll;
+  return (g * s + (1ll << 15)) >> 16;
+}
+__host__ __device__ inline long long mcl_clamp(long long v) {
+  return v < -kMclMaxOffset ? -kMclMaxOffset : (v > kMclMaxOffset ? kMclMaxOffset : v);
+}
+
+struct MclState {  // one of the two state buffers
+  long long *tx, *ty;
+  unsigned *h;
+};
+
+struct MclWalkArgs {
+  const int8_t *cls;
+  const int2 *table;    // rule 21: (ac, as) a beam
+  const int2 *heading;  // rule 29: (Cq, Sq) a heading
+  MclState in, out;
+  const int *zq;        // rule 33
+  const unsigned short *pen;
+  unsigned *cost;
+  unsigned long long key;
+  long long d_f, d_l, zmax;
+  int d_h, s_f, s_l, s_h;
+  int W, H, N, B, rc, unknown_blocks, E, err_shift;
+};
+
+__global__ __launch_bounds__(kMclBlock) void mcl_walk_kernel(MclWalkArgs a) {
+  __shared__ unsigned short s_pen[KC_MCL_MAX_TABLE];
+  for (int i = threadIdx.x; i < a.E; i += kMclBlock) s_pen[i] = a.pen[i];
+  __syncthreads();
+  const unsigned ray = blockIdx.x * kMclBlock + threadIdx.x;  // N B <= 2^22
+  const bool live = ray < static_cast<unsigned>(a.N) * static_cast<unsigned>(a.B);
+  int p = -1;
+  unsigned c = 0;
+  if (live) {
+    p = static_cast<int>(ray / static_cast<unsigned>(a.B));
+    const int k = static_cast<int>(ray - static_cast<unsigned>(p) * static_cast<unsigned>(a.B));
+    // rule 31, from the heading before the step
+    const unsigned h0 = a.in.h[p];
+    const int2 cs0 = a.heading[h0];
+    const long long C = cs0.x, S = cs0.y;
+    const long long F = a.d_f + mcl_noise(mcl_draw(a.key, p, 0), a.s_f);
+    const long long L = a.d_l + mcl_noise(mcl_draw(a.key, p, 1), a.s_l);
+    kc_worldmap_pose pose;
+    pose.tx = mcl_clamp(a.in.tx[p] + ((C * F - S * L + (1ll << 15)) >> 16));
+    pose.ty = mcl_clamp(a.in.ty[p] + ((S * F + C * L + (1ll << 15)) >> 16));
+    const unsigned h1 =
+        static_cast<unsigned>((static_cast<long long>(h0) + a.d_h + mcl_noise(mcl_draw(a.key, p, 2), a.s_h)) & 0xFFFF);
+    const int2 cs1 = a.heading[h1];
+    pose.cq = cs1.x;
+    pose.sq = cs1.y;
+    if (k == 0) {
+      a.out.tx[p] = pose.tx;
+      a.out.ty[p] = pose.ty;
+      a.out.h[p] = h1;
+    }
+    const long long zq = a.zq[k];
+    if (zq >= 0) {  // rule 33: -1 contributes nothing
+      // rule 32: q > ZMAX iff e 2^30 >= (ZMAX + 1) a; both sides below 2^59
+      const long long over = a.zmax + 1;
+      WmWalkHit hit{0, 1, 0, 0};
+      long long q = a.zmax;
+      if (wm_walk(a.cls, a.W, a.H, a.rc, a.unknown_blocks, pose, a.table[k],
+                  [&](int e, int ax) { return (static_cast<long long>(e) << 30) >= over * ax; }, &hit)) {
+        const unsigned long long num = static_cast<unsigned long long>(hit.e) << 30;
+        const unsigned long long qq = num / static_cast<unsigned long long>(hit.a);
+        if (qq <= static_cast<unsigned long long>(a.zmax)) q = static_cast<long long>(qq);
+      }
+      const long long d = q > zq ? q - zq : zq - q;
+      const long long bin = d >> a.err_shift;
+      c = s_pen[bin < a.E - 1 ? bin : a.E - 1];
+    }
+  }
+  // equal particles are contiguous lanes: after the steps the first lane of a segment holds the segment's sum
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned c2 = __shfl_down(c, off);
+    const int p2 = __shfl_down(p, off);
+    if (lane + off < 64 && p2 == p) c += c2;
+  }
+  const int before = __shfl_up(p, 1);
+  if (live && (lane == 0 || before != p)) atomicAdd(&a.cost[p], c);
+}
+
+// ---- sums over one workgroup of kMclOne: wavefront shuffles, then the 16 partials through LDS ----
+__device__ __forceinline__ long long mcl_block_sum(long long v, long long *s16) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  __syncthreads();  // s16 may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = v;
+  __syncthreads();
+  long long t = 0;
+#pragma unroll
+  for (int i = 0; i < kMclOne / 64; ++i) t += s16[i];
+  return t;
+}
+__device__ __forceinline__ unsigned long long mcl_block_min(unsigned long long v, unsigned long long *s16) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_down(v, off);
+    v = o < v ? o : v;
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = v;
+  __syncthreads();
+  unsigned long long t = s16[0];
+#pragma unroll
+  for (int i = 1; i < kMclOne / 64; ++i) t = s16[i] < t ? s16[i] : t;
+  return t;
+}
+
+struct MclWeighArgs {
+  MclState st;
+  unsigned *acc, *cost, *w, *min_prev;
+  const unsigned *wtab;
+  const int2 *heading;
+  kc_mcl_record *rec;
+  int N, EW, w_shift;
+  unsigned step;
+};
+
+// a 128-bit sum kept as sum of (t >> 32) and sum of (t & 0xFFFFFFFF): -> (lo, hi)
+__device__ __forceinline__ void mcl_join(long long high, long long low, unsigned long long *lo, long long *hi) {
+  const unsigned long long base = static_cast<unsigned long long>(high) << 32;
+  *lo = base + static_cast<unsigned long long>(low);
+  *hi = (high >> 32) + (*lo < base ? 1 : 0);
+}
+
+__global__ __launch_bounds__(kMclOne) void mcl_weigh_kernel(MclWeighArgs a) {
+  __shared__ long long s16[kMclOne / 64];
+  const unsigned min_prev = *a.min_prev;
+  unsigned long long key = ~0ull;
+  for (int p = threadIdx.x; p < a.N; p += kMclOne) {  // rule 35
+    const unsigned long long sum = static_cast<unsigned long long>(a.acc[p] - min_prev) + a.cost[p];
+    const unsigned v = sum < kMclAccCap ? static_cast<unsigned>(sum) : kMclAccCap;
+    a.acc[p] = v;
+    a.cost[p] = 0u;
+    const unsigned long long mine = (static_cast<unsigned long long>(v) << 32) | static_cast<unsigned>(p);
+    key = mine < key ? mine : key;
+  }
+  key = mcl_block_min(key, reinterpret_cast<unsigned long long *>(s16));
+  const unsigned amin = static_cast<unsigned>(key >> 32), best = static_cast<unsigned>(key & 0xFFFFFFFFull);
+  const long long bx = a.st.tx[best], by = a.st.ty[best];
+  long long w1 = 0, w2 = 0, sc = 0, ss = 0, sxh = 0, sxl = 0, syh = 0, syl = 0;
+  for (int p = threadIdx.x; p < a.N; p += kMclOne) {  // rules 36 and 37
+    const unsigned bin = (a.acc[p] - amin) >> a.w_shift;
+    const long long w = a.wtab[bin < static_cast<unsigned>(a.EW - 1) ? bin : static_cast<unsigned>(a.EW - 1)];
+    a.w[p] = static_cast<unsigned>(w);
+    const int2 cs = a.heading[a.st.h[p]];
+    const long long tx = w * (a.st.tx[p] - bx), ty = w * (a.st.ty[p] - by);
+    w1 += w;
+    w2 += w * w;
+    sc += w * cs.x;
+    ss += w * cs.y;
+    sxh += tx >> 32;
+    sxl += tx & 0xFFFFFFFFll;
+    syh += ty >> 32;
+    syl += ty & 0xFFFFFFFFll;
+  }
+  w1 = mcl_block_sum(w1, s16);
+  w2 = mcl_block_sum(w2, s16);
+  sc = mcl_block_sum(sc, s16);
+  ss = mcl_block_sum(ss, s16);
+  sxh = mcl_block_sum(sxh, s16);
+  sxl = mcl_block_sum(sxl, s16);
+  syh = mcl_block_sum(syh, s16);
+  syl = mcl_block_sum(syl, s16);
+  if (threadIdx.x == 0) {
+    kc_mcl_record r;
+    r.w1 = static_cast<uint64_t>(w1);
+    r.w2 = static_cast<uint64_t>(w2);
+    unsigned long long lo;
+    long long hi;
+    mcl_join(sxh, sxl, &lo, &hi);
+    r.sx_lo = lo;
+    r.sx_hi = hi;
+    mcl_join(syh, syl, &lo, &hi);
+    r.sy_lo = lo;
+    r.sy_hi = hi;
+    r.sc = sc;
+    r.ss = ss;
+    r.best_tx = bx;
+    r.best_ty = by;
+    r.best_h = a.st.h[best];
+    r.amin = amin;
+    r.best = best;
+    r.step = a.step;
+    *a.rec = r;
+    *a.min_prev = amin;
+  }
+}
+
+// rule 40: cum_i, the inclusive prefix sum of w in index order
+__global__ __launch_bounds__(kMclOne) void mcl_prefix_kernel(const unsigned *w, unsigned long long *cum, int N) {
+  __shared__ unsigned long long s[kMclOne];
+  const int chunk = (N + kMclOne - 1) / kMclOne;
+  const int lo = static_cast<int>(threadIdx.x) * chunk, hi = lo + chunk < N ? lo + chunk : N;
+  unsigned long long mine = 0;
+  for (int i = lo; i < hi; ++i) mine += w[i];
+  s[threadIdx.x] = mine;
+  __syncthreads();
+  for (int off = 1; off < kMclOne; off <<= 1) {
+    const unsigned long long add = static_cast<int>(threadIdx.x) >= off ? s[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s[threadIdx.x] += add;
+    __syncthreads();
+  }
+  unsigned long long run = s[threadIdx.x] - mine;  // the chunks before this one
+  for (int i = lo; i < hi; ++i) {
+    run += w[i];
+    cum[i] = run;
+  }
+}
+
+// rule 40: slot j takes the smallest i with N cum_i > u0 + j W1 (below 2^53 on both sides)
+__global__ __launch_bounds__(kMclBlock) void mcl_select_kernel(MclState in, MclState out, unsigned *acc, unsigned *min_prev,
+                                                               const unsigned long long *cum, unsigned long long u0,
+                                                               unsigned long long w1, int N) {
+  const int j = blockIdx.x * kMclBlock + threadIdx.x;
+  if (j >= N) return;
+  const unsigned long long t = u0 + static_cast<unsigned long long>(j) * w1, n = static_cast<unsigned long long>(N);
+  int lo = 0, hi = N - 1;  // N cum_{N-1} = N W1 > t: the answer exists
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (n * cum[mid] > t) hi = mid;
+    else lo = mid + 1;
+  }
+  out.tx[j] = in.tx[lo];
+  out.ty[j] = in.ty[lo];
+  out.h[j] = in.h[lo];
+  acc[j] = 0u;
+  if (j == 0) *min_prev = 0u;
+}
+
+// rule 41, Gaussian
+__global__ __launch_bounds__(kMclBlock) void mcl_init_pose_kernel(MclState out, unsigned *acc, unsigned *cost, unsigned *min_prev,
+                                                                  unsigned long long key, long long tx0, long long ty0,
+                                                                  unsigned h0, int s_xy, int s_h, int N) {
+  const int p = blockIdx.x * kMclBlock + threadIdx.x;
+  if (p >= N) return;
+  out.tx[p] = mcl_clamp(tx0 + mcl_noise(mcl_draw(key, p, 0), s_xy));
+  out.ty[p] = mcl_clamp(ty0 + mcl_noise(mcl_draw(key, p, 1), s_xy));
+  out.h[p] = static_cast<unsigned>((static_cast<long long>(h0) + mcl_noise(mcl_draw(key, p, 2), s_h)) & 0xFFFF);
+  acc[p] = 0u;
+  cost[p] = 0u;
+  if (p == 0) *min_prev = 0u;
+}
+
+// rule 41, global: KC_EMPTY cells a row; blockIdx.x: the row
+__global__ __launch_bounds__(kMclBlock) void mcl_row_count_kernel(const int8_t *cls, int W, unsigned *rows) {
+  __shared__ unsigned s[kMclBlock];
+  const int8_t *row = cls + static_cast<size_t>(blockIdx.x) * static_cast<size_t>(W);
+  unsigned n = 0;
+  for (int i = threadIdx.x; i < W; i += kMclBlock) n += row[i] == KC_EMPTY ? 1u : 0u;
+  s[threadIdx.x] = n;
+  __syncthreads();
+  for (int off = kMclBlock / 2; off > 0; off >>= 1) {
+    if (static_cast<int>(threadIdx.x) < off) s[threadIdx.x] += s[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) rows[blockIdx.x] = s[0];
+}
+
+// a wavefront a particle.  before[J]: the free cells of the rows below J, before[H] = n_free
+__global__ __launch_bounds__(kMclBlock) void mcl_init_global_kernel(const int8_t *cls, int W, int H, const unsigned long long *before,
+                                                                    MclState out, unsigned *acc, unsigned *cost, unsigned *min_prev,
+                                                                    unsigned long long key, int N) {
+  const int p = static_cast<int>((blockIdx.x * kMclBlock + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (p >= N) return;  // the whole wavefront
+  unsigned long long rest = mcl_draw(key, p, 0) % before[H];
+  int lo = 0, hi = H - 1;  // the last row with before[J] <= rest
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (before[mid] <= rest) lo = mid;
+    else hi = mid - 1;
+  }
+  const int J = lo;
+  rest -= before[J];
+  const int8_t *row = cls + static_cast<size_t>(J) * static_cast<size_t>(W);
+  for (int i0 = 0; i0 < W; i0 += 64) {
+    const int i = i0 + lane;
+    const bool free_cell = i < W && row[i] == KC_EMPTY;
+    const unsigned long long m = __ballot(free_cell);
+    const unsigned long long n = static_cast<unsigned long long>(__popcll(m));
+    if (rest < n) {
+      if (free_cell && static_cast<unsigned long long>(__popcll(m & ((1ull << lane) - 1ull))) == rest) {
+        const unsigned long long v = mcl_draw(key, p, 1);
+        out.tx[p] = (static_cast<long long>(i) << 16) + static_cast<long long>(v & 0xFFFF) - (1ll << 15);
+        out.ty[p] = (static_cast<long long>(J) << 16) + static_cast<long long>((v >> 16) & 0xFFFF) - (1ll << 15);
+        out.h[p] = static_cast<unsigned>((v >> 32) & 0xFFFF);
+        acc[p] = 0u;
+        cost[p] = 0u;
+        if (p == 0) *min_prev = 0u;
+      }
+      return;
+    }
+    rest -= n;
+  }
+}
+
+}  // namespace kc
+
+using namespace kc;
+
+struct kc_mcl {
+  kc_worldmap *map = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  OrderEvent map_ready;  // the map's writes, for the walk and the row counts
+  size_t N = 0, B = 0;
+  float range_max = 0.0f;
+  int rc = 0;
+  long long zmax = 0;
+  unsigned long long seed = 0;
+  unsigned step = 0;
+  ScanTable table;
+  DevBuf<int2> d_heading;
+  DevBuf<long long> d_tx[2], d_ty[2];
+  DevBuf<unsigned> d_h[2];
+  int cur = 0;  // the state buffer that holds the particles
+  DevBuf<unsigned> d_acc, d_cost, d_w, d_min_prev;
+  DevBuf<unsigned long long> d_cum;
+  DevBuf<unsigned short> d_pen;
+  DevBuf<unsigned> d_wtab;
+  int E = 0, err_shift = 0, EW = 0, w_shift = 0;
+  DevBuf<int> d_zq;
+  PinBuf<int> h_zq;
+  DevBuf<kc_mcl_record> d_rec;
+  PinBuf<kc_mcl_record> h_rec;
+  DevBuf<unsigned> d_rows;  // global init: scratch grown on demand and kept
+  DevBuf<unsigned long long> d_before;
+  bool have_model = false, inited = false, have_weights = false;
+  unsigned long long w1 = 0;  // of the last step
+  Timing step_time, resample_time;
+
+  MclState state(int which) { return MclState{d_tx[which].p, d_ty[which].p, d_h[which].p}; }
+};
+
+namespace {
+
+// libm's separate cos and sin through pointers, as kc_worldmap.hip's scan table: never one sincos call
+double (*volatile mcl_cos)(double) = static_cast<double (*)(double)>(std::cos);
+double (*volatile mcl_sin)(double) = static_cast<double (*)(double)>(std::sin);
+
+// rule 29: the 65536 pairs, formed once a process
+const int2 *mcl_heading_table() {
+  static std::vector<int2> table;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    table.resize(65536);
+    for (int h = 0; h < 65536; ++h) {
+      const double a = 2.0 * M_PI * static_cast<double>(h) / 65536.0;
+      table[h] = make_int2(static_cast<int>(std::lrint(mcl_cos(a) * 65536.0)), static_cast<int>(std::lrint(mcl_sin(a) * 65536.0)));
+    }
+  });
+  return table.data();
+}
+
+// rule 38, in its order
+int mcl_check(float res, size_t N, size_t B, float range_max, const uint16_t *pen, size_t E, int err_shift, const uint32_t *wtab,
+              size_t EW, int w_shift, unsigned flags, int *rc_out, long long *zmax_out) {
+  if (!(res > 0.0f) || !std::isfinite(res)) KC_FAIL(KC_ERR_INVALID, "the resolution must be positive");
+  if (N == 0 || B == 0) KC_FAIL(KC_ERR_INVALID, "a localiser needs at least one particle and one beam, got %zu x %zu", N, B);
+  if (N > KC_MCL_MAX_PARTICLES) KC_FAIL(KC_ERR_RANGE, "%zu particles are above the cap of %d", N, KC_MCL_MAX_PARTICLES);
+  if (B > KC_MCL_MAX_BEAMS) KC_FAIL(KC_ERR_RANGE, "%zu beams are above the cap of %d", B, KC_MCL_MAX_BEAMS);
+  if (N * B > (size_t{1} << 22)) KC_FAIL(KC_ERR_RANGE, "%zu particles x %zu beams are above the cap of 2^22 rays", N, B);
+  int rc = 0;
+  KC_TRY(worldmap_scan_check(res, N, B, range_max, 0u, &rc));  // range_max, then Rc
+  if (pen) {
+    if (E == 0) KC_FAIL(KC_ERR_INVALID, "an empty penalty table");
+    if (E > KC_MCL_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu penalty entries are above the cap of %d", E, KC_MCL_MAX_TABLE);
+    if (err_shift < 0 || err_shift > 30) KC_FAIL(KC_ERR_INVALID, "err_shift must be in 0 .. 30, got %d", err_shift);
+  }
+  if (wtab) {
+    if (EW == 0) KC_FAIL(KC_ERR_INVALID, "an empty weight table");
+    if (EW > KC_MCL_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu weight entries are above the cap of %d", EW, KC_MCL_MAX_TABLE);
+    if (w_shift < 0 || w_shift > 30) KC_FAIL(KC_ERR_INVALID, "w_shift must be in 0 .. 30, got %d", w_shift);
+    if (wtab[0] < 1u || wtab[0] > (1u << 20)) KC_FAIL(KC_ERR_INVALID, "wtab[0] must be in 1 .. 2^20, got %u", wtab[0]);
+    for (size_t i = 1; i < EW; ++i)
+      if (wtab[i] > wtab[i - 1]) KC_FAIL(KC_ERR_INVALID, "the weight table increases at entry %zu", i);
+  }
+  if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS | KC_MCL_SKIP_NO_RETURN))
+    KC_FAIL(KC_ERR_INVALID, "unknown localiser flag bits 0x%x", flags);
+  if (rc_out) *rc_out = rc;
+  if (zmax_out) *zmax_out = std::llrint(static_cast<double>(range_max) / static_cast<double>(res) * 65536.0);
+  return KC_OK;
+}
+
+unsigned mcl_blocks(size_t work) { return static_cast<unsigned>((work + kMclBlock - 1) / kMclBlock); }
+
+unsigned long long mcl_key(const kc_mcl *c, unsigned step) {
+  return mcl_mix64(c->seed ^ (static_cast<unsigned long long>(step) << 32));
+}
+
+// what either init leaves behind
+void mcl_started(kc_mcl *c, int into) {
+  c->cur = into;
+  c->step = 0;
+  c->inited = true;
+  c->have_weights = false;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kc_mcl_check(float resolution, size_t n_particles, size_t n_beams, float range_max, const uint16_t *pen_or_null, size_t n_pen,
+                 int err_shift, const uint32_t *wtab_or_null, size_t n_wtab, int w_shift, unsigned int flags, int32_t *rc_out,
+                 int64_t *zmax_out) {
+  if (rc_out) *rc_out = 0;
+  if (zmax_out) *zmax_out = 0;
+  int rc = 0;
+  long long zmax = 0;
+  KC_TRY(mcl_check(resolution, n_particles, n_beams, range_max, pen_or_null, n_pen, err_shift, wtab_or_null, n_wtab, w_shift, flags,
+                   &rc, &zmax));
+  if (rc_out) *rc_out = rc;
+  if (zmax_out) *zmax_out = zmax;
+  return KC_OK;
+}
+
+int kc_mcl_heading(uint32_t h, int32_t *cq_out, int32_t *sq_out) {
+  if (!cq_out || !sq_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (h > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h);
+  const int2 v = mcl_heading_table()[h];
+  *cq_out = v.x;
+  *sq_out = v.y;
+  return KC_OK;
+}
+
+int kc_mcl_create(kc_worldmap *map, size_t n_particles, const double *angles, size_t n_beams, float range_max, uint64_t seed,
+                  kc_mcl **out) {
+  if (!out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!map || !angles) KC_FAIL(KC_ERR_INVALID, "null argument");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(map, &v));
+  int rc = 0;
+  long long zmax = 0;
+  KC_TRY(mcl_check(v.res, n_particles, n_beams, range_max, nullptr, 0, 0, nullptr, 0, 0, 0u, &rc, &zmax));
+  for (size_t k = 0; k < n_beams; ++k)
+    if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(v.device, &stream));
+  auto *c = new kc_mcl();
+  c->map = map;
+  c->device = v.device;
+  c->stream = stream;
+  c->N = n_particles;
+  c->B = n_beams;
+  c->range_max = range_max;
+  c->rc = rc;
+  c->zmax = zmax;
+  c->seed = seed;
+  const size_t N = n_particles;
+  int e = KC_OK;
+  for (int b = 0; b < 2 && !e; ++b)
+    if ((e = c->d_tx[b].reserve(N)) || (e = c->d_ty[b].reserve(N)) || (e = c->d_h[b].reserve(N))) break;
+  if (!e && ((e = c->d_acc.reserve(N)) || (e = c->d_cost.reserve(N)) || (e = c->d_w.reserve(N)) || (e = c->d_cum.reserve(N)) ||
+             (e = c->d_min_prev.reserve(1)) || (e = c->d_heading.reserve(65536)) || (e = c->d_zq.reserve(n_beams)) ||
+             (e = c->h_zq.reserve(n_beams)) || (e = c->d_rec.reserve(1)) || (e = c->h_rec.reserve(1)) ||
+             (e = c->table.ensure(angles, n_beams, stream)))) {
+  }
+  if (!e) {
+    hipError_t he = hipMemcpyAsync(c->d_heading.p, mcl_heading_table(), 65536 * sizeof(int2), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) {
+      set_error("the heading table's upload failed: %s", hipGetErrorString(he));
+      e = KC_ERR_HIP;
+    }
+  }
+  if (e) {
+    kc_mcl_destroy(c);
+    return e;
+  }
+  *out = c;
+  return KC_OK;
+}
+
+void kc_mcl_destroy(kc_mcl *c) {
+  if (!c) return;
+  close_device_stream(c->device, &c->stream);
+  delete c;  // (the device is current: the buffers and the events go with the context)
+}
+
+int kc_mcl_info(kc_mcl *c, size_t *n_particles_out, size_t *n_beams_out, int32_t *rc_out, int64_t *zmax_out, uint32_t *step_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (n_particles_out) *n_particles_out = c->N;
+  if (n_beams_out) *n_beams_out = c->B;
+  if (rc_out) *rc_out = c->rc;
+  if (zmax_out) *zmax_out = c->zmax;
+  if (step_out) *step_out = c->step;
+  return KC_OK;
+}
+
+int kc_mcl_set_model(kc_mcl *c, const uint16_t *pen, size_t n_pen, int err_shift, const uint32_t *wtab, size_t n_wtab, int w_shift) {
+  if (!c || !pen || !wtab) KC_FAIL(KC_ERR_INVALID, "null argument");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
+  KC_TRY(mcl_check(v.res, c->N, c->B, c->range_max, pen, n_pen, err_shift, wtab, n_wtab, w_shift, 0u, nullptr, nullptr));
+  KC_HIP(hipSetDevice(c->device));
+  c->have_model = false;
+  KC_TRY(c->d_pen.reserve(n_pen));
+  KC_TRY(c->d_wtab.reserve(n_wtab));
+  // from the caller's memory: the copies return once the source may be reused or, as here, after the drain
+  KC_HIP(hipMemcpyAsync(c->d_pen.p, pen, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipMemcpyAsync(c->d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->E = static_cast<int>(n_pen);
+  c->err_shift = err_shift;
+  c->EW = static_cast<int>(n_wtab);
+  c->w_shift = w_shift;
+  c->have_model = true;
+  c->have_weights = false;  // weights of another table
+  return KC_OK;
+}
+
+int kc_mcl_init_pose(kc_mcl *c, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s_xy, int32_t s_h) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (tx0 < -kMclMaxOffset || tx0 > kMclMaxOffset || ty0 < -kMclMaxOffset || ty0 > kMclMaxOffset)
+    KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
+  if (h0 > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h0);
+  if (s_xy < 0 || s_h < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
+  KC_HIP(hipSetDevice(c->device));
+  c->inited = false;
+  const int N = static_cast<int>(c->N);
+  hipLaunchKernelGGL(mcl_init_pose_kernel, dim3(mcl_blocks(c->N)), dim3(kMclBlock), 0, c->stream, c->state(0), c->d_acc.p,
+                     c->d_cost.p, c->d_min_prev.p, mcl_key(c, 0), static_cast<long long>(tx0), static_cast<long long>(ty0), h0, s_xy,
+                     s_h, N);
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipStreamSynchronize(c->stream));
+  mcl_started(c, 0);
+  return KC_OK;
+}
+
+int kc_mcl_init_global(kc_mcl *c, size_t *n_free_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (n_free_out) *n_free_out = 0;
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
+  KC_HIP(hipSetDevice(c->device));
+  c->inited = false;
+  const size_t H = static_cast<size_t>(v.H);
+  KC_TRY(c->d_rows.reserve(H));
+  KC_TRY(c->d_before.reserve(H + 1));
+  KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
+  hipLaunchKernelGGL(mcl_row_count_kernel, dim3(static_cast<unsigned>(H)), dim3(kMclBlock), 0, c->stream, v.cls, v.W, c->d_rows.p);
+  KC_HIP(hipGetLastError());
+  std::vector<unsigned> rows(H);
+  KC_HIP(hipMemcpyAsync(rows.data(), c->d_rows.p, H * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  std::vector<unsigned long long> before(H + 1, 0ull);
+  for (size_t j = 0; j < H; ++j) before[j + 1] = before[j] + rows[j];
+  if (n_free_out) *n_free_out = static_cast<size_t>(before[H]);
+  if (before[H] == 0) KC_FAIL(KC_ERR_STATE, "the map has no KC_EMPTY cell to seed a particle in");
+  KC_HIP(hipMemcpyAsync(c->d_before.p, before.data(), (H + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(mcl_init_global_kernel, dim3(mcl_blocks(c->N * 64)), dim3(kMclBlock), 0, c->stream, v.cls, v.W, v.H,
+                     c->d_before.p, c->state(0), c->d_acc.p, c->d_cost.p, c->d_min_prev.p, mcl_key(c, 0), static_cast<int>(c->N));
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipStreamSynchronize(c->stream));  // `before` is the copy's source
+  mcl_started(c, 0);
+  return KC_OK;
+}
+
+// Check order: null arguments; the state (model, init); increments, scales, flags, the ranges; then the device
+int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, int32_t s_l, int32_t s_h, const int32_t *zq,
+                unsigned int flags, kc_mcl_record *out) {
+  if (!c || !zq || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  if (!c->have_model) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_set_model first");
+  if (!c->inited) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_init_pose or kc_mcl_init_global first");
+  if (d_f < -kMclMaxOffset || d_f > kMclMaxOffset || d_l < -kMclMaxOffset || d_l > kMclMaxOffset)
+    KC_FAIL(KC_ERR_RANGE, "the odometry increment is above 2^20 cells");
+  if (s_f < 0 || s_l < 0 || s_h < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
+  if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS | KC_MCL_SKIP_NO_RETURN))
+    KC_FAIL(KC_ERR_INVALID, "unknown localiser flag bits 0x%x", flags);
+  for (size_t k = 0; k < c->B; ++k)
+    if (!((zq[k] >= 0 && zq[k] <= c->zmax) || (zq[k] == -1 && (flags & KC_MCL_SKIP_NO_RETURN))))
+      KC_FAIL(KC_ERR_INVALID, "quantised range %zu is %d, outside 0 .. %lld", k, zq[k], c->zmax);
+  if (c->step == 0xFFFFFFFFu) KC_FAIL(KC_ERR_STATE, "the step counter is exhausted: init again");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
+  KC_HIP(hipSetDevice(c->device));
+  std::memcpy(c->h_zq.p, zq, c->B * sizeof(int32_t));
+  KC_HIP(hipMemcpyAsync(c->d_zq.p, c->h_zq.p, c->B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
+  const unsigned step = c->step + 1;
+  MclWalkArgs a{};
+  a.cls = v.cls;
+  a.table = reinterpret_cast<const int2 *>(c->table.d.p);
+  a.heading = c->d_heading.p;
+  a.in = c->state(c->cur);
+  a.out = c->state(c->cur ^ 1);
+  a.zq = c->d_zq.p;
+  a.pen = c->d_pen.p;
+  a.cost = c->d_cost.p;
+  a.key = mcl_key(c, step);
+  a.d_f = d_f;
+  a.d_l = d_l;
+  a.zmax = c->zmax;
+  a.d_h = d_h;
+  a.s_f = s_f;
+  a.s_l = s_l;
+  a.s_h = s_h;
+  a.W = v.W;
+  a.H = v.H;
+  a.N = static_cast<int>(c->N);
+  a.B = static_cast<int>(c->B);
+  a.rc = c->rc;
+  a.unknown_blocks = (flags & KC_SCAN_UNKNOWN_BLOCKS) ? 1 : 0;
+  a.E = c->E;
+  a.err_shift = c->err_shift;
+  // from here on the particles are the new buffer's, whatever fails: a failed step asks for a new init
+  c->inited = false;
+  c->have_weights = false;
+  c->step_time.begin_cycle();
+  KC_TRY(c->step_time.start("walk", c->stream));
+  hipLaunchKernelGGL(mcl_walk_kernel, dim3(mcl_blocks(c->N * c->B)), dim3(kMclBlock), 0, c->stream, a);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->step_time.stop(c->stream));
+  MclWeighArgs w{};
+  w.st = a.out;
+  w.acc = c->d_acc.p;
+  w.cost = c->d_cost.p;
+  w.w = c->d_w.p;
+  w.min_prev = c->d_min_prev.p;
+  w.wtab = c->d_wtab.p;
+  w.heading = c->d_heading.p;
+  w.rec = c->d_rec.p;
+  w.N = a.N;
+  w.EW = c->EW;
+  w.w_shift = c->w_shift;
+  w.step = step;
+  KC_TRY(c->step_time.start("weigh", c->stream));
+  hipLaunchKernelGGL(mcl_weigh_kernel, dim3(1), dim3(kMclOne), 0, c->stream, w);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->step_time.stop(c->stream));
+  KC_HIP(hipMemcpyAsync(c->h_rec.p, c->d_rec.p, sizeof(kc_mcl_record), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  *out = *c->h_rec.p;
+  if (out->step != step || out->w1 == 0) KC_FAIL(KC_ERR_HIP, "the step's record is not this step's");
+  c->cur ^= 1;
+  c->step = step;
+  c->w1 = out->w1;
+  c->inited = true;
+  c->have_weights = true;
+  return KC_OK;
+}
+
+int kc_mcl_resample(kc_mcl *c) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->inited || !c->have_weights) KC_FAIL(KC_ERR_STATE, "a resample needs the weights of a step since the last init or resample");
+  KC_HIP(hipSetDevice(c->device));
+  const int N = static_cast<int>(c->N);
+  const unsigned long long u0 = mcl_draw(mcl_key(c, c->step), c->N, 15) % c->w1;
+  c->inited = false;
+  c->have_weights = false;
+  c->resample_time.begin_cycle();
+  KC_TRY(c->resample_time.start("prefix", c->stream));
+  hipLaunchKernelGGL(mcl_prefix_kernel, dim3(1), dim3(kMclOne), 0, c->stream, c->d_w.p, c->d_cum.p, N);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->resample_time.stop(c->stream));
+  KC_TRY(c->resample_time.start("select", c->stream));
+  hipLaunchKernelGGL(mcl_select_kernel, dim3(mcl_blocks(c->N)), dim3(kMclBlock), 0, c->stream, c->state(c->cur), c->state(c->cur ^ 1),
+                     c->d_acc.p, c->d_min_prev.p, c->d_cum.p, u0, c->w1, N);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->resample_time.stop(c->stream));
+  c->cur ^= 1;
+  c->inited = true;
+  return KC_OK;
+}
+
+int kc_mcl_particles(kc_mcl *c, int64_t *tx_out, int64_t *ty_out, uint32_t *h_out, uint32_t *acc_out, size_t cap) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->inited) KC_FAIL(KC_ERR_STATE, "no particles before an init");
+  if (cap < c->N) KC_FAIL(KC_ERR_RANGE, "%zu particles do not fit the output capacity %zu", c->N, cap);
+  KC_HIP(hipSetDevice(c->device));
+  const MclState s = c->state(c->cur);
+  if (tx_out) KC_HIP(hipMemcpyAsync(tx_out, s.tx, c->N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (ty_out) KC_HIP(hipMemcpyAsync(ty_out, s.ty, c->N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  if (h_out) KC_HIP(hipMemcpyAsync(h_out, s.h, c->N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (acc_out) KC_HIP(hipMemcpyAsync(acc_out, c->d_acc.p, c->N * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_mcl_particles_device(kc_mcl *c, void **tx_out, void **ty_out, void **h_out, void **acc_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->inited) KC_FAIL(KC_ERR_STATE, "no particles before an init");
+  const MclState s = c->state(c->cur);
+  if (tx_out) *tx_out = s.tx;
+  if (ty_out) *ty_out = s.ty;
+  if (h_out) *h_out = s.h;
+  if (acc_out) *acc_out = c->d_acc.p;
+  return KC_OK;
+}
+
+int kc_mcl_set_timing(kc_mcl *c, int enable) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  c->step_time.enabled = c->resample_time.enabled = enable != 0;
+  c->step_time.begin_cycle();
+  c->resample_time.begin_cycle();
+  return KC_OK;
+}
+
+int kc_mcl_times(kc_mcl *c, float ms_out[4]) {
+  if (!c || !ms_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  ms_out[0] = ms_out[1] = ms_out[2] = ms_out[3] = 0.0f;
+  if (!c->step_time.enabled || c->step_time.used != 2) KC_FAIL(KC_ERR_STATE, "no step has been timed on this localiser");
+  KC_HIP(hipSetDevice(c->device));
+  size_t n = 0;
+  KC_TRY(c->step_time.get(nullptr, ms_out, 2, &n));
+  if (c->resample_time.used == 2) KC_TRY(c->resample_time.get(nullptr, ms_out + 2, 2, &n));
+  return KC_OK;
+}
+
+}  // extern "C"

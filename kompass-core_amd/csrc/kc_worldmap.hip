@@ -52,6 +52,7 @@
 
 #include "kc_internal.h"
 #include "kompass_hip.h"
+#include "kc_worldmap_walk.h"
 
 namespace kc {
 
@@ -405,8 +406,6 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_window_points_kernel(WmWind
 
 // ---- virtual laser scan (rules 20 to 27) -------------------------------------------------------------------------
 constexpr int kWmScanBlock = 256;          // beams a workgroup
-constexpr int kWmScanS = 8;                // steps of the walk a round: their byte loads are in flight together
-constexpr int kWmScanEnd = 1;              // a step outside rule 23's box; no cls byte has this value
 constexpr size_t kWmScanMaxBeams = 65536;
 constexpr size_t kWmScanMaxRays = size_t{1} << 22;
 
@@ -427,86 +426,23 @@ __device__ __forceinline__ double wm_scan_range(int e, int a, double res) {
   return (static_cast<double>(e) * 16384.0 / static_cast<double>(a)) * res;
 }
 
-__device__ __forceinline__ bool wm_scan_blocks(int v, int unknown_blocks) {
-  return v == KC_OCCUPIED || (unknown_blocks && v == KC_UNEXPLORED);
-}
-
-// blockIdx.x: the pose; blockIdx.y * 256 + threadIdx.x: the beam.  The walk's addresses do not depend on the bytes it
-// loads, so a round forms kWmScanS steps ahead, loads their bytes together (a step outside the map loads cell 0 and drops
-// it: no branch around a load), and only then looks for the first one that ends the beam.  D = ex |dy| - ey |dx| is kept
-// by addition.  Between rounds the walk also ends once the last step's own r is above range_max: r never decreases along
-// a walk (rule 24), so no later cell could count, and the output is that of the full box.
+// blockIdx.x: the pose; blockIdx.y * 256 + threadIdx.x: the beam.  The walk is wm_walk (kc_worldmap_walk.h), which the
+// Monte-Carlo localiser shares; it is given up between rounds once the last step's own r is above range_max: r never
+// decreases along a walk (rule 24), so no later cell could count, and the output is that of the full box.
 __global__ __launch_bounds__(kWmScanBlock) void worldmap_scan_kernel(WmScanArgs a) {
   const int k = static_cast<int>(blockIdx.y) * kWmScanBlock + static_cast<int>(threadIdx.x);
   if (k >= a.B) return;
   const kc_worldmap_pose p = a.poses ? a.poses[blockIdx.x] : a.pose;
-  const int2 t = a.table[k];
-  const long long cq = p.cq, sq = p.sq;
-  const int dx = static_cast<int>((cq * t.x - sq * t.y + (1ll << 15)) >> 16);
-  const int dy = static_cast<int>((sq * t.x + cq * t.y + (1ll << 15)) >> 16);
-  const long long X0 = p.tx + (1ll << 15), Y0 = p.ty + (1ll << 15);
-  const int I0 = static_cast<int>(X0 >> 16), J0 = static_cast<int>(Y0 >> 16);
-  const int fx = static_cast<int>(X0 & 0xFFFF), fy = static_cast<int>(Y0 & 0xFFFF);
-  const int sx = dx > 0 ? 1 : -1, sy = dy > 0 ? 1 : -1;
-  const int adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
-  int ex = dx > 0 ? 65536 - fx : fx, ey = dy > 0 ? 65536 - fy : fy;
-  long long D = static_cast<long long>(ex) * ady - static_cast<long long>(ey) * adx;
-  const long long step_x = 65536ll * ady, step_y = 65536ll * adx;
-  const bool only_x = dy == 0, only_y = dx == 0;
-  const int box = a.rc + 1;
-  int I = I0, J = J0;
-  bool hit = false, done = false;
+  WmWalkHit h{0, 1, 0, 0};
+  const bool blocked = wm_walk(a.cls, a.W, a.H, a.rc, a.unknown_blocks, p, a.table[k],
+                               [&](int e, int ax) { return wm_scan_range(e, ax, a.res) > a.range_max; }, &h);
+  bool hit = false;
   double r = 0.0;
-  int hit_i = I0, hit_j = J0;
-  if (I0 >= 0 && I0 < a.W && J0 >= 0 && J0 < a.H &&
-      wm_scan_blocks(a.cls[static_cast<size_t>(I0) + static_cast<size_t>(J0) * static_cast<size_t>(a.W)], a.unknown_blocks))
-    hit = done = true;  // rule 23: e = 0
-  // every step leaves a cell, so 2 (Rc + 2) steps leave the box along one axis: the count only bounds the loop
-  const int max_rounds = (2 * (a.rc + 2)) / kWmScanS + 2;
-  for (int round = 0; round < max_rounds && !done; ++round) {
-    const int Is = I, Js = J;
-    int es[kWmScanS], v[kWmScanS];
-    unsigned xmask = 0u;
-#pragma unroll
-    for (int s = 0; s < kWmScanS; ++s) {
-      if (only_x || (!only_y && D <= 0)) {
-        es[s] = ex;
-        I += sx;
-        ex += 65536;
-        D += step_x;
-        xmask |= 1u << s;
-      } else {
-        es[s] = ey;
-        J += sy;
-        ey += 65536;
-        D -= step_y;
-      }
-      const int di = I - I0, dj = J - J0;
-      const bool out = di > box || di < -box || dj > box || dj < -box;
-      const bool in = !out && I >= 0 && I < a.W && J >= 0 && J < a.H;
-      const size_t cell = in ? static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W) : size_t{0};
-      const int byte = a.cls[cell];
-      v[s] = out ? kWmScanEnd : (in ? byte : static_cast<int>(KC_EMPTY));
-    }
-#pragma unroll
-    for (int s = 0; s < kWmScanS; ++s) {
-      if (done) continue;
-      if (v[s] == kWmScanEnd) {
-        done = true;
-      } else if (wm_scan_blocks(v[s], a.unknown_blocks)) {
-        done = true;
-        const int nx = __popc(xmask & ((2u << s) - 1u));
-        const double rr = wm_scan_range(es[s], (xmask >> s) & 1u ? adx : ady, a.res);
-        if (rr <= a.range_max) {
-          hit = true;
-          r = rr;
-          hit_i = Is + sx * nx;
-          hit_j = Js + sy * (s + 1 - nx);
-        }
-      }
-    }
-    if (!done && wm_scan_range(es[kWmScanS - 1], (xmask >> (kWmScanS - 1)) & 1u ? adx : ady, a.res) > a.range_max) done = true;
+  if (blocked) {  // the first blocking cell decides, and counts iff r <= range_max
+    r = wm_scan_range(h.e, h.a, a.res);
+    hit = r <= a.range_max;
   }
+  const int hit_i = h.i, hit_j = h.j;
   double out = hit ? r : a.range_max;
   if (a.real) {  // rule 27: a NaN compares false, an infinity is left out by name
     const double q = a.real[k];

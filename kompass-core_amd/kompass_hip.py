@@ -8,6 +8,7 @@ loudly when the library has not been built, and every compute call raises
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from pathlib import Path
 
@@ -122,6 +123,28 @@ class WorldMapMatchResult(C.Structure):
         p = self.pose
         return dict(k=int(self.k), u=int(self.u), v=int(self.v), score=int(self.score), score_guess=int(self.score_guess),
                     points=int(self.n_points), pose=(int(p.cq), int(p.sq), int(p.tx), int(p.ty)))
+
+
+class MclRecord(C.Structure):
+    """kc_mcl_record: the exact sums of one localiser step (DESIGN.md 4.11 rule 37)."""
+    _fields_ = [("w1", C.c_uint64), ("w2", C.c_uint64), ("sx_lo", C.c_uint64), ("sx_hi", C.c_int64),
+                ("sy_lo", C.c_uint64), ("sy_hi", C.c_int64), ("sc", C.c_int64), ("ss", C.c_int64),
+                ("best_tx", C.c_int64), ("best_ty", C.c_int64), ("best_h", C.c_uint32), ("amin", C.c_uint32),
+                ("best", C.c_uint32), ("step", C.c_uint32)]
+
+    @property
+    def sx(self):
+        """SX as a Python int: (hi << 64) + lo."""
+        return (int(self.sx_hi) << 64) + int(self.sx_lo)
+
+    @property
+    def sy(self):
+        return (int(self.sy_hi) << 64) + int(self.sy_lo)
+
+    def as_tuple(self):
+        """(w1, w2, sx, sy, sc, ss, amin, best, best_tx, best_ty, best_h, step)"""
+        return (int(self.w1), int(self.w2), self.sx, self.sy, int(self.sc), int(self.ss), int(self.amin), int(self.best),
+                int(self.best_tx), int(self.best_ty), int(self.best_h), int(self.step))
 
 
 _fp = C.POINTER(C.c_float)
@@ -326,6 +349,22 @@ SIGNATURES = {
     "kc_worldmap_match_scores": (C.c_int, [_vp, C.c_void_p, _sz]),
     "kc_worldmap_match_set_timing": (C.c_int, [_vp, C.c_int]),
     "kc_worldmap_match_times": (C.c_int, [_vp, _fp]),
+    "kc_mcl_check": (C.c_int, [C.c_float, _sz, _sz, C.c_float, C.c_void_p, _sz, C.c_int, C.c_void_p, _sz, C.c_int, C.c_uint,
+                               _ip, C.POINTER(C.c_int64)]),
+    "kc_mcl_heading": (C.c_int, [C.c_uint32, _ip, _ip]),
+    "kc_mcl_create": (C.c_int, [_vp, _sz, _dp, _sz, C.c_float, C.c_uint64, C.POINTER(_vp)]),
+    "kc_mcl_destroy": (None, [_vp]),
+    "kc_mcl_info": (C.c_int, [_vp, C.POINTER(_sz), C.POINTER(_sz), _ip, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]),
+    "kc_mcl_set_model": (C.c_int, [_vp, C.c_void_p, _sz, C.c_int, C.c_void_p, _sz, C.c_int]),
+    "kc_mcl_init_pose": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_uint32, C.c_int32, C.c_int32]),
+    "kc_mcl_init_global": (C.c_int, [_vp, C.POINTER(_sz)]),
+    "kc_mcl_step": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip, C.c_uint,
+                              C.POINTER(MclRecord)]),
+    "kc_mcl_resample": (C.c_int, [_vp]),
+    "kc_mcl_particles": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz]),
+    "kc_mcl_particles_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "kc_mcl_set_timing": (C.c_int, [_vp, C.c_int]),
+    "kc_mcl_times": (C.c_int, [_vp, _fp]),
 }
 
 _lib = None
@@ -1644,3 +1683,110 @@ class WorldMapContext(_Owner, _StreamOrdered):
         e = np.empty((w, h), np.int8, order="F")
         _check(lib().kc_worldmap_get(self.h, c.ctypes.data, e.ctypes.data, c.size))
         return c, e
+
+
+MCL_SKIP_NO_RETURN = 2  # KC_MCL_SKIP_NO_RETURN
+MCL_NOISE_STD = math.sqrt((65536.0 * 65536.0 - 1.0) / 3.0)  # rule 30: of the sum of four uniform 16-bit fields
+
+
+def mcl_check(resolution, n_particles, n_beams, range_max, pen=None, err_shift=0, wtab=None, w_shift=0, flags=0):
+    """Rule 38's refusals (host only) -> (Rc, ZMAX); raises ValueError / IndexError.  pen, wtab: None skips a table."""
+    pn = None if pen is None else np.ascontiguousarray(pen, dtype=np.uint16)
+    wt = None if wtab is None else np.ascontiguousarray(wtab, dtype=np.uint32)
+    rc, zmax = C.c_int32(), C.c_int64()
+    _check(lib().kc_mcl_check(float(np.float32(resolution)), int(n_particles), int(n_beams), float(np.float32(range_max)),
+                              None if pn is None else pn.ctypes.data, 0 if pn is None else pn.size, int(err_shift),
+                              None if wt is None else wt.ctypes.data, 0 if wt is None else wt.size, int(w_shift),
+                              int(flags), C.byref(rc), C.byref(zmax)))
+    return rc.value, zmax.value
+
+
+def mcl_heading(h):
+    """Rule 29 for one heading (host only) -> (Cq, Sq)."""
+    cq, sq = C.c_int32(), C.c_int32()
+    _check(lib().kc_mcl_heading(int(h), C.byref(cq), C.byref(sq)))
+    return cq.value, sq.value
+
+
+def mcl_noise_scale(sigma_units):
+    """Rule 30: the int32 scale s of a sigma given in the quantity's own units (2^-16 cells, 2^-16 turns)."""
+    s = round(float(sigma_units) * 65536.0 / MCL_NOISE_STD)
+    if not 0 <= s <= 0x7FFFFFFF:
+        raise ValueError("sigma out of range")
+    return s
+
+
+def mcl_quantise_ranges(ranges, resolution, range_max, flags=0):
+    """Rule 33 (host): int32 [B]."""
+    r, m = float(np.float32(resolution)), float(np.float32(range_max))
+    zmax = round(m / r * 65536.0)
+    none = -1 if int(flags) & MCL_SKIP_NO_RETURN else zmax
+    return np.array([round(float(z) / r * 65536.0) if (math.isfinite(float(z)) and 0.0 <= float(z) < m) else none
+                     for z in np.asarray(ranges, dtype=np.float64).reshape(-1)], np.int32)
+
+
+class MclContext(_Owner):
+    """Owner of one kc_mcl context (DESIGN.md 4.11 rules 28 to 41): a Monte-Carlo localiser over a WorldMapContext,
+    which it keeps alive.  Works in the ABI's integers; kompass_core.mapping.MCL is the front end in metres."""
+    _kc = "kc_mcl"
+
+    def __init__(self, world_map: "WorldMapContext", n_particles, angles, range_max, seed=0):
+        self.map = world_map
+        a = _f64(angles).reshape(-1)
+        self.n, self.n_beams = int(n_particles), len(a)
+        self.range_max = float(np.float32(range_max))
+        self._open(lib().kc_mcl_create, world_map.h, self.n, _pd(a), len(a), self.range_max, int(seed) & (2 ** 64 - 1))
+        self.rc, self.zmax = mcl_check(world_map.resolution, self.n, self.n_beams, self.range_max)
+
+    def set_model(self, pen, err_shift, wtab, w_shift):
+        pn, wt = np.ascontiguousarray(pen, dtype=np.uint16), np.ascontiguousarray(wtab, dtype=np.uint32)
+        _check(lib().kc_mcl_set_model(self.h, pn.ctypes.data, pn.size, int(err_shift), wt.ctypes.data, wt.size,
+                                      int(w_shift)))
+
+    def init_pose(self, tx0, ty0, h0, s_xy, s_h):
+        _check(lib().kc_mcl_init_pose(self.h, int(tx0), int(ty0), int(h0), int(s_xy), int(s_h)))
+
+    def init_global(self) -> int:
+        """-> the free cells; KompassHipError (KC_ERR_STATE) when the map has none."""
+        n = _sz(0)
+        _check(lib().kc_mcl_init_global(self.h, C.byref(n)))
+        return int(n.value)
+
+    def step(self, d_f, d_l, d_h, s_f, s_l, s_h, zq, flags=0) -> MclRecord:
+        z = np.ascontiguousarray(zq, dtype=np.int32).reshape(-1)
+        if z.size != self.n_beams:
+            raise ValueError("one quantised range a beam")
+        r = MclRecord()
+        _check(lib().kc_mcl_step(self.h, int(d_f), int(d_l), int(d_h), int(s_f), int(s_l), int(s_h),
+                                 z.ctypes.data_as(_ip), int(flags), C.byref(r)))
+        return r
+
+    def resample(self):
+        _check(lib().kc_mcl_resample(self.h))
+
+    def particles(self):
+        """(tx int64, ty int64, h uint32, acc uint32), N each, copied to the host."""
+        tx, ty = np.empty(self.n, np.int64), np.empty(self.n, np.int64)
+        h, acc = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
+        _check(lib().kc_mcl_particles(self.h, tx.ctypes.data, ty.ctypes.data, h.ctypes.data, acc.ctypes.data, self.n))
+        return tx, ty, h, acc
+
+    def particles_device(self):
+        """The four device addresses (tx, ty, h, acc): valid until the next step, resample or init."""
+        p = [_vp() for _ in range(4)]
+        _check(lib().kc_mcl_particles_device(self.h, *[C.byref(v) for v in p]))
+        return tuple(v.value for v in p)
+
+    def step_count(self) -> int:
+        s = C.c_uint32()
+        _check(lib().kc_mcl_info(self.h, None, None, None, None, C.byref(s)))
+        return s.value
+
+    def set_timing(self, enable=True):
+        _check(lib().kc_mcl_set_timing(self.h, int(bool(enable))))
+
+    def times(self):
+        """(walk, weigh, prefix, select) launches in milliseconds, by HIP events; the last two 0 without a resample."""
+        ms = (C.c_float * 4)()
+        _check(lib().kc_mcl_times(self.h, ms))
+        return tuple(float(v) for v in ms)

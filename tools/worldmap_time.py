@@ -42,7 +42,18 @@ the scan frame in the middle, range_max 10 m (Rc = 200).  One JSON line with
       implementation) timed once.
 The ranges of (a) at 360 beams are compared with the statement once.
 
-  python tools/worldmap_time.py --scan [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --scan [--reps 30] [--warmup 3]
+
+--mcl times the Monte-Carlo localiser instead (rules 28 to 41): the same world, 4096 particles x 64 beams and 1024 x 256
+beams spread 2 m around the middle, range_max 10 m.  One JSON line a configuration with
+  (a) kc_mcl_step and kc_mcl_step + kc_mcl_resample by the host's clock, and their launches by HIP events (walk, weigh,
+      prefix, select);
+  (b) the route that exists without the localiser: kc_worldmap_scan of the same N poses x B beams to the host, and the
+      penalty sum over its ranges in numpy (vectorised numpy on one CPU thread: a Python statement's cost, not a compiled
+      CPU filter);
+  (c) kc_worldmap_scan alone for the same rays, by the host's clock with its read-back of N x B doubles: the floor the
+      walk sets, and the ratio of the step's walk launch to it.
+  python tools/worldmap_time.py --mcl [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -247,6 +258,72 @@ def scan_leg(args):
         print(json.dumps(line), flush=True)
 
 
+def mcl_leg(args):
+    import worldmap_mcl_ref as lref
+
+    ang, rng = syn.dense_scan(2048, 1.2)
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r, ORIGIN[1] + (H // 2) * r)
+    range_max = 10.0
+    pen, err_shift, wtab, w_shift = lref.sensor_tables(RES, 0.1)
+    pen_np = np.array(pen, np.int64)
+    cells = 65536.0 / r
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as wm:
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        wm.update_from_mapper(mapper, centre + (0.0,))
+        for n, b in ((4096, 64), (1024, 256)):
+            a = np.arange(b) * (2 * np.pi / b)
+            zq = kh.mcl_quantise_ranges(wm.scan(centre + (0.3,), a, range_max), RES, range_max)
+            with kh.MclContext(wm, n, a, range_max, seed=1) as mcl:
+                mcl.set_model(pen, err_shift, wtab, w_shift)
+                q0 = wm.quantise_pose(*centre, 0.0)
+                scales = (lref.noise_scale(0.02 * cells), lref.noise_scale(0.01 * cells), lref.noise_scale(0.01 / (2 * np.pi) * 65536))
+
+                def init():
+                    mcl.init_pose(q0.tx, q0.ty, 0, lref.noise_scale(2.0 * cells), lref.noise_scale(65536 / 4))
+
+                def step():
+                    return mcl.step(3000, 0, 50, *scales, zq)
+
+                def step_resample():
+                    step()
+                    mcl.resample()
+
+                init()
+                rec = step()
+                tx, ty, h, _ = mcl.particles()
+                poses = [kh.WorldMapPose(*kh.mcl_heading(int(hh)), int(x), int(y)) for x, y, hh in zip(tx, ty, h)]
+                zmax = mcl.zmax
+
+                def scan_only():
+                    return wm.scan(poses, a, range_max)
+
+                def scan_and_sum():
+                    ranges = scan_only()
+                    q = np.minimum(np.rint(ranges / r * 65536.0).astype(np.int64), zmax)
+                    bins = np.minimum(np.abs(q - zq[None, :].astype(np.int64)) >> err_shift, len(pen) - 1)
+                    return pen_np[bins].sum(axis=1)
+
+                line = {"world": [W, H], "particles": n, "beams": b, "rays": n * b, "range_max": range_max, "reps": args.reps,
+                        "warmup": args.warmup, "n_eff_first_step": round(rec.w1 * rec.w1 / rec.w2, 1),
+                        "a_step_ms": timed(step, args.reps, args.warmup),
+                        "a_step_and_resample_ms": timed(step_resample, args.reps, args.warmup)}
+                mcl.set_timing(True)
+                parts = []
+                for k in range(args.warmup + args.reps):
+                    step_resample()
+                    if k >= args.warmup:
+                        parts.append(mcl.times())
+                mcl.set_timing(False)
+                for i, name in enumerate(["walk", "weigh", "prefix", "select"]):
+                    line[f"launch_{name}_ms"] = spread([p[i] for p in parts])
+                line["b_scan_to_host_and_numpy_penalty_sum_ms"] = timed(scan_and_sum, args.reps, args.warmup)
+                line["c_scan_to_host_alone_ms"] = timed(scan_only, args.reps, args.warmup)
+                line["c_walk_launch_over_scan_call"] = round(line["launch_walk_ms"][0] / line["c_scan_to_host_alone_ms"][0], 3)
+                print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -255,6 +332,7 @@ def main():
     ap.add_argument("--match", action="store_true", help="time the correlative match instead of the update")
     ap.add_argument("--points", action="store_true", help="time the obstacle hand-off to the controller instead")
     ap.add_argument("--scan", action="store_true", help="time the virtual laser scan instead")
+    ap.add_argument("--mcl", action="store_true", help="time the Monte-Carlo localiser instead")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
@@ -264,6 +342,8 @@ def main():
         return points_leg(args)
     if args.scan:
         return scan_leg(args)
+    if args.mcl:
+        return mcl_leg(args)
     hip = hip_runtime()
     ang, rng = syn.dense_scan(2048, 1.2)                      # ranges 3.6 .. 8.4 m in a 20 m window
     pose_xy = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021)
