@@ -2,6 +2,8 @@
 // small list / count helpers.  Part of kc_dwa.hip.
 #pragma once
 
+#include "kc_launch_plan.h"
+
 namespace kc {
 
 // ===========================================================================
@@ -50,18 +52,10 @@ namespace kc {
 // ===========================================================================
 constexpr int kCostBlock = 1024;  // 16 wavefronts = 16 samples in flight, one workgroup per CU
 constexpr int kCostWaves = kCostBlock / 64;
-constexpr int kCostGrid = 256;    // one workgroup per CU
-// LDS the search tables of a workgroup may take
-constexpr size_t kCostLdsBudget = 150 * 1024;
+// (kCostGrid, kCostLdsBudget, kBlkLdsBudget, kBlockKernelMaxAdm, kCompactMaxPer: kc_launch_plan.h)
 constexpr int kSegChunkMin = 16;
 constexpr int kCoopMinSkip = 3;   // empty cells around every point from which the obstacle search
                                   // of a sample is done point by point by the whole wavefront
-// Longest list the workgroup-per-sample kernel gets by itself.  Round 2 measured a crossover near 650 samples; since then
-// the wavefront-per-sample kernel got the near table, the union-rectangle scan and the folded publish, and round 4's
-// density sweep finds it ahead at every list length (cfg3: 0 / 123 / 489 admissible: 10.4 / 24.2 / 25.7 us against
-// 7.3 + 6.5 / 27.7 + 6.6 / 36.7 + 6.6 with the publish kernel the block kernel needs; cfg2's three-kernel cycle at 393:
-// 18.9 against 16.4 + 6.6).  The block kernel stays behind option cost_kernel = 1.
-constexpr long long kBlockKernelMaxAdm = -1;
 
 struct BucketDev {
   int W, H;            // cells
@@ -338,7 +332,6 @@ __device__ __forceinline__ float wave_ordered_sum(float carry, float v, int lane
 // count of the previous cycle.
 // ---------------------------------------------------------------------------
 constexpr int kBlkCostBlock = 512;  // 8 wavefronts, two workgroups per CU
-constexpr size_t kBlkLdsBudget = 78 * 1024;
 
 // Where the float points of one sample come from: the sample-major rows in
 // global memory (split path, kc_cost_evaluate) or the double poses the fused
@@ -2282,7 +2275,6 @@ __global__ void republish_kernel(const long long *result, long long *host_pub, l
 // roll-out path and by kc_cost_evaluate (the fused kernel appends to the list
 // itself).  Every thread owns a contiguous chunk (all its flags are requested
 // up front: one memory latency), a block-wide scan gives the offsets.
-constexpr int kCompactMaxPer = 64;  // 1024 threads x 64 = 65536 samples
 
 #ifdef KC_TU_CYCLE  // (a non-template kernel is defined in ONE translation unit: kc_dwa_ctx.h)
 __global__ __launch_bounds__(1024) void compact_kernel(

@@ -754,8 +754,9 @@ int kc_trig_table(double yaw0, const double *omega, size_t n_rows, size_t n_step
   if (n_steps > 4096 || n_rows > (1u << 20)) KC_FAIL(KC_ERR_RANGE, "table of %zu x %zu entries", n_rows, n_steps);
   double om_max = 0.0;
   for (size_t i = 0; i < n_rows; ++i) om_max = std::max(om_max, std::fabs(omega[i]));
-  const double reach = std::fabs(yaw0) + om_max * std::fabs(dt) * static_cast<double>(n_steps);
-  if (!(reach < 1.0e8)) KC_FAIL(KC_ERR_RANGE, "yaw reaches %g: outside the table + Cody-Waite range of sincos", reach);
+  double reach;
+  if (!yaw_reach_ok(yaw0, om_max, std::fabs(dt), n_steps, &reach))
+    KC_FAIL(KC_ERR_RANGE, "yaw reaches %g: outside the table + Cody-Waite range of sincos", reach);
   DevBuf<double> d_om, d_tab;
   DevBuf<double2> d_out;
   KC_TRY(d_om.reserve(n_rows));
@@ -763,16 +764,7 @@ int kc_trig_table(double yaw0, const double *omega, size_t n_rows, size_t n_step
   KC_TRY(d_out.reserve(n_rows * n_steps));
   KC_HIP(hipMemcpy(d_om.p, omega, n_rows * sizeof(double), hipMemcpyHostToDevice));
   KC_HIP(hipMemcpy(d_tab.p, kc_sincostab_host, sizeof(kc_sincostab_host), hipMemcpyHostToDevice));
-  TrigJob tj{};
-  tj.yaw0 = yaw0;
-  tj.dt = dt;
-  tj.omega = d_om.p;
-  tj.tab = d_tab.p;
-  tj.out = d_out.p;
-  tj.A = static_cast<int>(n_rows);
-  tj.P = static_cast<int>(n_steps);
-  tj.nblk = static_cast<int>(std::min<size_t>(1024, blocks_for(n_rows * n_steps, kTrigBlock)));
-  KC_TRY(launch_trig_table(tj, nullptr));
+  KC_TRY(launch_trig_table(make_trig_job(yaw0, dt, d_om.p, d_tab.p, d_out.p, n_rows, n_steps, 1024, kTrigBlock), nullptr));
   KC_HIP(hipGetLastError());
   KC_HIP(hipMemcpy(cos_sin_out, d_out.p, n_rows * n_steps * sizeof(double2), hipMemcpyDeviceToHost));
   return KC_OK;

@@ -346,7 +346,7 @@ struct kc_dwa {
   int tilt_kz = 0;             // the scan's voxel layer in the octree frame
   // A tilted scan whose voxel columns span more than 8192 cells (fine octrees, long ranges) keeps the columns
   // within kTiltCrop cells of the robot's own column: nothing farther can be reached by a roll-out (checked
-  // per cycle against the horizon: rollout_impl), so dropping it changes no collision result.
+  // per cycle against the horizon: launch_tilted_collision), so dropping it changes no collision result.
   bool tilt_cropped = false;
   int tilt_cx = 0, tilt_cy = 0;  // the robot's column at the update (octree keys)
   double tilt_body_x = 0, tilt_body_y = 0;  // the pose of that update
@@ -374,10 +374,6 @@ struct kc_dwa {
   } pp;
 };
 
-// largest point list the device-side sensor update takes (bucket grid of at most 64 x 64 cells: about one obstacle per
-// cell up to 4 k points, hundreds per cell here); beyond: the host path, finer grid.  (262144 until a raw depth image --
-// 307 200 points -- was priced: 6 ms of host build at 500 k points against 0.16 ms here, tools/big_cloud_sweep.py.)
-constexpr size_t kSensorDeviceMax = 1048576;
 // sensor_points_kernel packs id | rank << 12 into an int (tcell): 12 bits of bucket id (kHistRow cells), and the rank of
 // a point among its workgroup's points in one cell, below kSensorBlock * ppt, with ppt the host's
 // ceil(n / (kHistRowsMax * kSensorBlock)).  At kSensorDeviceMax that is 64 k ranks: 28 bits.
@@ -388,19 +384,10 @@ constexpr size_t kSensorRankMax =
 static_assert(((kSensorRankMax << 12) | (kHistRow - 1)) <= static_cast<size_t>(INT_MAX),
               "id | rank << 12 of the largest device point list must fit an int");
 constexpr int kTiltCrop = 4000;                // half side of the kept window of a cropped tilted scan, in voxel columns
-constexpr size_t kSensorFusedMax = 32768;       // points up to which the one-launch sensor build CAN be used (spheres: it is their only device build)
-constexpr size_t kSensorFusedPays = 18432;      // ... and up to which it is ahead: every workgroup reads every point (tools/big_cloud_sweep.py,
-                                                // set_points + cycle with the one launch / the two: 10 k points 80.6 / 86.4 us, 16 k 161 / 160,
-                                                // 20 k 84.1 / 79.6, 24 k 91.7 / 84.4, 30 k 100.3 / 93.6)
-constexpr size_t kSensorFusedLds = 100 * 1024;  // dynamic LDS of sensor_fused_kernel (band rows; bucket tables + point ids)
 
 inline int use_device(const kc_dwa *c) {
   KC_HIP(hipSetDevice(c->prm.device));
   return KC_OK;
-}
-
-inline unsigned blocks_for(size_t n, unsigned per) {
-  return static_cast<unsigned>((n + per - 1) / per);
 }
 
 // accept one octree-frame point into the voxel column list
@@ -459,6 +446,65 @@ inline bool any_voxel(const kc_dwa *c) {
   return c->host_lists_valid ? !c->vox_kx.empty() : c->O > 0;
 }
 
+// dynamic LDS beyond 64 KB for a kernel (gfx950: 160 KB); false: the runtime refuses
+template <typename K>
+inline bool lds_optin(K kernel, size_t bytes) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) ==
+      hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  return false;
+}
+
+#ifdef KC_PHASE_STAMPS
+// the stamps of the first G workgroups (16 words each) -> h; *t0 = the first workgroup's start
+inline int fetch_stamps(kc_dwa *c, int G, std::vector<unsigned long long> &h, unsigned long long *t0) {
+  h.resize(static_cast<size_t>(G) * 16);
+  KC_HIP(hipStreamSynchronize(c->stream));
+  KC_HIP(hipMemcpy(h.data(), c->d_dbg.p, h.size() * 8, hipMemcpyDeviceToHost));
+  *t0 = ~0ull;
+  for (int r = 0; r < G; ++r) if (h[r * 16]) *t0 = std::min(*t0, h[r * 16]);
+  return KC_OK;
+}
+// per phase, average / maximum over the workgroups [r0, r1), in us since t0
+inline void dump_stamps(const char *title, const std::vector<unsigned long long> &h, unsigned long long t0, int r0, int r1,
+                        const char *const *nm, int cnt) {
+  std::fprintf(stderr, "[kc stamps] %s, us since the first workgroup (avg / max over workgroups):\n", title);
+  for (int k = 0; k < cnt; ++k) {
+    double sm = 0, mx = 0; int m = 0;
+    for (int r = r0; r < r1; ++r) {
+      if (!h[r * 16 + k]) continue;
+      const double us = (h[r * 16 + k] - t0) / 100.0;
+      sm += us; mx = std::max(mx, us); ++m;
+    }
+    if (m) std::fprintf(stderr, "  %-18s %6.2f / %6.2f\n", nm[k], sm / m, mx);
+  }
+}
+// option debug_stamps: `words` cleared stamp words of `buf` for the next launch -> *dbg
+inline int arm_stamps(kc_dwa *c, DevBuf<unsigned long long> &buf, size_t cap, size_t words, unsigned long long **dbg) {
+  if (!c->debug_stamps) return KC_OK;
+  KC_TRY(buf.reserve(cap));
+  KC_HIP(hipMemsetAsync(buf.p, 0, words * 8, c->stream));
+  *dbg = buf.p;
+  return KC_OK;
+}
+#endif
+
+// the cos / sin table of the yaw chains yaw0 + k * omega[r] * dt as a job of at most `nblk_max` workgroups of `block` threads
+inline TrigJob make_trig_job(double yaw0, double dt, const double *omega, const double *tab, double2 *out, size_t A, size_t P,
+                             size_t nblk_max, unsigned block) {
+  TrigJob j{};
+  j.yaw0 = yaw0;
+  j.dt = dt;
+  j.omega = omega;
+  j.tab = tab;
+  j.out = out;
+  j.A = static_cast<int>(A);
+  j.P = static_cast<int>(P);
+  j.nblk = static_cast<int>(std::min<size_t>(nblk_max, blocks_for(A * P, block)));
+  return j;
+}
+
 // ---- host functions shared between the translation units (kc_dwa.hip: context, options, lattice and shares;
 // kc_dwa_sensor.hip: sensor data, tracked segment, near tables; kc_dwa_cycle.hip: roll-out, costs, results;
 // kc_dwa_shard.hip: the exchange of a sharded cycle)
@@ -485,7 +531,7 @@ int window_geometry(kc_dwa *c, double wx, double wy, double reach, CollDev &cd);
 int window_bits_host(kc_dwa *c, CollDev &cd);
 int build_window_at(kc_dwa *c, double wx, double wy, double reach, CollDev &cd);
 int tilt_params(kc_dwa *c, TiltDev &t);  // the tilted-octree tests' parameters of the last kc_dwa_set_scan
-int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bool trig_ready = false);
+int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle);
 int materialise_paths(kc_dwa *c);
 void cycle_kernel_limits(kc_dwa *c);   // dynamic-LDS limits of the roll-out / cost kernels -> lds_limit, cost_lds_ok, cost_batch_ok
 int launch_init_result(kc_dwa *c);                       // init_result_kernel on the context's stream

@@ -217,34 +217,19 @@ int build_cost_args(kc_dwa *c, size_t n, size_t first, CostArgs &ca, DcArgs &dt)
   return KC_OK;
 }
 
-int run_evaluate(kc_dwa *c, size_t n, size_t first) {
-  const size_t P = c->P;
-  hipStream_t s = c->stream;
-  c->row_valid = false;
-  c->slots_pending = false;
-  c->device_record_valid = true;
-  if (n == 0) {  // empty batch: publish "nothing found"
-    hipLaunchKernelGGL(init_result_kernel, dim3(1), dim3(1), 0, s,
-                       c->d_result.p);
-    c->pub_pending = false;
-    return KC_OK;
-  }
-  if (n > 1024u * kCompactMaxPer)
-    KC_FAIL(KC_ERR_RANGE, "more than %d samples per context", 1024 * kCompactMaxPer);
-  // Short admissible lists (the count of the previous cycle is the predictor)
-  // go to the workgroup-per-sample kernel, long ones to the wavefront-per-
-  // sample kernel; both are correct for any list.
-  if (c->h_pub.p && c->seq > 0) {
-    // callers that never fetch (multi-GPU: the key is all-reduced on the
-    // device) still leave the previous cycle's record in the pinned mirror
-    volatile long long *hp = c->h_pub.p;
-    const long long w0 = hp[0], w1 = hp[1], w2 = hp[2], w3 = hp[3], w4 = hp[4];
-    if (w2 == c->seq && w3 == record_check(w0, w1, w2, w4)) c->last_nadm = w1 >> 32;
-  }
-  bool use_block = c->last_nadm >= 0 && c->last_nadm <= kBlockKernelMaxAdm;
-  if (c->cost_kernel_force == 1) use_block = true;
-  if (c->cost_kernel_force == 2) use_block = false;
-  // the wavefront-per-sample search of a roll-out's samples goes through the near table
+// ---- the cost stage: predictor -> near tables -> arguments -> plan (kc_launch_plan.h) -> launches -> record state ----
+
+// the admissible count of the previous cycle, the predictor of the kernel choice: callers that never fetch (multi-GPU:
+// the key is all-reduced on the device) still leave the previous cycle's record in the pinned mirror
+static void predict_nadm(kc_dwa *c) {
+  if (!c->h_pub.p || c->seq <= 0) return;
+  volatile long long *hp = c->h_pub.p;
+  const long long w0 = hp[0], w1 = hp[1], w2 = hp[2], w3 = hp[3], w4 = hp[4];
+  if (w2 == c->seq && w3 == record_check(w0, w1, w2, w4)) c->last_nadm = w1 >> 32;
+}
+
+// the wavefront-per-sample search of a roll-out's samples goes through the near table
+static int eval_near_tables(kc_dwa *c, bool use_block) {
   c->near_ok = false;
   c->near_wanted = !use_block && !c->external;
   c->onear_ok = false;
@@ -255,107 +240,164 @@ int run_evaluate(kc_dwa *c, size_t n, size_t first) {
   // caller-provided samples: the box found when they were uploaded
   if (!use_block && c->external && c->ext_box_valid)
     KC_TRY(ensure_near_table_box(c, c->ext_box[0], c->ext_box[1], c->ext_box[2], c->ext_box[3], 0.0));
+  return KC_OK;
+}
+
+static CostFacts cost_facts(const kc_dwa *c, size_t n, size_t first, bool use_block, const CostArgs &ca, const DcArgs &dt) {
+  return CostFacts{n, c->P, c->S, c->num_cus, c->last_nadm, use_block,
+                   c->external, c->timing.enabled, ca.use_seg != 0, ca.use_obs != 0,
+                   ca.have_vel != 0, n == c->n_roll && first == 0, (ca.w_smooth > 0.0 ? 1 : 0) + (ca.w_jerk > 0.0 ? 1 : 0),
+                   ca.b.W, ca.b.H, ca.b.nobs,
+                   static_cast<size_t>(seg_pairs_padded(ca.nch, ca.seg_chunk)), static_cast<size_t>(ca.nch), static_cast<size_t>(ca.nsup),
+                   dt.onear ? static_cast<size_t>(scan_block_floats(dt.on, dt.oscs)) : 0, batch_buf_bytes(static_cast<int>(c->P)),
+                   c->velocity_group, c->velocity_beside, c->fold_publish, c->cost_batch, c->cost_batch_forced,
+                   c->cost_batch_ok, c->cost_lds_ok, c->cost_obs_lds};
+}
+
+// the velocity sums as a pass of their own (CostPlan::group > 1): its launch, and what finishes the costs behind it
+struct VelPass {
+  VelSumArgs va;
+  VelFinishArgs vf;
+  dim3 grid;
+  hipStream_t stream;
+  int group;
+};
+static int launch_velocity_sums(kc_dwa *c, const VelPass &v) {
+  KC_TRY(c->timing.start("velocity_sums_kernel", v.stream));
+  if (v.group == 4)
+    hipLaunchKernelGGL(velocity_sums_kernel<16>, v.grid, dim3(kVelBlock), 0, v.stream, v.va);
+  else
+    hipLaunchKernelGGL(velocity_sums_kernel<4>, v.grid, dim3(kVelBlock), 0, v.stream, v.va);
+  return c->timing.stop(v.stream);
+}
+// In front of the cost kernel on its stream, or -- p.vel_beside -- forked to a second stream, where the pass is queued
+// BEHIND the cost kernel (finish_velocity_beside)
+static int prepare_velocity_sums(kc_dwa *c, const CostPlan &p, size_t n, CostArgs &ca, VelPass &v) {
+  hipStream_t s = c->stream;
+  KC_TRY(c->d_vsum.reserve(2 * n));
+  VelSumArgs &va = v.va;
+  va.vx = c->d_vvx.p;
+  va.vy = c->d_vvy.p;
+  va.om = c->d_vom.p;
+  va.n = static_cast<int>(n);
+  va.nv = static_cast<int>(c->P - 1);
+  va.acc0 = ca.acc0;
+  va.acc1 = ca.acc1;
+  va.acc2 = ca.acc2;
+  va.out[0] = c->d_vsum.p;
+  va.out[1] = c->d_vsum.p + n;
+  va.first_kind = ca.w_smooth > 0.0 ? 0 : 1;
+  const int kinds = (ca.w_smooth > 0.0 ? 1 : 0) + (ca.w_jerk > 0.0 ? 1 : 0);
+  v.group = p.group;
+  v.grid = dim3(blocks_for(n, (kVelBlock / 64) * static_cast<unsigned>(p.group)), kinds);
+  v.stream = s;
+  if (!p.vel_beside) {
+    KC_TRY(launch_velocity_sums(c, v));
+    if (ca.w_smooth > 0.0) ca.vsum_smooth = va.out[0];
+    if (ca.w_jerk > 0.0) ca.vsum_jerk = va.out[1];
+    return KC_OK;
+  }
+  if (!c->aux_stream) {
+    KC_HIP(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
+    KC_HIP(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
+    KC_HIP(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
+  }
+  v.stream = c->aux_stream;
+  KC_HIP(hipEventRecord(c->aux_fork, s));  // behind everything queued so far (the last reader of d_vsum too)
+  KC_HIP(hipStreamWaitEvent(v.stream, c->aux_fork, 0));
+  ca.defer_vel = 1;
+  VelFinishArgs &vf = v.vf;
+  vf.adm_list = ca.adm_list;
+  vf.adm_count = ca.adm_count;
+  vf.costs = ca.costs;
+  vf.vsum_smooth = ca.w_smooth > 0.0 ? va.out[0] : nullptr;
+  vf.vsum_jerk = ca.w_jerk > 0.0 ? va.out[1] : nullptr;
+  vf.w_smooth = ca.w_smooth;
+  vf.w_jerk = ca.w_jerk;
+  vf.div = static_cast<float>(3L * static_cast<long>(c->P - 1));
+  vf.first = ca.first;
+  return KC_OK;
+}
+// queued BEHIND the cost kernel: its one-per-CU workgroups take their registers first, the chains' small
+// workgroups fill what is left (the other way round the cost kernel waits for CUs the chains have filled).
+// Returns the workgroups of the kernel that finishes the costs (their keys are what publish_kernel reduces).
+static int finish_velocity_beside(kc_dwa *c, size_t n, VelPass &v, unsigned *blocks) {
+  KC_TRY(launch_velocity_sums(c, v));
+  KC_HIP(hipEventRecord(c->aux_join, c->aux_stream));
+  KC_HIP(hipStreamWaitEvent(c->stream, c->aux_join, 0));
+  *blocks = std::min(512u, blocks_for(n, 256));
+  v.vf.block_keys = c->d_block_keys.p;
+  hipLaunchKernelGGL(velocity_finish_kernel, dim3(*blocks), dim3(256), 0, c->stream, v.vf);
+  return KC_OK;
+}
+
+// sample_cost_block_kernel<tables in LDS, obstacles in LDS> / sample_cost_kernel<.., .., folded publish> /
+// sample_cost_batched_kernel<obstacles in LDS> of a plan
+static auto block_cost_kernel(const CostPlan &p) -> void (*)(CostArgs) {
+  if (p.obs_lds) return sample_cost_block_kernel<true, true>;
+  if (p.tab_lds) return sample_cost_block_kernel<true, false>;
+  return sample_cost_block_kernel<false, false>;
+}
+static auto wave_cost_kernel(const CostPlan &p) -> void (*)(CostArgs, DcArgs, PubArgs) {
+  if (p.batched && p.obs_lds) return sample_cost_batched_kernel<true>;
+  if (p.batched) return sample_cost_batched_kernel<false>;
+  if (p.fold && p.obs_lds) return sample_cost_kernel<true, true, true>;
+  if (p.fold && p.tab_lds) return sample_cost_kernel<true, false, true>;
+  if (p.fold) return sample_cost_kernel<false, false, true>;
+  if (p.obs_lds) return sample_cost_kernel<true, true, false>;
+  if (p.tab_lds) return sample_cost_kernel<true, false, false>;
+  return sample_cost_kernel<false, false, false>;
+}
+static int launch_cost(kc_dwa *c, const CostPlan &p, const CostArgs &ca, const DcArgs &dt, const PubArgs &pa) {
+  hipStream_t s = c->stream;
+  if (p.use_block) {
+    KC_TRY(c->timing.start("sample_cost_block_kernel", s));
+    hipLaunchKernelGGL(block_cost_kernel(p), dim3(p.grid), dim3(kBlkCostBlock), p.lds, s, ca);
+  } else {
+    if (c->debug_stamps && c->seq <= 2)
+      std::fprintf(stderr, "[kc] cost kernel: tables=%zu obstacles=%zu nobs=%d grid=%dx%d S=%zu chunk=%d tab_lds=%d obs_lds=%d\n",
+                   p.tab_bytes, p.obs_bytes, ca.b.nobs, ca.b.W, ca.b.H, c->S, ca.seg_chunk, int(p.tab_lds), int(p.obs_lds));
+    KC_TRY(c->timing.start(p.batched ? "sample_cost_batched_kernel" : "sample_cost_kernel", s));
+    hipLaunchKernelGGL(wave_cost_kernel(p), dim3(p.grid), dim3(kCostBlock), p.lds, s, ca, dt, pa);
+  }
+  return c->timing.stop(s);
+}
+
+int run_evaluate(kc_dwa *c, size_t n, size_t first) {
+  hipStream_t s = c->stream;
+  c->row_valid = false;
+  c->slots_pending = false;
+  c->device_record_valid = true;
+  if (n == 0) {  // empty batch: publish "nothing found"
+    hipLaunchKernelGGL(init_result_kernel, dim3(1), dim3(1), 0, s, c->d_result.p);
+    c->pub_pending = false;
+    return KC_OK;
+  }
+  if (n > 1024u * kCompactMaxPer) KC_FAIL(KC_ERR_RANGE, "more than %d samples per context", 1024 * kCompactMaxPer);
+  predict_nadm(c);
+  const bool use_block = cost_use_block(c->last_nadm, c->cost_kernel_force);
+  KC_TRY(eval_near_tables(c, use_block));
   CostArgs ca{};
   DcArgs dt{};
   KC_TRY(build_cost_args(c, n, first, ca, dt));
-  const size_t S = c->S;
-  bool vel_beside = false;
-  VelFinishArgs vf{};
-  std::function<int()> vel_launch;
-  if (ca.have_vel && (ca.w_smooth > 0.0 || ca.w_jerk > 0.0) && n == c->n_roll && first == 0) {
-    // ordered sums of the velocity profiles.  One sample per wavefront inside the cost kernel while the
-    // batch leaves a SIMD fewer than ~5 of these serial chains (latency bound either way); beyond, 4 samples
-    // per wavefront in a pass of their own (a quarter of the chain instructions), 16 for batches that still
-    // give every SIMD several chains then (tools/cost5k_terms.py)
-    const int kinds = (ca.w_smooth > 0.0 ? 1 : 0) + (ca.w_jerk > 0.0 ? 1 : 0);
-    const size_t simds = 4 * static_cast<size_t>(c->num_cus);
-    int group = c->velocity_group;
-    if (group == 0) group = kinds * n < 5 * simds ? 1 : (kinds * n < 96 * simds ? 4 : 16);
-    if (group > 1) {
-      KC_TRY(c->d_vsum.reserve(2 * n));
-      VelSumArgs va{};
-      va.vx = c->d_vvx.p;
-      va.vy = c->d_vvy.p;
-      va.om = c->d_vom.p;
-      va.n = static_cast<int>(n);
-      va.nv = static_cast<int>(P - 1);
-      va.acc0 = ca.acc0;
-      va.acc1 = ca.acc1;
-      va.acc2 = ca.acc2;
-      va.out[0] = c->d_vsum.p;
-      va.out[1] = c->d_vsum.p + n;
-      va.first_kind = ca.w_smooth > 0.0 ? 0 : 1;
-      const dim3 grid(blocks_for(n, (kVelBlock / 64) * static_cast<size_t>(group)), kinds);
-      // Beside the wavefront-per-sample cost kernel on a second stream: these chains leave most issue slots
-      // of their SIMDs idle, the segment searches fill them (not while kernels are being timed one by one)
-      vel_beside = !use_block && !c->timing.enabled && c->velocity_beside;
-      hipStream_t vs = s;
-      if (vel_beside) {
-        if (!c->aux_stream) {
-          KC_HIP(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-          KC_HIP(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-          KC_HIP(hipEventCreateWithFlags(&c->aux_join, hipEventDisableTiming));
-        }
-        vs = c->aux_stream;
-        KC_HIP(hipEventRecord(c->aux_fork, s));  // behind everything queued so far (the last reader of d_vsum too)
-        KC_HIP(hipStreamWaitEvent(vs, c->aux_fork, 0));
-      }
-      vel_launch = [=]() -> int {
-        KC_TRY(c->timing.start("velocity_sums_kernel", vs));
-        if (group == 4)
-          hipLaunchKernelGGL(velocity_sums_kernel<16>, grid, dim3(kVelBlock), 0, vs, va);
-        else
-          hipLaunchKernelGGL(velocity_sums_kernel<4>, grid, dim3(kVelBlock), 0, vs, va);
-        KC_TRY(c->timing.stop(vs));
-        return KC_OK;
-      };
-      if (!vel_beside) KC_TRY(vel_launch());  // in front of the cost kernel, same stream
-      if (vel_beside) {
-        ca.defer_vel = 1;
-        vf.adm_list = ca.adm_list;
-        vf.adm_count = ca.adm_count;
-        vf.costs = ca.costs;
-        vf.vsum_smooth = ca.w_smooth > 0.0 ? va.out[0] : nullptr;
-        vf.vsum_jerk = ca.w_jerk > 0.0 ? va.out[1] : nullptr;
-        vf.w_smooth = ca.w_smooth;
-        vf.w_jerk = ca.w_jerk;
-        vf.div = static_cast<float>(3L * static_cast<long>(P - 1));
-        vf.first = ca.first;
-      } else {
-        if (ca.w_smooth > 0.0) ca.vsum_smooth = va.out[0];
-        if (ca.w_jerk > 0.0) ca.vsum_jerk = va.out[1];
-      }
-    }
-  }
+  const CostPlan plan = plan_cost(cost_facts(c, n, first, use_block, ca, dt));
+  VelPass vel{};
+  if (plan.group > 1) KC_TRY(prepare_velocity_sums(c, plan, n, ca, vel));
   // caller-provided batches: every sample is admissible (kc_cost_upload), the list is the identity
   if (c->external && n == c->n_roll && first == 0) {
     ca.identity_n = static_cast<int>(n);
-    vf.identity_n = ca.identity_n;
+    vel.vf.identity_n = ca.identity_n;
   }
   if (c->need_compact && ca.identity_n == 0) {  // split roll-out path
     KC_TRY(c->timing.start("compact_kernel", s));
-    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, s, c->d_flags.p,
-                       static_cast<int>(n), c->d_adm.p, c->d_result.p + W_LIST);
+    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, s, c->d_flags.p, static_cast<int>(n), c->d_adm.p, c->d_result.p + W_LIST);
     KC_TRY(c->timing.stop(s));
   }
   KC_TRY(c->d_block_keys.reserve(512));
   ca.block_keys = c->d_block_keys.p;
 #ifdef KC_PHASE_STAMPS
-  if (c->debug_stamps) {
-    KC_TRY(c->d_dbg.reserve(512 * 16));
-    KC_HIP(hipMemsetAsync(c->d_dbg.p, 0, 512 * 16 * 8, s));
-    ca.dbg = c->d_dbg.p;
-  }
+  KC_TRY(arm_stamps(c, c->d_dbg, 512 * 16, 512 * 16, &ca.dbg));
 #endif
-  unsigned cost_blocks;
-  size_t lds_tab = 0, lds_obs = 0;
-  if (ca.use_obs) {
-    const size_t ncell = static_cast<size_t>(ca.b.W) * ca.b.H;
-    lds_tab += (ncell + 1) * sizeof(int) + ((ncell + 3) & ~size_t(3));
-    lds_obs = 2 * static_cast<size_t>(ca.b.nobs) * sizeof(float);
-    // (with a scan's near table the wavefront kernels keep the scan block there instead: x | y | chunk boxes)
-    if (dt.onear) lds_obs = std::max(lds_obs, static_cast<size_t>(scan_block_floats(dt.on, dt.oscs)) * sizeof(float));
-  }
   PubArgs pa{};
   pa.block_keys = c->d_block_keys.p;
   pa.flags = c->d_flags.p;
@@ -365,83 +407,14 @@ int run_evaluate(kc_dwa *c, size_t n, size_t first) {
   pa.host_pub = c->h_pub.p;
   pa.seq = ++c->seq;
   pa.identity_n = ca.identity_n;
-  // the long-list kernel publishes by itself (its last workgroup) unless the velocity sums finish behind it
-  pa.fold = (!use_block && !vel_beside && c->fold_publish) ? 1 : 0;
-  if (use_block) {
-    KC_TRY(c->timing.start("sample_cost_block_kernel", s));
-    cost_blocks = static_cast<unsigned>(std::min<size_t>(n, 512));
-    size_t lds = (P * 3 * sizeof(float) + 15) & ~size_t(15);
-    if (ca.use_seg) lds_tab += 5 * S * sizeof(float);
-    const bool tab_lds = c->cost_lds_ok && lds + lds_tab + 64 <= kBlkLdsBudget;
-    const bool obs_lds = tab_lds && ca.use_obs && lds + lds_tab + lds_obs + 64 <= kBlkLdsBudget;
-    if (obs_lds)
-      hipLaunchKernelGGL((sample_cost_block_kernel<true, true>), dim3(cost_blocks),
-                         dim3(kBlkCostBlock), lds + lds_tab + lds_obs, s, ca);
-    else if (tab_lds)
-      hipLaunchKernelGGL((sample_cost_block_kernel<true, false>), dim3(cost_blocks),
-                         dim3(kBlkCostBlock), lds + lds_tab, s, ca);
-    else
-      hipLaunchKernelGGL((sample_cost_block_kernel<false, false>), dim3(cost_blocks),
-                         dim3(kBlkCostBlock), lds, s, ca);
-  } else {
-    // one workgroup per CU, sixteen samples (wavefronts) in flight in each
-    cost_blocks = static_cast<unsigned>(std::min<size_t>(n, kCostGrid));
-    pa.nblocks = static_cast<int>(cost_blocks);
-    if (ca.use_seg)
-      lds_tab += (8 * static_cast<size_t>(seg_pairs_padded(ca.nch, ca.seg_chunk)) + 8 * static_cast<size_t>(ca.nch) +
-                  12 * static_cast<size_t>(ca.nsup)) * sizeof(float);  // pair records, capsules, spheres
-    // batched per-sample part (two buffers of 64 samples in front of the tables): the DWA cycle's lists, and
-    // caller-provided batches whose velocity sums are precomputed or not asked for
-    const size_t lds_batch = 2 * batch_buf_bytes(static_cast<int>(P));
-    const bool wave_sums = ca.have_vel && !ca.defer_vel &&
-                           ((ca.w_smooth > 0.0 && !ca.vsum_smooth) || (ca.w_jerk > 0.0 && !ca.vsum_jerk));
-    // ... and lists that fill more than one buffer per workgroup now and then (the last cycle's count is the
-    // predictor; measured: 141 samples per workgroup -14 % kernel time, 50: -3 %, 18: +4 %, 10: +6 %)
-    const long long expect = c->external ? static_cast<long long>(n) : (c->last_nadm >= 0 ? c->last_nadm : static_cast<long long>(n));
-    const bool batched = c->cost_batch && c->cost_batch_ok && c->cost_lds_ok && !wave_sums &&
-                         (c->cost_batch_forced || expect >= 40ll * kCostGrid) && lds_tab + lds_batch + 64 <= kCostLdsBudget;
-    if (batched) lds_tab += lds_batch;
-    const bool tab_lds = c->cost_lds_ok && lds_tab + 64 <= kCostLdsBudget;
-    const bool obs_lds = tab_lds && ca.use_obs && lds_tab + lds_obs + 64 <= kCostLdsBudget && c->cost_obs_lds;
-    if (c->debug_stamps && c->seq <= 2)
-      std::fprintf(stderr, "[kc] cost kernel: tables=%zu obstacles=%zu nobs=%d grid=%dx%d S=%zu chunk=%d tab_lds=%d obs_lds=%d\n",
-                   lds_tab, lds_obs, ca.b.nobs, ca.b.W, ca.b.H, S, ca.seg_chunk, int(tab_lds), int(obs_lds));
-    KC_TRY(c->timing.start(batched ? "sample_cost_batched_kernel" : "sample_cost_kernel", s));
-    if (batched && obs_lds)
-      hipLaunchKernelGGL((sample_cost_batched_kernel<true>), dim3(cost_blocks), dim3(kCostBlock),
-                         lds_tab + lds_obs, s, ca, dt, pa);
-    else if (batched)
-      hipLaunchKernelGGL((sample_cost_batched_kernel<false>), dim3(cost_blocks), dim3(kCostBlock),
-                         lds_tab, s, ca, dt, pa);
-    else {
-      auto launch = [&](auto kernel, size_t lds) {
-        hipLaunchKernelGGL(kernel, dim3(cost_blocks), dim3(kCostBlock), lds, s, ca, dt, pa);
-      };
-      if (pa.fold) {
-        if (obs_lds) launch(sample_cost_kernel<true, true, true>, lds_tab + lds_obs);
-        else if (tab_lds) launch(sample_cost_kernel<true, false, true>, lds_tab);
-        else launch(sample_cost_kernel<false, false, true>, 0);
-      } else {
-        if (obs_lds) launch(sample_cost_kernel<true, true, false>, lds_tab + lds_obs);
-        else if (tab_lds) launch(sample_cost_kernel<true, false, false>, lds_tab);
-        else launch(sample_cost_kernel<false, false, false>, 0);
-      }
-    }
-  }
-  KC_TRY(c->timing.stop(s));
-  if (vel_beside) {
-    // queued BEHIND the cost kernel: its one-per-CU workgroups take their registers first, the chains' small
-    // workgroups fill what is left (the other way round the cost kernel waits for CUs the chains have filled)
-    KC_TRY(vel_launch());
-    KC_HIP(hipEventRecord(c->aux_join, c->aux_stream));
-    KC_HIP(hipStreamWaitEvent(s, c->aux_join, 0));
-    cost_blocks = std::min(512u, blocks_for(n, 256));
-    vf.block_keys = c->d_block_keys.p;
-    hipLaunchKernelGGL(velocity_finish_kernel, dim3(cost_blocks), dim3(256), 0, s, vf);
-  }
+  pa.fold = plan.fold ? 1 : 0;
+  pa.nblocks = plan.use_block ? 0 : static_cast<int>(plan.grid);
+  KC_TRY(launch_cost(c, plan, ca, dt, pa));
+  unsigned key_blocks = plan.grid;
+  if (plan.vel_beside) KC_TRY(finish_velocity_beside(c, n, vel, &key_blocks));
   c->pub_pending = true;
   if (!pa.fold) {
-    pa.nblocks = static_cast<int>(cost_blocks);
+    pa.nblocks = static_cast<int>(key_blocks);
     KC_TRY(c->timing.start("publish_kernel", s));
     hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(kPubBlock), 0, s, pa);
     KC_TRY(c->timing.stop(s));
@@ -709,20 +682,17 @@ int tilt_params(kc_dwa *c, TiltDev &t) {
   return KC_OK;
 }
 
-// kc_dwa_rollout, or -- want_cycle -- the whole cycle in one launch when the
-// cost tables fit beside the roll-out tile (c->cycle_launched tells)
-int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bool trig_ready) {
+// ---- the roll-out: begin -> trig -> arguments -> plan (kc_launch_plan.h) -> launch -> record state ---------------
+
+// checks, the wait for the last cycle's staging buffers, the context's per-cycle state
+static int roll_begin(kc_dwa *c, const kc_state *start, size_t P) {
   if (!c || !start) KC_FAIL(KC_ERR_INVALID, "null argument");
-  if (P < 2 || P > c->prm.max_points)
-    KC_FAIL(KC_ERR_RANGE, "num_points %zu outside [2, %zu]", P,
-            c->prm.max_points);
+  if (P < 2 || P > c->prm.max_points) KC_FAIL(KC_ERR_RANGE, "num_points %zu outside [2, %zu]", P, c->prm.max_points);
   KC_TRY(use_device(c));
-  hipStream_t s = c->stream;
-  // The staging buffers of the last cycle must be free.  When the host has
-  // already seen the record the last cost kernel publishes at its very end,
-  // everything in front of it has completed and the (slow) stream wait is
-  // skipped; commands queued since then only read buffers this call leaves alone.
-  if (!c->drained || c->timing.enabled) KC_HIP(hipStreamSynchronize(s));
+  // The staging buffers of the last cycle must be free.  When the host has already seen the record the last cost kernel
+  // publishes at its very end, everything in front of it has completed and the (slow) stream wait is skipped; commands
+  // queued since then only read buffers this call leaves alone.
+  if (!c->drained || c->timing.enabled) KC_HIP(hipStreamSynchronize(c->stream));
   c->drained = false;
   if (!c->in_materialise) c->timing.begin_cycle();
   c->P = P;
@@ -734,23 +704,16 @@ int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bo
   c->slots_pending = false;
   c->paths_valid = true;
   c->last_start = *start;
-  const size_t n = c->shard_count;
-  c->n_roll = n;
-  if (n == 0) {
-    c->rolled = true;
-    return KC_OK;
-  }
-  // trig table: cos/sin of yaw_k for every omega row, from the host libm the
-  // reference calls (path.h:24-30); yaw_k by repeated addition of omega * dt
+  c->n_roll = c->shard_count;
+  return KC_OK;
+}
+
+// trig table: cos/sin of yaw_k for every omega row, from the host libm the reference calls (path.h:24-30); yaw_k by
+// repeated addition of omega * dt.  Where the table is written: straight into device memory when the host can address
+// it (large BAR: write-combined stores, no copy command and no copy engine latency on the critical path), else into
+// pinned memory followed by an H2D copy.
+static int host_trig_table(kc_dwa *c, double yaw0, double dt, size_t P) {
   const size_t A = c->lat.omega_values.size();
-  KC_TRY(c->h_trig.reserve(A * P));
-  KC_TRY(c->d_trig.reserve(A * P));
-  const double dt = static_cast<double>(static_cast<float>(c->prm.time_step));
-  // Where the table is written: straight into device memory when the host
-  // can address it (large BAR: write-combined stores, no copy command and no
-  // copy engine latency on the critical path), else into pinned memory
-  // followed by an H2D copy.
-  const double yaw0 = start->yaw;
   const double *om_v = c->lat.omega_values.data();
   double2 *tab = c->trig_direct ? c->d_trig.p : c->h_trig.p;
   auto trig_rows = [=](size_t r0, size_t r1) {
@@ -777,35 +740,43 @@ int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bo
     __builtin_ia32_sfence();  // write-combined stores leave the core before "done"
 #endif
   };
-  // Device trig (kc_trig_exact.h): the kernels form cos / sin(yaw_k) themselves -- no host table at all.  Only
-  // while every yaw_k stays inside the range the restated algorithm covers (|yaw| < 105414350; a bound on
-  // |yaw0| + P |omega| dt decides), and only when the restatement agreed with the installed libm when the
-  // library was loaded.  Otherwise -- the FALLBACK -- the host fills the table with its libm (the worker pool of
-  // kc_set_host_threads shares the rows), in front of the launch: no kernel ever waits for the host.
-  bool dev_trig = c->device_trig && trig_selfcheck_ok() && std::isfinite(yaw0);
-  if (dev_trig) {
+  WorkerPool::instance().parallel_for(A, 2, trig_rows);
+  c->timing.mark("host:trig_table");
+  if (!c->trig_direct)
+    KC_HIP(hipMemcpyAsync(c->d_trig.p, c->h_trig.p, A * P * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  return KC_OK;
+}
+
+struct TrigChoice {
+  bool dev;    // the kernels form cos / sin(yaw_k) themselves (kc_trig_exact.h): no host table at all
+  bool ahead;  // ... or the table is there already: formed inside the launch of the sensor update this cycle follows
+               // (plan_trig_job), for this yaw, this lattice and this horizon
+};
+// Device trig only while every yaw_k stays inside the range the restated algorithm covers (yaw_reach_ok), and only when
+// the restatement agreed with the installed libm when the library was loaded.  Otherwise -- the FALLBACK -- the host
+// fills the table with its libm (the worker pool of kc_set_host_threads shares the rows), in front of the launch: no
+// kernel ever waits for the host.
+static int roll_trig(kc_dwa *c, double yaw0, double dt, size_t P, TrigChoice &t) {
+  const size_t A = c->lat.omega_values.size();
+  KC_TRY(c->h_trig.reserve(A * P));
+  KC_TRY(c->d_trig.reserve(A * P));
+  t.dev = c->device_trig && trig_selfcheck_ok() && std::isfinite(yaw0);
+  if (t.dev) {
     double om_max = 0.0;
-    for (size_t i = 0; i < A; ++i) om_max = std::max(om_max, std::fabs(om_v[i]));
-    const double reach = std::fabs(yaw0) + om_max * dt * static_cast<double>(P);
-    dev_trig = std::isfinite(reach) && reach < 1.0e8;
+    for (double v : c->lat.omega_values) om_max = std::max(om_max, std::fabs(v));
+    t.dev = yaw_reach_ok(yaw0, om_max, dt, P);
   }
-  // ... or the table is there already: formed inside the launch of the sensor update this cycle follows
-  // (plan_trig_job), for this yaw, this lattice and this horizon
-  bool table_ahead = false;
-  if (dev_trig && c->trig_ahead_valid) {
-    table_ahead = P == c->trig_ahead_P && c->lat_version == c->trig_ahead_lat && c->d_trig.cap >= A * P &&
-                  std::memcmp(&yaw0, &c->trig_ahead_yaw, sizeof(double)) == 0;
-  }
-  if (!table_ahead) c->trig_ahead_valid = false;  // (d_trig is about to be rewritten, or belongs to another pose)
-  if (!dev_trig && !trig_ready) {
-    WorkerPool::instance().parallel_for(A, 2, trig_rows);
-    c->timing.mark("host:trig_table");
-    if (!c->trig_direct)
-      KC_HIP(hipMemcpyAsync(c->d_trig.p, c->h_trig.p, A * P * sizeof(double2), hipMemcpyHostToDevice, s));
-  }
-  trig_ready = true;
+  t.ahead = t.dev && c->trig_ahead_valid && P == c->trig_ahead_P && c->lat_version == c->trig_ahead_lat &&
+            c->d_trig.cap >= A * P && std::memcmp(&yaw0, &c->trig_ahead_yaw, sizeof(double)) == 0;
+  if (!t.ahead) c->trig_ahead_valid = false;  // (d_trig is about to be rewritten, or belongs to another pose)
+  if (!t.dev) KC_TRY(host_trig_table(c, yaw0, dt, P));
   c->hprof.mark(9);
-  RollArgs a{};
+  return KC_OK;
+}
+
+// the roll-out's arguments, its buffers, the collision window of everything within reach of the start
+static int fill_roll_args(kc_dwa *c, const kc_state *start, size_t P, double dt, const TrigChoice &t, RollArgs &a) {
+  const size_t n = c->n_roll, A = c->lat.omega_values.size();
   KC_TRY(ensure_cycle_buffers(c, n, P));
   a.n = static_cast<int>(n);
   a.first = static_cast<int>(c->shard_first);
@@ -821,10 +792,10 @@ int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bo
   a.vidx = c->d_vidx.p;
   a.row = c->d_row.p;
   a.trig = c->d_trig.p;
-  a.trig_dev = (dev_trig && !table_ahead) ? 1 : 0;
-  if (dev_trig) KC_TRY(ensure_sincostab(c));
+  a.trig_dev = (t.dev && !t.ahead) ? 1 : 0;
+  if (t.dev) KC_TRY(ensure_sincostab(c));
   a.sincostab = c->d_sincostab.p;
-  a.yaw0 = yaw0;
+  a.yaw0 = start->yaw;
   a.trig_out = c->d_trig.p;
   a.omega_values = c->d_omega.p;
   a.px = c->d_px.p;
@@ -848,234 +819,235 @@ int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle, bo
     a.acc2 = c->prm.acc_limits[2];
     c->freeze_valid = true;
   }
-  const bool may_collide = c->have_sensor && any_voxel(c);
-  KC_TRY(window_geometry(c, start->x, start->y, cycle_reach(c), a.c));
-  // single-launch cycle: cost arguments up front (their checks must not fail
-  // behind a launched kernel)
-  CycleTail tail{};
-  // One launch pays while every workgroup of the shard is resident at once (32 samples per
-  // workgroup, one workgroup per CU: 8192 samples on an MI355X -- the per-GPU share of every
-  // BASELINE config on 8 GPUs).  Beyond, the cycle kernel's LDS footprint (one workgroup per CU)
-  // loses to the three-kernel cycle, whose roll-out kernel fits two per CU (cfg5 on ONE GPU,
-  // 65536 samples: 0.214 against 0.129 ms).
-  // And a small shard with many survivors (cfg1: 128 samples in 4 workgroups, 104 admissible) is
-  // better served by the stand-alone cost kernels, which spread the survivors over all CUs; the
-  // admissible count of the previous cycle is the predictor (as for the choice of cost kernel).
-  // 32 samples per workgroup; 16 when that would leave half of the CUs without one (a 4096-sample
-  // shard -- cfg3 split over 8 GPUs -- or any mid-size lattice): twice the workgroups, half the poses
-  // and survivors in each.  (Option "cycle_samples": 0 = this rule, 16 / 32 = fixed.)
-  int cs = c->cycle_samples_opt;
-  if (cs == 0) cs = 2 * blocks_for(n, 32) <= static_cast<unsigned>(c->num_cus) ? 16 : 32;
-  // the last arriver of the ticket epilogue holds two workgroup keys per lane (kc_cycle_dev.h): at most
-  // 2048 workgroups, whatever the option says (65536 samples in 16-sample workgroups would be 4096)
-  if (blocks_for(n, static_cast<unsigned>(cs)) > 2048u) cs = 32;
-  c->cycle_samples = cs;
-  const unsigned cyc_G = blocks_for(n, static_cast<unsigned>(cs));
-  // (Rounds 2-3 sent small lattices with many survivors to the stand-alone cost kernels -- "they spread the survivors
-  // over all CUs".  Round 4's lattice sweep, 110 .. 2025 samples, half or all of them admissible: the single launch is
-  // 3 us ahead everywhere -- the second launch costs more than the spreading gains.  One resident round of workgroups is
-  // the only condition left.)
-  const bool cyc_wave = cyc_G <= static_cast<unsigned>(c->num_cus);
-  const bool sphere_ok = c->prm.shape != KC_SPHERE || (c->have_gbits && c->gz_valid);  // (fused path)
-  bool cycle = want_cycle && c->cycle_fused && sphere_ok && n <= 1024u * kCompactMaxPer &&
-               (c->cycle_forced || cyc_wave);
-  if (cycle) {
-    // workgroups with more than a handful of survivors search wavefront-per-sample: through the
-    // near table when the last cycle had that many
-    c->near_ok = false;
-    c->near_wanted = c->last_nadm < 0 || c->last_nadm > 2ll * cyc_G;
-    c->onear_ok = false;
-    if (c->near_wanted) {
-      KC_TRY(ensure_near_table(c, start->x, start->y));
-      KC_TRY(ensure_onear(c, start->x, start->y));
-    } else {
-      // few survivors: the scan's near table only if it is there already (the teams' last wavefronts use it: a tiny room
-      // puts the whole scan into the union rectangle of a sample, 35 us for 44 survivors without the table)
-      KC_TRY(ensure_onear(c, start->x, start->y, false));
-    }
-    KC_TRY(build_cost_args(c, n, c->shard_first, tail.c, tail.t));
-  }
-  // fused path: trig rows + poses (64 x P double2) and the window bits in LDS
-  // Roll-out tile of the three-kernel cycle: 32 samples per workgroup; 1024 threads, or 512 for a large
-  // lattice of short trajectories (cfg5, 65536 x 50: more workgroups resident per CU hide the serial
-  // recurrence of each other, 80 -> 45 us; P = 100 or one resident round: 1024 is better, tools/fused_cfg_sweep.sh)
-  int plain_fb = c->fused_block;
-  if (!c->fused_shape_fixed && P <= 64 && blocks_for(n, 32) > 4u * static_cast<unsigned>(c->num_cus)) plain_fb = 512;
-  const int fs = cycle ? cs : c->fused_samples, fb = cycle ? 1024 : plain_fb;
-  const size_t pos_bytes = static_cast<size_t>(fs) * (P | 1) * sizeof(double2);
-  size_t bits_bytes =
-      (a.c.enabled ? static_cast<size_t>(a.c.H) * a.c.wpr * 4 * (a.c.dil ? 3 : 1) : 0) +
-      static_cast<size_t>(fs) * P * sizeof(int);  // + queue of undecided poses
-  const bool fused = sphere_ok && !c->tilted && (!a.c.enabled || c->have_gbits) &&
-                     pos_bytes + bits_bytes + 512 <= c->lds_limit;
-  const size_t tab_off = (pos_bytes + bits_bytes + 15) & ~size_t(15);
-  cycle = cycle && fused && tab_off + cycle_table_bytes(tail.c) + 2048 <= c->lds_limit;
-  if (want_cycle && !cycle && fused && (fs != c->fused_samples || fb != plain_fb))
-  {
-    // sized for the cycle shape: start over for the plain one (a host-built table stays valid: same pose, same rows)
-    return rollout_impl(c, start, P, false, true);
-  }
-  c->need_compact = !fused || cycle;
-  if (dev_trig && !fused && !table_ahead) {  // the split path's kernels read a table: filled on the device, in stream order
-    KC_TRY(c->timing.start("trig_table_kernel", s));
-    TrigJob tj{};
-    tj.yaw0 = yaw0;
-    tj.dt = dt;
-    tj.omega = c->d_omega.p;
-    tj.tab = c->d_sincostab.p;
-    tj.out = c->d_trig.p;
-    tj.A = static_cast<int>(A);
-    tj.P = static_cast<int>(P);
-    tj.nblk = static_cast<int>(std::min<size_t>(1024, blocks_for(A * P, kTrigBlock)));
-    hipLaunchKernelGGL(trig_table_kernel, dim3(tj.nblk), dim3(kTrigBlock), 0, s, tj);
-    KC_TRY(c->timing.stop(s));
-  }
-  if (fused) {
-    if (!c->perm_valid || c->perm_first != c->shard_first || c->perm_count != c->shard_count || c->perm_cs != cs ||
-        !(cycle ? c->perm_dealt_dev : c->perm_plain_dev))
-      KC_TRY(build_perm(c, cycle));
-    a.perm = cycle ? c->d_cperm.p : c->d_perm.p;
-    a.prow = cycle ? c->d_cprow.p : c->d_prow.p;
-    a.pvi = cycle ? c->d_cpvi.p : c->d_pvi.p;
-    c->perm_busy = true;  // (until the host has seen this cycle's record)
-#ifdef KC_PHASE_STAMPS
-    if (c->debug_stamps) {
-      KC_TRY(c->d_dbg2.reserve(512 * 32));
-      KC_HIP(hipMemsetAsync(c->d_dbg2.p, 0, 512 * 32 * 8, s));
-      a.dbg = c->d_dbg2.p;
-    }
-#endif
-    if (c->list_dirty)  // previous roll-out was never evaluated: re-arm the list (and the error word a
-                        // failed cycle may have left)
-      KC_HIP(hipMemsetAsync(c->d_result.p + W_NADM, 0, 3 * sizeof(long long), s));
-    c->list_dirty = !cycle;
-    a.c.lds = 1;
-    if (cycle) {
-      const unsigned G = blocks_for(n, fs);
-      KC_TRY(c->d_block_keys.reserve(std::max<size_t>(512, 2 * static_cast<size_t>(G))));
-      {
-        const size_t words = n / 32 + 2;
-        const uint32_t *before = c->d_adm_bits.p;
-        KC_TRY(c->d_adm_bits.reserve(words));
-        if (c->d_adm_bits.p != before)  // a fresh bitmap starts clear; the last workgroup keeps it so
-          KC_HIP(hipMemsetAsync(c->d_adm_bits.p, 0, c->d_adm_bits.cap * sizeof(uint32_t), s));
-      }
-      KC_TRY(c->h_wrow.reserve(static_cast<size_t>(G) * 2 * P));
-      tail.tab_off = static_cast<unsigned>(tab_off);
-      tail.write_paths = c->write_paths ? 1 : 0;
-      tail.team_max = c->team_max;
-      tail.block_keys = c->d_block_keys.p;
-      tail.adm_bits = c->d_adm_bits.p;
-      tail.result = c->d_result.p;
-      tail.host_pub = c->sharded_call ? nullptr : c->h_pub.p;
-      tail.host_rows = c->sharded_call ? nullptr : c->h_wrow.p;
-      tail.host_slots = nullptr;
-      if (!c->sharded_call && c->host_reduce) {
-        KC_TRY(c->h_slots.reserve(4 * static_cast<size_t>(G)));
-        tail.host_slots = c->h_slots.p;
-        tail.host_pub = nullptr;
-      }
-      tail.seq = ++c->seq;
-      tail.c.block_keys = c->d_block_keys.p;
-      // sharded call: the last workgroup also writes this rank's words of the exchange record (no pack launch)
-      // (cycle_epilogue holds kMaxWords x kBlock = 2048 32-bit words of the bitmap in registers: a wider region --
-      // a share beyond 65536 samples -- is packed by xchg_pack_kernel behind the cycle instead)
-      tail.xs = (c->sharded_call && 2 * static_cast<size_t>(c->xchg_rw) <= 2048) ? c->xchg_send : nullptr;
-      tail.xgid = c->rows_active ? c->d_gid.p : nullptr;
-      tail.xrank = c->xchg_rank;
-      tail.xrw = c->xchg_rw;
-      c->xchg_packed = tail.xs != nullptr;
-      a.dev_err = c->d_result.p + W_NADM;
-    }
-    c->hprof.mark(1);
-    KC_TRY(c->timing.start(cycle ? "cycle_kernel" : "rollout_collide_kernel", s));
-    const dim3 grid(blocks_for(n, fs)), block(fb);
-    const size_t smem = pos_bytes + bits_bytes;
-    const NoTail nt{};
-    if (cycle && cs == 16)
-      hipLaunchKernelGGL((rollout_collide_kernel<16, 1024, CycleTail>), grid, block,
-                         tab_off + cycle_table_bytes(tail.c), s, a, tail);
-    else if (cycle)
-      hipLaunchKernelGGL((rollout_collide_kernel<32, 1024, CycleTail>), grid, block,
-                         tab_off + cycle_table_bytes(tail.c), s, a, tail);
-    else if (fs == 16 && fb == 256) hipLaunchKernelGGL((rollout_collide_kernel<16, 256>), grid, block, smem, s, a, nt);
-    else if (fs == 16 && fb == 512) hipLaunchKernelGGL((rollout_collide_kernel<16, 512>), grid, block, smem, s, a, nt);
-    else if (fs == 32 && fb == 1024) hipLaunchKernelGGL((rollout_collide_kernel<32, 1024>), grid, block, smem, s, a, nt);
-    else if (fs == 64 && fb == 1024) hipLaunchKernelGGL((rollout_collide_kernel<64, 1024>), grid, block, smem, s, a, nt);
-    else hipLaunchKernelGGL((rollout_collide_kernel<32, 512>), grid, block, smem, s, a, nt);
-    KC_TRY(c->timing.stop(s));
-    if (cycle) {
-      c->cycle_launched = true;
-      c->paths_valid = c->write_paths;
-      c->slots_pending = tail.host_slots != nullptr;
-      c->slots_G = grid.x;
-      c->pub_pending = !c->slots_pending;
-      c->device_record_valid = !c->slots_pending;
-      c->row_valid = false;
-    }
-    c->timing.mark("host:launch_rollout");
-    c->hprof.mark(2);
+  return window_geometry(c, start->x, start->y, cycle_reach(c), a.c);
+}
+
+static RollFacts roll_facts(const kc_dwa *c, size_t P, bool want_cycle, const CollDev &win) {
+  return RollFacts{c->n_roll, P, c->lds_limit, c->num_cus, want_cycle,
+                   c->prm.shape == KC_SPHERE, c->tilted, c->have_gbits, c->gz_valid,
+                   win.enabled != 0, win.H, win.wpr, win.dil,
+                   c->cycle_samples_opt, c->fused_samples, c->fused_block,
+                   c->cycle_fused, c->cycle_forced, c->fused_shape_fixed};
+}
+
+// The cost arguments of a single-launch cycle, up front: their checks must not fail behind a launched kernel.
+// Workgroups with more than a handful of survivors search wavefront-per-sample: through the near table when the last
+// cycle had that many.
+static int cycle_cost_args(kc_dwa *c, const kc_state *start, unsigned cyc_G, CycleTail &tail) {
+  c->near_ok = false;
+  c->near_wanted = c->last_nadm < 0 || c->last_nadm > 2ll * cyc_G;
+  c->onear_ok = false;
+  if (c->near_wanted) {
+    KC_TRY(ensure_near_table(c, start->x, start->y));
+    KC_TRY(ensure_onear(c, start->x, start->y));
   } else {
-    // split path (sphere, very long horizons, windows beyond LDS): roll-out
-    // first, window bits built on the host while it runs, then the pose-
-    // parallel collision pass
-    CollDev geom = a.c;
-    if (may_collide) {
-      KC_TRY(c->d_pos.reserve(n * P));
-      a.pos = c->d_pos.p;
-    }
-    a.c.enabled = may_collide ? 1 : 0;  // roll-out: "store the double poses"
-    if (a.freeze) {
-      KC_TRY(c->d_first_hit.reserve(n));
-      a.first_hit = c->d_first_hit.p;
-    }
-    const size_t tile_bytes = 2 * static_cast<size_t>(kRollBlock) * (P | 1) * 4;
-    a.stage = (tile_bytes <= 64 * 1024) ? 1 : 0;
-    KC_TRY(c->timing.start("rollout_kernel", s));
-    hipLaunchKernelGGL(rollout_kernel, dim3(blocks_for(n, kRollBlock)),
-                       dim3(kRollBlock), a.stage ? tile_bytes : 0, s, a);
-    KC_TRY(c->timing.stop(s));
-    c->timing.mark("host:launch_rollout");
-    if (may_collide && c->tilted) {
-      // tilted octree frame: every pose against the voxel columns within its reach, exact 3-D tests
-      TiltArgs ta{};
-      KC_TRY(tilt_params(c, ta.c));
-      if (c->tilt_cropped) {
-        // the cropped window (upload_voxels) must hold every column a pose of this roll-out can touch: the start's
-        // distance from the update's pose + the horizon's reach + the robot's bounding radius, in columns
-        const double far = std::hypot(start->x - c->tilt_body_x, start->y - c->tilt_body_y) + cycle_reach(c) + ta.c.rho;
-        if (!(far * c->inv_res + 4.0 < static_cast<double>(kTiltCrop)))
-          KC_FAIL(KC_ERR_UNSUPPORTED, "tilted sensor frame: the roll-out reaches %.0f voxel columns from the pose of the scan, "
-                                      "beyond the %d kept of a scan that spans more than 8192", far * c->inv_res, kTiltCrop);
-      }
-      ta.pos = c->d_pos.p;
-      ta.trig = c->d_trig.p;
-      ta.row = c->d_row.p;
-      ta.n = static_cast<int>(n);
-      ta.first = static_cast<int>(c->shard_first);
-      ta.P = static_cast<int>(P);
-      ta.A = static_cast<int>(A);
-      ta.flags = c->d_flags.p;
-      ta.first_hit = a.first_hit;
-      KC_TRY(c->timing.start("collision_tilted_kernel", s));
-      hipLaunchKernelGGL(collision_tilted_kernel, dim3(blocks_for(n * (P - 1), 256)), dim3(256), 0, s, ta);
-      KC_TRY(c->timing.stop(s));
-    } else if (may_collide) {
-      a.c = geom;
-      KC_TRY(window_bits_host(c, a.c));
-      c->timing.mark("host:window_bits");
-      if (a.c.enabled) {
-        const size_t bb = static_cast<size_t>(a.c.H) * a.c.wpr * 4;
-        KC_TRY(c->timing.start("collision_kernel", s));
-        hipLaunchKernelGGL(collision_kernel,
-                           dim3(blocks_for(n * (P - 1), kCollBlock)),
-                           dim3(kCollBlock), a.c.lds ? bb : 0, s, a);
-        KC_TRY(c->timing.stop(s));
-      }
-    }
-    if (a.freeze)  // (no collision pass: first_hit stays INT_MAX everywhere, nothing is frozen)
-      hipLaunchKernelGGL(freeze_fixup_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, a);
+    // few survivors: the scan's near table only if it is there already (the teams' last wavefronts use it: a tiny room
+    // puts the whole scan into the union rectangle of a sample, 35 us for 44 survivors without the table)
+    KC_TRY(ensure_onear(c, start->x, start->y, false));
   }
+  return build_cost_args(c, c->n_roll, c->shard_first, tail.c, tail.t);
+}
+
+// buffers and the rest of the tail of a single-launch cycle of G workgroups
+static int fill_cycle_tail(kc_dwa *c, const RollPlan &p, RollArgs &a, CycleTail &tail) {
+  const size_t n = c->n_roll, G = p.grid;
+  KC_TRY(c->d_block_keys.reserve(std::max<size_t>(512, 2 * G)));
+  {
+    const size_t words = n / 32 + 2;
+    const uint32_t *before = c->d_adm_bits.p;
+    KC_TRY(c->d_adm_bits.reserve(words));
+    if (c->d_adm_bits.p != before)  // a fresh bitmap starts clear; the last workgroup keeps it so
+      KC_HIP(hipMemsetAsync(c->d_adm_bits.p, 0, c->d_adm_bits.cap * sizeof(uint32_t), c->stream));
+  }
+  KC_TRY(c->h_wrow.reserve(G * 2 * c->P));
+  tail.tab_off = static_cast<unsigned>(p.tab_off);
+  tail.write_paths = c->write_paths ? 1 : 0;
+  tail.team_max = c->team_max;
+  tail.block_keys = c->d_block_keys.p;
+  tail.adm_bits = c->d_adm_bits.p;
+  tail.result = c->d_result.p;
+  tail.host_pub = c->sharded_call ? nullptr : c->h_pub.p;
+  tail.host_rows = c->sharded_call ? nullptr : c->h_wrow.p;
+  tail.host_slots = nullptr;
+  if (!c->sharded_call && c->host_reduce) {
+    KC_TRY(c->h_slots.reserve(4 * G));
+    tail.host_slots = c->h_slots.p;
+    tail.host_pub = nullptr;
+  }
+  tail.seq = ++c->seq;
+  tail.c.block_keys = c->d_block_keys.p;
+  // sharded call: the last workgroup also writes this rank's words of the exchange record (no pack launch)
+  // (cycle_epilogue holds kMaxWords x kBlock = 2048 32-bit words of the bitmap in registers: a wider region --
+  // a share beyond 65536 samples -- is packed by xchg_pack_kernel behind the cycle instead)
+  tail.xs = (c->sharded_call && 2 * static_cast<size_t>(c->xchg_rw) <= 2048) ? c->xchg_send : nullptr;
+  tail.xgid = c->rows_active ? c->d_gid.p : nullptr;
+  tail.xrank = c->xchg_rank;
+  tail.xrw = c->xchg_rw;
+  c->xchg_packed = tail.xs != nullptr;
+  a.dev_err = c->d_result.p + W_NADM;
+  return KC_OK;
+}
+
+// rollout_collide_kernel<samples, threads[, CycleTail]> of a plan
+static auto cycle_kernel_of(int cs) -> void (*)(RollArgs, CycleTail) {
+  if (cs == 16) return rollout_collide_kernel<16, 1024, CycleTail>;
+  return rollout_collide_kernel<32, 1024, CycleTail>;
+}
+static auto plain_kernel_of(int fs, int fb) -> void (*)(RollArgs, NoTail) {
+  if (fs == 16 && fb == 256) return rollout_collide_kernel<16, 256>;
+  if (fs == 16 && fb == 512) return rollout_collide_kernel<16, 512>;
+  if (fs == 32 && fb == 1024) return rollout_collide_kernel<32, 1024>;
+  if (fs == 64 && fb == 1024) return rollout_collide_kernel<64, 1024>;
+  return rollout_collide_kernel<32, 512>;
+}
+
+// fused path: trig rows + poses and the window bits in LDS; with p.cycle the cost stage and the record as well
+static int launch_fused(kc_dwa *c, const RollPlan &p, size_t table_bytes, RollArgs &a, CycleTail &tail) {
+  hipStream_t s = c->stream;
+  const bool cycle = p.cycle;
+  if (!c->perm_valid || c->perm_first != c->shard_first || c->perm_count != c->shard_count || c->perm_cs != p.cs ||
+      !(cycle ? c->perm_dealt_dev : c->perm_plain_dev))
+    KC_TRY(build_perm(c, cycle));
+  a.perm = cycle ? c->d_cperm.p : c->d_perm.p;
+  a.prow = cycle ? c->d_cprow.p : c->d_prow.p;
+  a.pvi = cycle ? c->d_cpvi.p : c->d_pvi.p;
+  c->perm_busy = true;  // (until the host has seen this cycle's record)
+#ifdef KC_PHASE_STAMPS
+  KC_TRY(arm_stamps(c, c->d_dbg2, 512 * 32, 512 * 32, &a.dbg));
+#endif
+  if (c->list_dirty)  // previous roll-out was never evaluated: re-arm the list (and the error word a
+                      // failed cycle may have left)
+    KC_HIP(hipMemsetAsync(c->d_result.p + W_NADM, 0, 3 * sizeof(long long), s));
+  c->list_dirty = !cycle;
+  a.c.lds = 1;
+  if (cycle) KC_TRY(fill_cycle_tail(c, p, a, tail));
+  c->hprof.mark(1);
+  KC_TRY(c->timing.start(cycle ? "cycle_kernel" : "rollout_collide_kernel", s));
+  const dim3 grid(p.grid), block(p.fb);
+  if (cycle) hipLaunchKernelGGL(cycle_kernel_of(p.cs), grid, block, p.tab_off + table_bytes, s, a, tail);
+  else hipLaunchKernelGGL(plain_kernel_of(p.fs, p.fb), grid, block, p.pos_bytes + p.bits_bytes, s, a, NoTail{});
+  KC_TRY(c->timing.stop(s));
+  if (cycle) {
+    c->cycle_launched = true;
+    c->paths_valid = c->write_paths;
+    c->slots_pending = tail.host_slots != nullptr;
+    c->slots_G = grid.x;
+    c->pub_pending = !c->slots_pending;
+    c->device_record_valid = !c->slots_pending;
+    c->row_valid = false;
+  }
+  c->timing.mark("host:launch_rollout");
+  c->hprof.mark(2);
+  return KC_OK;
+}
+
+// tilted octree frame: every pose against the voxel columns within its reach, exact 3-D tests
+static int launch_tilted_collision(kc_dwa *c, const kc_state *start, const RollArgs &a) {
+  const size_t n = c->n_roll, P = c->P;
+  TiltArgs ta{};
+  KC_TRY(tilt_params(c, ta.c));
+  if (c->tilt_cropped) {
+    // the cropped window (upload_voxels) must hold every column a pose of this roll-out can touch: the start's
+    // distance from the update's pose + the horizon's reach + the robot's bounding radius, in columns
+    const double far = std::hypot(start->x - c->tilt_body_x, start->y - c->tilt_body_y) + cycle_reach(c) + ta.c.rho;
+    if (!(far * c->inv_res + 4.0 < static_cast<double>(kTiltCrop)))
+      KC_FAIL(KC_ERR_UNSUPPORTED, "tilted sensor frame: the roll-out reaches %.0f voxel columns from the pose of the scan, "
+                                  "beyond the %d kept of a scan that spans more than 8192", far * c->inv_res, kTiltCrop);
+  }
+  ta.pos = c->d_pos.p;
+  ta.trig = c->d_trig.p;
+  ta.row = c->d_row.p;
+  ta.n = static_cast<int>(n);
+  ta.first = static_cast<int>(c->shard_first);
+  ta.P = static_cast<int>(P);
+  ta.A = a.A;
+  ta.flags = c->d_flags.p;
+  ta.first_hit = a.first_hit;
+  KC_TRY(c->timing.start("collision_tilted_kernel", c->stream));
+  hipLaunchKernelGGL(collision_tilted_kernel, dim3(blocks_for(n * (P - 1), 256)), dim3(256), 0, c->stream, ta);
+  return c->timing.stop(c->stream);
+}
+
+// split path (sphere, very long horizons, windows beyond LDS): roll-out first, window bits built on the host while it
+// runs, then the pose-parallel collision pass
+static int launch_split(kc_dwa *c, const kc_state *start, RollArgs &a) {
+  hipStream_t s = c->stream;
+  const size_t n = c->n_roll, P = c->P;
+  const bool may_collide = c->have_sensor && any_voxel(c);
+  const CollDev geom = a.c;
+  if (may_collide) {
+    KC_TRY(c->d_pos.reserve(n * P));
+    a.pos = c->d_pos.p;
+  }
+  a.c.enabled = may_collide ? 1 : 0;  // roll-out: "store the double poses"
+  if (a.freeze) {
+    KC_TRY(c->d_first_hit.reserve(n));
+    a.first_hit = c->d_first_hit.p;
+  }
+  const size_t tile_bytes = 2 * static_cast<size_t>(kRollBlock) * (P | 1) * 4;
+  a.stage = (tile_bytes <= 64 * 1024) ? 1 : 0;
+  KC_TRY(c->timing.start("rollout_kernel", s));
+  hipLaunchKernelGGL(rollout_kernel, dim3(blocks_for(n, kRollBlock)), dim3(kRollBlock), a.stage ? tile_bytes : 0, s, a);
+  KC_TRY(c->timing.stop(s));
+  c->timing.mark("host:launch_rollout");
+  if (may_collide && c->tilted) {
+    KC_TRY(launch_tilted_collision(c, start, a));
+  } else if (may_collide) {
+    a.c = geom;
+    KC_TRY(window_bits_host(c, a.c));
+    c->timing.mark("host:window_bits");
+    if (a.c.enabled) {
+      const size_t bb = static_cast<size_t>(a.c.H) * a.c.wpr * 4;
+      KC_TRY(c->timing.start("collision_kernel", s));
+      hipLaunchKernelGGL(collision_kernel, dim3(blocks_for(n * (P - 1), kCollBlock)), dim3(kCollBlock), a.c.lds ? bb : 0, s, a);
+      KC_TRY(c->timing.stop(s));
+    }
+  }
+  if (a.freeze)  // (no collision pass: first_hit stays INT_MAX everywhere, nothing is frozen)
+    hipLaunchKernelGGL(freeze_fixup_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, a);
+  return KC_OK;
+}
+
+// kc_dwa_rollout, or -- want_cycle -- the whole cycle in one launch when the
+// cost tables fit beside the roll-out tile (c->cycle_launched tells)
+int rollout_impl(kc_dwa *c, const kc_state *start, size_t P, bool want_cycle) {
+  KC_TRY(roll_begin(c, start, P));
+  if (c->n_roll == 0) {
+    c->rolled = true;
+    return KC_OK;
+  }
+  const double dt = static_cast<double>(static_cast<float>(c->prm.time_step));
+  TrigChoice trig{};
+  KC_TRY(roll_trig(c, start->yaw, dt, P, trig));
+  RollArgs a{};
+  KC_TRY(fill_roll_args(c, start, P, dt, trig, a));
+  const RollFacts facts = roll_facts(c, P, want_cycle, a.c);
+  RollPlan plan = plan_rollout(facts);
+  c->cycle_samples = plan.cs;
+  // A cycle that is a candidate gets its cost arguments (and near tables) now; when its tables then do not fit behind
+  // the tile, the roll-out takes the plain plan.  Nothing of the roll-out itself has been launched yet.
+  CycleTail tail{};
+  size_t table_bytes = 0;
+  if (plan.cycle) {
+    KC_TRY(cycle_cost_args(c, start, plan.cyc_G, tail));
+    table_bytes = cycle_table_bytes(tail.c);
+    if (!cycle_fits(facts, plan, table_bytes)) {
+      const RollPlan plain = without_cycle(facts, plan);
+      // (timings() reports the roll-out that ran: what the dropped cycle queued for itself -- a near table -- is not
+      // part of it when the tile changes shape)
+      if (plan.fused && (plain.fs != plan.fs || plain.fb != plan.fb) && !c->in_materialise) c->timing.begin_cycle();
+      plan = plain;
+    }
+  }
+  c->need_compact = !plan.fused || plan.cycle;
+  if (trig.dev && !plan.fused && !trig.ahead) {  // the split path's kernels read a table: filled on the device, in stream order
+    KC_TRY(c->timing.start("trig_table_kernel", c->stream));
+    KC_TRY(launch_trig_table(make_trig_job(start->yaw, dt, c->d_omega.p, c->d_sincostab.p, c->d_trig.p, a.A, P, 1024, kTrigBlock),
+                             c->stream));
+    KC_TRY(c->timing.stop(c->stream));
+  }
+  if (plan.fused) KC_TRY(launch_fused(c, plan, table_bytes, a, tail));
+  else KC_TRY(launch_split(c, start, a));
   KC_HIP(hipGetLastError());
   c->timing.mark("host:launch_collision");
   c->rolled = true;
@@ -1123,56 +1095,42 @@ int kc_dwa_check_poses(kc_dwa *c, const double *x, const double *y,
   double reach = 0.0;
   for (size_t i = 1; i < n; ++i)
     reach = std::max(reach, std::hypot(x[i] - x[0], y[i] - y[0]));
+  TiltDev td;
+  CollDev cd;
   if (c->tilted) {
     if (!c->have_sensor || c->vox_kx.empty()) {
       std::memset(hit_out, 0, n);
       return KC_OK;
     }
-    TiltDev td;
     KC_TRY(tilt_params(c, td));
-    if (c->tilt_cropped) {  // (see rollout_impl: every pose inside the kept window of the cropped scan)
+    if (c->tilt_cropped) {  // (see launch_tilted_collision: every pose inside the kept window of the cropped scan)
       double far = 0.0;
       for (size_t i = 0; i < n; ++i) far = std::max(far, std::hypot(x[i] - c->tilt_body_x, y[i] - c->tilt_body_y));
       if (!((far + td.rho) * c->inv_res + 4.0 < static_cast<double>(kTiltCrop)))
         KC_FAIL(KC_ERR_UNSUPPORTED, "tilted sensor frame: a pose lies %.0f voxel columns from the pose of the scan, beyond the "
                                     "%d kept of a scan that spans more than 8192", far * c->inv_res, kTiltCrop);
     }
-    KC_TRY(c->h_trig.reserve(2 * n));
-    KC_TRY(c->d_trig.reserve(2 * n));
-    for (size_t i = 0; i < n; ++i) {
-      c->h_trig.p[i] = make_double2(x[i], y[i]);
-      c->h_trig.p[n + i] = make_double2(std::cos(yaw[i]), std::sin(yaw[i]));
+  } else {
+    KC_TRY(build_window_at(c, x[0], y[0], reach * 1.0001 + 1e-9, cd));
+    if (!cd.enabled) {
+      std::memset(hit_out, 0, n);
+      return KC_OK;
     }
-    KC_HIP(hipMemcpyAsync(c->d_trig.p, c->h_trig.p, 2 * n * sizeof(double2), hipMemcpyHostToDevice, s));
-    KC_TRY(c->d_flags.reserve(n));
-    hipLaunchKernelGGL(pose_check_tilted_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, td, c->d_trig.p,
-                       c->d_trig.p + n, static_cast<int>(n), c->d_flags.p);
-    KC_HIP(hipGetLastError());
-    KC_HIP(hipMemcpyAsync(hit_out, c->d_flags.p, n, hipMemcpyDeviceToHost, s));
-    KC_HIP(hipStreamSynchronize(s));
-    c->rolled = false;
-    c->evaluated = false;
-    return KC_OK;
+    cd.lds = 0;
   }
-  CollDev cd;
-  KC_TRY(build_window_at(c, x[0], y[0], reach * 1.0001 + 1e-9, cd));
-  if (!cd.enabled) {
-    std::memset(hit_out, 0, n);
-    return KC_OK;
-  }
-  cd.lds = 0;
   KC_TRY(c->h_trig.reserve(2 * n));
   KC_TRY(c->d_trig.reserve(2 * n));
   for (size_t i = 0; i < n; ++i) {
     c->h_trig.p[i] = make_double2(x[i], y[i]);
     c->h_trig.p[n + i] = make_double2(std::cos(yaw[i]), std::sin(yaw[i]));
   }
-  KC_HIP(hipMemcpyAsync(c->d_trig.p, c->h_trig.p, 2 * n * sizeof(double2),
-                        hipMemcpyHostToDevice, s));
+  KC_HIP(hipMemcpyAsync(c->d_trig.p, c->h_trig.p, 2 * n * sizeof(double2), hipMemcpyHostToDevice, s));
   KC_TRY(c->d_flags.reserve(n));
-  hipLaunchKernelGGL(pose_check_kernel, dim3(blocks_for(n, 256)), dim3(256), 0,
-                     s, cd, c->d_trig.p, c->d_trig.p + n, static_cast<int>(n),
-                     c->d_flags.p);
+  const dim3 grid(blocks_for(n, 256));
+  if (c->tilted)
+    hipLaunchKernelGGL(pose_check_tilted_kernel, grid, dim3(256), 0, s, td, c->d_trig.p, c->d_trig.p + n, static_cast<int>(n), c->d_flags.p);
+  else
+    hipLaunchKernelGGL(pose_check_kernel, grid, dim3(256), 0, s, cd, c->d_trig.p, c->d_trig.p + n, static_cast<int>(n), c->d_flags.p);
   KC_HIP(hipGetLastError());
   KC_HIP(hipMemcpyAsync(hit_out, c->d_flags.p, n, hipMemcpyDeviceToHost, s));
   KC_HIP(hipStreamSynchronize(s));
@@ -1521,52 +1479,22 @@ int launch_trig_table(const TrigJob &tj, hipStream_t s) {
 }
 
 
-// opt in to more than 64 KB of dynamic LDS for the fused roll-out / cycle kernels and the cost kernels (gfx950: 160 KB)
+// opt in to more than 64 KB of dynamic LDS for the fused roll-out / cycle kernels and the cost kernels
 void cycle_kernel_limits(kc_dwa *c) {
-  {
-    bool ok = true;
-    auto optin = [&](const void *f) {
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-        (void)hipGetLastError();
-        ok = false;
-      }
-    };
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<32, 512>));
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<16, 256>));
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<16, 512>));
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<32, 1024>));
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<64, 1024>));
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<32, 1024, CycleTail>));
-    optin(reinterpret_cast<const void *>(rollout_collide_kernel<16, 1024, CycleTail>));
-    if (ok) c->lds_limit = 150 * 1024;
-    c->lds_limit_hw = c->lds_limit;
-    c->cost_lds_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_kernel<true, true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kCostLdsBudget)) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_kernel<true, false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kCostLdsBudget)) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_kernel<true, true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kCostLdsBudget)) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_kernel<true, false, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kCostLdsBudget)) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_block_kernel<true, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kBlkLdsBudget)) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_block_kernel<true, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kBlkLdsBudget)) == hipSuccess;
-    if (!c->cost_lds_ok) (void)hipGetLastError();
-    c->cost_lds_hw = c->cost_lds_ok;
-    c->cost_batch_ok =
-        c->cost_lds_ok &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_batched_kernel<true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kCostLdsBudget)) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(sample_cost_batched_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kCostLdsBudget)) == hipSuccess;
-    if (!c->cost_batch_ok) (void)hipGetLastError();
-  }
+  // (every instance is asked, whatever the ones before it answered)
+  bool ok = lds_optin(rollout_collide_kernel<32, 512>, 150 * 1024);
+  ok = lds_optin(rollout_collide_kernel<16, 256>, 150 * 1024) && ok;
+  ok = lds_optin(rollout_collide_kernel<16, 512>, 150 * 1024) && ok;
+  ok = lds_optin(rollout_collide_kernel<32, 1024>, 150 * 1024) && ok;
+  ok = lds_optin(rollout_collide_kernel<64, 1024>, 150 * 1024) && ok;
+  ok = lds_optin(rollout_collide_kernel<32, 1024, CycleTail>, 150 * 1024) && ok;
+  ok = lds_optin(rollout_collide_kernel<16, 1024, CycleTail>, 150 * 1024) && ok;
+  if (ok) c->lds_limit = 150 * 1024;
+  c->lds_limit_hw = c->lds_limit;
+  c->cost_lds_ok = lds_optin(sample_cost_kernel<true, true, true>, kCostLdsBudget) && lds_optin(sample_cost_kernel<true, false, true>, kCostLdsBudget) &&
+                   lds_optin(sample_cost_kernel<true, true, false>, kCostLdsBudget) && lds_optin(sample_cost_kernel<true, false, false>, kCostLdsBudget) &&
+                   lds_optin(sample_cost_block_kernel<true, true>, kBlkLdsBudget) && lds_optin(sample_cost_block_kernel<true, false>, kBlkLdsBudget);
+  c->cost_lds_hw = c->cost_lds_ok;
+  c->cost_batch_ok = c->cost_lds_ok && lds_optin(sample_cost_batched_kernel<true>, kCostLdsBudget) &&
+                     lds_optin(sample_cost_batched_kernel<false>, kCostLdsBudget);
 }

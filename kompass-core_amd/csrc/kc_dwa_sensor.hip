@@ -434,9 +434,7 @@ int ensure_host_lists(kc_dwa *c) {
 }
 
 // Sensor update on the device (kc_sensor_kernels.h): the host only bounds the
-// cloud (one min/max pass), derives the bitmap extent and the bucket grid from
-// the bounds, stores the raw points through the BAR and queues two kernels.
-// *done = false: conditions not met, the caller takes the host path.
+// cloud (one min/max pass, sensor_update_device) and hands the bounds on.
 int sensor_update_device_bounded(kc_dwa *c, const float *xyz, size_t n, const float lo[3],
                                  const float hi[3], bool *done, bool raw_copied = false);
 
@@ -493,92 +491,89 @@ __attribute__((target("avx512f"))) size_t bounds_copy_avx512(const float *src, f
 }
 #endif
 
+// whether the device takes the update at all: the option, a host-addressable device buffer, a list within
+// kSensorDeviceMax; a sphere has the one-launch build only
+static bool sensor_device_takes(const kc_dwa *c, size_t n) {
+  if (!c->device_sensor || !c->trig_direct || n == 0 || n > kSensorDeviceMax) return false;
+  return c->prm.shape != KC_SPHERE || !(c->sensor_two_launch || n > kSensorFusedMax || !c->sensor_fused_ok);
+}
+
+#if defined(__x86_64__)
+// The bounds + copy pass of sensor_update_device.  It sits on the critical path of a sensor update (nothing is launched
+// before the bounds are known): four points per step with SSE min / max (sixteen with AVX-512), and the same pass
+// stores the points to their device buffer through the BAR (write-combining stores): one trip over the list instead
+// of two.  *bounded: there is a finite value on every axis.
+// (Round 4: values that are not finite no longer send the list to a scalar loop -- a LaserScan with beams without a
+// return, a depth image with holes: 22 us at 4096 beams.  The bounds are those of the finite VALUES: a point with one
+// coordinate missing still widens the other two -- a looser box, which only sizes the tables; the kernels drop the
+// point as before.)
+static int bound_and_stage(kc_dwa *c, const float *xyz, size_t n, float lo[3], float hi[3], bool *bounded) {
+  KC_TRY(c->d_raw.reserve(3 * n + 16));
+  float *dst = c->d_raw.p;
+  typedef float v4 __attribute__((vector_size(16)));
+  typedef int v4i __attribute__((vector_size(16)));
+  const v4 big = {FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX}, zero = {0.f, 0.f, 0.f, 0.f};
+  v4 mn[3] = {big, big, big}, mx[3] = {-big, -big, -big};
+  const size_t total = 3 * n;
+  size_t i = 0;
+  if (total >= 96 && cpu_has_avx512f()) {
+    // 48 floats (16 points) per step as three 64-byte vectors: a write-combining store per cache line
+    float acc[2][3][4];
+    bool ok512 = true;
+    i = bounds_copy_avx512(xyz, dst, total, acc, &ok512);
+    for (int q = 0; q < 3; ++q) {
+      std::memcpy(&mn[q], acc[0][q], sizeof(v4));
+      std::memcpy(&mx[q], acc[1][q], sizeof(v4));
+    }
+  }
+  for (; i + 12 <= total; i += 12) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      v4 v;
+      std::memcpy(&v, xyz + i + 4 * q, sizeof(v));
+      __builtin_nontemporal_store(v, reinterpret_cast<v4 *>(dst + i + 4 * q));
+      const v4 dv = v - v;
+      const v4i fin = (dv == zero);  // (not finite: the element leaves the bounds alone)
+      mn[q] = __builtin_ia32_minps(mn[q], (v4)(((v4i)v & fin) | ((v4i)big & ~fin)));
+      mx[q] = __builtin_ia32_maxps(mx[q], (v4)(((v4i)v & fin) | ((v4i)(-big) & ~fin)));
+    }
+  }
+  // lanes: v0 = x0 y0 z0 x1 | v1 = y1 z1 x2 y2 | v2 = z2 x3 y3 z3
+  static const int vec_of[3][4] = {{0, 0, 1, 2}, {0, 1, 1, 2}, {0, 1, 2, 2}};
+  static const int lane_of[3][4] = {{0, 3, 2, 1}, {1, 0, 3, 2}, {2, 1, 0, 3}};
+  for (int a = 0; a < 3; ++a)
+    for (int q = 0; q < 4; ++q) {
+      lo[a] = std::min(lo[a], mn[vec_of[a][q]][lane_of[a][q]]);
+      hi[a] = std::max(hi[a], mx[vec_of[a][q]][lane_of[a][q]]);
+    }
+  for (; i < total; ++i) {  // fewer than four points
+    const float v = xyz[i];
+    dst[i] = v;
+    if (!std::isfinite(v)) continue;
+    lo[i % 3] = std::min(lo[i % 3], v);
+    hi[i % 3] = std::max(hi[i % 3], v);
+  }
+  *bounded = lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2];
+  for (int a = 0; a < 3 && !*bounded; ++a) {
+    lo[a] = FLT_MAX;
+    hi[a] = -FLT_MAX;
+  }
+  return KC_OK;
+}
+#endif
+
 int sensor_update_device(kc_dwa *c, const float *xyz, size_t n, bool *done) {
   *done = false;
   c->raw_on_device = false;
-  if (!c->device_sensor || !c->trig_direct || n == 0 || n > kSensorDeviceMax)
-    return KC_OK;
-  if (c->prm.shape == KC_SPHERE && (c->sensor_two_launch || n > kSensorFusedMax || !c->sensor_fused_ok)) return KC_OK;
+  if (!sensor_device_takes(c, n)) return KC_OK;
   float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  size_t nfin = 0;
   bool bounded = false, raw_copied = false;
 #if defined(__x86_64__)
-  // This pass sits on the critical path of a sensor update (nothing is launched
-  // before the bounds are known): four points per step with SSE min / max;
-  // any non-finite coordinate (v - v != 0) sends the whole list to the loop below.
-  // The same pass stores the points to their device buffer through the BAR
-  // (write-combining stores): one trip over the list instead of two.
-  KC_TRY(c->d_raw.reserve(3 * n + 16));
-  {
-    float *dst = c->d_raw.p;
-    typedef float v4 __attribute__((vector_size(16)));
-    typedef int v4i __attribute__((vector_size(16)));
-    const v4 big = {FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX}, zero = {0.f, 0.f, 0.f, 0.f};
-    v4 mn[3] = {big, big, big}, mx[3] = {-big, -big, -big};
-    v4i ok = {-1, -1, -1, -1};
-    const size_t total = 3 * n;
-    size_t i = 0;
-    if (total >= 96 && cpu_has_avx512f()) {
-      // 48 floats (16 points) per step as three 64-byte vectors: a write-combining store per cache line
-      float acc[2][3][4];
-      bool ok512 = true;
-      i = bounds_copy_avx512(xyz, dst, total, acc, &ok512);
-      for (int q = 0; q < 3; ++q) {
-        std::memcpy(&mn[q], acc[0][q], sizeof(v4));
-        std::memcpy(&mx[q], acc[1][q], sizeof(v4));
-      }
-      if (!ok512) ok = v4i{0, 0, 0, 0};
-    }
-    for (; i + 12 <= total; i += 12) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        v4 v;
-        std::memcpy(&v, xyz + i + 4 * q, sizeof(v));
-        __builtin_nontemporal_store(v, reinterpret_cast<v4 *>(dst + i + 4 * q));
-        const v4 dv = v - v;
-        const v4i fin = (dv == zero);  // (not finite: the element leaves the bounds alone)
-        mn[q] = __builtin_ia32_minps(mn[q], (v4)(((v4i)v & fin) | ((v4i)big & ~fin)));
-        mx[q] = __builtin_ia32_maxps(mx[q], (v4)(((v4i)v & fin) | ((v4i)(-big) & ~fin)));
-        ok &= fin;
-      }
-    }
-    // (Round 4: values that are not finite no longer send the list to the scalar loop below -- a LaserScan with beams
-    // without a return, a depth image with holes: 22 us at 4096 beams.  The bounds are those of the finite VALUES: a
-    // point with one coordinate missing still widens the other two -- a looser box, which only sizes the tables; the
-    // kernels drop the point as before.)
-    (void)ok;
-    {
-      // lanes: v0 = x0 y0 z0 x1 | v1 = y1 z1 x2 y2 | v2 = z2 x3 y3 z3
-      static const int vec_of[3][4] = {{0, 0, 1, 2}, {0, 1, 1, 2}, {0, 1, 2, 2}};
-      static const int lane_of[3][4] = {{0, 3, 2, 1}, {1, 0, 3, 2}, {2, 1, 0, 3}};
-      for (int a = 0; a < 3; ++a)
-        for (int q = 0; q < 4; ++q) {
-          lo[a] = std::min(lo[a], mn[vec_of[a][q]][lane_of[a][q]]);
-          hi[a] = std::max(hi[a], mx[vec_of[a][q]][lane_of[a][q]]);
-        }
-      bool tail_ok = true;
-      for (; i < total; ++i) {  // fewer than four points
-        const float v = xyz[i];
-        dst[i] = v;
-        if (!std::isfinite(v)) continue;
-        lo[i % 3] = std::min(lo[i % 3], v);
-        hi[i % 3] = std::max(hi[i % 3], v);
-      }
-      raw_copied = true;
-      tail_ok = lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2];  // (a finite value on every axis)
-      if (tail_ok) {
-        bounded = true;
-        nfin = n;
-      } else {
-        for (int a = 0; a < 3; ++a) {
-          lo[a] = FLT_MAX;
-          hi[a] = -FLT_MAX;
-        }
-      }
-    }
-  }
+  KC_TRY(bound_and_stage(c, xyz, n, lo, hi, &bounded));
+  raw_copied = true;
 #endif
-  for (size_t i = 0; i < n && !bounded; ++i) {
+  size_t nfin = bounded ? n : 0;
+  for (size_t i = 0; i < n && !bounded; ++i) {  // the bounds of the points that are finite on every axis
     const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) continue;
     lo[0] = std::min(lo[0], x);
@@ -593,8 +588,6 @@ int sensor_update_device(kc_dwa *c, const float *xyz, size_t n, bool *done) {
   return sensor_update_device_bounded(c, xyz, n, lo, hi, done, raw_copied);
 }
 
-// the part behind the bounds; xyz == nullptr: the points are in d_raw already
-// (grid hand-off)
 // The trig job of a sensor update (SensorArgs::trig): only for a context that has run a cycle (the horizon), whose
 // lattice is on the device and whose yaw chain stays inside the range of kc_trig_exact.h.
 int plan_trig_job(kc_dwa *c, TrigJob &j) {
@@ -607,136 +600,52 @@ int plan_trig_job(kc_dwa *c, TrigJob &j) {
   const double dt = static_cast<double>(static_cast<float>(c->prm.time_step));
   double om_max = 0.0;
   for (double v : c->lat.omega_values) om_max = std::max(om_max, std::fabs(v));
-  const double reach = std::fabs(c->trig_plan_yaw) + om_max * dt * static_cast<double>(P);
-  if (!(reach < 1.0e8)) return KC_OK;
+  if (!yaw_reach_ok(c->trig_plan_yaw, om_max, dt, P)) return KC_OK;
   KC_TRY(c->d_trig.reserve(A * P));
   KC_TRY(ensure_sincostab(c));
-  j.yaw0 = c->trig_plan_yaw;
-  j.dt = dt;
-  j.omega = c->d_omega.p;
-  j.tab = c->d_sincostab.p;
-  j.out = c->d_trig.p;
-  j.A = static_cast<int>(A);
-  j.P = static_cast<int>(P);
-  j.nblk = static_cast<int>(std::min<size_t>(32, (A * P + kSensorBlock - 1) / kSensorBlock));
+  j = make_trig_job(c->trig_plan_yaw, dt, c->d_omega.p, c->d_sincostab.p, c->d_trig.p, A, P, 32, kSensorBlock);
   c->trig_ahead_yaw = c->trig_plan_yaw;
   c->trig_ahead_P = P;
   c->trig_ahead_lat = c->lat_version;
   return KC_OK;
 }
 
-int sensor_update_device_bounded(kc_dwa *c, const float *xyz, size_t n, const float lo[3],
-                                 const float hi[3], bool *done, bool raw_copied) {
-  *done = false;
-  if (!c->device_sensor || !c->trig_direct || n == 0 || n > kSensorDeviceMax)
-    return KC_OK;
-  // bitmap: keys of the bounds (points beyond the 16-level octree are dropped
-  // by add_voxel anyway)
-  auto key = [&](float v) {
-    const double f = std::floor(c->inv_res * static_cast<double>(v));
-    return static_cast<int>(std::min(std::max(f, -32768.0), 32767.0));
-  };
-  // Spheres (round 4; the host build took 120 us of a 176 us cycle): a voxel's z gap to the sphere's centre is a function
-  // of its LAYER, so add_voxel's rule is evaluated here once per layer the cloud's z range can hold -- accepted layers,
-  // their gaps in ascending order (the LUT of the exact tests), the code of every layer -- and the one-launch build keeps
-  // the smallest code of every voxel column (sensor_band_body).  The gap bound of the dilated masks is the largest gap of
-  // those layers: at least the largest gap present, so "certain hits" stay certain.  More than 32 layers, more than
-  // 32 k points, bands beyond LDS: the host build.
-  const bool sphere = c->prm.shape == KC_SPHERE;
-  int sph_kz0 = 0, sph_nkz = 0;
-  unsigned char sph_code[36] = {0};
-  std::vector<double> sph_lut;
-  if (sphere) {
-    if (c->sensor_two_launch || n > kSensorFusedMax || !c->sensor_fused_ok) return KC_OK;
-    // (only the layers that can touch the sphere: a 3-D cloud spans two metres of height, forty layers of 5 cm -- the
-    // rule below rejects a layer whose gap exceeds the radius, i.e. every layer outside [zc - r, zc + r] and a layer of
-    // slack; the kernel rejects whatever lies outside the table)
-    const double zc = -static_cast<double>(c->frame.t[2]);
-    const int k0 = std::max(key(lo[2]), static_cast<int>(std::max(std::floor((zc - c->radius) * c->inv_res) - 1.0, -32768.0)));
-    const int k1 = std::min(key(hi[2]), static_cast<int>(std::min(std::floor((zc + c->radius) * c->inv_res) + 1.0, 32767.0)));
-    if (k1 - k0 + 1 > 36) return KC_OK;
-    double gap[36];
-    double gmax = -1.0;
-    for (int kz = k0; kz <= k1; ++kz) {  // add_voxel, the sphere branch
-      const double zlo = static_cast<double>(kz) * c->res, zhi = static_cast<double>(kz + 1) * c->res;
-      double ddz = 0.0;
-      if (zlo - zc > ddz) ddz = zlo - zc;
-      if (zc - zhi > ddz) ddz = zc - zhi;
-      gap[kz - k0] = ddz > c->radius ? -1.0 : ddz;
-      if (gap[kz - k0] >= 0.0) {
-        gmax = std::max(gmax, ddz);
-        bool seen = false;
-        for (double v : sph_lut) seen = seen || v == ddz;
-        if (!seen) sph_lut.push_back(ddz);
-      }
-    }
-    std::sort(sph_lut.begin(), sph_lut.end());
-    if (sph_lut.size() > 32) return KC_OK;
-    for (int kz = k0; kz <= k1; ++kz)
-      if (gap[kz - k0] >= 0.0)
-        sph_code[kz - k0] = static_cast<unsigned char>(std::lower_bound(sph_lut.begin(), sph_lut.end(), gap[kz - k0]) - sph_lut.begin() + 1);
-    sph_kz0 = k0;
-    sph_nkz = std::max(k1 - k0 + 1, 0);
-    c->sphere_ddz_max = gmax;  // (dil_geom: -1 = no layer of the cloud can touch the sphere: no masks, no voxels)
-  }
-  bool fits = false;
-  KC_TRY(bitmap_extent(c, key(lo[0]), key(lo[1]), key(hi[0]), key(hi[1]), &fits));
-  const size_t nwords = fits ? static_cast<size_t>(c->gH) * c->gwpr : 0;
-  if (!fits) {
-    c->have_gbits = false;
-      return KC_OK;
-  }
-  if (sphere) {
-    // (decided before anything is written: a sphere either takes the one-launch build or the host's)
-    const DilGeom dg0 = dil_geom(c);
-    const int dilR0 = c->have_dil ? dg0.R : -1;
-    int nb0 = std::min(64, c->gH), rows0 = (c->gH + nb0 - 1) / nb0;
-    auto bytes0 = [&] { return (3 * static_cast<size_t>(rows0) + 2 * static_cast<size_t>(std::max(dilR0, 0)) + 32 * static_cast<size_t>(rows0)) * c->gwpr * 4; };
-    while (bytes0() > kSensorFusedLds && rows0 > 1) rows0 = (rows0 + 1) / 2;
-    if (bytes0() > kSensorFusedLds || (c->gH + rows0 - 1) / rows0 > 1024) return KC_OK;
-  }
-  // one workgroup with everything in LDS, or (large clouds / bitmaps) the points
-  // over many workgroups with device atomics
-  const bool big_only = c->sensor_two_launch;  // option "sensor_two_launch": the build for clouds beyond kSensorFusedMax, for any size (tests)
-  // bucket grid: covers the image of the bounding box (an affine map takes the
-  // box into the hull of its eight transformed corners)
-  double blo[2] = {DBL_MAX, DBL_MAX}, bhi[2] = {-DBL_MAX, -DBL_MAX};
+// the hull of the bounding box under the obstacle transform (an affine map takes the box into the hull of its eight
+// transformed corners), the bitmap and its halo: what plan_sensor sizes the build from.  false: a corner is not finite.
+static bool sensor_facts(const kc_dwa *c, size_t n, const float lo[3], const float hi[3], int dilR, SensorFacts &f) {
+  f = SensorFacts{n, c->prm.shape == KC_SPHERE, c->sensor_two_launch, c->sensor_fused_ok, c->gH, c->gwpr, dilR,
+                  {DBL_MAX, DBL_MAX}, {-DBL_MAX, -DBL_MAX}};
   for (int k = 0; k < 8; ++k) {
     float o[3];
     const float zc = c->raw_is_scan ? 0.0f : ((k & 4) ? hi[2] : lo[2]);
     c->obs_tf.apply((k & 1) ? hi[0] : lo[0], (k & 2) ? hi[1] : lo[1], zc, o);
-    if (!std::isfinite(o[0]) || !std::isfinite(o[1])) return KC_OK;
-    blo[0] = std::min(blo[0], static_cast<double>(o[0]));
-    bhi[0] = std::max(bhi[0], static_cast<double>(o[0]));
-    blo[1] = std::min(blo[1], static_cast<double>(o[1]));
-    bhi[1] = std::max(bhi[1], static_cast<double>(o[1]));
+    if (!std::isfinite(o[0]) || !std::isfinite(o[1])) return false;
+    f.blo[0] = std::min(f.blo[0], static_cast<double>(o[0]));
+    f.bhi[0] = std::max(f.bhi[0], static_cast<double>(o[0]));
+    f.blo[1] = std::min(f.blo[1], static_cast<double>(o[1]));
+    f.bhi[1] = std::max(f.bhi[1], static_cast<double>(o[1]));
   }
-  const double ext0 = std::max(bhi[0] - blo[0], bhi[1] - blo[1]);
-  const double margin = 1e-4 * ext0 + 1e-4;  // float rounding of the transformed points
-  blo[0] -= margin;
-  blo[1] -= margin;
-  bhi[0] += margin;
-  bhi[1] += margin;
+  return true;
+}
+
+// the bucket grid of the plan into the context, the tables' buffers, the raw points through the BAR
+static int reserve_and_stage(kc_dwa *c, const float *xyz, size_t n, const SensorPlan &p, bool raw_copied) {
   BucketDev &b = c->bucket;
   std::memset(&b, 0, sizeof(b));
   b.cap = static_cast<double>(c->max_obs_dist) * 1.001;
-  const int side = std::min(64, std::max(8, static_cast<int>(std::ceil(std::sqrt(
-                                                static_cast<double>(n))))));
-  const double ext = std::max(bhi[0] - blo[0], bhi[1] - blo[1]);
-  b.g = std::max(0.125, ext / (side - 1));
-  b.inv_g = 1.0 / b.g;
-  b.gx0 = blo[0];
-  b.gy0 = blo[1];
-  b.W = std::min(side, static_cast<int>((bhi[0] - blo[0]) * b.inv_g) + 1);
-  b.H = std::min(side, static_cast<int>((bhi[1] - blo[1]) * b.inv_g) + 1);
+  b.g = p.g;
+  b.inv_g = p.inv_g;
+  b.gx0 = p.gx0;
+  b.gy0 = p.gy0;
+  b.W = p.W;
+  b.H = p.H;
   const size_t ncell = static_cast<size_t>(b.W) * b.H;
   KC_TRY(c->d_cells.reserve(ncell + 4));   // (+ the tail of the cycle kernel's 16-byte copies)
   KC_TRY(c->d_skip.reserve(ncell + 16));
   KC_TRY(c->d_bobs.reserve(2 * n));
   KC_TRY(c->d_raw.reserve(3 * n + 16));
-  // the raw points: host copy for the lazy lists, device copy through the BAR
   c->host_lists_valid = false;
-  if (xyz) {
+  if (xyz) {  // (nullptr: the points are in d_raw already -- a grid hand-off)
     // (no host copy: the lists that the split path and the debug getters need are rebuilt from the
     // device copy on demand, ensure_host_lists)
     const auto tb0 = std::chrono::steady_clock::now();
@@ -750,7 +659,11 @@ int sensor_update_device_bounded(kc_dwa *c, const float *xyz, size_t n, const fl
   c->raw_xyz.clear();
   c->raw_on_device = true;
   c->raw_n = n;
-  SensorArgs a{};
+  return KC_OK;
+}
+
+static void fill_sensor_args(const kc_dwa *c, size_t n, const SphereLayers &layers, SensorArgs &a) {
+  const BucketDev &b = c->bucket;
   a.xyz = c->d_raw.p;
   a.n = static_cast<int>(n);
   a.inv_res = c->inv_res;
@@ -776,180 +689,179 @@ int sensor_update_device_bounded(kc_dwa *c, const float *xyz, size_t n, const fl
   a.bx = c->d_bobs.p;
   a.by = c->d_bobs.p + n;
   a.obs_z_zero = c->raw_is_scan ? 1 : 0;
-  a.sphere = sphere ? 1 : 0;
-  a.kz0 = sph_kz0;
-  a.nkz = sph_nkz;
-  std::memcpy(a.zcode, sph_code, sizeof(a.zcode));
+  a.sphere = c->prm.shape == KC_SPHERE ? 1 : 0;
+  a.kz0 = layers.kz0;
+  a.nkz = layers.nkz;
+  std::memcpy(a.zcode, layers.code, sizeof(a.zcode));
+}
+
+// the sphere's tables of the one-launch build: the gap LUT to the device, a byte per voxel column for the codes
+static int stage_sphere_tables(kc_dwa *c, const SphereLayers &layers, SensorFusedArgs &f) {
+  const size_t gcells = static_cast<size_t>(c->gwpr) * 32 * c->gH, nl = static_cast<size_t>(layers.nlut);
+  KC_TRY(c->d_gz.reserve(gcells));
+  KC_TRY(c->h_zlut.reserve(256));
+  KC_TRY(c->d_zlut.reserve(256));
+  for (size_t k = 0; k < nl; ++k) c->h_zlut.p[k] = layers.lut[k];
+  if (nl) KC_TRY(upload_table(c, c->d_zlut.p, c->h_zlut.p, nl * sizeof(double)));
+  bar_flush(c);
+  c->sphere_layers = nl;
+  c->gz_valid = nl != 0;
+  f.gz = c->d_gz.p;
+  return KC_OK;
+}
+
+// One launch (sensor_fused_kernel): bands of the bitmap with their dilations, slices of the bucket tables, and the
+// riders -- the near table of a scan, the cycle's trig table
+static int launch_sensor_fused(kc_dwa *c, const SensorPlan &p, const SphereLayers &layers, const DilGeom &dg, int dilR,
+                               const SensorArgs &a) {
+  const BucketDev &b = c->bucket;
+  SensorFusedArgs f{};
+  f.a = a;
+  f.nb = p.nb;
+  f.kb = 8;
+  f.band_rows = p.band_rows;
+  f.R = dilR;
+  f.ginner = c->d_ginner.p;
+  f.gouter = c->d_gouter.p;
+  if (dilR >= 0) dil_tables(dg, f.win, f.wout);
+  c->gz_valid = false;
+  if (a.sphere) KC_TRY(stage_sphere_tables(c, layers, f));
+  // bucket workgroup: cell slots + row masks + (lists of more than one trip) a position per cell
+  const size_t ncell = static_cast<size_t>(b.W) * b.H;
+  const size_t bucket_lds = ((ncell + 4) & ~size_t(3)) * 4 + 64 * 8 + ((ncell + 3) & ~size_t(3)) * 4;
+  // float estimate of the cell index (sensor_obstacle_fast): its distance from the double expression
+  {
+    const double span = std::max(std::fabs(b.gx0), std::fabs(b.gy0)) + 64.0 * b.g;  // largest |coordinate| inside the grid
+    const double ulp = span * 1.2e-7;                                                  // float spacing there
+    const double err = (2.0 * ulp) * b.inv_g + 66.0 * 2.4e-7;                          // origin + difference, scaled; product rounding
+    f.gx0f = static_cast<float>(b.gx0);
+    f.gy0f = static_cast<float>(b.gy0);
+    f.inv_gf = static_cast<float>(b.inv_g);
+    f.id_eps = static_cast<float>(std::min(0.5, 8.0 * err));
+  }
+  // a band's y interval (sensor_band_body's first filter): keys gky0 + rows, padded by a voxel and the float rounding of y
+  f.band_y0 = static_cast<float>(static_cast<double>(c->gky0) * c->res);
+  f.band_dy = static_cast<float>(static_cast<double>(p.band_rows) * c->res);
+  f.band_pad = static_cast<float>((static_cast<double>(std::max(dilR, 0)) + 2.0) * c->res +
+                                  1e-5 * (std::fabs(static_cast<double>(c->gky0)) + c->gH) * c->res);
+  size_t lds = std::max(p.band_bytes, bucket_lds) + 16;
+  const size_t olds = 2 * static_cast<size_t>(c->onear_args.n) * sizeof(float);
+  if (c->onear_ahead && olds <= kObsNearLdsMax) {  // the scan's near table rides along
+    const int cells = c->onear_args.W * c->onear_args.H, per = kSensorBlock / kObsNearLanes;
+    f.o = c->onear_args;
+    f.o_blocks = (cells + per - 1) / per;
+    lds = std::max(lds, olds);
+    c->onear_version = c->sensor_version;
+    ++c->onear_rides;
+  }
+#ifdef KC_PHASE_STAMPS
+  KC_TRY(arm_stamps(c, c->d_dbg, 512 * 16, 512 * 16, &f.dbg));
+#endif
+  KC_TRY(c->timing.start("sensor_fused_kernel", c->stream));
+  hipLaunchKernelGGL(sensor_fused_kernel<true>, dim3(f.nb + f.kb + f.o_blocks + a.trig.nblk), dim3(kSensorBlock), lds, c->stream, f);
+  KC_TRY(c->timing.stop(c->stream));
+#ifdef KC_PHASE_STAMPS
+  if (f.dbg && (++c->sensor_stamp_calls % 100) == 50) {
+    const int G = std::min(512, f.nb + f.kb);
+    std::vector<unsigned long long> h;
+    unsigned long long t0;
+    KC_TRY(fetch_stamps(c, G, h, &t0));
+    static const char *bn[5] = {"start", "lds zero", "points", "dilated", "rows out"};
+    static const char *kn[7] = {"start", "lds zero", "counted", "scanned", "masks + pos", "slice out", "placed"};
+    dump_stamps("sensor_fused_kernel bands", h, t0, 0, std::min(G, f.nb), bn, 5);
+    dump_stamps("sensor_fused_kernel buckets", h, t0, f.nb, G, kn, 7);
+  }
+#endif
+  return KC_OK;
+}
+
+// Two launches (large clouds / bitmaps): the points over many workgroups, no global atomics (kc_sensor_kernels.h)
+static int launch_sensor_two(kc_dwa *c, const SensorPlan &p, size_t n, const SensorArgs &a) {
+  const size_t nwords = static_cast<size_t>(c->gH) * c->gwpr;
+  {  // byte map of the voxels: zero between updates (sensor_place_kernel clears what it packs)
+    const uint8_t *was = c->d_sensor_bytes.p;
+    KC_TRY(c->d_sensor_bytes.reserve(nwords * 32));
+    if (c->d_sensor_bytes.p != was)
+      KC_HIP(hipMemsetAsync(c->d_sensor_bytes.p, 0, c->d_sensor_bytes.cap, c->stream));
+  }
+  // scratch: [cell records n | ox n | oy n | histogram rows]
+  SensorBigArgs sb{};
+  sb.a = a;
+  sb.ppt = p.ppt;
+  sb.rows = p.rows;
+  KC_TRY(c->d_sensor_tmp.reserve(3 * n + static_cast<size_t>(sb.rows) * kHistRow + 4));
+  sb.tcell = reinterpret_cast<int *>(c->d_sensor_tmp.p);
+  sb.tox = reinterpret_cast<float *>(sb.tcell + n);
+  sb.toy = sb.tox + n;
+  sb.hist = reinterpret_cast<int *>((reinterpret_cast<uintptr_t>(sb.toy + n) + 15) & ~uintptr_t(15));
+  sb.bytes = c->d_sensor_bytes.p;
+#ifdef KC_PHASE_STAMPS
+  KC_TRY(arm_stamps(c, c->d_dbg, 512 * 16, 16 * 16, &sb.dbg));
+#endif
+  KC_TRY(c->timing.start("sensor_points_kernel", c->stream));
+  hipLaunchKernelGGL(sensor_points_kernel, dim3(sb.rows + a.trig.nblk), dim3(kSensorBlock), 0, c->stream, sb);
+  KC_TRY(c->timing.stop(c->stream));
+  KC_TRY(c->timing.start("sensor_place_kernel", c->stream));
+  const unsigned pack_blocks = std::min(240u, blocks_for(nwords, kSensorBlock));  // pack-only workgroups behind the rows
+  hipLaunchKernelGGL(sensor_place_kernel, dim3(sb.rows + pack_blocks), dim3(kSensorBlock), 0, c->stream, sb);
+  KC_TRY(c->timing.stop(c->stream));
+#ifdef KC_PHASE_STAMPS
+  if (sb.dbg) {
+    std::vector<unsigned long long> h;
+    unsigned long long t0;
+    KC_TRY(fetch_stamps(c, 16, h, &t0));
+    static const char *nm[12] = {"points: start", "lds zero", "points done", "row out", "place: start", "sums", "scan", "masks",
+                                 "cells", "placed", "pack: start", "pack: end"};
+    dump_stamps("sensor build (points, place)", h, t0, 0, 16, nm, 12);
+  }
+#endif
+  return KC_OK;
+}
+
+// The part behind the bounds: the host derives the bitmap extent and the bucket grid from the bounds, stores the raw
+// points through the BAR (xyz == nullptr: they are in d_raw already -- a grid hand-off) and queues one launch or two
+// (plan_sensor, kc_launch_plan.h).  *done = false: conditions not met, the caller takes the host path.
+int sensor_update_device_bounded(kc_dwa *c, const float *xyz, size_t n, const float lo[3],
+                                 const float hi[3], bool *done, bool raw_copied) {
+  *done = false;
+  if (!sensor_device_takes(c, n)) return KC_OK;
+  const bool sphere = c->prm.shape == KC_SPHERE;
+  SphereLayers layers{};
+  if (sphere) {
+    layers = plan_sphere_layers(voxel_key(c->inv_res, lo[2]), voxel_key(c->inv_res, hi[2]), -static_cast<double>(c->frame.t[2]),
+                                c->radius, c->res, c->inv_res);
+    if (!layers.ok) return KC_OK;
+    c->sphere_ddz_max = layers.gmax;  // (dil_geom: the padding of the bitmap depends on it)
+  }
+  bool fits = false;
+  KC_TRY(bitmap_extent(c, voxel_key(c->inv_res, lo[0]), voxel_key(c->inv_res, lo[1]), voxel_key(c->inv_res, hi[0]),
+                       voxel_key(c->inv_res, hi[1]), &fits));
+  if (!fits) {
+    c->have_gbits = false;
+    return KC_OK;
+  }
+  const DilGeom dg = dil_geom(c);
+  const int dilR = c->have_dil ? dg.R : -1;
+  SensorFacts facts;
+  if (!sensor_facts(c, n, lo, hi, dilR, facts)) return KC_OK;
+  const SensorPlan plan = plan_sensor(facts);
+  // (decided before anything is written: a sphere either takes the one-launch build or the host's)
+  if (sphere && !plan.fused) return KC_OK;
+  KC_TRY(reserve_and_stage(c, xyz, n, plan, raw_copied));
+  SensorArgs a{};
+  fill_sensor_args(c, n, layers, a);
   KC_TRY(plan_trig_job(c, a.trig));
-  const unsigned tj = static_cast<unsigned>(a.trig.nblk);
-  if (tj) {
+  if (a.trig.nblk) {
     c->trig_ahead_valid = true;
     ++c->trig_rides;
   }
-  // One launch, no hand-over between workgroups (sensor_fused_kernel): every workgroup reads all points and keeps
-  // its part -- bands of the bitmap with their dilations, slices of the bucket tables.  Beyond 32 k points (every
-  // workgroup reading every point stops being free) or with bands that do not fit LDS: the two-launch build.
-  const DilGeom dg = dil_geom(c);
-  const int dilR = c->have_dil ? dg.R : -1;
-  int nb = std::min(64, c->gH), band_rows = (c->gH + nb - 1) / nb;
-  // (LDS of a band: its rows + R rows of halo either side, and the two dilation accumulators of its own rows)
-  auto band_bytes = [&] {
-    return (3 * static_cast<size_t>(band_rows) + 2 * static_cast<size_t>(std::max(dilR, 0)) + (sphere ? 32 * static_cast<size_t>(band_rows) : 0)) * c->gwpr * 4;
-  };
-  while (band_bytes() > kSensorFusedLds && band_rows > 1) {
-    band_rows = (band_rows + 1) / 2;
-  }
-  nb = (c->gH + band_rows - 1) / band_rows;
-  const bool fused = !big_only && c->sensor_fused_ok && n <= (sphere ? kSensorFusedMax : kSensorFusedPays) &&
-                     band_bytes() <= kSensorFusedLds && nb <= 1024;
-  bool masks_built = false;
-  if (fused) {
-    SensorFusedArgs f{};
-    f.a = a;
-    f.nb = nb;
-    f.kb = 8;
-    f.band_rows = band_rows;
-    f.R = dilR;
-    f.ginner = c->d_ginner.p;
-    f.gouter = c->d_gouter.p;
-    if (dilR >= 0) dil_tables(dg, f.win, f.wout);
-    c->gz_valid = false;
-    if (sphere) {
-      const size_t gcells = static_cast<size_t>(c->gwpr) * 32 * c->gH;
-      KC_TRY(c->d_gz.reserve(gcells));
-      KC_TRY(c->h_zlut.reserve(256));
-      KC_TRY(c->d_zlut.reserve(256));
-      for (size_t k = 0; k < sph_lut.size(); ++k) c->h_zlut.p[k] = sph_lut[k];
-      if (!sph_lut.empty()) KC_TRY(upload_table(c, c->d_zlut.p, c->h_zlut.p, sph_lut.size() * sizeof(double)));
-      bar_flush(c);
-      c->sphere_layers = sph_lut.size();
-      c->gz_valid = !sph_lut.empty();
-      f.gz = c->d_gz.p;
-    }
-    // bucket workgroup: cell slots + row masks + (lists of more than one trip) a position per cell
-    const size_t bucket_lds = ((ncell + 4) & ~size_t(3)) * 4 + 64 * 8 + ((ncell + 3) & ~size_t(3)) * 4;
-    // float estimate of the cell index (sensor_obstacle_fast): its distance from the double expression
-    {
-      const double span = std::max(std::fabs(b.gx0), std::fabs(b.gy0)) + 64.0 * b.g;  // largest |coordinate| inside the grid
-      const double ulp = span * 1.2e-7;                                                  // float spacing there
-      const double err = (2.0 * ulp) * b.inv_g + 66.0 * 2.4e-7;                          // origin + difference, scaled; product rounding
-      f.gx0f = static_cast<float>(b.gx0);
-      f.gy0f = static_cast<float>(b.gy0);
-      f.inv_gf = static_cast<float>(b.inv_g);
-      f.id_eps = static_cast<float>(std::min(0.5, 8.0 * err));
-    }
-    // a band's y interval (sensor_band_body's first filter): keys gky0 + rows, padded by a voxel and the float rounding of y
-    f.band_y0 = static_cast<float>(static_cast<double>(c->gky0) * c->res);
-    f.band_dy = static_cast<float>(static_cast<double>(band_rows) * c->res);
-    f.band_pad = static_cast<float>((static_cast<double>(std::max(dilR, 0)) + 2.0) * c->res +
-                                    1e-5 * (std::fabs(static_cast<double>(c->gky0)) + c->gH) * c->res);
-    size_t lds = std::max(band_bytes(), bucket_lds) + 16;
-    const size_t olds = 2 * static_cast<size_t>(c->onear_args.n) * sizeof(float);
-    const bool ride = c->onear_ahead && olds <= kObsNearLdsMax;
-    if (ride) {
-      const int cells = c->onear_args.W * c->onear_args.H, per = kSensorBlock / kObsNearLanes;
-      f.o = c->onear_args;
-      f.o_blocks = (cells + per - 1) / per;
-      lds = std::max(lds, olds);
-      c->onear_version = c->sensor_version;
-      ++c->onear_rides;
-    }
-#ifdef KC_PHASE_STAMPS
-    if (c->debug_stamps) {
-      KC_TRY(c->d_dbg.reserve(512 * 16));
-      KC_HIP(hipMemsetAsync(c->d_dbg.p, 0, 512 * 16 * 8, c->stream));
-      f.dbg = c->d_dbg.p;
-    }
-#endif
-    KC_TRY(c->timing.start("sensor_fused_kernel", c->stream));
-    hipLaunchKernelGGL(sensor_fused_kernel<true>, dim3(f.nb + f.kb + f.o_blocks + tj), dim3(kSensorBlock), lds, c->stream, f);
-    KC_TRY(c->timing.stop(c->stream));
-#ifdef KC_PHASE_STAMPS
-    if (f.dbg && (++c->sensor_stamp_calls % 100) == 50) {
-      const int G = std::min(512, f.nb + f.kb);
-      std::vector<unsigned long long> h(static_cast<size_t>(G) * 16);
-      KC_HIP(hipStreamSynchronize(c->stream));
-      KC_HIP(hipMemcpy(h.data(), c->d_dbg.p, h.size() * 8, hipMemcpyDeviceToHost));
-      unsigned long long t0 = ~0ull;
-      for (int r = 0; r < G; ++r) if (h[r * 16]) t0 = std::min(t0, h[r * 16]);
-      auto dump = [&](const char *what, int r0, int r1, const char *const *nm, int cnt) {
-        std::fprintf(stderr, "[kc stamps] sensor_fused_kernel %s, us since the first workgroup (avg / max):\n", what);
-        for (int k = 0; k < cnt; ++k) {
-          double sm = 0, mx = 0; int m = 0;
-          for (int r = r0; r < r1; ++r) {
-            if (!h[r * 16 + k]) continue;
-            const double us = (h[r * 16 + k] - t0) / 100.0;
-            sm += us; mx = std::max(mx, us); ++m;
-          }
-          if (m) std::fprintf(stderr, "  %-18s %6.2f / %6.2f\n", nm[k], sm / m, mx);
-        }
-      };
-      static const char *bn[5] = {"start", "lds zero", "points", "dilated", "rows out"};
-      static const char *kn[7] = {"start", "lds zero", "counted", "scanned", "masks + pos", "slice out", "placed"};
-      dump("bands", 0, std::min(G, f.nb), bn, 5);
-      dump("buckets", f.nb, G, kn, 7);
-    }
-#endif
-    masks_built = true;
-  } else {
-    if (sphere) KC_FAIL(KC_ERR_STATE, "sphere: the one-launch sensor build was decided above");  // (cannot happen)
-    {  // byte map of the voxels: zero between updates (sensor_place_kernel clears what it packs)
-      const uint8_t *was = c->d_sensor_bytes.p;
-      KC_TRY(c->d_sensor_bytes.reserve(nwords * 32));
-      if (c->d_sensor_bytes.p != was)
-        KC_HIP(hipMemsetAsync(c->d_sensor_bytes.p, 0, c->d_sensor_bytes.cap, c->stream));
-    }
-    // scratch: [cell records n | ox n | oy n | histogram rows]
-    SensorBigArgs sb{};
-    sb.a = a;
-    sb.ppt = static_cast<int>((n + static_cast<size_t>(kHistRowsMax) * kSensorBlock - 1) / (static_cast<size_t>(kHistRowsMax) * kSensorBlock));
-    sb.rows = static_cast<int>(blocks_for(n, static_cast<size_t>(kSensorBlock) * sb.ppt));
-    KC_TRY(c->d_sensor_tmp.reserve(3 * n + static_cast<size_t>(sb.rows) * kHistRow + 4));
-    sb.tcell = reinterpret_cast<int *>(c->d_sensor_tmp.p);
-    sb.tox = reinterpret_cast<float *>(sb.tcell + n);
-    sb.toy = sb.tox + n;
-    sb.hist = reinterpret_cast<int *>((reinterpret_cast<uintptr_t>(sb.toy + n) + 15) & ~uintptr_t(15));
-    sb.bytes = c->d_sensor_bytes.p;
-#ifdef KC_PHASE_STAMPS
-    if (c->debug_stamps) {
-      KC_TRY(c->d_dbg.reserve(512 * 16));
-      KC_HIP(hipMemsetAsync(c->d_dbg.p, 0, 16 * 16 * 8, c->stream));
-      sb.dbg = c->d_dbg.p;
-    }
-#endif
-    KC_TRY(c->timing.start("sensor_points_kernel", c->stream));
-    hipLaunchKernelGGL(sensor_points_kernel, dim3(sb.rows + tj), dim3(kSensorBlock), 0, c->stream, sb);
-    KC_TRY(c->timing.stop(c->stream));
-    KC_TRY(c->timing.start("sensor_place_kernel", c->stream));
-    const unsigned pack_blocks = std::min(240u, blocks_for(nwords, kSensorBlock));  // pack-only workgroups behind the rows
-    hipLaunchKernelGGL(sensor_place_kernel, dim3(sb.rows + pack_blocks), dim3(kSensorBlock), 0, c->stream, sb);
-    KC_TRY(c->timing.stop(c->stream));
-#ifdef KC_PHASE_STAMPS
-    if (sb.dbg) {
-      std::vector<unsigned long long> h(16 * 16);
-      KC_HIP(hipStreamSynchronize(c->stream));
-      KC_HIP(hipMemcpy(h.data(), c->d_dbg.p, h.size() * 8, hipMemcpyDeviceToHost));
-      unsigned long long t0 = ~0ull;
-      for (int r = 0; r < 16; ++r) if (h[r * 16]) t0 = std::min(t0, h[r * 16]);
-      static const char *nm[12] = {"points: start", "lds zero", "points done", "row out", "place: start", "sums", "scan", "masks",
-                                   "cells", "placed", "pack: start", "pack: end"};
-      std::fprintf(stderr, "[kc stamps] sensor build, us since the first points workgroup (avg / max over workgroups):\n");
-      for (int k = 0; k < 12; ++k) {
-        double sm = 0, mx = 0; int cnt = 0;
-        for (int r = 0; r < 16; ++r) {
-          if (!h[r * 16 + k]) continue;
-          const double us = (h[r * 16 + k] - t0) / 100.0;
-          sm += us; mx = std::max(mx, us); ++cnt;
-        }
-        if (cnt) std::fprintf(stderr, "  %-14s %6.2f / %6.2f\n", nm[k], sm / cnt, mx);
-      }
-    }
-#endif
-  }
+  if (plan.fused) KC_TRY(launch_sensor_fused(c, plan, layers, dg, dilR, a));
+  else KC_TRY(launch_sensor_two(c, plan, n, a));
   KC_HIP(hipGetLastError());
   c->update_busy = true;
-  if (!masks_built) KC_TRY(launch_dilate(c));  // (sensor_fused_kernel writes both dilations beside the bitmap)
+  if (!plan.fused) KC_TRY(launch_dilate(c));  // (sensor_fused_kernel writes both dilations beside the bitmap)
   c->have_gbits = true;
+  BucketDev &b = c->bucket;
   b.skip = c->d_skip.p;
   b.cell_start = c->d_cells.p;
   b.bx = c->d_bobs.p;
@@ -961,8 +873,6 @@ int sensor_update_device_bounded(kc_dwa *c, const float *xyz, size_t n, const fl
   return KC_OK;
 }
 
-// Near table for the cycle that starts at (x, y): kept when the segment is the one it was built
-// from and the reachable box still lies inside it.
 // Near table over the box [lo, hi] (every query point of the coming cost stage lies inside): kept when
 // the segment is the one it was built from and the box still lies inside it.
 int ensure_near_table_box(kc_dwa *c, double lo_x, double lo_y, double hi_x, double hi_y, double margin) {
@@ -1725,8 +1635,5 @@ int kc_dwa_set_tracked_window(kc_dwa *c, size_t start, size_t S) {
 
 
 void sensor_kernel_limits(kc_dwa *c) {
-  c->sensor_fused_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(sensor_fused_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           static_cast<int>(kSensorFusedLds)) == hipSuccess;
-  if (!c->sensor_fused_ok) (void)hipGetLastError();
+  c->sensor_fused_ok = lds_optin(sensor_fused_kernel<true>, kSensorFusedLds);
 }

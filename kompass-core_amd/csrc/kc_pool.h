@@ -1,4 +1,4 @@
-// Worker pool of the host-trig FALLBACK (kc_dwa.hip, rollout_impl: `device_trig` off, another libm, |yaw| beyond
+// Worker pool of the host-trig FALLBACK (kc_dwa_cycle.hip, host_trig_table: `device_trig` off, another libm, |yaw| beyond
 // the restated range): the rows of the cos / sin table are shared between the caller and a few workers, the call
 // returns when all of them are done.  Rounds 1-3 ran this on the critical path of every cycle (spinning workers,
 // asynchronous tickets, staged hand-off to a kernel that was already waiting); since device trig (round 3) it is

@@ -188,10 +188,9 @@ int kc_dwa_first_clear_command(kc_dwa *c, const kc_state *start, const double *v
   while (a.G < 64 && a.G < horizon + 1) a.G <<= 1;
   a.slots = pp.d_slots.p;
   // Device trig while every yaw_j stays inside the range kc_trig_exact.h covers and the restatement agreed with
-  // the installed libm (the roll-out's rule, rollout_impl); otherwise -- and if the kernel reports a failure
+  // the installed libm (yaw_reach_ok: the roll-out's rule); otherwise -- and if the kernel reports a failure
   // anyway -- the host's libm fills the table, as the roll-out's fallback does.
-  const double yaw_reach = std::fabs(start->yaw) + om_max * std::fabs(dtf) * static_cast<double>(horizon);
-  bool dev_trig = c->device_trig && trig_selfcheck_ok() && std::isfinite(yaw_reach) && yaw_reach < 1.0e8;
+  bool dev_trig = c->device_trig && trig_selfcheck_ok() && yaw_reach_ok(start->yaw, om_max, std::fabs(dtf), static_cast<size_t>(horizon));
   if (dev_trig) {
     KC_TRY(ensure_sincostab(c));
     a.tab = c->d_sincostab.p;

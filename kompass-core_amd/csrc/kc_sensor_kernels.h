@@ -8,6 +8,8 @@
 // over them).  Part of kc_dwa.hip.
 #pragma once
 
+#include "kc_launch_plan.h"
+
 namespace kc {
 
 struct SensorArgs {
@@ -32,8 +34,6 @@ struct SensorArgs {
   int sphere, kz0, nkz;
   unsigned char zcode[36];
 };
-
-constexpr int kSensorBlock = 1024;
 
 __device__ __forceinline__ bool sensor_obstacle(const SensorArgs &a, float x, float y, float z,
                                                 float &ox, float &oy, int &id) {
@@ -70,7 +70,6 @@ __device__ __forceinline__ bool sensor_obstacle(const SensorArgs &a, float x, fl
 // rebuild) + cost_evaluator.h:174-223 (setPointScan).
 // ---------------------------------------------------------------------------
 constexpr int kHistRow = 64 * 64;  // ints per row of the histogram matrix
-constexpr int kHistRowsMax = 16;   // the host picks points per thread so that the rows fit
 struct SensorBigArgs {
   SensorArgs a;
   int ppt;          // points per thread (1 .. 64): a workgroup takes 1024 * ppt consecutive points
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(kSensorBlock) void sensor_points_kernel(SensorBigAr
     int id;
     int rec = -1;
     if (sensor_obstacle(a, x, y, a.obs_z_zero ? 0.0f : z, ox, oy, id)) {
-      rec = id | (atomicAdd(&lhist[id], 1) << 12);  // id < 4096 cells, rank < kSensorBlock * ppt (kc_dwa_ctx.h)
+      rec = id | (atomicAdd(&lhist[id], 1) << 12);  // id < 4096 cells, rank < kSensorBlock * ppt < 2^19 (kc_launch_plan.h)
       b.tox[i] = ox;
       b.toy[i] = oy;
     }
