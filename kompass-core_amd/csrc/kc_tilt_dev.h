@@ -2,8 +2,11 @@
 // F = body_tf * sensor_tf_body of collision_check.h:99-117 is not upright, collision_check.cpp:61-68 accepts
 // any quaternion).  The voxels of a laser scan form ONE layer kz = floor(hz / res) of cubes
 // [k res, (k + 1) res]^3 in F; the robot shape stands upright in the world.  Exact closed-set tests in f64
-// with a fixed operation order (the oracle restates them; FCL does these with GJK -- the reference holds no
-// vector for a tilted mount: parity unpinned beyond this build's restatement):
+// with a fixed operation order (the oracle restates them; FCL does these with GJK and the reference holds no
+// vector for a tilted mount).  Pinned by exact geometry in integers (tests/collision_exact_ref.py: half-space
+// vertex enumeration for the box, slab cut + exact hull for the cylinder, clamped distance for the sphere) at
+// contact, +-4 eps and +-64 eps about it and edge against edge for each of the nine cross-product axes, with
+// eps = 2^-20 L (1.9e-6 .. 3.4e-6 m here) covering only the float32 frame's distance from an orthonormal one:
 //   sphere    distance from the centre (taken into F) to the cube
 //   box       separating axes of two boxes: 3 cube axes, 3 box axes, 9 cross products
 //   cylinder  in the robot's frame the cylinder is {|z| <= hh} x disc(r): clip the cube to the slab, project
