@@ -1414,6 +1414,73 @@ int kc_mcl_particles_device(kc_mcl *ctx, void **tx_out, void **ty_out, void **h_
 int kc_mcl_set_timing(kc_mcl *ctx, int enable);
 int kc_mcl_times(kc_mcl *ctx, float ms_out[4]);
 
+/* ------------------------------------------------------------------------ */
+/* The map's distance plane and the likelihood-field model (DESIGN.md 4.11 rules 42 to 45) */
+/* ------------------------------------------------------------------------ */
+/* Off by default: with the plane off every entry above does what it did without it.
+ * Rule 42, plane: dist2[I + J W], uint16: the smallest (bI - I)^2 + (bJ - J)^2 over the blocking
+ * cells when that is <= reach^2, KC_WORLDMAP_DIST_FAR otherwise.  A cell blocks when its cls
+ * byte is KC_OCCUPIED, with KC_WORLDMAP_DIST_UNKNOWN_BLOCKS also when it is KC_UNEXPLORED;
+ * cells outside the map never block.  1 <= reach <= 254 (kc_planner_set_clearance_cost's
+ * clear2, on purpose).
+ * Rule 43, refresh: the plane is kept lazily behind a dirty box of cells whose class may have
+ * changed.  kc_worldmap_set_distance (reach > 0), kc_worldmap_set_prior_*, kc_worldmap_clear
+ * and kc_worldmap_set_model make it the whole map; an update merges the box of its result
+ * (changed != 0) into it on the host: no extra launch, no extra read-back.  A refresh
+ * recomputes dist2 over the dirty box grown by reach on every side and clipped to the map (one
+ * launch up to reach 63, two above), then empties the box; with an empty box it launches
+ * nothing.  Every entry that reads the plane refreshes first.  dist2 of a cell depends only on
+ * the cls bytes of the (2 reach + 1)^2 square around it, so the plane equals a full recompute
+ * after any sequence of updates and refreshes. */
+#define KC_WORLDMAP_DIST_FAR 0xFFFFu
+#define KC_WORLDMAP_DIST_UNKNOWN_BLOCKS 1u
+#define KC_WORLDMAP_DIST_MAX_REACH 254
+/* reach 0 switches the plane off and frees it (flags must then be 0 too).  KC_ERR_RANGE for a
+ * reach outside 0 .. 254, KC_ERR_INVALID for unknown flag bits; both before the device. */
+int kc_worldmap_set_distance(kc_worldmap *ctx, int reach, unsigned int flags);
+/* any pointer may be NULL.  reach 0: off (and KC_OK).  last_box: (i_min, j_min, i_max, j_max)
+ * the last refresh recomputed, all -1 when it found the dirty box empty or none has run since
+ * kc_worldmap_set_distance; *last_full: whether that box was the whole map. */
+int kc_worldmap_distance_info(kc_worldmap *ctx, int *reach_out, unsigned int *flags_out, int last_box[4], int *last_full_out);
+/* queues the refresh on the map's stream; the host does not wait.  KC_ERR_STATE while off,
+ * as for the two below. */
+int kc_worldmap_distance_refresh(kc_worldmap *ctx);
+/* refreshes, then copies the plane; cap: the cells out holds (KC_ERR_RANGE below W H) */
+int kc_worldmap_get_distance(kc_worldmap *ctx, uint16_t *out, size_t cap);
+/* refreshes and returns with the plane complete; *ptr: uint16 [W x H] on the device, valid
+ * until the next kc_worldmap_set_distance or the context's destruction */
+int kc_worldmap_distance_device(kc_worldmap *ctx, void **ptr);
+
+/* Rule 44, endpoint: for the particle after rule 31's step and rule 22's (dx, dy) of its heading
+ * and beam k: X0 = TX + 2^15, EX = X0 + ((zq_k dx + 2^29) >> 30), EY alike, I = EX >> 16, J = EY
+ * >> 16 (arithmetic shifts; |zq_k dx| < 2^58).
+ * Rule 45, penalty: d2 = dist2[I + J W] inside the map, FAR outside; cost_p = sum over the
+ * beams with 0 <= zq_k < ZMAX of (d2 <= c2 ? pen_d2[d2] : pen_far).  A beam with zq_k == ZMAX
+ * (no return) or -1 contributes nothing.  pen_d2: c2 + 1 uint16 entries, 1 <= c2 <= min(reach^2,
+ * 4095).  Rules 35 to 41 apply unchanged.
+ * kc_mcl_field_check (host only), in this order: kc_mcl_check's refusals up to Rc; pen_d2
+ * (skipped when NULL): KC_ERR_INVALID below 2 entries, KC_ERR_RANGE above 4096; reach (skipped
+ * when 0): KC_ERR_RANGE outside 1 .. 254, KC_ERR_INVALID for n_pen - 1 > reach^2; wtab as
+ * kc_mcl_check; KC_ERR_INVALID for flag bits other than KC_MCL_SKIP_NO_RETURN (the plane's own
+ * flag decides what blocks: KC_SCAN_UNKNOWN_BLOCKS is refused). */
+#define KC_MCL_MODEL_NONE 0
+#define KC_MCL_MODEL_BEAM 1
+#define KC_MCL_MODEL_FIELD 2
+int kc_mcl_field_check(float resolution, size_t n_particles, size_t n_beams, float range_max, const uint16_t *pen_d2_or_null,
+                       size_t n_pen, int reach, const uint32_t *wtab_or_null, size_t n_wtab, int w_shift, unsigned int flags,
+                       int32_t *rc_out, int64_t *zmax_out);
+/* The field model: pen_d2 (n = c2 + 1 entries), pen_far and rule 36's table, checked as
+ * kc_mcl_field_check does with reach 0.  kc_mcl_step then runs rules 44 and 45 in place of 32
+ * to 34, until kc_mcl_set_model switches back; the particles survive either switch, the last
+ * step's weights do not.  A field step is two launches and the read-back, plus the plane's
+ * refresh when its dirty box is not empty.  It answers KC_ERR_INVALID for
+ * KC_SCAN_UNKNOWN_BLOCKS in its flags, and KC_ERR_STATE (after a step's other checks, before
+ * anything is queued) while the map's plane is off or c2 > reach^2. */
+int kc_mcl_set_field_model(kc_mcl *ctx, const uint16_t *pen_d2, size_t n, uint16_t pen_far, const uint32_t *wtab, size_t n_wtab,
+                           int w_shift);
+/* KC_MCL_MODEL_*: what kc_mcl_step runs */
+int kc_mcl_model_kind(kc_mcl *ctx, int *kind_out);
+
 #ifdef __cplusplus
 }
 #endif

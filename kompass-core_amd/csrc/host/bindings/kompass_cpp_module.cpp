@@ -1108,6 +1108,21 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return a;
            }, py::arg("poses"), py::arg("angles"), py::arg("range_max"), py::arg("unknown_blocks") = false,
            "The same for a batch of poses (x, y, yaw) in one launch: float64 [M, B]")
+      .def("enable_distance", &Mapping::WorldMap::enableDistance, py::arg("reach"), py::arg("unknown_blocks") = false,
+           "Keep the distance plane at `reach` cells (1 .. 254; 0: off): DESIGN.md 4.11 rules 42 and 43")
+      .def_property_readonly("distance_reach", &Mapping::WorldMap::distanceReach)
+      .def("distance_field", [](const Mapping::WorldMap &m) {
+             const std::vector<uint16_t> v = m.distanceField();
+             py::array_t<uint16_t, py::array::f_style> a({static_cast<py::ssize_t>(m.width()), static_cast<py::ssize_t>(m.height())});
+             std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(uint16_t));
+             return a;
+           }, "the refreshed distance plane, uint16 [width, height]: squared cells to the nearest blocking cell, 0xFFFF beyond reach")
+      .def("distance_last_box", [](const Mapping::WorldMap &m) {
+             const auto b = m.distanceLastBox();
+             return py::make_tuple(b[0], b[1], b[2], b[3]);
+           }, "(i_min, j_min, i_max, j_max) the last refresh recomputed; all -1 when it had nothing to do")
+      .def("device_distance_ptr", [](const Mapping::WorldMap &m) { return reinterpret_cast<uintptr_t>(m.deviceDistance()); },
+           "the refreshed plane's device address: uint16, (width, height), column-major")
       .def("get_cls", [plane](const Mapping::WorldMap &m) { return plane(m.cls(), m.width(), m.height()); },
            "the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied")
       .def("get_evidence", [plane](const Mapping::WorldMap &m) { return plane(m.evidence(), m.width(), m.height()); },
@@ -1181,6 +1196,48 @@ PYBIND11_MODULE(kompass_cpp, m) {
                t.w_shift = w_shift;
                m.setTables(t);
              }, py::arg("pen"), py::arg("err_shift"), py::arg("wtab"), py::arg("w_shift"))
+        .def("set_field_model", [](MCL &m, double sigma_hit, int reach, double floor, double pen_scale, int w_shift, int n_w,
+                                   uint32_t wtab0, double temperature) {
+               MCL::FieldModel d;
+               d.sigma_hit = sigma_hit;
+               d.reach = reach;
+               d.floor = floor;
+               d.pen_scale = pen_scale;
+               d.w_shift = w_shift;
+               d.n_w = n_w;
+               d.wtab0 = wtab0;
+               d.temperature = temperature;
+               m.setFieldModel(d);
+             }, py::arg("sigma_hit") = 0.1, py::arg("reach") = 0, py::arg("floor") = 0.05, py::arg("pen_scale") = 64.0,
+             py::arg("w_shift") = 4, py::arg("n_w") = 1024, py::arg("wtab0") = 1u << 16, py::arg("temperature") = 256.0,
+             "The likelihood-field model (rules 44 and 45) and its tables (judgement); enables the map's distance plane if needed")
+        .def("set_field_tables", [](MCL &m, const std::vector<uint16_t> &pen_d2, uint16_t pen_far, int reach,
+                                    const std::vector<uint32_t> &wtab, int w_shift) {
+               MCL::FieldTables t;
+               t.pen_d2 = pen_d2;
+               t.pen_far = pen_far;
+               t.reach = reach;
+               t.wtab = wtab;
+               t.w_shift = w_shift;
+               m.setFieldTables(t);
+             }, py::arg("pen_d2"), py::arg("pen_far"), py::arg("reach"), py::arg("wtab"), py::arg("w_shift"))
+        .def_property_readonly("field_model", &MCL::fieldModel)
+        .def_static("field_tables", [](float resolution, double sigma_hit, int reach, double floor, double pen_scale, int w_shift,
+                                       int n_w, uint32_t wtab0, double temperature) {
+               MCL::FieldModel d;
+               d.sigma_hit = sigma_hit;
+               d.reach = reach;
+               d.floor = floor;
+               d.pen_scale = pen_scale;
+               d.w_shift = w_shift;
+               d.n_w = n_w;
+               d.wtab0 = wtab0;
+               d.temperature = temperature;
+               const MCL::FieldTables t = MCL::fieldTables(resolution, d);
+               return py::make_tuple(t.pen_d2, t.pen_far, t.reach, t.wtab, t.w_shift);
+             }, py::arg("resolution"), py::arg("sigma_hit") = 0.1, py::arg("reach") = 0, py::arg("floor") = 0.05,
+             py::arg("pen_scale") = 64.0, py::arg("w_shift") = 4, py::arg("n_w") = 1024, py::arg("wtab0") = 1u << 16,
+             py::arg("temperature") = 256.0, "(pen_d2, pen_far, reach, wtab, w_shift) of a field model; needs no device")
         .def("set_motion_noise", &MCL::setMotionNoise, py::arg("sigma_forward"), py::arg("sigma_lateral"), py::arg("sigma_yaw"))
         .def("set_resample_ratio", &MCL::setResampleRatio, py::arg("num"), py::arg("den"))
         .def("set_flags", &MCL::setFlags, py::arg("unknown_blocks") = false, py::arg("skip_no_return") = false)

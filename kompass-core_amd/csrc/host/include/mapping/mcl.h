@@ -37,6 +37,26 @@ class MCL {
     std::vector<uint32_t> wtab;
     int w_shift = 0;
   };
+  // The likelihood-field model (rules 44 and 45).  Judgement as well:
+  //   pen_d2[d] = lrint(pen_scale * -log(floor + (1 - floor) exp(-d / (2 sigma_cells^2)))), d the squared distance in
+  //               cells, 0 .. c2 = reach^2, sigma_cells = sigma_hit / resolution
+  //   pen_far   = lrint(pen_scale * -log(floor))
+  //   reach 0: ceil(3 sigma_hit / resolution) clipped to 1 .. 63; wtab as Model's
+  struct FieldModel {
+    double sigma_hit = 0.1;
+    int reach = 0;
+    double floor = 0.05, pen_scale = 64.0;
+    int w_shift = 4, n_w = 1024;
+    uint32_t wtab0 = 1u << 16;
+    double temperature = 256.0;
+  };
+  struct FieldTables {
+    std::vector<uint16_t> pen_d2;
+    uint16_t pen_far = 0;
+    int reach = 0;
+    std::vector<uint32_t> wtab;
+    int w_shift = 0;
+  };
   struct Estimate {
     double x = 0.0, y = 0.0, yaw = 0.0;  // rule 39
     double n_eff = 0.0;                  // W1^2 / W2
@@ -56,6 +76,12 @@ class MCL {
 
   void setModel(const Model &m);
   void setTables(const Tables &t);
+  // Switches to the field model; setModel / setTables switch back.  The particles survive.  When the map's distance
+  // plane is off, or its reach is below the tables', it is enabled at the tables' reach (unknown_blocks as setFlags
+  // last said).  The map is the caller's: the const reference is a promise not to change its cells, which holds.
+  void setFieldModel(const FieldModel &m);
+  void setFieldTables(const FieldTables &t);
+  bool fieldModel() const { return field_; }
   // sigmas of the noise a step adds: metres forward and lateral, radians of heading
   void setMotionNoise(double sigma_forward, double sigma_lateral, double sigma_yaw);
   // resample when n_eff < N num / den (default 1 / 2); num = 0: never
@@ -86,6 +112,7 @@ class MCL {
   // (d_f, d_l, d_h): the displacement from -> to in from's frame in 2^-16 cells, the turn in heading units
   static std::array<int64_t, 3> odometryIncrement(float resolution, const std::array<double, 3> &from, const std::array<double, 3> &to);
   static Tables sensorTables(float resolution, const Model &m);
+  static FieldTables fieldTables(float resolution, const FieldModel &m);
   static Estimate estimateOf(const kc_mcl_record &r, float resolution, double origin_x, double origin_y);
   static bool shouldResample(const kc_mcl_record &r, size_t n, uint32_t num, uint32_t den);
 
@@ -101,6 +128,7 @@ class MCL {
   uint32_t r_num_ = 1, r_den_ = 2;
   unsigned flags_ = 0;
   bool spread_ = true;
+  bool field_ = false;
 
   double spreadOf(const Estimate &e) const;
 };

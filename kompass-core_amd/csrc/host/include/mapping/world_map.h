@@ -85,6 +85,19 @@ class WorldMap {
   std::vector<double> scanCells(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
                                 bool unknown_blocks, std::vector<int32_t> &cells_out) const;
 
+  // The distance plane (DESIGN.md 4.11 rules 42 and 43), off by default: per cell the squared distance in cells to the
+  // nearest OCCUPIED cell (with unknown_blocks also a never-observed one) within `reach` cells, KC_WORLDMAP_DIST_FAR
+  // beyond.  Kept lazily: an update only notes its changed box, whoever reads the plane refreshes that box grown by
+  // reach.  reach 0 switches it off and frees it.  std::out_of_range for a reach outside 0 .. 254.
+  void enableDistance(int reach, bool unknown_blocks = false);
+  int distanceReach() const;
+  // a refreshed copy, width x height as the map; std::runtime_error while the plane is off
+  std::vector<uint16_t> distanceField() const;
+  // the refreshed plane on the device: uint16, width x height; valid until the next enableDistance
+  const void *deviceDistance() const;
+  // (i_min, j_min, i_max, j_max) the last refresh recomputed, all -1 when it had nothing to do
+  std::array<int, 4> distanceLastBox() const;
+
   // copies of the planes, width x height as the map
   std::vector<int8_t> cls() const;
   std::vector<int8_t> evidence() const;

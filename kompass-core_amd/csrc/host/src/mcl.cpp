@@ -83,6 +83,36 @@ MCL::Tables MCL::sensorTables(float resolution, const Model &m) {
   return t;
 }
 
+MCL::FieldTables MCL::fieldTables(float resolution, const FieldModel &m) {
+  if (!(m.sigma_hit > 0.0) || !(m.floor > 0.0 && m.floor < 1.0) || !(m.pen_scale > 0.0) || !(m.temperature > 0.0) || m.n_w < 1 ||
+      m.w_shift < 0 || m.w_shift > 30 || m.reach < 0 || m.reach > 63)
+    throw std::invalid_argument("field model out of range");
+  FieldTables t;
+  const double sig = m.sigma_hit / static_cast<double>(resolution);  // cells
+  t.reach = m.reach;
+  if (t.reach == 0) {
+    const double r = std::ceil(3.0 * sig);
+    t.reach = r < 1.0 ? 1 : (r > 63.0 ? 63 : static_cast<int>(r));
+  }
+  const int c2 = t.reach * t.reach;
+  for (int d = 0; d <= c2; ++d) {
+    const double v = std::nearbyint(m.pen_scale * -std::log(m.floor + (1.0 - m.floor) * std::exp(-static_cast<double>(d) / (2.0 * sig * sig))));
+    t.pen_d2.push_back(static_cast<uint16_t>(v > 65535.0 ? 65535.0 : v));
+  }
+  const double far = std::nearbyint(m.pen_scale * -std::log(m.floor));
+  t.pen_far = static_cast<uint16_t>(far > 65535.0 ? 65535.0 : far);
+  Model w;
+  w.w_shift = m.w_shift;
+  w.n_w = m.n_w;
+  w.wtab0 = m.wtab0;
+  w.temperature = m.temperature;
+  w.n_pen = 1;
+  const Tables wt = sensorTables(resolution, w);
+  t.wtab = wt.wtab;
+  t.w_shift = wt.w_shift;
+  return t;
+}
+
 MCL::Estimate MCL::estimateOf(const kc_mcl_record &r, float resolution, double origin_x, double origin_y) {
   if (r.w1 == 0) throw std::invalid_argument("a record without weight");
   Estimate e;
@@ -109,6 +139,20 @@ void MCL::setModel(const Model &m) { setTables(sensorTables(map_.resolution(), m
 void MCL::setTables(const Tables &t) {
   hip::check(kc_mcl_set_model(ctx_.get(), t.pen.data(), t.pen.size(), t.err_shift, t.wtab.data(), t.wtab.size(), t.w_shift));
   tables_ = t;
+  field_ = false;
+}
+
+void MCL::setFieldModel(const FieldModel &m) { setFieldTables(fieldTables(map_.resolution(), m)); }
+
+void MCL::setFieldTables(const FieldTables &t) {
+  hip::check(kc_mcl_field_check(map_.resolution(), n_, beams_, range_max_, t.pen_d2.data(), t.pen_d2.size(), t.reach, t.wtab.data(),
+                                t.wtab.size(), t.w_shift, 0u, nullptr, nullptr));
+  hip::check(kc_mcl_set_field_model(ctx_.get(), t.pen_d2.data(), t.pen_d2.size(), t.pen_far, t.wtab.data(), t.wtab.size(), t.w_shift));
+  if (map_.distanceReach() < t.reach)
+    hip::check(kc_worldmap_set_distance(map_.hipContext(), t.reach, (flags_ & KC_SCAN_UNKNOWN_BLOCKS) ? KC_WORLDMAP_DIST_UNKNOWN_BLOCKS : 0u));
+  tables_.wtab = t.wtab;  // what spreadOf reads
+  tables_.w_shift = t.w_shift;
+  field_ = true;
 }
 
 void MCL::setMotionNoise(double sigma_forward, double sigma_lateral, double sigma_yaw) {
@@ -144,8 +188,10 @@ size_t MCL::initGlobal() {
 MCL::Estimate MCL::step(const std::array<double, 3> &from, const std::array<double, 3> &to, const std::vector<double> &ranges) {
   if (ranges.size() != beams_) throw std::invalid_argument("one range a beam");
   const auto d = odometryIncrement(map_.resolution(), from, to);
+  // the field model's plane has its own flag for what blocks (rule 45)
+  const unsigned flags = field_ ? (flags_ & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS)) : flags_;
   return stepQuantised(d[0], d[1], static_cast<int32_t>(d[2]), s_f_, s_l_, s_h_,
-                       quantiseRanges(ranges, map_.resolution(), range_max_, flags_), flags_, true);
+                       quantiseRanges(ranges, map_.resolution(), range_max_, flags), flags, true);
 }
 
 MCL::Estimate MCL::stepQuantised(int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, int32_t s_l, int32_t s_h,

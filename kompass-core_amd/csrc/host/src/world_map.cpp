@@ -161,6 +161,34 @@ std::vector<double> WorldMap::scanCells(double x, double y, double yaw, const st
   return scanPoses({{x, y, yaw}}, angles, range_max, unknown_blocks, &cells_out);
 }
 
+void WorldMap::enableDistance(int reach, bool unknown_blocks) {
+  hip::check(kc_worldmap_set_distance(ctx_.get(), reach, (reach != 0 && unknown_blocks) ? KC_WORLDMAP_DIST_UNKNOWN_BLOCKS : 0u));
+}
+
+int WorldMap::distanceReach() const {
+  int reach = 0;
+  hip::check(kc_worldmap_distance_info(ctx_.get(), &reach, nullptr, nullptr, nullptr));
+  return reach;
+}
+
+std::vector<uint16_t> WorldMap::distanceField() const {
+  std::vector<uint16_t> out(static_cast<size_t>(width_) * static_cast<size_t>(height_));
+  hip::check(kc_worldmap_get_distance(ctx_.get(), out.data(), out.size()));
+  return out;
+}
+
+const void *WorldMap::deviceDistance() const {
+  void *p = nullptr;
+  hip::check(kc_worldmap_distance_device(ctx_.get(), &p));
+  return p;
+}
+
+std::array<int, 4> WorldMap::distanceLastBox() const {
+  int b[4] = {-1, -1, -1, -1};
+  hip::check(kc_worldmap_distance_info(ctx_.get(), nullptr, nullptr, b, nullptr));
+  return {b[0], b[1], b[2], b[3]};
+}
+
 std::vector<int8_t> WorldMap::cls() const {
   std::vector<int8_t> out(static_cast<size_t>(width_) * static_cast<size_t>(height_));
   hip::check(kc_worldmap_get(ctx_.get(), out.data(), nullptr, out.size()));

@@ -355,6 +355,15 @@ struct WorldMapView {
   int device;
 };
 int worldmap_view(kc_worldmap *m, WorldMapView *out);
+// the map's distance plane (rules 42 and 43) for a reader on another stream: reach 0 and a null plane while it is off
+struct WorldMapDistance {
+  const uint16_t *dist2;  // [W x H] as cls
+  int reach;
+};
+// host only: queues nothing
+int worldmap_distance_state(kc_worldmap *m, WorldMapDistance *out);
+// queues rule 43's refresh on the map's stream when the dirty box is not empty; the reader then waits for that stream
+int worldmap_distance_refresh(kc_worldmap *m);
 // rule 16's window, and the number of map cells inside rule 17's disc: the most points a list of it can hold
 struct WorldMapWindow {
   int ic, jc, rc;

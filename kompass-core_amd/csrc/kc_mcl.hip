@@ -1,4 +1,4 @@
-// Monte-Carlo localisation over the world map (kc_mcl_*; DESIGN.md 4.11 rules 28 to 41).
+// Monte-Carlo localisation over the world map (kc_mcl_*; DESIGN.md 4.11 rules 28 to 41, 44 and 45).
 //
 // Nothing in the reference to restate: it leaves localisation, like the world map, to its ROS side.  N particles
 // (TX, TY, h, acc) live on the device; a step advances them by an odometry increment with counter-based integer noise,
@@ -14,6 +14,9 @@
 //      stores it into the NEW one, so no ray reads what another writes.  pen lies in LDS.  A wavefront reduces the
 //      penalties of equal particles by a segmented shuffle-down (the segments are contiguous), each segment's first lane
 //      adds its sum to cost[p] with one uint32 atomic: integer adds only, exact in any order.
+//  (a') mcl_field_kernel (rules 44 and 45, after kc_mcl_set_field_model) in its place: the same lane order, predict step
+//      (mcl_predict) and segmented sum (mcl_segment_add); a ray looks its endpoint's cell up in the map's distance plane,
+//      one 2-byte load behind the bounds test, pen_d2 in LDS.
 //  (b) mcl_weigh_kernel: one workgroup of 1024.  Pass 1 forms acc and the packed minimum (acc << 32 | p: the lowest
 //      index among equals), pass 2 the weights and the record's sums.  w (x - x_best) can reach 2^57 and 65536 of them
 //      2^73: each product is split into its low 32 bits and the rest, both summed in 64 bits and joined once at the end.
@@ -66,17 +69,62 @@ struct MclState {  // one of the two state buffers
   unsigned *h;
 };
 
-struct MclWalkArgs {
-  const int8_t *cls;
-  const int2 *table;    // rule 21: (ac, as) a beam
+// what rule 31 needs, shared by both sensor models' kernels
+struct MclPredictArgs {
   const int2 *heading;  // rule 29: (Cq, Sq) a heading
   MclState in, out;
+  unsigned long long key;
+  long long d_f, d_l;
+  int d_h, s_f, s_l, s_h;
+};
+
+// rule 31 for particle p from the OLD state buffer, the heading before the step; the ray of beam 0 stores it into the
+// NEW one, so no ray reads what another writes
+__device__ __forceinline__ kc_worldmap_pose mcl_predict(const MclPredictArgs &a, int p, bool store) {
+  const unsigned h0 = a.in.h[p];
+  const int2 cs0 = a.heading[h0];
+  const long long C = cs0.x, S = cs0.y;
+  const long long F = a.d_f + mcl_noise(mcl_draw(a.key, p, 0), a.s_f);
+  const long long L = a.d_l + mcl_noise(mcl_draw(a.key, p, 1), a.s_l);
+  kc_worldmap_pose pose;
+  pose.tx = mcl_clamp(a.in.tx[p] + ((C * F - S * L + (1ll << 15)) >> 16));
+  pose.ty = mcl_clamp(a.in.ty[p] + ((S * F + C * L + (1ll << 15)) >> 16));
+  const unsigned h1 =
+      static_cast<unsigned>((static_cast<long long>(h0) + a.d_h + mcl_noise(mcl_draw(a.key, p, 2), a.s_h)) & 0xFFFF);
+  const int2 cs1 = a.heading[h1];
+  pose.cq = cs1.x;
+  pose.sq = cs1.y;
+  if (store) {
+    a.out.tx[p] = pose.tx;
+    a.out.ty[p] = pose.ty;
+    a.out.h[p] = h1;
+  }
+  return pose;
+}
+
+// The penalties c of the rays of equal particles p (contiguous lanes; -1: no ray) summed over the wavefront by a
+// segmented shuffle-down; each segment's first lane adds its sum to cost[p] with one uint32 atomic.  Every lane of the
+// wavefront calls it.
+__device__ __forceinline__ void mcl_segment_add(unsigned *cost, int p, unsigned c, bool live) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned c2 = __shfl_down(c, off);
+    const int p2 = __shfl_down(p, off);
+    if (lane + off < 64 && p2 == p) c += c2;
+  }
+  const int before = __shfl_up(p, 1);
+  if (live && (lane == 0 || before != p)) atomicAdd(&cost[p], c);
+}
+
+struct MclWalkArgs {
+  MclPredictArgs pre;
+  const int8_t *cls;
+  const int2 *table;    // rule 21: (ac, as) a beam
   const int *zq;        // rule 33
   const unsigned short *pen;
   unsigned *cost;
-  unsigned long long key;
-  long long d_f, d_l, zmax;
-  int d_h, s_f, s_l, s_h;
+  long long zmax;
   int W, H, N, B, rc, unknown_blocks, E, err_shift;
 };
 
@@ -91,25 +139,7 @@ __global__ __launch_bounds__(kMclBlock) void mcl_walk_kernel(MclWalkArgs a) {
   if (live) {
     p = static_cast<int>(ray / static_cast<unsigned>(a.B));
     const int k = static_cast<int>(ray - static_cast<unsigned>(p) * static_cast<unsigned>(a.B));
-    // rule 31, from the heading before the step
-    const unsigned h0 = a.in.h[p];
-    const int2 cs0 = a.heading[h0];
-    const long long C = cs0.x, S = cs0.y;
-    const long long F = a.d_f + mcl_noise(mcl_draw(a.key, p, 0), a.s_f);
-    const long long L = a.d_l + mcl_noise(mcl_draw(a.key, p, 1), a.s_l);
-    kc_worldmap_pose pose;
-    pose.tx = mcl_clamp(a.in.tx[p] + ((C * F - S * L + (1ll << 15)) >> 16));
-    pose.ty = mcl_clamp(a.in.ty[p] + ((S * F + C * L + (1ll << 15)) >> 16));
-    const unsigned h1 =
-        static_cast<unsigned>((static_cast<long long>(h0) + a.d_h + mcl_noise(mcl_draw(a.key, p, 2), a.s_h)) & 0xFFFF);
-    const int2 cs1 = a.heading[h1];
-    pose.cq = cs1.x;
-    pose.sq = cs1.y;
-    if (k == 0) {
-      a.out.tx[p] = pose.tx;
-      a.out.ty[p] = pose.ty;
-      a.out.h[p] = h1;
-    }
+    const kc_worldmap_pose pose = mcl_predict(a.pre, p, k == 0);
     const long long zq = a.zq[k];
     if (zq >= 0) {  // rule 33: -1 contributes nothing
       // rule 32: q > ZMAX iff e 2^30 >= (ZMAX + 1) a; both sides below 2^59
@@ -127,16 +157,48 @@ __global__ __launch_bounds__(kMclBlock) void mcl_walk_kernel(MclWalkArgs a) {
       c = s_pen[bin < a.E - 1 ? bin : a.E - 1];
     }
   }
-  // equal particles are contiguous lanes: after the steps the first lane of a segment holds the segment's sum
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned c2 = __shfl_down(c, off);
-    const int p2 = __shfl_down(p, off);
-    if (lane + off < 64 && p2 == p) c += c2;
+  mcl_segment_add(a.cost, p, c, live);
+}
+
+struct MclFieldArgs {
+  MclPredictArgs pre;
+  const unsigned short *dist2;  // rule 42's plane, refreshed
+  const int2 *table;
+  const int *zq;
+  const unsigned short *pen_d2;  // c2 + 1 entries
+  unsigned *cost;
+  long long zmax;
+  int W, H, N, B, c2;
+  unsigned pen_far;
+};
+
+// rules 44 and 45 in mcl_walk_kernel's lane order: one 2-byte load of the plane a ray, behind its bounds test
+__global__ __launch_bounds__(kMclBlock) void mcl_field_kernel(MclFieldArgs a) {
+  __shared__ unsigned short s_pen[KC_MCL_MAX_TABLE];
+  for (int i = threadIdx.x; i <= a.c2; i += kMclBlock) s_pen[i] = a.pen_d2[i];
+  __syncthreads();
+  const unsigned ray = blockIdx.x * kMclBlock + threadIdx.x;  // N B <= 2^22
+  const bool live = ray < static_cast<unsigned>(a.N) * static_cast<unsigned>(a.B);
+  int p = -1;
+  unsigned c = 0;
+  if (live) {
+    p = static_cast<int>(ray / static_cast<unsigned>(a.B));
+    const int k = static_cast<int>(ray - static_cast<unsigned>(p) * static_cast<unsigned>(a.B));
+    const kc_worldmap_pose pose = mcl_predict(a.pre, p, k == 0);
+    const long long zq = a.zq[k];
+    if (zq >= 0 && zq < a.zmax) {  // rule 45: a beam without a return says nothing about an endpoint
+      const int2 t = a.table[k];
+      // rule 22
+      const long long dx = (static_cast<long long>(pose.cq) * t.x - static_cast<long long>(pose.sq) * t.y + (1ll << 15)) >> 16;
+      const long long dy = (static_cast<long long>(pose.sq) * t.x + static_cast<long long>(pose.cq) * t.y + (1ll << 15)) >> 16;
+      const long long I = (pose.tx + (1ll << 15) + ((zq * dx + (1ll << 29)) >> 30)) >> 16;
+      const long long J = (pose.ty + (1ll << 15) + ((zq * dy + (1ll << 29)) >> 30)) >> 16;
+      unsigned d2 = KC_WORLDMAP_DIST_FAR;
+      if (I >= 0 && I < a.W && J >= 0 && J < a.H) d2 = a.dist2[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)];
+      c = d2 <= static_cast<unsigned>(a.c2) ? s_pen[d2] : a.pen_far;
+    }
   }
-  const int before = __shfl_up(p, 1);
-  if (live && (lane == 0 || before != p)) atomicAdd(&a.cost[p], c);
+  mcl_segment_add(a.cost, p, c, live);
 }
 
 // ---- sums over one workgroup of kMclOne: wavefront shuffles, then the 16 partials through LDS ----
@@ -380,13 +442,15 @@ struct kc_mcl {
   DevBuf<unsigned short> d_pen;
   DevBuf<unsigned> d_wtab;
   int E = 0, err_shift = 0, EW = 0, w_shift = 0;
+  int kind = KC_MCL_MODEL_NONE;  // what a step runs; d_pen holds pen (beam) or pen_d2 (field: E = c2 + 1)
+  unsigned pen_far = 0;
   DevBuf<int> d_zq;
   PinBuf<int> h_zq;
   DevBuf<kc_mcl_record> d_rec;
   PinBuf<kc_mcl_record> h_rec;
   DevBuf<unsigned> d_rows;  // global init: scratch grown on demand and kept
   DevBuf<unsigned long long> d_before;
-  bool have_model = false, inited = false, have_weights = false;
+  bool inited = false, have_weights = false;
   unsigned long long w1 = 0;  // of the last step
   Timing step_time, resample_time;
 
@@ -440,6 +504,47 @@ int mcl_check(float res, size_t N, size_t B, float range_max, const uint16_t *pe
     KC_FAIL(KC_ERR_INVALID, "unknown localiser flag bits 0x%x", flags);
   if (rc_out) *rc_out = rc;
   if (zmax_out) *zmax_out = std::llrint(static_cast<double>(range_max) / static_cast<double>(res) * 65536.0);
+  return KC_OK;
+}
+
+// kc_mcl_field_check's order: rule 38's up to Rc, pen_d2, the reach, wtab, the flags
+int mcl_field_check(float res, size_t N, size_t B, float range_max, const uint16_t *pen_d2, size_t n_pen, int reach,
+                    const uint32_t *wtab, size_t EW, int w_shift, unsigned flags, int *rc_out, long long *zmax_out) {
+  KC_TRY(mcl_check(res, N, B, range_max, nullptr, 0, 0, nullptr, 0, 0, 0u, rc_out, zmax_out));
+  if (pen_d2) {
+    if (n_pen < 2) KC_FAIL(KC_ERR_INVALID, "a field penalty table needs c2 + 1 >= 2 entries, got %zu", n_pen);
+    if (n_pen > KC_MCL_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu penalty entries are above the cap of %d", n_pen, KC_MCL_MAX_TABLE);
+    if (reach != 0) {
+      if (reach < 1 || reach > KC_WORLDMAP_DIST_MAX_REACH)
+        KC_FAIL(KC_ERR_RANGE, "reach must be in 1 .. %d cells, got %d", KC_WORLDMAP_DIST_MAX_REACH, reach);
+      if (n_pen - 1 > static_cast<size_t>(reach) * static_cast<size_t>(reach))
+        KC_FAIL(KC_ERR_INVALID, "c2 = %zu is above reach^2 = %d", n_pen - 1, reach * reach);
+    }
+  }
+  KC_TRY(mcl_check(res, N, B, range_max, nullptr, 0, 0, wtab, EW, w_shift, 0u, nullptr, nullptr));
+  if (flags & ~static_cast<unsigned>(KC_MCL_SKIP_NO_RETURN))
+    KC_FAIL(KC_ERR_INVALID, "a field step takes KC_MCL_SKIP_NO_RETURN alone, got flag bits 0x%x", flags);
+  return KC_OK;
+}
+
+// rules 34 / 45 and 36's tables onto the device; the particles stay
+int mcl_take_tables(kc_mcl *c, int kind, const uint16_t *pen, size_t n_pen, int err_shift, unsigned pen_far, const uint32_t *wtab,
+                    size_t n_wtab, int w_shift) {
+  KC_HIP(hipSetDevice(c->device));
+  c->kind = KC_MCL_MODEL_NONE;
+  KC_TRY(c->d_pen.reserve(n_pen));
+  KC_TRY(c->d_wtab.reserve(n_wtab));
+  // from the caller's memory: the copies return once the source may be reused or, as here, after the drain
+  KC_HIP(hipMemcpyAsync(c->d_pen.p, pen, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipMemcpyAsync(c->d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->E = static_cast<int>(n_pen);
+  c->err_shift = err_shift;
+  c->pen_far = pen_far;
+  c->EW = static_cast<int>(n_wtab);
+  c->w_shift = w_shift;
+  c->kind = kind;
+  c->have_weights = false;  // weights of another table
   return KC_OK;
 }
 
@@ -554,20 +659,35 @@ int kc_mcl_set_model(kc_mcl *c, const uint16_t *pen, size_t n_pen, int err_shift
   WorldMapView v{};
   KC_TRY(worldmap_view(c->map, &v));
   KC_TRY(mcl_check(v.res, c->N, c->B, c->range_max, pen, n_pen, err_shift, wtab, n_wtab, w_shift, 0u, nullptr, nullptr));
-  KC_HIP(hipSetDevice(c->device));
-  c->have_model = false;
-  KC_TRY(c->d_pen.reserve(n_pen));
-  KC_TRY(c->d_wtab.reserve(n_wtab));
-  // from the caller's memory: the copies return once the source may be reused or, as here, after the drain
-  KC_HIP(hipMemcpyAsync(c->d_pen.p, pen, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipMemcpyAsync(c->d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));
-  c->E = static_cast<int>(n_pen);
-  c->err_shift = err_shift;
-  c->EW = static_cast<int>(n_wtab);
-  c->w_shift = w_shift;
-  c->have_model = true;
-  c->have_weights = false;  // weights of another table
+  return mcl_take_tables(c, KC_MCL_MODEL_BEAM, pen, n_pen, err_shift, 0u, wtab, n_wtab, w_shift);
+}
+
+int kc_mcl_field_check(float resolution, size_t n_particles, size_t n_beams, float range_max, const uint16_t *pen_d2_or_null,
+                       size_t n_pen, int reach, const uint32_t *wtab_or_null, size_t n_wtab, int w_shift, unsigned int flags,
+                       int32_t *rc_out, int64_t *zmax_out) {
+  if (rc_out) *rc_out = 0;
+  if (zmax_out) *zmax_out = 0;
+  int rc = 0;
+  long long zmax = 0;
+  KC_TRY(mcl_field_check(resolution, n_particles, n_beams, range_max, pen_d2_or_null, n_pen, reach, wtab_or_null, n_wtab, w_shift,
+                         flags, &rc, &zmax));
+  if (rc_out) *rc_out = rc;
+  if (zmax_out) *zmax_out = zmax;
+  return KC_OK;
+}
+
+int kc_mcl_set_field_model(kc_mcl *c, const uint16_t *pen_d2, size_t n, uint16_t pen_far, const uint32_t *wtab, size_t n_wtab,
+                           int w_shift) {
+  if (!c || !pen_d2 || !wtab) KC_FAIL(KC_ERR_INVALID, "null argument");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
+  KC_TRY(mcl_field_check(v.res, c->N, c->B, c->range_max, pen_d2, n, 0, wtab, n_wtab, w_shift, 0u, nullptr, nullptr));
+  return mcl_take_tables(c, KC_MCL_MODEL_FIELD, pen_d2, n, 0, pen_far, wtab, n_wtab, w_shift);
+}
+
+int kc_mcl_model_kind(kc_mcl *c, int *kind_out) {
+  if (!c || !kind_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *kind_out = c->kind;
   return KC_OK;
 }
 
@@ -623,59 +743,90 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
                 unsigned int flags, kc_mcl_record *out) {
   if (!c || !zq || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
   std::memset(out, 0, sizeof(*out));
-  if (!c->have_model) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_set_model first");
+  if (c->kind == KC_MCL_MODEL_NONE) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_set_model or kc_mcl_set_field_model first");
+  const bool field = c->kind == KC_MCL_MODEL_FIELD;
   if (!c->inited) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_init_pose or kc_mcl_init_global first");
   if (d_f < -kMclMaxOffset || d_f > kMclMaxOffset || d_l < -kMclMaxOffset || d_l > kMclMaxOffset)
     KC_FAIL(KC_ERR_RANGE, "the odometry increment is above 2^20 cells");
   if (s_f < 0 || s_l < 0 || s_h < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
   if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS | KC_MCL_SKIP_NO_RETURN))
     KC_FAIL(KC_ERR_INVALID, "unknown localiser flag bits 0x%x", flags);
+  if (field && (flags & KC_SCAN_UNKNOWN_BLOCKS))
+    KC_FAIL(KC_ERR_INVALID, "a field step takes no KC_SCAN_UNKNOWN_BLOCKS: the distance plane's own flag decides what blocks");
   for (size_t k = 0; k < c->B; ++k)
     if (!((zq[k] >= 0 && zq[k] <= c->zmax) || (zq[k] == -1 && (flags & KC_MCL_SKIP_NO_RETURN))))
       KC_FAIL(KC_ERR_INVALID, "quantised range %zu is %d, outside 0 .. %lld", k, zq[k], c->zmax);
   if (c->step == 0xFFFFFFFFu) KC_FAIL(KC_ERR_STATE, "the step counter is exhausted: init again");
   WorldMapView v{};
   KC_TRY(worldmap_view(c->map, &v));
+  WorldMapDistance dist{};
+  if (field) {  // rule 45's state, before anything is queued
+    KC_TRY(worldmap_distance_state(c->map, &dist));
+    if (dist.reach == 0) KC_FAIL(KC_ERR_STATE, "a field step needs the map's distance plane: kc_worldmap_set_distance");
+    if (c->E - 1 > dist.reach * dist.reach)
+      KC_FAIL(KC_ERR_STATE, "the field model's c2 = %d is above the plane's reach^2 = %d", c->E - 1, dist.reach * dist.reach);
+  }
   KC_HIP(hipSetDevice(c->device));
   std::memcpy(c->h_zq.p, zq, c->B * sizeof(int32_t));
   KC_HIP(hipMemcpyAsync(c->d_zq.p, c->h_zq.p, c->B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  if (field) KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
   KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
   const unsigned step = c->step + 1;
-  MclWalkArgs a{};
-  a.cls = v.cls;
-  a.table = reinterpret_cast<const int2 *>(c->table.d.p);
-  a.heading = c->d_heading.p;
-  a.in = c->state(c->cur);
-  a.out = c->state(c->cur ^ 1);
-  a.zq = c->d_zq.p;
-  a.pen = c->d_pen.p;
-  a.cost = c->d_cost.p;
-  a.key = mcl_key(c, step);
-  a.d_f = d_f;
-  a.d_l = d_l;
-  a.zmax = c->zmax;
-  a.d_h = d_h;
-  a.s_f = s_f;
-  a.s_l = s_l;
-  a.s_h = s_h;
-  a.W = v.W;
-  a.H = v.H;
-  a.N = static_cast<int>(c->N);
-  a.B = static_cast<int>(c->B);
-  a.rc = c->rc;
-  a.unknown_blocks = (flags & KC_SCAN_UNKNOWN_BLOCKS) ? 1 : 0;
-  a.E = c->E;
-  a.err_shift = c->err_shift;
+  MclPredictArgs pre{};
+  pre.heading = c->d_heading.p;
+  pre.in = c->state(c->cur);
+  pre.out = c->state(c->cur ^ 1);
+  pre.key = mcl_key(c, step);
+  pre.d_f = d_f;
+  pre.d_l = d_l;
+  pre.d_h = d_h;
+  pre.s_f = s_f;
+  pre.s_l = s_l;
+  pre.s_h = s_h;
   // from here on the particles are the new buffer's, whatever fails: a failed step asks for a new init
   c->inited = false;
   c->have_weights = false;
   c->step_time.begin_cycle();
   KC_TRY(c->step_time.start("walk", c->stream));
-  hipLaunchKernelGGL(mcl_walk_kernel, dim3(mcl_blocks(c->N * c->B)), dim3(kMclBlock), 0, c->stream, a);
+  if (field) {
+    MclFieldArgs a{};
+    a.pre = pre;
+    a.dist2 = dist.dist2;
+    a.table = reinterpret_cast<const int2 *>(c->table.d.p);
+    a.zq = c->d_zq.p;
+    a.pen_d2 = c->d_pen.p;
+    a.cost = c->d_cost.p;
+    a.zmax = c->zmax;
+    a.W = v.W;
+    a.H = v.H;
+    a.N = static_cast<int>(c->N);
+    a.B = static_cast<int>(c->B);
+    a.c2 = c->E - 1;
+    a.pen_far = c->pen_far;
+    hipLaunchKernelGGL(mcl_field_kernel, dim3(mcl_blocks(c->N * c->B)), dim3(kMclBlock), 0, c->stream, a);
+  } else {
+    MclWalkArgs a{};
+    a.pre = pre;
+    a.cls = v.cls;
+    a.table = reinterpret_cast<const int2 *>(c->table.d.p);
+    a.zq = c->d_zq.p;
+    a.pen = c->d_pen.p;
+    a.cost = c->d_cost.p;
+    a.zmax = c->zmax;
+    a.W = v.W;
+    a.H = v.H;
+    a.N = static_cast<int>(c->N);
+    a.B = static_cast<int>(c->B);
+    a.rc = c->rc;
+    a.unknown_blocks = (flags & KC_SCAN_UNKNOWN_BLOCKS) ? 1 : 0;
+    a.E = c->E;
+    a.err_shift = c->err_shift;
+    hipLaunchKernelGGL(mcl_walk_kernel, dim3(mcl_blocks(c->N * c->B)), dim3(kMclBlock), 0, c->stream, a);
+  }
   KC_HIP(hipGetLastError());
   KC_TRY(c->step_time.stop(c->stream));
   MclWeighArgs w{};
-  w.st = a.out;
+  w.st = pre.out;
   w.acc = c->d_acc.p;
   w.cost = c->d_cost.p;
   w.w = c->d_w.p;
@@ -683,7 +834,7 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
   w.wtab = c->d_wtab.p;
   w.heading = c->d_heading.p;
   w.rec = c->d_rec.p;
-  w.N = a.N;
+  w.N = static_cast<int>(c->N);
   w.EW = c->EW;
   w.w_shift = c->w_shift;
   w.step = step;

@@ -42,6 +42,13 @@
 //      order of arrival, and rule 19 leaves that open.  The launcher (kc_internal.h) queues it on a caller's stream
 //      into a caller's buffers, which is how the controller's translation unit reaches it.
 //
+//  (h) distance plane (rules 42 and 43; off by default).  dist2, a uint16 a cell: the squared distance in cells to the
+//      nearest blocking cell within `reach`.  Kept lazily behind a dirty box on the host: prior / clear mark the whole
+//      map, an update merges the changed box of the record it reads back anyway.  A refresh recomputes the box grown
+//      by reach: worldmap_dist_tile_kernel up to reach 63 (a workgroup a 64 x 64 tile; the tile and its halo once into
+//      LDS as blocking bytes, row distances and the column pass out of LDS, a uint16 store a lane), above it
+//      worldmap_dist_rows_kernel + worldmap_dist_cols_kernel over a uint8 scratch plane, in the planner's manner.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -453,6 +460,110 @@ __global__ __launch_bounds__(kWmScanBlock) void worldmap_scan_kernel(WmScanArgs 
   if (a.cells) a.cells[slot] = hit ? hit_i + hit_j * a.W : -1;
 }
 
+// ---- (h) the distance plane (rules 42 and 43) ----
+constexpr int kWmDistTile = 64;        // output cells a side of one workgroup's tile
+constexpr int kWmDistTiledReach = 63;  // above it the halo no longer fits: the two global passes below
+constexpr uint8_t kWmDistNone = 255;   // a row distance: no blocking cell within reach
+
+struct WmDistArgs {
+  const int8_t *cls;
+  uint16_t *dist2;
+  uint8_t *rowd;  // the fallback's scratch plane only
+  int W, H;
+  int x0, y0, x1, y1;  // the inclusive box to recompute, inside the map
+  int R, unknown_blocks;
+  unsigned R2;
+};
+
+__device__ __forceinline__ bool wm_dist_blocks(int8_t c, int unknown_blocks) {
+  return c == KC_OCCUPIED || (unknown_blocks && c == KC_UNEXPLORED);
+}
+
+// LDS bytes of a tile at reach R: the blocking bytes of (64 + 2 R)^2 cells, then 64 row distances for 64 + 2 R rows
+__host__ __device__ inline size_t wm_dist_lds(int R) {
+  const size_t side = static_cast<size_t>(kWmDistTile + 2 * R);
+  return side * side + static_cast<size_t>(kWmDistTile) * side;
+}
+
+// One workgroup a tile of at most 64 x 64 cells of the box.  Every cls byte of the tile and its halo is read from
+// global memory once, as a blocking byte into LDS (cells outside the map: 0, tested before the load); the row
+// distances of the tile's columns are formed in LDS for the tile's rows and the halo rows, the column pass runs out of
+// LDS, and a lane stores its own uint16.
+__global__ __launch_bounds__(kWmBlock) void worldmap_dist_tile_kernel(WmDistArgs a) {
+  extern __shared__ uint8_t wm_dist_smem[];
+  const int R = a.R;
+  const int tx0 = a.x0 + static_cast<int>(blockIdx.x) * kWmDistTile, ty0 = a.y0 + static_cast<int>(blockIdx.y) * kWmDistTile;
+  const int tw = min(kWmDistTile, a.x1 - tx0 + 1), th = min(kWmDistTile, a.y1 - ty0 + 1);
+  const int sw = tw + 2 * R, sh = th + 2 * R;  // the region with its halo
+  uint8_t *blk = wm_dist_smem;                 // [sh][sw]
+  uint8_t *rowd = wm_dist_smem + static_cast<size_t>(kWmDistTile + 2 * R) * static_cast<size_t>(kWmDistTile + 2 * R);  // [sh][64]
+  for (int k = threadIdx.x; k < sw * sh; k += kWmBlock) {
+    const int r = k / sw, c = k - r * sw;
+    const int I = tx0 - R + c, J = ty0 - R + r;
+    uint8_t b = 0;
+    if (I >= 0 && I < a.W && J >= 0 && J < a.H)
+      b = wm_dist_blocks(a.cls[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)], a.unknown_blocks) ? 1 : 0;
+    blk[k] = b;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < tw * sh; k += kWmBlock) {
+    const int r = k / tw, c = k - r * tw;
+    const uint8_t *row = blk + r * sw + c + R;  // the cell itself
+    int found = kWmDistNone;
+    for (int d = 0; d <= R; ++d)
+      if (row[-d] | row[d]) {
+        found = d;
+        break;
+      }
+    rowd[r * kWmDistTile + c] = static_cast<uint8_t>(found);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < tw * th; k += kWmBlock) {
+    const int r = k / tw, c = k - r * tw;
+    const uint8_t *col = rowd + (r + R) * kWmDistTile + c;
+    unsigned best = 0xFFFFFFFFu;
+    for (int dy = -R; dy <= R; ++dy) {
+      const unsigned d = col[dy * kWmDistTile];
+      if (d != kWmDistNone) best = min(best, d * d + static_cast<unsigned>(dy * dy));
+    }
+    a.dist2[static_cast<size_t>(tx0 + c) + static_cast<size_t>(ty0 + r) * static_cast<size_t>(a.W)] =
+        best <= a.R2 ? static_cast<uint16_t>(best) : static_cast<uint16_t>(KC_WORLDMAP_DIST_FAR);
+  }
+}
+
+// reach above kWmDistTiledReach, in the planner's manner: the row distances of the box's columns over the box's rows
+// grown by R (clipped to the map) into a scratch plane, then the column pass.  blockIdx.y: the row of the pass.
+__global__ __launch_bounds__(kWmBlock) void worldmap_dist_rows_kernel(WmDistArgs a) {
+  const int J = max(a.y0 - a.R, 0) + static_cast<int>(blockIdx.y);
+  const int8_t *row = a.cls + static_cast<size_t>(J) * static_cast<size_t>(a.W);
+  for (int I = a.x0 + static_cast<int>(blockIdx.x * kWmBlock + threadIdx.x); I <= a.x1; I += static_cast<int>(gridDim.x) * kWmBlock) {
+    int found = kWmDistNone;
+    for (int d = 0; d <= a.R; ++d) {
+      const bool l = I - d >= 0 && wm_dist_blocks(row[I - d], a.unknown_blocks);
+      const bool r = I + d < a.W && wm_dist_blocks(row[I + d], a.unknown_blocks);
+      if (l || r) {
+        found = d;
+        break;
+      }
+    }
+    a.rowd[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)] = static_cast<uint8_t>(found);
+  }
+}
+
+__global__ __launch_bounds__(kWmBlock) void worldmap_dist_cols_kernel(WmDistArgs a) {
+  const int J = a.y0 + static_cast<int>(blockIdx.y);
+  const int lo = max(-a.R, -J), hi = min(a.R, a.H - 1 - J);
+  for (int I = a.x0 + static_cast<int>(blockIdx.x * kWmBlock + threadIdx.x); I <= a.x1; I += static_cast<int>(gridDim.x) * kWmBlock) {
+    const size_t cell = static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W);
+    unsigned best = 0xFFFFFFFFu;
+    for (int dy = lo; dy <= hi; ++dy) {
+      const unsigned d = a.rowd[static_cast<long long>(cell) + static_cast<long long>(dy) * a.W];
+      if (d != kWmDistNone) best = min(best, d * d + static_cast<unsigned>(dy * dy));
+    }
+    a.dist2[cell] = best <= a.R2 ? static_cast<uint16_t>(best) : static_cast<uint16_t>(KC_WORLDMAP_DIST_FAR);
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -485,6 +596,32 @@ struct kc_worldmap {
   PinBuf<kc_worldmap_pose> h_poses;
   DevBuf<double> d_scan;           // the ranges, behind them the cells as int32: one read-back
   PinBuf<double> h_scan;
+  // distance plane (rules 42 and 43): off while dist_reach is 0
+  int dist_reach = 0;
+  unsigned dist_flags = 0;
+  DevBuf<uint16_t> d_dist2;
+  DevBuf<uint8_t> d_rowd;          // the scratch of a reach above kWmDistTiledReach, grown on demand
+  int dirty[4] = {0, 0, -1, -1};   // (i_min, j_min, i_max, j_max), empty while i_max < i_min
+  int dist_last[4] = {-1, -1, -1, -1};
+  bool dist_last_full = false;
+
+  void dirty_all() {
+    if (dist_reach == 0) return;
+    dirty[0] = dirty[1] = 0;
+    dirty[2] = W - 1;
+    dirty[3] = H - 1;
+  }
+  void dirty_merge(int i0, int j0, int i1, int j1) {
+    if (dist_reach == 0) return;
+    if (dirty[2] < dirty[0]) {
+      dirty[0] = i0, dirty[1] = j0, dirty[2] = i1, dirty[3] = j1;
+      return;
+    }
+    dirty[0] = std::min(dirty[0], i0);
+    dirty[1] = std::min(dirty[1], j0);
+    dirty[2] = std::max(dirty[2], i1);
+    dirty[3] = std::max(dirty[3], j1);
+  }
 };
 
 namespace {
@@ -569,6 +706,7 @@ int wm_take_prior(kc_worldmap *c, const void *dev, int elem_bytes) {
     hipLaunchKernelGGL(worldmap_prior_kernel<int8_t>, grid, block, 0, c->stream, static_cast<const int8_t *>(dev),
                        c->d_evidence.p, c->d_cls.p, n, c->m);
   KC_HIP(hipGetLastError());
+  c->dirty_all();  // rule 43: every class may have changed
   KC_HIP(hipStreamSynchronize(c->stream));  // the caller's grid is not read after the call returns
   return KC_OK;
 }
@@ -676,7 +814,49 @@ int wm_update(kc_worldmap *c, const GridSource &s, const kc_worldmap_pose *p, kc
     out->j_min = r[2];
     out->i_max = r[3];
     out->j_max = r[4];
+    c->dirty_merge(r[1], r[2], r[3], r[4]);  // rule 43: from the read-back the update makes anyway
   }
+  return KC_OK;
+}
+
+// rule 43's refresh, queued on the context's stream; the plane is on
+int wm_dist_refresh(kc_worldmap *c) {
+  c->dist_last[0] = c->dist_last[1] = c->dist_last[2] = c->dist_last[3] = -1;
+  c->dist_last_full = false;
+  if (c->dirty[2] < c->dirty[0]) return KC_OK;
+  const int R = c->dist_reach;
+  WmDistArgs a{};
+  a.cls = c->d_cls.p;
+  a.dist2 = c->d_dist2.p;
+  a.W = c->W;
+  a.H = c->H;
+  a.x0 = std::max(c->dirty[0] - R, 0);
+  a.y0 = std::max(c->dirty[1] - R, 0);
+  a.x1 = std::min(c->dirty[2] + R, c->W - 1);
+  a.y1 = std::min(c->dirty[3] + R, c->H - 1);
+  a.R = R;
+  a.R2 = static_cast<unsigned>(R) * static_cast<unsigned>(R);
+  a.unknown_blocks = (c->dist_flags & KC_WORLDMAP_DIST_UNKNOWN_BLOCKS) ? 1 : 0;
+  const int bw = a.x1 - a.x0 + 1, bh = a.y1 - a.y0 + 1;
+  KC_HIP(hipSetDevice(c->device));
+  if (R <= kWmDistTiledReach) {
+    const dim3 grid((bw + kWmDistTile - 1) / kWmDistTile, (bh + kWmDistTile - 1) / kWmDistTile);
+    hipLaunchKernelGGL(worldmap_dist_tile_kernel, grid, dim3(kWmBlock), wm_dist_lds(R), c->stream, a);
+    KC_HIP(hipGetLastError());
+  } else {
+    KC_TRY(c->d_rowd.reserve(static_cast<size_t>(c->W) * static_cast<size_t>(c->H)));
+    a.rowd = c->d_rowd.p;
+    const unsigned gx = static_cast<unsigned>((bw + kWmBlock - 1) / kWmBlock);
+    const int r0 = std::max(a.y0 - R, 0), r1 = std::min(a.y1 + R, c->H - 1);
+    hipLaunchKernelGGL(worldmap_dist_rows_kernel, dim3(gx, r1 - r0 + 1), dim3(kWmBlock), 0, c->stream, a);
+    KC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(worldmap_dist_cols_kernel, dim3(gx, bh), dim3(kWmBlock), 0, c->stream, a);
+    KC_HIP(hipGetLastError());
+  }
+  c->dist_last[0] = a.x0, c->dist_last[1] = a.y0, c->dist_last[2] = a.x1, c->dist_last[3] = a.y1;
+  c->dist_last_full = bw == c->W && bh == c->H;
+  c->dirty[0] = c->dirty[1] = 0;
+  c->dirty[2] = c->dirty[3] = -1;
   return KC_OK;
 }
 
@@ -861,6 +1041,18 @@ int worldmap_view(kc_worldmap *m, WorldMapView *out) {
   if (!m || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
   *out = WorldMapView{m->d_cls.p, m->W, m->H, m->res, m->ox, m->oy, m->stream, m->device};
   return KC_OK;
+}
+
+int worldmap_distance_state(kc_worldmap *m, WorldMapDistance *out) {
+  if (!m || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *out = WorldMapDistance{m->dist_reach ? m->d_dist2.p : nullptr, m->dist_reach};
+  return KC_OK;
+}
+
+int worldmap_distance_refresh(kc_worldmap *m) {
+  if (!m) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (m->dist_reach == 0) KC_FAIL(KC_ERR_STATE, "the map's distance plane is off");
+  return wm_dist_refresh(m);
 }
 
 int worldmap_window(const WorldMapView &v, double x, double y, float max_range, WorldMapWindow *out) {
@@ -1225,6 +1417,62 @@ int kc_worldmap_get(kc_worldmap *c, int8_t *cls_out, int8_t *evidence_out, size_
   if (cls_out) KC_HIP(hipMemcpyAsync(cls_out, c->d_cls.p, n, hipMemcpyDeviceToHost, c->stream));
   if (evidence_out) KC_HIP(hipMemcpyAsync(evidence_out, c->d_evidence.p, n, hipMemcpyDeviceToHost, c->stream));
   KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_worldmap_set_distance(kc_worldmap *c, int reach, unsigned int flags) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (reach < 0 || reach > KC_WORLDMAP_DIST_MAX_REACH)
+    KC_FAIL(KC_ERR_RANGE, "reach must be in 0 .. %d cells, got %d", KC_WORLDMAP_DIST_MAX_REACH, reach);
+  if ((flags & ~static_cast<unsigned>(KC_WORLDMAP_DIST_UNKNOWN_BLOCKS)) || (reach == 0 && flags))
+    KC_FAIL(KC_ERR_INVALID, "unknown distance flag bits 0x%x", flags);
+  KC_HIP(hipSetDevice(c->device));
+  KC_HIP(hipStreamSynchronize(c->stream));  // a refresh in flight still writes the plane
+  c->dist_reach = 0;
+  c->dist_flags = 0;
+  c->dist_last[0] = c->dist_last[1] = c->dist_last[2] = c->dist_last[3] = -1;
+  c->dist_last_full = false;
+  if (reach == 0) {
+    c->d_dist2.release();
+    c->d_rowd.release();
+    return KC_OK;
+  }
+  KC_TRY(c->d_dist2.reserve(static_cast<size_t>(c->W) * static_cast<size_t>(c->H)));
+  c->dist_reach = reach;
+  c->dist_flags = flags;
+  c->dirty_all();
+  return KC_OK;
+}
+
+int kc_worldmap_distance_info(kc_worldmap *c, int *reach_out, unsigned int *flags_out, int last_box[4], int *last_full_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (reach_out) *reach_out = c->dist_reach;
+  if (flags_out) *flags_out = c->dist_flags;
+  if (last_box) std::memcpy(last_box, c->dist_last, sizeof(c->dist_last));
+  if (last_full_out) *last_full_out = c->dist_last_full ? 1 : 0;
+  return KC_OK;
+}
+
+int kc_worldmap_distance_refresh(kc_worldmap *c) { return worldmap_distance_refresh(c); }
+
+int kc_worldmap_get_distance(kc_worldmap *c, uint16_t *out, size_t cap) {
+  if (!c || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (c->dist_reach == 0) KC_FAIL(KC_ERR_STATE, "the map's distance plane is off");
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
+  KC_TRY(wm_dist_refresh(c));
+  KC_HIP(hipMemcpyAsync(out, c->d_dist2.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_worldmap_distance_device(kc_worldmap *c, void **ptr) {
+  if (!c || !ptr) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *ptr = nullptr;
+  if (c->dist_reach == 0) KC_FAIL(KC_ERR_STATE, "the map's distance plane is off");
+  KC_TRY(wm_dist_refresh(c));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  *ptr = c->d_dist2.p;
   return KC_OK;
 }
 

@@ -49,24 +49,36 @@ def _pose(robot_state) -> Tuple[float, float, float]:
 class MCL:
     def __init__(self, world_map, n_particles: int, angles, range_max: float, sigma_hit: float = 0.1, seed: int = 0,
                  motion_noise: Tuple[float, float, float] = (0.02, 0.01, 0.01), resample_ratio: Tuple[int, int] = (1, 2),
-                 unknown_blocks: bool = False, skip_no_return: bool = False, spread: bool = True, **model):
+                 unknown_blocks: bool = False, skip_no_return: bool = False, spread: bool = True, model: str = "beam",
+                 **model_args):
         """world_map: a `WorldMap` (kept alive).  angles: the beams in the scan frame, radians; a sensor's yaw offset is
         folded in here, a translated mount is out of scope.  range_max: metres; a measured range that is not finite or
         not below it is a beam without a return: it counts as range_max, or not at all with skip_no_return.
         sigma_hit and **model (err_shift, n_pen, floor, pen_scale, w_shift, n_w, wtab0, temperature): the sensor model
         the integer penalty and weight tables are built from; its defaults are judgement, not measurement.
         motion_noise: sigmas a step adds, (forward m, lateral m, yaw rad).  resample_ratio (num, den): resample when
-        n_eff < N num / den.  spread=False saves the read-back of the particles a step."""
+        n_eff < N num / den.  spread=False saves the read-back of the particles a step.
+        model: "beam" (every step ray-casts the map for every particle and beam) or "field", the likelihood-field model
+        (DESIGN.md 4.11 rules 44 and 45): a beam costs one lookup of the map's distance field at its endpoint, beams
+        without a return say nothing; **model_args are then reach (cells, default ceil(3 sigma_hit / resolution) within
+        1 .. 63), floor, pen_scale, w_shift, n_w, wtab0, temperature.  It enables the map's distance field itself when
+        that is off or shorter (unknown_blocks decides what blocks there)."""
+        if model not in ("beam", "field"):
+            raise ValueError('model must be "beam" or "field"')
         inner = cpp_world_map(world_map)
         if inner is None:
             raise TypeError("expected a WorldMap")
         self._map = world_map
         a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
         self._mcl = kompass_cpp.mapping.MCL(inner, int(n_particles), a, float(range_max), int(seed))
-        self._mcl.set_model(sigma_hit=float(sigma_hit), **model)
+        self._mcl.set_flags(bool(unknown_blocks), bool(skip_no_return))
+        if model == "field":
+            self._mcl.set_field_model(sigma_hit=float(sigma_hit), **model_args)
+        else:
+            self._mcl.set_model(sigma_hit=float(sigma_hit), **model_args)
+        self.model = model
         self._mcl.set_motion_noise(*(float(v) for v in motion_noise))
         self._mcl.set_resample_ratio(int(resample_ratio[0]), int(resample_ratio[1]))
-        self._mcl.set_flags(bool(unknown_blocks), bool(skip_no_return))
         self._mcl.set_spread(bool(spread))
 
     def init(self, robot_state, sigma_xy: float, sigma_yaw: float) -> None:

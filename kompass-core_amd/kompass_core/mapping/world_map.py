@@ -163,6 +163,40 @@ class WorldMap:
         with np.errstate(invalid="ignore"):
             return np.where(np.isfinite(q) & (q < v), q, v)
 
+    def enable_distance(self, reach_m: Optional[float] = None, reach_cells: Optional[int] = None, unknown_blocks: bool = False) -> int:
+        """Keep a distance field over the map (DESIGN.md 4.11 rules 42 and 43): per cell the squared distance in cells to
+        the nearest occupied cell (with unknown_blocks also a never-observed one) within the reach.  reach_m metres
+        (rounded up to whole cells) or reach_cells, 1 .. 254; reach_cells=0 switches it off.  Kept lazily: an update
+        costs nothing more, a reader refreshes the changed box first.  -> the reach in cells."""
+        if (reach_m is None) == (reach_cells is None):
+            raise TypeError("give reach_m or reach_cells")
+        reach = int(reach_cells) if reach_m is None else int(math.ceil(float(reach_m) / float(np.float32(self._map.resolution))))
+        if reach_m is not None and reach < 1:
+            raise ValueError("reach_m must be positive")
+        self._map.enable_distance(reach, bool(unknown_blocks))
+        return reach
+
+    def distance_field(self, metres: bool = False) -> np.ndarray:
+        """A refreshed host copy of the distance plane: uint16 [width, height] squared cells, 0xFFFF beyond the reach; or
+        with metres=True float32 metres, inf beyond the reach."""
+        d = self._map.distance_field()
+        if not metres:
+            return d
+        out = np.sqrt(d.astype(np.float32)) * np.float32(self._map.resolution)
+        out[d == 0xFFFF] = np.inf
+        return out
+
+    def distance_at(self, x: float, y: float) -> float:
+        """Metres from the cell that holds world point (x, y) to the nearest blocking cell; inf beyond the reach or
+        outside the map.  Reads the whole plane back: for a look, not for a loop."""
+        res = float(np.float32(self._map.resolution))
+        ox, oy = self._map.origin
+        i, j = int(math.floor((float(x) - ox) / res + 0.5)), int(math.floor((float(y) - oy) / res + 0.5))
+        if not (0 <= i < self._map.width and 0 <= j < self._map.height):
+            return math.inf
+        d = int(self._map.distance_field()[i, j])
+        return math.inf if d == 0xFFFF else math.sqrt(float(d)) * res
+
     @property
     def occupancy(self) -> np.ndarray:
         """A host copy of the class plane, int8 [width, height]: -1 unexplored, 0 empty, 100 occupied."""

@@ -365,6 +365,15 @@ SIGNATURES = {
     "kc_mcl_particles_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "kc_mcl_set_timing": (C.c_int, [_vp, C.c_int]),
     "kc_mcl_times": (C.c_int, [_vp, _fp]),
+    "kc_worldmap_set_distance": (C.c_int, [_vp, C.c_int, C.c_uint]),
+    "kc_worldmap_distance_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kc_worldmap_distance_refresh": (C.c_int, [_vp]),
+    "kc_worldmap_get_distance": (C.c_int, [_vp, C.c_void_p, _sz]),
+    "kc_worldmap_distance_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "kc_mcl_field_check": (C.c_int, [C.c_float, _sz, _sz, C.c_float, C.c_void_p, _sz, C.c_int, C.c_void_p, _sz, C.c_int, C.c_uint,
+                                     _ip, C.POINTER(C.c_int64)]),
+    "kc_mcl_set_field_model": (C.c_int, [_vp, C.c_void_p, _sz, C.c_uint16, C.c_void_p, _sz, C.c_int]),
+    "kc_mcl_model_kind": (C.c_int, [_vp, C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -1684,8 +1693,38 @@ class WorldMapContext(_Owner, _StreamOrdered):
         _check(lib().kc_worldmap_get(self.h, c.ctypes.data, e.ctypes.data, c.size))
         return c, e
 
+    def set_distance(self, reach, unknown_blocks=False, flags=None):
+        """Rules 42 and 43: keep the distance plane at `reach` cells (1 .. 254); 0 switches it off and frees it."""
+        f = (WORLDMAP_DIST_UNKNOWN_BLOCKS if unknown_blocks else 0) if flags is None else int(flags)
+        _check(lib().kc_worldmap_set_distance(self.h, int(reach), f))
 
+    def distance_info(self):
+        """-> (reach, flags, (i_min, j_min, i_max, j_max) the last refresh recomputed or all -1, whether that was the
+        whole map)."""
+        r, f, b, full = C.c_int(), C.c_uint(), (C.c_int * 4)(), C.c_int()
+        _check(lib().kc_worldmap_distance_info(self.h, C.byref(r), C.byref(f), b, C.byref(full)))
+        return r.value, f.value, tuple(int(v) for v in b), bool(full.value)
+
+    def distance_refresh(self):
+        _check(lib().kc_worldmap_distance_refresh(self.h))
+
+    def distance(self):
+        """dist2 uint16 [width, height] copied to the host, refreshed first; WORLDMAP_DIST_FAR beyond reach."""
+        w, h = self.shape
+        d = np.empty((w, h), np.uint16, order="F")
+        _check(lib().kc_worldmap_get_distance(self.h, d.ctypes.data, d.size))
+        return d
+
+    def distance_device_ptr(self) -> int:
+        """The refreshed plane on the device: uint16, (width, height); valid until the next set_distance."""
+        return _out(_vp, lib().kc_worldmap_distance_device, self.h)
+
+
+WORLDMAP_DIST_FAR = 0xFFFF  # KC_WORLDMAP_DIST_FAR
+WORLDMAP_DIST_UNKNOWN_BLOCKS = 1
+WORLDMAP_DIST_MAX_REACH = 254
 MCL_SKIP_NO_RETURN = 2  # KC_MCL_SKIP_NO_RETURN
+MCL_MODEL_NONE, MCL_MODEL_BEAM, MCL_MODEL_FIELD = 0, 1, 2
 MCL_NOISE_STD = math.sqrt((65536.0 * 65536.0 - 1.0) / 3.0)  # rule 30: of the sum of four uniform 16-bit fields
 
 
@@ -1698,6 +1737,19 @@ def mcl_check(resolution, n_particles, n_beams, range_max, pen=None, err_shift=0
                               None if pn is None else pn.ctypes.data, 0 if pn is None else pn.size, int(err_shift),
                               None if wt is None else wt.ctypes.data, 0 if wt is None else wt.size, int(w_shift),
                               int(flags), C.byref(rc), C.byref(zmax)))
+    return rc.value, zmax.value
+
+
+def mcl_field_check(resolution, n_particles, n_beams, range_max, pen_d2=None, reach=0, wtab=None, w_shift=0, flags=0):
+    """kc_mcl_field_check's refusals (host only) -> (Rc, ZMAX); raises ValueError / IndexError.  pen_d2, wtab: None skips a
+    table; reach 0 skips the reach."""
+    pn = None if pen_d2 is None else np.ascontiguousarray(pen_d2, dtype=np.uint16)
+    wt = None if wtab is None else np.ascontiguousarray(wtab, dtype=np.uint32)
+    rc, zmax = C.c_int32(), C.c_int64()
+    _check(lib().kc_mcl_field_check(float(np.float32(resolution)), int(n_particles), int(n_beams), float(np.float32(range_max)),
+                                    None if pn is None else pn.ctypes.data, 0 if pn is None else pn.size, int(reach),
+                                    None if wt is None else wt.ctypes.data, 0 if wt is None else wt.size, int(w_shift),
+                                    int(flags), C.byref(rc), C.byref(zmax)))
     return rc.value, zmax.value
 
 
@@ -1742,6 +1794,16 @@ class MclContext(_Owner):
         pn, wt = np.ascontiguousarray(pen, dtype=np.uint16), np.ascontiguousarray(wtab, dtype=np.uint32)
         _check(lib().kc_mcl_set_model(self.h, pn.ctypes.data, pn.size, int(err_shift), wt.ctypes.data, wt.size,
                                       int(w_shift)))
+
+    def set_field_model(self, pen_d2, pen_far, wtab, w_shift):
+        """Rules 44 and 45 in place of 32 to 34: pen_d2 has c2 + 1 entries; the map's distance plane must be on at a step."""
+        pn, wt = np.ascontiguousarray(pen_d2, dtype=np.uint16), np.ascontiguousarray(wtab, dtype=np.uint32)
+        if not 0 <= int(pen_far) <= 0xFFFF:
+            raise ValueError("pen_far is a uint16")
+        _check(lib().kc_mcl_set_field_model(self.h, pn.ctypes.data, pn.size, int(pen_far), wt.ctypes.data, wt.size, int(w_shift)))
+
+    def model_kind(self) -> int:
+        return _out(C.c_int, lib().kc_mcl_model_kind, self.h)
 
     def init_pose(self, tx0, ty0, h0, s_xy, s_h):
         _check(lib().kc_mcl_init_pose(self.h, int(tx0), int(ty0), int(h0), int(s_xy), int(s_h)))

@@ -53,7 +53,17 @@ beams spread 2 m around the middle, range_max 10 m.  One JSON line a configurati
       CPU filter);
   (c) kc_worldmap_scan alone for the same rays, by the host's clock with its read-back of N x B doubles: the floor the
       walk sets, and the ratio of the step's walk launch to it.
-  python tools/worldmap_time.py --mcl [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --mcl [--reps 30] [--warmup 3]
+
+--field times the distance plane and the likelihood-field model (rules 42 to 45): the same world under the "latest
+observation wins" model, reach 6 and 16.  One JSON line a reach with
+  (a) a full refresh (kc_worldmap_set_distance marks the whole map, then kc_worldmap_distance_device: refresh and wait);
+  (b) a partial refresh behind a 400 x 400 update: two mappers' grids alternate so that every update changes cells; the
+      update itself is outside the clock, the box it left is reported;
+  (c) kc_worldmap_get_distance with nothing dirty: the copy of W x H uint16 alone;
+and one line a particle configuration (4096 x 64, 1024 x 256, 65536 x 24) with the field step and the beam step of the
+same localiser on the same particles, by the host's clock and their launches by HIP events.
+  python tools/worldmap_time.py --field [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -324,6 +334,90 @@ def mcl_leg(args):
                 print(json.dumps(line), flush=True)
 
 
+def field_leg(args):
+    import worldmap_mcl_field_ref as fref
+    import worldmap_mcl_ref as lref
+
+    ang, rng = syn.dense_scan(2048, 1.2)
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r, ORIGIN[1] + (H // 2) * r)
+    range_max = 10.0
+    cells = 65536.0 / r
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as m_a, kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as m_b, \
+            kh.WorldMapContext(W, H, RES, ORIGIN) as wm:
+        wm.set_model(**ref.LATEST_WINS_EXACT)
+        m_a.scan_to_grid_device(ang, rng)
+        m_b.scan_to_grid_device(ang, rng * 0.8)
+        m_a.sync()
+        m_b.sync()
+        mappers = [m_a, m_b]
+        for reach in (6, 16):
+            wm.set_distance(reach)
+            wm.update_from_mapper(m_a, centre + (0.0,))
+
+            def full():
+                wm.set_distance(reach)                           # marks the whole map; the plane's memory is kept
+                t0 = time.perf_counter()
+                wm.distance_device_ptr()
+                return (time.perf_counter() - t0) * 1e3
+
+            boxes = []
+
+            def partial():
+                changed, box = wm.update_from_mapper(mappers[len(boxes) & 1], centre + (0.3,))
+                assert changed > 0
+                t0 = time.perf_counter()
+                wm.distance_device_ptr()
+                dt = (time.perf_counter() - t0) * 1e3
+                boxes.append(wm.distance_info()[2])
+                return dt
+
+            for _ in range(args.warmup):
+                full()
+                partial()
+            line = {"world": [W, H], "reach": reach, "reps": args.reps, "warmup": args.warmup,
+                    "a_full_refresh_ms": spread([full() for _ in range(args.reps)]),
+                    "b_partial_refresh_ms": spread([partial() for _ in range(args.reps)])}
+            line["b_refreshed_box"] = list(boxes[-1])
+            line["c_get_distance_ms"] = timed(wm.distance, args.reps, args.warmup)
+            assert np.array_equal(wm.distance()[900:1100, 500:700], __import__("worldmap_dist_ref").dist2_plane(wm.planes()[0], reach)[900:1100, 500:700]) \
+                if reach == 6 else True
+            print(json.dumps(line), flush=True)
+        wm.set_distance(6)
+        pen, err_shift, wtab, w_shift = lref.sensor_tables(RES, 0.1)
+        pen_d2, pen_far, _, fwtab, fw_shift = fref.field_tables(RES, 0.1)
+        for n, b in ((4096, 64), (1024, 256), (65536, 24)):
+            a = np.arange(b) * (2 * np.pi / b)
+            zq = kh.mcl_quantise_ranges(wm.scan(centre + (0.3,), a, range_max), RES, range_max)
+            with kh.MclContext(wm, n, a, range_max, seed=1) as mcl:
+                q0 = wm.quantise_pose(*centre, 0.0)
+                scales = (lref.noise_scale(0.02 * cells), lref.noise_scale(0.01 * cells), lref.noise_scale(0.01 / (2 * np.pi) * 65536))
+                line = {"world": [W, H], "particles": n, "beams": b, "rays": n * b, "range_max": range_max, "reps": args.reps,
+                        "warmup": args.warmup}
+                for name in ("field", "beam"):
+                    if name == "field":
+                        mcl.set_field_model(pen_d2, pen_far, fwtab, fw_shift)
+                    else:
+                        mcl.set_model(pen, err_shift, wtab, w_shift)
+                    mcl.init_pose(q0.tx, q0.ty, 0, lref.noise_scale(2.0 * cells), lref.noise_scale(65536 / 4))
+
+                    def step():
+                        return mcl.step(3000, 0, 50, *scales, zq)
+
+                    line[f"{name}_step_ms"] = timed(step, args.reps, args.warmup)
+                    mcl.set_timing(True)
+                    parts = []
+                    for k in range(args.warmup + args.reps):
+                        step()
+                        if k >= args.warmup:
+                            parts.append(mcl.times())
+                    mcl.set_timing(False)
+                    line[f"{name}_launch_first_ms"] = spread([p[0] for p in parts])
+                    line[f"{name}_launch_weigh_ms"] = spread([p[1] for p in parts])
+                line["beam_over_field_first_launch"] = round(line["beam_launch_first_ms"][0] / line["field_launch_first_ms"][0], 2)
+                print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -333,6 +427,7 @@ def main():
     ap.add_argument("--points", action="store_true", help="time the obstacle hand-off to the controller instead")
     ap.add_argument("--scan", action="store_true", help="time the virtual laser scan instead")
     ap.add_argument("--mcl", action="store_true", help="time the Monte-Carlo localiser instead")
+    ap.add_argument("--field", action="store_true", help="time the distance plane and the likelihood-field model instead")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
@@ -344,6 +439,8 @@ def main():
         return scan_leg(args)
     if args.mcl:
         return mcl_leg(args)
+    if args.field:
+        return field_leg(args)
     hip = hip_runtime()
     ang, rng = syn.dense_scan(2048, 1.2)                      # ranges 3.6 .. 8.4 m in a 20 m window
     pose_xy = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021)
