@@ -586,7 +586,17 @@ int kc_mapper_scan_to_grid_bayes_device(kc_mapper *ctx, const double *angles,
  * ask again after a warp */
 int kc_mapper_prob_device(kc_mapper *ctx, void **dev_prob_f32, void **dev_prev_f32);
 /* LocalMapper::getPreviousGridInCurrentPose (local_mapper.cpp:17-78): bilinear
- * warp of the previous probability grid, in place (stream-ordered) */
+ * warp of the previous probability grid, in place (stream-ordered).
+ * KC_ERR_RANGE, before anything is queued and with the previous grid as it
+ * was, for a pose whose offset position / resolution is not below 2^30 cells
+ * on either axis (NaN and inf included: kc_mapper_create's rule);
+ * a non-finite orientation is accepted and gives p_prior everywhere.
+ * Probabilities fed back scan after scan saturate: cells reach exactly 1.0f
+ * and 0.0f (benchmark sensor model) and then never move, or settle at the
+ * rounding fixed points 1 - 2^-24 and 2^-52 (defaults); subnormals are kept.
+ * Where the reference's arithmetic gives NaN (previous 1 with p_empty 0,
+ * p_prior 0 or 1, range_max 0, NaN / inf / out-of-[0, 1] previous values) the
+ * result is some NaN: its sign and payload are not part of the contract. */
 int kc_mapper_warp_previous(kc_mapper *ctx, const float current_position_in_previous_pose[2],
                             double current_orientation_in_previous_pose);
 int kc_mapper_get_previous_prob(kc_mapper *ctx, float *prob_out);

@@ -944,8 +944,12 @@ int kc_mapper_prob_device(kc_mapper *m, void **dev_prob, void **dev_prev) {
 int kc_mapper_warp_previous(kc_mapper *m, const float pos[2], double orient) {
   if (!m || !pos) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (!m->bayes) KC_FAIL(KC_ERR_INVALID, "kc_mapper_enable_bayes has not been called");
-  KC_HIP(hipSetDevice(m->device));
   const MapGeom &g = m->g;
+  // localToGrid's int conversion of the new centre: the 2^30 rule of kc_mapper_create, NaN and inf
+  // under the same comparison; nothing is queued for a refused pose
+  if (!(std::fabs(pos[0] / g.res) < kMaxCellOffset && std::fabs(pos[1] / g.res) < kMaxCellOffset))
+    KC_FAIL(KC_ERR_RANGE, "pose not below 2^30 cells from the grid centre");
+  KC_HIP(hipSetDevice(m->device));
   // localToGrid of the new centre, then the Matrix3f of local_mapper.cpp:27-37
   const int cc0 = g.c0 + static_cast<int>(pos[0] / g.res);
   const int cc1 = g.c1 + static_cast<int>(pos[1] / g.res);

@@ -237,17 +237,23 @@ def scan_to_grid_baysian(H, W, res, pos, orient, angles, ranges, previous, param
     return grid, prob
 
 
-def warp(previous, inv):
-    """The per-cell part of getPreviousGridInCurrentPose (local_mapper.cpp:44-75): inv is the inverted Matrix3f.
-    The lazy 3-term products reduce as a0 + (a1 + a2) (Eigen's unrolled redux); srcX / srcY are doubles of the
-    float results; the blend is float."""
-    previous = np.asarray(previous, F)
-    H, W = previous.shape
+def warp_sources(H, W, inv):
+    """srcX / srcY of every cell [H, W] (local_mapper.cpp:44-52): the lazy 3-term products reduce as a0 + (a1 + a2)
+    (Eigen's unrolled redux) in float, and the results widen to double."""
     inv = np.asarray(inv, F)
     yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
     fx, fy = xx.astype(F), yy.astype(F)
     src_x = (inv[0, 0] * fx + (inv[0, 1] * fy + inv[0, 2] * F(1))).astype(np.float64)
     src_y = (inv[1, 0] * fx + (inv[1, 1] * fy + inv[1, 2] * F(1))).astype(np.float64)
+    return src_x, src_y
+
+
+def warp(previous, inv):
+    """The per-cell part of getPreviousGridInCurrentPose (local_mapper.cpp:44-75): inv is the inverted Matrix3f.
+    srcX / srcY are doubles of the float results (warp_sources); the blend is float."""
+    previous = np.asarray(previous, F)
+    H, W = previous.shape
+    src_x, src_y = warp_sources(H, W, inv)
     ok = (src_x >= 0) & (src_x < W - 1) & (src_y >= 0) & (src_y < H - 1)
     x0 = np.floor(np.where(ok, src_x, 0)).astype(np.int64)
     y0 = np.floor(np.where(ok, src_y, 0)).astype(np.int64)
