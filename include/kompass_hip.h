@@ -967,6 +967,63 @@ int kc_planner_get_oriented_field(kc_planner *ctx, uint32_t *field4_out, uint8_t
  * walk's cells with the repeated cell of a turn collapsed; kc_planner_shortcut answers
  * KC_ERR_STATE (a segment at an arbitrary angle has no class). */
 int kc_planner_get_oriented_path(kc_planner *ctx, int32_t *states_ijk_out, size_t cap, size_t *count_out);
+/* Car motion (rules 27 to 36), off by default.  The state is (cell,
+ * heading); heading h = 0 .. 7 is the direction the front points: E, NE, N, NW, W, SW, S,
+ * SE = D[h].  step(h) is 10 for even h, 14 for odd h.  Six primitives out of (c, h), n =
+ * turn_cells, rw = reverse_weight, tried and ranked in this order:
+ *   0 S   one unit step along +D[h]                                cost step(h)
+ *   1 L   n steps along +D[h], then n along +D[h+1] in heading h+1   24 n
+ *   2 R   n steps along +D[h], then n along +D[h-1] in heading h-1   24 n
+ *   3 B   one unit step along -D[h]                                rw step(h)
+ *   4 BL  n steps along -D[h], then n along -D[h-1] in heading h-1   rw 24 n
+ *   5 BR  n steps along -D[h], then n along -D[h+1] in heading h+1   rw 24 n
+ * A unit step from (c, h) to c +- D[h] is allowed when both cells are inside the grid
+ * and valid in heading h (a cell outside the grid is never stepped on), and, with the
+ * disc and odd h, both orthogonal neighbours it passes between are valid.  An arc is
+ * allowed when each of its 2 n unit steps is.  There is no turn in place, and with
+ * rw = 0 no B, BL, BR.
+ * a2 = b2 = 0: the disc of kc_planner_solve_car's r2, every heading alike.  a2 > 0: the
+ * box of kc_planner_set_oriented's rule, heading h valid where class h & 3 is; turn
+ * validity plays no part.  turn_cells = 0 switches the mode off and forgets the last
+ * solve; every other call then answers what it answers without this one.
+ * KC_ERR_RANGE for turn_cells outside 0 .. KC_PLANNER_MAX_TURN_CELLS, reverse_weight above
+ * KC_PLANNER_MAX_REVERSE_WEIGHT and a2 + b2 > KC_PLANNER_MAX_RADIUS_CELLS^2; KC_ERR_STATE
+ * while a clearance cost or the oriented mode is set (and their setters answer the
+ * same while this mode is on).  While it is on, kc_planner_solve, kc_planner_solve_oriented,
+ * kc_planner_replan and kc_planner_explore answer KC_ERR_STATE. */
+#define KC_PLANNER_MAX_TURN_CELLS 8
+#define KC_PLANNER_MAX_REVERSE_WEIGHT 16
+int kc_planner_set_car(kc_planner *ctx, int turn_cells, uint32_t reverse_weight, uint32_t a2, uint32_t b2);
+/* Validity, moves, state field and the start's status for (start cell, start heading) ->
+ * (goal cell, goal heading); goal_heading -1: any.
+ *  - field[h][cell] = 0 for the valid goal states; otherwise the minimum over the
+ *    allowed primitives of cost + field[target]; 0xFFFFFFFF where nothing arrives.
+ *  - *status_out as kc_planner_solve: KC_PLAN_START_INVALID when (start, start_heading)
+ *    is invalid, KC_PLAN_GOAL_INVALID when no goal state is valid, then
+ *    KC_PLAN_UNREACHABLE.  *cost_out = field[start_heading][start].
+ * r2 is the disc's and ignored with a box.  KC_ERR_RANGE when 24 * n * max(rw, 1) * 8 *
+ * cells > 0xFFFFFFFE, or if the field still changes after 8 * cells + 1 passes (it
+ * cannot); KC_ERR_STATE without a grid or with the mode off; KC_ERR_INVALID for a start
+ * heading outside 0 .. 7 or a goal heading outside -1 .. 7. */
+int kc_planner_solve_car(kc_planner *ctx, const int start_cell[2], int start_heading, const int goal_cell[2], int goal_heading,
+                         uint32_t r2, int allow_unknown, int *status_out, uint32_t *cost_out, int *passes_out);
+/* the last car solve's field (eight layers of width x height cells, heading 0 first),
+ * moves (eight layers of bytes, bit p = primitive p allowed out of the state) and
+ * validity (a byte a cell, bit h = heading h valid), laid out as the grid; any may be
+ * NULL; cap: cells (field8_out holds 8 * cap words, moves8_out 8 * cap bytes);
+ * KC_ERR_STATE unless the last solve was kc_planner_solve_car */
+int kc_planner_get_car_field(kc_planner *ctx, uint32_t *field8_out, uint8_t *moves8_out, uint8_t *valid_out, size_t cap);
+/* the walk of the last car solve: from (start, start_heading) the allowed primitive
+ * with the smallest cost + field[target], the first among equals; that minimum equals
+ * field[current].  states_ijh_out: (i, j, h) triples, one per primitive boundary, start
+ * first; moves_out: the count - 1 primitive ids between them; both NULL asks for the
+ * count only; zero states when the solve found no path.  kc_planner_get_path then gives
+ * every unit step of every primitive, first leg then second; kc_planner_shortcut answers
+ * KC_ERR_STATE. */
+int kc_planner_get_car_path(kc_planner *ctx, int32_t *states_ijh_out, int32_t *moves_out, size_t cap, size_t *count_out);
+/* the mode as set (0, 0 while off) and what the last kc_planner_solve_car and its walk
+ * took on the host clock (tools): maps and moves, field, walk, in ms; any may be NULL */
+int kc_planner_car_info(kc_planner *ctx, int *turn_cells_out, uint32_t *reverse_weight_out, float phase_ms_out[3]);
 /* Replan from the kept cost field (rules 19 and 20).  Arguments and
  * outputs as kc_planner_solve, and the same field, validity, status, cost and path bit
  * for bit; what differs is the work.  A context keeps the field of its last

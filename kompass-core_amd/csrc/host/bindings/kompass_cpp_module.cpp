@@ -1541,6 +1541,31 @@ PYBIND11_MODULE(kompass_cpp, m) {
              if (!o.empty()) std::memcpy(a.mutable_data(), o.data(), o.size() * sizeof(int32_t));
              return a;
            }, py::arg("k"), py::arg("a2"), py::arg("b2"), "The (di, dj) offsets of class k's footprint mask, in integers")
+      .def("set_car_motion", &Planning::GridPlanner::setCarMotion, py::arg("on"), py::arg("min_turning_radius") = 0.0f,
+           py::arg("allow_reverse") = false, py::arg("reverse_weight") = 2, py::arg("honour_goal_yaw") = true,
+           "Plan over (cell, one of eight directed headings) with one straight step and 45-degree arcs whose legs follow "
+           "from the minimum turning radius; reverse at `reverse_weight` times the forward cost or not at all; no turn in place")
+      .def("car_on", &Planning::GridPlanner::carOn)
+      .def("get_car_turn_cells", &Planning::GridPlanner::carTurnCells)
+      .def("get_car_reverse_weight", &Planning::GridPlanner::carReverseWeight)
+      .def("get_path_moves", [](Planning::GridPlanner &p) {
+             const std::vector<int32_t> m = p.getPathMoves();
+             py::array_t<int32_t> a({(py::ssize_t)m.size()});
+             if (!m.empty()) std::memcpy(a.mutable_data(), m.data(), m.size() * sizeof(int32_t));
+             return a;
+           }, "(n - 1,) primitive ids (0 .. 5: S, L, R, B, BL, BR) between the states of get_path_states(); empty without a path or with car motion off")
+      .def("get_car_field", [](Planning::GridPlanner &p) {
+             const py::ssize_t w = p.width(), h = p.height();
+             py::array_t<uint32_t> f({(py::ssize_t)8, h, w});  // layer h, then cell (i, j) at i + j * width
+             py::array_t<uint8_t> m({(py::ssize_t)8, h, w});
+             py::array_t<uint8_t, py::array::f_style> v({w, h});
+             p.getCarField(f.mutable_data(), m.mutable_data(), v.mutable_data(), static_cast<size_t>(w) * static_cast<size_t>(h));
+             return py::make_tuple(f.attr("transpose")(0, 2, 1), m.attr("transpose")(0, 2, 1), v);
+           }, "(field uint32 [8, i, j], moves uint8 [8, i, j] (bit p = primitive p), validity bits uint8 [i, j] (bit h = heading h)) of the last car solve")
+      .def_static("heading_class", &Planning::GridPlanner::headingClass, py::arg("yaw"),
+                  "The heading 0 .. 7 of a yaw: ((lround(yaw / (pi / 4)) mod 8) + 8) mod 8")
+      .def_static("turn_cells", &Planning::GridPlanner::turnCells, py::arg("radius"), py::arg("resolution"),
+                  "The legs of a 45-degree arc in cells: max(1, ceil(radius / resolution * tan(pi / 8)))")
       .def("explore", [](Planning::GridPlanner &p, double robot_x, double robot_y, double min_distance, uint32_t min_size) {
              py::gil_scoped_release nogil;
              return p.explore(robot_x, robot_y, min_distance, min_size);

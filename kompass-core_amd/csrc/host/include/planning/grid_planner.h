@@ -12,7 +12,9 @@
 // plans over (cell, heading class) with the box's own oriented footprint instead of the disc: the robot moves along
 // its length axis wherever the box fits and turns in place only where the turning disc fits.  explore (rules 21 to 26)
 // asks the map instead of the caller for a goal: the frontiers of the known map that the robot can reach, nearest
-// first, and the path to each.
+// first, and the path to each.  setCarMotion (rules 27 to 36) plans for a car: the state is (cell, one of eight directed
+// headings), the transitions one straight step and 45-degree arcs whose legs follow from the minimum turning radius,
+// reverse at a price or not at all, no turn in place, and the goal's heading honoured.
 #pragma once
 
 #include <cstdint>
@@ -116,7 +118,8 @@ class GridPlanner {
   uint32_t orientedTurn10() const { return oriented_on_ ? turn10_ : 0u; }
   // A2, B2 of the bounds set (0, 0 while the mode is off)
   void orientedA2B2(uint32_t *a2_out, uint32_t *b2_out) const;
-  // the (i, j, k) triples of the last solve's state walk, start first; empty without a path or with the mode off
+  // the (i, j, k) triples of the last solve's state walk, start first; empty without a path or with the mode off.  With
+  // car motion: (i, j, h), one per primitive boundary.
   std::vector<int32_t> getPathStates();
   // the last oriented solve's field (four layers, class 0 first), validity bits (bit k = class k) and turn validity
   void getOrientedField(uint32_t *field4_out, uint8_t *valid4_out, uint8_t *turn_valid_out, size_t cap);
@@ -125,6 +128,35 @@ class GridPlanner {
   // rule 14's offsets of class k as (di, dj) pairs, row by row (dj rising, then di); needs no device.
   // std::invalid_argument for k outside 0 .. 3, std::out_of_range where A2 + B2 reaches beyond 254 cells.
   static std::vector<int32_t> orientedMask(int k, uint32_t a2, uint32_t b2);
+  // Car motion (rules 27 to 36).  The state is (cell, heading h = 0 .. 7: E, NE, N, NW, W, SW, S, SE); the primitives are
+  // S, L, R and, with allow_reverse, B, BL, BR at reverse_weight (1 .. 16) times the forward cost; the legs of an arc are
+  // n = turnCells(min_turning_radius, resolution) cells, evaluated with the bounds and again when they change.  The
+  // footprint is the disc, or with setOrientedFootprint(true) the box by heading (rule 28; turn_cost then plays no part:
+  // a car does not pivot).  The start heading comes from setupProblem's start_yaw, the goal heading from goal_yaw when
+  // honour_goal_yaw, else every valid heading at the goal cell ends the path.  A corner of the planned polyline has n
+  // cells of tangent on either side, so a fillet of radius n / tan(pi / 8) >= min_turning_radius / resolution cells
+  // fits; it leaves the polyline by at most 0.199 n cells, which `margin` has to allow for.  The polyline is what is
+  // planned and checked.  getPath / getPathCells give every unit step of every primitive; getCost weighs reverse,
+  // getPathLength does not.  replan() is a full solve.  std::invalid_argument together with a clearance cost (here or in
+  // setClearanceCost, whichever comes second) and from getAnyAngle* and explore while it is on; std::out_of_range for a
+  // radius of more than KC_PLANNER_MAX_TURN_CELLS turn cells or a reverse weight outside 1 .. 16.
+  void setCarMotion(bool on, float min_turning_radius = 0.0f, bool allow_reverse = false, int reverse_weight = 2,
+                    bool honour_goal_yaw = true);
+  bool carOn() const { return car_on_; }
+  // n of the bounds set (0 while the mode is off) / rw as the context gets it (0 without reverse)
+  int carTurnCells() const;
+  uint32_t carReverseWeight() const { return car_on_ && car_reverse_ ? car_rw_ : 0u; }
+  // the last car solve's field [8 layers], moves bytes [8 layers] and validity bits (bit h = heading h)
+  void getCarField(uint32_t *field8_out, uint8_t *moves8_out, uint8_t *valid_out, size_t cap);
+  // the primitive ids (0 .. 5: S, L, R, B, BL, BR) between the states of getPathStates(); empty without a path or with
+  // the mode off
+  std::vector<int32_t> getPathMoves();
+  // h = ((lround(yaw / (pi / 4)) mod 8) + 8) mod 8, in double, halves away from zero; needs no device
+  static int headingClass(double yaw);
+  // n = max(1, (int)ceil(radius / resolution * tan(pi / 8))), in double with tan(pi / 8) a literal; needs no device.
+  // std::invalid_argument for a radius or resolution that is not finite and positive, std::out_of_range where no int
+  // holds n
+  static int turnCells(double radius, double resolution);
   // Exploration (rules 21 to 26): the reachable frontiers of the grid from the cell of (robot_x, robot_y), the
   // footprint the disc (only occupied cells inflate, unknown cells are never crossed: allow_unknown plays no part).
   // min_distance_m: a frontier cell lies at least that far along the field, min_cost = lround(min_distance_m /
@@ -195,11 +227,22 @@ class GridPlanner {
   int start_class_ = 0;
   bool oriented_applied_ = false;  // the context holds (applied_a2_, applied_b2_, applied_turn10_)
   uint32_t applied_a2_ = 0, applied_b2_ = 0, applied_turn10_ = 0;
+  bool car_on_ = false, car_reverse_ = false, car_goal_yaw_ = true;
+  double car_radius_ = 0.0;
+  uint32_t car_rw_ = 0;
+  int start_heading_ = 0, goal_heading_ = -1;
+  bool car_applied_ = false;  // the context holds (applied_turn_, applied_rw_, applied_car_a2_, applied_car_b2_)
+  int applied_turn_ = 0;
+  uint32_t applied_rw_ = 0, applied_car_a2_ = 0, applied_car_b2_ = 0;
+  void applyCar();
+  static void checkTurnCells(int n);  // std::out_of_range above KC_PLANNER_MAX_TURN_CELLS
+  void applyModes();
   void applyOriented();
   void applyClearanceCost();
   void needBounds() const;
   void needDiscMode() const {  // the any-angle calls: a segment at an arbitrary angle has no heading class (rule 18)
     if (oriented_on_) throw std::invalid_argument("GridPlanner: no any-angle path with the oriented footprint on");
+    if (car_on_) throw std::invalid_argument("GridPlanner: no any-angle path with car motion on: a segment at an arbitrary angle is no primitive");
   }
   bool havePath() const { return status_ == KC_PLAN_FOUND && !explored_; }  // of a solve: explore() hands out frontier paths
   void forgetSolve();

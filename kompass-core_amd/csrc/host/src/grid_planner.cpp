@@ -2,6 +2,7 @@
 // on the device through kc_planner_* (DESIGN.md 4.10).
 #include "planning/grid_planner.h"
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <stdexcept>
@@ -57,7 +58,7 @@ void GridPlanner::setSpaceBoundsFromMap(float origin_x, float origin_y, int widt
   res_ = resolution;
   have_bounds_ = true;
   applyClearanceCost();  // R2 and C2 are cells of this resolution
-  applyOriented();       // and so are A2 and B2
+  applyModes();          // and so are A2 and B2, and the turn cells
 }
 
 void GridPlanner::setOrientedFootprint(bool on, float turn_cost) {
@@ -75,7 +76,7 @@ void GridPlanner::setOrientedFootprint(bool on, float turn_cost) {
   turn10_ = t10;
   if (!have_bounds_) return;
   try {
-    applyOriented();
+    applyModes();
   } catch (...) {  // a refused footprint leaves the one before
     oriented_on_ = was_on;
     turn10_ = old_t10;
@@ -93,7 +94,7 @@ void GridPlanner::orientedA2B2(uint32_t *a2_out, uint32_t *b2_out) const {
 
 // hands the box to the context when it is not the one the context holds, as applyClearanceCost does
 void GridPlanner::applyOriented() {
-  if (!oriented_on_) {
+  if (!oriented_on_ || car_on_) {  // with car motion the box goes to the context through applyCar
     if (oriented_applied_) {
       hip::check(kc_planner_set_oriented(ctx_.get(), 0, 0, 0));
       oriented_applied_ = false;
@@ -112,6 +113,108 @@ void GridPlanner::applyOriented() {
   applied_b2_ = b2;
   applied_turn10_ = turn10_;
   forgetSolve();
+}
+
+// the context holds one of the two state modes at a time: the one that leaves is switched off first
+void GridPlanner::applyModes() {
+  if (car_on_) {
+    applyOriented();
+    applyCar();
+  } else {
+    applyCar();
+    applyOriented();
+  }
+}
+
+void GridPlanner::setCarMotion(bool on, float min_turning_radius, bool allow_reverse, int reverse_weight, bool honour_goal_yaw) {
+  if (on) {
+    if (clear_on_) throw std::invalid_argument("car motion cannot be combined with a clearance cost");
+    if (!std::isfinite(min_turning_radius) || !(min_turning_radius > 0.0f)) throw std::invalid_argument("min_turning_radius must be positive and finite");
+    if (allow_reverse && (reverse_weight < 1 || reverse_weight > KC_PLANNER_MAX_REVERSE_WEIGHT))
+      throw std::out_of_range("reverse_weight must be in 1 .. " + std::to_string(KC_PLANNER_MAX_REVERSE_WEIGHT));
+    // refused before anything changes: the context keeps the mode it has
+    if (have_bounds_) checkTurnCells(turnCells(static_cast<double>(min_turning_radius), static_cast<double>(res_)));
+  }
+  const bool was_on = car_on_, old_reverse = car_reverse_, old_goal = car_goal_yaw_;
+  const double old_radius = car_radius_;
+  const uint32_t old_rw = car_rw_;
+  car_on_ = on;
+  car_reverse_ = on && allow_reverse;
+  car_goal_yaw_ = honour_goal_yaw;
+  car_radius_ = on ? static_cast<double>(min_turning_radius) : 0.0;
+  car_rw_ = car_reverse_ ? static_cast<uint32_t>(reverse_weight) : 0u;
+  forgetSolve();  // the goal heading may count differently now
+  if (!have_bounds_) return;
+  try {
+    applyModes();
+  } catch (...) {  // a refused mode leaves the one before
+    car_on_ = was_on;
+    car_reverse_ = old_reverse;
+    car_goal_yaw_ = old_goal;
+    car_radius_ = old_radius;
+    car_rw_ = old_rw;
+    throw;
+  }
+}
+
+void GridPlanner::checkTurnCells(int n) {
+  if (n > KC_PLANNER_MAX_TURN_CELLS)
+    throw std::out_of_range("a turning radius of " + std::to_string(n) + " turn cells is above the cap of " +
+                            std::to_string(KC_PLANNER_MAX_TURN_CELLS) + ": plan on a coarser grid");
+}
+
+int GridPlanner::carTurnCells() const {
+  if (!car_on_) return 0;
+  needBounds();
+  return turnCells(car_radius_, static_cast<double>(res_));
+}
+
+// hands the mode to the context when it is not the one the context holds, as applyClearanceCost does
+void GridPlanner::applyCar() {
+  if (!car_on_) {
+    if (car_applied_) {
+      hip::check(kc_planner_set_car(ctx_.get(), 0, 0, 0, 0));
+      car_applied_ = false;
+      forgetSolve();
+    }
+    return;
+  }
+  const int n = carTurnCells();
+  uint32_t a2 = 0, b2 = 0;
+  orientedA2B2(&a2, &b2);
+  if (n > KC_PLANNER_MAX_TURN_CELLS || (oriented_on_ && a2 == 0)) {
+    // new bounds the mode does not fit: the context drops the mode of the old ones, so that a solve says so instead of
+    // planning with the old turn length
+    if (car_applied_) {
+      hip::check(kc_planner_set_car(ctx_.get(), 0, 0, 0, 0));
+      car_applied_ = false;
+      forgetSolve();
+    }
+    checkTurnCells(n);
+    throw std::out_of_range("the box's half length is less than a cell: the oriented footprint has no length axis");
+  }
+  if (car_applied_ && applied_turn_ == n && applied_rw_ == car_rw_ && applied_car_a2_ == a2 && applied_car_b2_ == b2) return;
+  car_applied_ = false;
+  hip::check(kc_planner_set_car(ctx_.get(), n, car_rw_, a2, b2));
+  car_applied_ = true;
+  applied_turn_ = n;
+  applied_rw_ = car_rw_;
+  applied_car_a2_ = a2;
+  applied_car_b2_ = b2;
+  forgetSolve();
+}
+
+int GridPlanner::headingClass(double yaw) {
+  const long q = std::lround(yaw / (M_PI / 4.0));
+  return static_cast<int>(((q % 8) + 8) % 8);
+}
+
+int GridPlanner::turnCells(double radius, double resolution) {
+  if (!std::isfinite(radius) || !(radius >= 0.0)) throw std::invalid_argument("the turning radius must be finite and >= 0");
+  if (!std::isfinite(resolution) || !(resolution > 0.0)) throw std::invalid_argument("resolution must be positive and finite");
+  const double n = std::ceil(radius / resolution * 0.41421356237309503);  // tan(pi / 8) as a literal: no libm result takes part
+  if (!(n < 2147483647.0)) throw std::out_of_range("the turning radius is too many cells");
+  return std::max(1, static_cast<int>(n));
 }
 
 int GridPlanner::orientationClass(double yaw) {
@@ -150,6 +253,7 @@ std::vector<int32_t> GridPlanner::orientedMask(int k, uint32_t a2, uint32_t b2) 
 void GridPlanner::setClearanceCost(float reach, float weight) {
   const bool on = reach > 0.0f && weight > 0.0f;
   if (on && oriented_on_) throw std::invalid_argument("a clearance cost cannot be combined with the oriented footprint");
+  if (on && car_on_) throw std::invalid_argument("a clearance cost cannot be combined with car motion");
   if (on && (!std::isfinite(reach) || !std::isfinite(weight))) throw std::invalid_argument("reach and weight must be finite");
   uint32_t w10 = 0;
   if (on) {
@@ -281,9 +385,11 @@ uint32_t GridPlanner::footprintR2() const {
   return radiusToR2(radius_, res_);
 }
 
-void GridPlanner::setupProblem(double start_x, double start_y, double start_yaw, double goal_x, double goal_y, double) {
+void GridPlanner::setupProblem(double start_x, double start_y, double start_yaw, double goal_x, double goal_y, double goal_yaw) {
   needBounds();
-  start_class_ = std::isfinite(start_yaw) ? orientationClass(start_yaw) : 0;  // the oriented footprint's k0; goal_yaw stays unused
+  start_class_ = std::isfinite(start_yaw) ? orientationClass(start_yaw) : 0;  // the oriented footprint's k0; it leaves goal_yaw unused
+  start_heading_ = std::isfinite(start_yaw) ? headingClass(start_yaw) : 0;    // car motion's h0 and hg; a goal_yaw that is no number: any
+  goal_heading_ = std::isfinite(goal_yaw) ? headingClass(goal_yaw) : -1;
   // a coordinate no cell holds is outside the grid
   if (!worldToCell(static_cast<float>(start_x), ox_, res_, &start_[0])) start_[0] = -1;
   if (!worldToCell(static_cast<float>(start_y), oy_, res_, &start_[1])) start_[1] = -1;
@@ -312,6 +418,7 @@ uint32_t GridPlanner::minDistanceToCost(double min_distance_m, float resolution)
 bool GridPlanner::explore(double robot_x, double robot_y, double min_distance_m, uint32_t min_size) {
   if (oriented_on_) throw std::invalid_argument("GridPlanner: no exploration with the oriented footprint on: a frontier is ranked by the disc's travel cost to a cell");
   if (clear_on_) throw std::invalid_argument("GridPlanner: no exploration with a clearance cost set: a frontier is ranked by plain travel cost");
+  if (car_on_) throw std::invalid_argument("GridPlanner: no exploration with car motion on: a frontier is ranked by the disc's travel cost to a cell");
   needBounds();
   if (!have_grid_) throw std::runtime_error("GridPlanner: no grid set");
   const uint32_t min_cost = minDistanceToCost(min_distance_m, res_);
@@ -374,7 +481,10 @@ void GridPlanner::frontierLabels(uint32_t *labels_out, size_t cap) {
 
 bool GridPlanner::solve() {
   beginSolve();
-  if (oriented_on_)
+  if (car_on_)
+    hip::check(kc_planner_solve_car(ctx_.get(), start_, start_heading_, goal_, car_goal_yaw_ ? goal_heading_ : -1, footprintR2(),
+                                    allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
+  else if (oriented_on_)
     hip::check(kc_planner_solve_oriented(ctx_.get(), start_, start_class_, goal_, allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
   else
     hip::check(kc_planner_solve(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
@@ -382,7 +492,7 @@ bool GridPlanner::solve() {
 }
 
 bool GridPlanner::replan() {
-  if (oriented_on_) return solve();  // the state field is not kept (rule 20)
+  if (oriented_on_ || car_on_) return solve();  // the state fields are not kept (rules 20 and 35)
   beginSolve();
   hip::check(kc_planner_replan(ctx_.get(), start_, goal_, footprintR2(), allow_unknown_ ? 1 : 0, &status_, &cost_, &passes_));
   int kept = 0;
@@ -454,12 +564,33 @@ float GridPlanner::getPathLength() {
 
 std::vector<int32_t> GridPlanner::getPathStates() {
   std::vector<int32_t> ijk;
-  if (!havePath() || !oriented_on_) return ijk;
+  if (!havePath() || !(oriented_on_ || car_on_)) return ijk;
   size_t n = 0;
+  if (car_on_) {
+    hip::check(kc_planner_get_car_path(ctx_.get(), nullptr, nullptr, 0, &n));
+    ijk.resize(3 * n);
+    if (n) hip::check(kc_planner_get_car_path(ctx_.get(), ijk.data(), nullptr, n, &n));
+    return ijk;
+  }
   hip::check(kc_planner_get_oriented_path(ctx_.get(), nullptr, 0, &n));
   ijk.resize(3 * n);
   if (n) hip::check(kc_planner_get_oriented_path(ctx_.get(), ijk.data(), n, &n));
   return ijk;
+}
+
+std::vector<int32_t> GridPlanner::getPathMoves() {
+  std::vector<int32_t> moves;
+  if (!havePath() || !car_on_) return moves;
+  size_t n = 0;
+  hip::check(kc_planner_get_car_path(ctx_.get(), nullptr, nullptr, 0, &n));
+  moves.resize(n ? n - 1 : 0);
+  if (n > 1) hip::check(kc_planner_get_car_path(ctx_.get(), nullptr, moves.data(), n, &n));
+  return moves;
+}
+
+void GridPlanner::getCarField(uint32_t *field8_out, uint8_t *moves8_out, uint8_t *valid_out, size_t cap) {
+  if (status_ < 0) throw std::runtime_error("GridPlanner: no solve since the last grid or problem");
+  hip::check(kc_planner_get_car_field(ctx_.get(), field8_out, moves8_out, valid_out, cap));
 }
 
 void GridPlanner::getOrientedField(uint32_t *field4_out, uint8_t *valid4_out, uint8_t *turn_valid_out, size_t cap) {

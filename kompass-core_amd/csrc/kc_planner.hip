@@ -50,6 +50,15 @@
 //      atomics from plain HIP (32-bit add at the root, 64-bit add and min at the record); planner_walk_kernel<false, true>
 //      walks from an entry cell down to the robot by field + step, so that the path costs what the record says.
 //
+//  (i) car motion (rules 27 to 36; off unless kc_planner_set_car gave a turn length).  The state is (cell, one of eight
+//      directed headings); the transitions are one straight step and 45-degree arcs of n cells a leg, backward at a price
+//      or not at all, no turn in place.  planner_car_steps_kernel writes a byte a cell (bit h: the unit step along +D[h] is
+//      allowed) from the validity map of (a) or (f); planner_car_moves_kernel walks every arc's polyline over those bytes
+//      once a solve and writes a byte a state (bits 0 .. 5: S, L, R, B, BL, BR).  planner_relax8_kernel is (b) with a
+//      workgroup per (tile, heading): the layer's 66 x 66 region in LDS for the straight moves, which couple one layer
+//      along one line, and the arc candidates, which reach up to 2 n cells into the two neighbouring layers, taken once a
+//      pass from the read-only input.  planner_walk8_kernel is (c) over states: six lanes, a primitive each.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -893,6 +902,267 @@ __global__ __launch_bounds__(64) void planner_walk4_kernel(const uint32_t *field
   }
 }
 
+// ---- car motion (rules 27 to 36) ---------------------------------------------------------------------------------
+
+// heading h = 0 .. 7 is the direction the robot's front points: E, NE, N, NW, W, SW, S, SE
+__constant__ const int kCarDx[8] = {1, 1, 0, -1, -1, -1, 0, 1};
+__constant__ const int kCarDy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+constexpr int kCarS = 0, kCarL = 1, kCarR = 2, kCarB = 3, kCarBL = 4, kCarBR = 5;  // rule 30's order
+
+// rule 28: `vmap` is the disc's validity byte (every heading) or, BOX, the four class bits of rule 14 (heading h & 3)
+template <bool BOX>
+__device__ __forceinline__ bool car_valid(const uint8_t *__restrict__ vmap, size_t g, int h) {
+  if constexpr (BOX) return (vmap[g] >> (h & 3) & 1u) != 0;
+  return vmap[g] != 0;
+}
+
+// rule 29, one lane a cell: bit h of steps[c] says that the unit step from (c, h) along +D[h] is allowed.  The step
+// from (c, h) along -D[h] is the same pair of cells (and, for the disc, the same two corner cells) as the forward step
+// out of c - D[h], so one plane serves both signs.  A cell outside the grid is never stepped on.
+template <bool BOX>
+__global__ __launch_bounds__(kPlanBlock) void planner_car_steps_kernel(const uint8_t *__restrict__ vmap, uint8_t *__restrict__ steps, int W,
+                                                                       int H) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+    const int x = static_cast<int>(i % W), y = static_cast<int>(i / W);
+    uint32_t bits = 0;
+#pragma unroll
+    for (int h = 0; h < 8; ++h) {
+      const int nx = x + kCarDx[h], ny = y + kCarDy[h];
+      if (nx < 0 || nx >= W || ny < 0 || ny >= H) continue;
+      bool ok = car_valid<BOX>(vmap, static_cast<size_t>(i), h) &&
+                car_valid<BOX>(vmap, static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(nx), h);
+      if constexpr (!BOX) {  // rule 3's corner rule; both cells lie in the bounding box of two cells inside the grid
+        if (ok && (h & 1))
+          ok = vmap[static_cast<size_t>(y) * static_cast<size_t>(W) + static_cast<size_t>(nx)] != 0 &&
+               vmap[static_cast<size_t>(ny) * static_cast<size_t>(W) + static_cast<size_t>(x)] != 0;
+      }
+      bits |= ok ? 1u << h : 0u;
+    }
+    steps[i] = static_cast<uint8_t>(bits);
+  }
+}
+
+// `count` unit steps of sign sgn in heading h from (x, y), which is inside the grid: all allowed?  Moves (x, y) to the
+// end of the leg when they are.  A forward step out of a cell inside the grid whose bit is set ends inside the grid; a
+// backward step's bit is read at the cell it ends on, after the bounds test.
+__device__ __forceinline__ bool car_leg(const uint8_t *__restrict__ steps, int W, int H, int &x, int &y, int h, int sgn, int count) {
+  const int dx = sgn * kCarDx[h], dy = sgn * kCarDy[h];
+  for (int k = 0; k < count; ++k) {
+    const int nx = x + dx, ny = y + dy;
+    if (nx < 0 || nx >= W || ny < 0 || ny >= H) return false;
+    const int bx = sgn > 0 ? x : nx, by = sgn > 0 ? y : ny;
+    if (!(steps[static_cast<size_t>(by) * static_cast<size_t>(W) + static_cast<size_t>(bx)] >> h & 1u)) return false;
+    x = nx;
+    y = ny;
+  }
+  return true;
+}
+
+// rule 30, one lane a state: bits 0 .. 5 of moves[h * n + c] say which of S, L, R, B, BL, BR are allowed out of (c, h).
+// An arc is its polyline walked step by step over the steps plane, first leg in heading h, second in the new heading
+// from the corner cell; the walk ends at the first step that is refused.  The 2 n tests of an arc happen here only.
+__global__ __launch_bounds__(kPlanBlock) void planner_car_moves_kernel(const uint8_t *__restrict__ steps, uint8_t *__restrict__ moves, int W,
+                                                                       int H, int turn, int reverse) {
+  const long long n = static_cast<long long>(W) * H;
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long s = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; s < 8 * n; s += stride) {
+    const int h = static_cast<int>(s / n);
+    const long long i = s - static_cast<long long>(h) * n;
+    const int x = static_cast<int>(i % W), y = static_cast<int>(i / W);
+    uint32_t bits = 0;
+    int px = x, py = y;
+    if (car_leg(steps, W, H, px, py, h, 1, 1)) bits |= 1u << kCarS;
+    px = x, py = y;
+    if (car_leg(steps, W, H, px, py, h, 1, turn)) {
+      int qx = px, qy = py;
+      if (car_leg(steps, W, H, qx, qy, (h + 1) & 7, 1, turn)) bits |= 1u << kCarL;
+      if (car_leg(steps, W, H, px, py, (h + 7) & 7, 1, turn)) bits |= 1u << kCarR;
+    }
+    if (reverse) {
+      px = x, py = y;
+      if (car_leg(steps, W, H, px, py, h, -1, 1)) bits |= 1u << kCarB;
+      px = x, py = y;
+      if (car_leg(steps, W, H, px, py, h, -1, turn)) {
+        int qx = px, qy = py;
+        if (car_leg(steps, W, H, qx, qy, (h + 7) & 7, -1, turn)) bits |= 1u << kCarBL;
+        if (car_leg(steps, W, H, px, py, (h + 1) & 7, -1, turn)) bits |= 1u << kCarBR;
+      }
+    }
+    moves[s] = static_cast<uint8_t>(bits);
+  }
+}
+
+// where primitive p out of (x, y, h) ends, rule 30's table; turn = n
+__device__ __forceinline__ void car_target(int x, int y, int h, int p, int turn, int *tx, int *ty, int *th) {
+  const int sgn = p < kCarB ? 1 : -1;
+  const bool arc = p != kCarS && p != kCarB;
+  const int h2 = !arc ? h : ((p == kCarL || p == kCarBR) ? (h + 1) & 7 : (h + 7) & 7);
+  const int len = arc ? turn : 1;
+  *tx = x + sgn * len * (kCarDx[h] + (arc ? kCarDx[h2] : 0));
+  *ty = y + sgn * len * (kCarDy[h] + (arc ? kCarDy[h2] : 0));
+  *th = h2;
+}
+
+// rule 32's start state into both buffers: 0 at the goal cell's valid states of heading hg (every heading for hg < 0)
+template <bool BOX>
+__global__ __launch_bounds__(kPlanBlock) void planner_init8_kernel(uint32_t *a, uint32_t *b, const uint8_t *__restrict__ vmap, long long n,
+                                                                   long long goal, int hg) {
+  const long long stride = static_cast<long long>(gridDim.x) * kPlanBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kPlanBlock + threadIdx.x; i < n; i += stride) {
+#pragma unroll
+    for (int h = 0; h < 8; ++h) {
+      const bool root = i == goal && (hg < 0 || h == hg) && car_valid<BOX>(vmap, static_cast<size_t>(i), h);
+      const uint32_t v = root ? 0u : kPlanInf;
+      a[static_cast<size_t>(h) * static_cast<size_t>(n) + static_cast<size_t>(i)] = v;
+      b[static_cast<size_t>(h) * static_cast<size_t>(n) + static_cast<size_t>(i)] = v;
+    }
+  }
+}
+
+// rule 32, one pass over one (tile, heading): blockIdx.x = 8 * tile + h.  `in` is only read, `out` only written (the
+// tile's own cells of layer h).  The layer's 66 x 66 halo region sits in LDS as in planner_relax_kernel; the straight
+// moves couple states of this layer alone, along the line +D[h] (S) and -D[h] (B), and are iterated there.  The arcs
+// end in the layers h + 1 and h - 1, up to 2 n cells away: their candidates cost + in[target] are taken once from the
+// read-only input, guarded by the moves byte, and are constants of the pass.  A value therefore crosses one arc a
+// pass at the most; the fixed point is unique (every cost is positive), so the schedule does not decide it.
+// No validity plane: an invalid state has no move and is no goal state, so it holds INF from the init on; the ring
+// outside the grid is loaded as INF.
+__global__ __launch_bounds__(kPlanThreads) void planner_relax8_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
+                                                                      const uint8_t *__restrict__ moves, int W, int H, size_t n,
+                                                                      unsigned tiles_x, int turn, uint32_t rw, uint32_t *changed_word,
+                                                                      uint32_t pass) {
+  __shared__ uint32_t f[kPlanHalo * kPlanHalo];
+  const unsigned tile = blockIdx.x >> 3;
+  const int h = static_cast<int>(blockIdx.x & 7u);
+  const uint32_t *__restrict__ layer = in + static_cast<size_t>(h) * n;
+  const int x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
+  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
+    const int gx = x0 + k % kPlanHalo, gy = y0 + k / kPlanHalo;
+    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
+    f[k] = inside ? layer[static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)] : kPlanInf;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
+  const int off = kCarDy[h] * kPlanHalo + kCarDx[h];
+  const uint32_t fwd = (h & 1) ? 14u : 10u, bwd = fwd * rw, arc_f = 24u * static_cast<uint32_t>(turn), arc_b = arc_f * rw;
+  int idx[kPlanRows];
+  uint32_t cur[kPlanRows], orig[kPlanRows], mask[kPlanRows];
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int k = (1 + ty + r * (kPlanThreads / kPlanTile)) * kPlanHalo + 1 + tx;
+    idx[r] = k;
+    const int gx = x0 + 1 + tx, gy = y0 + 1 + ty + r * (kPlanThreads / kPlanTile);
+    uint32_t m = 0, best = orig[r] = f[k];
+    if (gx < W && gy < H) {
+      m = moves[static_cast<size_t>(h) * n + static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)];
+#pragma unroll
+      for (int p = kCarL; p <= kCarBR; ++p) {
+        if (p == kCarB || !(m >> p & 1u)) continue;
+        int ax, ay, ah;
+        car_target(gx, gy, h, p, turn, &ax, &ay, &ah);  // inside the grid: the moves bit says that every step of the arc is
+        const uint32_t fn = in[static_cast<size_t>(ah) * n + static_cast<size_t>(ay) * static_cast<size_t>(W) + static_cast<size_t>(ax)];
+        const uint32_t c = fn + (p < kCarB ? arc_f : arc_b);  // no wrap: 24 n max(rw, 1) * 8 * cells < 2^32 (kc_planner_solve_car)
+        if (fn != kPlanInf && c < best) best = c;
+      }
+    }
+    cur[r] = best;
+    mask[r] = m;
+  }
+  // an arc may have lowered an owned state below what LDS holds
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) f[idx[r]] = cur[r];
+  __syncthreads();
+  for (int it = 0; it < kPlanLocalIters; ++it) {
+    int ch = 0;
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) {
+      uint32_t best = cur[r];
+      if (mask[r] & (1u << kCarS)) {
+        const uint32_t fn = f[idx[r] + off];
+        if (fn != kPlanInf && fn + fwd < best) best = fn + fwd;
+      }
+      if (mask[r] & (1u << kCarB)) {
+        const uint32_t fn = f[idx[r] - off];
+        if (fn != kPlanInf && fn + bwd < best) best = fn + bwd;
+      }
+      if (best < cur[r]) {
+        cur[r] = best;
+        ch = 1;
+      }
+    }
+    if (!__syncthreads_or(ch)) break;  // every lane has read this iteration's values
+#pragma unroll
+    for (int r = 0; r < kPlanRows; ++r) f[idx[r]] = cur[r];
+    __syncthreads();
+  }
+  int changed = 0;
+#pragma unroll
+  for (int r = 0; r < kPlanRows; ++r) {
+    const int gx = x0 + 1 + tx, gy = y0 + 1 + ty + r * (kPlanThreads / kPlanTile);
+    if (gx < W && gy < H) out[static_cast<size_t>(h) * n + static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)] = cur[r];
+    changed |= cur[r] != orig[r];
+  }
+  if (__syncthreads_or(changed) && threadIdx.x == 0) *changed_word = pass;
+}
+
+// rule 33: one wavefront, six lanes, a primitive each in rule 30's order.  states[k] = 8 * cell + heading of state k, and
+// above that (from bit kCarMoveShift) the primitive taken out of it; the solve's range test keeps 8 * cells below that bit.
+// out[0] = states written, out[1] = 0 done / 1 capacity / 2 the minimum is not the field.
+constexpr int kCarMoveShift = 28;
+__global__ __launch_bounds__(64) void planner_walk8_kernel(const uint32_t *field, const uint8_t *moves, int W, int H, size_t n, int sx, int sy,
+                                                           int sh, int turn, uint32_t rw, int32_t *states, uint32_t cap, uint32_t *out) {
+  const int lane = threadIdx.x;
+  int cx = sx, cy = sy, chd = sh;
+  uint32_t count = 0, status = 0;
+  for (;;) {
+    const size_t c = static_cast<size_t>(cy) * static_cast<size_t>(W) + static_cast<size_t>(cx);
+    if (count >= cap) {
+      status = 1;
+      break;
+    }
+    const uint32_t fc = field[static_cast<size_t>(chd) * n + c];
+    unsigned long long key = ~0ull;
+    if (fc != 0u && lane < 6 && (moves[static_cast<size_t>(chd) * n + c] >> lane & 1u)) {
+      int ax, ay, ah;
+      car_target(cx, cy, chd, lane, turn, &ax, &ay, &ah);
+      const uint32_t base = (lane == kCarS || lane == kCarB) ? ((chd & 1) ? 14u : 10u) : 24u * static_cast<uint32_t>(turn);
+      const unsigned long long cost = static_cast<unsigned long long>(base) * (lane < kCarB ? 1ull : static_cast<unsigned long long>(rw));
+      // 64 bits hold an unreached state's 0xFFFFFFFF + cost as well; it never equals field[current]
+      key = ((static_cast<unsigned long long>(field[static_cast<size_t>(ah) * n + static_cast<size_t>(ay) * static_cast<size_t>(W) +
+                                                    static_cast<size_t>(ax)]) + cost) << 3) | static_cast<unsigned long long>(lane);
+    }
+#pragma unroll
+    for (int d = 4; d >= 1; d >>= 1) {
+      const unsigned long long o = __shfl_xor(key, d, 64);
+      key = o < key ? o : key;
+    }
+    key = __shfl(key, 0, 64);
+    const int q = static_cast<int>(key & 7ull);
+    const bool last = fc == 0u;
+    const bool off_field = !last && (key == ~0ull || (key >> 3) != static_cast<unsigned long long>(fc));
+    if (lane == 0)
+      states[count] = static_cast<int32_t>((8u * static_cast<uint32_t>(c) + static_cast<uint32_t>(chd)) |
+                                           ((last || off_field) ? 0u : static_cast<uint32_t>(q) << kCarMoveShift));
+    ++count;
+    if (last) break;
+    if (off_field) {  // not on a converged field with a reachable start
+      status = 2;
+      break;
+    }
+    int ax, ay, ah;
+    car_target(cx, cy, chd, q, turn, &ax, &ay, &ah);
+    cx = ax;
+    cy = ay;
+    chd = ah;
+  }
+  if (lane == 0) {
+    out[0] = count;
+    out[1] = status;
+  }
+}
+
 // The kernels' status words, one struct on the device and in pinned memory: a read-back copies a member onto itself.
 struct PlanWords {
   uint32_t changed;                                 // the last pass that changed a cell
@@ -964,6 +1234,18 @@ struct kc_planner {
   DevBuf<int16_t> d_offs;
   DevBuf<uint8_t> d_turn, d_valid4;
   DevBuf<uint32_t> d_field4[2];
+  // car motion (rules 27 to 36): on while car_turn > 0
+  int car_turn = 0;            // n, the turn length in cells
+  uint32_t car_rw = 0;         // the reverse weight, 0: no reverse
+  uint32_t car_a2 = 0, car_b2 = 0;  // the box footprint's masks (d_offs, or_ends, d_valid4 as the oriented mode's); 0, 0: the disc
+  bool car_solve = false;      // the last solve was kc_planner_solve_car: d_field8, d_moves, start_heading, car_states
+  bool car_have_moves = false; // d_moves holds rule 30's bytes of (the validity map in use, car_turn, car_rw)
+  int start_heading = 0;
+  std::vector<int32_t> car_states;  // the walk's states, 8 * cell + heading; `path` then holds rule 34's expansion
+  std::vector<int32_t> car_moves;   // the primitive taken out of each state but the last
+  float car_ms[3] = {0.0f, 0.0f, 0.0f};  // host clock around the maps + moves, the field and the walk, each ended by its read-back
+  DevBuf<uint8_t> d_steps, d_moves;
+  DevBuf<uint32_t> d_field8[2];
   // the replan (rules 19 and 20)
   bool fld_ok = false;         // d_field[final_buf] is the fixed point of (fld_goal, valid_r2, valid_unknown, the table) on a
                                // W x H grid whose maps are d_valid (d_pen), the goal valid; a new grid of that shape leaves it
@@ -996,7 +1278,7 @@ void forget_walk(kc_planner *c) { c->have_path = c->have_short = false; }
 
 // also what a solve starts with: its outputs say "nothing" until it ends
 void forget_solve(kc_planner *c, uint32_t *cost_out = nullptr, int *passes_out = nullptr) {
-  c->solved = c->or_solve = c->fld_ok = c->explored = false;
+  c->solved = c->or_solve = c->car_solve = c->fld_ok = c->explored = false;
   c->frontiers.clear();
   c->status = -1;
   c->cost = kPlanInf;
@@ -1008,6 +1290,7 @@ void forget_solve(kc_planner *c, uint32_t *cost_out = nullptr, int *passes_out =
 void forget_maps(kc_planner *c, bool disc, bool oriented) {
   if (disc) c->have_valid = false;
   if (oriented) c->or_have_valid = false;
+  c->car_have_moves = false;  // rule 30's bytes are made from a validity map
   forget_solve(c);
 }
 
@@ -1132,10 +1415,13 @@ int planner_walk_oriented(kc_planner *c) {
   return KC_OK;
 }
 
+int planner_walk_car(kc_planner *c);
+
 // the walk of the last solve (status KC_PLAN_FOUND), once: c->path, and c->path_clear2 with the clearance cost on
 int planner_walk(kc_planner *c) {
   if (c->have_path) return KC_OK;
   if (c->or_solve) return planner_walk_oriented(c);
+  if (c->car_solve) return planner_walk_car(c);
   KC_HIP(hipSetDevice(c->device));
   const bool pen_on = c->clear_c2 > 0;
   const uint32_t *pen = pen_on ? c->d_pen.p : nullptr;
@@ -1211,6 +1497,99 @@ int planner_validity(kc_planner *c, uint32_t r2, int unknown_blocks) {
   c->have_valid = true;
   c->valid_r2 = r2;
   c->valid_unknown = unknown_blocks;
+  return KC_OK;
+}
+
+// rule 14's four offset lists of the box (a2, b2) into d_offs and or_ends; the caller drops the maps made from another box
+int planner_upload_box(kc_planner *c, uint32_t a2, uint32_t b2) {
+  std::vector<int16_t> all;
+  PlanMaskEnds ends = {};
+  for (int k = 0; k < 4; ++k) {
+    const std::vector<int16_t> o = oriented_offsets(k, a2, b2);
+    all.insert(all.end(), o.begin(), o.end());
+    ends.at[k + 1] = static_cast<uint32_t>(all.size() / 2);
+  }
+  KC_HIP(hipSetDevice(c->device));
+  KC_TRY(c->d_offs.reserve(all.size()));
+  // pageable memory: the copy has left the vector when the call returns
+  KC_HIP(hipMemcpyAsync(c->d_offs.p, all.data(), all.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->or_ends = ends;
+  return KC_OK;
+}
+
+// rules 14 and 15: the class bits and the turn bit of the box (a2, b2) whose offsets d_offs holds into d_valid4, the turning
+// disc into d_turn, unless they are there
+int planner_oriented_validity(kc_planner *c, uint32_t a2, uint32_t b2, int unknown_blocks) {
+  if (c->or_have_valid && c->or_valid_unknown == unknown_blocks) return KC_OK;
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const long long n = static_cast<long long>(W) * H;
+  const unsigned blocks = plan_blocks_for(n);
+  c->or_have_valid = false;
+  const uint32_t t2 = a2 + b2;
+  const int R = plan_isqrt(t2);
+  KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_turn.reserve(static_cast<size_t>(n)));
+  KC_TRY(c->d_valid4.reserve(static_cast<size_t>(n)));
+  // rule 15 is rule 2's disc with r2 = T2: the row distances are scratch, the disc solve's d_valid is not touched
+  hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
+  hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_turn.p, W, H, R, t2);
+  hipLaunchKernelGGL(planner_oriented_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_turn.p, c->d_offs.p,
+                     c->or_ends, c->d_valid4.p, W, H, unknown_blocks);
+  KC_HIP(hipGetLastError());
+  c->or_have_valid = true;
+  c->or_valid_unknown = unknown_blocks;
+  return KC_OK;
+}
+
+// rule 34: the cell indices of every unit step of primitive p out of (cell, h), first leg then second, appended
+void car_expand(const kc_planner *c, int32_t cell, int h, int p, std::vector<int32_t> *cells) {
+  static const int dx[8] = {1, 1, 0, -1, -1, -1, 0, 1}, dy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+  const int sgn = p < 3 ? 1 : -1;
+  const bool arc = p != 0 && p != 3;
+  const int h2 = !arc ? h : ((p == 1 || p == 5) ? (h + 1) & 7 : (h + 7) & 7);
+  const int len = arc ? c->car_turn : 1;
+  int x = cell % c->W, y = cell / c->W;
+  for (int leg = 0; leg < (arc ? 2 : 1); ++leg) {
+    const int hl = leg == 0 ? h : h2;
+    for (int k = 0; k < len; ++k) {
+      x += sgn * dx[hl];
+      y += sgn * dy[hl];
+      cells->push_back(y * c->W + x);
+    }
+  }
+}
+
+// rule 33 over the last car solve (status KC_PLAN_FOUND), once: c->car_states, c->car_moves, and c->path with rule 34's expansion
+int planner_walk_car(kc_planner *c) {
+  KC_HIP(hipSetDevice(c->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  // every primitive lowers the field by 10 at least, and no state comes twice
+  const size_t cap = std::min<size_t>(8 * n, static_cast<size_t>(c->cost / 10u)) + 2;
+  KC_TRY(c->d_path.reserve(cap));
+  KC_TRY(c->h_path.reserve(cap));
+  hipLaunchKernelGGL(planner_walk8_kernel, dim3(1), dim3(64), 0, c->stream, c->d_field8[c->final_buf].p, c->d_moves.p, c->W, c->H, n, c->start[0],
+                     c->start[1], c->start_heading, c->car_turn, c->car_rw, c->d_path.p, static_cast<uint32_t>(cap), &c->d_word.p->walk_count);
+  uint32_t count = 0;
+  KC_TRY(planner_walk_fetch(c, cap, false, "car", "states", &count));
+  c->car_ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  c->car_states.resize(count);
+  c->car_moves.resize(count - 1);
+  c->path.clear();
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t word = static_cast<uint32_t>(c->h_path.p[k]);
+    const int32_t state = static_cast<int32_t>(word & ((1u << kCarMoveShift) - 1u));
+    c->car_states[k] = state;
+    if (k == 0) c->path.push_back(state / 8);
+    if (k + 1 < count) {
+      c->car_moves[k] = static_cast<int32_t>(word >> kCarMoveShift);
+      car_expand(c, state / 8, state % 8, c->car_moves[k], &c->path);
+    }
+  }
+  c->path_clear2 = static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
+  c->have_path = true;
   return KC_OK;
 }
 
@@ -1354,6 +1733,7 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve before a grid was set");
   if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve with the oriented footprint on: kc_planner_solve_oriented");
+  if (c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve with car motion on: kc_planner_solve_car");
   if (r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
     KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
   const long long n = static_cast<long long>(c->W) * c->H;
@@ -1387,7 +1767,7 @@ int kc_planner_replan(kc_planner *c, const int start_cell[2], const int goal_cel
   c->rp_touched = c->rp_tiles = 0;
   const int unknown_blocks = allow_unknown ? 0 : 1;
   // rule 20's fall-back: no kept field, or one of another problem; every refusal of kc_planner_solve is its own
-  if (!c->have_grid || c->or_a2 > 0 || !c->fld_ok || c->fld_goal[0] != goal_cell[0] || c->fld_goal[1] != goal_cell[1] ||
+  if (!c->have_grid || c->or_a2 > 0 || c->car_turn > 0 || !c->fld_ok || c->fld_goal[0] != goal_cell[0] || c->fld_goal[1] != goal_cell[1] ||
       c->valid_r2 != r2 || c->valid_unknown != unknown_blocks)
     return kc_planner_solve(c, start_cell, goal_cell, r2, allow_unknown, status_out, cost_out, passes_out);
   // r2, the penalty table and the shape are the kept solve's: its range checks hold
@@ -1457,6 +1837,7 @@ int kc_planner_get_field(kc_planner *c, uint32_t *field_out, uint8_t *valid_out,
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (!c->solved) KC_FAIL(KC_ERR_STATE, "kc_planner_get_field before kc_planner_solve");
   if (c->or_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_field after an oriented solve: kc_planner_get_oriented_field");
+  if (c->car_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_field after a car solve: kc_planner_get_car_field");
   const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
   if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
   KC_HIP(hipSetDevice(c->device));
@@ -1488,6 +1869,7 @@ int kc_planner_set_clearance_cost(kc_planner *c, uint32_t c2, const uint32_t *pe
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   const bool on = c2 > 0 && pen_by_d2 != nullptr;
   if (on && c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "a clearance cost cannot be set while the oriented footprint is on (rule 18)");
+  if (on && c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "a clearance cost cannot be set while car motion is on (rule 35)");
   if (on) {
     if (c2 > static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
       KC_FAIL(KC_ERR_RANGE, "a clearance reach of C2 = %u is wider than %d cells", c2, KC_PLANNER_MAX_RADIUS_CELLS);
@@ -1531,6 +1913,7 @@ int kc_planner_shortcut(kc_planner *c, int max_span, size_t *count_out, uint32_t
   if (count_out) *count_out = 0;
   if (!c->solved || c->explored || c->status != KC_PLAN_FOUND) KC_FAIL(KC_ERR_STATE, "kc_planner_shortcut without a path");
   if (c->or_solve) KC_FAIL(KC_ERR_STATE, "no any-angle path in oriented mode: a segment at an arbitrary angle has no class (rule 18)");
+  if (c->car_solve) KC_FAIL(KC_ERR_STATE, "no any-angle path with car motion: a segment at an arbitrary angle is no primitive (rule 35)");
   if (max_span < 1 || max_span > KC_PLANNER_MAX_SPAN)
     KC_FAIL(KC_ERR_RANGE, "max_span %d is outside 1 .. %d", max_span, KC_PLANNER_MAX_SPAN);
   KC_TRY(planner_shortcut(c, max_span));
@@ -1567,26 +1950,13 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
     return KC_OK;
   }
   if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "the oriented footprint cannot be set while a clearance cost is on (rule 18)");
+  if (c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "the oriented mode cannot be set while car motion is on: kc_planner_set_car takes the box (rule 35)");
   if (turn10 < 1u || turn10 > 10000u) KC_FAIL(KC_ERR_RANGE, "turn10 = %u is outside 1 .. 10000", turn10);
   const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
   if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
     KC_FAIL(KC_ERR_RANGE, "a turning disc of T2 = %llu is wider than %d cells", t2, KC_PLANNER_MAX_RADIUS_CELLS);
   const bool new_box = c->or_a2 != a2 || c->or_b2 != b2;
-  if (new_box) {
-    std::vector<int16_t> all;
-    PlanMaskEnds ends = {};
-    for (int k = 0; k < 4; ++k) {
-      const std::vector<int16_t> o = oriented_offsets(k, a2, b2);
-      all.insert(all.end(), o.begin(), o.end());
-      ends.at[k + 1] = static_cast<uint32_t>(all.size() / 2);
-    }
-    KC_HIP(hipSetDevice(c->device));
-    KC_TRY(c->d_offs.reserve(all.size()));
-    // pageable memory: the copy has left the vector when the call returns
-    KC_HIP(hipMemcpyAsync(c->d_offs.p, all.data(), all.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-    KC_HIP(hipStreamSynchronize(c->stream));
-    c->or_ends = ends;
-  }
+  if (new_box) KC_TRY(planner_upload_box(c, a2, b2));
   c->or_a2 = a2;
   c->or_b2 = b2;
   c->or_turn10 = turn10;
@@ -1598,6 +1968,7 @@ int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_
                               int *status_out, uint32_t *cost_out, int *passes_out) {
   if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_oriented before a grid was set");
+  if (c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_oriented with car motion on: kc_planner_solve_car");
   if (c->or_a2 == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_oriented before kc_planner_set_oriented");
   if (start_class < 0 || start_class > 3) KC_FAIL(KC_ERR_INVALID, "start class %d is outside 0 .. 3", start_class);
   const long long n = static_cast<long long>(c->W) * c->H;
@@ -1611,22 +1982,7 @@ int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_
   c->or_solve = true;
   const unsigned blocks = plan_blocks_for(n);
   const int unknown_blocks = allow_unknown ? 0 : 1;
-  if (!c->or_have_valid || c->or_valid_unknown != unknown_blocks) {
-    c->or_have_valid = false;
-    const uint32_t t2 = c->or_a2 + c->or_b2;
-    const int R = plan_isqrt(t2);
-    KC_TRY(c->d_rowd.reserve(static_cast<size_t>(n)));
-    KC_TRY(c->d_turn.reserve(static_cast<size_t>(n)));
-    KC_TRY(c->d_valid4.reserve(static_cast<size_t>(n)));
-    // rule 15 is rule 2's disc with r2 = T2: the row distances are scratch, the disc solve's d_valid is not touched
-    hipLaunchKernelGGL(planner_rowdist_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_rowd.p, W, H, R, unknown_blocks);
-    hipLaunchKernelGGL(planner_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_rowd.p, c->d_turn.p, W, H, R, t2);
-    hipLaunchKernelGGL(planner_oriented_valid_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_turn.p, c->d_offs.p,
-                       c->or_ends, c->d_valid4.p, W, H, unknown_blocks);
-    KC_HIP(hipGetLastError());
-    c->or_have_valid = true;
-    c->or_valid_unknown = unknown_blocks;
-  }
+  KC_TRY(planner_oriented_validity(c, c->or_a2, c->or_b2, unknown_blocks));
   const long long goal = plan_cell_index(c, goal_cell);
   KC_TRY(c->d_field4[0].reserve(4 * static_cast<size_t>(n)));
   KC_TRY(c->d_field4[1].reserve(4 * static_cast<size_t>(n)));
@@ -1684,6 +2040,160 @@ int kc_planner_get_oriented_path(kc_planner *c, int32_t *states_ijk_out, size_t 
   return KC_OK;
 }
 
+int kc_planner_set_car(kc_planner *c, int turn_cells, uint32_t reverse_weight, uint32_t a2, uint32_t b2) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (turn_cells == 0) {
+    if (c->car_turn == 0) return KC_OK;  // off already: nothing of another mode's is touched
+    const bool had_box = c->car_a2 > 0;
+    c->car_turn = 0;
+    c->car_rw = c->car_a2 = c->car_b2 = 0;
+    forget_maps(c, false, had_box);  // the box's masks leave with it; the disc's map is the disc solve's own
+    return KC_OK;
+  }
+  if (turn_cells < 0 || turn_cells > KC_PLANNER_MAX_TURN_CELLS)
+    KC_FAIL(KC_ERR_RANGE, "a turn of %d cells is outside 1 .. %d", turn_cells, KC_PLANNER_MAX_TURN_CELLS);
+  if (reverse_weight > static_cast<uint32_t>(KC_PLANNER_MAX_REVERSE_WEIGHT))
+    KC_FAIL(KC_ERR_RANGE, "a reverse weight of %u is outside 0 .. %d", reverse_weight, KC_PLANNER_MAX_REVERSE_WEIGHT);
+  if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "car motion cannot be set while a clearance cost is on (rule 35)");
+  if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "car motion cannot be set while the oriented mode is on: hand the box to kc_planner_set_car (rule 35)");
+  if (a2 == 0 && b2 != 0) KC_FAIL(KC_ERR_INVALID, "a box footprint needs a2 > 0 (a2 = b2 = 0 is the disc)");
+  const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
+  if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+    KC_FAIL(KC_ERR_RANGE, "a box of A2 + B2 = %llu is wider than %d cells", t2, KC_PLANNER_MAX_RADIUS_CELLS);
+  const bool new_box = c->car_turn == 0 || c->car_a2 != a2 || c->car_b2 != b2;
+  if (new_box && a2 > 0) KC_TRY(planner_upload_box(c, a2, b2));
+  c->car_turn = turn_cells;
+  c->car_rw = reverse_weight;
+  c->car_a2 = a2;
+  c->car_b2 = b2;
+  forget_maps(c, false, new_box);  // rule 30's bytes go in any case
+  return KC_OK;
+}
+
+int kc_planner_solve_car(kc_planner *c, const int start_cell[2], int start_heading, const int goal_cell[2], int goal_heading, uint32_t r2,
+                         int allow_unknown, int *status_out, uint32_t *cost_out, int *passes_out) {
+  if (!c || !start_cell || !goal_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_car before a grid was set");
+  if (c->car_turn == 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve_car before kc_planner_set_car");
+  if (start_heading < 0 || start_heading > 7) KC_FAIL(KC_ERR_INVALID, "start heading %d is outside 0 .. 7", start_heading);
+  if (goal_heading < -1 || goal_heading > 7) KC_FAIL(KC_ERR_INVALID, "goal heading %d is outside -1 .. 7", goal_heading);
+  const bool box = c->car_a2 > 0;
+  if (!box && r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
+    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  const long long n = static_cast<long long>(c->W) * c->H;
+  // field <= 24 n max(rw, 1) * (8 * cells - 1): the sums of the relaxation stay below the 0xFFFFFFFF of "nothing arrives",
+  // and 8 * cells below the bit the walk keeps its primitive in
+  if (24ull * static_cast<unsigned long long>(c->car_turn) * std::max<uint32_t>(c->car_rw, 1u) * 8ull * static_cast<unsigned long long>(n) > 0xFFFFFFFEull)
+    KC_FAIL(KC_ERR_RANGE, "arcs of %d cells at reverse weight %u over 8 x %lld states do not fit the 32-bit field", c->car_turn, c->car_rw, n);
+  KC_HIP(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int W = c->W, H = c->H;
+  const auto now = [] { return std::chrono::steady_clock::now(); };
+  const auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<float, std::milli>(now() - t).count(); };
+  forget_solve(c, cost_out, passes_out);  // the disc's kept field goes as with any other solve
+  c->car_solve = true;
+  c->car_ms[0] = c->car_ms[1] = c->car_ms[2] = 0.0f;
+  auto t0 = now();
+  const unsigned blocks = plan_blocks_for(n);
+  const int unknown_blocks = allow_unknown ? 0 : 1;
+  // rule 28: the maps of the footprint in use, made by the kernels of rules 2 and 14 as they are
+  if (box) {
+    if (!c->or_have_valid || c->or_valid_unknown != unknown_blocks) c->car_have_moves = false;
+    KC_TRY(planner_oriented_validity(c, c->car_a2, c->car_b2, unknown_blocks));
+  } else if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) {
+    c->car_have_moves = false;
+    KC_TRY(planner_validity(c, r2, unknown_blocks));
+  }
+  const uint8_t *vmap = box ? c->d_valid4.p : c->d_valid.p;
+  if (!c->car_have_moves) {
+    KC_TRY(c->d_steps.reserve(static_cast<size_t>(n)));
+    KC_TRY(c->d_moves.reserve(8 * static_cast<size_t>(n)));
+    with_bool(box, [&](auto on) {
+      hipLaunchKernelGGL(planner_car_steps_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanBlock), 0, s, vmap, c->d_steps.p, W, H);
+    });
+    hipLaunchKernelGGL(planner_car_moves_kernel, dim3(plan_blocks_for(8 * n)), dim3(kPlanBlock), 0, s, c->d_steps.p, c->d_moves.p, W, H,
+                       c->car_turn, c->car_rw > 0 ? 1 : 0);
+    KC_HIP(hipGetLastError());
+    c->car_have_moves = true;
+  }
+  const long long goal = plan_cell_index(c, goal_cell);
+  KC_TRY(c->d_field8[0].reserve(8 * static_cast<size_t>(n)));
+  KC_TRY(c->d_field8[1].reserve(8 * static_cast<size_t>(n)));
+  with_bool(box, [&](auto on) {
+    hipLaunchKernelGGL(planner_init8_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field8[0].p, c->d_field8[1].p, vmap, n,
+                       goal, goal_heading);
+  });
+  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), s));
+  KC_HIP(hipGetLastError());
+  KC_HIP(hipStreamSynchronize(s));  // the maps and the moves end here, inside the first phase's clock
+  c->car_ms[0] = ms_since(t0);
+  t0 = now();
+  c->final_buf = 0;  // both buffers hold the initial state
+  uint32_t passes = 0;
+  if (goal >= 0) {
+    const auto pass8 = [&](uint32_t pass, int b) {
+      hipLaunchKernelGGL(planner_relax8_kernel, dim3(8u * c->tiles_x * c->tiles_y), dim3(kPlanThreads), 0, s, c->d_field8[b].p, c->d_field8[b ^ 1].p,
+                         c->d_moves.p, W, H, static_cast<size_t>(n), c->tiles_x, c->car_turn, c->car_rw, &c->d_word.p->changed, pass);
+    };
+    KC_TRY(planner_relax(c, pass8, 8ull * n, "car", &c->final_buf, &passes));
+  }
+  c->start_heading = start_heading;
+  // the start needs its own heading, the goal the asked one or any (rule 32); the state field is not kept (rule 35)
+  const uint32_t start_mask = box ? 1u << (start_heading & 3) : 0xFFu;
+  const uint32_t goal_mask = !box ? 0xFFu : (goal_heading < 0 ? 15u : 1u << (goal_heading & 3));
+  KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field8[c->final_buf].p + static_cast<size_t>(start_heading) * static_cast<size_t>(n), vmap,
+                        start_mask, goal_mask, false, status_out, cost_out));
+  c->car_ms[1] = ms_since(t0);
+  if (passes_out) *passes_out = static_cast<int>(passes);
+  return KC_OK;
+}
+
+int kc_planner_get_car_field(kc_planner *c, uint32_t *field8_out, uint8_t *moves8_out, uint8_t *valid_out, size_t cap) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!c->solved || !c->car_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_car_field before kc_planner_solve_car");
+  const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (n > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", n, cap);
+  KC_HIP(hipSetDevice(c->device));
+  const bool box = c->car_a2 > 0;
+  if (field8_out) KC_HIP(hipMemcpyAsync(field8_out, c->d_field8[c->final_buf].p, 8 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (moves8_out) KC_HIP(hipMemcpyAsync(moves8_out, c->d_moves.p, 8 * n, hipMemcpyDeviceToHost, c->stream));
+  if (valid_out) KC_HIP(hipMemcpyAsync(valid_out, box ? c->d_valid4.p : c->d_valid.p, n, hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  if (valid_out)  // bit h of a cell's byte: heading h is valid there
+    for (size_t i = 0; i < n; ++i) valid_out[i] = box ? static_cast<uint8_t>((valid_out[i] & 15u) * 17u) : static_cast<uint8_t>(valid_out[i] ? 0xFFu : 0u);
+  return KC_OK;
+}
+
+int kc_planner_get_car_path(kc_planner *c, int32_t *states_ijh_out, int32_t *moves_out, size_t cap, size_t *count_out) {
+  if (!c || !count_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *count_out = 0;
+  if (!c->solved || !c->car_solve) KC_FAIL(KC_ERR_STATE, "kc_planner_get_car_path before kc_planner_solve_car");
+  if (c->status != KC_PLAN_FOUND) return KC_OK;  // no path: zero states
+  KC_TRY(planner_walk(c));
+  const size_t m = c->car_states.size();
+  *count_out = m;
+  if (!states_ijh_out && !moves_out) return KC_OK;  // the count alone
+  if (m > cap) KC_FAIL(KC_ERR_RANGE, "%zu states do not fit the output capacity %zu", m, cap);
+  for (size_t k = 0; k < m; ++k) {
+    const int32_t cell = c->car_states[k] / 8;
+    if (states_ijh_out) {
+      states_ijh_out[3 * k] = cell % c->W;
+      states_ijh_out[3 * k + 1] = cell / c->W;
+      states_ijh_out[3 * k + 2] = c->car_states[k] % 8;
+    }
+    if (moves_out && k + 1 < m) moves_out[k] = c->car_moves[k];
+  }
+  return KC_OK;
+}
+
+int kc_planner_car_info(kc_planner *c, int *turn_cells_out, uint32_t *reverse_weight_out, float phase_ms_out[3]) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (turn_cells_out) *turn_cells_out = c->car_turn;
+  if (reverse_weight_out) *reverse_weight_out = c->car_rw;
+  if (phase_ms_out) std::copy(c->car_ms, c->car_ms + 3, phase_ms_out);
+  return KC_OK;
+}
+
 int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint32_t min_cost, uint32_t min_size, int *status_out,
                        uint32_t *components_out, size_t *count_out, int *passes_out, int *label_passes_out) {
   if (!c || !robot_cell || !status_out) KC_FAIL(KC_ERR_INVALID, "null argument");
@@ -1696,6 +2206,7 @@ int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_explore before a grid was set");
   if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_explore with the oriented footprint on (rule 22)");
   if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_explore with a clearance cost set (rule 22)");
+  if (c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_explore with car motion on (rule 35)");
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int W = c->W, H = c->H;

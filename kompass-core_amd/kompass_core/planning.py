@@ -21,7 +21,14 @@ path.
 beside unexplored ones) that the robot's disc can reach without crossing an unexplored cell, as 8-connected components,
 nearest first by travel cost, each with its nearest cell, its centroid and the path to it.  The reference leaves
 frontier detection to its ROS side, as it does the world map; here it runs on the map where it lies on the device.
-Not combined with a clearance cost or the oriented footprint: a frontier is ranked by plain travel cost to a cell."""
+Not combined with a clearance cost or the oriented footprint: a frontier is ranked by plain travel cost to a cell.
+`motion="car"` (rules 27 to 36) plans for a car-like (Ackermann) robot: the state is (cell, one of eight directed
+headings), the transitions are one straight step and 45-degree arcs whose legs follow from `min_turning_radius`, reverse
+is optional and comes at a price, there is no turn in place, and `goal_yaw` is honoured.  That is the restricted,
+deterministic counterpart of the reference's SE(2) planning for its Ackermann users.  The planned polyline has
+n = ceil(min_turning_radius / resolution * tan(pi / 8)) cells of tangent on either side of every 45-degree corner, so a
+circular fillet of at least the turning radius fits; it leaves the polyline by at most 0.199 n cells: allow for that in
+`margin`.  The polyline is what is planned and checked, not the fillet."""
 import math
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
@@ -44,7 +51,9 @@ class Frontier(NamedTuple):
 class GridPlanner:
     def __init__(self, robot: Robot, allow_unknown: bool = True, margin: float = 0.0, simplify: bool = False,
                  clearance_reach: float = 0.0, clearance_weight: float = 0.0, any_angle: bool = False,
-                 max_span: int = 128, footprint: str = "disc", turn_cost: float = 1.0):
+                 max_span: int = 128, footprint: str = "disc", turn_cost: float = 1.0, motion: str = "grid",
+                 min_turning_radius: float = 0.0, allow_reverse: bool = False, reverse_weight: int = 2,
+                 goal_heading: str = "yaw"):
         """allow_unknown: UNEXPLORED cells can be crossed (default) or block like OCCUPIED ones.
         margin: metres added to the robot's radius.  simplify: drop the interior points of straight runs.
         clearance_reach, clearance_weight: see set_clearance_cost; the defaults leave it off.
@@ -53,7 +62,27 @@ class GridPlanner:
         than that path came.  `simplify` is then ignored: collinear runs within the span are subsumed.
         footprint: "disc" (default) or "oriented": the box's own footprint over four heading classes, BOX robots only,
         not together with a clearance cost or `any_angle`.  turn_cost: straight-cell lengths a turn of 45 degrees
-        costs (0.1 .. 1000); `get_cost()` includes the turns."""
+        costs (0.1 .. 1000); `get_cost()` includes the turns.
+        motion: "grid" (default) or "car": (cell, eight headings) states, a straight step and 45-degree arcs of
+        `min_turning_radius` metres (at most 8 turn cells at the map's resolution), no turn in place; with
+        `allow_reverse` also backward at `reverse_weight` (1 .. 16) times the forward cost.  goal_heading: "yaw" ends
+        the path in setup_problem's goal_yaw (to the nearest 45 degrees), "any" in whatever heading is cheapest.  With
+        footprint="oriented" the box is tested by heading and `turn_cost` plays no part.  Not together with a
+        clearance cost, `any_angle` or find_frontiers / explore; replan() is then a full solve."""
+        if motion not in ("grid", "car"):
+            raise ValueError(f"motion must be 'grid' or 'car', got {motion!r}")
+        if goal_heading not in ("yaw", "any"):
+            raise ValueError(f"goal_heading must be 'yaw' or 'any', got {goal_heading!r}")
+        self.motion = motion
+        if motion == "car":
+            if clearance_reach > 0.0 and clearance_weight > 0.0:
+                raise ValueError("car motion cannot be combined with a clearance cost")
+            if any_angle:
+                raise ValueError("car motion has no any-angle path: a segment at an arbitrary angle is no primitive")
+            if not (math.isfinite(min_turning_radius) and min_turning_radius > 0.0):
+                raise ValueError(f"car motion needs a positive min_turning_radius, got {min_turning_radius}")
+            if allow_reverse and not 1 <= int(reverse_weight) <= 16:
+                raise ValueError(f"reverse_weight must be in 1 .. 16, got {reverse_weight}")
         if footprint not in ("disc", "oriented"):
             raise ValueError(f"footprint must be 'disc' or 'oriented', got {footprint!r}")
         self.footprint = footprint
@@ -85,6 +114,9 @@ class GridPlanner:
             self.set_clearance_cost(clearance_reach, clearance_weight)
         if footprint == "oriented":
             self._planner.set_oriented_footprint(True, float(turn_cost))
+        if motion == "car":
+            self._planner.set_car_motion(True, float(min_turning_radius), bool(allow_reverse), int(reverse_weight),
+                                         goal_heading == "yaw")
 
     def set_clearance_cost(self, reach: float, weight: float):
         """Surcharge the cells within `reach` metres beyond the footprint (radius + margin): `weight` straight-cell
@@ -172,6 +204,9 @@ class GridPlanner:
         of the last setup_problem stays: the next solve() or replan() plans from its start to its goal, not from
         (robot_x, robot_y).  A map or metadata given here replaces the grid and the bounds as setup_problem's would, and
         that problem's start and goal are then taken into the new bounds' cells again."""
+        if self.motion == "car":
+            raise ValueError("exploration is not combined with car motion: a frontier is ranked by the disc's travel "
+                             "cost to a cell, and the car's field is one of (cell, heading) states")
         if self.footprint == "oriented":
             raise ValueError("exploration is not combined with the oriented footprint: a frontier is ranked by the "
                              "disc's travel cost to a cell, and the oriented field is one of (cell, heading) states")
@@ -270,9 +305,20 @@ class GridPlanner:
 
     def get_path_states(self):
         """(n, 3) int32 states (i, j, k) of the oriented path: cell and heading class, k = 0 .. 3 for the box's length
-        axis along (1, 0), (1, 1), (0, 1), (-1, 1); a turn repeats its cell.  Empty without a path or with
-        footprint="disc"."""
+        axis along (1, 0), (1, 1), (0, 1), (-1, 1); a turn repeats its cell.  With motion="car": (i, j, h), h = 0 .. 7
+        the heading E, NE, N, NW, W, SW, S, SE, one row per primitive boundary.  Empty without a path or with
+        footprint="disc" and motion="grid"."""
         return self._planner.get_path_states()
+
+    def get_path_moves(self):
+        """(n - 1,) int32 primitive ids between the rows of get_path_states() with motion="car": 0 S (a step ahead),
+        1 L / 2 R (a 45-degree arc ahead), 3 B, 4 BL, 5 BR (the same backward).  Empty otherwise."""
+        return self._planner.get_path_moves()
+
+    @property
+    def turn_cells(self) -> int:
+        """The legs of a 45-degree arc in cells at the map's resolution; 0 with motion="grid"."""
+        return self._planner.get_car_turn_cells()
 
     @property
     def any_angle_length(self) -> float:

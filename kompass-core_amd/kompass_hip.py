@@ -295,6 +295,12 @@ SIGNATURES = {
                                             C.POINTER(C.c_int)]),
     "kc_planner_get_oriented_field": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, _sz]),
     "kc_planner_get_oriented_path": (C.c_int, [_vp, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_set_car": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kc_planner_solve_car": (C.c_int, [_vp, _ip, C.c_int, _ip, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_int),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "kc_planner_get_car_field": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, _sz]),
+    "kc_planner_get_car_path": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz)]),
+    "kc_planner_car_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "kc_planner_replan": (C.c_int, [_vp, _ip, _ip, C.c_uint32, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_int)]),
     "kc_planner_replan_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
@@ -1282,6 +1288,8 @@ PLAN_FRONTIER_DTYPE = np.dtype([("sum_i", np.uint64), ("sum_j", np.uint64), ("si
 PLAN_INF = 0xFFFFFFFF
 PLAN_CLEAR_FAR = 0xFFFF
 PLAN_MAX_SPAN = 1024
+PLAN_MAX_TURN_CELLS = 8
+PLAN_MAX_REVERSE_WEIGHT = 16
 
 
 class PlannerContext(_Owner, _StreamOrdered):
@@ -1395,6 +1403,49 @@ class PlannerContext(_Owner, _StreamOrdered):
         """(n, 3) int32 states (i, j, k) of the walk from (start, start class) to the goal; n = 0 when the last
         oriented solve found none.  path() gives its cells with the repeated cell of a turn collapsed."""
         return _fill(lib().kc_planner_get_oriented_path, self.h, [(np.int32, (3,))])[0]
+
+    def set_car(self, turn_cells, reverse_weight=0, a2=0, b2=0):
+        """Car motion of rules 27 to 36: turn_cells the legs of a 45-degree arc in cells (1 .. PLAN_MAX_TURN_CELLS),
+        reverse_weight the factor on backward primitives (0: none, up to 16), a2 / b2 the box footprint as
+        set_oriented's (0, 0: the disc of solve_car's r2).  turn_cells = 0 switches it off.  Forgets the last solve."""
+        _check(lib().kc_planner_set_car(self.h, int(turn_cells), int(reverse_weight), int(a2), int(b2)))
+
+    def solve_car(self, start, start_heading, goal, goal_heading=-1, r2=0, allow_unknown=True):
+        """-> (status, cost, passes) for the state (start cell, start heading 0 .. 7) to (goal cell, goal heading; -1:
+        any): cost = field[start_heading][start]."""
+        s = (C.c_int32 * 2)(int(start[0]), int(start[1]))
+        g = (C.c_int32 * 2)(int(goal[0]), int(goal[1]))
+        st, cost, passes = C.c_int(-1), C.c_uint32(0), C.c_int(0)
+        _check(lib().kc_planner_solve_car(self.h, s, int(start_heading), g, int(goal_heading), int(r2),
+                                          int(bool(allow_unknown)), C.byref(st), C.byref(cost), C.byref(passes)))
+        return st.value, cost.value, passes.value
+
+    def car_field(self):
+        """(field uint32 [8, width, height], moves uint8 [8, width, height] (bit p = primitive p of S, L, R, B, BL, BR
+        allowed), valid bool [8, width, height]) of the last car solve."""
+        w, h = self.shape
+        f = np.empty((8, h, w), np.uint32)   # layer h, then the grid's layout: cell (i, j) at i + j * width
+        m = np.empty((8, h, w), np.uint8)
+        v = np.empty((w, h), np.uint8, order="F")
+        _check(lib().kc_planner_get_car_field(self.h, f.ctypes.data, m.ctypes.data, v.ctypes.data, v.size))
+        valid = np.stack([(v >> k & 1).astype(bool) for k in range(8)])
+        return f.transpose(0, 2, 1), m.transpose(0, 2, 1), valid
+
+    def car_path(self):
+        """(states (m, 3) int32 (i, j, h), one per primitive boundary, moves (m - 1,) int32 primitive ids) of the last
+        car solve; m = 0 when it found none.  path() gives every unit step of every primitive."""
+        n = _sz(0)
+        _check(lib().kc_planner_get_car_path(self.h, None, None, 0, C.byref(n)))
+        states, moves = np.empty((n.value, 3), np.int32), np.empty(max(n.value - 1, 0), np.int32)
+        if n.value:
+            _check(lib().kc_planner_get_car_path(self.h, states.ctypes.data, moves.ctypes.data, n.value, C.byref(n)))
+        return states, moves
+
+    def car_info(self):
+        """(turn_cells, reverse_weight, (maps + moves ms, field ms, walk ms)) of the mode and the last car solve."""
+        n, rw, ms = C.c_int(0), C.c_uint32(0), (C.c_float * 3)()
+        _check(lib().kc_planner_car_info(self.h, C.byref(n), C.byref(rw), ms))
+        return n.value, rw.value, tuple(float(v) for v in ms)
 
     def replan(self, start, goal, r2=0, allow_unknown=True):
         """solve() from the field the context kept (rules 19 and 20): the same outputs bit for bit, the passes only

@@ -24,8 +24,16 @@ label, sizes + records), the field and label passes, the tiles labelled of all t
 components, the path to the first; and the Python statement of tests/planner_frontier_ref.py on one CPU thread (numpy,
 a heap Dijkstra and a flood fill in the interpreter: not a compiled CPU implementation).
 
+--car R_MIN[,RW] adds a leg with car motion (rules 27 to 36) on the disc footprint of the scene: turn cells n from R_MIN
+metres at 0.05 m, reverse weight RW (none without it), start heading 0, any goal heading: classification + validity +
+moves + field, the field alone, the phases by the library's own host clock (maps + moves + init, field), the moves
+kernels on their own (steps + moves + init behind a set_car that keeps the validity map, less the init), the walk with
+its expansion on its own after an untimed solve, the passes, the states and arcs of the path.  May be given more than once.
+The Python statement of tests/planner_car_ref.py is not run here: a heap Dijkstra in the interpreter over eight layers of
+these maps takes minutes.
+
   python tools/planner_time.py [--reps 30] [--cpu-reps 1] [--clearance 20,40] [--shortcut 128] [--oriented 1.5,0.2]
-                               [--replan] [--frontiers] [--json out.json]
+                               [--car 0.5 --car 0.5,2] [--replan] [--frontiers] [--json out.json]
   rocprofv3 --kernel-trace --stats -d out -- python tools/planner_time.py --reps 5 --cpu-reps 0
 """
 import argparse
@@ -42,6 +50,7 @@ ROOT = Path(__file__).resolve().parent.parent
 for p in (ROOT, ROOT / "kompass-core_amd", ROOT / "tests"):
     sys.path.insert(0, str(p))
 import kompass_hip as kh  # noqa: E402
+import planner_car_ref as carref  # noqa: E402
 import planner_clearance_ref as cref  # noqa: E402
 import planner_frontier_ref as fref  # noqa: E402
 import planner_oriented_ref as oref  # noqa: E402
@@ -257,6 +266,59 @@ def scene(name, ctx, host_grid, dev_ptr, elem, start, goal, r2, a):
         out["clearance"] = clearance_leg(ctx, np.asarray(host_grid), start, goal, r2, a)
     if a.oriented:
         out["oriented"] = oriented_leg(ctx, host_grid, dev_ptr, elem, start, goal, a)
+    if a.car:
+        out["car"] = [car_leg(ctx, host_grid, dev_ptr, elem, start, goal, r2, spec, a) for spec in a.car]
+    return out
+
+
+def car_leg(ctx, host_grid, dev_ptr, elem, start, goal, r2, spec, a):
+    """The same grid with car motion on (the scene's disc, start heading 0, any goal heading), then off again."""
+    w, h = host_grid.shape
+    v = spec.split(",")
+    n, rw = carref.turn_cells(float(v[0]), 0.05), int(v[1]) if len(v) > 1 else 0
+    ctx.set_car(n, rw)
+    ctx.set_grid_device(dev_ptr, w, h, elem)
+    try:
+        st, cost, passes = ctx.solve_car(start, 0, goal, -1, r2)
+    except IndexError as e:   # rule 32's bound: 24 n max(rw, 1) * 8 * cells has to fit 32 bits
+        ctx.set_car(0)
+        ctx.set_grid_device(dev_ptr, w, h, elem)
+        return dict(r_min=float(v[0]), turn_cells=n, reverse_weight=rw, refused=str(e))
+    states, prims = ctx.car_path()
+    out = dict(r_min=float(v[0]), turn_cells=n, reverse_weight=rw, status=st, cost=cost, passes=passes, launched=-(-passes // 8) * 8,
+               states=int(len(states)), arcs=int(np.isin(prims, (carref.L, carref.R, carref.BL, carref.BR)).sum()),
+               reverse_primitives=int((prims >= carref.B).sum()), path_cells=int(len(ctx.path())))
+    st_ = lambda t: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), reps=len(t))  # noqa: E731
+
+    def timed(before):
+        whole, ph0, ph1 = [], [], []
+        for k in range(3 + a.reps):
+            t0 = time.perf_counter()
+            before()
+            ctx.solve_car(start, 0, goal, -1, r2)
+            t1 = time.perf_counter()
+            if k >= 3:
+                ms = ctx.car_info()[2]
+                whole.append((t1 - t0) * 1e3)
+                ph0.append(ms[0])
+                ph1.append(ms[1])
+        return st_(whole), st_(ph0), st_(ph1)
+
+    # the grid again: forgets the validity map and the moves; set_car again: the moves alone; nothing: the field alone
+    out["device_grid_ms"], out["maps_moves_init_ms"], _ = timed(lambda: ctx.set_grid_device(dev_ptr, w, h, elem))
+    _, out["moves_init_ms"], _ = timed(lambda: ctx.set_car(n, rw))
+    out["resolve_ms"], out["init_ms"], out["field_ms"] = timed(lambda: None)
+    out["moves_ms_by_difference"] = out["moves_init_ms"]["median"] - out["init_ms"]["median"]
+    walk_ms = []
+    for k in range(3 + a.reps):
+        ctx.solve_car(start, 0, goal, -1, r2)
+        t0 = time.perf_counter()
+        ctx.car_path()
+        if k >= 3:
+            walk_ms.append((time.perf_counter() - t0) * 1e3)
+    out["walk_ms"] = st_(walk_ms)
+    ctx.set_car(0)
+    ctx.set_grid_device(dev_ptr, w, h, elem)
     return out
 
 
@@ -342,6 +404,7 @@ def main():
     ap.add_argument("--clearance", default=None, metavar="REACH_CELLS,WEIGHT10")
     ap.add_argument("--shortcut", type=int, default=0, metavar="W", help="time the any-angle path of span W")
     ap.add_argument("--oriented", default=None, metavar="X,Y[,TURN]", help="time the oriented footprint of an X x Y m box")
+    ap.add_argument("--car", action="append", default=None, metavar="R_MIN[,RW]", help="time car motion of R_MIN metres of turning radius")
     ap.add_argument("--replan", action="store_true", help="time the replan against a full solve of the changed grid")
     ap.add_argument("--frontiers", action="store_true", help="time kc_planner_explore with the far part of the map unknown")
     ap.add_argument("--frontier-radius", type=int, default=300, metavar="CELLS", help="what the robot knows, in cells around it")
@@ -406,6 +469,17 @@ def main():
                     v = o[k]
                     print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
             print(f"    validity, by difference  {o['validity_ms_by_difference']:10.3f} ms")
+        for c in s.get("car", []):
+            if "refused" in c:
+                print(f"  car motion R_min {c['r_min']} m, n {c['turn_cells']}, reverse weight {c['reverse_weight']}: refused: {c['refused']}")
+                continue
+            print(f"  car motion R_min {c['r_min']} m, n {c['turn_cells']}, reverse weight {c['reverse_weight']}: status {c['status']}, cost "
+                  f"{c['cost']}, {c['passes']} passes ({c['launched']} launched), {c['states']} states, {c['arcs']} arcs, "
+                  f"{c['reverse_primitives']} reverse primitives, {c['path_cells']} path cells")
+            for k in ("device_grid_ms", "resolve_ms", "maps_moves_init_ms", "moves_init_ms", "init_ms", "field_ms", "walk_ms"):
+                v = c[k]
+                print(f"    {k:24s} median {v['median']:10.3f}  min {v['min']:10.3f}  max {v['max']:10.3f}  ({v['reps']} reps)")
+            print(f"    moves, by difference     {c['moves_ms_by_difference']:10.3f} ms")
     print(json.dumps(out))
     if a.json:
         Path(a.json).parent.mkdir(parents=True, exist_ok=True)
