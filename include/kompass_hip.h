@@ -1142,7 +1142,8 @@ typedef struct kc_worldmap_result { /* what an update did to the cls plane */
 int kc_worldmap_create(int device, int width, int height, float resolution, double origin_x, double origin_y,
                        kc_worldmap **out);
 void kc_worldmap_destroy(kc_worldmap *ctx);
-/* the geometry given to kc_worldmap_create; any pointer may be NULL */
+/* the geometry given to kc_worldmap_create, the origin at the current offset (rule 46: the
+ * one given while no shift has been made); any pointer may be NULL */
 int kc_worldmap_info(kc_worldmap *ctx, int *width_out, int *height_out, float *resolution_out, double *origin_x_out,
                      double *origin_y_out);
 /* The update model: an observation of KC_OCCUPIED adds hit (up to e_max), one of
@@ -1547,6 +1548,53 @@ int kc_mcl_set_field_model(kc_mcl *ctx, const uint16_t *pen_d2, size_t n, uint16
                            int w_shift);
 /* KC_MCL_MODEL_*: what kc_mcl_step runs */
 int kc_mcl_model_kind(kc_mcl *ctx, int *kind_out);
+
+/* ------------------------------------------------------------------------ */
+/* The rolling window: whole-cell shifts on the device (DESIGN.md 4.11 rules 46 to 51) */
+/* ------------------------------------------------------------------------ */
+/* With no shift made, every entry above gives bit for bit what it gave without these.
+ * Rule 46, offset and origin: the context keeps the origin given at creation (ox0, oy0) and an
+ * integer cell offset (OI, OJ), initially 0.  The map's origin is ox0 + (double)OI * (double)
+ * resolution per axis -- one product and one sum in double, never accumulated from shift to
+ * shift -- and everything that reads the origin uses that value: kc_worldmap_info,
+ * kc_worldmap_points, kc_worldmap_recentre, kc_dwa_set_worldmap, and whoever quantises a pose
+ * for the scan, update and match entries (from kc_worldmap_info's origin).  A shift that
+ * would take |OI| or |OJ| above 2^30 answers KC_ERR_RANGE and leaves the state untouched.
+ * Rule 47, shift by (di, dj) cells: for both planes P'[I, J] = P[I + di, J + dj] where that
+ * source cell lies inside the map; elsewhere the cell is never observed (evidence -128, cls
+ * KC_UNEXPLORED).  Then OI += di, OJ += dj: a positive di moves the window towards +x.
+ * di = dj = 0 launches nothing; |di| >= width or |dj| >= height is a clear at the new offset.
+ * Integers only.  One launch (worldmap_shift_kernel) into scratch planes the context keeps
+ * from its first shift on, and two device-to-device copies back; the call returns with the map
+ * finished, as an update does.
+ * Rule 48, what a shift leaves behind: the distance plane, when on, is wholly dirty (the next
+ * reader's refresh is a full recompute of the shifted map); the kept match table and point
+ * list are unaffected; every device pointer handed out (kc_worldmap_grid_device,
+ * kc_worldmap_distance_device) stays valid and points at the shifted content.
+ * Check order of kc_worldmap_shift: the context, the offset cap, then the device. */
+int kc_worldmap_shift(kc_worldmap *ctx, int di, int dj);
+/* rule 46's cap alone (host only, needs no device): KC_ERR_RANGE when a shift by (di, dj) from
+ * the offset (oi, oj) would leave |OI| or |OJ| above 2^30 */
+int kc_worldmap_check_shift(int32_t oi, int32_t oj, int di, int dj);
+/* rule 46's (OI, OJ); either pointer may be NULL */
+int kc_worldmap_offset(kc_worldmap *ctx, int32_t *oi_out, int32_t *oj_out);
+/* Rule 49, the recentring policy (host only, integers, needs no device): (ic, jc) the robot's
+ * cell by rule 16's quantisation.  Per axis, with size S and cell c: the shift is 0 while margin
+ * <= c <= S - 1 - margin, otherwise ((c - S / 2) / stride) * stride with C's truncating
+ * division.  KC_ERR_INVALID unless margin >= 0, stride >= 1 and 2 * margin < min(width,
+ * height) (and for a non-positive side). */
+int kc_worldmap_recentre_plan(int width, int height, int ic, int jc, int margin, int stride, int32_t *di_out,
+                              int32_t *dj_out);
+/* plan plus shift: (x, y) quantised by rule 16 at the current origin, rule 49, then rule 47;
+ * *di_out, *dj_out: the shift made (0, 0 on any refusal).  Check order: null arguments, the
+ * policy's, the position's (kc_worldmap_quantise_pose), the offset cap, then the device. */
+int kc_worldmap_recentre(kc_worldmap *ctx, double x, double y, int margin, int stride, int32_t *di_out, int32_t *dj_out);
+/* Rule 50, the localiser follows: a kc_mcl records the (OI, OJ) its particles are expressed in
+ * (kc_mcl_init_* set it to the map's).  kc_mcl_step, kc_mcl_resample, kc_mcl_particles and
+ * kc_mcl_particles_device first apply a difference (di, dj) as TX' = clamp(TX - (di << 16),
+ * +-2^36), TY alike, in one launch (mcl_shift_kernel); h, acc and the kept weights are
+ * untouched.
+ * Rule 51 (the planner does not carry its field across a shift) is the host classes'. */
 
 #ifdef __cplusplus
 }

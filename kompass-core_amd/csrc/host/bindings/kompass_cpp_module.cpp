@@ -1141,10 +1141,34 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return py::make_tuple(p.cq, p.sq, p.tx, p.ty);
            }, py::arg("resolution"), py::arg("origin_x"), py::arg("origin_y"), py::arg("x"), py::arg("y"), py::arg("yaw"),
            "(cq, sq, tx, ty): the pose as the update takes it, 16 fraction bits; needs no device")
+      .def("shift", [](Mapping::WorldMap &m, int di, int dj) {
+             py::gil_scoped_release nogil;
+             m.shift(di, dj);
+           }, py::arg("di"), py::arg("dj"),
+           "Move the window by whole cells on the device (DESIGN.md 4.11 rules 46 to 48), a positive di towards +x")
+      .def("recentre", [](Mapping::WorldMap &m, double x, double y, int margin, int stride) {
+             std::array<int, 2> d;
+             {
+               py::gil_scoped_release nogil;
+               d = m.recentre(x, y, margin, stride);
+             }
+             return py::make_tuple(d[0], d[1]);
+           }, py::arg("x"), py::arg("y"), py::arg("margin"), py::arg("stride"),
+           "Rule 49's plan for the robot at world (x, y), then the shift -> (di, dj), the shift made")
+      .def("offset", [](const Mapping::WorldMap &m) {
+             const auto o = m.offset();
+             return py::make_tuple(o[0], o[1]);
+           }, "(OI, OJ): the cells the window has moved since it was created")
+      .def_static("recentre_plan", [](int width, int height, int ic, int jc, int margin, int stride) {
+             const auto d = Mapping::WorldMap::recentrePlan(width, height, ic, jc, margin, stride);
+             return py::make_tuple(d[0], d[1]);
+           }, py::arg("width"), py::arg("height"), py::arg("ic"), py::arg("jc"), py::arg("margin"), py::arg("stride"),
+           "Rule 49 alone: the shift for a robot in cell (ic, jc); needs no device")
       .def_property_readonly("width", &Mapping::WorldMap::width)
       .def_property_readonly("height", &Mapping::WorldMap::height)
       .def_property_readonly("resolution", &Mapping::WorldMap::resolution)
-      .def_property_readonly("origin", [](const Mapping::WorldMap &m) { return py::make_tuple(m.originX(), m.originY()); });
+      .def_property_readonly("origin", [](const Mapping::WorldMap &m) { return py::make_tuple(m.originX(), m.originY()); },
+                             "the world position of cell (0, 0)'s centre at the current offset");
 
   // (not in the reference: Monte-Carlo localisation over a WorldMap, the particles on the device; DESIGN.md 4.11 rules
   // 28 to 41)
@@ -1452,6 +1476,16 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return p.replan();
            }, "solve() from the kept cost field after set_grid* and / or setup_problem with the same goal: the same "
               "outputs, the passes only over what changed; a full solve when nothing can be kept")
+      .def("set_grid_from_world_map", [](Planning::GridPlanner &p, const Mapping::WorldMap &map) {
+             py::gil_scoped_release nogil;
+             return p.setGridFromWorldMap(map);
+           }, py::arg("world_map"),
+           "The class plane of a WorldMap in place, its metadata read again (DESIGN.md 4.11 rule 51): when its window has been "
+           "shifted the bounds and the problem's cells are set again.  -> whether the bounds moved")
+      .def("replan", [](Planning::GridPlanner &p, const Mapping::WorldMap &map) {
+             py::gil_scoped_release nogil;
+             return p.replan(map);
+           }, py::arg("world_map"), "set_grid_from_world_map, then replan() -- a full solve() when the bounds moved")
       .def("replanned", &Planning::GridPlanner::replanned, "the last replan() kept a field (false after a full solve)")
       .def("get_replan_threshold", &Planning::GridPlanner::replanThreshold,
            "the last replan()'s rollback threshold in field units; 0xFFFFFFFF when nothing was rolled back")

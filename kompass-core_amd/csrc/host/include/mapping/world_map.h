@@ -43,6 +43,18 @@ class WorldMap {
   uint32_t updateOnDevice(const int32_t *dev_grid, int grid_height, int grid_width, double x, double y, double yaw);
   void clear();
 
+  // The rolling window (DESIGN.md 4.11 rules 46 to 49).  shift: the window moves by whole cells on the device, a positive
+  // di towards +x; what leaves is forgotten, what enters is never observed.  originX() / originY() follow (the origin at
+  // creation plus offset * resolution, never accumulated), changed() is 0 and changedBox() all -1 afterwards, the distance
+  // plane is wholly dirty, deviceGrid() and deviceDistance() keep their addresses.  std::out_of_range for an offset above
+  // 2^30 cells.  recentre: rule 49's plan for the robot at world (x, y) -- no shift while its cell is `margin` cells or
+  // more from every border, else the whole multiple of `stride` that brings it nearest the centre -- then the shift;
+  // returns the shift made.  recentrePlan is the policy alone and needs no device.
+  void shift(int di, int dj);
+  std::array<int, 2> recentre(double x, double y, int margin, int stride);
+  std::array<int, 2> offset() const;
+  static std::array<int, 2> recentrePlan(int width, int height, int ic, int jc, int margin, int stride);
+
   // Correlative match (DESIGN.md 4.11 rules 9 to 15): the pose within n_yaw steps of yaw_step each side of the guess's
   // yaw and `reach` cells each side of its position that puts the grid's occupied cells onto the map best.  The map is
   // not modified.  Same three sources as update.
@@ -119,7 +131,7 @@ class WorldMap {
  private:
   int width_, height_;
   float res_;
-  double ox_, oy_;
+  double ox_, oy_;  // rule 46's origin at the current offset: read again from the context after every shift
   hip::WorldMapHandle ctx_;
   kc_worldmap_result last_ = {0, -1, -1, -1, -1};
   uint64_t match_count_ = 0;
@@ -135,6 +147,7 @@ class WorldMap {
     GridSource(const LocalMapper &m) : kind(Mapper), mapper(&m), grid(nullptr), height(0), width(0), central_i(0), central_j(0) {}
     GridSource(Kind k, const int32_t *grid, int grid_height, int grid_width);
   };
+  void afterShift();
   uint32_t updateFrom(const GridSource &s, const kc_worldmap_pose &pose);
   Match matchFrom(const GridSource &s, double x, double y, double yaw, int n_yaw, double yaw_step, int reach);
   std::vector<double> scanPoses(const std::vector<std::array<double, 3>> &poses, const std::vector<double> &angles, float range_max,

@@ -25,6 +25,7 @@
 
 #include "datatypes/path.h"
 #include "mapping/local_mapper.h"
+#include "mapping/world_map.h"
 #include "utils/collision_check.h"
 #include "utils/hip_backend.h"
 
@@ -53,6 +54,11 @@ class GridPlanner {
   // the last grid of a LocalMapper where it lies (scanToGrid / scanToGridOnDevice); sets the bounds from the
   // mapper as well: origin = -(central cell) * resolution
   void setGridFromMapper(Mapping::LocalMapper &mapper);
+  // The class plane of a WorldMap where it lies on the device, with the map's metadata read again (DESIGN.md 4.11 rule
+  // 51): when the origin, shape or resolution differ from the bounds held -- the map's window has been shifted -- the
+  // bounds are set again and the start and goal of the last setupProblem are taken into the new bounds' cells.
+  // Returns whether the bounds moved.  The bounds are floats, as everywhere in this class: the comparison is theirs.
+  bool setGridFromWorldMap(const Mapping::WorldMap &map);
 
   void setupProblem(double start_x, double start_y, double start_yaw, double goal_x, double goal_y, double goal_yaw);
   // false (and no path) when the start or the goal is outside the grid or invalid, or the goal out of reach
@@ -63,6 +69,9 @@ class GridPlanner {
   // moved.  A full solve, silently, when there is no kept field, the goal, the footprint or the clearance cost
   // changed, or the oriented footprint is on (replanned() then says false).
   bool replan();
+  // setGridFromWorldMap(map), then replan() -- or, when the bounds moved, a full solve() with replanned() false: the
+  // kept field is one of the old window's cells and is not carried across a shift (rule 51)
+  bool replan(const Mapping::WorldMap &map);
   // the last replan() kept a field / its rollback threshold in field units (0xFFFFFFFF: nothing was rolled back)
   bool replanned() const { return replanned_; }
   uint32_t replanThreshold() const { return replan_threshold_; }
@@ -208,6 +217,7 @@ class GridPlanner {
   int width_ = 0, height_ = 0;
   bool have_bounds_ = false, have_grid_ = false, have_problem_ = false;
   int start_[2] = {-1, -1}, goal_[2] = {-1, -1};
+  double problem_[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // the last setupProblem in the world frame, for bounds that move
   int status_ = -1, passes_ = 0;
   uint32_t cost_ = 0xFFFFFFFFu;
   bool replanned_ = false;

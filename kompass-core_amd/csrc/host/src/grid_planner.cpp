@@ -366,6 +366,18 @@ void GridPlanner::setGridFromMapper(Mapping::LocalMapper &mapper) {
   setGridOnDevice(dev, 4);
 }
 
+bool GridPlanner::setGridFromWorldMap(const Mapping::WorldMap &map) {
+  const float ox = static_cast<float>(map.originX()), oy = static_cast<float>(map.originY());
+  const bool moved = !have_bounds_ || ox != ox_ || oy != oy_ || map.width() != width_ || map.height() != height_ ||
+                     map.resolution() != res_;
+  if (moved) {
+    setSpaceBoundsFromMap(ox, oy, map.width(), map.height(), map.resolution());
+    if (have_problem_) setupProblem(problem_[0], problem_[1], problem_[2], problem_[3], problem_[4], problem_[5]);
+  }
+  setGridOnDevice(map.deviceGrid(), 1);
+  return moved;
+}
+
 bool GridPlanner::worldToCell(float x, float origin, float resolution, int *cell) {
   const float q = (x - origin) / resolution;
   if (!std::isfinite(q) || std::fabs(q) >= 1073741824.0f) return false;
@@ -387,6 +399,8 @@ uint32_t GridPlanner::footprintR2() const {
 
 void GridPlanner::setupProblem(double start_x, double start_y, double start_yaw, double goal_x, double goal_y, double goal_yaw) {
   needBounds();
+  const double problem[6] = {start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw};
+  std::copy(problem, problem + 6, problem_);
   start_class_ = std::isfinite(start_yaw) ? orientationClass(start_yaw) : 0;  // the oriented footprint's k0; it leaves goal_yaw unused
   start_heading_ = std::isfinite(start_yaw) ? headingClass(start_yaw) : 0;    // car motion's h0 and hg; a goal_yaw that is no number: any
   goal_heading_ = std::isfinite(goal_yaw) ? headingClass(goal_yaw) : -1;
@@ -499,6 +513,11 @@ bool GridPlanner::replan() {
   hip::check(kc_planner_replan_info(ctx_.get(), &kept, &replan_threshold_, nullptr, nullptr));
   replanned_ = kept != 0;
   return status_ == KC_PLAN_FOUND;
+}
+
+bool GridPlanner::replan(const Mapping::WorldMap &map) {
+  if (setGridFromWorldMap(map)) return solve();  // rule 51: replanned() says false
+  return replan();
 }
 
 void GridPlanner::cells(int start_out[2], int goal_out[2]) const {

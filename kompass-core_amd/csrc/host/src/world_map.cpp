@@ -121,6 +121,36 @@ void WorldMap::clear() {
   last_ = {0, -1, -1, -1, -1};
 }
 
+// rules 46 and 48 on the host: the origin as the context now gives it, and no changed cells
+void WorldMap::afterShift() {
+  hip::check(kc_worldmap_info(ctx_.get(), nullptr, nullptr, nullptr, &ox_, &oy_));
+  last_ = {0, -1, -1, -1, -1};
+}
+
+void WorldMap::shift(int di, int dj) {
+  hip::check(kc_worldmap_shift(ctx_.get(), di, dj));
+  afterShift();
+}
+
+std::array<int, 2> WorldMap::recentre(double x, double y, int margin, int stride) {
+  int32_t di = 0, dj = 0;
+  hip::check(kc_worldmap_recentre(ctx_.get(), x, y, margin, stride, &di, &dj));
+  afterShift();
+  return {di, dj};
+}
+
+std::array<int, 2> WorldMap::offset() const {
+  int32_t oi = 0, oj = 0;
+  hip::check(kc_worldmap_offset(ctx_.get(), &oi, &oj));
+  return {oi, oj};
+}
+
+std::array<int, 2> WorldMap::recentrePlan(int width, int height, int ic, int jc, int margin, int stride) {
+  int32_t di = 0, dj = 0;
+  hip::check(kc_worldmap_recentre_plan(width, height, ic, jc, margin, stride, &di, &dj));
+  return {di, dj};
+}
+
 std::vector<Path::Point> WorldMap::points(double x, double y, float max_sensor_range) const {
   static_assert(sizeof(Path::Point) == 3 * sizeof(float), "Path::Point must be packed (x, y, z)");
   size_t n = 0;

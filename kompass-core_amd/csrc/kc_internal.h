@@ -350,9 +350,10 @@ struct WorldMapView {
   const int8_t *cls;  // [W x H], cell (I, J) at I + J * W
   int W, H;
   float res;
-  double ox, oy;
+  double ox, oy;      // rule 46's origin at the current offset
   hipStream_t stream;
   int device;
+  int OI, OJ;         // rule 46's offset, for whoever keeps cell coordinates across a shift (kc_mcl, rule 50)
 };
 int worldmap_view(kc_worldmap *m, WorldMapView *out);
 // the map's distance plane (rules 42 and 43) for a reader on another stream: reach 0 and a null plane while it is off

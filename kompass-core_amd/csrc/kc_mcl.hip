@@ -26,6 +26,9 @@
 //      other one.
 //  (e) global init: row counts of KC_EMPTY (a workgroup a row), the prefix over rows on the host, then a wavefront a
 //      particle: a binary search for the row and a ballot walk along it.
+//  (f) mcl_shift_kernel (rule 50): the map's window moved by whole cells since the particles were last touched; a lane a
+//      particle takes the difference out of (TX, TY) in place, clamped as every state is.  Applied lazily by the entries
+//      that read or write particles.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -115,6 +118,14 @@ __device__ __forceinline__ void mcl_segment_add(unsigned *cost, int p, unsigned 
   }
   const int before = __shfl_up(p, 1);
   if (live && (lane == 0 || before != p)) atomicAdd(&cost[p], c);
+}
+
+// rule 50: TX' = clamp(TX - (di << 16)), TY alike; sx = di << 16 and sy = dj << 16 formed on the host
+__global__ __launch_bounds__(kMclBlock) void mcl_shift_kernel(MclState st, long long sx, long long sy, int N) {
+  const int p = static_cast<int>(blockIdx.x) * kMclBlock + static_cast<int>(threadIdx.x);
+  if (p >= N) return;
+  st.tx[p] = mcl_clamp(st.tx[p] - sx);
+  st.ty[p] = mcl_clamp(st.ty[p] - sy);
 }
 
 struct MclWalkArgs {
@@ -452,6 +463,7 @@ struct kc_mcl {
   DevBuf<unsigned long long> d_before;
   bool inited = false, have_weights = false;
   unsigned long long w1 = 0;  // of the last step
+  int OI = 0, OJ = 0;         // rule 50: the map offset the particles are expressed in
   Timing step_time, resample_time;
 
   MclState state(int which) { return MclState{d_tx[which].p, d_ty[which].p, d_h[which].p}; }
@@ -554,8 +566,22 @@ unsigned long long mcl_key(const kc_mcl *c, unsigned step) {
   return mcl_mix64(c->seed ^ (static_cast<unsigned long long>(step) << 32));
 }
 
-// what either init leaves behind
-void mcl_started(kc_mcl *c, int into) {
+// rule 50, queued on the context's stream (the device is current): the particles into the map's present offset
+int mcl_follow(kc_mcl *c, const WorldMapView &v) {
+  const long long di = static_cast<long long>(v.OI) - c->OI, dj = static_cast<long long>(v.OJ) - c->OJ;
+  if (di == 0 && dj == 0) return KC_OK;
+  hipLaunchKernelGGL(mcl_shift_kernel, dim3(mcl_blocks(c->N)), dim3(kMclBlock), 0, c->stream, c->state(c->cur), di * 65536,
+                     dj * 65536, static_cast<int>(c->N));
+  KC_HIP(hipGetLastError());
+  c->OI = v.OI;
+  c->OJ = v.OJ;
+  return KC_OK;
+}
+
+// what either init leaves behind: particles in the map's present offset
+void mcl_started(kc_mcl *c, int into, const WorldMapView &v) {
+  c->OI = v.OI;
+  c->OJ = v.OJ;
   c->cur = into;
   c->step = 0;
   c->inited = true;
@@ -697,6 +723,8 @@ int kc_mcl_init_pose(kc_mcl *c, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s
     KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
   if (h0 > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h0);
   if (s_xy < 0 || s_h < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
   c->inited = false;
   const int N = static_cast<int>(c->N);
@@ -705,7 +733,7 @@ int kc_mcl_init_pose(kc_mcl *c, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s
                      s_h, N);
   KC_HIP(hipGetLastError());
   KC_HIP(hipStreamSynchronize(c->stream));
-  mcl_started(c, 0);
+  mcl_started(c, 0, v);
   return KC_OK;
 }
 
@@ -734,7 +762,7 @@ int kc_mcl_init_global(kc_mcl *c, size_t *n_free_out) {
                      c->d_before.p, c->state(0), c->d_acc.p, c->d_cost.p, c->d_min_prev.p, mcl_key(c, 0), static_cast<int>(c->N));
   KC_HIP(hipGetLastError());
   KC_HIP(hipStreamSynchronize(c->stream));  // `before` is the copy's source
-  mcl_started(c, 0);
+  mcl_started(c, 0, v);
   return KC_OK;
 }
 
@@ -767,6 +795,7 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
       KC_FAIL(KC_ERR_STATE, "the field model's c2 = %d is above the plane's reach^2 = %d", c->E - 1, dist.reach * dist.reach);
   }
   KC_HIP(hipSetDevice(c->device));
+  KC_TRY(mcl_follow(c, v));  // rule 50, ahead of the predict step in the stream's order
   std::memcpy(c->h_zq.p, zq, c->B * sizeof(int32_t));
   KC_HIP(hipMemcpyAsync(c->d_zq.p, c->h_zq.p, c->B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   if (field) KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
@@ -857,7 +886,10 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
 int kc_mcl_resample(kc_mcl *c) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (!c->inited || !c->have_weights) KC_FAIL(KC_ERR_STATE, "a resample needs the weights of a step since the last init or resample");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
+  KC_TRY(mcl_follow(c, v));  // rule 50: the select copies the moved states
   const int N = static_cast<int>(c->N);
   const unsigned long long u0 = mcl_draw(mcl_key(c, c->step), c->N, 15) % c->w1;
   c->inited = false;
@@ -881,7 +913,10 @@ int kc_mcl_particles(kc_mcl *c, int64_t *tx_out, int64_t *ty_out, uint32_t *h_ou
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (!c->inited) KC_FAIL(KC_ERR_STATE, "no particles before an init");
   if (cap < c->N) KC_FAIL(KC_ERR_RANGE, "%zu particles do not fit the output capacity %zu", c->N, cap);
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
+  KC_TRY(mcl_follow(c, v));  // rule 50
   const MclState s = c->state(c->cur);
   if (tx_out) KC_HIP(hipMemcpyAsync(tx_out, s.tx, c->N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
   if (ty_out) KC_HIP(hipMemcpyAsync(ty_out, s.ty, c->N * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -894,6 +929,13 @@ int kc_mcl_particles(kc_mcl *c, int64_t *tx_out, int64_t *ty_out, uint32_t *h_ou
 int kc_mcl_particles_device(kc_mcl *c, void **tx_out, void **ty_out, void **h_out, void **acc_out) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (!c->inited) KC_FAIL(KC_ERR_STATE, "no particles before an init");
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
+  if (v.OI != c->OI || v.OJ != c->OJ) {  // rule 50; the caller reads on a stream of its own, so the move is finished here
+    KC_HIP(hipSetDevice(c->device));
+    KC_TRY(mcl_follow(c, v));
+    KC_HIP(hipStreamSynchronize(c->stream));
+  }
   const MclState s = c->state(c->cur);
   if (tx_out) *tx_out = s.tx;
   if (ty_out) *ty_out = s.ty;

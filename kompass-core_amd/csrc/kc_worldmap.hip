@@ -49,6 +49,13 @@
 //      LDS as blocking bytes, row distances and the column pass out of LDS, a uint16 store a lane), above it
 //      worldmap_dist_rows_kernel + worldmap_dist_cols_kernel over a uint8 scratch plane, in the planner's manner.
 //
+//  (i) rolling window (rules 46 to 49).  worldmap_shift_kernel moves both planes by whole cells into two scratch planes
+//      the context keeps from its first shift on: a lane a destination cell in the update kernel's layout, a byte load
+//      (or the never-observed pair where the source cell lies outside the map) and a byte store a plane.  NOT in place: a
+//      workgroup must never read a cell another has already overwritten.  Two device-to-device copies on the context's
+//      stream bring the planes back to where they were, so every pointer handed out stays valid.  The origin is never
+//      summed from shift to shift: it is ox0 + (double)OI * (double)res whenever it is asked for.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -175,6 +182,33 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_prior_kernel(const T *grid,
     evidence[k] = static_cast<int8_t>(e);
     cls[k] = static_cast<int8_t>(c);
   }
+}
+
+// ---- rolling window (rules 46 to 49) -----------------------------------------------------------------------------
+constexpr int kWmMaxShift = 1 << 30;  // rule 46's cap on |OI| and |OJ|
+
+struct WmShiftArgs {
+  const int8_t *evidence, *cls;
+  int8_t *evidence_out, *cls_out;  // the scratch planes: never the planes read
+  int W, H;
+  int di, dj;                      // |di| < W and |dj| < H: the host turns anything larger into a clear
+};
+
+// rule 47: P'[I, J] = P[I + di, J + dj] where that cell lies inside the map, never observed elsewhere
+__global__ __launch_bounds__(kWmBlock) void worldmap_shift_kernel(WmShiftArgs a) {
+  const int I = static_cast<int>(blockIdx.x) * kWmLanes + static_cast<int>(threadIdx.x);
+  const int J = static_cast<int>(blockIdx.y) * kWmRows + static_cast<int>(threadIdx.y);
+  if (I >= a.W || J >= a.H) return;
+  const int si = I + a.di, sj = J + a.dj;
+  int8_t e = kWmNever, k = static_cast<int8_t>(KC_UNEXPLORED);
+  if (si >= 0 && si < a.W && sj >= 0 && sj < a.H) {
+    const size_t src = static_cast<size_t>(si) + static_cast<size_t>(sj) * static_cast<size_t>(a.W);
+    e = a.evidence[src];
+    k = a.cls[src];
+  }
+  const size_t cell = static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W);
+  a.evidence_out[cell] = e;
+  a.cls_out[cell] = k;
 }
 
 // ---- match (rules 9 to 15) ---------------------------------------------------------------------------------------
@@ -574,9 +608,11 @@ struct kc_worldmap {
   OrderEvent grid_ready;  // a mapper's scan, for the grids read where the mapper left them
   int W = 0, H = 0;
   float res = 0.0f;
-  double ox = 0.0, oy = 0.0;
+  double ox0 = 0.0, oy0 = 0.0;  // the origin given at creation
+  int OI = 0, OJ = 0;           // rule 46: the window's offset in cells
   WmModel m = {3, 1, -8, 14, 1};
   DevBuf<int8_t> d_evidence, d_cls;
+  DevBuf<int8_t> d_shift_e, d_shift_c;  // the shift's scratch planes, kept from the first shift on
   DevBuf<int32_t> d_stage;   // a host grid (local, or an int32 prior) on its way to a kernel
   FlipRecord rec;            // the update's: kWmRecWords a block
   // match: scratch grown on demand and kept
@@ -605,6 +641,9 @@ struct kc_worldmap {
   int dist_last[4] = {-1, -1, -1, -1};
   bool dist_last_full = false;
 
+  // rule 46: one product and one sum in double, never accumulated
+  double ox() const { return ox0 + static_cast<double>(OI) * static_cast<double>(res); }
+  double oy() const { return oy0 + static_cast<double>(OJ) * static_cast<double>(res); }
   void dirty_all() {
     if (dist_reach == 0) return;
     dirty[0] = dirty[1] = 0;
@@ -1028,6 +1067,65 @@ bool wm_window_box(int W, int H, int ic, int jc, int rc, int box[4]) {
   return box[0] <= box[2] && box[1] <= box[3];
 }
 
+// rule 49 for one axis: size S, the robot's cell c
+int wm_recentre_axis(int S, int c, int margin, int stride) {
+  if (c >= margin && c <= S - 1 - margin) return 0;
+  const long long d = static_cast<long long>(c) - S / 2;
+  return static_cast<int>((d / stride) * stride);  // C's truncating division; |d| is far below 2^31
+}
+
+int wm_recentre_plan(int W, int H, int ic, int jc, int margin, int stride, int *di, int *dj) {
+  if (W <= 0 || H <= 0) KC_FAIL(KC_ERR_INVALID, "the map's width and height must be positive, got %d x %d", W, H);
+  if (margin < 0 || stride < 1 || 2ll * margin >= std::min(W, H))
+    KC_FAIL(KC_ERR_INVALID, "recentring needs margin >= 0, stride >= 1 and 2 margin < min(W, H), got margin %d, stride %d on %d x %d",
+            margin, stride, W, H);
+  *di = wm_recentre_axis(W, ic, margin, stride);
+  *dj = wm_recentre_axis(H, jc, margin, stride);
+  return KC_OK;
+}
+
+// rule 46's cap, before any device use
+int wm_check_shift(int OI, int OJ, int di, int dj) {
+  const long long oi = static_cast<long long>(OI) + di, oj = static_cast<long long>(OJ) + dj;
+  if (oi < -kWmMaxShift || oi > kWmMaxShift || oj < -kWmMaxShift || oj > kWmMaxShift)
+    KC_FAIL(KC_ERR_RANGE, "a shift by (%d, %d) takes the offset (%d, %d) above 2^30 cells", di, dj, OI, OJ);
+  return KC_OK;
+}
+
+// rules 47 and 48; the arguments are checked
+int wm_shift(kc_worldmap *c, int di, int dj) {
+  if (di == 0 && dj == 0) return KC_OK;  // launches nothing
+  KC_HIP(hipSetDevice(c->device));
+  const bool clear = di <= -c->W || di >= c->W || dj <= -c->H || dj >= c->H;
+  if (clear) {
+    KC_TRY(wm_take_prior(c, nullptr, 1));  // no source cell lies inside the map
+  } else {
+    const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+    KC_TRY(c->d_shift_e.reserve(n));
+    KC_TRY(c->d_shift_c.reserve(n));
+    WmShiftArgs a{};
+    a.evidence = c->d_evidence.p;
+    a.cls = c->d_cls.p;
+    a.evidence_out = c->d_shift_e.p;
+    a.cls_out = c->d_shift_c.p;
+    a.W = c->W;
+    a.H = c->H;
+    a.di = di;
+    a.dj = dj;
+    const int box[4] = {0, 0, c->W - 1, c->H - 1};
+    hipLaunchKernelGGL(worldmap_shift_kernel, wm_box_grid(box), dim3(kWmLanes, kWmRows), 0, c->stream, a);
+    KC_HIP(hipGetLastError());
+    // back to where the planes were: the pointers handed out stay valid (rule 48)
+    KC_HIP(hipMemcpyAsync(c->d_evidence.p, c->d_shift_e.p, n, hipMemcpyDeviceToDevice, c->stream));
+    KC_HIP(hipMemcpyAsync(c->d_cls.p, c->d_shift_c.p, n, hipMemcpyDeviceToDevice, c->stream));
+    c->dirty_all();  // rule 48: the accepted first version
+    KC_HIP(hipStreamSynchronize(c->stream));
+  }
+  c->OI += di;
+  c->OJ += dj;
+  return KC_OK;
+}
+
 void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *out) {
   *out = kc_worldmap_match_result{};
   if (g) out->pose = *g;
@@ -1039,7 +1137,7 @@ namespace kc {
 
 int worldmap_view(kc_worldmap *m, WorldMapView *out) {
   if (!m || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
-  *out = WorldMapView{m->d_cls.p, m->W, m->H, m->res, m->ox, m->oy, m->stream, m->device};
+  *out = WorldMapView{m->d_cls.p, m->W, m->H, m->res, m->ox(), m->oy(), m->stream, m->device, m->OI, m->OJ};
   return KC_OK;
 }
 
@@ -1313,8 +1411,8 @@ int kc_worldmap_create(int device, int width, int height, float resolution, doub
   c->W = width;
   c->H = height;
   c->res = resolution;
-  c->ox = origin_x;
-  c->oy = origin_y;
+  c->ox0 = origin_x;
+  c->oy0 = origin_y;
   const int rec_start[kWmRecWords] = {0, INT_MAX, INT_MAX, -1, -1};  // what worldmap_update_kernel puts back
   c->rec.start.assign(rec_start, rec_start + kWmRecWords);
   std::vector<int> &pts_start = c->pts_rec.start;  // ... and worldmap_window_points_kernel
@@ -1344,8 +1442,8 @@ int kc_worldmap_info(kc_worldmap *c, int *width_out, int *height_out, float *res
   if (width_out) *width_out = c->W;
   if (height_out) *height_out = c->H;
   if (resolution_out) *resolution_out = c->res;
-  if (origin_x_out) *origin_x_out = c->ox;
-  if (origin_y_out) *origin_y_out = c->oy;
+  if (origin_x_out) *origin_x_out = c->ox();  // rule 46
+  if (origin_y_out) *origin_y_out = c->oy();
   return KC_OK;
 }
 
@@ -1401,6 +1499,49 @@ int kc_worldmap_update_host(kc_worldmap *c, const int32_t *grid, int grid_height
 int kc_worldmap_update_from_mapper(kc_worldmap *c, kc_mapper *mapper, const kc_worldmap_pose *pose, kc_worldmap_result *out) {
   if (!c || !mapper || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
   return wm_update(c, GridSource{GridSource::Mapper, {}, mapper}, pose, out);
+}
+
+int kc_worldmap_offset(kc_worldmap *c, int32_t *oi_out, int32_t *oj_out) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (oi_out) *oi_out = c->OI;
+  if (oj_out) *oj_out = c->OJ;
+  return KC_OK;
+}
+
+// Check order: the context, the offset cap, then the device
+int kc_worldmap_shift(kc_worldmap *c, int di, int dj) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_TRY(wm_check_shift(c->OI, c->OJ, di, dj));
+  return wm_shift(c, di, dj);
+}
+
+int kc_worldmap_check_shift(int32_t oi, int32_t oj, int di, int dj) { return wm_check_shift(oi, oj, di, dj); }
+
+int kc_worldmap_recentre_plan(int width, int height, int ic, int jc, int margin, int stride, int32_t *di_out, int32_t *dj_out) {
+  if (!di_out || !dj_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *di_out = *dj_out = 0;
+  int di = 0, dj = 0;
+  KC_TRY(wm_recentre_plan(width, height, ic, jc, margin, stride, &di, &dj));
+  *di_out = di;
+  *dj_out = dj;
+  return KC_OK;
+}
+
+// Check order: null arguments, the policy, the position (rule 16 at the current origin), the offset cap, then the device
+int kc_worldmap_recentre(kc_worldmap *c, double x, double y, int margin, int stride, int32_t *di_out, int32_t *dj_out) {
+  if (!c || !di_out || !dj_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *di_out = *dj_out = 0;
+  int di = 0, dj = 0;
+  KC_TRY(wm_recentre_plan(c->W, c->H, 0, 0, margin, stride, &di, &dj));  // the policy alone
+  kc_worldmap_pose p;
+  KC_TRY(kc_worldmap_quantise_pose(c->res, c->ox(), c->oy(), x, y, 0.0, &p));
+  const int ic = static_cast<int>((p.tx + (1ll << 15)) >> 16), jc = static_cast<int>((p.ty + (1ll << 15)) >> 16);
+  KC_TRY(wm_recentre_plan(c->W, c->H, ic, jc, margin, stride, &di, &dj));
+  KC_TRY(wm_check_shift(c->OI, c->OJ, di, dj));
+  KC_TRY(wm_shift(c, di, dj));
+  *di_out = di;
+  *dj_out = dj;
+  return KC_OK;
 }
 
 int kc_worldmap_grid_device(kc_worldmap *c, void **dev_cls_int8) {

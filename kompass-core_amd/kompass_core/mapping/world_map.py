@@ -94,7 +94,27 @@ class WorldMap:
         return WorldMapMatch(self._map.match(self._local(local_map), float(robot_state.x), float(robot_state.y),
                                              float(robot_state.yaw), int(n_yaw), float(yaw_step), int(reach)))
 
-    def update(self, robot_state, local_map, match: bool = False, min_ratio: float = 0.6, min_points: int = 30, **window) -> int:
+    def shift(self, di: int, dj: int) -> None:
+        """Move the window by whole cells on the device (DESIGN.md 4.11 rules 46 to 48), a positive di towards +x: what
+        leaves the window is forgotten, what enters it is never observed, evidence and class move together.  The origin
+        (`map_meta_data`) follows; `changed` is 0 afterwards; the distance field, when enabled, is recomputed by its next
+        reader; `device_grid` keeps its address.  An `MCL` over this map moves its particles by itself (rule 50); a
+        `GridPlanner` solves in full on its next `replan(map=world_map)` (rule 51)."""
+        self._map.shift(int(di), int(dj))
+
+    def recentre(self, robot_state, margin: int, stride: int) -> Tuple[int, int]:
+        """Rule 49: no shift while the robot's cell is `margin` cells or more from every border; otherwise the whole
+        multiple of `stride` cells, per axis, that brings it nearest the window's centre.  -> (di, dj), the shift made."""
+        x, y, _ = self._pose(robot_state)
+        return self._map.recentre(x, y, int(margin), int(stride))
+
+    @property
+    def offset(self) -> Tuple[int, int]:
+        """(OI, OJ): the cells the window has moved since the map was created."""
+        return self._map.offset()
+
+    def update(self, robot_state, local_map, match: bool = False, min_ratio: float = 0.6, min_points: int = 30,
+               follow: Optional[Tuple[int, int]] = None, **window) -> int:
         """Fuse one local grid; robot_state (x, y, yaw): the robot's pose in the world.  local_map: the front end's
         `LocalMapper` or a `kompass_cpp.mapping.LocalMapper` (its last grid where it lies on the device, no host
         round trip), or an int32 (grid_height, grid_width) array as `LocalMapper.occupancy`.  -> cells whose class
@@ -103,8 +123,13 @@ class WorldMap:
         match=True: `match(robot_state, local_map, **window)` first, and fuse at the corrected pose when the match
         is trusted: ratio >= min_ratio, points >= min_points and score > score_guess; at the given pose otherwise.
         `last_match` holds the WorldMapMatch, its `applied` the decision.  The defaults of min_ratio and min_points
-        are judgement, not measurement: nobody has tuned them on a robot."""
+        are judgement, not measurement: nobody has tuned them on a robot.
+
+        follow=(margin, stride): `recentre(robot_state, margin, stride)` before anything else, so the window rolls with the
+        robot and the grid is fused into the shifted map."""
         mapper = self._local(local_map)
+        if follow is not None:
+            self.recentre(robot_state, int(follow[0]), int(follow[1]))
         if not match:
             if window:
                 raise TypeError(f"unexpected arguments without match=True: {sorted(window)}")

@@ -173,12 +173,15 @@ class GridPlanner:
         cost of what changed.  map: the map's next state, a grid as setup_problem takes it (same shape and
         metadata), or None for the grid as it is.  start: the robot's new (x, y) or (x, y, yaw), or None.  With only a
         new start no pass runs; with a new map the passes run over the part of the field a changed cell can reach.
-        Falls back to a full solve by itself where nothing can be kept (`replanned` says which it was)."""
+        Falls back to a full solve by itself where nothing can be kept (`replanned` says which it was).  A WorldMap's
+        metadata is read again: when its window has been shifted since the bounds were taken, the bounds and the
+        problem's cells are set again and the solve is a full one (DESIGN.md 4.11 rule 51)."""
         if self._problem is None:
             raise RuntimeError("replan needs a setup_problem first: it keeps that goal")
-        if map is not None:
-            if isinstance(map, WorldMap):
-                map = map.device_grid
+        moved = False
+        if isinstance(map, WorldMap):
+            moved = self._planner.set_grid_from_world_map(map._map)
+        elif map is not None:
             mapper = map._mapper if hasattr(map, "_mapper") else map
             if mapper is None:
                 raise ValueError("the LocalMapper has no grid yet: update it from a scan first")
@@ -190,7 +193,7 @@ class GridPlanner:
             yaw = float(start[2]) if len(start) > 2 else self._problem[2]
             p = self._problem = (float(start[0]), float(start[1]), yaw) + self._problem[3:]
             self._planner.setup_problem(start_x=p[0], start_y=p[1], start_yaw=p[2], goal_x=p[3], goal_y=p[4], goal_yaw=p[5])
-        return self._solution(self._planner.replan())
+        return self._solution(self._planner.solve() if moved else self._planner.replan())
 
     def find_frontiers(self, robot_x: float, robot_y: float, map=None, map_meta_data: Optional[Dict] = None,
                        min_size: int = 8, min_distance: float = 0.0) -> List[Frontier]:

@@ -380,6 +380,11 @@ SIGNATURES = {
                                      _ip, C.POINTER(C.c_int64)]),
     "kc_mcl_set_field_model": (C.c_int, [_vp, C.c_void_p, _sz, C.c_uint16, C.c_void_p, _sz, C.c_int]),
     "kc_mcl_model_kind": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "kc_worldmap_shift": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "kc_worldmap_check_shift": (C.c_int, [C.c_int32, C.c_int32, C.c_int, C.c_int]),
+    "kc_worldmap_offset": (C.c_int, [_vp, _ip, _ip]),
+    "kc_worldmap_recentre_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip]),
+    "kc_worldmap_recentre": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _ip]),
 }
 
 _lib = None
@@ -1579,6 +1584,20 @@ def worldmap_match_rotations(yaw, n_yaw, yaw_step):
     return [(int(r.cq), int(r.sq)) for r in rot]
 
 
+def worldmap_recentre_plan(width, height, ic, jc, margin, stride):
+    """Rule 49 (host only): the shift (di, dj) that recentres a width x height window on the robot's cell (ic, jc), (0, 0)
+    while the cell is `margin` cells or more from every border; raises ValueError for a bad policy."""
+    di, dj = C.c_int32(), C.c_int32()
+    _check(lib().kc_worldmap_recentre_plan(int(width), int(height), int(ic), int(jc), int(margin), int(stride), C.byref(di),
+                                           C.byref(dj)))
+    return int(di.value), int(dj.value)
+
+
+def worldmap_check_shift(offset, di, dj):
+    """Rule 46's cap (host only): raises IndexError when a shift by (di, dj) would take `offset` above 2^30 cells."""
+    _check(lib().kc_worldmap_check_shift(int(offset[0]), int(offset[1]), int(di), int(dj)))
+
+
 class WorldMapContext(_Owner, _StreamOrdered):
     """Owner of one kc_worldmap context: a world-frame map on the device, fused from local grids.
     Works in cells: a plane is an array m[I, J] of (width, height) cells, I along x, as PlannerContext's grids."""
@@ -1697,6 +1716,32 @@ class WorldMapContext(_Owner, _StreamOrdered):
 
     def clear(self):
         _check(lib().kc_worldmap_clear(self.h))
+
+    def info(self):
+        """-> (width, height, resolution, (origin_x, origin_y)) as the library holds them: the origin at the current
+        offset (rule 46)."""
+        w, h, r, ox, oy = C.c_int(), C.c_int(), C.c_float(), C.c_double(), C.c_double()
+        _check(lib().kc_worldmap_info(self.h, C.byref(w), C.byref(h), C.byref(r), C.byref(ox), C.byref(oy)))
+        return w.value, h.value, r.value, (ox.value, oy.value)
+
+    def offset(self):
+        """Rule 46's (OI, OJ): the cells the window has moved since it was created."""
+        oi, oj = C.c_int32(), C.c_int32()
+        _check(lib().kc_worldmap_offset(self.h, C.byref(oi), C.byref(oj)))
+        return int(oi.value), int(oj.value)
+
+    def shift(self, di, dj):
+        """Rule 47: move the window by whole cells, a positive di towards +x; what leaves is forgotten, what enters is
+        never observed.  `origin`, which every quantisation here reads, follows (rule 46)."""
+        _check(lib().kc_worldmap_shift(self.h, int(di), int(dj)))
+        self.origin = self.info()[3]
+
+    def recentre(self, x, y, margin, stride):
+        """Rule 49's plan for the robot at world (x, y), then the shift -> (di, dj), the shift made."""
+        di, dj = C.c_int32(), C.c_int32()
+        _check(lib().kc_worldmap_recentre(self.h, float(x), float(y), int(margin), int(stride), C.byref(di), C.byref(dj)))
+        self.origin = self.info()[3]  # (a refusal leaves the state, and so the origin, untouched)
+        return int(di.value), int(dj.value)
 
     def points(self, x, y, max_sensor_range, cap=None, count_only=False):
         """Rules 16 to 19: the occupied cells within max_sensor_range of (x, y) as world-frame points, in no particular

@@ -63,7 +63,19 @@ observation wins" model, reach 6 and 16.  One JSON line a reach with
   (c) kc_worldmap_get_distance with nothing dirty: the copy of W x H uint16 alone;
 and one line a particle configuration (4096 x 64, 1024 x 256, 65536 x 24) with the field step and the beam step of the
 same localiser on the same particles, by the host's clock and their launches by HIP events.
-  python tools/worldmap_time.py --field [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --field [--reps 30] [--warmup 3]
+
+--shift times the rolling window (rules 46 to 48): the same world holding what the 400 x 400 local grid saw.  One JSON line
+with
+  (a) kc_worldmap_shift by (64, 0) and by (64, 64), each followed by the shift back, so that the window stays where the
+      map's content is; the figure is one call: the launch, the two device-to-device copies and the wait;
+  (b) the route it replaces: kc_worldmap_get of both planes, numpy.roll of the class plane with the entering strip put to
+      unknown, kc_worldmap_set_prior_host, each timed on its own.  THAT ROUTE LOSES THE EVIDENCE: a prior only knows
+      e_min and e_max, so every cell's count starts again at a bound;
+and one line a reach (6 and 16) with the first distance read after a shift (kc_worldmap_distance_device: the full
+refresh rule 48 asks for, and the wait).  The planes after (a) are compared with the statement (tests/worldmap_shift_ref.py)
+once.
+  python tools/worldmap_time.py --shift [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -418,6 +430,74 @@ def field_leg(args):
                 print(json.dumps(line), flush=True)
 
 
+def shift_leg(args):
+    import worldmap_shift_ref as shref
+
+    ang, rng = syn.dense_scan(2048, 1.2)
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r, ORIGIN[1] + (H // 2) * r)
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as wm:
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        for yaw in (0.0, 0.3, 0.3):
+            wm.update_from_mapper(mapper, centre + (yaw,))
+        cls0, ev0 = wm.planes()
+        line = {"world": [W, H], "reps": args.reps, "warmup": args.warmup}
+        for name, d in (("a_shift_64_0_ms", (64, 0)), ("a_shift_64_64_ms", (64, 64))):
+            wm.shift(*d)
+            cls, ev = wm.planes()
+            we, wc = shref.shift_planes(ev0, cls0, *d)
+            assert np.array_equal(ev, we) and np.array_equal(cls, wc), "the shifted planes differ from the statement"
+            wm.shift(-d[0], -d[1])
+            back = [d, (-d[0], -d[1])]
+            calls = []
+
+            def one():
+                wm.shift(*back[len(calls) & 1])
+                calls.append(0)
+
+            line[name] = timed(one, 2 * args.reps, 2 * args.warmup)
+            if len(calls) & 1:
+                one()
+            assert wm.offset() == (0, 0)
+        both = [None, None]
+
+        def get():
+            both[0], both[1] = wm.planes()
+
+        rolled = [None]
+
+        def roll():
+            c = np.roll(both[0], (-64, -64), axis=(0, 1))
+            c[W - 64:, :] = ref.UNEXPLORED
+            c[:, H - 64:] = ref.UNEXPLORED
+            rolled[0] = c
+
+        line["b_get_both_planes_ms"] = timed(get, args.reps, args.warmup)
+        line["b_numpy_roll_ms"] = timed(roll, args.reps, args.warmup)
+        line["b_set_prior_ms"] = timed(lambda: wm.set_prior(rolled[0]), args.reps, args.warmup)
+        line["b_route_total_ms"] = round(line["b_get_both_planes_ms"][0] + line["b_numpy_roll_ms"][0] + line["b_set_prior_ms"][0], 4)
+        line["b_route_loses_the_evidence"] = True
+        print(json.dumps(line), flush=True)
+        for reach in (6, 16):
+            wm.set_distance(reach)
+            wm.distance_device_ptr()
+            flip = []
+
+            def first_read():
+                wm.shift(64 if not len(flip) & 1 else -64, 0)              # outside the clock
+                flip.append(0)
+                t0 = time.perf_counter()
+                wm.distance_device_ptr()
+                return (time.perf_counter() - t0) * 1e3
+
+            for _ in range(args.warmup):
+                first_read()
+            print(json.dumps({"world": [W, H], "reach": reach, "reps": args.reps, "warmup": args.warmup,
+                              "first_distance_read_after_shift_ms": spread([first_read() for _ in range(args.reps)]),
+                              "refreshed_box": list(wm.distance_info()[2])}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -428,6 +508,7 @@ def main():
     ap.add_argument("--scan", action="store_true", help="time the virtual laser scan instead")
     ap.add_argument("--mcl", action="store_true", help="time the Monte-Carlo localiser instead")
     ap.add_argument("--field", action="store_true", help="time the distance plane and the likelihood-field model instead")
+    ap.add_argument("--shift", action="store_true", help="time the rolling window's shift and the route it replaces instead")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
@@ -441,6 +522,8 @@ def main():
         return mcl_leg(args)
     if args.field:
         return field_leg(args)
+    if args.shift:
+        return shift_leg(args)
     hip = hip_runtime()
     ang, rng = syn.dense_scan(2048, 1.2)                      # ranges 3.6 .. 8.4 m in a 20 m window
     pose_xy = (ORIGIN[0] + 0.5 * W * RES + 0.013, ORIGIN[1] + 0.5 * H * RES - 0.021)
