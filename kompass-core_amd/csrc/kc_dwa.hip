@@ -73,8 +73,7 @@ int upload_omega(kc_dwa *c) {
 // holds the tables of (sig, n) now.  Pointers only: nothing is written, nothing queued reads these tables between
 // cycles (the sensor kernels do not).
 static bool swap_in_pattern(kc_dwa *c, uint64_t sig, size_t n) {
-  // (40 bytes of device memory a sample and pattern: 128 MB of them at most, 16 to 256 patterns)
-  const size_t kKept = std::min<size_t>(256, std::max<size_t>(16, (size_t(128) << 20) / (40 * std::max<size_t>(n, 1))));
+  const size_t kKept = pattern_slots(n);  // (kc_launch_plan.h)
   auto exchange = [&](kc_dwa::PatternTables &t) {
     std::swap(t.vidx, c->d_vidx);
     std::swap(t.row, c->d_row);

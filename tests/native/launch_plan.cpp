@@ -361,7 +361,21 @@ static void yaw_reach() {
   CHECK(yaw_reach_ok(-1.0, 2.0, 0.5, 10, &reach) && reach == 11.0);
 }
 
+// kept window patterns: 128 MB / (40 bytes x n samples), held between 16 and 256.  By hand: 2^27 / 40 = 3355443.2, so
+// 256 patterns fit while n <= 13107 (3355443.2 / 256 = 13107.2) and the quotient falls below 16 past n = 209715
+// (3355443.2 / 16 = 209715.2)
+static void kept_patterns() {
+  CHECK(pattern_slots(0) == 256);
+  CHECK(pattern_slots(1) == 256);
+  CHECK(pattern_slots(13107) == 256);
+  CHECK(pattern_slots(13108) == 255);
+  CHECK(pattern_slots(209715) == 16);
+  CHECK(pattern_slots(209716) == 16);
+  CHECK(pattern_slots(size_t(1) << 20) == 16);
+}
+
 int main() {
+  kept_patterns();
   samples_per_workgroup();
   plain_tile();
   byte_formulas();

@@ -1,5 +1,6 @@
 """CPU: the vector forms of kc_dwa_set_scan's per-beam host loops (csrc/kc_scan_tables.h) against their scalar
-definitions, bit for bit (tests/native/scan_tables.cpp)."""
+definitions, bit for bit (tests/native/scan_tables.cpp); the window lattice of csrc/kc_hostmath.h reused against fresh
+(tests/native/window_lattice.cpp) and against the oracle's sampler at the window's edges (tests/native/window_edges.cpp)."""
 import shutil
 import subprocess
 from pathlib import Path
@@ -29,6 +30,23 @@ def test_reused_window_lattice_equals_a_fresh_one(tmp_path):
     p = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", f"-I{INC}", f"-I{ROOT / 'include'}",
                         str(ROOT / "tests" / "native" / "window_lattice.cpp"), "-o", str(exe)],
                        capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 bad" in r.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None or shutil.which("gcc") is None, reason="needs g++ and gcc")
+def test_window_lattice_equals_the_oracle_at_its_edges(tmp_path):
+    """hm::build_window_lattice against the oracle's ko_sample_velocities, bit for bit, fresh and reused: zero, empty and
+    clipped windows, one omega, the count rules, |v| = kMinVel, -0.0 limits, a narrowed dt (tests/native/window_edges.cpp)."""
+    obj, exe = tmp_path / "kompass_oracle.o", tmp_path / "window_edges"
+    p = subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fno-fast-math", "-c",
+                        str(ROOT / "oracle" / "kompass_oracle.c"), "-o", str(obj)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    p = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", f"-I{INC}", f"-I{ROOT / 'include'}",
+                        f"-I{ROOT / 'oracle'}", str(ROOT / "tests" / "native" / "window_edges.cpp"), str(obj), "-o", str(exe),
+                        "-lm", "-lpthread"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
