@@ -1596,6 +1596,62 @@ int kc_worldmap_recentre(kc_worldmap *ctx, double x, double y, int margin, int s
  * untouched.
  * Rule 51 (the planner does not carry its field across a shift) is the host classes'. */
 
+/* Integrating a measured laser scan by an inverse ray cast (DESIGN.md 4.11 rules 52 to 58): the
+ * one way into the map that needs no local grid.  Nothing in the reference to cite, as above;
+ * integers throughout, bit-equal to tests/worldmap_integrate_ref.py.
+ * Rule 52, input: the scan frame's pose (rule 20), the beam angles through rule 21's table (1 to
+ * 65536 beams, Rc <= 2048), and one int32 zq_k a beam: -1 (the beam says nothing), ZMAX =
+ * llrint((double)range_max / (double)resolution * 65536) (no return), or a range in 2^-16 cells,
+ * 0 <= zq_k < ZMAX.  Rule 53, crossed cells: rule 23's walk from the start cell, the map's
+ * content taking no part; step s enters its cell at q_s = floor(e_s 2^30 / a_s); a beam with
+ * limit z crosses the start cell and every step cell with q_s <= z, tested as e_s 2^30 < (z + 1)
+ * a_s; q_s never decreases, so the crossed cells are a prefix of the walk, and the step that
+ * leaves rule 23's box has q > ZMAX.  Rule 54, marks: a return beam (0 <= zq_k < ZMAX) marks its
+ * last crossed cell HIT and every one before it MISS; a no-return beam (zq_k == ZMAX) marks every
+ * crossed cell MISS with KC_INTEGRATE_CLEAR_NO_RETURN and nothing without; -1 marks nothing;
+ * cells outside the map are walked and never marked; a cell's marks are the OR over all beams.
+ * Rule 55, observation: HIT set -> 100, only MISS set -> 0 (a hit beats a miss); rule 5 is
+ * applied once a marked cell a scan, rule 6's record formed over the cells whose class changed.
+ * Rule 56: no thread order takes part.  Rule 57: the changed box merges into the distance
+ * plane's dirty box as an update's does; between calls the mark plane is all zero. */
+#define KC_INTEGRATE_CLEAR_NO_RETURN 1u
+/* rule 52's refusals (host only, needs no device), in this order: the resolution and the counts
+ * (KC_ERR_INVALID for no beam, KC_ERR_RANGE above 65536), range_max (KC_ERR_INVALID unless a
+ * finite float > 0, KC_ERR_RANGE for Rc > 2048), flags (KC_ERR_INVALID for any bit but
+ * KC_INTEGRATE_CLEAR_NO_RETURN), then zq_or_null when given (KC_ERR_INVALID for a value outside
+ * -1 .. ZMAX).  rc_out, zmax_out (each may be NULL): Rc and ZMAX, 0 on a refusal. */
+int kc_worldmap_integrate_check(float resolution, size_t n_beams, float range_max, unsigned int flags,
+                                const int32_t *zq_or_null, int32_t *rc_out, int64_t *zmax_out);
+/* rule 52's quantiser (host only, needs no device): zq_out[k] is -1 for a NaN, a negative range
+ * or a range below range_min; ZMAX for +inf or a range >= range_max; else llrint(ranges[k] /
+ * resolution * 65536), rule 33's arithmetic.  -0.0 is not negative.  Refusals: null arguments,
+ * kc_worldmap_integrate_check's without flags and zq, KC_ERR_INVALID unless range_min is a finite
+ * float >= 0; then nothing is written. */
+int kc_worldmap_quantise_ranges(float resolution, const double *ranges, size_t n, float range_max, float range_min,
+                                int32_t *zq_out);
+/* Rules 52 to 57 on the map: two launches on the map's stream (worldmap_mark_kernel, a beam's
+ * walk shared among lanes in segments of 8 steps; worldmap_integrate_apply_kernel over the walk's
+ * box clipped to the map) and the 20-byte read-back of rule 6's record; returns with the map final.  A scan whose box lies wholly outside
+ * the map launches nothing and returns the empty record.  Checks: null arguments, then
+ * kc_worldmap_integrate_check with zq, the angles (finite), the pose (as an update's), then the
+ * device; a refused call queues nothing and leaves the map and the mark plane as they were. */
+int kc_worldmap_integrate(kc_worldmap *ctx, const kc_worldmap_pose *pose, const double *angles, size_t n_beams,
+                          const int32_t *zq, float range_max, unsigned int flags, kc_worldmap_result *result_out);
+/* The same arguments, the mark launch alone (rules 53 and 54): the mark plane, a byte a cell at I
+ * + J * width with bit 0 = MISS and bit 1 = HIT, is copied into marks_out (cap cells, at least
+ * width * height, else KC_ERR_RANGE) and zeroed again; the map is untouched.  For tests, and for
+ * finding out which half is wrong. */
+int kc_worldmap_integrate_marks(kc_worldmap *ctx, const kc_worldmap_pose *pose, const double *angles, size_t n_beams,
+                                const int32_t *zq, float range_max, unsigned int flags, uint8_t *marks_out, size_t cap);
+/* Measurement only (rule 54's marks do not depend on it): a byte load in front of the mark kernel's
+ * atomic that skips the atomic where the bit stands already.  Off by default: measured, it makes
+ * the walk wait for a load every step. */
+int kc_worldmap_integrate_set_precheck(kc_worldmap *ctx, int enable);
+/* HIP events around the two launches of kc_worldmap_integrate; ms_out: mark, apply of the last
+ * call.  KC_ERR_STATE when no integration has been timed. */
+int kc_worldmap_integrate_set_timing(kc_worldmap *ctx, int enable);
+int kc_worldmap_integrate_times(kc_worldmap *ctx, float ms_out[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1108,6 +1108,21 @@ PYBIND11_MODULE(kompass_cpp, m) {
              return a;
            }, py::arg("poses"), py::arg("angles"), py::arg("range_max"), py::arg("unknown_blocks") = false,
            "The same for a batch of poses (x, y, yaw) in one launch: float64 [M, B]")
+      .def("integrate_scan", [](Mapping::WorldMap &m, double x, double y, double yaw, const std::vector<double> &angles,
+                                const std::vector<double> &ranges, float range_max, float range_min, bool clear_no_return) {
+             py::gil_scoped_release nogil;
+             return m.integrateScan(x, y, yaw, angles, ranges, range_max, range_min, clear_no_return);
+           }, py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("angles"), py::arg("ranges"), py::arg("range_max"),
+           py::arg("range_min") = 0.0f, py::arg("clear_no_return") = false,
+           "One measured laser scan into the map by an inverse ray cast (DESIGN.md 4.11 rules 52 to 58); (x, y, yaw): the scan "
+           "frame's pose in the world.  -> changed cells")
+      .def("integrate_scan_at", [](Mapping::WorldMap &m, const py::tuple &pose, const std::vector<double> &angles,
+                                   const std::vector<double> &ranges, float range_max, float range_min, bool clear_no_return) {
+             const kc_worldmap_pose p = worldMapPose(pose);
+             py::gil_scoped_release nogil;
+             return m.integrateScanAt(p, angles, ranges, range_max, range_min, clear_no_return);
+           }, py::arg("pose"), py::arg("angles"), py::arg("ranges"), py::arg("range_max"), py::arg("range_min") = 0.0f,
+           py::arg("clear_no_return") = false, "integrate_scan at a quantised pose (cq, sq, tx, ty), a match's `pose`")
       .def("enable_distance", &Mapping::WorldMap::enableDistance, py::arg("reach"), py::arg("unknown_blocks") = false,
            "Keep the distance plane at `reach` cells (1 .. 254; 0: off): DESIGN.md 4.11 rules 42 and 43")
       .def_property_readonly("distance_reach", &Mapping::WorldMap::distanceReach)

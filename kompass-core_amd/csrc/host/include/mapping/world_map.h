@@ -97,6 +97,19 @@ class WorldMap {
   std::vector<double> scanCells(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
                                 bool unknown_blocks, std::vector<int32_t> &cells_out) const;
 
+  // One measured laser scan into the map by an inverse ray cast (DESIGN.md 4.11 rules 52 to 58), no local grid in
+  // between: (x, y, yaw) is the scan frame's pose in the world, `angles` the beams in that frame, `ranges` one measured
+  // range a beam in metres.  A NaN, a negative range or one below range_min says nothing; +inf or a range >= range_max
+  // is a beam without a return, which clears the cells it crosses up to range_max with clear_no_return and says nothing
+  // without; any other beam marks the cell its range ends in occupied and the cells before it empty, a hit beating a
+  // miss where beams disagree.  Two launches on the device.  Returns changed(); changedBox() follows.
+  // std::invalid_argument (sizes that differ, no beam, range_max, range_min, a non-finite angle or pose),
+  // std::out_of_range (above 2048 cells of range or 65536 beams).  ...At: at a quantised pose (a Match's).
+  uint32_t integrateScan(double x, double y, double yaw, const std::vector<double> &angles, const std::vector<double> &ranges,
+                         float range_max, float range_min = 0.0f, bool clear_no_return = false);
+  uint32_t integrateScanAt(const kc_worldmap_pose &pose, const std::vector<double> &angles, const std::vector<double> &ranges,
+                           float range_max, float range_min = 0.0f, bool clear_no_return = false);
+
   // The distance plane (DESIGN.md 4.11 rules 42 and 43), off by default: per cell the squared distance in cells to the
   // nearest OCCUPIED cell (with unknown_blocks also a never-observed one) within `reach` cells, KC_WORLDMAP_DIST_FAR
   // beyond.  Kept lazily: an update only notes its changed box, whoever reads the plane refreshes that box grown by

@@ -1,6 +1,8 @@
 // WorldMap host side: argument plumbing over kc_worldmap_* (no reference counterpart, see the header).
 #include "mapping/world_map.h"
 
+#include <stdexcept>
+
 namespace Kompass {
 namespace Mapping {
 
@@ -189,6 +191,21 @@ std::vector<double> WorldMap::scans(const std::vector<std::array<double, 3>> &po
 std::vector<double> WorldMap::scanCells(double x, double y, double yaw, const std::vector<double> &angles, float range_max,
                                         bool unknown_blocks, std::vector<int32_t> &cells_out) const {
   return scanPoses({{x, y, yaw}}, angles, range_max, unknown_blocks, &cells_out);
+}
+
+uint32_t WorldMap::integrateScanAt(const kc_worldmap_pose &pose, const std::vector<double> &angles, const std::vector<double> &ranges,
+                                   float range_max, float range_min, bool clear_no_return) {
+  if (angles.size() != ranges.size()) throw std::invalid_argument("integrateScan: one range a beam angle");
+  std::vector<int32_t> zq(ranges.size());
+  hip::check(kc_worldmap_quantise_ranges(res_, ranges.data(), ranges.size(), range_max, range_min, zq.data()));
+  hip::check(kc_worldmap_integrate(ctx_.get(), &pose, angles.data(), angles.size(), zq.data(), range_max,
+                                   clear_no_return ? KC_INTEGRATE_CLEAR_NO_RETURN : 0u, &last_));
+  return last_.changed;
+}
+
+uint32_t WorldMap::integrateScan(double x, double y, double yaw, const std::vector<double> &angles, const std::vector<double> &ranges,
+                                 float range_max, float range_min, bool clear_no_return) {
+  return integrateScanAt(quantisePose(res_, ox_, oy_, x, y, yaw), angles, ranges, range_max, range_min, clear_no_return);
 }
 
 void WorldMap::enableDistance(int reach, bool unknown_blocks) {

@@ -56,6 +56,13 @@
 //      stream bring the planes back to where they were, so every pointer handed out stays valid.  The origin is never
 //      summed from shift to shift: it is ox0 + (double)OI * (double)res whenever it is asked for.
 //
+//  (j) scan integration (rules 52 to 57).  The one way into the map that does not go through a local grid: a measured
+//      scan's beams are walked through the world by rule 23 and leave MISS / HIT bits in a mark plane of a byte a cell
+//      (worldmap_mark_kernel: consecutive beams on consecutive lanes, a beam's walk shared among lanes in segments that
+//      are entered by a closed form, an atomic OR on the aligned dword); worldmap_integrate_apply_kernel then runs over the walk's box in the update kernel's
+//      layout, turns a mark byte into one observation (a hit beats a miss), puts the byte back to zero and applies
+//      rule 5 with the update's record.  OR commutes and a cell is applied once: no thread order takes part.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -598,6 +605,173 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_dist_cols_kernel(WmDistArgs
   }
 }
 
+// ---- (j) scan integration (rules 52 to 57) ----
+constexpr unsigned kWmMarkMiss = 1u, kWmMarkHit = 2u;  // the bits of a mark byte
+
+struct WmMarkArgs {
+  uint8_t *marks;        // a byte a world cell, the plane rounded up to whole dwords; all zero between calls
+  const int2 *table;     // rule 21: (ac, as) a beam
+  const int32_t *zq;     // rule 52
+  kc_worldmap_pose pose;
+  long long zmax;
+  int W, H, B, rc;
+  int clear_no_return, precheck;
+};
+
+// The OR of `bit` into the byte of cell (I, J): an atomic without a return value on the aligned dword that holds it, which
+// lies inside the plane whatever W is (the plane's size is a multiple of 4).  Two things in front of it:
+//  - a lane whose lower neighbour marks the same bit of the same cell in this step leaves the mark to it.  Near the sensor
+//    neighbouring beams stand in the same cell step after step; every lane still in the loop comes through here once a
+//    step, so the ballot names the lanes whose `code` the shuffle may read.  Kept: it is the faster kernel at every
+//    beam count measured.
+//  - `precheck`: a plain byte load that skips the atomic where the bit stands already (a stale byte only costs the atomic
+//    it would have saved, and OR is idempotent).  Measured and OFF by default: the walk then waits for a load every step,
+//    where the atomic alone is sent and forgotten.  The switch stays for the timing tool.
+__device__ __forceinline__ void wm_mark_cell(const WmMarkArgs &a, int I, int J, unsigned bit) {
+  const bool inside = I >= 0 && I < a.W && J >= 0 && J < a.H;  // rule 54: outside, walked and never marked
+  const size_t cell = inside ? static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W) : size_t{0};
+  const unsigned code = inside ? static_cast<unsigned>(cell) * 4u + bit : 0u;  // bit is 1 or 2, cells <= 2^28: 0 is no mark
+  const unsigned long long live = __ballot(1);
+  const int lane = static_cast<int>(threadIdx.x) & 63;
+  const unsigned below = __shfl_up(code, 1);
+  if (lane > 0 && ((live >> (lane - 1)) & 1ull) && below == code) return;
+  if (!inside) return;
+  if (a.precheck && (a.marks[cell] & bit)) return;
+  atomicOr(reinterpret_cast<unsigned int *>(a.marks) + (cell >> 2), bit << (8u * static_cast<unsigned>(cell & 3)));
+}
+
+constexpr int kWmMarkChunk = 8;  // steps along a beam's dominant axis that one lane walks
+
+// Rule 23's walk with nothing loaded that decides it, so no rounds: a step is the axis choice (D = ex |dy| - ey |dx| kept by
+// addition as in wm_walk), the crossing test of rule 53 for the step AHEAD, and the mark of the cell the beam stands in:
+// MISS while the step ahead is crossed, else this is the beam's last crossed cell, HIT for a return.  The test e 2^30 < (z +
+// 1) a is kept as a remainder per axis, r = (z + 1) a - e 2^30 > 0, that a step lowers by 2^46.  The step that leaves rule
+// 23's box is never crossed (rule 53), so the box is not tested; the count only bounds the loop.
+//
+// blockIdx.x * 256 + threadIdx.x: the beam, consecutive beams on consecutive lanes.  blockIdx.y: the segment of the walk
+// this lane makes.  A walk of a few hundred dependent steps leaves a lane alone with its latency, whatever the beam count
+// (DESIGN.md 4.11 has the figures), and the walk can be entered in the middle: it merges the x steps m = 0, 1, .. at
+// EX_m = ex + m 2^16 and the y steps n at EY_n = ey + n 2^16, x step m before y step n iff EX_m |dy| <= EY_n |dx| (rule 23's
+// comparison: the tie goes to x).  With x the dominant axis (|dx| >= |dy|), segment g > 0 starts in front of x step m0 = 8 g
+// with every y step before it made: n0 = #{n : EY_n |dx| < EX_m0 |dy|} = ceil(T / (2^16 |dx|)) for T = EX_m0 |dy| - ey |dx| >
+// 0, else 0.  With y dominant it starts in front of y step n0 = 8 g with m0 = #{m : EX_m |dy| <= EY_n0 |dx|} = floor(T /
+// (2^16 |dy|)) + 1 for T = EY_n0 |dx| - ex |dy| >= 0, else 0 (and 0 for dx == 0, where no step goes along x).  One 64-bit
+// division a lane; every product stays below 2^59.  The walk reaches that state iff the steps in front of it are crossed,
+// and since q never decreases (rule 53) that is: x step m0 - 1 and y step n0 - 1 are, where they exist.  A lane ends in
+// front of the next segment's first step, whose cell that segment marks.  Segment 0 starts in the start cell.
+__global__ __launch_bounds__(kWmBlock) void worldmap_mark_kernel(WmMarkArgs a) {
+  const int k = static_cast<int>(blockIdx.x) * kWmBlock + static_cast<int>(threadIdx.x);
+  if (k >= a.B) return;
+  const long long z = a.zq[k];
+  if (z < 0) return;  // rule 54: the beam says nothing
+  const bool ret = z < a.zmax;
+  if (!ret && !a.clear_no_return) return;
+  const int2 t = a.table[k];
+  const long long cq = a.pose.cq, sq = a.pose.sq;
+  const int dx = static_cast<int>((cq * t.x - sq * t.y + (1ll << 15)) >> 16);
+  const int dy = static_cast<int>((sq * t.x + cq * t.y + (1ll << 15)) >> 16);
+  const long long X0 = a.pose.tx + (1ll << 15), Y0 = a.pose.ty + (1ll << 15);
+  int I = static_cast<int>(X0 >> 16), J = static_cast<int>(Y0 >> 16);
+  const int fx = static_cast<int>(X0 & 0xFFFF), fy = static_cast<int>(Y0 & 0xFFFF);
+  const int sx = dx > 0 ? 1 : -1, sy = dy > 0 ? 1 : -1;
+  const long long adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
+  const long long ex = dx > 0 ? 65536 - fx : fx, ey = dy > 0 ? 65536 - fy : fy;
+  const long long step_x = 65536ll * ady, step_y = 65536ll * adx;
+  const bool x_dom = adx >= ady;
+  long long m0 = 0, n0 = 0;  // the x and y steps made in front of this segment
+  if (blockIdx.y > 0) {
+    const long long first = static_cast<long long>(blockIdx.y) * kWmMarkChunk;
+    if (x_dom) {
+      m0 = first;
+      const long long T = (ex + (m0 << 16)) * ady - ey * adx;
+      n0 = T > 0 ? (T + step_y - 1) / step_y : 0;
+    } else {
+      n0 = first;
+      const long long T = (ey + (n0 << 16)) * adx - ex * ady;
+      m0 = (dx != 0 && T >= 0) ? T / step_x + 1 : 0;
+    }
+    // the state is on the beam's crossed prefix iff the steps in front of it are crossed
+    if (m0 > 0 && !(((ex + ((m0 - 1) << 16)) << 30) < (z + 1) * adx)) return;
+    if (n0 > 0 && !(((ey + ((n0 - 1) << 16)) << 30) < (z + 1) * ady)) return;
+  }
+  const long long EX = ex + (m0 << 16), EY = ey + (n0 << 16);
+  I += sx * static_cast<int>(m0);
+  J += sy * static_cast<int>(n0);
+  // dy == 0: D = -EY |dx| <= 0 and stays (step_x = 0), every step goes along x.  dx == 0: D = EX |dy| may be 0, which would
+  // send a step along x, so it is put to 1, and stays (step_y = 0)
+  long long D = dx == 0 ? 1 : EX * ady - EY * adx;
+  long long rx = (z + 1) * adx - (EX << 30), ry = (z + 1) * ady - (EY << 30);  // all below 2^59 in magnitude
+  int dominant = 0;  // steps this lane has made along the dominant axis
+  // between two steps along the dominant axis lies at most one along the other (a tie included), and one may come first
+  for (int s = 0; s < 2 * kWmMarkChunk + 2; ++s) {
+    const bool along_x = D <= 0;
+    if (along_x == x_dom && dominant == kWmMarkChunk) return;  // the next segment's first step: its lane marks this cell
+    const bool last = (along_x ? rx : ry) <= 0;  // the step ahead is not crossed: this cell is the beam's last
+    wm_mark_cell(a, I, J, last && ret ? kWmMarkHit : kWmMarkMiss);
+    if (last) return;
+    dominant += along_x == x_dom ? 1 : 0;
+    if (along_x) {
+      I += sx;
+      rx -= 1ll << 46;
+      D += step_x;
+    } else {
+      J += sy;
+      ry -= 1ll << 46;
+      D -= step_y;
+    }
+  }
+}
+
+struct WmApplyArgs {
+  uint8_t *marks;
+  int8_t *evidence, *cls;
+  int *rec, *rec_next;    // as the update's
+  int W;
+  int i_lo, j_lo, i_hi, j_hi;  // the launch box, inclusive, inside the map
+  WmModel m;
+};
+
+// worldmap_update_kernel's geometry and record over the walk's box; the observation is the cell's mark byte (rule 55: a
+// hit beats a miss), which the lane that read it puts back to zero.  Byte loads and stores, for the update's reason.
+__global__ __launch_bounds__(kWmBlock) void worldmap_integrate_apply_kernel(WmApplyArgs a) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
+    a.rec_next[0] = 0;
+    a.rec_next[1] = INT_MAX;
+    a.rec_next[2] = INT_MAX;
+    a.rec_next[3] = -1;
+    a.rec_next[4] = -1;
+  }
+  const int I = a.i_lo + static_cast<int>(blockIdx.x) * kWmLanes + static_cast<int>(threadIdx.x);
+  const int J = a.j_lo + static_cast<int>(blockIdx.y) * kWmRows + static_cast<int>(threadIdx.y);
+  bool changed = false;
+  if (I <= a.i_hi && J <= a.j_hi) {
+    const size_t cell = static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W);
+    const unsigned mark = a.marks[cell];
+    if (mark != 0u) {
+      a.marks[cell] = 0;
+      const int old = a.evidence[cell];
+      const int base = old == kWmNever ? 0 : old;
+      const int e = (mark & kWmMarkHit) ? min(base + a.m.hit, a.m.e_max) : max(base - a.m.miss, a.m.e_min);
+      const int8_t k = wm_class(e, a.m.occ_thr);
+      changed = a.cls[cell] != k;
+      if (e != old) a.evidence[cell] = static_cast<int8_t>(e);
+      if (changed) a.cls[cell] = k;
+    }
+  }
+  // one wavefront is one row segment (blockDim.x == 64): J is uniform in it
+  const unsigned long long mask = __ballot(changed);
+  if (mask == 0) return;
+  const int lane = static_cast<int>(threadIdx.x);
+  const int first = __ffsll(mask) - 1, last = 63 - __clzll(mask);
+  if (lane == first) {
+    atomicAdd(reinterpret_cast<unsigned int *>(&a.rec[0]), static_cast<unsigned int>(__popcll(mask)));
+    atomicMin(&a.rec[1], I);
+    atomicMin(&a.rec[2], J);
+    atomicMax(&a.rec[4], J);
+  }
+  if (lane == last) atomicMax(&a.rec[3], I);
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -640,6 +814,13 @@ struct kc_worldmap {
   int dirty[4] = {0, 0, -1, -1};   // (i_min, j_min, i_max, j_max), empty while i_max < i_min
   int dist_last[4] = {-1, -1, -1, -1};
   bool dist_last_full = false;
+  // scan integration (rules 52 to 57): the mark plane from the first call on, all zero between calls
+  DevBuf<uint8_t> d_marks;
+  bool marks_zero = false;         // the plane has been zeroed once and every call since has left it so
+  DevBuf<int32_t> d_zq;
+  PinBuf<int32_t> h_zq;
+  bool mark_precheck = false;      // the byte load in front of the atomic: measured and off (on: for the timing tool)
+  Timing integ_time;               // mark, apply
 
   // rule 46: one product and one sum in double, never accumulated
   double ox() const { return ox0 + static_cast<double>(OI) * static_cast<double>(res); }
@@ -1126,6 +1307,118 @@ int wm_shift(kc_worldmap *c, int di, int dj) {
   return KC_OK;
 }
 
+// rule 52's refusals in its order: counts, range_max (and Rc), flags, zq (nullptr: not looked at)
+int wm_integrate_check(float res, size_t n_beams, float range_max, unsigned flags, const int32_t *zq, int *rc_out, long long *zmax_out) {
+  int rc = 0;
+  KC_TRY(worldmap_scan_check(res, 1, n_beams, range_max, 0u, &rc));
+  if (flags & ~static_cast<unsigned>(KC_INTEGRATE_CLEAR_NO_RETURN)) KC_FAIL(KC_ERR_INVALID, "unknown integration flag bits 0x%x", flags);
+  const long long zmax = std::llrint(static_cast<double>(range_max) / static_cast<double>(res) * 65536.0);
+  if (zq)
+    for (size_t k = 0; k < n_beams; ++k)
+      if (zq[k] < -1 || zq[k] > zmax) KC_FAIL(KC_ERR_INVALID, "quantised range %zu is %d, outside -1 .. %lld", k, zq[k], zmax);
+  if (rc_out) *rc_out = rc;
+  if (zmax_out) *zmax_out = zmax;
+  return KC_OK;
+}
+
+// The walk's box [I0 - Rc - 1, I0 + Rc + 1] x [J0 - Rc - 1, J0 + Rc + 1] clipped to the map, inclusive; false when empty
+bool wm_integrate_box(const kc_worldmap *c, const kc_worldmap_pose *p, int rc, int box[4]) {
+  const long long i0 = (p->tx + (1ll << 15)) >> 16, j0 = (p->ty + (1ll << 15)) >> 16;  // within 2^20 + 1 cells
+  const long long lo_i = i0 - rc - 1, hi_i = i0 + rc + 1, lo_j = j0 - rc - 1, hi_j = j0 + rc + 1;
+  if (hi_i < 0 || hi_j < 0 || lo_i > c->W - 1 || lo_j > c->H - 1) return false;
+  box[0] = static_cast<int>(std::max<long long>(lo_i, 0));
+  box[1] = static_cast<int>(std::max<long long>(lo_j, 0));
+  box[2] = static_cast<int>(std::min<long long>(hi_i, c->W - 1));
+  box[3] = static_cast<int>(std::min<long long>(hi_j, c->H - 1));
+  return true;
+}
+
+// Rules 52 to 57.  marks_out == nullptr: the mark launch, the apply launch and the record's read-back.  Otherwise the mark
+// launch alone, the plane copied into marks_out and zeroed again, the map untouched.  Check order: counts, range_max,
+// flags, zq, the angles, the pose, then the device; a refused call queues nothing.
+int wm_integrate(kc_worldmap *c, const kc_worldmap_pose *p, const double *angles, size_t n, const int32_t *zq, float range_max,
+                 unsigned flags, kc_worldmap_result *out, uint8_t *marks_out) {
+  int rc = 0;
+  long long zmax = 0;
+  KC_TRY(wm_integrate_check(c->res, n, range_max, flags, zq, &rc, &zmax));
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
+  KC_TRY(wm_check_pose(p));
+  if (out) *out = kc_worldmap_result{0, -1, -1, -1, -1};
+  const size_t cells = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  int box[4];
+  const bool inside = wm_integrate_box(c, p, rc, box);
+  if (!inside && !marks_out) return KC_OK;  // rule 54: no crossed cell lies inside the map; nothing is launched
+  KC_HIP(hipSetDevice(c->device));
+  const size_t plane = (cells + 3) / 4 * 4;
+  if (!c->marks_zero) {
+    KC_TRY(c->d_marks.reserve(plane));
+    KC_HIP(hipMemsetAsync(c->d_marks.p, 0, plane, c->stream));
+  }
+  c->marks_zero = false;  // until this call has put the plane back
+  if (inside) {
+    KC_TRY(c->d_zq.reserve(n));
+    KC_TRY(c->h_zq.reserve(n));
+    KC_TRY(c->scan_table.ensure(angles, n, c->stream));
+    std::memcpy(c->h_zq.p, zq, n * sizeof(int32_t));
+    KC_HIP(hipMemcpyAsync(c->d_zq.p, c->h_zq.p, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    WmMarkArgs m{};
+    m.marks = c->d_marks.p;
+    m.table = reinterpret_cast<const int2 *>(c->scan_table.d.p);
+    m.zq = c->d_zq.p;
+    m.pose = *p;
+    m.zmax = zmax;
+    m.W = c->W;
+    m.H = c->H;
+    m.B = static_cast<int>(n);
+    m.rc = rc;
+    m.clear_no_return = (flags & KC_INTEGRATE_CLEAR_NO_RETURN) ? 1 : 0;
+    m.precheck = c->mark_precheck ? 1 : 0;
+    c->integ_time.begin_cycle();
+    KC_TRY(c->integ_time.start("mark", c->stream));
+    // a crossed step stays inside rule 23's box (rule 53): at most Rc + 1 of them along one axis
+    const dim3 mgrid(static_cast<unsigned>((n + kWmBlock - 1) / kWmBlock), static_cast<unsigned>((rc + 2) / kWmMarkChunk + 1));
+    hipLaunchKernelGGL(worldmap_mark_kernel, mgrid, dim3(kWmBlock), 0, c->stream, m);
+    KC_HIP(hipGetLastError());
+    KC_TRY(c->integ_time.stop(c->stream));
+  }
+  if (marks_out) {
+    KC_HIP(hipMemcpyAsync(marks_out, c->d_marks.p, cells, hipMemcpyDeviceToHost, c->stream));
+    if (inside) KC_HIP(hipMemsetAsync(c->d_marks.p, 0, plane, c->stream));
+    KC_HIP(hipStreamSynchronize(c->stream));
+    c->marks_zero = true;
+    return KC_OK;
+  }
+  WmApplyArgs a{};
+  KC_TRY(c->rec.begin(c->stream, &a.rec_next));
+  a.rec = c->rec.cur;
+  a.marks = c->d_marks.p;
+  a.evidence = c->d_evidence.p;
+  a.cls = c->d_cls.p;
+  a.W = c->W;
+  a.i_lo = box[0];
+  a.j_lo = box[1];
+  a.i_hi = box[2];
+  a.j_hi = box[3];
+  a.m = c->m;
+  KC_TRY(c->integ_time.start("apply", c->stream));
+  hipLaunchKernelGGL(worldmap_integrate_apply_kernel, wm_box_grid(box), dim3(kWmLanes, kWmRows), 0, c->stream, a);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->integ_time.stop(c->stream));
+  KC_TRY(c->rec.commit(c->stream));
+  c->marks_zero = true;  // every marked cell lies in the box, and its lane has put the byte back
+  const int *r = c->rec.h.p;
+  out->changed = static_cast<uint32_t>(r[0]);
+  if (r[0] != 0) {
+    out->i_min = r[1];
+    out->j_min = r[2];
+    out->i_max = r[3];
+    out->j_max = r[4];
+    c->dirty_merge(r[1], r[2], r[3], r[4]);  // rule 57: exactly as an update's (rule 43)
+  }
+  return KC_OK;
+}
+
 void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *out) {
   *out = kc_worldmap_match_result{};
   if (g) out->pose = *g;
@@ -1542,6 +1835,69 @@ int kc_worldmap_recentre(kc_worldmap *c, double x, double y, int margin, int str
   *di_out = di;
   *dj_out = dj;
   return KC_OK;
+}
+
+int kc_worldmap_integrate_check(float resolution, size_t n_beams, float range_max, unsigned int flags, const int32_t *zq_or_null,
+                                int32_t *rc_out, int64_t *zmax_out) {
+  if (rc_out) *rc_out = 0;
+  if (zmax_out) *zmax_out = 0;
+  int rc = 0;
+  long long zmax = 0;
+  KC_TRY(wm_integrate_check(resolution, n_beams, range_max, flags, zq_or_null, &rc, &zmax));
+  if (rc_out) *rc_out = rc;
+  if (zmax_out) *zmax_out = zmax;
+  return KC_OK;
+}
+
+// rule 52, a beam a turn of the loop; the comparisons are written so that a NaN falls into the first
+int kc_worldmap_quantise_ranges(float resolution, const double *ranges, size_t n, float range_max, float range_min, int32_t *zq_out) {
+  if (!ranges || !zq_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  long long zmax = 0;
+  KC_TRY(wm_integrate_check(resolution, n, range_max, 0u, nullptr, nullptr, &zmax));
+  if (!std::isfinite(range_min) || range_min < 0.0f) KC_FAIL(KC_ERR_INVALID, "range_min must be a finite float >= 0, got %g", static_cast<double>(range_min));
+  const double r = static_cast<double>(resolution), lo = static_cast<double>(range_min), hi = static_cast<double>(range_max);
+  for (size_t k = 0; k < n; ++k) {
+    const double z = ranges[k];
+    if (!(z >= 0.0) || z < lo) zq_out[k] = -1;  // a NaN, a negative range (-0.0 is not one), a range below range_min
+    else if (z >= hi) zq_out[k] = static_cast<int32_t>(zmax);  // +inf included
+    else zq_out[k] = static_cast<int32_t>(std::llrint(z / r * 65536.0));
+  }
+  return KC_OK;
+}
+
+int kc_worldmap_integrate(kc_worldmap *c, const kc_worldmap_pose *pose, const double *angles, size_t n_beams, const int32_t *zq,
+                          float range_max, unsigned int flags, kc_worldmap_result *out) {
+  if (!c || !pose || !angles || !zq || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  return wm_integrate(c, pose, angles, n_beams, zq, range_max, flags, out, nullptr);
+}
+
+int kc_worldmap_integrate_marks(kc_worldmap *c, const kc_worldmap_pose *pose, const double *angles, size_t n_beams,
+                                const int32_t *zq, float range_max, unsigned int flags, uint8_t *marks_out, size_t cap) {
+  if (!c || !pose || !angles || !zq || !marks_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  const size_t cells = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
+  if (cells > cap) KC_FAIL(KC_ERR_RANGE, "%zu cells do not fit the output capacity %zu", cells, cap);
+  return wm_integrate(c, pose, angles, n_beams, zq, range_max, flags, nullptr, marks_out);
+}
+
+int kc_worldmap_integrate_set_precheck(kc_worldmap *c, int enable) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  c->mark_precheck = enable != 0;
+  return KC_OK;
+}
+
+int kc_worldmap_integrate_set_timing(kc_worldmap *c, int enable) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  c->integ_time.enabled = enable != 0;
+  c->integ_time.begin_cycle();
+  return KC_OK;
+}
+
+int kc_worldmap_integrate_times(kc_worldmap *c, float ms_out[2]) {
+  if (!c || !ms_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->integ_time.enabled || c->integ_time.used != 2) KC_FAIL(KC_ERR_STATE, "no integration has been timed on this map");
+  KC_HIP(hipSetDevice(c->device));
+  size_t n = 0;
+  return c->integ_time.get(nullptr, ms_out, 2, &n);
 }
 
 int kc_worldmap_grid_device(kc_worldmap *c, void **dev_cls_int8) {

@@ -141,6 +141,29 @@ class WorldMap:
             return self._map.update_at(mapper, m.pose)
         return self._map.update(mapper, float(robot_state.x), float(robot_state.y), float(robot_state.yaw))
 
+    def integrate_scan(self, robot_state, scan, angles=None, range_max: Optional[float] = None, range_min: float = 0.0,
+                       clear_no_return: bool = False, follow: Optional[Tuple[int, int]] = None) -> int:
+        """Fuse one raw laser scan by an inverse ray cast on the device (DESIGN.md 4.11 rules 52 to 58), no `LocalMapper`
+        in between; robot_state (x, y, yaw): the scan frame's pose in the world (a robot state, an `MCL` estimate or a
+        tuple).  scan: a `LaserScanData` (its angles, ranges, range_min and range_max; the arguments, where given, take
+        their place), or an array of ranges in metres together with `angles`.  A beam's range ends in an occupied cell and
+        crosses empty ones, a hit beating a miss where beams disagree; NaN, a negative range or one below range_min says
+        nothing; inf or a range >= range_max is a beam without a return, which clears what it crosses up to range_max
+        with clear_no_return and says nothing without.  A sensor's yaw offset is folded into `angles`; a translated mount
+        is out of scope.  follow=(margin, stride): `recentre` first, as in `update`.  -> cells whose class changed."""
+        ranges = getattr(scan, "ranges", scan)
+        if hasattr(scan, "ranges"):
+            angles = scan.angles if angles is None else angles
+            range_max = scan.range_max if range_max is None else range_max
+            range_min = scan.range_min if not range_min else range_min
+        if angles is None or range_max is None:
+            raise TypeError("an array of ranges needs angles and range_max")
+        a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        r = np.ascontiguousarray(ranges, dtype=np.float64).reshape(-1)
+        if follow is not None:
+            self.recentre(robot_state, int(follow[0]), int(follow[1]))
+        return self._map.integrate_scan(*self._pose(robot_state), a, r, float(range_max), float(range_min), bool(clear_no_return))
+
     def clear(self) -> None:
         self._map.clear()
 

@@ -385,6 +385,14 @@ SIGNATURES = {
     "kc_worldmap_offset": (C.c_int, [_vp, _ip, _ip]),
     "kc_worldmap_recentre_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip]),
     "kc_worldmap_recentre": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, _ip, _ip]),
+    "kc_worldmap_integrate_check": (C.c_int, [C.c_float, _sz, C.c_float, C.c_uint, C.c_void_p, _ip, C.POINTER(C.c_int64)]),
+    "kc_worldmap_quantise_ranges": (C.c_int, [C.c_float, _dp, _sz, C.c_float, C.c_float, _ip]),
+    "kc_worldmap_integrate": (C.c_int, [_vp, C.POINTER(WorldMapPose), _dp, _sz, _ip, C.c_float, C.c_uint,
+                                        C.POINTER(WorldMapResult)]),
+    "kc_worldmap_integrate_marks": (C.c_int, [_vp, C.POINTER(WorldMapPose), _dp, _sz, _ip, C.c_float, C.c_uint, C.c_void_p, _sz]),
+    "kc_worldmap_integrate_set_precheck": (C.c_int, [_vp, C.c_int]),
+    "kc_worldmap_integrate_set_timing": (C.c_int, [_vp, C.c_int]),
+    "kc_worldmap_integrate_times": (C.c_int, [_vp, _fp]),
 }
 
 _lib = None
@@ -1564,6 +1572,39 @@ def _scan_flags(unknown_blocks, flags):
     return int(flags) if flags is not None else (SCAN_UNKNOWN_BLOCKS if unknown_blocks else 0)
 
 
+INTEGRATE_CLEAR_NO_RETURN = 1  # KC_INTEGRATE_CLEAR_NO_RETURN
+INTEGRATE_MISS, INTEGRATE_HIT = 1, 2  # the bits of a mark byte (WorldMapContext.integrate_marks)
+
+
+def _zq(zq):
+    z = np.asarray(zq)
+    if z.dtype.kind not in "iu":
+        raise ValueError("quantised ranges are integers: worldmap_quantise_ranges makes them")
+    if z.size and (int(z.min()) < -(1 << 31) or int(z.max()) >= (1 << 31)):
+        raise ValueError("a quantised range does not fit int32")
+    return np.ascontiguousarray(z, dtype=np.int32).reshape(-1)
+
+
+def worldmap_integrate_check(resolution, n_beams, range_max, flags=0, zq=None):
+    """Rule 52's refusals (host only) in their order: counts, range_max, flags, zq -> (Rc, ZMAX); raises ValueError /
+    IndexError."""
+    z = None if zq is None else _zq(zq)
+    rc, zmax = C.c_int32(), C.c_int64()
+    _check(lib().kc_worldmap_integrate_check(float(np.float32(resolution)), int(n_beams), float(np.float32(range_max)), int(flags),
+                                             None if z is None else z.ctypes.data, C.byref(rc), C.byref(zmax)))
+    return rc.value, zmax.value
+
+
+def worldmap_quantise_ranges(ranges, resolution, range_max, range_min=0.0):
+    """Rule 52 (host only): measured ranges in metres -> int32 [B]: -1 for a NaN, a negative range or one below range_min,
+    ZMAX for +inf or a range >= range_max, else llrint(z / resolution * 65536)."""
+    r = _f64(ranges).reshape(-1)
+    out = np.zeros(len(r), np.int32)
+    _check(lib().kc_worldmap_quantise_ranges(float(np.float32(resolution)), _pd(r), len(r), float(np.float32(range_max)),
+                                             float(np.float32(range_min)), out.ctypes.data_as(_ip)))
+    return out
+
+
 def worldmap_match_check_window(n_yaw, yaw_step, reach):
     """Rule 10's ranges of a match's window (host only); raises ValueError."""
     _check(lib().kc_worldmap_match_check_window(int(n_yaw), float(yaw_step), int(reach)))
@@ -1775,6 +1816,42 @@ class WorldMapContext(_Owner, _StreamOrdered):
                                       c.ctypes.data_as(_ip) if return_cells else None))
         n = len(plist) * len(a)
         return (r[:n].reshape(shape), c[:n].reshape(shape)) if return_cells else r[:n].reshape(shape)
+
+    def integrate(self, pose, angles, zq, range_max, flags=0):
+        """Rules 52 to 57: one measured scan into the map by an inverse ray cast.  pose: (x, y, yaw) of the scan frame or a
+        WorldMapPose; angles: the beams in that frame; zq: int32 a beam as worldmap_quantise_ranges gives them; flags:
+        INTEGRATE_CLEAR_NO_RETURN or 0.  -> (changed, (i_min, j_min, i_max, j_max)) as update."""
+        p, r, a, z = self._pose(pose), WorldMapResult(), _f64(angles).reshape(-1), _zq(zq)
+        if len(z) != len(a):
+            raise ValueError("one quantised range a beam")
+        _check(lib().kc_worldmap_integrate(self.h, C.byref(p), _pd(a), len(a), z.ctypes.data_as(_ip), float(np.float32(range_max)),
+                                           int(flags), C.byref(r)))
+        return r.as_tuple()
+
+    def integrate_marks(self, pose, angles, zq, range_max, flags=0):
+        """The mark launch of `integrate` alone -> uint8 [width, height], INTEGRATE_MISS | INTEGRATE_HIT a cell; the map is
+        untouched and the mark plane zero again afterwards."""
+        p, a, z = self._pose(pose), _f64(angles).reshape(-1), _zq(zq)
+        if len(z) != len(a):
+            raise ValueError("one quantised range a beam")
+        w, h = self.shape
+        out = np.zeros((w, h), np.uint8, order="F")
+        _check(lib().kc_worldmap_integrate_marks(self.h, C.byref(p), _pd(a), len(a), z.ctypes.data_as(_ip),
+                                                 float(np.float32(range_max)), int(flags), out.ctypes.data, out.size))
+        return out
+
+    def integrate_set_precheck(self, enable=True):
+        """Measurement only: the mark kernel's byte load in front of its atomic."""
+        _check(lib().kc_worldmap_integrate_set_precheck(self.h, int(bool(enable))))
+
+    def integrate_set_timing(self, enable=True):
+        _check(lib().kc_worldmap_integrate_set_timing(self.h, int(bool(enable))))
+
+    def integrate_times(self):
+        """(mark, apply) launches of the last integrate in milliseconds, by HIP events."""
+        ms = (C.c_float * 2)()
+        _check(lib().kc_worldmap_integrate_times(self.h, ms))
+        return tuple(float(v) for v in ms)
 
     def grid_device_ptr(self) -> int:
         """The cls plane on the device: int8, (width, height), what PlannerContext.set_grid_device(ptr, width, height,

@@ -75,7 +75,17 @@ with
 and one line a reach (6 and 16) with the first distance read after a shift (kc_worldmap_distance_device: the full
 refresh rule 48 asks for, and the wait).  The planes after (a) are compared with the statement (tests/worldmap_shift_ref.py)
 once.
-  python tools/worldmap_time.py --shift [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --shift [--reps 30] [--warmup 3]
+
+--integrate times the scan integration (rules 52 to 57): an empty 2004 x 1204 world, the scan frame near the middle,
+range_max 10 m (Rc = 200), 360, 1440 and 4096 beams of a room scan with KC_INTEGRATE_CLEAR_NO_RETURN.  One JSON line a beam
+count with
+  (a) kc_worldmap_integrate by the host's clock (two launches and the 20-byte read-back) and its mark and apply launches by
+      HIP events, with the mark kernel's byte load in front of its atomic off (the default), on, and off again;
+  (b) the route that exists without it, for the same scan: the mapper's scan to its 400 x 400 grid on the device followed
+      by kc_worldmap_update_from_mapper, together and each on its own.
+At 360 beams the marks, the planes and the record are compared with the statement (tests/worldmap_integrate_ref.py) once.
+  python tools/worldmap_time.py --integrate [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -498,6 +508,59 @@ def shift_leg(args):
                               "refreshed_box": list(wm.distance_info()[2])}), flush=True)
 
 
+def integrate_leg(args):
+    import worldmap_integrate_ref as iref
+
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r + 0.013, ORIGIN[1] + (H // 2) * r - 0.021)
+    pose = centre + (0.3,)
+    range_max = 10.0
+    for n in (360, 1440, 4096):
+        ang, rng = syn.dense_scan(n, 1.2)                     # a room: ranges 3.6 .. 8.4 m
+        ang, rng = np.asarray(ang, dtype=np.float64), np.asarray(rng, dtype=np.float64)
+        zq = kh.worldmap_quantise_ranges(rng, RES, range_max)
+        with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, n) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as wm, \
+                kh.WorldMapContext(W, H, RES, ORIGIN) as wm_route:
+            line = {"world": [W, H], "beams": n, "range_max": range_max, "radius_cells": kh.worldmap_integrate_check(RES, n, range_max)[0],
+                    "reps": args.reps, "warmup": args.warmup}
+            if n == 360:                                      # the device against the statement, once
+                want = iref.IntegrateRef(W, H, RES, ORIGIN)
+                t0 = time.perf_counter()
+                marks, changed, box = want.integrate(pose, ang, zq, range_max, kh.INTEGRATE_CLEAR_NO_RETURN)
+                line["python_statement_one_thread_ms_once"] = round((time.perf_counter() - t0) * 1e3, 1)
+                assert np.array_equal(wm.integrate_marks(pose, ang, zq, range_max, kh.INTEGRATE_CLEAR_NO_RETURN), marks), "marks differ"
+                assert wm.integrate(pose, ang, zq, range_max, kh.INTEGRATE_CLEAR_NO_RETURN) == (changed, box), "records differ"
+                cls, ev = wm.planes()
+                assert np.array_equal(cls, want.cls) and np.array_equal(ev, want.evidence), "planes differ"
+                line["changed_first_scan"], line["box_first_scan"] = changed, list(box)
+
+            def call():
+                wm.integrate(pose, ang, zq, range_max, kh.INTEGRATE_CLEAR_NO_RETURN)
+
+            for name, on in (("precheck_off", False), ("precheck_on", True), ("precheck_off_again", False)):   # off is the default
+                wm.integrate_set_precheck(on)
+                line[f"integrate_call_{name}_ms"] = timed(call, args.reps, args.warmup)
+                wm.integrate_set_timing(True)
+                parts = []
+                for k in range(args.warmup + args.reps):
+                    call()
+                    if k >= args.warmup:
+                        parts.append(wm.integrate_times())
+                wm.integrate_set_timing(False)
+                line[f"launch_mark_{name}_ms"] = spread([p[0] for p in parts])
+                line[f"launch_apply_{name}_ms"] = spread([p[1] for p in parts])
+
+            def route():                                      # today's route for the same scan: rasterise twice
+                mapper.scan_to_grid_device(ang, rng)
+                wm_route.update_from_mapper(mapper, pose)
+
+            line["route_mapper_scan_plus_update_from_mapper_ms"] = timed(route, args.reps, args.warmup)
+            line["route_mapper_scan_alone_ms"] = timed(lambda: (mapper.scan_to_grid_device(ang, rng), mapper.sync()), args.reps, args.warmup)
+            line["route_update_from_mapper_alone_ms"] = timed(lambda: wm_route.update_from_mapper(mapper, pose), args.reps, args.warmup)
+            line["integrate_over_route"] = round(line["integrate_call_precheck_off_ms"][0] / line["route_mapper_scan_plus_update_from_mapper_ms"][0], 3)
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -509,9 +572,12 @@ def main():
     ap.add_argument("--mcl", action="store_true", help="time the Monte-Carlo localiser instead")
     ap.add_argument("--field", action="store_true", help="time the distance plane and the likelihood-field model instead")
     ap.add_argument("--shift", action="store_true", help="time the rolling window's shift and the route it replaces instead")
+    ap.add_argument("--integrate", action="store_true", help="time the scan integration and today's route for the same scan instead")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
+    if args.integrate:
+        return integrate_leg(args)
     if args.match:
         return match_leg(args)
     if args.points:
