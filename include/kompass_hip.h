@@ -1652,6 +1652,78 @@ int kc_worldmap_integrate_set_precheck(kc_worldmap *ctx, int enable);
 int kc_worldmap_integrate_set_timing(kc_worldmap *ctx, int enable);
 int kc_worldmap_integrate_times(kc_worldmap *ctx, float ms_out[2]);
 
+/* ------------------------------------------------------------------------ */
+/* The localiser's fit record and its recovery by injected particles (DESIGN.md 4.11 rules 59 to 63) */
+/* ------------------------------------------------------------------------ */
+/* The recovery is off unless a caller asks for it: kc_mcl_step, kc_mcl_resample, kc_mcl_record
+ * and the particles are what they were; the fit is formed at every step, beside the record.
+ * Integers throughout, bit-equal to tests/worldmap_mcl_recovery_ref.py.
+ * Rule 59, fit: with cost_p the penalty sum of particle p in this step alone (rule 34, or rules
+ * 44 and 45), cost_sum = sum_p cost_p (uint64: N B <= 2^22 times a uint16 penalty passes 32
+ * bits), cost_min = min_p cost_p, cost_best = cost_p of rule 35's best particle.  Unlike acc,
+ * amin and the weights, which are relative to the particle set, these are absolute.  Formed by
+ * the step's second launch from the costs it already reads, exact sums, no thread order; written
+ * next to the record and read back with it in one copy.
+ * Rule 60, the step's fit m: B_used is the number of beams that contributed, those with zq_k !=
+ * -1 under the beam model (rule 33) and those with 0 <= zq_k < ZMAX under the field model (rule
+ * 45); m = floor(cost_sum * 256 / (N * B_used)), the mean penalty a beam in 1 / 256, at most
+ * 65535 * 256; a step with B_used = 0 says nothing.
+ * Rule 61, two averages (Thrun's augmented MCL, in integers): a state (slow, fast, primed).
+ * B_used = 0 leaves it as it is, n_inject = 0.  Not primed: slow = fast = m, primed, n_inject =
+ * 0.  Primed: slow += (m - slow) >> a_slow, fast += (m - fast) >> a_fast, arithmetic shifts on
+ * int64 (both stay within 0 .. 65535 * 256); n_inject = 0 when fast <= slow, else min(floor(N *
+ * max_num / max_den), floor(N * (fast - slow) / fast)).  a_slow = 4, a_fast = 1 and max = 1 / 4
+ * are the front ends' defaults: judgement, not measurement.  No threshold on m for "lost" is
+ * given: a good one depends on the tables and the map, and none has been measured.
+ * Rule 62, injecting resample with n of N slots injected: slot j is injected iff floor((j + 1)
+ * n / N) > floor(j n / N): exactly n slots, spread evenly (the i-th is ceil((i + 1) N / n) - 1),
+ * because rule 40 orders the slots by source index and a tail would drop the high indices.
+ * Every other slot takes rule 40's state, u0 and the prefix sums over all N slots as there.  An
+ * injected slot takes a free cell as rule 41's global draw does, with the current step counter
+ * and channels 16 and 17: cell number draw(seed, step, j, 16) mod n_free in the order of I + J *
+ * width over the KC_EMPTY cells of the class plane as it is at the resample (behind the map's
+ * stream by the event, and behind rule 50's pending shift); with v = draw(seed, step, j, 17) the
+ * sub-cell offsets and the heading come from v as in rule 41; acc = 0 as for every slot.  With
+ * no free cell the injected slots keep rule 40's state, which is not an error.  n = 0 is
+ * kc_mcl_resample.
+ * Rule 63 (the host classes'): after every step m and rule 61 run, whether or not recovery is
+ * on; with it on, the step ends with an injecting resample when rule 40 asks for a resample or
+ * n_inject > 0; either init un-primes the averages. */
+typedef struct kc_mcl_fit { /* rule 59 */
+  uint64_t cost_sum;
+  uint32_t cost_min, cost_best;
+  uint32_t step; /* the step counter of the step that formed it, as the record's */
+} kc_mcl_fit;
+typedef struct kc_mcl_recovery { /* rule 61's state */
+  int64_t slow, fast;
+  int32_t primed;
+} kc_mcl_recovery;
+/* the last step's fit, from the host copy the step's read-back filled: no device work.
+ * KC_ERR_STATE before the first step and after an init, kc_mcl_set_model or
+ * kc_mcl_set_field_model; a resample leaves it. */
+int kc_mcl_last_fit(kc_mcl *ctx, kc_mcl_fit *out);
+/* Rules 60 and 61 (host only, needs no device).  *state is read and, unless the call is refused,
+ * written; *m_out (may be NULL): m, or -1 when B_used = 0 or on a refusal; *n_inject_out: rule
+ * 61's, 0 on a refusal.  Refusals, in this order: null arguments; KC_ERR_INVALID for a_slow, then
+ * a_fast, outside 0 .. 30, for max_den == 0, for max_num > max_den; KC_ERR_RANGE for n_particles
+ * outside 1 .. 65536, for beams_used above 1024, for cost_sum above n_particles * beams_used *
+ * 65535 (no step forms one), and for a primed state with an average outside 0 .. 65535 * 256. */
+int kc_mcl_recovery_update(uint64_t cost_sum, size_t n_particles, size_t beams_used, int a_slow, int a_fast, uint32_t max_num,
+                           uint32_t max_den, kc_mcl_recovery *state, int64_t *m_out, size_t *n_inject_out);
+/* Rule 62.  n_inject == 0 is kc_mcl_resample itself.  Otherwise five launches, no read-back:
+ * the row counts and a one-workgroup exclusive prefix over the rows (the free-cell index, built
+ * anew at every injecting resample, n_free read on the device), rule 40's prefix sum and select
+ * over all N slots, then a wavefront an injected slot that overwrites it.  With n_inject > 0 the
+ * call returns once its stream is idle: two of its kernels read the map's class plane, the map's
+ * writers wait for no reader, and so the map may be written as soon as the call is back (the
+ * plain resample reads no plane and returns without a wait, as before).  Checks: null context;
+ * KC_ERR_RANGE for n_inject above N; then kc_mcl_resample's KC_ERR_STATE. */
+int kc_mcl_resample_inject(kc_mcl *ctx, size_t n_inject);
+/* HIP-event times in milliseconds of the last injecting resample's three own launches (row
+ * counts, row prefix, inject), recorded while kc_mcl_set_timing is on; its prefix and select are
+ * kc_mcl_times' last two.  KC_ERR_STATE when none was timed. */
+int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
+
 #ifdef __cplusplus
 }
 #endif

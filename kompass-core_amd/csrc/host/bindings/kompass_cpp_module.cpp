@@ -1201,6 +1201,13 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def_readonly("best_cost", &MCL::Estimate::best_cost)
         .def_readonly("txe", &MCL::Estimate::txe)
         .def_readonly("tye", &MCL::Estimate::tye)
+        .def_readonly("fit", &MCL::Estimate::fit, "the step's mean penalty a contributing beam in 1 / 256 (rule 60), -1 without one")
+        .def_readonly("fit_slow", &MCL::Estimate::fit_slow)
+        .def_readonly("fit_fast", &MCL::Estimate::fit_fast)
+        .def_readonly("injected", &MCL::Estimate::injected, "the slots the step's resample drew anew over the free cells")
+        .def_readonly("cost_min", &MCL::Estimate::cost_min)
+        .def_readonly("cost_best", &MCL::Estimate::cost_best)
+        .def_readonly("beams_used", &MCL::Estimate::beams_used)
         .def_property_readonly("record", [wideInt](const MCL::Estimate &e) {
                const kc_mcl_record &r = e.record;
                return py::make_tuple(r.w1, r.w2, wideInt(r.sx_lo, r.sx_hi), wideInt(r.sy_lo, r.sy_hi), r.sc, r.ss, r.amin, r.best,
@@ -1281,6 +1288,17 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def("set_resample_ratio", &MCL::setResampleRatio, py::arg("num"), py::arg("den"))
         .def("set_flags", &MCL::setFlags, py::arg("unknown_blocks") = false, py::arg("skip_no_return") = false)
         .def("set_spread", &MCL::setSpread, py::arg("on"))
+        .def("set_recovery", [](MCL &m, int a_slow, int a_fast, uint32_t max_num, uint32_t max_den) {
+               MCL::Recovery r;
+               r.a_slow = a_slow;
+               r.a_fast = a_fast;
+               r.max_num = max_num;
+               r.max_den = max_den;
+               m.setRecovery(r);
+             }, py::arg("a_slow") = 4, py::arg("a_fast") = 1, py::arg("max_num") = 1u, py::arg("max_den") = 4u,
+             "Recovery by injected free-cell particles (rules 61 to 63); the defaults are judgement, not measurement")
+        .def("clear_recovery", &MCL::clearRecovery)
+        .def_property_readonly("recovery", &MCL::recovery)
         .def("init", &MCL::init, py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("sigma_xy"), py::arg("sigma_yaw"))
         .def("init_global", &MCL::initGlobal, "Seed the particles uniformly over the map's empty cells -> their count")
         .def("step", [](MCL &m, const std::array<double, 3> &from, const std::array<double, 3> &to, const std::vector<double> &ranges) {

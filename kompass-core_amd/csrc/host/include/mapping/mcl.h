@@ -65,6 +65,19 @@ class MCL {
     uint32_t best_cost = 0;              // amin
     int64_t txe = 0, tye = 0;            // the estimate's position in 2^-16 cells
     kc_mcl_record record = {};
+    // rules 59 to 61, always filled.  fit: the step's mean penalty a contributing beam in 1 / 256, -1 when no beam
+    // contributed; unlike n_eff, spread and best_cost it is absolute: a filter that is confidently wrong shows here.
+    // fit_slow, fit_fast: its two running averages (0 until a step has primed them); injected: the slots the step's
+    // resample drew anew over the free cells, 0 with recovery off.
+    int64_t fit = -1, fit_slow = 0, fit_fast = 0;
+    size_t injected = 0;
+    uint32_t cost_min = 0, cost_best = 0;  // the smallest step cost, and the best particle's
+    size_t beams_used = 0;                 // rule 60's B_used
+  };
+  // Rule 61's parameters.  Judgement, not measurement: nobody has tuned them on a robot.
+  struct Recovery {
+    int a_slow = 4, a_fast = 1;
+    uint32_t max_num = 1, max_den = 4;  // at most this share of the particles is injected in one step
   };
   struct Particles {
     std::vector<int64_t> tx, ty;
@@ -87,6 +100,13 @@ class MCL {
   // resample when n_eff < N num / den (default 1 / 2); num = 0: never
   void setResampleRatio(uint32_t num, uint32_t den);
   void setFlags(bool unknown_blocks, bool skip_no_return);
+  // Recovery by injected particles (rules 61 to 63), off by default.  On: a step whose fast average of the fit lies above
+  // the slow one ends with a resample that draws some slots anew over the map's free cells.  The parameters are checked
+  // as kc_mcl_recovery_update checks them; the averages keep running across either call.  Such a resample reads the map
+  // on the device and the step waits for it (kc_mcl_resample_inject): the map may be written once step() is back.
+  void setRecovery(const Recovery &r);
+  void clearRecovery() { recovery_on_ = false; }
+  bool recovery() const { return recovery_on_; }
   // whether step() reads the particles back for Estimate::spread (default: yes; one copy of N states a step)
   void setSpread(bool on) { spread_ = on; }
 
@@ -129,6 +149,9 @@ class MCL {
   unsigned flags_ = 0;
   bool spread_ = true;
   bool field_ = false;
+  bool recovery_on_ = false;
+  Recovery recovery_;
+  kc_mcl_recovery fit_state_ = {};  // un-primed by either init
 
   double spreadOf(const Estimate &e) const;
 };

@@ -172,16 +172,27 @@ void MCL::setFlags(bool unknown_blocks, bool skip_no_return) {
   flags_ = (unknown_blocks ? KC_SCAN_UNKNOWN_BLOCKS : 0u) | (skip_no_return ? KC_MCL_SKIP_NO_RETURN : 0u);
 }
 
+void MCL::setRecovery(const Recovery &r) {
+  // the library's own refusals, on a state and a step that are fine
+  kc_mcl_recovery probe{};
+  size_t n = 0;
+  hip::check(kc_mcl_recovery_update(0, 1, 0, r.a_slow, r.a_fast, r.max_num, r.max_den, &probe, nullptr, &n));
+  recovery_ = r;
+  recovery_on_ = true;
+}
+
 void MCL::init(double x, double y, double yaw, double sigma_xy, double sigma_yaw) {
   const kc_worldmap_pose p = WorldMap::quantisePose(map_.resolution(), map_.originX(), map_.originY(), x, y, 0.0);
   hip::check(kc_mcl_init_pose(ctx_.get(), p.tx, p.ty, quantiseHeading(yaw),
                               noiseScale(sigma_xy * 65536.0 / static_cast<double>(map_.resolution())),
                               noiseScale(sigma_yaw / kTwoPi * 65536.0)));
+  fit_state_ = {};
 }
 
 size_t MCL::initGlobal() {
   size_t n_free = 0;
   hip::check(kc_mcl_init_global(ctx_.get(), &n_free));
+  fit_state_ = {};
   return n_free;
 }
 
@@ -201,8 +212,21 @@ MCL::Estimate MCL::stepQuantised(int64_t d_f, int64_t d_l, int32_t d_h, int32_t 
   hip::check(kc_mcl_step(ctx_.get(), d_f, d_l, d_h, s_f, s_l, s_h, zq.data(), flags, &r));
   Estimate e = estimateOf(r, map_.resolution(), map_.originX(), map_.originY());
   if (spread_) e.spread = spreadOf(e);
-  if (resample_allowed && shouldResample(r, n_, r_num_, r_den_)) {
-    resample();
+  // rules 59 to 61: the averages run whether or not recovery is on
+  kc_mcl_fit fit{};
+  hip::check(kc_mcl_last_fit(ctx_.get(), &fit));
+  e.cost_min = fit.cost_min;
+  e.cost_best = fit.cost_best;
+  for (const int32_t z : zq) e.beams_used += field_ ? (z >= 0 && z < zmax_) : (z != -1);
+  size_t n_inject = 0;
+  hip::check(kc_mcl_recovery_update(fit.cost_sum, n_, e.beams_used, recovery_.a_slow, recovery_.a_fast, recovery_.max_num,
+                                    recovery_.max_den, &fit_state_, &e.fit, &n_inject));
+  e.fit_slow = fit_state_.slow;
+  e.fit_fast = fit_state_.fast;
+  if (!recovery_on_ || !resample_allowed) n_inject = 0;
+  if (resample_allowed && (n_inject > 0 || shouldResample(r, n_, r_num_, r_den_))) {  // rule 63
+    hip::check(kc_mcl_resample_inject(ctx_.get(), n_inject));
+    e.injected = n_inject;
     e.resampled = true;
   }
   return e;

@@ -1,4 +1,4 @@
-// Monte-Carlo localisation over the world map (kc_mcl_*; DESIGN.md 4.11 rules 28 to 41, 44 and 45).
+// Monte-Carlo localisation over the world map (kc_mcl_*; DESIGN.md 4.11 rules 28 to 41, 44 and 45, 59 to 62).
 //
 // Nothing in the reference to restate: it leaves localisation, like the world map, to its ROS side.  N particles
 // (TX, TY, h, acc) live on the device; a step advances them by an odometry increment with counter-based integer noise,
@@ -20,7 +20,11 @@
 //  (b) mcl_weigh_kernel: one workgroup of 1024.  Pass 1 forms acc and the packed minimum (acc << 32 | p: the lowest
 //      index among equals), pass 2 the weights and the record's sums.  w (x - x_best) can reach 2^57 and 65536 of them
 //      2^73: each product is split into its low 32 bits and the rest, both summed in 64 bits and joined once at the end.
-//      It leaves cost at 0 for the next step and amin in the state word rule 35 calls min_prev.
+//      It leaves cost at 0 for the next step and amin in the state word rule 35 calls min_prev.  Pass 1 also reduces
+//      rule 59's fit from the costs it reads anyway (their sum, their minimum, the best particle's), in the exchange of
+//      the packed minimum; the fit is written behind the record and read back with it.  Each pass has ONE exchange
+//      through LDS (three values, then the eight sums) and thread 0 alone adds the partials up: with every thread
+//      adding all of them up eight times the kernel spilled registers to scratch.
 //  (c) mcl_prefix_kernel: one workgroup; a lane sums a contiguous chunk, the 1024 partials are scanned in LDS.
 //  (d) mcl_select_kernel: a lane a slot, a binary search over the prefix; reads the current state buffer and writes the
 //      other one.
@@ -29,6 +33,10 @@
 //  (f) mcl_shift_kernel (rule 50): the map's window moved by whole cells since the particles were last touched; a lane a
 //      particle takes the difference out of (TX, TY) in place, clamped as every state is.  Applied lazily by the entries
 //      that read or write particles.
+//  (g) injecting resample (rule 62): (e)'s row counts, mcl_row_prefix_kernel (one workgroup, the exclusive prefix over the
+//      rows, chunked as (c) is), then (c) and (d) over all N slots, then mcl_inject_kernel: a wavefront an injected slot
+//      reads n_free on the device and overwrites the slot by (e)'s search and ballot walk.  No read-back, but the call
+//      waits for the stream: its kernels read the map's plane, which the map's next writer must not find half read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -212,39 +220,72 @@ __global__ __launch_bounds__(kMclBlock) void mcl_field_kernel(MclFieldArgs a) {
   mcl_segment_add(a.cost, p, c, live);
 }
 
-// ---- sums over one workgroup of kMclOne: wavefront shuffles, then the 16 partials through LDS ----
-__device__ __forceinline__ long long mcl_block_sum(long long v, long long *s16) {
+// ---- reductions over one workgroup of kMclOne: wavefront shuffles, then the 16 partials through LDS ----
+// The eight sums of pass 2 in one exchange; thread 0 alone needs the totals and alone reads the partials.
+__device__ __forceinline__ void mcl_block_sum8(long long (&v)[8], long long (*s)[kMclOne / 64]) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  __syncthreads();  // s16 may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long t = 0;
+  for (int i = 0; i < 8; ++i) {
 #pragma unroll
-  for (int i = 0; i < kMclOne / 64; ++i) t += s16[i];
-  return t;
-}
-__device__ __forceinline__ unsigned long long mcl_block_min(unsigned long long v, unsigned long long *s16) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_down(v, off);
-    v = o < v ? o : v;
+    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_down(v[i], off);
+    if ((threadIdx.x & 63) == 0) s[i][threadIdx.x >> 6] = v[i];
   }
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) s16[threadIdx.x >> 6] = v;
-  __syncthreads();
-  unsigned long long t = s16[0];
+  if (threadIdx.x != 0) return;
 #pragma unroll
-  for (int i = 1; i < kMclOne / 64; ++i) t = s16[i] < t ? s16[i] : t;
+  for (int i = 0; i < 8; ++i) {
+    long long t = 0;
+#pragma unroll
+    for (int w = 0; w < kMclOne / 64; ++w) t += s[i][w];
+    v[i] = t;
+  }
+}
+// What pass 1 of the weigh kernel reduces, in one exchange: rule 35's packed minimum, which every thread needs, and rule
+// 59's sum and minimum, which thread 0 alone needs and alone reads.
+struct MclPass1 {
+  unsigned long long key, cost_sum;
+  unsigned cost_min;
+};
+__device__ __forceinline__ MclPass1 mcl_block_pass1(MclPass1 v, unsigned long long *s_key, unsigned long long *s_sum,
+                                                    unsigned *s_min) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long k = __shfl_down(v.key, off);
+    const unsigned m = __shfl_down(v.cost_min, off);
+    v.key = k < v.key ? k : v.key;
+    v.cost_sum += __shfl_down(v.cost_sum, off);
+    v.cost_min = m < v.cost_min ? m : v.cost_min;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_key[threadIdx.x >> 6] = v.key;
+    s_sum[threadIdx.x >> 6] = v.cost_sum;
+    s_min[threadIdx.x >> 6] = v.cost_min;
+  }
+  __syncthreads();
+  MclPass1 t{s_key[0], 0ull, 0xFFFFFFFFu};
+#pragma unroll
+  for (int i = 1; i < kMclOne / 64; ++i) t.key = s_key[i] < t.key ? s_key[i] : t.key;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < kMclOne / 64; ++i) {
+      t.cost_sum += s_sum[i];
+      t.cost_min = s_min[i] < t.cost_min ? s_min[i] : t.cost_min;
+    }
+  }
   return t;
 }
+
+// the record and, next to it, the fit: one read-back
+struct MclOut {
+  kc_mcl_record rec;
+  kc_mcl_fit fit;
+};
 
 struct MclWeighArgs {
   MclState st;
   unsigned *acc, *cost, *w, *min_prev;
   const unsigned *wtab;
   const int2 *heading;
-  kc_mcl_record *rec;
+  MclOut *out;
   int N, EW, w_shift;
   unsigned step;
 };
@@ -257,18 +298,36 @@ __device__ __forceinline__ void mcl_join(long long high, long long low, unsigned
 }
 
 __global__ __launch_bounds__(kMclOne) void mcl_weigh_kernel(MclWeighArgs a) {
-  __shared__ long long s16[kMclOne / 64];
+  __shared__ long long s_sums[8][kMclOne / 64];
+  __shared__ unsigned long long s_key[kMclOne / 64], s_sum[kMclOne / 64];
+  __shared__ unsigned s_min[kMclOne / 64];
   const unsigned min_prev = *a.min_prev;
-  unsigned long long key = ~0ull;
-  for (int p = threadIdx.x; p < a.N; p += kMclOne) {  // rule 35
-    const unsigned long long sum = static_cast<unsigned long long>(a.acc[p] - min_prev) + a.cost[p];
+  MclPass1 mine{~0ull, 0ull, 0xFFFFFFFFu};
+  unsigned cost_of_key = 0u;  // the step cost of this thread's own best, for rule 59's cost_best
+  for (int p = threadIdx.x; p < a.N; p += kMclOne) {  // rules 35 and 59
+    const unsigned cost = a.cost[p];
+    const unsigned long long sum = static_cast<unsigned long long>(a.acc[p] - min_prev) + cost;
     const unsigned v = sum < kMclAccCap ? static_cast<unsigned>(sum) : kMclAccCap;
     a.acc[p] = v;
     a.cost[p] = 0u;
-    const unsigned long long mine = (static_cast<unsigned long long>(v) << 32) | static_cast<unsigned>(p);
-    key = mine < key ? mine : key;
+    const unsigned long long k = (static_cast<unsigned long long>(v) << 32) | static_cast<unsigned>(p);
+    if (k < mine.key) {
+      mine.key = k;
+      cost_of_key = cost;
+    }
+    mine.cost_sum += cost;
+    mine.cost_min = cost < mine.cost_min ? cost : mine.cost_min;
   }
-  key = mcl_block_min(key, reinterpret_cast<unsigned long long *>(s16));
+  const MclPass1 all = mcl_block_pass1(mine, s_key, s_sum, s_min);
+  const unsigned long long key = all.key;
+  // rule 59, written here so that nothing of it stays live across pass 2.  Keys are distinct (p is part of them): one
+  // thread holds the winner, and with it the best particle's cost
+  if (mine.key == key) a.out->fit.cost_best = cost_of_key;
+  if (threadIdx.x == 0) {
+    a.out->fit.cost_sum = all.cost_sum;
+    a.out->fit.cost_min = all.cost_min;
+    a.out->fit.step = a.step;
+  }
   const unsigned amin = static_cast<unsigned>(key >> 32), best = static_cast<unsigned>(key & 0xFFFFFFFFull);
   const long long bx = a.st.tx[best], by = a.st.ty[best];
   long long w1 = 0, w2 = 0, sc = 0, ss = 0, sxh = 0, sxl = 0, syh = 0, syl = 0;
@@ -287,35 +346,29 @@ __global__ __launch_bounds__(kMclOne) void mcl_weigh_kernel(MclWeighArgs a) {
     syh += ty >> 32;
     syl += ty & 0xFFFFFFFFll;
   }
-  w1 = mcl_block_sum(w1, s16);
-  w2 = mcl_block_sum(w2, s16);
-  sc = mcl_block_sum(sc, s16);
-  ss = mcl_block_sum(ss, s16);
-  sxh = mcl_block_sum(sxh, s16);
-  sxl = mcl_block_sum(sxl, s16);
-  syh = mcl_block_sum(syh, s16);
-  syl = mcl_block_sum(syl, s16);
+  long long sums[8] = {w1, w2, sc, ss, sxh, sxl, syh, syl};
+  mcl_block_sum8(sums, s_sums);
   if (threadIdx.x == 0) {
     kc_mcl_record r;
-    r.w1 = static_cast<uint64_t>(w1);
-    r.w2 = static_cast<uint64_t>(w2);
+    r.w1 = static_cast<uint64_t>(sums[0]);
+    r.w2 = static_cast<uint64_t>(sums[1]);
     unsigned long long lo;
     long long hi;
-    mcl_join(sxh, sxl, &lo, &hi);
+    mcl_join(sums[4], sums[5], &lo, &hi);
     r.sx_lo = lo;
     r.sx_hi = hi;
-    mcl_join(syh, syl, &lo, &hi);
+    mcl_join(sums[6], sums[7], &lo, &hi);
     r.sy_lo = lo;
     r.sy_hi = hi;
-    r.sc = sc;
-    r.ss = ss;
+    r.sc = sums[2];
+    r.ss = sums[3];
     r.best_tx = bx;
     r.best_ty = by;
     r.best_h = a.st.h[best];
     r.amin = amin;
     r.best = best;
     r.step = a.step;
-    *a.rec = r;
+    a.out->rec = r;
     *a.min_prev = amin;
   }
 }
@@ -391,6 +444,43 @@ __global__ __launch_bounds__(kMclBlock) void mcl_row_count_kernel(const int8_t *
   if (threadIdx.x == 0) rows[blockIdx.x] = s[0];
 }
 
+// For rule 62, mcl_init_global_kernel's search as a function (the init below keeps its own text: calling this one from
+// both measured about a tenth slower there at 65536 particles).
+// Rule 41's free cell number `rest` (< before[H]) found by a whole wavefront: a binary search for the row, a ballot walk
+// along it.  True on the one lane that stands on the cell, with (I, J); before[J]: the free cells of the rows below J.
+__device__ __forceinline__ bool mcl_free_cell(const int8_t *cls, int W, int H, const unsigned long long *before,
+                                              unsigned long long rest, int *I, int *J) {
+  const int lane = threadIdx.x & 63;
+  int lo = 0, hi = H - 1;  // the last row with before[J] <= rest
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (before[mid] <= rest) lo = mid;
+    else hi = mid - 1;
+  }
+  rest -= before[lo];
+  const int8_t *row = cls + static_cast<size_t>(lo) * static_cast<size_t>(W);
+  for (int i0 = 0; i0 < W; i0 += 64) {
+    const int i = i0 + lane;
+    const bool free_cell = i < W && row[i] == KC_EMPTY;
+    const unsigned long long m = __ballot(free_cell);
+    const unsigned long long n = static_cast<unsigned long long>(__popcll(m));
+    if (rest < n) {
+      *I = i;
+      *J = lo;
+      return free_cell && static_cast<unsigned long long>(__popcll(m & ((1ull << lane) - 1ull))) == rest;
+    }
+    rest -= n;
+  }
+  return false;
+}
+
+// rule 41's state in cell (I, J) from the draw v
+__device__ __forceinline__ void mcl_seed_in_cell(MclState out, int p, int I, int J, unsigned long long v) {
+  out.tx[p] = (static_cast<long long>(I) << 16) + static_cast<long long>(v & 0xFFFF) - (1ll << 15);
+  out.ty[p] = (static_cast<long long>(J) << 16) + static_cast<long long>((v >> 16) & 0xFFFF) - (1ll << 15);
+  out.h[p] = static_cast<unsigned>((v >> 32) & 0xFFFF);
+}
+
 // a wavefront a particle.  before[J]: the free cells of the rows below J, before[H] = n_free
 __global__ __launch_bounds__(kMclBlock) void mcl_init_global_kernel(const int8_t *cls, int W, int H, const unsigned long long *before,
                                                                     MclState out, unsigned *acc, unsigned *cost, unsigned *min_prev,
@@ -428,6 +518,44 @@ __global__ __launch_bounds__(kMclBlock) void mcl_init_global_kernel(const int8_t
   }
 }
 
+// rule 62's index: before[J] = the free cells of the rows below J, before[H] = n_free; one workgroup, a lane a
+// contiguous chunk of rows as mcl_prefix_kernel has it (H can exceed kMclOne)
+__global__ __launch_bounds__(kMclOne) void mcl_row_prefix_kernel(const unsigned *rows, unsigned long long *before, int H) {
+  __shared__ unsigned long long s[kMclOne];
+  const int chunk = (H + kMclOne - 1) / kMclOne;
+  const int lo = static_cast<int>(threadIdx.x) * chunk < H ? static_cast<int>(threadIdx.x) * chunk : H;
+  const int hi = lo + chunk < H ? lo + chunk : H;
+  unsigned long long mine = 0;
+  for (int i = lo; i < hi; ++i) mine += rows[i];
+  s[threadIdx.x] = mine;
+  __syncthreads();
+  for (int off = 1; off < kMclOne; off <<= 1) {
+    const unsigned long long add = static_cast<int>(threadIdx.x) >= off ? s[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s[threadIdx.x] += add;
+    __syncthreads();
+  }
+  unsigned long long run = s[threadIdx.x] - mine;  // the chunks before this one
+  for (int i = lo; i < hi; ++i) {
+    before[i] = run;
+    run += rows[i];
+  }
+  if (threadIdx.x == kMclOne - 1) before[H] = s[kMclOne - 1];
+}
+
+// rule 62: a wavefront an injected slot, over the buffer the select has filled.  Wavefront i stands for the i-th
+// injected slot, j = ceil((i + 1) N / n) - 1; with no free cell the slot keeps rule 40's state.
+__global__ __launch_bounds__(kMclBlock) void mcl_inject_kernel(const int8_t *cls, int W, int H, const unsigned long long *before,
+                                                               MclState out, unsigned long long key, int N, int n) {
+  const int i = static_cast<int>((blockIdx.x * kMclBlock + threadIdx.x) >> 6);
+  if (i >= n) return;  // the whole wavefront
+  const unsigned long long n_free = before[H];
+  if (n_free == 0) return;
+  const int j = static_cast<int>(((static_cast<long long>(i) + 1) * N + n - 1) / n) - 1;
+  int I = 0, J = 0;
+  if (mcl_free_cell(cls, W, H, before, mcl_draw(key, j, 16) % n_free, &I, &J)) mcl_seed_in_cell(out, j, I, J, mcl_draw(key, j, 17));
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -457,14 +585,14 @@ struct kc_mcl {
   unsigned pen_far = 0;
   DevBuf<int> d_zq;
   PinBuf<int> h_zq;
-  DevBuf<kc_mcl_record> d_rec;
-  PinBuf<kc_mcl_record> h_rec;
-  DevBuf<unsigned> d_rows;  // global init: scratch grown on demand and kept
+  DevBuf<MclOut> d_rec;  // the record and the fit, one read-back
+  PinBuf<MclOut> h_rec;
+  DevBuf<unsigned> d_rows;  // global init and rule 62: scratch grown on demand and kept
   DevBuf<unsigned long long> d_before;
-  bool inited = false, have_weights = false;
+  bool inited = false, have_weights = false, have_fit = false;
   unsigned long long w1 = 0;  // of the last step
   int OI = 0, OJ = 0;         // rule 50: the map offset the particles are expressed in
-  Timing step_time, resample_time;
+  Timing step_time, resample_time, inject_time;
 
   MclState state(int which) { return MclState{d_tx[which].p, d_ty[which].p, d_h[which].p}; }
 };
@@ -557,6 +685,7 @@ int mcl_take_tables(kc_mcl *c, int kind, const uint16_t *pen, size_t n_pen, int 
   c->w_shift = w_shift;
   c->kind = kind;
   c->have_weights = false;  // weights of another table
+  c->have_fit = false;      // and a fit in another table's penalties
   return KC_OK;
 }
 
@@ -586,6 +715,7 @@ void mcl_started(kc_mcl *c, int into, const WorldMapView &v) {
   c->step = 0;
   c->inited = true;
   c->have_weights = false;
+  c->have_fit = false;
 }
 
 }  // namespace
@@ -726,7 +856,7 @@ int kc_mcl_init_pose(kc_mcl *c, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s
   WorldMapView v{};
   KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
-  c->inited = false;
+  c->inited = c->have_fit = false;
   const int N = static_cast<int>(c->N);
   hipLaunchKernelGGL(mcl_init_pose_kernel, dim3(mcl_blocks(c->N)), dim3(kMclBlock), 0, c->stream, c->state(0), c->d_acc.p,
                      c->d_cost.p, c->d_min_prev.p, mcl_key(c, 0), static_cast<long long>(tx0), static_cast<long long>(ty0), h0, s_xy,
@@ -743,7 +873,7 @@ int kc_mcl_init_global(kc_mcl *c, size_t *n_free_out) {
   WorldMapView v{};
   KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
-  c->inited = false;
+  c->inited = c->have_fit = false;
   const size_t H = static_cast<size_t>(v.H);
   KC_TRY(c->d_rows.reserve(H));
   KC_TRY(c->d_before.reserve(H + 1));
@@ -815,6 +945,7 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
   // from here on the particles are the new buffer's, whatever fails: a failed step asks for a new init
   c->inited = false;
   c->have_weights = false;
+  c->have_fit = false;
   c->step_time.begin_cycle();
   KC_TRY(c->step_time.start("walk", c->stream));
   if (field) {
@@ -862,7 +993,7 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
   w.min_prev = c->d_min_prev.p;
   w.wtab = c->d_wtab.p;
   w.heading = c->d_heading.p;
-  w.rec = c->d_rec.p;
+  w.out = c->d_rec.p;
   w.N = static_cast<int>(c->N);
   w.EW = c->EW;
   w.w_shift = c->w_shift;
@@ -871,29 +1002,51 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
   hipLaunchKernelGGL(mcl_weigh_kernel, dim3(1), dim3(kMclOne), 0, c->stream, w);
   KC_HIP(hipGetLastError());
   KC_TRY(c->step_time.stop(c->stream));
-  KC_HIP(hipMemcpyAsync(c->h_rec.p, c->d_rec.p, sizeof(kc_mcl_record), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipMemcpyAsync(c->h_rec.p, c->d_rec.p, sizeof(MclOut), hipMemcpyDeviceToHost, c->stream));
   KC_HIP(hipStreamSynchronize(c->stream));
-  *out = *c->h_rec.p;
-  if (out->step != step || out->w1 == 0) KC_FAIL(KC_ERR_HIP, "the step's record is not this step's");
+  *out = c->h_rec.p->rec;
+  if (out->step != step || out->w1 == 0 || c->h_rec.p->fit.step != step) KC_FAIL(KC_ERR_HIP, "the step's record is not this step's");
   c->cur ^= 1;
   c->step = step;
   c->w1 = out->w1;
   c->inited = true;
   c->have_weights = true;
+  c->have_fit = true;
   return KC_OK;
 }
 
-int kc_mcl_resample(kc_mcl *c) {
+int kc_mcl_resample(kc_mcl *c) { return kc_mcl_resample_inject(c, 0); }
+
+int kc_mcl_resample_inject(kc_mcl *c, size_t n_inject) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (n_inject > c->N) KC_FAIL(KC_ERR_RANGE, "%zu injected slots are above the %zu particles", n_inject, c->N);
   if (!c->inited || !c->have_weights) KC_FAIL(KC_ERR_STATE, "a resample needs the weights of a step since the last init or resample");
   WorldMapView v{};
   KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
+  const size_t H = static_cast<size_t>(v.H);
+  if (n_inject > 0) {
+    KC_TRY(c->d_rows.reserve(H));
+    KC_TRY(c->d_before.reserve(H + 1));
+  }
   KC_TRY(mcl_follow(c, v));  // rule 50: the select copies the moved states
   const int N = static_cast<int>(c->N);
-  const unsigned long long u0 = mcl_draw(mcl_key(c, c->step), c->N, 15) % c->w1;
+  const unsigned long long key = mcl_key(c, c->step);
+  const unsigned long long u0 = mcl_draw(key, c->N, 15) % c->w1;
   c->inited = false;
   c->have_weights = false;
+  c->inject_time.begin_cycle();
+  if (n_inject > 0) {  // rule 62's index of the free cells, as the plane is behind the map's stream; it stays on the device
+    KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));
+    KC_TRY(c->inject_time.start("rows", c->stream));
+    hipLaunchKernelGGL(mcl_row_count_kernel, dim3(static_cast<unsigned>(H)), dim3(kMclBlock), 0, c->stream, v.cls, v.W, c->d_rows.p);
+    KC_HIP(hipGetLastError());
+    KC_TRY(c->inject_time.stop(c->stream));
+    KC_TRY(c->inject_time.start("row_prefix", c->stream));
+    hipLaunchKernelGGL(mcl_row_prefix_kernel, dim3(1), dim3(kMclOne), 0, c->stream, c->d_rows.p, c->d_before.p, v.H);
+    KC_HIP(hipGetLastError());
+    KC_TRY(c->inject_time.stop(c->stream));
+  }
   c->resample_time.begin_cycle();
   KC_TRY(c->resample_time.start("prefix", c->stream));
   hipLaunchKernelGGL(mcl_prefix_kernel, dim3(1), dim3(kMclOne), 0, c->stream, c->d_w.p, c->d_cum.p, N);
@@ -904,6 +1057,18 @@ int kc_mcl_resample(kc_mcl *c) {
                      c->d_acc.p, c->d_min_prev.p, c->d_cum.p, u0, c->w1, N);
   KC_HIP(hipGetLastError());
   KC_TRY(c->resample_time.stop(c->stream));
+  if (n_inject > 0) {  // over the slots the select has just filled
+    KC_TRY(c->inject_time.start("inject", c->stream));
+    hipLaunchKernelGGL(mcl_inject_kernel, dim3(mcl_blocks(n_inject * 64)), dim3(kMclBlock), 0, c->stream, v.cls, v.W, v.H, c->d_before.p,
+                       c->state(c->cur ^ 1), key, N, static_cast<int>(n_inject));
+    KC_HIP(hipGetLastError());
+    KC_TRY(c->inject_time.stop(c->stream));
+    // The row counts and the injection read the map's class plane on this stream, and the map's writers wait for no
+    // reader: the call returns only once those reads are over, so that whatever the caller does to the map next (an
+    // update, an integration, a shift's two copies) cannot reach into them.  Every other reader of the plane ends in a
+    // read-back; this path has none and runs only while the filter is lost.
+    KC_HIP(hipStreamSynchronize(c->stream));
+  }
   c->cur ^= 1;
   c->inited = true;
   return KC_OK;
@@ -946,9 +1111,64 @@ int kc_mcl_particles_device(kc_mcl *c, void **tx_out, void **ty_out, void **h_ou
 
 int kc_mcl_set_timing(kc_mcl *c, int enable) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
-  c->step_time.enabled = c->resample_time.enabled = enable != 0;
+  c->step_time.enabled = c->resample_time.enabled = c->inject_time.enabled = enable != 0;
   c->step_time.begin_cycle();
   c->resample_time.begin_cycle();
+  c->inject_time.begin_cycle();
+  return KC_OK;
+}
+
+int kc_mcl_inject_times(kc_mcl *c, float ms_out[3]) {
+  if (!c || !ms_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  ms_out[0] = ms_out[1] = ms_out[2] = 0.0f;
+  if (!c->inject_time.enabled || c->inject_time.used != 3) KC_FAIL(KC_ERR_STATE, "no injecting resample has been timed on this localiser");
+  KC_HIP(hipSetDevice(c->device));
+  size_t n = 0;
+  KC_TRY(c->inject_time.get(nullptr, ms_out, 3, &n));
+  return KC_OK;
+}
+
+int kc_mcl_last_fit(kc_mcl *c, kc_mcl_fit *out) {
+  if (!c || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  if (!c->have_fit) KC_FAIL(KC_ERR_STATE, "no fit before a step since the last init or change of model");
+  *out = c->h_rec.p->fit;
+  return KC_OK;
+}
+
+// rules 60 and 61, in the documented order
+int kc_mcl_recovery_update(uint64_t cost_sum, size_t n_particles, size_t beams_used, int a_slow, int a_fast, uint32_t max_num,
+                           uint32_t max_den, kc_mcl_recovery *state, int64_t *m_out, size_t *n_inject_out) {
+  if (m_out) *m_out = -1;
+  if (n_inject_out) *n_inject_out = 0;
+  if (!state || !n_inject_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  constexpr int64_t kMaxFit = 65535ll * 256;
+  if (a_slow < 0 || a_slow > 30) KC_FAIL(KC_ERR_INVALID, "a_slow must be in 0 .. 30, got %d", a_slow);
+  if (a_fast < 0 || a_fast > 30) KC_FAIL(KC_ERR_INVALID, "a_fast must be in 0 .. 30, got %d", a_fast);
+  if (max_den == 0) KC_FAIL(KC_ERR_INVALID, "max_den is 0");
+  if (max_num > max_den) KC_FAIL(KC_ERR_INVALID, "the injected share %u / %u is above 1", max_num, max_den);
+  if (n_particles == 0 || n_particles > KC_MCL_MAX_PARTICLES)
+    KC_FAIL(KC_ERR_RANGE, "%zu particles are outside 1 .. %d", n_particles, KC_MCL_MAX_PARTICLES);
+  if (beams_used > KC_MCL_MAX_BEAMS) KC_FAIL(KC_ERR_RANGE, "%zu beams are above the cap of %d", beams_used, KC_MCL_MAX_BEAMS);
+  const uint64_t rays = static_cast<uint64_t>(n_particles) * static_cast<uint64_t>(beams_used);  // <= 2^26
+  if (cost_sum > rays * 65535ull) KC_FAIL(KC_ERR_RANGE, "cost_sum is above what %zu x %zu uint16 penalties can sum to", n_particles, beams_used);
+  if (state->primed && (state->slow < 0 || state->slow > kMaxFit || state->fast < 0 || state->fast > kMaxFit))
+    KC_FAIL(KC_ERR_RANGE, "an average of the state is outside 0 .. 65535 * 256");
+  if (beams_used == 0) return KC_OK;  // the step said nothing
+  const int64_t m = static_cast<int64_t>(cost_sum * 256ull / rays);  // cost_sum * 256 < 2^50
+  if (m_out) *m_out = m;
+  if (!state->primed) {
+    state->slow = state->fast = m;
+    state->primed = 1;
+    return KC_OK;
+  }
+  state->slow += (m - state->slow) >> a_slow;  // arithmetic shifts: they floor
+  state->fast += (m - state->fast) >> a_fast;
+  if (state->fast <= state->slow) return KC_OK;
+  const uint64_t n = static_cast<uint64_t>(n_particles);
+  const uint64_t cap = n * max_num / max_den;  // n max_num < 2^49
+  const uint64_t want = n * static_cast<uint64_t>(state->fast - state->slow) / static_cast<uint64_t>(state->fast);
+  *n_inject_out = static_cast<size_t>(cap < want ? cap : want);
   return KC_OK;
 }
 

@@ -21,13 +21,24 @@ class MCLEstimate:
     `n_eff` (the effective particle count W1^2 / W2), `resampled` (whether the step ended with a resample),
     `best_cost` (the smallest accumulated penalty), `spread` (the weighted standard deviation of position in metres,
     formed in doubles from a read-back of the particles, not from the device's exact sums) and `record`, those sums.
-    It has `x`, `y` and `yaw`, so `WorldMap.update`, `match`, `scan` and `points` take it as a robot state."""
+    It has `x`, `y` and `yaw`, so `WorldMap.update`, `match`, `scan` and `points` take it as a robot state.
+
+    `fit` says how well the particles fit the scan in absolute terms (DESIGN.md 4.11 rules 59 and 60): the step's mean
+    penalty a contributing beam over ALL particles, in 1 / 256 of a penalty unit, or -1 when no beam contributed.
+    `n_eff`, `spread` and `best_cost` are relative to the particle set, so a filter that is confidently wrong looks the
+    same in them as one that is right; in `fit` it does not.  Use it to gate `WorldMap.integrate_scan` / `update`:
+    writing the map from a wrong pose damages it.  No threshold is shipped: a good value depends on the tables and
+    the map, and none has been measured; `fit_slow` and `fit_fast`, its two running averages (rule 61), show what is
+    usual for the run so far.  `injected` is the number of slots the step's resample drew anew over the map's free
+    cells (0 with recovery off); `cost_min` and `cost_best` are the smallest step cost and the best particle's,
+    `beams_used` the beams that contributed."""
 
     def __init__(self, inner):
         self._e = inner
 
     def __getattr__(self, name):
-        if name in ("x", "y", "yaw", "n_eff", "resampled", "best_cost", "spread", "record", "txe", "tye"):
+        if name in ("x", "y", "yaw", "n_eff", "resampled", "best_cost", "spread", "record", "txe", "tye", "fit", "fit_slow",
+                    "fit_fast", "injected", "cost_min", "cost_best", "beams_used"):
             return getattr(self._e, name)
         raise AttributeError(name)
 
@@ -36,7 +47,8 @@ class MCLEstimate:
 
     def __repr__(self):
         return (f"MCLEstimate(x={self.x:.3f}, y={self.y:.3f}, yaw={self.yaw:.4f}, n_eff={self.n_eff:.1f}, "
-                f"spread={self.spread:.3f}, resampled={self.resampled}, best_cost={self.best_cost})")
+                f"spread={self.spread:.3f}, resampled={self.resampled}, best_cost={self.best_cost}, fit={self.fit}, "
+                f"injected={self.injected})")
 
 
 def _pose(robot_state) -> Tuple[float, float, float]:
@@ -50,7 +62,7 @@ class MCL:
     def __init__(self, world_map, n_particles: int, angles, range_max: float, sigma_hit: float = 0.1, seed: int = 0,
                  motion_noise: Tuple[float, float, float] = (0.02, 0.01, 0.01), resample_ratio: Tuple[int, int] = (1, 2),
                  unknown_blocks: bool = False, skip_no_return: bool = False, spread: bool = True, model: str = "beam",
-                 **model_args):
+                 recovery=None, **model_args):
         """world_map: a `WorldMap` (kept alive).  angles: the beams in the scan frame, radians; a sensor's yaw offset is
         folded in here, a translated mount is out of scope.  range_max: metres; a measured range that is not finite or
         not below it is a beam without a return: it counts as range_max, or not at all with skip_no_return.
@@ -62,7 +74,8 @@ class MCL:
         (DESIGN.md 4.11 rules 44 and 45): a beam costs one lookup of the map's distance field at its endpoint, beams
         without a return say nothing; **model_args are then reach (cells, default ceil(3 sigma_hit / resolution) within
         1 .. 63), floor, pen_scale, w_shift, n_w, wtab0, temperature.  It enables the map's distance field itself when
-        that is off or shorter (unknown_blocks decides what blocks there)."""
+        that is off or shorter (unknown_blocks decides what blocks there).
+        recovery: None (off), True (the defaults) or (a_slow, a_fast, (num, den)): see `set_recovery`."""
         if model not in ("beam", "field"):
             raise ValueError('model must be "beam" or "field"')
         inner = cpp_world_map(world_map)
@@ -80,6 +93,24 @@ class MCL:
         self._mcl.set_motion_noise(*(float(v) for v in motion_noise))
         self._mcl.set_resample_ratio(int(resample_ratio[0]), int(resample_ratio[1]))
         self._mcl.set_spread(bool(spread))
+        self.set_recovery(recovery)
+
+    def set_recovery(self, recovery=True) -> None:
+        """Recovery from a lost filter by injected particles (DESIGN.md 4.11 rules 61 to 63).  The fit of every step feeds
+        a slow and a fast average, slow += (m - slow) >> a_slow and fast alike; while fast lies above slow, the scans fit
+        worse than they used to, and the step ends with a resample in which min(N num / den, N (fast - slow) / fast)
+        slots, spread evenly, are drawn anew over the map's free cells as `init_global` draws them.  None: off (the
+        averages still run and `MCLEstimate.fit` is still reported); True: a_slow 4, a_fast 1, at most 1 / 4 of the
+        particles, which are judgement, not measurement; or (a_slow, a_fast, (num, den)).  The injecting resample reads the
+        map on the device, and `step` waits for it: the map may be written (`integrate_scan`, `update`, `shift`) as soon
+        as `step` has returned."""
+        if recovery is None or recovery is False:
+            self._mcl.clear_recovery()
+        elif recovery is True:
+            self._mcl.set_recovery()
+        else:
+            a_slow, a_fast, (num, den) = recovery
+            self._mcl.set_recovery(int(a_slow), int(a_fast), int(num), int(den))
 
     def init(self, robot_state, sigma_xy: float, sigma_yaw: float) -> None:
         """Gaussian around robot_state (x, y, yaw), sigmas in metres and radians."""

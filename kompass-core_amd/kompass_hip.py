@@ -147,6 +147,20 @@ class MclRecord(C.Structure):
                 int(self.best_tx), int(self.best_ty), int(self.best_h), int(self.step))
 
 
+class MclFit(C.Structure):
+    """kc_mcl_fit: the absolute penalties of one localiser step (DESIGN.md 4.11 rule 59)."""
+    _fields_ = [("cost_sum", C.c_uint64), ("cost_min", C.c_uint32), ("cost_best", C.c_uint32), ("step", C.c_uint32)]
+
+    def as_tuple(self):
+        """(cost_sum, cost_min, cost_best, step)"""
+        return int(self.cost_sum), int(self.cost_min), int(self.cost_best), int(self.step)
+
+
+class MclRecovery(C.Structure):
+    """kc_mcl_recovery: rule 61's two averages."""
+    _fields_ = [("slow", C.c_int64), ("fast", C.c_int64), ("primed", C.c_int32)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -393,6 +407,11 @@ SIGNATURES = {
     "kc_worldmap_integrate_set_precheck": (C.c_int, [_vp, C.c_int]),
     "kc_worldmap_integrate_set_timing": (C.c_int, [_vp, C.c_int]),
     "kc_worldmap_integrate_times": (C.c_int, [_vp, _fp]),
+    "kc_mcl_last_fit": (C.c_int, [_vp, C.POINTER(MclFit)]),
+    "kc_mcl_recovery_update": (C.c_int, [C.c_uint64, _sz, _sz, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(MclRecovery),
+                                         C.POINTER(C.c_int64), C.POINTER(_sz)]),
+    "kc_mcl_resample_inject": (C.c_int, [_vp, _sz]),
+    "kc_mcl_inject_times": (C.c_int, [_vp, _fp]),
 }
 
 _lib = None
@@ -1950,6 +1969,16 @@ def mcl_quantise_ranges(ranges, resolution, range_max, flags=0):
                      for z in np.asarray(ranges, dtype=np.float64).reshape(-1)], np.int32)
 
 
+def mcl_recovery_update(cost_sum, n, b_used, state, a_slow=4, a_fast=1, max_num=1, max_den=4):
+    """Rules 60 and 61 (host only): state (slow, fast, primed) -> (state, m or -1, n_inject); raises ValueError /
+    IndexError.  The defaults are the front ends': judgement, not measurement."""
+    s = MclRecovery(int(state[0]), int(state[1]), int(bool(state[2])))
+    m, n_inject = C.c_int64(), _sz(0)
+    _check(lib().kc_mcl_recovery_update(int(cost_sum), int(n), int(b_used), int(a_slow), int(a_fast), int(max_num), int(max_den),
+                                        C.byref(s), C.byref(m), C.byref(n_inject)))
+    return (int(s.slow), int(s.fast), bool(s.primed)), int(m.value), int(n_inject.value)
+
+
 class MclContext(_Owner):
     """Owner of one kc_mcl context (DESIGN.md 4.11 rules 28 to 41): a Monte-Carlo localiser over a WorldMapContext,
     which it keeps alive.  Works in the ABI's integers; kompass_core.mapping.MCL is the front end in metres."""
@@ -1998,6 +2027,28 @@ class MclContext(_Owner):
 
     def resample(self):
         _check(lib().kc_mcl_resample(self.h))
+
+    def last_fit(self) -> MclFit:
+        """Rule 59's fit of the last step, from the host copy its read-back filled; KompassHipError (KC_ERR_STATE) before
+        a step and after an init or a change of model."""
+        f = MclFit()
+        _check(lib().kc_mcl_last_fit(self.h, C.byref(f)))
+        return f
+
+    def resample_inject(self, n_inject):
+        """Rule 62: rule 40's resample with n_inject of the N slots drawn anew over the map's free cells; 0 is resample()."""
+        _check(lib().kc_mcl_resample_inject(self.h, int(n_inject)))
+
+    @staticmethod
+    def recovery_update(cost_sum, n, b_used, state, a_slow=4, a_fast=1, max_num=1, max_den=4):
+        """mcl_recovery_update: rules 60 and 61, host only."""
+        return mcl_recovery_update(cost_sum, n, b_used, state, a_slow, a_fast, max_num, max_den)
+
+    def inject_times(self):
+        """(rows, row_prefix, inject) launches of the last injecting resample in milliseconds, by HIP events."""
+        ms = (C.c_float * 3)()
+        _check(lib().kc_mcl_inject_times(self.h, ms))
+        return tuple(float(v) for v in ms)
 
     def particles(self):
         """(tx int64, ty int64, h uint32, acc uint32), N each, copied to the host."""

@@ -55,6 +55,14 @@ beams spread 2 m around the middle, range_max 10 m.  One JSON line a configurati
       walk sets, and the ratio of the step's walk launch to it.
   python tools/worldmap_time.py --mcl [--reps 30] [--warmup 3]
 
+--mcl --recovery times the fit's step and the injecting resample (rules 59 to 62): the same world, the field model, 4096 x
+64 and 65536 x 24.  ONE JSON line with an entry a configuration: kc_mcl_step, step + kc_mcl_resample and step +
+kc_mcl_resample_inject(N / 4) by the host's clock (a resample has no wait of its own: the next step's read-back is its
+end), the launches of each by HIP events (the injecting resample's five: prefix, select, rows, row_prefix, inject), and
+kc_mcl_init_global by the host's clock beside them.  With KOMPASS_HIP_LIB_OLD=1 (tools/ab_libs.sh, a library from before
+these rules) the plain legs alone: the A/B of the step and the plain resample.
+  python tools/worldmap_time.py --mcl --recovery [--reps 30] [--warmup 3]
+
 --field times the distance plane and the likelihood-field model (rules 42 to 45): the same world under the "latest
 observation wins" model, reach 6 and 16.  One JSON line a reach with
   (a) a full refresh (kc_worldmap_set_distance marks the whole map, then kc_worldmap_distance_device: refresh and wait);
@@ -356,6 +364,77 @@ def mcl_leg(args):
                 print(json.dumps(line), flush=True)
 
 
+def recovery_leg(args):
+    """--mcl --recovery: ONE JSON line (tools/ab_libs.sh keeps a run's last line) with an entry a configuration."""
+    import os
+
+    import worldmap_mcl_field_ref as fref
+    import worldmap_mcl_ref as lref
+
+    old = os.environ.get("KOMPASS_HIP_LIB_OLD", "0") == "1"     # a library from before rules 59 to 63: the plain legs alone
+    ang, rng = syn.dense_scan(2048, 1.2)
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r, ORIGIN[1] + (H // 2) * r)
+    range_max = 10.0
+    cells = 65536.0 / r
+    pen_d2, pen_far, reach, wtab, w_shift = fref.field_tables(RES, 0.1)
+    out = []
+    with kh.MapperContext(GH, GW, RES, (0, 0, 0), 0.0, len(ang)) as mapper, kh.WorldMapContext(W, H, RES, ORIGIN) as wm:
+        wm.set_model(**ref.LATEST_WINS_EXACT)                # a miss makes a cell empty: the scan's inside is free
+        mapper.scan_to_grid_device(ang, rng)
+        mapper.sync()
+        wm.update_from_mapper(mapper, centre + (0.0,))
+        wm.set_distance(reach)
+        for n, b in ((4096, 64), (65536, 24)):
+            a = np.arange(b) * (2 * np.pi / b)
+            zq = kh.mcl_quantise_ranges(wm.scan(centre + (0.3,), a, range_max), RES, range_max)
+            with kh.MclContext(wm, n, a, range_max, seed=1) as mcl:
+                mcl.set_field_model(pen_d2, pen_far, wtab, w_shift)
+                q0 = wm.quantise_pose(*centre, 0.0)
+                scales = (lref.noise_scale(0.02 * cells), lref.noise_scale(0.01 * cells), lref.noise_scale(0.01 / (2 * np.pi) * 65536))
+                mcl.init_pose(q0.tx, q0.ty, 0, lref.noise_scale(2.0 * cells), lref.noise_scale(65536 / 4))
+
+                def step():
+                    return mcl.step(3000, 0, 50, *scales, zq)
+
+                def step_resample():
+                    step()
+                    mcl.resample()
+
+                def step_inject():
+                    step()
+                    mcl.resample_inject(n // 4)
+
+                def launches(cycle, get):
+                    mcl.set_timing(True)
+                    parts = []
+                    for k in range(args.warmup + args.reps):
+                        cycle()
+                        if k >= args.warmup:
+                            parts.append(get())
+                    mcl.set_timing(False)
+                    return parts
+
+                line = {"particles": n, "beams": b, "reps": args.reps, "warmup": args.warmup,
+                        "step_ms": timed(step, args.reps, args.warmup),
+                        "step_and_resample_ms": timed(step_resample, args.reps, args.warmup)}
+                parts = launches(step_resample, mcl.times)
+                for i, name in enumerate(["walk", "weigh", "prefix", "select"]):
+                    line[f"launch_{name}_ms"] = spread([p[i] for p in parts])
+                line["resample_launches_ms"] = spread([p[2] + p[3] for p in parts])
+                if not old:
+                    line["step_and_inject_ms"] = timed(step_inject, args.reps, args.warmup)
+                    parts = launches(step_inject, lambda: mcl.times()[2:] + mcl.inject_times())
+                    for i, name in enumerate(["prefix", "select", "rows", "row_prefix", "inject"]):
+                        line[f"inject_launch_{name}_ms"] = spread([p[i] for p in parts])
+                    line["inject_launches_ms"] = spread([sum(p) for p in parts])
+                    line["fit_last"] = list(mcl.last_fit().as_tuple())
+                line["init_global_ms"] = timed(mcl.init_global, args.reps, args.warmup)
+                line["free_cells"] = mcl.init_global()
+                out.append(line)
+    print(json.dumps({"world": [W, H], "model": "field", "inject": "N / 4", "recovery": out}), flush=True)
+
+
 def field_leg(args):
     import worldmap_mcl_field_ref as fref
     import worldmap_mcl_ref as lref
@@ -570,6 +649,7 @@ def main():
     ap.add_argument("--points", action="store_true", help="time the obstacle hand-off to the controller instead")
     ap.add_argument("--scan", action="store_true", help="time the virtual laser scan instead")
     ap.add_argument("--mcl", action="store_true", help="time the Monte-Carlo localiser instead")
+    ap.add_argument("--recovery", action="store_true", help="with --mcl: time the plain and the injecting resample instead")
     ap.add_argument("--field", action="store_true", help="time the distance plane and the likelihood-field model instead")
     ap.add_argument("--shift", action="store_true", help="time the rolling window's shift and the route it replaces instead")
     ap.add_argument("--integrate", action="store_true", help="time the scan integration and today's route for the same scan instead")
@@ -585,7 +665,7 @@ def main():
     if args.scan:
         return scan_leg(args)
     if args.mcl:
-        return mcl_leg(args)
+        return recovery_leg(args) if args.recovery else mcl_leg(args)
     if args.field:
         return field_leg(args)
     if args.shift:
