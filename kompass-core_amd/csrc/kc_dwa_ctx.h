@@ -25,6 +25,7 @@
 #include "kc_hostmath.h"
 #include "kc_internal.h"
 #include "kc_pool.h"
+#include "kc_sample_pattern.h"
 #include "kc_seg_tables.h"
 #include "kc_scan_tables.h"
 
@@ -102,19 +103,10 @@ struct kc_dwa {
   DevBuf<uint32_t> d_ginner, d_gouter;  // dilated sensor bitmaps
   bool have_dil = false;
   DevBuf<unsigned long long> d_dbg2;    // roll-out kernel stamps (diagnostic)
-  DevBuf<int32_t> d_prow;               // trig rows in d_perm order (velocities are read through d_perm)
-  DevBuf<int32_t> d_cprow, d_cperm;     // the same in the dealt order of the single-launch cycle
-  DevBuf<uint32_t> d_pvi, d_cpvi;       // value indices in those two orders
-  DevBuf<int32_t> d_perm;               // shard-local sample ids ordered by trig row
-  std::vector<int32_t> h_perm;
   std::vector<int32_t> perm_scratch;    // (counting sort of build_perm)
   std::vector<int32_t> perm_prow;       // (its staging rows)
   std::vector<uint32_t> perm_pvi;
-  bool perm_plain_dev = false, perm_dealt_dev = false;  // which of the two orders the device holds (perm_valid: the host does)
-  std::vector<int32_t> uploaded_rows;   // trig-row pattern the orders on the device were built for
-  size_t perm_first = 0, perm_count = 0;  // ... and the shard
   double inv_res = 0.0;      // 1.0 / res (octomap resolution_factor)
-  bool perm_valid = false;
   bool bar_dirty = false;    // BAR stores not yet fenced
   bool update_busy = false;  // an update call queued device work since the last idle point
   bool seg_busy = false;     // ... a kernel that writes the tracked-segment table (resident-path window)
@@ -145,7 +137,6 @@ struct kc_dwa {
   bool cost_lds_ok = false;             // sample_cost_kernel<true> may take kCostLdsBudget
   int fused_samples = 32, fused_block = 1024;
   int cycle_samples = 32;  // samples per workgroup of the single-launch cycle: 16 when 32 would leave half the CUs idle
-  int perm_cs = 0;         // ... the dealt order on the device was built for
   int cycle_samples_opt = 0;  // option "cycle_samples": 0 auto, 16, 32
   int velocity_group = 0;     // option "velocity_group": samples per wavefront of the velocity sums (0 auto, 1, 4, 16)
   bool velocity_beside = true;  // option "velocity_beside": velocity_sums_kernel on a second stream beside the cost kernel
@@ -160,31 +151,24 @@ struct kc_dwa {
   size_t shard_first = 0, shard_count = 0;
   double vmax_lin = 0.0;      // max hypot(vx, vy) over the list
   DevBuf<double> d_vxt, d_vyt;   // value tables of the axes (rewritten by every new window)
-  DevBuf<uint32_t> d_vidx;       // [n] (index into d_vxt) | (index into d_vyt) << 16: rewritten when the pattern changes
   // The index tables and the two walking orders of a window lattice belong to its PATTERN (which sample takes which
   // axis value; lattice signature).  A robot whose velocity moves changes pattern in every second cycle -- an axis
   // gains or loses a value, a value crosses |v| = kMinVel -- between a handful of patterns: the tables of the last
   // few stay on the device and a change back is a swap of pointers (tools/window_sweep.py: 380 us per change
   // before, the sort + six pageable copies of build_perm).
-  struct PatternTables {
-    uint64_t sig = 0;
-    size_t n = 0;
-    uint64_t stamp = 0;  // last use
-    DevBuf<uint32_t> vidx, pvi, cpvi;
-    DevBuf<int32_t> row, perm, prow, cperm, cprow;
-    std::vector<int32_t> h_perm, h_dealt, rows;
-    bool perm_valid = false, perm_plain_dev = false, perm_dealt_dev = false;
-    size_t perm_first = 0, perm_count = 0;
-    int perm_cs = 0;
+  // Everything that belongs to a pattern lives here (host side: kc_sample_pattern.h, with the rule that moves them).
+  struct PatternTables : PatternHost {
+    DevBuf<uint32_t> vidx;               // [n] (index into d_vxt) | (index into d_vyt) << 16
+    DevBuf<int32_t> row;                 // [n] trig row
+    DevBuf<int32_t> perm, prow;          // shard-local sample ids ordered by trig row (velocities are read through perm) / their rows
+    DevBuf<int32_t> cperm, cprow;        // the same in the dealt order of the single-launch cycle
+    DevBuf<uint32_t> pvi, cpvi;          // value indices in those two orders
   };
   static_assert(std::is_nothrow_move_constructible<PatternTables>::value, "`patterns` grows by moving its slots");
-  std::vector<PatternTables> patterns;  // (inactive ones; the active pattern lives in the members above / below)
+  PatternTables pat;                    // the active pattern
+  std::vector<PatternTables> patterns;  // the kept ones
   uint64_t pattern_clock = 0;
   long pattern_hits = 0, pattern_builds = 0;
-  DevBuf<int32_t> d_row;
-  uint64_t up_sig = 0;           // signature / size of the pattern on the device
-  size_t up_n = 0;
-  std::vector<uint16_t> up_ix, up_iy;  // ... and the pattern itself for lists without a signature
 
   // per cycle
   size_t P = 0;               // points of the last roll-out
@@ -266,7 +250,7 @@ struct kc_dwa {
   long long seq = 0;           // last cycle sequence handed to finalize
   bool pub_pending = false;
   int team_max = 4;        // option "team_max" (0..4): workgroups of the cycle kernel with that many survivors cost them by teams
-  bool perm_busy = false;  // a queued roll-out reads the walking orders (d_perm ...): cleared with `drained`
+  bool perm_busy = false;  // a queued roll-out reads the walking orders (pat.perm ...): cleared with `drained`
   bool drained = false;  // the host saw the last cost kernel's record: every earlier
                          // command of the stream has finished with the staging buffers
   PinBuf<float> h_row;         // winner row staging
@@ -294,7 +278,6 @@ struct kc_dwa {
   unsigned slots_G = 0;
   bool device_record_valid = true;  // d_result holds the last cycle's record (not after a host-reduced cycle)
   PinBuf<long long> h_slots;   // [grid][4]
-  std::vector<int32_t> h_dealt;     // host copy of the dealt order (compacted index of the winner)
   std::vector<uint64_t> slot_pending;   // scratch of fetch_slots
   long long *xchg_send = nullptr;  // sharded call: the send record, this rank, words per rank (set by kc_dwa_cycle_sharded)
   int xchg_rank = 0, xchg_rw = 0;
@@ -413,6 +396,17 @@ inline void bar_flush(kc_dwa *c) {
     c->bar_dirty = false;
   }
 }
+// The stream is idle: the host has waited for the context's stream, or has seen the record of the last thing queued
+// on it, so nothing queued reads any per-update table, the segment table or the walking orders.
+inline void stream_idle(kc_dwa *c) {
+  c->drained = true;
+  c->update_busy = c->seg_busy = c->perm_busy = false;
+}
+inline int wait_idle(kc_dwa *c) {
+  KC_HIP(hipStreamSynchronize(c->stream));
+  stream_idle(c);
+  return KC_OK;
+}
 // Before the host overwrites per-update tables: nothing queued may still read
 // them.  A cycle whose record the host has seen proves that everything queued
 // before it has finished; work queued since then (dilate_kernel, copies) is
@@ -420,13 +414,7 @@ inline void bar_flush(kc_dwa *c) {
 inline int quiesce_for_update(kc_dwa *c, bool sensor_tables = true) {
   // (the tracked-segment table is only read by cost kernels, i.e. by cycles:
   // work queued by a sensor update since the last cycle does not touch it)
-  if (!c->drained || (sensor_tables && c->update_busy) || (!sensor_tables && c->seg_busy)) {
-    KC_HIP(hipStreamSynchronize(c->stream));
-    c->update_busy = false;
-    c->seg_busy = false;
-    c->drained = true;
-    c->perm_busy = false;
-  }
+  if (!c->drained || (sensor_tables && c->update_busy) || (!sensor_tables && c->seg_busy)) return wait_idle(c);
   return KC_OK;
 }
 

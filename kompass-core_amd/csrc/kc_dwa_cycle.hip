@@ -473,10 +473,7 @@ int fetch_slots(kc_dwa *c, kc_result *out, size_t n) {
   }
   c->hprof.mark(6);
   c->slots_pending = false;
-  c->drained = true;        // every workgroup is past its last table read
-  c->perm_busy = false;
-  c->update_busy = false;
-  c->seg_busy = false;
+  stream_idle(c);  // every workgroup is past its last table read
   c->timing.mark("host:wait_result");
   kc_result r{};
   r.n_admissible = na;
@@ -494,13 +491,13 @@ int fetch_slots(kc_dwa *c, kc_result *out, size_t n) {
     r.raw_index = kc_key_index(fkey);
     // admissible samples in front of the winner (generation order = local id order)
     const int lim = static_cast<int>(r.raw_index - static_cast<int64_t>(c->shard_first));
-    const int32_t *ids = c->h_dealt.data();
-    const size_t nd = c->h_dealt.size();
+    const int32_t *ids = c->pat.h_dealt.data();
+    const size_t nd = c->pat.h_dealt.size();
     long long cnt = 0;
     for (unsigned g = 0; g < G; ++g) {
       const uint32_t m = static_cast<uint32_t>(static_cast<unsigned long long>(c->h_slots.p[4 * g + 1]) & 0xFFFFFFFFull);
       if (!m) continue;
-      const size_t cs = static_cast<size_t>(c->perm_cs);
+      const size_t cs = static_cast<size_t>(c->pat.perm_cs);
       const size_t base = static_cast<size_t>(g) * cs;
       uint32_t below = 0u;
 #if defined(__SSE2__)
@@ -563,10 +560,7 @@ int fetch(kc_dwa *c, kc_result *out, size_t n) {
         c->h_result.p[1] = w1 >> 32;  // n_admissible (-1: device error)
         c->h_result.p[2] = static_cast<long long>(static_cast<int32_t>(w1 & 0xFFFFFFFFll));
         got = true;
-        c->drained = true;
-        c->perm_busy = false;
-        c->update_busy = false;  // queued in front of the cycle whose record just arrived
-        c->seg_busy = false;
+        stream_idle(c);  // (update work was queued in front of the cycle whose record just arrived)
         break;
       }
       if ((spins & 1023) == 1023 &&
@@ -789,8 +783,8 @@ static int fill_roll_args(kc_dwa *c, const kc_state *start, size_t P, double dt,
   a.vyt = c->d_vyt.p;
   a.nvx = static_cast<int>(c->lat.vx_values.size());
   a.nvy = static_cast<int>(c->lat.vy_values.size());
-  a.vidx = c->d_vidx.p;
-  a.row = c->d_row.p;
+  a.vidx = c->pat.vidx.p;
+  a.row = c->pat.row.p;
   a.trig = c->d_trig.p;
   a.trig_dev = (t.dev && !t.ahead) ? 1 : 0;
   if (t.dev) KC_TRY(ensure_sincostab(c));
@@ -905,12 +899,13 @@ static auto plain_kernel_of(int fs, int fb) -> void (*)(RollArgs, NoTail) {
 static int launch_fused(kc_dwa *c, const RollPlan &p, size_t table_bytes, RollArgs &a, CycleTail &tail) {
   hipStream_t s = c->stream;
   const bool cycle = p.cycle;
-  if (!c->perm_valid || c->perm_first != c->shard_first || c->perm_count != c->shard_count || c->perm_cs != p.cs ||
-      !(cycle ? c->perm_dealt_dev : c->perm_plain_dev))
+  const kc_dwa::PatternTables &pat = c->pat;
+  if (!pat.perm_valid || pat.perm_first != c->shard_first || pat.perm_count != c->shard_count || pat.perm_cs != p.cs ||
+      !(cycle ? pat.perm_dealt_dev : pat.perm_plain_dev))
     KC_TRY(build_perm(c, cycle));
-  a.perm = cycle ? c->d_cperm.p : c->d_perm.p;
-  a.prow = cycle ? c->d_cprow.p : c->d_prow.p;
-  a.pvi = cycle ? c->d_cpvi.p : c->d_pvi.p;
+  a.perm = cycle ? pat.cperm.p : pat.perm.p;
+  a.prow = cycle ? pat.cprow.p : pat.prow.p;
+  a.pvi = cycle ? pat.cpvi.p : pat.pvi.p;
   c->perm_busy = true;  // (until the host has seen this cycle's record)
 #ifdef KC_PHASE_STAMPS
   KC_TRY(arm_stamps(c, c->d_dbg2, 512 * 32, 512 * 32, &a.dbg));
@@ -956,7 +951,7 @@ static int launch_tilted_collision(kc_dwa *c, const kc_state *start, const RollA
   }
   ta.pos = c->d_pos.p;
   ta.trig = c->d_trig.p;
-  ta.row = c->d_row.p;
+  ta.row = c->pat.row.p;
   ta.n = static_cast<int>(n);
   ta.first = static_cast<int>(c->shard_first);
   ta.P = static_cast<int>(P);
@@ -1330,10 +1325,7 @@ int kc_cost_upload(kc_dwa *c, const float *paths_x, const float *paths_y, const 
   const bool vel = vvx && vvy && vom;
   KC_TRY(use_device(c));
   hipStream_t s = c->stream;
-  KC_HIP(hipStreamSynchronize(s));
-  c->drained = true;
-  c->perm_busy = false;
-  c->update_busy = false;
+  KC_TRY(wait_idle(c));
   c->P = P;
   c->n_roll = n;
   c->external = true;

@@ -1273,8 +1273,7 @@ int finish_list_handoff(kc_dwa *c, BoundsOf bounds_of) {
   c->raw_xyz.resize(3 * n);
   KC_HIP(hipMemcpyAsync(c->raw_xyz.data(), c->d_raw.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost,
                         c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));
-  c->update_busy = false;
+  KC_TRY(wait_idle(c));
   c->raw_on_device = false;
   build_host_lists(c, c->raw_xyz.data(), n);
   KC_TRY(upload_voxels(c));
@@ -1547,10 +1546,7 @@ int kc_dwa_set_path(kc_dwa *c, const float *x, const float *y, const float *z, c
   if (!c || (n && (!x || !y || !acc))) KC_FAIL(KC_ERR_INVALID, "null argument");
   KC_TRY(use_device(c));
   // the old rows may still be read by a queued window kernel
-  KC_HIP(hipStreamSynchronize(c->stream));
-  c->update_busy = false;
-  c->drained = true;
-  c->perm_busy = false;
+  KC_TRY(wait_idle(c));
   c->path_n = n;
   c->path_len = total_length;
   c->path_edge.assign(n > 1 ? n - 1 : 0, 0.0f);
@@ -1598,10 +1594,7 @@ int kc_dwa_set_tracked_window(kc_dwa *c, size_t start, size_t S) {
   c->seg_nsup = static_cast<int>(nsup);
   const size_t seg_words = static_cast<size_t>(seg_cap_offset(static_cast<int>(S))) + 8 * nch + 12 * nsup;
   if (seg_words > c->d_seg.cap) {  // growing frees the old table: nothing may still read or write it
-    KC_HIP(hipStreamSynchronize(c->stream));
-    c->update_busy = false;
-    c->drained = true;
-    c->perm_busy = false;
+    KC_TRY(wait_idle(c));
     KC_TRY(c->d_seg.reserve(seg_words));
     KC_TRY(c->h_seg.reserve(seg_words));
   }

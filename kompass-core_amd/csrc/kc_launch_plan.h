@@ -325,8 +325,8 @@ inline CostPlan plan_cost(const CostFacts &f) {
 }
 
 // ---- window patterns -------------------------------------------------------------------------------------------
-// Kept patterns of a context whose windows hold n samples (swap_in_pattern): 40 bytes of device memory a sample and
-// pattern, 128 MB of them at most, 16 to 256 patterns.
+// Kept patterns of a context whose windows hold n samples (find_pattern, kc_sample_pattern.h): 40 bytes of device
+// memory a sample and pattern, 128 MB of them at most, 16 to 256 patterns.
 inline size_t pattern_slots(size_t n) {
   return std::min<size_t>(256, std::max<size_t>(16, (size_t(128) << 20) / (40 * std::max<size_t>(n, 1))));
 }

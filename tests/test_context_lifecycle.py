@@ -144,7 +144,7 @@ def test_create_use_destroy_rounds(name):
 
 
 def test_dwa_patterns_change_places_before_destroy():
-    """Two sample patterns alternate across the cycles of one context: from the third cycle on swap_in_pattern moves
+    """Two sample patterns alternate across the cycles of one context: from the third cycle on find_pattern moves
     the pattern's buffers between the context and a kept slot, and every cycle repeats the first of its pattern."""
     inp = _dwa_inputs()
     ctx = make_dwa()

@@ -1,6 +1,6 @@
-"""The velocity window's pattern store on the MI355X (csrc/kc_dwa.hip: upload_samples, swap_in_pattern, build_perm;
-DESIGN.md 0.4, point 11): the device tables a cycle reads after a window came back from the store, was replaced in it,
-was overwritten by an explicit list, met other options or another share than it was built for, or does not fit the
+"""The velocity window's pattern store on the MI355X (the rule and the orders: csrc/kc_sample_pattern.h, natively in
+tests/native/sample_pattern.cpp; the uploads: upload_samples / build_perm, csrc/kc_dwa.hip; DESIGN.md 0.4, point 11):
+the device tables a cycle reads after a window came back from the store, was replaced in it, was overwritten by an explicit list, met other options or another share than it was built for, or does not fit the
 kernels' LDS tables.  A stale table raises no error, it gives other samples, so every step runs three ways
 (tests/window_patterns.py: the context under test, a context that only ever sees explicit lists, the oracle) and
 everything a cycle leaves is compared as bits; the counters pattern_hits / pattern_builds follow a plain model of the

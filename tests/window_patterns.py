@@ -5,7 +5,8 @@ The scene.  cfg2's "mid" costmap cut to the points within 4 m of a robot that st
 straight tracked segment, P = 10 poses: a horizon of one second, in which the faster samples of a window reach the
 clutter and the slower ones do not (0 < admissible < n for the windows the tests draw).
 
-The model (point 11; csrc/kc_dwa.hip swap_in_pattern / upload_samples / build_perm).  A context holds one
+The model (point 11; csrc/kc_sample_pattern.h find_pattern, carried out by upload_samples / build_perm in
+csrc/kc_dwa.hip).  A context holds one
 ACTIVE set of index tables and walking orders and keeps those of up to pattern_slots(n) earlier window patterns, a
 pattern being (signature, sample count).  A window whose pattern is the active one changes nothing ("same").  One
 found among the kept patterns changes places with the active one ("hit", counter pattern_hits).  Any other one
