@@ -197,8 +197,12 @@ int kc_dwa_set_weights(kc_dwa *ctx, const kc_weights *w);
  *   "sensor_two_launch" (0) the sensor build of clouds beyond 32 k points (two launches) for every size
  *   "force_split"    (0) roll-out, collision and compaction as separate kernels
  *   "team_max"       (4) workgroups of the single-launch cycle with up to this many survivors cost them by teams
- *                        (halves / quarters of the workgroup, eight / four lanes a trajectory point); more: a
- *                        wavefront a sample.  0: always a wavefront a sample
+ *                        (R survivors: R teams of floor(16 / R) wavefronts, eight at most; a team's last place forms
+ *                        the obstacle term, the others hold every trajectory point at once, eight, four or two
+ *                        lanes a point, whichever is the widest that fits: csrc/kc_team_layout.h.  Trajectories
+ *                        of more than 64 points and cycles without an obstacle weight keep halves / quarters of
+ *                        the workgroup, eight / four lanes a point); more: a wavefront a sample.
+ *                        0: always a wavefront a sample
  * kc_dwa_get_option also reads "last_cycle_single_launch", "last_cycle_samples",
  * "host_threads", "trig_rows" (rows of the host's cos / sin table: distinct omegas of
  * this context's share), "shard_samples", and the counters "obs_near_rides" /

@@ -260,20 +260,21 @@ __device__ __forceinline__ uint32_t group8_min_u32(uint32_t v) {
   v = min(v, dpp_u32<0x141>(v));  // row_half_mirror
   return v;
 }
-// ... and inside each aligned group of kL = 4 or 8 lanes (quads need no third step)
+// ... and inside each aligned group of kL = 2, 4, 8 or 16 lanes (pairs need the first step only, quads no third)
 template <int kL>
 __device__ __forceinline__ uint32_t group_min_u32(uint32_t v) {
-  static_assert(kL == 4 || kL == 8 || kL == 16, "four, eight or sixteen lanes per group");
+  static_assert(kL == 2 || kL == 4 || kL == 8 || kL == 16, "two, four, eight or sixteen lanes per group");
   v = min(v, dpp_u32<0xB1>(v));   // quad_perm [1,0,3,2]
-  v = min(v, dpp_u32<0x4E>(v));   // quad_perm [2,3,0,1]
+  if (kL >= 4) v = min(v, dpp_u32<0x4E>(v));    // quad_perm [2,3,0,1]
   if (kL >= 8) v = min(v, dpp_u32<0x141>(v));   // row_half_mirror
   if (kL >= 16) v = min(v, dpp_u32<0x140>(v));  // row_mirror
   return v;
 }
 template <int kL>
 __device__ __forceinline__ uint32_t group_or_u32(uint32_t v) {
+  static_assert(kL == 2 || kL == 4 || kL == 8 || kL == 16, "two, four, eight or sixteen lanes per group");
   v |= dpp_u32<0xB1>(v);
-  v |= dpp_u32<0x4E>(v);
+  if (kL >= 4) v |= dpp_u32<0x4E>(v);
   if (kL >= 8) v |= dpp_u32<0x141>(v);
   if (kL >= 16) v |= dpp_u32<0x140>(v);
   return v;
@@ -432,13 +433,13 @@ __device__ __forceinline__ uint32_t pairs_min_bits(const Seg &seg, int k0, int k
 // query cell.  Leaves s_mind[P], *s_goal, *s_end and the sample-wide minimum in
 // *s_obest (armed by the caller, behind a barrier).  tid = lane id inside the team.
 // cap / sup (chunk capsules and super-chunk spheres): the pruned segment search;
-// null: the plain scan, eight lanes wide.
+// null: the plain scan, eight lanes wide (kPruned: cap is never null, no scan is compiled).
 template <class Seg, int kL>
 __device__ __forceinline__ void group_segment_search(const CostArgs &a, const Seg &seg, const float *cap,
                                                      const float *sup, float x, float y, int sub,
                                                      float &best_out, int &arg_out);
 
-template <int kTeam, class Seg, class Pts, int kL = 8>
+template <int kTeam, class Seg, class Pts, int kL = 8, bool kPruned = false>
 __device__ __forceinline__ void team_sample_search(const CostArgs &a, const Seg &seg, float sz_end,
                                                    const int *cells, const uint8_t *skip,
                                                    const float *obx, const float *oby, const Pts pts,
@@ -457,7 +458,7 @@ __device__ __forceinline__ void team_sample_search(const CostArgs &a, const Seg 
     if (a.use_seg) {
       float best = FLT_MAX;
       int arg = 0;
-      if (cap) {
+      if (kPruned || cap) {
         group_segment_search<Seg, kL>(a, seg, cap, sup, x, y, sub, best, arg);
       } else {
         const bool flat = a.seg_flat != 0;
@@ -581,7 +582,7 @@ __device__ __forceinline__ uint32_t group8_or_u32(uint32_t v) {
   return v;
 }
 
-// Nearest tracked-segment point of q = (x, y) by a group of kL (four or eight)
+// Nearest tracked-segment point of q = (x, y) by a group of kL (two, four or eight)
 // lanes (sub = lane id in the group) with the chunk hierarchy of
 // wave_sample_total spread over the lanes: (0) the heads of the (<= 8)
 // super-chunks, (1) their bounding spheres, (2) the heads of the chunks of the

@@ -14,12 +14,11 @@
 // visibility"), with no L2 write-back or invalidate on the critical path.
 #pragma once
 
+#include "kc_team_layout.h"  // kTeamMaxSurvivors, team_layout
+
 namespace kc {
 
 struct CycleTail;  // kc_rollout_kernels.h
-constexpr int kTeamMaxSurvivors = 4;  // one or two survivors: half the workgroup each, eight lanes per
-                                      // trajectory point; three or four: a quarter each, four lanes per
-                                      // point (one pass either way); more: one per wavefront
 
 // LDS layout of the cost tables behind tab_off (the host sizes it the same way:
 // cycle_table_bytes in kc_dwa_cycle.hip); every table starts on a 16-byte boundary
@@ -143,8 +142,8 @@ __device__ __forceinline__ void cycle_tables_store(const Tail &tail, unsigned ch
 }
 
 // Cost of the R survivors of this workgroup (slots lsurv[0..R), ascending).  Few
-// survivors: two at a time, half the workgroup each, eight lanes per point
-// (team_sample_search); many: one per wavefront, pulled from an LDS counter
+// survivors: all at once, a team of whole wavefronts each, eight, four or two lanes
+// per point (team_layout, team_sample_search); many: one per wavefront, pulled from an LDS counter
 // (wave_sample_total).  Same arithmetic as the stand-alone cost kernels.  Returns
 // the workgroup's best key (uniform) and the slot of that sample.
 template <int kSamples, int kBlock, class Tail>
@@ -174,40 +173,55 @@ __device__ __forceinline__ long long cycle_costs(const RollArgs &a, const Tail &
   const float *const woby = tail.t.onear != nullptr ? tail.t.osy : c.b.by;
   const bool teams = R <= tail.team_max;
   if (teams) {
-    // every survivor at once: R teams (two halves or four quarters of the workgroup)
-    const bool quarters = R > 2;
-    const int team = quarters ? kBlock / 4 : kBlock / 2;
-    const int h = tid / team, tt = tid - h * team;
+    // every survivor at once: R teams of W consecutive wavefronts, kL lanes per trajectory point (all wave-uniform)
+    static_assert(kBlock == 64 * kCycleWaves, "team_layout deals the sixteen wavefronts of the workgroup");
+    // The obstacle term of a team's sample is formed by the wavefront in the team's LAST place (team_wave_role), a lane
+    // a point, the way the wavefront-per-sample path forms it (wave_obstacle_term: near table of a scan / one scan of the
+    // union rectangle / cooperative ring walk) -- beside the segment search of the places in front of it, which hold every
+    // point of the sample in one pass (team_layout: that wavefront never holds a point, so the term is never serialised
+    // behind a share of the search).  The block walk a point apiece that the teams ran before took as many trips as the
+    // longest row of any point of a wavefront: quarters were 16 us late in clutter (cfg2, 38-step horizon).
+    // Trajectories of more than 64 points keep the walk, and they and the cycles without an obstacle term keep the
+    // halves (R <= 2, eight lanes per point) and quarters (four) in which every wavefront searches.
+    const bool wave_obs = c.use_obs && c.P <= 64;
+    const int Ru = __builtin_amdgcn_readfirstlane(R);
+    const TeamLayout lay = wave_obs ? team_layout(Ru, c.P) : (Ru > 2 ? TeamLayout{4, 4} : TeamLayout{8, 8});
+    const int W = lay.waves, kL = lay.lanes_per;
+    const int h = team_of_wave(W, wave);  // (at most 3)
+    const int wt = wave_obs ? team_wave_role(W, h, wave - h * W) : wave - h * W;  // its place in the team
+    const int tt = wt * 64 + lane;
     const bool active = h < R;
+#ifdef KC_PHASE_STAMPS
+    if (a.dbg && tid == 0 && blockIdx.x < 512) a.dbg[(size_t)blockIdx.x * 32 + 22] = static_cast<unsigned long long>(wave_obs ? W * 16 + kL : 0);
+#endif
     if (tt == 0) s_ob[h] = static_cast<unsigned long long>(__double_as_longlong(DBL_MAX));
     __syncthreads();  // (also s_key)
     const int s = active ? lsurv[h] : 0;
     const PosePts pts{lpos + s * PP, PP - 1};
-    // The obstacle term of a team's sample is formed by the team's LAST wavefront, a lane a point, the way the
-    // wavefront-per-sample path forms it (wave_obstacle_term: near table of a scan / one scan of the union rectangle /
-    // cooperative ring walk) -- beside the segment search of the other wavefronts when that wavefront holds no point of it
-    // (halves: 400 of 512 lanes search), behind its share otherwise (quarters).  The block walk a point apiece that the
-    // teams ran before took as many trips as the longest row of any point of a wavefront: quarters were 16 us late in
-    // clutter (cfg2, 38-step horizon).  Trajectories of more than 64 points keep the walk.
-    const bool wave_obs = c.use_obs && c.P <= 64;
-    const int lanes_per = quarters ? 4 : 8;
-    const bool last_wave = tt >= team - 64;
-    const bool holds_points = (team - 64) / lanes_per < c.P;  // (uniform: the last wavefront's first point slot)
-    if (active && !(wave_obs && last_wave && !holds_points)) {
-      if (quarters)
-        team_sample_search<kBlock / 4, SegPairs, PosePts, 4>(c, seg, sz_end, t.cells, t.skip, c.b.bx, c.b.by, pts, tt,
-                                                            t.mind + h * c.P, &s_goal[h], &s_end[h], &s_ob[h],
-                                                            t.cap, t.cap + 8 * c.nch, wave_obs);
-      else
-        team_sample_search<kBlock / 2, SegPairs, PosePts, 8>(c, seg, sz_end, t.cells, t.skip, c.b.bx, c.b.by, pts, tt,
-                                                            t.mind + h * c.P, &s_goal[h], &s_end[h], &s_ob[h],
-                                                            t.cap, t.cap + 8 * c.nch, wave_obs);
-    }
+    const bool last_wave = wt == W - 1;
+    // (a search wavefront of the layout whose point slots all lie beyond P has nothing to find)
+    const bool searches = wave_obs ? wt * 64 < c.P * kL : true;
     if (active && wave_obs && last_wave) {
       const bool live = lane < c.P;
       const int p = live ? lane : c.P - 1;
       double ubound2 = DBL_MAX;
       wave_obstacle_term(c, tail.t, t.cells, t.skip, wobx, woby, pts.x(p), pts.y(p), live, lane, &s_ob[h], ubound2);
+    } else if (active && searches) {
+      // one instance per group width, the pruned segment search always (kPruned: no plain scan in this kernel's code);
+      // 64 point slots a trip (the layout's single pass, P <= 64, or the trips of a
+      // longer trajectory through a half of eight or a quarter of four lanes per point)
+      if (kL == 8)
+        team_sample_search<64 * 8, SegPairs, PosePts, 8, true>(c, seg, sz_end, t.cells, t.skip, c.b.bx, c.b.by, pts, tt,
+                                                        t.mind + h * c.P, &s_goal[h], &s_end[h], &s_ob[h],
+                                                        t.cap, t.cap + 8 * c.nch, wave_obs);
+      else if (kL == 4)
+        team_sample_search<64 * 4, SegPairs, PosePts, 4, true>(c, seg, sz_end, t.cells, t.skip, c.b.bx, c.b.by, pts, tt,
+                                                        t.mind + h * c.P, &s_goal[h], &s_end[h], &s_ob[h],
+                                                        t.cap, t.cap + 8 * c.nch, wave_obs);
+      else
+        team_sample_search<64 * 2, SegPairs, PosePts, 2, true>(c, seg, sz_end, t.cells, t.skip, c.b.bx, c.b.by, pts, tt,
+                                                        t.mind + h * c.P, &s_goal[h], &s_end[h], &s_ob[h],
+                                                        t.cap, t.cap + 8 * c.nch, true);  // (only the layout deals two)
     }
     KC_RSTAMP(10);
     __syncthreads();
@@ -223,6 +237,9 @@ __device__ __forceinline__ long long cycle_costs(const RollArgs &a, const Tail &
     }
     KC_RSTAMP(12);
   } else {
+#ifdef KC_PHASE_STAMPS
+    if (a.dbg && tid == 0 && blockIdx.x < 512) a.dbg[(size_t)blockIdx.x * 32 + 22] = 0ull;  // no team layout
+#endif
     __syncthreads();  // s_next, s_key
     const float *cap = t.cap, *sup = t.cap + 8 * c.nch;
     long long wkey = KEY_NONE;

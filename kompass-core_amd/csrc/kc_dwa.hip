@@ -371,16 +371,26 @@ static void dump_diagnostics(kc_dwa *c) {
         ++cost_hist[std::min(std::max(d, 0), 63)];
       }
       {  // the cost phase by the number of survivors of the workgroup
-        double sum[34] = {0}, mx[34] = {0};
-        int cnt[34] = {0};
+        double sum[34] = {0}, mx[34] = {0}, part[34][3] = {{0}};
+        int cnt[34] = {0}, lay[34] = {0};  // lay: the team layout the kernel recorded (slot 22: wavefronts * 16 + lanes per point)
         for (int b = 0; b < 512; ++b) {
           if (!h[b * 32] || !h[b * 32 + 8] || !h[b * 32 + 6] || !h[b * 32 + 21]) continue;
           const int R = std::min<int>(static_cast<int>(h[b * 32 + 21]) - 1, 33);
           const double d = (h[b * 32 + 8] - h[b * 32 + 6]) / 100.0;
           sum[R] += d; mx[R] = std::max(mx[R], d); ++cnt[R];
+          lay[R] = static_cast<int>(h[b * 32 + 22]);
+          for (int k = 0; k < 3; ++k)  // thread 0's search, the barrier behind it, the totals: since `flags out`
+            if (h[b * 32 + 10 + k]) part[R][k] += (h[b * 32 + 10 + k] - h[b * 32 + 6]) / 100.0;
         }
-        std::fprintf(stderr, "  cost phase by survivors of the workgroup, survivors:workgroups avg/max us:");
-        for (int R = 0; R < 34; ++R) if (cnt[R]) std::fprintf(stderr, " %d:%d %.1f/%.1f", R, cnt[R], sum[R] / cnt[R], mx[R]);
+        std::fprintf(stderr, "  cost phase by survivors of the workgroup, survivors:workgroups avg/max us [wavefronts per team x lanes per point]:");
+        for (int R = 0; R < 34; ++R) {
+          if (!cnt[R]) continue;
+          std::fprintf(stderr, " %d:%d %.1f/%.1f", R, cnt[R], sum[R] / cnt[R], mx[R]);
+          if (R > 0 && lay[R]) std::fprintf(stderr, " [%dx%d]", lay[R] / 16, lay[R] % 16);
+        }
+        std::fprintf(stderr, "\n  ... of which up to pass 0 searched / barrier / total (avg us), survivors:");
+        for (int R = 0; R < 34; ++R)
+          if (cnt[R]) std::fprintf(stderr, " %d: %.1f/%.1f/%.1f", R, part[R][0] / cnt[R], part[R][1] / cnt[R], part[R][2] / cnt[R]);
         std::fprintf(stderr, "\n");
       }
       std::fprintf(stderr, "  workgroups by end of epilogue (us):");
