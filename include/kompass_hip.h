@@ -1728,6 +1728,111 @@ int kc_mcl_resample_inject(kc_mcl *ctx, size_t n_inject);
  * kc_mcl_times' last two.  KC_ERR_STATE when none was timed. */
 int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
 
+/* ------------------------------------------------------------------------ */
+/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 12) */
+/* ------------------------------------------------------------------------ */
+/* Nothing in the reference to cite: its controllers commit to one velocity for the whole
+ * look-ahead.  K noisy control sequences of T steps around a nominal one, rolled out in the
+ * localiser's integers, costed against the distance plane and a window of path points, blended
+ * by table weights.  Integers throughout, exact sums: no result depends on thread order,
+ * tests/mppi_ref.py states every rule in Python ints and the device equals it bit for bit.  No
+ * kernel modifies the map; the context keeps no sequence between calls (the warm start is the
+ * caller's).  "Rule 28 .. 45" below are 4.11's, above.
+ * Rule 1, state: (TX, TY, h) as rule 28: int64 with 16 fraction bits of a cell, clamped to
+ * +-2^36; h in 2^-16 turn.  Its cell: I = (TX + 2^15) >> 16, J alike (cell (0, 0)'s centre is
+ * the origin).
+ * Rule 2, control sequence: U[t] = (F, L, H), int32, t < T, 1 <= T <= 64.  F: the forward
+ * displacement a step, L the lateral one, 2^-16 cells; H: the heading change a step, heading
+ * units.  Limits F_lo <= F <= F_hi, |L| <= L_hi, |H| <= H_hi with |F_lo|, |F_hi|, L_hi <= 2^22,
+ * H_hi <= 32767.  The cone kq, 0 <= kq <= 2^24: when kq > 0 also |H| <= (|F| kq) >> 16 (a
+ * car: a front end forms kq = lrint(65536 / (2 pi R_min_cells))).  clampU(F, L, H) applies the
+ * box, then the cone with the clamped F.
+ * Rule 3, samples: 1 <= K <= 65536.  key = mix64(seed ^ (step << 32)), step the call's.  For
+ * sample k, step t, channel c in 0 .. 2: eps = noise(mix64(key ^ ((k << 8) | (3 t + c))), s_c),
+ * rule 30's mix64 and noise, s_c >= 0; sample 0 has eps = 0, so the nominal sequence is among
+ * the samples.  X_k[t] = clampU(U[t] + eps).
+ * Rule 4, roll-out: rule 31 without its noise.  With (C, S) = (Cq(h), Sq(h)) of the heading
+ * before the step: TX += (C F - S L + 2^15) >> 16, TY += (S F + C L + 2^15) >> 16, both
+ * clamped, h = (h + H) & 0xFFFF.
+ * Rule 5, obstacle term, at the state after each step t: d2 = dist2[I + J W] inside the map,
+ * FAR outside (rule 45).  d2 <= r2: the sample has hit; it adds pen_hit (T - t), its state is
+ * frozen and its later steps add nothing from rules 5 and 6.  Otherwise it adds d2 <= c2 ?
+ * pen_d2[d2] : pen_far.  pen_d2: c2 + 1 uint16 entries, 1 <= c2 <= min(reach^2, 4095), r2 <=
+ * c2, pen_hit <= 2^20.
+ * Rule 6, path term, the same states, samples that have not hit: M points (PX_j, PY_j) in the
+ * state's units, 1 <= M <= 256, |PX|, |PY| <= 2^36.  q_j = ((TX - PX_j) >> 8)^2 + ((TY - PY_j)
+ * >> 8)^2 (q >> 16 is cells^2), key_j = (min(q_j, qcap) << 8) | j; the smallest key gives qm
+ * and jm: the lowest index among equals, equals at the cap included.  It adds (qm w_path) >>
+ * 16.  qcap <= 2^40, w_path <= 2^16, (qcap >> 16) w_path <= 2^24.
+ * Rule 7, terminal term: w_goal (M - 1 - jm), jm of the last state rule 6 saw, 0 for a sample
+ * that hit at step 0; w_goal <= 2^20.
+ * Rule 8, total: the terms summed in 64 bits, S_k = min(sum, 2^30).  S_min the smallest,
+ * k_best the lowest index with it.
+ * Rule 9, weights: w_k = wtab[min((S_k - S_min) >> w_shift, EW - 1)], wtab as rule 36's: the
+ * best sample's weight is wtab[0] >= 1.
+ * Rule 10, update: den = sum_k w_k; for every t and channel num = sum_k w_k (X_k[t][c] -
+ * U[t][c]), exact in int64 (2^20 2^23 2^16); U'[t][c] = U[t][c] + floor((2 num + den) / (2
+ * den)), then clampU.
+ * Rule 11, record: kc_mppi_record.
+ * Rule 12, refusals: kc_mppi_check (host only, needs no device), in this order: KC_ERR_INVALID
+ * for no sample, no step or no path point; KC_ERR_RANGE above 65536 samples, then above 64
+ * steps, then above 256 path points; limits (skipped when NULL; five words F_lo, F_hi, L_hi,
+ * H_hi, kq): KC_ERR_INVALID for F_lo > F_hi or a negative L_hi, H_hi or kq, KC_ERR_RANGE for a
+ * displacement limit beyond 2^22, then H_hi above 32767, then kq above 2^24, KC_ERR_INVALID for
+ * s NULL or a negative scale; costs (skipped when pen_d2 is NULL): KC_ERR_INVALID below 2
+ * entries, KC_ERR_RANGE above 4096, KC_ERR_INVALID for r2 > c2, KC_ERR_RANGE for pen_hit above
+ * 2^20, w_path above 2^16, qcap above 2^40, (qcap >> 16) w_path above 2^24, w_goal above 2^20,
+ * in that order; reach (skipped when 0): KC_ERR_RANGE outside 1 .. 254, KC_ERR_INVALID for c2 >
+ * reach^2; then wtab as kc_mcl_check has it (KC_ERR_INVALID when NULL). */
+typedef struct kc_mppi kc_mppi;
+#define KC_MPPI_MAX_SAMPLES 65536
+#define KC_MPPI_MAX_HORIZON 64
+#define KC_MPPI_MAX_PATH 256
+#define KC_MPPI_MAX_TABLE 4096
+typedef struct kc_mppi_record { /* rule 11 */
+  uint64_t den;                 /* sum of the weights */
+  uint32_t s_min, k_best;       /* rule 8 */
+  uint32_t s_0;                 /* the nominal sequence's cost */
+  uint32_t n_hit;               /* samples that hit */
+  uint32_t step;                /* the call's */
+  uint32_t reserved;            /* 0 */
+} kc_mppi_record;
+int kc_mppi_check(size_t n_samples, size_t horizon, size_t n_path, const int32_t *limits_or_null, const int32_t *s_or_null, uint32_t r2,
+                  const uint16_t *pen_d2_or_null, size_t n_pen, uint32_t pen_hit, uint32_t w_path, uint64_t qcap, uint32_t w_goal,
+                  int reach, const uint32_t *wtab_or_null, size_t n_wtab, int w_shift);
+/* A controller of n_samples sequences of `horizon` steps over `map`, on its device, with its
+ * own stream; the map must outlive it.  Checks: null arguments, kc_mppi_check's counts, then
+ * the device. */
+int kc_mppi_create(kc_worldmap *map, size_t n_samples, size_t horizon, uint64_t seed, kc_mppi **out);
+void kc_mppi_destroy(kc_mppi *ctx);
+/* rule 2's limits and rule 3's three scales, checked as kc_mppi_check does */
+int kc_mppi_set_model(kc_mppi *ctx, int32_t f_lo, int32_t f_hi, int32_t l_hi, int32_t h_hi, int32_t kq, const int32_t *s);
+/* rules 5 to 9's tables and scalars, checked as kc_mppi_check does with reach 0 */
+int kc_mppi_set_costs(kc_mppi *ctx, uint32_t r2, const uint16_t *pen_d2, size_t n_pen, uint16_t pen_far, uint32_t pen_hit, uint32_t w_path,
+                      uint64_t qcap, uint32_t w_goal, const uint32_t *wtab, size_t n_wtab, int w_shift);
+/* rule 6's window, in the map's present offset (rule 46): KC_ERR_INVALID for none, KC_ERR_RANGE
+ * above 256 points or for a coordinate beyond +-2^36 */
+int kc_mppi_set_path(kc_mppi *ctx, const int64_t *px, const int64_t *py, size_t n);
+/* One step (rules 3 to 11): two launches (mppi_rollout_kernel, mppi_update_kernel) behind the
+ * plane's refresh and an event on the map's stream, and one read-back of U' and the record;
+ * returns with both final.  u_in, u_out: T x 3 int32 (F, L, H a step); they may be one array.
+ * Checks, in this order: null arguments; KC_ERR_STATE without a model, then without costs,
+ * then without a path; KC_ERR_RANGE for |tx|, |ty| > 2^36, then h > 65535, then a control of
+ * u_in outside +-2^22, +-2^22, +-32767; KC_ERR_STATE while the map's distance plane is off or
+ * c2 > reach^2; then the device.  A refused call queues nothing. */
+int kc_mppi_step(kc_mppi *ctx, int64_t tx, int64_t ty, uint32_t h, const int32_t *u_in, uint32_t step, int32_t *u_out,
+                 kc_mppi_record *record);
+/* all S_k of the last step, for tests and plots; cap: the entries s_out holds (KC_ERR_RANGE
+ * below K); KC_ERR_STATE before a step */
+int kc_mppi_costs(kc_mppi *ctx, uint32_t *s_out, size_t cap);
+/* Measurement only (no result depends on it): the lanes that share a sample in the roll-out, 1,
+ * 4 or 8; the default is what DESIGN.md 4.12 measured as the faster.  KC_ERR_INVALID otherwise. */
+int kc_mppi_set_team(kc_mppi *ctx, int lanes);
+/* HIP-event times in milliseconds of the last step's two launches (rollout, update), recorded
+ * only while enabled.  KC_ERR_STATE when no step was timed. */
+int kc_mppi_set_timing(kc_mppi *ctx, int enable);
+int kc_mppi_times(kc_mppi *ctx, float ms_out[2]);
+
 #ifdef __cplusplus
 }
 #endif

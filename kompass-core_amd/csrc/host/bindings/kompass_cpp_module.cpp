@@ -13,6 +13,7 @@
 #include "controllers/pure_pursuit.h"
 #include "controllers/rgb_follower.h"
 #include "controllers/rgbd_follower.h"
+#include "controllers/mppi.h"
 #include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
 #include "mapping/mcl.h"
@@ -764,6 +765,72 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def("compute_velocity_commands", &Control::Stanley::computeVelocityCommand)
       .def("execute", &Control::Stanley::execute)
       .def("set_robot_wheelbase", &Control::Stanley::setWheelBase);
+
+  // MPPI over a WorldMap's distance plane (not in the reference)
+  {
+    using MPPI = Control::MPPI;
+    py::class_<MPPI::Config>(c, "MPPIConfig")
+        .def(py::init<>())
+        .def_readwrite("samples", &MPPI::Config::samples)
+        .def_readwrite("horizon", &MPPI::Config::horizon)
+        .def_readwrite("window", &MPPI::Config::window)
+        .def_readwrite("sigma_forward", &MPPI::Config::sigma_forward)
+        .def_readwrite("sigma_lateral", &MPPI::Config::sigma_lateral)
+        .def_readwrite("sigma_turn", &MPPI::Config::sigma_turn)
+        .def_readwrite("lambda_", &MPPI::Config::lambda)
+        .def_readwrite("w_shift", &MPPI::Config::w_shift)
+        .def_readwrite("n_w", &MPPI::Config::n_w)
+        .def_readwrite("hit_radius", &MPPI::Config::hit_radius)
+        .def_readwrite("clearance", &MPPI::Config::clearance)
+        .def_readwrite("clearance_weight", &MPPI::Config::clearance_weight)
+        .def_readwrite("pen_far", &MPPI::Config::pen_far)
+        .def_readwrite("pen_hit", &MPPI::Config::pen_hit)
+        .def_readwrite("w_path", &MPPI::Config::w_path)
+        .def_readwrite("w_goal", &MPPI::Config::w_goal)
+        .def_readwrite("path_cap", &MPPI::Config::path_cap)
+        .def_readwrite("reach", &MPPI::Config::reach)
+        .def_readwrite("allow_reverse", &MPPI::Config::allow_reverse)
+        .def_readwrite("min_turning_radius", &MPPI::Config::min_turning_radius)
+        .def_readwrite("seed", &MPPI::Config::seed);
+    py::class_<MPPI, Control::Follower>(c, "MPPI")
+        .def(py::init<Control::ControlType, const Control::ControlLimitsParams &, double, const MPPI::Config &>(),
+             py::arg("control_type"), py::arg("control_limits"), py::arg("time_step"), py::arg("config") = MPPI::Config())
+        .def("execute", &MPPI::execute, py::arg("world_map"), py::arg("current_position"),
+             "One MPPI step over the world map's distance plane: two launches and one read-back")
+        .def("reset_sequence", &MPPI::resetSequence)
+        .def("set_follower_params", [](MPPI &m, const Control::Follower::FollowerParameters &p) { m.setParams(p); }, py::arg("params"),
+             "the Follower's own parameters: goal tolerances, interpolation and segment lengths")
+        .def("controls", &MPPI::controls, py::arg("n"), "the first n controls of the new sequence as (vx, vy, omega)")
+        .def("predicted_path", &MPPI::predictedPath, "the new sequence rolled out on the host: (x, y, yaw) after each step")
+        .def("sample_costs", &MPPI::sampleCosts)
+        .def_property_readonly("last_sequence", &MPPI::lastSequence)
+        .def_property_readonly("last_record", [](const MPPI &m) {
+               const kc_mppi_record &r = m.lastRecord();
+               return py::make_tuple(r.s_min, r.k_best, r.s_0, r.den, r.n_hit, r.step);
+             }, "(s_min, k_best, s_0, den, n_hit, step) of the last step")
+        .def_property_readonly("last_inputs", [](const MPPI &m) {
+               const MPPI::Inputs &i = m.lastInputs();
+               py::dict d;
+               d["tx"] = i.tx;
+               d["ty"] = i.ty;
+               d["h"] = i.h;
+               d["step"] = i.step;
+               d["px"] = i.px;
+               d["py"] = i.py;
+               d["u"] = i.u;
+               return d;
+             }, "the last step's inputs as the device took them")
+        .def_static("quantise", [](Control::ControlType type, const Control::ControlLimitsParams &lim, double dt, float res,
+                                   const MPPI::Config &cfg) {
+               const MPPI::Quantised q = MPPI::quantise(type, lim, dt, res, cfg);
+               return py::make_tuple(q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq, q.s);
+             }, py::arg("control_type"), py::arg("control_limits"), py::arg("time_step"), py::arg("resolution"), py::arg("config"),
+             "(F_lo, F_hi, L_hi, H_hi, kq, s[3]): host only")
+        .def_static("costs_of", [](const MPPI::Config &cfg) {
+               const MPPI::Costs t = MPPI::costsOf(cfg);
+               return py::make_tuple(t.r2, t.pen_d2, t.pen_far, t.pen_hit, t.w_path, t.qcap, t.w_goal, t.wtab, t.w_shift);
+             }, py::arg("config"), "(r2, pen_d2, pen_far, pen_hit, w_path, qcap, w_goal, wtab, w_shift): host only");
+  }
 
   // PurePursuit (bindings_control.cpp:159-207)
   using PP = Control::PurePursuit;

@@ -1,0 +1,106 @@
+// MPPI path follower over a WorldMap's distance plane (kc_mppi_*, csrc/kc_mppi.hip).
+//
+// Nothing in the reference to restate: its controllers commit to one velocity for the whole look-ahead.  The samples,
+// their roll-outs and the blend run on the device in the ABI's integers; this class does the doubles at both ends.  It
+// quantises the limits, the sigmas, the pose and the path window once each, keeps the nominal sequence between steps
+// (the warm start: shifted by one after every step) and turns the first control of the new sequence into a command.
+// Path, closest point and goal test are the Follower's.
+#pragma once
+
+#include <array>
+#include <cstdint>
+#include <vector>
+
+#include "controllers/follower.h"
+#include "mapping/world_map.h"
+#include "utils/hip_backend.h"
+
+namespace Kompass {
+namespace Control {
+
+// Judgement, not measurement: the values of the closed-loop scene of DESIGN.md 4.12, which nobody has tuned on a robot.
+// Lengths are in cells of the map, a step is the control time step.
+struct MPPIConfig {
+  size_t samples = 1024, horizon = 32, window = 96;  // K, T, M
+  double sigma_forward = 0.5, sigma_lateral = 0.5;   // cells a step (lateral: OMNI only)
+  double sigma_turn = 500.0 / 65536.0 * 2.0 * M_PI;  // radians a step
+  double lambda = 64.0;                              // temperature: wtab[i] = lrint(65535 exp(-(i << w_shift) / lambda))
+  int w_shift = 2, n_w = 256;
+  double hit_radius = 3.0;                           // cells: r2 = lrint(hit_radius^2)
+  double clearance = 7.0;                            // cells: c2 = lrint(clearance^2)
+  double clearance_weight = 60.0;                    // pen_d2[d] = lrint(weight max(0, 1 - sqrt(d) / clearance))
+  uint16_t pen_far = 0;
+  uint32_t pen_hit = 4000, w_path = 8, w_goal = 20;
+  double path_cap = 20.0;                            // cells: qcap = lrint(path_cap^2) << 16
+  int reach = 8;                                     // the plane's reach when this class has to enable it
+  bool allow_reverse = false;                        // F_lo = -F_hi instead of 0
+  double min_turning_radius = 0.5;                   // metres, ACKERMANN only: kq = lrint(65536 / (2 pi R / resolution))
+  uint64_t seed = 0;
+};
+
+class MPPI : public Follower {
+ public:
+  using Config = MPPIConfig;
+  struct Quantised {  // what a step hands to kc_mppi_set_model
+    int32_t f_lo = 0, f_hi = 0, l_hi = 0, h_hi = 0, kq = 0;
+    std::array<int32_t, 3> s = {0, 0, 0};
+  };
+  struct Costs {  // ... and to kc_mppi_set_costs
+    uint32_t r2 = 0;
+    std::vector<uint16_t> pen_d2;
+    uint16_t pen_far = 0;
+    uint32_t pen_hit = 0, w_path = 0;
+    uint64_t qcap = 0;
+    uint32_t w_goal = 0;
+    std::vector<uint32_t> wtab;
+    int w_shift = 0;
+  };
+  struct Inputs {  // the last step's, as the device took them
+    int64_t tx = 0, ty = 0;
+    uint32_t h = 0, step = 0;
+    std::vector<int64_t> px, py;
+    std::vector<int32_t> u;  // T x 3
+  };
+
+  MPPI(ControlType type, const ControlLimitsParams &limits, double time_step, const Config &config = Config());
+
+  // One step at the robot's state over `map` (which must outlive the controller's use of it).  The map's distance plane
+  // is enabled at config.reach when it is off or too short for the clearance; the map's cells are not changed.
+  Controller::Result execute(const Mapping::WorldMap &map, const Path::State &state);
+  void resetSequence();
+
+  const Config &mppiConfig() const { return cfg_; }
+  double timeStep() const { return dt_; }
+  const Inputs &lastInputs() const { return in_; }
+  const std::vector<int32_t> &lastSequence() const { return out_; }  // U' of the last step, T x 3
+  const kc_mppi_record &lastRecord() const { return rec_; }
+  // the first n controls of U' as velocities (vx, vy, omega each)
+  std::vector<std::array<double, 3>> controls(size_t n) const;
+  // U' rolled out on the host by rule 4 from the last step's pose: (x, y, yaw) in the world after each step
+  std::vector<std::array<double, 3>> predictedPath() const;
+  std::vector<uint32_t> sampleCosts() const;
+  kc_mppi *hipContext() const { return ctx_.get(); }
+
+  // ---- the host side's arithmetic, static: needs no device ----
+  static Quantised quantise(ControlType type, const ControlLimitsParams &limits, double time_step, float resolution, const Config &c);
+  static Costs costsOf(const Config &c);
+
+ private:
+  using Handle = hip::Handle<kc_mppi, kc_mppi_destroy>;
+  Config cfg_;
+  double dt_;
+  Handle ctx_;
+  const kc_worldmap *bound_ = nullptr;  // the map ctx_ was made over
+  float res_ = 0.0f;
+  double ox_ = 0.0, oy_ = 0.0;          // the origin the last step quantised against
+  std::vector<int32_t> u_, out_;
+  uint32_t step_ = 0;
+  Inputs in_;
+  kc_mppi_record rec_ = {};
+
+  void bind(const Mapping::WorldMap &map);
+  void buildWindow(const Mapping::WorldMap &map);
+};
+
+}  // namespace Control
+}  // namespace Kompass

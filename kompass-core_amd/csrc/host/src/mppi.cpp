@@ -1,0 +1,211 @@
+// MPPI host side: the doubles around kc_mppi_* (no reference counterpart, see the header).
+#include "controllers/mppi.h"
+
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
+
+#include "mapping/mcl.h"
+
+namespace Kompass {
+namespace Control {
+
+namespace {
+constexpr double kTwoPi = 2.0 * M_PI;
+
+int32_t quantiseLimit(double v, double cap, const char *what) {
+  if (!std::isfinite(v) || v < 0.0) throw std::invalid_argument(std::string(what) + " is negative or not finite");
+  return static_cast<int32_t>(std::llrint(std::min(v, cap)));
+}
+}  // namespace
+
+MPPI::MPPI(ControlType type, const ControlLimitsParams &limits, double time_step, const Config &config)
+    : Follower(), cfg_(config), dt_(time_step) {
+  if (!(time_step > 0.0) || !std::isfinite(time_step)) throw std::invalid_argument("the control time step must be positive");
+  setControlType(type);
+  setLinearControlLimits(limits.velXParams, limits.velYParams);
+  setAngularControlLimits(limits.omegaParams);
+  const Costs c = costsOf(cfg_);  // refuses a bad configuration before a device is looked for
+  hip::check(kc_mppi_check(cfg_.samples, cfg_.horizon, cfg_.window, nullptr, nullptr, c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_hit,
+                           c.w_path, c.qcap, c.w_goal, cfg_.reach, c.wtab.data(), c.wtab.size(), c.w_shift));
+  resetSequence();
+}
+
+void MPPI::resetSequence() {
+  u_.assign(cfg_.horizon * 3, 0);
+  out_.clear();
+  step_ = 0;
+}
+
+MPPI::Quantised MPPI::quantise(ControlType type, const ControlLimitsParams &limits, double time_step, float resolution, const Config &c) {
+  const double r = static_cast<double>(resolution);
+  if (!(r > 0.0) || !std::isfinite(r)) throw std::invalid_argument("the resolution must be positive");
+  Quantised q;
+  const double cap = 4194304.0;  // rule 2's 2^22
+  q.f_hi = quantiseLimit(limits.velXParams.maxVel * time_step / r * 65536.0, cap, "the forward limit");
+  q.f_lo = c.allow_reverse ? -q.f_hi : 0;
+  q.l_hi = type == ControlType::OMNI ? quantiseLimit(limits.velYParams.maxVel * time_step / r * 65536.0, cap, "the lateral limit") : 0;
+  q.h_hi = quantiseLimit(limits.omegaParams.maxOmega * time_step / kTwoPi * 65536.0, 32767.0, "the turn limit");
+  if (type == ControlType::ACKERMANN) {
+    if (!(c.min_turning_radius > 0.0)) throw std::invalid_argument("the turning radius must be positive");
+    q.kq = quantiseLimit(65536.0 / (kTwoPi * c.min_turning_radius / r), 16777216.0, "the turning cone");
+  }
+  q.s = {Mapping::MCL::noiseScale(c.sigma_forward * 65536.0),
+         type == ControlType::OMNI ? Mapping::MCL::noiseScale(c.sigma_lateral * 65536.0) : 0,
+         Mapping::MCL::noiseScale(c.sigma_turn / kTwoPi * 65536.0)};
+  return q;
+}
+
+MPPI::Costs MPPI::costsOf(const Config &c) {
+  if (!(c.hit_radius >= 0.0) || !(c.clearance >= 1.0) || !(c.clearance <= 63.0) || !(c.hit_radius <= c.clearance) ||
+      !(c.clearance_weight >= 0.0) || !(c.clearance_weight <= 65535.0) || !(c.lambda > 0.0) || c.n_w < 1 || c.w_shift < 0 ||
+      c.w_shift > 30 || !(c.path_cap >= 0.0) || !(c.path_cap <= 1024.0))
+    throw std::invalid_argument("MPPI configuration out of range");
+  Costs t;
+  t.r2 = static_cast<uint32_t>(std::llrint(c.hit_radius * c.hit_radius));
+  const int c2 = static_cast<int>(std::llrint(c.clearance * c.clearance));
+  for (int d = 0; d <= c2; ++d)
+    t.pen_d2.push_back(static_cast<uint16_t>(
+        std::nearbyint(c.clearance_weight * std::max(0.0, 1.0 - std::sqrt(static_cast<double>(d)) / c.clearance))));
+  t.pen_far = c.pen_far;
+  t.pen_hit = c.pen_hit;
+  t.w_path = c.w_path;
+  t.qcap = static_cast<uint64_t>(std::llrint(c.path_cap * c.path_cap)) << 16;
+  t.w_goal = c.w_goal;
+  t.w_shift = c.w_shift;
+  for (int i = 0; i < c.n_w; ++i)
+    t.wtab.push_back(static_cast<uint32_t>(
+        std::nearbyint(65535.0 * std::exp(-static_cast<double>(static_cast<int64_t>(i) << c.w_shift) / c.lambda))));
+  return t;
+}
+
+void MPPI::bind(const Mapping::WorldMap &map) {
+  const Costs c = costsOf(cfg_);
+  const int c2 = static_cast<int>(c.pen_d2.size()) - 1;
+  // The map is the caller's: the const reference is a promise not to change its cells, which holds
+  const int have = map.distanceReach();
+  if (have == 0 || have * have < c2) hip::check(kc_worldmap_set_distance(map.hipContext(), std::max(cfg_.reach, have), 0u));
+  if (bound_ == map.hipContext() && ctx_) return;
+  ctx_ = hip::make<Handle>(kc_mppi_create, map.hipContext(), cfg_.samples, cfg_.horizon, cfg_.seed);
+  bound_ = map.hipContext();
+  hip::check(kc_mppi_set_costs(ctx_.get(), c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_far, c.pen_hit, c.w_path, c.qcap, c.w_goal,
+                               c.wtab.data(), c.wtab.size(), c.w_shift));
+}
+
+// From the follower's closest point forward at one-cell arc spacing, up to M points; the path's end closes a window that
+// reaches it.  Quantised against the map's present origin.
+void MPPI::buildWindow(const Mapping::WorldMap &map) {
+  in_.px.clear();
+  in_.py.clear();
+  const Path::Path &p = *on_.path;
+  const size_t n = p.getSize();
+  size_t i = std::min<size_t>(on_.nearest->index, n - 1);
+  const double cell = static_cast<double>(res_);
+  auto push = [&](double x, double y) {
+    const kc_worldmap_pose q = Mapping::WorldMap::quantisePose(res_, ox_, oy_, x, y, 0.0);
+    in_.px.push_back(q.tx);
+    in_.py.push_back(q.ty);
+  };
+  double x = p.getIndex(i).x(), y = p.getIndex(i).y();
+  push(x, y);
+  double need = cell;  // arc length still to walk to the next point
+  while (in_.px.size() < cfg_.window && i + 1 < n) {
+    const double nx = p.getIndex(i + 1).x(), ny = p.getIndex(i + 1).y();
+    const double d = std::hypot(nx - x, ny - y);
+    if (d < need) {
+      need -= d;
+      x = nx;
+      y = ny;
+      ++i;
+      if (i + 1 == n) push(x, y);  // the end itself
+      continue;
+    }
+    const double f = d > 0.0 ? need / d : 0.0;
+    x += (nx - x) * f;
+    y += (ny - y) * f;
+    push(x, y);
+    need = cell;
+  }
+  (void)map;
+}
+
+Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State &state) {
+  setCurrentState(state);
+  if (!on_.ready || !on_.path || on_.path->getSize() == 0)
+    return {(on_.at_goal ? Result::Status::GOAL_REACHED : Result::Status::NO_COMMAND_POSSIBLE), {0.0, 0.0, 0.0}};
+  if (isGoalReached()) {
+    command_ = Velocity2D(0.0, 0.0, 0.0);
+    return {Result::Status::GOAL_REACHED, command_};
+  }
+  bind(map);
+  res_ = map.resolution();
+  ox_ = map.originX();
+  oy_ = map.originY();
+  const Quantised q = quantise(drive_, limits_, dt_, res_, cfg_);
+  hip::check(kc_mppi_set_model(ctx_.get(), q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq, q.s.data()));
+  aimAtTarget();
+  on_.segment = on_.target->segment_index;
+  on_.along = on_.target->position_in_segment;
+  buildWindow(map);
+  hip::check(kc_mppi_set_path(ctx_.get(), in_.px.data(), in_.py.data(), in_.px.size()));
+  const kc_worldmap_pose pose = Mapping::WorldMap::quantisePose(res_, ox_, oy_, state.x, state.y, state.yaw);
+  in_.tx = pose.tx;
+  in_.ty = pose.ty;
+  in_.h = Mapping::MCL::quantiseHeading(state.yaw);
+  in_.step = step_;
+  in_.u = u_;
+  out_.assign(cfg_.horizon * 3, 0);
+  hip::check(kc_mppi_step(ctx_.get(), in_.tx, in_.ty, in_.h, in_.u.data(), in_.step, out_.data(), &rec_));
+  ++step_;
+  // the warm start: U[t] = U'[t + 1], the last entry repeated
+  const size_t T = cfg_.horizon;
+  for (size_t t = 0; t + 1 < T; ++t)
+    for (int c = 0; c < 3; ++c) u_[3 * t + c] = out_[3 * (t + 1) + c];
+  for (int c = 0; c < 3; ++c) u_[3 * (T - 1) + c] = out_[3 * (T - 1) + c];
+  const std::array<double, 3> v = controls(1)[0];
+  const auto &lx = limits_.velXParams;
+  const auto &ly = limits_.velYParams;
+  const auto &lw = limits_.omegaParams;
+  command_ = Velocity2D(restrictVelocityTolimits(command_.vx(), v[0], lx.maxAcceleration, lx.maxDeceleration, lx.maxVel, dt_),
+                        restrictVelocityTolimits(command_.vy(), v[1], ly.maxAcceleration, ly.maxDeceleration, ly.maxVel, dt_),
+                        restrictVelocityTolimits(command_.omega(), v[2], lw.maxAcceleration, lw.maxDeceleration, lw.maxOmega, dt_));
+  return {Result::Status::COMMAND_FOUND, command_};
+}
+
+std::vector<std::array<double, 3>> MPPI::controls(size_t n) const {
+  std::vector<std::array<double, 3>> out;
+  const double r = static_cast<double>(res_);
+  for (size_t t = 0; t < n && 3 * t + 2 < out_.size(); ++t)
+    out.push_back({static_cast<double>(out_[3 * t]) / 65536.0 * r / dt_, static_cast<double>(out_[3 * t + 1]) / 65536.0 * r / dt_,
+                   static_cast<double>(out_[3 * t + 2]) / 65536.0 * kTwoPi / dt_});
+  return out;
+}
+
+std::vector<std::array<double, 3>> MPPI::predictedPath() const {
+  std::vector<std::array<double, 3>> out;
+  int64_t tx = in_.tx, ty = in_.ty;
+  uint32_t h = in_.h;
+  const int64_t cap = int64_t{1} << 36;
+  const double r = static_cast<double>(res_);
+  for (size_t t = 0; 3 * t + 2 < out_.size(); ++t) {
+    int32_t C = 0, S = 0;
+    hip::check(kc_mcl_heading(h, &C, &S));
+    const int64_t F = out_[3 * t], L = out_[3 * t + 1];
+    tx = std::max(-cap, std::min(cap, tx + ((C * F - S * L + (int64_t{1} << 15)) >> 16)));
+    ty = std::max(-cap, std::min(cap, ty + ((S * F + C * L + (int64_t{1} << 15)) >> 16)));
+    h = static_cast<uint32_t>((static_cast<int64_t>(h) + out_[3 * t + 2]) & 0xFFFF);
+    out.push_back({ox_ + static_cast<double>(tx) / 65536.0 * r, oy_ + static_cast<double>(ty) / 65536.0 * r,
+                   static_cast<double>(h) / 65536.0 * kTwoPi});
+  }
+  return out;
+}
+
+std::vector<uint32_t> MPPI::sampleCosts() const {
+  if (!ctx_) throw std::runtime_error("no step has run");
+  std::vector<uint32_t> s(cfg_.samples);
+  hip::check(kc_mppi_costs(ctx_.get(), s.data(), s.size()));
+  return s;
+}
+
+}  // namespace Control
+}  // namespace Kompass

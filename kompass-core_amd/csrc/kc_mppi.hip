@@ -1,0 +1,595 @@
+// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 12).
+//
+// Nothing in the reference to restate: its controllers commit to one velocity for the whole look-ahead.  K noisy
+// control sequences of T steps are drawn around a nominal one, rolled out from the robot's state in the localiser's
+// integers (rules 28 to 31 of 4.11: 16 fraction bits of a cell, the 65536-entry heading table, the counter-based noise),
+// costed against the map's distance plane and a window of path points, and blended by rule 36's table weights into the
+// next nominal sequence.  Integers only, exact sums: no result depends on thread order, and tests/mppi_ref.py states
+// every rule in Python ints.  No kernel modifies the map, and the context keeps no sequence between calls.
+//
+// A step is two launches and one read-back.
+//  (a) mppi_rollout_kernel<TEAM>: TEAM lanes a sample (1, 4 or 8; a team lies inside one wavefront).  pen_d2, the path
+//      window and the nominal sequence lie in LDS.  Every lane of a team carries the sample's state; the three noise
+//      draws of a step are split over the team's first three lanes and handed round by shuffles, the path search of
+//      rule 6 is split by j = lane, lane + TEAM, ... and its packed key (min(q, qcap) << 8 | j) reduced by one 64-bit
+//      minimum per shuffle.  The plane costs one 2-byte load a step behind the bounds test.  Control flow is uniform
+//      over a wavefront (a sample that has hit goes on masked; the loop ends when every sample of the wavefront has
+//      hit), so every shuffle finds its source lane active.  The wavefront reduces S_k << 32 | k to one 64-bit atomic
+//      minimum and its hits to one atomic add; both words were put to their start values by the step's upload.
+//  (b) mppi_update_kernel: a workgroup a step t.  It draws X_k[t] again from the counter noise (rule 3 depends on U[t],
+//      k and t only), forms the weights from S_k and the packed minimum, and reduces three int64 numerators and den
+//      exactly.  No K x T x 3 buffer exists.  Workgroup 0 writes the record behind U'.
+// The small inline functions of rule 30 are restated here from kc_mcl.hip, which keeps them to itself.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "kc_internal.h"
+#include "kompass_hip.h"
+
+namespace kc {
+
+constexpr int kMppiBlock = 64;   // the roll-out's workgroup: one wavefront, so that few samples still spread over the CUs
+constexpr int kMppiUpdate = 256;
+constexpr long long kMppiMaxOffset = 1ll << 36;
+constexpr unsigned kMppiCap = 1u << 30;
+
+__host__ __device__ inline unsigned long long mppi_mix64(unsigned long long x) {
+  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline long long mppi_noise(unsigned long long v, int s) {
+  const long long g =
+      static_cast<long long>((v & 0xFFFF) + ((v >> 16) & 0xFFFF) + ((v >> 32) & 0xFFFF) + (v >> 48)) - 131070ll;
+  return (g * s + (1ll << 15)) >> 16;
+}
+__host__ __device__ inline long long mppi_clamp(long long v) {
+  return v < -kMppiMaxOffset ? -kMppiMaxOffset : (v > kMppiMaxOffset ? kMppiMaxOffset : v);
+}
+__host__ __device__ inline long long mppi_within(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+struct MppiModel {  // rule 2's limits, rule 3's scales
+  int f_lo, f_hi, l_hi, h_hi, kq;
+  int s[3];
+};
+
+// rule 2: the box, then the cone
+__host__ __device__ inline void mppi_clamp_u(const MppiModel &m, long long &F, long long &L, long long &H) {
+  F = mppi_within(F, m.f_lo, m.f_hi);
+  L = mppi_within(L, -static_cast<long long>(m.l_hi), m.l_hi);
+  H = mppi_within(H, -static_cast<long long>(m.h_hi), m.h_hi);
+  if (m.kq > 0) {
+    const long long lim = ((F < 0 ? -F : F) * m.kq) >> 16;
+    H = mppi_within(H, -lim, lim);
+  }
+}
+
+// rule 3's eps of sample k, step t, channel c
+__device__ __forceinline__ long long mppi_eps(const MppiModel &m, unsigned long long key, int k, int t, int c) {
+  if (k == 0) return 0;
+  return mppi_noise(mppi_mix64(key ^ ((static_cast<unsigned long long>(k) << 8) | static_cast<unsigned>(3 * t + c))), m.s[c]);
+}
+
+// What a step uploads in one copy: the nominal sequence and the start values of the two words the roll-out reduces into
+struct MppiIn {
+  unsigned long long min_key;  // S_k << 32 | k, ~0 at the start
+  unsigned n_hit, pad;
+  int U[KC_MPPI_MAX_HORIZON * 3];
+};
+// and what it reads back in one copy
+struct MppiOut {
+  int U[KC_MPPI_MAX_HORIZON * 3];
+  kc_mppi_record rec;
+};
+
+struct MppiRollArgs {
+  const int2 *heading;           // rule 29
+  const unsigned short *dist2;   // rule 42's plane, refreshed
+  const unsigned short *pen_d2;  // c2 + 1 entries
+  const long long *px, *py;      // M points
+  MppiIn *in;
+  unsigned *S;
+  MppiModel m;
+  unsigned long long key, qcap;
+  long long tx, ty;
+  unsigned h, r2, pen_far, pen_hit, w_path, w_goal;
+  int W, H, K, T, M, c2;
+};
+
+template <int TEAM>
+__global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a) {
+  __shared__ unsigned short s_pen[KC_MPPI_MAX_TABLE];
+  __shared__ long long s_px[KC_MPPI_MAX_PATH], s_py[KC_MPPI_MAX_PATH];
+  __shared__ int s_U[KC_MPPI_MAX_HORIZON * 3];
+  for (int i = threadIdx.x; i <= a.c2; i += kMppiBlock) s_pen[i] = a.pen_d2[i];
+  for (int i = threadIdx.x; i < a.M; i += kMppiBlock) {
+    s_px[i] = a.px[i];
+    s_py[i] = a.py[i];
+  }
+  for (int i = threadIdx.x; i < 3 * a.T; i += kMppiBlock) s_U[i] = a.in->U[i];
+  __syncthreads();
+  const int lane = static_cast<int>(threadIdx.x);
+  const int k = (static_cast<int>(blockIdx.x) * kMppiBlock + lane) / TEAM, sub = lane % TEAM;  // K TEAM <= 2^19
+  const bool live = k < a.K;  // a whole team, or none of it
+  long long tx = a.tx, ty = a.ty;
+  unsigned h = a.h;
+  bool alive = live, hit = false;
+  long long total = 0;
+  int jm = 0;
+  for (int t = 0; t < a.T; ++t) {
+    if (__all(!alive)) break;  // wavefront-uniform
+    // rule 3.  Lanes 0 to 2 of a team draw a channel each; with one lane a sample it draws all three
+    long long e0, e1, e2;
+    if (TEAM == 1) {
+      e0 = mppi_eps(a.m, a.key, live ? k : 0, t, 0);
+      e1 = mppi_eps(a.m, a.key, live ? k : 0, t, 1);
+      e2 = mppi_eps(a.m, a.key, live ? k : 0, t, 2);
+    } else {
+      const long long mine = mppi_eps(a.m, a.key, live ? k : 0, t, sub < 3 ? sub : 0);
+      e0 = __shfl(mine, 0, TEAM);
+      e1 = __shfl(mine, 1, TEAM);
+      e2 = __shfl(mine, 2, TEAM);
+    }
+    long long F = s_U[3 * t] + e0, L = s_U[3 * t + 1] + e1, Hc = s_U[3 * t + 2] + e2;
+    mppi_clamp_u(a.m, F, L, Hc);
+    // rule 4, from the heading before the step; a sample that has hit stays where it is
+    const int2 cs = a.heading[h];
+    const long long C = cs.x, S = cs.y;
+    if (alive) {
+      tx = mppi_clamp(tx + ((C * F - S * L + (1ll << 15)) >> 16));
+      ty = mppi_clamp(ty + ((S * F + C * L + (1ll << 15)) >> 16));
+      h = static_cast<unsigned>((static_cast<long long>(h) + Hc) & 0xFFFF);
+    }
+    // rule 5
+    const long long I = (tx + (1ll << 15)) >> 16, J = (ty + (1ll << 15)) >> 16;
+    unsigned d2 = KC_WORLDMAP_DIST_FAR;
+    if (alive && I >= 0 && I < a.W && J >= 0 && J < a.H)
+      d2 = a.dist2[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)];
+    if (alive && d2 <= a.r2) {
+      total += static_cast<long long>(a.pen_hit) * (a.T - t);
+      hit = true;
+      alive = false;
+    }
+    if (alive) total += d2 <= static_cast<unsigned>(a.c2) ? s_pen[d2] : a.pen_far;
+    // rule 6: this lane's share of the window, then the team's minimum of the packed key
+    unsigned long long best = ~0ull;
+    for (int j = sub; j < a.M; j += TEAM) {
+      const long long dx = static_cast<int>((tx - s_px[j]) >> 8), dy = static_cast<int>((ty - s_py[j]) >> 8);  // |.| <= 2^29
+      const unsigned long long q = static_cast<unsigned long long>(dx * dx + dy * dy);
+      const unsigned long long key = ((q < a.qcap ? q : a.qcap) << 8) | static_cast<unsigned>(j);
+      best = key < best ? key : best;
+    }
+#pragma unroll
+    for (int off = TEAM / 2; off > 0; off >>= 1) {
+      const unsigned long long other = __shfl_xor(best, off, TEAM);
+      best = other < best ? other : best;
+    }
+    if (alive) {
+      total += static_cast<long long>(((best >> 8) * a.w_path) >> 16);  // below 2^56 before the shift
+      jm = static_cast<int>(best & 0xFF);
+    }
+  }
+  // rules 7 and 8
+  total += static_cast<long long>(a.w_goal) * (a.M - 1 - jm);
+  const unsigned Sk = total < static_cast<long long>(kMppiCap) ? static_cast<unsigned>(total) : kMppiCap;
+  const bool writer = live && sub == 0;
+  if (writer) a.S[k] = Sk;
+  unsigned long long key = writer ? (static_cast<unsigned long long>(Sk) << 32) | static_cast<unsigned>(k) : ~0ull;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long other = __shfl_xor(key, off);
+    key = other < key ? other : key;
+  }
+  const unsigned long long hits = __ballot(writer && hit);
+  if (lane == 0) {
+    if (key != ~0ull) atomicMin(&a.in->min_key, key);
+    if (hits != 0ull) atomicAdd(&a.in->n_hit, static_cast<unsigned>(__popcll(hits)));
+  }
+}
+
+struct MppiUpdateArgs {
+  const MppiIn *in;
+  const unsigned *S;
+  const unsigned *wtab;
+  MppiOut *out;
+  MppiModel m;
+  unsigned long long key;
+  int K, T, EW, w_shift;
+  unsigned step;
+};
+
+// floor(a / b) for b > 0
+__host__ __device__ inline long long mppi_floor_div(long long a, long long b) {
+  const long long q = a / b;
+  return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// rules 9 to 11; blockIdx.x: the step t
+__global__ __launch_bounds__(kMppiUpdate) void mppi_update_kernel(MppiUpdateArgs a) {
+  __shared__ long long s_part[4][kMppiUpdate / 64];
+  const int t = static_cast<int>(blockIdx.x);
+  const long long U0 = a.in->U[3 * t], U1 = a.in->U[3 * t + 1], U2 = a.in->U[3 * t + 2];
+  const unsigned long long min_key = a.in->min_key;
+  const unsigned s_min = static_cast<unsigned>(min_key >> 32);
+  long long sums[4] = {0, 0, 0, 0};  // three numerators (below 2^59) and den
+  for (int k = threadIdx.x; k < a.K; k += kMppiUpdate) {
+    const unsigned bin = (a.S[k] - s_min) >> a.w_shift;
+    const long long w = a.wtab[bin < static_cast<unsigned>(a.EW - 1) ? bin : static_cast<unsigned>(a.EW - 1)];
+    long long F = U0 + mppi_eps(a.m, a.key, k, t, 0), L = U1 + mppi_eps(a.m, a.key, k, t, 1), H = U2 + mppi_eps(a.m, a.key, k, t, 2);
+    mppi_clamp_u(a.m, F, L, H);
+    sums[0] += w * (F - U0);
+    sums[1] += w * (L - U1);
+    sums[2] += w * (H - U2);
+    sums[3] += w;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sums[i] += __shfl_down(sums[i], off);
+    if ((threadIdx.x & 63) == 0) s_part[i][threadIdx.x >> 6] = sums[i];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    long long v = 0;
+#pragma unroll
+    for (int w = 0; w < kMppiUpdate / 64; ++w) v += s_part[i][w];
+    sums[i] = v;
+  }
+  const long long den = sums[3];  // >= wtab[0] >= 1: the best sample's weight
+  long long F = U0 + mppi_floor_div(2 * sums[0] + den, 2 * den);
+  long long L = U1 + mppi_floor_div(2 * sums[1] + den, 2 * den);
+  long long H = U2 + mppi_floor_div(2 * sums[2] + den, 2 * den);
+  mppi_clamp_u(a.m, F, L, H);
+  a.out->U[3 * t] = static_cast<int>(F);
+  a.out->U[3 * t + 1] = static_cast<int>(L);
+  a.out->U[3 * t + 2] = static_cast<int>(H);
+  if (t == 0) {
+    kc_mppi_record r;
+    r.den = static_cast<uint64_t>(den);
+    r.s_min = s_min;
+    r.k_best = static_cast<uint32_t>(min_key & 0xFFFFFFFFull);
+    r.s_0 = a.S[0];
+    r.n_hit = a.in->n_hit;
+    r.step = a.step;
+    r.reserved = 0;
+    a.out->rec = r;
+  }
+}
+
+}  // namespace kc
+
+using namespace kc;
+
+struct kc_mppi {
+  kc_worldmap *map = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  OrderEvent map_ready;  // the map's writes, for the roll-out
+  size_t K = 0, T = 0, M = 0;
+  unsigned long long seed = 0;
+  DevBuf<int2> d_heading;
+  DevBuf<unsigned> d_S;
+  DevBuf<unsigned short> d_pen;
+  DevBuf<unsigned> d_wtab;
+  DevBuf<long long> d_px, d_py;
+  DevBuf<MppiIn> d_in;
+  PinBuf<MppiIn> h_in;
+  DevBuf<MppiOut> d_out;
+  PinBuf<MppiOut> h_out;
+  MppiModel m{};
+  bool have_model = false, have_costs = false, have_S = false;
+  int c2 = 0, EW = 0, w_shift = 0;
+  int team = 8;  // lanes a sample: the fastest of 1, 4 and 8 at both measured shapes
+  unsigned r2 = 0, pen_far = 0, pen_hit = 0, w_path = 0, w_goal = 0;
+  unsigned long long qcap = 0;
+  Timing time;
+};
+
+namespace {
+
+// rule 29's table through the localiser's entry, formed once a process
+const int2 *mppi_heading_table() {
+  static std::vector<int2> table;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    table.resize(65536);
+    for (uint32_t h = 0; h < 65536u; ++h) {
+      int32_t c = 0, s = 0;
+      kc_mcl_heading(h, &c, &s);
+      table[h] = make_int2(c, s);
+    }
+  });
+  return table.data();
+}
+
+// rule 12, in its order
+int mppi_check(size_t K, size_t T, size_t M, const int32_t *limits, const int32_t *s3, uint32_t r2, const uint16_t *pen_d2, size_t n_pen,
+               uint32_t pen_hit, uint32_t w_path, uint64_t qcap, uint32_t w_goal, int reach, const uint32_t *wtab, size_t EW,
+               int w_shift) {
+  if (K == 0 || T == 0 || M == 0)
+    KC_FAIL(KC_ERR_INVALID, "a controller needs at least one sample, one step and one path point, got %zu x %zu x %zu", K, T, M);
+  if (K > KC_MPPI_MAX_SAMPLES) KC_FAIL(KC_ERR_RANGE, "%zu samples are above the cap of %d", K, KC_MPPI_MAX_SAMPLES);
+  if (T > KC_MPPI_MAX_HORIZON) KC_FAIL(KC_ERR_RANGE, "%zu steps are above the cap of %d", T, KC_MPPI_MAX_HORIZON);
+  if (M > KC_MPPI_MAX_PATH) KC_FAIL(KC_ERR_RANGE, "%zu path points are above the cap of %d", M, KC_MPPI_MAX_PATH);
+  if (limits) {
+    const long long f_lo = limits[0], f_hi = limits[1], l_hi = limits[2], h_hi = limits[3], kq = limits[4];
+    if (f_lo > f_hi || l_hi < 0 || h_hi < 0 || kq < 0) KC_FAIL(KC_ERR_INVALID, "an empty or negative control limit");
+    if (f_lo < -(1ll << 22) || f_lo > (1ll << 22) || f_hi < -(1ll << 22) || f_hi > (1ll << 22) || l_hi > (1ll << 22))
+      KC_FAIL(KC_ERR_RANGE, "a displacement limit is above 2^22");
+    if (h_hi > 32767) KC_FAIL(KC_ERR_RANGE, "H_hi = %lld is above 32767", h_hi);
+    if (kq > (1ll << 24)) KC_FAIL(KC_ERR_RANGE, "kq = %lld is above 2^24", kq);
+    if (!s3) KC_FAIL(KC_ERR_INVALID, "null noise scales");
+    if (s3[0] < 0 || s3[1] < 0 || s3[2] < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
+  }
+  if (pen_d2) {
+    if (n_pen < 2) KC_FAIL(KC_ERR_INVALID, "the penalty table needs c2 + 1 >= 2 entries, got %zu", n_pen);
+    if (n_pen > KC_MPPI_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu penalty entries are above the cap of %d", n_pen, KC_MPPI_MAX_TABLE);
+    if (r2 > n_pen - 1) KC_FAIL(KC_ERR_INVALID, "r2 = %u is above c2 = %zu", r2, n_pen - 1);
+    if (pen_hit > (1u << 20)) KC_FAIL(KC_ERR_RANGE, "pen_hit = %u is above 2^20", pen_hit);
+    if (w_path > (1u << 16)) KC_FAIL(KC_ERR_RANGE, "w_path = %u is above 2^16", w_path);
+    if (qcap > (1ull << 40)) KC_FAIL(KC_ERR_RANGE, "qcap is above 2^40");
+    if ((qcap >> 16) * w_path > (1ull << 24)) KC_FAIL(KC_ERR_RANGE, "(qcap >> 16) w_path is above 2^24");
+    if (w_goal > (1u << 20)) KC_FAIL(KC_ERR_RANGE, "w_goal = %u is above 2^20", w_goal);
+    if (reach != 0) {
+      if (reach < 1 || reach > KC_WORLDMAP_DIST_MAX_REACH)
+        KC_FAIL(KC_ERR_RANGE, "reach must be in 1 .. %d cells, got %d", KC_WORLDMAP_DIST_MAX_REACH, reach);
+      if (n_pen - 1 > static_cast<size_t>(reach) * static_cast<size_t>(reach))
+        KC_FAIL(KC_ERR_INVALID, "c2 = %zu is above reach^2 = %d", n_pen - 1, reach * reach);
+    }
+    if (!wtab) KC_FAIL(KC_ERR_INVALID, "null weight table");
+    if (EW == 0) KC_FAIL(KC_ERR_INVALID, "an empty weight table");
+    if (EW > KC_MPPI_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu weight entries are above the cap of %d", EW, KC_MPPI_MAX_TABLE);
+    if (w_shift < 0 || w_shift > 30) KC_FAIL(KC_ERR_INVALID, "w_shift must be in 0 .. 30, got %d", w_shift);
+    if (wtab[0] < 1u || wtab[0] > (1u << 20)) KC_FAIL(KC_ERR_INVALID, "wtab[0] must be in 1 .. 2^20, got %u", wtab[0]);
+    for (size_t i = 1; i < EW; ++i)
+      if (wtab[i] > wtab[i - 1]) KC_FAIL(KC_ERR_INVALID, "the weight table increases at entry %zu", i);
+  }
+  return KC_OK;
+}
+
+template <int TEAM>
+void mppi_launch_rollout(const kc_mppi *c, const MppiRollArgs &a) {
+  const size_t lanes = c->K * static_cast<size_t>(TEAM);
+  hipLaunchKernelGGL(mppi_rollout_kernel<TEAM>, dim3(static_cast<unsigned>((lanes + kMppiBlock - 1) / kMppiBlock)), dim3(kMppiBlock), 0,
+                     c->stream, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int kc_mppi_check(size_t n_samples, size_t horizon, size_t n_path, const int32_t *limits_or_null, const int32_t *s_or_null, uint32_t r2,
+                  const uint16_t *pen_d2_or_null, size_t n_pen, uint32_t pen_hit, uint32_t w_path, uint64_t qcap, uint32_t w_goal,
+                  int reach, const uint32_t *wtab_or_null, size_t n_wtab, int w_shift) {
+  return mppi_check(n_samples, horizon, n_path, limits_or_null, s_or_null, r2, pen_d2_or_null, n_pen, pen_hit, w_path, qcap, w_goal, reach,
+                    wtab_or_null, n_wtab, w_shift);
+}
+
+int kc_mppi_create(kc_worldmap *map, size_t n_samples, size_t horizon, uint64_t seed, kc_mppi **out) {
+  if (!out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!map) KC_FAIL(KC_ERR_INVALID, "null argument");
+  KC_TRY(mppi_check(n_samples, horizon, 1, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, 0));
+  WorldMapView v{};
+  KC_TRY(worldmap_view(map, &v));
+  hipStream_t stream = nullptr;
+  KC_TRY(open_device_stream(v.device, &stream));
+  auto *c = new kc_mppi();
+  c->map = map;
+  c->device = v.device;
+  c->stream = stream;
+  c->K = n_samples;
+  c->T = horizon;
+  c->seed = seed;
+  int e = KC_OK;
+  if ((e = c->d_heading.reserve(65536)) || (e = c->d_S.reserve(n_samples)) || (e = c->d_px.reserve(KC_MPPI_MAX_PATH)) ||
+      (e = c->d_py.reserve(KC_MPPI_MAX_PATH)) || (e = c->d_in.reserve(1)) || (e = c->h_in.reserve(1)) || (e = c->d_out.reserve(1)) ||
+      (e = c->h_out.reserve(1))) {
+  }
+  if (!e) {
+    hipError_t he = hipMemcpyAsync(c->d_heading.p, mppi_heading_table(), 65536 * sizeof(int2), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) {
+      set_error("the heading table's upload failed: %s", hipGetErrorString(he));
+      e = KC_ERR_HIP;
+    }
+  }
+  if (e) {
+    kc_mppi_destroy(c);
+    return e;
+  }
+  *out = c;
+  return KC_OK;
+}
+
+void kc_mppi_destroy(kc_mppi *c) {
+  if (!c) return;
+  close_device_stream(c->device, &c->stream);
+  delete c;  // (the device is current: the buffers and the events go with the context)
+}
+
+int kc_mppi_set_model(kc_mppi *c, int32_t f_lo, int32_t f_hi, int32_t l_hi, int32_t h_hi, int32_t kq, const int32_t *s) {
+  if (!c || !s) KC_FAIL(KC_ERR_INVALID, "null argument");
+  const int32_t limits[5] = {f_lo, f_hi, l_hi, h_hi, kq};
+  KC_TRY(mppi_check(c->K, c->T, 1, limits, s, 0, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, 0));
+  c->m = MppiModel{f_lo, f_hi, l_hi, h_hi, kq, {s[0], s[1], s[2]}};
+  c->have_model = true;
+  return KC_OK;
+}
+
+int kc_mppi_set_costs(kc_mppi *c, uint32_t r2, const uint16_t *pen_d2, size_t n_pen, uint16_t pen_far, uint32_t pen_hit, uint32_t w_path,
+                      uint64_t qcap, uint32_t w_goal, const uint32_t *wtab, size_t n_wtab, int w_shift) {
+  if (!c || !pen_d2 || !wtab) KC_FAIL(KC_ERR_INVALID, "null argument");
+  KC_TRY(mppi_check(c->K, c->T, 1, nullptr, nullptr, r2, pen_d2, n_pen, pen_hit, w_path, qcap, w_goal, 0, wtab, n_wtab, w_shift));
+  KC_HIP(hipSetDevice(c->device));
+  c->have_costs = false;
+  KC_TRY(c->d_pen.reserve(n_pen));
+  KC_TRY(c->d_wtab.reserve(n_wtab));
+  // from the caller's memory: the call returns after the drain
+  KC_HIP(hipMemcpyAsync(c->d_pen.p, pen_d2, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipMemcpyAsync(c->d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->c2 = static_cast<int>(n_pen) - 1;
+  c->r2 = r2;
+  c->pen_far = pen_far;
+  c->pen_hit = pen_hit;
+  c->w_path = w_path;
+  c->qcap = qcap;
+  c->w_goal = w_goal;
+  c->EW = static_cast<int>(n_wtab);
+  c->w_shift = w_shift;
+  c->have_costs = true;
+  return KC_OK;
+}
+
+int kc_mppi_set_path(kc_mppi *c, const int64_t *px, const int64_t *py, size_t n) {
+  if (!c || !px || !py) KC_FAIL(KC_ERR_INVALID, "null argument");
+  KC_TRY(mppi_check(c->K, c->T, n, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, 0));
+  for (size_t j = 0; j < n; ++j)
+    if (px[j] < -kMppiMaxOffset || px[j] > kMppiMaxOffset || py[j] < -kMppiMaxOffset || py[j] > kMppiMaxOffset)
+      KC_FAIL(KC_ERR_RANGE, "path point %zu lies more than 2^20 cells from the map's origin", j);
+  KC_HIP(hipSetDevice(c->device));
+  c->M = 0;
+  KC_HIP(hipMemcpyAsync(c->d_px.p, px, n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipMemcpyAsync(c->d_py.p, py, n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->M = n;
+  return KC_OK;
+}
+
+int kc_mppi_set_team(kc_mppi *c, int lanes) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (lanes != 1 && lanes != 4 && lanes != 8) KC_FAIL(KC_ERR_INVALID, "a sample takes 1, 4 or 8 lanes, got %d", lanes);
+  c->team = lanes;
+  return KC_OK;
+}
+
+// Check order: null arguments; the state (model, costs, path); the pose, the heading, the sequence; the map's plane;
+// then the device
+int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *u_in, uint32_t step, int32_t *u_out, kc_mppi_record *rec) {
+  if (!c || !u_in || !u_out || !rec) KC_FAIL(KC_ERR_INVALID, "null argument");
+  std::memset(rec, 0, sizeof(*rec));
+  if (!c->have_model) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_model first");
+  if (!c->have_costs) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_costs first");
+  if (c->M == 0) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_path first");
+  if (tx < -kMppiMaxOffset || tx > kMppiMaxOffset || ty < -kMppiMaxOffset || ty > kMppiMaxOffset)
+    KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
+  if (h > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h);
+  const size_t T = c->T;
+  for (size_t t = 0; t < T; ++t) {
+    const long long F = u_in[3 * t], L = u_in[3 * t + 1], H = u_in[3 * t + 2];
+    if (F < -(1ll << 22) || F > (1ll << 22) || L < -(1ll << 22) || L > (1ll << 22) || H < -32767 || H > 32767)
+      KC_FAIL(KC_ERR_RANGE, "control %zu of the sequence is outside the bounds of the limits", t);
+  }
+  WorldMapView v{};
+  KC_TRY(worldmap_view(c->map, &v));
+  WorldMapDistance dist{};
+  KC_TRY(worldmap_distance_state(c->map, &dist));
+  if (dist.reach == 0) KC_FAIL(KC_ERR_STATE, "a step needs the map's distance plane: kc_worldmap_set_distance");
+  if (c->c2 > dist.reach * dist.reach)
+    KC_FAIL(KC_ERR_STATE, "the costs' c2 = %d is above the plane's reach^2 = %d", c->c2, dist.reach * dist.reach);
+  KC_HIP(hipSetDevice(c->device));
+  c->have_S = false;
+  MppiIn *in = c->h_in.p;  // pinned; the last step's copy from it is over (every step ends drained)
+  in->min_key = ~0ull;
+  in->n_hit = 0;
+  in->pad = 0;
+  std::memcpy(in->U, u_in, T * 3 * sizeof(int32_t));
+  KC_HIP(hipMemcpyAsync(c->d_in.p, in, sizeof(MppiIn), hipMemcpyHostToDevice, c->stream));
+  KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
+  KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
+  const unsigned long long key = mppi_mix64(c->seed ^ (static_cast<unsigned long long>(step) << 32));
+  MppiRollArgs a{};
+  a.heading = c->d_heading.p;
+  a.dist2 = dist.dist2;
+  a.pen_d2 = c->d_pen.p;
+  a.px = c->d_px.p;
+  a.py = c->d_py.p;
+  a.in = c->d_in.p;
+  a.S = c->d_S.p;
+  a.m = c->m;
+  a.key = key;
+  a.qcap = c->qcap;
+  a.tx = tx;
+  a.ty = ty;
+  a.h = h;
+  a.r2 = c->r2;
+  a.pen_far = c->pen_far;
+  a.pen_hit = c->pen_hit;
+  a.w_path = c->w_path;
+  a.w_goal = c->w_goal;
+  a.W = v.W;
+  a.H = v.H;
+  a.K = static_cast<int>(c->K);
+  a.T = static_cast<int>(T);
+  a.M = static_cast<int>(c->M);
+  a.c2 = c->c2;
+  c->time.begin_cycle();
+  KC_TRY(c->time.start("rollout", c->stream));
+  if (c->team == 8) mppi_launch_rollout<8>(c, a);
+  else if (c->team == 4) mppi_launch_rollout<4>(c, a);
+  else mppi_launch_rollout<1>(c, a);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->time.stop(c->stream));
+  MppiUpdateArgs u{};
+  u.in = c->d_in.p;
+  u.S = c->d_S.p;
+  u.wtab = c->d_wtab.p;
+  u.out = c->d_out.p;
+  u.m = c->m;
+  u.key = key;
+  u.K = static_cast<int>(c->K);
+  u.T = static_cast<int>(T);
+  u.EW = c->EW;
+  u.w_shift = c->w_shift;
+  u.step = step;
+  KC_TRY(c->time.start("update", c->stream));
+  hipLaunchKernelGGL(mppi_update_kernel, dim3(static_cast<unsigned>(T)), dim3(kMppiUpdate), 0, c->stream, u);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->time.stop(c->stream));
+  c->h_out.p->rec.den = 0;  // so that a copy that did not happen cannot pass for a record
+  KC_HIP(hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(MppiOut), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  const kc_mppi_record &r = c->h_out.p->rec;
+  if (r.step != step || r.den == 0 || r.k_best >= c->K) KC_FAIL(KC_ERR_HIP, "the step's record is not this step's");
+  std::memcpy(u_out, c->h_out.p->U, T * 3 * sizeof(int32_t));
+  *rec = r;
+  c->have_S = true;
+  return KC_OK;
+}
+
+int kc_mppi_costs(kc_mppi *c, uint32_t *s_out, size_t cap) {
+  if (!c || !s_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->have_S) KC_FAIL(KC_ERR_STATE, "no costs before a step");
+  if (cap < c->K) KC_FAIL(KC_ERR_RANGE, "%zu costs do not fit the output capacity %zu", c->K, cap);
+  KC_HIP(hipSetDevice(c->device));
+  KC_HIP(hipMemcpyAsync(s_out, c->d_S.p, c->K * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_mppi_set_timing(kc_mppi *c, int enable) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  c->time.enabled = enable != 0;
+  c->time.begin_cycle();
+  return KC_OK;
+}
+
+int kc_mppi_times(kc_mppi *c, float ms_out[2]) {
+  if (!c || !ms_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  ms_out[0] = ms_out[1] = 0.0f;
+  if (!c->time.enabled || c->time.used != 2) KC_FAIL(KC_ERR_STATE, "no step has been timed on this controller");
+  KC_HIP(hipSetDevice(c->device));
+  size_t n = 0;
+  KC_TRY(c->time.get(nullptr, ms_out, 2, &n));
+  return KC_OK;
+}
+
+}  // extern "C"

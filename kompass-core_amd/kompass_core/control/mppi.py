@@ -1,0 +1,133 @@
+"""MPPI front-end (not in the reference): a sampling model-predictive follower over the world map's
+distance plane.  The planner is `kompass_cpp.control.MPPI`; every step is two launches on the MI355X and one read-back.
+Unlike the reference's controllers it plans a whole sequence inside its horizon: slow down, turn into the door, speed
+up."""
+from __future__ import annotations
+
+import logging
+import math
+from typing import List, Optional
+
+from attrs import define, field, validators
+
+import kompass_cpp
+from ..mapping.world_map import cpp_world_map
+from ..models import Robot, RobotCtrlLimits, RobotState, RobotType
+from ._base_ import FollowerConfig, FollowerTemplate
+
+
+def _rng(lo, hi):
+    return [validators.ge(lo), validators.le(hi)]
+
+
+@define
+class MPPIConfig(FollowerConfig):
+    """The defaults are those of the closed-loop scene of DESIGN.md 4.12: judgement, not measurement; nobody has tuned
+    them on a robot.  Lengths are in cells of the map, a step is the control time step."""
+    samples: int = field(default=1024, validator=_rng(1, 65536))
+    horizon: int = field(default=32, validator=_rng(1, 64))
+    window: int = field(default=96, validator=_rng(1, 256))                 # path points the cost looks at
+    control_horizon: int = field(default=2, validator=_rng(1, 64))         # controls the getters return
+    sigma_forward: float = field(default=0.5, validator=_rng(0.0, 64.0))    # cells a step
+    sigma_lateral: float = field(default=0.5, validator=_rng(0.0, 64.0))    # cells a step, OMNI only
+    sigma_turn: float = field(default=500.0 / 65536.0 * 2.0 * math.pi, validator=_rng(0.0, math.pi))  # radians a step
+    temperature: float = field(default=64.0, validator=_rng(1e-3, 1e9))     # lambda: w = exp(-(S - S_min) / lambda)
+    weight_shift: int = field(default=2, validator=_rng(0, 30))
+    weight_entries: int = field(default=256, validator=_rng(1, 4096))
+    hit_radius: float = field(default=3.0, validator=_rng(0.0, 63.0))       # cells: closer to an obstacle is a hit
+    clearance: float = field(default=7.0, validator=_rng(1.0, 63.0))        # cells: the penalty fades out here
+    clearance_weight: float = field(default=60.0, validator=_rng(0.0, 65535.0))
+    far_penalty: int = field(default=0, validator=_rng(0, 65535))
+    hit_penalty: int = field(default=4000, validator=_rng(0, 1 << 20))
+    path_weight: int = field(default=8, validator=_rng(0, 1 << 16))
+    goal_weight: int = field(default=20, validator=_rng(0, 1 << 20))
+    path_cap: float = field(default=20.0, validator=_rng(0.0, 1024.0))      # cells: farther from the path costs no more
+    distance_reach: int = field(default=8, validator=_rng(1, 254))          # the plane's reach when it has to be enabled
+    allow_reverse: bool = field(default=False)
+    min_turning_radius: float = field(default=0.5, validator=_rng(1e-3, 1e3))  # metres, ACKERMANN only
+    seed: int = field(default=0)
+
+    def to_kompass_cpp(self) -> "kompass_cpp.control.MPPIConfig":
+        c = kompass_cpp.control.MPPIConfig()
+        c.samples, c.horizon, c.window = int(self.samples), int(self.horizon), int(self.window)
+        c.sigma_forward, c.sigma_lateral, c.sigma_turn = float(self.sigma_forward), float(self.sigma_lateral), float(self.sigma_turn)
+        c.lambda_, c.w_shift, c.n_w = float(self.temperature), int(self.weight_shift), int(self.weight_entries)
+        c.hit_radius, c.clearance, c.clearance_weight = float(self.hit_radius), float(self.clearance), float(self.clearance_weight)
+        c.pen_far, c.pen_hit, c.w_path, c.w_goal = int(self.far_penalty), int(self.hit_penalty), int(self.path_weight), int(self.goal_weight)
+        c.path_cap, c.reach = float(self.path_cap), int(self.distance_reach)
+        c.allow_reverse, c.min_turning_radius = bool(self.allow_reverse), float(self.min_turning_radius)
+        c.seed = int(self.seed) & (2 ** 64 - 1)
+        return c
+
+
+class MPPI(FollowerTemplate):
+    def __init__(self, robot: Robot, ctrl_limits: RobotCtrlLimits, config: Optional[MPPIConfig] = None,
+                 config_file: Optional[str] = None, config_root_name: Optional[str] = None, control_time_step: float = 0.1, **_):
+        if config_file:
+            raise NotImplementedError("config files are not read by this build; pass an MPPIConfig")
+        self._robot = robot
+        self._config = config or MPPIConfig()
+        self._control_time_step = float(control_time_step)
+        self._got_path = False
+        self._planner = kompass_cpp.control.MPPI(control_type=RobotType.to_kompass_cpp_lib(robot.robot_type),
+                                                 control_limits=ctrl_limits.to_kompass_cpp_lib(),
+                                                 time_step=self._control_time_step, config=self._config.to_kompass_cpp())
+        self._params = kompass_cpp.control.FollowerParameters()
+        self._params.from_dict({k: float(getattr(self._config, k)) for k in (
+            "max_point_interpolation_distance", "lookahead_distance", "goal_dist_tolerance", "goal_orientation_tolerance",
+            "path_segment_length", "loosing_goal_distance")})
+        self._planner.set_follower_params(self._params)
+        self._result = None
+        logging.info("MPPI CONTROLLER IS READY")
+
+    @property
+    def planner(self) -> "kompass_cpp.control.MPPI":
+        return self._planner
+
+    def loop_step(self, *, current_state: RobotState, local_map=None, **_) -> bool:
+        """One control step over `local_map`, a WorldMap (kompass_core.mapping.WorldMap or the kompass_cpp class); its
+        distance plane is enabled when it is off.  Nothing else can serve: the controller reads the plane on the device."""
+        world_map = cpp_world_map(local_map)
+        if world_map is None:
+            raise TypeError("MPPI.loop_step needs local_map=<WorldMap>: it costs its samples against the world map's "
+                            f"distance plane on the device, got {type(local_map).__name__}")
+        self._result = self._planner.execute(
+            world_map, kompass_cpp.types.State(current_state.x, current_state.y, current_state.yaw, current_state.speed))
+        return self._result.status in (kompass_cpp.control.FollowingStatus.COMMAND_FOUND,
+                                       kompass_cpp.control.FollowingStatus.GOAL_REACHED)
+
+    def logging_info(self) -> str:
+        if self._result:
+            v = self._result.velocity_command
+            return f"MPPI status: {self._result.status}, Cmd: vx={v.vx:.2f}, vy={v.vy:.2f}, w={v.omega:.2f}"
+        return "MPPI not started"
+
+    def _controls(self, k) -> List[float]:
+        """The first control_horizon entries of the new sequence; the first is the command the acceleration limits let
+        through."""
+        if not self._result or self._result.status != kompass_cpp.control.FollowingStatus.COMMAND_FOUND:
+            return [0.0]
+        v = self._result.velocity_command
+        first = (v.vx, v.vy, v.omega)[k]
+        return [first] + [c[k] for c in self._planner.controls(int(self._config.control_horizon))[1:]]
+
+    @property
+    def linear_x_control(self) -> List[float]:
+        return self._controls(0)
+
+    @property
+    def linear_y_control(self) -> List[float]:
+        return self._controls(1)
+
+    @property
+    def angular_control(self) -> List[float]:
+        return self._controls(2)
+
+    def predicted_path(self):
+        """The new sequence rolled out on the host by rule 4: [(x, y, yaw)] in the world, one a step."""
+        return [tuple(p) for p in self._planner.predicted_path()]
+
+    @property
+    def record(self):
+        """(s_min, k_best, s_0, den, n_hit, step) of the last step."""
+        return tuple(self._planner.last_record)

@@ -156,6 +156,16 @@ class MclFit(C.Structure):
         return int(self.cost_sum), int(self.cost_min), int(self.cost_best), int(self.step)
 
 
+class MppiRecord(C.Structure):
+    """kc_mppi_record: one controller step (DESIGN.md 4.12 rule 11)."""
+    _fields_ = [("den", C.c_uint64), ("s_min", C.c_uint32), ("k_best", C.c_uint32), ("s_0", C.c_uint32),
+                ("n_hit", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        """(s_min, k_best, s_0, den, n_hit, step)"""
+        return int(self.s_min), int(self.k_best), int(self.s_0), int(self.den), int(self.n_hit), int(self.step)
+
+
 class MclRecovery(C.Structure):
     """kc_mcl_recovery: rule 61's two averages."""
     _fields_ = [("slow", C.c_int64), ("fast", C.c_int64), ("primed", C.c_int32)]
@@ -412,6 +422,19 @@ SIGNATURES = {
                                          C.POINTER(C.c_int64), C.POINTER(_sz)]),
     "kc_mcl_resample_inject": (C.c_int, [_vp, _sz]),
     "kc_mcl_inject_times": (C.c_int, [_vp, _fp]),
+    "kc_mppi_check": (C.c_int, [_sz, _sz, _sz, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, _sz, C.c_uint32, C.c_uint32,
+                                C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, _sz, C.c_int]),
+    "kc_mppi_create": (C.c_int, [_vp, _sz, _sz, C.c_uint64, C.POINTER(_vp)]),
+    "kc_mppi_destroy": (None, [_vp]),
+    "kc_mppi_set_model": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "kc_mppi_set_costs": (C.c_int, [_vp, C.c_uint32, C.c_void_p, _sz, C.c_uint16, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                    C.c_void_p, _sz, C.c_int]),
+    "kc_mppi_set_path": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
+    "kc_mppi_step": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MppiRecord)]),
+    "kc_mppi_costs": (C.c_int, [_vp, C.c_void_p, _sz]),
+    "kc_mppi_set_team": (C.c_int, [_vp, C.c_int]),
+    "kc_mppi_set_timing": (C.c_int, [_vp, C.c_int]),
+    "kc_mppi_times": (C.c_int, [_vp, _fp]),
 }
 
 _lib = None
@@ -2075,4 +2098,97 @@ class MclContext(_Owner):
         """(walk, weigh, prefix, select) launches in milliseconds, by HIP events; the last two 0 without a resample."""
         ms = (C.c_float * 4)()
         _check(lib().kc_mcl_times(self.h, ms))
+        return tuple(float(v) for v in ms)
+
+
+def _in(v, lo, hi, what):
+    """int(v) when it fits the C type of the argument, ValueError otherwise (ctypes would wrap it silently)."""
+    v = int(v)
+    if not lo <= v <= hi:
+        raise ValueError(f"{what} = {v} does not fit its C type")
+    return v
+
+
+def mppi_check(n_samples, horizon, n_path, limits=None, s=None, costs=None, reach=0):
+    """kc_mppi_check's refusals (host only; DESIGN.md 4.12 rule 12); raises ValueError / IndexError.  limits: (F_lo, F_hi,
+    L_hi, H_hi, kq) with s the three scales, or None; costs: (r2, pen_d2, pen_hit, w_path, qcap, w_goal, wtab, w_shift) or
+    None."""
+    lim = None if limits is None else np.array([_in(v, -2 ** 31, 2 ** 31 - 1, "limit") for v in limits], np.int32)
+    sc = None if s is None else np.array([_in(v, -2 ** 31, 2 ** 31 - 1, "scale") for v in s], np.int32)
+    if lim is not None and lim.size != 5 or sc is not None and sc.size != 3:
+        raise ValueError("five limits and three scales")
+    r2 = pen_hit = w_path = qcap = w_goal = w_shift = 0
+    pn = wt = None
+    if costs is not None:
+        r2, pen, pen_hit, w_path, qcap, w_goal, wtab, w_shift = costs
+        pn, wt = np.ascontiguousarray(pen, dtype=np.uint16), np.ascontiguousarray(wtab, dtype=np.uint32)
+    u32 = 2 ** 32 - 1
+    _check(lib().kc_mppi_check(int(n_samples), int(horizon), int(n_path), None if lim is None else lim.ctypes.data,
+                               None if sc is None else sc.ctypes.data, _in(r2, 0, u32, "r2"),
+                               None if pn is None else pn.ctypes.data, 0 if pn is None else pn.size, _in(pen_hit, 0, u32, "pen_hit"),
+                               _in(w_path, 0, u32, "w_path"), _in(qcap, 0, 2 ** 64 - 1, "qcap"), _in(w_goal, 0, u32, "w_goal"),
+                               int(reach), None if wt is None else wt.ctypes.data, 0 if wt is None else wt.size, int(w_shift)))
+
+
+class MppiContext(_Owner):
+    """Owner of one kc_mppi context: an MPPI controller over a WorldMapContext's distance plane, which it
+    keeps alive.  Works in the ABI's integers and keeps no sequence between steps; kompass_core.control.MPPI is the front
+    end in metres."""
+    _kc = "kc_mppi"
+
+    def __init__(self, world_map: "WorldMapContext", n_samples, horizon, seed=0):
+        self.map = world_map
+        self.n, self.horizon = int(n_samples), int(horizon)
+        self._open(lib().kc_mppi_create, world_map.h, self.n, self.horizon, int(seed) & (2 ** 64 - 1))
+
+    def set_model(self, f_lo, f_hi, l_hi, h_hi, kq, s):
+        sc = np.array([_in(v, -2 ** 31, 2 ** 31 - 1, "scale") for v in s], np.int32)
+        if sc.size != 3:
+            raise ValueError("three scales")
+        i32 = (-2 ** 31, 2 ** 31 - 1)
+        _check(lib().kc_mppi_set_model(self.h, _in(f_lo, *i32, "F_lo"), _in(f_hi, *i32, "F_hi"), _in(l_hi, *i32, "L_hi"),
+                                       _in(h_hi, *i32, "H_hi"), _in(kq, *i32, "kq"), sc.ctypes.data))
+
+    def set_costs(self, r2, pen_d2, pen_far, pen_hit, w_path, qcap, w_goal, wtab, w_shift):
+        pn, wt = np.ascontiguousarray(pen_d2, dtype=np.uint16), np.ascontiguousarray(wtab, dtype=np.uint32)
+        u32 = 2 ** 32 - 1
+        _check(lib().kc_mppi_set_costs(self.h, _in(r2, 0, u32, "r2"), pn.ctypes.data, pn.size, _in(pen_far, 0, 0xFFFF, "pen_far"),
+                                       _in(pen_hit, 0, u32, "pen_hit"), _in(w_path, 0, u32, "w_path"), _in(qcap, 0, 2 ** 64 - 1, "qcap"),
+                                       _in(w_goal, 0, u32, "w_goal"), wt.ctypes.data, wt.size, int(w_shift)))
+
+    def set_path(self, px, py):
+        x, y = np.ascontiguousarray(px, dtype=np.int64).reshape(-1), np.ascontiguousarray(py, dtype=np.int64).reshape(-1)
+        if x.size != y.size:
+            raise ValueError("one y a x")
+        _check(lib().kc_mppi_set_path(self.h, x.ctypes.data, y.ctypes.data, x.size))
+
+    def step(self, tx, ty, h, u, step):
+        """-> (U' int32 [T, 3], MppiRecord).  u: the nominal sequence, T x (F, L, H)."""
+        ui = np.ascontiguousarray(u, dtype=np.int64).reshape(-1)
+        if ui.size != 3 * self.horizon or ui.size and (ui.min() < -2 ** 31 or ui.max() > 2 ** 31 - 1):
+            raise ValueError("the sequence is T x 3 int32")
+        ui = ui.astype(np.int32)
+        out, r = np.zeros((self.horizon, 3), np.int32), MppiRecord()
+        _check(lib().kc_mppi_step(self.h, _in(tx, -2 ** 63, 2 ** 63 - 1, "tx"), _in(ty, -2 ** 63, 2 ** 63 - 1, "ty"),
+                                  _in(h, 0, 2 ** 32 - 1, "h"), ui.ctypes.data, _in(step, 0, 2 ** 32 - 1, "step"), out.ctypes.data,
+                                  C.byref(r)))
+        return out, r
+
+    def costs(self):
+        """All S_k of the last step: uint32 [K]."""
+        s = np.empty(self.n, np.uint32)
+        _check(lib().kc_mppi_costs(self.h, s.ctypes.data, self.n))
+        return s
+
+    def set_team(self, lanes):
+        """Measurement only: 1, 4 or 8 lanes a sample in the roll-out; no result depends on it."""
+        _check(lib().kc_mppi_set_team(self.h, int(lanes)))
+
+    def set_timing(self, enable=True):
+        _check(lib().kc_mppi_set_timing(self.h, int(bool(enable))))
+
+    def times(self):
+        """(rollout, update) launches of the last step in milliseconds, by HIP events."""
+        ms = (C.c_float * 2)()
+        _check(lib().kc_mppi_times(self.h, ms))
         return tuple(float(v) for v in ms)

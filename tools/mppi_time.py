@@ -1,0 +1,147 @@
+"""MPPI step on the MI355X: kc_mppi_step over a 2004 x 1204 world at two shapes,
+K = 1024, T = 32, M = 96 and K = 8192, T = 64, M = 256, with 1, 4 and 8 lanes a sample in the roll-out.
+
+For every shape and variant: the wall time of the whole step (upload, plane check, two launches, read-back; the median
+of --reps after --warmup) and the HIP-event times of the two launches (rollout, update).  The variants are timed
+interleaved in one run, so their order in time cannot favour one.  Every variant's result is compared with the first's:
+a difference is an error, not a timing.
+
+Beside them, as yardsticks only:
+  * the statement tests/mppi_ref.py on the same inputs, labelled as what it is: a Python statement's cost on one CPU;
+  * the class-level DWA call of tools/class_cycle.py (kompass_cpp.control.DWA.compute_velocity_commands, 91 x 91
+    lattice, the "mid" scene), timed in this run.
+
+The world: a border, a wall with a door and scattered pillars; the robot in free space, the path a straight line
+through the door.  One JSON line a shape on stdout."""
+import argparse
+import json
+import math
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
+
+import kompass_hip as kh  # noqa: E402
+import mppi_ref as mp  # noqa: E402
+import worldmap_mcl_ref as mref  # noqa: E402
+from worldmap_ref import EMPTY, OCCUPIED  # noqa: E402
+
+W, H, RES, ORIGIN, REACH = 2004, 1204, 0.05, (-50.0, -30.0), 8
+ONE = 1 << 16
+SHAPES = ((1024, 32, 96), (8192, 64, 256))
+TEAMS = (1, 4, 8)
+
+
+def world():
+    rng = np.random.default_rng(3)
+    c = np.full((W, H), EMPTY, np.int8)
+    c[0, :] = c[-1, :] = OCCUPIED
+    c[:, 0] = c[:, -1] = OCCUPIED
+    c[1060, :] = OCCUPIED
+    c[1060, 596:608] = EMPTY
+    for _ in range(400):
+        i, j = int(rng.integers(20, W - 20)), int(rng.integers(20, H - 20))
+        if abs(j - 602) > 12:                                              # keep the corridor along the path free
+            c[i:i + 4, j:j + 4] = OCCUPIED
+    return c
+
+
+def median(v):
+    return round(statistics.median(v), 4)
+
+
+def dwa_yardstick(reps, warmup):
+    import synthetic as syn
+    from kompass_cpp.control import (DWA, AngularVelocityControlParams, ControlLimitsParams, ControlType,
+                                     LinearVelocityControlParams, TrajectoryCostWeights)
+    from kompass_cpp.types import Path as CppPath, RobotGeometry, Velocity2D
+    lim = ControlLimitsParams(LinearVelocityControlParams(1.0, 2.0, 2.0), LinearVelocityControlParams(0.0, 0.0, 0.0),
+                              AngularVelocityControlParams(2.0, 2.0, 3.0, 3.0))
+    w = TrajectoryCostWeights()
+    w.from_dict(dict(reference_path_distance_weight=1.0, goal_distance_weight=1.0, obstacles_distance_weight=1.0,
+                     smoothness_weight=0.0, jerk_weight=0.0))
+    d = DWA(lim, ControlType.DIFFERENTIAL_DRIVE, 0.1, 5.0, 0.2, 91, 91, RobotGeometry.get("CYLINDER"), [0.1, 0.4],
+            [0.0, 0.0, 0.0], [0.0, 0.0, 0.0, 1.0], 0.05, w, 1)
+    d.set_current_path(CppPath([[x, 0.0, 0.0] for x in np.arange(0.0, 12.01, 1.0)]))
+    pts = syn.scene_points("cfg2", "mid")
+    ts = []
+    for i in range(reps + warmup):
+        d.set_current_state(0.001 * (i % 7), 0.0, 0.0, 0.5)
+        t0 = time.perf_counter()
+        d.compute_velocity_commands(Velocity2D(0.5, 0.0, 0.001 * (i % 5), 0.0), pts)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return median(ts[warmup:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-statement", action="store_true", help="skip the Python statement's timing")
+    ap.add_argument("--no-dwa", action="store_true", help="skip the class-level DWA yardstick")
+    args = ap.parse_args()
+    if kh.device_count() < 1:
+        raise SystemExit("no HIP device visible")
+    cls = world()
+    model = mp.Model(0, 2 * ONE, 0, 1565, 0, (mref.noise_scale(0.5 * ONE), 0, mref.noise_scale(500.0)))
+    costs = mp.scene_costs()
+    dwa_ms = None if args.no_dwa else dwa_yardstick(args.reps, args.warmup)
+    with kh.WorldMapContext(W, H, RES, ORIGIN) as m:
+        m.set_prior(cls)
+        m.set_distance(REACH)
+        plane = None if args.no_statement else np.ascontiguousarray(m.distance())
+        for K, T, M in SHAPES:
+            px = [(1000 + j) * ONE for j in range(M)]
+            py = [602 * ONE] * M
+            pose = (1000 * ONE + 300, 601 * ONE, 700)
+            U = [(80000, 0, 20)] * T
+            line = dict(shape=dict(K=K, T=T, M=M), world=[W, H], reps=args.reps, warmup=args.warmup)
+            with kh.MppiContext(m, K, T, 1) as dev:
+                dev.set_model(model.f_lo, model.f_hi, model.l_hi, model.h_hi, model.kq, model.s)
+                dev.set_costs(costs.r2, costs.pen_d2, costs.pen_far, costs.pen_hit, costs.w_path, costs.qcap, costs.w_goal, costs.wtab,
+                              costs.w_shift)
+                dev.set_path(px, py)
+                dev.set_timing(True)
+                wall = {t: [] for t in TEAMS}
+                roll = {t: [] for t in TEAMS}
+                upd = {t: [] for t in TEAMS}
+                first = None
+                for n in range(args.reps + args.warmup):
+                    for team in TEAMS:                                     # interleaved
+                        dev.set_team(team)
+                        t0 = time.perf_counter()
+                        out, rec = dev.step(*pose, U, n)
+                        dt = (time.perf_counter() - t0) * 1e3
+                        if team == TEAMS[0]:
+                            first = (out.tolist(), rec.as_tuple())
+                        elif (out.tolist(), rec.as_tuple()) != first:
+                            raise SystemExit(f"{team} lanes a sample differ from {TEAMS[0]} at step {n}")
+                        if n >= args.warmup:
+                            r, u = dev.times()
+                            wall[team].append(dt)
+                            roll[team].append(r)
+                            upd[team].append(u)
+                for team in TEAMS:
+                    line[f"team{team}"] = dict(step_ms=median(wall[team]), rollout_ms=median(roll[team]), update_ms=median(upd[team]))
+                line["n_hit"], line["s_min"] = first[1][4], first[1][0]
+                if plane is not None:
+                    ts = []
+                    for n in range(3):
+                        t0 = time.perf_counter()
+                        want = mp.step(plane, K, 1, model, costs, px, py, *pose, U, args.reps + args.warmup - 1)
+                        ts.append((time.perf_counter() - t0) * 1e3)
+                    if (want[0], tuple(want[1])) != (first[0] and [tuple(r) for r in first[0]], first[1]):
+                        raise SystemExit("the device differs from the statement")
+                    line["python_statement_ms"] = median(ts)
+            if dwa_ms is not None:
+                line["dwa_class_level_91x91_mid_ms"] = dwa_ms
+            print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
