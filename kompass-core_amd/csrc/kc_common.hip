@@ -1,4 +1,7 @@
-// Error string, device probing and key helpers of libkompass_hip.so.
+// Error string, device probing and key helpers of libkompass_hip.so, and the host side of kc_q16.h's integers: the
+// heading table, the table checks and uploads that the localiser and the MPPI controller share.
+#include <cmath>
+
 #include "kc_internal.h"
 
 namespace kc {
@@ -85,6 +88,58 @@ int check_device_range(int device, const void *ptr, long long lo_bytes, long lon
     KC_FAIL(KC_ERR_INVALID, "the device %s (bytes %lld to %lld from its pointer) runs outside its %zu-byte allocation", what, lo_bytes,
             hi_bytes, size);
   if (align > 1 && p % align) KC_FAIL(KC_ERR_INVALID, "the device %s is not aligned to %zu bytes", what, align);
+  return KC_OK;
+}
+
+double (*volatile host_cos)(double) = static_cast<double (*)(double)>(std::cos);
+double (*volatile host_sin)(double) = static_cast<double (*)(double)>(std::sin);
+
+const int2 *heading_table() {
+  static const std::vector<int2> table = [] {
+    std::vector<int2> t(65536);
+    for (int h = 0; h < 65536; ++h) {
+      const double a = 2.0 * M_PI * static_cast<double>(h) / 65536.0;
+      t[h] = make_int2(static_cast<int>(std::lrint(host_cos(a) * 65536.0)), static_cast<int>(std::lrint(host_sin(a) * 65536.0)));
+    }
+    return t;
+  }();
+  return table.data();
+}
+
+int upload_heading_table(DevBuf<int2> &d, hipStream_t s) {
+  KC_TRY(d.reserve(65536));
+  hipError_t he = hipMemcpyAsync(d.p, heading_table(), 65536 * sizeof(int2), hipMemcpyHostToDevice, s);
+  if (he == hipSuccess) he = hipStreamSynchronize(s);
+  if (he != hipSuccess) KC_FAIL(KC_ERR_HIP, "the heading table's upload failed: %s", hipGetErrorString(he));
+  return KC_OK;
+}
+
+int check_weight_table(const uint32_t *wtab, size_t EW, int w_shift, int cap) {
+  if (EW == 0) KC_FAIL(KC_ERR_INVALID, "an empty weight table");
+  if (EW > static_cast<size_t>(cap)) KC_FAIL(KC_ERR_RANGE, "%zu weight entries are above the cap of %d", EW, cap);
+  if (w_shift < 0 || w_shift > 30) KC_FAIL(KC_ERR_INVALID, "w_shift must be in 0 .. 30, got %d", w_shift);
+  if (wtab[0] < 1u || wtab[0] > (1u << 20)) KC_FAIL(KC_ERR_INVALID, "wtab[0] must be in 1 .. 2^20, got %u", wtab[0]);
+  for (size_t i = 1; i < EW; ++i)
+    if (wtab[i] > wtab[i - 1]) KC_FAIL(KC_ERR_INVALID, "the weight table increases at entry %zu", i);
+  return KC_OK;
+}
+
+int check_reach(size_t n_pen, int reach) {
+  if (reach == 0) return KC_OK;
+  if (reach < 1 || reach > KC_WORLDMAP_DIST_MAX_REACH)
+    KC_FAIL(KC_ERR_RANGE, "reach must be in 1 .. %d cells, got %d", KC_WORLDMAP_DIST_MAX_REACH, reach);
+  if (n_pen - 1 > static_cast<size_t>(reach) * static_cast<size_t>(reach))
+    KC_FAIL(KC_ERR_INVALID, "c2 = %zu is above reach^2 = %d", n_pen - 1, reach * reach);
+  return KC_OK;
+}
+
+int upload_tables(DevBuf<unsigned short> &d_pen, const uint16_t *pen, size_t n_pen, DevBuf<unsigned> &d_wtab, const uint32_t *wtab,
+                  size_t n_wtab, hipStream_t s) {
+  KC_TRY(d_pen.reserve(n_pen));
+  KC_TRY(d_wtab.reserve(n_wtab));
+  KC_HIP(hipMemcpyAsync(d_pen.p, pen, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+  KC_HIP(hipMemcpyAsync(d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  KC_HIP(hipStreamSynchronize(s));
   return KC_OK;
 }
 

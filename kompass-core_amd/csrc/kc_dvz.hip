@@ -35,14 +35,11 @@ bool device_trig_covers(double x) {
   return (static_cast<uint32_t>(u >> 32) & 0x7fffffffu) < 0x419921FBu;
 }
 
-// The reference takes np.cos / np.sin: the host libm's separate cos and sin, called here through pointers so
-// that the compiler cannot fold the pair into one sincos call.  On x86-64, glibc picks FMA builds of cos and sin
-// on FMA hardware; those differ from `sincos` -- which kc_trig_exact.h restates and which has no FMA build -- by
-// one ulp in about 0.1 % of arguments.  The device trig is therefore used only when the restatement also agrees
-// with the separate cos and sin on a fixed argument set; otherwise the host fills the table.
-double (*volatile host_cos)(double) = static_cast<double (*)(double)>(std::cos);
-double (*volatile host_sin)(double) = static_cast<double (*)(double)>(std::sin);
-
+// The reference takes np.cos / np.sin: the host libm's separate cos and sin, called through pointers (host_cos and
+// host_sin, kc_internal.h) so that the compiler cannot fold the pair into one sincos call.  On x86-64, glibc picks
+// FMA builds of cos and sin on FMA hardware; those differ from `sincos` -- which kc_trig_exact.h restates and which
+// has no FMA build -- by one ulp in about 0.1 % of arguments.  The device trig is therefore used only when the
+// restatement also agrees with the separate cos and sin on a fixed argument set; otherwise the host fills the table.
 bool dvz_trig_ok() {
   static const bool ok = [] {
     if (!trig_selfcheck_ok()) return false;

@@ -271,6 +271,23 @@ int stream_wait_through(OrderEvent &ev, hipStream_t own, hipStream_t producer);
 int check_device_range(int device, const void *ptr, long long lo_bytes, long long hi_bytes, size_t align,
                        const char *what);
 
+// ---- the host side of kc_q16.h's integers, shared by kc_mcl.hip and kc_mppi.hip (kc_common.hip) ----
+// libm's separate cos and sin through pointers, so that the compiler cannot fold the pair into one sincos call (whose
+// bits differ from theirs in about 0.1 % of arguments where glibc picks its FMA builds: kc_dvz.hip has the story)
+extern double (*volatile host_cos)(double);
+extern double (*volatile host_sin)(double);
+// DESIGN.md 4.11 rule 29: the 65536 (Cq, Sq) pairs, formed once a process; and a context's own device copy of them:
+// reserved, uploaded and `s` drained
+const int2 *heading_table();
+int upload_heading_table(DevBuf<int2> &d, hipStream_t s);
+// rule 36's refusals of a weight table that is there, in their order (cap: the caller's KC_*_MAX_TABLE), and those of a
+// penalty table of n_pen = c2 + 1 entries against a distance plane's reach (0: no plane to compare with)
+int check_weight_table(const uint32_t *wtab, size_t EW, int w_shift, int cap);
+int check_reach(size_t n_pen, int reach);
+// a penalty and a weight table from the caller's memory into buffers grown to hold them; returns after the drain
+int upload_tables(DevBuf<unsigned short> &d_pen, const uint16_t *pen, size_t n_pen, DevBuf<unsigned> &d_wtab, const uint32_t *wtab,
+                  size_t n_wtab, hipStream_t s);
+
 // ---- correctly rounded f32 divide / sqrt on the device ----------------------
 // HIP's __fsqrt_rn lowers to the *native* (approximate) sqrt unless
 // OCML_BASIC_ROUNDED_OPERATIONS is defined; the plain operators are IEEE

@@ -4,7 +4,9 @@
 // (TX, TY, h, acc) live on the device; a step advances them by an odometry increment with counter-based integer noise,
 // ray-casts the map in place for every particle x beam with the scan's own walk (kc_worldmap_walk.h), sums a table
 // penalty per particle, and reduces the weights to one record the host turns into an estimate.  Integers only, exact
-// sums: no result depends on thread order, and tests/worldmap_mcl_ref.py states every rule in Python ints.
+// sums: no result depends on thread order, and tests/worldmap_mcl_ref.py states every rule in Python ints.  The scalar
+// rules (clamp, mix64, draw, noise, motion step, weight entry) are kc_q16.h's, the plane lookup kc_worldmap_walk.h's, the
+// heading table, the table checks and uploads kc_internal.h's (kc_common.hip): kc_mppi.hip uses the same ones.
 //
 // Launches: a step is mcl_walk_kernel + mcl_weigh_kernel and the read-back of the record; a resample is
 // mcl_prefix_kernel + mcl_select_kernel without a read-back.
@@ -42,7 +44,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "kc_internal.h"
@@ -53,27 +54,7 @@ namespace kc {
 
 constexpr int kMclBlock = 256;
 constexpr int kMclOne = 1024;  // the single-workgroup kernels
-constexpr long long kMclMaxOffset = 1ll << 36;
 constexpr unsigned kMclAccCap = 1u << 30;
-
-__host__ __device__ inline unsigned long long mcl_mix64(unsigned long long x) {
-  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// key = mix64(seed ^ (step << 32)), formed once on the host
-__host__ __device__ inline unsigned long long mcl_draw(unsigned long long key, unsigned long long p, unsigned c) {
-  return mcl_mix64(key ^ ((p << 8) | c));
-}
-__host__ __device__ inline long long mcl_noise(unsigned long long v, int s) {
-  const long long g =
-      static_cast<long long>((v & 0xFFFF) + ((v >> 16) & 0xFFFF) + ((v >> 32) & 0xFFFF) + (v >> 48)) - 131070ll;
-  return (g * s + (1ll << 15)) >> 16;
-}
-__host__ __device__ inline long long mcl_clamp(long long v) {
-  return v < -kMclMaxOffset ? -kMclMaxOffset : (v > kMclMaxOffset ? kMclMaxOffset : v);
-}
 
 struct MclState {  // one of the two state buffers
   long long *tx, *ty;
@@ -95,13 +76,13 @@ __device__ __forceinline__ kc_worldmap_pose mcl_predict(const MclPredictArgs &a,
   const unsigned h0 = a.in.h[p];
   const int2 cs0 = a.heading[h0];
   const long long C = cs0.x, S = cs0.y;
-  const long long F = a.d_f + mcl_noise(mcl_draw(a.key, p, 0), a.s_f);
-  const long long L = a.d_l + mcl_noise(mcl_draw(a.key, p, 1), a.s_l);
+  const long long F = a.d_f + q16_noise(q16_draw(a.key, p, 0), a.s_f);
+  const long long L = a.d_l + q16_noise(q16_draw(a.key, p, 1), a.s_l);
   kc_worldmap_pose pose;
-  pose.tx = mcl_clamp(a.in.tx[p] + ((C * F - S * L + (1ll << 15)) >> 16));
-  pose.ty = mcl_clamp(a.in.ty[p] + ((S * F + C * L + (1ll << 15)) >> 16));
+  pose.tx = q16_move_x(a.in.tx[p], C, S, F, L);
+  pose.ty = q16_move_y(a.in.ty[p], C, S, F, L);
   const unsigned h1 =
-      static_cast<unsigned>((static_cast<long long>(h0) + a.d_h + mcl_noise(mcl_draw(a.key, p, 2), a.s_h)) & 0xFFFF);
+      static_cast<unsigned>((static_cast<long long>(h0) + a.d_h + q16_noise(q16_draw(a.key, p, 2), a.s_h)) & 0xFFFF);
   const int2 cs1 = a.heading[h1];
   pose.cq = cs1.x;
   pose.sq = cs1.y;
@@ -132,8 +113,8 @@ __device__ __forceinline__ void mcl_segment_add(unsigned *cost, int p, unsigned 
 __global__ __launch_bounds__(kMclBlock) void mcl_shift_kernel(MclState st, long long sx, long long sy, int N) {
   const int p = static_cast<int>(blockIdx.x) * kMclBlock + static_cast<int>(threadIdx.x);
   if (p >= N) return;
-  st.tx[p] = mcl_clamp(st.tx[p] - sx);
-  st.ty[p] = mcl_clamp(st.ty[p] - sy);
+  st.tx[p] = q16_clamp(st.tx[p] - sx);
+  st.ty[p] = q16_clamp(st.ty[p] - sy);
 }
 
 struct MclWalkArgs {
@@ -208,13 +189,10 @@ __global__ __launch_bounds__(kMclBlock) void mcl_field_kernel(MclFieldArgs a) {
     if (zq >= 0 && zq < a.zmax) {  // rule 45: a beam without a return says nothing about an endpoint
       const int2 t = a.table[k];
       // rule 22
-      const long long dx = (static_cast<long long>(pose.cq) * t.x - static_cast<long long>(pose.sq) * t.y + (1ll << 15)) >> 16;
-      const long long dy = (static_cast<long long>(pose.sq) * t.x + static_cast<long long>(pose.cq) * t.y + (1ll << 15)) >> 16;
+      const long long dx = q16_turn_x(pose.cq, pose.sq, t.x, t.y), dy = q16_turn_y(pose.cq, pose.sq, t.x, t.y);
       const long long I = (pose.tx + (1ll << 15) + ((zq * dx + (1ll << 29)) >> 30)) >> 16;
       const long long J = (pose.ty + (1ll << 15) + ((zq * dy + (1ll << 29)) >> 30)) >> 16;
-      unsigned d2 = KC_WORLDMAP_DIST_FAR;
-      if (I >= 0 && I < a.W && J >= 0 && J < a.H) d2 = a.dist2[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)];
-      c = d2 <= static_cast<unsigned>(a.c2) ? s_pen[d2] : a.pen_far;
+      c = wm_dist2_pen(wm_dist2_at(a.dist2, a.W, a.H, I, J), a.c2, s_pen, a.pen_far);
     }
   }
   mcl_segment_add(a.cost, p, c, live);
@@ -332,8 +310,7 @@ __global__ __launch_bounds__(kMclOne) void mcl_weigh_kernel(MclWeighArgs a) {
   const long long bx = a.st.tx[best], by = a.st.ty[best];
   long long w1 = 0, w2 = 0, sc = 0, ss = 0, sxh = 0, sxl = 0, syh = 0, syl = 0;
   for (int p = threadIdx.x; p < a.N; p += kMclOne) {  // rules 36 and 37
-    const unsigned bin = (a.acc[p] - amin) >> a.w_shift;
-    const long long w = a.wtab[bin < static_cast<unsigned>(a.EW - 1) ? bin : static_cast<unsigned>(a.EW - 1)];
+    const long long w = a.wtab[q16_weight_bin(a.acc[p], amin, a.w_shift, a.EW)];
     a.w[p] = static_cast<unsigned>(w);
     const int2 cs = a.heading[a.st.h[p]];
     const long long tx = w * (a.st.tx[p] - bx), ty = w * (a.st.ty[p] - by);
@@ -421,9 +398,9 @@ __global__ __launch_bounds__(kMclBlock) void mcl_init_pose_kernel(MclState out, 
                                                                   unsigned h0, int s_xy, int s_h, int N) {
   const int p = blockIdx.x * kMclBlock + threadIdx.x;
   if (p >= N) return;
-  out.tx[p] = mcl_clamp(tx0 + mcl_noise(mcl_draw(key, p, 0), s_xy));
-  out.ty[p] = mcl_clamp(ty0 + mcl_noise(mcl_draw(key, p, 1), s_xy));
-  out.h[p] = static_cast<unsigned>((static_cast<long long>(h0) + mcl_noise(mcl_draw(key, p, 2), s_h)) & 0xFFFF);
+  out.tx[p] = q16_clamp(tx0 + q16_noise(q16_draw(key, p, 0), s_xy));
+  out.ty[p] = q16_clamp(ty0 + q16_noise(q16_draw(key, p, 1), s_xy));
+  out.h[p] = static_cast<unsigned>((static_cast<long long>(h0) + q16_noise(q16_draw(key, p, 2), s_h)) & 0xFFFF);
   acc[p] = 0u;
   cost[p] = 0u;
   if (p == 0) *min_prev = 0u;
@@ -487,7 +464,7 @@ __global__ __launch_bounds__(kMclBlock) void mcl_init_global_kernel(const int8_t
                                                                     unsigned long long key, int N) {
   const int p = static_cast<int>((blockIdx.x * kMclBlock + threadIdx.x) >> 6), lane = threadIdx.x & 63;
   if (p >= N) return;  // the whole wavefront
-  unsigned long long rest = mcl_draw(key, p, 0) % before[H];
+  unsigned long long rest = q16_draw(key, p, 0) % before[H];
   int lo = 0, hi = H - 1;  // the last row with before[J] <= rest
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -504,7 +481,7 @@ __global__ __launch_bounds__(kMclBlock) void mcl_init_global_kernel(const int8_t
     const unsigned long long n = static_cast<unsigned long long>(__popcll(m));
     if (rest < n) {
       if (free_cell && static_cast<unsigned long long>(__popcll(m & ((1ull << lane) - 1ull))) == rest) {
-        const unsigned long long v = mcl_draw(key, p, 1);
+        const unsigned long long v = q16_draw(key, p, 1);
         out.tx[p] = (static_cast<long long>(i) << 16) + static_cast<long long>(v & 0xFFFF) - (1ll << 15);
         out.ty[p] = (static_cast<long long>(J) << 16) + static_cast<long long>((v >> 16) & 0xFFFF) - (1ll << 15);
         out.h[p] = static_cast<unsigned>((v >> 32) & 0xFFFF);
@@ -553,7 +530,7 @@ __global__ __launch_bounds__(kMclBlock) void mcl_inject_kernel(const int8_t *cls
   if (n_free == 0) return;
   const int j = static_cast<int>(((static_cast<long long>(i) + 1) * N + n - 1) / n) - 1;
   int I = 0, J = 0;
-  if (mcl_free_cell(cls, W, H, before, mcl_draw(key, j, 16) % n_free, &I, &J)) mcl_seed_in_cell(out, j, I, J, mcl_draw(key, j, 17));
+  if (mcl_free_cell(cls, W, H, before, q16_draw(key, j, 16) % n_free, &I, &J)) mcl_seed_in_cell(out, j, I, J, q16_draw(key, j, 17));
 }
 
 }  // namespace kc
@@ -599,24 +576,6 @@ struct kc_mcl {
 
 namespace {
 
-// libm's separate cos and sin through pointers, as kc_worldmap.hip's scan table: never one sincos call
-double (*volatile mcl_cos)(double) = static_cast<double (*)(double)>(std::cos);
-double (*volatile mcl_sin)(double) = static_cast<double (*)(double)>(std::sin);
-
-// rule 29: the 65536 pairs, formed once a process
-const int2 *mcl_heading_table() {
-  static std::vector<int2> table;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    table.resize(65536);
-    for (int h = 0; h < 65536; ++h) {
-      const double a = 2.0 * M_PI * static_cast<double>(h) / 65536.0;
-      table[h] = make_int2(static_cast<int>(std::lrint(mcl_cos(a) * 65536.0)), static_cast<int>(std::lrint(mcl_sin(a) * 65536.0)));
-    }
-  });
-  return table.data();
-}
-
 // rule 38, in its order
 int mcl_check(float res, size_t N, size_t B, float range_max, const uint16_t *pen, size_t E, int err_shift, const uint32_t *wtab,
               size_t EW, int w_shift, unsigned flags, int *rc_out, long long *zmax_out) {
@@ -632,14 +591,7 @@ int mcl_check(float res, size_t N, size_t B, float range_max, const uint16_t *pe
     if (E > KC_MCL_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu penalty entries are above the cap of %d", E, KC_MCL_MAX_TABLE);
     if (err_shift < 0 || err_shift > 30) KC_FAIL(KC_ERR_INVALID, "err_shift must be in 0 .. 30, got %d", err_shift);
   }
-  if (wtab) {
-    if (EW == 0) KC_FAIL(KC_ERR_INVALID, "an empty weight table");
-    if (EW > KC_MCL_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu weight entries are above the cap of %d", EW, KC_MCL_MAX_TABLE);
-    if (w_shift < 0 || w_shift > 30) KC_FAIL(KC_ERR_INVALID, "w_shift must be in 0 .. 30, got %d", w_shift);
-    if (wtab[0] < 1u || wtab[0] > (1u << 20)) KC_FAIL(KC_ERR_INVALID, "wtab[0] must be in 1 .. 2^20, got %u", wtab[0]);
-    for (size_t i = 1; i < EW; ++i)
-      if (wtab[i] > wtab[i - 1]) KC_FAIL(KC_ERR_INVALID, "the weight table increases at entry %zu", i);
-  }
+  if (wtab) KC_TRY(check_weight_table(wtab, EW, w_shift, KC_MCL_MAX_TABLE));
   if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS | KC_MCL_SKIP_NO_RETURN))
     KC_FAIL(KC_ERR_INVALID, "unknown localiser flag bits 0x%x", flags);
   if (rc_out) *rc_out = rc;
@@ -654,12 +606,7 @@ int mcl_field_check(float res, size_t N, size_t B, float range_max, const uint16
   if (pen_d2) {
     if (n_pen < 2) KC_FAIL(KC_ERR_INVALID, "a field penalty table needs c2 + 1 >= 2 entries, got %zu", n_pen);
     if (n_pen > KC_MCL_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu penalty entries are above the cap of %d", n_pen, KC_MCL_MAX_TABLE);
-    if (reach != 0) {
-      if (reach < 1 || reach > KC_WORLDMAP_DIST_MAX_REACH)
-        KC_FAIL(KC_ERR_RANGE, "reach must be in 1 .. %d cells, got %d", KC_WORLDMAP_DIST_MAX_REACH, reach);
-      if (n_pen - 1 > static_cast<size_t>(reach) * static_cast<size_t>(reach))
-        KC_FAIL(KC_ERR_INVALID, "c2 = %zu is above reach^2 = %d", n_pen - 1, reach * reach);
-    }
+    KC_TRY(check_reach(n_pen, reach));
   }
   KC_TRY(mcl_check(res, N, B, range_max, nullptr, 0, 0, wtab, EW, w_shift, 0u, nullptr, nullptr));
   if (flags & ~static_cast<unsigned>(KC_MCL_SKIP_NO_RETURN))
@@ -672,12 +619,7 @@ int mcl_take_tables(kc_mcl *c, int kind, const uint16_t *pen, size_t n_pen, int 
                     size_t n_wtab, int w_shift) {
   KC_HIP(hipSetDevice(c->device));
   c->kind = KC_MCL_MODEL_NONE;
-  KC_TRY(c->d_pen.reserve(n_pen));
-  KC_TRY(c->d_wtab.reserve(n_wtab));
-  // from the caller's memory: the copies return once the source may be reused or, as here, after the drain
-  KC_HIP(hipMemcpyAsync(c->d_pen.p, pen, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipMemcpyAsync(c->d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));
+  KC_TRY(upload_tables(c->d_pen, pen, n_pen, c->d_wtab, wtab, n_wtab, c->stream));
   c->E = static_cast<int>(n_pen);
   c->err_shift = err_shift;
   c->pen_far = pen_far;
@@ -691,9 +633,7 @@ int mcl_take_tables(kc_mcl *c, int kind, const uint16_t *pen, size_t n_pen, int 
 
 unsigned mcl_blocks(size_t work) { return static_cast<unsigned>((work + kMclBlock - 1) / kMclBlock); }
 
-unsigned long long mcl_key(const kc_mcl *c, unsigned step) {
-  return mcl_mix64(c->seed ^ (static_cast<unsigned long long>(step) << 32));
-}
+unsigned long long mcl_key(const kc_mcl *c, unsigned step) { return q16_key(c->seed, step); }
 
 // rule 50, queued on the context's stream (the device is current): the particles into the map's present offset
 int mcl_follow(kc_mcl *c, const WorldMapView &v) {
@@ -739,7 +679,7 @@ int kc_mcl_check(float resolution, size_t n_particles, size_t n_beams, float ran
 int kc_mcl_heading(uint32_t h, int32_t *cq_out, int32_t *sq_out) {
   if (!cq_out || !sq_out) KC_FAIL(KC_ERR_INVALID, "null argument");
   if (h > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h);
-  const int2 v = mcl_heading_table()[h];
+  const int2 v = heading_table()[h];
   *cq_out = v.x;
   *sq_out = v.y;
   return KC_OK;
@@ -774,17 +714,9 @@ int kc_mcl_create(kc_worldmap *map, size_t n_particles, const double *angles, si
   for (int b = 0; b < 2 && !e; ++b)
     if ((e = c->d_tx[b].reserve(N)) || (e = c->d_ty[b].reserve(N)) || (e = c->d_h[b].reserve(N))) break;
   if (!e && ((e = c->d_acc.reserve(N)) || (e = c->d_cost.reserve(N)) || (e = c->d_w.reserve(N)) || (e = c->d_cum.reserve(N)) ||
-             (e = c->d_min_prev.reserve(1)) || (e = c->d_heading.reserve(65536)) || (e = c->d_zq.reserve(n_beams)) ||
+             (e = c->d_min_prev.reserve(1)) || (e = c->d_zq.reserve(n_beams)) ||
              (e = c->h_zq.reserve(n_beams)) || (e = c->d_rec.reserve(1)) || (e = c->h_rec.reserve(1)) ||
-             (e = c->table.ensure(angles, n_beams, stream)))) {
-  }
-  if (!e) {
-    hipError_t he = hipMemcpyAsync(c->d_heading.p, mcl_heading_table(), 65536 * sizeof(int2), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    if (he != hipSuccess) {
-      set_error("the heading table's upload failed: %s", hipGetErrorString(he));
-      e = KC_ERR_HIP;
-    }
+             (e = c->table.ensure(angles, n_beams, stream)) || (e = upload_heading_table(c->d_heading, stream)))) {
   }
   if (e) {
     kc_mcl_destroy(c);
@@ -849,7 +781,7 @@ int kc_mcl_model_kind(kc_mcl *c, int *kind_out) {
 
 int kc_mcl_init_pose(kc_mcl *c, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s_xy, int32_t s_h) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
-  if (tx0 < -kMclMaxOffset || tx0 > kMclMaxOffset || ty0 < -kMclMaxOffset || ty0 > kMclMaxOffset)
+  if (tx0 < -kQ16MaxOffset || tx0 > kQ16MaxOffset || ty0 < -kQ16MaxOffset || ty0 > kQ16MaxOffset)
     KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
   if (h0 > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h0);
   if (s_xy < 0 || s_h < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
@@ -904,7 +836,7 @@ int kc_mcl_step(kc_mcl *c, int64_t d_f, int64_t d_l, int32_t d_h, int32_t s_f, i
   if (c->kind == KC_MCL_MODEL_NONE) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_set_model or kc_mcl_set_field_model first");
   const bool field = c->kind == KC_MCL_MODEL_FIELD;
   if (!c->inited) KC_FAIL(KC_ERR_STATE, "a step needs kc_mcl_init_pose or kc_mcl_init_global first");
-  if (d_f < -kMclMaxOffset || d_f > kMclMaxOffset || d_l < -kMclMaxOffset || d_l > kMclMaxOffset)
+  if (d_f < -kQ16MaxOffset || d_f > kQ16MaxOffset || d_l < -kQ16MaxOffset || d_l > kQ16MaxOffset)
     KC_FAIL(KC_ERR_RANGE, "the odometry increment is above 2^20 cells");
   if (s_f < 0 || s_l < 0 || s_h < 0) KC_FAIL(KC_ERR_INVALID, "a noise scale is negative");
   if (flags & ~static_cast<unsigned>(KC_SCAN_UNKNOWN_BLOCKS | KC_MCL_SKIP_NO_RETURN))
@@ -1032,7 +964,7 @@ int kc_mcl_resample_inject(kc_mcl *c, size_t n_inject) {
   KC_TRY(mcl_follow(c, v));  // rule 50: the select copies the moved states
   const int N = static_cast<int>(c->N);
   const unsigned long long key = mcl_key(c, c->step);
-  const unsigned long long u0 = mcl_draw(key, c->N, 15) % c->w1;
+  const unsigned long long u0 = q16_draw(key, c->N, 15) % c->w1;
   c->inited = false;
   c->have_weights = false;
   c->inject_time.begin_cycle();

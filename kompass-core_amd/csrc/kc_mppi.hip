@@ -19,38 +19,20 @@
 //  (b) mppi_update_kernel: a workgroup a step t.  It draws X_k[t] again from the counter noise (rule 3 depends on U[t],
 //      k and t only), forms the weights from S_k and the packed minimum, and reduces three int64 numerators and den
 //      exactly.  No K x T x 3 buffer exists.  Workgroup 0 writes the record behind U'.
-// The small inline functions of rule 30 are restated here from kc_mcl.hip, which keeps them to itself.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 #include "kc_internal.h"
+#include "kc_worldmap_walk.h"
 #include "kompass_hip.h"
 
 namespace kc {
 
 constexpr int kMppiBlock = 64;   // the roll-out's workgroup: one wavefront, so that few samples still spread over the CUs
 constexpr int kMppiUpdate = 256;
-constexpr long long kMppiMaxOffset = 1ll << 36;
 constexpr unsigned kMppiCap = 1u << 30;
 
-__host__ __device__ inline unsigned long long mppi_mix64(unsigned long long x) {
-  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__host__ __device__ inline long long mppi_noise(unsigned long long v, int s) {
-  const long long g =
-      static_cast<long long>((v & 0xFFFF) + ((v >> 16) & 0xFFFF) + ((v >> 32) & 0xFFFF) + (v >> 48)) - 131070ll;
-  return (g * s + (1ll << 15)) >> 16;
-}
-__host__ __device__ inline long long mppi_clamp(long long v) {
-  return v < -kMppiMaxOffset ? -kMppiMaxOffset : (v > kMppiMaxOffset ? kMppiMaxOffset : v);
-}
 __host__ __device__ inline long long mppi_within(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct MppiModel {  // rule 2's limits, rule 3's scales
@@ -72,7 +54,7 @@ __host__ __device__ inline void mppi_clamp_u(const MppiModel &m, long long &F, l
 // rule 3's eps of sample k, step t, channel c
 __device__ __forceinline__ long long mppi_eps(const MppiModel &m, unsigned long long key, int k, int t, int c) {
   if (k == 0) return 0;
-  return mppi_noise(mppi_mix64(key ^ ((static_cast<unsigned long long>(k) << 8) | static_cast<unsigned>(3 * t + c))), m.s[c]);
+  return q16_noise(q16_draw(key, k, 3 * t + c), m.s[c]);
 }
 
 // What a step uploads in one copy: the nominal sequence and the start values of the two words the roll-out reduces into
@@ -141,21 +123,19 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     const int2 cs = a.heading[h];
     const long long C = cs.x, S = cs.y;
     if (alive) {
-      tx = mppi_clamp(tx + ((C * F - S * L + (1ll << 15)) >> 16));
-      ty = mppi_clamp(ty + ((S * F + C * L + (1ll << 15)) >> 16));
+      tx = q16_move_x(tx, C, S, F, L);
+      ty = q16_move_y(ty, C, S, F, L);
       h = static_cast<unsigned>((static_cast<long long>(h) + Hc) & 0xFFFF);
     }
     // rule 5
     const long long I = (tx + (1ll << 15)) >> 16, J = (ty + (1ll << 15)) >> 16;
-    unsigned d2 = KC_WORLDMAP_DIST_FAR;
-    if (alive && I >= 0 && I < a.W && J >= 0 && J < a.H)
-      d2 = a.dist2[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)];
+    const unsigned d2 = wm_dist2_at(a.dist2, a.W, a.H, I, J, alive);
     if (alive && d2 <= a.r2) {
       total += static_cast<long long>(a.pen_hit) * (a.T - t);
       hit = true;
       alive = false;
     }
-    if (alive) total += d2 <= static_cast<unsigned>(a.c2) ? s_pen[d2] : a.pen_far;
+    if (alive) total += wm_dist2_pen(d2, a.c2, s_pen, a.pen_far);
     // rule 6: this lane's share of the window, then the team's minimum of the packed key
     unsigned long long best = ~0ull;
     for (int j = sub; j < a.M; j += TEAM) {
@@ -218,8 +198,7 @@ __global__ __launch_bounds__(kMppiUpdate) void mppi_update_kernel(MppiUpdateArgs
   const unsigned s_min = static_cast<unsigned>(min_key >> 32);
   long long sums[4] = {0, 0, 0, 0};  // three numerators (below 2^59) and den
   for (int k = threadIdx.x; k < a.K; k += kMppiUpdate) {
-    const unsigned bin = (a.S[k] - s_min) >> a.w_shift;
-    const long long w = a.wtab[bin < static_cast<unsigned>(a.EW - 1) ? bin : static_cast<unsigned>(a.EW - 1)];
+    const long long w = a.wtab[q16_weight_bin(a.S[k], s_min, a.w_shift, a.EW)];
     long long F = U0 + mppi_eps(a.m, a.key, k, t, 0), L = U1 + mppi_eps(a.m, a.key, k, t, 1), H = U2 + mppi_eps(a.m, a.key, k, t, 2);
     mppi_clamp_u(a.m, F, L, H);
     sums[0] += w * (F - U0);
@@ -294,21 +273,6 @@ struct kc_mppi {
 
 namespace {
 
-// rule 29's table through the localiser's entry, formed once a process
-const int2 *mppi_heading_table() {
-  static std::vector<int2> table;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    table.resize(65536);
-    for (uint32_t h = 0; h < 65536u; ++h) {
-      int32_t c = 0, s = 0;
-      kc_mcl_heading(h, &c, &s);
-      table[h] = make_int2(c, s);
-    }
-  });
-  return table.data();
-}
-
 // rule 12, in its order
 int mppi_check(size_t K, size_t T, size_t M, const int32_t *limits, const int32_t *s3, uint32_t r2, const uint16_t *pen_d2, size_t n_pen,
                uint32_t pen_hit, uint32_t w_path, uint64_t qcap, uint32_t w_goal, int reach, const uint32_t *wtab, size_t EW,
@@ -337,19 +301,9 @@ int mppi_check(size_t K, size_t T, size_t M, const int32_t *limits, const int32_
     if (qcap > (1ull << 40)) KC_FAIL(KC_ERR_RANGE, "qcap is above 2^40");
     if ((qcap >> 16) * w_path > (1ull << 24)) KC_FAIL(KC_ERR_RANGE, "(qcap >> 16) w_path is above 2^24");
     if (w_goal > (1u << 20)) KC_FAIL(KC_ERR_RANGE, "w_goal = %u is above 2^20", w_goal);
-    if (reach != 0) {
-      if (reach < 1 || reach > KC_WORLDMAP_DIST_MAX_REACH)
-        KC_FAIL(KC_ERR_RANGE, "reach must be in 1 .. %d cells, got %d", KC_WORLDMAP_DIST_MAX_REACH, reach);
-      if (n_pen - 1 > static_cast<size_t>(reach) * static_cast<size_t>(reach))
-        KC_FAIL(KC_ERR_INVALID, "c2 = %zu is above reach^2 = %d", n_pen - 1, reach * reach);
-    }
+    KC_TRY(check_reach(n_pen, reach));
     if (!wtab) KC_FAIL(KC_ERR_INVALID, "null weight table");
-    if (EW == 0) KC_FAIL(KC_ERR_INVALID, "an empty weight table");
-    if (EW > KC_MPPI_MAX_TABLE) KC_FAIL(KC_ERR_RANGE, "%zu weight entries are above the cap of %d", EW, KC_MPPI_MAX_TABLE);
-    if (w_shift < 0 || w_shift > 30) KC_FAIL(KC_ERR_INVALID, "w_shift must be in 0 .. 30, got %d", w_shift);
-    if (wtab[0] < 1u || wtab[0] > (1u << 20)) KC_FAIL(KC_ERR_INVALID, "wtab[0] must be in 1 .. 2^20, got %u", wtab[0]);
-    for (size_t i = 1; i < EW; ++i)
-      if (wtab[i] > wtab[i - 1]) KC_FAIL(KC_ERR_INVALID, "the weight table increases at entry %zu", i);
+    KC_TRY(check_weight_table(wtab, EW, w_shift, KC_MPPI_MAX_TABLE));
   }
   return KC_OK;
 }
@@ -389,17 +343,9 @@ int kc_mppi_create(kc_worldmap *map, size_t n_samples, size_t horizon, uint64_t 
   c->T = horizon;
   c->seed = seed;
   int e = KC_OK;
-  if ((e = c->d_heading.reserve(65536)) || (e = c->d_S.reserve(n_samples)) || (e = c->d_px.reserve(KC_MPPI_MAX_PATH)) ||
-      (e = c->d_py.reserve(KC_MPPI_MAX_PATH)) || (e = c->d_in.reserve(1)) || (e = c->h_in.reserve(1)) || (e = c->d_out.reserve(1)) ||
-      (e = c->h_out.reserve(1))) {
-  }
-  if (!e) {
-    hipError_t he = hipMemcpyAsync(c->d_heading.p, mppi_heading_table(), 65536 * sizeof(int2), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    if (he != hipSuccess) {
-      set_error("the heading table's upload failed: %s", hipGetErrorString(he));
-      e = KC_ERR_HIP;
-    }
+  if ((e = c->d_S.reserve(n_samples)) || (e = c->d_px.reserve(KC_MPPI_MAX_PATH)) || (e = c->d_py.reserve(KC_MPPI_MAX_PATH)) ||
+      (e = c->d_in.reserve(1)) || (e = c->h_in.reserve(1)) || (e = c->d_out.reserve(1)) || (e = c->h_out.reserve(1)) ||
+      (e = upload_heading_table(c->d_heading, stream))) {
   }
   if (e) {
     kc_mppi_destroy(c);
@@ -430,12 +376,7 @@ int kc_mppi_set_costs(kc_mppi *c, uint32_t r2, const uint16_t *pen_d2, size_t n_
   KC_TRY(mppi_check(c->K, c->T, 1, nullptr, nullptr, r2, pen_d2, n_pen, pen_hit, w_path, qcap, w_goal, 0, wtab, n_wtab, w_shift));
   KC_HIP(hipSetDevice(c->device));
   c->have_costs = false;
-  KC_TRY(c->d_pen.reserve(n_pen));
-  KC_TRY(c->d_wtab.reserve(n_wtab));
-  // from the caller's memory: the call returns after the drain
-  KC_HIP(hipMemcpyAsync(c->d_pen.p, pen_d2, n_pen * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipMemcpyAsync(c->d_wtab.p, wtab, n_wtab * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  KC_HIP(hipStreamSynchronize(c->stream));
+  KC_TRY(upload_tables(c->d_pen, pen_d2, n_pen, c->d_wtab, wtab, n_wtab, c->stream));
   c->c2 = static_cast<int>(n_pen) - 1;
   c->r2 = r2;
   c->pen_far = pen_far;
@@ -453,7 +394,7 @@ int kc_mppi_set_path(kc_mppi *c, const int64_t *px, const int64_t *py, size_t n)
   if (!c || !px || !py) KC_FAIL(KC_ERR_INVALID, "null argument");
   KC_TRY(mppi_check(c->K, c->T, n, nullptr, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, 0));
   for (size_t j = 0; j < n; ++j)
-    if (px[j] < -kMppiMaxOffset || px[j] > kMppiMaxOffset || py[j] < -kMppiMaxOffset || py[j] > kMppiMaxOffset)
+    if (px[j] < -kQ16MaxOffset || px[j] > kQ16MaxOffset || py[j] < -kQ16MaxOffset || py[j] > kQ16MaxOffset)
       KC_FAIL(KC_ERR_RANGE, "path point %zu lies more than 2^20 cells from the map's origin", j);
   KC_HIP(hipSetDevice(c->device));
   c->M = 0;
@@ -479,7 +420,7 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   if (!c->have_model) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_model first");
   if (!c->have_costs) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_costs first");
   if (c->M == 0) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_path first");
-  if (tx < -kMppiMaxOffset || tx > kMppiMaxOffset || ty < -kMppiMaxOffset || ty > kMppiMaxOffset)
+  if (tx < -kQ16MaxOffset || tx > kQ16MaxOffset || ty < -kQ16MaxOffset || ty > kQ16MaxOffset)
     KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
   if (h > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h);
   const size_t T = c->T;
@@ -505,7 +446,7 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   KC_HIP(hipMemcpyAsync(c->d_in.p, in, sizeof(MppiIn), hipMemcpyHostToDevice, c->stream));
   KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
   KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
-  const unsigned long long key = mppi_mix64(c->seed ^ (static_cast<unsigned long long>(step) << 32));
+  const unsigned long long key = q16_key(c->seed, step);
   MppiRollArgs a{};
   a.heading = c->d_heading.p;
   a.dist2 = dist.dist2;

@@ -83,7 +83,6 @@ constexpr int kWmBlock = 256;
 constexpr int kWmMaxBlocks = 2048;
 constexpr int8_t kWmNever = -128;
 constexpr int kWmMaxSide = 32768;
-constexpr long long kWmMaxOffset = 1ll << 36;  // 2^20 cells in 16 fraction bits
 constexpr int kWmRecWords = 5;             // changed, i_min, j_min, i_max, j_max
 
 struct WmModel {
@@ -516,10 +515,6 @@ struct WmDistArgs {
   unsigned R2;
 };
 
-__device__ __forceinline__ bool wm_dist_blocks(int8_t c, int unknown_blocks) {
-  return c == KC_OCCUPIED || (unknown_blocks && c == KC_UNEXPLORED);
-}
-
 // LDS bytes of a tile at reach R: the blocking bytes of (64 + 2 R)^2 cells, then 64 row distances for 64 + 2 R rows
 __host__ __device__ inline size_t wm_dist_lds(int R) {
   const size_t side = static_cast<size_t>(kWmDistTile + 2 * R);
@@ -543,7 +538,7 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_dist_tile_kernel(WmDistArgs
     const int I = tx0 - R + c, J = ty0 - R + r;
     uint8_t b = 0;
     if (I >= 0 && I < a.W && J >= 0 && J < a.H)
-      b = wm_dist_blocks(a.cls[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)], a.unknown_blocks) ? 1 : 0;
+      b = wm_blocks(a.cls[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W)], a.unknown_blocks) ? 1 : 0;
     blk[k] = b;
   }
   __syncthreads();
@@ -580,8 +575,8 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_dist_rows_kernel(WmDistArgs
   for (int I = a.x0 + static_cast<int>(blockIdx.x * kWmBlock + threadIdx.x); I <= a.x1; I += static_cast<int>(gridDim.x) * kWmBlock) {
     int found = kWmDistNone;
     for (int d = 0; d <= a.R; ++d) {
-      const bool l = I - d >= 0 && wm_dist_blocks(row[I - d], a.unknown_blocks);
-      const bool r = I + d < a.W && wm_dist_blocks(row[I + d], a.unknown_blocks);
+      const bool l = I - d >= 0 && wm_blocks(row[I - d], a.unknown_blocks);
+      const bool r = I + d < a.W && wm_blocks(row[I + d], a.unknown_blocks);
       if (l || r) {
         found = d;
         break;
@@ -668,8 +663,7 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_mark_kernel(WmMarkArgs a) {
   if (!ret && !a.clear_no_return) return;
   const int2 t = a.table[k];
   const long long cq = a.pose.cq, sq = a.pose.sq;
-  const int dx = static_cast<int>((cq * t.x - sq * t.y + (1ll << 15)) >> 16);
-  const int dy = static_cast<int>((sq * t.x + cq * t.y + (1ll << 15)) >> 16);
+  const int dx = static_cast<int>(q16_turn_x(cq, sq, t.x, t.y)), dy = static_cast<int>(q16_turn_y(cq, sq, t.x, t.y));
   const long long X0 = a.pose.tx + (1ll << 15), Y0 = a.pose.ty + (1ll << 15);
   int I = static_cast<int>(X0 >> 16), J = static_cast<int>(Y0 >> 16);
   const int fx = static_cast<int>(X0 & 0xFFFF), fy = static_cast<int>(Y0 & 0xFFFF);
@@ -896,7 +890,7 @@ int wm_check_pose(const kc_worldmap_pose *p) {
   if (!p) KC_FAIL(KC_ERR_INVALID, "null pose");
   if (p->cq < -65536 || p->cq > 65536 || p->sq < -65536 || p->sq > 65536)
     KC_FAIL(KC_ERR_INVALID, "pose (cq, sq) = (%d, %d) is outside -65536 .. 65536", p->cq, p->sq);
-  if (p->tx < -kWmMaxOffset || p->tx > kWmMaxOffset || p->ty < -kWmMaxOffset || p->ty > kWmMaxOffset)
+  if (p->tx < -kQ16MaxOffset || p->tx > kQ16MaxOffset || p->ty < -kQ16MaxOffset || p->ty > kQ16MaxOffset)
     KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
   return KC_OK;
 }
@@ -1492,19 +1486,12 @@ int worldmap_queue_points(const WorldMapView &v, const WorldMapWindow &w, float 
 }
 
 // ---- virtual scan (rules 20 to 27) ----
-namespace {
-// libm's separate cos and sin through pointers, so that the compiler cannot fold the pair into one sincos call (whose
-// bits differ from theirs in about 0.1 % of arguments where glibc picks its FMA builds: kc_dvz.hip has the story)
-double (*volatile scan_cos)(double) = static_cast<double (*)(double)>(std::cos);
-double (*volatile scan_sin)(double) = static_cast<double (*)(double)>(std::sin);
-}  // namespace
-
 int worldmap_scan_table(const double *angles, size_t n, int32_t *out) {
   for (size_t k = 0; k < n; ++k)
     if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
   for (size_t k = 0; k < n; ++k) {
-    out[2 * k] = static_cast<int32_t>(std::lrint(scan_cos(angles[k]) * 1073741824.0));
-    out[2 * k + 1] = static_cast<int32_t>(std::lrint(scan_sin(angles[k]) * 1073741824.0));
+    out[2 * k] = static_cast<int32_t>(std::lrint(host_cos(angles[k]) * 1073741824.0));
+    out[2 * k + 1] = static_cast<int32_t>(std::lrint(host_sin(angles[k]) * 1073741824.0));
   }
   return KC_OK;
 }
@@ -1677,7 +1664,7 @@ int kc_worldmap_quantise_pose(float resolution, double origin_x, double origin_y
     KC_FAIL(KC_ERR_INVALID, "the pose and the origin must be finite");
   const double R = static_cast<double>(resolution);
   const double fx = (px - origin_x) / R * 65536.0, fy = (py - origin_y) / R * 65536.0;
-  const double cap = static_cast<double>(kWmMaxOffset);
+  const double cap = static_cast<double>(kQ16MaxOffset);
   if (!(std::fabs(fx) <= cap + 0.5) || !(std::fabs(fy) <= cap + 0.5))
     KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
   kc_worldmap_pose p;

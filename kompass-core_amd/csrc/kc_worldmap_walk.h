@@ -1,11 +1,13 @@
 // The world map's ray walk (DESIGN.md 4.11 rules 20 to 23 and 25) as one __device__ function: worldmap_scan_kernel
-// (kc_worldmap.hip) turns its result into a double range, mcl_walk_kernel (kc_mcl.hip) into an integer one.
+// (kc_worldmap.hip) turns its result into a double range, mcl_walk_kernel (kc_mcl.hip) into an integer one.  With it
+// the one blocking predicate of the map's readers and the distance plane's lookup (kc_mcl.hip, kc_mppi.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "kc_q16.h"
 #include "kompass_hip.h"
 
 namespace kc {
@@ -13,8 +15,21 @@ namespace kc {
 constexpr int kWmScanS = 8;    // steps of the walk a round: their byte loads are in flight together
 constexpr int kWmScanEnd = 1;  // a step outside rule 23's box; no cls byte has this value
 
-__device__ __forceinline__ bool wm_scan_blocks(int v, int unknown_blocks) {
+// a class byte that ends a beam and seeds the distance plane
+__device__ __forceinline__ bool wm_blocks(int v, int unknown_blocks) {
   return v == KC_OCCUPIED || (unknown_blocks && v == KC_UNEXPLORED);
+}
+
+// rules 42 to 45: the distance plane at cell (I, J), KC_WORLDMAP_DIST_FAR outside the map and for a lane with nothing to
+// look up (live false: an MPPI sample that has hit); one 2-byte load behind one chain of tests (a test of `live` around
+// the call instead changed the roll-out's instructions).  Then the penalty of that entry from a table of c2 + 1
+__device__ __forceinline__ unsigned wm_dist2_at(const unsigned short *dist2, int W, int H, long long I, long long J, bool live = true) {
+  unsigned d2 = KC_WORLDMAP_DIST_FAR;
+  if (live && I >= 0 && I < W && J >= 0 && J < H) d2 = dist2[static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(W)];
+  return d2;
+}
+__device__ __forceinline__ unsigned wm_dist2_pen(unsigned d2, int c2, const unsigned short *pen_d2, unsigned pen_far) {
+  return d2 <= static_cast<unsigned>(c2) ? pen_d2[d2] : pen_far;
 }
 
 // the first blocking cell of a walk: rule 23's candidate (I, J, e, a); a start cell that blocks has e = 0, a = 1
@@ -32,8 +47,7 @@ template <typename Beyond>
 __device__ __forceinline__ bool wm_walk(const int8_t *__restrict__ cls, int W, int H, int rc, int unknown_blocks,
                                         const kc_worldmap_pose &p, int2 t, Beyond beyond, WmWalkHit *h) {
   const long long cq = p.cq, sq = p.sq;
-  const int dx = static_cast<int>((cq * t.x - sq * t.y + (1ll << 15)) >> 16);
-  const int dy = static_cast<int>((sq * t.x + cq * t.y + (1ll << 15)) >> 16);
+  const int dx = static_cast<int>(q16_turn_x(cq, sq, t.x, t.y)), dy = static_cast<int>(q16_turn_y(cq, sq, t.x, t.y));
   const long long X0 = p.tx + (1ll << 15), Y0 = p.ty + (1ll << 15);
   const int I0 = static_cast<int>(X0 >> 16), J0 = static_cast<int>(Y0 >> 16);
   const int fx = static_cast<int>(X0 & 0xFFFF), fy = static_cast<int>(Y0 & 0xFFFF);
@@ -46,7 +60,7 @@ __device__ __forceinline__ bool wm_walk(const int8_t *__restrict__ cls, int W, i
   const int box = rc + 1;
   int I = I0, J = J0;
   if (I0 >= 0 && I0 < W && J0 >= 0 && J0 < H &&
-      wm_scan_blocks(cls[static_cast<size_t>(I0) + static_cast<size_t>(J0) * static_cast<size_t>(W)], unknown_blocks)) {
+      wm_blocks(cls[static_cast<size_t>(I0) + static_cast<size_t>(J0) * static_cast<size_t>(W)], unknown_blocks)) {
     *h = WmWalkHit{0, 1, I0, J0};  // rule 23: e = 0
     return true;
   }
@@ -80,7 +94,7 @@ __device__ __forceinline__ bool wm_walk(const int8_t *__restrict__ cls, int W, i
 #pragma unroll
     for (int s = 0; s < kWmScanS; ++s) {
       if (v[s] == kWmScanEnd) return false;
-      if (wm_scan_blocks(v[s], unknown_blocks)) {
+      if (wm_blocks(v[s], unknown_blocks)) {
         const int nx = __popc(xmask & ((2u << s) - 1u));
         *h = WmWalkHit{es[s], (xmask >> s) & 1u ? adx : ady, Is + sx * nx, Js + sy * (s + 1 - nx)};
         return true;
