@@ -1729,7 +1729,7 @@ int kc_mcl_resample_inject(kc_mcl *ctx, size_t n_inject);
 int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
 
 /* ------------------------------------------------------------------------ */
-/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 12) */
+/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 18) */
 /* ------------------------------------------------------------------------ */
 /* Nothing in the reference to cite: its controllers commit to one velocity for the whole
  * look-ahead.  K noisy control sequences of T steps around a nominal one, rolled out in the
@@ -1783,19 +1783,46 @@ int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
  * entries, KC_ERR_RANGE above 4096, KC_ERR_INVALID for r2 > c2, KC_ERR_RANGE for pen_hit above
  * 2^20, w_path above 2^16, qcap above 2^40, (qcap >> 16) w_path above 2^24, w_goal above 2^20,
  * in that order; reach (skipped when 0): KC_ERR_RANGE outside 1 .. 254, KC_ERR_INVALID for c2 >
- * reach^2; then wtab as kc_mcl_check has it (KC_ERR_INVALID when NULL). */
+ * reach^2; then wtab as kc_mcl_check has it (KC_ERR_INVALID when NULL).
+ * Moving obstacles, costed at each roll-out step's own time (tests/mppi_movers_ref.py states
+ * rules 13 to 18; with no mover every result is rules 1 to 12's, bit for bit):
+ * Rule 13, movers: 0 <= N <= 64, each (OX, OY, VX, VY, hq, sq, g).  OX, OY: int64 in the
+ * state's units and the map's present offset, valid at the time of the step's pose, |.| <=
+ * 2^36.  VX, VY: int32 displacements a control step, |.| <= 2^22.  hq <= sq <= 2^40: uint64
+ * squared centre distances in rule 6's q units, the hit distance and where the soft term
+ * begins.  g <= 2^32: the ramp's gain, with (((sq - hq) >> 16) g) >> 16 <= 2^20.  pen_hit_mv <=
+ * 2^20 is one value for all movers.
+ * Rule 14, position: at the state after step t mover i stands at OX_i + (t + 1) VX_i, OY_i + (t
+ * + 1) VY_i, exact and unclamped.  dx = (TX - OXt) >> 8, dy alike (|.| < 2^30), q_i = min(dx^2 +
+ * dy^2, 2^40).
+ * Rule 15, order inside a step: rule 4 moves the state, rule 5 tests the plane; a sample that
+ * hit the plane is frozen as before and rule 16 is not evaluated for it at that state or later
+ * (a static hit wins a tie).  A sample still alive meets rule 16, then rule 5's penalty, then
+ * rule 6.
+ * Rule 16, mover term: any q_i <= hq_i: the sample has hit; it adds pen_hit_mv (T - t), is
+ * frozen and adds nothing more from rules 5, 6 and 16.  Otherwise it adds the sum over i of q_i
+ * < sq_i ? (((sq_i - q_i) >> 16) g_i) >> 16 : 0, a ramp in the squared distance.  Rule 7's jm
+ * is that of the last state rule 6 saw.
+ * Rule 17, record: n_hit counts samples ended by either kind of hit, n_hit_moving those a
+ * mover ended; 0 with no mover.
+ * Rule 18, refusals: kc_mppi_check_movers (host only), in this order: N = 0 is never an error;
+ * KC_ERR_RANGE above 64 movers; KC_ERR_INVALID for a NULL array; KC_ERR_RANGE for pen_hit_mv
+ * above 2^20; then mover by mover in index order KC_ERR_RANGE for a position beyond 2^36, then
+ * a velocity beyond 2^22, KC_ERR_INVALID for hq > sq, KC_ERR_RANGE for sq above 2^40, then g
+ * above 2^32, then the ramp's top above 2^20. */
 typedef struct kc_mppi kc_mppi;
 #define KC_MPPI_MAX_SAMPLES 65536
 #define KC_MPPI_MAX_HORIZON 64
 #define KC_MPPI_MAX_PATH 256
 #define KC_MPPI_MAX_TABLE 4096
-typedef struct kc_mppi_record { /* rule 11 */
+#define KC_MPPI_MAX_MOVERS 64
+typedef struct kc_mppi_record { /* rules 11 and 17 */
   uint64_t den;                 /* sum of the weights */
   uint32_t s_min, k_best;       /* rule 8 */
   uint32_t s_0;                 /* the nominal sequence's cost */
-  uint32_t n_hit;               /* samples that hit */
+  uint32_t n_hit;               /* samples that hit, the plane or a mover */
   uint32_t step;                /* the call's */
-  uint32_t reserved;            /* 0 */
+  uint32_t n_hit_moving;        /* those among them that a mover ended; 0 with no mover */
 } kc_mppi_record;
 int kc_mppi_check(size_t n_samples, size_t horizon, size_t n_path, const int32_t *limits_or_null, const int32_t *s_or_null, uint32_t r2,
                   const uint16_t *pen_d2_or_null, size_t n_pen, uint32_t pen_hit, uint32_t w_path, uint64_t qcap, uint32_t w_goal,
@@ -1813,6 +1840,16 @@ int kc_mppi_set_costs(kc_mppi *ctx, uint32_t r2, const uint16_t *pen_d2, size_t 
 /* rule 6's window, in the map's present offset (rule 46): KC_ERR_INVALID for none, KC_ERR_RANGE
  * above 256 points or for a coordinate beyond +-2^36 */
 int kc_mppi_set_path(kc_mppi *ctx, const int64_t *px, const int64_t *py, size_t n);
+/* rule 18's refusals of a list of n movers; host only, needs no device */
+int kc_mppi_check_movers(const int64_t *ox, const int64_t *oy, const int32_t *vx, const int32_t *vy, const uint64_t *hq,
+                         const uint64_t *sq, const uint64_t *g, size_t n, uint32_t pen_hit_mv);
+/* rule 13's list, in the map's present offset and at the time of the next step's pose; checked
+ * as kc_mppi_check_movers does, then uploaded on the context's stream (one copy of 3 KB; the
+ * call returns with it over).  It holds for every later step until the next call; n = 0 clears
+ * it, and the steps after that are those of a context that never had one.  A refused call
+ * leaves the list as it was. */
+int kc_mppi_set_movers(kc_mppi *ctx, const int64_t *ox, const int64_t *oy, const int32_t *vx, const int32_t *vy, const uint64_t *hq,
+                       const uint64_t *sq, const uint64_t *g, size_t n, uint32_t pen_hit_mv);
 /* One step (rules 3 to 11): two launches (mppi_rollout_kernel, mppi_update_kernel) behind the
  * plane's refresh and an event on the map's stream, and one read-back of U' and the record;
  * returns with both final.  u_in, u_out: T x 3 int32 (F, L, H a step); they may be one array.

@@ -791,13 +791,31 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def_readwrite("reach", &MPPI::Config::reach)
         .def_readwrite("allow_reverse", &MPPI::Config::allow_reverse)
         .def_readwrite("min_turning_radius", &MPPI::Config::min_turning_radius)
-        .def_readwrite("seed", &MPPI::Config::seed);
+        .def_readwrite("seed", &MPPI::Config::seed)
+        .def_readwrite("mover_margin", &MPPI::Config::mover_margin)
+        .def_readwrite("mover_weight", &MPPI::Config::mover_weight)
+        .def_readwrite("mover_hit_penalty", &MPPI::Config::mover_hit_penalty);
+    using Mover = Control::MovingObstacle;
+    py::class_<Mover>(c, "MovingObstacle", "A disc that moves in a straight line: world metres and m/s at the time of the state")
+        .def(py::init([](double x, double y, double vx, double vy, double radius) { return Mover{x, y, vx, vy, radius}; }),
+             py::arg("x") = 0.0, py::arg("y") = 0.0, py::arg("vx") = 0.0, py::arg("vy") = 0.0, py::arg("radius") = 0.0)
+        .def_readwrite("x", &Mover::x)
+        .def_readwrite("y", &Mover::y)
+        .def_readwrite("vx", &Mover::vx)
+        .def_readwrite("vy", &Mover::vy)
+        .def_readwrite("radius", &Mover::radius);
+    auto movers_tuple = [](const MPPI::Movers &m) {
+      return py::make_tuple(m.ox, m.oy, m.vx, m.vy, m.hq, m.sq, m.g, m.pen_hit, m.dropped);
+    };
     py::class_<MPPI, Control::Follower>(c, "MPPI")
         .def(py::init<Control::ControlType, const Control::ControlLimitsParams &, double, const MPPI::Config &>(),
              py::arg("control_type"), py::arg("control_limits"), py::arg("time_step"), py::arg("config") = MPPI::Config())
         .def("execute", &MPPI::execute, py::arg("world_map"), py::arg("current_position"),
              "One MPPI step over the world map's distance plane: two launches and one read-back")
         .def("reset_sequence", &MPPI::resetSequence)
+        .def("set_moving_obstacles", &MPPI::setMovingObstacles, py::arg("obstacles"),
+             "the moving obstacles of the steps to come, at the time of the next step's state; kept until replaced or cleared")
+        .def_property_readonly("moving_obstacles", &MPPI::movingObstacles)
         .def("set_follower_params", [](MPPI &m, const Control::Follower::FollowerParameters &p) { m.setParams(p); }, py::arg("params"),
              "the Follower's own parameters: goal tolerances, interpolation and segment lengths")
         .def("controls", &MPPI::controls, py::arg("n"), "the first n controls of the new sequence as (vx, vy, omega)")
@@ -808,7 +826,9 @@ PYBIND11_MODULE(kompass_cpp, m) {
                const kc_mppi_record &r = m.lastRecord();
                return py::make_tuple(r.s_min, r.k_best, r.s_0, r.den, r.n_hit, r.step);
              }, "(s_min, k_best, s_0, den, n_hit, step) of the last step")
-        .def_property_readonly("last_inputs", [](const MPPI &m) {
+        .def_property_readonly("last_n_hit_moving", [](const MPPI &m) { return m.lastRecord().n_hit_moving; },
+                               "the samples among n_hit that a moving obstacle ended in the last step")
+        .def_property_readonly("last_inputs", [movers_tuple](const MPPI &m) {
                const MPPI::Inputs &i = m.lastInputs();
                py::dict d;
                d["tx"] = i.tx;
@@ -818,6 +838,7 @@ PYBIND11_MODULE(kompass_cpp, m) {
                d["px"] = i.px;
                d["py"] = i.py;
                d["u"] = i.u;
+               d["movers"] = movers_tuple(i.movers);
                return d;
              }, "the last step's inputs as the device took them")
         .def_static("quantise", [](Control::ControlType type, const Control::ControlLimitsParams &lim, double dt, float res,
@@ -829,7 +850,23 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def_static("costs_of", [](const MPPI::Config &cfg) {
                const MPPI::Costs t = MPPI::costsOf(cfg);
                return py::make_tuple(t.r2, t.pen_d2, t.pen_far, t.pen_hit, t.w_path, t.qcap, t.w_goal, t.wtab, t.w_shift);
-             }, py::arg("config"), "(r2, pen_d2, pen_far, pen_hit, w_path, qcap, w_goal, wtab, w_shift): host only");
+             }, py::arg("config"), "(r2, pen_d2, pen_far, pen_hit, w_path, qcap, w_goal, wtab, w_shift): host only")
+        .def_static("movers_of", [movers_tuple](const std::vector<Mover> &obstacles, double dt, float res, double ox, double oy, double x,
+                                                double y, const MPPI::Config &cfg) {
+               return movers_tuple(MPPI::moversOf(obstacles, dt, res, ox, oy, x, y, cfg));
+             }, py::arg("obstacles"), py::arg("time_step"), py::arg("resolution"), py::arg("origin_x"), py::arg("origin_y"),
+             py::arg("robot_x"), py::arg("robot_y"), py::arg("config"),
+             "(OX, OY, VX, VY, hq, sq, g, pen_hit_mv, dropped) against the origin given: host only")
+        .def_static("from_tracked_box", [](const std::array<float, 3> &center, const std::array<float, 3> &size,
+                                           const std::array<float, 3> &vel) {
+               Bbox3D b;
+               b.center = {center[0], center[1], center[2]};
+               b.size = {size[0], size[1], size[2]};
+               TrackedBbox3D t(b);
+               t.vel = {vel[0], vel[1], vel[2]};
+               return MPPI::fromTrackedBox(t);
+             }, py::arg("center"), py::arg("size"), py::arg("vel"),
+             "the MovingObstacle of a TrackedBbox3D that already lies in the world frame: centre, vel, hypot(size.x, size.y) / 2");
   }
 
   // PurePursuit (bindings_control.cpp:159-207)

@@ -5,11 +5,17 @@
 // quantises the limits, the sigmas, the pose and the path window once each, keeps the nominal sequence between steps
 // (the warm start: shifted by one after every step) and turns the first control of the new sequence into a command.
 // Path, closest point and goal test are the Follower's.
+//
+// Moving obstacles (rules 13 to 18): a list of discs with a velocity in the world, kept until replaced or cleared, and
+// quantised at every step against the map's origin of that step.  The device costs each at the time of each roll-out
+// step; finding them, and keeping them out of the map's cells, is the caller's.
 #pragma once
 
 #include <array>
 #include <cstdint>
 #include <vector>
+
+#include "datatypes/tracking.h"
 
 #include "controllers/follower.h"
 #include "mapping/world_map.h"
@@ -36,6 +42,16 @@ struct MPPIConfig {
   bool allow_reverse = false;                        // F_lo = -F_hi instead of 0
   double min_turning_radius = 0.5;                   // metres, ACKERMANN only: kq = lrint(65536 / (2 pi R / resolution))
   uint64_t seed = 0;
+  // Moving obstacles.  Judgement too, and tried only on the crossing scene of DESIGN.md 4.12: a mover is hit inside
+  // hit_radius + its own radius (cells), the ramp starts mover_margin cells farther out and is mover_weight at its top
+  double mover_margin = 4.0;                         // cells
+  double mover_weight = 200.0;
+  uint32_t mover_hit_penalty = 4000;
+};
+
+// A disc that moves in a straight line: world metres and m/s at the time of the state handed to execute()
+struct MovingObstacle {
+  double x = 0.0, y = 0.0, vx = 0.0, vy = 0.0, radius = 0.0;
 };
 
 class MPPI : public Follower {
@@ -55,11 +71,19 @@ class MPPI : public Follower {
     std::vector<uint32_t> wtab;
     int w_shift = 0;
   };
+  struct Movers {  // ... and to kc_mppi_set_movers
+    std::vector<int64_t> ox, oy;
+    std::vector<int32_t> vx, vy;
+    std::vector<uint64_t> hq, sq, g;
+    uint32_t pen_hit = 0;
+    size_t dropped = 0;  // obstacles beyond the 64 nearest
+  };
   struct Inputs {  // the last step's, as the device took them
     int64_t tx = 0, ty = 0;
     uint32_t h = 0, step = 0;
     std::vector<int64_t> px, py;
     std::vector<int32_t> u;  // T x 3
+    Movers movers;
   };
 
   MPPI(ControlType type, const ControlLimitsParams &limits, double time_step, const Config &config = Config());
@@ -68,6 +92,12 @@ class MPPI : public Follower {
   // is enabled at config.reach when it is off or too short for the clearance; the map's cells are not changed.
   Controller::Result execute(const Mapping::WorldMap &map, const Path::State &state);
   void resetSequence();
+  // The moving obstacles of the steps to come, at the time of the state of the next execute(); kept until replaced or
+  // cleared (an empty list).  More than 64: the 64 nearest to the robot are kept at every step, logged once.
+  void setMovingObstacles(std::vector<MovingObstacle> obstacles);
+  const std::vector<MovingObstacle> &movingObstacles() const { return movers_; }
+  // A tracked box that already lies in the world frame: its centre, its velocity, half its footprint's diagonal
+  static MovingObstacle fromTrackedBox(const TrackedBbox3D &box);
 
   const Config &mppiConfig() const { return cfg_; }
   double timeStep() const { return dt_; }
@@ -84,6 +114,12 @@ class MPPI : public Follower {
   // ---- the host side's arithmetic, static: needs no device ----
   static Quantised quantise(ControlType type, const ControlLimitsParams &limits, double time_step, float resolution, const Config &c);
   static Costs costsOf(const Config &c);
+  // The list in rule 13's integers against the origin (ox, oy): positions as the pose is quantised, V = llrint(v dt / res
+  // 65536), hq = llrint((hit_radius + radius / res)^2 65536), sq likewise with + mover_margin, g = floor(mover_weight
+  // 65536 / (((sq - hq) >> 16) + 1)).  (x, y): the robot, which picks the 64 nearest when there are more.  A quantity
+  // beyond rule 13's bounds throws std::out_of_range naming the mover.
+  static Movers moversOf(const std::vector<MovingObstacle> &obstacles, double time_step, float resolution, double ox, double oy,
+                         double x, double y, const Config &c);
 
  private:
   using Handle = hip::Handle<kc_mppi, kc_mppi_destroy>;
@@ -97,6 +133,8 @@ class MPPI : public Follower {
   uint32_t step_ = 0;
   Inputs in_;
   kc_mppi_record rec_ = {};
+  std::vector<MovingObstacle> movers_;
+  bool movers_on_device_ = false, logged_drop_ = false;
 
   void bind(const Mapping::WorldMap &map);
   void buildWindow(const Mapping::WorldMap &map);

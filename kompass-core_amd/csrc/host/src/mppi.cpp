@@ -3,7 +3,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <numeric>
 #include <stdexcept>
+#include <string>
 
 #include "mapping/mcl.h"
 
@@ -28,7 +30,62 @@ MPPI::MPPI(ControlType type, const ControlLimitsParams &limits, double time_step
   const Costs c = costsOf(cfg_);  // refuses a bad configuration before a device is looked for
   hip::check(kc_mppi_check(cfg_.samples, cfg_.horizon, cfg_.window, nullptr, nullptr, c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_hit,
                            c.w_path, c.qcap, c.w_goal, cfg_.reach, c.wtab.data(), c.wtab.size(), c.w_shift));
+  if (!(cfg_.mover_margin >= 0.0) || !(cfg_.mover_margin <= 1024.0) || !(cfg_.mover_weight >= 0.0) || !(cfg_.mover_weight <= 1048576.0) ||
+      cfg_.mover_hit_penalty > (1u << 20))
+    throw std::invalid_argument("MPPI moving-obstacle configuration out of range");
   resetSequence();
+}
+
+void MPPI::setMovingObstacles(std::vector<MovingObstacle> obstacles) { movers_ = std::move(obstacles); }
+
+MovingObstacle MPPI::fromTrackedBox(const TrackedBbox3D &b) {
+  return {static_cast<double>(b.box.center.x()), static_cast<double>(b.box.center.y()), static_cast<double>(b.vel.x()),
+          static_cast<double>(b.vel.y()), std::hypot(static_cast<double>(b.box.size.x()), static_cast<double>(b.box.size.y())) / 2.0};
+}
+
+MPPI::Movers MPPI::moversOf(const std::vector<MovingObstacle> &obstacles, double time_step, float resolution, double ox, double oy,
+                            double x, double y, const Config &c) {
+  const double r = static_cast<double>(resolution);
+  if (!(r > 0.0) || !std::isfinite(r)) throw std::invalid_argument("the resolution must be positive");
+  if (!(time_step > 0.0) || !std::isfinite(time_step)) throw std::invalid_argument("the control time step must be positive");
+  Movers m;
+  m.pen_hit = c.mover_hit_penalty;
+  std::vector<size_t> pick(obstacles.size());
+  std::iota(pick.begin(), pick.end(), size_t{0});
+  if (pick.size() > KC_MPPI_MAX_MOVERS) {  // the nearest to the robot now, the lower index among equals; kept in index order
+    std::stable_sort(pick.begin(), pick.end(), [&](size_t a, size_t b) {
+      return std::hypot(obstacles[a].x - x, obstacles[a].y - y) < std::hypot(obstacles[b].x - x, obstacles[b].y - y);
+    });
+    m.dropped = pick.size() - KC_MPPI_MAX_MOVERS;
+    pick.resize(KC_MPPI_MAX_MOVERS);
+    std::sort(pick.begin(), pick.end());
+  }
+  for (const size_t i : pick) {
+    const MovingObstacle &o = obstacles[i];
+    auto refuse = [&](const char *what) { throw std::out_of_range("moving obstacle " + std::to_string(i) + ": " + what); };
+    if (!std::isfinite(o.x) || !std::isfinite(o.y) || !std::isfinite(o.vx) || !std::isfinite(o.vy) || !std::isfinite(o.radius) ||
+        o.radius < 0.0)
+      refuse("a value is not finite or the radius is negative");
+    const double fx = (o.x - ox) / r * 65536.0, fy = (o.y - oy) / r * 65536.0;  // as the pose is quantised
+    const double pos_cap = 68719476736.0, vel_cap = 4194304.0, q_cap = 1099511627776.0;  // 2^36, 2^22, 2^40
+    if (!(std::fabs(fx) <= pos_cap + 0.5) || !(std::fabs(fy) <= pos_cap + 0.5)) refuse("it lies more than 2^20 cells from the map's origin");
+    const double vx = o.vx * time_step / r * 65536.0, vy = o.vy * time_step / r * 65536.0;
+    if (!(std::fabs(vx) <= vel_cap) || !(std::fabs(vy) <= vel_cap)) refuse("it moves more than 64 cells a control step");
+    const double hit = c.hit_radius + o.radius / r, soft = hit + c.mover_margin;
+    const double hq = hit * hit * 65536.0, sq = soft * soft * 65536.0;
+    if (!(sq <= q_cap)) refuse("its soft distance is above 4096 cells");
+    m.ox.push_back(std::llrint(fx));
+    m.oy.push_back(std::llrint(fy));
+    m.vx.push_back(static_cast<int32_t>(std::llrint(vx)));
+    m.vy.push_back(static_cast<int32_t>(std::llrint(vy)));
+    m.hq.push_back(static_cast<uint64_t>(std::llrint(hq)));
+    m.sq.push_back(static_cast<uint64_t>(std::llrint(sq)));
+    m.g.push_back(static_cast<uint64_t>(std::floor(c.mover_weight * 65536.0 / static_cast<double>(((m.sq.back() - m.hq.back()) >> 16) + 1))));
+  }
+  // what is left of rule 18 (a rounding at a bound, the gain, the ramp's top) is the library's to refuse
+  hip::check(kc_mppi_check_movers(m.ox.data(), m.oy.data(), m.vx.data(), m.vy.data(), m.hq.data(), m.sq.data(), m.g.data(), m.ox.size(),
+                                  m.pen_hit));
+  return m;
 }
 
 void MPPI::resetSequence() {
@@ -87,6 +144,7 @@ void MPPI::bind(const Mapping::WorldMap &map) {
   if (have == 0 || have * have < c2) hip::check(kc_worldmap_set_distance(map.hipContext(), std::max(cfg_.reach, have), 0u));
   if (bound_ == map.hipContext() && ctx_) return;
   ctx_ = hip::make<Handle>(kc_mppi_create, map.hipContext(), cfg_.samples, cfg_.horizon, cfg_.seed);
+  movers_on_device_ = false;
   bound_ = map.hipContext();
   hip::check(kc_mppi_set_costs(ctx_.get(), c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_far, c.pen_hit, c.w_path, c.qcap, c.w_goal,
                                c.wtab.data(), c.wtab.size(), c.w_shift));
@@ -154,6 +212,17 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
   in_.h = Mapping::MCL::quantiseHeading(state.yaw);
   in_.step = step_;
   in_.u = u_;
+  in_.movers = moversOf(movers_, dt_, res_, ox_, oy_, state.x, state.y, cfg_);
+  if (in_.movers.dropped != 0 && !logged_drop_) {
+    LOG_WARNING("MPPI takes the ", KC_MPPI_MAX_MOVERS, " moving obstacles nearest to the robot; ", in_.movers.dropped, " more were given");
+    logged_drop_ = true;
+  }
+  if (!in_.movers.ox.empty() || movers_on_device_) {  // an empty list after a full one clears it; none at all costs nothing
+    const Movers &mv = in_.movers;
+    hip::check(kc_mppi_set_movers(ctx_.get(), mv.ox.data(), mv.oy.data(), mv.vx.data(), mv.vy.data(), mv.hq.data(), mv.sq.data(), mv.g.data(),
+                                  mv.ox.size(), mv.pen_hit));
+    movers_on_device_ = !mv.ox.empty();
+  }
   out_.assign(cfg_.horizon * 3, 0);
   hip::check(kc_mppi_step(ctx_.get(), in_.tx, in_.ty, in_.h, in_.u.data(), in_.step, out_.data(), &rec_));
   ++step_;

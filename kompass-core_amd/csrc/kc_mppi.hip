@@ -1,4 +1,4 @@
-// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 12).
+// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 18).
 //
 // Nothing in the reference to restate: its controllers commit to one velocity for the whole look-ahead.  K noisy
 // control sequences of T steps are drawn around a nominal one, rolled out from the robot's state in the localiser's
@@ -19,6 +19,12 @@
 //  (b) mppi_update_kernel: a workgroup a step t.  It draws X_k[t] again from the counter noise (rule 3 depends on U[t],
 //      k and t only), forms the weights from S_k and the packed minimum, and reduces three int64 numerators and den
 //      exactly.  No K x T x 3 buffer exists.  Workgroup 0 writes the record behind U'.
+//
+// Moving obstacles (rules 13 to 18) are one more term inside (a): mppi_rollout_kernel<TEAM, true> runs while the context
+// holds a list, <TEAM, false> (the code without the term) while it holds none.  The list lies in LDS as seven arrays, 3 KB;
+// a team splits it by i = sub, sub + TEAM, ... as it splits the path window, adds its soft sums by shuffles and ORs its
+// hits by shuffles.  A mover's place at step t is OX + (t + 1) VX, formed where it is used.  The samples a mover ended
+// are one more ballot and one more atomic add a wavefront, into the word of the step's upload that was padding.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -60,7 +66,7 @@ __device__ __forceinline__ long long mppi_eps(const MppiModel &m, unsigned long 
 // What a step uploads in one copy: the nominal sequence and the start values of the two words the roll-out reduces into
 struct MppiIn {
   unsigned long long min_key;  // S_k << 32 | k, ~0 at the start
-  unsigned n_hit, pad;
+  unsigned n_hit, n_hit_mv;    // both 0 at the start; n_hit_mv: the hits by a mover among n_hit (rule 17)
   int U[KC_MPPI_MAX_HORIZON * 3];
 };
 // and what it reads back in one copy
@@ -68,6 +74,14 @@ struct MppiOut {
   int U[KC_MPPI_MAX_HORIZON * 3];
   kc_mppi_record rec;
 };
+
+// rule 13's list as the device holds it: what kc_mppi_set_movers uploads in one copy
+struct MppiMovers {
+  long long ox[KC_MPPI_MAX_MOVERS], oy[KC_MPPI_MAX_MOVERS];
+  unsigned long long hq[KC_MPPI_MAX_MOVERS], sq[KC_MPPI_MAX_MOVERS], g[KC_MPPI_MAX_MOVERS];
+  int vx[KC_MPPI_MAX_MOVERS], vy[KC_MPPI_MAX_MOVERS];
+};
+constexpr unsigned long long kMppiMoverCap = 1ull << 40;  // rule 14's cap of q
 
 struct MppiRollArgs {
   const int2 *heading;           // rule 29
@@ -81,9 +95,13 @@ struct MppiRollArgs {
   long long tx, ty;
   unsigned h, r2, pen_far, pen_hit, w_path, w_goal;
   int W, H, K, T, M, c2;
+  // rules 13 to 16, read by the MOVERS instantiations alone
+  const MppiMovers *movers;
+  int N;
+  unsigned pen_hit_mv;
 };
 
-template <int TEAM>
+template <int TEAM, bool MOVERS>
 __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a) {
   __shared__ unsigned short s_pen[KC_MPPI_MAX_TABLE];
   __shared__ long long s_px[KC_MPPI_MAX_PATH], s_py[KC_MPPI_MAX_PATH];
@@ -94,13 +112,28 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     s_py[i] = a.py[i];
   }
   for (int i = threadIdx.x; i < 3 * a.T; i += kMppiBlock) s_U[i] = a.in->U[i];
+  __shared__ long long s_ox[MOVERS ? KC_MPPI_MAX_MOVERS : 1], s_oy[MOVERS ? KC_MPPI_MAX_MOVERS : 1];
+  __shared__ unsigned long long s_hq[MOVERS ? KC_MPPI_MAX_MOVERS : 1], s_sq[MOVERS ? KC_MPPI_MAX_MOVERS : 1],
+      s_g[MOVERS ? KC_MPPI_MAX_MOVERS : 1];
+  __shared__ int s_vx[MOVERS ? KC_MPPI_MAX_MOVERS : 1], s_vy[MOVERS ? KC_MPPI_MAX_MOVERS : 1];
+  if constexpr (MOVERS) {
+    for (int i = threadIdx.x; i < a.N; i += kMppiBlock) {  // N <= 64: one pass
+      s_ox[i] = a.movers->ox[i];
+      s_oy[i] = a.movers->oy[i];
+      s_hq[i] = a.movers->hq[i];
+      s_sq[i] = a.movers->sq[i];
+      s_g[i] = a.movers->g[i];
+      s_vx[i] = a.movers->vx[i];
+      s_vy[i] = a.movers->vy[i];
+    }
+  }
   __syncthreads();
   const int lane = static_cast<int>(threadIdx.x);
   const int k = (static_cast<int>(blockIdx.x) * kMppiBlock + lane) / TEAM, sub = lane % TEAM;  // K TEAM <= 2^19
   const bool live = k < a.K;  // a whole team, or none of it
   long long tx = a.tx, ty = a.ty;
   unsigned h = a.h;
-  bool alive = live, hit = false;
+  bool alive = live, hit = false, hit_mv = false;
   long long total = 0;
   int jm = 0;
   for (int t = 0; t < a.T; ++t) {
@@ -134,6 +167,32 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
       total += static_cast<long long>(a.pen_hit) * (a.T - t);
       hit = true;
       alive = false;
+    }
+    // rules 14 to 16, behind rule 5's test (a static hit wins) and before its penalty: this lane's share of the list,
+    // then the team's sum and its OR.  A frozen sample goes through it masked, like rule 6 below
+    if constexpr (MOVERS) {
+      long long soft = 0;  // at most 64 tops of 2^20
+      int struck = 0;
+      for (int i = sub; i < a.N; i += TEAM) {
+        const long long mx = s_ox[i] + static_cast<long long>(t + 1) * s_vx[i], my = s_oy[i] + static_cast<long long>(t + 1) * s_vy[i];
+        const long long dx = static_cast<int>((tx - mx) >> 8), dy = static_cast<int>((ty - my) >> 8);  // |.| < 2^30
+        unsigned long long q = static_cast<unsigned long long>(dx * dx + dy * dy);
+        q = q < kMppiMoverCap ? q : kMppiMoverCap;
+        const unsigned long long sq = s_sq[i];
+        struck |= q <= s_hq[i] ? 1 : 0;
+        soft += q < sq ? static_cast<long long>((((sq - q) >> 16) * s_g[i]) >> 16) : 0;  // 2^24 2^32 before the shift
+      }
+#pragma unroll
+      for (int off = TEAM / 2; off > 0; off >>= 1) {
+        soft += __shfl_xor(soft, off, TEAM);
+        struck |= __shfl_xor(struck, off, TEAM);
+      }
+      if (alive && struck != 0) {
+        total += static_cast<long long>(a.pen_hit_mv) * (a.T - t);
+        hit = hit_mv = true;
+        alive = false;
+      }
+      if (alive) total += soft;
     }
     if (alive) total += wm_dist2_pen(d2, a.c2, s_pen, a.pen_far);
     // rule 6: this lane's share of the window, then the team's minimum of the packed key
@@ -169,6 +228,10 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
   if (lane == 0) {
     if (key != ~0ull) atomicMin(&a.in->min_key, key);
     if (hits != 0ull) atomicAdd(&a.in->n_hit, static_cast<unsigned>(__popcll(hits)));
+  }
+  if constexpr (MOVERS) {
+    const unsigned long long hits_mv = __ballot(writer && hit_mv);
+    if (lane == 0 && hits_mv != 0ull) atomicAdd(&a.in->n_hit_mv, static_cast<unsigned>(__popcll(hits_mv)));
   }
 }
 
@@ -237,7 +300,7 @@ __global__ __launch_bounds__(kMppiUpdate) void mppi_update_kernel(MppiUpdateArgs
     r.s_0 = a.S[0];
     r.n_hit = a.in->n_hit;
     r.step = a.step;
-    r.reserved = 0;
+    r.n_hit_moving = a.in->n_hit_mv;
     a.out->rec = r;
   }
 }
@@ -268,6 +331,9 @@ struct kc_mppi {
   int team = 8;  // lanes a sample: the fastest of 1, 4 and 8 at both measured shapes
   unsigned r2 = 0, pen_far = 0, pen_hit = 0, w_path = 0, w_goal = 0;
   unsigned long long qcap = 0;
+  DevBuf<MppiMovers> d_movers;  // rule 13's list; N_mv == 0: none, and the roll-out without the term runs
+  int N_mv = 0;
+  unsigned pen_hit_mv = 0;
   Timing time;
 };
 
@@ -308,11 +374,32 @@ int mppi_check(size_t K, size_t T, size_t M, const int32_t *limits, const int32_
   return KC_OK;
 }
 
+// rule 18, in its order
+int mppi_check_movers(const int64_t *ox, const int64_t *oy, const int32_t *vx, const int32_t *vy, const uint64_t *hq, const uint64_t *sq,
+                      const uint64_t *g, size_t n, uint32_t pen_hit_mv) {
+  if (n == 0) return KC_OK;  // clears the list, whatever else is given
+  if (n > KC_MPPI_MAX_MOVERS) KC_FAIL(KC_ERR_RANGE, "%zu movers are above the cap of %d", n, KC_MPPI_MAX_MOVERS);
+  if (!ox || !oy || !vx || !vy || !hq || !sq || !g) KC_FAIL(KC_ERR_INVALID, "a null array with %zu movers", n);
+  if (pen_hit_mv > (1u << 20)) KC_FAIL(KC_ERR_RANGE, "pen_hit_mv = %u is above 2^20", pen_hit_mv);
+  for (size_t i = 0; i < n; ++i) {
+    if (ox[i] < -kQ16MaxOffset || ox[i] > kQ16MaxOffset || oy[i] < -kQ16MaxOffset || oy[i] > kQ16MaxOffset)
+      KC_FAIL(KC_ERR_RANGE, "mover %zu: a position beyond 2^36 (2^20 cells from the map's origin)", i);
+    if (vx[i] < -(1 << 22) || vx[i] > (1 << 22) || vy[i] < -(1 << 22) || vy[i] > (1 << 22))
+      KC_FAIL(KC_ERR_RANGE, "mover %zu: a velocity beyond 2^22 a step", i);
+    if (hq[i] > sq[i]) KC_FAIL(KC_ERR_INVALID, "mover %zu: hq above sq", i);
+    if (sq[i] > kMppiMoverCap) KC_FAIL(KC_ERR_RANGE, "mover %zu: sq above 2^40", i);
+    if (g[i] > (1ull << 32)) KC_FAIL(KC_ERR_RANGE, "mover %zu: g above 2^32", i);
+    if (((((sq[i] - hq[i]) >> 16) * g[i]) >> 16) > (1ull << 20)) KC_FAIL(KC_ERR_RANGE, "mover %zu: the ramp's top above 2^20", i);
+  }
+  return KC_OK;
+}
+
 template <int TEAM>
 void mppi_launch_rollout(const kc_mppi *c, const MppiRollArgs &a) {
   const size_t lanes = c->K * static_cast<size_t>(TEAM);
-  hipLaunchKernelGGL(mppi_rollout_kernel<TEAM>, dim3(static_cast<unsigned>((lanes + kMppiBlock - 1) / kMppiBlock)), dim3(kMppiBlock), 0,
-                     c->stream, a);
+  const dim3 grid(static_cast<unsigned>((lanes + kMppiBlock - 1) / kMppiBlock));
+  if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
+  else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false>), grid, dim3(kMppiBlock), 0, c->stream, a);
 }
 
 }  // namespace
@@ -405,6 +492,36 @@ int kc_mppi_set_path(kc_mppi *c, const int64_t *px, const int64_t *py, size_t n)
   return KC_OK;
 }
 
+int kc_mppi_check_movers(const int64_t *ox, const int64_t *oy, const int32_t *vx, const int32_t *vy, const uint64_t *hq, const uint64_t *sq,
+                         const uint64_t *g, size_t n, uint32_t pen_hit_mv) {
+  return mppi_check_movers(ox, oy, vx, vy, hq, sq, g, n, pen_hit_mv);
+}
+
+int kc_mppi_set_movers(kc_mppi *c, const int64_t *ox, const int64_t *oy, const int32_t *vx, const int32_t *vy, const uint64_t *hq,
+                       const uint64_t *sq, const uint64_t *g, size_t n, uint32_t pen_hit_mv) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_TRY(mppi_check_movers(ox, oy, vx, vy, hq, sq, g, n, pen_hit_mv));
+  c->N_mv = 0;
+  if (n == 0) return KC_OK;
+  MppiMovers list{};
+  for (size_t i = 0; i < n; ++i) {
+    list.ox[i] = ox[i];
+    list.oy[i] = oy[i];
+    list.vx[i] = vx[i];
+    list.vy[i] = vy[i];
+    list.hq[i] = hq[i];
+    list.sq[i] = sq[i];
+    list.g[i] = g[i];
+  }
+  KC_HIP(hipSetDevice(c->device));
+  KC_TRY(c->d_movers.reserve(1));
+  KC_HIP(hipMemcpyAsync(c->d_movers.p, &list, sizeof(list), hipMemcpyHostToDevice, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  c->N_mv = static_cast<int>(n);
+  c->pen_hit_mv = pen_hit_mv;
+  return KC_OK;
+}
+
 int kc_mppi_set_team(kc_mppi *c, int lanes) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (lanes != 1 && lanes != 4 && lanes != 8) KC_FAIL(KC_ERR_INVALID, "a sample takes 1, 4 or 8 lanes, got %d", lanes);
@@ -441,7 +558,7 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   MppiIn *in = c->h_in.p;  // pinned; the last step's copy from it is over (every step ends drained)
   in->min_key = ~0ull;
   in->n_hit = 0;
-  in->pad = 0;
+  in->n_hit_mv = 0;
   std::memcpy(in->U, u_in, T * 3 * sizeof(int32_t));
   KC_HIP(hipMemcpyAsync(c->d_in.p, in, sizeof(MppiIn), hipMemcpyHostToDevice, c->stream));
   KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
@@ -472,6 +589,9 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   a.T = static_cast<int>(T);
   a.M = static_cast<int>(c->M);
   a.c2 = c->c2;
+  a.movers = c->d_movers.p;
+  a.N = c->N_mv;
+  a.pen_hit_mv = c->pen_hit_mv;
   c->time.begin_cycle();
   KC_TRY(c->time.start("rollout", c->stream));
   if (c->team == 8) mppi_launch_rollout<8>(c, a);

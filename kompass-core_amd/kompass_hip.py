@@ -157,9 +157,10 @@ class MclFit(C.Structure):
 
 
 class MppiRecord(C.Structure):
-    """kc_mppi_record: one controller step (DESIGN.md 4.12 rule 11)."""
+    """kc_mppi_record: one controller step (DESIGN.md 4.12 rules 11 and 17).  n_hit_moving: the samples among n_hit that a
+    moving obstacle ended, 0 with none set."""
     _fields_ = [("den", C.c_uint64), ("s_min", C.c_uint32), ("k_best", C.c_uint32), ("s_0", C.c_uint32),
-                ("n_hit", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32)]
+                ("n_hit", C.c_uint32), ("step", C.c_uint32), ("n_hit_moving", C.c_uint32)]
 
     def as_tuple(self):
         """(s_min, k_best, s_0, den, n_hit, step)"""
@@ -430,6 +431,10 @@ SIGNATURES = {
     "kc_mppi_set_costs": (C.c_int, [_vp, C.c_uint32, C.c_void_p, _sz, C.c_uint16, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
                                     C.c_void_p, _sz, C.c_int]),
     "kc_mppi_set_path": (C.c_int, [_vp, C.c_void_p, C.c_void_p, _sz]),
+    "kc_mppi_check_movers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
+                                       C.c_uint32]),
+    "kc_mppi_set_movers": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
+                                     C.c_uint32]),
     "kc_mppi_step": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MppiRecord)]),
     "kc_mppi_costs": (C.c_int, [_vp, C.c_void_p, _sz]),
     "kc_mppi_set_team": (C.c_int, [_vp, C.c_int]),
@@ -2130,6 +2135,27 @@ def mppi_check(n_samples, horizon, n_path, limits=None, s=None, costs=None, reac
                                int(reach), None if wt is None else wt.ctypes.data, 0 if wt is None else wt.size, int(w_shift)))
 
 
+def _mover_arrays(ox, oy, vx, vy, hq, sq, g):
+    """Rule 13's seven arrays in the ABI's types; a value that does not fit its C type is a ValueError, as _in has it."""
+    out = []
+    for a, dt, what in ((ox, np.int64, "OX"), (oy, np.int64, "OY"), (vx, np.int32, "VX"), (vy, np.int32, "VY"),
+                        (hq, np.uint64, "hq"), (sq, np.uint64, "sq"), (g, np.uint64, "g")):
+        info = np.iinfo(dt)
+        out.append(np.array([_in(v, int(info.min), int(info.max), what) for v in np.asarray(a, dtype=object).reshape(-1)], dt))
+    return out
+
+
+def mppi_check_movers(ox, oy, vx, vy, hq, sq, g, pen_hit_mv, n=None):
+    """kc_mppi_check_movers' refusals (host only; DESIGN.md 4.12 rule 18); raises ValueError / IndexError.  n: the count
+    handed over, len(ox) by default; an array may be None (NULL)."""
+    arr = [None if a is None else b for a, b in zip((ox, oy, vx, vy, hq, sq, g),
+                                                    _mover_arrays(*[() if a is None else a for a in (ox, oy, vx, vy, hq, sq, g)]))]
+    n = (0 if arr[0] is None else arr[0].size) if n is None else int(n)
+    if any(a is not None and a.size < n for a in arr):
+        raise ValueError("an array is shorter than the count")
+    _check(lib().kc_mppi_check_movers(*[None if a is None else a.ctypes.data for a in arr], n, _in(pen_hit_mv, 0, 2 ** 32 - 1, "pen_hit_mv")))
+
+
 class MppiContext(_Owner):
     """Owner of one kc_mppi context: an MPPI controller over a WorldMapContext's distance plane, which it
     keeps alive.  Works in the ABI's integers and keeps no sequence between steps; kompass_core.control.MPPI is the front
@@ -2161,6 +2187,17 @@ class MppiContext(_Owner):
         if x.size != y.size:
             raise ValueError("one y a x")
         _check(lib().kc_mppi_set_path(self.h, x.ctypes.data, y.ctypes.data, x.size))
+
+    def set_movers(self, ox=(), oy=(), vx=(), vy=(), hq=(), sq=(), g=(), pen_hit_mv=0):
+        """Rule 13's list for every later step, at the time of the next step's pose; none clears it."""
+        arr = _mover_arrays(ox, oy, vx, vy, hq, sq, g)
+        if any(a.size != arr[0].size for a in arr):
+            raise ValueError("one entry a mover in every array")
+        _check(lib().kc_mppi_set_movers(self.h, *[a.ctypes.data for a in arr], arr[0].size, _in(pen_hit_mv, 0, 2 ** 32 - 1, "pen_hit_mv")))
+
+    @staticmethod
+    def check_movers(ox, oy, vx, vy, hq, sq, g, pen_hit_mv, n=None):
+        mppi_check_movers(ox, oy, vx, vy, hq, sq, g, pen_hit_mv, n)
 
     def step(self, tx, ty, h, u, step):
         """-> (U' int32 [T, 3], MppiRecord).  u: the nominal sequence, T x (F, L, H)."""

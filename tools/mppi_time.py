@@ -11,6 +11,12 @@ Beside them, as yardsticks only:
   * the class-level DWA call of tools/class_cycle.py (kompass_cpp.control.DWA.compute_velocity_commands, 91 x 91
     lattice, the "mid" scene), timed in this run.
 
+--movers 0,8,64 adds a leg a count: that many moving obstacles (rules 13 to 18) walking across the path ahead of the
+robot, their soft rings over the first states, so that the term is computed and few samples are ended early.  The leg
+with 0 movers is the step as it was (the roll-out without the term runs) and needs no entry an older build of the
+library lacks.  With movers the statement compared against is tests/mppi_movers_ref.py.  Without --movers: the one leg
+with none.
+
 The world: a border, a wall with a door and scattered pillars; the robot in free space, the path a straight line
 through the door.  One JSON line a shape on stdout."""
 import argparse
@@ -27,6 +33,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
 
 import kompass_hip as kh  # noqa: E402
+import mppi_movers_ref as mm  # noqa: E402
 import mppi_ref as mp  # noqa: E402
 import worldmap_mcl_ref as mref  # noqa: E402
 from worldmap_ref import EMPTY, OCCUPIED  # noqa: E402
@@ -53,6 +60,19 @@ def world():
 
 def median(v):
     return round(statistics.median(v), 4)
+
+
+def mover_list(n, pose):
+    """n movers in a fan 6 to 20 cells ahead of the robot and 3 to 9 cells beside its path, drifting towards it at about
+    0.14 cells a step: hit distance half a cell, so that few samples are ended early and the term is paid in full; soft
+    from 9 cells, top 200."""
+    hq, sq = 1 << 14, 81 << 16
+    g = (200 * 65536) // (((sq - hq) >> 16) + 1)
+    rows = []
+    for i in range(n):
+        ahead, side = 6 + (i * 14) // max(n, 1), (-1) ** i * (3 + i % 7)
+        rows.append((pose[0] + ahead * ONE, pose[1] + side * ONE, (i % 5 - 2) * 3000, -(side // abs(side)) * (9000 + 300 * (i % 11)), hq, sq, g))
+    return mm.movers(rows, 4000)
 
 
 def dwa_yardstick(reps, warmup):
@@ -82,9 +102,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--movers", default="0", help="comma-separated counts of moving obstacles, a leg each, e.g. 0,8,64")
     ap.add_argument("--no-statement", action="store_true", help="skip the Python statement's timing")
     ap.add_argument("--no-dwa", action="store_true", help="skip the class-level DWA yardstick")
     args = ap.parse_args()
+    counts = [int(v) for v in args.movers.split(",")]
     if kh.device_count() < 1:
         raise SystemExit("no HIP device visible")
     cls = world()
@@ -100,47 +122,55 @@ def main():
             py = [602 * ONE] * M
             pose = (1000 * ONE + 300, 601 * ONE, 700)
             U = [(80000, 0, 20)] * T
-            line = dict(shape=dict(K=K, T=T, M=M), world=[W, H], reps=args.reps, warmup=args.warmup)
-            with kh.MppiContext(m, K, T, 1) as dev:
-                dev.set_model(model.f_lo, model.f_hi, model.l_hi, model.h_hi, model.kq, model.s)
-                dev.set_costs(costs.r2, costs.pen_d2, costs.pen_far, costs.pen_hit, costs.w_path, costs.qcap, costs.w_goal, costs.wtab,
-                              costs.w_shift)
-                dev.set_path(px, py)
-                dev.set_timing(True)
-                wall = {t: [] for t in TEAMS}
-                roll = {t: [] for t in TEAMS}
-                upd = {t: [] for t in TEAMS}
-                first = None
-                for n in range(args.reps + args.warmup):
-                    for team in TEAMS:                                     # interleaved
-                        dev.set_team(team)
-                        t0 = time.perf_counter()
-                        out, rec = dev.step(*pose, U, n)
-                        dt = (time.perf_counter() - t0) * 1e3
-                        if team == TEAMS[0]:
-                            first = (out.tolist(), rec.as_tuple())
-                        elif (out.tolist(), rec.as_tuple()) != first:
-                            raise SystemExit(f"{team} lanes a sample differ from {TEAMS[0]} at step {n}")
-                        if n >= args.warmup:
-                            r, u = dev.times()
-                            wall[team].append(dt)
-                            roll[team].append(r)
-                            upd[team].append(u)
-                for team in TEAMS:
-                    line[f"team{team}"] = dict(step_ms=median(wall[team]), rollout_ms=median(roll[team]), update_ms=median(upd[team]))
-                line["n_hit"], line["s_min"] = first[1][4], first[1][0]
-                if plane is not None:
-                    ts = []
-                    for n in range(3):
-                        t0 = time.perf_counter()
-                        want = mp.step(plane, K, 1, model, costs, px, py, *pose, U, args.reps + args.warmup - 1)
-                        ts.append((time.perf_counter() - t0) * 1e3)
-                    if (want[0], tuple(want[1])) != (first[0] and [tuple(r) for r in first[0]], first[1]):
-                        raise SystemExit("the device differs from the statement")
-                    line["python_statement_ms"] = median(ts)
-            if dwa_ms is not None:
-                line["dwa_class_level_91x91_mid_ms"] = dwa_ms
-            print(json.dumps(line), flush=True)
+            for n_mv in counts:
+                time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms)
+
+
+def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms):
+    mv = mover_list(n_mv, pose)
+    line = dict(shape=dict(K=K, T=T, M=M), movers=n_mv, world=[W, H], reps=args.reps, warmup=args.warmup)
+    with kh.MppiContext(m, K, T, 1) as dev:
+        dev.set_model(model.f_lo, model.f_hi, model.l_hi, model.h_hi, model.kq, model.s)
+        dev.set_costs(costs.r2, costs.pen_d2, costs.pen_far, costs.pen_hit, costs.w_path, costs.qcap, costs.w_goal, costs.wtab,
+                      costs.w_shift)
+        dev.set_path(px, py)
+        if n_mv:
+            dev.set_movers(*mv[:7], mv.pen_hit)
+        dev.set_timing(True)
+        wall = {t: [] for t in TEAMS}
+        roll = {t: [] for t in TEAMS}
+        upd = {t: [] for t in TEAMS}
+        first = None
+        for n in range(args.reps + args.warmup):
+            for team in TEAMS:                                     # interleaved
+                dev.set_team(team)
+                t0 = time.perf_counter()
+                out, rec = dev.step(*pose, U, n)
+                dt = (time.perf_counter() - t0) * 1e3
+                if team == TEAMS[0]:
+                    first = (out.tolist(), rec.as_tuple())
+                elif (out.tolist(), rec.as_tuple()) != first:
+                    raise SystemExit(f"{team} lanes a sample differ from {TEAMS[0]} at step {n}")
+                if n >= args.warmup:
+                    r, u = dev.times()
+                    wall[team].append(dt)
+                    roll[team].append(r)
+                    upd[team].append(u)
+        for team in TEAMS:
+            line[f"team{team}"] = dict(step_ms=median(wall[team]), rollout_ms=median(roll[team]), update_ms=median(upd[team]))
+        line["n_hit"], line["s_min"], line["n_hit_moving"] = first[1][4], first[1][0], int(rec.n_hit_moving) if n_mv else 0
+        if plane is not None:
+            ts = []
+            for n in range(3):
+                t0 = time.perf_counter()
+                want = mm.step(plane, K, 1, model, costs, px, py, *pose, U, args.reps + args.warmup - 1, mv)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            if (want[0], tuple(want[1])) != (first[0] and [tuple(r) for r in first[0]], first[1] + (line["n_hit_moving"],)):
+                raise SystemExit("the device differs from the statement")
+            line["python_statement_ms"] = median(ts)
+    if dwa_ms is not None:
+        line["dwa_class_level_91x91_mid_ms"] = dwa_ms
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
