@@ -10,15 +10,17 @@
 //      to the nearest blocking cell of its own row (255: none within R); planner_valid_kernel asks the 2 R + 1
 //      rows around a cell for rowdist^2 + dy^2 <= R2.  The nearest blocker of a row is the one that decides that
 //      row, so the two passes are the disc test exactly, at O(R) loads a cell instead of O(R^2).
-//  (b) cost field.  planner_relax_kernel: one workgroup per 64 x 64 tile, the tile and a one-cell halo in LDS,
-//      Jacobi iterations in LDS until the tile stops changing (or 256 iterations), the tile written to the OTHER
-//      of two field buffers.  A pass reads one buffer and writes the other: no workgroup reads what another one
-//      writes in the same launch, none waits for another, and the field after k passes is the same on every run.
-//      A workgroup that changed a cell stores the pass number into one device word; the host launches passes in
-//      batches of kPlanBatch and reads that word back once per batch; a word older than the batch's last pass means that
-//      pass changed nothing, i.e. both buffers hold the fixed point.
-//  (c) path.  planner_walk_kernel: one wavefront walks from the start, eight lanes load the eight neighbours of
-//      the current cell, a shuffle reduction takes the smallest (value, order) pair.
+//  (b) cost field.  planner_relax_kernel is a tile pass (below) whose rule is the 8-connected step with the corner
+//      rule.  The host launches passes in batches of kPlanBatch and reads the changed word back once per batch; a word
+//      older than the batch's last pass means that pass changed nothing, i.e. both buffers hold the fixed point.
+//  (c) path.  planner_walk_kernel is a walk (below) over cells: eight lanes load the eight neighbours of the current cell.
+//
+//  A tile pass: one workgroup per 64 x 64 tile, the tile and a one-cell halo in LDS (plan_tile_origin, plan_load_halo),
+//  Jacobi iterations in LDS until the tile stops changing (or 256 iterations), the tile written to the OTHER of two field
+//  buffers.  A pass reads one buffer and writes the other: no workgroup reads what another one writes in the same launch,
+//  none waits for another, and the field after k passes is the same on every run.  A workgroup that changed a cell stores
+//  the pass number into one device word, the changed word.  A walk: one wavefront walks down a converged field, a state an
+//  iteration; a shuffle reduction (plan_min_key) takes the smallest (value, lane) pair among the lanes' candidates.
 //  (d) clearance cost (rules 6 to 8; off unless kc_planner_set_clearance_cost gave a table).  The row pass reaches
 //      max(R, Rc) cells; planner_clear_kernel takes min(rowdist^2 + dy^2) over the rows in reach and writes clear2,
 //      the table's penalty and the validity map in one go.  planner_relax_kernel<true> adds the penalty of the cell
@@ -33,9 +35,9 @@
 //      class), four classes.  The turning disc goes through the row and column passes of (a) with r2 = T2;
 //      planner_oriented_valid_kernel tests the four host-built offset lists, nearest offsets first, and skips the cells
 //      the disc already cleared (T2 contains every mask); a byte a cell holds the four class bits and the turn bit.
-//      planner_relax4_kernel is (b) over four layers: the same tile, halo, two buffers and changed word, 16 states a
-//      lane; layers 0 and 2 couple along rows and columns, 1 and 3 along the diagonals, all four at the same cell by
-//      a turn.  planner_walk4_kernel is (c) over states: four lanes, the two moves of the class and the two turns.
+//      planner_relax4_kernel is a tile pass over four layers, 16 states a lane; layers 0 and 2 couple along rows and
+//      columns, 1 and 3 along the diagonals, all four at the same cell by a turn.  planner_walk4_kernel is a walk over
+//      states: four lanes, the two moves of the class and the two turns.
 //
 //  (g) replan (rules 19 and 20; kc_planner_replan).  The context keeps the field of its last solve, and through a new
 //      grid its validity map and penalty.  planner_touched_kernel compares them with the new grid's and reduces the
@@ -45,8 +47,8 @@
 //  (h) exploration (rules 21 to 26; kc_planner_explore).  The validity of (a) with unknown not blocking, then
 //      planner_known_kernel takes the unknown cells out; the field of (b) rooted at the robot's cell;
 //      planner_frontier_mark_kernel writes the frontier bytes, both label planes and the tiles that hold a frontier cell;
-//      planner_label_kernel is (b)'s tile, halo, two buffers and changed word with "the smallest label among my eight
-//      frontier neighbours and me" as its update, over the listed tiles; sizes, kept roots and the records go by vector
+//      planner_label_kernel is a tile pass with "the smallest label among my eight frontier neighbours and me" as its
+//      rule, over the listed tiles; sizes, kept roots and the records go by vector
 //      atomics from plain HIP (32-bit add at the root, 64-bit add and min at the record); planner_walk_kernel<false, true>
 //      walks from an entry cell down to the robot by field + step, so that the path costs what the record says.
 //
@@ -54,10 +56,10 @@
 //      directed headings); the transitions are one straight step and 45-degree arcs of n cells a leg, backward at a price
 //      or not at all, no turn in place.  planner_car_steps_kernel writes a byte a cell (bit h: the unit step along +D[h] is
 //      allowed) from the validity map of (a) or (f); planner_car_moves_kernel walks every arc's polyline over those bytes
-//      once a solve and writes a byte a state (bits 0 .. 5: S, L, R, B, BL, BR).  planner_relax8_kernel is (b) with a
-//      workgroup per (tile, heading): the layer's 66 x 66 region in LDS for the straight moves, which couple one layer
-//      along one line, and the arc candidates, which reach up to 2 n cells into the two neighbouring layers, taken once a
-//      pass from the read-only input.  planner_walk8_kernel is (c) over states: six lanes, a primitive each.
+//      once a solve and writes a byte a state (bits 0 .. 5: S, L, R, B, BL, BR).  planner_relax8_kernel is a tile pass with
+//      a workgroup per (tile, heading): its rule is the straight moves, which couple one layer along one line; the arc
+//      candidates, which reach up to 2 n cells into the two neighbouring layers, are taken once a pass from the read-only
+//      input.  planner_walk8_kernel is a walk over states: six lanes, a primitive each.
 //
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
@@ -173,25 +175,38 @@ __global__ __launch_bounds__(kPlanBlock) void planner_init_kernel(uint32_t *a, u
   }
 }
 
-// the 66 x 66 halo region of tile `tile` into LDS: v the byte of `map` (valid cells for the relaxation, frontier cells
-// for the labelling), f the value of `in` where that byte is set and INF elsewhere and outside the grid; *x0, *y0 the
-// grid cell of the region's corner.  Ends with the barrier behind the stores.
-__device__ __forceinline__ void plan_load_tile(unsigned tile, const uint32_t *__restrict__ in, const uint8_t *__restrict__ map, int W,
-                                               int H, unsigned tiles_x, uint32_t *f, uint8_t *v, int *x0_out, int *y0_out) {
-  // the tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more tile rows than gridDim.y holds
-  const int x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
-  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
-    const int lx = k % kPlanHalo, ly = k / kPlanHalo;
-    const int gx = x0 + lx, gy = y0 + ly;
+// ---- what the tile passes (planner_relax_kernel, planner_label_kernel, planner_relax4_kernel, planner_relax8_kernel) share
+constexpr int kPlanRegion = kPlanHalo * kPlanHalo;  // values of one layer's halo region in LDS
+
+// the grid cell of the halo region's corner.  The tiles are numbered row by row along gridDim.x: a 1 x 2^28 grid has more
+// tile rows than gridDim.y holds
+__device__ __forceinline__ void plan_tile_origin(unsigned tile, unsigned tiles_x, int *x0, int *y0) {
+  *x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1;
+  *y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
+}
+
+// the halo region of L layers (layer l of `in` is its cells [l * n, (l + 1) * n)) into f[l * kPlanRegion + k].  MAP: v[k]
+// takes the cell's byte of `map`, 0 outside the grid; with one layer the byte is that layer's own, with more bit l is
+// layer l's.  Invalid cells and cells outside the grid never carry a distance: INF.  Ends with the barrier behind the stores.
+template <int L, bool MAP>
+__device__ __forceinline__ void plan_load_halo(const uint32_t *__restrict__ in, size_t n, const uint8_t *__restrict__ map, int W, int H,
+                                               int x0, int y0, uint32_t *f, uint8_t *v) {
+  for (int k = threadIdx.x; k < kPlanRegion; k += kPlanThreads) {
+    const int gx = x0 + k % kPlanHalo, gy = y0 + k / kPlanHalo;
     const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
     const size_t g = inside ? static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx) : 0;
-    const uint8_t ok = inside ? map[g] : static_cast<uint8_t>(0);
-    v[k] = ok;
-    f[k] = ok ? in[g] : kPlanInf;  // invalid cells and cells outside the grid never carry a distance
+    uint32_t bits = inside ? 1u : 0u;
+    if constexpr (MAP) {
+      bits = inside ? map[g] : 0u;
+      v[k] = static_cast<uint8_t>(bits);
+    }
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+      const bool on = L == 1 ? bits != 0u : (bits >> l & 1u) != 0u;
+      f[l * kPlanRegion + k] = on ? in[static_cast<size_t>(l) * n + g] : kPlanInf;
+    }
   }
   __syncthreads();
-  *x0_out = x0;
-  *y0_out = y0;
 }
 
 // one pass over one tile: `in` is only read, `out` only written (the tile's own cells).  PEN: a step pays the
@@ -203,10 +218,11 @@ template <bool PEN>
 __device__ __forceinline__ void plan_relax_tile(unsigned tile, const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
                                                 const uint8_t *__restrict__ valid, const uint32_t *__restrict__ pen, int W, int H,
                                                 unsigned tiles_x, uint32_t *changed_word, uint32_t pass) {
-  __shared__ uint32_t f[kPlanHalo * kPlanHalo];
-  __shared__ uint8_t v[kPlanHalo * kPlanHalo];
+  __shared__ uint32_t f[kPlanRegion];
+  __shared__ uint8_t v[kPlanRegion];
   int x0, y0;
-  plan_load_tile(tile, in, valid, W, H, tiles_x, f, v, &x0, &y0);
+  plan_tile_origin(tile, tiles_x, &x0, &y0);
+  plan_load_halo<1, true>(in, 0, valid, W, H, x0, y0, f, v);
   const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
   const int off[8] = {1, kPlanHalo, -1, -kPlanHalo, kPlanHalo + 1, kPlanHalo - 1, -kPlanHalo - 1, -kPlanHalo + 1};
   int idx[kPlanRows];
@@ -409,21 +425,15 @@ __global__ __launch_bounds__(kPlanBlock) void planner_frontier_mark_kernel(const
   }
 }
 
-// rule 24, one pass over one listed tile, as plan_relax_tile: `in` is only read, `out` only written (the tile's own
-// cells).  A frontier cell takes the smallest label among itself and its eight neighbours; the cells that are no
-// frontier cells, and the ring outside the grid, hold INF and so never win.
-__global__ __launch_bounds__(kPlanThreads) void planner_label_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
-                                                                     const uint8_t *__restrict__ front, int W, int H, unsigned tiles_x,
-                                                                     const uint32_t *__restrict__ tiles, uint32_t *changed_word,
-                                                                     uint32_t pass) {
-  __shared__ uint32_t f[kPlanHalo * kPlanHalo];
-  // The shared load's byte plane is not read here, and the compiler drops it (17 680 bytes of LDS, f alone).  Nor does
-  // the frontier byte decide a value: the mark kernel put INF into both label planes wherever the byte is 0, so what
-  // the load selects is in[g] inside the grid and INF outside it.  The bytes are passed because the helper is the
-  // relaxation's, unchanged.
-  __shared__ uint8_t v[kPlanHalo * kPlanHalo];
+// rule 24, one tile pass over one listed tile.  A frontier cell takes the smallest label among itself and its eight
+// neighbours; the cells that are no frontier cells hold INF in both label planes from the mark kernel on, as the ring
+// outside the grid does in LDS, and so never win: no byte plane is read.
+__global__ __launch_bounds__(kPlanThreads) void planner_label_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int W, int H,
+                                                                     unsigned tiles_x, const uint32_t *__restrict__ tiles, uint32_t *changed_word, uint32_t pass) {
+  __shared__ uint32_t f[kPlanRegion];
   int x0, y0;
-  plan_load_tile(tiles[blockIdx.x], in, front, W, H, tiles_x, f, v, &x0, &y0);
+  plan_tile_origin(tiles[blockIdx.x], tiles_x, &x0, &y0);
+  plan_load_halo<1, false>(in, 0, nullptr, W, H, x0, y0, f, nullptr);
   const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
   const int off[8] = {1, kPlanHalo, -1, -kPlanHalo, kPlanHalo + 1, kPlanHalo - 1, -kPlanHalo - 1, -kPlanHalo + 1};
   int idx[kPlanRows];
@@ -531,6 +541,17 @@ __global__ __launch_bounds__(kPlanBlock) void planner_frontier_record_kernel(con
   }
 }
 
+// what the three walks share: the smallest key among the lanes 0 .. 2^K - 1, in every lane
+template <int K>
+__device__ __forceinline__ unsigned long long plan_min_key(unsigned long long key) {
+#pragma unroll
+  for (int d = 1 << (K - 1); d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(key, d, 64);
+    key = o < key ? o : key;
+  }
+  return __shfl(key, 0, 64);
+}
+
 // status words of the walk: out[0] = cells written, out[1] = 0 done / 1 capacity / 2 no descending neighbour.
 // PEN (rule 8): the key is field + step, its minimum must be field - penalty of the cell left, and out[2] = the
 // smallest clear2 among the cells visited.  STEP without PEN (rule 26): rule 8's key and test with no penalty plane,
@@ -568,12 +589,7 @@ __global__ __launch_bounds__(64) void planner_walk_kernel(const uint32_t *field,
         if (ok) key = ((static_cast<unsigned long long>(field[g]) + step) << 3) | static_cast<unsigned long long>(lane);
       }
     }
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) {
-      const unsigned long long o = __shfl_xor(key, d, 64);
-      key = o < key ? o : key;
-    }
-    key = __shfl(key, 0, 64);
+    key = plan_min_key<3>(key);
     bool off_field;  // not on a converged field with a reachable start
     if constexpr (PEN)
       off_field = key == ~0ull || (key >> 3) + static_cast<unsigned long long>(pen[c]) != static_cast<unsigned long long>(fc);
@@ -748,27 +764,17 @@ __global__ __launch_bounds__(kPlanBlock) void planner_init4_kernel(uint32_t *a, 
   }
 }
 
-// rule 16, one pass over one tile, as planner_relax_kernel: `in` is only read, `out` only written (the tile's own
-// cells, four layers).  A lane owns four cells and their sixteen states.  The moves read the neighbours' values of
-// the last iteration from LDS; the turns couple the four values of one cell, which one lane holds in registers.
+// rule 16, one tile pass over four layers.  A lane owns four cells and their sixteen states.  The moves read the neighbours'
+// values of the last iteration from LDS; the turns couple the four values of one cell, which one lane holds in registers.
 __global__ __launch_bounds__(kPlanThreads) void planner_relax4_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out,
                                                                       const uint8_t *__restrict__ valid4, int W, int H, size_t n,
                                                                       unsigned tiles_x, uint32_t turn10, uint32_t *changed_word,
                                                                       uint32_t pass) {
-  __shared__ uint32_t f[4][kPlanHalo * kPlanHalo];
-  __shared__ uint8_t v[kPlanHalo * kPlanHalo];
-  const int x0 = static_cast<int>(blockIdx.x % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(blockIdx.x / tiles_x) * kPlanTile - 1;
-  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
-    const int lx = k % kPlanHalo, ly = k / kPlanHalo;
-    const int gx = x0 + lx, gy = y0 + ly;
-    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
-    const size_t g = inside ? static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx) : 0;
-    const uint32_t bits = inside ? valid4[g] : 0u;
-    v[k] = static_cast<uint8_t>(bits);
-#pragma unroll
-    for (int l = 0; l < 4; ++l) f[l][k] = (bits >> l & 1u) ? in[static_cast<size_t>(l) * n + g] : kPlanInf;
-  }
-  __syncthreads();
+  __shared__ uint32_t f[4][kPlanRegion];
+  __shared__ uint8_t v[kPlanRegion];
+  int x0, y0;
+  plan_tile_origin(blockIdx.x, tiles_x, &x0, &y0);
+  plan_load_halo<4, true>(in, n, valid4, W, H, x0, y0, f[0], v);
   const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
   const int off[4] = {1, kPlanHalo + 1, kPlanHalo, kPlanHalo - 1};
   int idx[kPlanRows];
@@ -877,12 +883,7 @@ __global__ __launch_bounds__(64) void planner_walk4_kernel(const uint32_t *field
         key = ((static_cast<unsigned long long>(field[static_cast<size_t>(nk) * n + c]) + turn10) << 2) | static_cast<unsigned long long>(lane);
       }
     }
-#pragma unroll
-    for (int d = 2; d >= 1; d >>= 1) {
-      const unsigned long long o = __shfl_xor(key, d, 64);
-      key = o < key ? o : key;
-    }
-    key = __shfl(key, 0, 64);
+    key = plan_min_key<2>(key);
     if (key == ~0ull || (key >> 2) != static_cast<unsigned long long>(fc)) {  // not on a converged field with a reachable start
       status = 2;
       break;
@@ -1021,8 +1022,8 @@ __global__ __launch_bounds__(kPlanBlock) void planner_init8_kernel(uint32_t *a, 
   }
 }
 
-// rule 32, one pass over one (tile, heading): blockIdx.x = 8 * tile + h.  `in` is only read, `out` only written (the
-// tile's own cells of layer h).  The layer's 66 x 66 halo region sits in LDS as in planner_relax_kernel; the straight
+// rule 32, one tile pass over one (tile, heading): blockIdx.x = 8 * tile + h.  `in` is only read, `out` only written (the
+// tile's own cells of layer h).  The layer's 66 x 66 halo region sits in LDS; the straight
 // moves couple states of this layer alone, along the line +D[h] (S) and -D[h] (B), and are iterated there.  The arcs
 // end in the layers h + 1 and h - 1, up to 2 n cells away: their candidates cost + in[target] are taken once from the
 // read-only input, guarded by the moves byte, and are constants of the pass.  A value therefore crosses one arc a
@@ -1033,17 +1034,11 @@ __global__ __launch_bounds__(kPlanThreads) void planner_relax8_kernel(const uint
                                                                       const uint8_t *__restrict__ moves, int W, int H, size_t n,
                                                                       unsigned tiles_x, int turn, uint32_t rw, uint32_t *changed_word,
                                                                       uint32_t pass) {
-  __shared__ uint32_t f[kPlanHalo * kPlanHalo];
-  const unsigned tile = blockIdx.x >> 3;
+  __shared__ uint32_t f[kPlanRegion];
   const int h = static_cast<int>(blockIdx.x & 7u);
-  const uint32_t *__restrict__ layer = in + static_cast<size_t>(h) * n;
-  const int x0 = static_cast<int>(tile % tiles_x) * kPlanTile - 1, y0 = static_cast<int>(tile / tiles_x) * kPlanTile - 1;
-  for (int k = threadIdx.x; k < kPlanHalo * kPlanHalo; k += kPlanThreads) {
-    const int gx = x0 + k % kPlanHalo, gy = y0 + k / kPlanHalo;
-    const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
-    f[k] = inside ? layer[static_cast<size_t>(gy) * static_cast<size_t>(W) + static_cast<size_t>(gx)] : kPlanInf;
-  }
-  __syncthreads();
+  int x0, y0;
+  plan_tile_origin(blockIdx.x >> 3, tiles_x, &x0, &y0);
+  plan_load_halo<1, false>(in + static_cast<size_t>(h) * n, 0, nullptr, W, H, x0, y0, f, nullptr);
   const int tx = threadIdx.x & (kPlanTile - 1), ty = threadIdx.x / kPlanTile;
   const int off = kCarDy[h] * kPlanHalo + kCarDx[h];
   const uint32_t fwd = (h & 1) ? 14u : 10u, bwd = fwd * rw, arc_f = 24u * static_cast<uint32_t>(turn), arc_b = arc_f * rw;
@@ -1133,12 +1128,7 @@ __global__ __launch_bounds__(64) void planner_walk8_kernel(const uint32_t *field
       key = ((static_cast<unsigned long long>(field[static_cast<size_t>(ah) * n + static_cast<size_t>(ay) * static_cast<size_t>(W) +
                                                     static_cast<size_t>(ax)]) + cost) << 3) | static_cast<unsigned long long>(lane);
     }
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) {
-      const unsigned long long o = __shfl_xor(key, d, 64);
-      key = o < key ? o : key;
-    }
-    key = __shfl(key, 0, 64);
+    key = plan_min_key<3>(key);
     const int q = static_cast<int>(key & 7ull);
     const bool last = fc == 0u;
     const bool off_field = !last && (key == ~0ull || (key >> 3) != static_cast<unsigned long long>(fc));
@@ -1305,6 +1295,31 @@ int plan_isqrt(uint32_t v) {
   while (static_cast<uint32_t>(r + 1) * static_cast<uint32_t>(r + 1) <= v) ++r;
   return r;
 }
+
+// the refusal of a disc footprint whose row distances a rowd byte does not hold
+int check_radius(uint32_t r2) {
+  if (r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
+    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  return KC_OK;
+}
+// the same for a box, whose turning disc T2 = A2 + B2 contains every mask; `what` names the sum in the caller's terms
+int check_box(uint32_t a2, uint32_t b2, const char *what) {
+  const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
+  if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
+    KC_FAIL(KC_ERR_RANGE, "a %s = %llu is wider than %d cells", what, t2, KC_PLANNER_MAX_RADIUS_CELLS);
+  return KC_OK;
+}
+
+// the host clock of a call's phases: lap() is the milliseconds since the last lap, or since the clock was made
+struct PlanClock {
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  float lap() {
+    const auto now = std::chrono::steady_clock::now();
+    const float ms = std::chrono::duration<float, std::milli>(now - t).count();
+    t = now;
+    return ms;
+  }
+};
 
 // the linear index of a cell, -1 outside the grid
 long long plan_cell_index(const kc_planner *c, const int cell[2]) {
@@ -1564,7 +1579,7 @@ void car_expand(const kc_planner *c, int32_t cell, int h, int p, std::vector<int
 // rule 33 over the last car solve (status KC_PLAN_FOUND), once: c->car_states, c->car_moves, and c->path with rule 34's expansion
 int planner_walk_car(kc_planner *c) {
   KC_HIP(hipSetDevice(c->device));
-  const auto t0 = std::chrono::steady_clock::now();
+  PlanClock clock;
   const size_t n = static_cast<size_t>(c->W) * static_cast<size_t>(c->H);
   // every primitive lowers the field by 10 at least, and no state comes twice
   const size_t cap = std::min<size_t>(8 * n, static_cast<size_t>(c->cost / 10u)) + 2;
@@ -1574,7 +1589,7 @@ int planner_walk_car(kc_planner *c) {
                      c->start[1], c->start_heading, c->car_turn, c->car_rw, c->d_path.p, static_cast<uint32_t>(cap), &c->d_word.p->walk_count);
   uint32_t count = 0;
   KC_TRY(planner_walk_fetch(c, cap, false, "car", "states", &count));
-  c->car_ms[2] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  c->car_ms[2] = clock.lap();
   c->car_states.resize(count);
   c->car_moves.resize(count - 1);
   c->path.clear();
@@ -1590,6 +1605,19 @@ int planner_walk_car(kc_planner *c) {
   }
   c->path_clear2 = static_cast<uint32_t>(KC_PLANNER_CLEAR_FAR);
   c->have_path = true;
+  return KC_OK;
+}
+
+// the start of a field pair: both buffers hold `cells` values, init(a, b) queues the kernel that writes the start state
+// into both, the solve's words are zero.  Both buffers hold the initial state, so pass 1 reads either: final_buf = 0.
+template <typename Init>
+int planner_start_pair(kc_planner *c, DevBuf<uint32_t> (&pair)[2], size_t cells, Init &&init) {
+  KC_TRY(pair[0].reserve(cells));
+  KC_TRY(pair[1].reserve(cells));
+  init(pair[0].p, pair[1].p);
+  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), c->stream));
+  KC_HIP(hipGetLastError());
+  c->final_buf = 0;
   return KC_OK;
 }
 
@@ -1734,24 +1762,19 @@ int kc_planner_solve(kc_planner *c, const int start_cell[2], const int goal_cell
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_solve before a grid was set");
   if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve with the oriented footprint on: kc_planner_solve_oriented");
   if (c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_solve with car motion on: kc_planner_solve_car");
-  if (r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
-    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  KC_TRY(check_radius(r2));
   const long long n = static_cast<long long>(c->W) * c->H;
   // field <= (14 + max penalty) * cells: the sums of the relaxation stay below the 0xFFFFFFFF of "no walk"
   if (c->clear_c2 > 0 && (14ull + c->clear_max_pen) * static_cast<unsigned long long>(n) > 0xFFFFFFFEull)
     KC_FAIL(KC_ERR_RANGE, "a clearance penalty of %u over %lld cells does not fit the 32-bit cost field", c->clear_max_pen, n);
   KC_HIP(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
   forget_solve(c, cost_out, passes_out);
   const int unknown_blocks = allow_unknown ? 0 : 1;
   if (!c->have_valid || c->valid_r2 != r2 || c->valid_unknown != unknown_blocks) KC_TRY(planner_validity(c, r2, unknown_blocks));
   const long long goal = plan_cell_index(c, goal_cell);
-  KC_TRY(c->d_field[0].reserve(static_cast<size_t>(n)));
-  KC_TRY(c->d_field[1].reserve(static_cast<size_t>(n)));
-  hipLaunchKernelGGL(planner_init_kernel, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, goal);
-  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), s));
-  KC_HIP(hipGetLastError());
-  c->final_buf = 0;  // both buffers hold the initial state
+  KC_TRY(planner_start_pair(c, c->d_field, static_cast<size_t>(n), [&](uint32_t *a, uint32_t *b) {
+    hipLaunchKernelGGL(planner_init_kernel, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, c->stream, a, b, c->d_valid.p, n, goal);
+  }));
   uint32_t passes = 0;
   if (goal >= 0) KC_TRY(planner_relax(c, disc_pass(c, nullptr, c->tiles_x * c->tiles_y), n, "cost", &c->final_buf, &passes));
   KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field[c->final_buf].p, c->d_valid.p, 0xFFu, 0xFFu, true, status_out, cost_out));
@@ -1952,9 +1975,7 @@ int kc_planner_set_oriented(kc_planner *c, uint32_t a2, uint32_t b2, uint32_t tu
   if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "the oriented footprint cannot be set while a clearance cost is on (rule 18)");
   if (c->car_turn > 0) KC_FAIL(KC_ERR_STATE, "the oriented mode cannot be set while car motion is on: kc_planner_set_car takes the box (rule 35)");
   if (turn10 < 1u || turn10 > 10000u) KC_FAIL(KC_ERR_RANGE, "turn10 = %u is outside 1 .. 10000", turn10);
-  const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
-  if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
-    KC_FAIL(KC_ERR_RANGE, "a turning disc of T2 = %llu is wider than %d cells", t2, KC_PLANNER_MAX_RADIUS_CELLS);
+  KC_TRY(check_box(a2, b2, "turning disc of T2"));
   const bool new_box = c->or_a2 != a2 || c->or_b2 != b2;
   if (new_box) KC_TRY(planner_upload_box(c, a2, b2));
   c->or_a2 = a2;
@@ -1980,16 +2001,12 @@ int kc_planner_solve_oriented(kc_planner *c, const int start_cell[2], int start_
   const int W = c->W, H = c->H;
   forget_solve(c, cost_out, passes_out);  // no kept field to lose: kc_planner_set_oriented dropped it
   c->or_solve = true;
-  const unsigned blocks = plan_blocks_for(n);
   const int unknown_blocks = allow_unknown ? 0 : 1;
   KC_TRY(planner_oriented_validity(c, c->or_a2, c->or_b2, unknown_blocks));
   const long long goal = plan_cell_index(c, goal_cell);
-  KC_TRY(c->d_field4[0].reserve(4 * static_cast<size_t>(n)));
-  KC_TRY(c->d_field4[1].reserve(4 * static_cast<size_t>(n)));
-  hipLaunchKernelGGL(planner_init4_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field4[0].p, c->d_field4[1].p, c->d_valid4.p, n, goal);
-  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), s));
-  KC_HIP(hipGetLastError());
-  c->final_buf = 0;  // both buffers hold the initial state
+  KC_TRY(planner_start_pair(c, c->d_field4, 4 * static_cast<size_t>(n), [&](uint32_t *a, uint32_t *b) {
+    hipLaunchKernelGGL(planner_init4_kernel, dim3(plan_blocks_for(n)), dim3(kPlanBlock), 0, s, a, b, c->d_valid4.p, n, goal);
+  }));
   uint32_t passes = 0;
   if (goal >= 0) {
     const auto pass4 = [&](uint32_t pass, int b) {
@@ -2057,9 +2074,7 @@ int kc_planner_set_car(kc_planner *c, int turn_cells, uint32_t reverse_weight, u
   if (c->clear_c2 > 0) KC_FAIL(KC_ERR_STATE, "car motion cannot be set while a clearance cost is on (rule 35)");
   if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "car motion cannot be set while the oriented mode is on: hand the box to kc_planner_set_car (rule 35)");
   if (a2 == 0 && b2 != 0) KC_FAIL(KC_ERR_INVALID, "a box footprint needs a2 > 0 (a2 = b2 = 0 is the disc)");
-  const unsigned long long t2 = static_cast<unsigned long long>(a2) + b2;
-  if (t2 > static_cast<unsigned long long>(KC_PLANNER_MAX_RADIUS_CELLS) * KC_PLANNER_MAX_RADIUS_CELLS)
-    KC_FAIL(KC_ERR_RANGE, "a box of A2 + B2 = %llu is wider than %d cells", t2, KC_PLANNER_MAX_RADIUS_CELLS);
+  KC_TRY(check_box(a2, b2, "box of A2 + B2"));
   const bool new_box = c->car_turn == 0 || c->car_a2 != a2 || c->car_b2 != b2;
   if (new_box && a2 > 0) KC_TRY(planner_upload_box(c, a2, b2));
   c->car_turn = turn_cells;
@@ -2078,8 +2093,7 @@ int kc_planner_solve_car(kc_planner *c, const int start_cell[2], int start_headi
   if (start_heading < 0 || start_heading > 7) KC_FAIL(KC_ERR_INVALID, "start heading %d is outside 0 .. 7", start_heading);
   if (goal_heading < -1 || goal_heading > 7) KC_FAIL(KC_ERR_INVALID, "goal heading %d is outside -1 .. 7", goal_heading);
   const bool box = c->car_a2 > 0;
-  if (!box && r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
-    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  if (!box) KC_TRY(check_radius(r2));
   const long long n = static_cast<long long>(c->W) * c->H;
   // field <= 24 n max(rw, 1) * (8 * cells - 1): the sums of the relaxation stay below the 0xFFFFFFFF of "nothing arrives",
   // and 8 * cells below the bit the walk keeps its primitive in
@@ -2088,12 +2102,10 @@ int kc_planner_solve_car(kc_planner *c, const int start_cell[2], int start_headi
   KC_HIP(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const int W = c->W, H = c->H;
-  const auto now = [] { return std::chrono::steady_clock::now(); };
-  const auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<float, std::milli>(now() - t).count(); };
   forget_solve(c, cost_out, passes_out);  // the disc's kept field goes as with any other solve
   c->car_solve = true;
   c->car_ms[0] = c->car_ms[1] = c->car_ms[2] = 0.0f;
-  auto t0 = now();
+  PlanClock clock;
   const unsigned blocks = plan_blocks_for(n);
   const int unknown_blocks = allow_unknown ? 0 : 1;
   // rule 28: the maps of the footprint in use, made by the kernels of rules 2 and 14 as they are
@@ -2117,18 +2129,13 @@ int kc_planner_solve_car(kc_planner *c, const int start_cell[2], int start_headi
     c->car_have_moves = true;
   }
   const long long goal = plan_cell_index(c, goal_cell);
-  KC_TRY(c->d_field8[0].reserve(8 * static_cast<size_t>(n)));
-  KC_TRY(c->d_field8[1].reserve(8 * static_cast<size_t>(n)));
-  with_bool(box, [&](auto on) {
-    hipLaunchKernelGGL(planner_init8_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field8[0].p, c->d_field8[1].p, vmap, n,
-                       goal, goal_heading);
-  });
-  KC_HIP(hipMemsetAsync(c->d_word.p, 0, kPlanSolveWords * sizeof(uint32_t), s));
-  KC_HIP(hipGetLastError());
+  KC_TRY(planner_start_pair(c, c->d_field8, 8 * static_cast<size_t>(n), [&](uint32_t *a, uint32_t *b) {
+    with_bool(box, [&](auto on) {
+      hipLaunchKernelGGL(planner_init8_kernel<decltype(on)::value>, dim3(blocks), dim3(kPlanBlock), 0, s, a, b, vmap, n, goal, goal_heading);
+    });
+  }));
   KC_HIP(hipStreamSynchronize(s));  // the maps and the moves end here, inside the first phase's clock
-  c->car_ms[0] = ms_since(t0);
-  t0 = now();
-  c->final_buf = 0;  // both buffers hold the initial state
+  c->car_ms[0] = clock.lap();
   uint32_t passes = 0;
   if (goal >= 0) {
     const auto pass8 = [&](uint32_t pass, int b) {
@@ -2143,7 +2150,7 @@ int kc_planner_solve_car(kc_planner *c, const int start_cell[2], int start_headi
   const uint32_t goal_mask = !box ? 0xFFu : (goal_heading < 0 ? 15u : 1u << (goal_heading & 3));
   KC_TRY(planner_finish(c, start_cell, goal_cell, c->d_field8[c->final_buf].p + static_cast<size_t>(start_heading) * static_cast<size_t>(n), vmap,
                         start_mask, goal_mask, false, status_out, cost_out));
-  c->car_ms[1] = ms_since(t0);
+  c->car_ms[1] = clock.lap();
   if (passes_out) *passes_out = static_cast<int>(passes);
   return KC_OK;
 }
@@ -2200,8 +2207,7 @@ int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint
   if (components_out) *components_out = 0;
   if (count_out) *count_out = 0;
   if (label_passes_out) *label_passes_out = 0;
-  if (r2 >= static_cast<uint32_t>(KC_PLANNER_MAX_RADIUS_CELLS + 1) * (KC_PLANNER_MAX_RADIUS_CELLS + 1))
-    KC_FAIL(KC_ERR_RANGE, "a footprint of R2 = %u is wider than %d cells", r2, KC_PLANNER_MAX_RADIUS_CELLS);
+  KC_TRY(check_radius(r2));
   if (min_size == 0) KC_FAIL(KC_ERR_RANGE, "min_size must be at least 1");
   if (!c->have_grid) KC_FAIL(KC_ERR_STATE, "kc_planner_explore before a grid was set");
   if (c->or_a2 > 0) KC_FAIL(KC_ERR_STATE, "kc_planner_explore with the oriented footprint on (rule 22)");
@@ -2215,29 +2221,23 @@ int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint
   PlanWords *d = c->d_word.p;
   forget_solve(c, nullptr, passes_out);
   c->ex_components = c->ex_tiles = 0;
-  const auto now = [] { return std::chrono::steady_clock::now(); };
-  const auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<float, std::milli>(now() - t).count(); };
-  auto t0 = now();
+  PlanClock clock;
   // rule 21.  d_valid then describes no (r2, unknown) of a solve: the cache says so, and forget_solve dropped the kept field
   KC_TRY(planner_validity(c, r2, 0));
   c->have_valid = false;
   hipLaunchKernelGGL(planner_known_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_cls.p, c->d_valid.p, n);
   // rule 22: rule 3's field with the robot's cell as its root
   const long long robot = plan_cell_index(c, robot_cell);
-  KC_TRY(c->d_field[0].reserve(static_cast<size_t>(n)));
-  KC_TRY(c->d_field[1].reserve(static_cast<size_t>(n)));
-  hipLaunchKernelGGL(planner_init_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, c->d_field[0].p, c->d_field[1].p, c->d_valid.p, n, robot);
-  KC_HIP(hipMemsetAsync(d, 0, kPlanSolveWords * sizeof(uint32_t), s));
-  KC_HIP(hipGetLastError());
-  c->final_buf = 0;  // both buffers hold the initial state
+  KC_TRY(planner_start_pair(c, c->d_field, static_cast<size_t>(n), [&](uint32_t *a, uint32_t *b) {
+    hipLaunchKernelGGL(planner_init_kernel, dim3(blocks), dim3(kPlanBlock), 0, s, a, b, c->d_valid.p, n, robot);
+  }));
   uint32_t passes = 0, label_passes = 0;
   if (robot >= 0) KC_TRY(planner_relax(c, disc_pass(c, nullptr, ntiles), n, "cost", &c->final_buf, &passes));
   PlanPinned *h = c->h_word.p;
   h->start_valid = 0;
   if (robot >= 0) KC_HIP(hipMemcpyAsync(&h->start_valid, c->d_valid.p + robot, 1, hipMemcpyDeviceToHost, s));
   KC_HIP(hipStreamSynchronize(s));
-  c->ex_ms[0] = ms_since(t0);
-  t0 = now();
+  c->ex_ms[0] = clock.lap();
   // rule 23, and the tiles that hold a frontier cell.  With the robot outside the grid or on a cell that is not
   // explore-valid the field is INF everywhere and nothing is marked.
   const uint32_t *field = c->d_field[c->final_buf].p;
@@ -2262,13 +2262,12 @@ int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint
   if (listed) {
     // rule 24 over the listed tiles, to the fixed point
     const auto label_pass = [&](uint32_t pass, int b) {
-      hipLaunchKernelGGL(planner_label_kernel, dim3(listed), dim3(kPlanThreads), 0, s, c->d_label[b].p, c->d_label[b ^ 1].p, c->d_front.p, W, H,
-                         c->tiles_x, c->d_tile_list.p, &d->changed, pass);
+      hipLaunchKernelGGL(planner_label_kernel, dim3(listed), dim3(kPlanThreads), 0, s, c->d_label[b].p, c->d_label[b ^ 1].p, W, H, c->tiles_x,
+                         c->d_tile_list.p, &d->changed, pass);
     };
     KC_TRY(planner_relax(c, label_pass, n, "label", &c->label_buf, &label_passes));
   }
-  c->ex_ms[1] = ms_since(t0);
-  t0 = now();
+  c->ex_ms[1] = clock.lap();
   uint32_t components = 0, kept = 0;
   if (listed) {
     // rule 24's sizes at the roots, in the plane the labels no longer need (both hold the fixed point), then the two counts
@@ -2309,7 +2308,7 @@ int kc_planner_explore(kc_planner *c, const int robot_cell[2], uint32_t r2, uint
       }
     }
   }
-  c->ex_ms[2] = ms_since(t0);
+  c->ex_ms[2] = clock.lap();
   int st = kept ? KC_PLAN_FOUND : KC_PLAN_NO_FRONTIER;
   if (robot < 0) st = KC_PLAN_START_OUTSIDE;
   else if (!h->start_valid) st = KC_PLAN_START_INVALID;
