@@ -1656,6 +1656,62 @@ int kc_worldmap_integrate_set_precheck(kc_worldmap *ctx, int enable);
 int kc_worldmap_integrate_set_timing(kc_worldmap *ctx, int enable);
 int kc_worldmap_integrate_times(kc_worldmap *ctx, float ms_out[2]);
 
+/* Finding moving obstacles in a measured scan (DESIGN.md 4.11 rules 64 to 70): the returns that
+ * end where the map has seen free space far from anything occupied, grouped into runs of
+ * neighbouring beams.  Nothing in the reference to cite, as above; integers throughout, bit-equal
+ * to tests/worldmap_movers_ref.py.  The map is read and never written.
+ * Rule 64, input: pose, angles and zq as rule 52's; m2 (1 <= m2 <= reach^2), gap (<= 64), join_q
+ * (<= 2^40, in 2^-16 cells^2) and min_beams (1 .. 65536).  The distance plane must be on and m2
+ * <= reach^2; it is refreshed first (rule 43) and read in place.  Rule 65, endpoint: for 0 <= zq_k
+ * < ZMAX, (EX_k, EY_k) by rule 44 from the pose's (TX, TY) and rule 22's direction, I = EX >> 16,
+ * J = EY >> 16; a beam with zq_k of -1 or ZMAX has none.  Rule 66, dynamic beam: it has an
+ * endpoint, the endpoint lies inside the map, cls is KC_EMPTY there and dist2 > m2 (FAR counts as
+ * above); a never-observed cell is new territory, not motion.  Rule 67, runs: over the dynamic
+ * beams in scan order, beam k whose nearest earlier dynamic beam is p continues p's run iff k - p
+ * <= gap + 1 and ((EX_k - EX_p) >> 8)^2 + ((EY_k - EY_p) >> 8)^2 <= join_q (arithmetic shifts);
+ * otherwise, and for the first dynamic beam, it starts one.  The scan is not circular.  Rule 68,
+ * kept clusters: the runs of at least min_beams members, numbered from 0 in the order of their
+ * first beam, each with the record below; integer sums, minima and maxima, so no thread order
+ * takes part.  Rule 69, outputs: label[k] is the kept cluster's number (beyond 255 too), -1 for a
+ * beam that is not dynamic, -2 for a dynamic beam of a dropped run; the record; the first
+ * n_returned cluster records. */
+#define KC_WORLDMAP_MAX_CLUSTERS 256
+typedef struct kc_worldmap_cluster { /* rule 68; 64 bytes */
+  int32_t k_first, k_last;           /* the run's first and last beam */
+  int32_t n;                         /* its members */
+  int32_t reserved;                  /* 0 */
+  int64_t sx, sy;                    /* the sums of EX and EY, below 2^54 in magnitude */
+  int64_t min_x, max_x, min_y, max_y; /* of EX and EY */
+} kc_worldmap_cluster;
+typedef struct kc_worldmap_movers_record { /* rule 69 */
+  uint32_t n_dynamic, n_runs, n_kept;
+  uint32_t n_returned;                     /* min(n_kept, KC_WORLDMAP_MAX_CLUSTERS) */
+} kc_worldmap_movers_record;
+/* Rule 70's refusals (host only, needs no device), in this order: kc_worldmap_integrate_check's
+ * without flags (the resolution and the counts, range_max, zq_or_null when given); then m2 == 0
+ * (KC_ERR_INVALID), gap > 64, join_q > 2^40 (KC_ERR_RANGE), min_beams == 0 (KC_ERR_INVALID),
+ * min_beams > 65536 (KC_ERR_RANGE).  zmax_out (may be NULL): ZMAX, 0 on a refusal. */
+int kc_worldmap_movers_check(float resolution, size_t n_beams, float range_max, const int32_t *zq_or_null, uint32_t m2,
+                             uint32_t gap, uint64_t join_q, uint32_t min_beams, int64_t *zmax_out);
+/* Rules 64 to 69: the refresh of the distance plane where its box is dirty, then two launches on
+ * the map's stream (worldmap_movers_flag_kernel, a lane a beam: the endpoint, the bounds test and
+ * the two loads; worldmap_movers_cluster_kernel, one workgroup of 1024 lanes with a chunk of
+ * consecutive beams a lane: compaction, rule 67's head test, the run and kept numbering by prefix
+ * counts, a wavefront a returned cluster for the sums, the labels) and one read-back of record,
+ * clusters and labels; returns with the outputs final.  label_out_or_null: n_beams int32.
+ * clusters_out: cap records, of which min(n_returned, cap) are written.  Checks: null arguments,
+ * then kc_worldmap_movers_check with zq, the angles (finite), the pose (as an update's), then
+ * KC_ERR_STATE while the distance plane is off or for m2 > reach^2; a refused call queues
+ * nothing, the refresh included, and writes an all-zero record. */
+int kc_worldmap_movers(kc_worldmap *ctx, const kc_worldmap_pose *pose, const double *angles, size_t n_beams,
+                       const int32_t *zq, float range_max, uint32_t m2, uint32_t gap, uint64_t join_q, uint32_t min_beams,
+                       int32_t *label_out_or_null, kc_worldmap_cluster *clusters_out, size_t cap,
+                       kc_worldmap_movers_record *record_out);
+/* HIP events around the two launches of kc_worldmap_movers; ms_out: flag, cluster of the last
+ * call.  KC_ERR_STATE when no detection has been timed. */
+int kc_worldmap_movers_set_timing(kc_worldmap *ctx, int enable);
+int kc_worldmap_movers_times(kc_worldmap *ctx, float ms_out[2]);
+
 /* ------------------------------------------------------------------------ */
 /* The localiser's fit record and its recovery by injected particles (DESIGN.md 4.11 rules 59 to 63) */
 /* ------------------------------------------------------------------------ */

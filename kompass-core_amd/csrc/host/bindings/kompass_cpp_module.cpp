@@ -17,6 +17,7 @@
 #include "controllers/stanley.h"
 #include "mapping/local_mapper_gpu.h"
 #include "mapping/mcl.h"
+#include "mapping/mover_tracker.h"
 #include "mapping/world_map.h"
 #include "planning/grid_planner.h"
 #include "utils/logger.h"
@@ -1112,6 +1113,68 @@ PYBIND11_MODULE(kompass_cpp, m) {
       .def("scores", &worldMapMatchScores,
            "the score table, uint32 [2 n_yaw + 1, 2 reach + 1, 2 reach + 1] indexed [k + n_yaw, v + reach, u + reach]; "
            "RuntimeError once the map has made another match");
+  py::class_<Mapping::MoverDetectConfig>(mp, "MoverDetectConfig",
+                                         "WorldMap.detect_movers' parameters (DESIGN.md 4.11 rule 64); the defaults are judgement")
+      .def(py::init([](uint32_t m2, uint32_t gap, uint64_t join_q, uint32_t min_beams) {
+             Mapping::MoverDetectConfig c;
+             c.m2 = m2, c.gap = gap, c.join_q = join_q, c.min_beams = min_beams;
+             return c;
+           }), py::arg("m2") = 4, py::arg("gap") = 2, py::arg("join_q") = 9ull << 16, py::arg("min_beams") = 3)
+      .def_readwrite("m2", &Mapping::MoverDetectConfig::m2)
+      .def_readwrite("gap", &Mapping::MoverDetectConfig::gap)
+      .def_readwrite("join_q", &Mapping::MoverDetectConfig::join_q)
+      .def_readwrite("min_beams", &Mapping::MoverDetectConfig::min_beams);
+  py::class_<Mapping::MoverCluster>(mp, "MoverCluster", "A kept cluster: world metres, and rule 68's integers")
+      .def(py::init([](double x, double y, double radius) {
+             Mapping::MoverCluster c;
+             c.x = x, c.y = y, c.radius = radius;
+             return c;
+           }), py::arg("x") = 0.0, py::arg("y") = 0.0, py::arg("radius") = 0.0)
+      .def_readwrite("x", &Mapping::MoverCluster::x)
+      .def_readwrite("y", &Mapping::MoverCluster::y)
+      .def_readwrite("radius", &Mapping::MoverCluster::radius)
+      .def_property_readonly("raw", [](const Mapping::MoverCluster &c) {
+             const kc_worldmap_cluster &r = c.raw;
+             return py::make_tuple(r.k_first, r.k_last, r.n, r.sx, r.sy, r.min_x, r.max_x, r.min_y, r.max_y);
+           }, "(k_first, k_last, n, sx, sy, min_x, max_x, min_y, max_y)");
+  py::class_<Mapping::MoverDetection>(mp, "MoverDetection")
+      .def_readonly("clusters", &Mapping::MoverDetection::clusters)
+      .def_property_readonly("labels", [](const Mapping::MoverDetection &d) {
+             return py::array_t<int32_t>(static_cast<py::ssize_t>(d.labels.size()), d.labels.data());
+           }, "int32 a beam: the kept cluster's number, -1 not dynamic, -2 a dynamic beam of a dropped run")
+      .def_property_readonly("record", [](const Mapping::MoverDetection &d) {
+             return py::make_tuple(d.record.n_dynamic, d.record.n_runs, d.record.n_kept, d.record.n_returned);
+           }, "(n_dynamic, n_runs, n_kept, n_returned)");
+  {
+    using Tracker = Mapping::MoverTracker;
+    py::class_<Tracker::Track>(mp, "MoverTrack")
+        .def_readonly("id", &Tracker::Track::id)
+        .def_readonly("x", &Tracker::Track::x)
+        .def_readonly("y", &Tracker::Track::y)
+        .def_readonly("vx", &Tracker::Track::vx)
+        .def_readonly("vy", &Tracker::Track::vy)
+        .def_readonly("radius", &Tracker::Track::radius)
+        .def_readonly("hits", &Tracker::Track::hits)
+        .def_readonly("misses", &Tracker::Track::misses);
+    py::class_<Tracker>(mp, "MoverTracker",
+                        "Alpha-beta tracks over detect_movers' clusters, greedy nearest neighbour; host only.  The defaults are judgement")
+        .def(py::init([](double alpha, double beta, int max_misses, double gate) {
+               Mapping::MoverTrackerConfig c;
+               c.alpha = alpha, c.beta = beta, c.max_misses = max_misses, c.gate = gate;
+               return std::make_unique<Tracker>(c);
+             }), py::arg("alpha") = 0.5, py::arg("beta") = 0.3, py::arg("max_misses") = 3, py::arg("gate") = 6.0)
+        .def("update", [](Tracker &t, const std::vector<Mapping::MoverCluster> &clusters, double dt) { t.update(clusters, dt); },
+             py::arg("clusters"), py::arg("dt"))
+        .def("update", [](Tracker &t, const Mapping::MoverDetection &d, double dt) { t.update(d, dt); }, py::arg("detection"),
+             py::arg("dt"))
+        .def_property_readonly("tracks", &Tracker::tracks)
+        .def("moving_obstacles", &Tracker::movingObstacles, "a MovingObstacle for every live track")
+        .def_static("skip_mask", [](const std::vector<int32_t> &labels) {
+               const std::vector<uint8_t> m = Tracker::skipMask(labels);
+               return py::array_t<uint8_t>(static_cast<py::ssize_t>(m.size()), m.data());
+             }, py::arg("labels"), "uint8 a beam: 1 for the member beams of every kept cluster")
+        .def("clear", &Tracker::clear);
+  }
   py::class_<Mapping::WorldMap>(mp, "WorldMap")
       .def(py::init([](int width, int height, float resolution, double origin_x, double origin_y) {
              return std::make_unique<Mapping::WorldMap>(width, height, resolution, origin_x, origin_y);
@@ -1213,20 +1276,50 @@ PYBIND11_MODULE(kompass_cpp, m) {
            }, py::arg("poses"), py::arg("angles"), py::arg("range_max"), py::arg("unknown_blocks") = false,
            "The same for a batch of poses (x, y, yaw) in one launch: float64 [M, B]")
       .def("integrate_scan", [](Mapping::WorldMap &m, double x, double y, double yaw, const std::vector<double> &angles,
-                                const std::vector<double> &ranges, float range_max, float range_min, bool clear_no_return) {
+                                const std::vector<double> &ranges, float range_max, float range_min, bool clear_no_return,
+                                const std::vector<uint8_t> &skip) {
              py::gil_scoped_release nogil;
-             return m.integrateScan(x, y, yaw, angles, ranges, range_max, range_min, clear_no_return);
+             return m.integrateScan(x, y, yaw, angles, ranges, range_max, range_min, clear_no_return, skip);
            }, py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("angles"), py::arg("ranges"), py::arg("range_max"),
-           py::arg("range_min") = 0.0f, py::arg("clear_no_return") = false,
+           py::arg("range_min") = 0.0f, py::arg("clear_no_return") = false, py::arg("skip") = std::vector<uint8_t>(),
            "One measured laser scan into the map by an inverse ray cast (DESIGN.md 4.11 rules 52 to 58); (x, y, yaw): the scan "
-           "frame's pose in the world.  -> changed cells")
+           "frame's pose in the world; skip: empty, or an entry a beam, not 0 where the beam is to say nothing.  -> changed cells")
       .def("integrate_scan_at", [](Mapping::WorldMap &m, const py::tuple &pose, const std::vector<double> &angles,
-                                   const std::vector<double> &ranges, float range_max, float range_min, bool clear_no_return) {
+                                   const std::vector<double> &ranges, float range_max, float range_min, bool clear_no_return,
+                                   const std::vector<uint8_t> &skip) {
              const kc_worldmap_pose p = worldMapPose(pose);
              py::gil_scoped_release nogil;
-             return m.integrateScanAt(p, angles, ranges, range_max, range_min, clear_no_return);
+             return m.integrateScanAt(p, angles, ranges, range_max, range_min, clear_no_return, skip);
            }, py::arg("pose"), py::arg("angles"), py::arg("ranges"), py::arg("range_max"), py::arg("range_min") = 0.0f,
-           py::arg("clear_no_return") = false, "integrate_scan at a quantised pose (cq, sq, tx, ty), a match's `pose`")
+           py::arg("clear_no_return") = false, py::arg("skip") = std::vector<uint8_t>(),
+           "integrate_scan at a quantised pose (cq, sq, tx, ty), a match's `pose`")
+      .def("detect_movers", [](const Mapping::WorldMap &m, double x, double y, double yaw, const std::vector<double> &angles,
+                               const std::vector<double> &ranges, float range_max, float range_min,
+                               const Mapping::MoverDetectConfig &config) {
+             py::gil_scoped_release nogil;
+             return m.detectMovers(x, y, yaw, angles, ranges, range_max, range_min, config);
+           }, py::arg("x"), py::arg("y"), py::arg("yaw"), py::arg("angles"), py::arg("ranges"), py::arg("range_max"),
+           py::arg("range_min") = 0.0f, py::arg("config") = Mapping::MoverDetectConfig(),
+           "Moving obstacles in a measured scan (DESIGN.md 4.11 rules 64 to 69): the returns that end in free space the map has "
+           "seen, grouped into clusters in world metres, and a label a beam.  The distance plane must be on.  -> MoverDetection")
+      .def("detect_movers_at", [](const Mapping::WorldMap &m, const py::tuple &pose, const std::vector<double> &angles,
+                                  const std::vector<double> &ranges, float range_max, float range_min,
+                                  const Mapping::MoverDetectConfig &config) {
+             const kc_worldmap_pose p = worldMapPose(pose);
+             py::gil_scoped_release nogil;
+             return m.detectMoversAt(p, angles, ranges, range_max, range_min, config);
+           }, py::arg("pose"), py::arg("angles"), py::arg("ranges"), py::arg("range_max"), py::arg("range_min") = 0.0f,
+           py::arg("config") = Mapping::MoverDetectConfig(), "detect_movers at a quantised pose (cq, sq, tx, ty)")
+      .def_static("cluster_to_world", [](const py::tuple &raw, float resolution, double origin_x, double origin_y) {
+             if (raw.size() != 9) throw std::invalid_argument("a raw cluster has nine entries");
+             kc_worldmap_cluster c{};
+             c.k_first = raw[0].cast<int32_t>(), c.k_last = raw[1].cast<int32_t>(), c.n = raw[2].cast<int32_t>();
+             c.sx = raw[3].cast<int64_t>(), c.sy = raw[4].cast<int64_t>();
+             c.min_x = raw[5].cast<int64_t>(), c.max_x = raw[6].cast<int64_t>();
+             c.min_y = raw[7].cast<int64_t>(), c.max_y = raw[8].cast<int64_t>();
+             return Mapping::WorldMap::clusterToWorld(c, resolution, origin_x, origin_y);
+           }, py::arg("raw"), py::arg("resolution"), py::arg("origin_x"), py::arg("origin_y"),
+           "A cluster's (k_first, k_last, n, sx, sy, min_x, max_x, min_y, max_y) in world metres; needs no device")
       .def("enable_distance", &Mapping::WorldMap::enableDistance, py::arg("reach"), py::arg("unknown_blocks") = false,
            "Keep the distance plane at `reach` cells (1 .. 254; 0: off): DESIGN.md 4.11 rules 42 and 43")
       .def_property_readonly("distance_reach", &Mapping::WorldMap::distanceReach)

@@ -18,6 +18,24 @@
 namespace Kompass {
 namespace Mapping {
 
+// WorldMap::detectMovers' parameters (DESIGN.md 4.11 rule 64) and results.  The defaults are the prototype's values:
+// judgement, not measurement.
+struct MoverDetectConfig {
+  uint32_t m2 = 4;               // cells^2: a return nearer than this to an occupied cell is the wall's
+  uint32_t gap = 2;              // beams that may be missing inside a run
+  uint64_t join_q = 9ull << 16;  // 2^-16 cells^2: neighbours further apart than this start a new run
+  uint32_t min_beams = 3;        // a run of fewer beams is dropped
+};
+struct MoverCluster {
+  double x = 0.0, y = 0.0, radius = 0.0;  // world metres: the mean endpoint, half the longer side of the endpoints' box
+  kc_worldmap_cluster raw = {};           // rule 68's integers
+};
+struct MoverDetection {
+  std::vector<MoverCluster> clusters;     // the first n_returned
+  std::vector<int32_t> labels;            // rule 69, a beam
+  kc_worldmap_movers_record record = {};
+};
+
 class WorldMap {
  public:
   // width x height cells, cell (I, J) at I + J * width; (origin_x, origin_y): the world position of cell (0, 0)'s
@@ -105,10 +123,30 @@ class WorldMap {
   // miss where beams disagree.  Two launches on the device.  Returns changed(); changedBox() follows.
   // std::invalid_argument (sizes that differ, no beam, range_max, range_min, a non-finite angle or pose),
   // std::out_of_range (above 2048 cells of range or 65536 beams).  ...At: at a quantised pose (a Match's).
+  // skip: empty, or one entry a beam; a beam whose entry is not 0 says nothing (rule 54), whatever its range: zq_k = -1
+  // behind the quantiser, on the host, so the kernels see nothing new and a call without a mask is what it was.  What
+  // MoverTracker::skipMask gives keeps a mover's returns out of the map.
   uint32_t integrateScan(double x, double y, double yaw, const std::vector<double> &angles, const std::vector<double> &ranges,
-                         float range_max, float range_min = 0.0f, bool clear_no_return = false);
+                         float range_max, float range_min = 0.0f, bool clear_no_return = false,
+                         const std::vector<uint8_t> &skip = {});
   uint32_t integrateScanAt(const kc_worldmap_pose &pose, const std::vector<double> &angles, const std::vector<double> &ranges,
-                           float range_max, float range_min = 0.0f, bool clear_no_return = false);
+                           float range_max, float range_min = 0.0f, bool clear_no_return = false,
+                           const std::vector<uint8_t> &skip = {});
+
+  // Moving obstacles in a measured scan (DESIGN.md 4.11 rules 64 to 69): the returns that end in cells the map has seen
+  // EMPTY, more than sqrt(m2) cells from anything occupied, grouped into runs of neighbouring beams.  Arguments as
+  // integrateScan's; the map is read and never written, the distance plane must be on (std::runtime_error otherwise,
+  // and for m2 above its reach^2).  Two launches on the device and one read-back.  The defaults are the prototype's
+  // values: judgement, not measurement.
+  MoverDetection detectMovers(double x, double y, double yaw, const std::vector<double> &angles, const std::vector<double> &ranges,
+                              float range_max, float range_min = 0.0f, const MoverDetectConfig &config = MoverDetectConfig()) const;
+  MoverDetection detectMoversAt(const kc_worldmap_pose &pose, const std::vector<double> &angles, const std::vector<double> &ranges,
+                                float range_max, float range_min = 0.0f, const MoverDetectConfig &config = MoverDetectConfig()) const;
+  // A cluster in world metres: centre origin + ((SX / n) - 32768) / 65536 * resolution -- rule 65's EX of a return in the
+  // middle of cell I is (I << 16) + 2^15, and the origin is cell (0, 0)'s centre -- with rule 46's origin at the current
+  // offset; radius max(max_x - min_x, max_y - min_y) / 2 / 65536 * resolution, which a disc's returns never push past the
+  // disc's own radius (half the box's diagonal would, by up to sqrt(2)).  Needs no device.
+  static MoverCluster clusterToWorld(const kc_worldmap_cluster &c, float resolution, double origin_x, double origin_y);
 
   // The distance plane (DESIGN.md 4.11 rules 42 and 43), off by default: per cell the squared distance in cells to the
   // nearest OCCUPIED cell (with unknown_blocks also a never-observed one) within `reach` cells, KC_WORLDMAP_DIST_FAR

@@ -1,6 +1,8 @@
 // WorldMap host side: argument plumbing over kc_worldmap_* (no reference counterpart, see the header).
 #include "mapping/world_map.h"
 
+#include <algorithm>
+#include <cmath>
 #include <stdexcept>
 
 namespace Kompass {
@@ -194,18 +196,54 @@ std::vector<double> WorldMap::scanCells(double x, double y, double yaw, const st
 }
 
 uint32_t WorldMap::integrateScanAt(const kc_worldmap_pose &pose, const std::vector<double> &angles, const std::vector<double> &ranges,
-                                   float range_max, float range_min, bool clear_no_return) {
+                                   float range_max, float range_min, bool clear_no_return, const std::vector<uint8_t> &skip) {
   if (angles.size() != ranges.size()) throw std::invalid_argument("integrateScan: one range a beam angle");
+  if (!skip.empty() && skip.size() != ranges.size()) throw std::invalid_argument("integrateScan: one skip entry a beam, or none");
   std::vector<int32_t> zq(ranges.size());
   hip::check(kc_worldmap_quantise_ranges(res_, ranges.data(), ranges.size(), range_max, range_min, zq.data()));
+  for (size_t k = 0; k < skip.size(); ++k)
+    if (skip[k]) zq[k] = -1;  // rule 54: the beam says nothing
   hip::check(kc_worldmap_integrate(ctx_.get(), &pose, angles.data(), angles.size(), zq.data(), range_max,
                                    clear_no_return ? KC_INTEGRATE_CLEAR_NO_RETURN : 0u, &last_));
   return last_.changed;
 }
 
 uint32_t WorldMap::integrateScan(double x, double y, double yaw, const std::vector<double> &angles, const std::vector<double> &ranges,
-                                 float range_max, float range_min, bool clear_no_return) {
-  return integrateScanAt(quantisePose(res_, ox_, oy_, x, y, yaw), angles, ranges, range_max, range_min, clear_no_return);
+                                 float range_max, float range_min, bool clear_no_return, const std::vector<uint8_t> &skip) {
+  return integrateScanAt(quantisePose(res_, ox_, oy_, x, y, yaw), angles, ranges, range_max, range_min, clear_no_return, skip);
+}
+
+MoverCluster WorldMap::clusterToWorld(const kc_worldmap_cluster &c, float resolution, double origin_x, double origin_y) {
+  if (c.n < 1) throw std::invalid_argument("clusterToWorld: a cluster has at least one beam");
+  const double r = static_cast<double>(resolution), n = static_cast<double>(c.n);
+  MoverCluster out;
+  out.x = origin_x + (static_cast<double>(c.sx) / n - 32768.0) / 65536.0 * r;
+  out.y = origin_y + (static_cast<double>(c.sy) / n - 32768.0) / 65536.0 * r;
+  // half the longer side of the endpoints' box: at most the mover's own radius, which half the diagonal can pass by sqrt(2)
+  out.radius = static_cast<double>(std::max(c.max_x - c.min_x, c.max_y - c.min_y)) / 2.0 / 65536.0 * r;
+  out.raw = c;
+  return out;
+}
+
+MoverDetection WorldMap::detectMoversAt(const kc_worldmap_pose &pose, const std::vector<double> &angles,
+                                        const std::vector<double> &ranges, float range_max, float range_min,
+                                        const MoverDetectConfig &config) const {
+  if (angles.size() != ranges.size()) throw std::invalid_argument("detectMovers: one range a beam angle");
+  std::vector<int32_t> zq(ranges.size());
+  hip::check(kc_worldmap_quantise_ranges(res_, ranges.data(), ranges.size(), range_max, range_min, zq.data()));
+  MoverDetection out;
+  out.labels.assign(ranges.size(), -1);
+  std::vector<kc_worldmap_cluster> raw(KC_WORLDMAP_MAX_CLUSTERS);
+  hip::check(kc_worldmap_movers(ctx_.get(), &pose, angles.data(), angles.size(), zq.data(), range_max, config.m2, config.gap,
+                                config.join_q, config.min_beams, out.labels.data(), raw.data(), raw.size(), &out.record));
+  out.clusters.reserve(out.record.n_returned);
+  for (uint32_t i = 0; i < out.record.n_returned; ++i) out.clusters.push_back(clusterToWorld(raw[i], res_, ox_, oy_));  // rule 46's origin
+  return out;
+}
+
+MoverDetection WorldMap::detectMovers(double x, double y, double yaw, const std::vector<double> &angles, const std::vector<double> &ranges,
+                                      float range_max, float range_min, const MoverDetectConfig &config) const {
+  return detectMoversAt(quantisePose(res_, ox_, oy_, x, y, yaw), angles, ranges, range_max, range_min, config);
 }
 
 void WorldMap::enableDistance(int reach, bool unknown_blocks) {

@@ -63,6 +63,12 @@
 //      layout, turns a mark byte into one observation (a hit beats a miss), puts the byte back to zero and applies
 //      rule 5 with the update's record.  OR commutes and a cell is applied once: no thread order takes part.
 //
+//  (k) movers (rules 64 to 70).  The map read and never written: worldmap_movers_flag_kernel (a lane a beam) forms rule
+//      44's endpoint and tests rule 66 against the cls and dist2 planes; worldmap_movers_cluster_kernel (one workgroup of
+//      1024 lanes, consecutive beams a lane) compacts the dynamic beams, runs rule 67's head test and numbers runs and
+//      kept clusters by prefix counts, then a wavefront a returned cluster sums its endpoints.  Integer sums, minima and
+//      maxima: no thread order takes part.  Record, clusters and labels leave in one copy.
+//
 // Plain vector loads and stores only.
 #include <hip/hip_runtime.h>
 
@@ -766,6 +772,206 @@ __global__ __launch_bounds__(kWmBlock) void worldmap_integrate_apply_kernel(WmAp
   if (lane == last) atomicMax(&a.rec[3], I);
 }
 
+// ---- (k) movers in a scan (rules 64 to 70) ----
+constexpr int kWmMvBlock = 1024;               // the cluster kernel's one workgroup
+constexpr int kWmMvWaves = kWmMvBlock / 64;
+constexpr size_t kWmMvRecBytes = 64;           // the record's share of the output block, a cache line
+static_assert(sizeof(kc_worldmap_cluster) == 64, "rule 68's record is 64 bytes");
+static_assert(sizeof(kc_worldmap_movers_record) <= kWmMvRecBytes, "the record fits its line");
+
+struct WmMoversArgs {
+  const int8_t *cls;
+  const uint16_t *dist2;
+  const int2 *table;     // rule 21
+  const int32_t *zq;     // rule 52
+  kc_worldmap_pose pose;
+  long long zmax;
+  unsigned long long join_q;
+  unsigned m2;
+  int W, H, B, gap, min_beams;
+  // scratch the context keeps, B entries each (run_start: B + 1)
+  long long *ex, *ey;    // rule 65's endpoint; 0 where a beam has none
+  uint8_t *flag;         // rule 66
+  int *comp;             // the dynamic beams in scan order
+  int *run_of;           // the run of a compacted beam
+  int *run_start;        // a run's first compacted index; [n_runs] = n_dynamic
+  int *run_kept;         // a run's kept number, or -2
+  // the output block
+  kc_worldmap_movers_record *rec;
+  kc_worldmap_cluster *clusters;
+  int32_t *label;
+};
+
+// A lane a beam.  The bounds test stands in front of both loads, and neither load waits for the other.
+__global__ __launch_bounds__(kWmBlock) void worldmap_movers_flag_kernel(WmMoversArgs a) {
+  const int k = static_cast<int>(blockIdx.x) * kWmBlock + static_cast<int>(threadIdx.x);
+  if (k >= a.B) return;
+  const long long z = a.zq[k];
+  long long EX = 0, EY = 0;
+  bool dyn = false;
+  if (z >= 0 && z < a.zmax) {  // rule 65
+    const int2 t = a.table[k];
+    const long long dx = q16_turn_x(a.pose.cq, a.pose.sq, t.x, t.y), dy = q16_turn_y(a.pose.cq, a.pose.sq, t.x, t.y);
+    EX = a.pose.tx + (1ll << 15) + ((z * dx + (1ll << 29)) >> 30);
+    EY = a.pose.ty + (1ll << 15) + ((z * dy + (1ll << 29)) >> 30);
+    const long long I = EX >> 16, J = EY >> 16;
+    if (I >= 0 && I < a.W && J >= 0 && J < a.H) {  // rule 66
+      const size_t cell = static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W);
+      const int8_t c = a.cls[cell];
+      const unsigned d = a.dist2[cell];
+      dyn = c == KC_EMPTY && d > a.m2;
+    }
+  }
+  a.ex[k] = EX;
+  a.ey[k] = EY;
+  a.flag[k] = dyn ? 1 : 0;
+}
+
+// The exclusive prefix of v over the workgroup's 1024 lanes in lane order, and the total: a shuffle scan in the
+// wavefront, the 16 wavefront sums through `part`.  Every lane calls it; `part` is free again on return.
+__device__ __forceinline__ int wm_mv_exscan(int v, int *part, int *total) {
+  const int lane = static_cast<int>(threadIdx.x) & 63, w = static_cast<int>(threadIdx.x) >> 6;
+  int inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(inc, d);
+    if (lane >= d) inc += u;
+  }
+  if (lane == 63) part[w] = inc;
+  __syncthreads();
+  int before = 0, all = 0;
+  for (int i = 0; i < kWmMvWaves; ++i) {
+    const int p = part[i];
+    all += p;
+    before += i < w ? p : 0;
+  }
+  __syncthreads();
+  *total = all;
+  return before + inc - v;
+}
+
+__device__ __forceinline__ long long wm_mv_shfl_xor(long long v, int m) {
+  const int lo = __shfl_xor(static_cast<int>(v & 0xFFFFFFFFll), m), hi = __shfl_xor(static_cast<int>(v >> 32), m);
+  return (static_cast<long long>(hi) << 32) | static_cast<long long>(static_cast<unsigned>(lo));
+}
+
+// One workgroup.  Lane t owns the beams [t C, (t + 1) C), C = ceil(B / 1024) <= 64, so lane order is scan order and a
+// prefix count over the lanes numbers things in scan order.  Five steps, a barrier between them; what one step leaves
+// for the next goes through global scratch (the workgroup's own writes, visible behind the barrier).
+//  A  compaction: a lane counts its dynamic beams, the prefix gives its first compacted index, it writes its beams.
+//  B  rule 67's head test of a compacted beam against the one in front of it; the prefix count of heads numbers the runs.
+//  C  rule 68: a run's size is the distance of two run starts; the prefix count of kept runs numbers the clusters.
+//  D  a wavefront a returned cluster: sums, minima and maxima by shuffles, in int64.
+//  E  rule 69's labels, a lane over its own beams again.
+__global__ __launch_bounds__(kWmMvBlock) void worldmap_movers_cluster_kernel(WmMoversArgs a) {
+  __shared__ int s_part[kWmMvWaves];
+  __shared__ int s_kept_run[KC_WORLDMAP_MAX_CLUSTERS];
+  const int t = static_cast<int>(threadIdx.x);
+  const int C = (a.B + kWmMvBlock - 1) / kWmMvBlock;
+  const int k0 = min(t * C, a.B), k1 = min(k0 + C, a.B);
+  // A
+  int cnt = 0;
+  for (int k = k0; k < k1; ++k) cnt += a.flag[k];
+  int n_dyn = 0;
+  const int base = wm_mv_exscan(cnt, s_part, &n_dyn);
+  {
+    int idx = base;
+    for (int k = k0; k < k1; ++k)
+      if (a.flag[k]) a.comp[idx++] = k;
+  }
+  __syncthreads();
+  // B: bit j of hm, the head test of compacted beam base + j (cnt <= C <= 64)
+  unsigned long long hm = 0;
+  for (int j = 0; j < cnt; ++j) {
+    const int idx = base + j;
+    bool head = idx == 0;
+    if (!head) {
+      const int k = a.comp[idx], p = a.comp[idx - 1];
+      const long long ddx = (a.ex[k] - a.ex[p]) >> 8, ddy = (a.ey[k] - a.ey[p]) >> 8;  // below 2^30 in magnitude
+      head = k - p > a.gap + 1 || static_cast<unsigned long long>(ddx * ddx + ddy * ddy) > a.join_q;
+    }
+    hm |= static_cast<unsigned long long>(head) << j;
+  }
+  int n_runs = 0;
+  const int rbase = wm_mv_exscan(__popcll(hm), s_part, &n_runs);
+  {
+    int r = rbase - 1;  // the run of the compacted beam in front of this lane's first
+    for (int j = 0; j < cnt; ++j) {
+      if ((hm >> j) & 1ull) a.run_start[++r] = base + j;
+      a.run_of[base + j] = r;
+    }
+  }
+  if (t == 0) a.run_start[n_runs] = n_dyn;
+  __syncthreads();
+  // C: the runs in chunks of consecutive runs a lane
+  const int RC = (n_runs + kWmMvBlock - 1) / kWmMvBlock;
+  const int r0 = min(t * RC, n_runs), r1 = min(r0 + RC, n_runs);
+  int kept = 0;
+  for (int r = r0; r < r1; ++r) kept += a.run_start[r + 1] - a.run_start[r] >= a.min_beams ? 1 : 0;
+  int n_kept = 0;
+  const int kbase = wm_mv_exscan(kept, s_part, &n_kept);
+  {
+    int id = kbase;
+    for (int r = r0; r < r1; ++r) {
+      const bool keep = a.run_start[r + 1] - a.run_start[r] >= a.min_beams;
+      a.run_kept[r] = keep ? id : -2;
+      if (keep && id < KC_WORLDMAP_MAX_CLUSTERS) s_kept_run[id] = r;
+      id += keep ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  // D
+  const int n_ret = min(n_kept, KC_WORLDMAP_MAX_CLUSTERS);
+  const int lane = t & 63;
+  for (int id = t >> 6; id < n_ret; id += kWmMvWaves) {
+    const int r = s_kept_run[id];
+    const int s = a.run_start[r], e = a.run_start[r + 1];
+    long long sx = 0, sy = 0, lo_x = LLONG_MAX, hi_x = LLONG_MIN, lo_y = LLONG_MAX, hi_y = LLONG_MIN;
+    for (int i = s + lane; i < e; i += 64) {
+      const int k = a.comp[i];
+      const long long x = a.ex[k], y = a.ey[k];
+      sx += x;
+      sy += y;
+      lo_x = min(lo_x, x);
+      hi_x = max(hi_x, x);
+      lo_y = min(lo_y, y);
+      hi_y = max(hi_y, y);
+    }
+    for (int m = 32; m > 0; m >>= 1) {
+      sx += wm_mv_shfl_xor(sx, m);
+      sy += wm_mv_shfl_xor(sy, m);
+      lo_x = min(lo_x, wm_mv_shfl_xor(lo_x, m));
+      hi_x = max(hi_x, wm_mv_shfl_xor(hi_x, m));
+      lo_y = min(lo_y, wm_mv_shfl_xor(lo_y, m));
+      hi_y = max(hi_y, wm_mv_shfl_xor(hi_y, m));
+    }
+    if (lane == 0) {
+      kc_worldmap_cluster c;
+      c.k_first = a.comp[s];
+      c.k_last = a.comp[e - 1];
+      c.n = e - s;
+      c.reserved = 0;
+      c.sx = sx;
+      c.sy = sy;
+      c.min_x = lo_x;
+      c.max_x = hi_x;
+      c.min_y = lo_y;
+      c.max_y = hi_y;
+      a.clusters[id] = c;
+    }
+  }
+  // E
+  {
+    int idx = base;
+    for (int k = k0; k < k1; ++k) a.label[k] = a.flag[k] ? a.run_kept[a.run_of[idx++]] : -1;
+  }
+  if (t == 0) {
+    a.rec->n_dynamic = static_cast<uint32_t>(n_dyn);
+    a.rec->n_runs = static_cast<uint32_t>(n_runs);
+    a.rec->n_kept = static_cast<uint32_t>(n_kept);
+    a.rec->n_returned = static_cast<uint32_t>(n_ret);
+  }
+}
+
 }  // namespace kc
 
 using namespace kc;
@@ -815,6 +1021,13 @@ struct kc_worldmap {
   PinBuf<int32_t> h_zq;
   bool mark_precheck = false;      // the byte load in front of the atomic: measured and off (on: for the timing tool)
   Timing integ_time;               // mark, apply
+  // movers (rules 64 to 70): scratch and the output block, grown on demand and kept
+  DevBuf<long long> d_mv_xy;       // EX, behind it EY
+  DevBuf<uint8_t> d_mv_flag;
+  DevBuf<int> d_mv_idx;            // comp, run_of, run_kept, run_start (B + 1)
+  DevBuf<uint8_t> d_mv_out;        // the record's line, the clusters, the labels: one read-back
+  PinBuf<uint8_t> h_mv_out;
+  Timing mv_time;                  // flag, cluster
 
   // rule 46: one product and one sum in double, never accumulated
   double ox() const { return ox0 + static_cast<double>(OI) * static_cast<double>(res); }
@@ -1413,6 +1626,87 @@ int wm_integrate(kc_worldmap *c, const kc_worldmap_pose *p, const double *angles
   return KC_OK;
 }
 
+// rule 70's refusals in its order: rule 52's without flags, then m2, gap, join_q, min_beams
+int wm_movers_check(float res, size_t n_beams, float range_max, const int32_t *zq, uint32_t m2, uint32_t gap, uint64_t join_q,
+                    uint32_t min_beams, long long *zmax_out) {
+  KC_TRY(wm_integrate_check(res, n_beams, range_max, 0u, zq, nullptr, zmax_out));
+  if (m2 == 0) KC_FAIL(KC_ERR_INVALID, "m2 must be at least 1");
+  if (gap > 64u) KC_FAIL(KC_ERR_RANGE, "gap %u is above 64 beams", gap);
+  if (join_q > (1ull << 40)) KC_FAIL(KC_ERR_RANGE, "join_q %llu is above 2^40", static_cast<unsigned long long>(join_q));
+  if (min_beams == 0) KC_FAIL(KC_ERR_INVALID, "min_beams must be at least 1");
+  if (min_beams > 65536u) KC_FAIL(KC_ERR_RANGE, "min_beams %u is above 65536", min_beams);
+  return KC_OK;
+}
+
+// Rules 64 to 69.  Check order: rule 70, the angles, the pose, the plane's state; a refused call queues nothing.
+int wm_movers(kc_worldmap *c, const kc_worldmap_pose *p, const double *angles, size_t n, const int32_t *zq, float range_max,
+              uint32_t m2, uint32_t gap, uint64_t join_q, uint32_t min_beams, int32_t *label_out, kc_worldmap_cluster *clusters_out,
+              size_t cap, kc_worldmap_movers_record *out) {
+  long long zmax = 0;
+  KC_TRY(wm_movers_check(c->res, n, range_max, zq, m2, gap, join_q, min_beams, &zmax));
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(angles[k])) KC_FAIL(KC_ERR_INVALID, "beam angle %zu is not finite", k);
+  KC_TRY(wm_check_pose(p));
+  if (c->dist_reach == 0) KC_FAIL(KC_ERR_STATE, "finding movers needs the map's distance plane: kc_worldmap_set_distance");
+  if (m2 > static_cast<uint32_t>(c->dist_reach * c->dist_reach))
+    KC_FAIL(KC_ERR_STATE, "m2 = %u is above the plane's reach^2 = %d", m2, c->dist_reach * c->dist_reach);
+  KC_HIP(hipSetDevice(c->device));
+  const size_t labels_at = kWmMvRecBytes + KC_WORLDMAP_MAX_CLUSTERS * sizeof(kc_worldmap_cluster);
+  const size_t out_bytes = labels_at + n * sizeof(int32_t);
+  KC_TRY(c->d_mv_xy.reserve(2 * n));
+  KC_TRY(c->d_mv_flag.reserve(n));
+  KC_TRY(c->d_mv_idx.reserve(4 * n + 1));
+  KC_TRY(c->d_mv_out.reserve(out_bytes));
+  KC_TRY(c->h_mv_out.reserve(out_bytes));
+  KC_TRY(c->d_zq.reserve(n));
+  KC_TRY(c->h_zq.reserve(n));
+  KC_TRY(wm_dist_refresh(c));  // rule 43
+  KC_TRY(c->scan_table.ensure(angles, n, c->stream));
+  std::memcpy(c->h_zq.p, zq, n * sizeof(int32_t));
+  KC_HIP(hipMemcpyAsync(c->d_zq.p, c->h_zq.p, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  WmMoversArgs a{};
+  a.cls = c->d_cls.p;
+  a.dist2 = c->d_dist2.p;
+  a.table = reinterpret_cast<const int2 *>(c->scan_table.d.p);
+  a.zq = c->d_zq.p;
+  a.pose = *p;
+  a.zmax = zmax;
+  a.join_q = join_q;
+  a.m2 = m2;
+  a.W = c->W;
+  a.H = c->H;
+  a.B = static_cast<int>(n);
+  a.gap = static_cast<int>(gap);
+  a.min_beams = static_cast<int>(min_beams);
+  a.ex = c->d_mv_xy.p;
+  a.ey = c->d_mv_xy.p + n;
+  a.flag = c->d_mv_flag.p;
+  a.comp = c->d_mv_idx.p;
+  a.run_of = c->d_mv_idx.p + n;
+  a.run_kept = c->d_mv_idx.p + 2 * n;
+  a.run_start = c->d_mv_idx.p + 3 * n;
+  a.rec = reinterpret_cast<kc_worldmap_movers_record *>(c->d_mv_out.p);
+  a.clusters = reinterpret_cast<kc_worldmap_cluster *>(c->d_mv_out.p + kWmMvRecBytes);
+  a.label = reinterpret_cast<int32_t *>(c->d_mv_out.p + labels_at);
+  c->mv_time.begin_cycle();
+  KC_TRY(c->mv_time.start("flag", c->stream));
+  hipLaunchKernelGGL(worldmap_movers_flag_kernel, dim3(static_cast<unsigned>((n + kWmBlock - 1) / kWmBlock)), dim3(kWmBlock), 0,
+                     c->stream, a);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->mv_time.stop(c->stream));
+  KC_TRY(c->mv_time.start("cluster", c->stream));
+  hipLaunchKernelGGL(worldmap_movers_cluster_kernel, dim3(1), dim3(kWmMvBlock), 0, c->stream, a);
+  KC_HIP(hipGetLastError());
+  KC_TRY(c->mv_time.stop(c->stream));
+  KC_HIP(hipMemcpyAsync(c->h_mv_out.p, c->d_mv_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  KC_HIP(hipStreamSynchronize(c->stream));
+  std::memcpy(out, c->h_mv_out.p, sizeof(*out));
+  const size_t n_copy = std::min<size_t>(out->n_returned, cap);
+  if (n_copy > 0) std::memcpy(clusters_out, c->h_mv_out.p + kWmMvRecBytes, n_copy * sizeof(kc_worldmap_cluster));
+  if (label_out) std::memcpy(label_out, c->h_mv_out.p + labels_at, n * sizeof(int32_t));
+  return KC_OK;
+}
+
 void wm_clear_match_result(const kc_worldmap_pose *g, kc_worldmap_match_result *out) {
   *out = kc_worldmap_match_result{};
   if (g) out->pose = *g;
@@ -1885,6 +2179,39 @@ int kc_worldmap_integrate_times(kc_worldmap *c, float ms_out[2]) {
   KC_HIP(hipSetDevice(c->device));
   size_t n = 0;
   return c->integ_time.get(nullptr, ms_out, 2, &n);
+}
+
+int kc_worldmap_movers_check(float resolution, size_t n_beams, float range_max, const int32_t *zq_or_null, uint32_t m2, uint32_t gap,
+                             uint64_t join_q, uint32_t min_beams, int64_t *zmax_out) {
+  if (zmax_out) *zmax_out = 0;
+  long long zmax = 0;
+  KC_TRY(wm_movers_check(resolution, n_beams, range_max, zq_or_null, m2, gap, join_q, min_beams, &zmax));
+  if (zmax_out) *zmax_out = zmax;
+  return KC_OK;
+}
+
+int kc_worldmap_movers(kc_worldmap *c, const kc_worldmap_pose *pose, const double *angles, size_t n_beams, const int32_t *zq,
+                       float range_max, uint32_t m2, uint32_t gap, uint64_t join_q, uint32_t min_beams, int32_t *label_out_or_null,
+                       kc_worldmap_cluster *clusters_out, size_t cap, kc_worldmap_movers_record *record_out) {
+  if (record_out) *record_out = kc_worldmap_movers_record{};
+  if (!c || !pose || !angles || !zq || !record_out || (!clusters_out && cap > 0)) KC_FAIL(KC_ERR_INVALID, "null argument");
+  return wm_movers(c, pose, angles, n_beams, zq, range_max, m2, gap, join_q, min_beams, label_out_or_null, clusters_out, cap,
+                   record_out);
+}
+
+int kc_worldmap_movers_set_timing(kc_worldmap *c, int enable) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  c->mv_time.enabled = enable != 0;
+  c->mv_time.begin_cycle();
+  return KC_OK;
+}
+
+int kc_worldmap_movers_times(kc_worldmap *c, float ms_out[2]) {
+  if (!c || !ms_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->mv_time.enabled || c->mv_time.used != 2) KC_FAIL(KC_ERR_STATE, "no detection has been timed on this map");
+  KC_HIP(hipSetDevice(c->device));
+  size_t n = 0;
+  return c->mv_time.get(nullptr, ms_out, 2, &n);
 }
 
 int kc_worldmap_grid_device(kc_worldmap *c, void **dev_cls_int8) {

@@ -14,6 +14,8 @@ import numpy as np
 
 import kompass_cpp
 
+from .movers import MoverDetection
+
 
 class WorldMapMatch:
     """What `WorldMap.match` found (DESIGN.md 4.11 rules 9 to 15): the winner (k, u, v) of the window in yaw steps and
@@ -141,16 +143,9 @@ class WorldMap:
             return self._map.update_at(mapper, m.pose)
         return self._map.update(mapper, float(robot_state.x), float(robot_state.y), float(robot_state.yaw))
 
-    def integrate_scan(self, robot_state, scan, angles=None, range_max: Optional[float] = None, range_min: float = 0.0,
-                       clear_no_return: bool = False, follow: Optional[Tuple[int, int]] = None) -> int:
-        """Fuse one raw laser scan by an inverse ray cast on the device (DESIGN.md 4.11 rules 52 to 58), no `LocalMapper`
-        in between; robot_state (x, y, yaw): the scan frame's pose in the world (a robot state, an `MCL` estimate or a
-        tuple).  scan: a `LaserScanData` (its angles, ranges, range_min and range_max; the arguments, where given, take
-        their place), or an array of ranges in metres together with `angles`.  A beam's range ends in an occupied cell and
-        crosses empty ones, a hit beating a miss where beams disagree; NaN, a negative range or one below range_min says
-        nothing; inf or a range >= range_max is a beam without a return, which clears what it crosses up to range_max
-        with clear_no_return and says nothing without.  A sensor's yaw offset is folded into `angles`; a translated mount
-        is out of scope.  follow=(margin, stride): `recentre` first, as in `update`.  -> cells whose class changed."""
+    @staticmethod
+    def _scan_args(scan, angles, range_max, range_min):
+        """A `LaserScanData` or ranges plus angles -> (angles float64 [B], ranges float64 [B], range_max, range_min)"""
         ranges = getattr(scan, "ranges", scan)
         if hasattr(scan, "ranges"):
             angles = scan.angles if angles is None else angles
@@ -160,9 +155,41 @@ class WorldMap:
             raise TypeError("an array of ranges needs angles and range_max")
         a = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
         r = np.ascontiguousarray(ranges, dtype=np.float64).reshape(-1)
+        return a, r, float(range_max), float(range_min)
+
+    def detect_movers(self, robot_state, scan, angles=None, range_max: Optional[float] = None, range_min: float = 0.0,
+                      **config) -> "MoverDetection":
+        """Moving obstacles in one raw laser scan (DESIGN.md 4.11 rules 64 to 69): the returns that end in cells the map has
+        seen empty, more than sqrt(m2) cells from anything occupied, grouped into runs of neighbouring beams.  Arguments as
+        `integrate_scan`'s; config: m2, gap, join_q (2^-16 cells^2), min_beams, whose defaults (4, 2, 9 << 16, 3) are
+        judgement, not measurement.  The map is not modified; its distance field must be enabled.  Two launches on the
+        device.  -> MoverDetection: `clusters` (x, y, radius in world metres), `labels` (int32 a beam) and `record`.
+        Hand it to a `MoverTracker`, and `MoverTracker.skip_mask(detection)` to `integrate_scan(skip=...)` so that a
+        mover's returns never reach the map."""
+        a, r, range_max, range_min = self._scan_args(scan, angles, range_max, range_min)
+        cfg = kompass_cpp.mapping.MoverDetectConfig(**{k: int(v) for k, v in config.items()})
+        return MoverDetection(self._map.detect_movers(*self._pose(robot_state), a, r, range_max, range_min, cfg),
+                              float(self._map.resolution))
+
+    def integrate_scan(self, robot_state, scan, angles=None, range_max: Optional[float] = None, range_min: float = 0.0,
+                       clear_no_return: bool = False, follow: Optional[Tuple[int, int]] = None, skip=None) -> int:
+        """Fuse one raw laser scan by an inverse ray cast on the device (DESIGN.md 4.11 rules 52 to 58), no `LocalMapper`
+        in between; robot_state (x, y, yaw): the scan frame's pose in the world (a robot state, an `MCL` estimate or a
+        tuple).  scan: a `LaserScanData` (its angles, ranges, range_min and range_max; the arguments, where given, take
+        their place), or an array of ranges in metres together with `angles`.  A beam's range ends in an occupied cell and
+        crosses empty ones, a hit beating a miss where beams disagree; NaN, a negative range or one below range_min says
+        nothing; inf or a range >= range_max is a beam without a return, which clears what it crosses up to range_max
+        with clear_no_return and says nothing without.  A sensor's yaw offset is folded into `angles`; a translated mount
+        is out of scope.  follow=(margin, stride): `recentre` first, as in `update`.  skip: a mask a beam, true where the
+        beam is to say nothing whatever its range (`MoverTracker.skip_mask`); the free space along a skipped beam is not
+        cleared either.  -> cells whose class changed."""
+        a, r, range_max, range_min = self._scan_args(scan, angles, range_max, range_min)
         if follow is not None:
             self.recentre(robot_state, int(follow[0]), int(follow[1]))
-        return self._map.integrate_scan(*self._pose(robot_state), a, r, float(range_max), float(range_min), bool(clear_no_return))
+        if skip is None:
+            return self._map.integrate_scan(*self._pose(robot_state), a, r, range_max, range_min, bool(clear_no_return))
+        mask = np.ascontiguousarray(np.asarray(skip).astype(bool), dtype=np.uint8).reshape(-1)
+        return self._map.integrate_scan(*self._pose(robot_state), a, r, range_max, range_min, bool(clear_no_return), mask)
 
     def clear(self) -> None:
         self._map.clear()

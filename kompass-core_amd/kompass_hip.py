@@ -108,6 +108,27 @@ class WorldMapResult(C.Structure):
         return int(self.changed), (int(self.i_min), int(self.j_min), int(self.i_max), int(self.j_max))
 
 
+class WorldMapCluster(C.Structure):
+    """kc_worldmap_cluster: rule 68's record of a kept cluster, 64 bytes."""
+    _fields_ = [("k_first", C.c_int32), ("k_last", C.c_int32), ("n", C.c_int32), ("reserved", C.c_int32),
+                ("sx", C.c_int64), ("sy", C.c_int64), ("min_x", C.c_int64), ("max_x", C.c_int64), ("min_y", C.c_int64),
+                ("max_y", C.c_int64)]
+
+    def as_tuple(self):
+        """(k_first, k_last, n, sx, sy, min_x, max_x, min_y, max_y)"""
+        return (int(self.k_first), int(self.k_last), int(self.n), int(self.sx), int(self.sy), int(self.min_x), int(self.max_x),
+                int(self.min_y), int(self.max_y))
+
+
+class WorldMapMoversRecord(C.Structure):
+    """kc_worldmap_movers_record: rule 69's counts."""
+    _fields_ = [("n_dynamic", C.c_uint32), ("n_runs", C.c_uint32), ("n_kept", C.c_uint32), ("n_returned", C.c_uint32)]
+
+    def as_tuple(self):
+        """(n_dynamic, n_runs, n_kept, n_returned)"""
+        return int(self.n_dynamic), int(self.n_runs), int(self.n_kept), int(self.n_returned)
+
+
 class WorldMapRotation(C.Structure):
     """kc_worldmap_rotation: one rotation of a match's window, 16 fraction bits."""
     _fields_ = [("cq", C.c_int32), ("sq", C.c_int32)]
@@ -418,6 +439,13 @@ SIGNATURES = {
     "kc_worldmap_integrate_set_precheck": (C.c_int, [_vp, C.c_int]),
     "kc_worldmap_integrate_set_timing": (C.c_int, [_vp, C.c_int]),
     "kc_worldmap_integrate_times": (C.c_int, [_vp, _fp]),
+    "kc_worldmap_movers_check": (C.c_int, [C.c_float, _sz, C.c_float, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                           C.POINTER(C.c_int64)]),
+    "kc_worldmap_movers": (C.c_int, [_vp, C.POINTER(WorldMapPose), _dp, _sz, _ip, C.c_float, C.c_uint32, C.c_uint32, C.c_uint64,
+                                     C.c_uint32, C.c_void_p, C.POINTER(WorldMapCluster), _sz,
+                                     C.POINTER(WorldMapMoversRecord)]),
+    "kc_worldmap_movers_set_timing": (C.c_int, [_vp, C.c_int]),
+    "kc_worldmap_movers_times": (C.c_int, [_vp, _fp]),
     "kc_mcl_last_fit": (C.c_int, [_vp, C.POINTER(MclFit)]),
     "kc_mcl_recovery_update": (C.c_int, [C.c_uint64, _sz, _sz, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(MclRecovery),
                                          C.POINTER(C.c_int64), C.POINTER(_sz)]),
@@ -1652,6 +1680,34 @@ def worldmap_quantise_ranges(ranges, resolution, range_max, range_min=0.0):
     return out
 
 
+WORLDMAP_MAX_CLUSTERS = 256  # KC_WORLDMAP_MAX_CLUSTERS
+
+
+def _movers_params(m2, gap, join_q, min_beams):
+    """The four as Python ints that fit the C types: a negative one is a ValueError, one too wide an IndexError (ctypes
+    would wrap both silently)."""
+    out = []
+    for name, v, bits in (("m2", m2, 32), ("gap", gap, 32), ("join_q", join_q, 64), ("min_beams", min_beams, 32)):
+        v = int(v)
+        if v < 0:
+            raise ValueError(f"{name} is negative")
+        if v >> bits:
+            raise IndexError(f"{name} does not fit {bits} bits")
+        out.append(v)
+    return out
+
+
+def worldmap_movers_check(resolution, n_beams, range_max, zq=None, m2=4, gap=2, join_q=9 << 16, min_beams=3):
+    """Rule 70's refusals (host only) in their order: rule 52's without flags, then m2, gap, join_q, min_beams -> ZMAX;
+    raises ValueError / IndexError."""
+    z = None if zq is None else _zq(zq)
+    m2, gap, join_q, min_beams = _movers_params(m2, gap, join_q, min_beams)
+    zmax = C.c_int64()
+    _check(lib().kc_worldmap_movers_check(float(np.float32(resolution)), int(n_beams), float(np.float32(range_max)),
+                                          None if z is None else z.ctypes.data, m2, gap, join_q, min_beams, C.byref(zmax)))
+    return zmax.value
+
+
 def worldmap_match_check_window(n_yaw, yaw_step, reach):
     """Rule 10's ranges of a match's window (host only); raises ValueError."""
     _check(lib().kc_worldmap_match_check_window(int(n_yaw), float(yaw_step), int(reach)))
@@ -1898,6 +1954,35 @@ class WorldMapContext(_Owner, _StreamOrdered):
         """(mark, apply) launches of the last integrate in milliseconds, by HIP events."""
         ms = (C.c_float * 2)()
         _check(lib().kc_worldmap_integrate_times(self.h, ms))
+        return tuple(float(v) for v in ms)
+
+    def movers(self, pose, angles, zq, range_max, m2=4, gap=2, join_q=9 << 16, min_beams=3, return_labels=True):
+        """Rules 64 to 69: the scan's returns that end in free space the map has seen, at least sqrt(m2) cells from
+        anything occupied, grouped into runs of neighbouring beams.  pose, angles, zq as `integrate`; join_q in 2^-16
+        cells^2.  The distance plane must be on (KompassHipError otherwise, and for m2 > reach^2).  The defaults are
+        the prototype's values: judgement, not measurement.
+        -> (labels int32 [B] or None, (n_dynamic, n_runs, n_kept, n_returned), [cluster tuples as
+        WorldMapCluster.as_tuple, n_returned of them])."""
+        p, a, z = self._pose(pose), _f64(angles).reshape(-1), _zq(zq)
+        if len(z) != len(a):
+            raise ValueError("one quantised range a beam")
+        m2, gap, join_q, min_beams = _movers_params(m2, gap, join_q, min_beams)
+        labels = np.zeros(max(len(a), 1), np.int32) if return_labels else None
+        clusters = (WorldMapCluster * WORLDMAP_MAX_CLUSTERS)()
+        rec = WorldMapMoversRecord()
+        _check(lib().kc_worldmap_movers(self.h, C.byref(p), _pd(a), len(a), z.ctypes.data_as(_ip), float(np.float32(range_max)),
+                                        m2, gap, join_q, min_beams, labels.ctypes.data if return_labels else None, clusters,
+                                        WORLDMAP_MAX_CLUSTERS, C.byref(rec)))
+        return (labels[:len(a)] if return_labels else None, rec.as_tuple(),
+                [clusters[i].as_tuple() for i in range(int(rec.n_returned))])
+
+    def movers_set_timing(self, enable=True):
+        _check(lib().kc_worldmap_movers_set_timing(self.h, int(bool(enable))))
+
+    def movers_times(self):
+        """(flag, cluster) launches of the last `movers` in milliseconds, by HIP events."""
+        ms = (C.c_float * 2)()
+        _check(lib().kc_worldmap_movers_times(self.h, ms))
         return tuple(float(v) for v in ms)
 
     def grid_device_ptr(self) -> int:

@@ -1,6 +1,11 @@
 #!/bin/bash
 # tools/ab_libs.sh ROUNDS "python tools/x.py args" NAME [NAME...] -- the same command on builds of the library
 # under kompass-core_amd/lib_ab/NAME/ (tools/build_variant.sh), alternating, ROUNDS times: a same-box A/B.
+# A change that grows a context struct alternates every leg of that context, the new one beside them on the builds that
+# have it.  For kc_worldmap, grown by the detection of movers (worldmap_time.py --movers needs a build with the entry):
+#   for leg in "" --match --points --scan --field --shift --integrate; do
+#     tools/ab_libs.sh 3 "python tools/worldmap_time.py $leg" old_parent new; done
+#   tools/ab_libs.sh 3 "python tools/worldmap_time.py --movers --integrate" new
 rounds=$1; cmd=$2; shift 2
 root=$(cd "$(dirname "$0")/.." && pwd)
 for r in $(seq 1 "$rounds"); do

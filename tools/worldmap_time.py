@@ -93,7 +93,15 @@ count with
   (b) the route that exists without it, for the same scan: the mapper's scan to its 400 x 400 grid on the device followed
       by kc_worldmap_update_from_mapper, together and each on its own.
 At 360 beams the marks, the planes and the record are compared with the statement (tests/worldmap_integrate_ref.py) once.
-  python tools/worldmap_time.py --integrate [--reps 30] [--warmup 3]"""
+  python tools/worldmap_time.py --integrate [--reps 30] [--warmup 3]
+
+--movers times the detection of movers in a scan (rules 64 to 69): the same world, seen and free everywhere with the distance
+plane on at reach 8 and refreshed beforehand, the same room scan with every seventh beam of its last two thirds without a
+return, so that every return is a dynamic beam and the runs are cut.  One JSON line a beam count (360, 1440, 4096) with
+kc_worldmap_movers by the host's clock (two launches and the one read-back), its flag and cluster launches by HIP events,
+and kc_worldmap_integrate for the same scan on a map of its own beside it.  At 360 beams labels, record and clusters are
+compared with the statement (tests/worldmap_movers_ref.py) once.  With --integrate as well, that leg follows in the same run.
+  python tools/worldmap_time.py --movers [--integrate] [--reps 30] [--warmup 3]"""
 import argparse
 import ctypes as C
 import json
@@ -640,6 +648,49 @@ def integrate_leg(args):
             print(json.dumps(line), flush=True)
 
 
+def movers_leg(args):
+    import worldmap_dist_ref as dref
+    import worldmap_movers_ref as wmr
+
+    r = float(np.float32(RES))
+    centre = (ORIGIN[0] + (W // 2) * r + 0.013, ORIGIN[1] + (H // 2) * r - 0.021)
+    pose = centre + (0.3,)
+    range_max, reach = 10.0, 8
+    prior = np.zeros((W, H), np.int8, order="F")              # seen and free everywhere: every return is a dynamic beam
+    for n in (360, 1440, 4096):
+        ang, rng = syn.dense_scan(n, 1.2)                     # a room: ranges 3.6 .. 8.4 m
+        ang, rng = np.asarray(ang, dtype=np.float64), np.asarray(rng, dtype=np.float64)
+        rng[n // 3::7] = np.inf                               # beams without a return cut the runs
+        zq = kh.worldmap_quantise_ranges(rng, RES, range_max)
+        with kh.WorldMapContext(W, H, RES, ORIGIN) as wm, kh.WorldMapContext(W, H, RES, ORIGIN) as wm_int:
+            wm.set_prior(prior)
+            wm.set_distance(reach)
+            wm.distance_refresh()
+            line = {"world": [W, H], "beams": n, "range_max": range_max, "reach": reach, "reps": args.reps, "warmup": args.warmup}
+            labels, rec, clusters = wm.movers(pose, ang, zq, range_max)
+            line["record"] = list(rec)
+            if n == 360:                                      # the device against the statement, once
+                q = wm.quantise_pose(*pose)
+                plane = np.full((W, H), dref.FAR, np.uint16)  # nothing occupied anywhere
+                w_labels, w_rec, w_clusters = wmr.detect(prior, plane, reach, RES, (q.cq, q.sq, q.tx, q.ty), ang, zq, range_max)
+                assert rec == tuple(w_rec) and clusters == [tuple(c) for c in w_clusters], "record or clusters differ"
+                assert labels.tobytes() == w_labels.tobytes(), "labels differ"
+            line["movers_call_ms"] = timed(lambda: wm.movers(pose, ang, zq, range_max), args.reps, args.warmup)
+            wm.movers_set_timing(True)
+            parts = []
+            for k in range(args.warmup + args.reps):
+                wm.movers(pose, ang, zq, range_max)
+                if k >= args.warmup:
+                    parts.append(wm.movers_times())
+            wm.movers_set_timing(False)
+            line["launch_flag_ms"] = spread([p[0] for p in parts])
+            line["launch_cluster_ms"] = spread([p[1] for p in parts])
+            line["integrate_call_ms"] = timed(lambda: wm_int.integrate(pose, ang, zq, range_max, kh.INTEGRATE_CLEAR_NO_RETURN),
+                                              args.reps, args.warmup)
+            line["movers_over_integrate"] = round(line["movers_call_ms"][0] / line["integrate_call_ms"][0], 3)
+            print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -653,9 +704,13 @@ def main():
     ap.add_argument("--field", action="store_true", help="time the distance plane and the likelihood-field model instead")
     ap.add_argument("--shift", action="store_true", help="time the rolling window's shift and the route it replaces instead")
     ap.add_argument("--integrate", action="store_true", help="time the scan integration and today's route for the same scan instead")
+    ap.add_argument("--movers", action="store_true", help="time the detection of movers in a scan; with --integrate: both, in one run")
     args = ap.parse_args()
     if kh.device_count() < 1:
         raise SystemExit("needs a HIP device")
+    if args.movers:
+        movers_leg(args)
+        return integrate_leg(args) if args.integrate else None
     if args.integrate:
         return integrate_leg(args)
     if args.match:
