@@ -1460,7 +1460,8 @@ int kc_mcl_info(kc_mcl *ctx, size_t *n_particles_out, size_t *n_beams_out, int32
 int kc_mcl_set_model(kc_mcl *ctx, const uint16_t *pen, size_t n_pen, int err_shift, const uint32_t *wtab, size_t n_wtab, int w_shift);
 /* rule 41.  init_pose: KC_ERR_RANGE for |TX0|, |TY0| > 2^36 or h0 > 65535, KC_ERR_INVALID for
  * a negative scale.  init_global: two launches around a read-back of the row counts, ordered
- * behind the map's stream; *n_free_out (may be NULL) the free cells; KC_ERR_STATE with none. */
+ * behind the map's stream; *n_free_out (may be NULL) the free cells; KC_ERR_STATE with none.
+ * A refused init of either kind leaves the particles, weights and fit of an earlier one. */
 int kc_mcl_init_pose(kc_mcl *ctx, int64_t tx0, int64_t ty0, uint32_t h0, int32_t s_xy, int32_t s_h);
 int kc_mcl_init_global(kc_mcl *ctx, size_t *n_free_out);
 /* One step (rules 31 to 37): two launches (predict + walk + penalty; weight + record) behind

@@ -805,7 +805,6 @@ int kc_mcl_init_global(kc_mcl *c, size_t *n_free_out) {
   WorldMapView v{};
   KC_TRY(worldmap_view(c->map, &v));
   KC_HIP(hipSetDevice(c->device));
-  c->inited = c->have_fit = false;
   const size_t H = static_cast<size_t>(v.H);
   KC_TRY(c->d_rows.reserve(H));
   KC_TRY(c->d_before.reserve(H + 1));
@@ -819,6 +818,7 @@ int kc_mcl_init_global(kc_mcl *c, size_t *n_free_out) {
   for (size_t j = 0; j < H; ++j) before[j + 1] = before[j] + rows[j];
   if (n_free_out) *n_free_out = static_cast<size_t>(before[H]);
   if (before[H] == 0) KC_FAIL(KC_ERR_STATE, "the map has no KC_EMPTY cell to seed a particle in");
+  c->inited = c->have_fit = false;  // only now: the refusal above has touched nothing but the row counts' scratch
   KC_HIP(hipMemcpyAsync(c->d_before.p, before.data(), (H + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(mcl_init_global_kernel, dim3(mcl_blocks(c->N * 64)), dim3(kMclBlock), 0, c->stream, v.cls, v.W, v.H,
                      c->d_before.p, c->state(0), c->d_acc.p, c->d_cost.p, c->d_min_prev.p, mcl_key(c, 0), static_cast<int>(c->N));

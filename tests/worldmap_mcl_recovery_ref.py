@@ -107,12 +107,13 @@ class FitRef(fref.MclFieldRef):
         self.fit = None
 
     def init_pose(self, *a):
+        super().init_pose(*a)                                             # a refused init leaves the fit with the particles
         self.fit = None
-        super().init_pose(*a)
 
     def init_global(self):
+        n = super().init_global()
         self.fit = None
-        return super().init_global()
+        return n
 
     def step_costs(self, zq, flags):
         """cost_p of rule 34 or rules 44 and 45 for the states as the step left them."""
@@ -174,12 +175,13 @@ class FitVec(fref.MclFieldVec):
     fit = None
 
     def init_pose(self, *a):
-        self.fit = None
         super().init_pose(*a)
+        self.fit = None
 
     def init_global(self):
+        n = super().init_global()
         self.fit = None
-        return super().init_global()
+        return n
 
     def step(self, d_f, d_l, d_h, s_f, s_l, s_h, zq, flags=0):
         """MclFieldVec.step, the cost kept."""

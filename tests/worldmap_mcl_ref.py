@@ -265,6 +265,7 @@ class MclRef:
     def set_model(self, pen, err_shift, wtab, w_shift):
         check(self.resolution, self.n, len(self.table), self.range_max, pen, err_shift, wtab, w_shift)
         self.model = ([int(v) for v in pen], int(err_shift), [int(v) for v in wtab], int(w_shift))
+        self.w = None                                                     # weights of another table: a resample needs a new step
 
     def _start(self):
         self.acc = [0] * self.n
