@@ -879,6 +879,15 @@ int kc_planner_solve(kc_planner *ctx, const int start_cell[2], const int goal_ce
 /* the last solve's cost field and validity map (1 valid, 0 invalid), laid out as
  * the grid (tests); either pointer may be NULL */
 int kc_planner_get_field(kc_planner *ctx, uint32_t *field_out, uint8_t *valid_out, size_t cap);
+/* The kept cost field where it lies on the device (width * height uint32, cell (I, J) at
+ * I + J * width, 0xFFFFFFFF: no walk reaches the goal), its shape and the planner's stream
+ * (a hipStream_t), for a reader that orders itself behind that stream: kc_mppi_step with a field
+ * attached.  Host only, queues nothing.  The field's two buffers alternate between solves, so
+ * the pointer holds until the next solve-type call and a reader asks again after each.
+ * KC_ERR_STATE unless the last solve-type call was kc_planner_solve or kc_planner_replan (plain
+ * or with the clearance cost): before any solve, after kc_planner_solve_oriented,
+ * kc_planner_solve_car and kc_planner_explore. */
+int kc_planner_field_device(kc_planner *ctx, const uint32_t **field_out, int *width_out, int *height_out, void **stream_out);
 /* the path of the last solve by steepest descent: from the start cell, the
  * neighbour with the smallest field value among those a step may go to (valid,
  * and for a diagonal between two valid orthogonal neighbours), the first of
@@ -1866,7 +1875,28 @@ int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
  * KC_ERR_RANGE above 64 movers; KC_ERR_INVALID for a NULL array; KC_ERR_RANGE for pen_hit_mv
  * above 2^20; then mover by mover in index order KC_ERR_RANGE for a position beyond 2^36, then
  * a velocity beyond 2^22, KC_ERR_INVALID for hq > sq, KC_ERR_RANGE for sq above 2^40, then g
- * above 2^32, then the ramp's top above 2^20. */
+ * above 2^32, then the ramp's top above 2^20.
+ * The grid planner's cost field, read in place (tests/mppi_field_ref.py states rules 19 to 24;
+ * with no field attached every result is rules 1 to 18's, bit for bit):
+ * Rule 19, field: fld[I + J W], uint32, with the map's W x H and the map's cell frame;
+ * 0xFFFFFFFF: no walk reaches the goal.  fv(I, J) is the plane's value inside the map and
+ * 0xFFFFFFFF outside; fc = min(fv, fcap), 1 <= fcap <= 2^24.
+ * Rule 20, mode: with a field attached rules 6 and 7 are not evaluated; no path window is
+ * needed (kc_mppi_set_path need not have been called, M plays no part).  At every state a live
+ * sample reaches it adds (fc w_run) >> 8, w_run <= 2^12, behind rule 5's test, rule 16 where
+ * movers are set, and rule 5's penalty.
+ * Rule 21, terminal term: w_term fl, w_term <= 64; fl is the fc of the last state rule 20 saw,
+ * for a sample that hit at step 0 the fc of the step's own pose cell.  Rule 8 sums and caps.
+ * Rule 22, read-back: behind the record, in the same copy, f0 (the uncapped fv of the pose's
+ * cell) and f_nom (the fl of sample 0): kc_mppi_last_field.  kc_mppi_record keeps its layout.
+ * Rule 23, refusals: kc_mppi_check_field (host only), in this order: KC_ERR_INVALID for fcap ==
+ * 0; KC_ERR_RANGE for fcap above 2^24, then w_run above 2^12, then w_term above 64.  A step with
+ * a field attached answers KC_ERR_STATE, before anything is queued, when the planner holds no
+ * goal-rooted disc-mode field (its last solve-type call was not kc_planner_solve or
+ * kc_planner_replan, plain or with the clearance cost: none yet, or the oriented, car or explore
+ * call), then when the field's shape is not the map's.
+ * Rule 24, frame: the ABI works in cells; the caller sees to it that the field was solved on
+ * this map at its present window offset. */
 typedef struct kc_mppi kc_mppi;
 #define KC_MPPI_MAX_SAMPLES 65536
 #define KC_MPPI_MAX_HORIZON 64
@@ -1907,20 +1937,39 @@ int kc_mppi_check_movers(const int64_t *ox, const int64_t *oy, const int32_t *vx
  * leaves the list as it was. */
 int kc_mppi_set_movers(kc_mppi *ctx, const int64_t *ox, const int64_t *oy, const int32_t *vx, const int32_t *vy, const uint64_t *hq,
                        const uint64_t *sq, const uint64_t *g, size_t n, uint32_t pen_hit_mv);
+/* rule 23's refusals of the field term's three scalars; host only, needs no device */
+int kc_mppi_check_field(uint32_t fcap, uint32_t w_run, uint32_t w_term);
+/* Attaches `planner`'s kept cost field (rules 19 to 24), checked as kc_mppi_check_field does;
+ * the planner must be on the controller's device and outlive the attachment.  Nothing is read
+ * here: every later step asks the planner for its field (kc_planner_field_device; its two
+ * buffers alternate between solves), orders its stream behind the planner's and reads the field
+ * where it lies.  A step ends in its read-back, so once it has returned no reader is in flight
+ * and the planner may solve or replan.  planner NULL detaches, whatever else is given: the
+ * steps after that are those of a context that never had a field.  A refused call leaves the
+ * attachment as it was. */
+int kc_mppi_set_field(kc_mppi *ctx, kc_planner *planner_or_null, uint32_t fcap, uint32_t w_run, uint32_t w_term);
+/* rule 22's two words of the last step; KC_ERR_STATE (both 0xFFFFFFFF) when that step had no
+ * field attached or there was none */
+int kc_mppi_last_field(kc_mppi *ctx, uint32_t *f0_out, uint32_t *f_nom_out);
 /* One step (rules 3 to 11): two launches (mppi_rollout_kernel, mppi_update_kernel) behind the
  * plane's refresh and an event on the map's stream, and one read-back of U' and the record;
  * returns with both final.  u_in, u_out: T x 3 int32 (F, L, H a step); they may be one array.
  * Checks, in this order: null arguments; KC_ERR_STATE without a model, then without costs,
  * then without a path; KC_ERR_RANGE for |tx|, |ty| > 2^36, then h > 65535, then a control of
  * u_in outside +-2^22, +-2^22, +-32767; KC_ERR_STATE while the map's distance plane is off or
- * c2 > reach^2; then the device.  A refused call queues nothing. */
+ * c2 > reach^2; then the device.  A refused call queues nothing.  With a field attached (rules
+ * 19 to 24) no path is asked for, rule 23's KC_ERR_STATE comes behind the plane's (then
+ * KC_ERR_INVALID for a planner on another device), the roll-out is mppi_rollout_kernel<TEAM,
+ * MOVERS, true> and the read-back carries f0 and f_nom behind the record: still two launches,
+ * one upload and one read-back. */
 int kc_mppi_step(kc_mppi *ctx, int64_t tx, int64_t ty, uint32_t h, const int32_t *u_in, uint32_t step, int32_t *u_out,
                  kc_mppi_record *record);
 /* all S_k of the last step, for tests and plots; cap: the entries s_out holds (KC_ERR_RANGE
  * below K); KC_ERR_STATE before a step */
 int kc_mppi_costs(kc_mppi *ctx, uint32_t *s_out, size_t cap);
 /* Measurement only (no result depends on it): the lanes that share a sample in the roll-out, 1,
- * 4 or 8; the default is what DESIGN.md 4.12 measured as the faster.  KC_ERR_INVALID otherwise. */
+ * 4 or 8; the default is what DESIGN.md 4.12 measured as the faster: 8, and in the field mode 4
+ * while no mover is set.  A call fixes the count for both modes.  KC_ERR_INVALID otherwise. */
 int kc_mppi_set_team(kc_mppi *ctx, int lanes);
 /* HIP-event times in milliseconds of the last step's two launches (rollout, update), recorded
  * only while enabled.  KC_ERR_STATE when no step was timed. */

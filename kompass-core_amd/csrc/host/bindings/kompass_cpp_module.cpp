@@ -795,7 +795,10 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def_readwrite("seed", &MPPI::Config::seed)
         .def_readwrite("mover_margin", &MPPI::Config::mover_margin)
         .def_readwrite("mover_weight", &MPPI::Config::mover_weight)
-        .def_readwrite("mover_hit_penalty", &MPPI::Config::mover_hit_penalty);
+        .def_readwrite("mover_hit_penalty", &MPPI::Config::mover_hit_penalty)
+        .def_readwrite("field_run_weight", &MPPI::Config::field_run_weight)
+        .def_readwrite("field_goal_weight", &MPPI::Config::field_goal_weight)
+        .def_readwrite("field_cap", &MPPI::Config::field_cap);
     using Mover = Control::MovingObstacle;
     py::class_<Mover>(c, "MovingObstacle", "A disc that moves in a straight line: world metres and m/s at the time of the state")
         .def(py::init([](double x, double y, double vx, double vy, double radius) { return Mover{x, y, vx, vy, radius}; }),
@@ -814,6 +817,14 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def("execute", &MPPI::execute, py::arg("world_map"), py::arg("current_position"),
              "One MPPI step over the world map's distance plane: two launches and one read-back")
         .def("reset_sequence", &MPPI::resetSequence)
+        .def("set_cost_field", &MPPI::setCostField, py::arg("planner"),
+             "the planner's kept cost field in the place of the path, from the next execute() on (rules 19 to 24); the caller "
+             "keeps the planner alive while it is attached")
+        .def("clear_cost_field", &MPPI::clearCostField, "back to the path mode")
+        .def_property_readonly("has_cost_field", &MPPI::hasCostField)
+        .def_property_readonly("field_at_robot", &MPPI::fieldAtRobot,
+                               "f0 of the last step in field mode: the field at the robot's cell, 0xFFFFFFFF in an invalid or cut-off cell")
+        .def_property_readonly("field_nominal", &MPPI::fieldNominal, "f_nom of the last step in field mode")
         .def("set_moving_obstacles", &MPPI::setMovingObstacles, py::arg("obstacles"),
              "the moving obstacles of the steps to come, at the time of the next step's state; kept until replaced or cleared")
         .def_property_readonly("moving_obstacles", &MPPI::movingObstacles)
@@ -840,6 +851,7 @@ PYBIND11_MODULE(kompass_cpp, m) {
                d["py"] = i.py;
                d["u"] = i.u;
                d["movers"] = movers_tuple(i.movers);
+               d["field"] = i.field;
                return d;
              }, "the last step's inputs as the device took them")
         .def_static("quantise", [](Control::ControlType type, const Control::ControlLimitsParams &lim, double dt, float res,

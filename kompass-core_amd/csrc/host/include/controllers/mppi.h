@@ -9,6 +9,12 @@
 // Moving obstacles (rules 13 to 18): a list of discs with a velocity in the world, kept until replaced or cleared, and
 // quantised at every step against the map's origin of that step.  The device costs each at the time of each roll-out
 // step; finding them, and keeping them out of the map's cells, is the caller's.
+//
+// The grid planner's cost field (rules 19 to 24): setCostField attaches a GridPlanner, and from then on a step needs no
+// path and builds no window.  The device reads the planner's kept cost-to-go field where it lies: every state a sample
+// reaches pays for how far it still is from the goal, not for how far it is from a polyline.  The planner must have
+// solved (or replanned) on this map at its present window offset; that is the caller's to see to (the Python front end
+// checks it).
 #pragma once
 
 #include <array>
@@ -19,6 +25,7 @@
 
 #include "controllers/follower.h"
 #include "mapping/world_map.h"
+#include "planning/grid_planner.h"
 #include "utils/hip_backend.h"
 
 namespace Kompass {
@@ -47,6 +54,11 @@ struct MPPIConfig {
   double mover_margin = 4.0;                         // cells
   double mover_weight = 200.0;
   uint32_t mover_hit_penalty = 4000;
+  // The planner's cost field (rules 19 to 21; the field counts 10 a straight cell).  Judgement, not tuning: the values
+  // the two scenes of DESIGN.md 4.12 were tried with
+  uint32_t field_run_weight = 32;                    // w_run: a state adds (fc w_run) >> 8
+  uint32_t field_goal_weight = 2;                    // w_term: the last state adds w_term fl
+  uint32_t field_cap = 1u << 20;                     // fcap: an unreachable cell costs as one this far away
 };
 
 // A disc that moves in a straight line: world metres and m/s at the time of the state handed to execute()
@@ -84,6 +96,7 @@ class MPPI : public Follower {
     std::vector<int64_t> px, py;
     std::vector<int32_t> u;  // T x 3
     Movers movers;
+    bool field = false;      // a cost field was attached: px, py are empty
   };
 
   MPPI(ControlType type, const ControlLimitsParams &limits, double time_step, const Config &config = Config());
@@ -92,6 +105,18 @@ class MPPI : public Follower {
   // is enabled at config.reach when it is off or too short for the clearance; the map's cells are not changed.
   Controller::Result execute(const Mapping::WorldMap &map, const Path::State &state);
   void resetSequence();
+  // The planner's kept cost field in the place of the path (rules 19 to 24), from the next execute() on and until
+  // clearCostField().  The planner must outlive the attachment, and its last solve-type call at every execute() must be
+  // solve() or replan() in disc mode on this map at its present offset.  execute() then needs no path: its goal test is
+  // the follower's goal tolerance around the planner's goal.
+  void setCostField(Planning::GridPlanner &planner);
+  void clearCostField();
+  bool hasCostField() const { return field_ != nullptr; }
+  // f0 of the last step in field mode: the field's value at the robot's cell, in the planner's units (10 a straight
+  // cell); 0xFFFFFFFF when the robot stands in an invalid or cut-off cell or outside the map, and before such a step.
+  // The controller does not refuse then: the caller decides
+  uint32_t fieldAtRobot() const { return f0_; }
+  uint32_t fieldNominal() const { return f_nom_; }  // f_nom: the field where the nominal sequence's roll-out ended
   // The moving obstacles of the steps to come, at the time of the state of the next execute(); kept until replaced or
   // cleared (an empty list).  More than 64: the 64 nearest to the robot are kept at every step, logged once.
   void setMovingObstacles(std::vector<MovingObstacle> obstacles);
@@ -135,6 +160,9 @@ class MPPI : public Follower {
   kc_mppi_record rec_ = {};
   std::vector<MovingObstacle> movers_;
   bool movers_on_device_ = false, logged_drop_ = false;
+  Planning::GridPlanner *field_ = nullptr;  // the attached planner, not owned
+  bool field_on_device_ = false;            // ctx_ holds an attachment
+  uint32_t f0_ = 0xFFFFFFFFu, f_nom_ = 0xFFFFFFFFu;
 
   void bind(const Mapping::WorldMap &map);
   void buildWindow(const Mapping::WorldMap &map);

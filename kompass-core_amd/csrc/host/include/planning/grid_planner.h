@@ -201,6 +201,8 @@ class GridPlanner {
   uint32_t footprintR2() const;
   float footprintRadius() const { return radius_; }
   void cells(int start_out[2], int goal_out[2]) const;
+  // the goal of the last setupProblem in the world frame; false before one
+  bool goalWorld(double *x_out, double *y_out) const;
   kc_planner *hipContext() const { return ctx_.get(); }
 
   // (int)((x - origin) / resolution) in float, as localToGrid; false for what no int holds

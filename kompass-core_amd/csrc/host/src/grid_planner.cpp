@@ -520,6 +520,13 @@ bool GridPlanner::replan(const Mapping::WorldMap &map) {
   return replan();
 }
 
+bool GridPlanner::goalWorld(double *x_out, double *y_out) const {
+  if (!have_problem_) return false;
+  *x_out = problem_[3];
+  *y_out = problem_[4];
+  return true;
+}
+
 void GridPlanner::cells(int start_out[2], int goal_out[2]) const {
   start_out[0] = start_[0];
   start_out[1] = start_[1];

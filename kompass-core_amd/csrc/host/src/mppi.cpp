@@ -33,7 +33,15 @@ MPPI::MPPI(ControlType type, const ControlLimitsParams &limits, double time_step
   if (!(cfg_.mover_margin >= 0.0) || !(cfg_.mover_margin <= 1024.0) || !(cfg_.mover_weight >= 0.0) || !(cfg_.mover_weight <= 1048576.0) ||
       cfg_.mover_hit_penalty > (1u << 20))
     throw std::invalid_argument("MPPI moving-obstacle configuration out of range");
+  hip::check(kc_mppi_check_field(cfg_.field_cap, cfg_.field_run_weight, cfg_.field_goal_weight));
   resetSequence();
+}
+
+void MPPI::setCostField(Planning::GridPlanner &planner) { field_ = &planner; }
+
+void MPPI::clearCostField() {
+  field_ = nullptr;
+  f0_ = f_nom_ = 0xFFFFFFFFu;
 }
 
 void MPPI::setMovingObstacles(std::vector<MovingObstacle> obstacles) { movers_ = std::move(obstacles); }
@@ -145,6 +153,7 @@ void MPPI::bind(const Mapping::WorldMap &map) {
   if (bound_ == map.hipContext() && ctx_) return;
   ctx_ = hip::make<Handle>(kc_mppi_create, map.hipContext(), cfg_.samples, cfg_.horizon, cfg_.seed);
   movers_on_device_ = false;
+  field_on_device_ = false;
   bound_ = map.hipContext();
   hip::check(kc_mppi_set_costs(ctx_.get(), c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_far, c.pen_hit, c.w_path, c.qcap, c.w_goal,
                                c.wtab.data(), c.wtab.size(), c.w_shift));
@@ -189,11 +198,21 @@ void MPPI::buildWindow(const Mapping::WorldMap &map) {
 
 Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State &state) {
   setCurrentState(state);
-  if (!on_.ready || !on_.path || on_.path->getSize() == 0)
-    return {(on_.at_goal ? Result::Status::GOAL_REACHED : Result::Status::NO_COMMAND_POSSIBLE), {0.0, 0.0, 0.0}};
-  if (isGoalReached()) {
-    command_ = Velocity2D(0.0, 0.0, 0.0);
-    return {Result::Status::GOAL_REACHED, command_};
+  const bool field = field_ != nullptr;
+  if (field) {  // rule 20: no path; the goal is the planner's
+    double gx = 0.0, gy = 0.0;
+    if (!field_->goalWorld(&gx, &gy)) throw std::runtime_error("MPPI: the cost field's planner has no problem set up");
+    if (std::hypot(state.x - gx, state.y - gy) <= knob_.goal_radius) {
+      command_ = Velocity2D(0.0, 0.0, 0.0);
+      return {Result::Status::GOAL_REACHED, command_};
+    }
+  } else {
+    if (!on_.ready || !on_.path || on_.path->getSize() == 0)
+      return {(on_.at_goal ? Result::Status::GOAL_REACHED : Result::Status::NO_COMMAND_POSSIBLE), {0.0, 0.0, 0.0}};
+    if (isGoalReached()) {
+      command_ = Velocity2D(0.0, 0.0, 0.0);
+      return {Result::Status::GOAL_REACHED, command_};
+    }
   }
   bind(map);
   res_ = map.resolution();
@@ -201,11 +220,23 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
   oy_ = map.originY();
   const Quantised q = quantise(drive_, limits_, dt_, res_, cfg_);
   hip::check(kc_mppi_set_model(ctx_.get(), q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq, q.s.data()));
-  aimAtTarget();
-  on_.segment = on_.target->segment_index;
-  on_.along = on_.target->position_in_segment;
-  buildWindow(map);
-  hip::check(kc_mppi_set_path(ctx_.get(), in_.px.data(), in_.py.data(), in_.px.size()));
+  in_.field = field;
+  if (field) {
+    in_.px.clear();
+    in_.py.clear();
+    hip::check(kc_mppi_set_field(ctx_.get(), field_->hipContext(), cfg_.field_cap, cfg_.field_run_weight, cfg_.field_goal_weight));
+    field_on_device_ = true;
+  } else {
+    if (field_on_device_) {
+      hip::check(kc_mppi_set_field(ctx_.get(), nullptr, 0u, 0u, 0u));
+      field_on_device_ = false;
+    }
+    aimAtTarget();
+    on_.segment = on_.target->segment_index;
+    on_.along = on_.target->position_in_segment;
+    buildWindow(map);
+    hip::check(kc_mppi_set_path(ctx_.get(), in_.px.data(), in_.py.data(), in_.px.size()));
+  }
   const kc_worldmap_pose pose = Mapping::WorldMap::quantisePose(res_, ox_, oy_, state.x, state.y, state.yaw);
   in_.tx = pose.tx;
   in_.ty = pose.ty;
@@ -226,6 +257,7 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
   out_.assign(cfg_.horizon * 3, 0);
   hip::check(kc_mppi_step(ctx_.get(), in_.tx, in_.ty, in_.h, in_.u.data(), in_.step, out_.data(), &rec_));
   ++step_;
+  if (field) hip::check(kc_mppi_last_field(ctx_.get(), &f0_, &f_nom_));
   // the warm start: U[t] = U'[t + 1], the last entry repeated
   const size_t T = cfg_.horizon;
   for (size_t t = 0; t + 1 < T; ++t)

@@ -382,6 +382,15 @@ struct WorldMapDistance {
 int worldmap_distance_state(kc_worldmap *m, WorldMapDistance *out);
 // queues rule 43's refresh on the map's stream when the dirty box is not empty; the reader then waits for that stream
 int worldmap_distance_refresh(kc_worldmap *m);
+// the grid planner's kept goal-rooted disc-mode cost field for a reader on another stream (kc_planner.hip owns it;
+// DESIGN.md 4.12 rules 19 and 23).  Host only: queues nothing.  KC_ERR_STATE while the planner holds no such field
+struct PlannerFieldView {
+  const uint32_t *field;  // [W x H], cell (I, J) at I + J * W; 0xFFFFFFFF: no walk reaches the goal
+  int W, H;
+  hipStream_t stream;
+  int device;
+};
+int planner_field_view(kc_planner *p, PlannerFieldView *out);
 // rule 16's window, and the number of map cells inside rule 17's disc: the most points a list of it can hold
 struct WorldMapWindow {
   int ic, jc, rc;

@@ -1,4 +1,4 @@
-// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 18).
+// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 24).
 //
 // Nothing in the reference to restate: its controllers commit to one velocity for the whole look-ahead.  K noisy
 // control sequences of T steps are drawn around a nominal one, rolled out from the robot's state in the localiser's
@@ -25,8 +25,17 @@
 // a team splits it by i = sub, sub + TEAM, ... as it splits the path window, adds its soft sums by shuffles and ORs its
 // hits by shuffles.  A mover's place at step t is OX + (t + 1) VX, formed where it is used.  The samples a mover ended
 // are one more ballot and one more atomic add a wavefront, into the word of the step's upload that was padding.
+//
+// The grid planner's cost field (rules 19 to 24) is a mode of (a): mppi_rollout_kernel<TEAM, MOVERS, true> runs while a
+// planner is attached (kc_mppi_set_field), the six instantiations with FIELD false (the code from before) while none is.
+// Rule 20's term stands in the place of rule 6's path search and rule 21's in the place of rule 7's: no path window and no
+// LDS for it, the last field value in a register.  A step asks the planner for its kept field (its two buffers alternate
+// between solves), orders its stream behind the planner's and reads the field where it lies: the plane's 2 bytes and the
+// field's 4 of a state's cell are loaded together.  f0 and f_nom (rule 22) are written by sample 0's first lane behind the
+// record and ride in the step's one read-back.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 
 #include "kc_internal.h"
@@ -73,6 +82,7 @@ struct MppiIn {
 struct MppiOut {
   int U[KC_MPPI_MAX_HORIZON * 3];
   kc_mppi_record rec;
+  unsigned f0, f_nom;  // rule 22, written by the field roll-out and copied only while a field is attached
 };
 
 // rule 13's list as the device holds it: what kc_mppi_set_movers uploads in one copy
@@ -99,17 +109,26 @@ struct MppiRollArgs {
   const MppiMovers *movers;
   int N;
   unsigned pen_hit_mv;
+  // rules 19 to 22, read by the FIELD instantiations alone
+  const unsigned *fld;  // the planner's kept field, W x H as the plane
+  MppiOut *out;         // f0 and f_nom go behind the record
+  unsigned fcap, w_run, w_term;
 };
 
-template <int TEAM, bool MOVERS>
+constexpr unsigned kMppiFieldInf = 0xFFFFFFFFu;  // rule 19: no walk reaches the goal
+
+// FIELD: rules 20 and 21 stand in for rules 6 and 7.  No path window, no LDS for it; fl is carried in a register
+template <int TEAM, bool MOVERS, bool FIELD = false>
 __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a) {
   __shared__ unsigned short s_pen[KC_MPPI_MAX_TABLE];
-  __shared__ long long s_px[KC_MPPI_MAX_PATH], s_py[KC_MPPI_MAX_PATH];
+  __shared__ long long s_px[FIELD ? 1 : KC_MPPI_MAX_PATH], s_py[FIELD ? 1 : KC_MPPI_MAX_PATH];
   __shared__ int s_U[KC_MPPI_MAX_HORIZON * 3];
   for (int i = threadIdx.x; i <= a.c2; i += kMppiBlock) s_pen[i] = a.pen_d2[i];
-  for (int i = threadIdx.x; i < a.M; i += kMppiBlock) {
-    s_px[i] = a.px[i];
-    s_py[i] = a.py[i];
+  if constexpr (!FIELD) {
+    for (int i = threadIdx.x; i < a.M; i += kMppiBlock) {
+      s_px[i] = a.px[i];
+      s_py[i] = a.py[i];
+    }
   }
   for (int i = threadIdx.x; i < 3 * a.T; i += kMppiBlock) s_U[i] = a.in->U[i];
   __shared__ long long s_ox[MOVERS ? KC_MPPI_MAX_MOVERS : 1], s_oy[MOVERS ? KC_MPPI_MAX_MOVERS : 1];
@@ -136,6 +155,13 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
   bool alive = live, hit = false, hit_mv = false;
   long long total = 0;
   int jm = 0;
+  // rules 21 and 22: fv of the pose's own cell, one address for every lane
+  unsigned f0 = kMppiFieldInf, fl = 0;
+  if constexpr (FIELD) {
+    const long long I0 = (a.tx + (1ll << 15)) >> 16, J0 = (a.ty + (1ll << 15)) >> 16;
+    if (I0 >= 0 && I0 < a.W && J0 >= 0 && J0 < a.H) f0 = a.fld[static_cast<size_t>(I0) + static_cast<size_t>(J0) * static_cast<size_t>(a.W)];
+    fl = f0 < a.fcap ? f0 : a.fcap;
+  }
   for (int t = 0; t < a.T; ++t) {
     if (__all(!alive)) break;  // wavefront-uniform
     // rule 3.  Lanes 0 to 2 of a team draw a channel each; with one lane a sample it draws all three
@@ -162,7 +188,18 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     }
     // rule 5
     const long long I = (tx + (1ll << 15)) >> 16, J = (ty + (1ll << 15)) >> 16;
-    const unsigned d2 = wm_dist2_at(a.dist2, a.W, a.H, I, J, alive);
+    unsigned d2, fv = kMppiFieldInf;
+    if constexpr (FIELD) {
+      // the plane's 2 bytes and the field's 4 of one cell, issued together: neither address waits for the other's
+      // data, and a state outside the map (or a frozen sample) loads cell 0 and drops it, so no branch stands around them
+      const bool in = alive && I >= 0 && I < a.W && J >= 0 && J < a.H;
+      const size_t cell = in ? static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W) : size_t{0};
+      const unsigned dv = a.dist2[cell], fw = a.fld[cell];
+      d2 = in ? dv : static_cast<unsigned>(KC_WORLDMAP_DIST_FAR);
+      fv = in ? fw : kMppiFieldInf;
+    } else {
+      d2 = wm_dist2_at(a.dist2, a.W, a.H, I, J, alive);
+    }
     if (alive && d2 <= a.r2) {
       total += static_cast<long long>(a.pen_hit) * (a.T - t);
       hit = true;
@@ -195,26 +232,34 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
       if (alive) total += soft;
     }
     if (alive) total += wm_dist2_pen(d2, a.c2, s_pen, a.pen_far);
-    // rule 6: this lane's share of the window, then the team's minimum of the packed key
-    unsigned long long best = ~0ull;
-    for (int j = sub; j < a.M; j += TEAM) {
-      const long long dx = static_cast<int>((tx - s_px[j]) >> 8), dy = static_cast<int>((ty - s_py[j]) >> 8);  // |.| <= 2^29
-      const unsigned long long q = static_cast<unsigned long long>(dx * dx + dy * dy);
-      const unsigned long long key = ((q < a.qcap ? q : a.qcap) << 8) | static_cast<unsigned>(j);
-      best = key < best ? key : best;
-    }
+    if constexpr (FIELD) {  // rule 20, in place of rule 6
+      if (alive) {
+        fl = fv < a.fcap ? fv : a.fcap;
+        total += static_cast<long long>((static_cast<unsigned long long>(fl) * a.w_run) >> 8);  // 2^24 2^12 before the shift
+      }
+    } else {
+      // rule 6: this lane's share of the window, then the team's minimum of the packed key
+      unsigned long long best = ~0ull;
+      for (int j = sub; j < a.M; j += TEAM) {
+        const long long dx = static_cast<int>((tx - s_px[j]) >> 8), dy = static_cast<int>((ty - s_py[j]) >> 8);  // |.| <= 2^29
+        const unsigned long long q = static_cast<unsigned long long>(dx * dx + dy * dy);
+        const unsigned long long key = ((q < a.qcap ? q : a.qcap) << 8) | static_cast<unsigned>(j);
+        best = key < best ? key : best;
+      }
 #pragma unroll
-    for (int off = TEAM / 2; off > 0; off >>= 1) {
-      const unsigned long long other = __shfl_xor(best, off, TEAM);
-      best = other < best ? other : best;
-    }
-    if (alive) {
-      total += static_cast<long long>(((best >> 8) * a.w_path) >> 16);  // below 2^56 before the shift
-      jm = static_cast<int>(best & 0xFF);
+      for (int off = TEAM / 2; off > 0; off >>= 1) {
+        const unsigned long long other = __shfl_xor(best, off, TEAM);
+        best = other < best ? other : best;
+      }
+      if (alive) {
+        total += static_cast<long long>(((best >> 8) * a.w_path) >> 16);  // below 2^56 before the shift
+        jm = static_cast<int>(best & 0xFF);
+      }
     }
   }
-  // rules 7 and 8
-  total += static_cast<long long>(a.w_goal) * (a.M - 1 - jm);
+  // rules 7 (21 with a field) and 8
+  if constexpr (FIELD) total += static_cast<long long>(a.w_term) * fl;
+  else total += static_cast<long long>(a.w_goal) * (a.M - 1 - jm);
   const unsigned Sk = total < static_cast<long long>(kMppiCap) ? static_cast<unsigned>(total) : kMppiCap;
   const bool writer = live && sub == 0;
   if (writer) a.S[k] = Sk;
@@ -232,6 +277,12 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
   if constexpr (MOVERS) {
     const unsigned long long hits_mv = __ballot(writer && hit_mv);
     if (lane == 0 && hits_mv != 0ull) atomicAdd(&a.in->n_hit_mv, static_cast<unsigned>(__popcll(hits_mv)));
+  }
+  if constexpr (FIELD) {  // rule 22: sample 0 is lane 0 of workgroup 0
+    if (writer && k == 0) {
+      a.out->f0 = f0;
+      a.out->f_nom = fl;
+    }
   }
 }
 
@@ -329,11 +380,17 @@ struct kc_mppi {
   bool have_model = false, have_costs = false, have_S = false;
   int c2 = 0, EW = 0, w_shift = 0;
   int team = 8;  // lanes a sample: the fastest of 1, 4 and 8 at both measured shapes
+  bool team_set = false;  // kc_mppi_set_team was called: `team` holds in both modes.  Otherwise the field mode takes 4
+                          // lanes a sample while no mover is set, the faster there by the same measurement
   unsigned r2 = 0, pen_far = 0, pen_hit = 0, w_path = 0, w_goal = 0;
   unsigned long long qcap = 0;
   DevBuf<MppiMovers> d_movers;  // rule 13's list; N_mv == 0: none, and the roll-out without the term runs
   int N_mv = 0;
   unsigned pen_hit_mv = 0;
+  kc_planner *planner = nullptr;  // rules 19 to 24: attached while not null; asked for its field at every step
+  OrderEvent fld_ready;           // the planner's writes, for the roll-out
+  unsigned fcap = 0, w_run = 0, w_term = 0;
+  bool have_fld = false;          // the last step ran with a field: h_out's f0 and f_nom are its
   Timing time;
 };
 
@@ -394,10 +451,24 @@ int mppi_check_movers(const int64_t *ox, const int64_t *oy, const int32_t *vx, c
   return KC_OK;
 }
 
+// rule 23, in its order
+int mppi_check_field(uint32_t fcap, uint32_t w_run, uint32_t w_term) {
+  if (fcap == 0) KC_FAIL(KC_ERR_INVALID, "fcap = 0: a field term needs a cap of at least 1");
+  if (fcap > (1u << 24)) KC_FAIL(KC_ERR_RANGE, "fcap = %u is above 2^24", fcap);
+  if (w_run > (1u << 12)) KC_FAIL(KC_ERR_RANGE, "w_run = %u is above 2^12", w_run);
+  if (w_term > 64u) KC_FAIL(KC_ERR_RANGE, "w_term = %u is above 64", w_term);
+  return KC_OK;
+}
+
 template <int TEAM>
 void mppi_launch_rollout(const kc_mppi *c, const MppiRollArgs &a) {
   const size_t lanes = c->K * static_cast<size_t>(TEAM);
   const dim3 grid(static_cast<unsigned>((lanes + kMppiBlock - 1) / kMppiBlock));
+  if (a.fld) {
+    if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
+    return;
+  }
   if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
   else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false>), grid, dim3(kMppiBlock), 0, c->stream, a);
 }
@@ -522,21 +593,48 @@ int kc_mppi_set_movers(kc_mppi *c, const int64_t *ox, const int64_t *oy, const i
   return KC_OK;
 }
 
+int kc_mppi_check_field(uint32_t fcap, uint32_t w_run, uint32_t w_term) { return mppi_check_field(fcap, w_run, w_term); }
+
+int kc_mppi_set_field(kc_mppi *c, kc_planner *planner, uint32_t fcap, uint32_t w_run, uint32_t w_term) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!planner) {  // detaches, whatever else is given: the steps after this are the path mode's
+    c->planner = nullptr;
+    return KC_OK;
+  }
+  KC_TRY(mppi_check_field(fcap, w_run, w_term));
+  c->planner = planner;
+  c->fcap = fcap;
+  c->w_run = w_run;
+  c->w_term = w_term;
+  return KC_OK;
+}
+
+int kc_mppi_last_field(kc_mppi *c, uint32_t *f0_out, uint32_t *f_nom_out) {
+  if (!c || !f0_out || !f_nom_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *f0_out = *f_nom_out = kMppiFieldInf;
+  if (!c->have_S || !c->have_fld) KC_FAIL(KC_ERR_STATE, "the last step had no field attached, or there was none");
+  *f0_out = c->h_out.p->f0;
+  *f_nom_out = c->h_out.p->f_nom;
+  return KC_OK;
+}
+
 int kc_mppi_set_team(kc_mppi *c, int lanes) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (lanes != 1 && lanes != 4 && lanes != 8) KC_FAIL(KC_ERR_INVALID, "a sample takes 1, 4 or 8 lanes, got %d", lanes);
   c->team = lanes;
+  c->team_set = true;
   return KC_OK;
 }
 
-// Check order: null arguments; the state (model, costs, path); the pose, the heading, the sequence; the map's plane;
-// then the device
+// Check order: null arguments; the state (model, costs, path unless a field is attached); the pose, the heading, the
+// sequence; the map's plane; the planner's field (rule 23); then the device
 int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *u_in, uint32_t step, int32_t *u_out, kc_mppi_record *rec) {
   if (!c || !u_in || !u_out || !rec) KC_FAIL(KC_ERR_INVALID, "null argument");
   std::memset(rec, 0, sizeof(*rec));
   if (!c->have_model) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_model first");
   if (!c->have_costs) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_costs first");
-  if (c->M == 0) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_path first");
+  const bool field = c->planner != nullptr;  // rule 20: no path window then
+  if (!field && c->M == 0) KC_FAIL(KC_ERR_STATE, "a step needs kc_mppi_set_path first");
   if (tx < -kQ16MaxOffset || tx > kQ16MaxOffset || ty < -kQ16MaxOffset || ty > kQ16MaxOffset)
     KC_FAIL(KC_ERR_RANGE, "the pose lies more than 2^20 cells from the map's origin");
   if (h > 65535u) KC_FAIL(KC_ERR_RANGE, "heading %u is outside 0 .. 65535", h);
@@ -553,8 +651,16 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   if (dist.reach == 0) KC_FAIL(KC_ERR_STATE, "a step needs the map's distance plane: kc_worldmap_set_distance");
   if (c->c2 > dist.reach * dist.reach)
     KC_FAIL(KC_ERR_STATE, "the costs' c2 = %d is above the plane's reach^2 = %d", c->c2, dist.reach * dist.reach);
+  PlannerFieldView fld{};
+  if (field) {  // rule 23; asked at every step: the planner's two buffers alternate between solves
+    KC_TRY(planner_field_view(c->planner, &fld));
+    if (fld.W != v.W || fld.H != v.H)
+      KC_FAIL(KC_ERR_STATE, "the planner's field is %d x %d, the map %d x %d", fld.W, fld.H, v.W, v.H);
+    if (fld.device != c->device) KC_FAIL(KC_ERR_INVALID, "the planner is on device %d, the controller on device %d", fld.device, c->device);
+  }
   KC_HIP(hipSetDevice(c->device));
   c->have_S = false;
+  c->have_fld = false;
   MppiIn *in = c->h_in.p;  // pinned; the last step's copy from it is over (every step ends drained)
   in->min_key = ~0ull;
   in->n_hit = 0;
@@ -563,6 +669,7 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   KC_HIP(hipMemcpyAsync(c->d_in.p, in, sizeof(MppiIn), hipMemcpyHostToDevice, c->stream));
   KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
   KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
+  if (field) KC_TRY(stream_wait_through(c->fld_ready, c->stream, fld.stream));  // and for the planner's
   const unsigned long long key = q16_key(c->seed, step);
   MppiRollArgs a{};
   a.heading = c->d_heading.p;
@@ -592,10 +699,16 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   a.movers = c->d_movers.p;
   a.N = c->N_mv;
   a.pen_hit_mv = c->pen_hit_mv;
+  a.fld = field ? fld.field : nullptr;
+  a.out = c->d_out.p;
+  a.fcap = c->fcap;
+  a.w_run = c->w_run;
+  a.w_term = c->w_term;
   c->time.begin_cycle();
   KC_TRY(c->time.start("rollout", c->stream));
-  if (c->team == 8) mppi_launch_rollout<8>(c, a);
-  else if (c->team == 4) mppi_launch_rollout<4>(c, a);
+  const int team = (field && !c->team_set && c->N_mv == 0) ? 4 : c->team;
+  if (team == 8) mppi_launch_rollout<8>(c, a);
+  else if (team == 4) mppi_launch_rollout<4>(c, a);
   else mppi_launch_rollout<1>(c, a);
   KC_HIP(hipGetLastError());
   KC_TRY(c->time.stop(c->stream));
@@ -616,13 +729,15 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   KC_HIP(hipGetLastError());
   KC_TRY(c->time.stop(c->stream));
   c->h_out.p->rec.den = 0;  // so that a copy that did not happen cannot pass for a record
-  KC_HIP(hipMemcpyAsync(c->h_out.p, c->d_out.p, sizeof(MppiOut), hipMemcpyDeviceToHost, c->stream));
+  // rule 22: f0 and f_nom ride behind the record in the same copy, and only while a field is attached
+  KC_HIP(hipMemcpyAsync(c->h_out.p, c->d_out.p, field ? sizeof(MppiOut) : offsetof(MppiOut, f0), hipMemcpyDeviceToHost, c->stream));
   KC_HIP(hipStreamSynchronize(c->stream));
   const kc_mppi_record &r = c->h_out.p->rec;
   if (r.step != step || r.den == 0 || r.k_best >= c->K) KC_FAIL(KC_ERR_HIP, "the step's record is not this step's");
   std::memcpy(u_out, c->h_out.p->U, T * 3 * sizeof(int32_t));
   *rec = r;
   c->have_S = true;
+  c->have_fld = field;
   return KC_OK;
 }
 

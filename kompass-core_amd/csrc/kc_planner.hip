@@ -1706,6 +1706,18 @@ int planner_finish(kc_planner *c, const int start_cell[2], const int goal_cell[2
 
 }  // namespace
 
+// DESIGN.md 4.12 rules 19 and 23: the field of the last solve-type call, where it lies, when that call was kc_planner_solve
+// or kc_planner_replan.  The pair's buffers alternate between solves, so a reader asks at every use
+int kc::planner_field_view(kc_planner *c, PlannerFieldView *out) {
+  if (!c || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  if (!c->solved) KC_FAIL(KC_ERR_STATE, "the planner holds no cost field: kc_planner_solve or kc_planner_replan first");
+  if (c->or_solve || c->car_solve || c->explored)
+    KC_FAIL(KC_ERR_STATE, "the planner's last field is %s, not a goal-rooted disc-mode one",
+            c->or_solve ? "an oriented solve's" : (c->car_solve ? "a car solve's" : "rooted at the robot by kc_planner_explore"));
+  *out = PlannerFieldView{c->d_field[c->final_buf].p, c->W, c->H, c->stream, c->device};
+  return KC_OK;
+}
+
 extern "C" {
 
 int kc_planner_create(int device, kc_planner **out) {
@@ -1868,6 +1880,20 @@ int kc_planner_get_field(kc_planner *c, uint32_t *field_out, uint8_t *valid_out,
     KC_HIP(hipMemcpyAsync(field_out, c->d_field[c->final_buf].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if (valid_out) KC_HIP(hipMemcpyAsync(valid_out, c->d_valid.p, n, hipMemcpyDeviceToHost, c->stream));
   KC_HIP(hipStreamSynchronize(c->stream));
+  return KC_OK;
+}
+
+int kc_planner_field_device(kc_planner *c, const uint32_t **field_out, int *width_out, int *height_out, void **stream_out) {
+  if (!c || !field_out || !width_out || !height_out || !stream_out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  *field_out = nullptr;
+  *width_out = *height_out = 0;
+  *stream_out = nullptr;
+  PlannerFieldView v{};
+  KC_TRY(kc::planner_field_view(c, &v));
+  *field_out = v.field;
+  *width_out = v.W;
+  *height_out = v.H;
+  *stream_out = v.stream;
   return KC_OK;
 }
 

@@ -57,6 +57,12 @@ class MPPIConfig(FollowerConfig):
     mover_margin: float = field(default=4.0, validator=_rng(0.0, 1024.0))    # cells
     mover_weight: float = field(default=200.0, validator=_rng(0.0, 1048576.0))
     mover_hit_penalty: int = field(default=4000, validator=_rng(0, 1 << 20))
+    # The grid planner's cost field (loop_step(cost_field=...), rules 19 to 21; the field counts 10 a straight cell):
+    # every state a sample reaches adds (min(field, field_cap) * field_run_weight) >> 8, the last one field_goal_weight
+    # times its capped field.  Judgement, not tuning: the values the two scenes of DESIGN.md 4.12 were tried with
+    field_run_weight: int = field(default=32, validator=_rng(0, 1 << 12))
+    field_goal_weight: int = field(default=2, validator=_rng(0, 64))
+    field_cap: int = field(default=1 << 20, validator=_rng(1, 1 << 24))
 
     def to_kompass_cpp(self) -> "kompass_cpp.control.MPPIConfig":
         c = kompass_cpp.control.MPPIConfig()
@@ -69,6 +75,7 @@ class MPPIConfig(FollowerConfig):
         c.allow_reverse, c.min_turning_radius = bool(self.allow_reverse), float(self.min_turning_radius)
         c.seed = int(self.seed) & (2 ** 64 - 1)
         c.mover_margin, c.mover_weight, c.mover_hit_penalty = float(self.mover_margin), float(self.mover_weight), int(self.mover_hit_penalty)
+        c.field_run_weight, c.field_goal_weight, c.field_cap = int(self.field_run_weight), int(self.field_goal_weight), int(self.field_cap)
         return c
 
 
@@ -113,23 +120,48 @@ class MPPI(FollowerTemplate):
             "path_segment_length", "loosing_goal_distance")})
         self._planner.set_follower_params(self._params)
         self._result = None
+        self._warned_r2 = False
+        self._cost_field = None
         logging.info("MPPI CONTROLLER IS READY")
 
     @property
     def planner(self) -> "kompass_cpp.control.MPPI":
         return self._planner
 
-    def loop_step(self, *, current_state: RobotState, local_map=None, moving_obstacles=None, **_) -> bool:
+    def loop_step(self, *, current_state: RobotState, local_map=None, moving_obstacles=None, cost_field=None, **_) -> bool:
         """One control step over `local_map`, a WorldMap (kompass_core.mapping.WorldMap or the kompass_cpp class); its
         distance plane is enabled when it is off.  Nothing else can serve: the controller reads the plane on the device.
 
         moving_obstacles: discs in the world frame at the time of `current_state`, metres and m/s: a sequence of (x, y,
         vx, vy, radius), an (n, 5) array, or objects with those attributes.  They hold for this step only: None or an
-        empty sequence clears the list.  More than 64: the 64 nearest to the robot are taken."""
+        empty sequence clears the list.  More than 64: the 64 nearest to the robot are taken.
+
+        cost_field: a `kompass_core.planning.GridPlanner` that has solved (or replanned) on `local_map`; for this step
+        the controller steers by its kept cost-to-go field, read where it lies on the device, instead of the path (rules
+        19 to 24): no path need be set, and the goal is the planner's.  None: the path mode.  ValueError when the
+        planner's grid was not read from this map, or the map's window has moved since (`WorldMap.shift` / `recentre`)
+        and the planner has not read it again through `replan(map=world_map)`.  `field_at_robot` tells afterwards
+        whether the robot stands where the field has a value; the controller itself does not refuse."""
         world_map = cpp_world_map(local_map)
         if world_map is None:
             raise TypeError("MPPI.loop_step needs local_map=<WorldMap>: it costs its samples against the world map's "
                             f"distance plane on the device, got {type(local_map).__name__}")
+        if cost_field is None:
+            if self._planner.has_cost_field:
+                self._planner.clear_cost_field()
+        else:
+            if not hasattr(cost_field, "reads") or not hasattr(cost_field, "_planner"):
+                raise TypeError(f"cost_field is a kompass_core.planning.GridPlanner, got {type(cost_field).__name__}")
+            if not cost_field.reads(world_map):
+                raise ValueError("cost_field: the planner's grid was not read from this WorldMap at its present window "
+                                 "offset; plan on it (setup_problem(grid=world_map) / replan(map=world_map)) first")
+            hit_r2 = int(round(float(self._config.hit_radius) ** 2))
+            if cost_field.footprint_r2 < hit_r2 and not self._warned_r2:
+                logging.warning("MPPI: the planner's footprint r2 = %d is below the controller's hit r2 = %d: a cell the "
+                                "field holds valid can be a hit", cost_field.footprint_r2, hit_r2)
+                self._warned_r2 = True
+            self._planner.set_cost_field(cost_field._planner)
+        self._cost_field = cost_field   # kept alive while attached
         self._planner.set_moving_obstacles(_moving_obstacles(moving_obstacles))
         self._result = self._planner.execute(
             world_map, kompass_cpp.types.State(current_state.x, current_state.y, current_state.yaw, current_state.speed))
@@ -171,6 +203,12 @@ class MPPI(FollowerTemplate):
     def record(self):
         """(s_min, k_best, s_0, den, n_hit, step) of the last step."""
         return tuple(self._planner.last_record)
+
+    @property
+    def field_at_robot(self) -> int:
+        """The cost field at the robot's cell in the last step with a cost_field, in the planner's units (10 a straight
+        cell); 0xFFFFFFFF when the robot stands in an invalid or cut-off cell or outside the map."""
+        return int(self._planner.field_at_robot)
 
     @property
     def n_hit_moving(self) -> int:

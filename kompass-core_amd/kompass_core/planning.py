@@ -110,6 +110,7 @@ class GridPlanner:
         self.solution = None
         self.frontiers: List[Frontier] = []   # of the last find_frontiers()
         self._problem = None   # the last setup_problem's (start_x, start_y, start_yaw, goal_x, goal_y, goal_yaw)
+        self._map_source = None   # (the kompass_cpp WorldMap the grid was last read from, its offset then), else None
         if clearance_reach > 0.0 and clearance_weight > 0.0:
             self.set_clearance_cost(clearance_reach, clearance_weight)
         if footprint == "oriented":
@@ -143,6 +144,8 @@ class GridPlanner:
 
     def _set_map(self, map_meta_data, grid):
         """The bounds and the grid as setup_problem takes them."""
+        if grid is not None:
+            self._map_source = (grid._map, tuple(grid.offset)) if isinstance(grid, WorldMap) else None
         if isinstance(grid, WorldMap):
             map_meta_data, grid = grid.map_meta_data, grid.device_grid
         mapper = grid
@@ -181,7 +184,9 @@ class GridPlanner:
         moved = False
         if isinstance(map, WorldMap):
             moved = self._planner.set_grid_from_world_map(map._map)
+            self._map_source = (map._map, tuple(map.offset))
         elif map is not None:
+            self._map_source = None
             mapper = map._mapper if hasattr(map, "_mapper") else map
             if mapper is None:
                 raise ValueError("the LocalMapper has no grid yet: update it from a scan first")
@@ -257,6 +262,18 @@ class GridPlanner:
     def frontier_labels(self):
         """uint32 [width, height]: the label of every frontier cell of the last find_frontiers(), 0xFFFFFFFF elsewhere."""
         return self._planner.get_frontier_labels()
+
+    def reads(self, world_map) -> bool:
+        """The grid was last read from this WorldMap (the front end's or the kompass_cpp class), at the window offset the
+        map has now: what a reader of the kept cost field in the map's cell frame has to know (DESIGN.md 4.12 rule 24)."""
+        inner = getattr(world_map, "_map", world_map)
+        return (self._map_source is not None and self._map_source[0] is inner
+                and tuple(self._map_source[1]) == tuple(inner.offset()))
+
+    @property
+    def footprint_r2(self) -> int:
+        """The disc's squared radius in cells: a cell is valid when no blocking cell lies within it."""
+        return int(self._planner.get_footprint_r2())
 
     @property
     def replanned(self) -> bool:

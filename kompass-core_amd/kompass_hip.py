@@ -463,6 +463,10 @@ SIGNATURES = {
                                        C.c_uint32]),
     "kc_mppi_set_movers": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
                                      C.c_uint32]),
+    "kc_mppi_check_field": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kc_mppi_set_field": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "kc_mppi_last_field": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "kc_planner_field_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "kc_mppi_step": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MppiRecord)]),
     "kc_mppi_costs": (C.c_int, [_vp, C.c_void_p, _sz]),
     "kc_mppi_set_team": (C.c_int, [_vp, C.c_int]),
@@ -1421,6 +1425,14 @@ class PlannerContext(_Owner, _StreamOrdered):
         _check(lib().kc_planner_get_field(self.h, f.ctypes.data, v.ctypes.data, f.size))
         return f, v.astype(bool)
 
+    def field_device(self):
+        """(device pointer, width, height, stream) of the kept cost field where it lies (kc_planner_field_device): uint32,
+        cell (i, j) at i + j * width.  Holds until the next solve-type call.  Raises KompassHipError (KC_ERR_STATE) unless
+        the last solve-type call was solve or replan."""
+        f, w, h, st = C.c_void_p(None), C.c_int(0), C.c_int(0), C.c_void_p(None)
+        _check(lib().kc_planner_field_device(self.h, C.byref(f), C.byref(w), C.byref(h), C.byref(st)))
+        return int(f.value or 0), w.value, h.value, int(st.value or 0)
+
     def path(self):
         """(n, 2) int32 cells (i, j) from the start to the goal; n = 0 when the last solve found none."""
         return _fill(lib().kc_planner_get_path, self.h, [(np.int32, (2,))])[0]
@@ -2241,6 +2253,12 @@ def mppi_check_movers(ox, oy, vx, vy, hq, sq, g, pen_hit_mv, n=None):
     _check(lib().kc_mppi_check_movers(*[None if a is None else a.ctypes.data for a in arr], n, _in(pen_hit_mv, 0, 2 ** 32 - 1, "pen_hit_mv")))
 
 
+def mppi_check_field(fcap, w_run, w_term):
+    """kc_mppi_check_field's refusals (host only; DESIGN.md 4.12 rule 23); raises ValueError / IndexError."""
+    u32 = 2 ** 32 - 1
+    _check(lib().kc_mppi_check_field(_in(fcap, 0, u32, "fcap"), _in(w_run, 0, u32, "w_run"), _in(w_term, 0, u32, "w_term")))
+
+
 class MppiContext(_Owner):
     """Owner of one kc_mppi context: an MPPI controller over a WorldMapContext's distance plane, which it
     keeps alive.  Works in the ABI's integers and keeps no sequence between steps; kompass_core.control.MPPI is the front
@@ -2249,6 +2267,7 @@ class MppiContext(_Owner):
 
     def __init__(self, world_map: "WorldMapContext", n_samples, horizon, seed=0):
         self.map = world_map
+        self.field_planner = None
         self.n, self.horizon = int(n_samples), int(horizon)
         self._open(lib().kc_mppi_create, world_map.h, self.n, self.horizon, int(seed) & (2 ** 64 - 1))
 
@@ -2283,6 +2302,25 @@ class MppiContext(_Owner):
     @staticmethod
     def check_movers(ox, oy, vx, vy, hq, sq, g, pen_hit_mv, n=None):
         mppi_check_movers(ox, oy, vx, vy, hq, sq, g, pen_hit_mv, n)
+
+    def set_field(self, planner=None, fcap=1 << 20, w_run=0, w_term=0):
+        """Attaches a PlannerContext's kept cost field (rules 19 to 24) for every later step, and keeps the planner alive;
+        None detaches and returns to the path mode."""
+        if planner is None:
+            _check(lib().kc_mppi_set_field(self.h, None, 0, 0, 0))
+            self.field_planner = None
+            return
+        u32 = 2 ** 32 - 1
+        _check(lib().kc_mppi_set_field(self.h, planner.h, _in(fcap, 0, u32, "fcap"), _in(w_run, 0, u32, "w_run"),
+                                       _in(w_term, 0, u32, "w_term")))
+        self.field_planner = planner
+
+    def last_field(self):
+        """(f0, f_nom) of the last step (rule 22): the uncapped field value of the pose's cell, 0xFFFFFFFF in an invalid or
+        cut-off cell or outside the map, and the nominal sample's fl."""
+        f0, fn = C.c_uint32(0), C.c_uint32(0)
+        _check(lib().kc_mppi_last_field(self.h, C.byref(f0), C.byref(fn)))
+        return f0.value, fn.value
 
     def step(self, tx, ty, h, u, step):
         """-> (U' int32 [T, 3], MppiRecord).  u: the nominal sequence, T x (F, L, H)."""

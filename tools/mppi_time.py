@@ -17,6 +17,12 @@ with 0 movers is the step as it was (the roll-out without the term runs) and nee
 library lacks.  With movers the statement compared against is tests/mppi_movers_ref.py.  Without --movers: the one leg
 with none.
 
+--field adds, beside every leg, the same leg in field mode (rules 19 to 24): a grid planner solves on the world for a goal
+beyond the door (cell 1500, 602; r2 = 9), the controller is attached to its kept cost field with MPPIConfig's default
+weights (fcap 2^20, w_run 32, w_term 2) and is given no path.  The statement compared against is tests/mppi_field_ref.py,
+handed the planner's own field as read back from the device (tests/test_mppi_field_gpu.py shows that field equal to
+tests/planner_ref.py's; the Python Dijkstra over 2.4 million cells would only add minutes here).
+
 The world: a border, a wall with a door and scattered pillars; the robot in free space, the path a straight line
 through the door.  One JSON line a shape on stdout."""
 import argparse
@@ -33,6 +39,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
 
 import kompass_hip as kh  # noqa: E402
+import mppi_field_ref as mf  # noqa: E402
 import mppi_movers_ref as mm  # noqa: E402
 import mppi_ref as mp  # noqa: E402
 import worldmap_mcl_ref as mref  # noqa: E402
@@ -42,6 +49,7 @@ W, H, RES, ORIGIN, REACH = 2004, 1204, 0.05, (-50.0, -30.0), 8
 ONE = 1 << 16
 SHAPES = ((1024, 32, 96), (8192, 64, 256))
 TEAMS = (1, 4, 8)
+FIELD_GOAL, FIELD_R2, FIELD_WEIGHTS = (1500, 602), 9, (1 << 20, 32, 2)
 
 
 def world():
@@ -103,6 +111,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--movers", default="0", help="comma-separated counts of moving obstacles, a leg each, e.g. 0,8,64")
+    ap.add_argument("--field", action="store_true", help="beside every leg, the same leg steered by the grid planner's cost field")
     ap.add_argument("--no-statement", action="store_true", help="skip the Python statement's timing")
     ap.add_argument("--no-dwa", action="store_true", help="skip the class-level DWA yardstick")
     args = ap.parse_args()
@@ -117,6 +126,15 @@ def main():
         m.set_prior(cls)
         m.set_distance(REACH)
         plane = None if args.no_statement else np.ascontiguousarray(m.distance())
+        planner = fplane = None
+        if args.field:
+            planner = kh.PlannerContext()
+            planner.set_grid(cls)
+            t0 = time.perf_counter()
+            status, cost, passes = planner.solve((1000, 601), FIELD_GOAL, FIELD_R2)
+            print(json.dumps(dict(planner_solve_ms=round((time.perf_counter() - t0) * 1e3, 3), status=status, cost=cost, passes=passes)),
+                  flush=True)
+            fplane = None if args.no_statement else np.ascontiguousarray(planner.field()[0])
         for K, T, M in SHAPES:
             px = [(1000 + j) * ONE for j in range(M)]
             py = [602 * ONE] * M
@@ -124,16 +142,24 @@ def main():
             U = [(80000, 0, 20)] * T
             for n_mv in counts:
                 time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms)
+                if planner is not None:
+                    time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner, fplane)
+        if planner is not None:
+            planner.close()
 
 
-def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms):
+def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner=None, fplane=None):
     mv = mover_list(n_mv, pose)
-    line = dict(shape=dict(K=K, T=T, M=M), movers=n_mv, world=[W, H], reps=args.reps, warmup=args.warmup)
+    line = dict(mode="field" if planner is not None else "path", shape=dict(K=K, T=T, M=M), movers=n_mv, world=[W, H], reps=args.reps,
+                warmup=args.warmup)
     with kh.MppiContext(m, K, T, 1) as dev:
         dev.set_model(model.f_lo, model.f_hi, model.l_hi, model.h_hi, model.kq, model.s)
         dev.set_costs(costs.r2, costs.pen_d2, costs.pen_far, costs.pen_hit, costs.w_path, costs.qcap, costs.w_goal, costs.wtab,
                       costs.w_shift)
-        dev.set_path(px, py)
+        if planner is not None:
+            dev.set_field(planner, *FIELD_WEIGHTS)                 # and no path: rule 20
+        else:
+            dev.set_path(px, py)
         if n_mv:
             dev.set_movers(*mv[:7], mv.pen_hit)
         dev.set_timing(True)
@@ -147,9 +173,10 @@ def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_m
                 t0 = time.perf_counter()
                 out, rec = dev.step(*pose, U, n)
                 dt = (time.perf_counter() - t0) * 1e3
+                words = dev.last_field() if planner is not None else None
                 if team == TEAMS[0]:
-                    first = (out.tolist(), rec.as_tuple())
-                elif (out.tolist(), rec.as_tuple()) != first:
+                    first = (out.tolist(), rec.as_tuple(), words)
+                elif (out.tolist(), rec.as_tuple(), words) != first:
                     raise SystemExit(f"{team} lanes a sample differ from {TEAMS[0]} at step {n}")
                 if n >= args.warmup:
                     r, u = dev.times()
@@ -163,9 +190,12 @@ def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_m
             ts = []
             for n in range(3):
                 t0 = time.perf_counter()
-                want = mm.step(plane, K, 1, model, costs, px, py, *pose, U, args.reps + args.warmup - 1, mv)
+                if planner is not None:
+                    want = mf.step(plane, K, 1, model, costs, *pose, U, args.reps + args.warmup - 1, mf.Field(fplane, *FIELD_WEIGHTS), mv)
+                else:
+                    want = mm.step(plane, K, 1, model, costs, px, py, *pose, U, args.reps + args.warmup - 1, mv) + (None,)
                 ts.append((time.perf_counter() - t0) * 1e3)
-            if (want[0], tuple(want[1])) != (first[0] and [tuple(r) for r in first[0]], first[1] + (line["n_hit_moving"],)):
+            if (want[0], tuple(want[1]), want[3]) != (first[0] and [tuple(r) for r in first[0]], first[1] + (line["n_hit_moving"],), first[2]):
                 raise SystemExit("the device differs from the statement")
             line["python_statement_ms"] = median(ts)
     if dwa_ms is not None:
