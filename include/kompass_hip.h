@@ -1795,7 +1795,7 @@ int kc_mcl_resample_inject(kc_mcl *ctx, size_t n_inject);
 int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
 
 /* ------------------------------------------------------------------------ */
-/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 18) */
+/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 29) */
 /* ------------------------------------------------------------------------ */
 /* Nothing in the reference to cite: its controllers commit to one velocity for the whole
  * look-ahead.  K noisy control sequences of T steps around a nominal one, rolled out in the
@@ -1896,7 +1896,28 @@ int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
  * kc_planner_replan, plain or with the clearance cost: none yet, or the oriented, car or explore
  * call), then when the field's shape is not the map's.
  * Rule 24, frame: the ABI works in cells; the caller sees to it that the field was solved on
- * this map at its present window offset. */
+ * this map at its present window offset.
+ * Acceleration limits inside the roll-out (tests/mppi_rates_ref.py states rules 25 to 29; off by
+ * default, and with no rates set every result, launch, upload and read-back is rules 1 to 24's):
+ * Rule 25, rates and start velocity: R = (F_up, F_dn, L_up, L_dn, H_up, H_dn), int32, a change a
+ * control step in rule 2's units, each at least 1; the F and L rates at most 2^23, the H rates at
+ * most 65535.  V0 = (F0, L0, H0), int32: the robot's velocity in front of the step, |F0|, |L0| <=
+ * 2^22, |H0| <= 32767; it need not lie inside rule 2's box.
+ * Rule 26, applied control: lim(p, x, up, dn) = p < x ? min(p + up, x) : max(p - dn, x) (up for
+ * a rising value, dn for a falling one, signed).  A_k[-1] = V0; for each t, channel by channel, A
+ * = lim(A_k[t - 1], X_k[t], up, dn); then, when kq > 0, A_H is clamped to +-((|A_F| kq) >> 16)
+ * with the F just applied.  The value behind the cone is the p of the next step; a shrinking
+ * cone may move A_H faster than H_dn (a car's yaw rate is tied to its speed).
+ * Rule 27, roll-out: rule 4 moves the state by A_k[t] in place of X_k[t].  Rules 5 to 9, 13 to
+ * 17 and 19 to 22 are unchanged, and so is rule 10: it blends X_k, not A_k.  Sample 0 is the
+ * nominal sequence under the limits: S_0 and f_nom are what the robot would pay for U.  With V0
+ * inside the box and every rate at least the box's width (F_hi - F_lo, 2 L_hi, 2 H_hi), A = X.
+ * Rule 28, applied sequence: kc_mppi_apply_rates (host only) is rule 26 over a sequence; a front
+ * end forms its command from out[0] of U' and keeps that triple as the next step's V0.
+ * Rule 29, refusals: kc_mppi_check_rates (host only), in this order: NULL rates are never an
+ * error (the mode is off, whatever v0 is); KC_ERR_INVALID for a rate below 1, in index order;
+ * KC_ERR_RANGE for an F or L rate above 2^23, then an H rate above 65535; v0 (skipped when
+ * NULL): KC_ERR_RANGE for |F0| or |L0| beyond 2^22, then |H0| above 32767. */
 typedef struct kc_mppi kc_mppi;
 #define KC_MPPI_MAX_SAMPLES 65536
 #define KC_MPPI_MAX_HORIZON 64
@@ -1951,6 +1972,23 @@ int kc_mppi_set_field(kc_mppi *ctx, kc_planner *planner_or_null, uint32_t fcap, 
 /* rule 22's two words of the last step; KC_ERR_STATE (both 0xFFFFFFFF) when that step had no
  * field attached or there was none */
 int kc_mppi_last_field(kc_mppi *ctx, uint32_t *f0_out, uint32_t *f_nom_out);
+/* rule 29's refusals of six rates and, when given, a start velocity; host only, needs no device */
+int kc_mppi_check_rates(const int32_t *rates_or_null, const int32_t *v0_or_null);
+/* Rule 25's six rates for every later step, checked as kc_mppi_check_rates does: the roll-out is
+ * mppi_rollout_kernel<TEAM, MOVERS, FIELD, true> from then on.  NULL turns the mode off: the
+ * steps after that are those of a context that never had rates.  A refused call leaves the rates
+ * as they were. */
+int kc_mppi_set_rates(kc_mppi *ctx, const int32_t *rates_or_null);
+/* Rule 25's V0 (three words) for every later step until the next call; zero in a new context.
+ * Kept on the host: it rides behind U in the step's one upload while rates are set and plays no
+ * part while none are.  KC_ERR_INVALID for NULL, then rule 29's two refusals of a v0. */
+int kc_mppi_set_velocity(kc_mppi *ctx, const int32_t *v0);
+/* Rule 28: rule 26 over the sequence u (horizon x 3, inside rule 2's bounds) from v0, into out
+ * (horizon x 3; it may be u).  Host only.  limits: rule 12's five words, of which the cone kq
+ * plays a part.  Checks, in this order: null arguments; the horizon and the limits as
+ * kc_mppi_check has them; kc_mppi_check_rates; KC_ERR_RANGE for a control of u outside +-2^22,
+ * +-2^22, +-32767. */
+int kc_mppi_apply_rates(const int32_t *limits, const int32_t *rates, const int32_t *v0, const int32_t *u, size_t horizon, int32_t *out);
 /* One step (rules 3 to 11): two launches (mppi_rollout_kernel, mppi_update_kernel) behind the
  * plane's refresh and an event on the map's stream, and one read-back of U' and the record;
  * returns with both final.  u_in, u_out: T x 3 int32 (F, L, H a step); they may be one array.
@@ -1961,7 +1999,8 @@ int kc_mppi_last_field(kc_mppi *ctx, uint32_t *f0_out, uint32_t *f_nom_out);
  * 19 to 24) no path is asked for, rule 23's KC_ERR_STATE comes behind the plane's (then
  * KC_ERR_INVALID for a planner on another device), the roll-out is mppi_rollout_kernel<TEAM,
  * MOVERS, true> and the read-back carries f0 and f_nom behind the record: still two launches,
- * one upload and one read-back. */
+ * one upload and one read-back.  With rates set (rules 25 to 29) V0 rides behind U in the upload
+ * and rule 4 moves every sample by its applied control: the same counts again. */
 int kc_mppi_step(kc_mppi *ctx, int64_t tx, int64_t ty, uint32_t h, const int32_t *u_in, uint32_t step, int32_t *u_out,
                  kc_mppi_record *record);
 /* all S_k of the last step, for tests and plots; cap: the entries s_out holds (KC_ERR_RANGE

@@ -798,7 +798,8 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def_readwrite("mover_hit_penalty", &MPPI::Config::mover_hit_penalty)
         .def_readwrite("field_run_weight", &MPPI::Config::field_run_weight)
         .def_readwrite("field_goal_weight", &MPPI::Config::field_goal_weight)
-        .def_readwrite("field_cap", &MPPI::Config::field_cap);
+        .def_readwrite("field_cap", &MPPI::Config::field_cap)
+        .def_readwrite("acceleration_limits", &MPPI::Config::acceleration_limits);
     using Mover = Control::MovingObstacle;
     py::class_<Mover>(c, "MovingObstacle", "A disc that moves in a straight line: world metres and m/s at the time of the state")
         .def(py::init([](double x, double y, double vx, double vy, double radius) { return Mover{x, y, vx, vy, radius}; }),
@@ -834,6 +835,10 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def("predicted_path", &MPPI::predictedPath, "the new sequence rolled out on the host: (x, y, yaw) after each step")
         .def("sample_costs", &MPPI::sampleCosts)
         .def_property_readonly("last_sequence", &MPPI::lastSequence)
+        .def_property_readonly("last_applied", &MPPI::lastApplied,
+                               "with acceleration_limits, rule 28's applied sequence of the new one, T x 3 ints; empty otherwise")
+        .def_property_readonly("last_velocity", &MPPI::lastVelocity,
+                               "the applied (F, L, H) the last command was formed from: the next step's V0 (rule 28)")
         .def_property_readonly("last_record", [](const MPPI &m) {
                const kc_mppi_record &r = m.lastRecord();
                return py::make_tuple(r.s_min, r.k_best, r.s_0, r.den, r.n_hit, r.step);
@@ -852,14 +857,17 @@ PYBIND11_MODULE(kompass_cpp, m) {
                d["u"] = i.u;
                d["movers"] = movers_tuple(i.movers);
                d["field"] = i.field;
+               d["limited"] = i.limited;
+               d["rates"] = i.rates;
+               d["v0"] = i.v0;
                return d;
              }, "the last step's inputs as the device took them")
         .def_static("quantise", [](Control::ControlType type, const Control::ControlLimitsParams &lim, double dt, float res,
                                    const MPPI::Config &cfg) {
                const MPPI::Quantised q = MPPI::quantise(type, lim, dt, res, cfg);
-               return py::make_tuple(q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq, q.s);
+               return py::make_tuple(q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq, q.s, q.rates);
              }, py::arg("control_type"), py::arg("control_limits"), py::arg("time_step"), py::arg("resolution"), py::arg("config"),
-             "(F_lo, F_hi, L_hi, H_hi, kq, s[3]): host only")
+             "(F_lo, F_hi, L_hi, H_hi, kq, s[3], rates[6]): host only")
         .def_static("costs_of", [](const MPPI::Config &cfg) {
                const MPPI::Costs t = MPPI::costsOf(cfg);
                return py::make_tuple(t.r2, t.pen_d2, t.pen_far, t.pen_hit, t.w_path, t.qcap, t.w_goal, t.wtab, t.w_shift);

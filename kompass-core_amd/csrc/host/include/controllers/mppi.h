@@ -15,6 +15,10 @@
 // reaches pays for how far it still is from the goal, not for how far it is from a polyline.  The planner must have
 // solved (or replanned) on this map at its present window offset; that is the caller's to see to (the Python front end
 // checks it).
+//
+// Acceleration limits (rules 25 to 29): with MPPIConfig.acceleration_limits every sample is rolled out by the control the
+// robot can apply, from the velocity this class applied last.  The command is then the first applied control of the new
+// sequence (kc_mppi_apply_rates), kept as integers for the next step; restrictVelocityTolimits plays no part.
 #pragma once
 
 #include <array>
@@ -59,6 +63,8 @@ struct MPPIConfig {
   uint32_t field_run_weight = 32;                    // w_run: a state adds (fc w_run) >> 8
   uint32_t field_goal_weight = 2;                    // w_term: the last state adds w_term fl
   uint32_t field_cap = 1u << 20;                     // fcap: an unreachable cell costs as one this far away
+  // Rules 25 to 29: roll every sample out under the control limits' accelerations.  Off: the step of rules 1 to 24
+  bool acceleration_limits = false;
 };
 
 // A disc that moves in a straight line: world metres and m/s at the time of the state handed to execute()
@@ -72,6 +78,8 @@ class MPPI : public Follower {
   struct Quantised {  // what a step hands to kc_mppi_set_model
     int32_t f_lo = 0, f_hi = 0, l_hi = 0, h_hi = 0, kq = 0;
     std::array<int32_t, 3> s = {0, 0, 0};
+    // rule 25's rates (F_up, F_dn, L_up, L_dn, H_up, H_dn), formed while acceleration_limits is set
+    std::array<int32_t, 6> rates = {1, 1, 1, 1, 1, 1};
   };
   struct Costs {  // ... and to kc_mppi_set_costs
     uint32_t r2 = 0;
@@ -97,6 +105,9 @@ class MPPI : public Follower {
     std::vector<int32_t> u;  // T x 3
     Movers movers;
     bool field = false;      // a cost field was attached: px, py are empty
+    bool limited = false;    // rules 25 to 29 were on: rates and v0 are what the device took
+    std::array<int32_t, 6> rates = {0, 0, 0, 0, 0, 0};
+    std::array<int32_t, 3> v0 = {0, 0, 0};
   };
 
   MPPI(ControlType type, const ControlLimitsParams &limits, double time_step, const Config &config = Config());
@@ -128,15 +139,23 @@ class MPPI : public Follower {
   double timeStep() const { return dt_; }
   const Inputs &lastInputs() const { return in_; }
   const std::vector<int32_t> &lastSequence() const { return out_; }  // U' of the last step, T x 3
+  // With acceleration_limits: rule 28's applied sequence of U', T x 3 (empty otherwise), and the applied triple the last
+  // command was formed from, which is the next step's V0: zero at the first step, after resetSequence() and when the
+  // map's resolution changes
+  const std::vector<int32_t> &lastApplied() const { return applied_; }
+  const std::array<int32_t, 3> &lastVelocity() const { return v0_; }
   const kc_mppi_record &lastRecord() const { return rec_; }
-  // the first n controls of U' as velocities (vx, vy, omega each)
+  // the first n controls of U' as velocities (vx, vy, omega each); with acceleration_limits, of its applied sequence
   std::vector<std::array<double, 3>> controls(size_t n) const;
-  // U' rolled out on the host by rule 4 from the last step's pose: (x, y, yaw) in the world after each step
+  // U' (with acceleration_limits its applied sequence) rolled out on the host by rule 4 from the last step's pose: (x,
+  // y, yaw) in the world after each step
   std::vector<std::array<double, 3>> predictedPath() const;
   std::vector<uint32_t> sampleCosts() const;
   kc_mppi *hipContext() const { return ctx_.get(); }
 
   // ---- the host side's arithmetic, static: needs no device ----
+  // quantise() forms rule 25's rates beside the box: lrint(a dt^2 / res 65536) from velXParams and velYParams, lrint(a
+  // dt^2 / (2 pi) 65536) from omegaParams, maxAcceleration for up and maxDeceleration for dn, clamped into rule 25's range
   static Quantised quantise(ControlType type, const ControlLimitsParams &limits, double time_step, float resolution, const Config &c);
   static Costs costsOf(const Config &c);
   // The list in rule 13's integers against the origin (ox, oy): positions as the pose is quantised, V = llrint(v dt / res
@@ -155,6 +174,10 @@ class MPPI : public Follower {
   float res_ = 0.0f;
   double ox_ = 0.0, oy_ = 0.0;          // the origin the last step quantised against
   std::vector<int32_t> u_, out_;
+  std::vector<int32_t> applied_;            // rule 28's sequence of out_, while the mode is on
+  std::array<int32_t, 3> v0_ = {0, 0, 0};   // what the robot was last told, in rule 2's units
+  bool rates_on_device_ = false;            // ctx_ holds rates
+  const std::vector<int32_t> &shown() const { return applied_.empty() ? out_ : applied_; }
   uint32_t step_ = 0;
   Inputs in_;
   kc_mppi_record rec_ = {};

@@ -15,6 +15,12 @@ namespace Control {
 namespace {
 constexpr double kTwoPi = 2.0 * M_PI;
 
+// rule 25: a rate from an acceleration already in rule 2's units a step^2, clamped into 1 .. cap
+int32_t quantiseRate(double v, double cap, const char *what) {
+  if (!std::isfinite(v) || v < 0.0) throw std::invalid_argument(std::string(what) + " is negative or not finite");
+  return static_cast<int32_t>(std::llrint(std::max(1.0, std::min(v, cap))));
+}
+
 int32_t quantiseLimit(double v, double cap, const char *what) {
   if (!std::isfinite(v) || v < 0.0) throw std::invalid_argument(std::string(what) + " is negative or not finite");
   return static_cast<int32_t>(std::llrint(std::min(v, cap)));
@@ -99,6 +105,8 @@ MPPI::Movers MPPI::moversOf(const std::vector<MovingObstacle> &obstacles, double
 void MPPI::resetSequence() {
   u_.assign(cfg_.horizon * 3, 0);
   out_.clear();
+  applied_.clear();
+  v0_ = {0, 0, 0};
   step_ = 0;
 }
 
@@ -118,6 +126,16 @@ MPPI::Quantised MPPI::quantise(ControlType type, const ControlLimitsParams &limi
   q.s = {Mapping::MCL::noiseScale(c.sigma_forward * 65536.0),
          type == ControlType::OMNI ? Mapping::MCL::noiseScale(c.sigma_lateral * 65536.0) : 0,
          Mapping::MCL::noiseScale(c.sigma_turn / kTwoPi * 65536.0)};
+  // rule 25: a change a control step
+  const double lin = time_step * time_step / r * 65536.0, ang = time_step * time_step / kTwoPi * 65536.0;
+  const double lin_cap = 8388608.0, ang_cap = 65535.0;  // 2^23
+  if (c.acceleration_limits)
+    q.rates = {quantiseRate(limits.velXParams.maxAcceleration * lin, lin_cap, "the forward acceleration"),
+               quantiseRate(limits.velXParams.maxDeceleration * lin, lin_cap, "the forward deceleration"),
+               quantiseRate(limits.velYParams.maxAcceleration * lin, lin_cap, "the lateral acceleration"),
+               quantiseRate(limits.velYParams.maxDeceleration * lin, lin_cap, "the lateral deceleration"),
+               quantiseRate(limits.omegaParams.maxAcceleration * ang, ang_cap, "the turn acceleration"),
+               quantiseRate(limits.omegaParams.maxDeceleration * ang, ang_cap, "the turn deceleration")};
   return q;
 }
 
@@ -154,6 +172,7 @@ void MPPI::bind(const Mapping::WorldMap &map) {
   ctx_ = hip::make<Handle>(kc_mppi_create, map.hipContext(), cfg_.samples, cfg_.horizon, cfg_.seed);
   movers_on_device_ = false;
   field_on_device_ = false;
+  rates_on_device_ = false;
   bound_ = map.hipContext();
   hip::check(kc_mppi_set_costs(ctx_.get(), c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_far, c.pen_hit, c.w_path, c.qcap, c.w_goal,
                                c.wtab.data(), c.wtab.size(), c.w_shift));
@@ -215,11 +234,24 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
     }
   }
   bind(map);
+  if (res_ != map.resolution()) v0_ = {0, 0, 0};  // rule 28: the kept triple is in cells of another size
   res_ = map.resolution();
   ox_ = map.originX();
   oy_ = map.originY();
   const Quantised q = quantise(drive_, limits_, dt_, res_, cfg_);
   hip::check(kc_mppi_set_model(ctx_.get(), q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq, q.s.data()));
+  const bool limited = cfg_.acceleration_limits;
+  in_.limited = limited;
+  in_.rates = limited ? q.rates : std::array<int32_t, 6>{0, 0, 0, 0, 0, 0};
+  in_.v0 = limited ? v0_ : std::array<int32_t, 3>{0, 0, 0};
+  if (limited) {
+    hip::check(kc_mppi_set_rates(ctx_.get(), q.rates.data()));
+    hip::check(kc_mppi_set_velocity(ctx_.get(), v0_.data()));
+    rates_on_device_ = true;
+  } else if (rates_on_device_) {
+    hip::check(kc_mppi_set_rates(ctx_.get(), nullptr));
+    rates_on_device_ = false;
+  }
   in_.field = field;
   if (field) {
     in_.px.clear();
@@ -263,6 +295,17 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
   for (size_t t = 0; t + 1 < T; ++t)
     for (int c = 0; c < 3; ++c) u_[3 * t + c] = out_[3 * (t + 1) + c];
   for (int c = 0; c < 3; ++c) u_[3 * (T - 1) + c] = out_[3 * (T - 1) + c];
+  applied_.clear();
+  if (limited) {  // rule 28: the command is the first applied control of U', and the next step's V0; no doubles in between
+    const int32_t box[5] = {q.f_lo, q.f_hi, q.l_hi, q.h_hi, q.kq};
+    std::vector<int32_t> applied(T * 3, 0);
+    hip::check(kc_mppi_apply_rates(box, q.rates.data(), v0_.data(), out_.data(), T, applied.data()));
+    applied_ = std::move(applied);
+    v0_ = {applied_[0], applied_[1], applied_[2]};
+    const std::array<double, 3> a = controls(1)[0];
+    command_ = Velocity2D(a[0], a[1], a[2]);
+    return {Result::Status::COMMAND_FOUND, command_};
+  }
   const std::array<double, 3> v = controls(1)[0];
   const auto &lx = limits_.velXParams;
   const auto &ly = limits_.velYParams;
@@ -276,9 +319,10 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
 std::vector<std::array<double, 3>> MPPI::controls(size_t n) const {
   std::vector<std::array<double, 3>> out;
   const double r = static_cast<double>(res_);
-  for (size_t t = 0; t < n && 3 * t + 2 < out_.size(); ++t)
-    out.push_back({static_cast<double>(out_[3 * t]) / 65536.0 * r / dt_, static_cast<double>(out_[3 * t + 1]) / 65536.0 * r / dt_,
-                   static_cast<double>(out_[3 * t + 2]) / 65536.0 * kTwoPi / dt_});
+  const std::vector<int32_t> &u = shown();
+  for (size_t t = 0; t < n && 3 * t + 2 < u.size(); ++t)
+    out.push_back({static_cast<double>(u[3 * t]) / 65536.0 * r / dt_, static_cast<double>(u[3 * t + 1]) / 65536.0 * r / dt_,
+                   static_cast<double>(u[3 * t + 2]) / 65536.0 * kTwoPi / dt_});
   return out;
 }
 
@@ -288,13 +332,14 @@ std::vector<std::array<double, 3>> MPPI::predictedPath() const {
   uint32_t h = in_.h;
   const int64_t cap = int64_t{1} << 36;
   const double r = static_cast<double>(res_);
-  for (size_t t = 0; 3 * t + 2 < out_.size(); ++t) {
+  const std::vector<int32_t> &u = shown();
+  for (size_t t = 0; 3 * t + 2 < u.size(); ++t) {
     int32_t C = 0, S = 0;
     hip::check(kc_mcl_heading(h, &C, &S));
-    const int64_t F = out_[3 * t], L = out_[3 * t + 1];
+    const int64_t F = u[3 * t], L = u[3 * t + 1];
     tx = std::max(-cap, std::min(cap, tx + ((C * F - S * L + (int64_t{1} << 15)) >> 16)));
     ty = std::max(-cap, std::min(cap, ty + ((S * F + C * L + (int64_t{1} << 15)) >> 16)));
-    h = static_cast<uint32_t>((static_cast<int64_t>(h) + out_[3 * t + 2]) & 0xFFFF);
+    h = static_cast<uint32_t>((static_cast<int64_t>(h) + u[3 * t + 2]) & 0xFFFF);
     out.push_back({ox_ + static_cast<double>(tx) / 65536.0 * r, oy_ + static_cast<double>(ty) / 65536.0 * r,
                    static_cast<double>(h) / 65536.0 * kTwoPi});
   }

@@ -1,4 +1,4 @@
-// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 24).
+// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 29).
 //
 // Nothing in the reference to restate: its controllers commit to one velocity for the whole look-ahead.  K noisy
 // control sequences of T steps are drawn around a nominal one, rolled out from the robot's state in the localiser's
@@ -33,6 +33,13 @@
 // between solves), orders its stream behind the planner's and reads the field where it lies: the plane's 2 bytes and the
 // field's 4 of a state's cell are loaded together.  f0 and f_nom (rule 22) are written by sample 0's first lane behind the
 // record and ride in the step's one read-back.
+//
+// Acceleration limits (rules 25 to 29) are a mode of (a) too: mppi_rollout_kernel<TEAM, MOVERS, FIELD, true> runs while the
+// context holds rates (kc_mppi_set_rates), the twelve instantiations with RATE false (the code from before) while it
+// holds none.  Rule 26 (mppi_apply_rates, which kc_mppi_apply_rates calls on the host as well) stands between rule 2's
+// clamp and rule 4's move: the applied triple is three ints in registers of every lane, as the state is, and rule 4
+// moves by it.  No LDS, no shuffle and no load inside the step loop for it: the rates are kernel arguments, and V0, which
+// rides behind U in the step's one upload, is read once in front of the loop.  (b) is not touched: rule 10 blends X.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -66,6 +73,28 @@ __host__ __device__ inline void mppi_clamp_u(const MppiModel &m, long long &F, l
   }
 }
 
+struct MppiRates {  // rule 25: a change a control step, each at least 1
+  int f_up, f_dn, l_up, l_dn, h_up, h_dn;
+};
+
+// rule 26's lim: up for a rising value, dn for a falling one, signed.  |p|, |x| <= 2^22 and a rate <= 2^23: no int wraps
+__host__ __device__ inline int mppi_lim(int p, int x, int up, int dn) {
+  if (p < x) return p + up < x ? p + up : x;
+  return p - dn > x ? p - dn : x;
+}
+
+// rule 26: (AF, AL, AH) holds A[t - 1] on entry and A[t] on return; (F, L, H) is X[t], inside rule 2's bounds.  The
+// value behind the cone is the next step's p
+__host__ __device__ inline void mppi_apply_rates(const MppiRates &r, int kq, int F, int L, int H, int &AF, int &AL, int &AH) {
+  AF = mppi_lim(AF, F, r.f_up, r.f_dn);
+  AL = mppi_lim(AL, L, r.l_up, r.l_dn);
+  AH = mppi_lim(AH, H, r.h_up, r.h_dn);
+  if (kq > 0) {
+    const int lim = static_cast<int>(((AF < 0 ? -static_cast<long long>(AF) : static_cast<long long>(AF)) * kq) >> 16);
+    AH = AH < -lim ? -lim : (AH > lim ? lim : AH);
+  }
+}
+
 // rule 3's eps of sample k, step t, channel c
 __device__ __forceinline__ long long mppi_eps(const MppiModel &m, unsigned long long key, int k, int t, int c) {
   if (k == 0) return 0;
@@ -77,6 +106,7 @@ struct MppiIn {
   unsigned long long min_key;  // S_k << 32 | k, ~0 at the start
   unsigned n_hit, n_hit_mv;    // both 0 at the start; n_hit_mv: the hits by a mover among n_hit (rule 17)
   int U[KC_MPPI_MAX_HORIZON * 3];
+  int V0[3];  // rule 25's start velocity, copied only while rates are set
 };
 // and what it reads back in one copy
 struct MppiOut {
@@ -113,12 +143,15 @@ struct MppiRollArgs {
   const unsigned *fld;  // the planner's kept field, W x H as the plane
   MppiOut *out;         // f0 and f_nom go behind the record
   unsigned fcap, w_run, w_term;
+  // rules 25 to 27, read by the RATE instantiations alone (V0 is in->V0)
+  MppiRates rates;
 };
 
 constexpr unsigned kMppiFieldInf = 0xFFFFFFFFu;  // rule 19: no walk reaches the goal
 
-// FIELD: rules 20 and 21 stand in for rules 6 and 7.  No path window, no LDS for it; fl is carried in a register
-template <int TEAM, bool MOVERS, bool FIELD = false>
+// FIELD: rules 20 and 21 stand in for rules 6 and 7.  No path window, no LDS for it; fl is carried in a register.
+// RATE: rule 26 between rule 2's clamp and rule 4's move; the applied triple is carried in three registers
+template <int TEAM, bool MOVERS, bool FIELD = false, bool RATE = false>
 __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a) {
   __shared__ unsigned short s_pen[KC_MPPI_MAX_TABLE];
   __shared__ long long s_px[FIELD ? 1 : KC_MPPI_MAX_PATH], s_py[FIELD ? 1 : KC_MPPI_MAX_PATH];
@@ -162,6 +195,13 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     if (I0 >= 0 && I0 < a.W && J0 >= 0 && J0 < a.H) f0 = a.fld[static_cast<size_t>(I0) + static_cast<size_t>(J0) * static_cast<size_t>(a.W)];
     fl = f0 < a.fcap ? f0 : a.fcap;
   }
+  // rule 26: A[-1] = V0, one address for every lane
+  int aF = 0, aL = 0, aH = 0;
+  if constexpr (RATE) {
+    aF = a.in->V0[0];
+    aL = a.in->V0[1];
+    aH = a.in->V0[2];
+  }
   for (int t = 0; t < a.T; ++t) {
     if (__all(!alive)) break;  // wavefront-uniform
     // rule 3.  Lanes 0 to 2 of a team draw a channel each; with one lane a sample it draws all three
@@ -178,6 +218,12 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     }
     long long F = s_U[3 * t] + e0, L = s_U[3 * t + 1] + e1, Hc = s_U[3 * t + 2] + e2;
     mppi_clamp_u(a.m, F, L, Hc);
+    if constexpr (RATE) {  // rules 26 and 27: the state moves by A, not by X
+      mppi_apply_rates(a.rates, a.m.kq, static_cast<int>(F), static_cast<int>(L), static_cast<int>(Hc), aF, aL, aH);
+      F = aF;
+      L = aL;
+      Hc = aH;
+    }
     // rule 4, from the heading before the step; a sample that has hit stays where it is
     const int2 cs = a.heading[h];
     const long long C = cs.x, S = cs.y;
@@ -391,6 +437,9 @@ struct kc_mppi {
   OrderEvent fld_ready;           // the planner's writes, for the roll-out
   unsigned fcap = 0, w_run = 0, w_term = 0;
   bool have_fld = false;          // the last step ran with a field: h_out's f0 and f_nom are its
+  bool have_rates = false;        // rules 25 to 29: the mode is on while rates are set
+  MppiRates rates{};
+  int v0[3] = {0, 0, 0};          // rule 25's V0, kept here and sent in the step's upload
   Timing time;
 };
 
@@ -460,17 +509,49 @@ int mppi_check_field(uint32_t fcap, uint32_t w_run, uint32_t w_term) {
   return KC_OK;
 }
 
-template <int TEAM>
+// rule 29's two halves, each in its order
+int mppi_check_rates6(const int32_t *r) {
+  for (int i = 0; i < 6; ++i)
+    if (r[i] < 1) KC_FAIL(KC_ERR_INVALID, "rate %d = %d is below 1", i, r[i]);
+  for (int i = 0; i < 4; ++i)
+    if (r[i] > (1 << 23)) KC_FAIL(KC_ERR_RANGE, "rate %d = %d, an F or L rate, is above 2^23", i, r[i]);
+  for (int i = 4; i < 6; ++i)
+    if (r[i] > 65535) KC_FAIL(KC_ERR_RANGE, "rate %d = %d, an H rate, is above 65535", i, r[i]);
+  return KC_OK;
+}
+
+int mppi_check_v0(const int32_t *v) {
+  for (int i = 0; i < 2; ++i)
+    if (v[i] < -(1 << 22) || v[i] > (1 << 22)) KC_FAIL(KC_ERR_RANGE, "V0[%d] = %d is beyond 2^22", i, v[i]);
+  if (v[2] < -32767 || v[2] > 32767) KC_FAIL(KC_ERR_RANGE, "H0 = %d is beyond 32767", v[2]);
+  return KC_OK;
+}
+
+int mppi_check_rates(const int32_t *rates, const int32_t *v0) {
+  if (!rates) return KC_OK;  // the mode is off, whatever v0 is
+  KC_TRY(mppi_check_rates6(rates));
+  if (v0) KC_TRY(mppi_check_v0(v0));
+  return KC_OK;
+}
+
+template <int TEAM, bool RATE>
 void mppi_launch_rollout(const kc_mppi *c, const MppiRollArgs &a) {
   const size_t lanes = c->K * static_cast<size_t>(TEAM);
   const dim3 grid(static_cast<unsigned>((lanes + kMppiBlock - 1) / kMppiBlock));
   if (a.fld) {
-    if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
-    else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
+    if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, true, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, true, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
     return;
   }
-  if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true>), grid, dim3(kMppiBlock), 0, c->stream, a);
-  else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false>), grid, dim3(kMppiBlock), 0, c->stream, a);
+  if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, false, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
+  else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, false, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
+}
+
+template <bool RATE>
+void mppi_launch_team(const kc_mppi *c, const MppiRollArgs &a, int team) {
+  if (team == 8) mppi_launch_rollout<8, RATE>(c, a);
+  else if (team == 4) mppi_launch_rollout<4, RATE>(c, a);
+  else mppi_launch_rollout<1, RATE>(c, a);
 }
 
 }  // namespace
@@ -618,6 +699,49 @@ int kc_mppi_last_field(kc_mppi *c, uint32_t *f0_out, uint32_t *f_nom_out) {
   return KC_OK;
 }
 
+int kc_mppi_check_rates(const int32_t *rates_or_null, const int32_t *v0_or_null) { return mppi_check_rates(rates_or_null, v0_or_null); }
+
+int kc_mppi_set_rates(kc_mppi *c, const int32_t *rates_or_null) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  if (!rates_or_null) {  // the mode is off: the steps after this are those of a context that never had rates
+    c->have_rates = false;
+    return KC_OK;
+  }
+  KC_TRY(mppi_check_rates6(rates_or_null));
+  const int32_t *r = rates_or_null;
+  c->rates = MppiRates{r[0], r[1], r[2], r[3], r[4], r[5]};
+  c->have_rates = true;
+  return KC_OK;
+}
+
+int kc_mppi_set_velocity(kc_mppi *c, const int32_t *v0) {
+  if (!c || !v0) KC_FAIL(KC_ERR_INVALID, "null argument");
+  KC_TRY(mppi_check_v0(v0));
+  for (int i = 0; i < 3; ++i) c->v0[i] = v0[i];
+  return KC_OK;
+}
+
+int kc_mppi_apply_rates(const int32_t *limits, const int32_t *rates, const int32_t *v0, const int32_t *u, size_t horizon, int32_t *out) {
+  if (!limits || !rates || !v0 || !u || !out) KC_FAIL(KC_ERR_INVALID, "null argument");
+  const int32_t quiet[3] = {0, 0, 0};
+  KC_TRY(mppi_check(1, horizon, 1, limits, quiet, 0, nullptr, 0, 0, 0, 0, 0, 0, nullptr, 0, 0));
+  KC_TRY(mppi_check_rates(rates, v0));
+  for (size_t t = 0; t < horizon; ++t) {
+    const long long F = u[3 * t], L = u[3 * t + 1], H = u[3 * t + 2];
+    if (F < -(1ll << 22) || F > (1ll << 22) || L < -(1ll << 22) || L > (1ll << 22) || H < -32767 || H > 32767)
+      KC_FAIL(KC_ERR_RANGE, "control %zu of the sequence is outside the bounds of the limits", t);
+  }
+  const MppiRates r{rates[0], rates[1], rates[2], rates[3], rates[4], rates[5]};
+  int aF = v0[0], aL = v0[1], aH = v0[2];
+  for (size_t t = 0; t < horizon; ++t) {
+    mppi_apply_rates(r, limits[4], u[3 * t], u[3 * t + 1], u[3 * t + 2], aF, aL, aH);
+    out[3 * t] = aF;
+    out[3 * t + 1] = aL;
+    out[3 * t + 2] = aH;
+  }
+  return KC_OK;
+}
+
 int kc_mppi_set_team(kc_mppi *c, int lanes) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (lanes != 1 && lanes != 4 && lanes != 8) KC_FAIL(KC_ERR_INVALID, "a sample takes 1, 4 or 8 lanes, got %d", lanes);
@@ -666,7 +790,10 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   in->n_hit = 0;
   in->n_hit_mv = 0;
   std::memcpy(in->U, u_in, T * 3 * sizeof(int32_t));
-  KC_HIP(hipMemcpyAsync(c->d_in.p, in, sizeof(MppiIn), hipMemcpyHostToDevice, c->stream));
+  const bool rate = c->have_rates;
+  for (int i = 0; i < 3; ++i) in->V0[i] = c->v0[i];
+  // rule 25: V0 rides behind U in the same copy, and only while rates are set
+  KC_HIP(hipMemcpyAsync(c->d_in.p, in, rate ? sizeof(MppiIn) : offsetof(MppiIn, V0), hipMemcpyHostToDevice, c->stream));
   KC_TRY(worldmap_distance_refresh(c->map));  // on the map's stream, a launch only when its dirty box is not empty
   KC_TRY(stream_wait_through(c->map_ready, c->stream, v.stream));  // for the map's writes; the host does not wait
   if (field) KC_TRY(stream_wait_through(c->fld_ready, c->stream, fld.stream));  // and for the planner's
@@ -704,12 +831,12 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   a.fcap = c->fcap;
   a.w_run = c->w_run;
   a.w_term = c->w_term;
+  a.rates = c->rates;
   c->time.begin_cycle();
   KC_TRY(c->time.start("rollout", c->stream));
   const int team = (field && !c->team_set && c->N_mv == 0) ? 4 : c->team;
-  if (team == 8) mppi_launch_rollout<8>(c, a);
-  else if (team == 4) mppi_launch_rollout<4>(c, a);
-  else mppi_launch_rollout<1>(c, a);
+  if (rate) mppi_launch_team<true>(c, a, team);
+  else mppi_launch_team<false>(c, a, team);
   KC_HIP(hipGetLastError());
   KC_TRY(c->time.stop(c->stream));
   MppiUpdateArgs u{};

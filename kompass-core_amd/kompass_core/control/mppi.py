@@ -5,7 +5,11 @@ up.
 
 It is also the one controller here whose roll-out carries a time index, so it can cost moving obstacles at each step's own
 time (rules 13 to 18): `loop_step(..., moving_obstacles=[(x, y, vx, vy, radius), ...])`, discs in the world with a
-constant velocity.  Where they come from, a tracker for instance, is the caller's."""
+constant velocity.  Where they come from, a tracker for instance, is the caller's.
+
+`MPPIConfig(acceleration_limits=True)` rolls every sample out under the control limits' accelerations, from the velocity
+the controller commanded last (rules 25 to 29): what the robot is told is then the first step of a roll-out that was
+costed.  Off by default."""
 from __future__ import annotations
 
 import logging
@@ -63,6 +67,10 @@ class MPPIConfig(FollowerConfig):
     field_run_weight: int = field(default=32, validator=_rng(0, 1 << 12))
     field_goal_weight: int = field(default=2, validator=_rng(0, 64))
     field_cap: int = field(default=1 << 20, validator=_rng(1, 1 << 24))
+    # Rules 25 to 29: the roll-out obeys max_acc / max_decel of the control limits, from the velocity commanded last, and
+    # the command is the first applied control of the new sequence.  Off: the step of rules 1 to 24, whose first control
+    # is passed through the limits after the step
+    acceleration_limits: bool = field(default=False)
 
     def to_kompass_cpp(self) -> "kompass_cpp.control.MPPIConfig":
         c = kompass_cpp.control.MPPIConfig()
@@ -76,6 +84,7 @@ class MPPIConfig(FollowerConfig):
         c.seed = int(self.seed) & (2 ** 64 - 1)
         c.mover_margin, c.mover_weight, c.mover_hit_penalty = float(self.mover_margin), float(self.mover_weight), int(self.mover_hit_penalty)
         c.field_run_weight, c.field_goal_weight, c.field_cap = int(self.field_run_weight), int(self.field_goal_weight), int(self.field_cap)
+        c.acceleration_limits = bool(self.acceleration_limits)
         return c
 
 
@@ -209,6 +218,12 @@ class MPPI(FollowerTemplate):
         """The cost field at the robot's cell in the last step with a cost_field, in the planner's units (10 a straight
         cell); 0xFFFFFFFF when the robot stands in an invalid or cut-off cell or outside the map."""
         return int(self._planner.field_at_robot)
+
+    @property
+    def last_velocity(self):
+        """(F, L, H) in the roll-out's integers that the last command was formed from, and the next step's start velocity
+        (rule 28); zero before a step with acceleration_limits, after a reset and when the map's resolution changes."""
+        return tuple(int(v) for v in self._planner.last_velocity)
 
     @property
     def n_hit_moving(self) -> int:

@@ -466,6 +466,10 @@ SIGNATURES = {
     "kc_mppi_check_field": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "kc_mppi_set_field": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "kc_mppi_last_field": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "kc_mppi_check_rates": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kc_mppi_set_rates": (C.c_int, [_vp, C.c_void_p]),
+    "kc_mppi_set_velocity": (C.c_int, [_vp, C.c_void_p]),
+    "kc_mppi_apply_rates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]),
     "kc_planner_field_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "kc_mppi_step": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MppiRecord)]),
     "kc_mppi_costs": (C.c_int, [_vp, C.c_void_p, _sz]),
@@ -2259,6 +2263,36 @@ def mppi_check_field(fcap, w_run, w_term):
     _check(lib().kc_mppi_check_field(_in(fcap, 0, u32, "fcap"), _in(w_run, 0, u32, "w_run"), _in(w_term, 0, u32, "w_term")))
 
 
+def _i32_words(v, n, what):
+    """n int32 words, or None for None; a value that does not fit its C type is a ValueError, as _in has it."""
+    if v is None:
+        return None
+    a = np.array([_in(x, -2 ** 31, 2 ** 31 - 1, what) for x in np.asarray(v, dtype=object).reshape(-1)], np.int32)
+    if a.size != n:
+        raise ValueError(f"{what}: {n} words, got {a.size}")
+    return a
+
+
+def mppi_check_rates(rates=None, v0=None):
+    """kc_mppi_check_rates' refusals (host only; DESIGN.md 4.12 rule 29); raises ValueError / IndexError.  rates: (F_up,
+    F_dn, L_up, L_dn, H_up, H_dn) or None (the mode is off); v0: (F0, L0, H0) or None."""
+    r, v = _i32_words(rates, 6, "rates"), _i32_words(v0, 3, "v0")
+    _check(lib().kc_mppi_check_rates(None if r is None else r.ctypes.data, None if v is None else v.ctypes.data))
+
+
+def mppi_apply_rates(limits, rates, v0, u):
+    """kc_mppi_apply_rates (host only; rule 28): rule 26 over the sequence u, T x (F, L, H), from v0 -> int32 [T, 3].
+    limits: rule 12's five words (the cone kq plays a part)."""
+    lim, r, v = _i32_words(limits, 5, "limits"), _i32_words(rates, 6, "rates"), _i32_words(v0, 3, "v0")
+    ui = np.array([_in(x, -2 ** 31, 2 ** 31 - 1, "u") for x in np.asarray(u, dtype=object).reshape(-1)], np.int32)
+    if ui.size % 3:
+        raise ValueError("the sequence is T x 3 int32")
+    out = np.zeros((ui.size // 3, 3), np.int32)
+    _check(lib().kc_mppi_apply_rates(*[None if a is None else a.ctypes.data for a in (lim, r, v)], ui.ctypes.data, ui.size // 3,
+                                     out.ctypes.data))
+    return out
+
+
 class MppiContext(_Owner):
     """Owner of one kc_mppi context: an MPPI controller over a WorldMapContext's distance plane, which it
     keeps alive.  Works in the ABI's integers and keeps no sequence between steps; kompass_core.control.MPPI is the front
@@ -2321,6 +2355,18 @@ class MppiContext(_Owner):
         f0, fn = C.c_uint32(0), C.c_uint32(0)
         _check(lib().kc_mppi_last_field(self.h, C.byref(f0), C.byref(fn)))
         return f0.value, fn.value
+
+    def set_rates(self, rates=None):
+        """Rule 25's six rates (F_up, F_dn, L_up, L_dn, H_up, H_dn) for every later step: every sample is rolled out by
+        its applied control (rules 26 and 27).  None turns the mode off."""
+        r = _i32_words(rates, 6, "rates")
+        _check(lib().kc_mppi_set_rates(self.h, None if r is None else r.ctypes.data))
+
+    def set_velocity(self, v0):
+        """Rule 25's V0 = (F0, L0, H0), the robot's velocity in front of the next step, until the next call; zero in a
+        new context.  It plays a part only while rates are set."""
+        v = _i32_words(v0, 3, "v0")
+        _check(lib().kc_mppi_set_velocity(self.h, None if v is None else v.ctypes.data))
 
     def step(self, tx, ty, h, u, step):
         """-> (U' int32 [T, 3], MppiRecord).  u: the nominal sequence, T x (F, L, H)."""

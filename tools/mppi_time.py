@@ -23,6 +23,11 @@ weights (fcap 2^20, w_run 32, w_term 2) and is given no path.  The statement com
 handed the planner's own field as read back from the device (tests/test_mppi_field_gpu.py shows that field equal to
 tests/planner_ref.py's; the Python Dijkstra over 2.4 million cells would only add minutes here).
 
+--rates adds, beside every leg, the same leg with acceleration limits inside the roll-out (rules 25 to 29): the rates of the
+closed-loop scene of DESIGN.md 4.12 (F 4096 a step both ways, H 50) from a start velocity of 60000, so that the limiter
+binds on the way up to the nominal sequence's 80000 and on most samples' noise after it.  The statement compared against
+is tests/mppi_rates_ref.py.  The legs without it set no rates and need no entry an older build of the library lacks.
+
 The world: a border, a wall with a door and scattered pillars; the robot in free space, the path a straight line
 through the door.  One JSON line a shape on stdout."""
 import argparse
@@ -41,6 +46,7 @@ sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
 import kompass_hip as kh  # noqa: E402
 import mppi_field_ref as mf  # noqa: E402
 import mppi_movers_ref as mm  # noqa: E402
+import mppi_rates_ref as mr  # noqa: E402
 import mppi_ref as mp  # noqa: E402
 import worldmap_mcl_ref as mref  # noqa: E402
 from worldmap_ref import EMPTY, OCCUPIED  # noqa: E402
@@ -50,6 +56,7 @@ ONE = 1 << 16
 SHAPES = ((1024, 32, 96), (8192, 64, 256))
 TEAMS = (1, 4, 8)
 FIELD_GOAL, FIELD_R2, FIELD_WEIGHTS = (1500, 602), 9, (1 << 20, 32, 2)
+RATES, RATES_V0 = mr.Rates(4096, 4096, 1, 1, 50, 50), (60000, 0, 0)
 
 
 def world():
@@ -112,6 +119,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--movers", default="0", help="comma-separated counts of moving obstacles, a leg each, e.g. 0,8,64")
     ap.add_argument("--field", action="store_true", help="beside every leg, the same leg steered by the grid planner's cost field")
+    ap.add_argument("--rates", action="store_true", help="beside every leg, the same leg with acceleration limits inside the roll-out")
     ap.add_argument("--no-statement", action="store_true", help="skip the Python statement's timing")
     ap.add_argument("--no-dwa", action="store_true", help="skip the class-level DWA yardstick")
     args = ap.parse_args()
@@ -141,17 +149,18 @@ def main():
             pose = (1000 * ONE + 300, 601 * ONE, 700)
             U = [(80000, 0, 20)] * T
             for n_mv in counts:
-                time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms)
-                if planner is not None:
-                    time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner, fplane)
+                for rates in (None, RATES) if args.rates else (None,):
+                    time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, rates=rates)
+                    if planner is not None:
+                        time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner, fplane, rates)
         if planner is not None:
             planner.close()
 
 
-def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner=None, fplane=None):
+def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner=None, fplane=None, rates=None):
     mv = mover_list(n_mv, pose)
     line = dict(mode="field" if planner is not None else "path", shape=dict(K=K, T=T, M=M), movers=n_mv, world=[W, H], reps=args.reps,
-                warmup=args.warmup)
+                warmup=args.warmup, rates=None if rates is None else list(rates))
     with kh.MppiContext(m, K, T, 1) as dev:
         dev.set_model(model.f_lo, model.f_hi, model.l_hi, model.h_hi, model.kq, model.s)
         dev.set_costs(costs.r2, costs.pen_d2, costs.pen_far, costs.pen_hit, costs.w_path, costs.qcap, costs.w_goal, costs.wtab,
@@ -162,6 +171,9 @@ def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_m
             dev.set_path(px, py)
         if n_mv:
             dev.set_movers(*mv[:7], mv.pen_hit)
+        if rates is not None:
+            dev.set_rates(rates)
+            dev.set_velocity(RATES_V0)
         dev.set_timing(True)
         wall = {t: [] for t in TEAMS}
         roll = {t: [] for t in TEAMS}
@@ -190,7 +202,11 @@ def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_m
             ts = []
             for n in range(3):
                 t0 = time.perf_counter()
-                if planner is not None:
+                if rates is not None:
+                    fld = None if planner is None else mf.Field(fplane, *FIELD_WEIGHTS)
+                    want = mr.step(plane, K, 1, model, costs, *pose, U, args.reps + args.warmup - 1, rates, RATES_V0, fld, mv, px, py)
+                    want = want[:3] + (want[3] if planner is not None else None,)
+                elif planner is not None:
                     want = mf.step(plane, K, 1, model, costs, *pose, U, args.reps + args.warmup - 1, mf.Field(fplane, *FIELD_WEIGHTS), mv)
                 else:
                     want = mm.step(plane, K, 1, model, costs, px, py, *pose, U, args.reps + args.warmup - 1, mv) + (None,)
