@@ -1795,7 +1795,7 @@ int kc_mcl_resample_inject(kc_mcl *ctx, size_t n_inject);
 int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
 
 /* ------------------------------------------------------------------------ */
-/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 29) */
+/* MPPI control over the map's distance plane (DESIGN.md 4.12 rules 1 to 36) */
 /* ------------------------------------------------------------------------ */
 /* Nothing in the reference to cite: its controllers commit to one velocity for the whole
  * look-ahead.  K noisy control sequences of T steps around a nominal one, rolled out in the
@@ -1917,13 +1917,32 @@ int kc_mcl_inject_times(kc_mcl *ctx, float ms_out[3]);
  * Rule 29, refusals: kc_mppi_check_rates (host only), in this order: NULL rates are never an
  * error (the mode is off, whatever v0 is); KC_ERR_INVALID for a rate below 1, in index order;
  * KC_ERR_RANGE for an F or L rate above 2^23, then an H rate above 65535; v0 (skipped when
- * NULL): KC_ERR_RANGE for |F0| or |L0| beyond 2^22, then |H0| above 32767. */
+ * NULL): KC_ERR_RANGE for |F0| or |L0| beyond 2^22, then |H0| above 32767.
+ * A box footprint as a chain of discs (tests/mppi_box_ref.py states rules 30 to 36; off by
+ * default, and with no footprint set every result, launch, upload and read-back is rules 1 to
+ * 29's):
+ * Rule 30, footprint list: NB offsets o_i along the body's forward axis, 1 <= NB <= 8, int32 in
+ * 16 fraction bits of a cell, |o_i| <= 2^22; they need not be symmetric about the pose.  All
+ * discs share rule 5's r2.
+ * Rule 31, disc centres: with (C, S) the heading pair of the state's heading after the step
+ * (not the pair the step moved by), CX_i = TX + ((C o_i + 2^15) >> 16), CY_i = TY + ((S o_i +
+ * 2^15) >> 16), not clamped; their cells by rule 5's rounding, d2_i from the plane or FAR outside
+ * the map, dm = min d2_i.  Rule 5 runs on dm in the place of d2.
+ * Rule 32, movers: rule 14's q is the least over the discs of the capped squared distance from
+ * (CX_i, CY_i) to the mover, in the same >> 8 arithmetic.
+ * Rule 33, field mode: the field is still read at the pose's own cell.
+ * Rule 34, rates: the discs turn with the heading the applied control produced.
+ * Rule 35, refusals: kc_mppi_check_footprint (host only), in this order: n = 0 is never an
+ * error; KC_ERR_RANGE for n above 8; KC_ERR_INVALID for a NULL array; KC_ERR_RANGE for an offset
+ * beyond 2^22, in index order.
+ * Rule 36, cover: the front ends' doubles (Control::MPPI::footprintOf), not the ABI's. */
 typedef struct kc_mppi kc_mppi;
 #define KC_MPPI_MAX_SAMPLES 65536
 #define KC_MPPI_MAX_HORIZON 64
 #define KC_MPPI_MAX_PATH 256
 #define KC_MPPI_MAX_TABLE 4096
 #define KC_MPPI_MAX_MOVERS 64
+#define KC_MPPI_MAX_DISCS 8
 typedef struct kc_mppi_record { /* rules 11 and 17 */
   uint64_t den;                 /* sum of the weights */
   uint32_t s_min, k_best;       /* rule 8 */
@@ -1989,6 +2008,13 @@ int kc_mppi_set_velocity(kc_mppi *ctx, const int32_t *v0);
  * kc_mppi_check has them; kc_mppi_check_rates; KC_ERR_RANGE for a control of u outside +-2^22,
  * +-2^22, +-32767. */
 int kc_mppi_apply_rates(const int32_t *limits, const int32_t *rates, const int32_t *v0, const int32_t *u, size_t horizon, int32_t *out);
+/* rule 35's refusals of a list of n disc offsets; host only, needs no device */
+int kc_mppi_check_footprint(const int32_t *offsets_or_null, size_t n);
+/* Rule 30's list for every later step, checked as kc_mppi_check_footprint does: the roll-out is
+ * mppi_rollout_kernel<TEAM, MOVERS, FIELD, RATE, true> from then on, the offsets eight ints
+ * among its arguments (no upload).  n = 0 clears it: the steps after that are those of a context
+ * that never had a footprint.  A refused call leaves the list as it was. */
+int kc_mppi_set_footprint(kc_mppi *ctx, const int32_t *offsets_or_null, size_t n);
 /* One step (rules 3 to 11): two launches (mppi_rollout_kernel, mppi_update_kernel) behind the
  * plane's refresh and an event on the map's stream, and one read-back of U' and the record;
  * returns with both final.  u_in, u_out: T x 3 int32 (F, L, H a step); they may be one array.
@@ -2000,7 +2026,8 @@ int kc_mppi_apply_rates(const int32_t *limits, const int32_t *rates, const int32
  * KC_ERR_INVALID for a planner on another device), the roll-out is mppi_rollout_kernel<TEAM,
  * MOVERS, true> and the read-back carries f0 and f_nom behind the record: still two launches,
  * one upload and one read-back.  With rates set (rules 25 to 29) V0 rides behind U in the upload
- * and rule 4 moves every sample by its applied control: the same counts again. */
+ * and rule 4 moves every sample by its applied control: the same counts again.  With a footprint
+ * set (rules 30 to 36) the offsets ride in the roll-out's arguments: the same counts once more. */
 int kc_mppi_step(kc_mppi *ctx, int64_t tx, int64_t ty, uint32_t h, const int32_t *u_in, uint32_t step, int32_t *u_out,
                  kc_mppi_record *record);
 /* all S_k of the last step, for tests and plots; cap: the entries s_out holds (KC_ERR_RANGE
@@ -2008,7 +2035,8 @@ int kc_mppi_step(kc_mppi *ctx, int64_t tx, int64_t ty, uint32_t h, const int32_t
 int kc_mppi_costs(kc_mppi *ctx, uint32_t *s_out, size_t cap);
 /* Measurement only (no result depends on it): the lanes that share a sample in the roll-out, 1,
  * 4 or 8; the default is what DESIGN.md 4.12 measured as the faster: 8, and in the field mode 4
- * while no mover is set.  A call fixes the count for both modes.  KC_ERR_INVALID otherwise. */
+ * while neither a mover nor a footprint is set.  A call fixes the count for both modes.
+ * KC_ERR_INVALID otherwise. */
 int kc_mppi_set_team(kc_mppi *ctx, int lanes);
 /* HIP-event times in milliseconds of the last step's two launches (rollout, update), recorded
  * only while enabled.  KC_ERR_STATE when no step was timed. */

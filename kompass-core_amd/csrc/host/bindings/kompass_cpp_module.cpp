@@ -799,7 +799,8 @@ PYBIND11_MODULE(kompass_cpp, m) {
         .def_readwrite("field_run_weight", &MPPI::Config::field_run_weight)
         .def_readwrite("field_goal_weight", &MPPI::Config::field_goal_weight)
         .def_readwrite("field_cap", &MPPI::Config::field_cap)
-        .def_readwrite("acceleration_limits", &MPPI::Config::acceleration_limits);
+        .def_readwrite("acceleration_limits", &MPPI::Config::acceleration_limits)
+        .def_readwrite("footprint_margin", &MPPI::Config::footprint_margin);
     using Mover = Control::MovingObstacle;
     py::class_<Mover>(c, "MovingObstacle", "A disc that moves in a straight line: world metres and m/s at the time of the state")
         .def(py::init([](double x, double y, double vx, double vy, double radius) { return Mover{x, y, vx, vy, radius}; }),
@@ -823,6 +824,11 @@ PYBIND11_MODULE(kompass_cpp, m) {
              "keeps the planner alive while it is attached")
         .def("clear_cost_field", &MPPI::clearCostField, "back to the path mode")
         .def_property_readonly("has_cost_field", &MPPI::hasCostField)
+        .def("set_box_footprint", &MPPI::setBoxFootprint, py::arg("length"), py::arg("width"),
+             "a box of length x width metres, the pose at its centre, covered by up to eight discs (rules 30 to 36), from the "
+             "next execute() on")
+        .def("clear_footprint", &MPPI::clearFootprint, "back to the one disc of hit_radius")
+        .def_property_readonly("has_box_footprint", &MPPI::hasBoxFootprint)
         .def_property_readonly("field_at_robot", &MPPI::fieldAtRobot,
                                "f0 of the last step in field mode: the field at the robot's cell, 0xFFFFFFFF in an invalid or cut-off cell")
         .def_property_readonly("field_nominal", &MPPI::fieldNominal, "f_nom of the last step in field mode")
@@ -860,6 +866,8 @@ PYBIND11_MODULE(kompass_cpp, m) {
                d["limited"] = i.limited;
                d["rates"] = i.rates;
                d["v0"] = i.v0;
+               d["offsets"] = i.offsets;
+               d["r2"] = i.r2;
                return d;
              }, "the last step's inputs as the device took them")
         .def_static("quantise", [](Control::ControlType type, const Control::ControlLimitsParams &lim, double dt, float res,
@@ -873,11 +881,17 @@ PYBIND11_MODULE(kompass_cpp, m) {
                return py::make_tuple(t.r2, t.pen_d2, t.pen_far, t.pen_hit, t.w_path, t.qcap, t.w_goal, t.wtab, t.w_shift);
              }, py::arg("config"), "(r2, pen_d2, pen_far, pen_hit, w_path, qcap, w_goal, wtab, w_shift): host only")
         .def_static("movers_of", [movers_tuple](const std::vector<Mover> &obstacles, double dt, float res, double ox, double oy, double x,
-                                                double y, const MPPI::Config &cfg) {
-               return movers_tuple(MPPI::moversOf(obstacles, dt, res, ox, oy, x, y, cfg));
+                                                double y, const MPPI::Config &cfg, double hit_cells) {
+               return movers_tuple(MPPI::moversOf(obstacles, dt, res, ox, oy, x, y, cfg, hit_cells));
              }, py::arg("obstacles"), py::arg("time_step"), py::arg("resolution"), py::arg("origin_x"), py::arg("origin_y"),
-             py::arg("robot_x"), py::arg("robot_y"), py::arg("config"),
-             "(OX, OY, VX, VY, hq, sq, g, pen_hit_mv, dropped) against the origin given: host only")
+             py::arg("robot_x"), py::arg("robot_y"), py::arg("config"), py::arg("hit_cells") = -1.0,
+             "(OX, OY, VX, VY, hq, sq, g, pen_hit_mv, dropped) against the origin given: host only; hit_cells >= 0 in the place "
+             "of hit_radius (a box footprint's rho + margin)")
+        .def_static("footprint_of", [](double length, double width, float res, double margin) {
+               const MPPI::Footprint f = MPPI::footprintOf(length, width, res, margin);
+               return py::make_tuple(f.offsets, f.r2, f.rho);
+             }, py::arg("length"), py::arg("width"), py::arg("resolution"), py::arg("margin_cells") = 1.5,
+             "rule 36: (offsets in 16 fraction bits of a cell, r2, rho in cells) of a box of length x width metres: host only")
         .def_static("from_tracked_box", [](const std::array<float, 3> &center, const std::array<float, 3> &size,
                                            const std::array<float, 3> &vel) {
                Bbox3D b;

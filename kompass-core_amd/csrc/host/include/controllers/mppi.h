@@ -19,6 +19,11 @@
 // Acceleration limits (rules 25 to 29): with MPPIConfig.acceleration_limits every sample is rolled out by the control the
 // robot can apply, from the velocity this class applied last.  The command is then the first applied control of the new
 // sequence (kc_mppi_apply_rates), kept as integers for the next step; restrictVelocityTolimits plays no part.
+//
+// A box footprint (rules 30 to 36): setBoxFootprint(length, width) covers the box by up to eight equal discs along its
+// length axis, the pose at its centre (footprintOf, rule 36), and every state of a roll-out is a hit when any disc is, at
+// the state's own heading.  The discs' r2 stands in the place of hit_radius' while the box is set; the offsets are formed
+// again when the map's resolution changes.
 #pragma once
 
 #include <array>
@@ -65,6 +70,10 @@ struct MPPIConfig {
   uint32_t field_cap = 1u << 20;                     // fcap: an unreachable cell costs as one this far away
   // Rules 25 to 29: roll every sample out under the control limits' accelerations.  Off: the step of rules 1 to 24
   bool acceleration_limits = false;
+  // Rule 36's margin in cells around the discs of a box footprint: sqrt(2) rounded up to half a cell.  Derived, not
+  // judged: a disc centre lies within sqrt(2) / 2 of its cell's centre and an occupied cell reaches
+  // sqrt(2) / 2 beyond its own
+  double footprint_margin = 1.5;
 };
 
 // A disc that moves in a straight line: world metres and m/s at the time of the state handed to execute()
@@ -91,6 +100,11 @@ class MPPI : public Follower {
     std::vector<uint32_t> wtab;
     int w_shift = 0;
   };
+  struct Footprint {  // rule 36: what a box hands to kc_mppi_set_footprint, and the r2 that goes with it
+    std::vector<int32_t> offsets;  // 16 fraction bits of a cell, along the forward axis from the pose
+    uint32_t r2 = 0;
+    double rho = 0.0;              // cells: the radius at which the discs cover the box
+  };
   struct Movers {  // ... and to kc_mppi_set_movers
     std::vector<int64_t> ox, oy;
     std::vector<int32_t> vx, vy;
@@ -108,6 +122,8 @@ class MPPI : public Follower {
     bool limited = false;    // rules 25 to 29 were on: rates and v0 are what the device took
     std::array<int32_t, 6> rates = {0, 0, 0, 0, 0, 0};
     std::array<int32_t, 3> v0 = {0, 0, 0};
+    std::vector<int32_t> offsets;  // rule 30's list while a box is set, empty otherwise
+    uint32_t r2 = 0;               // rule 5's r2 of the step: the footprint's while a box is set, hit_radius' otherwise
   };
 
   MPPI(ControlType type, const ControlLimitsParams &limits, double time_step, const Config &config = Config());
@@ -123,6 +139,12 @@ class MPPI : public Follower {
   void setCostField(Planning::GridPlanner &planner);
   void clearCostField();
   bool hasCostField() const { return field_ != nullptr; }
+  // A box of length x width metres, the pose at its centre and the length along the heading, from the next execute() on
+  // and until clearFootprint() (rules 30 to 36).  std::invalid_argument for a size that is not positive and finite;
+  // execute() throws std::invalid_argument naming `clearance` when the discs' r2 is above the clearance's c2
+  void setBoxFootprint(double length, double width);
+  void clearFootprint();
+  bool hasBoxFootprint() const { return box_; }
   // f0 of the last step in field mode: the field's value at the robot's cell, in the planner's units (10 a straight
   // cell); 0xFFFFFFFF when the robot stands in an invalid or cut-off cell or outside the map, and before such a step.
   // The controller does not refuse then: the caller decides
@@ -162,8 +184,14 @@ class MPPI : public Follower {
   // 65536), hq = llrint((hit_radius + radius / res)^2 65536), sq likewise with + mover_margin, g = floor(mover_weight
   // 65536 / (((sq - hq) >> 16) + 1)).  (x, y): the robot, which picks the 64 nearest when there are more.  A quantity
   // beyond rule 13's bounds throws std::out_of_range naming the mover.
+  // hit_cells >= 0 stands in the place of c.hit_radius: rho + margin while a box is set
   static Movers moversOf(const std::vector<MovingObstacle> &obstacles, double time_step, float resolution, double ox, double oy,
-                         double x, double y, const Config &c);
+                         double x, double y, const Config &c, double hit_cells = -1.0);
+  // Rule 36: a = length / (2 res), b = width / (2 res) cells; n = min(8, max(1, ceil(a / b))), s = 2 a / n, o_i =
+  // llrint((-a + s / 2 + i s) 65536), rho = sqrt(b^2 + (s / 2)^2), r2 = ceil((rho + margin)^2).  std::invalid_argument
+  // for a size, resolution or margin that is not finite or not positive (the margin may be 0), std::out_of_range for
+  // an offset beyond rule 30's 2^22
+  static Footprint footprintOf(double length_m, double width_m, float resolution, double margin_cells);
 
  private:
   using Handle = hip::Handle<kc_mppi, kc_mppi_destroy>;
@@ -186,6 +214,10 @@ class MPPI : public Follower {
   Planning::GridPlanner *field_ = nullptr;  // the attached planner, not owned
   bool field_on_device_ = false;            // ctx_ holds an attachment
   uint32_t f0_ = 0xFFFFFFFFu, f_nom_ = 0xFFFFFFFFu;
+  bool box_ = false;                        // a box is set: box_len_ x box_wid_ metres
+  double box_len_ = 0.0, box_wid_ = 0.0;
+  bool footprint_on_device_ = false;        // ctx_ holds a footprint
+  uint32_t r2_on_device_ = 0;               // the r2 ctx_'s costs were set with
 
   void bind(const Mapping::WorldMap &map);
   void buildWindow(const Mapping::WorldMap &map);

@@ -50,6 +50,39 @@ void MPPI::clearCostField() {
   f0_ = f_nom_ = 0xFFFFFFFFu;
 }
 
+void MPPI::setBoxFootprint(double length, double width) {
+  if (!(length > 0.0) || !(width > 0.0) || !std::isfinite(length) || !std::isfinite(width))
+    throw std::invalid_argument("a box footprint needs a positive, finite length and width");
+  box_ = true;
+  box_len_ = length;
+  box_wid_ = width;
+}
+
+void MPPI::clearFootprint() { box_ = false; }
+
+MPPI::Footprint MPPI::footprintOf(double length_m, double width_m, float resolution, double margin_cells) {
+  const double r = static_cast<double>(resolution);
+  if (!(r > 0.0) || !std::isfinite(r)) throw std::invalid_argument("the resolution must be positive");
+  if (!(length_m > 0.0) || !(width_m > 0.0) || !std::isfinite(length_m) || !std::isfinite(width_m))
+    throw std::invalid_argument("a box footprint needs a positive, finite length and width");
+  if (!(margin_cells >= 0.0) || !std::isfinite(margin_cells)) throw std::invalid_argument("the footprint margin is negative or not finite");
+  const double a = length_m / (2.0 * r), b = width_m / (2.0 * r);
+  const int n = static_cast<int>(std::min(static_cast<double>(KC_MPPI_MAX_DISCS), std::max(1.0, std::ceil(a / b))));
+  const double s = 2.0 * a / n;
+  Footprint f;
+  for (int i = 0; i < n; ++i) {
+    const double o = (-a + s / 2.0 + i * s) * 65536.0;
+    if (!(std::fabs(o) <= 4194304.0)) throw std::out_of_range("a disc of the footprint lies more than 64 cells from the pose");
+    f.offsets.push_back(static_cast<int32_t>(std::llrint(o)));
+  }
+  f.rho = std::sqrt(b * b + s * s / 4.0);
+  const double reach = f.rho + margin_cells;
+  if (!(reach * reach <= 4294967295.0)) throw std::out_of_range("the footprint's r2 does not fit 32 bits");
+  f.r2 = static_cast<uint32_t>(std::ceil(reach * reach));
+  hip::check(kc_mppi_check_footprint(f.offsets.data(), f.offsets.size()));
+  return f;
+}
+
 void MPPI::setMovingObstacles(std::vector<MovingObstacle> obstacles) { movers_ = std::move(obstacles); }
 
 MovingObstacle MPPI::fromTrackedBox(const TrackedBbox3D &b) {
@@ -58,8 +91,9 @@ MovingObstacle MPPI::fromTrackedBox(const TrackedBbox3D &b) {
 }
 
 MPPI::Movers MPPI::moversOf(const std::vector<MovingObstacle> &obstacles, double time_step, float resolution, double ox, double oy,
-                            double x, double y, const Config &c) {
+                            double x, double y, const Config &c, double hit_cells) {
   const double r = static_cast<double>(resolution);
+  const double hit_radius = hit_cells >= 0.0 ? hit_cells : c.hit_radius;
   if (!(r > 0.0) || !std::isfinite(r)) throw std::invalid_argument("the resolution must be positive");
   if (!(time_step > 0.0) || !std::isfinite(time_step)) throw std::invalid_argument("the control time step must be positive");
   Movers m;
@@ -85,7 +119,7 @@ MPPI::Movers MPPI::moversOf(const std::vector<MovingObstacle> &obstacles, double
     if (!(std::fabs(fx) <= pos_cap + 0.5) || !(std::fabs(fy) <= pos_cap + 0.5)) refuse("it lies more than 2^20 cells from the map's origin");
     const double vx = o.vx * time_step / r * 65536.0, vy = o.vy * time_step / r * 65536.0;
     if (!(std::fabs(vx) <= vel_cap) || !(std::fabs(vy) <= vel_cap)) refuse("it moves more than 64 cells a control step");
-    const double hit = c.hit_radius + o.radius / r, soft = hit + c.mover_margin;
+    const double hit = hit_radius + o.radius / r, soft = hit + c.mover_margin;
     const double hq = hit * hit * 65536.0, sq = soft * soft * 65536.0;
     if (!(sq <= q_cap)) refuse("its soft distance is above 4096 cells");
     m.ox.push_back(std::llrint(fx));
@@ -173,6 +207,8 @@ void MPPI::bind(const Mapping::WorldMap &map) {
   movers_on_device_ = false;
   field_on_device_ = false;
   rates_on_device_ = false;
+  footprint_on_device_ = false;
+  r2_on_device_ = c.r2;
   bound_ = map.hipContext();
   hip::check(kc_mppi_set_costs(ctx_.get(), c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_far, c.pen_hit, c.w_path, c.qcap, c.w_goal,
                                c.wtab.data(), c.wtab.size(), c.w_shift));
@@ -252,6 +288,32 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
     hip::check(kc_mppi_set_rates(ctx_.get(), nullptr));
     rates_on_device_ = false;
   }
+  // rules 30 to 36: the offsets in cells of this map; the discs' r2 in the place of hit_radius'
+  Footprint fp;
+  double mover_hit = -1.0;
+  in_.offsets.clear();
+  in_.r2 = static_cast<uint32_t>(std::llrint(cfg_.hit_radius * cfg_.hit_radius));  // costsOf's r2, without its tables
+  if (box_) {
+    fp = footprintOf(box_len_, box_wid_, res_, cfg_.footprint_margin);
+    const uint32_t c2 = static_cast<uint32_t>(std::llrint(cfg_.clearance * cfg_.clearance));
+    if (fp.r2 > c2)
+      throw std::invalid_argument("MPPI: the box footprint's r2 = " + std::to_string(fp.r2) + " is above c2 = " + std::to_string(c2) +
+                                  ": raise `clearance` to at least " + std::to_string(std::sqrt(static_cast<double>(fp.r2))) + " cells");
+    in_.offsets = fp.offsets;
+    in_.r2 = fp.r2;
+    mover_hit = fp.rho + cfg_.footprint_margin;
+  }
+  if (in_.r2 != r2_on_device_) {  // the costs with the other r2: only when a box was set, cleared or the resolution changed
+    Costs c = costsOf(cfg_);
+    c.r2 = in_.r2;
+    hip::check(kc_mppi_set_costs(ctx_.get(), c.r2, c.pen_d2.data(), c.pen_d2.size(), c.pen_far, c.pen_hit, c.w_path, c.qcap, c.w_goal,
+                                 c.wtab.data(), c.wtab.size(), c.w_shift));
+    r2_on_device_ = c.r2;
+  }
+  if (box_ || footprint_on_device_) {
+    hip::check(kc_mppi_set_footprint(ctx_.get(), in_.offsets.data(), in_.offsets.size()));
+    footprint_on_device_ = box_;
+  }
   in_.field = field;
   if (field) {
     in_.px.clear();
@@ -275,7 +337,7 @@ Controller::Result MPPI::execute(const Mapping::WorldMap &map, const Path::State
   in_.h = Mapping::MCL::quantiseHeading(state.yaw);
   in_.step = step_;
   in_.u = u_;
-  in_.movers = moversOf(movers_, dt_, res_, ox_, oy_, state.x, state.y, cfg_);
+  in_.movers = moversOf(movers_, dt_, res_, ox_, oy_, state.x, state.y, cfg_, mover_hit);
   if (in_.movers.dropped != 0 && !logged_drop_) {
     LOG_WARNING("MPPI takes the ", KC_MPPI_MAX_MOVERS, " moving obstacles nearest to the robot; ", in_.movers.dropped, " more were given");
     logged_drop_ = true;

@@ -1,4 +1,4 @@
-// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 29).
+// Model-predictive path-integral control over the world map's distance plane (kc_mppi_*; DESIGN.md 4.12 rules 1 to 36).
 //
 // Nothing in the reference to restate: its controllers commit to one velocity for the whole look-ahead.  K noisy
 // control sequences of T steps are drawn around a nominal one, rolled out from the robot's state in the localiser's
@@ -40,6 +40,15 @@
 // clamp and rule 4's move: the applied triple is three ints in registers of every lane, as the state is, and rule 4
 // moves by it.  No LDS, no shuffle and no load inside the step loop for it: the rates are kernel arguments, and V0, which
 // rides behind U in the step's one upload, is read once in front of the loop.  (b) is not touched: rule 10 blends X.
+//
+// A box footprint (rules 30 to 36) is one more mode of (a): mppi_rollout_kernel<TEAM, MOVERS, FIELD, RATE, true> runs while
+// the context holds a list of disc offsets (kc_mppi_set_footprint), the twenty-four instantiations with BOX false (the code
+// from before) while it holds none.  The offsets are eight ints among the kernel arguments: no LDS, no upload.  A team
+// splits the discs by i = sub, sub + TEAM, ... as it splits the mover list: a lane picks its offsets once in front of the
+// loop, forms its centres by the heading pair of the state's new heading, loads their cells together (a disc off the map,
+// past the list or of a frozen sample loads cell 0 and drops it) and the team reduces dm by shuffle-minimum.  That heading
+// pair is the next step's rule-4 pair and is carried over: one table load a step, as before.  With movers every lane
+// forms all NB centres from the scalar offsets and takes rule 32's minimum inside its share of the list.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -145,13 +154,17 @@ struct MppiRollArgs {
   unsigned fcap, w_run, w_term;
   // rules 25 to 27, read by the RATE instantiations alone (V0 is in->V0)
   MppiRates rates;
+  // rules 30 to 32, read by the BOX instantiations alone: NB and the offsets, the entries past NB zero
+  int nb;
+  int off[KC_MPPI_MAX_DISCS];
 };
 
 constexpr unsigned kMppiFieldInf = 0xFFFFFFFFu;  // rule 19: no walk reaches the goal
 
 // FIELD: rules 20 and 21 stand in for rules 6 and 7.  No path window, no LDS for it; fl is carried in a register.
 // RATE: rule 26 between rule 2's clamp and rule 4's move; the applied triple is carried in three registers
-template <int TEAM, bool MOVERS, bool FIELD = false, bool RATE = false>
+// BOX: rule 31's minimum over the discs in the place of rule 5's one lookup, rule 32's in the place of rule 14's q
+template <int TEAM, bool MOVERS, bool FIELD = false, bool RATE = false, bool BOX = false>
 __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a) {
   __shared__ unsigned short s_pen[KC_MPPI_MAX_TABLE];
   __shared__ long long s_px[FIELD ? 1 : KC_MPPI_MAX_PATH], s_py[FIELD ? 1 : KC_MPPI_MAX_PATH];
@@ -202,6 +215,21 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     aL = a.in->V0[1];
     aH = a.in->V0[2];
   }
+  // rule 31: this lane's discs i = sub + j TEAM and their offsets, picked once (the index differs by lane, so a chain of
+  // selects over the eight scalar arguments, not an indexed load); the heading pair of h, carried from step to step
+  constexpr int kPer = KC_MPPI_MAX_DISCS / (TEAM < KC_MPPI_MAX_DISCS ? TEAM : KC_MPPI_MAX_DISCS);
+  long long my_off[kPer];
+  int2 cs_next = make_int2(0, 0);
+  if constexpr (BOX) {
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      int o = 0;
+#pragma unroll
+      for (int d = 0; d < KC_MPPI_MAX_DISCS; ++d) o = (sub + j * TEAM == d) ? a.off[d] : o;
+      my_off[j] = o;
+    }
+    cs_next = a.heading[h];
+  }
   for (int t = 0; t < a.T; ++t) {
     if (__all(!alive)) break;  // wavefront-uniform
     // rule 3.  Lanes 0 to 2 of a team draw a channel each; with one lane a sample it draws all three
@@ -225,7 +253,9 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
       Hc = aH;
     }
     // rule 4, from the heading before the step; a sample that has hit stays where it is
-    const int2 cs = a.heading[h];
+    int2 cs;
+    if constexpr (BOX) cs = cs_next;  // loaded behind the last step's turn (in front of the loop for t = 0)
+    else cs = a.heading[h];
     const long long C = cs.x, S = cs.y;
     if (alive) {
       tx = q16_move_x(tx, C, S, F, L);
@@ -235,7 +265,42 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
     // rule 5
     const long long I = (tx + (1ll << 15)) >> 16, J = (ty + (1ll << 15)) >> 16;
     unsigned d2, fv = kMppiFieldInf;
-    if constexpr (FIELD) {
+    long long DC = 0, DS = 0;  // rule 31's pair, of the heading after the step
+    if constexpr (BOX) {
+      cs_next = a.heading[h];
+      DC = cs_next.x;
+      DS = cs_next.y;
+      // this lane's share of the discs: every cell's address first, then the loads, then the minimum.  j TEAM < NB is
+      // uniform over the wavefront; the field's word of the pose's own cell (rule 33) goes out with them
+      size_t cell[kPer];
+      bool in[kPer];
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) {
+        const long long DI = (tx + q16_turn_x(DC, DS, my_off[j], 0) + (1ll << 15)) >> 16;
+        const long long DJ = (ty + q16_turn_y(DC, DS, my_off[j], 0) + (1ll << 15)) >> 16;
+        in[j] = alive && sub + j * TEAM < a.nb && DI >= 0 && DI < a.W && DJ >= 0 && DJ < a.H;
+        cell[j] = in[j] ? static_cast<size_t>(DI) + static_cast<size_t>(DJ) * static_cast<size_t>(a.W) : size_t{0};
+      }
+      unsigned dv[kPer];
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) dv[j] = j * TEAM < a.nb ? a.dist2[cell[j]] : 0u;
+      if constexpr (FIELD) {
+        const bool pin = alive && I >= 0 && I < a.W && J >= 0 && J < a.H;
+        const unsigned fw = a.fld[pin ? static_cast<size_t>(I) + static_cast<size_t>(J) * static_cast<size_t>(a.W) : size_t{0}];
+        fv = pin ? fw : kMppiFieldInf;
+      }
+      d2 = static_cast<unsigned>(KC_WORLDMAP_DIST_FAR);
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) {
+        const unsigned dj = in[j] ? dv[j] : static_cast<unsigned>(KC_WORLDMAP_DIST_FAR);
+        d2 = dj < d2 ? dj : d2;
+      }
+#pragma unroll
+      for (int off = TEAM / 2; off > 0; off >>= 1) {
+        const unsigned other = __shfl_xor(d2, off, TEAM);
+        d2 = other < d2 ? other : d2;
+      }
+    } else if constexpr (FIELD) {
       // the plane's 2 bytes and the field's 4 of one cell, issued together: neither address waits for the other's
       // data, and a state outside the map (or a frozen sample) loads cell 0 and drops it, so no branch stands around them
       const bool in = alive && I >= 0 && I < a.W && J >= 0 && J < a.H;
@@ -258,9 +323,23 @@ __global__ __launch_bounds__(kMppiBlock) void mppi_rollout_kernel(MppiRollArgs a
       int struck = 0;
       for (int i = sub; i < a.N; i += TEAM) {
         const long long mx = s_ox[i] + static_cast<long long>(t + 1) * s_vx[i], my = s_oy[i] + static_cast<long long>(t + 1) * s_vy[i];
-        const long long dx = static_cast<int>((tx - mx) >> 8), dy = static_cast<int>((ty - my) >> 8);  // |.| < 2^30
-        unsigned long long q = static_cast<unsigned long long>(dx * dx + dy * dy);
-        q = q < kMppiMoverCap ? q : kMppiMoverCap;
+        unsigned long long q;
+        if constexpr (BOX) {  // rule 32: the least over the discs, the centres from the scalar offsets; d < NB is uniform
+          q = kMppiMoverCap;
+#pragma unroll
+          for (int d = 0; d < KC_MPPI_MAX_DISCS; ++d) {
+            if (d < a.nb) {
+              const long long cx = tx + q16_turn_x(DC, DS, a.off[d], 0), cy = ty + q16_turn_y(DC, DS, a.off[d], 0);
+              const long long dx = static_cast<int>((cx - mx) >> 8), dy = static_cast<int>((cy - my) >> 8);  // |.| < 2^30
+              const unsigned long long qd = static_cast<unsigned long long>(dx * dx + dy * dy);
+              q = qd < q ? qd : q;
+            }
+          }
+        } else {
+          const long long dx = static_cast<int>((tx - mx) >> 8), dy = static_cast<int>((ty - my) >> 8);  // |.| < 2^30
+          q = static_cast<unsigned long long>(dx * dx + dy * dy);
+          q = q < kMppiMoverCap ? q : kMppiMoverCap;
+        }
         const unsigned long long sq = s_sq[i];
         struck |= q <= s_hq[i] ? 1 : 0;
         soft += q < sq ? static_cast<long long>((((sq - q) >> 16) * s_g[i]) >> 16) : 0;  // 2^24 2^32 before the shift
@@ -440,6 +519,8 @@ struct kc_mppi {
   bool have_rates = false;        // rules 25 to 29: the mode is on while rates are set
   MppiRates rates{};
   int v0[3] = {0, 0, 0};          // rule 25's V0, kept here and sent in the step's upload
+  int nb = 0;                     // rules 30 to 36: the mode is on while nb > 0
+  int off[KC_MPPI_MAX_DISCS] = {0, 0, 0, 0, 0, 0, 0, 0};  // rule 30's offsets, the entries past nb zero
   Timing time;
 };
 
@@ -534,24 +615,34 @@ int mppi_check_rates(const int32_t *rates, const int32_t *v0) {
   return KC_OK;
 }
 
-template <int TEAM, bool RATE>
+// rule 35, in its order
+int mppi_check_footprint(const int32_t *offsets, size_t n) {
+  if (n == 0) return KC_OK;  // clears the list, whatever else is given
+  if (n > KC_MPPI_MAX_DISCS) KC_FAIL(KC_ERR_RANGE, "%zu discs are above the cap of %d", n, KC_MPPI_MAX_DISCS);
+  if (!offsets) KC_FAIL(KC_ERR_INVALID, "a null array with %zu discs", n);
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i] < -(1 << 22) || offsets[i] > (1 << 22)) KC_FAIL(KC_ERR_RANGE, "offset %zu = %d is beyond 2^22", i, offsets[i]);
+  return KC_OK;
+}
+
+template <int TEAM, bool RATE, bool BOX>
 void mppi_launch_rollout(const kc_mppi *c, const MppiRollArgs &a) {
   const size_t lanes = c->K * static_cast<size_t>(TEAM);
   const dim3 grid(static_cast<unsigned>((lanes + kMppiBlock - 1) / kMppiBlock));
   if (a.fld) {
-    if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, true, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
-    else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, true, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
+    if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, true, RATE, BOX>), grid, dim3(kMppiBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, true, RATE, BOX>), grid, dim3(kMppiBlock), 0, c->stream, a);
     return;
   }
-  if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, false, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
-  else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, false, RATE>), grid, dim3(kMppiBlock), 0, c->stream, a);
+  if (a.N > 0) hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, true, false, RATE, BOX>), grid, dim3(kMppiBlock), 0, c->stream, a);
+  else hipLaunchKernelGGL((mppi_rollout_kernel<TEAM, false, false, RATE, BOX>), grid, dim3(kMppiBlock), 0, c->stream, a);
 }
 
-template <bool RATE>
+template <bool RATE, bool BOX>
 void mppi_launch_team(const kc_mppi *c, const MppiRollArgs &a, int team) {
-  if (team == 8) mppi_launch_rollout<8, RATE>(c, a);
-  else if (team == 4) mppi_launch_rollout<4, RATE>(c, a);
-  else mppi_launch_rollout<1, RATE>(c, a);
+  if (team == 8) mppi_launch_rollout<8, RATE, BOX>(c, a);
+  else if (team == 4) mppi_launch_rollout<4, RATE, BOX>(c, a);
+  else mppi_launch_rollout<1, RATE, BOX>(c, a);
 }
 
 }  // namespace
@@ -742,6 +833,16 @@ int kc_mppi_apply_rates(const int32_t *limits, const int32_t *rates, const int32
   return KC_OK;
 }
 
+int kc_mppi_check_footprint(const int32_t *offsets_or_null, size_t n) { return mppi_check_footprint(offsets_or_null, n); }
+
+int kc_mppi_set_footprint(kc_mppi *c, const int32_t *offsets_or_null, size_t n) {
+  if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
+  KC_TRY(mppi_check_footprint(offsets_or_null, n));
+  c->nb = static_cast<int>(n);  // n == 0: the steps after this are those of a context that never had a footprint
+  for (size_t i = 0; i < KC_MPPI_MAX_DISCS; ++i) c->off[i] = i < n ? offsets_or_null[i] : 0;
+  return KC_OK;
+}
+
 int kc_mppi_set_team(kc_mppi *c, int lanes) {
   if (!c) KC_FAIL(KC_ERR_INVALID, "null context");
   if (lanes != 1 && lanes != 4 && lanes != 8) KC_FAIL(KC_ERR_INVALID, "a sample takes 1, 4 or 8 lanes, got %d", lanes);
@@ -832,11 +933,20 @@ int kc_mppi_step(kc_mppi *c, int64_t tx, int64_t ty, uint32_t h, const int32_t *
   a.w_run = c->w_run;
   a.w_term = c->w_term;
   a.rates = c->rates;
+  a.nb = c->nb;
+  for (int i = 0; i < KC_MPPI_MAX_DISCS; ++i) a.off[i] = c->off[i];
   c->time.begin_cycle();
   KC_TRY(c->time.start("rollout", c->stream));
-  const int team = (field && !c->team_set && c->N_mv == 0) ? 4 : c->team;
-  if (rate) mppi_launch_team<true>(c, a, team);
-  else mppi_launch_team<false>(c, a, team);
+  // (with a footprint the field mode's loads are the discs', and 8 lanes a sample measured the faster again: DESIGN.md 4.12)
+  const int team = (field && !c->team_set && c->N_mv == 0 && c->nb == 0) ? 4 : c->team;
+  if (a.nb > 0) {
+    if (rate) mppi_launch_team<true, true>(c, a, team);
+    else mppi_launch_team<false, true>(c, a, team);
+  } else if (rate) {
+    mppi_launch_team<true, false>(c, a, team);
+  } else {
+    mppi_launch_team<false, false>(c, a, team);
+  }
   KC_HIP(hipGetLastError());
   KC_TRY(c->time.stop(c->stream));
   MppiUpdateArgs u{};

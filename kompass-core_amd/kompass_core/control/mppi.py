@@ -9,7 +9,11 @@ constant velocity.  Where they come from, a tracker for instance, is the caller'
 
 `MPPIConfig(acceleration_limits=True)` rolls every sample out under the control limits' accelerations, from the velocity
 the controller commanded last (rules 25 to 29): what the robot is told is then the first step of a roll-out that was
-costed.  Off by default."""
+costed.  Off by default.
+
+`MPPIConfig(footprint="box")` gives the roll-out the robot's shape (rules 30 to 36): a BOX robot's length x width is covered
+by up to eight equal discs along its length, and a state is a hit when any of them is, at the state's own heading.  The
+default, "disc", is the one disc of `hit_radius` at the pose."""
 from __future__ import annotations
 
 import logging
@@ -22,7 +26,7 @@ from attrs import define, field, validators
 
 import kompass_cpp
 from ..mapping.world_map import cpp_world_map
-from ..models import Robot, RobotCtrlLimits, RobotState, RobotType
+from ..models import Robot, RobotCtrlLimits, RobotGeometry, RobotState, RobotType
 from ._base_ import FollowerConfig, FollowerTemplate
 
 
@@ -71,6 +75,11 @@ class MPPIConfig(FollowerConfig):
     # the command is the first applied control of the new sequence.  Off: the step of rules 1 to 24, whose first control
     # is passed through the limits after the step
     acceleration_limits: bool = field(default=False)
+    # Rules 30 to 36: "box" takes (length, width) from a BOX robot's geometry_params and covers it with up to eight discs
+    # along its length; their r2 stands in the place of hit_radius'.  footprint_margin (cells) is rule 36's: sqrt(2)
+    # rounded up to half a cell, derived in DESIGN.md 4.12, not tuned.  "disc": the step of rules 1 to 29
+    footprint: str = field(default="disc", validator=validators.in_(("disc", "box")))
+    footprint_margin: float = field(default=1.5, validator=_rng(0.0, 63.0))
 
     def to_kompass_cpp(self) -> "kompass_cpp.control.MPPIConfig":
         c = kompass_cpp.control.MPPIConfig()
@@ -85,6 +94,7 @@ class MPPIConfig(FollowerConfig):
         c.mover_margin, c.mover_weight, c.mover_hit_penalty = float(self.mover_margin), float(self.mover_weight), int(self.mover_hit_penalty)
         c.field_run_weight, c.field_goal_weight, c.field_cap = int(self.field_run_weight), int(self.field_goal_weight), int(self.field_cap)
         c.acceleration_limits = bool(self.acceleration_limits)
+        c.footprint_margin = float(self.footprint_margin)
         return c
 
 
@@ -123,6 +133,11 @@ class MPPI(FollowerTemplate):
         self._planner = kompass_cpp.control.MPPI(control_type=RobotType.to_kompass_cpp_lib(robot.robot_type),
                                                  control_limits=ctrl_limits.to_kompass_cpp_lib(),
                                                  time_step=self._control_time_step, config=self._config.to_kompass_cpp())
+        if self._config.footprint == "box":
+            if robot.geometry_type != RobotGeometry.Type.BOX:
+                raise ValueError(f'MPPIConfig(footprint="box") needs a BOX robot, got {robot.geometry_type}')
+            length, width = (float(v) for v in np.asarray(robot.geometry_params, dtype=float).reshape(-1)[:2])
+            self._planner.set_box_footprint(length, width)
         self._params = kompass_cpp.control.FollowerParameters()
         self._params.from_dict({k: float(getattr(self._config, k)) for k in (
             "max_point_interpolation_distance", "lookahead_distance", "goal_dist_tolerance", "goal_orientation_tolerance",
@@ -224,6 +239,15 @@ class MPPI(FollowerTemplate):
         """(F, L, H) in the roll-out's integers that the last command was formed from, and the next step's start velocity
         (rule 28); zero before a step with acceleration_limits, after a reset and when the map's resolution changes."""
         return tuple(int(v) for v in self._planner.last_velocity)
+
+    @property
+    def footprint(self):
+        """(the disc offsets along the heading in cells, r2) the last step ran with: one offset 0.0 and hit_radius' r2 in
+        "disc" mode; None before a step."""
+        if self._result is None:
+            return None
+        i = self._planner.last_inputs
+        return ([o / 65536.0 for o in i["offsets"]] or [0.0]), int(i["r2"])
 
     @property
     def n_hit_moving(self) -> int:

@@ -470,6 +470,8 @@ SIGNATURES = {
     "kc_mppi_set_rates": (C.c_int, [_vp, C.c_void_p]),
     "kc_mppi_set_velocity": (C.c_int, [_vp, C.c_void_p]),
     "kc_mppi_apply_rates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]),
+    "kc_mppi_check_footprint": (C.c_int, [C.c_void_p, _sz]),
+    "kc_mppi_set_footprint": (C.c_int, [_vp, C.c_void_p, _sz]),
     "kc_planner_field_device": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "kc_mppi_step": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MppiRecord)]),
     "kc_mppi_costs": (C.c_int, [_vp, C.c_void_p, _sz]),
@@ -2293,6 +2295,23 @@ def mppi_apply_rates(limits, rates, v0, u):
     return out
 
 
+def _offset_words(offsets):
+    """Rule 30's offsets as int32 words, or None for None; a value that does not fit its C type is a ValueError."""
+    if offsets is None:
+        return None
+    return np.array([_in(x, -2 ** 31, 2 ** 31 - 1, "offset") for x in np.asarray(offsets, dtype=object).reshape(-1)], np.int32)
+
+
+def mppi_check_footprint(offsets=(), n=None):
+    """kc_mppi_check_footprint's refusals (host only; DESIGN.md 4.12 rule 35); raises ValueError / IndexError.  offsets:
+    the disc offsets in 16 fraction bits of a cell, or None (NULL); n: the count handed over, len(offsets) by default."""
+    o = _offset_words(offsets)
+    n = (0 if o is None else o.size) if n is None else int(n)
+    if o is not None and n <= 8 and o.size < n:                            # (above 8 the library answers before it reads)
+        raise ValueError("the array is shorter than the count")
+    _check(lib().kc_mppi_check_footprint(None if o is None or o.size == 0 else o.ctypes.data, n))
+
+
 class MppiContext(_Owner):
     """Owner of one kc_mppi context: an MPPI controller over a WorldMapContext's distance plane, which it
     keeps alive.  Works in the ABI's integers and keeps no sequence between steps; kompass_core.control.MPPI is the front
@@ -2367,6 +2386,12 @@ class MppiContext(_Owner):
         new context.  It plays a part only while rates are set."""
         v = _i32_words(v0, 3, "v0")
         _check(lib().kc_mppi_set_velocity(self.h, None if v is None else v.ctypes.data))
+
+    def set_footprint(self, offsets=()):
+        """Rule 30's disc offsets along the body's forward axis (16 fraction bits of a cell, at most 8) for every later
+        step: rule 5 runs on the least plane value under the discs (rules 31 and 32).  None clear the list."""
+        o = _offset_words(() if offsets is None else offsets)
+        _check(lib().kc_mppi_set_footprint(self.h, o.ctypes.data if o.size else None, o.size))
 
     def step(self, tx, ty, h, u, step):
         """-> (U' int32 [T, 3], MppiRecord).  u: the nominal sequence, T x (F, L, H)."""

@@ -28,6 +28,11 @@ closed-loop scene of DESIGN.md 4.12 (F 4096 a step both ways, H 50) from a start
 binds on the way up to the nominal sequence's 80000 and on most samples' noise after it.  The statement compared against
 is tests/mppi_rates_ref.py.  The legs without it set no rates and need no entry an older build of the library lacks.
 
+--box N adds, beside every leg, the same leg with a box footprint of N discs (rules 30 to 36): rule 36's cover of a box N
+links of 3.75 cells long and 4 cells wide (N = 8: the 1.5 x 0.2 m robot at 0.05 m), its r2 in the place of the costs' r2.
+The statement compared against is tests/mppi_box_ref.py.  The legs without it set no footprint and need no entry an older
+build of the library lacks.
+
 The world: a border, a wall with a door and scattered pillars; the robot in free space, the path a straight line
 through the door.  One JSON line a shape on stdout."""
 import argparse
@@ -44,6 +49,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT), str(ROOT / "kompass-core_amd"), str(ROOT / "tests")]
 
 import kompass_hip as kh  # noqa: E402
+import mppi_box_ref as mb  # noqa: E402
 import mppi_field_ref as mf  # noqa: E402
 import mppi_movers_ref as mm  # noqa: E402
 import mppi_rates_ref as mr  # noqa: E402
@@ -120,10 +126,14 @@ def main():
     ap.add_argument("--movers", default="0", help="comma-separated counts of moving obstacles, a leg each, e.g. 0,8,64")
     ap.add_argument("--field", action="store_true", help="beside every leg, the same leg steered by the grid planner's cost field")
     ap.add_argument("--rates", action="store_true", help="beside every leg, the same leg with acceleration limits inside the roll-out")
+    ap.add_argument("--box", type=int, default=0, help="beside every leg, the same leg with a box footprint of this many discs (1 to 8)")
     ap.add_argument("--no-statement", action="store_true", help="skip the Python statement's timing")
     ap.add_argument("--no-dwa", action="store_true", help="skip the class-level DWA yardstick")
     args = ap.parse_args()
     counts = [int(v) for v in args.movers.split(",")]
+    if not 0 <= args.box <= 8:
+        raise SystemExit("--box takes 1 to 8 discs")
+    boxes = (None, mb.cover(args.box * 1.875, 2.0)[:2]) if args.box else (None,)
     if kh.device_count() < 1:
         raise SystemExit("no HIP device visible")
     cls = world()
@@ -150,17 +160,20 @@ def main():
             U = [(80000, 0, 20)] * T
             for n_mv in counts:
                 for rates in (None, RATES) if args.rates else (None,):
-                    time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, rates=rates)
-                    if planner is not None:
-                        time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner, fplane, rates)
+                    for box in boxes:
+                        time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, rates=rates, box=box)
+                        if planner is not None:
+                            time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner, fplane, rates, box)
         if planner is not None:
             planner.close()
 
 
-def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner=None, fplane=None, rates=None):
+def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_ms, planner=None, fplane=None, rates=None, box=None):
     mv = mover_list(n_mv, pose)
+    if box is not None:
+        costs = costs._replace(r2=box[1])
     line = dict(mode="field" if planner is not None else "path", shape=dict(K=K, T=T, M=M), movers=n_mv, world=[W, H], reps=args.reps,
-                warmup=args.warmup, rates=None if rates is None else list(rates))
+                warmup=args.warmup, rates=None if rates is None else list(rates), box=None if box is None else len(box[0]))
     with kh.MppiContext(m, K, T, 1) as dev:
         dev.set_model(model.f_lo, model.f_hi, model.l_hi, model.h_hi, model.kq, model.s)
         dev.set_costs(costs.r2, costs.pen_d2, costs.pen_far, costs.pen_hit, costs.w_path, costs.qcap, costs.w_goal, costs.wtab,
@@ -174,6 +187,8 @@ def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_m
         if rates is not None:
             dev.set_rates(rates)
             dev.set_velocity(RATES_V0)
+        if box is not None:
+            dev.set_footprint(box[0])
         dev.set_timing(True)
         wall = {t: [] for t in TEAMS}
         roll = {t: [] for t in TEAMS}
@@ -200,9 +215,13 @@ def time_leg(args, m, plane, model, costs, K, T, M, px, py, pose, U, n_mv, dwa_m
         line["n_hit"], line["s_min"], line["n_hit_moving"] = first[1][4], first[1][0], int(rec.n_hit_moving) if n_mv else 0
         if plane is not None:
             ts = []
-            for n in range(3):
+            for n in range(1 if box is not None else 3):           # (a box leg's statement is compared, hardly timed)
                 t0 = time.perf_counter()
-                if rates is not None:
+                if box is not None:
+                    fld = None if planner is None else mf.Field(fplane, *FIELD_WEIGHTS)
+                    want = mb.step(plane, K, 1, model, costs, *pose, U, args.reps + args.warmup - 1, box[0], rates, RATES_V0, fld, mv, px, py)
+                    want = want[:3] + (want[3] if planner is not None else None,)
+                elif rates is not None:
                     fld = None if planner is None else mf.Field(fplane, *FIELD_WEIGHTS)
                     want = mr.step(plane, K, 1, model, costs, *pose, U, args.reps + args.warmup - 1, rates, RATES_V0, fld, mv, px, py)
                     want = want[:3] + (want[3] if planner is not None else None,)
